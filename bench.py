@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Headline benchmark: images/sec + p50 latency of DenseNet-121 fp32, batch 32 per GPU, device-resident inputs.
+"""Headline benchmark: images/sec of DenseNet-121 fp32, batch 32 per GPU, device-resident inputs (+ p50 latency with --full).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one forward pass of the hot path (the captured hipGraph of the fused DenseNet-121 plan) over one batch of
 synthetic 3x224x224 images that already sit in the engine's HBM input buffer.  Weak scaling: every rank owns an
 independent shard of `--batch` images (no data-path collective); the only RCCL traffic is the load-time weight
-broadcast from rank 0.  Rank 0 prints ONE JSON line (contract in the task statement) extended with
+broadcast from rank 0.  Rank 0 prints ONE JSON line.  A plain run only loads, warms up, times the K steps and prints it;
+--dump-outputs DIR also saves the output of the last timed step (DIR/<output name>.npy, float32; the inputs are seeded,
+so two builds can be compared output for output).  --full extends the line with
 
   roofline      the kernel family with the largest share of the forward's time (kernel name up to '<'): algorithmic FLOPs and
                 bytes per launch / average launch duration, measured with HIP events on the model's stream in an instrumented
@@ -16,6 +18,7 @@ broadcast from rank 0.  Rank 0 prints ONE JSON line (contract in the task statem
                 sample of the same workload; kind "port" — it is NOT ONNX Runtime (absent from the image)
   p50_ms, modelinfer_*   per-call latency of the device-resident step and of the full ModelInfer C-ABI call
                 (host buffers, PCIe-inclusive; never used for `value`)
+  secondary     the other BASELINE configurations that fit one GPU (headline runs at N=1 only)
 """
 from __future__ import annotations
 
@@ -125,8 +128,19 @@ DTYPES = {"f32": ("fp32", "fp32", PEAK_FP32_MFMA_TFLOPS), "f16": ("fp16", "fp16 
 BASELINE_CONFIG = {("densenet121", "f32"): "BASELINE configs[1]", ("densenet121", "f16"): "BASELINE configs[2]", ("resnet50", "f8"): "BASELINE configs[4]"}
 
 
-def measure(B, models, sharding, *, model_name, dtype, Bsz, steps, warmup, rank, world, local_rank, dist, hostpath, want_detail=True):
-    """Load `model_name` in precision `dtype`, put a synthetic batch into HBM, time K graph replays; returns the JSON-line dict on rank 0."""
+DUMP_BYTES = 64 << 20      # --dump-outputs writes at most this much in all (the first rows of a larger output)
+
+
+def dump_output(dump_dir, name, y, world):
+    os.makedirs(dump_dir, exist_ok=True)
+    rows = DUMP_BYTES // world // y[0].nbytes
+    np.save(os.path.join(dump_dir, name + ".npy"), y[:rows])
+
+
+def measure(B, models, sharding, *, model_name, dtype, Bsz, steps, warmup, rank, world, local_rank, dist, hostpath, full=True,
+            want_detail=True, dump_dir=None):
+    """Load `model_name` in precision `dtype`, put a synthetic batch into HBM, time K graph replays; returns the JSON-line dict on rank 0.
+    `full`: also the p50 latency, roofline and (with `hostpath`) ModelInfer figures; `dump_dir`: save the last timed step's output there."""
     _, in_name, out_name, arch = MODELS[model_name]
     if rank == 0:
         model_dir(model_name)                        # rank 0 writes the synthetic model file once; the others wait for it
@@ -170,23 +184,26 @@ def measure(B, models, sharding, *, model_name, dtype, Bsz, steps, warmup, rank,
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
 
-        # per-call latency of the device-resident step (sync after every step)
-        lat = []
-        for _ in range(min(steps, 50)):
-            t1 = time.perf_counter()
-            B.RunPrepared(model, 1, True)
-            lat.append((time.perf_counter() - t1) * 1e3)
-        p50 = float(np.percentile(lat, 50))
-
         y = np.empty((Bsz, 1000), np.float32)
-        B.CopyToHost(model, y, dout[0])
+        B.CopyToHost(model, y, dout[0])                  # the output of the last timed step
         assert np.isfinite(y).all()
+        if dump_dir is not None:
+            dump_output(dump_dir, out_name if world == 1 else f"{out_name}_rank{rank}", y, world)
+
+        if full:      # per-call latency of the device-resident step (sync after every step)
+            lat = []
+            for _ in range(min(steps, 50)):
+                t1 = time.perf_counter()
+                B.RunPrepared(model, 1, True)
+                lat.append((time.perf_counter() - t1) * 1e3)
+            p50 = float(np.percentile(lat, 50))
         if rank != 0:
             return None
         total_images = Bsz * world * steps
         cfg_name = BASELINE_CONFIG.get((model_name, dtype), "additional configuration")
         result = {
-            "metric": f"images/sec, {arch} {'fp32 (bf16x6 1x1 convs)' if dtype == 'f32x6' else DTYPES[dtype][0]}, batch {Bsz} per GPU, device-resident inputs (+ p50 step latency)",
+            "metric": f"images/sec, {arch} {'fp32 (bf16x6 1x1 convs)' if dtype == 'f32x6' else DTYPES[dtype][0]}, batch {Bsz} per GPU, device-resident inputs"
+                      + (" (+ p50 step latency)" if full else ""),
             "value": round(total_images / elapsed, 2), "unit": "images/sec", "n_gpus": world, "steps": steps,
             "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
@@ -196,8 +213,10 @@ def measure(B, models, sharding, *, model_name, dtype, Bsz, steps, warmup, rank,
                        "scaling_note": "weak scaling: every rank runs the SAME per-GPU batch, so N ranks are expected at ~N x this value (no data-path "
                                        "collective); a FIXED global batch of 32 cut over 8 GPUs (4 images each, ~1.0 ms per step against 2.2 ms for 32) "
                                        "would scale ~2.2x, not 8x: DESIGN.md section 6"},
-            "p50_ms": round(p50, 4),
         }
+        if not full:
+            return result
+        result["p50_ms"] = round(p50, 4)
         # ---- roofline of the dominant kernel family, HIP events on the model's stream --------------------------
         prof = B.Profile(model, 9)
         fam = {}
@@ -286,14 +305,19 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (default 32; 128 for f16, 256 for f8)")
-    ap.add_argument("--cpu-sample", type=int, default=32, help="images for the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: p50 step latency, roofline (an instrumented eager pass), "
+                         "the ModelInfer host path, the secondary configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step as DIR/<output name>.npy (float32)")
+    ap.add_argument("--cpu-sample", type=int, default=32, help="images for the CPU baseline (0 = skip; --full)")
     ap.add_argument("--cpu-backend", choices=["auto", "torch", "numpy"], default="auto")
     ap.add_argument("--dtype", choices=["f32", "f16", "f8", "f32x6"], default="f32",
                     help="f32 = the headline (BASELINE configs[1]); f16 = the fp16 precision mode (configs[2-3]); f8 = the fp8 mode (configs[4], --model resnet50)")
     ap.add_argument("--model", choices=sorted(MODELS), default="densenet121",
                     help="densenet121 = the headline workload; resnet50 = the second model family (BASELINE configs[4]'s architecture)")
-    ap.add_argument("--no-hostpath", action="store_true", help="skip the ModelInfer (PCIe-inclusive) measurement")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only: skip the fp16 B=128 and ResNet-50 fp8 B=256 lines")
+    ap.add_argument("--no-hostpath", action="store_true", help="skip the ModelInfer (PCIe-inclusive) measurement (--full)")
+    ap.add_argument("--no-secondary", action="store_true", help="headline only: skip the fp16 B=128 and ResNet-50 fp8 B=256 lines (--full)")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = {"f32": 32, "f16": 128, "f8": 256, "f32x6": 32}[args.dtype]
@@ -322,11 +346,11 @@ def main() -> None:
 
     common = dict(rank=rank, world=world, local_rank=local_rank, dist=dist)
     result = measure(B, models, sharding, model_name=args.model, dtype=args.dtype, Bsz=args.batch, steps=args.steps, warmup=args.warmup,
-                     hostpath=not args.no_hostpath, **common)
+                     hostpath=not args.no_hostpath, full=args.full, dump_dir=args.dump_outputs, **common)
     # The other BASELINE configurations that fit one GPU ride on the same line (a few hundred ms each), so they are driver-run
     # numbers too: DenseNet-121 fp16 B=128 (configs[2]) and ResNet-50 fp8 B=256 (configs[4]).  Only behind the default headline.
     headline = args.model == "densenet121" and args.dtype == "f32"
-    if headline and not args.no_secondary and world == 1:
+    if args.full and headline and not args.no_secondary and world == 1:
         secondary = []
         for mname, dt, bsz in (("densenet121", "f16", 128), ("resnet50", "f8", 256), ("densenet121", "f32x6", 32)):
             r = measure(B, models, sharding, model_name=mname, dtype=dt, Bsz=bsz, steps=max(5, args.steps // 2), warmup=max(2, args.warmup // 2),
@@ -337,7 +361,7 @@ def main() -> None:
                                  {k: v for k, v in r.items() if k.startswith("modelinfer")})
         if result is not None:
             result["secondary"] = secondary
-    if rank == 0:
+    if args.full and rank == 0:
         if args.cpu_sample > 0 and world == 1:       # reported on rank 0 at N=1 only (the other ranks would idle behind it)
             # the numpy oracle needs ~0.5 s per image: keep its sample small
             nimg = args.cpu_sample if args.cpu_backend != "numpy" else min(args.cpu_sample, 8)

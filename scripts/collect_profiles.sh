@@ -24,13 +24,13 @@ echo "step tables done"
 CONFIGS=("f32|--model densenet121 --dtype f32 --batch 32|" "f16|--model densenet121 --dtype f16 --batch 128|_f16_b128" "r50f8|--model resnet50 --dtype f8 --batch 256|_resnet50_f8_b256" "f32x6|--model densenet121 --dtype f32x6 --batch 32|_f32x6_b32")
 for CFG in "${CONFIGS[@]}"; do
   IFS="|" read -r NAME ARGS SUF <<< "$CFG"
-  env $TRACE_ENV rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$NAME -- python3 $R/bench.py --steps 50 --warmup 10 --cpu-sample 0 --no-hostpath --no-secondary $ARGS > $OUT/rocprof_kernel_trace$SUF.log 2>&1
+  env $TRACE_ENV rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$NAME -- python3 $R/bench.py --full --steps 50 --warmup 10 --cpu-sample 0 --no-hostpath --no-secondary $ARGS > $OUT/rocprof_kernel_trace$SUF.log 2>&1
   echo "kernel trace $NAME rc=$?"
   cp $OUT/kt_$NAME/*/*_kernel_stats.csv $OUT/kernel_stats$SUF.csv 2>/dev/null
   rm -rf $OUT/kt_$NAME
   for C in "FETCH_SIZE TCC_HIT_sum" "WRITE_SIZE TCC_MISS_sum" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
     N=$(echo $C | cut -d" " -f1)
-    env $TRACE_ENV rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_${NAME}_$N -- python3 $R/bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-hostpath --no-secondary $ARGS > $OUT/pmc_$N$SUF.log 2>&1 || echo "PMC pass $N ($NAME) failed"
+    env $TRACE_ENV rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_${NAME}_$N -- python3 $R/bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-hostpath --no-secondary $ARGS > $OUT/pmc_$N$SUF.log 2>&1 || echo "PMC pass $N ($NAME) failed"
     python3 $R/scripts/pmc_summary.py $OUT/pmc_${NAME}_$N > $OUT/pmc_$N$SUF.summary.csv
     rm -rf $OUT/pmc_${NAME}_$N
   done
@@ -39,6 +39,6 @@ for CFG in "${CONFIGS[@]}"; do
 done
 # the bench line last, with this run's traffic files already in profiles/<round>/ so that its roofline.traffic comes from the same session
 mkdir -p $R/profiles/$ROUND && cp $OUT/traffic*.json $R/profiles/$ROUND/
-python3 $R/bench.py --steps 50 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python3 $R/bench.py --full --steps 50 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err || exit 1
 echo "bench done"
 ls -la $OUT

@@ -333,11 +333,35 @@ def test_bench_under_torchrun_single_rank(tmp_path):
     env = dict(os.environ, IE_BENCH_MODEL_ROOT=str(tmp_path))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29617", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                        "--cpu-sample", "0", "--no-hostpath", "--no-secondary"], capture_output=True, text=True, timeout=600, env=env)
+                        "--full", "--cpu-sample", "0", "--no-hostpath", "--no-secondary"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 1 and d["steps"] == 5 and d["value"] > 1000 and d["scaling"] == "weak" and d["roofline"]["bound"] == "mfma"
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run: exactly --steps timed replays, the headline keys only, and --dump-outputs saves the last timed step's
+    logits; a second run with the same arguments feeds the same seeded inputs and returns the same logits."""
+    import json
+    import sys
+    env = dict(os.environ, IE_BENCH_MODEL_ROOT=str(tmp_path / "models"))
+    runs = []
+    for out in (tmp_path / "a", tmp_path / "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "f32" and d["unit"] == "images/sec"
+        assert d["higher_is_better"] is True and d["metric"].startswith("images/sec, DenseNet-121 fp32, batch 32 per GPU")
+        assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+        assert not {"roofline", "p50_ms", "secondary", "cpu_baseline"} & set(d)
+        y = np.load(out / "fc6_1.npy")
+        assert y.shape == (32, 1000) and y.dtype == np.float32 and np.isfinite(y).all() and y.std() > 0
+        runs.append(y)
+    np.testing.assert_allclose(runs[0], runs[1], rtol=1e-4, atol=1e-5 * np.abs(runs[0]).max())
 
 
 def test_concurrent_infer_load_unload(mgr):
