@@ -99,6 +99,33 @@ std::string tune_file_header() {
     return o.str();
 }
 
+// Tune-file codes of the conv choices: base + tile of one kernel family, the family of a code is the last base at or below it.  Codes
+// below 100 are tiles of the tiled implicit GEMM in whichever staging (vec / scalar) the step has.  fp8 plans store their run-time
+// Step::tile (kernels.h kWs8Code, kWs38Code), which lies inside the ranges of the raster and weights-stationary 1x1 codes.
+struct TuneFamily { int base; ConvAlgo algo; int tiles; };
+constexpr TuneFamily kTuneFamilies[] = {
+    {0, ConvAlgo::IgemmVec, kNumIgemmTiles},          {100, ConvAlgo::Raster3x3, kNumConvRasterTiles},
+    {200, ConvAlgo::Ws1x1, std::max(kNumConvWs16Tiles, kNumConvWs32Tiles)},
+    {300, ConvAlgo::Ws3x3, kNumConvWs3Tiles},         {400, ConvAlgo::Direct, kNumConvDirectTiles},
+    {500, ConvAlgo::Wino3x3, kNumConvWinoTiles},      {600, ConvAlgo::X6, kNumConvX6Tiles},
+};
+
+const TuneFamily& tune_family(int code) {
+    const TuneFamily* f = &kTuneFamilies[0];
+    for (const auto& g : kTuneFamilies) if (code >= g.base) f = &g;
+    return *f;
+}
+
+int tune_code(ConvAlgo algo, int tile) {
+    for (const auto& g : kTuneFamilies) if (g.base != 0 && g.algo == algo) return g.base + tile;
+    return tile;
+}
+
+bool tune_code_valid(int t) {
+    return (t >= 0 && t - tune_family(t).base < tune_family(t).tiles) || (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles) ||
+           (t >= kWs38Code && t < kWs38Code + kNumConvWs38Tiles);
+}
+
 // "<signature ints> : <encoded tile> <splitk>" per line behind a header naming the tile tables the numbers index into; a file
 // written by an engine with other tables is ignored as a whole.
 void load_tune_file(const std::string& path, std::map<std::vector<int64_t>, std::pair<int, int>>& cache) {
@@ -117,10 +144,8 @@ void load_tune_file(const std::string& path, std::map<std::vector<int64_t>, std:
             key.push_back(v);
         }
         int t = -1, sp = 0;
-        if (ok && (is >> t >> sp) && ((t >= 0 && t < kNumIgemmTiles) || (t >= 100 && t < 100 + (kNumConvRasterTiles > kNumConvWs8Tiles ? kNumConvRasterTiles : kNumConvWs8Tiles)) ||      // (fp32: raster tiles; fp8 files: conv1x1_ws_f8 tiles)
-                                        (t >= 200 && t < 200 + (kNumConvWs16Tiles > kNumConvWs32Tiles ? kNumConvWs16Tiles : kNumConvWs32Tiles)) ||
-                                       (t >= 300 && t < 300 + kNumConvWs3Tiles) || (t >= 400 && t < 400 + kNumConvDirectTiles) || (t >= 500 && t < 500 + kNumConvWinoTiles) || (t >= 600 && t < 600 + kNumConvX6Tiles)) &&
-            sp >= 1 && sp <= 64 && key.size() >= 6)          // (the fused steps have short signatures: stem + pool 7 numbers, dense block 10, dual 9)
+        if (ok && (is >> t >> sp) && tune_code_valid(t) && sp >= 1 && sp <= 64 &&
+            key.size() >= 6)          // (the fused steps have short signatures: stem + pool 7 numbers, dense block 10, dual 9)
             cache[key] = {t, sp};
     }
 }
@@ -776,489 +801,295 @@ void DeviceModel::EnsurePipeline(PlanInstance& pi, bool allow_tune) {
     pi.head_steps = int(head);
 }
 
+// One top-level Autotune call: the timing events and the L2 scrub buffer (freed on every way out), the cache accessors, and whether a
+// choice was searched (the tune file is then saved once, at the end).  The parts of a fused step are tuned with the same context.
+struct DeviceModel::TuneContext {
+    DeviceWeights& w;
+    bool allow_search, log;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    void* scrub = nullptr;                 // nullptr: the hot protocol
+    bool searched = false;
+    static constexpr size_t kScrubBytes = size_t(64) << 20;       // > 8 x 4 MiB of L2
+    ~TuneContext() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (scrub) (void)hipFree(scrub);
+    }
+    bool lookup(const std::vector<int64_t>& key, std::pair<int, int>* choice) {     // (encoded tile, split-K) of a signature
+        std::lock_guard<std::mutex> g(w.tune_mu);
+        auto hit = w.tune_cache.find(key);
+        if (hit == w.tune_cache.end()) return false;
+        *choice = hit->second;
+        return true;
+    }
+    void store(const std::vector<int64_t>& key, int code, int splitk) {
+        std::lock_guard<std::mutex> g(w.tune_mu);
+        w.tune_cache[key] = {code, splitk};
+        w.tune_dirty = true;
+        searched = true;
+    }
+};
+
 // Kernel choice per conv step of pi.plan.steps[0, nsteps): an exact hit in the device's cache, else (allow_search) the exhaustive
 // timed search, else the cached choice of the same conv at the nearest pixel count (within 2x), else the planner's default.
 void DeviceModel::Autotune(PlanInstance& pi, size_t nsteps, bool allow_search) {
-    hipEvent_t e0, e1;
-    check(hipEventCreate(&e0), "hipEventCreate");
-    check(hipEventCreate(&e1), "hipEventCreate");
-    static const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24};
-    constexpr size_t kScrubBytes = size_t(64) << 20;       // > 8 x 4 MiB of L2
-    void* scrub = nullptr;
+    TuneContext ctx{*w_, allow_search, env_.flag("IE_TUNE_LOG")};
+    check(hipEventCreate(&ctx.e0), "hipEventCreate");
+    check(hipEventCreate(&ctx.e1), "hipEventCreate");
     if (const char* e = env_.get("IE_TUNE_HOT"); allow_search && !(e && std::atoi(e) != 0))
-        if (hipMalloc(&scrub, kScrubBytes) != hipSuccess) { scrub = nullptr; (void)hipGetLastError(); }
-    bool searched = false;
-    try {
-        for (size_t si = 0; si < nsteps && si < pi.plan.steps.size(); ++si) {
-            Step& s = pi.plan.steps[si];
-            if (s.kind != StepKind::Conv || s.algo == ConvAlgo::Naive || s.algo == ConvAlgo::Stem) continue;
-            if (s.algo == ConvAlgo::DualF8) {
-                if (!s.in.f8) continue;                // (a calibration plan: never tuned)
-                std::vector<int64_t> keyd = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, s.parts.size() == 2 ? s.parts[0].in.c : 0, s.parts.size() == 2 ? s.parts[0].sh : 0,
-                                             s.in.pitch, s.out.pitch, int64_t(ConvAlgo::DualF8), s.bias_off >= 0};
-                {
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    auto hit = w_->tune_cache.find(keyd);
-                    if (hit != w_->tune_cache.end()) { s.tile = hit->second.first; continue; }
-                }
-                if (!allow_search || !w_->f8_ready) continue;
-                searched = true;
-                float bestd = 1e30f;
-                int best_t = 101;
-                for (int t = 1; t < kNumConvWs8Tiles; ++t) {
-                    Step trial = s;
-                    trial.tile = 100 + t;
-                    if (!ConvWs8Eligible(MakeConvArgs(pi, trial), t)) continue;
-                    LaunchStep(pi, trial, stream_);
-                    float ms_best = 1e30f;
-                    for (int rep = 0; rep < 3; ++rep) {
-                        if (scrub) check(hipMemsetAsync(scrub, 0, kScrubBytes, stream_), "hipMemsetAsync(scrub)");
-                        check(hipEventRecord(e0, stream_), "hipEventRecord");
-                        LaunchStep(pi, trial, stream_);
-                        check(hipEventRecord(e1, stream_), "hipEventRecord");
-                        check(hipEventSynchronize(e1), "hipEventSynchronize");
-                        float ms = 0;
-                        check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-                        ms_best = std::min(ms_best, ms);
-                    }
-                    if (ms_best < bestd) { bestd = ms_best; best_t = 100 + t; }
-                }
-                s.tile = best_t;
-                std::lock_guard<std::mutex> g(w_->tune_mu);
-                w_->tune_cache[keyd] = {best_t, 1};
-                w_->tune_dirty = true;
-                continue;
-            }
-            if (s.algo == ConvAlgo::StemPool) {
-                // fused vs the two launches: one timed choice (tile 1 / 0), cached like the others
-                std::vector<int64_t> keys = {s.in.n, s.in.h, s.in.w, s.out.c, s.out.pitch, s.out.f8 ? 2 : (s.out.f16 ? 1 : 0), int64_t(ConvAlgo::StemPool)};
-                int choice = -1;
-                {
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    auto hit = w_->tune_cache.find(keys);
-                    if (hit != w_->tune_cache.end()) choice = hit->second.first;
-                }
-                const bool can = ConvStemPoolEligible(MakeConvArgs(pi, s));
-                if (choice < 0 && allow_search && can && !(s.out.f8 && !w_->f8_ready)) {
-                    searched = true;
-                    float best[2] = {1e30f, 1e30f};
-                    for (int t = 0; t < 2; ++t) {
-                        Step trial = s;
-                        trial.tile = t;
-                        LaunchStep(pi, trial, stream_);
-                        for (int rep = 0; rep < 3; ++rep) {
-                            if (scrub) check(hipMemsetAsync(scrub, 0, kScrubBytes, stream_), "hipMemsetAsync(scrub)");
-                            check(hipEventRecord(e0, stream_), "hipEventRecord");
-                            LaunchStep(pi, trial, stream_);
-                            check(hipEventRecord(e1, stream_), "hipEventRecord");
-                            check(hipEventSynchronize(e1), "hipEventSynchronize");
-                            float ms = 0;
-                            check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-                            best[t] = std::min(best[t], ms);
-                        }
-                    }
-                    choice = best[1] <= best[0] * 1.05f ? 1 : 0;      // within the timer's noise the single launch wins: it moves a third of the bytes
-                    if (env_.get("IE_TUNE_LOG")) std::fprintf(stderr, "[tune] stem + pool %s: one launch %.1f us, two launches %.1f us\n", s.name.c_str(), best[1] * 1e3, best[0] * 1e3);
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    w_->tune_cache[keys] = {choice, 1};
-                    w_->tune_dirty = true;
-                }
-                if (!can) choice = 0;
-                if (choice >= 0) s.tile = choice;
-                continue;
-            }
-            if (s.algo == ConvAlgo::DenseBlock) {
-                // the parts get their own kernel choices (what runs when the chain kernel declines, and the yardstick); chain vs parts is
-                // one more timed choice (tile 1 = one launch, 0 = the 2n plain launches)
-                PlanInstance tmp;
-                tmp.plan.steps = s.parts;
-                tmp.buffers = pi.buffers;
-                tmp.owned.assign(pi.buffers.size(), 0);
-                tmp.workspace = pi.workspace;
-                tmp.workspace_floats = pi.workspace_floats;
-                tmp.counters = pi.counters;
-                tmp.batch_off = pi.batch_off;
-                for (size_t q = 0; q < tmp.plan.steps.size(); ++q) tmp.plan.steps[q].idx = int(q);
-                Autotune(tmp, tmp.plan.steps.size(), allow_search);
-                for (size_t q = 0; q < s.parts.size(); ++q) { s.parts[q].algo = tmp.plan.steps[q].algo; s.parts[q].tile = tmp.plan.steps[q].tile; s.parts[q].splitk = tmp.plan.steps[q].splitk; }
-                std::vector<int64_t> keyb = {s.in.n * s.in.h * s.in.w, int64_t(s.parts.size()), s.in.c, s.in.h, s.in.w, s.in.pitch, s.in.c_off, int64_t(ConvAlgo::DenseBlock),
-                                             s.pre_scale_off >= 0, s.bias_off >= 0};
-                int choice = -1;
-                {
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    auto hit = w_->tune_cache.find(keyb);
-                    if (hit != w_->tune_cache.end()) choice = hit->second.first;
-                }
-                DenseBlockArgs b;
-                const bool can = MakeBlockArgs(pi, s, &b) && DenseBlockEligible(b);
-                if (choice < 0 && allow_search && can) {
-                    searched = true;
-                    float best[2] = {1e30f, 1e30f};
-                    for (int t = 0; t < 2; ++t) {
-                        Step trial = s;
-                        trial.tile = t;
-                        LaunchStep(pi, trial, stream_);
-                        for (int rep = 0; rep < 3; ++rep) {
-                            if (scrub) check(hipMemsetAsync(scrub, 0, kScrubBytes, stream_), "hipMemsetAsync(scrub)");
-                            check(hipEventRecord(e0, stream_), "hipEventRecord");
-                            LaunchStep(pi, trial, stream_);
-                            check(hipEventRecord(e1, stream_), "hipEventRecord");
-                            check(hipEventSynchronize(e1), "hipEventSynchronize");
-                            float ms = 0;
-                            check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-                            best[t] = std::min(best[t], ms);
-                        }
-                    }
-                    choice = best[1] <= best[0] ? 1 : 0;
-                    if (env_.get("IE_TUNE_LOG")) std::fprintf(stderr, "[tune] dense block %s: chain %.1f us, %zu launches %.1f us\n", s.name.c_str(), best[1] * 1e3, s.parts.size(), best[0] * 1e3);
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    w_->tune_cache[keyb] = {choice, 1};
-                    w_->tune_dirty = true;
-                }
-                if (!can) choice = 0;
-                if (choice >= 0) s.tile = choice;
-                continue;
-            }
-            if (s.algo == ConvAlgo::DenseFused) {
-                // the parts get their own kernel choices (they are what runs when the fused launcher declines, and the yardstick);
-                // then fused vs split is one more timed choice, cached like the others (tile 1 = fused, 0 = split)
-                PlanInstance tmp;
-                tmp.plan.steps = s.parts;
-                tmp.buffers = pi.buffers;
-                tmp.owned.assign(pi.buffers.size(), 0);
-                tmp.workspace = pi.workspace;
-                tmp.workspace_floats = pi.workspace_floats;
-                tmp.counters = pi.counters;
-                tmp.batch_off = pi.batch_off;
-                for (size_t q = 0; q < tmp.plan.steps.size(); ++q) tmp.plan.steps[q].idx = int(q);
-                Autotune(tmp, tmp.plan.steps.size(), allow_search);
-                for (size_t q = 0; q < s.parts.size(); ++q) { s.parts[q].algo = tmp.plan.steps[q].algo; s.parts[q].tile = tmp.plan.steps[q].tile; s.parts[q].splitk = tmp.plan.steps[q].splitk; }
-                const Step& p3 = s.parts[0];
-                std::vector<int64_t> keyf = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, 1, 1, 1, 1, 0, 0, s.in.h, s.in.w, s.in.pitch, s.out.pitch, 0, int64_t(ConvAlgo::DenseFused),
-                                             s.pre_scale_off >= 0, s.bias_off >= 0, p3.in.c, p3.in.pitch};
-                int choice = -1;
-                {
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    auto hit = w_->tune_cache.find(keyf);
-                    if (hit != w_->tune_cache.end()) choice = hit->second.first;
-                }
-                if (choice < 0 && allow_search) {
-                    searched = true;
-                    auto time_it = [&](const Step& trial) {
-                        LaunchStep(pi, trial, stream_);
-                        float best_ms = 1e30f;
-                        for (int rep = 0; rep < 3; ++rep) {
-                            if (scrub) check(hipMemsetAsync(scrub, 0, kScrubBytes, stream_), "hipMemsetAsync(scrub)");
-                            check(hipEventRecord(e0, stream_), "hipEventRecord");
-                            LaunchStep(pi, trial, stream_);
-                            check(hipEventRecord(e1, stream_), "hipEventRecord");
-                            check(hipEventSynchronize(e1), "hipEventSynchronize");
-                            float ms = 0;
-                            check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-                            best_ms = std::min(best_ms, ms);
-                        }
-                        return best_ms;
-                    };
-                    float best_t = 1e30f;
-                    choice = 0;
-                    for (int t = 0; t <= 5; ++t) {         // 0 = the two plain launches; 1 .. 5 = fused tile variants (kernels_fused.hip)
-                        Step trial = s;
-                        trial.tile = t;
-                        if (t > 0) {
-                            ConvArgs a1 = MakeConvArgs(pi, trial);
-                            FusedArgs f;
-                            f.in3 = make_arg(pi, p3.in);
-                            f.out3 = make_arg(pi, p3.out);
-                            f.wfrag3 = w_->d_weights_frag && p3.w_off >= 0 ? w_->d_weights_frag + p3.w_off : nullptr;
-                            if (!ConvDenseFusedEligible(a1, f, t)) continue;
-                        }
-                        const float ms = time_it(trial);
-                        if (ms < best_t) { best_t = ms; choice = t; }
-                    }
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    w_->tune_cache[keyf] = {choice, 1};
-                    w_->tune_dirty = true;
-                }
-                if (choice >= 0) s.tile = choice;          // tile 0: ConvDenseFusedEligible declines, the parts run
-                continue;
-            }
-            const Step planned = s;                    // the planner's default, kept when nothing better is known
-            // the planner's default may already name a specialised kernel: the search starts from the tiled implicit GEMM either way
-            if (s.algo == ConvAlgo::Ws1x1 || s.algo == ConvAlgo::Ws3x3 || s.algo == ConvAlgo::Direct || s.algo == ConvAlgo::Raster3x3 || s.algo == ConvAlgo::Wino3x3 || s.algo == ConvAlgo::X6) {
-                s.algo = ConvAlgo::IgemmVec;
-                s.tile = s.base_tile;
-                s.splitk = 1;
-            }
-            const int64_t M = s.out.n * s.out.h * s.out.w, N = s.out.c;
-            if (s.algo == ConvAlgo::IgemmF8) {
-                // fp8 convs: one kernel family, the search is over its tile shapes
-                std::vector<int64_t> key8 = {M, N, s.in.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch, s.out.pitch, 0, int64_t(s.algo), 0,
-                                             s.bias_off >= 0, 8, s.has_in2};
-                {
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    auto hit = w_->tune_cache.find(key8);
-                    if (hit != w_->tune_cache.end()) { s.tile = hit->second.first; continue; }
-                }
-                if (!allow_search || !w_->f8_ready) continue;
-                searched = true;
-                float best8 = 1e30f;
-                int best_t = s.tile;
-                for (int tc = 0; tc < kNumConvF8Tiles + kNumConvWs8Tiles + kNumConvWs38Tiles; ++tc) {
-                    // candidates: the tiled implicit GEMM's tiles, then (tile >= 100) the weights-stationary 1x1 kernel's, then (>= 200) the 3x3's
-                    const int t = tc < kNumConvF8Tiles ? tc : (tc < kNumConvF8Tiles + kNumConvWs8Tiles ? 100 + (tc - kNumConvF8Tiles) : 200 + (tc - kNumConvF8Tiles - kNumConvWs8Tiles));
-                    if (t < 100 && kIgemmTiles[t].bn > 32 && N <= 32) continue;
-                    Step trial = s;
-                    trial.tile = t;
-                    if (t >= 200 ? !ConvWs38Eligible(MakeConvArgs(pi, trial), t - 200) : (t >= 100 && !ConvWs8Eligible(MakeConvArgs(pi, trial), t - 100))) continue;
-                    LaunchStep(pi, trial, stream_);
-                    float ms_best = 1e30f;
-                    for (int rep = 0; rep < 3; ++rep) {
-                        if (scrub) check(hipMemsetAsync(scrub, 0, kScrubBytes, stream_), "hipMemsetAsync(scrub)");
-                        check(hipEventRecord(e0, stream_), "hipEventRecord");
-                        LaunchStep(pi, trial, stream_);
-                        check(hipEventRecord(e1, stream_), "hipEventRecord");
-                        check(hipEventSynchronize(e1), "hipEventSynchronize");
-                        float ms = 0;
-                        check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-                        ms_best = std::min(ms_best, ms);
-                    }
-                    if (ms_best < best8) { best8 = ms_best; best_t = t; }
-                }
-                s.tile = best_t;
-                std::lock_guard<std::mutex> g(w_->tune_mu);
-                w_->tune_cache[key8] = {best_t, 1};
-                w_->tune_dirty = true;
-                continue;
-            }
-            const int64_t bk = s.in.f16 ? 2 * kIgemmBK : kIgemmBK;
-            const int64_t KT = s.algo == ConvAlgo::IgemmVec ? int64_t(s.kh) * s.kw * ((s.in.c + bk - 1) / bk)
-                                                           : (int64_t(s.kh) * s.kw * s.in.c + kIgemmBK - 1) / kIgemmBK;
-            std::vector<int64_t> key = {M, N, s.in.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch, s.out.pitch,
-                                        s.in.nchw, int64_t(s.algo), s.pre_scale_off >= 0, s.bias_off >= 0};
-            if (s.in.f16 || s.out.f16) { key.push_back(s.in.f16); key.push_back(s.out.f16); }   // fp32 signatures keep 17 entries
-            if (s.has_in2) key.push_back(1);              // a fused residual changes which kernels apply (18 / 20 entries)
-            auto apply = [&](int enc_tile, int sp) {     // tile >= 100 encodes the raster kernel, >= 200 the weights-stationary 1x1
-                if (enc_tile >= 600) { s.algo = ConvAlgo::X6; s.tile = enc_tile - 600; }
-                else if (enc_tile >= 500) { s.algo = ConvAlgo::Wino3x3; s.tile = enc_tile - 500; }
-                else if (enc_tile >= 400) { s.algo = ConvAlgo::Direct; s.tile = enc_tile - 400; }
-                else if (enc_tile >= 300) { s.algo = ConvAlgo::Ws3x3; s.tile = enc_tile - 300; }
-                else if (enc_tile >= 200) { s.algo = ConvAlgo::Ws1x1; s.tile = enc_tile - 200; }
-                else if (enc_tile >= 100) { s.algo = ConvAlgo::Raster3x3; s.tile = enc_tile - 100; }
-                else s.tile = enc_tile;
-                s.splitk = sp;
-            };
-            {
-                std::pair<int, int> choice{-1, 0};
-                bool exact = false;
-                {
-                    std::lock_guard<std::mutex> g(w_->tune_mu);
-                    auto hit = w_->tune_cache.find(key);
-                    if (hit != w_->tune_cache.end()) { choice = hit->second; exact = true; }
-                    else if (!allow_search) {
-                        // nearest pixel count of the same conv (every other field of the signature equal), at most 2x away
-                        double best_d = 1.0;        // |log2(M' / M)| <= 1
-                        for (const auto& kv : w_->tune_cache) {
-                            if (kv.first.size() != key.size() || !std::equal(kv.first.begin() + 1, kv.first.end(), key.begin() + 1)) continue;
-                            const double d = std::fabs(std::log2(double(kv.first[0]) / double(M)));
-                            if (d <= best_d) { best_d = d; choice = kv.second; }
-                        }
-                    }
-                }
-                if (choice.first >= 0) {
-                    int sp = choice.second;
-                    if (!exact && sp > 1) {     // split-K slabs must fit this instance's workspace at this pixel count
-                        if (choice.first < 100) {
-                            const IgemmTile& T = kIgemmTiles[choice.first];
-                            const int64_t wgs = ((M + T.bm - 1) / T.bm) * ((N + T.bn - 1) / T.bn);
-                            if (KT / sp < 2 || int64_t(sp) * wgs * T.bm * T.bn > pi.workspace_floats || wgs > kNumCounters || wgs * sp > 8192 || wgs >= 1024) sp = 1;
-                        } else if (choice.first >= 500) {
-                            sp = 1;
-                        } else if (choice.first < 200) {
-                            if (int64_t(sp) * (M + 256) * (N + 64) * 2 > pi.workspace_floats || (s.in.n * (s.in.h + 1) * (s.in.w + 1)) / 64 * sp > 16384) sp = 1;
-                        } else sp = 1;
-                    }
-                    apply(choice.first, sp);
-                    continue;
-                }
-                if (!allow_search) { s = planned; continue; }
-            }
-            searched = true;
-            float best = 1e30f;
-            int best_tile = s.tile, best_split = s.splitk;
-            const bool tune_log = env_.flag("IE_TUNE_LOG");
-            auto time_trial_raw = [&](const Step& trial) {
-                LaunchStep(pi, trial, stream_);              // warm
-                float best_ms = 1e30f;
-                if (scrub) {
-                    // cold-cache protocol: in the real forward a layer finds neither its weights nor its input in L2 (the other 125
-                    // layers ran in between); back-to-back repeats would flatter every kernel that re-reads operands from L2
-                    for (int rep = 0; rep < 3; ++rep) {
-                        check(hipMemsetAsync(scrub, 0, kScrubBytes, stream_), "hipMemsetAsync(scrub)");
-                        check(hipEventRecord(e0, stream_), "hipEventRecord");
-                        LaunchStep(pi, trial, stream_);
-                        check(hipEventRecord(e1, stream_), "hipEventRecord");
-                        check(hipEventSynchronize(e1), "hipEventSynchronize");
-                        float ms = 0;
-                        check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-                        best_ms = std::min(best_ms, ms);
-                    }
-                    return best_ms;
-                }
-                for (int rep = 0; rep < 2; ++rep) {          // best of two timed triples: robust against one-off hiccups
-                    check(hipEventRecord(e0, stream_), "hipEventRecord");
-                    for (int r = 0; r < 3; ++r) LaunchStep(pi, trial, stream_);
-                    check(hipEventRecord(e1, stream_), "hipEventRecord");
-                    check(hipEventSynchronize(e1), "hipEventSynchronize");
-                    float ms = 0;
-                    check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-                    best_ms = std::min(best_ms, ms);
-                }
-                return best_ms;
-            };
-            auto time_trial = [&](const Step& trial) {
-                const float ms = time_trial_raw(trial);
-                if (tune_log)
-                    std::fprintf(stderr, "[ie-tune] M=%lld N=%lld K=%lld algo=%d tile=%d splitk=%d: %.4f ms\n", static_cast<long long>(M), static_cast<long long>(N),
-                                 static_cast<long long>(s.kh * s.kw * s.in.c), int(trial.algo), trial.tile, trial.splitk, ms);
-                return ms;
-            };
-            // LDS-window kernel for 3x3/s1/p1 convs without an activation prologue
-            if (!s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.sh == 1 && s.sw == 1 && s.pt == 1 && s.pl == 1 && s.pb == 1 &&
-                s.pr == 1 && s.pre_scale_off < 0) {
-                ConvArgs probe;
-                probe.in = make_arg(pi, s.in);
-                probe.out = make_arg(pi, s.out);
-                probe.w = w_->d_weights + s.w_off;
-                probe.kh = 3; probe.kw = 3; probe.pt = 1; probe.pl = 1;
-                const int64_t chunks = (s.in.c + kIgemmBK - 1) / kIgemmBK;
-                const int64_t Mr = s.in.n * (s.in.h + 1) * (s.in.w + 1);
-                for (int t = 0; t < kNumConvRasterTiles; ++t) {
-                    if (!ConvRasterEligible(probe, t)) continue;
-                    const int bn = ConvRasterTileBn(t);
-                    if ((bn > 32 && N <= 32)) continue;
-                    for (int sp : {1, 2, 4, 8}) {
-                        if (sp > chunks) continue;
-                        if (sp > 1 && Mr / 64 * sp > 16384) continue;
-                        if (sp > 1 && int64_t(sp) * (M + 256) * (N + 64) * 2 > pi.workspace_floats) continue;
-                        Step trial = s;
-                        trial.algo = ConvAlgo::Raster3x3;
-                        trial.tile = t;
-                        trial.splitk = sp;
-                        float ms = time_trial(trial);
-                        if (ms < best) { best = ms; best_tile = 100 + t; best_split = sp; }
-                    }
-                }
-            }
-            // Winograd F(2x2, 3x3): 2.25x fewer MACs for the 32-channel 3x3 convs on even-sized images
-            if (!s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.out.c == 32 && !s.has_in2) {
-                Step probe_step = s;
-                probe_step.algo = ConvAlgo::Wino3x3;
-                ConvArgs probe = MakeConvArgs(pi, probe_step);
-                for (int t = 0; t < kNumConvWinoTiles; ++t) {
-                    if (!ConvWinoEligible(probe, t)) {
-                        if (tune_log)
-                            std::fprintf(stderr, "[ie-tune] M=%lld wino tile %d ineligible: wfrag=%p in(c=%d h=%d w=%d sw=%lld sh=%lld sn=%lld p=%p) out(c=%d sw=%lld p=%p) bias=%p pre=%p\n",
-                                         static_cast<long long>(M), t, (const void*)probe.wfrag, probe.in.c, probe.in.h, probe.in.w, (long long)probe.in.sw, (long long)probe.in.sh,
-                                         (long long)probe.in.sn, (void*)probe.in.p, probe.out.c, (long long)probe.out.sw, (void*)probe.out.p, (const void*)probe.bias, (const void*)probe.pre_scale);
-                        continue;
-                    }
-                    Step trial = s;
-                    trial.algo = ConvAlgo::Wino3x3;
-                    trial.tile = t;
-                    trial.splitk = 1;
-                    float ms = time_trial(trial);
-                    if (ms < best) { best = ms; best_tile = 500 + t; best_split = 1; }
-                }
-            }
-            // bf16x6 (opt-in): the 1x1 convs on the bf16 matrix pipe with exactly split operands
-            if (w_->d_weights_x6 && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1 && !s.has_in2) {
-                Step probe_step = s;
-                probe_step.algo = ConvAlgo::X6;
-                ConvArgs probe = MakeConvArgs(pi, probe_step);
-                for (int t = 0; t < kNumConvX6Tiles; ++t) {
-                    if (!ConvX6Eligible(probe, t)) continue;
-                    Step trial = s;
-                    trial.algo = ConvAlgo::X6;
-                    trial.tile = t;
-                    trial.splitk = 1;
-                    float ms = time_trial(trial);
-                    if (ms < best) { best = ms; best_tile = 600 + t; best_split = 1; }
-                }
-            }
-            // the kernels_direct.hip family (every variant checks its own pixel-count / shape limits): K split over the waves with
-            // operands straight from global memory, LDS-window tiles, activations-stationary 1x1, window + streamed weights
-            if (s.algo == ConvAlgo::IgemmVec) {
-                ConvArgs probe = MakeConvArgs(pi, s);
-                probe.res = TensorArg();                   // LaunchStep adds the shortcut in a second kernel for this family
-                for (int t = 0; t < kNumConvDirectTiles; ++t) {
-                    if (!ConvDirectEligible(probe, t)) continue;
-                    Step trial = s;
-                    trial.algo = ConvAlgo::Direct;
-                    trial.tile = t;
-                    trial.splitk = 1;
-                    float ms = time_trial(trial);
-                    if (ms < best) { best = ms; best_tile = 400 + t; best_split = 1; }
-                }
-            }
-            // 1x1/s1: weights-stationary streaming kernel (either precision)
-            if (s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1) {
-                ConvArgs probe = MakeConvArgs(pi, s);
-                for (int t = 0; t < (s.in.f16 ? kNumConvWs16Tiles : kNumConvWs32Tiles); ++t) {
-                    if (!(s.in.f16 ? ConvWsEligible(probe, t) : ConvWs32Eligible(probe, t))) continue;
-                    Step trial = s;
-                    trial.algo = ConvAlgo::Ws1x1;
-                    trial.tile = t;
-                    trial.splitk = 1;
-                    float ms = time_trial(trial);
-                    if (ms < best) { best = ms; best_tile = 200 + t; best_split = 1; }
-                }
-            }
-            if (s.in.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3) {
-                ConvArgs probe = MakeConvArgs(pi, s);
-                for (int t = 0; t < kNumConvWs3Tiles; ++t) {
-                    if (!ConvWs3Eligible(probe, t)) continue;
-                    Step trial = s;
-                    trial.algo = ConvAlgo::Ws3x3;
-                    trial.tile = t;
-                    trial.splitk = 1;
-                    float ms = time_trial(trial);
-                    if (ms < best) { best = ms; best_tile = 300 + t; best_split = 1; }
-                }
-            }
-            for (int t = 0; t < kNumIgemmTiles; ++t) {
-                const IgemmTile& T = kIgemmTiles[t];
-                if ((T.bn > 32 && N <= 32) || (T.bn > 64 && N <= 64)) continue;
-                if ((T.kg > 1 || T.deep) && (s.algo != ConvAlgo::IgemmVec || KT < 2 * T.kg)) continue;
-                if (T.deep && s.in.f16) continue;         // the fp16 kernel has no deep-prefetch variants
-                const int64_t wgs = ((M + T.bm - 1) / T.bm) * ((N + T.bn - 1) / T.bn);
-                if (T.deep && wgs > 1024) continue;       // the deep-prefetch variants target grids that cannot fill the chip
-                for (int sp : kSplits) {
-                    if (sp > 1 && T.kg > 1 && ((!two_pass_splitk_ && !s.in.f16) || KT / (sp * T.kg) < 2)) continue;
-                    if (sp > 1 && (KT / sp < 2 || int64_t(sp) * wgs * T.bm * T.bn > pi.workspace_floats || wgs > kNumCounters ||
-                                   wgs * sp > 8192 || wgs >= 1024))
-                        continue;
-                    Step trial = s;
-                    trial.tile = t;
-                    trial.splitk = sp;
-                    float ms = time_trial(trial);
-                    if (ms < best) { best = ms; best_tile = t; best_split = sp; }
-                }
-            }
-            apply(best_tile, best_split);
-            std::lock_guard<std::mutex> g(w_->tune_mu);
-            w_->tune_cache[key] = {best_tile, best_split};
-            w_->tune_dirty = true;
-        }
-    } catch (...) {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (scrub) (void)hipFree(scrub);
-        throw;
+        if (hipMalloc(&ctx.scrub, TuneContext::kScrubBytes) != hipSuccess) { ctx.scrub = nullptr; (void)hipGetLastError(); }
+    for (size_t si = 0; si < nsteps && si < pi.plan.steps.size(); ++si) TuneStep(ctx, pi, pi.plan.steps[si]);
+    if (ctx.searched) SaveTuneCache();
+}
+
+// Best time in ms of one trial step: a warm launch, then cold -- three rounds of L2 scrub + one timed launch: in the real
+// forward a layer finds neither its weights nor its input in L2 (the other layers ran in between), back-to-back repeats would flatter
+// every kernel that re-reads operands from L2 -- or hot (IE_TUNE_HOT=1, or no scrub buffer): two timed triples.
+float DeviceModel::TimeTrial(TuneContext& ctx, const PlanInstance& pi, const Step& trial) {
+    auto timed = [&](int launches) {
+        check(hipEventRecord(ctx.e0, stream_), "hipEventRecord");
+        for (int r = 0; r < launches; ++r) LaunchStep(pi, trial, stream_);
+        check(hipEventRecord(ctx.e1, stream_), "hipEventRecord");
+        check(hipEventSynchronize(ctx.e1), "hipEventSynchronize");
+        float ms = 0;
+        check(hipEventElapsedTime(&ms, ctx.e0, ctx.e1), "hipEventElapsedTime");
+        return ms;
+    };
+    LaunchStep(pi, trial, stream_);                  // warm
+    float best = 1e30f;
+    for (int rep = 0; rep < (ctx.scrub ? 3 : 2); ++rep) {
+        if (ctx.scrub) check(hipMemsetAsync(ctx.scrub, 0, TuneContext::kScrubBytes, stream_), "hipMemsetAsync(scrub)");
+        best = std::min(best, timed(ctx.scrub ? 1 : 3));
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (scrub) (void)hipFree(scrub);
-    if (searched) SaveTuneCache();
+    if (ctx.log)
+        std::fprintf(stderr, "[ie-tune] M=%lld N=%lld K=%lld algo=%d tile=%d splitk=%d: %.4f ms\n", static_cast<long long>(trial.out.n * trial.out.h * trial.out.w),
+                     static_cast<long long>(trial.out.c), static_cast<long long>(trial.kh * trial.kw * trial.in.c), int(trial.algo), trial.tile, trial.splitk, best);
+    return best;
+}
+
+void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
+    if (s.kind != StepKind::Conv || s.algo == ConvAlgo::Naive || s.algo == ConvAlgo::Stem) return;
+    std::pair<int, int> hit{-1, 0};
+    auto cached_tile = [&](const std::vector<int64_t>& key) { return ctx.lookup(key, &hit) ? hit.first : -1; };
+    auto time_tile = [&](int t) {
+        Step trial = s;
+        trial.tile = t;
+        return TimeTrial(ctx, pi, trial);
+    };
+    if (s.algo == ConvAlgo::DualF8) {
+        if (!s.in.f8) return;                  // (a calibration plan: never tuned)
+        const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, s.parts.size() == 2 ? s.parts[0].in.c : 0, s.parts.size() == 2 ? s.parts[0].sh : 0,
+                                          s.in.pitch, s.out.pitch, int64_t(ConvAlgo::DualF8), s.bias_off >= 0};
+        if (ctx.lookup(key, &hit)) { s.tile = hit.first; return; }
+        if (!ctx.allow_search || !w_->f8_ready) return;
+        const ConvArgs a = MakeConvArgs(pi, s);
+        float best = 1e30f;
+        int best_t = kWs8Code + 1;             // (tile 0 is not a candidate)
+        for (int t = 1; t < kNumConvWs8Tiles; ++t)
+            if (ConvWs8Eligible(a, t))
+                if (const float ms = time_tile(kWs8Code + t); ms < best) { best = ms; best_t = kWs8Code + t; }
+        s.tile = best_t;
+        ctx.store(key, best_t, 1);
+        return;
+    }
+    if (s.algo == ConvAlgo::StemPool) {
+        // fused vs the two launches: one timed choice (tile 1 / 0), cached like the others
+        const std::vector<int64_t> key = {s.in.n, s.in.h, s.in.w, s.out.c, s.out.pitch, s.out.f8 ? 2 : (s.out.f16 ? 1 : 0), int64_t(ConvAlgo::StemPool)};
+        int choice = cached_tile(key);
+        const bool can = ConvStemPoolEligible(MakeConvArgs(pi, s));
+        if (choice < 0 && ctx.allow_search && can && !(s.out.f8 && !w_->f8_ready)) {
+            const float two = time_tile(0), one = time_tile(1);
+            choice = one <= two * 1.05f ? 1 : 0;      // within the timer's noise the single launch wins: it moves a third of the bytes
+            ctx.store(key, choice, 1);
+        }
+        if (!can) choice = 0;
+        if (choice >= 0) s.tile = choice;
+        return;
+    }
+    // the parts of a fused step get their own kernel choices (what runs when the fused launcher declines, and the yardstick), tuned in
+    // place: they address the parent's buffers like every step (make_arg reads only buffers and batch_off)
+    if (s.algo == ConvAlgo::DenseBlock || s.algo == ConvAlgo::DenseFused)
+        for (Step& q : s.parts) TuneStep(ctx, pi, q);
+    if (s.algo == ConvAlgo::DenseBlock) {
+        // chain vs parts is one more timed choice (tile 1 = one launch, 0 = the 2n plain launches)
+        const std::vector<int64_t> key = {s.in.n * s.in.h * s.in.w, int64_t(s.parts.size()), s.in.c, s.in.h, s.in.w, s.in.pitch, s.in.c_off, int64_t(ConvAlgo::DenseBlock),
+                                          s.pre_scale_off >= 0, s.bias_off >= 0};
+        int choice = cached_tile(key);
+        DenseBlockArgs b;
+        const bool can = MakeBlockArgs(pi, s, &b) && DenseBlockEligible(b);
+        if (choice < 0 && ctx.allow_search && can) {
+            const float parts = time_tile(0), chain = time_tile(1);
+            choice = chain <= parts ? 1 : 0;
+            ctx.store(key, choice, 1);
+        }
+        if (!can) choice = 0;
+        if (choice >= 0) s.tile = choice;
+        return;
+    }
+    if (s.algo == ConvAlgo::DenseFused) {
+        // fused vs split is one more timed choice (tile 1 .. 5 = fused tile variants of kernels_fused.hip, 0 = the two plain launches)
+        const Step& p3 = s.parts[0];
+        const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, 1, 1, 1, 1, 0, 0, s.in.h, s.in.w, s.in.pitch, s.out.pitch, 0, int64_t(ConvAlgo::DenseFused),
+                                          s.pre_scale_off >= 0, s.bias_off >= 0, p3.in.c, p3.in.pitch};
+        int choice = cached_tile(key);
+        if (choice < 0 && ctx.allow_search) {
+            FusedArgs f;
+            f.in3 = make_arg(pi, p3.in);
+            f.out3 = make_arg(pi, p3.out);
+            f.wfrag3 = w_->d_weights_frag && p3.w_off >= 0 ? w_->d_weights_frag + p3.w_off : nullptr;
+            const ConvArgs a1 = MakeConvArgs(pi, s);
+            float best = 1e30f;
+            choice = 0;
+            for (int t = 0; t <= 5; ++t)
+                if (t == 0 || ConvDenseFusedEligible(a1, f, t))
+                    if (const float ms = time_tile(t); ms < best) { best = ms; choice = t; }
+            ctx.store(key, choice, 1);
+        }
+        if (choice >= 0) s.tile = choice;          // tile 0: ConvDenseFusedEligible declines, the parts run
+        return;
+    }
+    const int64_t M = s.out.n * s.out.h * s.out.w, N = s.out.c;
+    if (s.algo == ConvAlgo::IgemmF8) {
+        // fp8 convs: the tiled implicit GEMM's tiles, then the weights-stationary 1x1 kernel's, then the 3x3's
+        const std::vector<int64_t> key = {M, N, s.in.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch, s.out.pitch, 0, int64_t(s.algo), 0,
+                                          s.bias_off >= 0, 8, s.has_in2};
+        if (ctx.lookup(key, &hit)) { s.tile = hit.first; return; }
+        if (!ctx.allow_search || !w_->f8_ready) return;
+        const ConvArgs a = MakeConvArgs(pi, s);
+        float best = 1e30f;
+        int best_t = s.tile;
+        auto consider = [&](int t) { if (const float ms = time_tile(t); ms < best) { best = ms; best_t = t; } };
+        for (int t = 0; t < kNumConvF8Tiles; ++t) if (!(kIgemmTiles[t].bn > 32 && N <= 32)) consider(t);
+        for (int t = 0; t < kNumConvWs8Tiles; ++t) if (ConvWs8Eligible(a, t)) consider(kWs8Code + t);
+        for (int t = 0; t < kNumConvWs38Tiles; ++t) if (ConvWs38Eligible(a, t)) consider(kWs38Code + t);
+        s.tile = best_t;
+        ctx.store(key, best_t, 1);
+        return;
+    }
+    const Step planned = s;                    // the planner's default, kept when nothing better is known
+    // the planner's default may already name a specialised kernel: the search starts from the tiled implicit GEMM either way
+    if (s.algo == ConvAlgo::Ws1x1 || s.algo == ConvAlgo::Ws3x3 || s.algo == ConvAlgo::Direct || s.algo == ConvAlgo::Raster3x3 || s.algo == ConvAlgo::Wino3x3 || s.algo == ConvAlgo::X6) {
+        s.algo = ConvAlgo::IgemmVec;
+        s.tile = s.base_tile;
+        s.splitk = 1;
+    }
+    const int64_t bk = s.in.f16 ? 2 * kIgemmBK : kIgemmBK;
+    const int64_t KT = s.algo == ConvAlgo::IgemmVec ? int64_t(s.kh) * s.kw * ((s.in.c + bk - 1) / bk)
+                                                   : (int64_t(s.kh) * s.kw * s.in.c + kIgemmBK - 1) / kIgemmBK;
+    std::vector<int64_t> key = {M, N, s.in.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch, s.out.pitch,
+                                s.in.nchw, int64_t(s.algo), s.pre_scale_off >= 0, s.bias_off >= 0};
+    if (s.in.f16 || s.out.f16) { key.push_back(s.in.f16); key.push_back(s.out.f16); }   // fp32 signatures keep 17 entries
+    if (s.has_in2) key.push_back(1);              // a fused residual changes which kernels apply (18 / 20 entries)
+    // Split-K admissibility (sp > 1) of the two families that split, for the search and for a choice taken from another pixel count
+    auto igemm_split_ok = [&](const IgemmTile& T, int sp) {
+        const int64_t wgs = ((M + T.bm - 1) / T.bm) * ((N + T.bn - 1) / T.bn);
+        if (T.kg > 1 && ((!two_pass_splitk_ && !s.in.f16) || KT / (sp * T.kg) < 2)) return false;
+        return KT / sp >= 2 && int64_t(sp) * wgs * T.bm * T.bn <= pi.workspace_floats && wgs <= kNumCounters && wgs * sp <= 8192 && wgs < 1024;
+    };
+    auto raster_split_ok = [&](int sp) {
+        const int64_t chunks = (s.in.c + kIgemmBK - 1) / kIgemmBK, Mr = s.in.n * (s.in.h + 1) * (s.in.w + 1);
+        return sp <= chunks && Mr / 64 * sp <= 16384 && int64_t(sp) * (M + 256) * (N + 64) * 2 <= pi.workspace_floats;
+    };
+    bool exact = ctx.lookup(key, &hit);
+    if (!exact && !ctx.allow_search) {
+        // nearest pixel count of the same conv (every other field of the signature equal), at most 2x away
+        double best_d = 1.0;        // |log2(M' / M)| <= 1
+        std::lock_guard<std::mutex> g(w_->tune_mu);
+        for (const auto& kv : w_->tune_cache) {
+            if (kv.first.size() != key.size() || !std::equal(kv.first.begin() + 1, kv.first.end(), key.begin() + 1)) continue;
+            const double d = std::fabs(std::log2(double(kv.first[0]) / double(M)));
+            if (d <= best_d) { best_d = d; hit = kv.second; }
+        }
+    }
+    if (exact || hit.first >= 0) {
+        const TuneFamily& f = tune_family(hit.first);
+        int sp = hit.second;
+        if (!exact && sp > 1 && !(f.base == 0 ? igemm_split_ok(kIgemmTiles[hit.first], sp) : f.algo == ConvAlgo::Raster3x3 && raster_split_ok(sp)))
+            sp = 1;                             // split-K slabs must fit this instance's workspace at this pixel count
+        if (f.base != 0) s.algo = f.algo;
+        s.tile = hit.first - f.base;
+        s.splitk = sp;
+        return;
+    }
+    if (!ctx.allow_search) { s = planned; return; }
+    float best = 1e30f;
+    Step chosen = s;
+    auto consider = [&](ConvAlgo algo, int t, int sp) {
+        Step trial = s;
+        trial.algo = algo;
+        trial.tile = t;
+        trial.splitk = sp;
+        if (const float ms = TimeTrial(ctx, pi, trial); ms < best) { best = ms; chosen = trial; }
+    };
+    // LDS-window kernel for 3x3/s1/p1 convs without an activation prologue
+    if (!s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.sh == 1 && s.sw == 1 && s.pt == 1 && s.pl == 1 && s.pb == 1 &&
+        s.pr == 1 && s.pre_scale_off < 0) {
+        ConvArgs probe;
+        probe.in = make_arg(pi, s.in);
+        probe.out = make_arg(pi, s.out);
+        probe.w = w_->d_weights + s.w_off;
+        probe.kh = 3; probe.kw = 3; probe.pt = 1; probe.pl = 1;
+        for (int t = 0; t < kNumConvRasterTiles; ++t) {
+            if (!ConvRasterEligible(probe, t) || (ConvRasterTileBn(t) > 32 && N <= 32)) continue;
+            for (int sp : {1, 2, 4, 8})
+                if (sp == 1 || raster_split_ok(sp)) consider(ConvAlgo::Raster3x3, t, sp);
+        }
+    }
+    // Winograd F(2x2, 3x3): 2.25x fewer MACs for the 32-channel 3x3 convs on even-sized images
+    if (!s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.out.c == 32 && !s.has_in2) {
+        Step probe_step = s;
+        probe_step.algo = ConvAlgo::Wino3x3;
+        ConvArgs probe = MakeConvArgs(pi, probe_step);
+        for (int t = 0; t < kNumConvWinoTiles; ++t) {
+            if (!ConvWinoEligible(probe, t)) {
+                if (ctx.log)
+                    std::fprintf(stderr, "[ie-tune] M=%lld wino tile %d ineligible: wfrag=%p in(c=%d h=%d w=%d sw=%lld sh=%lld sn=%lld p=%p) out(c=%d sw=%lld p=%p) bias=%p pre=%p\n",
+                                 static_cast<long long>(M), t, (const void*)probe.wfrag, probe.in.c, probe.in.h, probe.in.w, (long long)probe.in.sw, (long long)probe.in.sh,
+                                 (long long)probe.in.sn, (void*)probe.in.p, probe.out.c, (long long)probe.out.sw, (void*)probe.out.p, (const void*)probe.bias, (const void*)probe.pre_scale);
+                continue;
+            }
+            consider(ConvAlgo::Wino3x3, t, 1);
+        }
+    }
+    // bf16x6 (opt-in): the 1x1 convs on the bf16 matrix pipe with exactly split operands
+    if (w_->d_weights_x6 && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1 && !s.has_in2) {
+        Step probe_step = s;
+        probe_step.algo = ConvAlgo::X6;
+        ConvArgs probe = MakeConvArgs(pi, probe_step);
+        for (int t = 0; t < kNumConvX6Tiles; ++t)
+            if (ConvX6Eligible(probe, t)) consider(ConvAlgo::X6, t, 1);
+    }
+    // the kernels_direct.hip family (every variant checks its own pixel-count / shape limits): K split over the waves with
+    // operands straight from global memory, LDS-window tiles, activations-stationary 1x1, window + streamed weights
+    if (s.algo == ConvAlgo::IgemmVec) {
+        ConvArgs probe = MakeConvArgs(pi, s);
+        probe.res = TensorArg();                   // LaunchStep adds the shortcut in a second kernel for this family
+        for (int t = 0; t < kNumConvDirectTiles; ++t)
+            if (ConvDirectEligible(probe, t)) consider(ConvAlgo::Direct, t, 1);
+    }
+    // 1x1/s1: weights-stationary streaming kernel (either precision)
+    if (s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1) {
+        ConvArgs probe = MakeConvArgs(pi, s);
+        for (int t = 0; t < (s.in.f16 ? kNumConvWs16Tiles : kNumConvWs32Tiles); ++t)
+            if (s.in.f16 ? ConvWsEligible(probe, t) : ConvWs32Eligible(probe, t)) consider(ConvAlgo::Ws1x1, t, 1);
+    }
+    if (s.in.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3) {
+        ConvArgs probe = MakeConvArgs(pi, s);
+        for (int t = 0; t < kNumConvWs3Tiles; ++t)
+            if (ConvWs3Eligible(probe, t)) consider(ConvAlgo::Ws3x3, t, 1);
+    }
+    static const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24};
+    for (int t = 0; t < kNumIgemmTiles; ++t) {
+        const IgemmTile& T = kIgemmTiles[t];
+        if ((T.bn > 32 && N <= 32) || (T.bn > 64 && N <= 64)) continue;
+        if ((T.kg > 1 || T.deep) && (s.algo != ConvAlgo::IgemmVec || KT < 2 * T.kg)) continue;
+        if (T.deep && s.in.f16) continue;         // the fp16 kernel has no deep-prefetch variants
+        if (T.deep && ((M + T.bm - 1) / T.bm) * ((N + T.bn - 1) / T.bn) > 1024) continue;       // the deep-prefetch variants target grids that cannot fill the chip
+        for (int sp : kSplits)
+            if (sp == 1 || igemm_split_ok(T, sp)) consider(s.algo, t, sp);
+    }
+    s = chosen;
+    ctx.store(key, tune_code(s.algo, s.tile), s.splitk);
 }
 
 // Whole-file rewrite through a temporary + rename, so a reader (another process loading the same model) never sees a torn file
@@ -1390,7 +1221,7 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
                 if (s.in.f8) {          // fp8 plan: the two GEMMs of one launch; e4m3 tensors never reach another kernel
                     if (!w_->f8_ready) throw std::runtime_error("fp8 precision: scales are not calibrated yet");
                     const ConvArgs a = MakeConvArgs(pi, s);
-                    const int t = s.tile >= 100 ? s.tile - 100 : 1;
+                    const int t = s.tile >= kWs8Code ? s.tile - kWs8Code : 1;
                     if (a.in2.p == nullptr || !ConvWs8Eligible(a, t)) throw std::runtime_error("fp8 precision: the projection-shortcut step " + s.name + " cannot run on the dual 1x1 kernel");
                     check(LaunchConvWs1x1F8(a, t, stream_), "conv1x1_ws_f8(dual)");
                 } else {                // the fp16 plan of the fp8 calibration: the same step list, the two plain convs
@@ -1459,9 +1290,9 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
                 // would read the bytes as floats
                 if (!w_->f8_ready) throw std::runtime_error("fp8 precision: scales are not calibrated yet");
                 int t8 = s_in.tile;         // a weights-stationary launcher that declines these operands hands the step to the tiled fp8 kernel
-                if (t8 >= 200 ? !ConvWs38Eligible(a, t8 - 200) : (t8 >= 100 && !ConvWs8Eligible(a, t8 - 100))) t8 = s_in.base_tile < kNumConvF8Tiles ? s_in.base_tile : 3;
-                if (t8 >= 200) check(LaunchConvWs3x3F8(a, t8 - 200, stream_), "conv3x3_ws_f8");        // weights-stationary 3x3 (kernels_ws8.hip)
-                else if (t8 >= 100) check(LaunchConvWs1x1F8(a, t8 - 100, stream_), "conv1x1_ws_f8");   // weights-stationary 1x1
+                if (t8 >= kWs38Code ? !ConvWs38Eligible(a, t8 - kWs38Code) : (t8 >= kWs8Code && !ConvWs8Eligible(a, t8 - kWs8Code))) t8 = s_in.base_tile < kNumConvF8Tiles ? s_in.base_tile : 3;
+                if (t8 >= kWs38Code) check(LaunchConvWs3x3F8(a, t8 - kWs38Code, stream_), "conv3x3_ws_f8");        // weights-stationary 3x3 (kernels_ws8.hip)
+                else if (t8 >= kWs8Code) check(LaunchConvWs1x1F8(a, t8 - kWs8Code, stream_), "conv1x1_ws_f8");   // weights-stationary 1x1
                 else check(LaunchConvIgemmF8(a, t8, stream_), "conv_igemm_f8");
                 break;
             }
@@ -1544,9 +1375,9 @@ static std::string kernel_label(const Step& s) {
             if (s.algo == ConvAlgo::Naive) return "conv_naive_kernel";
             if (s.algo == ConvAlgo::DenseBlock) return s.tile != 0 ? "dense_block_f16_kernel<" + std::to_string(s.parts.size() / 2) + " layers>" : "dense_block_parts<" + std::to_string(s.parts.size()) + " launches>";
             if (s.algo == ConvAlgo::DenseFused) return (s.tile >= 4 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";
-            if (s.algo == ConvAlgo::DualF8) return s.in.f8 ? "conv1x1_ws_f8_kernel<dual,t" + std::to_string(s.tile >= 100 ? s.tile - 100 : 1) + ">" : "dual_f8_parts<2 launches>";
-            if (s.algo == ConvAlgo::IgemmF8 && s.tile >= 200) return "conv3x3_ws_f8_kernel<t" + std::to_string(s.tile - 200) + ">";
-            if (s.algo == ConvAlgo::IgemmF8 && s.tile >= 100) return "conv1x1_ws_f8_kernel<t" + std::to_string(s.tile - 100) + ">";
+            if (s.algo == ConvAlgo::DualF8) return s.in.f8 ? "conv1x1_ws_f8_kernel<dual,t" + std::to_string(s.tile >= kWs8Code ? s.tile - kWs8Code : 1) + ">" : "dual_f8_parts<2 launches>";
+            if (s.algo == ConvAlgo::IgemmF8 && s.tile >= kWs38Code) return "conv3x3_ws_f8_kernel<t" + std::to_string(s.tile - kWs38Code) + ">";
+            if (s.algo == ConvAlgo::IgemmF8 && s.tile >= kWs8Code) return "conv1x1_ws_f8_kernel<t" + std::to_string(s.tile - kWs8Code) + ">";
             if (s.algo == ConvAlgo::IgemmF8)
                 return "conv_igemm_f8_kernel<" + std::to_string(kIgemmTiles[s.tile].bm) + "x" + std::to_string(kIgemmTiles[s.tile].bn) + ">";
             if (s.algo == ConvAlgo::Direct) {       // one launcher family, three kernels (kernels_direct.hip): report the one that runs

@@ -174,6 +174,9 @@ private:
     // Exhaustive (tile, split-K) search per distinct conv shape, timed with HIP events on the model's stream; the
     // MI355X counterpart of the reference's cudnn_conv_algo_search = Exhaustive (model.cpp:886).  Only steps [0, nsteps).
     void Autotune(PlanInstance& pi, size_t nsteps, bool allow_search);
+    struct TuneContext;                  // one top-level Autotune call: timing events, L2 scrub buffer, cache access (executor.cpp)
+    void TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s);
+    float TimeTrial(TuneContext& ctx, const PlanInstance& pi, const Step& trial);
     void SaveTuneCache();
     void EnsurePipeline(PlanInstance& pi, bool allow_tune);
     void AllocInstance(PlanInstance& pi);

@@ -10,6 +10,7 @@
 
 #include "env.h"
 #include "igemm_tiles.h"
+#include "kernels.h"
 
 namespace ie {
 
@@ -1001,10 +1002,10 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                     if (const char* ft = env.get("IE_FORCE_TILE")) {
                         const int t = std::atoi(ft);
                         if (t >= 0 && t < kNumIgemmBaseTiles && !(kIgemmTiles[t].bn > 32 && N <= 32)) s.tile = t;
-                        // >= 100: the weights-stationary 1x1 kernel's tiles, >= 200: the 3x3's (kernels_ws8.hip); a launcher that declines the
-                        // operands hands the step back to the tiled kernel (executor)
-                        if (t >= 100 && t < 110 && n.kh == 1 && n.kw == 1) s.tile = t;           // (strided 1x1 convs too: the kernel's STR form)
-                        if (t >= 200 && t < 208 && is3x3) s.tile = t;
+                        // kWs8Code + t: the weights-stationary 1x1 kernel's tiles, kWs38Code + t: the 3x3's (kernels_ws8.hip); a launcher that
+                        // declines the operands hands the step back to the tiled kernel (executor)
+                        if (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles && n.kh == 1 && n.kw == 1) s.tile = t;      // (strided 1x1 convs too: the kernel's STR form)
+                        if (t >= kWs38Code && t < kWs38Code + kNumConvWs38Tiles && is3x3) s.tile = t;
                     }
                     break;
                 }
@@ -1036,14 +1037,14 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                         s.algo = (vec_ok || vec16_ok) ? ConvAlgo::IgemmVec : (K <= 2048 && !in16 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive);
                     else if (f == "ws") {
                         int t = 0;
-                        if (const char* ft = env.get("IE_FORCE_TILE")) { int v = std::atoi(ft); if (v >= 0 && v < (in16 ? 18 : 20)) t = v; }
+                        if (const char* ft = env.get("IE_FORCE_TILE")) { int v = std::atoi(ft); if (v >= 0 && v < (in16 ? kNumConvWs16Tiles : kNumConvWs32Tiles)) t = v; }
                         if (ws16_ok(t) || ws32_ok(t)) { s.algo = ConvAlgo::Ws1x1; s.tile = t; }
-                        else if (ws3_ok(t % 5)) { s.algo = ConvAlgo::Ws3x3; s.tile = t % 5; }
+                        else if (ws3_ok(t % kNumConvWs3Tiles)) { s.algo = ConvAlgo::Ws3x3; s.tile = t % kNumConvWs3Tiles; }
                         else if (s.algo == ConvAlgo::Naive && vec16_ok) s.algo = ConvAlgo::IgemmVec;
                     }
                     else if (f == "direct") {
                         int t = 0;
-                        if (const char* ft = env.get("IE_FORCE_TILE")) { int v = std::atoi(ft); if (v >= 0 && v < 15) t = v; }
+                        if (const char* ft = env.get("IE_FORCE_TILE")) { int v = std::atoi(ft); if (v >= 0 && v < kNumConvDirectTiles) t = v; }
                         if (direct_ok(t)) { s.algo = ConvAlgo::Direct; s.tile = t; }
                         else if (s.algo == ConvAlgo::Naive && (vec_ok || vec16_ok)) s.algo = ConvAlgo::IgemmVec;
                     }
@@ -1052,14 +1053,14 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                         if (x6_ok) {
                             s.algo = ConvAlgo::X6;
                             s.tile = 0;
-                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < 2) s.tile = t; }
+                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < kNumConvX6Tiles) s.tile = t; }
                         }
                     }
                     else if (f == "wino") {
                         if (wino_ok) {
                             s.algo = ConvAlgo::Wino3x3;
                             s.tile = 0;
-                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < 12) s.tile = t; }
+                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < kNumConvWinoTiles) s.tile = t; }
                         } else if (s.algo == ConvAlgo::Naive)
                             s.algo = (vec_ok || vec16_ok) ? ConvAlgo::IgemmVec : (K <= 2048 && !in16 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive);
                     }
@@ -1067,7 +1068,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                         if (raster_ok) {
                             s.algo = ConvAlgo::Raster3x3;
                             s.tile = 0;
-                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < 8) s.tile = t; }
+                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < kNumConvRasterTiles) s.tile = t; }
                         } else if (s.algo == ConvAlgo::Naive)
                             s.algo = (vec_ok || vec16_ok) ? ConvAlgo::IgemmVec : (K <= 2048 && !in16 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive);
                     }

@@ -1606,6 +1606,36 @@ def test_fused_step_choices_survive_a_restart(tmp_path):
         m2.Destroy()
 
 
+def test_fp8_choices_survive_a_restart(tmp_path):
+    """fp8 mode: the convs' codes (tiled kernel tiles, weights-stationary 1x1 at 100 + t, 3x3 at 200 + t) and the dual 1x1's choice (9-number
+    signature) go through the tune file; a second model of the same directory must search nothing (the file is not rewritten) and run the
+    kernels the first one ran, step for step."""
+    mb = models.resnet("N", layers=(2, 2), width=32, image=64, classes=20, seed=53)
+    path = models.write_repo(str(tmp_path), "tuned8", mb, config_json='{"tune_batches": [4], "precision": "fp8"}')
+    cache = os.path.join(path, ".ie_tune.fp8.txt")
+    x = models.synthetic_input((4, 3, 64, 64), stream="tuned8")
+
+    def kernels():
+        m = B.CreateModel(path, "tuned8")
+        try:
+            assert B.Precision(m) == "fp8"
+            din, _ = B.Prepare(m, [[4, 3, 64, 64]], 1)
+            B.CopyToDevice(m, din[0], x)
+            B.RunPrepared(m, 1, True)
+            return [p_["kernel"] for p_ in B.Profile(m, 1)]
+        finally:
+            m.Destroy()
+    first = kernels()
+    assert os.path.exists(cache)
+    stamp = (os.stat(cache).st_mtime_ns, open(cache).read())
+    entries = [(k.split(), int(v.split()[0])) for k, v in (ln.split(":") for ln in stamp[1].splitlines()[1:])]
+    assert any(len(k) == 9 and 100 < code < 110 for k, code in entries), entries          # the dual 1x1: a weights-stationary tile 1 .. 9
+    assert any(k.startswith("conv1x1_ws_f8_kernel<dual") for k in first), first
+    second = kernels()
+    assert (os.stat(cache).st_mtime_ns, open(cache).read()) == stamp
+    assert second == first
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # fp8 precision mode (BASELINE.json configs[4]: ResNet-50 fp8).  The reference never computes in fp8: parity unpinned.
 # Checkers: (1) the OFP8 E4M3 format restated in numpy (oracle/fp8.py) against the device conversion, code for code;
