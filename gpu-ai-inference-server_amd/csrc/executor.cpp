@@ -108,6 +108,7 @@ constexpr TuneFamily kTuneFamilies[] = {
     {200, ConvAlgo::Ws1x1, std::max(kNumConvWs16Tiles, kNumConvWs32Tiles)},
     {300, ConvAlgo::Ws3x3, kNumConvWs3Tiles},         {400, ConvAlgo::Direct, kNumConvDirectTiles},
     {500, ConvAlgo::Wino3x3, kNumConvWinoTiles},      {600, ConvAlgo::X6, kNumConvX6Tiles},
+    {700, ConvAlgo::Depthwise, kNumConvDwTiles},
 };
 
 const TuneFamily& tune_family(int code) {
@@ -282,7 +283,7 @@ void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<
                     // fragment-major mirror of the dense-layer convs (1x1 -> 128 and 3x3 128 -> 32 channels), whatever step they are part of in
                     // this plan instance: the weights are shared by every plan instance, another batch size may fuse other layers
                     auto add16 = [&](const Step& st) {
-                        if (st.kind != StepKind::Conv || st.w_off < 0 || st.in.nchw || st.sh != 1 || st.sw != 1) return;
+                        if (st.kind != StepKind::Conv || st.algo == ConvAlgo::Depthwise || st.w_off < 0 || st.in.nchw || st.sh != 1 || st.sw != 1) return;
                         const bool one = st.kh == 1 && st.kw == 1 && st.out.c == 128 && st.in.c % 32 == 0;
                         const bool three = st.kh == 3 && st.kw == 3 && st.out.c == 32 && st.in.c == 128;
                         if (one || three) w_->frag16_regions.push_back({st.w_off, int(st.out.c), int(st.kh * st.kw * st.in.c)});
@@ -318,7 +319,7 @@ void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<
                 }
             } else if (const char* nf = env_.get("IE_NO_FRAG_WEIGHTS"); !(nf && std::atoi(nf) != 0)) {
                 auto add_region = [&](const Step& st) {
-                    if (st.kind == StepKind::Conv && st.w_off >= 0 && st.out.c % 16 == 0 && st.in.c % 16 == 0 && st.kh * st.kw <= 49)
+                    if (st.kind == StepKind::Conv && st.algo != ConvAlgo::Depthwise && st.w_off >= 0 && st.out.c % 16 == 0 && st.in.c % 16 == 0 && st.kh * st.kw <= 49)
                         w_->frag_regions.push_back({st.w_off, int(st.out.c), st.kh * st.kw, int(st.in.c)});
                 };
                 for (const Step& st : pi.plan.steps) {
@@ -334,7 +335,7 @@ void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<
                 // shared by all plan instances, and another batch size fuses other layers)
                 int64_t utot = 0;
                 auto add_wino = [&](const Step& st) {
-                    if (st.kind == StepKind::Conv && st.w_off >= 0 && st.kh == 3 && st.kw == 3 && st.sh == 1 && st.sw == 1 && st.pt == 1 && st.pl == 1 &&
+                    if (st.kind == StepKind::Conv && st.algo != ConvAlgo::Depthwise && st.w_off >= 0 && st.kh == 3 && st.kw == 3 && st.sh == 1 && st.sw == 1 && st.pt == 1 && st.pl == 1 &&
                         st.out.c == 32 && st.in.c % 32 == 0 && !st.in.nchw) {
                         w_->wino_regions.push_back({st.w_off, utot, 32, int(st.in.c)});
                         utot += int64_t(16) * 32 * st.in.c;
@@ -355,7 +356,7 @@ void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<
                 if (split) {
                     int64_t xtot = 0;
                     auto add_x6 = [&](const Step& st) {
-                        if (st.kind == StepKind::Conv && st.w_off >= 0 && st.kh == 1 && st.kw == 1 && st.sh == 1 && st.sw == 1 && st.out.c % 128 == 0 && st.in.c % 32 == 0 &&
+                        if (st.kind == StepKind::Conv && st.algo != ConvAlgo::Depthwise && st.w_off >= 0 && st.kh == 1 && st.kw == 1 && st.sh == 1 && st.sw == 1 && st.out.c % 128 == 0 && st.in.c % 32 == 0 &&
                             !st.in.nchw) {
                             w_->x6_regions.push_back({st.w_off, xtot, int(st.out.c), int(st.in.c)});
                             xtot += int64_t(3) * st.out.c * st.in.c * 2;
@@ -948,6 +949,25 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
         if (choice >= 0) s.tile = choice;          // tile 0: ConvDenseFusedEligible declines, the parts run
         return;
     }
+    if (s.algo == ConvAlgo::Depthwise) {
+        // the generic kernel and the three channel-vector variants (tune-file codes 700 + tile); nothing else may run a depthwise conv
+        const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch, s.out.pitch,
+                                          s.in.nchw ? 2 : int64_t(s.in.f16), int64_t(ConvAlgo::Depthwise), s.pre_scale_off >= 0, s.has_in2};
+        if (ctx.lookup(key, &hit)) {
+            if (tune_family(hit.first).algo == ConvAlgo::Depthwise) s.tile = hit.first - tune_family(hit.first).base;
+            return;
+        }
+        if (!ctx.allow_search) return;
+        const DwArgs a = MakeDwArgs(pi, s);
+        float best = 1e30f;
+        int best_t = s.tile;
+        for (int t = 0; t < kNumConvDwTiles; ++t)
+            if (ConvDwEligible(a, t))
+                if (const float ms = time_tile(t); ms < best) { best = ms; best_t = t; }
+        s.tile = best_t;
+        ctx.store(key, tune_code(ConvAlgo::Depthwise, best_t), 1);
+        return;
+    }
     const int64_t M = s.out.n * s.out.h * s.out.w, N = s.out.c;
     if (s.algo == ConvAlgo::IgemmF8) {
         // fp8 convs: the tiled implicit GEMM's tiles, then the weights-stationary 1x1 kernel's, then the 3x3's
@@ -1211,6 +1231,26 @@ ConvArgs DeviceModel::MakeConvArgs(const PlanInstance& pi, const Step& s) const 
     return a;
 }
 
+DwArgs DeviceModel::MakeDwArgs(const PlanInstance& pi, const Step& s) const {
+    const float* wb = w_->d_weights;
+    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
+    DwArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    if (s.has_in2) a.res = make_arg(pi, s.in2);
+    a.w = wp(s.w_off);
+    a.bias = wp(s.bias_off);
+    a.pre_scale = wp(s.pre_scale_off);
+    a.pre_shift = wp(s.pre_shift_off);
+    a.pre_relu = s.pre_relu;
+    a.pre_hi = s.pre_hi;
+    a.kh = s.kh; a.kw = s.kw; a.sh = s.sh; a.sw = s.sw; a.pt = s.pt; a.pl = s.pl;
+    a.relu = s.relu;
+    a.lo = s.lo;
+    a.hi = s.hi;
+    return a;
+}
+
 void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream_t stream_) {
     const Step& s = s_in;
     const float* wb = w_->d_weights;
@@ -1227,6 +1267,12 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
                 } else {                // the fp16 plan of the fp8 calibration: the same step list, the two plain convs
                     for (const Step& q : s.parts) LaunchStep(pi, q, stream_);
                 }
+                break;
+            }
+            if (s.algo == ConvAlgo::Depthwise) {
+                // a variant that declines these operands (alignment) hands the step to the generic kernel, which takes every depthwise conv
+                const DwArgs a = MakeDwArgs(pi, s);
+                check(LaunchConvDw(a, ConvDwEligible(a, s.tile) ? s.tile : 0, stream_), "conv_dw");
                 break;
             }
             if (s.algo == ConvAlgo::StemPool) {
@@ -1359,6 +1405,8 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             a.scale = wp(s.pre_scale_off);
             a.shift = wp(s.pre_shift_off);
             a.relu = s.relu;
+            a.lo = s.lo;
+            a.hi = s.hi;
             check(LaunchEltwise(a, stream_), "eltwise");
             break;
         }
@@ -1373,6 +1421,11 @@ static std::string kernel_label(const Step& s) {
     switch (s.kind) {
         case StepKind::Conv:
             if (s.algo == ConvAlgo::Naive) return "conv_naive_kernel";
+            if (s.algo == ConvAlgo::Depthwise) {
+                static const char* px[kNumConvDwTiles] = {"", "1", "2", "4"};
+                return s.tile == 0 ? std::string("conv_dw_generic_kernel")
+                                   : std::string("conv_dw_kernel<") + (s.out.f16 ? "f16,k" : "f32,k") + std::to_string(s.kh) + ",s" + std::to_string(s.sh) + ",px" + px[s.tile] + ">";
+            }
             if (s.algo == ConvAlgo::DenseBlock) return s.tile != 0 ? "dense_block_f16_kernel<" + std::to_string(s.parts.size() / 2) + " layers>" : "dense_block_parts<" + std::to_string(s.parts.size()) + " launches>";
             if (s.algo == ConvAlgo::DenseFused) return (s.tile >= 4 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";
             if (s.algo == ConvAlgo::DualF8) return s.in.f8 ? "conv1x1_ws_f8_kernel<dual,t" + std::to_string(s.tile >= kWs8Code ? s.tile - kWs8Code : 1) + ">" : "dual_f8_parts<2 launches>";

@@ -77,7 +77,29 @@ struct EltArgs {
     const float* scale = nullptr;      // per channel, or null
     const float* shift = nullptr;
     int relu = 0;
+    float lo = -__builtin_huge_valf(), hi = __builtin_huge_valf();   // then min(max(v, lo), hi) (ONNX Clip); the defaults clamp nothing
 };
+
+// Depthwise conv (group == Cin == Cout, kernels_dw.hip): out[n, y, x, c] = clamp(act(sum_{ky,kx} w[c][ky][kx] * f(in[n, y*sh - pt + ky,
+// x*sw - pl + kx, c]) + bias[c] (+ res)), lo, hi), f = the optional prologue min(act(x * pre_scale[c] + pre_shift[c]), pre_hi) on the
+// in-range taps (padding taps contribute 0).  fp32 accumulation; activations float or half (TensorArg::f16), weights / vectors fp32.
+struct DwArgs {
+    TensorArg in, out, res;            // out NHWC (sc == 1); res.p != null: residual added before the ReLU / clamp
+    const float* w = nullptr;          // [C][kh][kw] (BatchNorm folded)
+    const float* bias = nullptr;       // [C] or null
+    const float* pre_scale = nullptr;  // [C] or null
+    const float* pre_shift = nullptr;
+    int pre_relu = 0;
+    float pre_hi = __builtin_huge_valf();
+    int kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0;
+    int relu = 0;
+    float lo = -__builtin_huge_valf(), hi = __builtin_huge_valf();
+};
+// tile 0: generic (one channel per lane; any k <= 7, stride, padding, C, NCHW input); tiles 1-3: 16-byte channel vectors per lane (4 floats /
+// 8 halfs) and 1 / 2 / 4 output pixels along W per lane, for k in {3, 5}, stride in {1, 2}, C and pitches multiples of the vector width
+constexpr int kNumConvDwTiles = 4;
+bool ConvDwEligible(const DwArgs& a, int tile);
+hipError_t LaunchConvDw(const DwArgs& a, int tile, hipStream_t stream);
 
 // vec: 1 = float4 NHWC operand staging, 0 = scalar gather staging.  tile: index into kIgemmTiles.
 // splitk > 1: the K-tiles are divided over grid.y workgroups that write partial slabs to a.workspace; the slabs are

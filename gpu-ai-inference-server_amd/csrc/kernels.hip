@@ -1230,7 +1230,7 @@ hipError_t LaunchGlobalAvgPool(const TensorArg& in, const TensorArg& out, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// elementwise: out = relu?( scale[c]*a + shift[c] (+ b) )   (stand-alone BN / ReLU / residual Add)
+// elementwise: out = clamp(relu?( scale[c]*a + shift[c] (+ b) ), lo, hi)   (stand-alone BN / ReLU / residual Add / Clip)
 // ------------------------------------------------------------------------------------------------
 __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
     const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1244,6 +1244,8 @@ __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
     if (a.scale) v = v * a.scale[c] + a.shift[c];
     if (a.b.p) v += ld_elem(a.b.p, a.b.f16, int64_t(b) * a.b.sn + int64_t(y) * a.b.sh + int64_t(x) * a.b.sw + int64_t(c) * a.b.sc);
     if (a.relu) v = fmaxf(v, 0.f);
+    if (a.lo > -__builtin_huge_valf()) v = fmaxf(v, a.lo);
+    if (a.hi < __builtin_huge_valf()) v = fminf(v, a.hi);
     st_elem(a.out.p, a.out.f16, int64_t(b) * a.out.sn + int64_t(y) * a.out.sh + int64_t(x) * a.out.sw + int64_t(c) * a.out.sc, v);
 }
 
@@ -1280,6 +1282,14 @@ __global__ void eltwise_vec_kernel(const EltArgs a, const int64_t total_vec, con
     if (a.relu) {
 #pragma unroll
         for (int i = 0; i < V; ++i) v[i] = fmaxf(v[i], 0.f);
+    }
+    if (a.lo > -__builtin_huge_valf()) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[i] = fmaxf(v[i], a.lo);
+    }
+    if (a.hi < __builtin_huge_valf()) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[i] = fminf(v[i], a.hi);
     }
     if constexpr (HALF) {
         h8v o;

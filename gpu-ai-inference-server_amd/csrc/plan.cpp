@@ -39,7 +39,9 @@ struct Val {
     bool dedicated = false;             // its buffer is never recycled
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP };
+
+constexpr float kInf = __builtin_huge_valf();
 
 struct LNode {
     LKind kind;
@@ -53,6 +55,9 @@ struct LNode {
     bool has_pre = false, pre_relu = false, relu = false;
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
+    bool dw = false;                    // depthwise conv (group == Cin == Cout): w packed [C][kh][kw]
+    float lo = -kInf, hi = kInf;        // Clip bounds (L_CLIP; a depthwise conv's epilogue clamp)
+    float pre_hi = kInf;                // depthwise conv: upper bound of the prologue
     bool dead = false;
 };
 
@@ -166,6 +171,15 @@ void read_window_attrs(const OnnxNode& on, LNode& n, int64_t h, int64_t w, bool 
     }
 }
 
+// Depthwise steps: the views the 16-byte channel-vector kernels need (kernels_dw.hip ConvDwEligible re-checks them with the pointers)
+bool DwFastViews(const Step& s) {
+    const int64_t V = s.out.f16 ? 8 : 4;
+    auto ok = [&](const View& v) { return !v.nchw && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == s.out.f16; };
+    return s.kh == s.kw && (s.kh == 3 || s.kh == 5) && s.sh == s.sw && (s.sh == 1 || s.sh == 2) && ok(s.in) && ok(s.out) && (!s.has_in2 || ok(s.in2));
+}
+// 4 output pixels per lane on wide rows, 2 on narrow ones (7x7 maps: 4 groups of 2 instead of 2 of 4, one wasted lane in eight), the generic kernel otherwise
+int DwDefaultTile(const Step& s) { return DwFastViews(s) ? (s.out.w >= 14 ? 3 : 2) : 0; }
+
 int choose_tile(int64_t M, int64_t N) {
     // Estimated time = rounds over the 256 CUs x tile area / tile efficiency.  Larger tiles reuse operands
     // better (higher MFMA duty); smaller ones fill the chip when M*N is small.  A lone workgroup per CU
@@ -243,6 +257,23 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
 
     // ---- ONNX nodes -> logical nodes with shape inference ---------------------------------------
     for (const auto& on : m.nodes) {
+        if (on.op == "Constant") {
+            // a constant becomes an initializer under its output name (exporters write Clip bounds this way)
+            if (on.outputs.size() != 1 || on.attrs.size() != 1) fail("Constant " + on.name + ": expected one output and one value attribute");
+            const OnnxAttr& at = on.attrs.begin()->second;
+            OnnxTensor t;
+            if (at.name == "value" && at.has_t) t = at.t;
+            else if (at.name == "value_float") { t.dtype = ONNX_FLOAT; t.f = {at.f}; }
+            else if (at.name == "value_floats") { t.dtype = ONNX_FLOAT; t.f = at.floats; t.dims = {int64_t(at.floats.size())}; }
+            else if (at.name == "value_int") { t.dtype = ONNX_INT64; t.i = {at.i}; }
+            else if (at.name == "value_ints") { t.dtype = ONNX_INT64; t.i = at.ints; t.dims = {int64_t(at.ints.size())}; }
+            else fail("Constant " + on.name + ": the form '" + at.name + "' is not supported");
+            t.name = on.outputs[0];
+            if (L.derived.count(t.name) || m.initializers.count(t.name) || L.val_of.count(t.name))
+                fail("ONNX graph error: value defined twice: " + t.name);
+            L.derived[t.name] = std::move(t);
+            continue;
+        }
         if (on.outputs.empty() || on.inputs.empty()) fail("node " + on.name + " (" + on.op + ") has no inputs/outputs");
         LNode n;
         n.name = on.name.empty() ? on.outputs[0] : on.name;
@@ -318,12 +349,18 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             if (!act_input(0)) fail("Conv " + n.name + ": constant input is not supported");
             const OnnxTensor* w = L.init(on.inputs.at(1));
             if (!w || w->dims.size() != 4) fail("Conv " + n.name + ": weights must be a 4-D initializer");
-            if (on.attr_i("group", 1) != 1) fail("Conv " + n.name + ": group != 1 is not supported");
             int x = in_val(0);
             const Val& X = L.vals[x];
             if (X.dims.size() != 4) fail("Conv " + n.name + ": input must be 4-D");
             int64_t co = w->dims[0], ci = w->dims[1];
-            if (ci != X.c) fail("Conv " + n.name + ": input channels " + std::to_string(X.c) + " != weight channels " + std::to_string(ci));
+            const int64_t group = on.attr_i("group", 1);
+            if (group != 1) {
+                // depthwise: one filter per channel; the weights [C, 1, kh, kw] pack as [C][kh][kw] (= [Cout][kh][kw][Cin] with Cin = 1)
+                if (group != X.c || co != group || ci != 1)
+                    fail("Conv " + n.name + ": group = " + std::to_string(group) + " is not supported (only depthwise grouped convolutions, with group == input channels == output channels, are)");
+                n.dw = true;
+            }
+            if (n.dw ? ci != 1 : ci != X.c) fail("Conv " + n.name + ": input channels " + std::to_string(X.c) + " != weight channels " + std::to_string(ci));
             n.kind = L_CONV;
             read_window_attrs(on, n, X.h, X.w, true, w);
             if (n.kh != w->dims[2] || n.kw != w->dims[3]) fail("Conv " + n.name + ": kernel_shape does not match weights");
@@ -390,6 +427,21 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             }
             n.in = {x};
             odims = X.dims;
+        } else if (op == "Clip") {
+            // opset < 11: min / max attributes; opset >= 11: optional scalar inputs 2 and 3 (absent or "" = unbounded)
+            n.kind = L_CLIP;
+            n.in = {in_val(0)};
+            odims = L.vals[n.in[0]].dims;
+            if (on.attrs.count("min")) n.lo = on.attr_f("min", -kInf);
+            if (on.attrs.count("max")) n.hi = on.attr_f("max", kInf);
+            for (size_t k = 1; k < 3 && k < on.inputs.size(); ++k) {
+                if (on.inputs[k].empty()) continue;
+                const OnnxTensor* b = L.init(on.inputs[k]);
+                if (!b) fail("Clip " + n.name + ": the " + (k == 1 ? "min" : "max") + " bound must be a constant (initializer or Constant node)");
+                if (b->numel() != 1 || (b->dtype != ONNX_FLOAT && b->dtype != ONNX_DOUBLE && b->dtype != ONNX_FLOAT16))
+                    fail("Clip " + n.name + ": the " + (k == 1 ? "min" : "max") + " bound must be a floating-point scalar");
+                (k == 1 ? n.lo : n.hi) = b->f[0];
+            }
         } else if (op == "Relu") {
             n.kind = L_RELU;
             n.in = {in_val(0)};
@@ -523,6 +575,9 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         int v = L.get_val(vo.name);
         L.vals[v].is_output = true;
     }
+    if (precision == Precision::F8 || f8_fusions)
+        for (const LNode& n : L.nodes)
+            if (n.dw) fail("depthwise convolution is not supported in fp8 mode (Conv " + n.name + ")");
 
     auto single_consumer = [&](int v) { return !L.vals[v].is_output && L.consumers(v).size() == 1; };
 
@@ -550,10 +605,17 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         if (cv.dead || cv.kind != L_CONV) continue;
         int64_t cout = L.vals[cv.out].c;
         size_t kper = cv.w.size() / size_t(cout);
-        while (single_consumer(cv.out) && !cv.relu) {
+        bool clamped = false;
+        while (single_consumer(cv.out) && !cv.relu && !clamped) {
             int ci = L.consumers(cv.out)[0];
             LNode& b = L.nodes[ci];
-            if (b.kind == L_AFFINE) {
+            if (b.kind == L_CLIP) {
+                // only the depthwise kernel has a clamp epilogue (a Clip behind another conv: see the ReLU6 pass below, or an eltwise step)
+                if (!cv.dw) break;
+                cv.lo = b.lo;
+                cv.hi = b.hi;
+                clamped = true;
+            } else if (b.kind == L_AFFINE) {
                 // Once a residual has been absorbed the epilogue computes conv + bias + res: scaling weights and bias would leave
                 // the shortcut unscaled (pre-activation / ResNet-v2 blocks: Conv -> Add -> BN -> ReLU).  The BN then becomes the
                 // consumer's prologue (fusion 3) or a standalone eltwise step (fusion 4).
@@ -578,6 +640,30 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             L.vals[cv.out].producer = int(i);
             b.dead = true;
         }
+    }
+    // ---- fusion 2b: ReLU6 between a conv and a depthwise conv (MobileNetV2's expand 1x1 -> Clip(0, 6) -> depthwise 3x3) ---------------
+    // A Clip with lo == 0 on a conv's output whose only reader is a depthwise conv without a prologue: the producing conv's epilogue applies
+    // the ReLU, the upper bound rides into the depthwise conv's prologue (min(max(x, 0), hi) on every in-range tap).  No dense-conv kernel
+    // needs a clamp epilogue.
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& c = L.nodes[i];
+        if (c.dead || c.kind != L_CLIP || c.lo != 0.f) continue;
+        const int x = c.in[0];
+        const int p = L.vals[x].producer;
+        if (p < 0 || L.nodes[p].dead || L.nodes[p].kind != L_CONV || L.nodes[p].dw || !single_consumer(x) || !single_consumer(c.out)) continue;
+        LNode& d = L.nodes[L.consumers(c.out)[0]];
+        if (d.kind != L_CONV || !d.dw || d.has_pre || d.in[0] != c.out || d.res == c.out) continue;
+        LNode& cv = L.nodes[p];
+        cv.relu = true;
+        cv.name += "+" + c.name;
+        cv.out = c.out;
+        L.vals[cv.out].producer = p;
+        d.has_pre = true;
+        d.pre_relu = true;
+        d.pre_hi = c.hi;
+        d.pre_s.assign(size_t(L.vals[c.out].c), 1.f);
+        d.pre_t.assign(size_t(L.vals[c.out].c), 0.f);
+        c.dead = true;
     }
     // ---- fusion 2c: Conv1x1 -> AveragePool  ==>  AveragePool -> Conv1x1 ---------------------------------
     // Both are linear and a 1x1/stride-1 conv acts per pixel, so they commute (the conv's bias too: the mean of a constant is the
@@ -771,7 +857,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             while (nxt < order.size() && (L.nodes[order[nxt]].kind == L_CONCAT || L.nodes[order[nxt]].kind == L_ALIAS)) ++nxt;
             if (nxt >= order.size()) break;
             const LNode& b1 = L.nodes[order[nxt]];
-            if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre) continue;
+            if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre || a3.dw || b1.dw) continue;
             if (L.vals[a3.out].c != 32 || L.vals[b1.out].c != 128 || L.vals[b1.in[0]].root != L.vals[a3.out].root) continue;
             if (L.vals[a3.out].n * L.vals[a3.out].h * L.vals[a3.out].w > FuseMaxPixels(env)) continue;
             const int rb = L.vals[a3.in[0]].root;
@@ -893,6 +979,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             s.pre_scale_off = push_vec(n.pre_s);
             s.pre_shift_off = push_vec(n.pre_t);
             s.pre_relu = n.pre_relu;
+            s.pre_hi = n.pre_hi;
         }
         switch (n.kind) {
             case L_CONV: {
@@ -901,6 +988,21 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 s.w_off = push_vec(n.w);
                 if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
                 if (n.res >= 0) { s.in2 = view_of(n.res); s.has_in2 = true; }
+                if (n.dw) {
+                    // depthwise: its own kernel whatever IE_FORCE_ALGO says; IE_FORCE_TILE indexes the depthwise variants (kernels.h kNumConvDwTiles)
+                    s.algo = ConvAlgo::Depthwise;
+                    s.lo = n.lo;
+                    s.hi = n.hi;
+                    s.flops = 2.0 * double(s.out.n) * double(s.out.c) * double(s.out.h) * double(s.out.w) * n.kh * n.kw;
+                    s.bytes = vbytes(s.in) + vbytes(s.out) + 4.0 * double(n.w.size()) + (n.res >= 0 ? vbytes(s.in2) : 0.0);
+                    s.tile = DwDefaultTile(s);
+                    if (const char* ft = env.get("IE_FORCE_TILE")) {
+                        const int t = std::atoi(ft);
+                        if (t >= 0 && t < kNumConvDwTiles && (t == 0 || DwFastViews(s))) s.tile = t;
+                    }
+                    s.base_tile = 0;
+                    break;
+                }
                 int64_t M = s.out.n * s.out.h * s.out.w, N = s.out.c, K = int64_t(n.kh) * n.kw * s.in.c;
                 s.flops = 2.0 * double(M) * double(N) * double(K);
                 const bool in16 = s.in.f16;
@@ -1131,6 +1233,14 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 s.bytes = vbytes(s.in) + vbytes(s.out);
                 s.flops = 2.0 * double(s.in.numel());
                 break;
+            case L_CLIP:
+                if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone Clip " + n.name + " on an fp8 tensor is not supported");
+                s.kind = StepKind::Eltwise;
+                s.lo = n.lo;
+                s.hi = n.hi;
+                s.bytes = vbytes(s.in) + vbytes(s.out);
+                s.flops = 2.0 * double(s.in.numel());
+                break;
             case L_RELU:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone Relu " + n.name + " on an fp8 tensor is not supported");
                 s.kind = StepKind::Eltwise;
@@ -1176,7 +1286,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             if (i + 1 < plan.steps.size()) {
                 const Step& s1 = plan.steps[i + 1];
                 const int64_t M = s3.out.n * s3.out.h * s3.out.w;
-                fuse = s3.kind == StepKind::Conv && s1.kind == StepKind::Conv && s3.kh == 3 && s3.kw == 3 && s3.sh == 1 && s3.sw == 1 && s3.pt == 1 && s3.pl == 1 &&
+                fuse = s3.kind == StepKind::Conv && s1.kind == StepKind::Conv && s3.algo != ConvAlgo::Depthwise && s1.algo != ConvAlgo::Depthwise && s3.kh == 3 && s3.kw == 3 && s3.sh == 1 && s3.sw == 1 && s3.pt == 1 && s3.pl == 1 &&
                        s3.pb == 1 && s3.pr == 1 && s3.pre_scale_off < 0 && !s3.has_in2 && s3.out.c == 32 && s3.in.c % 16 == 0 && 9 * (s3.in.c / 16) <= 72 &&
                        9 * (s3.in.c / 16) >= 8 && s1.kh == 1 && s1.kw == 1 && s1.sh == 1 && s1.sw == 1 && s1.pt == 0 && s1.pl == 0 && s1.pb == 0 && s1.pr == 0 &&
                        !s1.has_in2 && s1.out.c == 128 && s1.in.buf == s3.out.buf && s1.in.pitch == s3.out.pitch && !s1.in.nchw && !s3.in.nchw &&
@@ -1240,6 +1350,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             const Step& s1 = plan.steps[i];
             const Step& s3 = plan.steps[i + 1];
             if (s1.kind != StepKind::Conv || s3.kind != StepKind::Conv || !s1.parts.empty() || !s3.parts.empty()) return false;
+            if (s1.algo == ConvAlgo::Depthwise || s3.algo == ConvAlgo::Depthwise) return false;
             if (s1.kh != 1 || s1.kw != 1 || s1.sh != 1 || s1.sw != 1 || s1.pt || s1.pl || s1.pb || s1.pr || s1.has_in2 || s1.out.c != 128) return false;
             if (s3.kh != 3 || s3.kw != 3 || s3.sh != 1 || s3.sw != 1 || s3.pt != 1 || s3.pl != 1 || s3.pb != 1 || s3.pr != 1 || s3.has_in2 || s3.out.c != 32) return false;
             if (s3.pre_scale_off >= 0 || s1.w_off < 0 || s3.w_off < 0) return false;
@@ -1479,7 +1590,7 @@ static std::string json_escape(const std::string& s) {
 
 std::string PlanToJson(const Plan& p) {
     static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy"};
-    static const char* algos[] = {"igemm_vec", "igemm_scalar", "naive", "raster3x3", "ws1x1", "ws3x3", "stem", "direct", "igemm_f8", "dense_fused", "wino3x3", "conv1x1_x6", "dense_block", "dual_f8", "stem_pool"};
+    static const char* algos[] = {"igemm_vec", "igemm_scalar", "naive", "raster3x3", "ws1x1", "ws3x3", "stem", "direct", "igemm_f8", "dense_fused", "wino3x3", "conv1x1_x6", "dense_block", "dual_f8", "stem_pool", "depthwise"};
     std::ostringstream o;
     o.precision(17);
     o << "{\"inputs\":[";
@@ -1510,6 +1621,15 @@ std::string PlanToJson(const Plan& p) {
           << s.pl << "," << s.pb << "," << s.pr << "]";
         o << ",\"pre\":" << (s.pre_scale_off >= 0 ? "true" : "false") << ",\"pre_relu\":" << (s.pre_relu ? "true" : "false")
           << ",\"relu\":" << (s.relu ? "true" : "false") << ",\"bias\":" << (s.bias_off >= 0 ? "true" : "false");
+        // (only on the steps that have them: the plans of graphs without a Clip are unchanged)
+        if (s.pre_hi < kInf) o << ",\"pre_clip\":" << s.pre_hi;
+        if (s.lo > -kInf || s.hi < kInf) {
+            o << ",\"clip\":[";
+            if (s.lo > -kInf) o << s.lo; else o << "null";
+            o << ",";
+            if (s.hi < kInf) o << s.hi; else o << "null";
+            o << "]";
+        }
         if (s.kind == StepKind::Conv) o << ",\"algo\":\"" << algos[int(s.algo)] << "\",\"tile\":" << s.tile << ",\"splitk\":" << s.splitk;
         if (s.kind == StepKind::Pool) o << ",\"max\":" << (s.pool_max ? "true" : "false");
         if (!s.parts.empty()) {

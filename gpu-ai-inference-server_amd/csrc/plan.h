@@ -61,6 +61,8 @@ enum class ConvAlgo : int {
     DualF8 = 13,      // fp8: a bottleneck block's last 1x1 conv AND the projection conv of its shortcut as two GEMMs of one launch (kernels_ws8.hip):
                       // the shortcut tensor never exists.  Step::parts = {projection conv, last conv}; this step's own fields repeat the last
                       // conv's with has_in2 cleared.  The fp16 plan built for the fp8 calibration carries the same step and runs its parts.
+    Depthwise = 15,   // group == Cin == Cout conv (kernels_dw.hip): weights [C][kh][kw]; tile 0 = the generic kernel, 1-3 = 16-byte channel vectors with
+                      // 1 / 2 / 4 output pixels per lane.  Epilogue clamp [lo, hi] (a fused Clip) and prologue bound pre_hi (ReLU6 in front of it)
 };
 
 struct Step {
@@ -77,7 +79,9 @@ struct Step {
     int64_t bias_off = -1;     // [Cout]
     int64_t pre_scale_off = -1, pre_shift_off = -1;   // per input channel, applied before the op (then pre_relu)
     bool pre_relu = false;
+    float pre_hi = __builtin_huge_valf();     // depthwise convs: the prologue's upper bound (a ReLU6 whose ReLU runs in the producer's epilogue)
     bool relu = false;         // applied to the result
+    float lo = -__builtin_huge_valf(), hi = __builtin_huge_valf();   // then min(max(v, lo), hi): a Clip (depthwise conv epilogue / eltwise step)
     ConvAlgo algo = ConvAlgo::Naive;
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)
     int base_tile = 0;         // the tiled implicit GEMM's heuristic tile (what the executor falls back to when a specialised launcher declines)

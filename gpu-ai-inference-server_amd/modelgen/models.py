@@ -1,4 +1,4 @@
-"""Synthetic ONNX model builders (DenseNet-121 and small test graphs).
+"""Synthetic ONNX model builders (DenseNet-121, ResNet-50, MobileNetV2 and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -38,20 +38,50 @@ class GraphBuilder:
 
     # ---- ops ----
     def conv(self, x: str, cin: int, cout: int, k: int, stride: int = 1, pad: int = 0, bias: bool = False,
-             name: str | None = None, w_scale: float | None = None) -> str:
+             name: str | None = None, w_scale: float | None = None, group: int = 1) -> str:
         name = name or self._uid("conv")
-        fan_in = cin * k * k
+        cg = cin // group                       # input channels per group (1 for a depthwise conv)
+        fan_in = cg * k * k
         std = w_scale if w_scale is not None else float(np.sqrt(2.0 / fan_in))
-        w = rng.gaussish(self.seed, name + "_w", cout * cin * k * k).reshape(cout, cin, k, k) * np.float32(std)
+        w = rng.gaussish(self.seed, name + "_w", cout * cg * k * k).reshape(cout, cg, k, k) * np.float32(std)
         ins = [x, self.init(name + "_w", w.astype(np.float32))]
         if bias:
             b = (rng.uniform(self.seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
             ins.append(self.init(name + "_b", b.astype(np.float32)))
         y = name + "_out"
         self.nodes.append(pb.node("Conv", ins, [y], name, [
-            pb.attr_ints("dilations", [1, 1]), pb.attr_int("group", 1),
+            pb.attr_ints("dilations", [1, 1]), pb.attr_int("group", group),
             pb.attr_ints("kernel_shape", [k, k]), pb.attr_ints("pads", [pad] * 4),
             pb.attr_ints("strides", [stride, stride])]))
+        return y
+
+    def clip(self, x: str, lo: float | None = 0.0, hi: float | None = 6.0, form: str = "initializer") -> str:
+        """ONNX Clip in the forms exporters write (None = that bound absent):
+          "attrs"        min / max attributes (opset < 11: build the model with finish(..., opset=6))
+          "initializer"  scalar initializers as inputs 2 / 3 (opset >= 11; an absent min is the empty input name "")
+          "constant"     the same inputs produced by Constant nodes
+        """
+        name = self._uid("clip")
+        y = name + "_out"
+        if form == "attrs":
+            attrs = ([pb.attr_float("min", lo)] if lo is not None else []) + ([pb.attr_float("max", hi)] if hi is not None else [])
+            self.nodes.append(pb.node("Clip", [x], [y], name, attrs))
+            return y
+        ins = [x]
+        for tag, v in (("min", lo), ("max", hi)):
+            if v is None:
+                ins.append("")
+            elif form == "initializer":
+                ins.append(self.init(f"{name}_{tag}", np.array(v, np.float32)))
+            elif form == "constant":
+                self.nodes.append(pb.node("Constant", [], [f"{name}_{tag}"], f"{name}_{tag}_const",
+                                          [pb.attr_tensor("value", np.array(v, np.float32))]))
+                ins.append(f"{name}_{tag}")
+            else:
+                raise ValueError(form)
+        while ins[-1] == "":
+            ins.pop()
+        self.nodes.append(pb.node("Clip", ins, [y], name))
         return y
 
     def bn(self, x: str, c: int, name: str | None = None, eps: float = 1e-5, g_center: float = 1.0) -> str:
@@ -297,6 +327,55 @@ def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width:
 
 def resnet50(batch: int | str = 1) -> bytes:
     return resnet(batch)
+
+
+# MobileNetV2 inverted-residual table (Sandler et al. 2018, Table 2): expansion t, output channels c, repeats n, first stride s
+MOBILENET_V2_BLOCKS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))
+
+
+def _divisible8(v: float) -> int:
+    """Channel rounding of the published MobileNetV2 (nearest multiple of 8, never below 90 % of v)."""
+    n = max(8, int(v + 4) // 8 * 8)
+    return n + 8 if n < 0.9 * v else n
+
+
+def mobilenet_v2(batch: int | str = 1, *, width_mult: float = 1.0, image: int = 224, classes: int = 1000, seed: int = 62,
+                 clip_form: str = "initializer", in_name: str = "data", out_name: str = "logits") -> bytes:
+    """MobileNetV2: conv3x3/s2 (32) -> BN -> ReLU6 -> 17 inverted-residual blocks -> conv1x1 (1280) -> BN -> ReLU6 -> global pool ->
+    Flatten -> Gemm.  A block is [expand 1x1 -> BN -> ReLU6 ->] depthwise 3x3 (stride s) -> BN -> ReLU6 -> project 1x1 -> BN, plus an
+    identity Add where the stride is 1 and the channel count is kept (10 of them); the first block has no expand conv.  ReLU6 is
+    Clip(0, 6) in the given export form (GraphBuilder.clip).  The projection BNs get a small gamma (as trained networks end up with)
+    so activations stay O(1) through the residual additions.
+    """
+    gb = GraphBuilder("mobilenet_v2", seed)
+    c = _divisible8(32 * width_mult)
+    last = _divisible8(1280 * max(1.0, width_mult))
+    x = gb.clip(gb.bn(gb.conv(in_name, 3, c, 3, stride=2, pad=1, name="stem"), c, name="stem_bn"), 0.0, 6.0, clip_form)
+    bi = 0
+    for t, ch, n, s in MOBILENET_V2_BLOCKS:
+        cout = _divisible8(ch * width_mult)
+        for i in range(n):
+            bi += 1
+            stride = s if i == 0 else 1
+            tag = f"b{bi}"
+            hid = c * t
+            y = x
+            if t != 1:
+                y = gb.clip(gb.bn(gb.conv(y, c, hid, 1, name=tag + "_expand"), hid, name=tag + "_bn1"), 0.0, 6.0, clip_form)
+            y = gb.clip(gb.bn(gb.conv(y, hid, hid, 3, stride=stride, pad=1, group=hid, name=tag + "_dw"), hid, name=tag + "_bn2"), 0.0, 6.0, clip_form)
+            y = gb.bn(gb.conv(y, hid, cout, 1, name=tag + "_project"), cout, name=tag + "_bn3", g_center=0.3)
+            if stride == 1 and c == cout:
+                y = gb.simple("Add", [y, x])
+            x = y
+            c = cout
+    x = gb.clip(gb.bn(gb.conv(x, c, last, 1, name="head"), last, name="head_bn"), 0.0, 6.0, clip_form)
+    x = gb.gap(x)
+    x = gb.simple("Flatten", [x], [pb.attr_int("axis", 1)])
+    wfc = rng.gaussish(seed, "fc_w", classes * last).reshape(classes, last) * np.float32(np.sqrt(1.0 / last))
+    bfc = (rng.uniform(seed, "fc_b", classes) - np.float32(0.5)) * np.float32(0.2)
+    gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))],
+              [pb.attr_int("transB", 1)], out=out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=6 if clip_form == "attrs" else 11)
 
 
 def write_repo(root: str, name: str, model_bytes: bytes, version: str = "1", config_json: str | None = None) -> str:

@@ -100,6 +100,10 @@ def attr_ints(name: str, vs: Sequence[int], packed: bool = False) -> bytes:
     return out + f_varint(20, A_INTS)
 
 
+def attr_tensor(name: str, arr: np.ndarray) -> bytes:
+    return f_str(1, name) + f_bytes(5, tensor("", arr)) + f_varint(20, A_TENSOR)
+
+
 def attr_str(name: str, s: str) -> bytes:
     return f_str(1, name) + f_bytes(4, s.encode()) + f_varint(20, A_STRING)
 

@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
-"""Per-step timing table of the DenseNet-121 plan (HIP events around each launch, eager mode)."""
+"""Per-step timing table of a plan (HIP events around each launch, eager mode).
+
+    python scripts/profile_steps.py [batch] [model]      model: a bench.py model (densenet121, resnet50) or any other modelgen builder
+                                                          (mobilenet_v2), written to its own repository under IE_BENCH_MODEL_ROOT
+
+For a graph with depthwise convolutions it also prints the device-resident graph-replay time of the whole forward, the algorithmic GB/s of
+every depthwise step against the 6.29 TB/s measured copy rate, and torch's own F.conv2d(groups=C) on channels_last tensors for the same
+shapes as a yardstick (IE_PRECISION=fp16: half tensors)."""
 import json
 import os
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,9 +25,38 @@ from gpu_ai_inference_server_amd.modelgen import models  # noqa: E402
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
+# F.conv2d(groups=C) on channels_last tensors, ms per call (20 timed calls after 5 warm ones) for each [n, c, h, w, k, stride, pad]
+TORCH_DW = """
+import json, sys, torch
+import torch.nn.functional as F
+dt = torch.float16 if sys.argv[2] == "fp16" else torch.float32
+out = []
+for n, c, h, w, k, st, pd in json.loads(sys.argv[1]):
+    x = torch.randn(n, c, h, w, device="cuda", dtype=dt).to(memory_format=torch.channels_last)
+    wt = torch.randn(c, 1, k, k, device="cuda", dtype=dt)
+    b = torch.randn(c, device="cuda", dtype=dt)
+    f = lambda: F.conv2d(x, wt, b, stride=st, padding=pd, groups=c)
+    for _ in range(5):
+        f()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        f()
+    e1.record()
+    torch.cuda.synchronize()
+    out.append(e0.elapsed_time(e1) / 20)
+print(json.dumps(out))
+"""
+
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 model_name = sys.argv[2] if len(sys.argv) > 2 else "densenet121"
-mdir = bench.model_dir(model_name)
+if model_name in bench.MODELS:
+    mdir = bench.model_dir(model_name)
+else:
+    root = os.environ.get("IE_BENCH_MODEL_ROOT", "/tmp/ie_bench_models")
+    mdir = os.path.join(root, model_name, "1")
+    if not os.path.exists(os.path.join(mdir, "model.onnx")):
+        models.write_repo(root, model_name, getattr(models, model_name)("N"))
 plan = B.DescribeModel(mdir, batch)["plan"]
 m = B.CreateModel(mdir, os.path.basename(os.path.dirname(mdir)))
 din, dout = B.Prepare(m, [[batch, 3, 224, 224]], 1)
@@ -33,4 +70,26 @@ for i, (p, s) in enumerate(zip(prof, plan["steps"])):
     M = s["out"]["n"] * s["out"]["h"] * s["out"]["w"]
     K = s["k"][0] * s["k"][1] * s["in"]["c"]
     print(f"{i:3d} {p['kernel']:34} {M:7d} {s['out']['c']:5d} {K:5d} {p['ms']:8.4f} {p['flops']/p['ms']/1e9:7.2f} {p['bytes']/p['ms']/1e6:7.0f}  {p['name'][:40]}")
+
+dws = [(p, s) for p, s in zip(prof, plan["steps"]) if s.get("algo") == "depthwise"]
+if dws:
+    import time
+    B.RunPrepared(m, 10, True)
+    t0 = time.perf_counter()
+    reps = 50
+    B.RunPrepared(m, reps, True)
+    ms = (time.perf_counter() - t0) * 1e3 / reps
+    print(json.dumps({"model": model_name, "batch": batch, "precision": plan["precision"], "replay_ms_per_step": round(ms, 4),
+                      "images_per_s": round(batch / ms * 1e3, 1)}))
+    # torch's yardstick runs in a child process of its own (a fresh HIP context, no state shared with the engine's)
+    shapes = [[s["in"]["n"], s["in"]["c"], s["in"]["h"], s["in"]["w"], s["k"][0], s["stride"][0], s["pads"][0]] for _, s in dws]
+    child = subprocess.run([sys.executable, "-c", TORCH_DW, json.dumps(shapes), plan["precision"]], capture_output=True, text=True, timeout=300)
+    tms = json.loads(child.stdout.strip().splitlines()[-1]) if child.returncode == 0 else [float("nan")] * len(dws)
+    if child.returncode != 0:
+        print("# torch yardstick failed:", child.stderr.strip().splitlines()[-1:])
+    print(f"{'depthwise step':40} {'HxWxC':>14} {'s':>2} {'ms':>8} {'GB/s':>7} {'%6.29T':>7} {'torch ms':>9}")
+    for (p, s), t in zip(dws, tms):
+        gbs = p["bytes"] / p["ms"] / 1e6
+        shape = f"{s['in']['h']}x{s['in']['w']}x{s['in']['c']}"
+        print(f"{p['name'][:40]:40} {shape:>14} {s['stride'][0]:2d} {p['ms']:8.4f} {gbs:7.0f} {gbs / 6290 * 100:6.1f}% {t:9.4f}")
 m.Destroy()
