@@ -1248,6 +1248,27 @@ DwArgs DeviceModel::MakeDwArgs(const PlanInstance& pi, const Step& s) const {
     a.relu = s.relu;
     a.lo = s.lo;
     a.hi = s.hi;
+    a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
+    a.pre_act = int(s.pre_act.kind); a.pre_act_a = s.pre_act.a; a.pre_act_b = s.pre_act.b;
+    return a;
+}
+
+SeArgs DeviceModel::MakeSeArgs(const PlanInstance& pi, const Step& s) const {
+    const float* wb = w_->d_weights;
+    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
+    SeArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    a.w1 = wp(s.w_off);
+    a.b1 = wp(s.bias_off);
+    a.w2t = wp(s.w2_off);
+    a.b2 = wp(s.bias2_off);
+    a.mid = s.se_mid;
+    a.act1 = int(s.se_act1.kind); a.act1_a = s.se_act1.a; a.act1_b = s.se_act1.b;
+    a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
+    a.chunks = s.se_chunks;
+    a.workspace = pi.workspace;
+    a.workspace_floats = pi.workspace_floats;
     return a;
 }
 
@@ -1394,7 +1415,7 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
                 break;
             }
             check(LaunchGlobalAvgPool(make_arg(pi, s.in), make_arg(pi, s.out), wp(s.pre_scale_off), wp(s.pre_shift_off),
-                                      s.pre_relu, stream_), "global_avg_pool");
+                                      s.pre_relu, stream_, int(s.pre_act.kind), s.pre_act.a, s.pre_act.b), "global_avg_pool");
             break;
         case StepKind::Eltwise: {
             if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the eltwise kernel");
@@ -1407,7 +1428,17 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             a.relu = s.relu;
             a.lo = s.lo;
             a.hi = s.hi;
+            a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
+            a.b_mul = s.mul;
+            a.b_bcast = s.has_in2 && s.in2.h * s.in2.w == 1 && s.out.h * s.out.w > 1;
             check(LaunchEltwise(a, stream_), "eltwise");
+            break;
+        }
+        case StepKind::SqueezeExcite: {
+            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the squeeze-excite kernels");
+            const SeArgs a = MakeSeArgs(pi, s);
+            if (!SqueezeExciteEligible(a)) throw std::runtime_error("squeeze-excite step " + s.name + ": the kernels decline its operands");
+            check(LaunchSqueezeExcite(a, stream_), "squeeze_excite");
             break;
         }
         case StepKind::Copy:
@@ -1422,9 +1453,11 @@ static std::string kernel_label(const Step& s) {
         case StepKind::Conv:
             if (s.algo == ConvAlgo::Naive) return "conv_naive_kernel";
             if (s.algo == ConvAlgo::Depthwise) {
-                static const char* px[kNumConvDwTiles] = {"", "1", "2", "4"};
+                static const int px[kNumConvDwTiles] = {0, 1, 2, 4};
+                const bool act = s.act.kind != ActKind::None || s.pre_act.kind != ActKind::None;
                 return s.tile == 0 ? std::string("conv_dw_generic_kernel")
-                                   : std::string("conv_dw_kernel<") + (s.out.f16 ? "f16,k" : "f32,k") + std::to_string(s.kh) + ",s" + std::to_string(s.sh) + ",px" + px[s.tile] + ">";
+                                   : std::string("conv_dw_kernel<") + (s.out.f16 ? "f16,k" : "f32,k") + std::to_string(s.kh) + ",s" + std::to_string(s.sh) + ",px" +
+                                         std::to_string(DwLanePixels(px[s.tile], s.out.f16, s.kh, s.sh, act)) + (act ? ",act>" : ">");
             }
             if (s.algo == ConvAlgo::DenseBlock) return s.tile != 0 ? "dense_block_f16_kernel<" + std::to_string(s.parts.size() / 2) + " layers>" : "dense_block_parts<" + std::to_string(s.parts.size()) + " launches>";
             if (s.algo == ConvAlgo::DenseFused) return (s.tile >= 4 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";
@@ -1455,6 +1488,7 @@ static std::string kernel_label(const Step& s) {
         case StepKind::GlobalAvgPool: return s.in.f8 ? "gap_f8_kernel" : "gap_kernel";
         case StepKind::Eltwise: return "eltwise_kernel";
         case StepKind::Copy: return "copy_kernel";
+        case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }
     return "?";
 }

@@ -19,6 +19,19 @@ struct TensorArg {
     int f8 = 0;                        // the buffer holds OCP e4m3 bytes (fp8 precision mode); strides in ELEMENTS = bytes; never set together with f16
 };
 
+// Fused pointwise activations (plan.h ActKind): 0 none, 1 sigmoid, 2 hardsigmoid max(0, min(1, a*x + b)), 3 silu x*sigmoid(x),
+// 4 hardswish x*hardsigmoid(x; a, b), 5 relu.  fp32 math in every element type.
+__host__ __device__ inline float ApplyAct(int kind, float a, float b, float x) {
+    switch (kind) {
+        case 1: return 1.f / (1.f + expf(-x));
+        case 2: return fminf(fmaxf(a * x + b, 0.f), 1.f);
+        case 3: return x / (1.f + expf(-x));
+        case 4: return x * fminf(fmaxf(a * x + b, 0.f), 1.f);
+        case 5: return fmaxf(x, 0.f);
+        default: return x;
+    }
+}
+
 struct ConvArgs {
     TensorArg in, out;                 // out is always NHWC (sc == 1)
     TensorArg res;                     // res.p != null: out = act(conv + bias + res), res has the output's shape (residual Add fused)
@@ -78,6 +91,10 @@ struct EltArgs {
     const float* shift = nullptr;
     int relu = 0;
     float lo = -__builtin_huge_valf(), hi = __builtin_huge_valf();   // then min(max(v, lo), hi) (ONNX Clip); the defaults clamp nothing
+    int act = 0;                       // then ApplyAct(act, act_a, act_b, v); 0 = none
+    float act_a = 0.f, act_b = 0.f;
+    int b_mul = 0;                     // 1: the second operand multiplies instead of adding
+    int b_bcast = 0;                   // 1: b is [N, C, 1, 1], read at (n, c) for every pixel (a per-image channel gate)
 };
 
 // Depthwise conv (group == Cin == Cout, kernels_dw.hip): out[n, y, x, c] = clamp(act(sum_{ky,kx} w[c][ky][kx] * f(in[n, y*sh - pt + ky,
@@ -94,12 +111,48 @@ struct DwArgs {
     int kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0;
     int relu = 0;
     float lo = -__builtin_huge_valf(), hi = __builtin_huge_valf();
+    int act = 0, pre_act = 0;          // ApplyAct codes: after the clamp / after the prologue's bound (0 = none)
+    float act_a = 0.f, act_b = 0.f, pre_act_a = 0.f, pre_act_b = 0.f;
 };
 // tile 0: generic (one channel per lane; any k <= 7, stride, padding, C, NCHW input); tiles 1-3: 16-byte channel vectors per lane (4 floats /
 // 8 halfs) and 1 / 2 / 4 output pixels along W per lane, for k in {3, 5}, stride in {1, 2}, C and pitches multiples of the vector width
 constexpr int kNumConvDwTiles = 4;
+// Output pixels per lane the fast kernel runs for `px` requested: with a fused activation (act / pre_act) the prologue's per-element activation
+// must still fit the fully unrolled filter-row loop, so the wide variants step down (k x input vectors per row x vector width <= 200)
+constexpr int DwLanePixels(int px, bool f16, int k, int s, bool act) {
+    return !act ? px : (px >= 4 && k * (3 * s + k) * (f16 ? 8 : 4) <= 200 ? 4 : (px >= 2 && k * (s + k) * (f16 ? 8 : 4) <= 200 ? 2 : 1));
+}
 bool ConvDwEligible(const DwArgs& a, int tile);
 hipError_t LaunchConvDw(const DwArgs& a, int tile, hipStream_t stream);
+
+// Squeeze-and-excitation block (kernels_se.hip): out = in * gate[n, c], gate = act(W2^T-packed FC(act1(W1 * mean_hw(in) + b1)) + b2).
+// Three phases, four launches: squeeze (fp32 partial sums per pixel chunk), fc1 (means + FC1 + act1 -> hidden [N][mid]), fc2 (FC2 + act -> gate [N][C]),
+// apply.  Deterministic (fixed summation orders, no atomics).  The workspace holds chunks * N * C partials, N * mid hidden values and the N * C gate.
+struct SeArgs {
+    TensorArg in, out;                 // NHWC, same shape; out may be a channel slice
+    const float* w1 = nullptr;         // [mid][C]
+    const float* b1 = nullptr;         // [mid] or null
+    const float* w2t = nullptr;        // [mid][C] (FC2's [C][mid] transposed)
+    const float* b2 = nullptr;         // [C] or null
+    int mid = 0;
+    int act1 = 0, act = 0;             // ApplyAct codes of the inner activation and of the gate
+    float act1_a = 0.f, act1_b = 0.f, act_a = 0.f, act_b = 0.f;
+    int chunks = 1;                    // pixel chunks of the squeeze (SeSqueezeChunks)
+    float* workspace = nullptr;
+    int64_t workspace_floats = 0;
+};
+// Pixel chunks of the squeeze: enough (image, chunk) workgroups to fill the chip on large maps, at least 64 pixels per chunk
+inline int SeSqueezeChunks(int64_t n, int64_t hw) {
+    int64_t want = (1024 + n - 1) / n;
+    int64_t by_px = hw / 64;
+    int64_t c = want < by_px ? want : by_px;
+    return int(c < 1 ? 1 : (c > 64 ? 64 : c));
+}
+inline int64_t SeWorkspaceFloats(int64_t n, int64_t c, int64_t mid, int chunks) { return int64_t(chunks) * n * c + n * mid + n * c + 64; }
+bool SqueezeExciteEligible(const SeArgs& a);
+hipError_t LaunchSqueezeExcite(const SeArgs& a, hipStream_t stream);
+// the phases one by one (profiling / scripts): 0 squeeze, 1 fc1, 2 fc2, 3 apply
+hipError_t LaunchSqueezeExcitePhase(const SeArgs& a, int phase, hipStream_t stream);
 
 // vec: 1 = float4 NHWC operand staging, 0 = scalar gather staging.  tile: index into kIgemmTiles.
 // splitk > 1: the K-tiles are divided over grid.y workgroups that write partial slabs to a.workspace; the slabs are
@@ -244,8 +297,9 @@ hipError_t LaunchConvertF32ToF16(const float* src, void* dst, int64_t n, hipStre
 hipError_t LaunchConvertU8ToF32(const void* src, float* dst, int64_t n, float scale, float bias, hipStream_t stream);
 hipError_t LaunchPool(const PoolArgs& a, hipStream_t stream);
 // out[n, c] = mean over (y, x) of f(in[n, y, x, c]),  f = optional scale/shift/ReLU prologue
+// then ApplyAct(pre_act, pre_act_a, pre_act_b, .) before the mean
 hipError_t LaunchGlobalAvgPool(const TensorArg& in, const TensorArg& out, const float* pre_scale, const float* pre_shift,
-                               int pre_relu, hipStream_t stream);
+                               int pre_relu, hipStream_t stream, int pre_act = 0, float pre_act_a = 0.f, float pre_act_b = 0.f);
 hipError_t LaunchEltwise(const EltArgs& a, hipStream_t stream);
 hipError_t LaunchCopy(const TensorArg& in, const TensorArg& out, hipStream_t stream);
 // result[i] = a[i] + b[i]  (the reference's only authored kernel: cuda_utils.cu:10-15)

@@ -1195,7 +1195,7 @@ hipError_t LaunchPool(const PoolArgs& a, hipStream_t stream) {
 // global average pool with fused scale/shift/ReLU prologue.  Block = 64 channels x 4 pixel groups.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gap_kernel(const TensorArg in, const TensorArg out, const float* __restrict__ ps,
-                                                   const float* __restrict__ pt, const int pre_relu) {
+                                                   const float* __restrict__ pt, const int pre_relu, const int pre_act, const float pa, const float pb) {
     __shared__ float red[4][64];
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
@@ -1211,6 +1211,7 @@ __global__ __launch_bounds__(256) void gap_kernel(const TensorArg in, const Tens
             float v = ld_elem(in.p, in.f16, int64_t(b) * in.sn + int64_t(y) * in.sh + int64_t(x) * in.sw + c);
             if (ps) { v = v * s + t; }
             if (pre_relu) v = fmaxf(v, 0.f);
+            if (pre_act) v = ApplyAct(pre_act, pa, pb, v);
             acc += v;
         }
     red[g][cl] = acc;
@@ -1222,15 +1223,16 @@ __global__ __launch_bounds__(256) void gap_kernel(const TensorArg in, const Tens
 }
 
 hipError_t LaunchGlobalAvgPool(const TensorArg& in, const TensorArg& out, const float* pre_scale, const float* pre_shift,
-                               int pre_relu, hipStream_t stream) {
+                               int pre_relu, hipStream_t stream, int pre_act, float pre_act_a, float pre_act_b) {
     if (in.sc != 1 || out.sc != 1) return hipErrorInvalidValue;
     if (in.n == 0 || in.c == 0) return hipSuccess;
-    hipLaunchKernelGGL(gap_kernel, dim3((in.c + 63) / 64, in.n), dim3(256), 0, stream, in, out, pre_scale, pre_shift, pre_relu);
+    hipLaunchKernelGGL(gap_kernel, dim3((in.c + 63) / 64, in.n), dim3(256), 0, stream, in, out, pre_scale, pre_shift, pre_relu, pre_act, pre_act_a, pre_act_b);
     return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
-// elementwise: out = clamp(relu?( scale[c]*a + shift[c] (+ b) ), lo, hi)   (stand-alone BN / ReLU / residual Add / Clip)
+// elementwise: out = act(clamp(relu?( scale[c]*a + shift[c] (+ or * b) ), lo, hi))   (stand-alone BN / ReLU / residual Add / Clip / activation /
+// Mul; b_bcast: b is [N, C, 1, 1], a per-image channel gate)
 // ------------------------------------------------------------------------------------------------
 __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
     const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1242,10 +1244,15 @@ __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
     const int b = int(m / a.out.h);
     float v = ld_elem(a.a.p, a.a.f16, int64_t(b) * a.a.sn + int64_t(y) * a.a.sh + int64_t(x) * a.a.sw + int64_t(c) * a.a.sc);
     if (a.scale) v = v * a.scale[c] + a.shift[c];
-    if (a.b.p) v += ld_elem(a.b.p, a.b.f16, int64_t(b) * a.b.sn + int64_t(y) * a.b.sh + int64_t(x) * a.b.sw + int64_t(c) * a.b.sc);
+    if (a.b.p) {
+        const float u = ld_elem(a.b.p, a.b.f16, a.b_bcast ? int64_t(b) * a.b.sn + int64_t(c) * a.b.sc
+                                                           : int64_t(b) * a.b.sn + int64_t(y) * a.b.sh + int64_t(x) * a.b.sw + int64_t(c) * a.b.sc);
+        v = a.b_mul ? v * u : v + u;
+    }
     if (a.relu) v = fmaxf(v, 0.f);
     if (a.lo > -__builtin_huge_valf()) v = fmaxf(v, a.lo);
     if (a.hi < __builtin_huge_valf()) v = fminf(v, a.hi);
+    if (a.act) v = ApplyAct(a.act, a.act_a, a.act_b, v);
     st_elem(a.out.p, a.out.f16, int64_t(b) * a.out.sn + int64_t(y) * a.out.sh + int64_t(x) * a.out.sw + int64_t(c) * a.out.sc, v);
 }
 
@@ -1259,25 +1266,30 @@ __global__ void eltwise_vec_kernel(const EltArgs a, const int64_t total_vec, con
     const int64_t p = idx / cv;
     const int c = int(idx - p * cv) * V;
     float v[V], w[V];
-    auto load = [&](const TensorArg& t, float* dst) {
+    auto load = [&](const TensorArg& t, float* dst, int64_t off) {
         if constexpr (HALF) {
-            const h8v x = *reinterpret_cast<const h8v*>(reinterpret_cast<const _Float16*>(t.p) + p * t.sw + c);
+            const h8v x = *reinterpret_cast<const h8v*>(reinterpret_cast<const _Float16*>(t.p) + off);
 #pragma unroll
             for (int i = 0; i < V; ++i) dst[i] = float(x[i]);
         } else {
-            const float4 x = *reinterpret_cast<const float4*>(t.p + p * t.sw + c);
+            const float4 x = *reinterpret_cast<const float4*>(t.p + off);
             dst[0] = x.x; dst[1] = x.y; dst[2] = x.z; dst[3] = x.w;
         }
     };
-    load(a.a, v);
+    load(a.a, v, p * a.a.sw + c);
     if (a.scale) {
 #pragma unroll
         for (int i = 0; i < V; ++i) v[i] = v[i] * a.scale[c + i] + a.shift[c + i];
     }
     if (a.b.p) {
-        load(a.b, w);
+        load(a.b, w, a.b_bcast ? p / (int64_t(a.out.h) * a.out.w) * a.b.sn + c : p * a.b.sw + c);
+        if (a.b_mul) {
 #pragma unroll
-        for (int i = 0; i < V; ++i) v[i] += w[i];
+            for (int i = 0; i < V; ++i) v[i] *= w[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) v[i] += w[i];
+        }
     }
     if (a.relu) {
 #pragma unroll
@@ -1290,6 +1302,10 @@ __global__ void eltwise_vec_kernel(const EltArgs a, const int64_t total_vec, con
     if (a.hi < __builtin_huge_valf()) {
 #pragma unroll
         for (int i = 0; i < V; ++i) v[i] = fminf(v[i], a.hi);
+    }
+    if (a.act) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[i] = ApplyAct(a.act, a.act_a, a.act_b, v[i]);
     }
     if constexpr (HALF) {
         h8v o;
@@ -1311,7 +1327,10 @@ hipError_t LaunchEltwise(const EltArgs& a, hipStream_t stream) {
     if (total == 0) return hipSuccess;
     {
         const int f16 = a.out.f16, V = f16 ? 8 : 4;
-        if (elt_vec_ok(a.out, f16, V) && elt_vec_ok(a.a, f16, V) && (a.b.p == nullptr || elt_vec_ok(a.b, f16, V))) {
+        // a broadcast gate [N, C, 1, 1]: 16-byte vectors at (n, c)
+        const bool b_ok = a.b.p == nullptr || (a.b_bcast ? (a.b.f16 == f16 && a.b.sc == 1 && a.b.c % V == 0 && a.b.sn % V == 0 && (reinterpret_cast<uintptr_t>(a.b.p) % 16) == 0)
+                                                         : elt_vec_ok(a.b, f16, V));
+        if (elt_vec_ok(a.out, f16, V) && elt_vec_ok(a.a, f16, V) && b_ok) {
             const int64_t tv = total / V;
             const int64_t vblocks = (tv + 255) / 256;
             if (vblocks < (int64_t(1) << 31)) {

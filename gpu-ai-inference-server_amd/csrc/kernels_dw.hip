@@ -14,6 +14,8 @@
 //
 // Padding taps contribute 0 (explicit bounds): the prologue (folded pre-activation BN, ReLU, ReLU6's upper bound) applies to in-range taps only,
 // as the ONNX graph pads the prologue's OUTPUT.  Epilogue: + bias (+ residual), ReLU, then the Clip bounds.
+// Fused activations (sigmoid / hardsigmoid / SiLU / hardswish: MobileNetV3, EfficientNet) close the prologue (pre_act, after pre_hi) and the
+// epilogue (act, after the clamp).  The fast kernel takes them only in its ACT instantiations, so the graphs without them run the same code as before.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +33,17 @@ constexpr int kDwBlock = 256;
 
 __device__ __forceinline__ bool finite_lo(float lo) { return lo > -__builtin_huge_valf(); }
 __device__ __forceinline__ bool finite_hi(float hi) { return hi < __builtin_huge_valf(); }
+
+// ApplyAct without control flow (the fast kernel's unrolled loops): g = hard ? clamp(a*x + b, 0, 1) : sigmoid(x), then x * g (silu / hardswish)
+// or g; kind 0 = identity.  kind is uniform; both branches are selects.
+__device__ __forceinline__ float act_sel(int kind, float a, float b, float x) {
+    const bool hard = kind == 2 || kind == 4, mul = kind == 3 || kind == 4;
+    const float h = fminf(fmaxf(fmaf(a, x, b), 0.f), 1.f);
+    const float sg = 1.f / (1.f + __expf(-x));
+    const float g = hard ? h : sg;
+    const float y = mul ? x * g : g;
+    return kind == 0 ? x : (kind == 5 ? fmaxf(x, 0.f) : y);
+}
 
 // V consecutive elements (16 bytes) -> floats
 template <typename T>
@@ -61,7 +74,7 @@ __device__ __forceinline__ void store16<_Float16>(_Float16* p, const float* v) {
 }
 
 // groups = N * OH * ceil(OW / PX) pixel groups; the grid holds cvn * nslots lanes, lane (slot, cv) walks groups slot, slot + nslots, ...
-template <typename T, int K, int S, int PX>
+template <typename T, int K, int S, int PX, bool ACT>
 __global__ __launch_bounds__(kDwBlock) void conv_dw_kernel(const DwArgs a, const int cvn, const int owg, const int64_t groups, const int64_t nslots) {
     constexpr int V = 16 / int(sizeof(T));
     constexpr int KK = K * K;
@@ -87,7 +100,7 @@ __global__ __launch_bounds__(kDwBlock) void conv_dw_kernel(const DwArgs a, const
 #pragma unroll
     for (int v = 0; v < V; ++v) { bias[v] = 0.f; ps[v] = 1.f; pt[v] = 0.f; }
     if (a.bias) { load16<float>(a.bias + c0, bias); if constexpr (V == 8) load16<float>(a.bias + c0 + 4, bias + 4); }
-    const bool pre = a.pre_scale != nullptr;
+    const bool pre = a.pre_scale != nullptr || (ACT && a.pre_act != 0);
     if (pre) {
         load16<float>(a.pre_scale + c0, ps); load16<float>(a.pre_shift + c0, pt);
         if constexpr (V == 8) { load16<float>(a.pre_scale + c0 + 4, ps + 4); load16<float>(a.pre_shift + c0 + 4, pt + 4); }
@@ -129,6 +142,7 @@ __global__ __launch_bounds__(kDwBlock) void conv_dw_kernel(const DwArgs a, const
                             float y = x[j][v] * ps[v] + pt[v];
                             if (pre_relu) y = fmaxf(y, 0.f);
                             if (pre_clip) y = fminf(y, pre_hi);
+                            if constexpr (ACT) y = act_sel(a.pre_act, a.pre_act_a, a.pre_act_b, y);
                             x[j][v] = y;
                         }
                     }
@@ -173,6 +187,7 @@ __global__ __launch_bounds__(kDwBlock) void conv_dw_kernel(const DwArgs a, const
                 if (a.relu) o[v] = fmaxf(o[v], 0.f);
                 if (finite_lo(a.lo)) o[v] = fmaxf(o[v], a.lo);
                 if (finite_hi(a.hi)) o[v] = fminf(o[v], a.hi);
+                if constexpr (ACT) o[v] = act_sel(a.act, a.act_a, a.act_b, o[v]);
             }
             store16<T>(out + int64_t(n) * a.out.sn + int64_t(oy) * a.out.sh + int64_t(ox) * a.out.sw + c0, o);
         }
@@ -208,6 +223,7 @@ __global__ __launch_bounds__(kDwBlock) void conv_dw_generic_kernel(const DwArgs 
                 if (a.pre_relu) x = fmaxf(x, 0.f);
                 if (finite_hi(a.pre_hi)) x = fminf(x, a.pre_hi);
             }
+            if (a.pre_act) x = ApplyAct(a.pre_act, a.pre_act_a, a.pre_act_b, x);
             acc = fmaf(w[ky * a.kw + kx], x, acc);
         }
     }
@@ -216,6 +232,7 @@ __global__ __launch_bounds__(kDwBlock) void conv_dw_generic_kernel(const DwArgs 
     if (a.relu) o = fmaxf(o, 0.f);
     if (finite_lo(a.lo)) o = fmaxf(o, a.lo);
     if (finite_hi(a.hi)) o = fminf(o, a.hi);
+    if (a.act) o = ApplyAct(a.act, a.act_a, a.act_b, o);
     const int64_t oi = int64_t(n) * a.out.sn + int64_t(oy) * a.out.sh + int64_t(ox) * a.out.sw + c;
     if (a.out.f16) reinterpret_cast<_Float16*>(a.out.p)[oi] = _Float16(o);
     else a.out.p[oi] = o;
@@ -227,9 +244,10 @@ bool vec_view_ok(const TensorArg& t, int V) {
     return t.sc == 1 && t.c % V == 0 && t.sw % V == 0 && t.sh % V == 0 && t.sn % V == 0 && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
 }
 
-template <typename T, int K, int S>
+template <typename T, int K, int S, bool ACT>
 hipError_t launch_fast(const DwArgs& a, int px, hipStream_t stream) {
     constexpr int V = 16 / int(sizeof(T));
+    px = DwLanePixels(px, V == 8, K, S, ACT);
     const int cvn = a.out.c / V;
     const int owg = (a.out.w + px - 1) / px;
     const int64_t groups = int64_t(a.out.n) * a.out.h * owg;
@@ -239,16 +257,22 @@ hipError_t launch_fast(const DwArgs& a, int px, hipStream_t stream) {
     const int64_t blocks = (int64_t(cvn) * nslots + kDwBlock - 1) / kDwBlock;
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
     const dim3 grid = dim3(unsigned(blocks)), block = dim3(kDwBlock);
-    if (px == 1) conv_dw_kernel<T, K, S, 1><<<grid, block, 0, stream>>>(a, cvn, owg, groups, nslots);
-    else if (px == 2) conv_dw_kernel<T, K, S, 2><<<grid, block, 0, stream>>>(a, cvn, owg, groups, nslots);
-    else conv_dw_kernel<T, K, S, 4><<<grid, block, 0, stream>>>(a, cvn, owg, groups, nslots);
+    constexpr bool kPx2 = DwLanePixels(2, V == 8, K, S, ACT) == 2, kPx4 = DwLanePixels(4, V == 8, K, S, ACT) == 4;
+    if (px == 1) conv_dw_kernel<T, K, S, 1, ACT><<<grid, block, 0, stream>>>(a, cvn, owg, groups, nslots);
+    else if constexpr (!kPx2) return hipErrorInvalidValue;
+    else if (px == 2) conv_dw_kernel<T, K, S, 2, ACT><<<grid, block, 0, stream>>>(a, cvn, owg, groups, nslots);
+    else if constexpr (kPx4) conv_dw_kernel<T, K, S, 4, ACT><<<grid, block, 0, stream>>>(a, cvn, owg, groups, nslots);
     return hipGetLastError();
 }
 
+template <typename T, bool ACT>
+hipError_t launch_fast_a(const DwArgs& a, int px, hipStream_t stream) {
+    if (a.kh == 3) return a.sh == 1 ? launch_fast<T, 3, 1, ACT>(a, px, stream) : launch_fast<T, 3, 2, ACT>(a, px, stream);
+    return a.sh == 1 ? launch_fast<T, 5, 1, ACT>(a, px, stream) : launch_fast<T, 5, 2, ACT>(a, px, stream);
+}
 template <typename T>
 hipError_t launch_fast_t(const DwArgs& a, int px, hipStream_t stream) {
-    if (a.kh == 3) return a.sh == 1 ? launch_fast<T, 3, 1>(a, px, stream) : launch_fast<T, 3, 2>(a, px, stream);
-    return a.sh == 1 ? launch_fast<T, 5, 1>(a, px, stream) : launch_fast<T, 5, 2>(a, px, stream);
+    return a.act || a.pre_act ? launch_fast_a<T, true>(a, px, stream) : launch_fast_a<T, false>(a, px, stream);
 }
 
 }  // namespace

@@ -39,7 +39,7 @@ struct Val {
     bool dedicated = false;             // its buffer is never recycled
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -58,6 +58,12 @@ struct LNode {
     bool dw = false;                    // depthwise conv (group == Cin == Cout): w packed [C][kh][kw]
     float lo = -kInf, hi = kInf;        // Clip bounds (L_CLIP; a depthwise conv's epilogue clamp)
     float pre_hi = kInf;                // depthwise conv: upper bound of the prologue
+    Act act;                            // L_ACT; a depthwise conv's epilogue activation; L_SE: the gate's
+    Act pre_act;                        // depthwise conv / global pool: prologue activation
+    // L_SE: w = FC1 [mid][C], bias = its bias, w2 = FC2 transposed [mid][C], bias2 = [C]
+    std::vector<float> w2, bias2;
+    int se_mid = 0;
+    Act se_act1;
     bool dead = false;
 };
 
@@ -179,6 +185,18 @@ bool DwFastViews(const Step& s) {
 }
 // 4 output pixels per lane on wide rows, 2 on narrow ones (7x7 maps: 4 groups of 2 instead of 2 of 4, one wasted lane in eight), the generic kernel otherwise
 int DwDefaultTile(const Step& s) { return DwFastViews(s) ? (s.out.w >= 14 ? 3 : 2) : 0; }
+
+// Algorithmic FLOPs per element of a fused activation
+double ActFlops(ActKind k) {
+    switch (k) {
+        case ActKind::Sigmoid: return 3;       // exp, add, divide
+        case ActKind::HardSigmoid: return 3;   // fma, two clamps
+        case ActKind::Silu: return 4;
+        case ActKind::HardSwish: return 4;
+        case ActKind::Relu: return 1;
+        default: return 0;
+    }
+}
 
 int choose_tile(int64_t M, int64_t N) {
     // Estimated time = rounds over the 256 CUs x tile area / tile efficiency.  Larger tiles reuse operands
@@ -442,14 +460,35 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                     fail("Clip " + n.name + ": the " + (k == 1 ? "min" : "max") + " bound must be a floating-point scalar");
                 (k == 1 ? n.lo : n.hi) = b->f[0];
             }
+        } else if (op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish") {
+            n.kind = L_ACT;
+            if (op == "Sigmoid") n.act.kind = ActKind::Sigmoid;
+            else if (op == "HardSigmoid") { n.act.kind = ActKind::HardSigmoid; n.act.a = on.attr_f("alpha", 0.2f); n.act.b = on.attr_f("beta", 0.5f); }
+            else { n.act.kind = ActKind::HardSwish; n.act.a = 1.f / 6.f; n.act.b = 0.5f; }
+            if (!act_input(0)) fail(op + " " + n.name + ": constant input is not supported");
+            n.in = {in_val(0)};
+            odims = L.vals[n.in[0]].dims;
         } else if (op == "Relu") {
             n.kind = L_RELU;
             n.in = {in_val(0)};
             odims = L.vals[n.in[0]].dims;
-        } else if (op == "Add" || op == "Mul") {
+        } else if (op == "Add" || op == "Mul" || op == "Div") {
             bool a0 = act_input(0), a1 = act_input(1);
-            if (a0 && a1) {
-                if (op == "Mul") fail("Mul of two activations is not supported (node " + n.name + ")");
+            if (op == "Div" && (a1 || !a0)) fail("Div " + n.name + ": only the division of an activation by a constant is supported");
+            if (a0 && a1 && op == "Mul") {
+                // same shapes, or [N,C,H,W] x [N,C,1,1] in either order (a squeeze-excite gate); in[0] = the full tensor
+                int a = in_val(0), b = in_val(1);
+                const Val &A = L.vals[a], &Bv = L.vals[b];
+                const bool bcast_b = A.dims.size() == 4 && Bv.dims.size() == 4 && A.n == Bv.n && A.c == Bv.c && Bv.h == 1 && Bv.w == 1;
+                const bool bcast_a = A.dims.size() == 4 && Bv.dims.size() == 4 && A.n == Bv.n && A.c == Bv.c && A.h == 1 && A.w == 1;
+                if (A.dims != Bv.dims) {
+                    if (bcast_a && !bcast_b) std::swap(a, b);
+                    else if (!bcast_b) fail("Mul " + n.name + ": only same-shape activations or [N,C,H,W] x [N,C,1,1] broadcasting are supported between two activations");
+                }
+                n.kind = L_MUL;
+                n.in = {a, b};
+                odims = L.vals[a].dims;
+            } else if (a0 && a1) {
                 int a = in_val(0), b = in_val(1);
                 if (L.vals[a].dims != L.vals[b].dims) fail("Add " + n.name + ": broadcasting between activations is not supported");
                 n.kind = L_ADD;
@@ -476,6 +515,15 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 if (!ok) fail(op + " " + n.name + ": constant operand must broadcast per channel");
                 n.kind = L_AFFINE;
                 if (op == "Add") { n.s.assign(size_t(X.c), 1.f); n.t = pc; }
+                else if (op == "Div") {
+                    // x / c = x * (1 / c): an affine step like a Mul (hardswish exports that end in "/ 6")
+                    for (float& v : pc) {
+                        if (v == 0.f) fail("Div " + n.name + ": division by zero");
+                        v = 1.f / v;
+                    }
+                    n.s = pc;
+                    n.t.assign(size_t(X.c), 0.f);
+                }
                 else { n.s = pc; n.t.assign(size_t(X.c), 0.f); }
                 n.in = {x};
                 odims = X.dims;
@@ -579,7 +627,80 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         for (const LNode& n : L.nodes)
             if (n.dw) fail("depthwise convolution is not supported in fp8 mode (Conv " + n.name + ")");
 
+    if (precision == Precision::F8 || f8_fusions)
+        for (const LNode& n : L.nodes)
+            if (n.kind == L_ACT || n.kind == L_MUL)
+                fail("activation and squeeze-excite nodes (Sigmoid, HardSigmoid, HardSwish, Mul of two activations) are not supported in fp8 mode (node " + n.name + ")");
+
     auto single_consumer = [&](int v) { return !L.vals[v].is_output && L.consumers(v).size() == 1; };
+
+    // ---- activation patterns: Mul(x, Sigmoid(x)) = SiLU, Mul(x, HardSigmoid(x; a, b)) = hardswish(a, b) (opset < 14 exports), either order ----
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& mu = L.nodes[i];
+        if (mu.dead || mu.kind != L_MUL || L.vals[mu.in[0]].dims != L.vals[mu.in[1]].dims) continue;
+        for (int k = 0; k < 2; ++k) {
+            const int g = L.vals[mu.in[k]].producer, x = mu.in[1 - k];
+            if (g < 0 || L.nodes[g].dead || L.nodes[g].kind != L_ACT || L.nodes[g].in[0] != x || !single_consumer(mu.in[k])) continue;
+            LNode& sg = L.nodes[g];
+            if (sg.act.kind == ActKind::Sigmoid) mu.act.kind = ActKind::Silu;
+            else if (sg.act.kind == ActKind::HardSigmoid) { mu.act = sg.act; mu.act.kind = ActKind::HardSwish; }
+            else continue;
+            mu.kind = L_ACT;
+            mu.in = {x};
+            mu.name = sg.name + "+" + mu.name;
+            sg.dead = true;
+            break;
+        }
+    }
+    // ---- squeeze-excite: GlobalAveragePool -> Conv1x1 -> ReLU | act -> Conv1x1 -> act -> Mul(x, gate) as ONE node, where x is read by the pool
+    //      and the Mul only (IE_NO_SE_FUSE=1: the separate steps) ----
+    if (!env.get("IE_NO_SE_FUSE")) {
+        auto prod = [&](int v, LKind k) -> LNode* {
+            const int p = L.vals[v].producer;
+            if (p < 0 || L.nodes[p].dead || L.nodes[p].kind != k || !single_consumer(v)) return nullptr;
+            return &L.nodes[p];
+        };
+        auto fc_ok = [&](const LNode* c, int64_t cin, int64_t cout) {
+            return c && !c->dw && c->kh == 1 && c->kw == 1 && c->sh == 1 && c->sw == 1 && !c->pt && !c->pl && !c->pb && !c->pr && c->res < 0 &&
+                   L.vals[c->in[0]].dims.size() == 4 && L.vals[c->in[0]].c == cin && L.vals[c->out].c == cout && int64_t(c->w.size()) == cin * cout;
+        };
+        for (size_t i = 0; i < L.nodes.size(); ++i) {
+            LNode& mu = L.nodes[i];
+            if (mu.dead || mu.kind != L_MUL) continue;
+            const int x = mu.in[0];
+            const Val& X = L.vals[x];
+            if (X.dims.size() != 4 || L.vals[mu.in[1]].h * L.vals[mu.in[1]].w != 1 || X.h * X.w == 1 || X.is_output || X.is_input) continue;
+            LNode* gate = prod(mu.in[1], L_ACT);
+            LNode* c2 = gate ? prod(gate->in[0], L_CONV) : nullptr;
+            if (!c2) continue;
+            const int hv = c2->in[0];
+            const int64_t mid = L.vals[hv].c;
+            LNode* a1 = prod(hv, L_RELU);
+            if (!a1) a1 = prod(hv, L_ACT);
+            LNode* c1 = a1 ? prod(a1->in[0], L_CONV) : nullptr;
+            LNode* gp = c1 ? prod(c1->in[0], L_GAP) : nullptr;
+            if (!gp || gp->in[0] != x || !fc_ok(c1, X.c, mid) || !fc_ok(c2, mid, X.c)) continue;
+            const std::vector<int> readers = L.consumers(x);
+            if (readers.size() != 2) continue;
+            LNode se;
+            se.kind = L_SE;
+            se.name = gp->name + " ... " + mu.name;
+            se.in = {x};
+            se.out = mu.out;
+            se.w = c1->w;
+            se.bias = c1->bias;
+            se.w2.resize(c2->w.size());
+            for (int64_t o = 0; o < X.c; ++o)
+                for (int64_t j = 0; j < mid; ++j) se.w2[size_t(j * X.c + o)] = c2->w[size_t(o * mid + j)];
+            se.bias2 = c2->bias;
+            se.se_mid = int(mid);
+            if (a1->kind == L_RELU) se.se_act1.kind = ActKind::Relu;
+            else se.se_act1 = a1->act;
+            se.act = gate->act;
+            gp->dead = c1->dead = a1->dead = c2->dead = gate->dead = true;
+            mu = std::move(se);
+        }
+    }
 
     // ---- fusion 1: merge Affine->Affine chains (BN followed by Caffe-style Scale Mul/Add) ----------
     for (size_t i = 0; i < L.nodes.size(); ++i) {
@@ -606,10 +727,14 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         int64_t cout = L.vals[cv.out].c;
         size_t kper = cv.w.size() / size_t(cout);
         bool clamped = false;
-        while (single_consumer(cv.out) && !cv.relu && !clamped) {
+        while (single_consumer(cv.out) && !cv.relu && !clamped && cv.act.kind == ActKind::None) {
             int ci = L.consumers(cv.out)[0];
             LNode& b = L.nodes[ci];
-            if (b.kind == L_CLIP) {
+            if (b.kind == L_ACT) {
+                // only the depthwise kernel has an activation epilogue (an activation behind another conv: fusion 2d below, or an eltwise step)
+                if (!cv.dw) break;
+                cv.act = b.act;
+            } else if (b.kind == L_CLIP) {
                 // only the depthwise kernel has a clamp epilogue (a Clip behind another conv: see the ReLU6 pass below, or an eltwise step)
                 if (!cv.dw) break;
                 cv.lo = b.lo;
@@ -664,6 +789,33 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         d.pre_s.assign(size_t(L.vals[c.out].c), 1.f);
         d.pre_t.assign(size_t(L.vals[c.out].c), 0.f);
         c.dead = true;
+    }
+    // ---- fusion 2d: an activation between a conv and a depthwise conv (expand 1x1 -> BN -> act -> depthwise) goes into the depthwise conv's
+    //      prologue (the producer runs linear: no dense-conv kernel needs an activation epilogue); one in front of a global pool (head 1x1 ->
+    //      act -> GlobalAveragePool) into the pool's prologue.  Any other activation becomes an eltwise step. -------------------------------
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& a = L.nodes[i];
+        if (a.dead || a.kind != L_ACT || !single_consumer(a.out)) continue;
+        const int x = a.in[0];
+        LNode& d = L.nodes[L.consumers(a.out)[0]];
+        const int p = L.vals[x].producer;
+        if (d.kind == L_CONV && d.dw && !d.has_pre && d.in[0] == a.out && d.res != a.out && p >= 0 && !L.nodes[p].dead && L.nodes[p].kind == L_CONV &&
+            !L.nodes[p].dw && single_consumer(x)) {
+            LNode& cv = L.nodes[p];
+            cv.name += "+" + a.name;
+            cv.out = a.out;
+            L.vals[cv.out].producer = p;
+            d.has_pre = true;
+            d.pre_act = a.act;
+            d.pre_s.assign(size_t(L.vals[a.out].c), 1.f);
+            d.pre_t.assign(size_t(L.vals[a.out].c), 0.f);
+            a.dead = true;
+        } else if (d.kind == L_GAP && d.in[0] == a.out && d.pre_act.kind == ActKind::None && !d.has_pre) {
+            d.pre_act = a.act;
+            d.name = a.name + "+" + d.name;
+            d.in[0] = x;
+            a.dead = true;
+        }
     }
     // ---- fusion 2c: Conv1x1 -> AveragePool  ==>  AveragePool -> Conv1x1 ---------------------------------
     // Both are linear and a 1x1/stride-1 conv acts per pixel, so they commute (the conv's bias too: the mean of a constant is the
@@ -993,6 +1145,8 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                     s.algo = ConvAlgo::Depthwise;
                     s.lo = n.lo;
                     s.hi = n.hi;
+                    s.act = n.act;
+                    s.pre_act = n.pre_act;
                     s.flops = 2.0 * double(s.out.n) * double(s.out.c) * double(s.out.h) * double(s.out.w) * n.kh * n.kw;
                     s.bytes = vbytes(s.in) + vbytes(s.out) + 4.0 * double(n.w.size()) + (n.res >= 0 ? vbytes(s.in2) : 0.0);
                     s.tile = DwDefaultTile(s);
@@ -1222,9 +1376,41 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             case L_GAP:
                 if (s.in.f8 && (n.has_pre || s.out.f8)) fail("fp8 precision: global pool " + n.name + " with a prologue is not supported");
                 s.kind = StepKind::GlobalAvgPool;
+                s.pre_act = n.pre_act;
                 s.bytes = vbytes(s.in) + vbytes(s.out);
-                s.flops = double(s.in.numel());
+                s.flops = double(s.in.numel()) * (1.0 + ActFlops(n.pre_act.kind));
                 break;
+            case L_ACT:
+                s.kind = StepKind::Eltwise;
+                s.act = n.act;
+                s.bytes = vbytes(s.in) + vbytes(s.out);
+                s.flops = double(s.in.numel()) * ActFlops(n.act.kind);
+                break;
+            case L_MUL:
+                s.kind = StepKind::Eltwise;
+                s.in2 = view_of(n.in[1]);
+                s.has_in2 = true;
+                s.mul = true;
+                s.bytes = vbytes(s.in) + vbytes(s.in2) + vbytes(s.out);
+                s.flops = double(s.out.numel());
+                break;
+            case L_SE: {
+                s.kind = StepKind::SqueezeExcite;
+                s.w_off = push_vec(n.w);
+                if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
+                s.w2_off = push_vec(n.w2);
+                if (!n.bias2.empty()) s.bias2_off = push_vec(n.bias2);
+                s.se_mid = n.se_mid;
+                s.se_act1 = n.se_act1;
+                s.act = n.act;
+                s.se_chunks = SeSqueezeChunks(s.in.n, s.in.h * s.in.w);
+                plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, SeWorkspaceFloats(s.in.n, s.in.c, n.se_mid, s.se_chunks));
+                // squeeze (one add per element), the two FCs (2 x MACs, activations), the gate multiply; the input is read twice
+                const double nc = double(s.in.n) * double(s.in.c), nm = double(s.in.n) * n.se_mid;
+                s.flops = double(s.in.numel()) + 4.0 * nc * n.se_mid + nm * ActFlops(n.se_act1.kind) + nc * ActFlops(n.act.kind) + double(s.out.numel());
+                s.bytes = 2.0 * vbytes(s.in) + vbytes(s.out) + 4.0 * double(n.w.size() + n.w2.size() + n.bias.size() + n.bias2.size());
+                break;
+            }
             case L_AFFINE:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone scale/shift " + n.name + " on an fp8 tensor is not supported");
                 s.kind = StepKind::Eltwise;
@@ -1582,6 +1768,10 @@ static void json_view(std::ostringstream& o, const View& v) {
       << ",\"c_off\":" << v.c_off << ",\"pitch\":" << v.pitch << ",\"nchw\":" << (v.nchw ? "true" : "false")
       << ",\"f16\":" << (v.f16 ? "true" : "false") << ",\"f8\":" << (v.f8 ? "true" : "false") << "}";
 }
+static void json_act(std::ostringstream& o, const char* key, const Act& a) {
+    static const char* names[] = {"none", "sigmoid", "hardsigmoid", "silu", "hardswish", "relu"};
+    o << ",\"" << key << "\":[\"" << names[int(a.kind)] << "\"," << a.a << "," << a.b << "]";
+}
 static std::string json_escape(const std::string& s) {
     std::string o;
     for (char c : s) { if (c == '"' || c == '\\') o += '\\'; if (uint8_t(c) >= 0x20) o += c; }
@@ -1589,7 +1779,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite"};
     static const char* algos[] = {"igemm_vec", "igemm_scalar", "naive", "raster3x3", "ws1x1", "ws3x3", "stem", "direct", "igemm_f8", "dense_fused", "wino3x3", "conv1x1_x6", "dense_block", "dual_f8", "stem_pool", "depthwise"};
     std::ostringstream o;
     o.precision(17);
@@ -1629,6 +1819,15 @@ std::string PlanToJson(const Plan& p) {
             o << ",";
             if (s.hi < kInf) o << s.hi; else o << "null";
             o << "]";
+        }
+        // (only where set: the plans of graphs without these activations are unchanged)
+        if (s.act.kind != ActKind::None) json_act(o, "act", s.act);
+        if (s.pre_act.kind != ActKind::None) json_act(o, "pre_act", s.pre_act);
+        if (s.mul) o << ",\"mul\":true";
+        if (s.kind == StepKind::SqueezeExcite) {
+            o << ",\"se\":{\"mid\":" << s.se_mid << ",\"chunks\":" << s.se_chunks << ",\"w2_off\":" << s.w2_off << ",\"bias2_off\":" << s.bias2_off;
+            json_act(o, "act1", s.se_act1);
+            o << "}";
         }
         if (s.kind == StepKind::Conv) o << ",\"algo\":\"" << algos[int(s.algo)] << "\",\"tile\":" << s.tile << ",\"splitk\":" << s.splitk;
         if (s.kind == StepKind::Pool) o << ",\"max\":" << (s.pool_max ? "true" : "false");

@@ -38,7 +38,16 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5 };
+
+// Pointwise activation fused into a step (kernels.h ApplyAct): sigmoid(x), hardsigmoid(x) = max(0, min(1, a*x + b)), silu(x) = x * sigmoid(x),
+// hardswish(x) = x * hardsigmoid(x; a, b) (the ONNX HardSwish op: a = 1/6, b = 1/2).  Relu only as a squeeze-excite block's inner activation.
+enum class ActKind : int { None = 0, Sigmoid = 1, HardSigmoid = 2, Silu = 3, HardSwish = 4, Relu = 5 };
+struct Act {
+    ActKind kind = ActKind::None;
+    float a = 0.f, b = 0.f;
+    bool operator==(const Act& o) const { return kind == o.kind && a == o.a && b == o.b; }
+};
 
 // Conv algorithm chosen at plan time.
 enum class ConvAlgo : int {
@@ -82,6 +91,16 @@ struct Step {
     float pre_hi = __builtin_huge_valf();     // depthwise convs: the prologue's upper bound (a ReLU6 whose ReLU runs in the producer's epilogue)
     bool relu = false;         // applied to the result
     float lo = -__builtin_huge_valf(), hi = __builtin_huge_valf();   // then min(max(v, lo), hi): a Clip (depthwise conv epilogue / eltwise step)
+    Act act;                   // then this activation (depthwise conv epilogue / eltwise step); SqueezeExcite: the gate's activation
+    Act pre_act;               // prologue activation after pre_relu / pre_hi (depthwise conv: in-range taps only; global pool)
+    // Eltwise: in2 is a second operand multiplied (not added); in2 of [N, C, 1, 1] broadcasts over the pixels of `in`
+    bool mul = false;
+    // SqueezeExcite (kernels_se.hip): out = in * act(W2 * act1(W1 * mean_hw(in) + bias) + bias2); w_off = W1 [mid][C], bias_off = its bias [mid],
+    // w2_off = W2 transposed [mid][C], bias2_off = [C], all fp32 in every precision; the squeeze partials and the [N, C] gate live in the workspace
+    int se_mid = 0;
+    Act se_act1;
+    int64_t w2_off = -1, bias2_off = -1;
+    int se_chunks = 0;         // pixel chunks of the squeeze (kernels.h SeSqueezeChunks)
     ConvAlgo algo = ConvAlgo::Naive;
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)
     int base_tile = 0;         // the tiled implicit GEMM's heuristic tile (what the executor falls back to when a specialised launcher declines)

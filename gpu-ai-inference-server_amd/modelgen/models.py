@@ -1,4 +1,4 @@
-"""Synthetic ONNX model builders (DenseNet-121, ResNet-50, MobileNetV2 and small test graphs).
+"""Synthetic ONNX model builders (DenseNet-121, ResNet-50, MobileNetV2, MobileNetV3, EfficientNet-B0 and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -101,6 +101,61 @@ class GraphBuilder:
         name = self._uid("relu")
         self.nodes.append(pb.node("Relu", [x], [name + "_out"], name))
         return name + "_out"
+
+    # ---- activations (MobileNetV3 / EfficientNet) ----
+    def sigmoid(self, x: str) -> str:
+        return self.simple("Sigmoid", [x])
+
+    def hardsigmoid(self, x: str, alpha: float = 0.2, beta: float = 0.5) -> str:
+        return self.simple("HardSigmoid", [x], [pb.attr_float("alpha", alpha), pb.attr_float("beta", beta)])
+
+    def hardswish(self, x: str, form: str = "op") -> str:
+        """x * hardsigmoid(x; 1/6, 1/2) in the forms exporters write:
+          "op"               the HardSwish operator (opset >= 14)
+          "hardsigmoid_mul"  Mul(x, HardSigmoid(x))  (torch's export below opset 14)
+          "mul_hardsigmoid"  Mul(HardSigmoid(x), x)  (the same, operands swapped)
+        """
+        if form == "op":
+            return self.simple("HardSwish", [x])
+        g = self.hardsigmoid(x, 1.0 / 6.0, 0.5)
+        if form == "hardsigmoid_mul":
+            return self.simple("Mul", [x, g])
+        if form == "mul_hardsigmoid":
+            return self.simple("Mul", [g, x])
+        raise ValueError(form)
+
+    def silu(self, x: str, swap: bool = False) -> str:
+        """SiLU as exporters write it: Mul(x, Sigmoid(x)) (swap: Mul(Sigmoid(x), x))."""
+        g = self.sigmoid(x)
+        return self.simple("Mul", [g, x] if swap else [x, g])
+
+    def act(self, x: str, kind: str, form: str = "op") -> str:
+        """kind: relu | hardswish | silu | sigmoid | hardsigmoid | relu6 | none"""
+        if kind == "relu":
+            return self.relu(x)
+        if kind == "hardswish":
+            return self.hardswish(x, form)
+        if kind == "silu":
+            return self.silu(x, swap=form == "mul_hardsigmoid")
+        if kind == "sigmoid":
+            return self.sigmoid(x)
+        if kind == "hardsigmoid":
+            return self.hardsigmoid(x, 1.0 / 6.0, 0.5)
+        if kind == "relu6":
+            return self.clip(x, 0.0, 6.0)
+        if kind == "none":
+            return x
+        raise ValueError(kind)
+
+    def se(self, x: str, c: int, mid: int, act1: str = "relu", gate: str = "hardsigmoid", name: str | None = None, swap: bool = False,
+           form: str = "op") -> str:
+        """Squeeze-and-excitation: GlobalAveragePool -> Conv1x1(+bias) C -> mid -> act1 -> Conv1x1(+bias) mid -> C -> gate -> Mul(x, gate)
+        (swap: Mul(gate, x))."""
+        name = name or self._uid("se")
+        s = self.gap(x)
+        s = self.act(self.conv(s, c, mid, 1, bias=True, name=name + "_fc1", w_scale=float(np.sqrt(1.0 / c))), act1, form)
+        s = self.act(self.conv(s, mid, c, 1, bias=True, name=name + "_fc2", w_scale=float(np.sqrt(1.0 / mid))), gate, form)
+        return self.simple("Mul", [s, x] if swap else [x, s])
 
     def concat(self, xs: Sequence[str], axis: int = 1) -> str:
         name = self._uid("concat")
@@ -376,6 +431,102 @@ def mobilenet_v2(batch: int | str = 1, *, width_mult: float = 1.0, image: int = 
     gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))],
               [pb.attr_int("transB", 1)], out=out_name)
     return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=6 if clip_form == "attrs" else 11)
+
+
+# torchvision's MobileNetV3 tables (Howard et al. 2019, Tables 1-2): input channels, kernel, expanded channels, output channels, SE, activation, stride
+MOBILENET_V3_LARGE = ((16, 3, 16, 16, False, "RE", 1), (16, 3, 64, 24, False, "RE", 2), (24, 3, 72, 24, False, "RE", 1),
+                      (24, 5, 72, 40, True, "RE", 2), (40, 5, 120, 40, True, "RE", 1), (40, 5, 120, 40, True, "RE", 1),
+                      (40, 3, 240, 80, False, "HS", 2), (80, 3, 200, 80, False, "HS", 1), (80, 3, 184, 80, False, "HS", 1),
+                      (80, 3, 184, 80, False, "HS", 1), (80, 3, 480, 112, True, "HS", 1), (112, 3, 672, 112, True, "HS", 1),
+                      (112, 5, 672, 160, True, "HS", 2), (160, 5, 960, 160, True, "HS", 1), (160, 5, 960, 160, True, "HS", 1))
+MOBILENET_V3_SMALL = ((16, 3, 16, 16, True, "RE", 2), (16, 3, 72, 24, False, "RE", 2), (24, 3, 88, 24, False, "RE", 1),
+                      (24, 5, 96, 40, True, "HS", 2), (40, 5, 240, 40, True, "HS", 1), (40, 5, 240, 40, True, "HS", 1),
+                      (40, 5, 120, 48, True, "HS", 1), (48, 5, 144, 48, True, "HS", 1), (48, 5, 288, 96, True, "HS", 2),
+                      (96, 5, 576, 96, True, "HS", 1), (96, 5, 576, 96, True, "HS", 1))
+
+
+def mobilenet_v3(batch: int | str = 1, *, variant: str = "large", width_mult: float = 1.0, image: int = 224, classes: int = 1000, seed: int = 73,
+                 act_form: str = "op", in_name: str = "data", out_name: str = "logits") -> bytes:
+    """MobileNetV3-Large / -Small as torchvision builds them: conv3x3/s2 (16) -> BN -> hardswish -> inverted-residual blocks [expand 1x1 -> BN ->
+    act ->] depthwise k x k (stride s) -> BN -> act [-> SE: squeeze make_divisible(exp // 4, 8), ReLU, hardsigmoid] -> project 1x1 -> BN (+ identity
+    where the stride is 1 and the channel count is kept) -> conv1x1 (6 x last block channels) -> BN -> hardswish -> global pool -> Flatten ->
+    Gemm -> hardswish -> Dropout -> Gemm.  act_form: how HardSwish / HardSigmoid reach the graph (GraphBuilder.hardswish); the SE gate's
+    HardSigmoid is the operator itself in every form.  Projection BNs get a small gamma so activations stay O(1) through the residual adds."""
+    table = {"large": MOBILENET_V3_LARGE, "small": MOBILENET_V3_SMALL}[variant]
+    last_channel = {"large": 1280, "small": 1024}[variant]
+    gb = GraphBuilder("mobilenet_v3_" + variant, seed)
+
+    def act(x: str, kind: str) -> str:
+        return gb.relu(x) if kind == "RE" else gb.hardswish(x, act_form)
+    ch = lambda v: _divisible8(v * width_mult)  # noqa: E731
+    c = ch(16)
+    x = act(gb.bn(gb.conv(in_name, 3, c, 3, stride=2, pad=1, name="stem"), c, name="stem_bn"), "HS")
+    for bi, (cin, k, exp, cout, use_se, a, s) in enumerate(table, 1):
+        tag = f"b{bi}"
+        cin, exp, cout = ch(cin), ch(exp), ch(cout)
+        assert cin == c
+        y = x
+        if exp != cin:
+            y = act(gb.bn(gb.conv(y, cin, exp, 1, name=tag + "_expand"), exp, name=tag + "_bn1"), a)
+        y = act(gb.bn(gb.conv(y, exp, exp, k, stride=s, pad=k // 2, group=exp, name=tag + "_dw"), exp, name=tag + "_bn2"), a)
+        if use_se:
+            y = gb.se(y, exp, _divisible8(exp // 4), "relu", "hardsigmoid", name=tag + "_se")
+        y = gb.bn(gb.conv(y, exp, cout, 1, name=tag + "_project"), cout, name=tag + "_bn3", g_center=0.3)
+        if s == 1 and cin == cout:
+            y = gb.simple("Add", [y, x])
+        x, c = y, cout
+    head = 6 * c
+    x = act(gb.bn(gb.conv(x, c, head, 1, name="head"), head, name="head_bn"), "HS")
+    x = gb.simple("Flatten", [gb.gap(x)], [pb.attr_int("axis", 1)])
+    w1 = rng.gaussish(seed, "fc1_w", last_channel * head).reshape(last_channel, head) * np.float32(np.sqrt(2.0 / head))
+    b1 = (rng.uniform(seed, "fc1_b", last_channel) - np.float32(0.5)) * np.float32(0.2)
+    x = gb.simple("Gemm", [x, gb.init("fc1_w", w1.astype(np.float32)), gb.init("fc1_b", b1.astype(np.float32))], [pb.attr_int("transB", 1)])
+    x = gb.simple("Dropout", [gb.hardswish(x, act_form)])
+    w2 = rng.gaussish(seed, "fc2_w", classes * last_channel).reshape(classes, last_channel) * np.float32(np.sqrt(1.0 / last_channel))
+    b2 = (rng.uniform(seed, "fc2_b", classes) - np.float32(0.5)) * np.float32(0.2)
+    gb.simple("Gemm", [x, gb.init("fc2_w", w2.astype(np.float32)), gb.init("fc2_b", b2.astype(np.float32))], [pb.attr_int("transB", 1)], out=out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=14 if act_form == "op" else 13)
+
+
+# torchvision's EfficientNet-B0 stages (Tan & Le 2019, Table 1): expand ratio, kernel, first stride, input channels, output channels, layers
+EFFICIENTNET_B0 = ((1, 3, 1, 32, 16, 1), (6, 3, 2, 16, 24, 2), (6, 5, 2, 24, 40, 2), (6, 3, 2, 40, 80, 3), (6, 5, 1, 80, 112, 3),
+                   (6, 5, 2, 112, 192, 4), (6, 3, 1, 192, 320, 1))
+
+
+def efficientnet_b0(batch: int | str = 1, *, width_mult: float = 1.0, image: int = 224, classes: int = 1000, seed: int = 80, swap_mul: bool = False,
+                    in_name: str = "data", out_name: str = "logits") -> bytes:
+    """EfficientNet-B0 as torchvision builds it: conv3x3/s2 (32) -> BN -> SiLU -> MBConv blocks [expand 1x1 -> BN -> SiLU ->] depthwise k x k ->
+    BN -> SiLU -> SE (squeeze = block input channels // 4, SiLU, sigmoid) -> project 1x1 -> BN (+ identity where the stride is 1 and the
+    channel count is kept) -> conv1x1 (1280) -> BN -> SiLU -> global pool -> Flatten -> Gemm.  SiLU is Mul(x, Sigmoid(x)) (swap_mul: Mul(Sigmoid(x), x),
+    and the SE gate Mul with its operands swapped)."""
+    gb = GraphBuilder("efficientnet_b0", seed)
+    ch = lambda v: _divisible8(v * width_mult)  # noqa: E731
+    c = ch(32)
+    x = gb.silu(gb.bn(gb.conv(in_name, 3, c, 3, stride=2, pad=1, name="stem"), c, name="stem_bn"), swap_mul)
+    bi = 0
+    for t, k, s, cin, cout, n in EFFICIENTNET_B0:
+        cout = ch(cout)
+        for i in range(n):
+            bi += 1
+            tag = f"b{bi}"
+            stride = s if i == 0 else 1
+            exp = c * t
+            y = x
+            if t != 1:
+                y = gb.silu(gb.bn(gb.conv(y, c, exp, 1, name=tag + "_expand"), exp, name=tag + "_bn1"), swap_mul)
+            y = gb.silu(gb.bn(gb.conv(y, exp, exp, k, stride=stride, pad=k // 2, group=exp, name=tag + "_dw"), exp, name=tag + "_bn2"), swap_mul)
+            y = gb.se(y, exp, max(1, c // 4), "silu", "sigmoid", name=tag + "_se", swap=swap_mul, form="mul_hardsigmoid" if swap_mul else "op")
+            y = gb.bn(gb.conv(y, exp, cout, 1, name=tag + "_project"), cout, name=tag + "_bn3", g_center=0.3)
+            if stride == 1 and c == cout:
+                y = gb.simple("Add", [y, x])
+            x, c = y, cout
+    head = 4 * c
+    x = gb.silu(gb.bn(gb.conv(x, c, head, 1, name="head"), head, name="head_bn"), swap_mul)
+    x = gb.simple("Flatten", [gb.gap(x)], [pb.attr_int("axis", 1)])
+    wfc = rng.gaussish(seed, "fc_w", classes * head).reshape(classes, head) * np.float32(np.sqrt(1.0 / head))
+    bfc = (rng.uniform(seed, "fc_b", classes) - np.float32(0.5)) * np.float32(0.2)
+    gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))], [pb.attr_int("transB", 1)], out=out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=13)
 
 
 def write_repo(root: str, name: str, model_bytes: bytes, version: str = "1", config_json: str | None = None) -> str:

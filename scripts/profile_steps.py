@@ -2,11 +2,13 @@
 """Per-step timing table of a plan (HIP events around each launch, eager mode).
 
     python scripts/profile_steps.py [batch] [model]      model: a bench.py model (densenet121, resnet50) or any other modelgen builder
-                                                          (mobilenet_v2), written to its own repository under IE_BENCH_MODEL_ROOT
+                                                          (mobilenet_v2, mobilenet_v3_large, mobilenet_v3_small, efficientnet_b0), written to
+                                                          its own repository under IE_BENCH_MODEL_ROOT
 
 For a graph with depthwise convolutions it also prints the device-resident graph-replay time of the whole forward, the algorithmic GB/s of
 every depthwise step against the 6.29 TB/s measured copy rate, and torch's own F.conv2d(groups=C) on channels_last tensors for the same
-shapes as a yardstick (IE_PRECISION=fp16: half tensors)."""
+shapes as a yardstick (IE_PRECISION=fp16: half tensors).  For squeeze-excite steps likewise: their share of the eager forward, their algorithmic
+GB/s (the input read twice, the output written once) and torch's mean + two 1x1 convs + sigmoid + mul on channels_last tensors per SE shape."""
 import json
 import os
 import subprocess
@@ -48,6 +50,30 @@ for n, c, h, w, k, st, pd in json.loads(sys.argv[1]):
 print(json.dumps(out))
 """
 
+# torch's SE: mean over H, W -> 1x1 conv (+bias) -> ReLU -> 1x1 conv (+bias) -> sigmoid -> x * gate, for each [n, c, h, w, mid]
+TORCH_SE = """
+import json, sys, torch
+import torch.nn.functional as F
+dt = torch.float16 if sys.argv[2] == "fp16" else torch.float32
+out = []
+for n, c, h, w, mid in json.loads(sys.argv[1]):
+    x = torch.randn(n, c, h, w, device="cuda", dtype=dt).to(memory_format=torch.channels_last)
+    w1, b1 = torch.randn(mid, c, 1, 1, device="cuda", dtype=dt), torch.randn(mid, device="cuda", dtype=dt)
+    w2, b2 = torch.randn(c, mid, 1, 1, device="cuda", dtype=dt), torch.randn(c, device="cuda", dtype=dt)
+    f = lambda: x * torch.sigmoid(F.conv2d(torch.relu(F.conv2d(x.mean((2, 3), keepdim=True), w1, b1)), w2, b2))
+    for _ in range(5):
+        f()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        f()
+    e1.record()
+    torch.cuda.synchronize()
+    out.append(e0.elapsed_time(e1) / 20)
+print(json.dumps(out))
+"""
+BUILDERS = {"mobilenet_v3_large": lambda: models.mobilenet_v3("N", variant="large"), "mobilenet_v3_small": lambda: models.mobilenet_v3("N", variant="small")}
+
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 model_name = sys.argv[2] if len(sys.argv) > 2 else "densenet121"
 if model_name in bench.MODELS:
@@ -56,7 +82,7 @@ else:
     root = os.environ.get("IE_BENCH_MODEL_ROOT", "/tmp/ie_bench_models")
     mdir = os.path.join(root, model_name, "1")
     if not os.path.exists(os.path.join(mdir, "model.onnx")):
-        models.write_repo(root, model_name, getattr(models, model_name)("N"))
+        models.write_repo(root, model_name, BUILDERS[model_name]() if model_name in BUILDERS else getattr(models, model_name)("N"))
 plan = B.DescribeModel(mdir, batch)["plan"]
 m = B.CreateModel(mdir, os.path.basename(os.path.dirname(mdir)))
 din, dout = B.Prepare(m, [[batch, 3, 224, 224]], 1)
@@ -72,7 +98,8 @@ for i, (p, s) in enumerate(zip(prof, plan["steps"])):
     print(f"{i:3d} {p['kernel']:34} {M:7d} {s['out']['c']:5d} {K:5d} {p['ms']:8.4f} {p['flops']/p['ms']/1e9:7.2f} {p['bytes']/p['ms']/1e6:7.0f}  {p['name'][:40]}")
 
 dws = [(p, s) for p, s in zip(prof, plan["steps"]) if s.get("algo") == "depthwise"]
-if dws:
+ses = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "squeeze_excite"]
+if dws or ses:
     import time
     B.RunPrepared(m, 10, True)
     t0 = time.perf_counter()
@@ -92,4 +119,17 @@ if dws:
         gbs = p["bytes"] / p["ms"] / 1e6
         shape = f"{s['in']['h']}x{s['in']['w']}x{s['in']['c']}"
         print(f"{p['name'][:40]:40} {shape:>14} {s['stride'][0]:2d} {p['ms']:8.4f} {gbs:7.0f} {gbs / 6290 * 100:6.1f}% {t:9.4f}")
+if ses:
+    se_ms = sum(p["ms"] for p, _ in ses)
+    print(f"# {len(ses)} squeeze-excite steps: {se_ms:.4f} ms, {se_ms / tot * 100:.1f}% of the eager forward")
+    shapes = [[s["in"]["n"], s["in"]["c"], s["in"]["h"], s["in"]["w"], s["se"]["mid"]] for _, s in ses]
+    child = subprocess.run([sys.executable, "-c", TORCH_SE, json.dumps(shapes), plan["precision"]], capture_output=True, text=True, timeout=300)
+    tms = json.loads(child.stdout.strip().splitlines()[-1]) if child.returncode == 0 else [float("nan")] * len(ses)
+    if child.returncode != 0:
+        print("# torch yardstick failed:", child.stderr.strip().splitlines()[-1:])
+    print(f"{'squeeze-excite step':40} {'HxWxC/mid':>16} {'chunks':>6} {'ms':>8} {'GB/s':>7} {'%6.29T':>7} {'torch ms':>9}")
+    for (p, s), t in zip(ses, tms):
+        gbs = p["bytes"] / p["ms"] / 1e6
+        shape = f"{s['in']['h']}x{s['in']['w']}x{s['in']['c']}/{s['se']['mid']}"
+        print(f"{p['name'][:40]:40} {shape:>16} {s['se']['chunks']:6d} {p['ms']:8.4f} {gbs:7.0f} {gbs / 6290 * 100:6.1f}% {t:9.4f}")
 m.Destroy()
