@@ -23,6 +23,7 @@ const char* const kNames[] = {
     // ---- planner -----------------------------------------------------------------------------------------------------------------
     "IE_NO_POOL_SWAP", "IE_NO_DENSE_FUSE", "IE_NO_DENSE_BLOCK", "IE_DENSE_BAND", "IE_NO_DUAL_F8", "IE_NO_STEM_POOL", "IE_FUSE_MAX_M", "IE_FUSE_PB",
     "IE_NO_SE_FUSE",           // 1: squeeze-excite blocks as separate steps (global pool, two 1x1 convs, eltwise activation and gate Mul)
+    "IE_GROUPED_CONV",         // 1: plan convs with 1 < group (not depthwise) as grouped steps (kernels_grouped.hip); unset: they are refused
     "IE_FORCE_ALGO", "IE_FORCE_TILE", "IE_FORCE_SPLITK",      // tests: pin the kernel family / tile / split-K of every conv
     // ---- executor ----------------------------------------------------------------------------------------------------------------
     "IE_AUTOTUNE", "IE_TUNE_CACHE", "IE_TUNE_BATCHES", "IE_TUNE_ON_DEMAND", "IE_TUNE_HOT", "IE_TUNE_LOG",

@@ -108,7 +108,7 @@ constexpr TuneFamily kTuneFamilies[] = {
     {200, ConvAlgo::Ws1x1, std::max(kNumConvWs16Tiles, kNumConvWs32Tiles)},
     {300, ConvAlgo::Ws3x3, kNumConvWs3Tiles},         {400, ConvAlgo::Direct, kNumConvDirectTiles},
     {500, ConvAlgo::Wino3x3, kNumConvWinoTiles},      {600, ConvAlgo::X6, kNumConvX6Tiles},
-    {700, ConvAlgo::Depthwise, kNumConvDwTiles},
+    {700, ConvAlgo::Depthwise, kNumConvDwTiles},      {800, ConvAlgo::Grouped, kNumConvGroupedTiles},
 };
 
 const TuneFamily& tune_family(int code) {
@@ -283,7 +283,7 @@ void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<
                     // fragment-major mirror of the dense-layer convs (1x1 -> 128 and 3x3 128 -> 32 channels), whatever step they are part of in
                     // this plan instance: the weights are shared by every plan instance, another batch size may fuse other layers
                     auto add16 = [&](const Step& st) {
-                        if (st.kind != StepKind::Conv || st.algo == ConvAlgo::Depthwise || st.w_off < 0 || st.in.nchw || st.sh != 1 || st.sw != 1) return;
+                        if (st.kind != StepKind::Conv || IsGroupConv(st.algo) || st.w_off < 0 || st.in.nchw || st.sh != 1 || st.sw != 1) return;
                         const bool one = st.kh == 1 && st.kw == 1 && st.out.c == 128 && st.in.c % 32 == 0;
                         const bool three = st.kh == 3 && st.kw == 3 && st.out.c == 32 && st.in.c == 128;
                         if (one || three) w_->frag16_regions.push_back({st.w_off, int(st.out.c), int(st.kh * st.kw * st.in.c)});
@@ -319,7 +319,7 @@ void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<
                 }
             } else if (const char* nf = env_.get("IE_NO_FRAG_WEIGHTS"); !(nf && std::atoi(nf) != 0)) {
                 auto add_region = [&](const Step& st) {
-                    if (st.kind == StepKind::Conv && st.algo != ConvAlgo::Depthwise && st.w_off >= 0 && st.out.c % 16 == 0 && st.in.c % 16 == 0 && st.kh * st.kw <= 49)
+                    if (st.kind == StepKind::Conv && !IsGroupConv(st.algo) && st.w_off >= 0 && st.out.c % 16 == 0 && st.in.c % 16 == 0 && st.kh * st.kw <= 49)
                         w_->frag_regions.push_back({st.w_off, int(st.out.c), st.kh * st.kw, int(st.in.c)});
                 };
                 for (const Step& st : pi.plan.steps) {
@@ -335,7 +335,7 @@ void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<
                 // shared by all plan instances, and another batch size fuses other layers)
                 int64_t utot = 0;
                 auto add_wino = [&](const Step& st) {
-                    if (st.kind == StepKind::Conv && st.algo != ConvAlgo::Depthwise && st.w_off >= 0 && st.kh == 3 && st.kw == 3 && st.sh == 1 && st.sw == 1 && st.pt == 1 && st.pl == 1 &&
+                    if (st.kind == StepKind::Conv && !IsGroupConv(st.algo) && st.w_off >= 0 && st.kh == 3 && st.kw == 3 && st.sh == 1 && st.sw == 1 && st.pt == 1 && st.pl == 1 &&
                         st.out.c == 32 && st.in.c % 32 == 0 && !st.in.nchw) {
                         w_->wino_regions.push_back({st.w_off, utot, 32, int(st.in.c)});
                         utot += int64_t(16) * 32 * st.in.c;
@@ -356,7 +356,7 @@ void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<
                 if (split) {
                     int64_t xtot = 0;
                     auto add_x6 = [&](const Step& st) {
-                        if (st.kind == StepKind::Conv && st.algo != ConvAlgo::Depthwise && st.w_off >= 0 && st.kh == 1 && st.kw == 1 && st.sh == 1 && st.sw == 1 && st.out.c % 128 == 0 && st.in.c % 32 == 0 &&
+                        if (st.kind == StepKind::Conv && !IsGroupConv(st.algo) && st.w_off >= 0 && st.kh == 1 && st.kw == 1 && st.sh == 1 && st.sw == 1 && st.out.c % 128 == 0 && st.in.c % 32 == 0 &&
                             !st.in.nchw) {
                             w_->x6_regions.push_back({st.w_off, xtot, int(st.out.c), int(st.in.c)});
                             xtot += int64_t(3) * st.out.c * st.in.c * 2;
@@ -968,6 +968,25 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
         ctx.store(key, tune_code(ConvAlgo::Depthwise, best_t), 1);
         return;
     }
+    if (s.algo == ConvAlgo::Grouped) {
+        // the generic kernel and the channel-block variants (tune-file codes 800 + tile); nothing else may run a grouped conv
+        const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, s.group, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch,
+                                          s.out.pitch, s.in.nchw ? 2 : int64_t(s.in.f16), int64_t(ConvAlgo::Grouped), s.pre_scale_off >= 0, s.has_in2};
+        if (ctx.lookup(key, &hit)) {
+            if (tune_family(hit.first).algo == ConvAlgo::Grouped) s.tile = hit.first - tune_family(hit.first).base;
+            return;
+        }
+        if (!ctx.allow_search) return;
+        const GroupedArgs a = MakeGroupedArgs(pi, s);
+        float best = 1e30f;
+        int best_t = s.tile;
+        for (int t = 0; t < kNumConvGroupedTiles; ++t)
+            if (ConvGroupedEligible(a, t))
+                if (const float ms = time_tile(t); ms < best) { best = ms; best_t = t; }
+        s.tile = best_t;
+        ctx.store(key, tune_code(ConvAlgo::Grouped, best_t), 1);
+        return;
+    }
     const int64_t M = s.out.n * s.out.h * s.out.w, N = s.out.c;
     if (s.algo == ConvAlgo::IgemmF8) {
         // fp8 convs: the tiled implicit GEMM's tiles, then the weights-stationary 1x1 kernel's, then the 3x3's
@@ -1253,6 +1272,14 @@ DwArgs DeviceModel::MakeDwArgs(const PlanInstance& pi, const Step& s) const {
     return a;
 }
 
+GroupedArgs DeviceModel::MakeGroupedArgs(const PlanInstance& pi, const Step& s) const {
+    GroupedArgs a;
+    static_cast<DwArgs&>(a) = MakeDwArgs(pi, s);
+    a.w16 = w_->d_weights16 && s.w_off >= 0 ? static_cast<const char*>(w_->d_weights16) + s.w_off * 2 : nullptr;
+    a.groups = s.group;
+    return a;
+}
+
 SeArgs DeviceModel::MakeSeArgs(const PlanInstance& pi, const Step& s) const {
     const float* wb = w_->d_weights;
     auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
@@ -1294,6 +1321,12 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
                 // a variant that declines these operands (alignment) hands the step to the generic kernel, which takes every depthwise conv
                 const DwArgs a = MakeDwArgs(pi, s);
                 check(LaunchConvDw(a, ConvDwEligible(a, s.tile) ? s.tile : 0, stream_), "conv_dw");
+                break;
+            }
+            if (s.algo == ConvAlgo::Grouped) {
+                // a variant that declines these operands (alignment) hands the step to the generic kernel, which takes every grouped conv
+                const GroupedArgs a = MakeGroupedArgs(pi, s);
+                check(LaunchConvGrouped(a, ConvGroupedEligible(a, s.tile) ? s.tile : 0, stream_), "conv_grouped");
                 break;
             }
             if (s.algo == ConvAlgo::StemPool) {
@@ -1458,6 +1491,13 @@ static std::string kernel_label(const Step& s) {
                 return s.tile == 0 ? std::string("conv_dw_generic_kernel")
                                    : std::string("conv_dw_kernel<") + (s.out.f16 ? "f16,k" : "f32,k") + std::to_string(s.kh) + ",s" + std::to_string(s.sh) + ",px" +
                                          std::to_string(DwLanePixels(px[s.tile], s.out.f16, s.kh, s.sh, act)) + (act ? ",act>" : ">");
+            }
+            if (s.algo == ConvAlgo::Grouped) {
+                const int cfg = GroupedCfgFor(s.in.c, s.out.c, s.group);
+                if (s.tile == 0 || cfg < 0) return "conv_grouped_generic_kernel";
+                const GroupedCfg& c = kGroupedCfgs[cfg];
+                return std::string("conv_grouped_kernel<") + (s.out.f16 ? "f16,c" : "f32,c") + std::to_string(c.cpg) + ",o" + std::to_string(c.opb) + "x" +
+                       std::to_string(c.gpb) + ",px" + std::to_string(kGroupedPx[s.tile]) + ">";
             }
             if (s.algo == ConvAlgo::DenseBlock) return s.tile != 0 ? "dense_block_f16_kernel<" + std::to_string(s.parts.size() / 2) + " layers>" : "dense_block_parts<" + std::to_string(s.parts.size()) + " launches>";
             if (s.algo == ConvAlgo::DenseFused) return (s.tile >= 4 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";

@@ -185,6 +185,7 @@ private:
     void LaunchStep(const PlanInstance& pi, const Step& s, hipStream_t stream);
     ConvArgs MakeConvArgs(const PlanInstance& pi, const Step& s) const;
     DwArgs MakeDwArgs(const PlanInstance& pi, const Step& s) const;
+    GroupedArgs MakeGroupedArgs(const PlanInstance& pi, const Step& s) const;
     SeArgs MakeSeArgs(const PlanInstance& pi, const Step& s) const;
     bool MakeBlockArgs(const PlanInstance& pi, const Step& s, DenseBlockArgs* out) const;   // false: the step is not a well-formed dense-block chain
 

@@ -125,6 +125,41 @@ constexpr int DwLanePixels(int px, bool f16, int k, int s, bool act) {
 bool ConvDwEligible(const DwArgs& a, int tile);
 hipError_t LaunchConvDw(const DwArgs& a, int tile, hipStream_t stream);
 
+// Grouped conv (1 < group, not depthwise; kernels_grouped.hip): the DwArgs epilogue / prologue with output channel o reading the input channels
+// [(o / (Cout / groups)) * (Cin / groups), + Cin / groups).  w is [Cout][kh][kw][Cin / groups].
+struct GroupedArgs : DwArgs {
+    const void* w16 = nullptr;         // the same weights as halfs at the same element offsets (fp16 plans), or null
+    int groups = 1;
+};
+// The fast kernel's per-wave channel blocks: gpb whole groups of opb output channels (opb == Cout / groups), or, with gpb == 1, a slice of opb
+// output channels of one group (opb divides Cout / groups); the wave reads the cpg * gpb input channels of its groups.
+struct GroupedCfg { int cpg, opb, gpb; };
+inline constexpr GroupedCfg kGroupedCfgs[] = {{1, 2, 8}, {2, 2, 8}, {4, 4, 4}, {8, 8, 2}, {8, 8, 1}, {16, 16, 1}, {32, 16, 1}, {64, 16, 1}};
+inline constexpr int kNumGroupedCfgs = int(sizeof(kGroupedCfgs) / sizeof(kGroupedCfgs[0]));
+// tile 0: generic (one output element per thread; any group, k <= 7, stride, padding, NCHW input, mixed element types); tiles 1-3: the
+// channel-block kernel with 1 / 2 / 4 output pixels per lane
+constexpr int kNumConvGroupedTiles = 4;
+inline constexpr int kGroupedPx[kNumConvGroupedTiles] = {0, 1, 2, 4};
+// the fast config of a conv (-1: none; the generic kernel runs it)
+constexpr int GroupedCfgFor(int64_t cin, int64_t cout, int64_t groups) {
+    if (groups < 2 || cin % groups || cout % groups) return -1;
+    const int64_t cpg = cin / groups, opg = cout / groups;
+    for (int i = 0; i < kNumGroupedCfgs; ++i) {
+        const GroupedCfg& c = kGroupedCfgs[i];
+        if (c.cpg == cpg && (c.gpb > 1 ? opg == c.opb && groups % c.gpb == 0 : opg % c.opb == 0)) return i;
+    }
+    return -1;
+}
+// a lane's accumulators and input registers (px pixels: px * (outputs + inputs), halfs packed in pairs) stay within 128 VGPRs
+constexpr bool GroupedTileFits(int cfg, bool f16, int tile) {
+    if (cfg < 0 || tile < 1 || tile >= kNumConvGroupedTiles) return false;
+    const GroupedCfg& c = kGroupedCfgs[cfg];
+    const int in_regs = f16 && c.cpg % 2 == 0 ? c.cpg * c.gpb / 2 : c.cpg * c.gpb;
+    return kGroupedPx[tile] * (c.opb * c.gpb + in_regs) <= 128;
+}
+bool ConvGroupedEligible(const GroupedArgs& a, int tile);
+hipError_t LaunchConvGrouped(const GroupedArgs& a, int tile, hipStream_t stream);
+
 // Squeeze-and-excitation block (kernels_se.hip): out = in * gate[n, c], gate = act(W2^T-packed FC(act1(W1 * mean_hw(in) + b1)) + b2).
 // Three phases, four launches: squeeze (fp32 partial sums per pixel chunk), fc1 (means + FC1 + act1 -> hidden [N][mid]), fc2 (FC2 + act -> gate [N][C]),
 // apply.  Deterministic (fixed summation orders, no atomics).  The workspace holds chunks * N * C partials, N * mid hidden values and the N * C gate.

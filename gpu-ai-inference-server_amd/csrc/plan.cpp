@@ -56,6 +56,7 @@ struct LNode {
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
     bool dw = false;                    // depthwise conv (group == Cin == Cout): w packed [C][kh][kw]
+    int64_t group = 1;                  // conv: the ONNX group count (> 1 and not dw: a grouped conv, w packed [Cout][kh][kw][Cin / group])
     float lo = -kInf, hi = kInf;        // Clip bounds (L_CLIP; a depthwise conv's epilogue clamp)
     float pre_hi = kInf;                // depthwise conv: upper bound of the prologue
     Act act;                            // L_ACT; a depthwise conv's epilogue activation; L_SE: the gate's
@@ -185,6 +186,21 @@ bool DwFastViews(const Step& s) {
 }
 // 4 output pixels per lane on wide rows, 2 on narrow ones (7x7 maps: 4 groups of 2 instead of 2 of 4, one wasted lane in eight), the generic kernel otherwise
 int DwDefaultTile(const Step& s) { return DwFastViews(s) ? (s.out.w >= 14 ? 3 : 2) : 0; }
+
+// Grouped steps: the views and channel blocks the fast kernel needs for `tile` (kernels_grouped.hip ConvGroupedEligible re-checks them with the pointers)
+bool GroupedFastViews(const Step& s, int tile) {
+    const int cfg = GroupedCfgFor(s.in.c, s.out.c, s.group);
+    if (cfg < 0 || !GroupedTileFits(cfg, s.out.f16, tile) || s.out.c % (kGroupedCfgs[cfg].opb * kGroupedCfgs[cfg].gpb) || s.kh > 7 || s.kw > 7) return false;
+    const int64_t V = s.out.f16 ? 8 : 4;
+    auto ok = [&](const View& v) { return !v.nchw && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == s.out.f16; };
+    return ok(s.in) && ok(s.out) && (!s.has_in2 || ok(s.in2));
+}
+// What the autotuner picked on 63 of the 64 grouped steps of ResNeXt-50 / RegNetY-400MF (fp32 b32, fp16 b128): 2 output pixels per
+// lane for fp16 groups of 16 or more input channels, else 1; the generic kernel when no channel block fits
+int GroupedDefaultTile(const Step& s) {
+    if (s.out.f16 && s.in.c / s.group >= 16 && GroupedFastViews(s, 2)) return 2;
+    return GroupedFastViews(s, 1) ? 1 : 0;
+}
 
 // Algorithmic FLOPs per element of a fused activation
 double ActFlops(ActKind k) {
@@ -372,13 +388,26 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             if (X.dims.size() != 4) fail("Conv " + n.name + ": input must be 4-D");
             int64_t co = w->dims[0], ci = w->dims[1];
             const int64_t group = on.attr_i("group", 1);
+            if (group < 1) fail("Conv " + n.name + ": group = " + std::to_string(group) + " must be positive");
             if (group != 1) {
-                // depthwise: one filter per channel; the weights [C, 1, kh, kw] pack as [C][kh][kw] (= [Cout][kh][kw][Cin] with Cin = 1)
-                if (group != X.c || co != group || ci != 1)
-                    fail("Conv " + n.name + ": group = " + std::to_string(group) + " is not supported (only depthwise grouped convolutions, with group == input channels == output channels, are)");
-                n.dw = true;
+                // depthwise: one filter per channel; the weights [C, 1, kh, kw] pack as [C][kh][kw] (= [Cout][kh][kw][Cin] with Cin = 1).
+                // Any other group: output channel o reads input channels (o / (Cout / group)) * Cin / group ..., weights [Cout, Cin / group, kh, kw]
+                if (X.c % group != 0)
+                    fail("Conv " + n.name + ": group = " + std::to_string(group) + " does not divide the input channels " + std::to_string(X.c));
+                if (co % group != 0)
+                    fail("Conv " + n.name + ": group = " + std::to_string(group) + " does not divide the output channels " + std::to_string(co));
+                if (ci != X.c / group)
+                    fail("Conv " + n.name + ": weight channels " + std::to_string(ci) + " != input channels / group = " + std::to_string(X.c / group));
+                n.dw = group == X.c && co == group;
+                // Grouped convolutions are opt-in: without IE_GROUPED_CONV=1 the planner keeps refusing them as it always has, so a model that
+                // loads (or is refused) today is planned exactly as before
+                if (!n.dw && !env.flag("IE_GROUPED_CONV"))
+                    fail("Conv " + n.name + ": group = " + std::to_string(group) + " is not supported (only depthwise grouped convolutions, with group == input "
+                         "channels == output channels, are; set IE_GROUPED_CONV=1 to run the others on the grouped-convolution kernels)");
+                n.group = group;
+            } else if (ci != X.c) {
+                fail("Conv " + n.name + ": input channels " + std::to_string(X.c) + " != weight channels " + std::to_string(ci));
             }
-            if (n.dw ? ci != 1 : ci != X.c) fail("Conv " + n.name + ": input channels " + std::to_string(X.c) + " != weight channels " + std::to_string(ci));
             n.kind = L_CONV;
             read_window_attrs(on, n, X.h, X.w, true, w);
             if (n.kh != w->dims[2] || n.kw != w->dims[3]) fail("Conv " + n.name + ": kernel_shape does not match weights");
@@ -624,8 +653,10 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         L.vals[v].is_output = true;
     }
     if (precision == Precision::F8 || f8_fusions)
-        for (const LNode& n : L.nodes)
+        for (const LNode& n : L.nodes) {
             if (n.dw) fail("depthwise convolution is not supported in fp8 mode (Conv " + n.name + ")");
+            if (n.kind == L_CONV && n.group != 1) fail("grouped convolution is not supported in fp8 mode (Conv " + n.name + ")");
+        }
 
     if (precision == Precision::F8 || f8_fusions)
         for (const LNode& n : L.nodes)
@@ -661,7 +692,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             return &L.nodes[p];
         };
         auto fc_ok = [&](const LNode* c, int64_t cin, int64_t cout) {
-            return c && !c->dw && c->kh == 1 && c->kw == 1 && c->sh == 1 && c->sw == 1 && !c->pt && !c->pl && !c->pb && !c->pr && c->res < 0 &&
+            return c && c->group == 1 && c->kh == 1 && c->kw == 1 && c->sh == 1 && c->sw == 1 && !c->pt && !c->pl && !c->pb && !c->pr && c->res < 0 &&
                    L.vals[c->in[0]].dims.size() == 4 && L.vals[c->in[0]].c == cin && L.vals[c->out].c == cout && int64_t(c->w.size()) == cin * cout;
         };
         for (size_t i = 0; i < L.nodes.size(); ++i) {
@@ -731,12 +762,14 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             int ci = L.consumers(cv.out)[0];
             LNode& b = L.nodes[ci];
             if (b.kind == L_ACT) {
-                // only the depthwise kernel has an activation epilogue (an activation behind another conv: fusion 2d below, or an eltwise step)
-                if (!cv.dw) break;
+                // only the depthwise and grouped kernels have an activation epilogue (an activation behind another conv: fusion 2d below, or an
+                // eltwise step)
+                if (cv.group == 1) break;
                 cv.act = b.act;
             } else if (b.kind == L_CLIP) {
-                // only the depthwise kernel has a clamp epilogue (a Clip behind another conv: see the ReLU6 pass below, or an eltwise step)
-                if (!cv.dw) break;
+                // only the depthwise and grouped kernels have a clamp epilogue (a Clip behind another conv: see the ReLU6 pass below, or an
+                // eltwise step)
+                if (cv.group == 1) break;
                 cv.lo = b.lo;
                 cv.hi = b.hi;
                 clamped = true;
@@ -1009,7 +1042,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             while (nxt < order.size() && (L.nodes[order[nxt]].kind == L_CONCAT || L.nodes[order[nxt]].kind == L_ALIAS)) ++nxt;
             if (nxt >= order.size()) break;
             const LNode& b1 = L.nodes[order[nxt]];
-            if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre || a3.dw || b1.dw) continue;
+            if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre || a3.group != 1 || b1.group != 1) continue;
             if (L.vals[a3.out].c != 32 || L.vals[b1.out].c != 128 || L.vals[b1.in[0]].root != L.vals[a3.out].root) continue;
             if (L.vals[a3.out].n * L.vals[a3.out].h * L.vals[a3.out].w > FuseMaxPixels(env)) continue;
             const int rb = L.vals[a3.in[0]].root;
@@ -1153,6 +1186,24 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                     if (const char* ft = env.get("IE_FORCE_TILE")) {
                         const int t = std::atoi(ft);
                         if (t >= 0 && t < kNumConvDwTiles && (t == 0 || DwFastViews(s))) s.tile = t;
+                    }
+                    s.base_tile = 0;
+                    break;
+                }
+                if (n.group != 1) {
+                    // grouped: its own kernels whatever IE_FORCE_ALGO says; IE_FORCE_TILE indexes the grouped variants (kernels.h kNumConvGroupedTiles)
+                    s.algo = ConvAlgo::Grouped;
+                    s.group = int(n.group);
+                    s.lo = n.lo;
+                    s.hi = n.hi;
+                    s.act = n.act;
+                    s.pre_act = n.pre_act;
+                    s.flops = 2.0 * double(s.out.n) * double(s.out.h) * double(s.out.w) * double(s.out.c) * n.kh * n.kw * double(s.in.c / n.group);
+                    s.bytes = vbytes(s.in) + vbytes(s.out) + (s.in.f16 ? 2.0 : 4.0) * double(n.w.size()) + (n.res >= 0 ? vbytes(s.in2) : 0.0);
+                    s.tile = GroupedDefaultTile(s);
+                    if (const char* ft = env.get("IE_FORCE_TILE")) {
+                        const int t = std::atoi(ft);
+                        if (t >= 0 && t < kNumConvGroupedTiles && (t == 0 || GroupedFastViews(s, t))) s.tile = t;
                     }
                     s.base_tile = 0;
                     break;
@@ -1472,7 +1523,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             if (i + 1 < plan.steps.size()) {
                 const Step& s1 = plan.steps[i + 1];
                 const int64_t M = s3.out.n * s3.out.h * s3.out.w;
-                fuse = s3.kind == StepKind::Conv && s1.kind == StepKind::Conv && s3.algo != ConvAlgo::Depthwise && s1.algo != ConvAlgo::Depthwise && s3.kh == 3 && s3.kw == 3 && s3.sh == 1 && s3.sw == 1 && s3.pt == 1 && s3.pl == 1 &&
+                fuse = s3.kind == StepKind::Conv && s1.kind == StepKind::Conv && !IsGroupConv(s3.algo) && !IsGroupConv(s1.algo) && s3.kh == 3 && s3.kw == 3 && s3.sh == 1 && s3.sw == 1 && s3.pt == 1 && s3.pl == 1 &&
                        s3.pb == 1 && s3.pr == 1 && s3.pre_scale_off < 0 && !s3.has_in2 && s3.out.c == 32 && s3.in.c % 16 == 0 && 9 * (s3.in.c / 16) <= 72 &&
                        9 * (s3.in.c / 16) >= 8 && s1.kh == 1 && s1.kw == 1 && s1.sh == 1 && s1.sw == 1 && s1.pt == 0 && s1.pl == 0 && s1.pb == 0 && s1.pr == 0 &&
                        !s1.has_in2 && s1.out.c == 128 && s1.in.buf == s3.out.buf && s1.in.pitch == s3.out.pitch && !s1.in.nchw && !s3.in.nchw &&
@@ -1536,7 +1587,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             const Step& s1 = plan.steps[i];
             const Step& s3 = plan.steps[i + 1];
             if (s1.kind != StepKind::Conv || s3.kind != StepKind::Conv || !s1.parts.empty() || !s3.parts.empty()) return false;
-            if (s1.algo == ConvAlgo::Depthwise || s3.algo == ConvAlgo::Depthwise) return false;
+            if (IsGroupConv(s1.algo) || IsGroupConv(s3.algo)) return false;
             if (s1.kh != 1 || s1.kw != 1 || s1.sh != 1 || s1.sw != 1 || s1.pt || s1.pl || s1.pb || s1.pr || s1.has_in2 || s1.out.c != 128) return false;
             if (s3.kh != 3 || s3.kw != 3 || s3.sh != 1 || s3.sw != 1 || s3.pt != 1 || s3.pl != 1 || s3.pb != 1 || s3.pr != 1 || s3.has_in2 || s3.out.c != 32) return false;
             if (s3.pre_scale_off >= 0 || s1.w_off < 0 || s3.w_off < 0) return false;
@@ -1780,7 +1831,7 @@ static std::string json_escape(const std::string& s) {
 
 std::string PlanToJson(const Plan& p) {
     static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite"};
-    static const char* algos[] = {"igemm_vec", "igemm_scalar", "naive", "raster3x3", "ws1x1", "ws3x3", "stem", "direct", "igemm_f8", "dense_fused", "wino3x3", "conv1x1_x6", "dense_block", "dual_f8", "stem_pool", "depthwise"};
+    static const char* algos[] = {"igemm_vec", "igemm_scalar", "naive", "raster3x3", "ws1x1", "ws3x3", "stem", "direct", "igemm_f8", "dense_fused", "wino3x3", "conv1x1_x6", "dense_block", "dual_f8", "stem_pool", "depthwise", "grouped"};
     std::ostringstream o;
     o.precision(17);
     o << "{\"inputs\":[";
@@ -1830,6 +1881,7 @@ std::string PlanToJson(const Plan& p) {
             o << "}";
         }
         if (s.kind == StepKind::Conv) o << ",\"algo\":\"" << algos[int(s.algo)] << "\",\"tile\":" << s.tile << ",\"splitk\":" << s.splitk;
+        if (s.kind == StepKind::Conv && s.algo == ConvAlgo::Grouped) o << ",\"group\":" << s.group;      // (grouped steps only)
         if (s.kind == StepKind::Pool) o << ",\"max\":" << (s.pool_max ? "true" : "false");
         if (!s.parts.empty()) {
             Plan sub;

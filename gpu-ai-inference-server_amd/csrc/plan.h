@@ -72,7 +72,12 @@ enum class ConvAlgo : int {
                       // conv's with has_in2 cleared.  The fp16 plan built for the fp8 calibration carries the same step and runs its parts.
     Depthwise = 15,   // group == Cin == Cout conv (kernels_dw.hip): weights [C][kh][kw]; tile 0 = the generic kernel, 1-3 = 16-byte channel vectors with
                       // 1 / 2 / 4 output pixels per lane.  Epilogue clamp [lo, hi] (a fused Clip) and prologue bound pre_hi (ReLU6 in front of it)
+    Grouped = 16,     // any other group > 1 (kernels_grouped.hip): weights [Cout][kh][kw][Cin / group]; tile 0 = the generic kernel, 1-3 = channel blocks
+                      // with 1 / 2 / 4 output pixels per lane.  The depthwise epilogue / prologue fields
 };
+
+// The conv algorithms whose weights are not the dense [Cout][kh][kw][Cin] layout: no dense-conv pass or weight mirror may take their steps
+inline bool IsGroupConv(ConvAlgo a) { return a == ConvAlgo::Depthwise || a == ConvAlgo::Grouped; }
 
 struct Step {
     StepKind kind = StepKind::Conv;
@@ -102,6 +107,7 @@ struct Step {
     int64_t w2_off = -1, bias2_off = -1;
     int se_chunks = 0;         // pixel chunks of the squeeze (kernels.h SeSqueezeChunks)
     ConvAlgo algo = ConvAlgo::Naive;
+    int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)
     int base_tile = 0;         // the tiled implicit GEMM's heuristic tile (what the executor falls back to when a specialised launcher declines)
     int splitk = 1;            // >1: K-tiles split over this many workgroups per output tile (+ reduce kernel)

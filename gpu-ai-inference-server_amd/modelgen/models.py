@@ -1,4 +1,5 @@
-"""Synthetic ONNX model builders (DenseNet-121, ResNet-50, MobileNetV2, MobileNetV3, EfficientNet-B0 and small test graphs).
+"""Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY and small
+test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -342,8 +343,11 @@ def two_input_graph(batch: int | str = 2, ca: int = 8, cb: int = 16, image: int 
 
 
 def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width: int = 64, image: int = 224, classes: int = 1000,
-           seed: int = 50, in_name: str = "data", out_name: str = "logits") -> bytes:
+           seed: int = 50, in_name: str = "data", out_name: str = "logits", groups: int = 1, width_per_group: int = 64) -> bytes:
     """ResNet-v1.5 bottleneck network (ResNet-50 with the defaults; BASELINE.json configs[4] names this architecture).
+
+    groups / width_per_group give ResNeXt as torchvision builds it: the bottleneck's 3x3 is a grouped conv of
+    int(planes * width_per_group / 64) * groups channels (planes = width * 2^stage; ResNeXt-50 32x4d: 128 / 256 / 512 / 1024).
 
     conv7x7/s2 -> BN -> ReLU -> maxpool3x3/s2 -> 4 stages of bottlenecks [1x1 -> 3x3 (stride on the 3x3) -> 1x1 (x4)] with a
     projection shortcut (1x1/stride conv + BN) on the first block of a stage and identity shortcuts elsewhere -> global average
@@ -357,13 +361,14 @@ def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width:
     x = gb.pool("MaxPool", x, 3, 2, pad=1)
     cin = width
     for si, nblocks in enumerate(layers):
-        mid = width * (2 ** si)
-        cout = mid * 4
+        planes = width * (2 ** si)
+        mid = int(planes * (width_per_group / 64.0)) * groups
+        cout = planes * 4
         for bi in range(nblocks):
             stride = 2 if (bi == 0 and si > 0) else 1
             tag = f"s{si + 1}b{bi + 1}"
             y = gb.relu(gb.bn(gb.conv(x, cin, mid, 1, name=tag + "_c1"), mid, name=tag + "_bn1"))
-            y = gb.relu(gb.bn(gb.conv(y, mid, mid, 3, stride=stride, pad=1, name=tag + "_c2"), mid, name=tag + "_bn2"))
+            y = gb.relu(gb.bn(gb.conv(y, mid, mid, 3, stride=stride, pad=1, name=tag + "_c2", group=groups), mid, name=tag + "_bn2"))
             y = gb.bn(gb.conv(y, mid, cout, 1, name=tag + "_c3", w_scale=float(0.5 * np.sqrt(2.0 / mid))), cout, name=tag + "_bn3")
             if bi == 0:
                 sc = gb.bn(gb.conv(x, cin, cout, 1, stride=stride, name=tag + "_proj"), cout, name=tag + "_bnp")
@@ -382,6 +387,51 @@ def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width:
 
 def resnet50(batch: int | str = 1) -> bytes:
     return resnet(batch)
+
+
+def resnext50_32x4d(batch: int | str = 1, **kw) -> bytes:
+    return resnet(batch, groups=32, width_per_group=4, **kw)
+
+
+def regnet(batch: int | str = 1, *, depths: Sequence[int], widths: Sequence[int], group_width: int, se_ratio: float = 0.0, stem: int = 32,
+           image: int = 224, classes: int = 1000, seed: int = 90, in_name: str = "data", out_name: str = "logits") -> bytes:
+    """RegNet as torchvision builds it: conv3x3/s2 (stem) -> BN -> ReLU -> stages of residual bottlenecks [1x1 -> BN -> ReLU -> grouped 3x3
+    (stride 2 on a stage's first block, group width `group_width`) -> BN -> ReLU [-> SE: squeeze round(se_ratio * block input width), ReLU,
+    sigmoid] -> 1x1 -> BN] + shortcut (1x1/stride conv + BN where the width or the stride changes) -> ReLU -> global pool -> Flatten -> Gemm.
+    The last 1x1 of every block gets half the He scale, as in resnet(), so activations stay O(1) through the residual additions."""
+    gb = GraphBuilder("regnet", seed)
+    x = gb.relu(gb.bn(gb.conv(in_name, 3, stem, 3, stride=2, pad=1, name="stem"), stem, name="stem_bn"))
+    cin = stem
+    for si, (depth, w) in enumerate(zip(depths, widths)):
+        for bi in range(depth):
+            stride = 2 if bi == 0 else 1
+            tag = f"s{si + 1}b{bi + 1}"
+            y = gb.relu(gb.bn(gb.conv(x, cin, w, 1, name=tag + "_a"), w, name=tag + "_a_bn"))
+            y = gb.relu(gb.bn(gb.conv(y, w, w, 3, stride=stride, pad=1, name=tag + "_b", group=w // group_width), w, name=tag + "_b_bn"))
+            if se_ratio > 0:
+                y = gb.se(y, w, int(round(se_ratio * cin)), act1="relu", gate="sigmoid", name=tag + "_se")
+            y = gb.bn(gb.conv(y, w, w, 1, name=tag + "_c", w_scale=float(0.5 * np.sqrt(2.0 / w))), w, name=tag + "_c_bn")
+            if cin != w or stride != 1:
+                sc = gb.bn(gb.conv(x, cin, w, 1, stride=stride, name=tag + "_proj"), w, name=tag + "_proj_bn")
+            else:
+                sc = x
+            x = gb.relu(gb.simple("Add", [y, sc]))
+            cin = w
+    x = gb.gap(x)
+    x = gb.simple("Flatten", [x], [pb.attr_int("axis", 1)])
+    wfc = rng.gaussish(seed, "fc_w", classes * cin).reshape(classes, cin) * np.float32(np.sqrt(1.0 / cin))
+    bfc = (rng.uniform(seed, "fc_b", classes) - np.float32(0.5)) * np.float32(0.2)
+    gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))],
+              [pb.attr_int("transB", 1)], out=out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=11)
+
+
+def regnet_y_400mf(batch: int | str = 1, **kw) -> bytes:
+    return regnet(batch, depths=(1, 3, 6, 6), widths=(48, 104, 208, 440), group_width=8, se_ratio=0.25, **kw)
+
+
+def regnet_x_400mf(batch: int | str = 1, **kw) -> bytes:
+    return regnet(batch, depths=(1, 2, 7, 12), widths=(32, 64, 160, 400), group_width=16, **kw)
 
 
 # MobileNetV2 inverted-residual table (Sandler et al. 2018, Table 2): expansion t, output channels c, repeats n, first stride s

@@ -8,7 +8,10 @@
 For a graph with depthwise convolutions it also prints the device-resident graph-replay time of the whole forward, the algorithmic GB/s of
 every depthwise step against the 6.29 TB/s measured copy rate, and torch's own F.conv2d(groups=C) on channels_last tensors for the same
 shapes as a yardstick (IE_PRECISION=fp16: half tensors).  For squeeze-excite steps likewise: their share of the eager forward, their algorithmic
-GB/s (the input read twice, the output written once) and torch's mean + two 1x1 convs + sigmoid + mul on channels_last tensors per SE shape."""
+GB/s (the input read twice, the output written once) and torch's mean + two 1x1 convs + sigmoid + mul on channels_last tensors per SE shape.
+For grouped convolutions (resnext50_32x4d, regnet_y_400mf, regnet_x_400mf; run with IE_GROUPED_CONV=1): every grouped step's algorithmic GB/s, its roofline
+max(bytes / 6.29 TB/s, FLOPs / peak) with peak = 157.3 TF (fp32) or 2.5 PF (fp16), the fraction of that roofline the step reaches, and torch's
+F.conv2d(groups=g) on channels_last tensors for the same shape."""
 import json
 import os
 import subprocess
@@ -38,6 +41,29 @@ for n, c, h, w, k, st, pd in json.loads(sys.argv[1]):
     wt = torch.randn(c, 1, k, k, device="cuda", dtype=dt)
     b = torch.randn(c, device="cuda", dtype=dt)
     f = lambda: F.conv2d(x, wt, b, stride=st, padding=pd, groups=c)
+    for _ in range(5):
+        f()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        f()
+    e1.record()
+    torch.cuda.synchronize()
+    out.append(e0.elapsed_time(e1) / 20)
+print(json.dumps(out))
+"""
+
+# F.conv2d(groups=g) on channels_last tensors, ms per call (20 timed calls after 5 warm ones) for each [n, cin, h, w, cout, g, k, stride, pad]
+TORCH_GROUPED = """
+import json, sys, torch
+import torch.nn.functional as F
+dt = torch.float16 if sys.argv[2] == "fp16" else torch.float32
+out = []
+for n, c, h, w, co, g, k, st, pd in json.loads(sys.argv[1]):
+    x = torch.randn(n, c, h, w, device="cuda", dtype=dt).to(memory_format=torch.channels_last)
+    wt = torch.randn(co, c // g, k, k, device="cuda", dtype=dt).to(memory_format=torch.channels_last)
+    b = torch.randn(co, device="cuda", dtype=dt)
+    f = lambda: F.conv2d(x, wt, b, stride=st, padding=pd, groups=g)
     for _ in range(5):
         f()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -99,7 +125,8 @@ for i, (p, s) in enumerate(zip(prof, plan["steps"])):
 
 dws = [(p, s) for p, s in zip(prof, plan["steps"]) if s.get("algo") == "depthwise"]
 ses = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "squeeze_excite"]
-if dws or ses:
+grs = [(p, s) for p, s in zip(prof, plan["steps"]) if s.get("algo") == "grouped"]
+if dws or ses or grs:
     import time
     B.RunPrepared(m, 10, True)
     t0 = time.perf_counter()
@@ -119,6 +146,21 @@ if dws or ses:
         gbs = p["bytes"] / p["ms"] / 1e6
         shape = f"{s['in']['h']}x{s['in']['w']}x{s['in']['c']}"
         print(f"{p['name'][:40]:40} {shape:>14} {s['stride'][0]:2d} {p['ms']:8.4f} {gbs:7.0f} {gbs / 6290 * 100:6.1f}% {t:9.4f}")
+if grs:
+    peak_tf = 2500.0 if plan["precision"] == "fp16" else 157.3
+    g_ms = sum(p["ms"] for p, _ in grs)
+    print(f"# {len(grs)} grouped steps: {g_ms:.4f} ms, {g_ms / tot * 100:.1f}% of the eager forward; roofline peak {peak_tf} TF/s, 6.29 TB/s")
+    shapes = [[s["in"]["n"], s["in"]["c"], s["in"]["h"], s["in"]["w"], s["out"]["c"], s["group"], s["k"][0], s["stride"][0], s["pads"][0]] for _, s in grs]
+    child = subprocess.run([sys.executable, "-c", TORCH_GROUPED, json.dumps(shapes), plan["precision"]], capture_output=True, text=True, timeout=300)
+    tms = json.loads(child.stdout.strip().splitlines()[-1]) if child.returncode == 0 else [float("nan")] * len(grs)
+    if child.returncode != 0:
+        print("# torch yardstick failed:", child.stderr.strip().splitlines()[-1:])
+    print(f"{'grouped step':24} {'kernel':36} {'HxWxC/g':>14} {'s':>2} {'ms':>8} {'GB/s':>7} {'roof ms':>8} {'%roof':>6} {'torch ms':>9}")
+    for (p, s), t in zip(grs, tms):
+        gbs = p["bytes"] / p["ms"] / 1e6
+        roof = max(p["bytes"] / 6.29e9, p["flops"] / (peak_tf * 1e9))
+        shape = f"{s['in']['h']}x{s['in']['w']}x{s['in']['c']}/{s['group']}"
+        print(f"{p['name'][:24]:24} {p['kernel'][:36]:36} {shape:>14} {s['stride'][0]:2d} {p['ms']:8.4f} {gbs:7.0f} {roof:8.4f} {roof / p['ms'] * 100:5.1f}% {t:9.4f}")
 if ses:
     se_ms = sum(p["ms"] for p, _ in ses)
     print(f"# {len(ses)} squeeze-excite steps: {se_ms:.4f} ms, {se_ms / tot * 100:.1f}% of the eager forward")

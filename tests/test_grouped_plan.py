@@ -1,0 +1,215 @@
+"""CPU: grouped convolutions (opt-in, IE_GROUPED_CONV=1) through the ONNX reader and the planner (EngineDescribeModel): ResNeXt-50 32x4d, RegNetY-400MF and RegNetX-400MF
+step structures, FLOP accounting, the refusals (malformed groups, fp8), the switches that must not move a grouped step, and the plans of the
+graphs that loaded before grouped convolutions, which must stay byte-identical (tests/golden/plan_sha256_parent.json)."""
+import ctypes as C
+import hashlib
+import json
+import os
+
+import numpy as np
+import pytest
+
+import grouped_ref
+from gpu_ai_inference_server_amd import binding as B
+from gpu_ai_inference_server_amd.modelgen import models
+from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_sha256_parent.json")
+HASH_NETS = {"densenet121": models.densenet121, "resnet50": models.resnet50, "mobilenet_v2": models.mobilenet_v2,
+             "mobilenet_v3_large": lambda b: models.mobilenet_v3(b, variant="large"), "efficientnet_b0": models.efficientnet_b0}
+
+
+def plan_json(path, batch):
+    """The plan's JSON text exactly as the engine writes it (the "plan" member of EngineDescribeModel's document, its last one)."""
+    err = C.c_void_p()
+    p = B.lib().EngineDescribeModel(path.encode(), batch, C.byref(err))
+    if not p:
+        raise RuntimeError(B._take_error(err))
+    s = B._take_string(p)
+    assert s.endswith("}")
+    return s[s.index('"plan":') + len('"plan":'):-1]
+
+
+@pytest.fixture(scope="module")
+def nets(tmp_path_factory):
+    root = str(tmp_path_factory.mktemp("grouped_nets"))
+    out = {}
+    for name, f in (("resnext50", models.resnext50_32x4d), ("resnet50", models.resnet50), ("regnet_y", models.regnet_y_400mf),
+                    ("regnet_x", models.regnet_x_400mf)):
+        mb = f("N")
+        out[name] = (mb, models.write_repo(root, name, mb))
+    return out
+
+
+@pytest.fixture(autouse=True)
+def grouped_on(monkeypatch):
+    """Grouped convolutions are opt-in (IE_GROUPED_CONV=1); every test here plans with them on unless it removes the switch."""
+    monkeypatch.setenv("IE_GROUPED_CONV", "1")
+
+
+def _describe(path, batch, monkeypatch, prec):
+    monkeypatch.setenv("IE_PRECISION", prec)
+    return B.DescribeModel(path, batch)["plan"]
+
+
+def _grouped(p):
+    return [s for s in p["steps"] if s.get("algo") == "grouped"]
+
+
+def _check_conv_flops(p, mb, batch):
+    """The conv steps' FLOPs are 2x the graph's conv + Gemm MACs (a fused stem + max-pool step also counts the pool's 9 compares per output)."""
+    convs = [s for s in p["steps"] if s["kind"] == "conv"]
+    pool = sum(9 * s["out"]["n"] * s["out"]["c"] * s["out"]["h"] * s["out"]["w"] for s in convs if s["algo"] == "stem_pool")
+    assert sum(s["flops"] for s in convs) - pool == 2 * grouped_ref.conv_macs(mb, (batch, 3, 224, 224))
+
+
+@pytest.mark.parametrize("prec,batch", [("fp32", 32), ("fp16", 128)])
+def test_resnext50_plan(nets, monkeypatch, prec, batch):
+    mb, path = nets["resnext50"]
+    p = _describe(path, batch, monkeypatch, prec)
+    g = _grouped(p)
+    assert len(g) == 16 and all(s["group"] == 32 and s["k"] == [3, 3] and s["pads"] == [1, 1, 1, 1] for s in g)
+    # Cin / group = 4 / 8 / 16 / 32 by stage (128 / 256 / 512 / 1024 channels at 56 / 28 / 14 / 7), stride 2 on the first block of stages 2-4
+    assert [s["in"]["c"] // 32 for s in g] == [4] * 3 + [8] * 4 + [16] * 6 + [32] * 3
+    assert [s["out"]["h"] for s in g] == [56] * 3 + [28] * 4 + [14] * 6 + [7] * 3
+    assert [i for i, s in enumerate(g) if s["stride"] == [2, 2]] == [3, 7, 13]
+    assert all(s["bias"] and s["relu"] and not s["pre"] and not s["residual"] for s in g)       # BN folded, ReLU in the epilogue
+    assert all(s["in"]["f16"] == (prec == "fp16") for s in g)
+    assert all(s["tile"] != 0 for s in g)                 # every ResNeXt shape has a channel-block variant
+    for s in g:
+        o = s["out"]
+        assert s["flops"] == 2 * o["n"] * o["h"] * o["w"] * o["c"] * 9 * (s["in"]["c"] // 32)
+    _check_conv_flops(p, mb, batch)
+
+
+def test_resnext50_fp32_structure_equals_resnet50(nets, monkeypatch):
+    def structure(p):
+        return [(s["kind"], s.get("residual", False), s["relu"]) for s in p["steps"]]
+    px = _describe(nets["resnext50"][1], 32, monkeypatch, "fp32")
+    pr = _describe(nets["resnet50"][1], 32, monkeypatch, "fp32")
+    assert structure(px) == structure(pr)
+
+
+@pytest.mark.parametrize("prec,batch", [("fp32", 32), ("fp16", 128)])
+def test_regnet_plans(nets, monkeypatch, prec, batch):
+    p = _describe(nets["regnet_y"][1], batch, monkeypatch, prec)
+    g = _grouped(p)
+    ses = [s for s in p["steps"] if s["kind"] == "squeeze_excite"]
+    assert len(g) == 16 and len(ses) == 16
+    assert [s["in"]["c"] for s in g] == [48] + [104] * 3 + [208] * 6 + [440] * 6
+    assert all(s["in"]["c"] // s["group"] == 8 and s["tile"] != 0 for s in g)       # group width 8, 104 and 440 included
+    # the squeeze-excite reads the grouped conv's output
+    assert all(p["steps"][s["in_src"]].get("algo") == "grouped" for s in ses)
+    p = _describe(nets["regnet_x"][1], batch, monkeypatch, prec)
+    g = _grouped(p)
+    assert len(g) == 22 and all(s["in"]["c"] // s["group"] == 16 and s["tile"] != 0 for s in g)
+    assert [s["in"]["c"] for s in g] == [32] + [64] * 2 + [160] * 7 + [400] * 12
+    assert not [s for s in p["steps"] if s["kind"] == "squeeze_excite"]
+    _check_conv_flops(p, nets["regnet_x"][0], batch)
+
+
+def test_plans_of_existing_graphs_are_byte_identical(tmp_path, monkeypatch):
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    paths = {}
+    for key, h in want.items():
+        name, prec, b = key.split("/")
+        if name not in paths:
+            paths[name] = models.write_repo(str(tmp_path), name, HASH_NETS[name]("N"))
+        monkeypatch.setenv("IE_PRECISION", prec)
+        assert hashlib.sha256(plan_json(paths[name], int(b[1:])).encode()).hexdigest() == h, key
+
+
+def _one_conv(tmp_path, name, cin, cout, group, wshape=None, k=3):
+    """x -> 1x1 conv (so the grouped conv reads an NHWC tensor) -> Conv(group) named `name` with weights [cout, cin / group, k, k] or `wshape`
+    -> global pool"""
+    gb = models.GraphBuilder(name, 11)
+    x = gb.conv("x", cin, cin, 1)
+    wshape = wshape or (cout, cin // group, k, k)
+    w = gb.init(name + "_w", (np.arange(np.prod(wshape)) % 7 - 3).reshape(wshape).astype(np.float32) * np.float32(0.1))
+    gb.nodes.append(pb.node("Conv", [x, w], [name + "_out"], name, [
+        pb.attr_int("group", group), pb.attr_ints("kernel_shape", [k, k]), pb.attr_ints("pads", [k // 2] * 4), pb.attr_ints("strides", [1, 1])]))
+    gb.nodes.append(pb.node("GlobalAveragePool", [name + "_out"], ["y"], "gap"))
+    return models.write_repo(str(tmp_path), name, gb.finish([("x", [1, cin, 6, 6])], [("y", [1, cout, 1, 1])]))
+
+
+def test_grouped_convs_are_refused_without_the_switch(nets, tmp_path, monkeypatch):
+    """Without IE_GROUPED_CONV=1 the planner refuses grouped convs as before (the message names the node and the switch); depthwise and dense
+    graphs do not need it."""
+    monkeypatch.delenv("IE_GROUPED_CONV")
+    with pytest.raises(RuntimeError, match=r"Conv s1b1_c2: group = 32 is not supported \(only depthwise grouped convolutions.*IE_GROUPED_CONV=1"):
+        B.DescribeModel(nets["resnext50"][1], 2)
+    with pytest.raises(RuntimeError, match=r"Conv g2off: group = 2 is not supported"):
+        B.DescribeModel(_one_conv(tmp_path, "g2off", 8, 8, 2), 1)
+    monkeypatch.setenv("IE_GROUPED_CONV", "0")
+    with pytest.raises(RuntimeError, match=r"group = 32 is not supported"):
+        B.DescribeModel(nets["resnext50"][1], 2)
+    d = [s for s in B.DescribeModel(_one_conv(tmp_path, "dwoff", 16, 16, 16), 1)["plan"]["steps"] if s["kind"] == "conv"][-1]
+    assert d["algo"] == "depthwise"
+    assert len(B.DescribeModel(nets["resnet50"][1], 2)["plan"]["steps"]) > 0
+
+
+def test_group_2_conv_plans_as_grouped(tmp_path):
+    """What the parent refused ("group = 2 is not supported ..."): a group-2 conv is a grouped step now."""
+    steps = B.DescribeModel(_one_conv(tmp_path, "g2", 8, 8, 2), 1)["plan"]["steps"]
+    c1, g = [s for s in steps if s["kind"] == "conv"]
+    assert g["algo"] == "grouped" and g["group"] == 2
+    assert "group" not in c1 and "group" not in steps[-1]
+
+
+def test_channel_multiplier_and_depthwise_split(tmp_path):
+    # Cin / group = 1 with Cout = 2 Cin: grouped; group == Cin == Cout stays depthwise (no "group" field)
+    g = [s for s in B.DescribeModel(_one_conv(tmp_path, "mult", 16, 32, 16), 1)["plan"]["steps"] if s["kind"] == "conv"][-1]
+    assert g["algo"] == "grouped" and g["group"] == 16 and g["tile"] != 0
+    d = [s for s in B.DescribeModel(_one_conv(tmp_path, "dwc", 16, 16, 16), 1)["plan"]["steps"] if s["kind"] == "conv"][-1]
+    assert d["algo"] == "depthwise" and "group" not in d
+
+
+def test_malformed_groups_are_refused(tmp_path):
+    with pytest.raises(RuntimeError, match=r"Conv bad_cin: group = 3 does not divide the input channels 8"):
+        B.DescribeModel(_one_conv(tmp_path, "bad_cin", 8, 12, 3, wshape=(12, 2, 3, 3)), 1)
+    with pytest.raises(RuntimeError, match=r"Conv bad_cout: group = 4 does not divide the output channels 6"):
+        B.DescribeModel(_one_conv(tmp_path, "bad_cout", 8, 6, 4, wshape=(6, 2, 3, 3)), 1)
+    with pytest.raises(RuntimeError, match=r"Conv bad_w: weight channels 4 != input channels / group = 2"):
+        B.DescribeModel(_one_conv(tmp_path, "bad_w", 8, 8, 4, wshape=(8, 4, 3, 3)), 1)
+    with pytest.raises(RuntimeError, match=r"Conv bad_g: group = 0 must be positive"):
+        B.DescribeModel(_one_conv(tmp_path, "bad_g", 8, 8, 0, wshape=(8, 8, 3, 3)), 1)
+
+
+def test_fp8_plan_of_a_grouped_graph_is_refused(nets, monkeypatch):
+    monkeypatch.setenv("IE_PRECISION", "fp8")
+    with pytest.raises(RuntimeError, match=r"grouped convolution is not supported in fp8 mode \(Conv s1b1_c2"):
+        B.DescribeModel(nets["resnext50"][1], 4)
+
+
+def test_forced_switches_keep_grouped_steps_on_the_grouped_kernels(nets, monkeypatch):
+    path = nets["regnet_y"][1]
+    for algo in ("naive", "igemm", "ws", "direct", "raster"):
+        monkeypatch.setenv("IE_FORCE_ALGO", algo)
+        assert len(_grouped(B.DescribeModel(path, 2)["plan"])) == 16, algo
+    monkeypatch.delenv("IE_FORCE_ALGO")
+    for t in (0, 1, 2, 3, 9):
+        monkeypatch.setenv("IE_FORCE_TILE", str(t))
+        g = _grouped(B.DescribeModel(path, 2)["plan"])
+        assert len(g) == 16
+        # every variant fits RegNetY's 8-channel groups; an unknown tile leaves the default (1 output pixel per lane)
+        assert all(s["tile"] == (t if t < 4 else 1) for s in g), (t, [s["tile"] for s in g])
+
+
+def test_grouped_fusions_and_slices(tmp_path):
+    """Pre-activation BN + ReLU as the prologue, BN folded, a residual Add in the epilogue, input and output in concat slices."""
+    gb = models.GraphBuilder("gfuse", 5)
+    a1 = gb.conv("x", 8, 32, 1, bias=True)
+    a2 = gb.conv("x", 8, 8, 1, bias=True)
+    cat0 = gb.concat([a2, a1])
+    u = gb.relu(gb.bn(a1, 32))
+    d = gb.bn(gb.conv(u, 32, 32, 3, pad=1, group=4), 32)
+    d = gb.simple("Add", [d, a1])
+    side = gb.conv(cat0, 40, 8, 1)
+    gb.nodes.append(pb.node("Concat", [d, side], ["y"], "cat_out", [pb.attr_int("axis", 1)]))
+    path = models.write_repo(str(tmp_path), "gfuse", gb.finish([("x", [2, 8, 11, 11])], [("y", [2, 40, 11, 11])]))
+    steps = B.DescribeModel(path, 2)["plan"]["steps"]
+    (g,) = _grouped({"steps": steps})
+    assert g["pre"] and g["pre_relu"] and g["bias"] and g["residual"] and g["group"] == 4
+    assert g["in"]["c_off"] == 8 and g["in"]["pitch"] == 40 and g["in2"]["c_off"] == 8
+    assert g["out"]["c_off"] == 0 and g["out"]["pitch"] == 40 and g["tile"] != 0
