@@ -41,6 +41,29 @@ TensorArg make_arg(const PlanInstance& pi, const View& v) {
     return t;
 }
 
+// A view's shape and strides as make_arg lays them out, without a buffer (kernel labels of steps outside a plan instance)
+TensorArg view_strides(const View& v) {
+    TensorArg t;
+    t.n = int(v.n); t.h = int(v.h); t.w = int(v.w); t.c = int(v.c);
+    t.f16 = v.f16 ? 1 : 0;
+    t.f8 = v.f8 ? 1 : 0;
+    if (v.nchw) { t.sw = 1; t.sh = v.w; t.sc = v.h * v.w; t.sn = v.c * v.h * v.w; }
+    else { t.sc = 1; t.sw = v.pitch; t.sh = v.w * v.pitch; t.sn = v.h * v.w * v.pitch; }
+    return t;
+}
+
+ResizeArgs MakeResizeArgs(const PlanInstance& pi, const Step& s) {
+    ResizeArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    a.mode = int(s.rs_mode);
+    a.coord = int(s.rs_coord);
+    a.nearest = int(s.rs_nearest);
+    a.scale_h = s.rs_scale_h;
+    a.scale_w = s.rs_scale_w;
+    return a;
+}
+
 constexpr size_t kPinnedBytes = size_t(4) << 20;              // pinned staging for results (logits are KBs; larger outputs go direct)
 constexpr int64_t kTuneWorkspaceFloats = int64_t(16) << 20;   // 64 MiB of split-K slabs available to the autotuner
 constexpr int kNumCounters = 1 << 16;
@@ -1019,6 +1042,8 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
                                 s.in.nchw, int64_t(s.algo), s.pre_scale_off >= 0, s.bias_off >= 0};
     if (s.in.f16 || s.out.f16) { key.push_back(s.in.f16); key.push_back(s.out.f16); }   // fp32 signatures keep 17 entries
     if (s.has_in2) key.push_back(1);              // a fused residual changes which kernels apply (18 / 20 entries)
+    const bool dil = s.dh != 1 || s.dw != 1;
+    if (dil) key.insert(key.end(), {-1, s.dh, s.dw});   // dilated convs: -1 (no other signature has a negative entry) and the dilation
     // Split-K admissibility (sp > 1) of the two families that split, for the search and for a choice taken from another pixel count
     auto igemm_split_ok = [&](const IgemmTile& T, int sp) {
         const int64_t wgs = ((M + T.bm - 1) / T.bm) * ((N + T.bn - 1) / T.bn);
@@ -1061,7 +1086,8 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
         if (const float ms = TimeTrial(ctx, pi, trial); ms < best) { best = ms; chosen = trial; }
     };
     // LDS-window kernel for 3x3/s1/p1 convs without an activation prologue
-    if (!s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.sh == 1 && s.sw == 1 && s.pt == 1 && s.pl == 1 && s.pb == 1 &&
+    // (a dilated conv only has the implicit GEMM's base tiles: every other family reads adjacent taps)
+    if (!dil && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.sh == 1 && s.sw == 1 && s.pt == 1 && s.pl == 1 && s.pb == 1 &&
         s.pr == 1 && s.pre_scale_off < 0) {
         ConvArgs probe;
         probe.in = make_arg(pi, s.in);
@@ -1075,7 +1101,7 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
         }
     }
     // Winograd F(2x2, 3x3): 2.25x fewer MACs for the 32-channel 3x3 convs on even-sized images
-    if (!s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.out.c == 32 && !s.has_in2) {
+    if (!dil && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.out.c == 32 && !s.has_in2) {
         Step probe_step = s;
         probe_step.algo = ConvAlgo::Wino3x3;
         ConvArgs probe = MakeConvArgs(pi, probe_step);
@@ -1091,7 +1117,7 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
         }
     }
     // bf16x6 (opt-in): the 1x1 convs on the bf16 matrix pipe with exactly split operands
-    if (w_->d_weights_x6 && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1 && !s.has_in2) {
+    if (!dil && w_->d_weights_x6 && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1 && !s.has_in2) {
         Step probe_step = s;
         probe_step.algo = ConvAlgo::X6;
         ConvArgs probe = MakeConvArgs(pi, probe_step);
@@ -1100,19 +1126,19 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
     }
     // the kernels_direct.hip family (every variant checks its own pixel-count / shape limits): K split over the waves with
     // operands straight from global memory, LDS-window tiles, activations-stationary 1x1, window + streamed weights
-    if (s.algo == ConvAlgo::IgemmVec) {
+    if (!dil && s.algo == ConvAlgo::IgemmVec) {
         ConvArgs probe = MakeConvArgs(pi, s);
         probe.res = TensorArg();                   // LaunchStep adds the shortcut in a second kernel for this family
         for (int t = 0; t < kNumConvDirectTiles; ++t)
             if (ConvDirectEligible(probe, t)) consider(ConvAlgo::Direct, t, 1);
     }
     // 1x1/s1: weights-stationary streaming kernel (either precision)
-    if (s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1) {
+    if (!dil && s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1) {
         ConvArgs probe = MakeConvArgs(pi, s);
         for (int t = 0; t < (s.in.f16 ? kNumConvWs16Tiles : kNumConvWs32Tiles); ++t)
             if (s.in.f16 ? ConvWsEligible(probe, t) : ConvWs32Eligible(probe, t)) consider(ConvAlgo::Ws1x1, t, 1);
     }
-    if (s.in.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3) {
+    if (!dil && s.in.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3) {
         ConvArgs probe = MakeConvArgs(pi, s);
         for (int t = 0; t < kNumConvWs3Tiles; ++t)
             if (ConvWs3Eligible(probe, t)) consider(ConvAlgo::Ws3x3, t, 1);
@@ -1120,6 +1146,7 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
     static const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24};
     for (int t = 0; t < kNumIgemmTiles; ++t) {
         const IgemmTile& T = kIgemmTiles[t];
+        if (dil && t >= kNumIgemmBaseTiles) continue;
         if ((T.bn > 32 && N <= 32) || (T.bn > 64 && N <= 64)) continue;
         if ((T.kg > 1 || T.deep) && (s.algo != ConvAlgo::IgemmVec || KT < 2 * T.kg)) continue;
         if (T.deep && s.in.f16) continue;         // the fp16 kernel has no deep-prefetch variants
@@ -1206,6 +1233,7 @@ ConvArgs DeviceModel::MakeConvArgs(const PlanInstance& pi, const Step& s) const 
         a.pre_shift16 = static_cast<const char*>(w_->d_weights16) + s.pre_shift_off * 2;
     }
     a.kh = s.kh; a.kw = s.kw; a.sh = s.sh; a.sw = s.sw; a.pt = s.pt; a.pl = s.pl;
+    a.dh = int16_t(s.dh); a.dw = int16_t(s.dw);
     a.pre_relu = s.pre_relu; a.relu = s.relu;
     a.workspace = pi.workspace;
     a.workspace_floats = pi.workspace_floats;
@@ -1398,6 +1426,7 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             }
             if (a.in.f8 || a.res.f8 || (a.out.f8 && s_in.algo != ConvAlgo::Stem)) throw std::runtime_error("internal error: fp8 tensor reached a non-fp8 conv kernel");
             const Step& s = *sp;
+            if ((s.dh != 1 || s.dw != 1) && !DilationOk(s.algo)) throw std::runtime_error("internal error: dilated conv " + s.name + " reached a kernel without dilation");
             // A fused residual Add lives in the weights-stationary 1x1 epilogues; any other kernel runs the conv without its ReLU
             // and adds the shortcut in place afterwards.
             const TensorArg res = a.res;
@@ -1478,6 +1507,12 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the copy kernel");
             check(LaunchCopy(make_arg(pi, s.in), make_arg(pi, s.out), stream_), "copy");
             break;
+        case StepKind::Resize: {
+            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the resize kernels");
+            const ResizeArgs a = MakeResizeArgs(pi, s);
+            check(LaunchResize(a, ResizePath(a), stream_), "resize");
+            break;
+        }
     }
 }
 
@@ -1528,6 +1563,16 @@ static std::string kernel_label(const Step& s) {
         case StepKind::GlobalAvgPool: return s.in.f8 ? "gap_f8_kernel" : "gap_kernel";
         case StepKind::Eltwise: return "eltwise_kernel";
         case StepKind::Copy: return "copy_kernel";
+        case StepKind::Resize: {
+            static const char* const names[3] = {"resize_generic_kernel", "resize_vec_kernel<", "resize_nchw_kernel<"};
+            ResizeArgs a;
+            a.in = view_strides(s.in);
+            a.out = view_strides(s.out);
+            if (s.in.c_off % (s.in.f16 ? 8 : 4)) a.in.p = reinterpret_cast<float*>(uintptr_t(4));    // (a misaligned view: the launcher sees its address)
+            if (s.out.c_off % (s.out.f16 ? 8 : 4)) a.out.p = reinterpret_cast<float*>(uintptr_t(4));
+            const int path = ResizePath(a);
+            return path == 0 ? std::string(names[0]) : std::string(names[path]) + (s.in.f16 ? "f16>" : "f32>");
+        }
         case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }
     return "?";

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace ie {
@@ -63,8 +64,12 @@ struct ConvArgs {
     int sh2 = 1, sw2 = 1;
     int64_t in2_bytes = 0;
     int debug = 0;                     // timing-only ablation bits (IE_DEBUG_ABLATE), 0 in production
+    // dilation: tap (ky, kx) reads input pixel (oy*sh - pt + ky*dh, ox*sw - pl + kx*dw).  Only the naive kernel and the dilated instantiations
+    // of the implicit GEMMs read it; it sits in the padding before in_bytes, so no other field moves and the other kernels are unchanged
+    int16_t dh = 1, dw = 1;
     int64_t in_bytes = 0;              // filled by LaunchConvIgemm: byte span of the input view (buffer descriptor range)
 };
+static_assert(sizeof(ConvArgs) == 464 && offsetof(ConvArgs, in_bytes) == 456, "ConvArgs layout: the dilation must stay in the padding");
 
 // The 3x3 half of a fused dense-layer step (kernels_fused.hip): bottleneck tensor in, 32 fresh channels out (the tail of the 1x1's
 // input view), fragment-major 3x3 weights.
@@ -194,6 +199,20 @@ hipError_t LaunchSqueezeExcitePhase(const SeArgs& a, int phase, hipStream_t stre
 // combined inside the same launch by the last-arriving workgroup of each tile (a.counters != null) or by a second
 // kernel (a.counters == null).  Both sum in slice order: deterministic, no float atomics.
 bool SplitKWorkspaceOk(int64_t workspace_floats, int num_counters, int splitk, int64_t num_tiles, int tile_elems);
+// Resize / Upsample (kernels_resize.hip): out(n, c, y, x) = in(n, c, f(y), g(x)) interpolated per axis, in NHWC (sc == 1, any pitch; h = w = 1
+// broadcasts), out NHWC (sc == 1) or dense NCHW (sw == 1: the graph output).  fp32 or half elements, fp32 interpolation math; the source
+// coordinate is computed in double from the ONNX formulas, so nearest-pixel ties break as the spec's reference does.
+struct ResizeArgs {
+    TensorArg in, out;
+    int mode = 0;                      // plan.h ResizeMode: 0 nearest, 1 linear
+    int coord = 0;                     // ResizeCoord: 0 half_pixel, 1 pytorch_half_pixel, 2 align_corners, 3 asymmetric
+    int nearest = 0;                   // ResizeNearest: 0 round_prefer_floor, 1 round_prefer_ceil, 2 floor, 3 ceil
+    double scale_h = 1.0, scale_w = 1.0;
+};
+// path 0: the generic kernel (one thread per output element); 1: 16-byte channel vectors NHWC -> NHWC; 2: NHWC -> NCHW, one thread per output
+// pixel looping over the channels (stores coalesced along W).  ResizePath picks the fastest one the operands allow.
+int ResizePath(const ResizeArgs& a);
+hipError_t LaunchResize(const ResizeArgs& a, int path, hipStream_t stream);
 hipError_t LaunchConvIgemm(const ConvArgs& a, int tile, int vec, int splitk, hipStream_t stream);
 // 3x3 / stride 1 / pad 1 with an LDS-resident input window (see kernels.hip).  tile: 0..kNumConvRasterTiles-1.
 constexpr int kNumConvRasterTiles = 8;

@@ -100,7 +100,9 @@ __device__ __forceinline__ bool splitk_combine(f32x16 (&acc)[TM][TN], float* __r
 // ------------------------------------------------------------------------------------------------
 // implicit-GEMM convolution on v_mfma_f32_32x32x2_f32
 // ------------------------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, int KG, bool VEC, bool PRE, bool DEEP>
+// DIL: tap (ky, kx) reads input pixel (iy0 + ky*dh, ix0 + kx*dw) (ConvArgs::dh / dw); without it the taps are adjacent and the kernel is the
+// one every undilated conv runs
+template <int BM, int BN, int WM, int WN, int KG, bool VEC, bool PRE, bool DEEP, bool DIL = false>
 __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_kernel(const ConvArgs a, const int tiles_n, const int num_tiles) {
     constexpr int NT = 64 * WM * WN;            // threads of one K-group (they stage and compute one K-slice together)
     constexpr int BK = kIgemmBK;
@@ -141,6 +143,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_kernel(const Con
     const float* __restrict__ wgt = a.w;
     const bool has_pre = a.pre_scale != nullptr;
     const int nsplit = gridDim.y, split = blockIdx.y;   // split-K over workgroups: grid.y slices the K-tiles
+    const int dh = DIL ? int(a.dh) : 1, dw = DIL ? int(a.dw) : 1;
 
     f32x16 acc[TM][TN];
     auto zero_acc = [&]() {
@@ -300,7 +303,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_kernel(const Con
                 unsigned msk = 0;
                 for (int ky = 0; ky < a.kh; ++ky)
                     for (int kx = 0; kx < a.kw; ++kx)
-                        if (unsigned(iy0 + ky) < unsigned(H) && unsigned(ix0 + kx) < unsigned(W)) msk |= 1u << (ky * a.kw + kx);
+                        if (unsigned(iy0 + ky * dh) < unsigned(H) && unsigned(ix0 + kx * dw) < unsigned(W)) msk |= 1u << (ky * a.kw + kx);
                 taps[i] = mok ? msk : 0u;
             }
 #pragma unroll
@@ -319,7 +322,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_kernel(const Con
             const int tap = kt / cblocks;
             const int c0 = (kt - tap * cblocks) * BK;
             const int ky = tap / a.kw, kx = tap - ky * a.kw;
-            const int tapoff = ky * ish + kx * isw + c0;          // scalar
+            const int tapoff = ky * dh * ish + kx * dw * isw + c0;          // scalar
             const int woff = tap * Cin + c0;                      // scalar
             const bool cok = c0 + c4 < Cin;
             unsigned okmask = 0;
@@ -489,7 +492,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_kernel(const Con
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
                 const int row = rw + i * ROWS_PER_PASS;
-                const int iy = s_iy0[row] + ky, ix = s_ix0[row] + kx;
+                const int iy = s_iy0[row] + ky * dh, ix = s_ix0[row] + kx * dw;
                 const bool ok = kok && unsigned(iy) < unsigned(H) && unsigned(ix) < unsigned(W);
                 okA |= ok ? (1u << i) : 0u;
                 const int64_t off = ok ? s_rbase[row] + int64_t(iy) * a.in.sh + int64_t(ix) * a.in.sw + int64_t(c) * a.in.sc : 0;
@@ -608,7 +611,7 @@ static size_t igemm_lds_bytes() {
     return b;
 }
 
-template <int T, bool VEC, bool PRE>
+template <int T, bool VEC, bool PRE, bool DIL = false>
 static hipError_t launch_igemm_t(const ConvArgs& a, int splitk, hipStream_t stream) {
     constexpr IgemmTile t = kIgemmTiles[T];
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
@@ -618,11 +621,11 @@ static hipError_t launch_igemm_t(const ConvArgs& a, int splitk, hipStream_t stre
     if (t.kg > 1 && splitk > 1 && a.counters != nullptr) return hipErrorInvalidValue;   // in-launch combine assumes one K-group
     int grid = num_tiles;
     if (VEC && t.kg == 1 && !t.deep && !(splitk > 1 && a.counters != nullptr)) {
-        const int slots = PersistentSlots(reinterpret_cast<const void*>(&conv_igemm_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, VEC, PRE, (t.deep != 0)>),
+        const int slots = PersistentSlots(reinterpret_cast<const void*>(&conv_igemm_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, VEC, PRE, (t.deep != 0), DIL>),
                                           64 * t.wm * t.wn * t.kg, igemm_lds_bytes<T, VEC>());
         grid = PersistentGrid(num_tiles, slots, splitk);
     }
-    conv_igemm_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, VEC, PRE, (t.deep != 0)>
+    conv_igemm_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, VEC, PRE, (t.deep != 0), DIL>
         <<<dim3(grid, splitk), dim3(64 * t.wm * t.wn * t.kg), igemm_lds_bytes<T, VEC>(), stream>>>(a, tiles_n, num_tiles);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || splitk == 1 || a.counters != nullptr) return e;
@@ -632,10 +635,10 @@ static hipError_t launch_igemm_t(const ConvArgs& a, int splitk, hipStream_t stre
     return hipGetLastError();
 }
 
-template <int T, bool VEC, bool PRE>
+template <int T, bool VEC, bool PRE, bool DIL = false>
 static hipError_t init_igemm_t() {
     constexpr IgemmTile t = kIgemmTiles[T];
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, VEC, PRE, (t.deep != 0)>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, VEC, PRE, (t.deep != 0), DIL>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(igemm_lds_bytes<T, VEC>()));
 }
 
@@ -661,6 +664,19 @@ hipError_t LaunchConvIgemm(const ConvArgs& a_in, int tile, int vec, int splitk, 
             return hipErrorInvalidValue;
         if (a.pre_scale && ((reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift) & 15)))
             return hipErrorInvalidValue;
+    }
+    if (a.dh != 1 || a.dw != 1) {
+        // dilated convs: the base tiles (kg == 1, no deep prefetch), vector or scalar staging
+        if (a.dh < 1 || a.dw < 1 || tile < 0 || tile >= kNumIgemmBaseTiles) return hipErrorInvalidValue;
+#define IE_CASE(T)                                                                                                                     \
+    case T:                                                                                                                             \
+        if (!vec) return launch_igemm_t<T, false, false, true>(a, splitk, stream);                                                      \
+        return a.pre_scale ? launch_igemm_t<T, true, true, true>(a, splitk, stream) : launch_igemm_t<T, true, false, true>(a, splitk, stream);
+        switch (tile) {
+            IE_CASE(0) IE_CASE(1) IE_CASE(2) IE_CASE(3) IE_CASE(4) IE_CASE(5) IE_CASE(6)
+            default: return hipErrorInvalidValue;
+        }
+#undef IE_CASE
     }
 #define IE_CASE(T)                                                                                  \
     case T:                                                                                          \
@@ -689,6 +705,12 @@ hipError_t InitKernels() {
     if ((e = init_igemm_t<T, true, false>()) != hipSuccess) return e;  \
     if ((e = init_igemm_t<T, false, false>()) != hipSuccess) return e;
     IE_INIT(0) IE_INIT(1) IE_INIT(2) IE_INIT(3) IE_INIT(4) IE_INIT(5) IE_INIT(6)
+#undef IE_INIT
+#define IE_INIT(T)                                                           \
+    if ((e = init_igemm_t<T, true, true, true>()) != hipSuccess) return e;   \
+    if ((e = init_igemm_t<T, true, false, true>()) != hipSuccess) return e;  \
+    if ((e = init_igemm_t<T, false, false, true>()) != hipSuccess) return e;
+    IE_INIT(0) IE_INIT(1) IE_INIT(2) IE_INIT(3) IE_INIT(4) IE_INIT(5) IE_INIT(6)     // the dilated instantiations
 #undef IE_INIT
 #define IE_INIT_VEC(T)                                                 \
     if ((e = init_igemm_t<T, true, true>()) != hipSuccess) return e;   \
@@ -1061,10 +1083,10 @@ __global__ void conv_naive_kernel(const ConvArgs a, const int64_t total) {
     float acc = 0.f;
     const float* wrow = a.w + int64_t(n) * a.kh * a.kw * Cin;
     for (int ky = 0; ky < a.kh; ++ky) {
-        const int iy = oy * a.sh - a.pt + ky;
+        const int iy = oy * a.sh - a.pt + ky * a.dh;
         if (unsigned(iy) >= unsigned(a.in.h)) continue;
         for (int kx = 0; kx < a.kw; ++kx) {
-            const int ix = ox * a.sw - a.pl + kx;
+            const int ix = ox * a.sw - a.pl + kx * a.dw;
             if (unsigned(ix) >= unsigned(a.in.w)) continue;
             const int64_t px = int64_t(b) * a.in.sn + int64_t(iy) * a.in.sh + int64_t(ix) * a.in.sw;
             const float* wp = wrow + (ky * a.kw + kx) * Cin;

@@ -18,7 +18,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-template <int BM, int BN, int WM, int WN, int KG, bool PRE>
+// DIL: tap (ky, kx) reads input pixel (iy0 + ky*dh, ix0 + kx*dw) (ConvArgs::dh / dw), as in the fp32 kernel
+template <int BM, int BN, int WM, int WN, int KG, bool PRE, bool DIL = false>
 __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_f16_kernel(const ConvArgs a, const int tiles_n, const int num_tiles,
                                                                                   const int vec_store) {
     constexpr int NT = 64 * WM * WN;             // threads of one K-group
@@ -55,6 +56,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_f16_kernel(const
     const int M = a.out.n * OH * OW;
     const int Ktot = a.kh * a.kw * Cin;
     const int nsplit = gridDim.y, split = blockIdx.y;
+    const int dh = DIL ? int(a.dh) : 1, dw = DIL ? int(a.dw) : 1;
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_f16_kernel(const
         unsigned msk = 0;
         for (int ky = 0; ky < a.kh; ++ky)
             for (int kx = 0; kx < a.kw; ++kx)
-                if (unsigned(iy0 + ky) < unsigned(H) && unsigned(ix0 + kx) < unsigned(W)) msk |= 1u << (ky * a.kw + kx);
+                if (unsigned(iy0 + ky * dh) < unsigned(H) && unsigned(ix0 + kx * dw) < unsigned(W)) msk |= 1u << (ky * a.kw + kx);
         taps[i] = mok ? msk : 0u;
     }
 #pragma unroll
@@ -139,7 +141,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_f16_kernel(const
         const int tap = kt / cblocks;
         const int c0 = (kt - tap * cblocks) * BKE;
         const int ky = tap / a.kw, kx = tap - ky * a.kw;
-        const int tapoff = ky * ish + kx * isw + c0;
+        const int tapoff = ky * dh * ish + kx * dw * isw + c0;
         const int woff = tap * Cin + c0;
         const bool cok = c0 + c8 < Cin;
         if constexpr (PRE) {
@@ -277,7 +279,7 @@ static size_t f16_lds_bytes() {
     return size_t(2) * (t.bm + t.bn) * 72 * sizeof(_Float16) * t.kg;
 }
 
-template <int T, bool PRE>
+template <int T, bool PRE, bool DIL = false>
 static hipError_t launch_f16_t(const ConvArgs& a, int splitk, hipStream_t stream) {
     constexpr IgemmTile t = kIgemmTiles[T];
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
@@ -289,17 +291,17 @@ static hipError_t launch_f16_t(const ConvArgs& a, int splitk, hipStream_t stream
     if (splitk > 1) vec_store = (a.out.c % 4 == 0) && (reinterpret_cast<uintptr_t>(a.workspace) % 16 == 0);
     else if (a.out.f16) vec_store = (a.out.c % 4 == 0) && (a.out.sw % 4 == 0) && (reinterpret_cast<uintptr_t>(a.out.p) % 8 == 0);
     else vec_store = (a.out.c % 4 == 0) && (a.out.sw % 4 == 0) && (reinterpret_cast<uintptr_t>(a.out.p) % 16 == 0);
-    conv_igemm_f16_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, PRE>
+    conv_igemm_f16_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, PRE, DIL>
         <<<dim3(num_tiles, splitk), dim3(64 * t.wm * t.wn * t.kg), f16_lds_bytes<T>(), stream>>>(a, tiles_n, num_tiles, vec_store);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || splitk == 1) return e;
     return LaunchSplitKReduce(a, splitk, stream);
 }
 
-template <int T, bool PRE>
+template <int T, bool PRE, bool DIL = false>
 static hipError_t init_f16_t() {
     constexpr IgemmTile t = kIgemmTiles[T];
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f16_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, PRE>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f16_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, PRE, DIL>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
@@ -315,6 +317,17 @@ hipError_t LaunchConvIgemmF16(const ConvArgs& a_in, int tile, int splitk, hipStr
     a.in_bytes = 2 * (int64_t(a.in.n - 1) * a.in.sn + int64_t(a.in.h - 1) * a.in.sh + int64_t(a.in.w - 1) * a.in.sw + int64_t(a.in.c - 1) + 1);
     if (a.in_bytes >= (int64_t(1) << 31) || int64_t(a.out.c) * a.kh * a.kw * a.in.c * 2 >= (int64_t(1) << 31)) return hipErrorInvalidValue;
     if (int64_t(a.out.n) * a.out.h * a.out.w * a.out.sw >= (int64_t(1) << 31) || splitk < 1 || splitk > 64) return hipErrorInvalidValue;
+    if (a.dh != 1 || a.dw != 1) {
+        // dilated convs: the base tiles only (kg == 1), as in the fp32 kernel
+        if (a.dh < 1 || a.dw < 1 || tile < 0 || tile >= kNumIgemmBaseTiles) return hipErrorInvalidValue;
+#define IE_CASE(T) \
+    case T: return a.pre_scale ? launch_f16_t<T, true, true>(a, splitk, stream) : launch_f16_t<T, false, true>(a, splitk, stream);
+        switch (tile) {
+            IE_CASE(0) IE_CASE(1) IE_CASE(2) IE_CASE(3) IE_CASE(4) IE_CASE(5) IE_CASE(6)
+            default: return hipErrorInvalidValue;
+        }
+#undef IE_CASE
+    }
 #define IE_CASE(T) \
     case T: return a.pre_scale ? launch_f16_t<T, true>(a, splitk, stream) : launch_f16_t<T, false>(a, splitk, stream);
     switch (tile) {
@@ -330,6 +343,11 @@ hipError_t InitKernelsF16() {
     if ((e = init_f16_t<T, true>()) != hipSuccess) return e;    \
     if ((e = init_f16_t<T, false>()) != hipSuccess) return e;
     IE_INIT(0) IE_INIT(1) IE_INIT(2) IE_INIT(3) IE_INIT(4) IE_INIT(5) IE_INIT(6) IE_INIT(7) IE_INIT(8) IE_INIT(9) IE_INIT(10)
+#undef IE_INIT
+#define IE_INIT(T)                                                    \
+    if ((e = init_f16_t<T, true, true>()) != hipSuccess) return e;    \
+    if ((e = init_f16_t<T, false, true>()) != hipSuccess) return e;
+    IE_INIT(0) IE_INIT(1) IE_INIT(2) IE_INIT(3) IE_INIT(4) IE_INIT(5) IE_INIT(6)     // the dilated instantiations
 #undef IE_INIT
     return hipSuccess;
 }

@@ -39,7 +39,7 @@ struct Val {
     bool dedicated = false;             // its buffer is never recycled
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -49,7 +49,13 @@ struct LNode {
     std::vector<int> in;
     int out = -1;
     int kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0, pb = 0, pr = 0;
+    int dil_h = 1, dil_w = 1;           // conv dilation (1 on an axis whose kernel extent is 1)
     bool count_include_pad = false;
+    // L_RESIZE: mode, coordinate transform, nearest rounding, the scales (output / input) the coordinate transform divides by
+    ResizeMode rs_mode = ResizeMode::Nearest;
+    ResizeCoord rs_coord = ResizeCoord::HalfPixel;
+    ResizeNearest rs_nearest = ResizeNearest::RoundPreferFloor;
+    double rs_sh = 1.0, rs_sw = 1.0;
     std::vector<float> w, bias;         // conv: w packed [Cout][kh][kw][Cin]
     std::vector<float> s, t;            // affine
     bool has_pre = false, pre_relu = false, relu = false;
@@ -76,6 +82,8 @@ struct Lowering {
     // initializers produced at plan time by folding shape-only ops (Unsqueeze / Squeeze / Reshape / Flatten / Identity) whose
     // input is itself a constant: model-zoo exports of Caffe BN+Scale pairs route the [C] scale and bias through Unsqueeze nodes
     std::map<std::string, OnnxTensor> derived;
+    // derived initializers computed from a Shape node (and the int64 arithmetic behind it): only a Resize's `sizes` may read them
+    std::set<std::string> shape_derived;
 
     explicit Lowering(const OnnxModel& mm) : m(mm) {}
 
@@ -145,8 +153,8 @@ void conv_out_hw(int64_t h, int64_t w, const LNode& n, bool ceil_mode, int64_t& 
         if (num < 0) fail("kernel larger than padded input in node " + n.name);
         return (ceil_mode ? (num + s - 1) / s : num / s) + 1;
     };
-    oh = f(h, n.kh, n.sh, n.pt, n.pb);
-    ow = f(w, n.kw, n.sw, n.pl, n.pr);
+    oh = f(h, (n.kh - 1) * n.dil_h + 1, n.sh, n.pt, n.pb);     // a dilated window spans (k - 1) * d + 1 pixels
+    ow = f(w, (n.kw - 1) * n.dil_w + 1, n.sw, n.pl, n.pr);
 }
 
 void read_window_attrs(const OnnxNode& on, LNode& n, int64_t h, int64_t w, bool is_conv, const OnnxTensor* wt) {
@@ -157,7 +165,11 @@ void read_window_attrs(const OnnxNode& on, LNode& n, int64_t h, int64_t w, bool 
     auto st = on.attr_ints("strides", {1, 1});
     n.sh = int(st[0]); n.sw = int(st[1]);
     auto dl = on.attr_ints("dilations", {1, 1});
-    if (dl[0] != 1 || dl[1] != 1) fail("node " + on.name + ": dilations != 1 are not supported");
+    if (dl.size() != 2 || dl[0] < 1 || dl[1] < 1) fail("node " + on.name + ": dilations must be two positive integers");
+    if (!is_conv && (dl[0] != 1 || dl[1] != 1)) fail(on.op + " " + on.name + ": dilations != 1 are only supported on Conv");
+    // a kernel extent of 1 reads one pixel whatever the dilation: such an axis is planned undilated
+    n.dil_h = n.kh == 1 ? 1 : int(dl[0]);
+    n.dil_w = n.kw == 1 ? 1 : int(dl[1]);
     auto pads = on.attr_ints("pads", {0, 0, 0, 0});
     if (pads.size() != 4) fail("node " + on.name + ": pads must have 4 entries");
     n.pt = int(pads[0]); n.pl = int(pads[1]); n.pb = int(pads[2]); n.pr = int(pads[3]);
@@ -172,8 +184,8 @@ void read_window_attrs(const OnnxNode& on, LNode& n, int64_t h, int64_t w, bool 
                 int64_t a = tot / 2, b = tot - a;
                 if (mode == "SAME_UPPER") { p0 = int(a); p1 = int(b); } else { p0 = int(b); p1 = int(a); }
             };
-            same(h, n.kh, n.sh, n.pt, n.pb);
-            same(w, n.kw, n.sw, n.pl, n.pr);
+            same(h, (n.kh - 1) * n.dil_h + 1, n.sh, n.pt, n.pb);
+            same(w, (n.kw - 1) * n.dil_w + 1, n.sw, n.pl, n.pr);
         } else fail("node " + on.name + ": unsupported auto_pad " + mode);
     }
 }
@@ -316,6 +328,102 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         auto act_input = [&](size_t k) { return k < on.inputs.size() && !on.inputs[k].empty() && !L.init(on.inputs[k]); };
         std::vector<int64_t> odims;
 
+        // ---- Shape arithmetic: every shape is known at plan time, so Shape -> Gather / Slice -> Unsqueeze -> Concat (-> Cast), the way torch
+        //      exports the `sizes` of an F.interpolate, folds into derived int64 initializers.  Only a Resize's `sizes` may read the result ----
+        {
+            const bool folding = op == "Shape" || op == "Gather" || op == "Slice" || op == "Cast" || op == "Concat" || op == "Unsqueeze" || op == "Squeeze" ||
+                                 op == "Reshape" || op == "Flatten" || op == "Identity";
+            bool from_shape = op == "Shape";
+            for (size_t k = 0; k < on.inputs.size(); ++k) {
+                if (!L.shape_derived.count(on.inputs[k])) continue;
+                const bool sizes_in = (op == "Resize" && k == 3);
+                if (!folding && !sizes_in)
+                    fail(op + " " + n.name + ": reads the shape arithmetic of a Shape node; shapes are only supported as the sizes of a Resize");
+                from_shape = true;
+            }
+            if (from_shape && folding && op != "Shape" && !L.init(on.inputs[0]))
+                fail(op + " " + n.name + ": reads the shape arithmetic of a Shape node; shapes are only supported as the sizes of a Resize");
+            if (from_shape && folding) {
+                OnnxTensor t;
+                t.dtype = ONNX_INT64;
+                auto const_in = [&](size_t k) -> const OnnxTensor& {
+                    const OnnxTensor* c = k < on.inputs.size() && !on.inputs[k].empty() ? L.init(on.inputs[k]) : nullptr;
+                    if (!c) fail(op + " " + n.name + ": shape arithmetic needs constant operands");
+                    return *c;
+                };
+                auto ints_of = [&](const OnnxTensor& c) {
+                    if (!c.i.empty() || c.numel() == 0) return c.i;
+                    std::vector<int64_t> v;
+                    for (float f : c.f) v.push_back(int64_t(f));
+                    return v;
+                };
+                if (op == "Shape") {
+                    const Val& X = L.vals[in_val(0)];
+                    int64_t r = int64_t(X.dims.size());
+                    int64_t b = on.attr_i("start", 0), e = on.attr_i("end", r);
+                    if (b < 0) b += r;
+                    if (e < 0) e += r;
+                    b = std::clamp<int64_t>(b, 0, r);
+                    e = std::clamp<int64_t>(e, b, r);
+                    t.i.assign(X.dims.begin() + b, X.dims.begin() + e);
+                    t.dims = {e - b};
+                } else if (op == "Gather") {
+                    const std::vector<int64_t> d = ints_of(const_in(0));
+                    const OnnxTensor& ix = const_in(1);
+                    if (const_in(0).dims.size() != 1 || on.attr_i("axis", 0) != 0) fail("Gather " + n.name + ": shape arithmetic only gathers from a 1-D shape");
+                    for (int64_t v : ints_of(ix)) {
+                        if (v < 0) v += int64_t(d.size());
+                        if (v < 0 || v >= int64_t(d.size())) fail("Gather " + n.name + ": index out of range");
+                        t.i.push_back(d[size_t(v)]);
+                    }
+                    t.dims = ix.dims;
+                } else if (op == "Slice") {
+                    const std::vector<int64_t> d = ints_of(const_in(0));
+                    const int64_t r = int64_t(d.size());
+                    std::vector<int64_t> st = on.attr_ints("starts", {}), en = on.attr_ints("ends", {}), ax = on.attr_ints("axes", {0}), stp = {1};
+                    if (on.inputs.size() > 1) {              // opset >= 10: starts, ends, axes, steps are inputs
+                        st = ints_of(const_in(1));
+                        en = ints_of(const_in(2));
+                        if (on.inputs.size() > 3 && !on.inputs[3].empty()) ax = ints_of(const_in(3));
+                        if (on.inputs.size() > 4 && !on.inputs[4].empty()) stp = ints_of(const_in(4));
+                    }
+                    if (st.size() != 1 || en.size() != 1 || ax.size() != 1 || (ax[0] != 0 && ax[0] != -1) || stp.size() != 1 || stp[0] != 1)
+                        fail("Slice " + n.name + ": shape arithmetic only slices a 1-D shape with step 1");
+                    int64_t b = st[0] < 0 ? st[0] + r : st[0], e = en[0] < 0 ? en[0] + r : en[0];
+                    b = std::clamp<int64_t>(b, 0, r);
+                    e = std::clamp<int64_t>(e, b, r);
+                    t.i.assign(d.begin() + b, d.begin() + e);
+                    t.dims = {e - b};
+                } else if (op == "Concat") {
+                    for (size_t k = 0; k < on.inputs.size(); ++k) {
+                        const OnnxTensor& c = const_in(k);
+                        if (c.dims.size() > 1) fail("Concat " + n.name + ": shape arithmetic only concatenates 1-D tensors (" + on.inputs[k] + " has rank " + std::to_string(c.dims.size()) + ")");
+                        const std::vector<int64_t> v = ints_of(c);
+                        t.i.insert(t.i.end(), v.begin(), v.end());
+                    }
+                    t.dims = {int64_t(t.i.size())};
+                } else if (op == "Cast") {
+                    const OnnxTensor& c = const_in(0);
+                    const int64_t to = on.attr_i("to", ONNX_INT64);
+                    t = c;
+                    if (to == ONNX_INT64 || to == ONNX_INT32) { t.i = ints_of(c); t.f.clear(); t.dtype = int(to); }
+                    else if (to == ONNX_FLOAT || to == ONNX_DOUBLE) { t.f.clear(); for (int64_t v : ints_of(c)) t.f.push_back(float(v)); t.i.clear(); t.dtype = int(to); }
+                    else fail("Cast " + n.name + ": shape arithmetic only casts to integer or floating-point types");
+                } else {
+                    t.dtype = -1;                            // Unsqueeze / Squeeze / Reshape / Flatten / Identity: the constant folding below
+                }
+                if (t.dtype != -1) {
+                    t.name = on.outputs[0];
+                    if (L.derived.count(t.name) || m.initializers.count(t.name) || L.val_of.count(t.name))
+                        fail("ONNX graph error: value defined twice: " + t.name);
+                    L.derived[t.name] = std::move(t);
+                    L.shape_derived.insert(on.outputs[0]);
+                    continue;
+                }
+                L.shape_derived.insert(on.outputs[0]);
+            }
+        }
+
         // ---- shape-only ops on constants fold into a derived initializer (nothing is emitted) ----
         if ((op == "Unsqueeze" || op == "Squeeze" || op == "Reshape" || op == "Flatten" || op == "Identity") && L.init(on.inputs[0])) {
             OnnxTensor t = *L.init(on.inputs[0]);
@@ -422,6 +530,26 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 const OnnxTensor* b = L.init(on.inputs[2]);
                 if (!b || b->numel() != co) fail("Conv " + n.name + ": bias must be a [Cout] initializer");
                 n.bias = b->f;
+            }
+            if (n.dil_h > 1 || n.dil_w > 1) {
+                if (group != 1)
+                    fail("Conv " + n.name + ": dilated " + std::string(n.dw ? "depthwise" : "grouped") + " convolutions are not supported (dilations " +
+                         std::to_string(n.dil_h) + "x" + std::to_string(n.dil_w) + ", group = " + std::to_string(group) + ")");
+                // Centre-tap collapse (exact): stride 1, odd k, pads d * (k / 2) and d >= the image extent on every dilated axis.  The nearest
+                // off-centre tap is d pixels from the output pixel, so it lands in the padding for EVERY output pixel: the conv is the 1x1 conv of
+                // its centre weights (DeepLabV3's rate-36 ASPP branch at 28x28).  It then takes every 1x1 path, and its FLOPs are the 1x1's.
+                auto centre_only = [](int k, int d, int s, int p0, int p1, int64_t len) {
+                    return k == 1 ? (p0 == 0 && p1 == 0) : (s == 1 && k % 2 == 1 && p0 == d * (k / 2) && p1 == p0 && d >= len);
+                };
+                if (centre_only(n.kh, n.dil_h, n.sh, n.pt, n.pb, X.h) && centre_only(n.kw, n.dil_w, n.sw, n.pl, n.pr, X.w)) {
+                    std::vector<float> wc(size_t(co * ci));
+                    for (int64_t o = 0; o < co; ++o)
+                        for (int64_t c = 0; c < ci; ++c) wc[size_t(o * ci + c)] = n.w[size_t(((o * n.kh + n.kh / 2) * n.kw + n.kw / 2) * ci + c)];
+                    n.w = std::move(wc);
+                    n.kh = n.kw = 1;
+                    n.pt = n.pl = n.pb = n.pr = 0;
+                    n.dil_h = n.dil_w = 1;
+                }
             }
             int64_t oh, ow;
             conv_out_hw(X.h, X.w, n, false, oh, ow);
@@ -640,6 +768,83 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                     odims = d;
                 }
             }
+        } else if (op == "Resize" || op == "Upsample") {
+            // Resize-10 / 11 / 13 / 18 / 19 and Upsample-7 / 9 over 4-D tensors, scaling H and W only.  Resize-10 and Upsample have no
+            // coordinate_transformation_mode: they are `asymmetric` (with floor rounding for nearest, what the opset-10 definitions compute)
+            if (!act_input(0)) fail(op + " " + n.name + ": constant input is not supported");
+            const int x = in_val(0);
+            const Val& X = L.vals[x];
+            if (X.dims.size() != 4) fail(op + " " + n.name + ": only 4-D inputs are supported");
+            const bool legacy = op == "Upsample" || m.opset < 11;
+            std::string mode = "nearest";
+            if (on.attrs.count("mode")) mode = on.attrs.at("mode").s;
+            if (mode == "nearest") n.rs_mode = ResizeMode::Nearest;
+            else if (mode == "linear" || mode == "bilinear") n.rs_mode = ResizeMode::Linear;
+            else fail(op + " " + n.name + ": mode '" + mode + "' is not supported (nearest and linear are)");
+            std::string coord = legacy ? "asymmetric" : "half_pixel";
+            if (!legacy && on.attrs.count("coordinate_transformation_mode")) coord = on.attrs.at("coordinate_transformation_mode").s;
+            if (coord == "half_pixel") n.rs_coord = ResizeCoord::HalfPixel;
+            else if (coord == "pytorch_half_pixel") n.rs_coord = ResizeCoord::PytorchHalfPixel;
+            else if (coord == "align_corners") n.rs_coord = ResizeCoord::AlignCorners;
+            else if (coord == "asymmetric") n.rs_coord = ResizeCoord::Asymmetric;
+            else fail(op + " " + n.name + ": coordinate_transformation_mode '" + coord + "' is not supported");
+            std::string nearest = legacy ? "floor" : "round_prefer_floor";
+            if (!legacy && on.attrs.count("nearest_mode")) nearest = on.attrs.at("nearest_mode").s;
+            if (nearest == "round_prefer_floor") n.rs_nearest = ResizeNearest::RoundPreferFloor;
+            else if (nearest == "round_prefer_ceil") n.rs_nearest = ResizeNearest::RoundPreferCeil;
+            else if (nearest == "floor") n.rs_nearest = ResizeNearest::Floor;
+            else if (nearest == "ceil") n.rs_nearest = ResizeNearest::Ceil;
+            else fail(op + " " + n.name + ": nearest_mode '" + nearest + "' is not supported");
+            if (on.attr_i("antialias", 0) != 0) fail(op + " " + n.name + ": antialias = 1 is not supported");
+            if (on.attrs.count("keep_aspect_ratio_policy") && on.attrs.at("keep_aspect_ratio_policy").s != "stretch")
+                fail(op + " " + n.name + ": keep_aspect_ratio_policy '" + on.attrs.at("keep_aspect_ratio_policy").s + "' is not supported (stretch is)");
+            const bool has_axes = on.attrs.count("axes") != 0;
+            std::vector<int64_t> axes = on.attr_ints("axes", {0, 1, 2, 3});
+            for (auto& a : axes) {
+                if (a < 0) a += 4;
+                if (a < 0 || a > 3 || (has_axes && a < 2)) fail(op + " " + n.name + ": axes must be a subset of {2, 3}");
+            }
+            // the scales / sizes operand: Upsample-7 an attribute, Upsample-9 / Resize-10 input 1, Resize-11+ input 2 (scales) or 3 (sizes)
+            auto operand = [&](size_t k) -> const OnnxTensor* {
+                if (k >= on.inputs.size() || on.inputs[k].empty()) return nullptr;
+                const OnnxTensor* t = L.init(on.inputs[k]);
+                if (!t) fail(op + " " + n.name + ": " + (k == 3 ? "sizes" : "scales") + " must be a constant (initializer or Constant node)");
+                return t->numel() == 0 ? nullptr : t;
+            };
+            std::vector<double> scales;
+            std::vector<int64_t> sizes;
+            if (op == "Upsample" && on.attrs.count("scales")) for (float f : on.attrs.at("scales").floats) scales.push_back(f);
+            else if (legacy) { if (const OnnxTensor* t = operand(1)) for (float f : t->f) scales.push_back(f); }
+            else {
+                if (const OnnxTensor* t = operand(2)) for (float f : t->f) scales.push_back(f);
+                if (const OnnxTensor* t = operand(3)) sizes = t->i;
+                if (!scales.empty() && !sizes.empty()) fail(op + " " + n.name + ": only one of scales and sizes may be given");
+            }
+            if (scales.empty() && sizes.empty()) fail(op + " " + n.name + ": scales or sizes must be given");
+            const size_t cnt = scales.empty() ? sizes.size() : scales.size();
+            if (cnt != axes.size()) fail(op + " " + n.name + ": " + (scales.empty() ? "sizes" : "scales") + " must have one entry per axis");
+            double sc[4] = {1, 1, 1, 1};
+            int64_t out[4] = {X.dims[0], X.dims[1], X.dims[2], X.dims[3]};
+            for (size_t k = 0; k < axes.size(); ++k) {
+                const int a = int(axes[k]);
+                if (scales.empty()) {
+                    if (sizes[k] <= 0) fail(op + " " + n.name + ": sizes must be positive");
+                    out[a] = sizes[k];
+                    sc[a] = double(sizes[k]) / double(X.dims[size_t(a)]);
+                } else {
+                    if (!(scales[k] > 0)) fail(op + " " + n.name + ": scales must be positive");
+                    sc[a] = scales[k];
+                    out[a] = int64_t(std::floor(double(X.dims[size_t(a)]) * scales[k]));
+                    if (out[a] <= 0) fail(op + " " + n.name + ": the output would be empty");
+                }
+            }
+            if (out[0] != X.dims[0] || out[1] != X.dims[1])
+                fail(op + " " + n.name + ": only the spatial axes (2 and 3) may be resized; N and C must keep their size");
+            n.kind = L_RESIZE;
+            n.rs_sh = sc[2];
+            n.rs_sw = sc[3];
+            n.in = {x};
+            odims = {out[0], out[1], out[2], out[3]};
         } else {
             fail("Unsupported ONNX operator: " + op + " (node " + n.name + ")");
         }
@@ -656,6 +861,8 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         for (const LNode& n : L.nodes) {
             if (n.dw) fail("depthwise convolution is not supported in fp8 mode (Conv " + n.name + ")");
             if (n.kind == L_CONV && n.group != 1) fail("grouped convolution is not supported in fp8 mode (Conv " + n.name + ")");
+            if (n.kind == L_CONV && (n.dil_h > 1 || n.dil_w > 1)) fail("dilated convolution is not supported in fp8 mode (Conv " + n.name + ")");
+            if (n.kind == L_RESIZE) fail("Resize is not supported in fp8 mode (node " + n.name + ")");
         }
 
     if (precision == Precision::F8 || f8_fusions)
@@ -969,6 +1176,14 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         // [N,C,1,1] / [N,C] tensors are already in ABI order and only need their own dense buffer.
         bool spatial = L.vals[v].h * L.vals[v].w > 1;
         bool consumed = !L.consumers(v).empty();
+        // a Resize whose result is read by nothing else writes the dense NCHW fp32 output itself (a segmentation head's last step)
+        const int pr = L.vals[v].producer;
+        if (spatial && !consumed && !L.vals[v].is_input && pr >= 0 && L.nodes[size_t(pr)].kind == L_RESIZE && !L.nodes[size_t(pr)].dead &&
+            std::find(out_vals.begin(), out_vals.end(), v) == out_vals.end()) {
+            L.vals[v].input_nchw = true;           // reused flag: dense NCHW layout
+            out_vals.push_back(v);
+            continue;
+        }
         if (spatial || L.vals[v].is_input || consumed) {
             LNode cp;
             cp.kind = L_COPY;
@@ -1042,7 +1257,9 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             while (nxt < order.size() && (L.nodes[order[nxt]].kind == L_CONCAT || L.nodes[order[nxt]].kind == L_ALIAS)) ++nxt;
             if (nxt >= order.size()) break;
             const LNode& b1 = L.nodes[order[nxt]];
-            if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre || a3.group != 1 || b1.group != 1) continue;
+            if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre || a3.group != 1 || b1.group != 1 ||
+                a3.dil_h != 1 || a3.dil_w != 1)
+                continue;
             if (L.vals[a3.out].c != 32 || L.vals[b1.out].c != 128 || L.vals[b1.in[0]].root != L.vals[a3.out].root) continue;
             if (L.vals[a3.out].n * L.vals[a3.out].h * L.vals[a3.out].w > FuseMaxPixels(env)) continue;
             const int rb = L.vals[a3.in[0]].root;
@@ -1170,6 +1387,10 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             case L_CONV: {
                 s.kind = StepKind::Conv;
                 s.kh = n.kh; s.kw = n.kw; s.sh = n.sh; s.sw = n.sw; s.pt = n.pt; s.pl = n.pl; s.pb = n.pb; s.pr = n.pr;
+                s.dh = n.dil_h; s.dw = n.dil_w;
+                // a dilated conv may only take the kernels that honour the dilation (plan.h DilationOk): the implicit GEMMs' base tiles and the
+                // naive kernel.  Every specialised kernel's eligibility below is false for it, and the forcing switches cannot move it elsewhere
+                const bool dil = s.dh > 1 || s.dw > 1;
                 s.w_off = push_vec(n.w);
                 if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
                 if (n.res >= 0) { s.in2 = view_of(n.res); s.has_in2 = true; }
@@ -1227,7 +1448,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 else if (K <= 2048 && !in16) s.algo = ConvAlgo::IgemmScalar;
                 else s.algo = ConvAlgo::Naive;
                 // the stem of an image classifier (7x7 / stride 2 / pad 3 over the 3-channel NCHW graph input) has its own kernel
-                const bool stem_ok = s.in.nchw && !in16 && s.in.c == 3 && n.kh == 7 && n.kw == 7 && n.sh == 2 && n.sw == 2 && n.pt == 3 &&
+                const bool stem_ok = !dil && s.in.nchw && !in16 && s.in.c == 3 && n.kh == 7 && n.kw == 7 && n.sh == 2 && n.sw == 2 && n.pt == 3 &&
                                      n.pl == 3 && n.pb == 3 && n.pr == 3 && !n.has_pre && N <= 64 && N % 8 == 0 && s.out.pitch % 8 == 0 &&
                                      s.out.c_off % 8 == 0 && s.in.numel() * 4 < (int64_t(1) << 31) &&
                                      s.out.n * s.out.h * s.out.w * s.out.pitch * 4 < (int64_t(1) << 31);
@@ -1254,7 +1475,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 // ---- plan-time eligibility of the specialised kernels (the launchers re-check pointers / alignment; the executor falls
                 //      back to the tiled implicit GEMM when a launcher declines) ----
                 const bool is1x1 = n.kh == 1 && n.kw == 1 && n.sh == 1 && n.sw == 1 && n.pt == 0 && n.pl == 0 && n.pb == 0 && n.pr == 0;
-                const bool is3x3 = n.kh == 3 && n.kw == 3 && n.sh == 1 && n.sw == 1 && n.pt == 1 && n.pl == 1 && n.pb == 1 && n.pr == 1;
+                const bool is3x3 = !dil && n.kh == 3 && n.kw == 3 && n.sh == 1 && n.sw == 1 && n.pt == 1 && n.pl == 1 && n.pb == 1 && n.pr == 1;
                 static const int ws_tn[14] = {4, 4, 2, 2, 1, 1, 4, 4, 2, 2, 1, 1, 1, 1};      // 12, 13: fp32 K-split variants (8 / 4 waves)
                 auto ws16_ok = [&](int t) {
                     if (t < 0 || t >= 18) return false;          // (12-17: the one-workgroup-per-CU grids of shapes 0-5)
@@ -1281,7 +1502,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 static const int dcfg[6][3] = {{1, 8, 8}, {1, 16, 4}, {1, 9, 8}, {1, 4, 8}, {1, 12, 6}, {2, 8, 4}};   // tn, waves, max chunks
                 static const int wcfg[4][3] = {{1, 8, 9}, {2, 8, 9}, {1, 4, 18}, {2, 4, 18}};                      // window variants: tn, waves, max chunks
                 auto direct_ok = [&](int t) {
-                    if (t < 0 || t >= 15) return false;
+                    if (t < 0 || t >= 15 || dil) return false;
                     if (t >= 10) {     // activations-stationary 1x1 (fp32): the workgroup's 32 / 16 pixel rows in LDS, weights streamed from the mirror
                         static const int acfg[5] = {128, 64, 256, 64, 64};                                        // output channels per workgroup
                         return vec_ok && !in16 && !s.out.f16 && !s.has_in2 && is1x1 && s.in.c % 16 == 0 && N % acfg[t - 10] == 0 && s.out.pitch % 4 == 0 &&
@@ -1335,7 +1556,9 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                     }
                 }
                 // Test / tuning overrides (read at plan time): IE_FORCE_TILE=<n>, IE_FORCE_ALGO=naive|scalar|igemm|raster|ws|direct
-                if (const char* fa = env.get("IE_FORCE_ALGO")) {
+                const char* fa = env.get("IE_FORCE_ALGO");
+                if (fa && dil && std::string(fa) != "naive" && std::string(fa) != "scalar" && std::string(fa) != "igemm") fa = nullptr;
+                if (fa) {
                     std::string f = fa;
                     if (f == "naive") s.algo = ConvAlgo::Naive;
                     else if (f == "scalar" && K <= 2048 && !in16) s.algo = ConvAlgo::IgemmScalar;
@@ -1383,7 +1606,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 if (const char* ft = (s.algo == ConvAlgo::Raster3x3 || s.algo == ConvAlgo::Ws1x1 || s.algo == ConvAlgo::Ws3x3 || s.algo == ConvAlgo::Stem || s.algo == ConvAlgo::Direct || s.algo == ConvAlgo::Wino3x3 || s.algo == ConvAlgo::X6) ? nullptr
                                                                                                                                           : env.get("IE_FORCE_TILE")) {
                     int t = std::atoi(ft);
-                    if (t >= 0 && t < kNumIgemmTiles && (t < kNumIgemmBaseTiles || s.algo == ConvAlgo::IgemmVec) && !(in16 && kIgemmTiles[t].deep)) s.tile = t;
+                    if (t >= 0 && t < kNumIgemmTiles && (t < kNumIgemmBaseTiles || (s.algo == ConvAlgo::IgemmVec && !dil)) && !(in16 && kIgemmTiles[t].deep)) s.tile = t;
                 }
                 if (s.algo != ConvAlgo::IgemmVec && s.algo != ConvAlgo::Raster3x3 && s.algo != ConvAlgo::Ws1x1 && s.algo != ConvAlgo::Ws3x3 && s.algo != ConvAlgo::Direct && s.algo != ConvAlgo::Wino3x3 && s.algo != ConvAlgo::X6 && s.tile >= kNumIgemmBaseTiles)
                     s.tile = heuristic_tile;       // K-group tiles exist for the vector path only
@@ -1492,6 +1715,16 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
                 s.bytes = vbytes(s.in) + vbytes(s.in2) + vbytes(s.out);
                 s.flops = double(s.in.numel());
                 break;
+            case L_RESIZE:
+                s.kind = StepKind::Resize;
+                s.rs_mode = n.rs_mode;
+                s.rs_coord = n.rs_coord;
+                s.rs_nearest = n.rs_nearest;
+                s.rs_scale_h = n.rs_sh;
+                s.rs_scale_w = n.rs_sw;
+                s.bytes = vbytes(s.in) + vbytes(s.out);
+                s.flops = n.rs_mode == ResizeMode::Linear ? 6.0 * double(s.out.numel()) : 0.0;    // two lerps per axis pair: 3 FMA-equivalents
+                break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -1523,7 +1756,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             if (i + 1 < plan.steps.size()) {
                 const Step& s1 = plan.steps[i + 1];
                 const int64_t M = s3.out.n * s3.out.h * s3.out.w;
-                fuse = s3.kind == StepKind::Conv && s1.kind == StepKind::Conv && !IsGroupConv(s3.algo) && !IsGroupConv(s1.algo) && s3.kh == 3 && s3.kw == 3 && s3.sh == 1 && s3.sw == 1 && s3.pt == 1 && s3.pl == 1 &&
+                fuse = s3.kind == StepKind::Conv && s1.kind == StepKind::Conv && !IsGroupConv(s3.algo) && !IsGroupConv(s1.algo) && s3.dh == 1 && s3.dw == 1 && s3.kh == 3 && s3.kw == 3 && s3.sh == 1 && s3.sw == 1 && s3.pt == 1 && s3.pl == 1 &&
                        s3.pb == 1 && s3.pr == 1 && s3.pre_scale_off < 0 && !s3.has_in2 && s3.out.c == 32 && s3.in.c % 16 == 0 && 9 * (s3.in.c / 16) <= 72 &&
                        9 * (s3.in.c / 16) >= 8 && s1.kh == 1 && s1.kw == 1 && s1.sh == 1 && s1.sw == 1 && s1.pt == 0 && s1.pl == 0 && s1.pb == 0 && s1.pr == 0 &&
                        !s1.has_in2 && s1.out.c == 128 && s1.in.buf == s3.out.buf && s1.in.pitch == s3.out.pitch && !s1.in.nchw && !s3.in.nchw &&
@@ -1590,6 +1823,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             if (IsGroupConv(s1.algo) || IsGroupConv(s3.algo)) return false;
             if (s1.kh != 1 || s1.kw != 1 || s1.sh != 1 || s1.sw != 1 || s1.pt || s1.pl || s1.pb || s1.pr || s1.has_in2 || s1.out.c != 128) return false;
             if (s3.kh != 3 || s3.kw != 3 || s3.sh != 1 || s3.sw != 1 || s3.pt != 1 || s3.pl != 1 || s3.pb != 1 || s3.pr != 1 || s3.has_in2 || s3.out.c != 32) return false;
+            if (s3.dh != 1 || s3.dw != 1) return false;
             if (s3.pre_scale_off >= 0 || s1.w_off < 0 || s3.w_off < 0) return false;
             if (!s1.in.f16 || !s1.out.f16 || !s3.out.f16 || s1.in.nchw || s1.out.nchw || s3.out.nchw) return false;
             if (!same_view(s3.in, s1.out) || s3.out.buf != s1.in.buf || s3.out.pitch != s1.in.pitch || s1.out.buf == s1.in.buf) return false;
@@ -1830,7 +2064,10 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize"};
+    static const char* rs_modes[] = {"nearest", "linear"};
+    static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
+    static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
     static const char* algos[] = {"igemm_vec", "igemm_scalar", "naive", "raster3x3", "ws1x1", "ws3x3", "stem", "direct", "igemm_f8", "dense_fused", "wino3x3", "conv1x1_x6", "dense_block", "dual_f8", "stem_pool", "depthwise", "grouped"};
     std::ostringstream o;
     o.precision(17);
@@ -1860,6 +2097,7 @@ std::string PlanToJson(const Plan& p) {
         o << ",\"out\":"; json_view(o, s.out);
         o << ",\"k\":[" << s.kh << "," << s.kw << "],\"stride\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt << ","
           << s.pl << "," << s.pb << "," << s.pr << "]";
+        if (s.dh != 1 || s.dw != 1) o << ",\"dilations\":[" << s.dh << "," << s.dw << "]";     // (dilated convs only: other plans are unchanged)
         o << ",\"pre\":" << (s.pre_scale_off >= 0 ? "true" : "false") << ",\"pre_relu\":" << (s.pre_relu ? "true" : "false")
           << ",\"relu\":" << (s.relu ? "true" : "false") << ",\"bias\":" << (s.bias_off >= 0 ? "true" : "false");
         // (only on the steps that have them: the plans of graphs without a Clip are unchanged)
@@ -1883,6 +2121,9 @@ std::string PlanToJson(const Plan& p) {
         if (s.kind == StepKind::Conv) o << ",\"algo\":\"" << algos[int(s.algo)] << "\",\"tile\":" << s.tile << ",\"splitk\":" << s.splitk;
         if (s.kind == StepKind::Conv && s.algo == ConvAlgo::Grouped) o << ",\"group\":" << s.group;      // (grouped steps only)
         if (s.kind == StepKind::Pool) o << ",\"max\":" << (s.pool_max ? "true" : "false");
+        if (s.kind == StepKind::Resize)
+            o << ",\"resize\":{\"mode\":\"" << rs_modes[int(s.rs_mode)] << "\",\"coord\":\"" << rs_coords[int(s.rs_coord)] << "\",\"nearest\":\""
+              << rs_nearest[int(s.rs_nearest)] << "\",\"scales\":[" << s.rs_scale_h << "," << s.rs_scale_w << "]}";
         if (!s.parts.empty()) {
             Plan sub;
             sub.steps = s.parts;

@@ -38,7 +38,12 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6 };
+
+// Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
+enum class ResizeMode : int { Nearest = 0, Linear = 1 };
+enum class ResizeCoord : int { HalfPixel = 0, PytorchHalfPixel = 1, AlignCorners = 2, Asymmetric = 3 };
+enum class ResizeNearest : int { RoundPreferFloor = 0, RoundPreferCeil = 1, Floor = 2, Ceil = 3 };
 
 // Pointwise activation fused into a step (kernels.h ApplyAct): sigmoid(x), hardsigmoid(x) = max(0, min(1, a*x + b)), silu(x) = x * sigmoid(x),
 // hardswish(x) = x * hardsigmoid(x; a, b) (the ONNX HardSwish op: a = 1/6, b = 1/2).  Relu only as a squeeze-excite block's inner activation.
@@ -78,6 +83,8 @@ enum class ConvAlgo : int {
 
 // The conv algorithms whose weights are not the dense [Cout][kh][kw][Cin] layout: no dense-conv pass or weight mirror may take their steps
 inline bool IsGroupConv(ConvAlgo a) { return a == ConvAlgo::Depthwise || a == ConvAlgo::Grouped; }
+// The conv algorithms that honour a dilation > 1 (the only ones a dilated step may take)
+inline bool DilationOk(ConvAlgo a) { return a == ConvAlgo::IgemmVec || a == ConvAlgo::IgemmScalar || a == ConvAlgo::Naive; }
 
 struct Step {
     StepKind kind = StepKind::Conv;
@@ -86,6 +93,7 @@ struct Step {
     bool has_in2 = false;
     // conv / pool geometry
     int kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0, pb = 0, pr = 0;
+    int dh = 1, dw = 1;        // conv dilation (> 1 only on IgemmVec / IgemmScalar / Naive steps)
     bool pool_max = false;
     bool count_include_pad = false;
     // offsets (in floats) into the weight blob; -1 = absent
@@ -106,6 +114,12 @@ struct Step {
     Act se_act1;
     int64_t w2_off = -1, bias2_off = -1;
     int se_chunks = 0;         // pixel chunks of the squeeze (kernels.h SeSqueezeChunks)
+    // Resize: in (NHWC, [N, C, 1, 1] broadcasts) -> out (NHWC, or the dense NCHW graph output); the coordinate transform divides by the given
+    // per-axis scales (output / input; the ONNX `scales`, or sizes / input when the graph gives `sizes`)
+    ResizeMode rs_mode = ResizeMode::Nearest;
+    ResizeCoord rs_coord = ResizeCoord::HalfPixel;
+    ResizeNearest rs_nearest = ResizeNearest::RoundPreferFloor;
+    double rs_scale_h = 1.0, rs_scale_w = 1.0;
     ConvAlgo algo = ConvAlgo::Naive;
     int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)

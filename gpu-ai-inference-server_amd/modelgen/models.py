@@ -1,5 +1,5 @@
-"""Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY and small
-test graphs).
+"""Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY,
+FCN-ResNet50, DeepLabV3-ResNet50 and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -38,8 +38,9 @@ class GraphBuilder:
         return name
 
     # ---- ops ----
-    def conv(self, x: str, cin: int, cout: int, k: int, stride: int = 1, pad: int = 0, bias: bool = False,
-             name: str | None = None, w_scale: float | None = None, group: int = 1) -> str:
+    def conv(self, x: str, cin: int, cout: int, k: int, stride: int = 1, pad: int | Sequence[int] = 0, bias: bool = False,
+             name: str | None = None, w_scale: float | None = None, group: int = 1, dilation: int = 1) -> str:
+        """pad: one value for all four sides or ONNX order [top, left, bottom, right]"""
         name = name or self._uid("conv")
         cg = cin // group                       # input channels per group (1 for a depthwise conv)
         fan_in = cg * k * k
@@ -51,8 +52,8 @@ class GraphBuilder:
             ins.append(self.init(name + "_b", b.astype(np.float32)))
         y = name + "_out"
         self.nodes.append(pb.node("Conv", ins, [y], name, [
-            pb.attr_ints("dilations", [1, 1]), pb.attr_int("group", group),
-            pb.attr_ints("kernel_shape", [k, k]), pb.attr_ints("pads", [pad] * 4),
+            pb.attr_ints("dilations", [dilation, dilation]), pb.attr_int("group", group),
+            pb.attr_ints("kernel_shape", [k, k]), pb.attr_ints("pads", [pad] * 4 if isinstance(pad, int) else list(pad)),
             pb.attr_ints("strides", [stride, stride])]))
         return y
 
@@ -157,6 +158,45 @@ class GraphBuilder:
         s = self.act(self.conv(s, c, mid, 1, bias=True, name=name + "_fc1", w_scale=float(np.sqrt(1.0 / c))), act1, form)
         s = self.act(self.conv(s, mid, c, 1, bias=True, name=name + "_fc2", w_scale=float(np.sqrt(1.0 / mid))), gate, form)
         return self.simple("Mul", [s, x] if swap else [x, s])
+
+    def resize(self, x: str, in_shape: Sequence[int], *, sizes: Sequence[int] | None = None, scales: Sequence[float] | None = None,
+               mode: str = "linear", coord: str = "pytorch_half_pixel", nearest: str | None = None, form: str = "sizes", opset: int = 11,
+               name: str | None = None, out: str | None = None) -> str:
+        """ONNX Resize of a 4-D tensor of `in_shape` to `sizes` [H, W] or by `scales` [sh, sw], in the forms exporters write:
+        form "scales": Resize(x, roi "", scales [1, 1, sh, sw]); "sizes": Resize(x, "", "", sizes [N, C, H, W]) (a concrete batch);
+        "shape": the sizes as torch exports them -- Shape(x) -> Gather(0), Gather(1) -> Unsqueeze -> Concat with [H, W] -> Cast;
+        "upsample": Upsample-9 (x, scales), asymmetric.  opset 10: Resize(x, scales), asymmetric."""
+        name = name or self._uid("resize")
+        attrs = [pb.attr_str("mode", mode)]
+        if form != "upsample" and opset >= 11:
+            attrs.append(pb.attr_str("coordinate_transformation_mode", coord))
+            if nearest is not None:
+                attrs.append(pb.attr_str("nearest_mode", nearest))
+        y = out or name + "_out"
+        if form in ("scales", "upsample") or opset < 11:
+            sc = self.init(name + "_scales", np.array([1.0, 1.0, *scales], np.float32))
+            ins = [x, sc] if (form == "upsample" or opset < 11) else [x, "", sc]
+            self.nodes.append(pb.node("Upsample" if form == "upsample" else "Resize", ins, [y], name, attrs))
+            return y
+        if form == "sizes":
+            sz = self.init(name + "_sizes", np.array([in_shape[0], in_shape[1], *sizes], np.int64))
+        elif form == "shape":
+            self.nodes.append(pb.node("Shape", [x], [name + "_shape"], name + "_shape"))
+            parts = []
+            for i in (0, 1):
+                idx = name + f"_i{i}"            # a scalar index (a Constant node: initializers here are at least 1-D)
+                self.nodes.append(pb.node("Constant", [], [idx], idx, [pb.attr_int("value_int", i)]))
+                self.nodes.append(pb.node("Gather", [name + "_shape", idx], [name + f"_g{i}"], name + f"_g{i}", [pb.attr_int("axis", 0)]))
+                self.nodes.append(pb.node("Unsqueeze", [name + f"_g{i}"], [name + f"_u{i}"], name + f"_u{i}", [pb.attr_ints("axes", [0])]))
+                parts.append(name + f"_u{i}")
+            hw = self.init(name + "_hw", np.array(list(sizes), np.int64))
+            self.nodes.append(pb.node("Concat", [*parts, hw], [name + "_cat"], name + "_cat", [pb.attr_int("axis", 0)]))
+            self.nodes.append(pb.node("Cast", [name + "_cat"], [name + "_sizes"], name + "_cast", [pb.attr_int("to", 7)]))
+            sz = name + "_sizes"
+        else:
+            raise ValueError(form)
+        self.nodes.append(pb.node("Resize", [x, "", "", sz], [y], name, attrs))
+        return y
 
     def concat(self, xs: Sequence[str], axis: int = 1) -> str:
         name = self._uid("concat")
@@ -343,7 +383,8 @@ def two_input_graph(batch: int | str = 2, ca: int = 8, cb: int = 16, image: int 
 
 
 def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width: int = 64, image: int = 224, classes: int = 1000,
-           seed: int = 50, in_name: str = "data", out_name: str = "logits", groups: int = 1, width_per_group: int = 64) -> bytes:
+           seed: int = 50, in_name: str = "data", out_name: str = "logits", groups: int = 1, width_per_group: int = 64,
+           dilate: Sequence[bool] = (False, False, False)) -> bytes:
     """ResNet-v1.5 bottleneck network (ResNet-50 with the defaults; BASELINE.json configs[4] names this architecture).
 
     groups / width_per_group give ResNeXt as torchvision builds it: the bottleneck's 3x3 is a grouped conv of
@@ -354,28 +395,12 @@ def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width:
     pool -> Flatten -> Gemm.  Exercises what DenseNet does not: residual Add + ReLU, strided 1x1 / 3x3 convs, Cout up to 2048,
     Conv->BN folding without a ReLU, a Gemm classifier.  The last BN of every block gets a small gamma (as zero-init-residual
     training leaves it) so activations stay O(1) through 16 residual additions.
+
+    dilate[i] replaces the stride of stage i + 2 by a dilation, as torchvision's replace_stride_with_dilation does: the first block of a
+    dilated stage keeps the previous dilation, the others use the doubled one (3x3 convs with pads = dilation).
     """
     gb = GraphBuilder("resnet", seed)
-    x = gb.conv(in_name, 3, width, 7, stride=2, pad=3, name="conv1")
-    x = gb.relu(gb.bn(x, width, name="bn1"))
-    x = gb.pool("MaxPool", x, 3, 2, pad=1)
-    cin = width
-    for si, nblocks in enumerate(layers):
-        planes = width * (2 ** si)
-        mid = int(planes * (width_per_group / 64.0)) * groups
-        cout = planes * 4
-        for bi in range(nblocks):
-            stride = 2 if (bi == 0 and si > 0) else 1
-            tag = f"s{si + 1}b{bi + 1}"
-            y = gb.relu(gb.bn(gb.conv(x, cin, mid, 1, name=tag + "_c1"), mid, name=tag + "_bn1"))
-            y = gb.relu(gb.bn(gb.conv(y, mid, mid, 3, stride=stride, pad=1, name=tag + "_c2", group=groups), mid, name=tag + "_bn2"))
-            y = gb.bn(gb.conv(y, mid, cout, 1, name=tag + "_c3", w_scale=float(0.5 * np.sqrt(2.0 / mid))), cout, name=tag + "_bn3")
-            if bi == 0:
-                sc = gb.bn(gb.conv(x, cin, cout, 1, stride=stride, name=tag + "_proj"), cout, name=tag + "_bnp")
-            else:
-                sc = x
-            x = gb.relu(gb.simple("Add", [y, sc]))
-            cin = cout
+    x, cin = _resnet_body(gb, in_name, layers, width, groups, width_per_group, dilate)
     x = gb.gap(x)
     x = gb.simple("Flatten", [x], [pb.attr_int("axis", 1)])
     wfc = rng.gaussish(seed, "fc_w", classes * cin).reshape(classes, cin) * np.float32(np.sqrt(1.0 / cin))
@@ -383,6 +408,92 @@ def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width:
     gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))],
               [pb.attr_int("transB", 1)], out=out_name)
     return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=11)
+
+
+def _resnet_body(gb: GraphBuilder, in_name: str, layers: Sequence[int], width: int, groups: int, width_per_group: int,
+                 dilate: Sequence[bool]) -> tuple[str, int]:
+    """The stem and the four bottleneck stages of resnet(); returns (feature map, its channels)"""
+    x = gb.conv(in_name, 3, width, 7, stride=2, pad=3, name="conv1")
+    x = gb.relu(gb.bn(x, width, name="bn1"))
+    x = gb.pool("MaxPool", x, 3, 2, pad=1)
+    cin = width
+    dilation = 1
+    for si, nblocks in enumerate(layers):
+        planes = width * (2 ** si)
+        mid = int(planes * (width_per_group / 64.0)) * groups
+        cout = planes * 4
+        first_dilation = dilation
+        stage_stride = 2 if si > 0 else 1
+        if si > 0 and dilate[si - 1]:
+            dilation *= stage_stride
+            stage_stride = 1
+        for bi in range(nblocks):
+            stride = stage_stride if bi == 0 else 1
+            d = first_dilation if bi == 0 else dilation
+            tag = f"s{si + 1}b{bi + 1}"
+            y = gb.relu(gb.bn(gb.conv(x, cin, mid, 1, name=tag + "_c1"), mid, name=tag + "_bn1"))
+            y = gb.relu(gb.bn(gb.conv(y, mid, mid, 3, stride=stride, pad=d, name=tag + "_c2", group=groups, dilation=d), mid, name=tag + "_bn2"))
+            y = gb.bn(gb.conv(y, mid, cout, 1, name=tag + "_c3", w_scale=float(0.5 * np.sqrt(2.0 / mid))), cout, name=tag + "_bn3")
+            if bi == 0:
+                sc = gb.bn(gb.conv(x, cin, cout, 1, stride=stride, name=tag + "_proj"), cout, name=tag + "_bnp")
+            else:
+                sc = x
+            x = gb.relu(gb.simple("Add", [y, sc]))
+            cin = cout
+    return x, cin
+
+
+def _seg_head_out(gb: GraphBuilder, x: str, feat_shape: Sequence[int], batch: int | str, image: int, resize: str, coord: str, out_name: str) -> str:
+    """The final upsampling of a segmentation net: the [N, classes, h, w] logits to the input's [image, image], bilinear"""
+    if resize == "scales":
+        return gb.resize(x, feat_shape, scales=[image / feat_shape[2], image / feat_shape[3]], coord=coord, form="scales", name="final_resize", out=out_name)
+    return gb.resize(x, (batch, *feat_shape[1:]), sizes=[image, image], coord=coord, form=resize, name="final_resize", out=out_name)
+
+
+def fcn_resnet50(batch: int | str = 1, *, image: int = 224, classes: int = 21, width: int = 64, resize: str = "sizes",
+                 coord: str = "pytorch_half_pixel", seed: int = 95, in_name: str = "image", out_name: str = "out") -> bytes:
+    """FCN-ResNet50 as torchvision builds it: the ResNet-50 body with stages 3 and 4 dilated (output stride 8) -> FCNHead [3x3 conv
+    2048 -> 512 -> BN -> ReLU -> Dropout -> 1x1 conv -> classes (bias)] -> bilinear Resize to the input size ([N, classes, image, image]).
+    width scales every channel count (64: the real net).  resize: "sizes" (a concrete batch), "scales", or "shape" (the sizes computed by
+    Shape -> Gather -> Unsqueeze -> Concat -> Cast, as torch exports them); coord: pytorch_half_pixel (torch's align_corners=False) or half_pixel."""
+    gb = GraphBuilder("fcn_resnet50", seed)
+    x, cin = _resnet_body(gb, in_name, (3, 4, 6, 3), width, 1, 64, (False, True, True))
+    inter = cin // 4
+    y = gb.relu(gb.bn(gb.conv(x, cin, inter, 3, pad=1, name="head_c1"), inter, name="head_bn1"))
+    y = gb.simple("Dropout", [y])
+    y = gb.conv(y, inter, classes, 1, bias=True, name="head_cls")
+    fh = (image + 7) // 8
+    _seg_head_out(gb, y, (batch, classes, fh, fh), batch, image, resize, coord, out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes, image, image])], opset=11)
+
+
+def deeplabv3_resnet50(batch: int | str = 1, *, image: int = 224, classes: int = 21, width: int = 64, resize: str = "sizes",
+                       coord: str = "pytorch_half_pixel", rates: Sequence[int] = (12, 24, 36), seed: int = 96, in_name: str = "image",
+                       out_name: str = "out") -> bytes:
+    """DeepLabV3-ResNet50 as torchvision builds it: the dilated ResNet-50 body (output stride 8) -> ASPP [1x1 conv; three 3x3 convs with
+    dilation = pads = rate; pooling: GlobalAveragePool -> 1x1 conv -> BN -> ReLU -> Resize back to the map] (each branch 256 channels with BN
+    and ReLU) -> Concat -> 1x1 projection -> BN -> ReLU -> Dropout -> 3x3 conv -> BN -> ReLU -> 1x1 classifier (bias) -> bilinear Resize to
+    the input size.  width, resize and coord as fcn_resnet50 (the pooling branch's Resize takes the same export form)."""
+    gb = GraphBuilder("deeplabv3_resnet50", seed)
+    x, cin = _resnet_body(gb, in_name, (3, 4, 6, 3), width, 1, 64, (False, True, True))
+    a = 4 * width
+    fh = (image + 7) // 8
+    branches = [gb.relu(gb.bn(gb.conv(x, cin, a, 1, name="aspp0"), a, name="aspp0_bn"))]
+    for i, r in enumerate(rates):
+        branches.append(gb.relu(gb.bn(gb.conv(x, cin, a, 3, pad=r, dilation=r, name=f"aspp{i + 1}"), a, name=f"aspp{i + 1}_bn")))
+    p = gb.relu(gb.bn(gb.conv(gb.gap(x), cin, a, 1, name="aspp_pool"), a, name="aspp_pool_bn"))
+    if resize == "scales":
+        p = gb.resize(p, (batch, a, 1, 1), scales=[fh, fh], coord=coord, form="scales", name="aspp_pool_up")
+    else:
+        p = gb.resize(p, (batch, a, 1, 1), sizes=[fh, fh], coord=coord, form=resize, name="aspp_pool_up")
+    branches.append(p)
+    y = gb.concat(branches)
+    y = gb.relu(gb.bn(gb.conv(y, 5 * a, a, 1, name="aspp_proj"), a, name="aspp_proj_bn"))
+    y = gb.simple("Dropout", [y])
+    y = gb.relu(gb.bn(gb.conv(y, a, a, 3, pad=1, name="head_c1"), a, name="head_bn1"))
+    y = gb.conv(y, a, classes, 1, bias=True, name="head_cls")
+    _seg_head_out(gb, y, (batch, classes, fh, fh), batch, image, resize, coord, out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes, image, image])], opset=11)
 
 
 def resnet50(batch: int | str = 1) -> bytes:
