@@ -1327,8 +1327,75 @@ SeArgs DeviceModel::MakeSeArgs(const PlanInstance& pi, const Step& s) const {
     return a;
 }
 
+// The step that really runs when `s` is launched: `s` itself, or -- a specialised launcher that declines this operand set (alignment,
+// LDS budget, a missing weight mirror ...) -- the hand-over step, built in `scratch`.  LaunchStep launches what this returns and
+// Profile() labels it, so a declined step is reported under the kernel that ran.
+const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Step& scratch) const {
+    if (s.kind != StepKind::Conv) return s;
+    auto with_tile = [&](int tile) -> const Step& {
+        if (tile == s.tile) return s;
+        scratch = s;
+        scratch.tile = tile;
+        return scratch;
+    };
+    switch (s.algo) {
+        case ConvAlgo::Depthwise:       // the generic kernel takes every depthwise conv
+            return with_tile(ConvDwEligible(MakeDwArgs(pi, s), s.tile) ? s.tile : 0);
+        case ConvAlgo::Grouped:         // the generic kernel takes every grouped conv
+            return with_tile(ConvGroupedEligible(MakeGroupedArgs(pi, s), s.tile) ? s.tile : 0);
+        case ConvAlgo::StemPool:        // tile 0: the two plain steps
+            return with_tile(s.tile != 0 && ConvStemPoolEligible(MakeConvArgs(pi, s)) ? s.tile : 0);
+        case ConvAlgo::DenseBlock: {    // tile 0: the 2n plain steps
+            DenseBlockArgs b;
+            return with_tile(s.tile != 0 && MakeBlockArgs(pi, s, &b) && DenseBlockEligible(b) ? s.tile : 0);
+        }
+        case ConvAlgo::DenseFused: {    // tile 0: the two plain steps
+            if (s.tile == 0) return s;
+            const Step& s3 = s.parts.at(0);
+            FusedArgs f;
+            f.in3 = make_arg(pi, s3.in);
+            f.out3 = make_arg(pi, s3.out);
+            f.wfrag3 = w_->d_weights_frag && s3.w_off >= 0 ? w_->d_weights_frag + s3.w_off : nullptr;
+            f.bias3 = s3.bias_off >= 0 ? w_->d_weights + s3.bias_off : nullptr;
+            f.relu3 = s3.relu;
+            return with_tile(ConvDenseFusedEligible(MakeConvArgs(pi, s), f, s.tile) ? s.tile : 0);
+        }
+        case ConvAlgo::IgemmF8: {       // a weights-stationary launcher that declines these operands hands the step to the tiled fp8 kernel
+            const int t8 = s.tile;
+            if (t8 < kWs8Code) return s;
+            const ConvArgs a = MakeConvArgs(pi, s);
+            const bool ok = t8 >= kWs38Code ? ConvWs38Eligible(a, t8 - kWs38Code) : ConvWs8Eligible(a, t8 - kWs8Code);
+            return with_tile(ok ? t8 : (s.base_tile < kNumConvF8Tiles ? s.base_tile : 3));
+        }
+        case ConvAlgo::Ws1x1: case ConvAlgo::Ws3x3: case ConvAlgo::Direct: case ConvAlgo::Raster3x3: case ConvAlgo::Wino3x3: case ConvAlgo::X6:
+        case ConvAlgo::Stem: {          // the tiled kernel takes every dense conv
+            const ConvArgs a = MakeConvArgs(pi, s);
+            ConvArgs plain = a;                        // what a kernel without a residual epilogue is asked to do (see split_res in LaunchStep)
+            plain.res = TensorArg();
+            bool ok = true;
+            switch (s.algo) {
+                case ConvAlgo::Ws1x1: ok = s.in.f16 ? ConvWsEligible(a, s.tile) : ConvWs32Eligible(a, s.tile); break;
+                case ConvAlgo::Ws3x3: ok = ConvWs3Eligible(plain, s.tile); break;
+                case ConvAlgo::Direct: ok = ConvDirectEligible(plain, s.tile); break;
+                case ConvAlgo::Raster3x3: ok = ConvRasterEligible(plain, s.tile); break;
+                case ConvAlgo::Wino3x3: ok = ConvWinoEligible(plain, s.tile); break;
+                case ConvAlgo::X6: ok = ConvX6Eligible(plain, s.tile); break;
+                default: ok = ConvStemEligible(a); break;
+            }
+            if (ok) return s;
+            scratch = s;
+            scratch.algo = s.algo == ConvAlgo::Stem ? ConvAlgo::IgemmScalar : ConvAlgo::IgemmVec;
+            scratch.tile = s.base_tile;
+            scratch.splitk = 1;
+            return scratch;
+        }
+        default: return s;
+    }
+}
+
 void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream_t stream_) {
-    const Step& s = s_in;
+    Step handed;
+    const Step& s = LaunchedStep(pi, s_in, handed);
     const float* wb = w_->d_weights;
     auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
     switch (s.kind) {
@@ -1346,32 +1413,27 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
                 break;
             }
             if (s.algo == ConvAlgo::Depthwise) {
-                // a variant that declines these operands (alignment) hands the step to the generic kernel, which takes every depthwise conv
-                const DwArgs a = MakeDwArgs(pi, s);
-                check(LaunchConvDw(a, ConvDwEligible(a, s.tile) ? s.tile : 0, stream_), "conv_dw");
+                check(LaunchConvDw(MakeDwArgs(pi, s), s.tile, stream_), "conv_dw");
                 break;
             }
             if (s.algo == ConvAlgo::Grouped) {
-                // a variant that declines these operands (alignment) hands the step to the generic kernel, which takes every grouped conv
-                const GroupedArgs a = MakeGroupedArgs(pi, s);
-                check(LaunchConvGrouped(a, ConvGroupedEligible(a, s.tile) ? s.tile : 0, stream_), "conv_grouped");
+                check(LaunchConvGrouped(MakeGroupedArgs(pi, s), s.tile, stream_), "conv_grouped");
                 break;
             }
             if (s.algo == ConvAlgo::StemPool) {
-                // the stem conv and the max pool behind it in one launch (out = the pooled tensor); the two plain steps when the launcher declines
-                const ConvArgs a = MakeConvArgs(pi, s);
-                if (s.tile != 0 && ConvStemPoolEligible(a)) check(LaunchConvStemPool(a, stream_), "conv_stem_pool");
+                // the stem conv and the max pool behind it in one launch (out = the pooled tensor); tile 0: the two plain steps
+                if (s.tile != 0) check(LaunchConvStemPool(MakeConvArgs(pi, s), stream_), "conv_stem_pool");
                 else for (const Step& q : s.parts) LaunchStep(pi, q, stream_);
                 break;
             }
             if (s.algo == ConvAlgo::DenseBlock) {
                 DenseBlockArgs b;
-                if (s.tile != 0 && MakeBlockArgs(pi, s, &b) && DenseBlockEligible(b)) check(LaunchDenseBlockF16(b, stream_), "dense_block_f16");
+                if (s.tile != 0 && MakeBlockArgs(pi, s, &b)) check(LaunchDenseBlockF16(b, stream_), "dense_block_f16");
                 else for (const Step& q : s.parts) LaunchStep(pi, q, stream_);
                 break;
             }
             if (s.algo == ConvAlgo::DenseFused) {
-                // one launch for the 3x3 of dense layer L and the 1x1 of layer L+1; the two plain steps when the fused kernel declines
+                // one launch for the 3x3 of dense layer L and the 1x1 of layer L+1; tile 0: the two plain steps
                 const Step& s3 = s.parts.at(0);
                 ConvArgs a1 = MakeConvArgs(pi, s);
                 FusedArgs f;
@@ -1380,7 +1442,7 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
                 f.wfrag3 = w_->d_weights_frag && s3.w_off >= 0 ? w_->d_weights_frag + s3.w_off : nullptr;
                 f.bias3 = wp(s3.bias_off);
                 f.relu3 = s3.relu;
-                if (ConvDenseFusedEligible(a1, f, s.tile)) check(LaunchConvDenseFused(a1, f, s.tile, stream_), "conv_dense_fused");
+                if (s.tile != 0) check(LaunchConvDenseFused(a1, f, s.tile, stream_), "conv_dense_fused");
                 else {
                     LaunchStep(pi, s.parts[0], stream_);
                     LaunchStep(pi, s.parts[1], stream_);
@@ -1388,44 +1450,17 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
                 break;
             }
             ConvArgs a = MakeConvArgs(pi, s);
-            // A specialised launcher that declines this operand set (alignment, LDS budget ...) hands the step to the tiled kernel.
-            Step fb;
-            const Step* sp = &s_in;
-            {
-                bool ok = true;
-                ConvArgs plain = a;                        // what a kernel without a residual epilogue is asked to do (see split_res below)
-                plain.res = TensorArg();
-                switch (s_in.algo) {
-                    case ConvAlgo::Ws1x1: ok = s_in.in.f16 ? ConvWsEligible(a, s_in.tile) : ConvWs32Eligible(a, s_in.tile); break;
-                    case ConvAlgo::Ws3x3: ok = ConvWs3Eligible(plain, s_in.tile); break;
-                    case ConvAlgo::Direct: ok = ConvDirectEligible(plain, s_in.tile); break;
-                    case ConvAlgo::Raster3x3: ok = ConvRasterEligible(plain, s_in.tile); break;
-                    case ConvAlgo::Wino3x3: ok = ConvWinoEligible(plain, s_in.tile); break;
-                    case ConvAlgo::X6: ok = ConvX6Eligible(plain, s_in.tile); break;
-                    case ConvAlgo::Stem: ok = ConvStemEligible(a); break;
-                    default: break;
-                }
-                if (!ok) {
-                    fb = s_in;
-                    fb.algo = s_in.algo == ConvAlgo::Stem ? ConvAlgo::IgemmScalar : ConvAlgo::IgemmVec;
-                    fb.tile = s_in.base_tile;
-                    fb.splitk = 1;
-                    sp = &fb;
-                }
-            }
-            if (s_in.algo == ConvAlgo::IgemmF8) {
+            if (s.algo == ConvAlgo::IgemmF8) {
                 // e4m3 tensors: only the fp8 kernel may touch them; a declined launch is an error, never a hand-over to a kernel that
                 // would read the bytes as floats
                 if (!w_->f8_ready) throw std::runtime_error("fp8 precision: scales are not calibrated yet");
-                int t8 = s_in.tile;         // a weights-stationary launcher that declines these operands hands the step to the tiled fp8 kernel
-                if (t8 >= kWs38Code ? !ConvWs38Eligible(a, t8 - kWs38Code) : (t8 >= kWs8Code && !ConvWs8Eligible(a, t8 - kWs8Code))) t8 = s_in.base_tile < kNumConvF8Tiles ? s_in.base_tile : 3;
+                const int t8 = s.tile;
                 if (t8 >= kWs38Code) check(LaunchConvWs3x3F8(a, t8 - kWs38Code, stream_), "conv3x3_ws_f8");        // weights-stationary 3x3 (kernels_ws8.hip)
                 else if (t8 >= kWs8Code) check(LaunchConvWs1x1F8(a, t8 - kWs8Code, stream_), "conv1x1_ws_f8");   // weights-stationary 1x1
                 else check(LaunchConvIgemmF8(a, t8, stream_), "conv_igemm_f8");
                 break;
             }
             if (a.in.f8 || a.res.f8 || (a.out.f8 && s_in.algo != ConvAlgo::Stem)) throw std::runtime_error("internal error: fp8 tensor reached a non-fp8 conv kernel");
-            const Step& s = *sp;
             if ((s.dh != 1 || s.dw != 1) && !DilationOk(s.algo)) throw std::runtime_error("internal error: dilated conv " + s.name + " reached a kernel without dilation");
             // A fused residual Add lives in the weights-stationary 1x1 epilogues; any other kernel runs the conv without its ReLU
             // and adds the shortcut in place afterwards.
@@ -1535,6 +1570,7 @@ static std::string kernel_label(const Step& s) {
                        std::to_string(c.gpb) + ",px" + std::to_string(kGroupedPx[s.tile]) + ">";
             }
             if (s.algo == ConvAlgo::DenseBlock) return s.tile != 0 ? "dense_block_f16_kernel<" + std::to_string(s.parts.size() / 2) + " layers>" : "dense_block_parts<" + std::to_string(s.parts.size()) + " launches>";
+            if (s.algo == ConvAlgo::DenseFused && s.tile == 0) return "dense_fused_parts<2 launches>";
             if (s.algo == ConvAlgo::DenseFused) return (s.tile >= 4 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";
             if (s.algo == ConvAlgo::DualF8) return s.in.f8 ? "conv1x1_ws_f8_kernel<dual,t" + std::to_string(s.tile >= kWs8Code ? s.tile - kWs8Code : 1) + ">" : "dual_f8_parts<2 launches>";
             if (s.algo == ConvAlgo::IgemmF8 && s.tile >= kWs38Code) return "conv3x3_ws_f8_kernel<t" + std::to_string(s.tile - kWs38Code) + ">";
@@ -1634,7 +1670,8 @@ std::vector<StepTiming> DeviceModel::Profile(PlanInstance& pi, int iters) {
     std::vector<StepTiming> out(ns);
     for (size_t i = 0; i < ns; ++i) {
         out[i].name = pi.plan.steps[i].name;
-        out[i].kernel = kernel_label(pi.plan.steps[i]);
+        Step handed;
+        out[i].kernel = kernel_label(LaunchedStep(pi, pi.plan.steps[i], handed));
         out[i].flops = pi.plan.steps[i].flops;
         out[i].bytes = pi.plan.steps[i].bytes;
     }

@@ -183,6 +183,7 @@ private:
     void RefreshGraphs(PlanInstance& pi);   // (re)capture the graphs of `pi` when they are missing or older than the current fp8 scales
     void PrepareF8(const std::vector<float>* adopt_act_scales = nullptr);       // quantise the conv weights, calibrate the activation scales, derive the epilogue multipliers (once per DeviceWeights)
     void LaunchStep(const PlanInstance& pi, const Step& s, hipStream_t stream);
+    const Step& LaunchedStep(const PlanInstance& pi, const Step& s, Step& scratch) const;   // what LaunchStep really runs for `s` (a declined launcher hands over)
     ConvArgs MakeConvArgs(const PlanInstance& pi, const Step& s) const;
     DwArgs MakeDwArgs(const PlanInstance& pi, const Step& s) const;
     GroupedArgs MakeGroupedArgs(const PlanInstance& pi, const Step& s) const;

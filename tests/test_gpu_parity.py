@@ -1733,7 +1733,7 @@ def test_fp8_stem_and_max_pool_one_launch_or_two(tmp_path, image):
 def test_fp8_weights_stationary_kernels(tmp_path, tile):
     """conv1x1_ws_f8_kernel (tiles 100-104; 105-109: the same shapes on a grid of one workgroup per CU; also its DUAL form for the projection shortcut of the first block and its STRIDED-input form for the
     stride-2 projection shortcut of the second stage) and conv3x3_ws_f8_kernel (tiles
-    200-203; 204-207: one workgroup per CU) forced on a bottleneck ResNet whose channel counts are multiples of 32 (every 1x1 / 3x3 stride-1 conv qualifies): against the fp8
+    200-203; 204-207: one workgroup per CU) forced on a bottleneck ResNet whose channel counts are multiples of 32 (every 1x1 / 3x3 stride-1 conv qualifies at plan time; the 1x1 variants decline the narrow ones at launch, asserted step by step below): against the fp8
     plan emulation (same quantisation points: kernel correctness), the float64 oracle (stated fp8 bound) and the tiled fp8 kernel's answer."""
     from oracle import fp8 as F
     mb = models.resnet(3, layers=(2, 2), width=32, image=64, classes=20, seed=53)
@@ -1758,9 +1758,20 @@ def test_fp8_weights_stationary_kernels(tmp_path, tile):
     nws = sum(k.startswith(want) for k in kern)
     assert nws >= (4 if tile < 200 else 2), kern         # (the strided 3x3 of a stage's first block stays on the tiled kernel)
     assert any(k.startswith("conv1x1_ws_f8_kernel<dual") for k in kern), kern          # the first block's projection shortcut: one launch, two GEMMs
-    if tile < 200:       # every 1x1 runs weights-stationary, the STRIDED projection shortcut of stage 2 included: only the four 3x3 convs stay tiled
-        assert sum(k.startswith("conv_igemm_f8_kernel") for k in kern) == 4, kern
     plan, blob = _run_with_env(dict(IE_PRECISION="fp8", **env), lambda: (B.DescribeModel(path, 3)["plan"], B.PlanWeights(path, 3)))
+    if tile < 200:
+        # Profile() names what was launched, step by step.  A 1x1 variant of tn x 32 output channels per workgroup declines a conv of at most
+        # 32 x (tn / 2) of them (MFMA rows spent on padding: here the 32-channel reductions of stage 1 for every variant, the 64-channel
+        # ones of stage 2 from tn = 4, the 128-channel expansion from tn = 8) or one whose weight slice does not fit the LDS; such a step
+        # runs tiled, like the four 3x3 convs.  Every other 1x1, the STRIDED projection shortcut of stage 2 included, runs weights-stationary
+        tn = (8, 4, 2, 4, 2)[tile % 5]
+        for st, k in zip(plan["steps"], kern):
+            if st["kind"] != "conv" or st.get("algo") != "igemm_f8":
+                continue
+            fits = st["out"]["c"] > 32 * (tn // 2) and 32 * tn * (st["in"]["c"] + 16) + 3 * 32 * tn * 4 <= 160 * 1024
+            ws = st["k"] == [1, 1] and st["tile"] >= 100 and fits
+            assert k.startswith("conv1x1_ws_f8_kernel" if ws else "conv_igemm_f8_kernel"), (st["name"], st["in"]["c"], st["out"]["c"], k)
+        assert any(st["k"] == [1, 1] and st["stride"] == [2, 2] and k.startswith("conv1x1_ws_f8_kernel<t") for st, k in zip(plan["steps"], kern)), kern
     emu = F.run_plan(plan, blob, {"data": x}, act_scales=info["f8_act_scales"], fp8=True)["logits"]
     e_emu, e_ref, e_t = rel_err(y, emu), rel_err(y, ref), rel_err(y, y0)
     print(f"fp8 weights-stationary tile {tile}: {nws} launches; vs fp8 emulation {e_emu:.2e}, vs float64 oracle {e_ref:.2e}, vs the tiled kernels {e_t:.2e}")
@@ -2003,3 +2014,39 @@ def test_winograd_3x3_kernel(tmp_path, tile, batch, image, blocks):
     e = rel_err(y, ref)
     print(f"winograd tile {tile} B={batch} image={image}: {len(nw)} convs, rel err {e:.2e} (default kernels {rel_err(y0, ref):.2e})")
     assert e < RTOL and rel_err(y, y0) < 2e-5
+
+
+@pytest.mark.parametrize("algo,tile,planned,want", [("wino", 5, "wino3x3", "conv3x3_wino_kernel<t5>"), ("direct", 6, "direct", "conv_win_kernel<f32,t6>"),
+                                                    ("direct", 10, "direct", "conv1x1_as_kernel<f32,t10>")])
+def test_profile_names_the_kernel_that_was_launched(tmp_path, algo, tile, planned, want):
+    """A launcher that declines its operands hands the step to the tiled implicit GEMM, and Profile() says so.  IE_NO_FRAG_WEIGHTS=1: Load
+    builds neither the fragment-major weight mirror nor the Winograd U, so the Winograd, window and activations-stationary launchers
+    decline every step that was planned for them: the labels are the tiled kernel's, the plan is unchanged, the result is still right.
+    With the mirrors the same plan runs on the kernels it names."""
+    mb = models.densenet(3, growth=32, blocks=(2, 2), stem=128, image=64, classes=12, seed=97)
+    path = models.write_repo(str(tmp_path), "decl", mb)
+    x = models.synthetic_input((3, 3, 64, 64), stream="decl")
+    ref = O.run(O.load_model(mb), {"data_0": x}, dtype=np.float64)["fc6_1"]
+
+    def go():
+        steps = B.DescribeModel(path, 3)["plan"]["steps"]
+        m = B.CreateModel(path, "decl")
+        try:
+            y = infer(m, "", "data_0", x, "fc6_1", [3, 12, 1, 1])[0].copy()
+            prof = B.Profile(m, 1)
+        finally:
+            m.Destroy()
+        return steps, y, prof
+    env = dict(IE_FORCE_ALGO=algo, IE_FORCE_TILE=str(tile))
+    steps, y, prof = _run_with_env(env, go)
+    steps0, y0, prof0 = _run_with_env(dict(env, IE_NO_FRAG_WEIGHTS="1"), go)
+    idx = [i for i, s in enumerate(steps) if s.get("algo") == planned]
+    assert len(idx) >= 4 and [s.get("algo") for s in steps0] == [s.get("algo") for s in steps]
+    assert [p_["name"] for p_ in prof] == [s["name"] for s in steps] == [p_["name"] for p_ in prof0]
+    for i in idx:
+        assert prof[i]["kernel"] == want, (steps[i]["name"], prof[i]["kernel"])
+        assert prof0[i]["kernel"].startswith("conv_igemm_kernel<") and ",vec" in prof0[i]["kernel"], (steps[i]["name"], prof0[i]["kernel"])
+    for i in set(range(len(steps))) - set(idx):
+        assert prof0[i]["kernel"] == prof[i]["kernel"]
+    print(f"{algo} tile {tile}: {len(idx)} steps declined without the mirrors -> {sorted({prof0[i]['kernel'] for i in idx})}; rel err {rel_err(y0, ref):.2e} / {rel_err(y, ref):.2e}")
+    assert rel_err(y, ref) < RTOL and rel_err(y0, ref) < RTOL
