@@ -14,7 +14,7 @@
 //      issued BEFORE step 1 and land while it runs), the 32 fresh ones from step 1, BN+ReLU prologue on the way into LDS, weights
 //      streamed through a register ring, each wave 16 of the 128 output channels.
 // No barrier between workgroups, no recomputed halo: launch k reads only what launch k-1 wrote.  The planner emits these steps for a
-// run of dense layers (plan.cpp, "dense fusion"); a block of n layers becomes n+1 launches instead of 2n, and the bottleneck tensor
+// run of dense layers (plan.cpp, FuseDenseLayers); a block of n layers becomes n+1 launches instead of 2n, and the bottleneck tensor
 // ping-pongs between two buffers (one being read as halo by neighbouring tiles while the other is written).
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,7 @@
 #include "plan.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -112,6 +113,12 @@ struct Lowering {
         if (it != m.initializers.end()) return &it->second;
         auto jt = derived.find(name);
         return jt == derived.end() ? nullptr : &jt->second;
+    }
+    // a derived initializer under `t.name`; the name must be new to the graph
+    void add_derived(OnnxTensor t) {
+        if (derived.count(t.name) || m.initializers.count(t.name) || val_of.count(t.name)) fail("ONNX graph error: value defined twice: " + t.name);
+        const std::string name = t.name;
+        derived[name] = std::move(t);
     }
     std::vector<int> consumers(int v) const {
         std::vector<int> out;
@@ -247,6 +254,123 @@ int choose_tile(int64_t M, int64_t N) {
     return best;
 }
 
+double vbytes(const View& v) { return double(v.numel()) * double(v.esize()); }
+
+const int ws_tn[14] = {4, 4, 2, 2, 1, 1, 4, 4, 2, 2, 1, 1, 1, 1};      // 12, 13: fp32 K-split variants (8 / 4 waves)
+
+// Schedule position of a value that is never recycled (graph inputs and outputs)
+constexpr int kLiveForever = 1 << 30;
+
+// What the kernel choice of one dense conv step reads: the GEMM extents, the operand types, and the plan-time eligibility of the specialised
+// kernels (the launchers re-check pointers / alignment; the executor falls back to the tiled implicit GEMM when a launcher declines)
+struct ConvFacts {
+    const LNode& n;
+    const Step& s;                    // its views and has_in2 are final; algo / tile / splitk are what the choice fills in
+    int64_t M, N, K;
+    bool in16, in8, dil, vec_ok, vec16_ok, is1x1, is3x3;
+    ConvFacts(const LNode& n, const Step& s);
+    ConvAlgo tiled_algo() const { return (vec_ok || vec16_ok) ? ConvAlgo::IgemmVec : (K <= 2048 && !in16 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive); }
+    bool ws16_ok(int t) const;
+    bool ws32_ok(int t) const;
+    bool ws3_ok(int t3) const;
+    bool direct_ok(int t) const;
+    bool raster_ok() const { return vec_ok && !s.out.f16 && is3x3 && !n.has_pre; }
+    bool wino_ok() const { return raster_ok() && N == 32 && s.in.c % 32 == 0 && s.in.h % 2 == 0 && s.in.w % 2 == 0 && n.res < 0 && s.out.pitch % 4 == 0 && s.out.c_off % 4 == 0; }
+};
+
+// What the passes of one BuildPlan share.  The passes run once each, in the order BuildPlan lists them; a pass may read anything an
+// earlier pass left here.
+struct Planner {
+    const OnnxModel& m;
+    const std::vector<std::vector<int64_t>>& input_shapes;
+    const Env& env;                        // the planner's switches, read once per plan build
+    const Precision precision;
+    const bool f8_fusions;
+    Lowering L;
+    Plan plan;
+    std::vector<int> out_vals;             // DensifyOutputs: the value each graph output is read from, in graph order
+    std::vector<int> order;                // ComputeLiveness: the live nodes in schedule order
+    std::vector<int> first_def, last_use;  // ComputeLiveness: schedule positions per root value
+    std::vector<char> used;                // ComputeLiveness: root values some live node touches
+    std::map<std::vector<int64_t>, int> writer;   // EmitSteps: (buffer, channel offset, channels) -> step index, for Step::in_src / in2_src
+
+    Planner(const OnnxModel& mm, const std::vector<std::vector<int64_t>>& shapes, const Env& e, Precision p, bool f8)
+        : m(mm), input_shapes(shapes), env(e), precision(p), f8_fusions(f8), L(mm) { plan.precision = p; }
+
+    // ---- helpers ----
+    bool single_consumer(int v) const { return !L.vals[v].is_output && L.consumers(v).size() == 1; }
+    int ForcedTile(int limit) const;       // IE_FORCE_TILE when it is set and in [0, limit), else -1
+    int64_t root_floats(int r) const { const Val& R = L.vals[r]; return R.n * R.c * R.h * R.w; }
+    View view_of(int v) const;
+    int64_t push_vec(const std::vector<float>& v);       // append to the weight blob (32-byte aligned), return the offset
+    int src_of(const View& v) const;
+    bool output_in_buffer(int buf) const;  // a graph output lives in this buffer
+
+    // ---- ONNX graph -> logical nodes ----
+    void ImportInputs();
+    void ImportNode(const OnnxNode& on);
+    void MarkOutputs();
+    void RefuseForF8() const;
+    int in_val(const OnnxNode& on, size_t k) const { return L.get_val(on.inputs[k]); }
+    bool act_input(const OnnxNode& on, size_t k) const { return k < on.inputs.size() && !on.inputs[k].empty() && !L.init(on.inputs[k]); }
+    bool FoldConstantNode(const OnnxNode& on);
+    bool FoldShapeArithmetic(const OnnxNode& on, const LNode& n);
+    bool FoldShapeOnlyOp(const OnnxNode& on, const LNode& n);
+    void ImportConv(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportBatchNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportPool(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportReshape(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportResize(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+
+    // ---- graph-level fusions ----
+    void FuseActivationPatterns();
+    void FuseSqueezeExcite();
+    void MergeAffineChains();
+    void FuseConvEpilogues();
+    void FuseRelu6IntoDepthwise();
+    void FuseActivationPrologues();
+    void SwapConvAndAvgPool();
+    void FusePrologues();
+    void FuseTrailingRelu();
+
+    // ---- where every value lives ----
+    void StageNchwInputs();
+    void DensifyOutputs();
+    void PlaceConcatsAndAliases();
+    void ComputeLiveness();
+    void KeepDenseFusionInputsLive();
+    void AssignBuffers();
+    void alloc_buf(int r, std::multimap<int64_t, int>& free_pool);
+    void MarkBufferTypes();
+
+    // ---- logical nodes -> steps ----
+    void EmitSteps();
+    void EmitConcatCopies(const LNode& n);
+    void EmitConv(const LNode& n, Step& s);
+    void EmitGroupConv(const LNode& n, Step& s);
+    void ChooseBaseAlgo(const ConvFacts& f, Step& s) const;
+    void ForceTileF8(const ConvFacts& f, Step& s) const;
+    void ApplyForcedAlgo(const ConvFacts& f, Step& s) const;
+    void ApplyForcedTileAndSplitK(const ConvFacts& f, Step& s);
+    void EmitPool(const LNode& n, Step& s) const;
+    void EmitSqueezeExcite(const LNode& n, Step& s);
+    void EmitEltwise(const LNode& n, Step& s);
+    void EmitResize(const LNode& n, Step& s) const;
+
+    // ---- step-level fusions, I/O descriptors ----
+    void FuseDenseLayers();
+    bool DenseLayerAt(size_t i) const;
+    void FuseDenseBlocks();
+    void FuseStemPool();
+    void FuseDualF8();
+    void DescribeIo();
+};
+
+
 }  // namespace
 
 ModelInfo DescribeModel(const OnnxModel& m) {
@@ -274,15 +398,10 @@ ModelInfo DescribeModel(const OnnxModel& m) {
     return info;
 }
 
-Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& input_shapes, Precision precision, bool f8_fusions) {
-    const Env env = Env::Read();          // the planner's switches, read once per plan build (load / prepare time)
-    Lowering L(m);
-    Plan plan;
-    plan.precision = precision;
+// ---- graph inputs ---------------------------------------------------------------------------
+void Planner::ImportInputs() {
     if (input_shapes.size() != m.inputs.size())
         fail("Expected " + std::to_string(m.inputs.size()) + " inputs, got " + std::to_string(input_shapes.size()));
-
-    // ---- graph inputs ---------------------------------------------------------------------------
     for (size_t i = 0; i < m.inputs.size(); ++i) {
         const auto& vi = m.inputs[i];
         const auto& got = input_shapes[i];
@@ -300,579 +419,621 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         L.vals[v].is_input = true;
         L.vals[v].input_nchw = (L.vals[v].h * L.vals[v].w > 1);
     }
+}
 
-    // ---- ONNX nodes -> logical nodes with shape inference ---------------------------------------
-    for (const auto& on : m.nodes) {
-        if (on.op == "Constant") {
-            // a constant becomes an initializer under its output name (exporters write Clip bounds this way)
-            if (on.outputs.size() != 1 || on.attrs.size() != 1) fail("Constant " + on.name + ": expected one output and one value attribute");
-            const OnnxAttr& at = on.attrs.begin()->second;
-            OnnxTensor t;
-            if (at.name == "value" && at.has_t) t = at.t;
-            else if (at.name == "value_float") { t.dtype = ONNX_FLOAT; t.f = {at.f}; }
-            else if (at.name == "value_floats") { t.dtype = ONNX_FLOAT; t.f = at.floats; t.dims = {int64_t(at.floats.size())}; }
-            else if (at.name == "value_int") { t.dtype = ONNX_INT64; t.i = {at.i}; }
-            else if (at.name == "value_ints") { t.dtype = ONNX_INT64; t.i = at.ints; t.dims = {int64_t(at.ints.size())}; }
-            else fail("Constant " + on.name + ": the form '" + at.name + "' is not supported");
-            t.name = on.outputs[0];
-            if (L.derived.count(t.name) || m.initializers.count(t.name) || L.val_of.count(t.name))
-                fail("ONNX graph error: value defined twice: " + t.name);
-            L.derived[t.name] = std::move(t);
-            continue;
-        }
-        if (on.outputs.empty() || on.inputs.empty()) fail("node " + on.name + " (" + on.op + ") has no inputs/outputs");
-        LNode n;
-        n.name = on.name.empty() ? on.outputs[0] : on.name;
-        const std::string& op = on.op;
-        auto in_val = [&](size_t k) { return L.get_val(on.inputs[k]); };
-        auto act_input = [&](size_t k) { return k < on.inputs.size() && !on.inputs[k].empty() && !L.init(on.inputs[k]); };
-        std::vector<int64_t> odims;
+// a constant becomes an initializer under its output name (exporters write Clip bounds this way)
+bool Planner::FoldConstantNode(const OnnxNode& on) {
+    if (on.op != "Constant") return false;
+    if (on.outputs.size() != 1 || on.attrs.size() != 1) fail("Constant " + on.name + ": expected one output and one value attribute");
+    const OnnxAttr& at = on.attrs.begin()->second;
+    OnnxTensor t;
+    if (at.name == "value" && at.has_t) t = at.t;
+    else if (at.name == "value_float") { t.dtype = ONNX_FLOAT; t.f = {at.f}; }
+    else if (at.name == "value_floats") { t.dtype = ONNX_FLOAT; t.f = at.floats; t.dims = {int64_t(at.floats.size())}; }
+    else if (at.name == "value_int") { t.dtype = ONNX_INT64; t.i = {at.i}; }
+    else if (at.name == "value_ints") { t.dtype = ONNX_INT64; t.i = at.ints; t.dims = {int64_t(at.ints.size())}; }
+    else fail("Constant " + on.name + ": the form '" + at.name + "' is not supported");
+    t.name = on.outputs[0];
+    L.add_derived(std::move(t));
+    return true;
+}
 
-        // ---- Shape arithmetic: every shape is known at plan time, so Shape -> Gather / Slice -> Unsqueeze -> Concat (-> Cast), the way torch
-        //      exports the `sizes` of an F.interpolate, folds into derived int64 initializers.  Only a Resize's `sizes` may read the result ----
-        {
-            const bool folding = op == "Shape" || op == "Gather" || op == "Slice" || op == "Cast" || op == "Concat" || op == "Unsqueeze" || op == "Squeeze" ||
-                                 op == "Reshape" || op == "Flatten" || op == "Identity";
-            bool from_shape = op == "Shape";
-            for (size_t k = 0; k < on.inputs.size(); ++k) {
-                if (!L.shape_derived.count(on.inputs[k])) continue;
-                const bool sizes_in = (op == "Resize" && k == 3);
-                if (!folding && !sizes_in)
-                    fail(op + " " + n.name + ": reads the shape arithmetic of a Shape node; shapes are only supported as the sizes of a Resize");
-                from_shape = true;
-            }
-            if (from_shape && folding && op != "Shape" && !L.init(on.inputs[0]))
-                fail(op + " " + n.name + ": reads the shape arithmetic of a Shape node; shapes are only supported as the sizes of a Resize");
-            if (from_shape && folding) {
-                OnnxTensor t;
-                t.dtype = ONNX_INT64;
-                auto const_in = [&](size_t k) -> const OnnxTensor& {
-                    const OnnxTensor* c = k < on.inputs.size() && !on.inputs[k].empty() ? L.init(on.inputs[k]) : nullptr;
-                    if (!c) fail(op + " " + n.name + ": shape arithmetic needs constant operands");
-                    return *c;
-                };
-                auto ints_of = [&](const OnnxTensor& c) {
-                    if (!c.i.empty() || c.numel() == 0) return c.i;
-                    std::vector<int64_t> v;
-                    for (float f : c.f) v.push_back(int64_t(f));
-                    return v;
-                };
-                if (op == "Shape") {
-                    const Val& X = L.vals[in_val(0)];
-                    int64_t r = int64_t(X.dims.size());
-                    int64_t b = on.attr_i("start", 0), e = on.attr_i("end", r);
-                    if (b < 0) b += r;
-                    if (e < 0) e += r;
-                    b = std::clamp<int64_t>(b, 0, r);
-                    e = std::clamp<int64_t>(e, b, r);
-                    t.i.assign(X.dims.begin() + b, X.dims.begin() + e);
-                    t.dims = {e - b};
-                } else if (op == "Gather") {
-                    const std::vector<int64_t> d = ints_of(const_in(0));
-                    const OnnxTensor& ix = const_in(1);
-                    if (const_in(0).dims.size() != 1 || on.attr_i("axis", 0) != 0) fail("Gather " + n.name + ": shape arithmetic only gathers from a 1-D shape");
-                    for (int64_t v : ints_of(ix)) {
-                        if (v < 0) v += int64_t(d.size());
-                        if (v < 0 || v >= int64_t(d.size())) fail("Gather " + n.name + ": index out of range");
-                        t.i.push_back(d[size_t(v)]);
-                    }
-                    t.dims = ix.dims;
-                } else if (op == "Slice") {
-                    const std::vector<int64_t> d = ints_of(const_in(0));
-                    const int64_t r = int64_t(d.size());
-                    std::vector<int64_t> st = on.attr_ints("starts", {}), en = on.attr_ints("ends", {}), ax = on.attr_ints("axes", {0}), stp = {1};
-                    if (on.inputs.size() > 1) {              // opset >= 10: starts, ends, axes, steps are inputs
-                        st = ints_of(const_in(1));
-                        en = ints_of(const_in(2));
-                        if (on.inputs.size() > 3 && !on.inputs[3].empty()) ax = ints_of(const_in(3));
-                        if (on.inputs.size() > 4 && !on.inputs[4].empty()) stp = ints_of(const_in(4));
-                    }
-                    if (st.size() != 1 || en.size() != 1 || ax.size() != 1 || (ax[0] != 0 && ax[0] != -1) || stp.size() != 1 || stp[0] != 1)
-                        fail("Slice " + n.name + ": shape arithmetic only slices a 1-D shape with step 1");
-                    int64_t b = st[0] < 0 ? st[0] + r : st[0], e = en[0] < 0 ? en[0] + r : en[0];
-                    b = std::clamp<int64_t>(b, 0, r);
-                    e = std::clamp<int64_t>(e, b, r);
-                    t.i.assign(d.begin() + b, d.begin() + e);
-                    t.dims = {e - b};
-                } else if (op == "Concat") {
-                    for (size_t k = 0; k < on.inputs.size(); ++k) {
-                        const OnnxTensor& c = const_in(k);
-                        if (c.dims.size() > 1) fail("Concat " + n.name + ": shape arithmetic only concatenates 1-D tensors (" + on.inputs[k] + " has rank " + std::to_string(c.dims.size()) + ")");
-                        const std::vector<int64_t> v = ints_of(c);
-                        t.i.insert(t.i.end(), v.begin(), v.end());
-                    }
-                    t.dims = {int64_t(t.i.size())};
-                } else if (op == "Cast") {
-                    const OnnxTensor& c = const_in(0);
-                    const int64_t to = on.attr_i("to", ONNX_INT64);
-                    t = c;
-                    if (to == ONNX_INT64 || to == ONNX_INT32) { t.i = ints_of(c); t.f.clear(); t.dtype = int(to); }
-                    else if (to == ONNX_FLOAT || to == ONNX_DOUBLE) { t.f.clear(); for (int64_t v : ints_of(c)) t.f.push_back(float(v)); t.i.clear(); t.dtype = int(to); }
-                    else fail("Cast " + n.name + ": shape arithmetic only casts to integer or floating-point types");
-                } else {
-                    t.dtype = -1;                            // Unsqueeze / Squeeze / Reshape / Flatten / Identity: the constant folding below
-                }
-                if (t.dtype != -1) {
-                    t.name = on.outputs[0];
-                    if (L.derived.count(t.name) || m.initializers.count(t.name) || L.val_of.count(t.name))
-                        fail("ONNX graph error: value defined twice: " + t.name);
-                    L.derived[t.name] = std::move(t);
-                    L.shape_derived.insert(on.outputs[0]);
-                    continue;
-                }
-                L.shape_derived.insert(on.outputs[0]);
-            }
-        }
-
-        // ---- shape-only ops on constants fold into a derived initializer (nothing is emitted) ----
-        if ((op == "Unsqueeze" || op == "Squeeze" || op == "Reshape" || op == "Flatten" || op == "Identity") && L.init(on.inputs[0])) {
-            OnnxTensor t = *L.init(on.inputs[0]);
-            auto axes_of = [&]() {
-                std::vector<int64_t> ax = on.attr_ints("axes", {});
-                if (ax.empty() && on.inputs.size() > 1 && !on.inputs[1].empty()) {       // opset >= 13: axes is an input
-                    const OnnxTensor* at = L.init(on.inputs[1]);
-                    if (!at) fail(op + " " + n.name + ": axes must be an initializer");
-                    ax = at->i;
-                }
-                return ax;
-            };
-            if (op == "Unsqueeze") {
-                std::vector<int64_t> ax = axes_of();
-                if (ax.empty()) fail("Unsqueeze " + n.name + ": axes are required");
-                const int64_t orank = int64_t(t.dims.size() + ax.size());
-                for (auto& a : ax) { if (a < 0) a += orank; if (a < 0 || a >= orank) fail("Unsqueeze " + n.name + ": axis out of range"); }
-                std::sort(ax.begin(), ax.end());
-                std::vector<int64_t> nd;
-                size_t src = 0;
-                for (int64_t k = 0; k < orank; ++k) {
-                    if (std::binary_search(ax.begin(), ax.end(), k)) nd.push_back(1);
-                    else nd.push_back(t.dims.at(src++));
-                }
-                t.dims = nd;
-            } else if (op == "Squeeze") {
-                std::vector<int64_t> ax = axes_of();
-                const int64_t rank = int64_t(t.dims.size());
-                for (auto& a : ax) if (a < 0) a += rank;
-                std::vector<int64_t> nd;
-                for (int64_t k = 0; k < rank; ++k) {
-                    const bool listed = std::find(ax.begin(), ax.end(), k) != ax.end();
-                    if (listed && t.dims[size_t(k)] != 1) fail("Squeeze " + n.name + ": cannot squeeze a dimension of size != 1");
-                    if (ax.empty() ? t.dims[size_t(k)] != 1 : !listed) nd.push_back(t.dims[size_t(k)]);
-                }
-                t.dims = nd;
-            } else if (op == "Reshape") {
-                const OnnxTensor* shp = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
-                std::vector<int64_t> d = shp ? shp->i : on.attr_ints("shape", {});
-                if (d.empty() && t.numel() != 1) fail("Reshape " + n.name + ": shape must be an initializer");
-                int64_t known = 1, neg = -1;
-                for (size_t k = 0; k < d.size(); ++k) {
-                    if (d[k] == 0 && k < t.dims.size()) d[k] = t.dims[k];
-                    if (d[k] == -1) neg = int64_t(k); else known *= d[k];
-                }
-                if (neg >= 0 && known > 0) d[size_t(neg)] = t.numel() / known;
-                int64_t tot = 1; for (auto v : d) tot *= v;
-                if (tot != t.numel()) fail("Reshape " + n.name + ": element count mismatch");
-                t.dims = d;
-            } else if (op == "Flatten") {
-                int64_t ax = on.attr_i("axis", 1);
-                if (ax < 0) ax += int64_t(t.dims.size());
-                int64_t a = 1, b = 1;
-                for (size_t k = 0; k < t.dims.size(); ++k) (int64_t(k) < ax ? a : b) *= t.dims[k];
-                t.dims = {a, b};
-            }
-            t.name = on.outputs[0];
-            if (L.derived.count(t.name) || m.initializers.count(t.name) || L.val_of.count(t.name))
-                fail("ONNX graph error: value defined twice: " + t.name);
-            L.derived[t.name] = std::move(t);
-            continue;
-        }
-
-        if (op == "Conv") {
-            if (!act_input(0)) fail("Conv " + n.name + ": constant input is not supported");
-            const OnnxTensor* w = L.init(on.inputs.at(1));
-            if (!w || w->dims.size() != 4) fail("Conv " + n.name + ": weights must be a 4-D initializer");
-            int x = in_val(0);
-            const Val& X = L.vals[x];
-            if (X.dims.size() != 4) fail("Conv " + n.name + ": input must be 4-D");
-            int64_t co = w->dims[0], ci = w->dims[1];
-            const int64_t group = on.attr_i("group", 1);
-            if (group < 1) fail("Conv " + n.name + ": group = " + std::to_string(group) + " must be positive");
-            if (group != 1) {
-                // depthwise: one filter per channel; the weights [C, 1, kh, kw] pack as [C][kh][kw] (= [Cout][kh][kw][Cin] with Cin = 1).
-                // Any other group: output channel o reads input channels (o / (Cout / group)) * Cin / group ..., weights [Cout, Cin / group, kh, kw]
-                if (X.c % group != 0)
-                    fail("Conv " + n.name + ": group = " + std::to_string(group) + " does not divide the input channels " + std::to_string(X.c));
-                if (co % group != 0)
-                    fail("Conv " + n.name + ": group = " + std::to_string(group) + " does not divide the output channels " + std::to_string(co));
-                if (ci != X.c / group)
-                    fail("Conv " + n.name + ": weight channels " + std::to_string(ci) + " != input channels / group = " + std::to_string(X.c / group));
-                n.dw = group == X.c && co == group;
-                // Grouped convolutions are opt-in: without IE_GROUPED_CONV=1 the planner keeps refusing them as it always has, so a model that
-                // loads (or is refused) today is planned exactly as before
-                if (!n.dw && !env.flag("IE_GROUPED_CONV"))
-                    fail("Conv " + n.name + ": group = " + std::to_string(group) + " is not supported (only depthwise grouped convolutions, with group == input "
-                         "channels == output channels, are; set IE_GROUPED_CONV=1 to run the others on the grouped-convolution kernels)");
-                n.group = group;
-            } else if (ci != X.c) {
-                fail("Conv " + n.name + ": input channels " + std::to_string(X.c) + " != weight channels " + std::to_string(ci));
-            }
-            n.kind = L_CONV;
-            read_window_attrs(on, n, X.h, X.w, true, w);
-            if (n.kh != w->dims[2] || n.kw != w->dims[3]) fail("Conv " + n.name + ": kernel_shape does not match weights");
-            n.w.resize(size_t(co * ci * n.kh * n.kw));
-            for (int64_t o = 0; o < co; ++o)
-                for (int64_t c = 0; c < ci; ++c)
-                    for (int ky = 0; ky < n.kh; ++ky)
-                        for (int kx = 0; kx < n.kw; ++kx)
-                            n.w[size_t(((o * n.kh + ky) * n.kw + kx) * ci + c)] =
-                                w->f[size_t(((o * ci + c) * n.kh + ky) * n.kw + kx)];
-            if (on.inputs.size() > 2 && !on.inputs[2].empty()) {
-                const OnnxTensor* b = L.init(on.inputs[2]);
-                if (!b || b->numel() != co) fail("Conv " + n.name + ": bias must be a [Cout] initializer");
-                n.bias = b->f;
-            }
-            if (n.dil_h > 1 || n.dil_w > 1) {
-                if (group != 1)
-                    fail("Conv " + n.name + ": dilated " + std::string(n.dw ? "depthwise" : "grouped") + " convolutions are not supported (dilations " +
-                         std::to_string(n.dil_h) + "x" + std::to_string(n.dil_w) + ", group = " + std::to_string(group) + ")");
-                // Centre-tap collapse (exact): stride 1, odd k, pads d * (k / 2) and d >= the image extent on every dilated axis.  The nearest
-                // off-centre tap is d pixels from the output pixel, so it lands in the padding for EVERY output pixel: the conv is the 1x1 conv of
-                // its centre weights (DeepLabV3's rate-36 ASPP branch at 28x28).  It then takes every 1x1 path, and its FLOPs are the 1x1's.
-                auto centre_only = [](int k, int d, int s, int p0, int p1, int64_t len) {
-                    return k == 1 ? (p0 == 0 && p1 == 0) : (s == 1 && k % 2 == 1 && p0 == d * (k / 2) && p1 == p0 && d >= len);
-                };
-                if (centre_only(n.kh, n.dil_h, n.sh, n.pt, n.pb, X.h) && centre_only(n.kw, n.dil_w, n.sw, n.pl, n.pr, X.w)) {
-                    std::vector<float> wc(size_t(co * ci));
-                    for (int64_t o = 0; o < co; ++o)
-                        for (int64_t c = 0; c < ci; ++c) wc[size_t(o * ci + c)] = n.w[size_t(((o * n.kh + n.kh / 2) * n.kw + n.kw / 2) * ci + c)];
-                    n.w = std::move(wc);
-                    n.kh = n.kw = 1;
-                    n.pt = n.pl = n.pb = n.pr = 0;
-                    n.dil_h = n.dil_w = 1;
-                }
-            }
-            int64_t oh, ow;
-            conv_out_hw(X.h, X.w, n, false, oh, ow);
-            n.in = {x};
-            odims = {X.n, co, oh, ow};
-        } else if (op == "MatMul" || op == "Gemm") {
-            if (!act_input(0)) fail(op + " " + n.name + ": constant first operand is not supported");
-            const OnnxTensor* b = L.init(on.inputs.at(1));
-            if (!b || b->dims.size() != 2) fail(op + " " + n.name + ": second operand must be a 2-D initializer");
-            int x = in_val(0);
-            const Val& X = L.vals[x];
-            if (X.h * X.w != 1) fail(op + " " + n.name + ": input must be [N, K]");
-            bool transB = op == "Gemm" && on.attr_i("transB", 0) != 0;
-            if (op == "Gemm" && on.attr_i("transA", 0) != 0) fail("Gemm " + n.name + ": transA is not supported");
-            float alpha = op == "Gemm" ? on.attr_f("alpha", 1.f) : 1.f;
-            float beta = op == "Gemm" ? on.attr_f("beta", 1.f) : 1.f;
-            int64_t K = transB ? b->dims[1] : b->dims[0], N = transB ? b->dims[0] : b->dims[1];
-            if (K != X.c) fail(op + " " + n.name + ": inner dimensions do not match");
-            n.kind = L_CONV;
-            n.w.resize(size_t(N * K));
-            for (int64_t o = 0; o < N; ++o)
-                for (int64_t k = 0; k < K; ++k)
-                    n.w[size_t(o * K + k)] = alpha * (transB ? b->f[size_t(o * K + k)] : b->f[size_t(k * N + o)]);
-            if (op == "Gemm" && on.inputs.size() > 2 && !on.inputs[2].empty()) {
-                const OnnxTensor* c = L.init(on.inputs[2]);
-                if (!c) fail("Gemm " + n.name + ": C must be an initializer");
-                if (c->numel() == N) n.bias = c->f;
-                else if (c->numel() == 1) n.bias.assign(size_t(N), c->f[0]);
-                else fail("Gemm " + n.name + ": C must broadcast over rows");
-                for (auto& v : n.bias) v *= beta;
-            }
-            n.in = {x};
-            odims = {X.n, N};
-            if (X.dims.size() == 1) odims = {N};
-        } else if (op == "BatchNormalization") {
-            int x = in_val(0);
-            const Val& X = L.vals[x];
-            const OnnxTensor *g = L.init(on.inputs.at(1)), *be = L.init(on.inputs.at(2)), *mu = L.init(on.inputs.at(3)),
-                             *var = L.init(on.inputs.at(4));
-            if (!g || !be || !mu || !var) fail("BatchNormalization " + n.name + ": parameters must be initializers");
-            if (g->numel() != X.c || be->numel() != X.c || mu->numel() != X.c || var->numel() != X.c)
-                fail("BatchNormalization " + n.name + ": parameter size != channels");
-            double eps = on.attr_f("epsilon", 1e-5f);
-            n.kind = L_AFFINE;
-            n.s.resize(size_t(X.c)); n.t.resize(size_t(X.c));
-            for (int64_t c = 0; c < X.c; ++c) {
-                double s = double(g->f[c]) / std::sqrt(double(var->f[c]) + eps);
-                n.s[c] = float(s);
-                n.t[c] = float(double(be->f[c]) - double(mu->f[c]) * s);
-            }
-            n.in = {x};
-            odims = X.dims;
-        } else if (op == "Clip") {
-            // opset < 11: min / max attributes; opset >= 11: optional scalar inputs 2 and 3 (absent or "" = unbounded)
-            n.kind = L_CLIP;
-            n.in = {in_val(0)};
-            odims = L.vals[n.in[0]].dims;
-            if (on.attrs.count("min")) n.lo = on.attr_f("min", -kInf);
-            if (on.attrs.count("max")) n.hi = on.attr_f("max", kInf);
-            for (size_t k = 1; k < 3 && k < on.inputs.size(); ++k) {
-                if (on.inputs[k].empty()) continue;
-                const OnnxTensor* b = L.init(on.inputs[k]);
-                if (!b) fail("Clip " + n.name + ": the " + (k == 1 ? "min" : "max") + " bound must be a constant (initializer or Constant node)");
-                if (b->numel() != 1 || (b->dtype != ONNX_FLOAT && b->dtype != ONNX_DOUBLE && b->dtype != ONNX_FLOAT16))
-                    fail("Clip " + n.name + ": the " + (k == 1 ? "min" : "max") + " bound must be a floating-point scalar");
-                (k == 1 ? n.lo : n.hi) = b->f[0];
-            }
-        } else if (op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish") {
-            n.kind = L_ACT;
-            if (op == "Sigmoid") n.act.kind = ActKind::Sigmoid;
-            else if (op == "HardSigmoid") { n.act.kind = ActKind::HardSigmoid; n.act.a = on.attr_f("alpha", 0.2f); n.act.b = on.attr_f("beta", 0.5f); }
-            else { n.act.kind = ActKind::HardSwish; n.act.a = 1.f / 6.f; n.act.b = 0.5f; }
-            if (!act_input(0)) fail(op + " " + n.name + ": constant input is not supported");
-            n.in = {in_val(0)};
-            odims = L.vals[n.in[0]].dims;
-        } else if (op == "Relu") {
-            n.kind = L_RELU;
-            n.in = {in_val(0)};
-            odims = L.vals[n.in[0]].dims;
-        } else if (op == "Add" || op == "Mul" || op == "Div") {
-            bool a0 = act_input(0), a1 = act_input(1);
-            if (op == "Div" && (a1 || !a0)) fail("Div " + n.name + ": only the division of an activation by a constant is supported");
-            if (a0 && a1 && op == "Mul") {
-                // same shapes, or [N,C,H,W] x [N,C,1,1] in either order (a squeeze-excite gate); in[0] = the full tensor
-                int a = in_val(0), b = in_val(1);
-                const Val &A = L.vals[a], &Bv = L.vals[b];
-                const bool bcast_b = A.dims.size() == 4 && Bv.dims.size() == 4 && A.n == Bv.n && A.c == Bv.c && Bv.h == 1 && Bv.w == 1;
-                const bool bcast_a = A.dims.size() == 4 && Bv.dims.size() == 4 && A.n == Bv.n && A.c == Bv.c && A.h == 1 && A.w == 1;
-                if (A.dims != Bv.dims) {
-                    if (bcast_a && !bcast_b) std::swap(a, b);
-                    else if (!bcast_b) fail("Mul " + n.name + ": only same-shape activations or [N,C,H,W] x [N,C,1,1] broadcasting are supported between two activations");
-                }
-                n.kind = L_MUL;
-                n.in = {a, b};
-                odims = L.vals[a].dims;
-            } else if (a0 && a1) {
-                int a = in_val(0), b = in_val(1);
-                if (L.vals[a].dims != L.vals[b].dims) fail("Add " + n.name + ": broadcasting between activations is not supported");
-                n.kind = L_ADD;
-                n.in = {a, b};
-                odims = L.vals[a].dims;
-            } else if (a0 || a1) {
-                int x = in_val(a0 ? 0 : 1);
-                const OnnxTensor* c = L.init(on.inputs[a0 ? 1 : 0]);
-                std::vector<float> pc;
-                // rank-1 constant against a rank-2 activation aligns with the last (= channel) axis
-                const Val& X = L.vals[x];
-                // opset < 7 (Caffe2-era exports): Add/Mul carry broadcast=1 and an axis that places the constant's dims inside the
-                // activation's (axis=1 with a [C] constant = per channel); without an axis the constant aligns with the trailing dims
-                int64_t legacy_axis = -1;
-                if (m.opset > 0 && m.opset < 7 && on.attr_i("broadcast", 0) != 0 && on.attrs.count("axis")) {
-                    legacy_axis = on.attr_i("axis", 0);
-                    if (legacy_axis < 0) legacy_axis += int64_t(X.dims.size());
-                }
-                if (m.opset > 0 && m.opset < 7 && on.attr_i("broadcast", 0) == 0 && c->dims != X.dims && c->numel() != 1)
-                    fail(op + " " + n.name + ": operand shapes differ and the opset-" + std::to_string(m.opset) + " broadcast attribute is not set");
-                bool ok = L.per_channel_const(*c, X, pc, legacy_axis);
-                if (!ok && X.dims.size() == 2 && c->dims.size() == 1 && c->numel() == X.c) { pc = c->f; ok = true; }
-                if (!ok && X.dims.size() == 2 && c->dims.size() == 2 && c->dims[0] == 1 && c->dims[1] == X.c) { pc = c->f; ok = true; }
-                if (!ok) fail(op + " " + n.name + ": constant operand must broadcast per channel");
-                n.kind = L_AFFINE;
-                if (op == "Add") { n.s.assign(size_t(X.c), 1.f); n.t = pc; }
-                else if (op == "Div") {
-                    // x / c = x * (1 / c): an affine step like a Mul (hardswish exports that end in "/ 6")
-                    for (float& v : pc) {
-                        if (v == 0.f) fail("Div " + n.name + ": division by zero");
-                        v = 1.f / v;
-                    }
-                    n.s = pc;
-                    n.t.assign(size_t(X.c), 0.f);
-                }
-                else { n.s = pc; n.t.assign(size_t(X.c), 0.f); }
-                n.in = {x};
-                odims = X.dims;
-            } else fail(op + " " + n.name + ": constant folding of two initializers is not supported");
-        } else if (op == "Concat") {
-            int64_t axis = on.attr_i("axis", 1);
-            n.kind = L_CONCAT;
-            for (size_t k = 0; k < on.inputs.size(); ++k) {
-                if (!act_input(k)) fail("Concat " + n.name + ": constant inputs are not supported");
-                n.in.push_back(in_val(k));
-            }
-            const Val& X0 = L.vals[n.in[0]];
-            if (axis < 0) axis += int64_t(X0.dims.size());
-            if (axis != 1) fail("Concat " + n.name + ": only axis=1 (channels) is supported");
-            odims = X0.dims;
-            int64_t ctot = 0;
-            for (int v : n.in) {
-                const Val& X = L.vals[v];
-                if (X.dims.size() != X0.dims.size()) fail("Concat " + n.name + ": rank mismatch");
-                for (size_t k = 0; k < X.dims.size(); ++k)
-                    if (k != 1 && X.dims[k] != X0.dims[k]) fail("Concat " + n.name + ": shape mismatch");
-                ctot += X.c;
-            }
-            odims[1] = ctot;
-        } else if (op == "MaxPool" || op == "AveragePool") {
-            int x = in_val(0);
-            const Val& X = L.vals[x];
-            if (X.dims.size() != 4) fail(op + " " + n.name + ": input must be 4-D");
-            if (on.outputs.size() > 1 && !on.outputs[1].empty()) fail("MaxPool " + n.name + ": Indices output is not supported");
-            n.kind = op == "MaxPool" ? L_MAXPOOL : L_AVGPOOL;
-            read_window_attrs(on, n, X.h, X.w, false, nullptr);
-            n.count_include_pad = on.attr_i("count_include_pad", 0) != 0;
-            int64_t oh, ow;
-            conv_out_hw(X.h, X.w, n, on.attr_i("ceil_mode", 0) != 0, oh, ow);
-            n.in = {x};
-            odims = {X.n, X.c, oh, ow};
-        } else if (op == "GlobalAveragePool") {
-            int x = in_val(0);
-            const Val& X = L.vals[x];
-            if (X.dims.size() != 4) fail("GlobalAveragePool " + n.name + ": input must be 4-D");
-            n.kind = L_GAP;
-            n.in = {x};
-            odims = {X.n, X.c, 1, 1};
-        } else if (op == "Unsqueeze") {
-            // [N,C] -> [N,C,1,1]: storage is unchanged when only trailing unit axes are added
-            int x = in_val(0);
-            const Val& X = L.vals[x];
-            std::vector<int64_t> ax = on.attr_ints("axes", {});
-            if (ax.empty() && on.inputs.size() > 1) { const OnnxTensor* at = L.init(on.inputs[1]); if (at) ax = at->i; }
-            const int64_t orank = int64_t(X.dims.size() + ax.size());
-            for (auto& a : ax) if (a < 0) a += orank;
-            std::sort(ax.begin(), ax.end());
-            if (ax.empty() || X.h * X.w != 1 || X.dims.size() < 2 || ax[0] < int64_t(X.dims.size()) || orank > 4)
-                fail("Unsqueeze " + n.name + ": only trailing unit axes on [N,C] tensors are supported");
-            n.kind = L_ALIAS;
-            n.in = {x};
-            odims = X.dims;
-            while (int64_t(odims.size()) < orank) odims.push_back(1);
-        } else if (op == "Flatten" || op == "Reshape" || op == "Identity" || op == "Dropout" || op == "Squeeze") {
-            int x = in_val(0);
-            const Val& X = L.vals[x];
-            n.kind = L_ALIAS;
-            n.in = {x};
-            if (op == "Identity" || op == "Dropout") odims = X.dims;
-            else {
-                // Storage is NHWC: a reshape is a pure alias only when H*W == 1 on both sides.
-                if (X.h * X.w != 1) fail(op + " " + n.name + ": only supported on [N,C,1,1] / [N,C] tensors");
-                if (op == "Flatten") {
-                    if (on.attr_i("axis", 1) != 1) fail("Flatten " + n.name + ": only axis=1 is supported");
-                    odims = {X.n, X.c};
-                } else if (op == "Squeeze") odims = {X.n, X.c};
-                else {
-                    const OnnxTensor* shp = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
-                    if (!shp) fail("Reshape " + n.name + ": shape must be an initializer");
-                    std::vector<int64_t> d = shp->i;
-                    int64_t known = 1, neg = -1;
-                    for (size_t k = 0; k < d.size(); ++k) {
-                        if (d[k] == 0 && k < X.dims.size()) d[k] = X.dims[k];
-                        if (d[k] == -1) neg = int64_t(k); else known *= d[k];
-                    }
-                    if (neg >= 0) d[size_t(neg)] = X.n * X.c / known;
-                    int64_t tot = 1; for (auto v : d) tot *= v;
-                    if (tot != X.n * X.c || d.empty() || d[0] != X.n) fail("Reshape " + n.name + ": must keep the batch axis");
-                    for (size_t k = 2; k < d.size(); ++k) if (d[k] != 1) fail("Reshape " + n.name + ": unsupported target shape");
-                    odims = d;
-                }
-            }
-        } else if (op == "Resize" || op == "Upsample") {
-            // Resize-10 / 11 / 13 / 18 / 19 and Upsample-7 / 9 over 4-D tensors, scaling H and W only.  Resize-10 and Upsample have no
-            // coordinate_transformation_mode: they are `asymmetric` (with floor rounding for nearest, what the opset-10 definitions compute)
-            if (!act_input(0)) fail(op + " " + n.name + ": constant input is not supported");
-            const int x = in_val(0);
-            const Val& X = L.vals[x];
-            if (X.dims.size() != 4) fail(op + " " + n.name + ": only 4-D inputs are supported");
-            const bool legacy = op == "Upsample" || m.opset < 11;
-            std::string mode = "nearest";
-            if (on.attrs.count("mode")) mode = on.attrs.at("mode").s;
-            if (mode == "nearest") n.rs_mode = ResizeMode::Nearest;
-            else if (mode == "linear" || mode == "bilinear") n.rs_mode = ResizeMode::Linear;
-            else fail(op + " " + n.name + ": mode '" + mode + "' is not supported (nearest and linear are)");
-            std::string coord = legacy ? "asymmetric" : "half_pixel";
-            if (!legacy && on.attrs.count("coordinate_transformation_mode")) coord = on.attrs.at("coordinate_transformation_mode").s;
-            if (coord == "half_pixel") n.rs_coord = ResizeCoord::HalfPixel;
-            else if (coord == "pytorch_half_pixel") n.rs_coord = ResizeCoord::PytorchHalfPixel;
-            else if (coord == "align_corners") n.rs_coord = ResizeCoord::AlignCorners;
-            else if (coord == "asymmetric") n.rs_coord = ResizeCoord::Asymmetric;
-            else fail(op + " " + n.name + ": coordinate_transformation_mode '" + coord + "' is not supported");
-            std::string nearest = legacy ? "floor" : "round_prefer_floor";
-            if (!legacy && on.attrs.count("nearest_mode")) nearest = on.attrs.at("nearest_mode").s;
-            if (nearest == "round_prefer_floor") n.rs_nearest = ResizeNearest::RoundPreferFloor;
-            else if (nearest == "round_prefer_ceil") n.rs_nearest = ResizeNearest::RoundPreferCeil;
-            else if (nearest == "floor") n.rs_nearest = ResizeNearest::Floor;
-            else if (nearest == "ceil") n.rs_nearest = ResizeNearest::Ceil;
-            else fail(op + " " + n.name + ": nearest_mode '" + nearest + "' is not supported");
-            if (on.attr_i("antialias", 0) != 0) fail(op + " " + n.name + ": antialias = 1 is not supported");
-            if (on.attrs.count("keep_aspect_ratio_policy") && on.attrs.at("keep_aspect_ratio_policy").s != "stretch")
-                fail(op + " " + n.name + ": keep_aspect_ratio_policy '" + on.attrs.at("keep_aspect_ratio_policy").s + "' is not supported (stretch is)");
-            const bool has_axes = on.attrs.count("axes") != 0;
-            std::vector<int64_t> axes = on.attr_ints("axes", {0, 1, 2, 3});
-            for (auto& a : axes) {
-                if (a < 0) a += 4;
-                if (a < 0 || a > 3 || (has_axes && a < 2)) fail(op + " " + n.name + ": axes must be a subset of {2, 3}");
-            }
-            // the scales / sizes operand: Upsample-7 an attribute, Upsample-9 / Resize-10 input 1, Resize-11+ input 2 (scales) or 3 (sizes)
-            auto operand = [&](size_t k) -> const OnnxTensor* {
-                if (k >= on.inputs.size() || on.inputs[k].empty()) return nullptr;
-                const OnnxTensor* t = L.init(on.inputs[k]);
-                if (!t) fail(op + " " + n.name + ": " + (k == 3 ? "sizes" : "scales") + " must be a constant (initializer or Constant node)");
-                return t->numel() == 0 ? nullptr : t;
-            };
-            std::vector<double> scales;
-            std::vector<int64_t> sizes;
-            if (op == "Upsample" && on.attrs.count("scales")) for (float f : on.attrs.at("scales").floats) scales.push_back(f);
-            else if (legacy) { if (const OnnxTensor* t = operand(1)) for (float f : t->f) scales.push_back(f); }
-            else {
-                if (const OnnxTensor* t = operand(2)) for (float f : t->f) scales.push_back(f);
-                if (const OnnxTensor* t = operand(3)) sizes = t->i;
-                if (!scales.empty() && !sizes.empty()) fail(op + " " + n.name + ": only one of scales and sizes may be given");
-            }
-            if (scales.empty() && sizes.empty()) fail(op + " " + n.name + ": scales or sizes must be given");
-            const size_t cnt = scales.empty() ? sizes.size() : scales.size();
-            if (cnt != axes.size()) fail(op + " " + n.name + ": " + (scales.empty() ? "sizes" : "scales") + " must have one entry per axis");
-            double sc[4] = {1, 1, 1, 1};
-            int64_t out[4] = {X.dims[0], X.dims[1], X.dims[2], X.dims[3]};
-            for (size_t k = 0; k < axes.size(); ++k) {
-                const int a = int(axes[k]);
-                if (scales.empty()) {
-                    if (sizes[k] <= 0) fail(op + " " + n.name + ": sizes must be positive");
-                    out[a] = sizes[k];
-                    sc[a] = double(sizes[k]) / double(X.dims[size_t(a)]);
-                } else {
-                    if (!(scales[k] > 0)) fail(op + " " + n.name + ": scales must be positive");
-                    sc[a] = scales[k];
-                    out[a] = int64_t(std::floor(double(X.dims[size_t(a)]) * scales[k]));
-                    if (out[a] <= 0) fail(op + " " + n.name + ": the output would be empty");
-                }
-            }
-            if (out[0] != X.dims[0] || out[1] != X.dims[1])
-                fail(op + " " + n.name + ": only the spatial axes (2 and 3) may be resized; N and C must keep their size");
-            n.kind = L_RESIZE;
-            n.rs_sh = sc[2];
-            n.rs_sw = sc[3];
-            n.in = {x};
-            odims = {out[0], out[1], out[2], out[3]};
-        } else {
-            fail("Unsupported ONNX operator: " + op + " (node " + n.name + ")");
-        }
-        n.out = L.new_val(on.outputs[0], odims);
-        L.vals[n.out].producer = int(L.nodes.size());
-        L.nodes.push_back(std::move(n));
+// Shape arithmetic: every shape is known at plan time, so Shape -> Gather / Slice -> Unsqueeze -> Concat (-> Cast), the way torch exports the
+// `sizes` of an F.interpolate, folds into derived int64 initializers.  Only a Resize's `sizes` may read the result.  true: the node is done
+bool Planner::FoldShapeArithmetic(const OnnxNode& on, const LNode& n) {
+    const std::string& op = on.op;
+    const bool folding = op == "Shape" || op == "Gather" || op == "Slice" || op == "Cast" || op == "Concat" || op == "Unsqueeze" || op == "Squeeze" ||
+                         op == "Reshape" || op == "Flatten" || op == "Identity";
+    bool from_shape = op == "Shape";
+    for (size_t k = 0; k < on.inputs.size(); ++k) {
+        if (!L.shape_derived.count(on.inputs[k])) continue;
+        const bool sizes_in = (op == "Resize" && k == 3);
+        if (!folding && !sizes_in)
+            fail(op + " " + n.name + ": reads the shape arithmetic of a Shape node; shapes are only supported as the sizes of a Resize");
+        from_shape = true;
     }
+    if (from_shape && folding && op != "Shape" && !L.init(on.inputs[0]))
+        fail(op + " " + n.name + ": reads the shape arithmetic of a Shape node; shapes are only supported as the sizes of a Resize");
+    if (from_shape && folding) {
+        OnnxTensor t;
+        t.dtype = ONNX_INT64;
+        auto const_in = [&](size_t k) -> const OnnxTensor& {
+            const OnnxTensor* c = k < on.inputs.size() && !on.inputs[k].empty() ? L.init(on.inputs[k]) : nullptr;
+            if (!c) fail(op + " " + n.name + ": shape arithmetic needs constant operands");
+            return *c;
+        };
+        auto ints_of = [&](const OnnxTensor& c) {
+            if (!c.i.empty() || c.numel() == 0) return c.i;
+            std::vector<int64_t> v;
+            for (float f : c.f) v.push_back(int64_t(f));
+            return v;
+        };
+        if (op == "Shape") {
+            const Val& X = L.vals[in_val(on, 0)];
+            int64_t r = int64_t(X.dims.size());
+            int64_t b = on.attr_i("start", 0), e = on.attr_i("end", r);
+            if (b < 0) b += r;
+            if (e < 0) e += r;
+            b = std::clamp<int64_t>(b, 0, r);
+            e = std::clamp<int64_t>(e, b, r);
+            t.i.assign(X.dims.begin() + b, X.dims.begin() + e);
+            t.dims = {e - b};
+        } else if (op == "Gather") {
+            const std::vector<int64_t> d = ints_of(const_in(0));
+            const OnnxTensor& ix = const_in(1);
+            if (const_in(0).dims.size() != 1 || on.attr_i("axis", 0) != 0) fail("Gather " + n.name + ": shape arithmetic only gathers from a 1-D shape");
+            for (int64_t v : ints_of(ix)) {
+                if (v < 0) v += int64_t(d.size());
+                if (v < 0 || v >= int64_t(d.size())) fail("Gather " + n.name + ": index out of range");
+                t.i.push_back(d[size_t(v)]);
+            }
+            t.dims = ix.dims;
+        } else if (op == "Slice") {
+            const std::vector<int64_t> d = ints_of(const_in(0));
+            const int64_t r = int64_t(d.size());
+            std::vector<int64_t> st = on.attr_ints("starts", {}), en = on.attr_ints("ends", {}), ax = on.attr_ints("axes", {0}), stp = {1};
+            if (on.inputs.size() > 1) {              // opset >= 10: starts, ends, axes, steps are inputs
+                st = ints_of(const_in(1));
+                en = ints_of(const_in(2));
+                if (on.inputs.size() > 3 && !on.inputs[3].empty()) ax = ints_of(const_in(3));
+                if (on.inputs.size() > 4 && !on.inputs[4].empty()) stp = ints_of(const_in(4));
+            }
+            if (st.size() != 1 || en.size() != 1 || ax.size() != 1 || (ax[0] != 0 && ax[0] != -1) || stp.size() != 1 || stp[0] != 1)
+                fail("Slice " + n.name + ": shape arithmetic only slices a 1-D shape with step 1");
+            int64_t b = st[0] < 0 ? st[0] + r : st[0], e = en[0] < 0 ? en[0] + r : en[0];
+            b = std::clamp<int64_t>(b, 0, r);
+            e = std::clamp<int64_t>(e, b, r);
+            t.i.assign(d.begin() + b, d.begin() + e);
+            t.dims = {e - b};
+        } else if (op == "Concat") {
+            for (size_t k = 0; k < on.inputs.size(); ++k) {
+                const OnnxTensor& c = const_in(k);
+                if (c.dims.size() > 1) fail("Concat " + n.name + ": shape arithmetic only concatenates 1-D tensors (" + on.inputs[k] + " has rank " + std::to_string(c.dims.size()) + ")");
+                const std::vector<int64_t> v = ints_of(c);
+                t.i.insert(t.i.end(), v.begin(), v.end());
+            }
+            t.dims = {int64_t(t.i.size())};
+        } else if (op == "Cast") {
+            const OnnxTensor& c = const_in(0);
+            const int64_t to = on.attr_i("to", ONNX_INT64);
+            t = c;
+            if (to == ONNX_INT64 || to == ONNX_INT32) { t.i = ints_of(c); t.f.clear(); t.dtype = int(to); }
+            else if (to == ONNX_FLOAT || to == ONNX_DOUBLE) { t.f.clear(); for (int64_t v : ints_of(c)) t.f.push_back(float(v)); t.i.clear(); t.dtype = int(to); }
+            else fail("Cast " + n.name + ": shape arithmetic only casts to integer or floating-point types");
+        } else {
+            t.dtype = -1;                            // Unsqueeze / Squeeze / Reshape / Flatten / Identity: the constant folding below
+        }
+        L.shape_derived.insert(on.outputs[0]);
+        if (t.dtype != -1) {
+            t.name = on.outputs[0];
+            L.add_derived(std::move(t));
+            return true;
+        }
+    }
+    return false;
+}
 
+// shape-only ops on constants fold into a derived initializer (nothing is emitted).  true: the node is done
+bool Planner::FoldShapeOnlyOp(const OnnxNode& on, const LNode& n) {
+    const std::string& op = on.op;
+    if (!((op == "Unsqueeze" || op == "Squeeze" || op == "Reshape" || op == "Flatten" || op == "Identity") && L.init(on.inputs[0]))) return false;
+    OnnxTensor t = *L.init(on.inputs[0]);
+    auto axes_of = [&]() {
+        std::vector<int64_t> ax = on.attr_ints("axes", {});
+        if (ax.empty() && on.inputs.size() > 1 && !on.inputs[1].empty()) {       // opset >= 13: axes is an input
+            const OnnxTensor* at = L.init(on.inputs[1]);
+            if (!at) fail(op + " " + n.name + ": axes must be an initializer");
+            ax = at->i;
+        }
+        return ax;
+    };
+    if (op == "Unsqueeze") {
+        std::vector<int64_t> ax = axes_of();
+        if (ax.empty()) fail("Unsqueeze " + n.name + ": axes are required");
+        const int64_t orank = int64_t(t.dims.size() + ax.size());
+        for (auto& a : ax) { if (a < 0) a += orank; if (a < 0 || a >= orank) fail("Unsqueeze " + n.name + ": axis out of range"); }
+        std::sort(ax.begin(), ax.end());
+        std::vector<int64_t> nd;
+        size_t src = 0;
+        for (int64_t k = 0; k < orank; ++k) {
+            if (std::binary_search(ax.begin(), ax.end(), k)) nd.push_back(1);
+            else nd.push_back(t.dims.at(src++));
+        }
+        t.dims = nd;
+    } else if (op == "Squeeze") {
+        std::vector<int64_t> ax = axes_of();
+        const int64_t rank = int64_t(t.dims.size());
+        for (auto& a : ax) if (a < 0) a += rank;
+        std::vector<int64_t> nd;
+        for (int64_t k = 0; k < rank; ++k) {
+            const bool listed = std::find(ax.begin(), ax.end(), k) != ax.end();
+            if (listed && t.dims[size_t(k)] != 1) fail("Squeeze " + n.name + ": cannot squeeze a dimension of size != 1");
+            if (ax.empty() ? t.dims[size_t(k)] != 1 : !listed) nd.push_back(t.dims[size_t(k)]);
+        }
+        t.dims = nd;
+    } else if (op == "Reshape") {
+        const OnnxTensor* shp = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
+        std::vector<int64_t> d = shp ? shp->i : on.attr_ints("shape", {});
+        if (d.empty() && t.numel() != 1) fail("Reshape " + n.name + ": shape must be an initializer");
+        int64_t known = 1, neg = -1;
+        for (size_t k = 0; k < d.size(); ++k) {
+            if (d[k] == 0 && k < t.dims.size()) d[k] = t.dims[k];
+            if (d[k] == -1) neg = int64_t(k); else known *= d[k];
+        }
+        if (neg >= 0 && known > 0) d[size_t(neg)] = t.numel() / known;
+        int64_t tot = 1; for (auto v : d) tot *= v;
+        if (tot != t.numel()) fail("Reshape " + n.name + ": element count mismatch");
+        t.dims = d;
+    } else if (op == "Flatten") {
+        int64_t ax = on.attr_i("axis", 1);
+        if (ax < 0) ax += int64_t(t.dims.size());
+        int64_t a = 1, b = 1;
+        for (size_t k = 0; k < t.dims.size(); ++k) (int64_t(k) < ax ? a : b) *= t.dims[k];
+        t.dims = {a, b};
+    }
+    t.name = on.outputs[0];
+    L.add_derived(std::move(t));
+    return true;
+}
+
+void Planner::ImportConv(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    if (!act_input(on, 0)) fail("Conv " + n.name + ": constant input is not supported");
+    const OnnxTensor* w = L.init(on.inputs.at(1));
+    if (!w || w->dims.size() != 4) fail("Conv " + n.name + ": weights must be a 4-D initializer");
+    int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    if (X.dims.size() != 4) fail("Conv " + n.name + ": input must be 4-D");
+    int64_t co = w->dims[0], ci = w->dims[1];
+    const int64_t group = on.attr_i("group", 1);
+    if (group < 1) fail("Conv " + n.name + ": group = " + std::to_string(group) + " must be positive");
+    if (group != 1) {
+        // depthwise: one filter per channel; the weights [C, 1, kh, kw] pack as [C][kh][kw] (= [Cout][kh][kw][Cin] with Cin = 1).
+        // Any other group: output channel o reads input channels (o / (Cout / group)) * Cin / group ..., weights [Cout, Cin / group, kh, kw]
+        if (X.c % group != 0)
+            fail("Conv " + n.name + ": group = " + std::to_string(group) + " does not divide the input channels " + std::to_string(X.c));
+        if (co % group != 0)
+            fail("Conv " + n.name + ": group = " + std::to_string(group) + " does not divide the output channels " + std::to_string(co));
+        if (ci != X.c / group)
+            fail("Conv " + n.name + ": weight channels " + std::to_string(ci) + " != input channels / group = " + std::to_string(X.c / group));
+        n.dw = group == X.c && co == group;
+        // Grouped convolutions are opt-in: without IE_GROUPED_CONV=1 the planner keeps refusing them as it always has, so a model that
+        // loads (or is refused) today is planned exactly as before
+        if (!n.dw && !env.flag("IE_GROUPED_CONV"))
+            fail("Conv " + n.name + ": group = " + std::to_string(group) + " is not supported (only depthwise grouped convolutions, with group == input "
+                 "channels == output channels, are; set IE_GROUPED_CONV=1 to run the others on the grouped-convolution kernels)");
+        n.group = group;
+    } else if (ci != X.c) {
+        fail("Conv " + n.name + ": input channels " + std::to_string(X.c) + " != weight channels " + std::to_string(ci));
+    }
+    n.kind = L_CONV;
+    read_window_attrs(on, n, X.h, X.w, true, w);
+    if (n.kh != w->dims[2] || n.kw != w->dims[3]) fail("Conv " + n.name + ": kernel_shape does not match weights");
+    n.w.resize(size_t(co * ci * n.kh * n.kw));
+    for (int64_t o = 0; o < co; ++o)
+        for (int64_t c = 0; c < ci; ++c)
+            for (int ky = 0; ky < n.kh; ++ky)
+                for (int kx = 0; kx < n.kw; ++kx)
+                    n.w[size_t(((o * n.kh + ky) * n.kw + kx) * ci + c)] =
+                        w->f[size_t(((o * ci + c) * n.kh + ky) * n.kw + kx)];
+    if (on.inputs.size() > 2 && !on.inputs[2].empty()) {
+        const OnnxTensor* b = L.init(on.inputs[2]);
+        if (!b || b->numel() != co) fail("Conv " + n.name + ": bias must be a [Cout] initializer");
+        n.bias = b->f;
+    }
+    if (n.dil_h > 1 || n.dil_w > 1) {
+        if (group != 1)
+            fail("Conv " + n.name + ": dilated " + std::string(n.dw ? "depthwise" : "grouped") + " convolutions are not supported (dilations " +
+                 std::to_string(n.dil_h) + "x" + std::to_string(n.dil_w) + ", group = " + std::to_string(group) + ")");
+        // Centre-tap collapse (exact): stride 1, odd k, pads d * (k / 2) and d >= the image extent on every dilated axis.  The nearest
+        // off-centre tap is d pixels from the output pixel, so it lands in the padding for EVERY output pixel: the conv is the 1x1 conv of
+        // its centre weights (DeepLabV3's rate-36 ASPP branch at 28x28).  It then takes every 1x1 path, and its FLOPs are the 1x1's.
+        auto centre_only = [](int k, int d, int s, int p0, int p1, int64_t len) {
+            return k == 1 ? (p0 == 0 && p1 == 0) : (s == 1 && k % 2 == 1 && p0 == d * (k / 2) && p1 == p0 && d >= len);
+        };
+        if (centre_only(n.kh, n.dil_h, n.sh, n.pt, n.pb, X.h) && centre_only(n.kw, n.dil_w, n.sw, n.pl, n.pr, X.w)) {
+            std::vector<float> wc(size_t(co * ci));
+            for (int64_t o = 0; o < co; ++o)
+                for (int64_t c = 0; c < ci; ++c) wc[size_t(o * ci + c)] = n.w[size_t(((o * n.kh + n.kh / 2) * n.kw + n.kw / 2) * ci + c)];
+            n.w = std::move(wc);
+            n.kh = n.kw = 1;
+            n.pt = n.pl = n.pb = n.pr = 0;
+            n.dil_h = n.dil_w = 1;
+        }
+    }
+    int64_t oh, ow;
+    conv_out_hw(X.h, X.w, n, false, oh, ow);
+    n.in = {x};
+    odims = {X.n, co, oh, ow};
+}
+
+void Planner::ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    const std::string& op = on.op;
+    if (!act_input(on, 0)) fail(op + " " + n.name + ": constant first operand is not supported");
+    const OnnxTensor* b = L.init(on.inputs.at(1));
+    if (!b || b->dims.size() != 2) fail(op + " " + n.name + ": second operand must be a 2-D initializer");
+    int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    if (X.h * X.w != 1) fail(op + " " + n.name + ": input must be [N, K]");
+    bool transB = op == "Gemm" && on.attr_i("transB", 0) != 0;
+    if (op == "Gemm" && on.attr_i("transA", 0) != 0) fail("Gemm " + n.name + ": transA is not supported");
+    float alpha = op == "Gemm" ? on.attr_f("alpha", 1.f) : 1.f;
+    float beta = op == "Gemm" ? on.attr_f("beta", 1.f) : 1.f;
+    int64_t K = transB ? b->dims[1] : b->dims[0], N = transB ? b->dims[0] : b->dims[1];
+    if (K != X.c) fail(op + " " + n.name + ": inner dimensions do not match");
+    n.kind = L_CONV;
+    n.w.resize(size_t(N * K));
+    for (int64_t o = 0; o < N; ++o)
+        for (int64_t k = 0; k < K; ++k)
+            n.w[size_t(o * K + k)] = alpha * (transB ? b->f[size_t(o * K + k)] : b->f[size_t(k * N + o)]);
+    if (op == "Gemm" && on.inputs.size() > 2 && !on.inputs[2].empty()) {
+        const OnnxTensor* c = L.init(on.inputs[2]);
+        if (!c) fail("Gemm " + n.name + ": C must be an initializer");
+        if (c->numel() == N) n.bias = c->f;
+        else if (c->numel() == 1) n.bias.assign(size_t(N), c->f[0]);
+        else fail("Gemm " + n.name + ": C must broadcast over rows");
+        for (auto& v : n.bias) v *= beta;
+    }
+    n.in = {x};
+    odims = {X.n, N};
+    if (X.dims.size() == 1) odims = {N};
+}
+
+void Planner::ImportBatchNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    const OnnxTensor *g = L.init(on.inputs.at(1)), *be = L.init(on.inputs.at(2)), *mu = L.init(on.inputs.at(3)),
+                     *var = L.init(on.inputs.at(4));
+    if (!g || !be || !mu || !var) fail("BatchNormalization " + n.name + ": parameters must be initializers");
+    if (g->numel() != X.c || be->numel() != X.c || mu->numel() != X.c || var->numel() != X.c)
+        fail("BatchNormalization " + n.name + ": parameter size != channels");
+    double eps = on.attr_f("epsilon", 1e-5f);
+    n.kind = L_AFFINE;
+    n.s.resize(size_t(X.c)); n.t.resize(size_t(X.c));
+    for (int64_t c = 0; c < X.c; ++c) {
+        double s = double(g->f[c]) / std::sqrt(double(var->f[c]) + eps);
+        n.s[c] = float(s);
+        n.t[c] = float(double(be->f[c]) - double(mu->f[c]) * s);
+    }
+    n.in = {x};
+    odims = X.dims;
+}
+
+// Add / Mul / Div: of two activations (L_ADD, L_MUL), or of an activation and a per-channel constant (L_AFFINE)
+void Planner::ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    const std::string& op = on.op;
+    bool a0 = act_input(on, 0), a1 = act_input(on, 1);
+    if (op == "Div" && (a1 || !a0)) fail("Div " + n.name + ": only the division of an activation by a constant is supported");
+    if (a0 && a1 && op == "Mul") {
+        // same shapes, or [N,C,H,W] x [N,C,1,1] in either order (a squeeze-excite gate); in[0] = the full tensor
+        int a = in_val(on, 0), b = in_val(on, 1);
+        const Val &A = L.vals[a], &Bv = L.vals[b];
+        const bool bcast_b = A.dims.size() == 4 && Bv.dims.size() == 4 && A.n == Bv.n && A.c == Bv.c && Bv.h == 1 && Bv.w == 1;
+        const bool bcast_a = A.dims.size() == 4 && Bv.dims.size() == 4 && A.n == Bv.n && A.c == Bv.c && A.h == 1 && A.w == 1;
+        if (A.dims != Bv.dims) {
+            if (bcast_a && !bcast_b) std::swap(a, b);
+            else if (!bcast_b) fail("Mul " + n.name + ": only same-shape activations or [N,C,H,W] x [N,C,1,1] broadcasting are supported between two activations");
+        }
+        n.kind = L_MUL;
+        n.in = {a, b};
+        odims = L.vals[a].dims;
+    } else if (a0 && a1) {
+        int a = in_val(on, 0), b = in_val(on, 1);
+        if (L.vals[a].dims != L.vals[b].dims) fail("Add " + n.name + ": broadcasting between activations is not supported");
+        n.kind = L_ADD;
+        n.in = {a, b};
+        odims = L.vals[a].dims;
+    } else if (a0 || a1) {
+        int x = in_val(on, a0 ? 0 : 1);
+        const OnnxTensor* c = L.init(on.inputs[a0 ? 1 : 0]);
+        std::vector<float> pc;
+        // rank-1 constant against a rank-2 activation aligns with the last (= channel) axis
+        const Val& X = L.vals[x];
+        // opset < 7 (Caffe2-era exports): Add/Mul carry broadcast=1 and an axis that places the constant's dims inside the
+        // activation's (axis=1 with a [C] constant = per channel); without an axis the constant aligns with the trailing dims
+        int64_t legacy_axis = -1;
+        if (m.opset > 0 && m.opset < 7 && on.attr_i("broadcast", 0) != 0 && on.attrs.count("axis")) {
+            legacy_axis = on.attr_i("axis", 0);
+            if (legacy_axis < 0) legacy_axis += int64_t(X.dims.size());
+        }
+        if (m.opset > 0 && m.opset < 7 && on.attr_i("broadcast", 0) == 0 && c->dims != X.dims && c->numel() != 1)
+            fail(op + " " + n.name + ": operand shapes differ and the opset-" + std::to_string(m.opset) + " broadcast attribute is not set");
+        bool ok = L.per_channel_const(*c, X, pc, legacy_axis);
+        if (!ok && X.dims.size() == 2 && c->dims.size() == 1 && c->numel() == X.c) { pc = c->f; ok = true; }
+        if (!ok && X.dims.size() == 2 && c->dims.size() == 2 && c->dims[0] == 1 && c->dims[1] == X.c) { pc = c->f; ok = true; }
+        if (!ok) fail(op + " " + n.name + ": constant operand must broadcast per channel");
+        n.kind = L_AFFINE;
+        if (op == "Add") { n.s.assign(size_t(X.c), 1.f); n.t = pc; }
+        else if (op == "Div") {
+            // x / c = x * (1 / c): an affine step like a Mul (hardswish exports that end in "/ 6")
+            for (float& v : pc) {
+                if (v == 0.f) fail("Div " + n.name + ": division by zero");
+                v = 1.f / v;
+            }
+            n.s = pc;
+            n.t.assign(size_t(X.c), 0.f);
+        }
+        else { n.s = pc; n.t.assign(size_t(X.c), 0.f); }
+        n.in = {x};
+        odims = X.dims;
+    } else fail(op + " " + n.name + ": constant folding of two initializers is not supported");
+}
+
+// Clip, Sigmoid / HardSigmoid / HardSwish, Relu
+void Planner::ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    const std::string& op = on.op;
+    if (op == "Clip") {
+        // opset < 11: min / max attributes; opset >= 11: optional scalar inputs 2 and 3 (absent or "" = unbounded)
+        n.kind = L_CLIP;
+        n.in = {in_val(on, 0)};
+        odims = L.vals[n.in[0]].dims;
+        if (on.attrs.count("min")) n.lo = on.attr_f("min", -kInf);
+        if (on.attrs.count("max")) n.hi = on.attr_f("max", kInf);
+        for (size_t k = 1; k < 3 && k < on.inputs.size(); ++k) {
+            if (on.inputs[k].empty()) continue;
+            const OnnxTensor* b = L.init(on.inputs[k]);
+            if (!b) fail("Clip " + n.name + ": the " + (k == 1 ? "min" : "max") + " bound must be a constant (initializer or Constant node)");
+            if (b->numel() != 1 || (b->dtype != ONNX_FLOAT && b->dtype != ONNX_DOUBLE && b->dtype != ONNX_FLOAT16))
+                fail("Clip " + n.name + ": the " + (k == 1 ? "min" : "max") + " bound must be a floating-point scalar");
+            (k == 1 ? n.lo : n.hi) = b->f[0];
+        }
+    } else if (op == "Relu") {
+        n.kind = L_RELU;
+        n.in = {in_val(on, 0)};
+        odims = L.vals[n.in[0]].dims;
+    } else {
+        n.kind = L_ACT;
+        if (op == "Sigmoid") n.act.kind = ActKind::Sigmoid;
+        else if (op == "HardSigmoid") { n.act.kind = ActKind::HardSigmoid; n.act.a = on.attr_f("alpha", 0.2f); n.act.b = on.attr_f("beta", 0.5f); }
+        else { n.act.kind = ActKind::HardSwish; n.act.a = 1.f / 6.f; n.act.b = 0.5f; }
+        if (!act_input(on, 0)) fail(op + " " + n.name + ": constant input is not supported");
+        n.in = {in_val(on, 0)};
+        odims = L.vals[n.in[0]].dims;
+    }
+}
+
+void Planner::ImportConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    int64_t axis = on.attr_i("axis", 1);
+    n.kind = L_CONCAT;
+    for (size_t k = 0; k < on.inputs.size(); ++k) {
+        if (!act_input(on, k)) fail("Concat " + n.name + ": constant inputs are not supported");
+        n.in.push_back(in_val(on, k));
+    }
+    const Val& X0 = L.vals[n.in[0]];
+    if (axis < 0) axis += int64_t(X0.dims.size());
+    if (axis != 1) fail("Concat " + n.name + ": only axis=1 (channels) is supported");
+    odims = X0.dims;
+    int64_t ctot = 0;
+    for (int v : n.in) {
+        const Val& X = L.vals[v];
+        if (X.dims.size() != X0.dims.size()) fail("Concat " + n.name + ": rank mismatch");
+        for (size_t k = 0; k < X.dims.size(); ++k)
+            if (k != 1 && X.dims[k] != X0.dims[k]) fail("Concat " + n.name + ": shape mismatch");
+        ctot += X.c;
+    }
+    odims[1] = ctot;
+}
+
+// MaxPool / AveragePool / GlobalAveragePool
+void Planner::ImportPool(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    const std::string& op = on.op;
+    if (op == "GlobalAveragePool") {
+        int x = in_val(on, 0);
+        const Val& X = L.vals[x];
+        if (X.dims.size() != 4) fail("GlobalAveragePool " + n.name + ": input must be 4-D");
+        n.kind = L_GAP;
+        n.in = {x};
+        odims = {X.n, X.c, 1, 1};
+        return;
+    }
+    int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    if (X.dims.size() != 4) fail(op + " " + n.name + ": input must be 4-D");
+    if (on.outputs.size() > 1 && !on.outputs[1].empty()) fail("MaxPool " + n.name + ": Indices output is not supported");
+    n.kind = op == "MaxPool" ? L_MAXPOOL : L_AVGPOOL;
+    read_window_attrs(on, n, X.h, X.w, false, nullptr);
+    n.count_include_pad = on.attr_i("count_include_pad", 0) != 0;
+    int64_t oh, ow;
+    conv_out_hw(X.h, X.w, n, on.attr_i("ceil_mode", 0) != 0, oh, ow);
+    n.in = {x};
+    odims = {X.n, X.c, oh, ow};
+}
+
+// The ops that only rename storage: Unsqueeze, Flatten, Reshape, Squeeze, Identity, Dropout
+void Planner::ImportReshape(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    const std::string& op = on.op;
+    if (op == "Unsqueeze") {
+        // [N,C] -> [N,C,1,1]: storage is unchanged when only trailing unit axes are added
+        int x = in_val(on, 0);
+        const Val& X = L.vals[x];
+        std::vector<int64_t> ax = on.attr_ints("axes", {});
+        if (ax.empty() && on.inputs.size() > 1) { const OnnxTensor* at = L.init(on.inputs[1]); if (at) ax = at->i; }
+        const int64_t orank = int64_t(X.dims.size() + ax.size());
+        for (auto& a : ax) if (a < 0) a += orank;
+        std::sort(ax.begin(), ax.end());
+        if (ax.empty() || X.h * X.w != 1 || X.dims.size() < 2 || ax[0] < int64_t(X.dims.size()) || orank > 4)
+            fail("Unsqueeze " + n.name + ": only trailing unit axes on [N,C] tensors are supported");
+        n.kind = L_ALIAS;
+        n.in = {x};
+        odims = X.dims;
+        while (int64_t(odims.size()) < orank) odims.push_back(1);
+        return;
+    }
+    int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    n.kind = L_ALIAS;
+    n.in = {x};
+    if (op == "Identity" || op == "Dropout") odims = X.dims;
+    else {
+        // Storage is NHWC: a reshape is a pure alias only when H*W == 1 on both sides.
+        if (X.h * X.w != 1) fail(op + " " + n.name + ": only supported on [N,C,1,1] / [N,C] tensors");
+        if (op == "Flatten") {
+            if (on.attr_i("axis", 1) != 1) fail("Flatten " + n.name + ": only axis=1 is supported");
+            odims = {X.n, X.c};
+        } else if (op == "Squeeze") odims = {X.n, X.c};
+        else {
+            const OnnxTensor* shp = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
+            if (!shp) fail("Reshape " + n.name + ": shape must be an initializer");
+            std::vector<int64_t> d = shp->i;
+            int64_t known = 1, neg = -1;
+            for (size_t k = 0; k < d.size(); ++k) {
+                if (d[k] == 0 && k < X.dims.size()) d[k] = X.dims[k];
+                if (d[k] == -1) neg = int64_t(k); else known *= d[k];
+            }
+            if (neg >= 0) d[size_t(neg)] = X.n * X.c / known;
+            int64_t tot = 1; for (auto v : d) tot *= v;
+            if (tot != X.n * X.c || d.empty() || d[0] != X.n) fail("Reshape " + n.name + ": must keep the batch axis");
+            for (size_t k = 2; k < d.size(); ++k) if (d[k] != 1) fail("Reshape " + n.name + ": unsupported target shape");
+            odims = d;
+        }
+    }
+}
+
+// Resize-10 / 11 / 13 / 18 / 19 and Upsample-7 / 9 over 4-D tensors, scaling H and W only.  Resize-10 and Upsample have no
+// coordinate_transformation_mode: they are `asymmetric` (with floor rounding for nearest, what the opset-10 definitions compute)
+void Planner::ImportResize(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    const std::string& op = on.op;
+    if (!act_input(on, 0)) fail(op + " " + n.name + ": constant input is not supported");
+    const int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    if (X.dims.size() != 4) fail(op + " " + n.name + ": only 4-D inputs are supported");
+    const bool legacy = op == "Upsample" || m.opset < 11;
+    std::string mode = "nearest";
+    if (on.attrs.count("mode")) mode = on.attrs.at("mode").s;
+    if (mode == "nearest") n.rs_mode = ResizeMode::Nearest;
+    else if (mode == "linear" || mode == "bilinear") n.rs_mode = ResizeMode::Linear;
+    else fail(op + " " + n.name + ": mode '" + mode + "' is not supported (nearest and linear are)");
+    std::string coord = legacy ? "asymmetric" : "half_pixel";
+    if (!legacy && on.attrs.count("coordinate_transformation_mode")) coord = on.attrs.at("coordinate_transformation_mode").s;
+    if (coord == "half_pixel") n.rs_coord = ResizeCoord::HalfPixel;
+    else if (coord == "pytorch_half_pixel") n.rs_coord = ResizeCoord::PytorchHalfPixel;
+    else if (coord == "align_corners") n.rs_coord = ResizeCoord::AlignCorners;
+    else if (coord == "asymmetric") n.rs_coord = ResizeCoord::Asymmetric;
+    else fail(op + " " + n.name + ": coordinate_transformation_mode '" + coord + "' is not supported");
+    std::string nearest = legacy ? "floor" : "round_prefer_floor";
+    if (!legacy && on.attrs.count("nearest_mode")) nearest = on.attrs.at("nearest_mode").s;
+    if (nearest == "round_prefer_floor") n.rs_nearest = ResizeNearest::RoundPreferFloor;
+    else if (nearest == "round_prefer_ceil") n.rs_nearest = ResizeNearest::RoundPreferCeil;
+    else if (nearest == "floor") n.rs_nearest = ResizeNearest::Floor;
+    else if (nearest == "ceil") n.rs_nearest = ResizeNearest::Ceil;
+    else fail(op + " " + n.name + ": nearest_mode '" + nearest + "' is not supported");
+    if (on.attr_i("antialias", 0) != 0) fail(op + " " + n.name + ": antialias = 1 is not supported");
+    if (on.attrs.count("keep_aspect_ratio_policy") && on.attrs.at("keep_aspect_ratio_policy").s != "stretch")
+        fail(op + " " + n.name + ": keep_aspect_ratio_policy '" + on.attrs.at("keep_aspect_ratio_policy").s + "' is not supported (stretch is)");
+    const bool has_axes = on.attrs.count("axes") != 0;
+    std::vector<int64_t> axes = on.attr_ints("axes", {0, 1, 2, 3});
+    for (auto& a : axes) {
+        if (a < 0) a += 4;
+        if (a < 0 || a > 3 || (has_axes && a < 2)) fail(op + " " + n.name + ": axes must be a subset of {2, 3}");
+    }
+    // the scales / sizes operand: Upsample-7 an attribute, Upsample-9 / Resize-10 input 1, Resize-11+ input 2 (scales) or 3 (sizes)
+    auto operand = [&](size_t k) -> const OnnxTensor* {
+        if (k >= on.inputs.size() || on.inputs[k].empty()) return nullptr;
+        const OnnxTensor* t = L.init(on.inputs[k]);
+        if (!t) fail(op + " " + n.name + ": " + (k == 3 ? "sizes" : "scales") + " must be a constant (initializer or Constant node)");
+        return t->numel() == 0 ? nullptr : t;
+    };
+    std::vector<double> scales;
+    std::vector<int64_t> sizes;
+    if (op == "Upsample" && on.attrs.count("scales")) for (float f : on.attrs.at("scales").floats) scales.push_back(f);
+    else if (legacy) { if (const OnnxTensor* t = operand(1)) for (float f : t->f) scales.push_back(f); }
+    else {
+        if (const OnnxTensor* t = operand(2)) for (float f : t->f) scales.push_back(f);
+        if (const OnnxTensor* t = operand(3)) sizes = t->i;
+        if (!scales.empty() && !sizes.empty()) fail(op + " " + n.name + ": only one of scales and sizes may be given");
+    }
+    if (scales.empty() && sizes.empty()) fail(op + " " + n.name + ": scales or sizes must be given");
+    const size_t cnt = scales.empty() ? sizes.size() : scales.size();
+    if (cnt != axes.size()) fail(op + " " + n.name + ": " + (scales.empty() ? "sizes" : "scales") + " must have one entry per axis");
+    double sc[4] = {1, 1, 1, 1};
+    int64_t out[4] = {X.dims[0], X.dims[1], X.dims[2], X.dims[3]};
+    for (size_t k = 0; k < axes.size(); ++k) {
+        const int a = int(axes[k]);
+        if (scales.empty()) {
+            if (sizes[k] <= 0) fail(op + " " + n.name + ": sizes must be positive");
+            out[a] = sizes[k];
+            sc[a] = double(sizes[k]) / double(X.dims[size_t(a)]);
+        } else {
+            if (!(scales[k] > 0)) fail(op + " " + n.name + ": scales must be positive");
+            sc[a] = scales[k];
+            out[a] = int64_t(std::floor(double(X.dims[size_t(a)]) * scales[k]));
+            if (out[a] <= 0) fail(op + " " + n.name + ": the output would be empty");
+        }
+    }
+    if (out[0] != X.dims[0] || out[1] != X.dims[1])
+        fail(op + " " + n.name + ": only the spatial axes (2 and 3) may be resized; N and C must keep their size");
+    n.kind = L_RESIZE;
+    n.rs_sh = sc[2];
+    n.rs_sw = sc[3];
+    n.in = {x};
+    odims = {out[0], out[1], out[2], out[3]};
+}
+
+// ---- one ONNX node -> one logical node with shape inference (or a derived initializer) ----
+void Planner::ImportNode(const OnnxNode& on) {
+    if (FoldConstantNode(on)) return;
+    if (on.outputs.empty() || on.inputs.empty()) fail("node " + on.name + " (" + on.op + ") has no inputs/outputs");
+    LNode n;
+    n.name = on.name.empty() ? on.outputs[0] : on.name;
+    if (FoldShapeArithmetic(on, n) || FoldShapeOnlyOp(on, n)) return;
+    const std::string& op = on.op;
+    std::vector<int64_t> odims;
+    if (op == "Conv") ImportConv(on, n, odims);
+    else if (op == "MatMul" || op == "Gemm") ImportGemm(on, n, odims);
+    else if (op == "BatchNormalization") ImportBatchNorm(on, n, odims);
+    else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu") ImportActivation(on, n, odims);
+    else if (op == "Add" || op == "Mul" || op == "Div") ImportArithmetic(on, n, odims);
+    else if (op == "Concat") ImportConcat(on, n, odims);
+    else if (op == "MaxPool" || op == "AveragePool" || op == "GlobalAveragePool") ImportPool(on, n, odims);
+    else if (op == "Unsqueeze" || op == "Flatten" || op == "Reshape" || op == "Identity" || op == "Dropout" || op == "Squeeze") ImportReshape(on, n, odims);
+    else if (op == "Resize" || op == "Upsample") ImportResize(on, n, odims);
+    else fail("Unsupported ONNX operator: " + op + " (node " + n.name + ")");
+    n.out = L.new_val(on.outputs[0], odims);
+    L.vals[n.out].producer = int(L.nodes.size());
+    L.nodes.push_back(std::move(n));
+}
+
+void Planner::MarkOutputs() {
     for (const auto& vo : m.outputs) {
         int v = L.get_val(vo.name);
         L.vals[v].is_output = true;
     }
-    if (precision == Precision::F8 || f8_fusions)
-        for (const LNode& n : L.nodes) {
-            if (n.dw) fail("depthwise convolution is not supported in fp8 mode (Conv " + n.name + ")");
-            if (n.kind == L_CONV && n.group != 1) fail("grouped convolution is not supported in fp8 mode (Conv " + n.name + ")");
-            if (n.kind == L_CONV && (n.dil_h > 1 || n.dil_w > 1)) fail("dilated convolution is not supported in fp8 mode (Conv " + n.name + ")");
-            if (n.kind == L_RESIZE) fail("Resize is not supported in fp8 mode (node " + n.name + ")");
-        }
+}
 
-    if (precision == Precision::F8 || f8_fusions)
-        for (const LNode& n : L.nodes)
-            if (n.kind == L_ACT || n.kind == L_MUL)
-                fail("activation and squeeze-excite nodes (Sigmoid, HardSigmoid, HardSwish, Mul of two activations) are not supported in fp8 mode (node " + n.name + ")");
+// fp8 mode has no kernels for these: a load error, never another kernel reading the bytes
+void Planner::RefuseForF8() const {
+    for (const LNode& n : L.nodes) {
+        if (n.dw) fail("depthwise convolution is not supported in fp8 mode (Conv " + n.name + ")");
+        if (n.kind == L_CONV && n.group != 1) fail("grouped convolution is not supported in fp8 mode (Conv " + n.name + ")");
+        if (n.kind == L_CONV && (n.dil_h > 1 || n.dil_w > 1)) fail("dilated convolution is not supported in fp8 mode (Conv " + n.name + ")");
+        if (n.kind == L_RESIZE) fail("Resize is not supported in fp8 mode (node " + n.name + ")");
+    }
+    for (const LNode& n : L.nodes)
+        if (n.kind == L_ACT || n.kind == L_MUL)
+            fail("activation and squeeze-excite nodes (Sigmoid, HardSigmoid, HardSwish, Mul of two activations) are not supported in fp8 mode (node " + n.name + ")");
+}
 
-    auto single_consumer = [&](int v) { return !L.vals[v].is_output && L.consumers(v).size() == 1; };
-
-    // ---- activation patterns: Mul(x, Sigmoid(x)) = SiLU, Mul(x, HardSigmoid(x; a, b)) = hardswish(a, b) (opset < 14 exports), either order ----
+// ---- activation patterns: Mul(x, Sigmoid(x)) = SiLU, Mul(x, HardSigmoid(x; a, b)) = hardswish(a, b) (opset < 14 exports), either order ----
+void Planner::FuseActivationPatterns() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& mu = L.nodes[i];
         if (mu.dead || mu.kind != L_MUL || L.vals[mu.in[0]].dims != L.vals[mu.in[1]].dims) continue;
@@ -890,57 +1051,60 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             break;
         }
     }
-    // ---- squeeze-excite: GlobalAveragePool -> Conv1x1 -> ReLU | act -> Conv1x1 -> act -> Mul(x, gate) as ONE node, where x is read by the pool
-    //      and the Mul only (IE_NO_SE_FUSE=1: the separate steps) ----
-    if (!env.get("IE_NO_SE_FUSE")) {
-        auto prod = [&](int v, LKind k) -> LNode* {
-            const int p = L.vals[v].producer;
-            if (p < 0 || L.nodes[p].dead || L.nodes[p].kind != k || !single_consumer(v)) return nullptr;
-            return &L.nodes[p];
-        };
-        auto fc_ok = [&](const LNode* c, int64_t cin, int64_t cout) {
-            return c && c->group == 1 && c->kh == 1 && c->kw == 1 && c->sh == 1 && c->sw == 1 && !c->pt && !c->pl && !c->pb && !c->pr && c->res < 0 &&
-                   L.vals[c->in[0]].dims.size() == 4 && L.vals[c->in[0]].c == cin && L.vals[c->out].c == cout && int64_t(c->w.size()) == cin * cout;
-        };
-        for (size_t i = 0; i < L.nodes.size(); ++i) {
-            LNode& mu = L.nodes[i];
-            if (mu.dead || mu.kind != L_MUL) continue;
-            const int x = mu.in[0];
-            const Val& X = L.vals[x];
-            if (X.dims.size() != 4 || L.vals[mu.in[1]].h * L.vals[mu.in[1]].w != 1 || X.h * X.w == 1 || X.is_output || X.is_input) continue;
-            LNode* gate = prod(mu.in[1], L_ACT);
-            LNode* c2 = gate ? prod(gate->in[0], L_CONV) : nullptr;
-            if (!c2) continue;
-            const int hv = c2->in[0];
-            const int64_t mid = L.vals[hv].c;
-            LNode* a1 = prod(hv, L_RELU);
-            if (!a1) a1 = prod(hv, L_ACT);
-            LNode* c1 = a1 ? prod(a1->in[0], L_CONV) : nullptr;
-            LNode* gp = c1 ? prod(c1->in[0], L_GAP) : nullptr;
-            if (!gp || gp->in[0] != x || !fc_ok(c1, X.c, mid) || !fc_ok(c2, mid, X.c)) continue;
-            const std::vector<int> readers = L.consumers(x);
-            if (readers.size() != 2) continue;
-            LNode se;
-            se.kind = L_SE;
-            se.name = gp->name + " ... " + mu.name;
-            se.in = {x};
-            se.out = mu.out;
-            se.w = c1->w;
-            se.bias = c1->bias;
-            se.w2.resize(c2->w.size());
-            for (int64_t o = 0; o < X.c; ++o)
-                for (int64_t j = 0; j < mid; ++j) se.w2[size_t(j * X.c + o)] = c2->w[size_t(o * mid + j)];
-            se.bias2 = c2->bias;
-            se.se_mid = int(mid);
-            if (a1->kind == L_RELU) se.se_act1.kind = ActKind::Relu;
-            else se.se_act1 = a1->act;
-            se.act = gate->act;
-            gp->dead = c1->dead = a1->dead = c2->dead = gate->dead = true;
-            mu = std::move(se);
-        }
-    }
+}
 
-    // ---- fusion 1: merge Affine->Affine chains (BN followed by Caffe-style Scale Mul/Add) ----------
+// ---- squeeze-excite: GlobalAveragePool -> Conv1x1 -> ReLU | act -> Conv1x1 -> act -> Mul(x, gate) as ONE node, where x is read by the pool
+//      and the Mul only (IE_NO_SE_FUSE=1: the separate steps) ----
+void Planner::FuseSqueezeExcite() {
+    auto prod = [&](int v, LKind k) -> LNode* {
+        const int p = L.vals[v].producer;
+        if (p < 0 || L.nodes[p].dead || L.nodes[p].kind != k || !single_consumer(v)) return nullptr;
+        return &L.nodes[p];
+    };
+    auto fc_ok = [&](const LNode* c, int64_t cin, int64_t cout) {
+        return c && c->group == 1 && c->kh == 1 && c->kw == 1 && c->sh == 1 && c->sw == 1 && !c->pt && !c->pl && !c->pb && !c->pr && c->res < 0 &&
+               L.vals[c->in[0]].dims.size() == 4 && L.vals[c->in[0]].c == cin && L.vals[c->out].c == cout && int64_t(c->w.size()) == cin * cout;
+    };
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& mu = L.nodes[i];
+        if (mu.dead || mu.kind != L_MUL) continue;
+        const int x = mu.in[0];
+        const Val& X = L.vals[x];
+        if (X.dims.size() != 4 || L.vals[mu.in[1]].h * L.vals[mu.in[1]].w != 1 || X.h * X.w == 1 || X.is_output || X.is_input) continue;
+        LNode* gate = prod(mu.in[1], L_ACT);
+        LNode* c2 = gate ? prod(gate->in[0], L_CONV) : nullptr;
+        if (!c2) continue;
+        const int hv = c2->in[0];
+        const int64_t mid = L.vals[hv].c;
+        LNode* a1 = prod(hv, L_RELU);
+        if (!a1) a1 = prod(hv, L_ACT);
+        LNode* c1 = a1 ? prod(a1->in[0], L_CONV) : nullptr;
+        LNode* gp = c1 ? prod(c1->in[0], L_GAP) : nullptr;
+        if (!gp || gp->in[0] != x || !fc_ok(c1, X.c, mid) || !fc_ok(c2, mid, X.c)) continue;
+        const std::vector<int> readers = L.consumers(x);
+        if (readers.size() != 2) continue;
+        LNode se;
+        se.kind = L_SE;
+        se.name = gp->name + " ... " + mu.name;
+        se.in = {x};
+        se.out = mu.out;
+        se.w = c1->w;
+        se.bias = c1->bias;
+        se.w2.resize(c2->w.size());
+        for (int64_t o = 0; o < X.c; ++o)
+            for (int64_t j = 0; j < mid; ++j) se.w2[size_t(j * X.c + o)] = c2->w[size_t(o * mid + j)];
+        se.bias2 = c2->bias;
+        se.se_mid = int(mid);
+        if (a1->kind == L_RELU) se.se_act1.kind = ActKind::Relu;
+        else se.se_act1 = a1->act;
+        se.act = gate->act;
+        gp->dead = c1->dead = a1->dead = c2->dead = gate->dead = true;
+        mu = std::move(se);
+    }
+}
+
+// ---- fusion 1: merge Affine->Affine chains (BN followed by Caffe-style Scale Mul/Add) ----------
+void Planner::MergeAffineChains() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& a = L.nodes[i];
         if (a.dead || a.kind != L_AFFINE) continue;
@@ -958,7 +1122,10 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             b.dead = true;
         }
     }
-    // ---- fusion 2: conv epilogues (Conv -> Affine -> Relu) -----------------------------------------
+}
+
+// ---- fusion 2: conv epilogues (Conv -> Affine -> Relu) -----------------------------------------
+void Planner::FuseConvEpilogues() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& cv = L.nodes[i];
         if (cv.dead || cv.kind != L_CONV) continue;
@@ -1006,10 +1173,13 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             b.dead = true;
         }
     }
-    // ---- fusion 2b: ReLU6 between a conv and a depthwise conv (MobileNetV2's expand 1x1 -> Clip(0, 6) -> depthwise 3x3) ---------------
-    // A Clip with lo == 0 on a conv's output whose only reader is a depthwise conv without a prologue: the producing conv's epilogue applies
-    // the ReLU, the upper bound rides into the depthwise conv's prologue (min(max(x, 0), hi) on every in-range tap).  No dense-conv kernel
-    // needs a clamp epilogue.
+}
+
+// ---- fusion 2b: ReLU6 between a conv and a depthwise conv (MobileNetV2's expand 1x1 -> Clip(0, 6) -> depthwise 3x3) ---------------
+// A Clip with lo == 0 on a conv's output whose only reader is a depthwise conv without a prologue: the producing conv's epilogue applies
+// the ReLU, the upper bound rides into the depthwise conv's prologue (min(max(x, 0), hi) on every in-range tap).  No dense-conv kernel
+// needs a clamp epilogue.
+void Planner::FuseRelu6IntoDepthwise() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& c = L.nodes[i];
         if (c.dead || c.kind != L_CLIP || c.lo != 0.f) continue;
@@ -1030,9 +1200,12 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         d.pre_t.assign(size_t(L.vals[c.out].c), 0.f);
         c.dead = true;
     }
-    // ---- fusion 2d: an activation between a conv and a depthwise conv (expand 1x1 -> BN -> act -> depthwise) goes into the depthwise conv's
-    //      prologue (the producer runs linear: no dense-conv kernel needs an activation epilogue); one in front of a global pool (head 1x1 ->
-    //      act -> GlobalAveragePool) into the pool's prologue.  Any other activation becomes an eltwise step. -------------------------------
+}
+
+// ---- fusion 2d: an activation between a conv and a depthwise conv (expand 1x1 -> BN -> act -> depthwise) goes into the depthwise conv's
+//      prologue (the producer runs linear: no dense-conv kernel needs an activation epilogue); one in front of a global pool (head 1x1 ->
+//      act -> GlobalAveragePool) into the pool's prologue.  Any other activation becomes an eltwise step. -------------------------------
+void Planner::FuseActivationPrologues() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& a = L.nodes[i];
         if (a.dead || a.kind != L_ACT || !single_consumer(a.out)) continue;
@@ -1057,42 +1230,46 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             a.dead = true;
         }
     }
-    // ---- fusion 2c: Conv1x1 -> AveragePool  ==>  AveragePool -> Conv1x1 ---------------------------------
-    // Both are linear and a 1x1/stride-1 conv acts per pixel, so they commute (the conv's bias too: the mean of a constant is the
-    // constant).  DenseNet's transitions (BN -> ReLU -> Conv1x1 -> AvgPool2x2) then run their conv on a quarter of the pixels:
-    // 4x fewer FLOPs for those layers (8 % of the network), and the BN+ReLU prologue rides on the pool.  Only when the pool window
-    // tiles the image exactly (no padding, no partial windows), so every output averages the same number of inputs.
-    if (!env.get("IE_NO_POOL_SWAP")) {
-        for (size_t i = 0; i < L.nodes.size(); ++i) {
-            if (L.nodes[i].dead || L.nodes[i].kind != L_CONV) continue;
-            const LNode& cv0 = L.nodes[i];
-            if (cv0.kh != 1 || cv0.kw != 1 || cv0.sh != 1 || cv0.sw != 1 || cv0.pt || cv0.pl || cv0.pb || cv0.pr || cv0.relu || cv0.res >= 0) continue;
-            if (!single_consumer(cv0.out)) continue;
-            const int pj = L.consumers(cv0.out)[0];
-            const LNode& pl0 = L.nodes[pj];
-            const Val& X = L.vals[cv0.in[0]];
-            if (pl0.kind != L_AVGPOOL || pl0.pt || pl0.pl || pl0.pb || pl0.pr || pl0.kh != pl0.sh || pl0.kw != pl0.sw || X.h % pl0.kh || X.w % pl0.kw ||
-                X.is_input)
-                continue;
-            // new value: the pooled conv input [N, Cin, H/k, W/k]
-            const int x = cv0.in[0], conv_out = cv0.out, pool_out = pl0.out;
-            const int pooled = L.new_val(L.vals[x].name + "/pooled@" + pl0.name, {X.n, X.c, X.h / pl0.kh, X.w / pl0.kw});
-            LNode conv = L.nodes[i], pool = L.nodes[size_t(pj)];
-            pool.in = {x};
-            pool.out = pooled;
-            pool.name = pl0.name + "(before " + cv0.name + ")";
-            conv.in[0] = pooled;
-            conv.out = pool_out;                        // same dims as before: [N, Cout, H/k, W/k]
-            (void)conv_out;                             // the full-resolution conv output no longer exists
-            // the pool takes the conv's slot in the schedule, the conv the pool's (everything in between is independent of both)
-            L.nodes[i] = pool;
-            L.nodes[size_t(pj)] = conv;
-            L.vals[pooled].producer = int(i);
-            L.vals[pool_out].producer = pj;
-            L.vals[conv_out].producer = -1;
-        }
+}
+
+// ---- fusion 2c: Conv1x1 -> AveragePool  ==>  AveragePool -> Conv1x1 ---------------------------------
+// Both are linear and a 1x1/stride-1 conv acts per pixel, so they commute (the conv's bias too: the mean of a constant is the
+// constant).  DenseNet's transitions (BN -> ReLU -> Conv1x1 -> AvgPool2x2) then run their conv on a quarter of the pixels:
+// 4x fewer FLOPs for those layers (8 % of the network), and the BN+ReLU prologue rides on the pool.  Only when the pool window
+// tiles the image exactly (no padding, no partial windows), so every output averages the same number of inputs.
+void Planner::SwapConvAndAvgPool() {
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        if (L.nodes[i].dead || L.nodes[i].kind != L_CONV) continue;
+        const LNode& cv0 = L.nodes[i];
+        if (cv0.kh != 1 || cv0.kw != 1 || cv0.sh != 1 || cv0.sw != 1 || cv0.pt || cv0.pl || cv0.pb || cv0.pr || cv0.relu || cv0.res >= 0) continue;
+        if (!single_consumer(cv0.out)) continue;
+        const int pj = L.consumers(cv0.out)[0];
+        const LNode& pl0 = L.nodes[pj];
+        const Val& X = L.vals[cv0.in[0]];
+        if (pl0.kind != L_AVGPOOL || pl0.pt || pl0.pl || pl0.pb || pl0.pr || pl0.kh != pl0.sh || pl0.kw != pl0.sw || X.h % pl0.kh || X.w % pl0.kw ||
+            X.is_input)
+            continue;
+        // new value: the pooled conv input [N, Cin, H/k, W/k]
+        const int x = cv0.in[0], conv_out = cv0.out, pool_out = pl0.out;
+        const int pooled = L.new_val(L.vals[x].name + "/pooled@" + pl0.name, {X.n, X.c, X.h / pl0.kh, X.w / pl0.kw});
+        LNode conv = L.nodes[i], pool = L.nodes[size_t(pj)];
+        pool.in = {x};
+        pool.out = pooled;
+        pool.name = pl0.name + "(before " + cv0.name + ")";
+        conv.in[0] = pooled;
+        conv.out = pool_out;                        // same dims as before: [N, Cout, H/k, W/k]
+        (void)conv_out;                             // the full-resolution conv output no longer exists
+        // the pool takes the conv's slot in the schedule, the conv the pool's (everything in between is independent of both)
+        L.nodes[i] = pool;
+        L.nodes[size_t(pj)] = conv;
+        L.vals[pooled].producer = int(i);
+        L.vals[pool_out].producer = pj;
+        L.vals[conv_out].producer = -1;
     }
-    // ---- fusion 3: prologues (Affine -> Relu -> {Conv, GlobalAveragePool, swapped AveragePool}) ---------
+}
+
+// ---- fusion 3: prologues (Affine -> Relu -> {Conv, GlobalAveragePool, swapped AveragePool}) ---------
+void Planner::FusePrologues() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& cv = L.nodes[i];
         if (cv.dead || (cv.kind != L_CONV && cv.kind != L_GAP && cv.kind != L_AVGPOOL)) continue;
@@ -1127,7 +1304,10 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         }
         cv.in[0] = x;
     }
-    // ---- fusion 4: Add -> Relu, Affine -> Relu -----------------------------------------------------
+}
+
+// ---- fusion 4: Add -> Relu, Affine -> Relu -----------------------------------------------------
+void Planner::FuseTrailingRelu() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& a = L.nodes[i];
         if (a.dead || (a.kind != L_ADD && a.kind != L_AFFINE)) continue;
@@ -1142,34 +1322,35 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             }
         }
     }
+}
 
-    // ---- graph inputs in NCHW: only convs can read them strided; otherwise stage an NHWC copy ------
-    {
-        std::vector<LNode> pre;
-        for (size_t v = 0; v < L.vals.size(); ++v) {
-            if (!L.vals[v].is_input || !L.vals[v].input_nchw) continue;
-            bool all_conv = true;
-            for (int ci : L.consumers(int(v)))
-                if (L.nodes[ci].kind != L_CONV || L.nodes[ci].in[0] != int(v) || L.nodes[ci].res == int(v)) all_conv = false;
-            if (all_conv && !L.vals[v].is_output) continue;
-            LNode cp;
-            cp.kind = L_COPY;
-            cp.name = "nchw_to_nhwc(" + L.vals[v].name + ")";
-            cp.in = {int(v)};
-            cp.out = L.new_val(L.vals[v].name + "/nhwc", L.vals[v].dims);
-            for (auto& nd : L.nodes) if (!nd.dead) for (int& x : nd.in) if (x == int(v)) x = cp.out;
-            pre.push_back(cp);
-        }
-        if (!pre.empty()) {
-            size_t shift = pre.size();
-            L.nodes.insert(L.nodes.begin(), pre.begin(), pre.end());
-            for (auto& val : L.vals) if (val.producer >= 0) val.producer += int(shift);
-            for (size_t k = 0; k < shift; ++k) L.vals[L.nodes[k].out].producer = int(k);
-        }
+// ---- graph inputs in NCHW: only convs can read them strided; otherwise stage an NHWC copy ------
+void Planner::StageNchwInputs() {
+    std::vector<LNode> pre;
+    for (size_t v = 0; v < L.vals.size(); ++v) {
+        if (!L.vals[v].is_input || !L.vals[v].input_nchw) continue;
+        bool all_conv = true;
+        for (int ci : L.consumers(int(v)))
+            if (L.nodes[ci].kind != L_CONV || L.nodes[ci].in[0] != int(v) || L.nodes[ci].res == int(v)) all_conv = false;
+        if (all_conv && !L.vals[v].is_output) continue;
+        LNode cp;
+        cp.kind = L_COPY;
+        cp.name = "nchw_to_nhwc(" + L.vals[v].name + ")";
+        cp.in = {int(v)};
+        cp.out = L.new_val(L.vals[v].name + "/nhwc", L.vals[v].dims);
+        for (auto& nd : L.nodes) if (!nd.dead) for (int& x : nd.in) if (x == int(v)) x = cp.out;
+        pre.push_back(cp);
     }
+    if (!pre.empty()) {
+        size_t shift = pre.size();
+        L.nodes.insert(L.nodes.begin(), pre.begin(), pre.end());
+        for (auto& val : L.vals) if (val.producer >= 0) val.producer += int(shift);
+        for (size_t k = 0; k < shift; ++k) L.vals[L.nodes[k].out].producer = int(k);
+    }
+}
 
-    // ---- graph outputs must end up dense (NCHW order) in their own buffer --------------------------
-    std::vector<int> out_vals;
+// ---- graph outputs must end up dense (NCHW order) in their own buffer --------------------------
+void Planner::DensifyOutputs() {
     for (const auto& vo : m.outputs) {
         int v = L.get_val(vo.name);
         // Always materialise through a copy when the tensor is spatial (NHWC->NCHW) or is a graph input;
@@ -1198,8 +1379,10 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             out_vals.push_back(cp.out);
         } else out_vals.push_back(v);
     }
+}
 
-    // ---- concat / alias placement ---------------------------------------------------------------
+// ---- concat / alias placement ---------------------------------------------------------------
+void Planner::PlaceConcatsAndAliases() {
     for (int i = int(L.nodes.size()) - 1; i >= 0; --i) {
         LNode& n = L.nodes[i];
         if (n.dead) continue;
@@ -1222,7 +1405,6 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         }
     }
     // roots, absolute offsets
-    std::vector<int64_t> pitch(L.vals.size(), 0);
     for (size_t v = 0; v < L.vals.size(); ++v) {
         int r = int(v);
         int64_t off = 0;
@@ -1230,13 +1412,14 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         L.vals[v].root = r;
         L.vals[v].abs_off = off;
     }
+}
 
-    // ---- liveness over live nodes, buffer recycling -------------------------------------------------
-    std::vector<int> order;
+// ---- liveness over live nodes ----
+void Planner::ComputeLiveness() {
     for (size_t i = 0; i < L.nodes.size(); ++i) if (!L.nodes[i].dead) order.push_back(int(i));
-    const int INF = 1 << 30;
-    std::vector<int> first_def(L.vals.size(), INF), last_use(L.vals.size(), -1);
-    std::vector<char> used(L.vals.size(), 0);
+    first_def.assign(L.vals.size(), kLiveForever);
+    last_use.assign(L.vals.size(), -1);
+    used.assign(L.vals.size(), 0);
     for (size_t v = 0; v < L.vals.size(); ++v)
         if (L.vals[v].is_input) { first_def[L.vals[v].root] = -1; used[L.vals[v].root] = 1; }
     for (size_t pos = 0; pos < order.size(); ++pos) {
@@ -1247,133 +1430,492 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         last_use[r] = std::max(last_use[r], int(pos));
         for (int x : n.in) { int rx = L.vals[x].root; last_use[rx] = std::max(last_use[rx], int(pos)); used[rx] = 1; }
     }
-    // Dense fusion (see the pass after step emission): when a 3x3 conv and the 1x1 conv behind it will run as ONE launch, the 3x3's
-    // input (the bottleneck tensor, read as halo by neighbouring tiles) must outlive the launch that also writes the next
-    // bottleneck: keep it live one position longer so the two never share a buffer.
-    if (precision == Precision::F32 && !env.get("IE_NO_DENSE_FUSE"))
-        for (size_t pos = 0; pos + 1 < order.size(); ++pos) {
-            const LNode& a3 = L.nodes[order[pos]];
-            size_t nxt = pos + 1;                      // Concat / alias nodes emit nothing: the launch behind the 3x3 is the next real node
-            while (nxt < order.size() && (L.nodes[order[nxt]].kind == L_CONCAT || L.nodes[order[nxt]].kind == L_ALIAS)) ++nxt;
-            if (nxt >= order.size()) break;
-            const LNode& b1 = L.nodes[order[nxt]];
-            if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre || a3.group != 1 || b1.group != 1 ||
-                a3.dil_h != 1 || a3.dil_w != 1)
-                continue;
-            if (L.vals[a3.out].c != 32 || L.vals[b1.out].c != 128 || L.vals[b1.in[0]].root != L.vals[a3.out].root) continue;
-            if (L.vals[a3.out].n * L.vals[a3.out].h * L.vals[a3.out].w > FuseMaxPixels(env)) continue;
-            const int rb = L.vals[a3.in[0]].root;
-            last_use[rb] = std::max(last_use[rb], int(nxt));
-        }
-    for (int v : out_vals) last_use[L.vals[v].root] = INF;
-    for (size_t v = 0; v < L.vals.size(); ++v) if (L.vals[v].is_input) last_use[L.vals[v].root] = INF;  // staging buffers stay dedicated
+}
 
-    auto root_floats = [&](int r) {
-        const Val& R = L.vals[r];
-        return R.n * R.c * R.h * R.w;
-    };
-    std::multimap<int64_t, int> free_pool;   // size -> buffer id
-    auto alloc_buf = [&](int r) {
-        int64_t need = root_floats(r);
-        // fp8 mode types buffers by tensor shape ([N, C] vectors are halfs, spatial tensors e4m3): vectors get their own buffers so
-        // a recycled buffer never changes element type
-        bool dedicated = last_use[r] == INF || (precision == Precision::F8 && L.vals[r].h * L.vals[r].w == 1);
-        L.vals[r].dedicated = dedicated;
-        if (!dedicated) {
-            auto it = free_pool.lower_bound(need);
-            // accept a recycled buffer up to 2x the needed size; otherwise grow a new one
-            if (it != free_pool.end() && it->first <= 2 * need) {
-                int b = it->second;
-                free_pool.erase(it);
-                L.vals[r].buf = b;
-                return;
-            }
+// Dense fusion (FuseDenseLayers): when a 3x3 conv and the 1x1 conv behind it will run as ONE launch, the 3x3's
+// input (the bottleneck tensor, read as halo by neighbouring tiles) must outlive the launch that also writes the next
+// bottleneck: keep it live one position longer so the two never share a buffer.
+void Planner::KeepDenseFusionInputsLive() {
+    for (size_t pos = 0; pos + 1 < order.size(); ++pos) {
+        const LNode& a3 = L.nodes[order[pos]];
+        size_t nxt = pos + 1;                      // Concat / alias nodes emit nothing: the launch behind the 3x3 is the next real node
+        while (nxt < order.size() && (L.nodes[order[nxt]].kind == L_CONCAT || L.nodes[order[nxt]].kind == L_ALIAS)) ++nxt;
+        if (nxt >= order.size()) break;
+        const LNode& b1 = L.nodes[order[nxt]];
+        if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre || a3.group != 1 || b1.group != 1 ||
+            a3.dil_h != 1 || a3.dil_w != 1)
+            continue;
+        if (L.vals[a3.out].c != 32 || L.vals[b1.out].c != 128 || L.vals[b1.in[0]].root != L.vals[a3.out].root) continue;
+        if (L.vals[a3.out].n * L.vals[a3.out].h * L.vals[a3.out].w > FuseMaxPixels(env)) continue;
+        const int rb = L.vals[a3.in[0]].root;
+        last_use[rb] = std::max(last_use[rb], int(nxt));
+    }
+}
+
+void Planner::alloc_buf(int r, std::multimap<int64_t, int>& free_pool) {
+    int64_t need = root_floats(r);
+    // fp8 mode types buffers by tensor shape ([N, C] vectors are halfs, spatial tensors e4m3): vectors get their own buffers so
+    // a recycled buffer never changes element type
+    bool dedicated = last_use[r] == kLiveForever || (precision == Precision::F8 && L.vals[r].h * L.vals[r].w == 1);
+    L.vals[r].dedicated = dedicated;
+    if (!dedicated) {
+        auto it = free_pool.lower_bound(need);
+        // accept a recycled buffer up to 2x the needed size; otherwise grow a new one
+        if (it != free_pool.end() && it->first <= 2 * need) {
+            int b = it->second;
+            free_pool.erase(it);
+            L.vals[r].buf = b;
+            return;
         }
-        plan.buffer_floats.push_back(need);
-        L.vals[r].buf = int(plan.buffer_floats.size()) - 1;
-    };
+    }
+    plan.buffer_floats.push_back(need);
+    L.vals[r].buf = int(plan.buffer_floats.size()) - 1;
+}
+
+// ---- buffer recycling: graph inputs and outputs keep their buffers, every other root value takes a free buffer of a fitting size ----
+void Planner::AssignBuffers() {
+    for (int v : out_vals) last_use[L.vals[v].root] = kLiveForever;
+    for (size_t v = 0; v < L.vals.size(); ++v) if (L.vals[v].is_input) last_use[L.vals[v].root] = kLiveForever;  // staging buffers stay dedicated
+    std::multimap<int64_t, int> free_pool;   // size -> buffer id
     for (size_t v = 0; v < L.vals.size(); ++v)
-        if (used[v] && L.vals[v].root == int(v) && first_def[v] == -1) alloc_buf(int(v));
+        if (used[v] && L.vals[v].root == int(v) && first_def[v] == -1) alloc_buf(int(v), free_pool);
     for (size_t pos = 0; pos < order.size(); ++pos) {
         for (size_t v = 0; v < L.vals.size(); ++v)
-            if (used[v] && L.vals[v].root == int(v) && first_def[v] == int(pos)) alloc_buf(int(v));
+            if (used[v] && L.vals[v].root == int(v) && first_def[v] == int(pos)) alloc_buf(int(v), free_pool);
         for (size_t v = 0; v < L.vals.size(); ++v)
             if (used[v] && L.vals[v].root == int(v) && last_use[v] == int(pos) && L.vals[v].buf >= 0 && !L.vals[v].dedicated)
                 free_pool.insert({plan.buffer_floats[size_t(L.vals[v].buf)], L.vals[v].buf});
     }
+}
 
-    // fp16 mode: every buffer except the graph's own inputs/outputs (dedicated, never recycled) holds halfs
-    auto mark_buffer_types = [&] {
-        plan.buffer_f16.assign(plan.buffer_floats.size(), precision == Precision::F16 ? 1 : (precision == Precision::F8 ? 2 : 0));
-        if (precision == Precision::F8)
-            for (size_t v = 0; v < L.vals.size(); ++v)
-                if (used[v] && L.vals[v].root == int(v) && L.vals[v].buf >= 0 && L.vals[v].h * L.vals[v].w == 1) plan.buffer_f16[size_t(L.vals[v].buf)] = 1;
+// fp16 mode: every buffer except the graph's own inputs/outputs (dedicated, never recycled) holds halfs
+void Planner::MarkBufferTypes() {
+    plan.buffer_f16.assign(plan.buffer_floats.size(), precision == Precision::F16 ? 1 : (precision == Precision::F8 ? 2 : 0));
+    if (precision == Precision::F8)
         for (size_t v = 0; v < L.vals.size(); ++v)
-            if (L.vals[v].is_input && L.vals[L.vals[v].root].buf >= 0) plan.buffer_f16[size_t(L.vals[L.vals[v].root].buf)] = 0;
-        for (int v : out_vals)
-            if (L.vals[L.vals[v].root].buf >= 0) plan.buffer_f16[size_t(L.vals[L.vals[v].root].buf)] = 0;
-    };
-    mark_buffer_types();
+            if (used[v] && L.vals[v].root == int(v) && L.vals[v].buf >= 0 && L.vals[v].h * L.vals[v].w == 1) plan.buffer_f16[size_t(L.vals[v].buf)] = 1;
+    for (size_t v = 0; v < L.vals.size(); ++v)
+        if (L.vals[v].is_input && L.vals[L.vals[v].root].buf >= 0) plan.buffer_f16[size_t(L.vals[L.vals[v].root].buf)] = 0;
+    for (int v : out_vals)
+        if (L.vals[L.vals[v].root].buf >= 0) plan.buffer_f16[size_t(L.vals[L.vals[v].root].buf)] = 0;
+}
 
-    auto view_of = [&](int v) {
-        const Val& X = L.vals[v];
-        const Val& R = L.vals[X.root];
-        View w;
-        w.buf = R.buf;
-        w.f16 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 1;
-        w.f8 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 2;
-        w.n = X.n; w.c = X.c; w.h = X.h; w.w = X.w;
-        w.c_off = X.abs_off;
-        w.pitch = R.c;
-        w.nchw = (X.is_input || X.is_output) && X.input_nchw;
-        if (w.buf < 0) fail("internal planner error: value " + X.name + " has no buffer");
-        return w;
-    };
+View Planner::view_of(int v) const {
+    const Val& X = L.vals[v];
+    const Val& R = L.vals[X.root];
+    View w;
+    w.buf = R.buf;
+    w.f16 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 1;
+    w.f8 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 2;
+    w.n = X.n; w.c = X.c; w.h = X.h; w.w = X.w;
+    w.c_off = X.abs_off;
+    w.pitch = R.c;
+    w.nchw = (X.is_input || X.is_output) && X.input_nchw;
+    if (w.buf < 0) fail("internal planner error: value " + X.name + " has no buffer");
+    return w;
+}
 
-    // ---- emit steps --------------------------------------------------------------------------------
-    auto push_vec = [&](const std::vector<float>& v) {
-        while (plan.weights.size() % 8) plan.weights.push_back(0.f);   // 32 B in the fp32 blob, 16 B in its half mirror
-        int64_t off = int64_t(plan.weights.size());
-        plan.weights.insert(plan.weights.end(), v.begin(), v.end());
-        return off;
-    };
-    auto vbytes = [](const View& v) { return double(v.numel()) * double(v.esize()); };
-    // who wrote what: (buffer, channel offset, channels) -> step index, for Step::in_src / in2_src
-    std::map<std::vector<int64_t>, int> writer;
-    auto src_of = [&](const View& v) {
-        auto it = writer.find({int64_t(v.buf), v.c_off, v.c});
-        return it == writer.end() ? -1 : it->second;
-    };
+bool Planner::output_in_buffer(int buf) const {
+    for (int v : out_vals) if (view_of(v).buf == buf) return true;
+    return false;
+}
+
+ConvFacts::ConvFacts(const LNode& nn, const Step& ss) : n(nn), s(ss) {
+    // a dilated conv may only take the kernels that honour the dilation (plan.h DilationOk): the implicit GEMMs' base tiles and the
+    // naive kernel.  Every specialised kernel's eligibility is false for it, and the forcing switches cannot move it elsewhere
+    dil = s.dh > 1 || s.dw > 1;
+    M = s.out.n * s.out.h * s.out.w; N = s.out.c; K = int64_t(n.kh) * n.kw * s.in.c;
+    in16 = s.in.f16;
+    in8 = s.in.f8;
+    vec_ok = !in16 && !in8 && !s.in.nchw && s.in.c % 4 == 0 && s.in.pitch % 4 == 0 && s.in.c_off % 4 == 0 && n.kh * n.kw <= 32 &&
+             s.in.n * s.in.h * s.in.w * s.in.pitch * 4 < (int64_t(1) << 31) && int64_t(n.w.size()) * 4 < (int64_t(1) << 31);
+    // fp16 MFMA path: 16-byte chunks of 8 halfs, so channel counts / slice offsets must be multiples of 8
+    vec16_ok = in16 && !s.in.nchw && s.in.c % 8 == 0 && s.in.pitch % 8 == 0 && s.in.c_off % 8 == 0 && n.kh * n.kw <= 32 &&
+               s.in.n * s.in.h * s.in.w * s.in.pitch * 2 < (int64_t(1) << 31) && int64_t(n.w.size()) * 2 < (int64_t(1) << 31) &&
+               s.out.n * s.out.h * s.out.w * s.out.pitch < (int64_t(1) << 31);
+    is1x1 = n.kh == 1 && n.kw == 1 && n.sh == 1 && n.sw == 1 && n.pt == 0 && n.pl == 0 && n.pb == 0 && n.pr == 0;
+    is3x3 = !dil && n.kh == 3 && n.kw == 3 && n.sh == 1 && n.sw == 1 && n.pt == 1 && n.pl == 1 && n.pb == 1 && n.pr == 1;
+}
+
+bool ConvFacts::ws16_ok(int t) const {
+    if (t < 0 || t >= 18) return false;          // (12-17: the one-workgroup-per-CU grids of shapes 0-5)
+    const int tn = ws_tn[t % 6];
+    return vec16_ok && is1x1 && s.in.c % 32 == 0 &&
+           (32 * tn * (s.in.c + 8) + 2 * s.in.c) * 2 + 128 * tn <= 160 * 1024 && !(tn > 1 && N <= 32 * (tn / 2)) &&
+           (s.out.f16 ? (N % 8 == 0 && s.out.pitch % 8 == 0 && s.out.c_off % 8 == 0) : (N % 4 == 0 && s.out.pitch % 4 == 0 && s.out.c_off % 4 == 0));
+}
+
+bool ConvFacts::ws32_ok(int t) const {
+    if (t >= 14 && t < 20) t -= 14;              // 14-19: shapes 0-5 on a grid of one workgroup per CU: same operand conditions
+    return t >= 0 && t < 14 && vec_ok && !s.out.f16 && is1x1 && s.in.c % 16 == 0 &&
+           (t < 12 ? (32 * ws_tn[t] * (s.in.c + 4) + 2 * s.in.c + 32 * ws_tn[t]) * 4 <= 160 * 1024
+                   : (s.in.c / 16 >= (t == 12 ? 8 : 4) &&
+                      (32 * (s.in.c + 4) + 2 * s.in.c + 32 + (t == 12 ? 4 : 2) * 32 * 36) * 4 <= 160 * 1024)) &&
+           !(ws_tn[t] > 1 && N <= 32 * (ws_tn[t] / 2)) && N % 4 == 0 && s.out.pitch % 4 == 0 && s.out.c_off % 4 == 0;
+}
+
+bool ConvFacts::ws3_ok(int t3) const {
+    static const int ws3_cfg[5][3] = {{4, 2, 12}, {4, 1, 8}, {8, 1, 6}, {2, 1, 12}, {12, 1, 6}};   // waves, row blocks per wave, prefetch depth (kWs3Tiles, kernels_ws.hip)
+    if (t3 < 0 || t3 >= 5) return false;
+    const int64_t pr3 = 32 * ws3_cfg[t3][1] * ws3_cfg[t3][0] + 2 * (s.in.w + 1) + 2;
+    return vec16_ok && s.out.f16 && is3x3 && !n.has_pre && N % 8 == 0 && s.out.pitch % 8 == 0 && s.out.c_off % 8 == 0 &&
+           pr3 <= ws3_cfg[t3][2] * (64 * ws3_cfg[t3][0] / 8) && (9 * ((s.in.c + 63) / 64) * 32 + pr3) * 144 + 128 <= 160 * 1024;
+}
+
+bool ConvFacts::direct_ok(int t) const {
+    static const int dcfg[6][3] = {{1, 8, 8}, {1, 16, 4}, {1, 9, 8}, {1, 4, 8}, {1, 12, 6}, {2, 8, 4}};   // tn, waves, max chunks
+    static const int wcfg[4][3] = {{1, 8, 9}, {2, 8, 9}, {1, 4, 18}, {2, 4, 18}};                      // window variants: tn, waves, max chunks
+    if (t < 0 || t >= 15 || dil) return false;
+    if (t >= 10) {     // activations-stationary 1x1 (fp32): the workgroup's 32 / 16 pixel rows in LDS, weights streamed from the mirror
+        static const int acfg[5] = {128, 64, 256, 64, 64};                                        // output channels per workgroup
+        return vec_ok && !in16 && !s.out.f16 && !s.has_in2 && is1x1 && s.in.c % 16 == 0 && N % acfg[t - 10] == 0 && s.out.pitch % 4 == 0 &&
+               s.out.c_off % 4 == 0 && M <= (int64_t(1) << 22) && 32 * (s.in.c + 4) * 4 <= 160 * 1024;
+    }
+    if (t >= 6) {      // fp32, output grid == input grid, activations through an LDS window, fragment-major weights
+        const int* wc = wcfg[t - 6];
+        const int64_t total = s.in.c % 16 == 0 ? int64_t(n.kh) * n.kw * (s.in.c / 16) : 0;
+        const int64_t win = (16 + (n.kh - 1) * s.in.w + (n.kw - 1)) * (s.in.c + 4) * 4, part = int64_t(wc[1]) * 16 * (16 * wc[0] + 4) * 4;
+        return vec_ok && !in16 && !s.out.f16 && !s.has_in2 && s.in.c % 16 == 0 && N % (16 * wc[0]) == 0 && n.sh == 1 && n.sw == 1 &&
+               s.out.h == s.in.h && s.out.w == s.in.w && n.pt < n.kh && n.pl < n.kw && s.out.pitch % 2 == 0 && s.out.c_off % 2 == 0 &&
+               total >= wc[1] && total <= wc[1] * wc[2] && M <= 65536 && n.kh * n.kw <= 49 && std::max(win, part) <= 160 * 1024;
+    }
+    const int cw = in16 ? 32 : 16, al = in16 ? 8 : 4;
+    const int64_t total = s.in.c % cw == 0 ? int64_t(n.kh) * n.kw * (s.in.c / cw) : 0;
+    return (vec_ok || vec16_ok) && s.in.c % cw == 0 && s.in.pitch % al == 0 && s.in.c_off % al == 0 && N % 2 == 0 && s.out.pitch % 2 == 0 &&
+           s.out.c_off % 2 == 0 && total >= dcfg[t][1] && total <= dcfg[t][1] * dcfg[t][2] && !(dcfg[t][0] > 1 && N <= 32) && M <= 65536 &&
+           n.kh * n.kw <= 49;
+}
+
+int Planner::ForcedTile(int limit) const {
+    const char* ft = env.get("IE_FORCE_TILE");
+    const int t = ft ? std::atoi(ft) : -1;
+    return t >= 0 && t < limit ? t : -1;
+}
+
+int64_t Planner::push_vec(const std::vector<float>& v) {
+    while (plan.weights.size() % 8) plan.weights.push_back(0.f);   // 32 B in the fp32 blob, 16 B in its half mirror
+    int64_t off = int64_t(plan.weights.size());
+    plan.weights.insert(plan.weights.end(), v.begin(), v.end());
+    return off;
+}
+
+int Planner::src_of(const View& v) const {
+    auto it = writer.find({int64_t(v.buf), v.c_off, v.c});
+    return it == writer.end() ? -1 : it->second;
+}
+
+// members that could not be placed in the parent buffer are copied into their slice
+void Planner::EmitConcatCopies(const LNode& n) {
+    int64_t off = 0;
+    for (size_t k = 0; k < n.in.size(); ++k) {
+        const Val& src = L.vals[n.in[k]];
+        bool placed = src.root == L.vals[n.out].root && src.abs_off == L.vals[n.out].abs_off + off;
+        if (!placed) {
+            Step c;
+            c.kind = StepKind::Copy;
+            c.name = n.name + "/copy" + std::to_string(k);
+            c.in = view_of(n.in[k]);
+            c.out = view_of(n.out);
+            c.out.c = src.c;
+            c.out.c_off += off;
+            c.bytes = vbytes(c.in) + vbytes(c.out);
+            if (c.in.f8 || c.out.f8) fail("fp8 precision: concat copy " + c.name + " of an fp8 tensor is not supported");
+            c.idx = int(plan.steps.size());
+            c.in_src = src_of(c.in);
+            writer[{int64_t(c.out.buf), c.out.c_off, c.out.c}] = c.idx;
+            plan.steps.push_back(c);
+        }
+        off += src.c;
+    }
+}
+
+// depthwise and grouped convs: their own kernels whatever IE_FORCE_ALGO says; IE_FORCE_TILE indexes the depthwise / grouped variants
+// (kernels.h kNumConvDwTiles, kNumConvGroupedTiles)
+void Planner::EmitGroupConv(const LNode& n, Step& s) {
+    s.algo = n.dw ? ConvAlgo::Depthwise : ConvAlgo::Grouped;
+    if (!n.dw) s.group = int(n.group);
+    s.lo = n.lo;
+    s.hi = n.hi;
+    s.act = n.act;
+    s.pre_act = n.pre_act;
+    if (n.dw) s.flops = 2.0 * double(s.out.n) * double(s.out.c) * double(s.out.h) * double(s.out.w) * n.kh * n.kw;
+    else s.flops = 2.0 * double(s.out.n) * double(s.out.h) * double(s.out.w) * double(s.out.c) * n.kh * n.kw * double(s.in.c / n.group);
+    s.bytes = vbytes(s.in) + vbytes(s.out) + (!n.dw && s.in.f16 ? 2.0 : 4.0) * double(n.w.size()) + (n.res >= 0 ? vbytes(s.in2) : 0.0);
+    s.tile = n.dw ? DwDefaultTile(s) : GroupedDefaultTile(s);
+    const int t = ForcedTile(n.dw ? kNumConvDwTiles : kNumConvGroupedTiles);
+    if (t >= 0 && (t == 0 || (n.dw ? DwFastViews(s) : GroupedFastViews(s, t)))) s.tile = t;
+    s.base_tile = 0;
+}
+
+// ---- the base algorithm: naive for toy problems, the implicit GEMMs, the stem kernel, the fp8 GEMM; the heuristic tile ----
+void Planner::ChooseBaseAlgo(const ConvFacts& f, Step& s) const {
+    const LNode& n = f.n;
+    // one-thread-per-output only for toy problems (test_model's 3->5->2 MLP): at batch 1 DenseNet's block-4 convs have
+    // M*N = 1568 outputs but K = 1152 - the naive kernel took 141 us there, the MFMA kernels 13 us
+    if (f.M * f.N * f.K <= 32768 || (f.M * f.N < 2048 && f.K <= 4096 && !(f.vec_ok || f.vec16_ok))) s.algo = ConvAlgo::Naive;
+    else if (f.vec_ok || f.vec16_ok) s.algo = ConvAlgo::IgemmVec;
+    else if (f.K <= 2048 && !f.in16) s.algo = ConvAlgo::IgemmScalar;
+    else s.algo = ConvAlgo::Naive;
+    // the stem of an image classifier (7x7 / stride 2 / pad 3 over the 3-channel NCHW graph input) has its own kernel
+    const bool stem_ok = !f.dil && s.in.nchw && !f.in16 && s.in.c == 3 && n.kh == 7 && n.kw == 7 && n.sh == 2 && n.sw == 2 && n.pt == 3 &&
+                         n.pl == 3 && n.pb == 3 && n.pr == 3 && !n.has_pre && f.N <= 64 && f.N % 8 == 0 && s.out.pitch % 8 == 0 &&
+                         s.out.c_off % 8 == 0 && s.in.numel() * 4 < (int64_t(1) << 31) &&
+                         s.out.n * s.out.h * s.out.w * s.out.pitch * 4 < (int64_t(1) << 31);
+    if (stem_ok && f.M * f.N >= 2048 && !(s.out.f8 && (f.N % 16 || s.out.pitch % 16 || s.out.c_off % 16))) s.algo = ConvAlgo::Stem;
+    if (f.in8 || s.out.f8) {
+        // fp8 mode: e4m3 tensors are only understood by the fp8 kernels; anything they cannot run is a load error, never a
+        // silent reinterpretation of the bytes by another kernel
+        if (s.out.f8 && !f.in8) {
+            if (s.algo != ConvAlgo::Stem)
+                fail("fp8 precision: conv " + n.name + " reads a non-fp8 tensor and writes an fp8 one; only the 7x7/s2 stem over the fp32 graph input does that");
+        } else {
+            if (n.has_pre) fail("fp8 precision: conv " + n.name + " has an activation prologue (pre-activation graphs are not supported in fp8 mode)");
+            if (!s.out.f8) fail("fp8 precision: conv " + n.name + " reads an fp8 tensor and writes a non-fp8 one");
+            if (s.in.nchw || s.in.c % 16 || s.in.pitch % 16 || s.in.c_off % 16 || f.N % 16 || s.out.pitch % 16 || s.out.c_off % 16 || n.kh * n.kw > 32)
+                fail("fp8 precision: conv " + n.name + " needs channel counts and slice offsets that are multiples of 16");
+            if (n.res >= 0 && !s.in2.f8) fail("fp8 precision: the shortcut of conv " + n.name + " is not an fp8 tensor");
+            s.algo = ConvAlgo::IgemmF8;
+        }
+    }
+    s.tile = choose_tile(f.M, f.N);
+    s.splitk = 1;
+    s.base_tile = s.tile;
+}
+
+// fp8 steps: IE_FORCE_TILE names a tile of the tiled kernel or one of the weights-stationary kernels
+void Planner::ForceTileF8(const ConvFacts& f, Step& s) const {
+    const int t = ForcedTile(INT_MAX);
+    if (t >= 0 && t < kNumIgemmBaseTiles && !(kIgemmTiles[t].bn > 32 && f.N <= 32)) s.tile = t;
+    // kWs8Code + t: the weights-stationary 1x1 kernel's tiles, kWs38Code + t: the 3x3's (kernels_ws8.hip); a launcher that
+    // declines the operands hands the step back to the tiled kernel (executor)
+    if (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles && f.n.kh == 1 && f.n.kw == 1) s.tile = t;      // (strided 1x1 convs too: the kernel's STR form)
+    if (t >= kWs38Code && t < kWs38Code + kNumConvWs38Tiles && f.is3x3) s.tile = t;
+}
+
+namespace {
+// ---- default choice without the autotuner (IE_AUTOTUNE=0, or before Prepare() has timed anything): the kernels
+//      the exhaustive search picks for DenseNet / ResNet shapes ----
+void PickDefaultKernel(const ConvFacts& f, Step& s) {
+    int pick = -1;
+    if (f.M <= 2048) {                                                       // tiny grids: split K over the waves
+        if (f.is3x3 && f.direct_ok(6)) pick = 6;                             // 16-pixel window tiles: 4x the workgroups
+        else if (f.is1x1 && f.direct_ok(13)) pick = 13;                      // 16-pixel activations-stationary tiles
+        for (int t : {1, 0, 4, 3}) if (pick < 0 && f.direct_ok(t)) pick = t;
+        if (pick >= 0) { s.algo = ConvAlgo::Direct; s.tile = pick; }
+    } else if (f.in16) {
+        if (f.is1x1) { for (int t : {0, 2, 4}) if (pick < 0 && f.ws16_ok(t)) pick = t; if (pick >= 0) { s.algo = ConvAlgo::Ws1x1; s.tile = pick; } }
+        else if (f.is3x3) { for (int t : {2, 1, 0}) if (pick < 0 && f.ws3_ok(t)) pick = t; if (pick >= 0) { s.algo = ConvAlgo::Ws3x3; s.tile = pick; } }
+    } else {
+        if (f.is1x1 && f.direct_ok(10)) { s.algo = ConvAlgo::Direct; s.tile = 10; }      // activations-stationary 1x1: 128-channel multiples whose 32 pixel rows fit in LDS
+        else if (f.is1x1 && f.M >= 20000) { for (int t : {0, 2, 4}) if (pick < 0 && f.ws32_ok(t)) pick = t; if (pick >= 0) { s.algo = ConvAlgo::Ws1x1; s.tile = pick; } }
+        else if (f.wino_ok() && f.M >= 20000) { s.algo = ConvAlgo::Wino3x3; s.tile = 5; }     // Winograd F(2x2,3x3), 2x14 tiles, eight waves (falls back to the tiled kernel without the U mirror)
+        else if (f.raster_ok() && f.M >= 20000 && f.N <= 64) { s.algo = ConvAlgo::Raster3x3; s.tile = f.N <= 32 ? 0 : 4; }
+        else if (f.is3x3 && f.M <= 8192) { if (f.direct_ok(4)) { s.algo = ConvAlgo::Direct; s.tile = 4; } }
+    }
+}
+}  // namespace
+
+// Test / tuning override (read at plan time): IE_FORCE_ALGO=naive|scalar|igemm|raster|ws|direct|x6|wino; ws, direct, x6, wino and raster read
+// IE_FORCE_TILE as an index into their own tile tables
+void Planner::ApplyForcedAlgo(const ConvFacts& f, Step& s) const {
+    const LNode& n = f.n;
+    const char* fa = env.get("IE_FORCE_ALGO");
+    if (fa && f.dil && std::string(fa) != "naive" && std::string(fa) != "scalar" && std::string(fa) != "igemm") fa = nullptr;
+    if (fa) {
+        const std::string word = fa;
+        if (word == "naive") s.algo = ConvAlgo::Naive;
+        else if (word == "scalar" && f.K <= 2048 && !f.in16) s.algo = ConvAlgo::IgemmScalar;
+        else if (word == "igemm" && s.algo == ConvAlgo::Stem) s.algo = f.K <= 2048 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive;
+        else if (word == "igemm" && s.algo == ConvAlgo::Naive) s.algo = f.tiled_algo();
+        else if (word == "ws") {
+            const int t = std::max(0, ForcedTile(f.in16 ? kNumConvWs16Tiles : kNumConvWs32Tiles));
+            if (f.ws16_ok(t) || f.ws32_ok(t)) { s.algo = ConvAlgo::Ws1x1; s.tile = t; }
+            else if (f.ws3_ok(t % kNumConvWs3Tiles)) { s.algo = ConvAlgo::Ws3x3; s.tile = t % kNumConvWs3Tiles; }
+            else if (s.algo == ConvAlgo::Naive && f.vec16_ok) s.algo = ConvAlgo::IgemmVec;
+        }
+        else if (word == "direct") {
+            const int t = std::max(0, ForcedTile(kNumConvDirectTiles));
+            if (f.direct_ok(t)) { s.algo = ConvAlgo::Direct; s.tile = t; }
+            else if (s.algo == ConvAlgo::Naive && (f.vec_ok || f.vec16_ok)) s.algo = ConvAlgo::IgemmVec;
+        }
+        else if (word == "x6") {
+            const bool x6_ok = f.vec_ok && !s.out.f16 && f.is1x1 && n.sh == 1 && n.sw == 1 && s.in.c % 32 == 0 && f.N % 128 == 0 && n.res < 0;
+            if (x6_ok) {
+                s.algo = ConvAlgo::X6;
+                s.tile = std::max(0, ForcedTile(kNumConvX6Tiles));
+            }
+        }
+        else if (word == "wino") {
+            if (f.wino_ok()) {
+                s.algo = ConvAlgo::Wino3x3;
+                s.tile = std::max(0, ForcedTile(kNumConvWinoTiles));
+            } else if (s.algo == ConvAlgo::Naive) s.algo = f.tiled_algo();
+        }
+        else if (word == "raster") {
+            if (f.raster_ok()) {
+                s.algo = ConvAlgo::Raster3x3;
+                s.tile = std::max(0, ForcedTile(kNumConvRasterTiles));
+            } else if (s.algo == ConvAlgo::Naive) s.algo = f.tiled_algo();
+        }
+    }
+}
+
+// IE_FORCE_TILE on the tiled implicit GEMMs, then split-K: the heuristic, or IE_FORCE_SPLITK
+void Planner::ApplyForcedTileAndSplitK(const ConvFacts& f, Step& s) {
+    const LNode& n = f.n;
+    const int heuristic_tile = s.base_tile;
+    // the specialised kernels read IE_FORCE_TILE through their own tables (ApplyForcedAlgo) or not at all
+    const bool own_tiles = s.algo == ConvAlgo::Raster3x3 || s.algo == ConvAlgo::Ws1x1 || s.algo == ConvAlgo::Ws3x3 || s.algo == ConvAlgo::Stem || s.algo == ConvAlgo::Direct || s.algo == ConvAlgo::Wino3x3 || s.algo == ConvAlgo::X6;
+    const int t = own_tiles ? -1 : ForcedTile(kNumIgemmTiles);
+    if (t >= 0 && (t < kNumIgemmBaseTiles || (s.algo == ConvAlgo::IgemmVec && !f.dil)) && !(f.in16 && kIgemmTiles[t].deep)) s.tile = t;
+    if (s.algo != ConvAlgo::IgemmVec && s.algo != ConvAlgo::Raster3x3 && s.algo != ConvAlgo::Ws1x1 && s.algo != ConvAlgo::Ws3x3 && s.algo != ConvAlgo::Direct && s.algo != ConvAlgo::Wino3x3 && s.algo != ConvAlgo::X6 && s.tile >= kNumIgemmBaseTiles)
+        s.tile = heuristic_tile;       // K-group tiles exist for the vector path only
+    if (s.algo == ConvAlgo::Raster3x3) {
+        if (const char* fs = env.get("IE_FORCE_SPLITK")) {
+            int v = std::atoi(fs);
+            if (v >= 1 && v <= 64) s.splitk = v;
+        }
+        if (s.splitk > 1) plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, int64_t(s.splitk) * f.M * f.N);
+    } else if (s.algo == ConvAlgo::Ws1x1 || s.algo == ConvAlgo::Ws3x3 || s.algo == ConvAlgo::Stem || s.algo == ConvAlgo::Direct || s.algo == ConvAlgo::Wino3x3 || s.algo == ConvAlgo::X6) {
+        s.splitk = 1;
+    } else if (s.algo != ConvAlgo::Naive) {
+        // split-K when the output grid cannot fill the chip: aim for >= ~768 workgroups, keep >= 2 K-tiles
+        // per split.  (Deterministic two-pass reduction, see kernels.hip.)
+        const IgemmTile& T = kIgemmTiles[s.tile];
+        const int64_t bk = f.in16 ? 2 * kIgemmBK : kIgemmBK;       // K-tile depth in elements (128 B per LDS row either way)
+        const int64_t wgs = ((f.M + T.bm - 1) / T.bm) * ((f.N + T.bn - 1) / T.bn);
+        const int64_t cblocks = (s.in.c + bk - 1) / bk;
+        const int64_t KT = s.algo == ConvAlgo::IgemmVec ? int64_t(n.kh) * n.kw * cblocks : (f.K + kIgemmBK - 1) / kIgemmBK;
+        if (wgs < 384 && KT >= 4) {
+            int64_t want = (768 + wgs - 1) / wgs;
+            s.splitk = int(std::max<int64_t>(1, std::min<int64_t>({want, KT / 2, 32})));
+        }
+        if (const char* fs = env.get("IE_FORCE_SPLITK")) {
+            int v = std::atoi(fs);
+            if (v >= 1 && v <= 64) s.splitk = v;
+        }
+        if (s.splitk > 1) plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, int64_t(s.splitk) * f.M * f.N);
+    }
+}
+
+void Planner::EmitConv(const LNode& n, Step& s) {
+    s.kind = StepKind::Conv;
+    s.kh = n.kh; s.kw = n.kw; s.sh = n.sh; s.sw = n.sw; s.pt = n.pt; s.pl = n.pl; s.pb = n.pb; s.pr = n.pr;
+    s.dh = n.dil_h; s.dw = n.dil_w;
+    s.w_off = push_vec(n.w);
+    if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
+    if (n.res >= 0) { s.in2 = view_of(n.res); s.has_in2 = true; }
+    if (n.dw || n.group != 1) { EmitGroupConv(n, s); return; }
+    const ConvFacts f(n, s);
+    s.flops = 2.0 * double(f.M) * double(f.N) * double(f.K);
+    s.bytes = vbytes(s.in) + vbytes(s.out) + (f.in8 ? 1.0 : (f.in16 ? 2.0 : 4.0)) * double(n.w.size()) + (n.res >= 0 ? vbytes(s.in2) : 0.0);
+    ChooseBaseAlgo(f, s);
+    if (s.algo == ConvAlgo::IgemmF8) { ForceTileF8(f, s); return; }
+    if (!env.get("IE_FORCE_ALGO") && !env.get("IE_FORCE_TILE") && s.algo == ConvAlgo::IgemmVec) PickDefaultKernel(f, s);
+    ApplyForcedAlgo(f, s);
+    ApplyForcedTileAndSplitK(f, s);
+}
+
+void Planner::EmitPool(const LNode& n, Step& s) const {
+    if (n.kind == L_GAP) {
+        if (s.in.f8 && (n.has_pre || s.out.f8)) fail("fp8 precision: global pool " + n.name + " with a prologue is not supported");
+        s.kind = StepKind::GlobalAvgPool;
+        s.pre_act = n.pre_act;
+        s.bytes = vbytes(s.in) + vbytes(s.out);
+        s.flops = double(s.in.numel()) * (1.0 + ActFlops(n.pre_act.kind));
+        return;
+    }
+    if ((s.in.f8 || s.out.f8) && (!s.in.f8 || !s.out.f8 || n.has_pre || s.in.c % 16 || s.in.pitch % 16 || s.in.c_off % 16 || s.out.pitch % 16 || s.out.c_off % 16))
+        fail("fp8 precision: pool " + n.name + " needs fp8 operands without a prologue and channel counts that are multiples of 16");
+    s.kind = StepKind::Pool;
+    s.pool_max = n.kind == L_MAXPOOL;
+    s.count_include_pad = n.count_include_pad;
+    s.kh = n.kh; s.kw = n.kw; s.sh = n.sh; s.sw = n.sw; s.pt = n.pt; s.pl = n.pl; s.pb = n.pb; s.pr = n.pr;
+    s.bytes = vbytes(s.in) + vbytes(s.out);
+    s.flops = double(s.out.numel()) * n.kh * n.kw;
+}
+
+void Planner::EmitSqueezeExcite(const LNode& n, Step& s) {
+    s.kind = StepKind::SqueezeExcite;
+    s.w_off = push_vec(n.w);
+    if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
+    s.w2_off = push_vec(n.w2);
+    if (!n.bias2.empty()) s.bias2_off = push_vec(n.bias2);
+    s.se_mid = n.se_mid;
+    s.se_act1 = n.se_act1;
+    s.act = n.act;
+    s.se_chunks = SeSqueezeChunks(s.in.n, s.in.h * s.in.w);
+    plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, SeWorkspaceFloats(s.in.n, s.in.c, n.se_mid, s.se_chunks));
+    // squeeze (one add per element), the two FCs (2 x MACs, activations), the gate multiply; the input is read twice
+    const double nc = double(s.in.n) * double(s.in.c), nm = double(s.in.n) * n.se_mid;
+    s.flops = double(s.in.numel()) + 4.0 * nc * n.se_mid + nm * ActFlops(n.se_act1.kind) + nc * ActFlops(n.act.kind) + double(s.out.numel());
+    s.bytes = 2.0 * vbytes(s.in) + vbytes(s.out) + 4.0 * double(n.w.size() + n.w2.size() + n.bias.size() + n.bias2.size());
+}
+
+// the stand-alone pointwise steps: activation, gate multiply, scale/shift, Clip, Relu, Add
+void Planner::EmitEltwise(const LNode& n, Step& s) {
+    s.kind = StepKind::Eltwise;
+    switch (n.kind) {
+        case L_ACT:
+            s.act = n.act;
+            s.bytes = vbytes(s.in) + vbytes(s.out);
+            s.flops = double(s.in.numel()) * ActFlops(n.act.kind);
+            break;
+        case L_MUL:
+            s.in2 = view_of(n.in[1]);
+            s.has_in2 = true;
+            s.mul = true;
+            s.bytes = vbytes(s.in) + vbytes(s.in2) + vbytes(s.out);
+            s.flops = double(s.out.numel());
+            break;
+        case L_AFFINE:
+            if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone scale/shift " + n.name + " on an fp8 tensor is not supported");
+            s.pre_scale_off = push_vec(n.s);
+            s.pre_shift_off = push_vec(n.t);
+            s.bytes = vbytes(s.in) + vbytes(s.out);
+            s.flops = 2.0 * double(s.in.numel());
+            break;
+        case L_CLIP:
+            if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone Clip " + n.name + " on an fp8 tensor is not supported");
+            s.lo = n.lo;
+            s.hi = n.hi;
+            s.bytes = vbytes(s.in) + vbytes(s.out);
+            s.flops = 2.0 * double(s.in.numel());
+            break;
+        case L_RELU:
+            if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone Relu " + n.name + " on an fp8 tensor is not supported");
+            s.relu = true;
+            s.bytes = vbytes(s.in) + vbytes(s.out);
+            break;
+        default:      // L_ADD
+            if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone Add " + n.name + " on fp8 tensors is not supported (only shortcuts folded into a conv)");
+            s.in2 = view_of(n.in[1]);
+            s.has_in2 = true;
+            s.bytes = vbytes(s.in) + vbytes(s.in2) + vbytes(s.out);
+            s.flops = double(s.in.numel());
+            break;
+    }
+}
+
+void Planner::EmitResize(const LNode& n, Step& s) const {
+    s.kind = StepKind::Resize;
+    s.rs_mode = n.rs_mode;
+    s.rs_coord = n.rs_coord;
+    s.rs_nearest = n.rs_nearest;
+    s.rs_scale_h = n.rs_sh;
+    s.rs_scale_w = n.rs_sw;
+    s.bytes = vbytes(s.in) + vbytes(s.out);
+    s.flops = n.rs_mode == ResizeMode::Linear ? 6.0 * double(s.out.numel()) : 0.0;    // two lerps per axis pair: 3 FMA-equivalents
+}
+
+// ---- emit steps --------------------------------------------------------------------------------
+void Planner::EmitSteps() {
     for (int idx : order) {
         const LNode& n = L.nodes[idx];
         if (n.kind == L_ALIAS) continue;
+        if (n.kind == L_CONCAT) { EmitConcatCopies(n); continue; }
         Step s;
         s.name = n.name;
-        if (n.kind == L_CONCAT) {
-            // members that could not be placed in the parent buffer are copied into their slice
-            int64_t off = 0;
-            for (size_t k = 0; k < n.in.size(); ++k) {
-                const Val& src = L.vals[n.in[k]];
-                bool placed = src.root == L.vals[n.out].root && src.abs_off == L.vals[n.out].abs_off + off;
-                if (!placed) {
-                    Step c;
-                    c.kind = StepKind::Copy;
-                    c.name = n.name + "/copy" + std::to_string(k);
-                    c.in = view_of(n.in[k]);
-                    c.out = view_of(n.out);
-                    c.out.c = src.c;
-                    c.out.c_off += off;
-                    c.bytes = vbytes(c.in) + vbytes(c.out);
-                    if (c.in.f8 || c.out.f8) fail("fp8 precision: concat copy " + c.name + " of an fp8 tensor is not supported");
-                    c.idx = int(plan.steps.size());
-                    c.in_src = src_of(c.in);
-                    writer[{int64_t(c.out.buf), c.out.c_off, c.out.c}] = c.idx;
-                    plan.steps.push_back(c);
-                }
-                off += src.c;
-            }
-            continue;
-        }
         s.in = view_of(n.in[0]);
         s.out = view_of(n.out);
         s.relu = n.relu;
@@ -1384,347 +1926,11 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             s.pre_hi = n.pre_hi;
         }
         switch (n.kind) {
-            case L_CONV: {
-                s.kind = StepKind::Conv;
-                s.kh = n.kh; s.kw = n.kw; s.sh = n.sh; s.sw = n.sw; s.pt = n.pt; s.pl = n.pl; s.pb = n.pb; s.pr = n.pr;
-                s.dh = n.dil_h; s.dw = n.dil_w;
-                // a dilated conv may only take the kernels that honour the dilation (plan.h DilationOk): the implicit GEMMs' base tiles and the
-                // naive kernel.  Every specialised kernel's eligibility below is false for it, and the forcing switches cannot move it elsewhere
-                const bool dil = s.dh > 1 || s.dw > 1;
-                s.w_off = push_vec(n.w);
-                if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
-                if (n.res >= 0) { s.in2 = view_of(n.res); s.has_in2 = true; }
-                if (n.dw) {
-                    // depthwise: its own kernel whatever IE_FORCE_ALGO says; IE_FORCE_TILE indexes the depthwise variants (kernels.h kNumConvDwTiles)
-                    s.algo = ConvAlgo::Depthwise;
-                    s.lo = n.lo;
-                    s.hi = n.hi;
-                    s.act = n.act;
-                    s.pre_act = n.pre_act;
-                    s.flops = 2.0 * double(s.out.n) * double(s.out.c) * double(s.out.h) * double(s.out.w) * n.kh * n.kw;
-                    s.bytes = vbytes(s.in) + vbytes(s.out) + 4.0 * double(n.w.size()) + (n.res >= 0 ? vbytes(s.in2) : 0.0);
-                    s.tile = DwDefaultTile(s);
-                    if (const char* ft = env.get("IE_FORCE_TILE")) {
-                        const int t = std::atoi(ft);
-                        if (t >= 0 && t < kNumConvDwTiles && (t == 0 || DwFastViews(s))) s.tile = t;
-                    }
-                    s.base_tile = 0;
-                    break;
-                }
-                if (n.group != 1) {
-                    // grouped: its own kernels whatever IE_FORCE_ALGO says; IE_FORCE_TILE indexes the grouped variants (kernels.h kNumConvGroupedTiles)
-                    s.algo = ConvAlgo::Grouped;
-                    s.group = int(n.group);
-                    s.lo = n.lo;
-                    s.hi = n.hi;
-                    s.act = n.act;
-                    s.pre_act = n.pre_act;
-                    s.flops = 2.0 * double(s.out.n) * double(s.out.h) * double(s.out.w) * double(s.out.c) * n.kh * n.kw * double(s.in.c / n.group);
-                    s.bytes = vbytes(s.in) + vbytes(s.out) + (s.in.f16 ? 2.0 : 4.0) * double(n.w.size()) + (n.res >= 0 ? vbytes(s.in2) : 0.0);
-                    s.tile = GroupedDefaultTile(s);
-                    if (const char* ft = env.get("IE_FORCE_TILE")) {
-                        const int t = std::atoi(ft);
-                        if (t >= 0 && t < kNumConvGroupedTiles && (t == 0 || GroupedFastViews(s, t))) s.tile = t;
-                    }
-                    s.base_tile = 0;
-                    break;
-                }
-                int64_t M = s.out.n * s.out.h * s.out.w, N = s.out.c, K = int64_t(n.kh) * n.kw * s.in.c;
-                s.flops = 2.0 * double(M) * double(N) * double(K);
-                const bool in16 = s.in.f16;
-                const bool in8 = s.in.f8;
-                s.bytes = vbytes(s.in) + vbytes(s.out) + (in8 ? 1.0 : (in16 ? 2.0 : 4.0)) * double(n.w.size()) + (n.res >= 0 ? vbytes(s.in2) : 0.0);
-                bool vec_ok = !in16 && !in8 && !s.in.nchw && s.in.c % 4 == 0 && s.in.pitch % 4 == 0 && s.in.c_off % 4 == 0 && n.kh * n.kw <= 32 &&
-                              s.in.n * s.in.h * s.in.w * s.in.pitch * 4 < (int64_t(1) << 31) && int64_t(n.w.size()) * 4 < (int64_t(1) << 31);
-                // fp16 MFMA path: 16-byte chunks of 8 halfs, so channel counts / slice offsets must be multiples of 8
-                const bool vec16_ok = in16 && !s.in.nchw && s.in.c % 8 == 0 && s.in.pitch % 8 == 0 && s.in.c_off % 8 == 0 && n.kh * n.kw <= 32 &&
-                                      s.in.n * s.in.h * s.in.w * s.in.pitch * 2 < (int64_t(1) << 31) && int64_t(n.w.size()) * 2 < (int64_t(1) << 31) &&
-                                      s.out.n * s.out.h * s.out.w * s.out.pitch < (int64_t(1) << 31);
-                const int64_t bk = in16 ? 2 * kIgemmBK : kIgemmBK;       // K-tile depth in elements (128 B per LDS row either way)
-                // one-thread-per-output only for toy problems (test_model's 3->5->2 MLP): at batch 1 DenseNet's block-4 convs have
-                // M*N = 1568 outputs but K = 1152 - the naive kernel took 141 us there, the MFMA kernels 13 us
-                if (M * N * K <= 32768 || (M * N < 2048 && K <= 4096 && !(vec_ok || vec16_ok))) s.algo = ConvAlgo::Naive;
-                else if (vec_ok || vec16_ok) s.algo = ConvAlgo::IgemmVec;
-                else if (K <= 2048 && !in16) s.algo = ConvAlgo::IgemmScalar;
-                else s.algo = ConvAlgo::Naive;
-                // the stem of an image classifier (7x7 / stride 2 / pad 3 over the 3-channel NCHW graph input) has its own kernel
-                const bool stem_ok = !dil && s.in.nchw && !in16 && s.in.c == 3 && n.kh == 7 && n.kw == 7 && n.sh == 2 && n.sw == 2 && n.pt == 3 &&
-                                     n.pl == 3 && n.pb == 3 && n.pr == 3 && !n.has_pre && N <= 64 && N % 8 == 0 && s.out.pitch % 8 == 0 &&
-                                     s.out.c_off % 8 == 0 && s.in.numel() * 4 < (int64_t(1) << 31) &&
-                                     s.out.n * s.out.h * s.out.w * s.out.pitch * 4 < (int64_t(1) << 31);
-                if (stem_ok && M * N >= 2048 && !(s.out.f8 && (N % 16 || s.out.pitch % 16 || s.out.c_off % 16))) s.algo = ConvAlgo::Stem;
-                if (in8 || s.out.f8) {
-                    // fp8 mode: e4m3 tensors are only understood by the fp8 kernels; anything they cannot run is a load error, never a
-                    // silent reinterpretation of the bytes by another kernel
-                    if (s.out.f8 && !in8) {
-                        if (s.algo != ConvAlgo::Stem)
-                            fail("fp8 precision: conv " + n.name + " reads a non-fp8 tensor and writes an fp8 one; only the 7x7/s2 stem over the fp32 graph input does that");
-                    } else {
-                        if (n.has_pre) fail("fp8 precision: conv " + n.name + " has an activation prologue (pre-activation graphs are not supported in fp8 mode)");
-                        if (!s.out.f8) fail("fp8 precision: conv " + n.name + " reads an fp8 tensor and writes a non-fp8 one");
-                        if (s.in.nchw || s.in.c % 16 || s.in.pitch % 16 || s.in.c_off % 16 || N % 16 || s.out.pitch % 16 || s.out.c_off % 16 || n.kh * n.kw > 32)
-                            fail("fp8 precision: conv " + n.name + " needs channel counts and slice offsets that are multiples of 16");
-                        if (n.res >= 0 && !s.in2.f8) fail("fp8 precision: the shortcut of conv " + n.name + " is not an fp8 tensor");
-                        s.algo = ConvAlgo::IgemmF8;
-                    }
-                }
-                s.tile = choose_tile(M, N);
-                s.splitk = 1;
-                const int heuristic_tile = s.tile;
-                s.base_tile = heuristic_tile;
-                // ---- plan-time eligibility of the specialised kernels (the launchers re-check pointers / alignment; the executor falls
-                //      back to the tiled implicit GEMM when a launcher declines) ----
-                const bool is1x1 = n.kh == 1 && n.kw == 1 && n.sh == 1 && n.sw == 1 && n.pt == 0 && n.pl == 0 && n.pb == 0 && n.pr == 0;
-                const bool is3x3 = !dil && n.kh == 3 && n.kw == 3 && n.sh == 1 && n.sw == 1 && n.pt == 1 && n.pl == 1 && n.pb == 1 && n.pr == 1;
-                static const int ws_tn[14] = {4, 4, 2, 2, 1, 1, 4, 4, 2, 2, 1, 1, 1, 1};      // 12, 13: fp32 K-split variants (8 / 4 waves)
-                auto ws16_ok = [&](int t) {
-                    if (t < 0 || t >= 18) return false;          // (12-17: the one-workgroup-per-CU grids of shapes 0-5)
-                    const int tn = ws_tn[t % 6];
-                    return vec16_ok && is1x1 && s.in.c % 32 == 0 &&
-                           (32 * tn * (s.in.c + 8) + 2 * s.in.c) * 2 + 128 * tn <= 160 * 1024 && !(tn > 1 && N <= 32 * (tn / 2)) &&
-                           (s.out.f16 ? (N % 8 == 0 && s.out.pitch % 8 == 0 && s.out.c_off % 8 == 0) : (N % 4 == 0 && s.out.pitch % 4 == 0 && s.out.c_off % 4 == 0));
-                };
-                auto ws32_ok = [&](int t) {
-                    if (t >= 14 && t < 20) t -= 14;              // 14-19: shapes 0-5 on a grid of one workgroup per CU: same operand conditions
-                    return t >= 0 && t < 14 && vec_ok && !s.out.f16 && is1x1 && s.in.c % 16 == 0 &&
-                           (t < 12 ? (32 * ws_tn[t] * (s.in.c + 4) + 2 * s.in.c + 32 * ws_tn[t]) * 4 <= 160 * 1024
-                                   : (s.in.c / 16 >= (t == 12 ? 8 : 4) &&
-                                      (32 * (s.in.c + 4) + 2 * s.in.c + 32 + (t == 12 ? 4 : 2) * 32 * 36) * 4 <= 160 * 1024)) &&
-                           !(ws_tn[t] > 1 && N <= 32 * (ws_tn[t] / 2)) && N % 4 == 0 && s.out.pitch % 4 == 0 && s.out.c_off % 4 == 0;
-                };
-                static const int ws3_cfg[5][3] = {{4, 2, 12}, {4, 1, 8}, {8, 1, 6}, {2, 1, 12}, {12, 1, 6}};   // waves, row blocks per wave, prefetch depth (kWs3Tiles, kernels_ws.hip)
-                auto ws3_ok = [&](int t3) {
-                    if (t3 < 0 || t3 >= 5) return false;
-                    const int64_t pr3 = 32 * ws3_cfg[t3][1] * ws3_cfg[t3][0] + 2 * (s.in.w + 1) + 2;
-                    return vec16_ok && s.out.f16 && is3x3 && !n.has_pre && N % 8 == 0 && s.out.pitch % 8 == 0 && s.out.c_off % 8 == 0 &&
-                           pr3 <= ws3_cfg[t3][2] * (64 * ws3_cfg[t3][0] / 8) && (9 * ((s.in.c + 63) / 64) * 32 + pr3) * 144 + 128 <= 160 * 1024;
-                };
-                static const int dcfg[6][3] = {{1, 8, 8}, {1, 16, 4}, {1, 9, 8}, {1, 4, 8}, {1, 12, 6}, {2, 8, 4}};   // tn, waves, max chunks
-                static const int wcfg[4][3] = {{1, 8, 9}, {2, 8, 9}, {1, 4, 18}, {2, 4, 18}};                      // window variants: tn, waves, max chunks
-                auto direct_ok = [&](int t) {
-                    if (t < 0 || t >= 15 || dil) return false;
-                    if (t >= 10) {     // activations-stationary 1x1 (fp32): the workgroup's 32 / 16 pixel rows in LDS, weights streamed from the mirror
-                        static const int acfg[5] = {128, 64, 256, 64, 64};                                        // output channels per workgroup
-                        return vec_ok && !in16 && !s.out.f16 && !s.has_in2 && is1x1 && s.in.c % 16 == 0 && N % acfg[t - 10] == 0 && s.out.pitch % 4 == 0 &&
-                               s.out.c_off % 4 == 0 && M <= (int64_t(1) << 22) && 32 * (s.in.c + 4) * 4 <= 160 * 1024;
-                    }
-                    if (t >= 6) {      // fp32, output grid == input grid, activations through an LDS window, fragment-major weights
-                        const int* wc = wcfg[t - 6];
-                        const int64_t total = s.in.c % 16 == 0 ? int64_t(n.kh) * n.kw * (s.in.c / 16) : 0;
-                        const int64_t win = (16 + (n.kh - 1) * s.in.w + (n.kw - 1)) * (s.in.c + 4) * 4, part = int64_t(wc[1]) * 16 * (16 * wc[0] + 4) * 4;
-                        return vec_ok && !in16 && !s.out.f16 && !s.has_in2 && s.in.c % 16 == 0 && N % (16 * wc[0]) == 0 && n.sh == 1 && n.sw == 1 &&
-                               s.out.h == s.in.h && s.out.w == s.in.w && n.pt < n.kh && n.pl < n.kw && s.out.pitch % 2 == 0 && s.out.c_off % 2 == 0 &&
-                               total >= wc[1] && total <= wc[1] * wc[2] && M <= 65536 && n.kh * n.kw <= 49 && std::max(win, part) <= 160 * 1024;
-                    }
-                    const int cw = in16 ? 32 : 16, al = in16 ? 8 : 4;
-                    const int64_t total = s.in.c % cw == 0 ? int64_t(n.kh) * n.kw * (s.in.c / cw) : 0;
-                    return (vec_ok || vec16_ok) && s.in.c % cw == 0 && s.in.pitch % al == 0 && s.in.c_off % al == 0 && N % 2 == 0 && s.out.pitch % 2 == 0 &&
-                           s.out.c_off % 2 == 0 && total >= dcfg[t][1] && total <= dcfg[t][1] * dcfg[t][2] && !(dcfg[t][0] > 1 && N <= 32) && M <= 65536 &&
-                           n.kh * n.kw <= 49;
-                };
-                const bool raster_ok = vec_ok && !s.out.f16 && is3x3 && !n.has_pre;
-                const bool wino_ok = raster_ok && N == 32 && s.in.c % 32 == 0 && s.in.h % 2 == 0 && s.in.w % 2 == 0 && n.res < 0 && s.out.pitch % 4 == 0 && s.out.c_off % 4 == 0;
-                // ---- default choice without the autotuner (IE_AUTOTUNE=0, or before Prepare() has timed anything): the kernels
-                //      the exhaustive search picks for DenseNet / ResNet shapes ----
-                if (s.algo == ConvAlgo::IgemmF8) {
-                    if (const char* ft = env.get("IE_FORCE_TILE")) {
-                        const int t = std::atoi(ft);
-                        if (t >= 0 && t < kNumIgemmBaseTiles && !(kIgemmTiles[t].bn > 32 && N <= 32)) s.tile = t;
-                        // kWs8Code + t: the weights-stationary 1x1 kernel's tiles, kWs38Code + t: the 3x3's (kernels_ws8.hip); a launcher that
-                        // declines the operands hands the step back to the tiled kernel (executor)
-                        if (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles && n.kh == 1 && n.kw == 1) s.tile = t;      // (strided 1x1 convs too: the kernel's STR form)
-                        if (t >= kWs38Code && t < kWs38Code + kNumConvWs38Tiles && is3x3) s.tile = t;
-                    }
-                    break;
-                }
-                if (!env.get("IE_FORCE_ALGO") && !env.get("IE_FORCE_TILE") && s.algo == ConvAlgo::IgemmVec) {
-                    int pick = -1;
-                    if (M <= 2048) {                                                       // tiny grids: split K over the waves
-                        if (is3x3 && direct_ok(6)) pick = 6;                             // 16-pixel window tiles: 4x the workgroups
-                        else if (is1x1 && direct_ok(13)) pick = 13;                      // 16-pixel activations-stationary tiles
-                        for (int t : {1, 0, 4, 3}) if (pick < 0 && direct_ok(t)) pick = t;
-                        if (pick >= 0) { s.algo = ConvAlgo::Direct; s.tile = pick; }
-                    } else if (in16) {
-                        if (is1x1) { for (int t : {0, 2, 4}) if (pick < 0 && ws16_ok(t)) pick = t; if (pick >= 0) { s.algo = ConvAlgo::Ws1x1; s.tile = pick; } }
-                        else if (is3x3) { for (int t : {2, 1, 0}) if (pick < 0 && ws3_ok(t)) pick = t; if (pick >= 0) { s.algo = ConvAlgo::Ws3x3; s.tile = pick; } }
-                    } else {
-                        if (is1x1 && direct_ok(10)) { s.algo = ConvAlgo::Direct; s.tile = 10; }      // activations-stationary 1x1: 128-channel multiples whose 32 pixel rows fit in LDS
-                        else if (is1x1 && M >= 20000) { for (int t : {0, 2, 4}) if (pick < 0 && ws32_ok(t)) pick = t; if (pick >= 0) { s.algo = ConvAlgo::Ws1x1; s.tile = pick; } }
-                        else if (wino_ok && M >= 20000) { s.algo = ConvAlgo::Wino3x3; s.tile = 5; }     // Winograd F(2x2,3x3), 2x14 tiles, eight waves (falls back to the tiled kernel without the U mirror)
-                        else if (raster_ok && M >= 20000 && N <= 64) { s.algo = ConvAlgo::Raster3x3; s.tile = N <= 32 ? 0 : 4; }
-                        else if (is3x3 && M <= 8192) { if (direct_ok(4)) { s.algo = ConvAlgo::Direct; s.tile = 4; } }
-                    }
-                }
-                // Test / tuning overrides (read at plan time): IE_FORCE_TILE=<n>, IE_FORCE_ALGO=naive|scalar|igemm|raster|ws|direct
-                const char* fa = env.get("IE_FORCE_ALGO");
-                if (fa && dil && std::string(fa) != "naive" && std::string(fa) != "scalar" && std::string(fa) != "igemm") fa = nullptr;
-                if (fa) {
-                    std::string f = fa;
-                    if (f == "naive") s.algo = ConvAlgo::Naive;
-                    else if (f == "scalar" && K <= 2048 && !in16) s.algo = ConvAlgo::IgemmScalar;
-                    else if (f == "igemm" && s.algo == ConvAlgo::Stem) s.algo = K <= 2048 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive;
-                    else if (f == "igemm" && s.algo == ConvAlgo::Naive)
-                        s.algo = (vec_ok || vec16_ok) ? ConvAlgo::IgemmVec : (K <= 2048 && !in16 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive);
-                    else if (f == "ws") {
-                        int t = 0;
-                        if (const char* ft = env.get("IE_FORCE_TILE")) { int v = std::atoi(ft); if (v >= 0 && v < (in16 ? kNumConvWs16Tiles : kNumConvWs32Tiles)) t = v; }
-                        if (ws16_ok(t) || ws32_ok(t)) { s.algo = ConvAlgo::Ws1x1; s.tile = t; }
-                        else if (ws3_ok(t % kNumConvWs3Tiles)) { s.algo = ConvAlgo::Ws3x3; s.tile = t % kNumConvWs3Tiles; }
-                        else if (s.algo == ConvAlgo::Naive && vec16_ok) s.algo = ConvAlgo::IgemmVec;
-                    }
-                    else if (f == "direct") {
-                        int t = 0;
-                        if (const char* ft = env.get("IE_FORCE_TILE")) { int v = std::atoi(ft); if (v >= 0 && v < kNumConvDirectTiles) t = v; }
-                        if (direct_ok(t)) { s.algo = ConvAlgo::Direct; s.tile = t; }
-                        else if (s.algo == ConvAlgo::Naive && (vec_ok || vec16_ok)) s.algo = ConvAlgo::IgemmVec;
-                    }
-                    else if (f == "x6") {
-                        const bool x6_ok = vec_ok && !s.out.f16 && is1x1 && n.sh == 1 && n.sw == 1 && s.in.c % 32 == 0 && N % 128 == 0 && n.res < 0;
-                        if (x6_ok) {
-                            s.algo = ConvAlgo::X6;
-                            s.tile = 0;
-                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < kNumConvX6Tiles) s.tile = t; }
-                        }
-                    }
-                    else if (f == "wino") {
-                        if (wino_ok) {
-                            s.algo = ConvAlgo::Wino3x3;
-                            s.tile = 0;
-                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < kNumConvWinoTiles) s.tile = t; }
-                        } else if (s.algo == ConvAlgo::Naive)
-                            s.algo = (vec_ok || vec16_ok) ? ConvAlgo::IgemmVec : (K <= 2048 && !in16 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive);
-                    }
-                    else if (f == "raster") {
-                        if (raster_ok) {
-                            s.algo = ConvAlgo::Raster3x3;
-                            s.tile = 0;
-                            if (const char* ft = env.get("IE_FORCE_TILE")) { int t = std::atoi(ft); if (t >= 0 && t < kNumConvRasterTiles) s.tile = t; }
-                        } else if (s.algo == ConvAlgo::Naive)
-                            s.algo = (vec_ok || vec16_ok) ? ConvAlgo::IgemmVec : (K <= 2048 && !in16 ? ConvAlgo::IgemmScalar : ConvAlgo::Naive);
-                    }
-                }
-                if (const char* ft = (s.algo == ConvAlgo::Raster3x3 || s.algo == ConvAlgo::Ws1x1 || s.algo == ConvAlgo::Ws3x3 || s.algo == ConvAlgo::Stem || s.algo == ConvAlgo::Direct || s.algo == ConvAlgo::Wino3x3 || s.algo == ConvAlgo::X6) ? nullptr
-                                                                                                                                          : env.get("IE_FORCE_TILE")) {
-                    int t = std::atoi(ft);
-                    if (t >= 0 && t < kNumIgemmTiles && (t < kNumIgemmBaseTiles || (s.algo == ConvAlgo::IgemmVec && !dil)) && !(in16 && kIgemmTiles[t].deep)) s.tile = t;
-                }
-                if (s.algo != ConvAlgo::IgemmVec && s.algo != ConvAlgo::Raster3x3 && s.algo != ConvAlgo::Ws1x1 && s.algo != ConvAlgo::Ws3x3 && s.algo != ConvAlgo::Direct && s.algo != ConvAlgo::Wino3x3 && s.algo != ConvAlgo::X6 && s.tile >= kNumIgemmBaseTiles)
-                    s.tile = heuristic_tile;       // K-group tiles exist for the vector path only
-                if (s.algo == ConvAlgo::Raster3x3) {
-                    if (const char* fs = env.get("IE_FORCE_SPLITK")) {
-                        int v = std::atoi(fs);
-                        if (v >= 1 && v <= 64) s.splitk = v;
-                    }
-                    if (s.splitk > 1) plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, int64_t(s.splitk) * M * N);
-                } else if (s.algo == ConvAlgo::Ws1x1 || s.algo == ConvAlgo::Ws3x3 || s.algo == ConvAlgo::Stem || s.algo == ConvAlgo::Direct || s.algo == ConvAlgo::Wino3x3 || s.algo == ConvAlgo::X6) {
-                    s.splitk = 1;
-                } else if (s.algo != ConvAlgo::Naive) {
-                    // split-K when the output grid cannot fill the chip: aim for >= ~768 workgroups, keep >= 2 K-tiles
-                    // per split.  (Deterministic two-pass reduction, see kernels.hip.)
-                    const IgemmTile& T = kIgemmTiles[s.tile];
-                    const int64_t wgs = ((M + T.bm - 1) / T.bm) * ((N + T.bn - 1) / T.bn);
-                    const int64_t cblocks = (s.in.c + bk - 1) / bk;
-                    const int64_t KT = s.algo == ConvAlgo::IgemmVec ? int64_t(n.kh) * n.kw * cblocks : (K + kIgemmBK - 1) / kIgemmBK;
-                    if (wgs < 384 && KT >= 4) {
-                        int64_t want = (768 + wgs - 1) / wgs;
-                        s.splitk = int(std::max<int64_t>(1, std::min<int64_t>({want, KT / 2, 32})));
-                    }
-                    if (const char* fs = env.get("IE_FORCE_SPLITK")) {
-                        int v = std::atoi(fs);
-                        if (v >= 1 && v <= 64) s.splitk = v;
-                    }
-                    if (s.splitk > 1) plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, int64_t(s.splitk) * M * N);
-                }
-                break;
-            }
-            case L_MAXPOOL: case L_AVGPOOL:
-                if ((s.in.f8 || s.out.f8) && (!s.in.f8 || !s.out.f8 || n.has_pre || s.in.c % 16 || s.in.pitch % 16 || s.in.c_off % 16 || s.out.pitch % 16 || s.out.c_off % 16))
-                    fail("fp8 precision: pool " + n.name + " needs fp8 operands without a prologue and channel counts that are multiples of 16");
-                s.kind = StepKind::Pool;
-                s.pool_max = n.kind == L_MAXPOOL;
-                s.count_include_pad = n.count_include_pad;
-                s.kh = n.kh; s.kw = n.kw; s.sh = n.sh; s.sw = n.sw; s.pt = n.pt; s.pl = n.pl; s.pb = n.pb; s.pr = n.pr;
-                s.bytes = vbytes(s.in) + vbytes(s.out);
-                s.flops = double(s.out.numel()) * n.kh * n.kw;
-                break;
-            case L_GAP:
-                if (s.in.f8 && (n.has_pre || s.out.f8)) fail("fp8 precision: global pool " + n.name + " with a prologue is not supported");
-                s.kind = StepKind::GlobalAvgPool;
-                s.pre_act = n.pre_act;
-                s.bytes = vbytes(s.in) + vbytes(s.out);
-                s.flops = double(s.in.numel()) * (1.0 + ActFlops(n.pre_act.kind));
-                break;
-            case L_ACT:
-                s.kind = StepKind::Eltwise;
-                s.act = n.act;
-                s.bytes = vbytes(s.in) + vbytes(s.out);
-                s.flops = double(s.in.numel()) * ActFlops(n.act.kind);
-                break;
-            case L_MUL:
-                s.kind = StepKind::Eltwise;
-                s.in2 = view_of(n.in[1]);
-                s.has_in2 = true;
-                s.mul = true;
-                s.bytes = vbytes(s.in) + vbytes(s.in2) + vbytes(s.out);
-                s.flops = double(s.out.numel());
-                break;
-            case L_SE: {
-                s.kind = StepKind::SqueezeExcite;
-                s.w_off = push_vec(n.w);
-                if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
-                s.w2_off = push_vec(n.w2);
-                if (!n.bias2.empty()) s.bias2_off = push_vec(n.bias2);
-                s.se_mid = n.se_mid;
-                s.se_act1 = n.se_act1;
-                s.act = n.act;
-                s.se_chunks = SeSqueezeChunks(s.in.n, s.in.h * s.in.w);
-                plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, SeWorkspaceFloats(s.in.n, s.in.c, n.se_mid, s.se_chunks));
-                // squeeze (one add per element), the two FCs (2 x MACs, activations), the gate multiply; the input is read twice
-                const double nc = double(s.in.n) * double(s.in.c), nm = double(s.in.n) * n.se_mid;
-                s.flops = double(s.in.numel()) + 4.0 * nc * n.se_mid + nm * ActFlops(n.se_act1.kind) + nc * ActFlops(n.act.kind) + double(s.out.numel());
-                s.bytes = 2.0 * vbytes(s.in) + vbytes(s.out) + 4.0 * double(n.w.size() + n.w2.size() + n.bias.size() + n.bias2.size());
-                break;
-            }
-            case L_AFFINE:
-                if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone scale/shift " + n.name + " on an fp8 tensor is not supported");
-                s.kind = StepKind::Eltwise;
-                s.pre_scale_off = push_vec(n.s);
-                s.pre_shift_off = push_vec(n.t);
-                s.bytes = vbytes(s.in) + vbytes(s.out);
-                s.flops = 2.0 * double(s.in.numel());
-                break;
-            case L_CLIP:
-                if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone Clip " + n.name + " on an fp8 tensor is not supported");
-                s.kind = StepKind::Eltwise;
-                s.lo = n.lo;
-                s.hi = n.hi;
-                s.bytes = vbytes(s.in) + vbytes(s.out);
-                s.flops = 2.0 * double(s.in.numel());
-                break;
-            case L_RELU:
-                if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone Relu " + n.name + " on an fp8 tensor is not supported");
-                s.kind = StepKind::Eltwise;
-                s.relu = true;
-                s.bytes = vbytes(s.in) + vbytes(s.out);
-                break;
-            case L_ADD:
-                if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone Add " + n.name + " on fp8 tensors is not supported (only shortcuts folded into a conv)");
-                s.kind = StepKind::Eltwise;
-                s.in2 = view_of(n.in[1]);
-                s.has_in2 = true;
-                s.bytes = vbytes(s.in) + vbytes(s.in2) + vbytes(s.out);
-                s.flops = double(s.in.numel());
-                break;
-            case L_RESIZE:
-                s.kind = StepKind::Resize;
-                s.rs_mode = n.rs_mode;
-                s.rs_coord = n.rs_coord;
-                s.rs_nearest = n.rs_nearest;
-                s.rs_scale_h = n.rs_sh;
-                s.rs_scale_w = n.rs_sw;
-                s.bytes = vbytes(s.in) + vbytes(s.out);
-                s.flops = n.rs_mode == ResizeMode::Linear ? 6.0 * double(s.out.numel()) : 0.0;    // two lerps per axis pair: 3 FMA-equivalents
-                break;
+            case L_CONV: EmitConv(n, s); break;
+            case L_MAXPOOL: case L_AVGPOOL: case L_GAP: EmitPool(n, s); break;
+            case L_SE: EmitSqueezeExcite(n, s); break;
+            case L_ACT: case L_MUL: case L_AFFINE: case L_CLIP: case L_RELU: case L_ADD: EmitEltwise(n, s); break;
+            case L_RESIZE: EmitResize(n, s); break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -1743,282 +1949,278 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
         plan.steps.push_back(std::move(s));
     }
     while (plan.weights.size() % 8) plan.weights.push_back(0.f);
+}
 
-    // ---- dense fusion (fp32, small output grids): 3x3 growth conv of layer L + the 1x1 bottleneck conv of layer L+1 ------------------
-    // Pattern: step i = plain 3x3/s1/p1 conv (no prologue, 32 output channels) writing a channel slice of a concat buffer; step i+1 =
-    // 1x1 conv with 128 output channels whose input view is that buffer's channels [c_off, slice end): its last 32 input channels are
-    // exactly what step i produces, for the same pixels (kernels_fused.hip).  Only where launches are latency-bound (M <= 8192).
-    if (precision == Precision::F32 && !env.get("IE_NO_DENSE_FUSE") && !env.get("IE_FORCE_ALGO") && !env.get("IE_FORCE_TILE")) {
-        std::vector<Step> fusedsteps;
-        for (size_t i = 0; i < plan.steps.size(); ++i) {
-            const Step& s3 = plan.steps[i];
-            bool fuse = false;
-            if (i + 1 < plan.steps.size()) {
-                const Step& s1 = plan.steps[i + 1];
-                const int64_t M = s3.out.n * s3.out.h * s3.out.w;
-                fuse = s3.kind == StepKind::Conv && s1.kind == StepKind::Conv && !IsGroupConv(s3.algo) && !IsGroupConv(s1.algo) && s3.dh == 1 && s3.dw == 1 && s3.kh == 3 && s3.kw == 3 && s3.sh == 1 && s3.sw == 1 && s3.pt == 1 && s3.pl == 1 &&
-                       s3.pb == 1 && s3.pr == 1 && s3.pre_scale_off < 0 && !s3.has_in2 && s3.out.c == 32 && s3.in.c % 16 == 0 && 9 * (s3.in.c / 16) <= 72 &&
-                       9 * (s3.in.c / 16) >= 8 && s1.kh == 1 && s1.kw == 1 && s1.sh == 1 && s1.sw == 1 && s1.pt == 0 && s1.pl == 0 && s1.pb == 0 && s1.pr == 0 &&
-                       !s1.has_in2 && s1.out.c == 128 && s1.in.buf == s3.out.buf && s1.in.pitch == s3.out.pitch && !s1.in.nchw && !s3.in.nchw &&
-                       s1.in.c_off + s1.in.c == s3.out.c_off + s3.out.c && s1.in.c >= 48 && s1.in.c % 16 == 0 && s1.in.n == s3.out.n && s1.in.h == s3.out.h &&
-                       s1.in.w == s3.out.w && s1.out.buf != s3.in.buf && M <= FuseMaxPixels(env) && s3.algo != ConvAlgo::Naive && s1.algo != ConvAlgo::Naive &&
-                       s3.in.pitch % 4 == 0 && s3.in.c_off % 4 == 0 && s1.in.pitch % 4 == 0 && s1.in.c_off % 4 == 0 && s1.out.pitch % 4 == 0 && s1.out.c_off % 4 == 0;
+namespace {
+
+// `steps` replaces the plan's step list: a step of algorithm `fused` stands for all of its parts.  idx, in_src / in2_src follow the new
+// positions (a fused step is the producer of every output of its parts)
+void ReplaceSteps(Plan& plan, std::vector<Step> steps, ConvAlgo fused) {
+    if (steps.size() == plan.steps.size()) return;
+    std::vector<int> remap(plan.steps.size(), -1);
+    for (size_t k = 0; k < steps.size(); ++k) {
+        if (steps[k].algo == fused) for (const Step& q : steps[k].parts) remap[size_t(q.idx)] = int(k);
+        else remap[size_t(steps[k].idx)] = int(k);
+    }
+    for (size_t k = 0; k < steps.size(); ++k) {
+        Step& st = steps[k];
+        st.idx = int(k);
+        if (st.in_src >= 0) st.in_src = remap[size_t(st.in_src)];
+        if (st.in2_src >= 0) st.in2_src = remap[size_t(st.in2_src)];
+    }
+    plan.steps = std::move(steps);
+}
+
+}  // namespace
+
+// ---- dense fusion (fp32, small output grids): 3x3 growth conv of layer L + the 1x1 bottleneck conv of layer L+1 ------------------
+// Pattern: step i = plain 3x3/s1/p1 conv (no prologue, 32 output channels) writing a channel slice of a concat buffer; step i+1 =
+// 1x1 conv with 128 output channels whose input view is that buffer's channels [c_off, slice end): its last 32 input channels are
+// exactly what step i produces, for the same pixels (kernels_fused.hip).  Only where launches are latency-bound (M <= 8192).
+void Planner::FuseDenseLayers() {
+    std::vector<Step> fusedsteps;
+    for (size_t i = 0; i < plan.steps.size(); ++i) {
+        const Step& s3 = plan.steps[i];
+        bool fuse = false;
+        if (i + 1 < plan.steps.size()) {
+            const Step& s1 = plan.steps[i + 1];
+            const int64_t M = s3.out.n * s3.out.h * s3.out.w;
+            fuse = s3.kind == StepKind::Conv && s1.kind == StepKind::Conv && !IsGroupConv(s3.algo) && !IsGroupConv(s1.algo) && s3.dh == 1 && s3.dw == 1 && s3.kh == 3 && s3.kw == 3 && s3.sh == 1 && s3.sw == 1 && s3.pt == 1 && s3.pl == 1 &&
+                   s3.pb == 1 && s3.pr == 1 && s3.pre_scale_off < 0 && !s3.has_in2 && s3.out.c == 32 && s3.in.c % 16 == 0 && 9 * (s3.in.c / 16) <= 72 &&
+                   9 * (s3.in.c / 16) >= 8 && s1.kh == 1 && s1.kw == 1 && s1.sh == 1 && s1.sw == 1 && s1.pt == 0 && s1.pl == 0 && s1.pb == 0 && s1.pr == 0 &&
+                   !s1.has_in2 && s1.out.c == 128 && s1.in.buf == s3.out.buf && s1.in.pitch == s3.out.pitch && !s1.in.nchw && !s3.in.nchw &&
+                   s1.in.c_off + s1.in.c == s3.out.c_off + s3.out.c && s1.in.c >= 48 && s1.in.c % 16 == 0 && s1.in.n == s3.out.n && s1.in.h == s3.out.h &&
+                   s1.in.w == s3.out.w && s1.out.buf != s3.in.buf && M <= FuseMaxPixels(env) && s3.algo != ConvAlgo::Naive && s1.algo != ConvAlgo::Naive &&
+                   s3.in.pitch % 4 == 0 && s3.in.c_off % 4 == 0 && s1.in.pitch % 4 == 0 && s1.in.c_off % 4 == 0 && s1.out.pitch % 4 == 0 && s1.out.c_off % 4 == 0;
+            if (fuse) {
+                int pb = M <= 2048 ? 1 : 2;
+                int ftile = 0;
+                if (const char* e = env.get("IE_FUSE_PB")) { const int v = std::atoi(e); if (v == 1 || v == 2) pb = v; if (v == 3) { pb = 1; ftile = 3; } if (v == 4 || v == 5) { pb = v - 3; ftile = v; } }
+                const int64_t px = 16 * pb;
+                const int64_t win = (px + 2 * s3.in.w + 2) * (s3.in.c + 8) * 4, part = 4 * px * 36 * 4;
+                const int64_t c4n = (s1.in.c - 32) / 4, rpp = c4n > 0 && c4n <= 512 ? 512 / c4n : 0;
+                if (std::max(px * (s1.in.c + 8) * 4, win) + part > 160 * 1024 || rpp == 0 || (px + rpp - 1) / rpp > (pb == 1 ? 8 : 16) ||
+                    (px + 2 * s3.in.w + 2) * (s3.in.c / 4) > 8 * 512)
+                    fuse = false;
                 if (fuse) {
-                    int pb = M <= 2048 ? 1 : 2;
-                    int ftile = 0;
-                    if (const char* e = env.get("IE_FUSE_PB")) { const int v = std::atoi(e); if (v == 1 || v == 2) pb = v; if (v == 3) { pb = 1; ftile = 3; } if (v == 4 || v == 5) { pb = v - 3; ftile = v; } }
-                    const int64_t px = 16 * pb;
-                    const int64_t win = (px + 2 * s3.in.w + 2) * (s3.in.c + 8) * 4, part = 4 * px * 36 * 4;
-                    const int64_t c4n = (s1.in.c - 32) / 4, rpp = c4n > 0 && c4n <= 512 ? 512 / c4n : 0;
-                    if (std::max(px * (s1.in.c + 8) * 4, win) + part > 160 * 1024 || rpp == 0 || (px + rpp - 1) / rpp > (pb == 1 ? 8 : 16) ||
-                        (px + 2 * s3.in.w + 2) * (s3.in.c / 4) > 8 * 512)
-                        fuse = false;
-                    if (fuse) {
-                        Step f = s1;
-                        f.algo = ConvAlgo::DenseFused;
-                        f.tile = ftile ? ftile : pb;
-                        f.splitk = 1;
-                        f.name = s3.name + " | " + s1.name;
-                        f.flops = s3.flops + s1.flops;
-                        f.bytes = s3.bytes + s1.bytes;
-                        f.parts = {s3, s1};
-                        fusedsteps.push_back(std::move(f));
-                        ++i;
-                    }
+                    Step f = s1;
+                    f.algo = ConvAlgo::DenseFused;
+                    f.tile = ftile ? ftile : pb;
+                    f.splitk = 1;
+                    f.name = s3.name + " | " + s1.name;
+                    f.flops = s3.flops + s1.flops;
+                    f.bytes = s3.bytes + s1.bytes;
+                    f.parts = {s3, s1};
+                    fusedsteps.push_back(std::move(f));
+                    ++i;
                 }
             }
-            if (!fuse) fusedsteps.push_back(s3);
         }
-        if (fusedsteps.size() != plan.steps.size()) {
-            // renumber: idx, in_src / in2_src follow the new positions (a fused step is the producer of both of its outputs)
-            std::vector<int> remap(plan.steps.size(), -1);
-            for (size_t k = 0; k < fusedsteps.size(); ++k) {
-                if (fusedsteps[k].algo == ConvAlgo::DenseFused) { remap[size_t(fusedsteps[k].parts[0].idx)] = int(k); remap[size_t(fusedsteps[k].parts[1].idx)] = int(k); }
-                else remap[size_t(fusedsteps[k].idx)] = int(k);
-            }
-            for (size_t k = 0; k < fusedsteps.size(); ++k) {
-                Step& st = fusedsteps[k];
-                st.idx = int(k);
-                if (st.in_src >= 0) st.in_src = remap[size_t(st.in_src)];
-                if (st.in2_src >= 0) st.in2_src = remap[size_t(st.in2_src)];
-            }
-            plan.steps = std::move(fusedsteps);
-        }
+        if (!fuse) fusedsteps.push_back(s3);
     }
+    ReplaceSteps(plan, std::move(fusedsteps), ConvAlgo::DenseFused);
+}
 
-    // ---- dense-block chains (fp16, small maps): consecutive dense layers of one concat buffer as ONE step ---------------------------------------
-    // Pattern per layer: step i = 1x1/s1 conv with 128 output channels reading channels [c_off, c_off + K) of a concat buffer into a bottleneck
-    // tensor T, step i+1 = plain 3x3/s1/p1 conv (no prologue, no residual) from T to 32 channels of the SAME concat buffer outside what the
-    // layer reads, T read by nothing else.  A layer touches only its own image, so a workgroup per image walks the whole chain with T in LDS
-    // (kernels_block.hip): DenseNet-121 blocks 3-4 at batch 128 go from 80 launches to 2.  Maps of at most 8 x 32 raster positions (14x14, 7x7).
-    if (precision == Precision::F16 && !env.get("IE_NO_DENSE_BLOCK") && !env.get("IE_FORCE_ALGO") && !env.get("IE_FORCE_TILE")) {
-        auto same_view = [](const View& a, const View& b) {
-            return a.buf == b.buf && a.n == b.n && a.c == b.c && a.h == b.h && a.w == b.w && a.c_off == b.c_off && a.pitch == b.pitch && a.nchw == b.nchw && a.f16 == b.f16;
+// One dense layer of a dense-block chain at steps i (the 1x1 conv) and i + 1 (the 3x3 conv): see FuseDenseBlocks
+bool Planner::DenseLayerAt(size_t i) const {
+    auto same_view = [](const View& a, const View& b) {
+        return a.buf == b.buf && a.n == b.n && a.c == b.c && a.h == b.h && a.w == b.w && a.c_off == b.c_off && a.pitch == b.pitch && a.nchw == b.nchw && a.f16 == b.f16;
+    };
+    if (i + 1 >= plan.steps.size()) return false;
+    const Step& s1 = plan.steps[i];
+    const Step& s3 = plan.steps[i + 1];
+    if (s1.kind != StepKind::Conv || s3.kind != StepKind::Conv || !s1.parts.empty() || !s3.parts.empty()) return false;
+    if (IsGroupConv(s1.algo) || IsGroupConv(s3.algo)) return false;
+    if (s1.kh != 1 || s1.kw != 1 || s1.sh != 1 || s1.sw != 1 || s1.pt || s1.pl || s1.pb || s1.pr || s1.has_in2 || s1.out.c != 128) return false;
+    if (s3.kh != 3 || s3.kw != 3 || s3.sh != 1 || s3.sw != 1 || s3.pt != 1 || s3.pl != 1 || s3.pb != 1 || s3.pr != 1 || s3.has_in2 || s3.out.c != 32) return false;
+    if (s3.dh != 1 || s3.dw != 1) return false;
+    if (s3.pre_scale_off >= 0 || s1.w_off < 0 || s3.w_off < 0) return false;
+    if (!s1.in.f16 || !s1.out.f16 || !s3.out.f16 || s1.in.nchw || s1.out.nchw || s3.out.nchw) return false;
+    if (!same_view(s3.in, s1.out) || s3.out.buf != s1.in.buf || s3.out.pitch != s1.in.pitch || s1.out.buf == s1.in.buf) return false;
+    if (s3.out.n != s1.in.n || s3.out.h != s1.in.h || s3.out.w != s1.in.w) return false;
+    if (s1.in.c < 64 || s1.in.c % 32 || s1.in.pitch % 8 || s1.in.c_off % 8 || s3.out.c_off % 8) return false;
+    if (s3.out.c_off < s1.in.c_off + s1.in.c && s3.out.c_off + 32 > s1.in.c_off) return false;
+    if ((s1.pre_scale_off >= 0) != (s1.pre_shift_off >= 0)) return false;
+    // up to 7 raster tiles: a workgroup per image (chains of layers); larger maps: bands of rows, one layer per launch, while at least one
+    // row + halo fits the 8 staged tiles
+    // Band mode measured no faster than the two streaming kernels at batch 128 (28x28: 39-58 vs 42-54 us per layer; 56x56: 160-218 vs 93-123 us:
+    // the per-band fixed cost -- 72 KB of 3x3 weights into LDS, raster reset, epilogue -- is paid 5 ... 28 times per image), so such steps are
+    // only formed on request (IE_DENSE_BAND=1: tests, experiments).
+    const int64_t ntiles = (s1.in.h * (s1.in.w + 1) + 31) / 32;
+    if (ntiles > 7 && (!env.flag("IE_DENSE_BAND") || (s1.in.w + 1 > 64 && 256 / (s1.in.w + 1) < 3))) return false;
+    // T must have no other reader: the fused kernel never writes it to memory
+    for (size_t j = i + 2; j < plan.steps.size(); ++j) {
+        const Step& q = plan.steps[j];
+        if (q.in.buf == s1.out.buf || (q.has_in2 && q.in2.buf == s1.out.buf)) return false;
+        if (q.out.buf == s1.out.buf) break;                // the buffer was recycled for another tensor: T was dead by then (liveness pass)
+    }
+    return !output_in_buffer(s1.out.buf);
+}
+
+// ---- dense-block chains (fp16, small maps): consecutive dense layers of one concat buffer as ONE step ---------------------------------------
+// Pattern per layer: step i = 1x1/s1 conv with 128 output channels reading channels [c_off, c_off + K) of a concat buffer into a bottleneck
+// tensor T, step i+1 = plain 3x3/s1/p1 conv (no prologue, no residual) from T to 32 channels of the SAME concat buffer outside what the
+// layer reads, T read by nothing else.  A layer touches only its own image, so a workgroup per image walks the whole chain with T in LDS
+// (kernels_block.hip): DenseNet-121 blocks 3-4 at batch 128 go from 80 launches to 2.  Maps of at most 8 x 32 raster positions (14x14, 7x7).
+void Planner::FuseDenseBlocks() {
+    std::vector<Step> blocksteps;
+    for (size_t i = 0; i < plan.steps.size();) {
+        size_t n = 0;
+        while (n < 24 && DenseLayerAt(i + 2 * n)) {
+            if (n > 0) {
+                if ((plan.steps[i].in.h * (plan.steps[i].in.w + 1) + 31) / 32 > 7) break;       // band mode: one layer per launch
+                const Step& f1 = plan.steps[i], &c1 = plan.steps[i + 2 * n], &p3 = plan.steps[i + 2 * n - 1];
+                if (c1.in.buf != f1.in.buf || c1.in.pitch != f1.in.pitch || c1.in.c_off != f1.in.c_off || c1.in.n != f1.in.n || c1.in.h != f1.in.h || c1.in.w != f1.in.w)
+                    break;
+                // a layer's first 192 input channels are requested while the previous layer's 3x3 still runs: they must not be its output
+                if (p3.out.c_off < c1.in.c_off + 192 && p3.out.c_off + 32 > c1.in.c_off) break;
+            }
+            ++n;
+        }
+        if (n == 0) { blocksteps.push_back(plan.steps[i]); ++i; continue; }
+        Step f = plan.steps[i];
+        f.algo = ConvAlgo::DenseBlock;
+        f.tile = 1;
+        f.splitk = 1;
+        f.flops = 0;
+        f.bytes = 0;
+        f.parts.clear();
+        for (size_t q = 0; q < 2 * n; ++q) {
+            const Step& ps = plan.steps[i + q];
+            f.parts.push_back(ps);
+            f.flops += ps.flops;
+            f.bytes += ps.bytes;       // SURVEY §8d's per-conv accounting (the bottleneck tensor's write + read is in it although it stays on-chip here)
+        }
+        f.name = plan.steps[i].name + " ... " + plan.steps[i + 2 * n - 1].name;
+        f.out = plan.steps[i + 2 * n - 1].out;             // what the step leaves in memory last (every part's slice is produced by this step)
+        blocksteps.push_back(std::move(f));
+        i += 2 * n;
+    }
+    ReplaceSteps(plan, std::move(blocksteps), ConvAlgo::DenseBlock);
+}
+
+// ---- stem + max pool: the 7x7/s2 stem conv and the 3x3/s2/p1 max pool behind it -> ONE step -------------------------------------
+// Pattern: step i = the stem conv (algo Stem, ReLU'd), step i + 1 = a max pool 3x3 / stride 2 / pad 1 without a prologue that
+// reads exactly step i's output, which nothing else reads.  conv_stem_kernel<POOL> (kernels_stem.hip) pools the conv tile in LDS: the tensor
+// between the two ops (the largest of DenseNet / ResNet) is never written.  parts = {conv, pool}; tile 1 = fused, 0 = the two launches.
+void Planner::FuseStemPool() {
+    for (size_t i = 0; i + 1 < plan.steps.size(); ++i) {
+        const Step& c = plan.steps[i];
+        const Step& pl = plan.steps[i + 1];
+        if (c.kind != StepKind::Conv || c.algo != ConvAlgo::Stem || !c.relu || c.has_in2 || !c.parts.empty() || c.out.nchw || c.out.c > 64 || c.out.c % 8) continue;
+        if (pl.kind != StepKind::Pool || !pl.pool_max || pl.kh != 3 || pl.kw != 3 || pl.sh != 2 || pl.sw != 2 || pl.pt != 1 || pl.pl != 1 || pl.pb > 1 || pl.pr > 1) continue;
+        if (pl.pre_scale_off >= 0 || pl.pre_relu || pl.has_in2 || pl.in_src != int(i)) continue;
+        if (pl.in.buf != c.out.buf || pl.in.c_off != c.out.c_off || pl.in.c != c.out.c || pl.in.pitch != c.out.pitch || pl.in.h != c.out.h || pl.in.w != c.out.w) continue;
+        if (pl.out.f16 != c.out.f16 || pl.out.f8 != c.out.f8 || pl.out.nchw || pl.out.buf == c.out.buf || pl.out.buf == c.in.buf) continue;
+        if (pl.out.h != (c.out.h + 2 - 3) / 2 + 1 || pl.out.w != (c.out.w + 2 - 3) / 2 + 1) continue;
+        if (pl.out.pitch % 8 || pl.out.c_off % 8 || (pl.out.f8 && (pl.out.pitch % 16 || pl.out.c_off % 16))) continue;
+        // the conv's output must have no other reader: walk the launches behind the pool in execution order (a fused step = its parts) until the
+        // buffer is written again -- recycled for another tensor, so the stem's tensor was dead by then (liveness pass)
+        bool ok = true, recycled = false;
+        auto visit = [&](const Step& u) {
+            if (recycled || !ok) return;
+            if (u.in.buf == c.out.buf || (u.has_in2 && u.in2.buf == c.out.buf)) ok = false;
+            else if (u.out.buf == c.out.buf) recycled = true;
         };
-        auto layer_at = [&](size_t i) {
-            if (i + 1 >= plan.steps.size()) return false;
-            const Step& s1 = plan.steps[i];
-            const Step& s3 = plan.steps[i + 1];
-            if (s1.kind != StepKind::Conv || s3.kind != StepKind::Conv || !s1.parts.empty() || !s3.parts.empty()) return false;
-            if (IsGroupConv(s1.algo) || IsGroupConv(s3.algo)) return false;
-            if (s1.kh != 1 || s1.kw != 1 || s1.sh != 1 || s1.sw != 1 || s1.pt || s1.pl || s1.pb || s1.pr || s1.has_in2 || s1.out.c != 128) return false;
-            if (s3.kh != 3 || s3.kw != 3 || s3.sh != 1 || s3.sw != 1 || s3.pt != 1 || s3.pl != 1 || s3.pb != 1 || s3.pr != 1 || s3.has_in2 || s3.out.c != 32) return false;
-            if (s3.dh != 1 || s3.dw != 1) return false;
-            if (s3.pre_scale_off >= 0 || s1.w_off < 0 || s3.w_off < 0) return false;
-            if (!s1.in.f16 || !s1.out.f16 || !s3.out.f16 || s1.in.nchw || s1.out.nchw || s3.out.nchw) return false;
-            if (!same_view(s3.in, s1.out) || s3.out.buf != s1.in.buf || s3.out.pitch != s1.in.pitch || s1.out.buf == s1.in.buf) return false;
-            if (s3.out.n != s1.in.n || s3.out.h != s1.in.h || s3.out.w != s1.in.w) return false;
-            if (s1.in.c < 64 || s1.in.c % 32 || s1.in.pitch % 8 || s1.in.c_off % 8 || s3.out.c_off % 8) return false;
-            if (s3.out.c_off < s1.in.c_off + s1.in.c && s3.out.c_off + 32 > s1.in.c_off) return false;
-            if ((s1.pre_scale_off >= 0) != (s1.pre_shift_off >= 0)) return false;
-            // up to 7 raster tiles: a workgroup per image (chains of layers); larger maps: bands of rows, one layer per launch, while at least one
-            // row + halo fits the 8 staged tiles
-            // Band mode measured no faster than the two streaming kernels at batch 128 (28x28: 39-58 vs 42-54 us per layer; 56x56: 160-218 vs 93-123 us:
-            // the per-band fixed cost -- 72 KB of 3x3 weights into LDS, raster reset, epilogue -- is paid 5 ... 28 times per image), so such steps are
-            // only formed on request (IE_DENSE_BAND=1: tests, experiments).
-            const int64_t ntiles = (s1.in.h * (s1.in.w + 1) + 31) / 32;
-            if (ntiles > 7 && (!env.flag("IE_DENSE_BAND") || (s1.in.w + 1 > 64 && 256 / (s1.in.w + 1) < 3))) return false;
-            // T must have no other reader: the fused kernel never writes it to memory
-            for (size_t j = i + 2; j < plan.steps.size(); ++j) {
-                const Step& q = plan.steps[j];
-                if (q.in.buf == s1.out.buf || (q.has_in2 && q.in2.buf == s1.out.buf)) return false;
-                if (q.out.buf == s1.out.buf) break;                // the buffer was recycled for another tensor: T was dead by then (liveness pass)
-            }
-            for (size_t o = 0; o < out_vals.size(); ++o) if (view_of(out_vals[o]).buf == s1.out.buf) return false;
-            return true;
-        };
-        std::vector<Step> blocksteps;
-        for (size_t i = 0; i < plan.steps.size();) {
-            size_t n = 0;
-            while (n < 24 && layer_at(i + 2 * n)) {
-                if (n > 0) {
-                    if ((plan.steps[i].in.h * (plan.steps[i].in.w + 1) + 31) / 32 > 7) break;       // band mode: one layer per launch
-                    const Step& f1 = plan.steps[i], &c1 = plan.steps[i + 2 * n], &p3 = plan.steps[i + 2 * n - 1];
-                    if (c1.in.buf != f1.in.buf || c1.in.pitch != f1.in.pitch || c1.in.c_off != f1.in.c_off || c1.in.n != f1.in.n || c1.in.h != f1.in.h || c1.in.w != f1.in.w)
-                        break;
-                    // a layer's first 192 input channels are requested while the previous layer's 3x3 still runs: they must not be its output
-                    if (p3.out.c_off < c1.in.c_off + 192 && p3.out.c_off + 32 > c1.in.c_off) break;
-                }
-                ++n;
-            }
-            if (n == 0) { blocksteps.push_back(plan.steps[i]); ++i; continue; }
-            Step f = plan.steps[i];
-            f.algo = ConvAlgo::DenseBlock;
-            f.tile = 1;
-            f.splitk = 1;
-            f.flops = 0;
-            f.bytes = 0;
-            f.parts.clear();
-            for (size_t q = 0; q < 2 * n; ++q) {
-                const Step& ps = plan.steps[i + q];
-                f.parts.push_back(ps);
-                f.flops += ps.flops;
-                f.bytes += ps.bytes;       // SURVEY §8d's per-conv accounting (the bottleneck tensor's write + read is in it although it stays on-chip here)
-            }
-            f.name = plan.steps[i].name + " ... " + plan.steps[i + 2 * n - 1].name;
-            f.out = plan.steps[i + 2 * n - 1].out;             // what the step leaves in memory last (every part's slice is produced by this step)
-            blocksteps.push_back(std::move(f));
-            i += 2 * n;
+        for (size_t q = i + 2; q < plan.steps.size() && ok && !recycled; ++q) {
+            const Step& t = plan.steps[q];
+            if (t.parts.empty()) visit(t);
+            else for (const Step& tp : t.parts) visit(tp);
         }
-        if (blocksteps.size() != plan.steps.size()) {
-            std::vector<int> remap(plan.steps.size(), -1);
-            for (size_t k = 0; k < blocksteps.size(); ++k) {
-                if (blocksteps[k].algo == ConvAlgo::DenseBlock) for (const Step& q : blocksteps[k].parts) remap[size_t(q.idx)] = int(k);
-                else remap[size_t(blocksteps[k].idx)] = int(k);
-            }
-            for (size_t k = 0; k < blocksteps.size(); ++k) {
-                Step& st = blocksteps[k];
-                st.idx = int(k);
-                if (st.in_src >= 0) st.in_src = remap[size_t(st.in_src)];
-                if (st.in2_src >= 0) st.in2_src = remap[size_t(st.in2_src)];
-            }
-            plan.steps = std::move(blocksteps);
+        if (!ok || output_in_buffer(c.out.buf)) continue;
+        Step f = c;
+        f.algo = ConvAlgo::StemPool;
+        f.tile = 1;
+        f.out = pl.out;
+        f.name = c.name + " + " + pl.name;
+        f.flops = c.flops + pl.flops;
+        f.bytes = double(c.in.numel()) * c.in.esize() + double(pl.out.numel()) * pl.out.esize() + double(c.out.c) * c.kh * c.kw * c.in.c * 4;
+        f.parts = {c, pl};
+        std::vector<Step> ns;
+        ns.reserve(plan.steps.size() - 1);
+        for (size_t q = 0; q < plan.steps.size(); ++q) {
+            if (q == i + 1) continue;
+            ns.push_back(q == i ? f : plan.steps[q]);
         }
+        auto remap = [&](int src) { return src < 0 ? src : (size_t(src) > i ? src - 1 : src); };     // i + 1 -> i, everything behind moves up
+        for (size_t q = 0; q < ns.size(); ++q) {
+            Step& st = ns[q];
+            st.idx = int(q);
+            st.in_src = remap(st.in_src);
+            st.in2_src = remap(st.in2_src);
+            for (Step& part : st.parts) { part.in_src = remap(part.in_src); part.in2_src = remap(part.in2_src); }
+        }
+        // run as two launches, the parts share the fused step's slot: one tensor scale (a max pool keeps its operand's), same producer index
+        ns[i].parts[0].idx = int(i);
+        ns[i].parts[1].idx = int(i);
+        ns[i].parts[1].in_src = int(i);
+        plan.steps = std::move(ns);
+        break;                                // one stem per graph
     }
+}
 
-    // ---- stem + max pool: the 7x7/s2 stem conv and the 3x3/s2/p1 max pool behind it -> ONE step -------------------------------------
-    // Pattern: step i = the stem conv (algo Stem, ReLU'd), step i + 1 = a max pool 3x3 / stride 2 / pad 1 without a prologue that
-    // reads exactly step i's output, which nothing else reads.  conv_stem_kernel<POOL> (kernels_stem.hip) pools the conv tile in LDS: the tensor
-    // between the two ops (the largest of DenseNet / ResNet) is never written.  parts = {conv, pool}; tile 1 = fused, 0 = the two launches.
-    if (!env.get("IE_NO_STEM_POOL")) {
-        for (size_t i = 0; i + 1 < plan.steps.size(); ++i) {
-            const Step& c = plan.steps[i];
-            const Step& pl = plan.steps[i + 1];
-            if (c.kind != StepKind::Conv || c.algo != ConvAlgo::Stem || !c.relu || c.has_in2 || !c.parts.empty() || c.out.nchw || c.out.c > 64 || c.out.c % 8) continue;
-            if (pl.kind != StepKind::Pool || !pl.pool_max || pl.kh != 3 || pl.kw != 3 || pl.sh != 2 || pl.sw != 2 || pl.pt != 1 || pl.pl != 1 || pl.pb > 1 || pl.pr > 1) continue;
-            if (pl.pre_scale_off >= 0 || pl.pre_relu || pl.has_in2 || pl.in_src != int(i)) continue;
-            if (pl.in.buf != c.out.buf || pl.in.c_off != c.out.c_off || pl.in.c != c.out.c || pl.in.pitch != c.out.pitch || pl.in.h != c.out.h || pl.in.w != c.out.w) continue;
-            if (pl.out.f16 != c.out.f16 || pl.out.f8 != c.out.f8 || pl.out.nchw || pl.out.buf == c.out.buf || pl.out.buf == c.in.buf) continue;
-            if (pl.out.h != (c.out.h + 2 - 3) / 2 + 1 || pl.out.w != (c.out.w + 2 - 3) / 2 + 1) continue;
-            if (pl.out.pitch % 8 || pl.out.c_off % 8 || (pl.out.f8 && (pl.out.pitch % 16 || pl.out.c_off % 16))) continue;
-            // the conv's output must have no other reader: walk the launches behind the pool in execution order (a fused step = its parts) until the
-            // buffer is written again -- recycled for another tensor, so the stem's tensor was dead by then (liveness pass)
-            bool ok = true, recycled = false;
-            auto visit = [&](const Step& u) {
-                if (recycled || !ok) return;
-                if (u.in.buf == c.out.buf || (u.has_in2 && u.in2.buf == c.out.buf)) ok = false;
-                else if (u.out.buf == c.out.buf) recycled = true;
-            };
-            for (size_t q = i + 2; q < plan.steps.size() && ok && !recycled; ++q) {
-                const Step& t = plan.steps[q];
-                if (t.parts.empty()) visit(t);
-                else for (const Step& tp : t.parts) visit(tp);
-            }
-            for (size_t o = 0; o < out_vals.size() && ok; ++o) if (view_of(out_vals[o]).buf == c.out.buf) ok = false;
-            if (!ok) continue;
-            Step f = c;
-            f.algo = ConvAlgo::StemPool;
-            f.tile = 1;
-            f.out = pl.out;
-            f.name = c.name + " + " + pl.name;
-            f.flops = c.flops + pl.flops;
-            f.bytes = double(c.in.numel()) * c.in.esize() + double(pl.out.numel()) * pl.out.esize() + double(c.out.c) * c.kh * c.kw * c.in.c * 4;
-            f.parts = {c, pl};
-            std::vector<Step> ns;
-            ns.reserve(plan.steps.size() - 1);
-            for (size_t q = 0; q < plan.steps.size(); ++q) {
-                if (q == i + 1) continue;
-                ns.push_back(q == i ? f : plan.steps[q]);
-            }
-            auto remap = [&](int src) { return src < 0 ? src : (size_t(src) > i ? src - 1 : src); };     // i + 1 -> i, everything behind moves up
-            for (size_t q = 0; q < ns.size(); ++q) {
-                Step& st = ns[q];
-                st.idx = int(q);
-                st.in_src = remap(st.in_src);
-                st.in2_src = remap(st.in2_src);
-                for (Step& part : st.parts) { part.in_src = remap(part.in_src); part.in2_src = remap(part.in2_src); }
-            }
-            // run as two launches, the parts share the fused step's slot: one tensor scale (a max pool keeps its operand's), same producer index
-            ns[i].parts[0].idx = int(i);
-            ns[i].parts[1].idx = int(i);
-            ns[i].parts[1].in_src = int(i);
-            plan.steps = std::move(ns);
-            break;                                // one stem per graph
+// ---- projection shortcuts (fp8): conv3 + residual where the residual is a 1x1 projection conv -> ONE step of two GEMMs ------------------------
+// Pattern: step j = 1x1/s1 conv C with a fused residual whose producer is step i < j = a plain 1x1 conv P (any stride, no prologue, no
+// residual, no ReLU) read by nothing else.  out = relu(C(a) + P(x)) then runs as two accumulator sets of one launch (kernels_ws8.hip) and
+// P's output -- the largest tensor of the block -- is never written.  P moves down to C's position (everything between them is independent
+// of P's output: its only reader is C).
+void Planner::FuseDualF8() {
+    for (size_t j = 0; j < plan.steps.size(); ++j) {
+        Step& c = plan.steps[j];
+        if (c.kind != StepKind::Conv || !c.has_in2 || !c.parts.empty() || c.kh != 1 || c.kw != 1 || c.sh != 1 || c.sw != 1 || c.pt || c.pl || c.pb || c.pr) continue;
+        if (c.pre_scale_off >= 0 || c.in.nchw || c.out.nchw || c.in.c % 32 || c.out.c % 32 || c.in2_src < 0 || size_t(c.in2_src) >= j) continue;
+        const size_t i = size_t(c.in2_src);
+        const Step& pr = plan.steps[i];
+        if (pr.kind != StepKind::Conv || !pr.parts.empty() || pr.has_in2 || pr.relu || pr.pre_scale_off >= 0 || pr.kh != 1 || pr.kw != 1 || pr.pt || pr.pl || pr.pb || pr.pr) continue;
+        if (pr.in.nchw || pr.in.c % 32 || pr.out.buf != c.in2.buf || pr.out.c_off != c.in2.c_off || pr.out.c != c.in2.c || pr.out.pitch != c.in2.pitch) continue;
+        if (pr.out.n != c.out.n || pr.out.h != c.out.h || pr.out.w != c.out.w || pr.out.c != c.out.c) continue;
+        if (precision == Precision::F8 && (!pr.in.f8 || !c.in.f8 || !c.out.f8)) continue;
+        if (pr.in.buf == c.out.buf || pr.out.buf == c.out.buf) continue;
+        // P's output must have no other reader, and P's INPUT must still hold its value at C's position (not recycled in between)
+        bool ok = true;
+        for (size_t q = i + 1; q < plan.steps.size() && ok; ++q) {
+            const Step& t = plan.steps[q];
+            if (q != j && (t.in.buf == pr.out.buf || (t.has_in2 && t.in2.buf == pr.out.buf))) ok = false;
+            if (q > j && t.out.buf == pr.out.buf) break;
         }
-    }
-
-    // ---- projection shortcuts (fp8): conv3 + residual where the residual is a 1x1 projection conv -> ONE step of two GEMMs ------------------------
-    // Pattern: step j = 1x1/s1 conv C with a fused residual whose producer is step i < j = a plain 1x1 conv P (any stride, no prologue, no
-    // residual, no ReLU) read by nothing else.  out = relu(C(a) + P(x)) then runs as two accumulator sets of one launch (kernels_ws8.hip) and
-    // P's output -- the largest tensor of the block -- is never written.  P moves down to C's position (everything between them is independent
-    // of P's output: its only reader is C).
-    if ((precision == Precision::F8 || f8_fusions) && !env.get("IE_NO_DUAL_F8")) {
-        for (size_t j = 0; j < plan.steps.size(); ++j) {
-            Step& c = plan.steps[j];
-            if (c.kind != StepKind::Conv || !c.has_in2 || !c.parts.empty() || c.kh != 1 || c.kw != 1 || c.sh != 1 || c.sw != 1 || c.pt || c.pl || c.pb || c.pr) continue;
-            if (c.pre_scale_off >= 0 || c.in.nchw || c.out.nchw || c.in.c % 32 || c.out.c % 32 || c.in2_src < 0 || size_t(c.in2_src) >= j) continue;
-            const size_t i = size_t(c.in2_src);
-            const Step& pr = plan.steps[i];
-            if (pr.kind != StepKind::Conv || !pr.parts.empty() || pr.has_in2 || pr.relu || pr.pre_scale_off >= 0 || pr.kh != 1 || pr.kw != 1 || pr.pt || pr.pl || pr.pb || pr.pr) continue;
-            if (pr.in.nchw || pr.in.c % 32 || pr.out.buf != c.in2.buf || pr.out.c_off != c.in2.c_off || pr.out.c != c.in2.c || pr.out.pitch != c.in2.pitch) continue;
-            if (pr.out.n != c.out.n || pr.out.h != c.out.h || pr.out.w != c.out.w || pr.out.c != c.out.c) continue;
-            if (precision == Precision::F8 && (!pr.in.f8 || !c.in.f8 || !c.out.f8)) continue;
-            if (pr.in.buf == c.out.buf || pr.out.buf == c.out.buf) continue;
-            // P's output must have no other reader, and P's INPUT must still hold its value at C's position (not recycled in between)
-            bool ok = true;
-            for (size_t q = i + 1; q < plan.steps.size() && ok; ++q) {
-                const Step& t = plan.steps[q];
-                if (q != j && (t.in.buf == pr.out.buf || (t.has_in2 && t.in2.buf == pr.out.buf))) ok = false;
-                if (q > j && t.out.buf == pr.out.buf) break;
-            }
-            for (size_t q = i + 1; q < j && ok; ++q)
-                if (plan.steps[q].out.buf == pr.in.buf) ok = false;
-            for (size_t o = 0; o < out_vals.size() && ok; ++o) if (view_of(out_vals[o]).buf == pr.out.buf) ok = false;
-            if (!ok) continue;
-            Step f = c;
-            f.algo = ConvAlgo::DualF8;
-            f.tile = 1;
-            f.splitk = 1;
-            f.has_in2 = false;
-            f.in2 = View();
-            f.in2_src = -1;
-            f.name = pr.name + " (+) " + c.name;
-            f.flops = pr.flops + c.flops;
-            f.bytes = pr.bytes + c.bytes;
-            f.parts = {pr, c};
-            // steps i+1 .. j-1 move up by one, the fused step takes position j - 1 ... simpler: erase i, replace j (indices above i shift by -1)
-            std::vector<Step> ns;
-            ns.reserve(plan.steps.size() - 1);
-            for (size_t q = 0; q < plan.steps.size(); ++q) {
-                if (q == i) continue;
-                ns.push_back(q == j ? f : plan.steps[q]);
-            }
-            auto remap = [&](int src) { return src < 0 ? src : (size_t(src) == i ? int(j) - 1 : (size_t(src) > i ? src - 1 : src)); };
-            for (size_t q = 0; q < ns.size(); ++q) {
-                Step& st = ns[q];
-                st.idx = int(q);
-                st.in_src = remap(st.in_src);
-                st.in2_src = remap(st.in2_src);
-                for (Step& part : st.parts) { part.in_src = remap(part.in_src); part.in2_src = remap(part.in2_src); }
-            }
-            // inside the fused step: the last conv's shortcut comes from the projection part (no plan step of its own any more)
-            ns[j - 1].parts[1].in2_src = -1;
-            plan.steps = std::move(ns);
-            --j;
+        for (size_t q = i + 1; q < j && ok; ++q)
+            if (plan.steps[q].out.buf == pr.in.buf) ok = false;
+        if (!ok || output_in_buffer(pr.out.buf)) continue;
+        Step f = c;
+        f.algo = ConvAlgo::DualF8;
+        f.tile = 1;
+        f.splitk = 1;
+        f.has_in2 = false;
+        f.in2 = View();
+        f.in2_src = -1;
+        f.name = pr.name + " (+) " + c.name;
+        f.flops = pr.flops + c.flops;
+        f.bytes = pr.bytes + c.bytes;
+        f.parts = {pr, c};
+        // steps i+1 .. j-1 move up by one, the fused step takes position j - 1 ... simpler: erase i, replace j (indices above i shift by -1)
+        std::vector<Step> ns;
+        ns.reserve(plan.steps.size() - 1);
+        for (size_t q = 0; q < plan.steps.size(); ++q) {
+            if (q == i) continue;
+            ns.push_back(q == j ? f : plan.steps[q]);
         }
+        auto remap = [&](int src) { return src < 0 ? src : (size_t(src) == i ? int(j) - 1 : (size_t(src) > i ? src - 1 : src)); };
+        for (size_t q = 0; q < ns.size(); ++q) {
+            Step& st = ns[q];
+            st.idx = int(q);
+            st.in_src = remap(st.in_src);
+            st.in2_src = remap(st.in2_src);
+            for (Step& part : st.parts) { part.in_src = remap(part.in_src); part.in2_src = remap(part.in2_src); }
+        }
+        // inside the fused step: the last conv's shortcut comes from the projection part (no plan step of its own any more)
+        ns[j - 1].parts[1].in2_src = -1;
+        plan.steps = std::move(ns);
+        --j;
     }
+}
 
-    // ---- I/O descriptors ---------------------------------------------------------------------------
+// ---- I/O descriptors ---------------------------------------------------------------------------
+void Planner::DescribeIo() {
     for (size_t i = 0; i < m.inputs.size(); ++i) {
         IoDesc d;
         d.name = m.inputs[i].name;
@@ -2045,7 +2247,52 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
             fail("internal planner error: output " + d.name + " is not dense");
         plan.outputs.push_back(d);
     }
-    return plan;
+}
+
+// The passes in the order they run.  Their order, the order in which they append to the weight blob and the order of their checks are
+// behaviour: the blob layout and which error a bad graph reports first follow from them (tests/test_plan_digests.py pins both).
+Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& input_shapes, Precision precision, bool f8_fusions) {
+    const Env env = Env::Read();          // the planner's switches, read once per plan build (load / prepare time)
+    Planner P(m, input_shapes, env, precision, f8_fusions);
+    const bool f8 = precision == Precision::F8 || f8_fusions;
+    const bool forced = env.get("IE_FORCE_ALGO") || env.get("IE_FORCE_TILE");
+
+    // ---- ONNX graph -> logical nodes with shape inference ----
+    P.ImportInputs();
+    for (const OnnxNode& on : m.nodes) P.ImportNode(on);
+    P.MarkOutputs();
+    if (f8) P.RefuseForF8();
+
+    // ---- graph-level fusions ----
+    P.FuseActivationPatterns();                                  // Mul(x, Sigmoid(x)) -> SiLU, Mul(x, HardSigmoid(x)) -> hardswish
+    if (!env.get("IE_NO_SE_FUSE")) P.FuseSqueezeExcite();        // pool -> 1x1 -> act -> 1x1 -> act -> Mul as one node
+    P.MergeAffineChains();                                       // fusion 1: Affine -> Affine
+    P.FuseConvEpilogues();                                       // fusion 2: Conv -> Affine / ReLU / Add / Clip / activation
+    P.FuseRelu6IntoDepthwise();                                  // fusion 2b
+    P.FuseActivationPrologues();                                 // fusion 2d
+    if (!env.get("IE_NO_POOL_SWAP")) P.SwapConvAndAvgPool();     // fusion 2c: Conv1x1 -> AveragePool => AveragePool -> Conv1x1
+    P.FusePrologues();                                           // fusion 3: Affine -> Relu -> {Conv, GlobalAveragePool, swapped AveragePool}
+    P.FuseTrailingRelu();                                        // fusion 4: Add -> Relu, Affine -> Relu
+
+    // ---- where every value lives ----
+    P.StageNchwInputs();
+    P.DensifyOutputs();
+    P.PlaceConcatsAndAliases();
+    P.ComputeLiveness();
+    if (precision == Precision::F32 && !env.get("IE_NO_DENSE_FUSE")) P.KeepDenseFusionInputsLive();
+    P.AssignBuffers();
+    P.MarkBufferTypes();
+
+    // ---- one step per live node, the kernel choice of every conv ----
+    P.EmitSteps();
+
+    // ---- step-level fusions, I/O descriptors ----
+    if (precision == Precision::F32 && !env.get("IE_NO_DENSE_FUSE") && !forced) P.FuseDenseLayers();
+    if (precision == Precision::F16 && !env.get("IE_NO_DENSE_BLOCK") && !forced) P.FuseDenseBlocks();
+    if (!env.get("IE_NO_STEM_POOL")) P.FuseStemPool();
+    if (f8 && !env.get("IE_NO_DUAL_F8")) P.FuseDualF8();
+    P.DescribeIo();
+    return std::move(P.plan);
 }
 
 static void json_view(std::ostringstream& o, const View& v) {

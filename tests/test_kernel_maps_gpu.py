@@ -39,7 +39,7 @@ def build(case):
 # ---------------------------------------------------------------------------------------------------------------------
 # case tables.  Every family has: a ragged last pixel block and a pixel block that straddles two images (N >= 2, H * W not a multiple
 # of 16), the family's smallest K and one near its largest, Cout of one channel block and of several, and the prologue / bias / BN /
-# ReLU variants the family supports (plan.cpp, the *_ok lambdas).
+# ReLU variants the family supports (plan.cpp, ConvFacts::*_ok).
 # ---------------------------------------------------------------------------------------------------------------------
 IGEMM32 = [C(1, 2, 9, 7, 4, 5, pre=1, bias=1, post=1), C(2, 3, 7, 11, 96, 40, k=3, p=1, post=2), C(3, 2, 13, 10, 20, 130, k=5, s=2, p=2, bias=1),
            C(4, 2, 11, 9, 64, 64, k=3, s=2, pre=1, post=3), C(5, 1, 6, 5, 256, 32, k=3, p=1, bias=1, post=1)]
