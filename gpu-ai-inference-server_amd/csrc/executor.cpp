@@ -132,6 +132,7 @@ constexpr TuneFamily kTuneFamilies[] = {
     {300, ConvAlgo::Ws3x3, kNumConvWs3Tiles},         {400, ConvAlgo::Direct, kNumConvDirectTiles},
     {500, ConvAlgo::Wino3x3, kNumConvWinoTiles},      {600, ConvAlgo::X6, kNumConvX6Tiles},
     {700, ConvAlgo::Depthwise, kNumConvDwTiles},      {800, ConvAlgo::Grouped, kNumConvGroupedTiles},
+    {900, ConvAlgo::Transposed, kNumConvtTiles},
 };
 
 const TuneFamily& tune_family(int code) {
@@ -1010,6 +1011,25 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
         ctx.store(key, tune_code(ConvAlgo::Grouped, best_t), 1);
         return;
     }
+    if (s.algo == ConvAlgo::Transposed) {
+        // the generic kernel and the MFMA variants of the non-overlapping case (tune-file codes 900 + tile); nothing else may run a transposed conv
+        const std::vector<int64_t> key = {s.in.n * s.in.h * s.in.w, s.out.c, s.in.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.pb, s.pr, s.oph, s.opw, s.in.h, s.in.w,
+                                          s.in.pitch, s.out.pitch, s.in.nchw ? 2 : int64_t(s.in.f16), int64_t(ConvAlgo::Transposed), s.bias_off >= 0};
+        if (ctx.lookup(key, &hit)) {
+            if (tune_family(hit.first).algo == ConvAlgo::Transposed) s.tile = hit.first - tune_family(hit.first).base;
+            return;
+        }
+        if (!ctx.allow_search) return;
+        const ConvtArgs a = MakeConvtArgs(pi, s);
+        float best = 1e30f;
+        int best_t = s.tile;
+        for (int t = 0; t < kNumConvtTiles; ++t)
+            if (ConvTransposedEligible(a, t))
+                if (const float ms = time_tile(t); ms < best) { best = ms; best_t = t; }
+        s.tile = best_t;
+        ctx.store(key, tune_code(ConvAlgo::Transposed, best_t), 1);
+        return;
+    }
     const int64_t M = s.out.n * s.out.h * s.out.w, N = s.out.c;
     if (s.algo == ConvAlgo::IgemmF8) {
         // fp8 convs: the tiled implicit GEMM's tiles, then the weights-stationary 1x1 kernel's, then the 3x3's
@@ -1308,6 +1328,18 @@ GroupedArgs DeviceModel::MakeGroupedArgs(const PlanInstance& pi, const Step& s) 
     return a;
 }
 
+ConvtArgs DeviceModel::MakeConvtArgs(const PlanInstance& pi, const Step& s) const {
+    ConvtArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    a.w = s.w_off >= 0 ? w_->d_weights + s.w_off : nullptr;
+    a.w16 = w_->d_weights16 && s.w_off >= 0 ? static_cast<const char*>(w_->d_weights16) + s.w_off * 2 : nullptr;
+    a.bias = s.bias_off >= 0 ? w_->d_weights + s.bias_off : nullptr;
+    a.kh = s.kh; a.kw = s.kw; a.sh = s.sh; a.sw = s.sw; a.pt = s.pt; a.pl = s.pl; a.pb = s.pb; a.pr = s.pr; a.oph = s.oph; a.opw = s.opw;
+    a.relu = s.relu;
+    return a;
+}
+
 SeArgs DeviceModel::MakeSeArgs(const PlanInstance& pi, const Step& s) const {
     const float* wb = w_->d_weights;
     auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
@@ -1343,6 +1375,8 @@ const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Ste
             return with_tile(ConvDwEligible(MakeDwArgs(pi, s), s.tile) ? s.tile : 0);
         case ConvAlgo::Grouped:         // the generic kernel takes every grouped conv
             return with_tile(ConvGroupedEligible(MakeGroupedArgs(pi, s), s.tile) ? s.tile : 0);
+        case ConvAlgo::Transposed:      // the generic kernel takes every transposed conv
+            return with_tile(ConvTransposedEligible(MakeConvtArgs(pi, s), s.tile) ? s.tile : 0);
         case ConvAlgo::StemPool:        // tile 0: the two plain steps
             return with_tile(s.tile != 0 && ConvStemPoolEligible(MakeConvArgs(pi, s)) ? s.tile : 0);
         case ConvAlgo::DenseBlock: {    // tile 0: the 2n plain steps
@@ -1418,6 +1452,11 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             }
             if (s.algo == ConvAlgo::Grouped) {
                 check(LaunchConvGrouped(MakeGroupedArgs(pi, s), s.tile, stream_), "conv_grouped");
+                break;
+            }
+            if (s.algo == ConvAlgo::Transposed) {
+                if (s.has_in2 || s.pre_scale_off >= 0) throw std::runtime_error("internal error: transposed conv " + s.name + " with a prologue or a residual");
+                check(LaunchConvTransposed(MakeConvtArgs(pi, s), s.tile, stream_), "conv_transposed");
                 break;
             }
             if (s.algo == ConvAlgo::StemPool) {
@@ -1569,6 +1608,9 @@ static std::string kernel_label(const Step& s) {
                 return std::string("conv_grouped_kernel<") + (s.out.f16 ? "f16,c" : "f32,c") + std::to_string(c.cpg) + ",o" + std::to_string(c.opb) + "x" +
                        std::to_string(c.gpb) + ",px" + std::to_string(kGroupedPx[s.tile]) + ">";
             }
+            if (s.algo == ConvAlgo::Transposed)
+                return s.tile == 0 ? std::string("convt_generic_kernel")
+                                   : std::string("convt_phase_kernel<") + (s.out.f16 ? "f16,px" : "f32,px") + std::to_string(32 * kConvtPixelBlocks[s.tile]) + ">";
             if (s.algo == ConvAlgo::DenseBlock) return s.tile != 0 ? "dense_block_f16_kernel<" + std::to_string(s.parts.size() / 2) + " layers>" : "dense_block_parts<" + std::to_string(s.parts.size()) + " launches>";
             if (s.algo == ConvAlgo::DenseFused && s.tile == 0) return "dense_fused_parts<2 launches>";
             if (s.algo == ConvAlgo::DenseFused) return (s.tile >= 4 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";

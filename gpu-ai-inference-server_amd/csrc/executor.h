@@ -187,6 +187,7 @@ private:
     ConvArgs MakeConvArgs(const PlanInstance& pi, const Step& s) const;
     DwArgs MakeDwArgs(const PlanInstance& pi, const Step& s) const;
     GroupedArgs MakeGroupedArgs(const PlanInstance& pi, const Step& s) const;
+    ConvtArgs MakeConvtArgs(const PlanInstance& pi, const Step& s) const;
     SeArgs MakeSeArgs(const PlanInstance& pi, const Step& s) const;
     bool MakeBlockArgs(const PlanInstance& pi, const Step& s, DenseBlockArgs* out) const;   // false: the step is not a well-formed dense-block chain
 

@@ -165,6 +165,26 @@ constexpr bool GroupedTileFits(int cfg, bool f16, int tile) {
 bool ConvGroupedEligible(const GroupedArgs& a, int tile);
 hipError_t LaunchConvGrouped(const GroupedArgs& a, int tile, hipStream_t stream);
 
+// Transposed conv (ONNX ConvTranspose, group 1, no dilation; kernels_convt.hip): out[n, iy*sh + ky - pt, ix*sw + kx - pl, o] += sum_c in[n, iy, ix, c] *
+// w[ky][kx][o][c]; output rows / columns the pads cut off are dropped, the output_padding rows / columns at the bottom / right receive the bias
+// only.  Epilogue: + bias, ReLU.  fp32 accumulation; activations float or half (TensorArg::f16), bias fp32.
+struct ConvtArgs {
+    TensorArg in, out;                 // out NHWC (sc == 1) of extent (in.h - 1) * sh + kh - pt - pb + output_padding
+    const float* w = nullptr;          // [kh][kw][Cout][Cin] (BatchNorm folded)
+    const void* w16 = nullptr;         // the same weights as halfs at the same element offsets (fp16 plans), or null
+    const float* bias = nullptr;       // [Cout] or null
+    int kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0, pb = 0, pr = 0, oph = 0, opw = 0;
+    int relu = 0;
+};
+// tile 0: generic (one output element per thread in gather form; any k, stride, pads, output_padding, channel counts, NCHW input, mixed element
+// types); tiles 1-2: the MFMA kernel of the non-overlapping case (kh == sh, kw == sw, no pads, no output_padding, kh * kw <= 16) with 32 / 64
+// input pixels per wave: NHWC operands of one element type, Cin a multiple of the K-step (8 floats / 16 halfs), 16-byte aligned input pixel rows
+// and weights.  Cout and pixel tails are masked
+constexpr int kNumConvtTiles = 3;
+inline constexpr int kConvtPixelBlocks[kNumConvtTiles] = {0, 1, 2};      // 32-pixel MFMA row blocks per wave
+bool ConvTransposedEligible(const ConvtArgs& a, int tile);
+hipError_t LaunchConvTransposed(const ConvtArgs& a, int tile, hipStream_t stream);
+
 // Squeeze-and-excitation block (kernels_se.hip): out = in * gate[n, c], gate = act(W2^T-packed FC(act1(W1 * mean_hw(in) + b1)) + b2).
 // Three phases, four launches: squeeze (fp32 partial sums per pixel chunk), fc1 (means + FC1 + act1 -> hidden [N][mid]), fc2 (FC2 + act -> gate [N][C]),
 // apply.  Deterministic (fixed summation orders, no atomics).  The workspace holds chunks * N * C partials, N * mid hidden values and the N * C gate.

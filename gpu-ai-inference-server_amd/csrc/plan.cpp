@@ -64,6 +64,8 @@ struct LNode {
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
     bool dw = false;                    // depthwise conv (group == Cin == Cout): w packed [C][kh][kw]
     int64_t group = 1;                  // conv: the ONNX group count (> 1 and not dw: a grouped conv, w packed [Cout][kh][kw][Cin / group])
+    bool transposed = false;            // ConvTranspose: w packed [kh][kw][Cout][Cin]; no dense-conv pass may take it
+    int op_h = 0, op_w = 0;             // ConvTranspose: output_padding
     float lo = -kInf, hi = kInf;        // Clip bounds (L_CLIP; a depthwise conv's epilogue clamp)
     float pre_hi = kInf;                // depthwise conv: upper bound of the prologue
     Act act;                            // L_ACT; a depthwise conv's epilogue activation; L_SE: the gate's
@@ -221,6 +223,22 @@ int GroupedDefaultTile(const Step& s) {
     return GroupedFastViews(s, 1) ? 1 : 0;
 }
 
+// Transposed steps: what the MFMA kernel of the non-overlapping case needs (kernels_convt.hip ConvTransposedEligible re-checks it with the
+// pointers): k == stride with no pads and no output_padding, so every output pixel receives exactly one tap; at most 16 taps; NHWC operands of
+// the plan's element type with Cin a multiple of the K-step (8 floats / 16 halfs) and 16-byte aligned input pixel rows
+bool ConvtFastViews(const Step& s) {
+    const int64_t KS = s.out.f16 ? 16 : 8, V = s.out.f16 ? 8 : 4;
+    return s.kh == s.sh && s.kw == s.sw && !s.pt && !s.pl && !s.pb && !s.pr && !s.oph && !s.opw && s.kh * s.kw <= 16 && !s.in.nchw && !s.out.nchw &&
+           s.in.f16 == s.out.f16 && !s.in.f8 && !s.out.f8 && s.in.c % KS == 0 && s.in.pitch % V == 0 && s.in.c_off % V == 0;
+}
+// 64 input pixels per wave reuse every weight fragment twice; 32 where that would leave the 256 CUs short of waves (one wave per
+// 32-channel block, pixel block and group of four taps)
+int ConvtDefaultTile(const Step& s) {
+    if (!ConvtFastViews(s)) return 0;
+    const int64_t M = s.in.n * s.in.h * s.in.w, waves64 = ((M + 63) / 64) * ((s.out.c + 31) / 32) * ((s.kh * s.kw + 3) / 4);
+    return waves64 >= 2048 ? 2 : 1;
+}
+
 // Algorithmic FLOPs per element of a fused activation
 double ActFlops(ActKind k) {
     switch (k) {
@@ -317,6 +335,7 @@ struct Planner {
     bool FoldShapeArithmetic(const OnnxNode& on, const LNode& n);
     bool FoldShapeOnlyOp(const OnnxNode& on, const LNode& n);
     void ImportConv(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportConvTranspose(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportBatchNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
@@ -352,6 +371,7 @@ struct Planner {
     void EmitConcatCopies(const LNode& n);
     void EmitConv(const LNode& n, Step& s);
     void EmitGroupConv(const LNode& n, Step& s);
+    void EmitTransposedConv(const LNode& n, Step& s);
     void ChooseBaseAlgo(const ConvFacts& f, Step& s) const;
     void ForceTileF8(const ConvFacts& f, Step& s) const;
     void ApplyForcedAlgo(const ConvFacts& f, Step& s) const;
@@ -662,6 +682,64 @@ void Planner::ImportConv(const OnnxNode& on, LNode& n, std::vector<int64_t>& odi
     }
     int64_t oh, ow;
     conv_out_hw(X.h, X.w, n, false, oh, ow);
+    n.in = {x};
+    odims = {X.n, co, oh, ow};
+}
+
+// ConvTranspose: out[n, o, iy * sh + ky - pt, ix * sw + kx - pl] += x[n, c, iy, ix] * W[c, o, ky, kx].  The weights [Cin, Cout, kh, kw] pack as
+// [kh][kw][Cout][Cin]: each tap is one [Cout][Cin] GEMM operand.
+void Planner::ImportConvTranspose(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    if (!act_input(on, 0)) fail("ConvTranspose " + n.name + ": constant input is not supported");
+    const OnnxTensor* w = L.init(on.inputs.at(1));
+    if (!w || w->dims.size() != 4) fail("ConvTranspose " + n.name + ": weights must be a 4-D initializer");
+    int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    if (X.dims.size() != 4) fail("ConvTranspose " + n.name + ": input must be 4-D");
+    const int64_t group = on.attr_i("group", 1);
+    if (group != 1) fail("ConvTranspose " + n.name + ": group = " + std::to_string(group) + " is not supported (only group = 1 is)");
+    const int64_t ci = w->dims[0], co = w->dims[1];
+    if (ci != X.c) fail("ConvTranspose " + n.name + ": input channels " + std::to_string(X.c) + " != weight channels " + std::to_string(ci));
+    std::vector<int64_t> ks = on.attr_ints("kernel_shape", {w->dims[2], w->dims[3]});
+    if (ks.size() != 2) fail("node " + on.name + ": only 2-D kernels are supported");
+    if (ks[0] != w->dims[2] || ks[1] != w->dims[3]) fail("ConvTranspose " + n.name + ": kernel_shape does not match weights");
+    auto st = on.attr_ints("strides", {1, 1});
+    auto dl = on.attr_ints("dilations", {1, 1});
+    auto pads = on.attr_ints("pads", {0, 0, 0, 0});
+    auto op = on.attr_ints("output_padding", {0, 0});
+    if (st.size() != 2 || st[0] < 1 || st[1] < 1) fail("ConvTranspose " + n.name + ": strides must be two positive integers");
+    if (dl.size() != 2 || dl[0] < 1 || dl[1] < 1) fail("node " + on.name + ": dilations must be two positive integers");
+    if (dl[0] != 1 || dl[1] != 1)
+        fail("ConvTranspose " + n.name + ": dilated transposed convolutions are not supported (dilations " + std::to_string(dl[0]) + "x" + std::to_string(dl[1]) + ")");
+    if (pads.size() != 4 || pads[0] < 0 || pads[1] < 0 || pads[2] < 0 || pads[3] < 0) fail("node " + on.name + ": pads must have 4 non-negative entries");
+    auto ap = on.attrs.find("auto_pad");
+    if (ap != on.attrs.end() && !ap->second.s.empty() && ap->second.s != "NOTSET") {
+        if (ap->second.s == "VALID") pads = {0, 0, 0, 0};
+        else fail("ConvTranspose " + n.name + ": auto_pad " + ap->second.s + " is not supported (NOTSET and VALID are)");
+    }
+    if (on.attrs.count("output_shape")) fail("ConvTranspose " + n.name + ": the output_shape attribute is not supported (give pads and output_padding)");
+    if (op.size() != 2 || op[0] < 0 || op[1] < 0) fail("ConvTranspose " + n.name + ": output_padding must be two non-negative integers");
+    if (op[0] >= st[0] || op[1] >= st[1])
+        fail("ConvTranspose " + n.name + ": output_padding " + std::to_string(op[0]) + "x" + std::to_string(op[1]) + " must be smaller than the strides " +
+             std::to_string(st[0]) + "x" + std::to_string(st[1]));
+    n.kind = L_CONV;
+    n.transposed = true;
+    n.kh = int(ks[0]); n.kw = int(ks[1]);
+    n.sh = int(st[0]); n.sw = int(st[1]);
+    n.pt = int(pads[0]); n.pl = int(pads[1]); n.pb = int(pads[2]); n.pr = int(pads[3]);
+    n.op_h = int(op[0]); n.op_w = int(op[1]);
+    const int64_t oh = (X.h - 1) * n.sh + n.kh - n.pt - n.pb + n.op_h, ow = (X.w - 1) * n.sw + n.kw - n.pl - n.pr + n.op_w;
+    if (oh < 1 || ow < 1) fail("ConvTranspose " + n.name + ": the output would be empty (" + std::to_string(oh) + "x" + std::to_string(ow) + ")");
+    n.w.resize(size_t(co * ci * n.kh * n.kw));
+    for (int64_t c = 0; c < ci; ++c)
+        for (int64_t o = 0; o < co; ++o)
+            for (int ky = 0; ky < n.kh; ++ky)
+                for (int kx = 0; kx < n.kw; ++kx)
+                    n.w[size_t(((int64_t(ky) * n.kw + kx) * co + o) * ci + c)] = w->f[size_t(((c * co + o) * n.kh + ky) * n.kw + kx)];
+    if (on.inputs.size() > 2 && !on.inputs[2].empty()) {
+        const OnnxTensor* b = L.init(on.inputs[2]);
+        if (!b || b->numel() != co) fail("ConvTranspose " + n.name + ": bias must be a [Cout] initializer");
+        n.bias = b->f;
+    }
     n.in = {x};
     odims = {X.n, co, oh, ow};
 }
@@ -998,6 +1076,7 @@ void Planner::ImportNode(const OnnxNode& on) {
     const std::string& op = on.op;
     std::vector<int64_t> odims;
     if (op == "Conv") ImportConv(on, n, odims);
+    else if (op == "ConvTranspose") ImportConvTranspose(on, n, odims);
     else if (op == "MatMul" || op == "Gemm") ImportGemm(on, n, odims);
     else if (op == "BatchNormalization") ImportBatchNorm(on, n, odims);
     else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu") ImportActivation(on, n, odims);
@@ -1022,6 +1101,7 @@ void Planner::MarkOutputs() {
 // fp8 mode has no kernels for these: a load error, never another kernel reading the bytes
 void Planner::RefuseForF8() const {
     for (const LNode& n : L.nodes) {
+        if (n.transposed) fail("ConvTranspose is not supported in fp8 mode (node " + n.name + ")");
         if (n.dw) fail("depthwise convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_CONV && n.group != 1) fail("grouped convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_CONV && (n.dil_h > 1 || n.dil_w > 1)) fail("dilated convolution is not supported in fp8 mode (Conv " + n.name + ")");
@@ -1062,7 +1142,7 @@ void Planner::FuseSqueezeExcite() {
         return &L.nodes[p];
     };
     auto fc_ok = [&](const LNode* c, int64_t cin, int64_t cout) {
-        return c && c->group == 1 && c->kh == 1 && c->kw == 1 && c->sh == 1 && c->sw == 1 && !c->pt && !c->pl && !c->pb && !c->pr && c->res < 0 &&
+        return c && c->group == 1 && !c->transposed && c->kh == 1 && c->kw == 1 && c->sh == 1 && c->sw == 1 && !c->pt && !c->pl && !c->pb && !c->pr && c->res < 0 &&
                L.vals[c->in[0]].dims.size() == 4 && L.vals[c->in[0]].c == cin && L.vals[c->out].c == cout && int64_t(c->w.size()) == cin * cout;
     };
     for (size_t i = 0; i < L.nodes.size(); ++i) {
@@ -1138,7 +1218,7 @@ void Planner::FuseConvEpilogues() {
             if (b.kind == L_ACT) {
                 // only the depthwise and grouped kernels have an activation epilogue (an activation behind another conv: fusion 2d below, or an
                 // eltwise step)
-                if (cv.group == 1) break;
+                if (cv.group == 1) break;              // (a transposed conv has group 1: it keeps the eltwise step)
                 cv.act = b.act;
             } else if (b.kind == L_CLIP) {
                 // only the depthwise and grouped kernels have a clamp epilogue (a Clip behind another conv: see the ReLU6 pass below, or an
@@ -1153,12 +1233,19 @@ void Planner::FuseConvEpilogues() {
                 // consumer's prologue (fusion 3) or a standalone eltwise step (fusion 4).
                 if (cv.res >= 0) break;
                 if (cv.bias.empty()) cv.bias.assign(size_t(cout), 0.f);
-                for (int64_t o = 0; o < cout; ++o) {
-                    for (size_t k = 0; k < kper; ++k) cv.w[size_t(o) * kper + k] *= b.s[o];
-                    cv.bias[o] = cv.bias[o] * b.s[o] + b.t[o];
+                if (cv.transposed) {               // w is [kh][kw][Cout][Cin]: row (tap, o) scales by s[o]
+                    const size_t cin = size_t(L.vals[cv.in[0]].c);
+                    for (size_t row = 0; row < cv.w.size() / cin; ++row)
+                        for (size_t c = 0; c < cin; ++c) cv.w[row * cin + c] *= b.s[row % size_t(cout)];
+                    for (int64_t o = 0; o < cout; ++o) cv.bias[o] = cv.bias[o] * b.s[o] + b.t[o];
+                } else {
+                    for (int64_t o = 0; o < cout; ++o) {
+                        for (size_t k = 0; k < kper; ++k) cv.w[size_t(o) * kper + k] *= b.s[o];
+                        cv.bias[o] = cv.bias[o] * b.s[o] + b.t[o];
+                    }
                 }
             } else if (b.kind == L_RELU) cv.relu = true;
-            else if (b.kind == L_ADD && cv.res < 0) {
+            else if (b.kind == L_ADD && cv.res < 0 && !cv.transposed) {
                 // residual shortcut: fold the Add into this conv's epilogue when the other operand already exists at this point of
                 // the schedule (its producer runs earlier); otherwise the other branch's conv picks the Add up when its turn comes
                 const int other = b.in[0] == cv.out ? b.in[1] : b.in[0];
@@ -1185,7 +1272,7 @@ void Planner::FuseRelu6IntoDepthwise() {
         if (c.dead || c.kind != L_CLIP || c.lo != 0.f) continue;
         const int x = c.in[0];
         const int p = L.vals[x].producer;
-        if (p < 0 || L.nodes[p].dead || L.nodes[p].kind != L_CONV || L.nodes[p].dw || !single_consumer(x) || !single_consumer(c.out)) continue;
+        if (p < 0 || L.nodes[p].dead || L.nodes[p].kind != L_CONV || L.nodes[p].dw || L.nodes[p].transposed || !single_consumer(x) || !single_consumer(c.out)) continue;
         LNode& d = L.nodes[L.consumers(c.out)[0]];
         if (d.kind != L_CONV || !d.dw || d.has_pre || d.in[0] != c.out || d.res == c.out) continue;
         LNode& cv = L.nodes[p];
@@ -1213,7 +1300,7 @@ void Planner::FuseActivationPrologues() {
         LNode& d = L.nodes[L.consumers(a.out)[0]];
         const int p = L.vals[x].producer;
         if (d.kind == L_CONV && d.dw && !d.has_pre && d.in[0] == a.out && d.res != a.out && p >= 0 && !L.nodes[p].dead && L.nodes[p].kind == L_CONV &&
-            !L.nodes[p].dw && single_consumer(x)) {
+            !L.nodes[p].dw && !L.nodes[p].transposed && single_consumer(x)) {
             LNode& cv = L.nodes[p];
             cv.name += "+" + a.name;
             cv.out = a.out;
@@ -1241,7 +1328,7 @@ void Planner::SwapConvAndAvgPool() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         if (L.nodes[i].dead || L.nodes[i].kind != L_CONV) continue;
         const LNode& cv0 = L.nodes[i];
-        if (cv0.kh != 1 || cv0.kw != 1 || cv0.sh != 1 || cv0.sw != 1 || cv0.pt || cv0.pl || cv0.pb || cv0.pr || cv0.relu || cv0.res >= 0) continue;
+        if (cv0.transposed || cv0.kh != 1 || cv0.kw != 1 || cv0.sh != 1 || cv0.sw != 1 || cv0.pt || cv0.pl || cv0.pb || cv0.pr || cv0.relu || cv0.res >= 0) continue;
         if (!single_consumer(cv0.out)) continue;
         const int pj = L.consumers(cv0.out)[0];
         const LNode& pl0 = L.nodes[pj];
@@ -1272,7 +1359,7 @@ void Planner::SwapConvAndAvgPool() {
 void Planner::FusePrologues() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& cv = L.nodes[i];
-        if (cv.dead || (cv.kind != L_CONV && cv.kind != L_GAP && cv.kind != L_AVGPOOL)) continue;
+        if (cv.dead || (cv.kind != L_CONV && cv.kind != L_GAP && cv.kind != L_AVGPOOL) || cv.transposed) continue;
         int x = cv.in[0];
         bool took_relu = false;
         int p = L.vals[x].producer;
@@ -1331,7 +1418,7 @@ void Planner::StageNchwInputs() {
         if (!L.vals[v].is_input || !L.vals[v].input_nchw) continue;
         bool all_conv = true;
         for (int ci : L.consumers(int(v)))
-            if (L.nodes[ci].kind != L_CONV || L.nodes[ci].in[0] != int(v) || L.nodes[ci].res == int(v)) all_conv = false;
+            if (L.nodes[ci].kind != L_CONV || L.nodes[ci].transposed || L.nodes[ci].in[0] != int(v) || L.nodes[ci].res == int(v)) all_conv = false;
         if (all_conv && !L.vals[v].is_output) continue;
         LNode cp;
         cp.kind = L_COPY;
@@ -1443,7 +1530,7 @@ void Planner::KeepDenseFusionInputsLive() {
         if (nxt >= order.size()) break;
         const LNode& b1 = L.nodes[order[nxt]];
         if (a3.kind != L_CONV || b1.kind != L_CONV || a3.kh != 3 || a3.kw != 3 || b1.kh != 1 || b1.kw != 1 || a3.has_pre || a3.group != 1 || b1.group != 1 ||
-            a3.dil_h != 1 || a3.dil_w != 1)
+            a3.dil_h != 1 || a3.dil_w != 1 || a3.transposed || b1.transposed)
             continue;
         if (L.vals[a3.out].c != 32 || L.vals[b1.out].c != 128 || L.vals[b1.in[0]].root != L.vals[a3.out].root) continue;
         if (L.vals[a3.out].n * L.vals[a3.out].h * L.vals[a3.out].w > FuseMaxPixels(env)) continue;
@@ -1647,6 +1734,21 @@ void Planner::EmitGroupConv(const LNode& n, Step& s) {
     s.base_tile = 0;
 }
 
+// transposed convs: their own kernels whatever IE_FORCE_ALGO says; IE_FORCE_TILE picks a variant where eligible (kernels.h kNumConvtTiles)
+void Planner::EmitTransposedConv(const LNode& n, Step& s) {
+    s.algo = ConvAlgo::Transposed;
+    s.oph = n.op_h;
+    s.opw = n.op_w;
+    if (s.in.f8 || s.out.f8) fail("ConvTranspose is not supported in fp8 mode (node " + n.name + ")");
+    if (s.out.nchw) fail("internal planner error: transposed conv " + n.name + " writes an NCHW view");
+    s.flops = 2.0 * double(s.in.n) * double(s.in.h) * double(s.in.w) * double(s.in.c) * double(s.out.c) * n.kh * n.kw;
+    s.bytes = vbytes(s.in) + vbytes(s.out) + (s.in.f16 ? 2.0 : 4.0) * double(n.w.size());
+    s.tile = ConvtDefaultTile(s);
+    const int t = ForcedTile(kNumConvtTiles);
+    if (t >= 0 && (t == 0 || ConvtFastViews(s))) s.tile = t;
+    s.base_tile = 0;
+}
+
 // ---- the base algorithm: naive for toy problems, the implicit GEMMs, the stem kernel, the fp8 GEMM; the heuristic tile ----
 void Planner::ChooseBaseAlgo(const ConvFacts& f, Step& s) const {
     const LNode& n = f.n;
@@ -1805,6 +1907,7 @@ void Planner::EmitConv(const LNode& n, Step& s) {
     s.w_off = push_vec(n.w);
     if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
     if (n.res >= 0) { s.in2 = view_of(n.res); s.has_in2 = true; }
+    if (n.transposed) { EmitTransposedConv(n, s); return; }
     if (n.dw || n.group != 1) { EmitGroupConv(n, s); return; }
     const ConvFacts f(n, s);
     s.flops = 2.0 * double(f.M) * double(f.N) * double(f.K);
@@ -2167,11 +2270,11 @@ void Planner::FuseStemPool() {
 void Planner::FuseDualF8() {
     for (size_t j = 0; j < plan.steps.size(); ++j) {
         Step& c = plan.steps[j];
-        if (c.kind != StepKind::Conv || !c.has_in2 || !c.parts.empty() || c.kh != 1 || c.kw != 1 || c.sh != 1 || c.sw != 1 || c.pt || c.pl || c.pb || c.pr) continue;
+        if (c.kind != StepKind::Conv || IsGroupConv(c.algo) || !c.has_in2 || !c.parts.empty() || c.kh != 1 || c.kw != 1 || c.sh != 1 || c.sw != 1 || c.pt || c.pl || c.pb || c.pr) continue;
         if (c.pre_scale_off >= 0 || c.in.nchw || c.out.nchw || c.in.c % 32 || c.out.c % 32 || c.in2_src < 0 || size_t(c.in2_src) >= j) continue;
         const size_t i = size_t(c.in2_src);
         const Step& pr = plan.steps[i];
-        if (pr.kind != StepKind::Conv || !pr.parts.empty() || pr.has_in2 || pr.relu || pr.pre_scale_off >= 0 || pr.kh != 1 || pr.kw != 1 || pr.pt || pr.pl || pr.pb || pr.pr) continue;
+        if (pr.kind != StepKind::Conv || IsGroupConv(pr.algo) || !pr.parts.empty() || pr.has_in2 || pr.relu || pr.pre_scale_off >= 0 || pr.kh != 1 || pr.kw != 1 || pr.pt || pr.pl || pr.pb || pr.pr) continue;
         if (pr.in.nchw || pr.in.c % 32 || pr.out.buf != c.in2.buf || pr.out.c_off != c.in2.c_off || pr.out.c != c.in2.c || pr.out.pitch != c.in2.pitch) continue;
         if (pr.out.n != c.out.n || pr.out.h != c.out.h || pr.out.w != c.out.w || pr.out.c != c.out.c) continue;
         if (precision == Precision::F8 && (!pr.in.f8 || !c.in.f8 || !c.out.f8)) continue;
@@ -2315,7 +2418,7 @@ std::string PlanToJson(const Plan& p) {
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
-    static const char* algos[] = {"igemm_vec", "igemm_scalar", "naive", "raster3x3", "ws1x1", "ws3x3", "stem", "direct", "igemm_f8", "dense_fused", "wino3x3", "conv1x1_x6", "dense_block", "dual_f8", "stem_pool", "depthwise", "grouped"};
+    static const char* algos[] = {"igemm_vec", "igemm_scalar", "naive", "raster3x3", "ws1x1", "ws3x3", "stem", "direct", "igemm_f8", "dense_fused", "wino3x3", "conv1x1_x6", "dense_block", "dual_f8", "stem_pool", "depthwise", "grouped", "transposed"};
     std::ostringstream o;
     o.precision(17);
     o << "{\"inputs\":[";
@@ -2367,6 +2470,7 @@ std::string PlanToJson(const Plan& p) {
         }
         if (s.kind == StepKind::Conv) o << ",\"algo\":\"" << algos[int(s.algo)] << "\",\"tile\":" << s.tile << ",\"splitk\":" << s.splitk;
         if (s.kind == StepKind::Conv && s.algo == ConvAlgo::Grouped) o << ",\"group\":" << s.group;      // (grouped steps only)
+        if (s.kind == StepKind::Conv && s.algo == ConvAlgo::Transposed) o << ",\"output_padding\":[" << s.oph << "," << s.opw << "]";      // (transposed steps only)
         if (s.kind == StepKind::Pool) o << ",\"max\":" << (s.pool_max ? "true" : "false");
         if (s.kind == StepKind::Resize)
             o << ",\"resize\":{\"mode\":\"" << rs_modes[int(s.rs_mode)] << "\",\"coord\":\"" << rs_coords[int(s.rs_coord)] << "\",\"nearest\":\""

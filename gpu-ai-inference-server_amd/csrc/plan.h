@@ -79,10 +79,13 @@ enum class ConvAlgo : int {
                       // 1 / 2 / 4 output pixels per lane.  Epilogue clamp [lo, hi] (a fused Clip) and prologue bound pre_hi (ReLU6 in front of it)
     Grouped = 16,     // any other group > 1 (kernels_grouped.hip): weights [Cout][kh][kw][Cin / group]; tile 0 = the generic kernel, 1-3 = channel blocks
                       // with 1 / 2 / 4 output pixels per lane.  The depthwise epilogue / prologue fields
+    Transposed = 17,  // ConvTranspose (kernels_convt.hip): weights [kh][kw][Cout][Cin]; tile 0 = the generic gather kernel, 1-2 = the MFMA kernel of the
+                      // non-overlapping case (k == stride, no pads, no output_padding) with 32 / 64 input pixels per wave.  Epilogue: bias, ReLU
 };
 
-// The conv algorithms whose weights are not the dense [Cout][kh][kw][Cin] layout: no dense-conv pass or weight mirror may take their steps
-inline bool IsGroupConv(ConvAlgo a) { return a == ConvAlgo::Depthwise || a == ConvAlgo::Grouped; }
+// The conv algorithms whose weights are not the dense [Cout][kh][kw][Cin] layout (depthwise, grouped, transposed): no dense-conv pass or weight
+// mirror may take their steps
+inline bool IsGroupConv(ConvAlgo a) { return a == ConvAlgo::Depthwise || a == ConvAlgo::Grouped || a == ConvAlgo::Transposed; }
 // The conv algorithms that honour a dilation > 1 (the only ones a dilated step may take)
 inline bool DilationOk(ConvAlgo a) { return a == ConvAlgo::IgemmVec || a == ConvAlgo::IgemmScalar || a == ConvAlgo::Naive; }
 
@@ -94,10 +97,11 @@ struct Step {
     // conv / pool geometry
     int kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0, pb = 0, pr = 0;
     int dh = 1, dw = 1;        // conv dilation (> 1 only on IgemmVec / IgemmScalar / Naive steps)
+    int oph = 0, opw = 0;      // ConvAlgo::Transposed: the ONNX output_padding (extra output rows / columns at the bottom / right)
     bool pool_max = false;
     bool count_include_pad = false;
     // offsets (in floats) into the weight blob; -1 = absent
-    int64_t w_off = -1;        // conv weights packed [Cout][kh][kw][Cin]
+    int64_t w_off = -1;        // conv weights packed [Cout][kh][kw][Cin] (ConvAlgo::Transposed: [kh][kw][Cout][Cin])
     int64_t bias_off = -1;     // [Cout]
     int64_t pre_scale_off = -1, pre_shift_off = -1;   // per input channel, applied before the op (then pre_relu)
     bool pre_relu = false;

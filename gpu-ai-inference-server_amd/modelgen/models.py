@@ -1,5 +1,5 @@
 """Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY,
-FCN-ResNet50, DeepLabV3-ResNet50 and small test graphs).
+FCN-ResNet50, DeepLabV3-ResNet50, U-Net and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -39,8 +39,8 @@ class GraphBuilder:
 
     # ---- ops ----
     def conv(self, x: str, cin: int, cout: int, k: int, stride: int = 1, pad: int | Sequence[int] = 0, bias: bool = False,
-             name: str | None = None, w_scale: float | None = None, group: int = 1, dilation: int = 1) -> str:
-        """pad: one value for all four sides or ONNX order [top, left, bottom, right]"""
+             name: str | None = None, w_scale: float | None = None, group: int = 1, dilation: int = 1, out: str | None = None) -> str:
+        """pad: one value for all four sides or ONNX order [top, left, bottom, right]; out: the result's name (default: name + "_out")"""
         name = name or self._uid("conv")
         cg = cin // group                       # input channels per group (1 for a depthwise conv)
         fan_in = cg * k * k
@@ -50,11 +50,34 @@ class GraphBuilder:
         if bias:
             b = (rng.uniform(self.seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
             ins.append(self.init(name + "_b", b.astype(np.float32)))
-        y = name + "_out"
+        y = out or name + "_out"
         self.nodes.append(pb.node("Conv", ins, [y], name, [
             pb.attr_ints("dilations", [dilation, dilation]), pb.attr_int("group", group),
             pb.attr_ints("kernel_shape", [k, k]), pb.attr_ints("pads", [pad] * 4 if isinstance(pad, int) else list(pad)),
             pb.attr_ints("strides", [stride, stride])]))
+        return y
+
+    def conv_transpose(self, x: str, cin: int, cout: int, k: int | Sequence[int], stride: int | Sequence[int], pad: int | Sequence[int] = 0,
+                       output_padding: int | Sequence[int] = 0, bias: bool = False, name: str | None = None) -> str:
+        """ONNX ConvTranspose, weights [cin, cout, kh, kw].  k, stride, output_padding: one value or [h, w]; pad: one value for all four sides or
+        ONNX order [top, left, bottom, right].  The same named rng streams as conv()."""
+        name = name or self._uid("convt")
+        kh, kw = (k, k) if isinstance(k, int) else k
+        sh, sw = (stride, stride) if isinstance(stride, int) else stride
+        oph, opw = (output_padding, output_padding) if isinstance(output_padding, int) else output_padding
+        # every output pixel sums about cin * kh * kw / (sh * sw) products
+        std = float(np.sqrt(2.0 * sh * sw / (cin * kh * kw)))
+        w = rng.gaussish(self.seed, name + "_w", cin * cout * kh * kw).reshape(cin, cout, kh, kw) * np.float32(std)
+        ins = [x, self.init(name + "_w", w.astype(np.float32))]
+        if bias:
+            b = (rng.uniform(self.seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
+            ins.append(self.init(name + "_b", b.astype(np.float32)))
+        y = name + "_out"
+        attrs = [pb.attr_ints("dilations", [1, 1]), pb.attr_int("group", 1), pb.attr_ints("kernel_shape", [kh, kw])]
+        if oph or opw:
+            attrs.append(pb.attr_ints("output_padding", [oph, opw]))
+        attrs += [pb.attr_ints("pads", [pad] * 4 if isinstance(pad, int) else list(pad)), pb.attr_ints("strides", [sh, sw])]
+        self.nodes.append(pb.node("ConvTranspose", ins, [y], name, attrs))
         return y
 
     def clip(self, x: str, lo: float | None = 0.0, hi: float | None = 6.0, form: str = "initializer") -> str:
@@ -493,6 +516,47 @@ def deeplabv3_resnet50(batch: int | str = 1, *, image: int = 224, classes: int =
     y = gb.relu(gb.bn(gb.conv(y, a, a, 3, pad=1, name="head_c1"), a, name="head_bn1"))
     y = gb.conv(y, a, classes, 1, bias=True, name="head_cls")
     _seg_head_out(gb, y, (batch, classes, fh, fh), batch, image, resize, coord, out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes, image, image])], opset=11)
+
+
+def unet(batch: int | str = 1, *, image: int = 224, base: int = 64, depth: int = 4, classes: int = 2, up: str = "convtranspose", final: str = "none",
+         seed: int = 97, in_name: str = "image", out_name: str = "out") -> bytes:
+    """U-Net (Ronneberger et al. 2015) with BatchNorm and padded convs, as segmentation libraries build it: `depth` encoder levels of two
+    [3x3/p1 conv -> BN -> ReLU] (base, 2 base, ... channels) each followed by a 2x2/s2 max pool, a bottleneck of two such convs (base * 2^depth
+    channels), then per decoder level an upsampling that halves the channels, Concat [skip, up] and two [3x3/p1 conv -> BN -> ReLU]; a 1x1
+    conv (bias) writes the [N, classes, image, image] logits.  up: "convtranspose" = 2x2/s2 ConvTranspose -> BN -> ReLU; "resize" = bilinear
+    x2 Resize -> 1x1 conv -> BN -> ReLU (no transposed conv in the graph).  final: "none" or "sigmoid"."""
+    assert image % 2 ** depth == 0, "the image extent must be a multiple of 2^depth"
+    assert up in ("convtranspose", "resize") and final in ("none", "sigmoid")
+    gb = GraphBuilder("unet", seed)
+
+    def double(x: str, cin: int, cout: int, tag: str) -> str:
+        x = gb.relu(gb.bn(gb.conv(x, cin, cout, 3, pad=1, name=tag + "_c1"), cout, name=tag + "_bn1"))
+        return gb.relu(gb.bn(gb.conv(x, cout, cout, 3, pad=1, name=tag + "_c2"), cout, name=tag + "_bn2"))
+
+    x, c, skips = in_name, 3, []
+    for lv in range(depth):
+        x = double(x, c, base << lv, f"enc{lv}")
+        c = base << lv
+        skips.append((x, c))
+        x = gb.pool("MaxPool", x, 2, 2, 0)
+    x = double(x, c, base << depth, "mid")
+    c = base << depth
+    for lv in reversed(range(depth)):
+        skip, cs = skips[lv]
+        hw = image >> (lv + 1)
+        if up == "convtranspose":
+            u = gb.conv_transpose(x, c, cs, 2, 2, name=f"up{lv}")
+        else:
+            u = gb.resize(x, (batch, c, hw, hw), scales=[2.0, 2.0], form="scales", name=f"up{lv}_resize")
+            u = gb.conv(u, c, cs, 1, name=f"up{lv}")
+        u = gb.relu(gb.bn(u, cs, name=f"up{lv}_bn"))
+        x = double(gb.concat([skip, u]), 2 * cs, cs, f"dec{lv}")
+        c = cs
+    if final == "sigmoid":
+        gb.simple("Sigmoid", [gb.conv(x, c, classes, 1, bias=True, name="head")], out=out_name)
+    else:
+        gb.conv(x, c, classes, 1, bias=True, name="head", out=out_name)
     return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes, image, image])], opset=11)
 
 

@@ -11,7 +11,10 @@ shapes as a yardstick (IE_PRECISION=fp16: half tensors).  For squeeze-excite ste
 GB/s (the input read twice, the output written once) and torch's mean + two 1x1 convs + sigmoid + mul on channels_last tensors per SE shape.
 For grouped convolutions (resnext50_32x4d, regnet_y_400mf, regnet_x_400mf; run with IE_GROUPED_CONV=1): every grouped step's algorithmic GB/s, its roofline
 max(bytes / 6.29 TB/s, FLOPs / peak) with peak = 157.3 TF (fp32) or 2.5 PF (fp16), the fraction of that roofline the step reaches, and torch's
-F.conv2d(groups=g) on channels_last tensors for the same shape."""
+F.conv2d(groups=g) on channels_last tensors for the same shape.
+For transposed convolutions (unet): the graph-replay time as the median of 50 single replays, the transposed steps' share of the eager forward,
+and per step the launched kernel (IE_FORCE_TILE=0 / 1 / 2 picks the generic kernel / the MFMA tiles), its algorithmic TB/s against the copy
+rate, its roofline and torch's F.conv_transpose2d on channels_last tensors for the same shape."""
 import json
 import os
 import subprocess
@@ -76,6 +79,32 @@ for n, c, h, w, co, g, k, st, pd in json.loads(sys.argv[1]):
 print(json.dumps(out))
 """
 
+# F.conv_transpose2d on channels_last tensors, ms per call (median of 20 timed calls after 5 warm ones) for each
+# [n, cin, h, w, cout, kh, kw, sh, sw, pad_h, pad_w, op_h, op_w]
+TORCH_CONVT = """
+import json, sys, torch
+import torch.nn.functional as F
+dt = torch.float16 if sys.argv[2] == "fp16" else torch.float32
+out = []
+for n, c, h, w, co, kh, kw, sh, sw, ph, pw, oh, ow in json.loads(sys.argv[1]):
+    x = torch.randn(n, c, h, w, device="cuda", dtype=dt).to(memory_format=torch.channels_last)
+    wt = torch.randn(c, co, kh, kw, device="cuda", dtype=dt).to(memory_format=torch.channels_last)
+    b = torch.randn(co, device="cuda", dtype=dt)
+    f = lambda: torch.relu_(F.conv_transpose2d(x, wt, b, stride=(sh, sw), padding=(ph, pw), output_padding=(oh, ow)))
+    for _ in range(5):
+        f()
+    ts = []
+    for _ in range(20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    out.append(sorted(ts)[len(ts) // 2])
+print(json.dumps(out))
+"""
+
 # torch's SE: mean over H, W -> 1x1 conv (+bias) -> ReLU -> 1x1 conv (+bias) -> sigmoid -> x * gate, for each [n, c, h, w, mid]
 TORCH_SE = """
 import json, sys, torch
@@ -114,7 +143,8 @@ m = B.CreateModel(mdir, os.path.basename(os.path.dirname(mdir)))
 din, dout = B.Prepare(m, [[batch, 3, 224, 224]], 1)
 B.CopyToDevice(m, din[0], models.synthetic_input((batch, 3, 224, 224), stream="prof"))
 B.RunPrepared(m, 5, True)
-prof = B.Profile(m, 10)
+# per step the median over the passes (50 for a graph with transposed convs: its table is what DESIGN 3.21 records)
+prof = B.Profile(m, 50 if any(s.get("algo") == "transposed" for s in plan["steps"]) else 10)
 tot = sum(p["ms"] for p in prof)
 print(f"# batch {batch}: eager forward {tot:.3f} ms, {sum(p['flops'] for p in prof)/tot/1e9:.1f} TFLOP/s overall")
 print(f"{'idx':>3} {'kernel':34} {'M':>7} {'N':>5} {'K':>5} {'ms':>8} {'TF/s':>7} {'GB/s':>7}  name")
@@ -126,6 +156,38 @@ for i, (p, s) in enumerate(zip(prof, plan["steps"])):
 dws = [(p, s) for p, s in zip(prof, plan["steps"]) if s.get("algo") == "depthwise"]
 ses = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "squeeze_excite"]
 grs = [(p, s) for p, s in zip(prof, plan["steps"]) if s.get("algo") == "grouped"]
+cts = [(p, s) for p, s in zip(prof, plan["steps"]) if s.get("algo") == "transposed"]
+if cts:
+    import time
+    B.RunPrepared(m, 10, True)
+    ts = []
+    for _ in range(50):
+        t0 = time.perf_counter()
+        B.RunPrepared(m, 1, True)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    ms = sorted(ts)[len(ts) // 2]
+    print(json.dumps({"model": model_name, "batch": batch, "precision": plan["precision"], "replay_ms_per_step_median50": round(ms, 4),
+                      "images_per_s": round(batch / ms * 1e3, 1), "force_tile": os.environ.get("IE_FORCE_TILE")}))
+    peak_tf = 2500.0 if plan["precision"] == "fp16" else 157.3
+    c_ms = sum(p["ms"] for p, _ in cts)
+    print(f"# {len(cts)} transposed steps: {c_ms:.4f} ms, {c_ms / tot * 100:.1f}% of the eager forward; roofline peak {peak_tf} TF/s, 6.29 TB/s")
+    # (torch takes symmetric pads only: a step with asymmetric pads is timed with its top / left pads)
+    shapes = [[s["in"]["n"], s["in"]["c"], s["in"]["h"], s["in"]["w"], s["out"]["c"], *s["k"], *s["stride"], s["pads"][0], s["pads"][1], *s["output_padding"]]
+              for _, s in cts]
+    tms = [float("nan")] * len(cts)
+    if not os.environ.get("PROFILE_NO_TORCH"):            # (set it for the forced-tile passes of one session: torch's time does not depend on our tile)
+        child = subprocess.run([sys.executable, "-c", TORCH_CONVT, json.dumps(shapes), plan["precision"]], capture_output=True, text=True, timeout=300)
+        if child.returncode == 0:
+            tms = json.loads(child.stdout.strip().splitlines()[-1])
+        else:
+            print("# torch yardstick failed:", child.stderr.strip().splitlines()[-1:])
+    print(f"{'transposed step':16} {'kernel':30} {'HxWxCin->Cout':>20} {'k/s':>5} {'ms':>8} {'TB/s':>6} {'%6.29T':>7} {'roof ms':>8} {'%roof':>6} {'torch ms':>9}")
+    for (p, s), t in zip(cts, tms):
+        tbs = p["bytes"] / p["ms"] / 1e9
+        roof = max(p["bytes"] / 6.29e9, p["flops"] / (peak_tf * 1e9))
+        shape = f"{s['in']['h']}x{s['in']['w']}x{s['in']['c']}->{s['out']['c']}"
+        ks = f"{s['k'][0]}/{s['stride'][0]}"
+        print(f"{p['name'][:16]:16} {p['kernel'][:30]:30} {shape:>20} {ks:>5} {p['ms']:8.4f} {tbs:6.2f} {tbs / 6.29 * 100:6.1f}% {roof:8.4f} {roof / p['ms'] * 100:5.1f}% {t:9.4f}")
 if dws or ses or grs:
     import time
     B.RunPrepared(m, 10, True)
