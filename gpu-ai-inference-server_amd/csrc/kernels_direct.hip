@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "env.h"
 #include "kernels.h"
@@ -408,7 +409,8 @@ static hipError_t launch_win_t(const ConvArgs& a, hipStream_t stream) {
 // The tiled implicit GEMM has one 64 x 64 workgroup per CU on block 3 and pays an LDS round trip
 // + barrier per K tile with nothing to overlap it (16-31 us against an MFMA floor of 4-15 us); the weight slice [128][K] does not fit
 // in LDS, so the weights-stationary kernel does not apply.  Roles swapped: a workgroup copies ITS 32 (16) pixels' K channels into LDS once
-// (coalesced rows, BN+ReLU prologue on the way; one barrier), every wave owns 16*TNW output channels and streams their weights
+// (coalesced rows, BN+ReLU prologue on the way; one barrier; one 4-channel column per thread, so no division or multiply per item and the
+// prologue constants once per thread -- fp32 MFMAs share the issue slot with every vector instruction), every wave owns 16*TNW output channels and streams their weights
 // from the fragment-major mirror (1 KiB contiguous per load) through a register ring with static slots - no barrier and no LDS
 // write in the K loop.  16x16x4 MFMAs, two 16-pixel blocks per wave share each weight fragment; a lane ends up with 4 consecutive
 // channels of one pixel and stores them as one 16-byte quad.  Loads past the last chunk use an out-of-range offset (no traffic); the
@@ -417,13 +419,12 @@ static hipError_t launch_win_t(const ConvArgs& a, hipStream_t stream) {
 template <int WAVES, int TNW, int PB, bool PRE>
 __global__ __launch_bounds__(64 * WAVES) void conv1x1_as_kernel(const ConvArgs a) {
     constexpr int NT = 64 * WAVES, D = PB == 1 ? 16 : 8, BNW = 16 * TNW, BN = BNW * WAVES;      // 16-pixel tiles: 128 MFMA cycles per chunk need a deeper ring to cover the weight latency
-    constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_direct[];
     float* const sA = reinterpret_cast<float*>(smem_direct);                       // [16 * PB][P]
 
-    const int tid = threadIdx.x, lane = tid & 63, r = lane & 15, gk = lane >> 4;
+    const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int K = a.in.c, P = K + (a.debug >> 8), CH = K >> 4, Cout = a.out.c;      // row pad (floats) comes from the launcher
+    const int K = a.in.c, P = K + ((a.debug >> 8) & 0xff), CH = K >> 4, Cout = a.out.c;      // row pad (floats) comes from the launcher
     const int M = a.out.n * a.out.h * a.out.w;
     const int m0 = blockIdx.x * (16 * PB), n0 = blockIdx.y * BN + wave * BNW;
     const int ipitch = int(a.in.sw), opitch = int(a.out.sw);
@@ -436,53 +437,93 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_as_kernel(const ConvArgs a
     // (in range, never consumed).  Fragment reads: one base per pixel block, bumped once per ring trip, chunk = immediate offset.
     u32x4 ring[D][TNW];
     int c_l = 0;
-    const unsigned wlane = unsigned(lane) * 16u;
+    unsigned wlane = unsigned(tid & 63) * 16u;
     auto issue = [&](int slot) {
         const int c = c_l < CH ? c_l : CH - 1;
 #pragma unroll
         for (int j = 0; j < TNW; ++j) ring[slot][j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, wlane, ((nb + j) * CH + c) * 1024, 0);
         ++c_l;
     };
+    // the last quarter of the ring is primed behind the staging loop: with every slot, the prologue constants and four rows in flight the
+    // kernel would not fit the registers of eight waves per SIMD; those slots are first consumed 3/4 of a ring trip after the barrier
+    constexpr int DLATE = D / 4;
 #pragma unroll
-    for (int s = 0; s < D; ++s) issue(s);
+    for (int s = 0; s < D - DLATE; ++s) issue(s);
 
     // ---- this workgroup's 16 * PB pixel rows -> LDS ----
+    // A thread keeps ONE 4-channel column (of CT = 1 << cs columns, cs from the launcher) and walks rows: row = tid >> cs, NT / CT rows on per
+    // pass, so an item costs one add on each of the two offsets and no division.  K > 4 * CT is walked in column blocks (scalar offset),
+    // the prologue constants are loaded once per block; lanes past K / 4 in the last block sit the block out.  Rows past M lie behind the
+    // descriptor's range ((M - 1) * pitch + K floats, pitch >= K): they read zeros without a predicate.
     {
-        constexpr int U = 4;
-        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-        const int c4n = K >> 2;
-        const int items = 16 * PB * c4n;
-        for (int idx0 = tid; idx0 < items; idx0 += U * NT) {
-            u32x4 v[U];
-            int row[U], c4[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int idx = idx0 + u * NT;
-                row[u] = idx / c4n;
-                c4[u] = idx - row[u] * c4n;
-                const int p = m0 + row[u];
-                v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (idx < items && p < M) ? unsigned(p * ipitch + c4[u] * 4) * 4u : OOB, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (idx0 + u * NT < items) {
-                    f32x4 x = __builtin_bit_cast(f32x4, v[u]);
+        constexpr int R = 16 * PB, U = 4;
+        static_assert(R * 16 >= NT, "the narrowest column block (16 columns) must not span more rows than the tile has");
+        const int cs = a.debug >> 16, CT = 1 << cs;
+        const int rstep = NT >> cs, npass = R / rstep;                            // wave-uniform (R, NT and CT are powers of two)
+        const int col = tid & (CT - 1), row0 = tid >> cs;
+        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, ((M - 1) * ipitch + K) * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_scale), 0, PRE ? K * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_shift), 0, PRE ? K * 4 : 0, 0x00020000);
+        const unsigned c16 = unsigned(col) * 16u;                                  // byte offset of the lane's column within a block
+        unsigned g = (unsigned(m0) * unsigned(ipitch) + __umul24(row0, ipitch)) * 4u + c16;      // pitches < 2^22 (as_eligible)
+        unsigned char* l = smem_direct + (__umul24(row0, P) * 4u + c16);            // the LDS address itself: no base to add per item
+        const unsigned gstep = unsigned(rstep * ipitch) * 4u;
+        const unsigned gnext = unsigned(CT) * 16u - unsigned(npass) * gstep;       // back to the first row, one column block on (modulo 2^32)
+        const int lstep = rstep * P * 4, lnext = CT * 16 - npass * lstep;
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        auto stage = [&](auto relu_) {                                             // the prologue's ReLU is decided once, not per element
+            constexpr bool RELU = decltype(relu_)::value;
+            for (int left = K * 4; left > 0; left -= CT * 16) {                    // bytes of a row from this column block on
+                if (c16 < unsigned(left)) {
+                    f32x4 sc = zero, sf = zero;
                     if constexpr (PRE) {
-                        const f32x4 sc = *reinterpret_cast<const f32x4*>(a.pre_scale + c4[u] * 4);
-                        const f32x4 sf = *reinterpret_cast<const f32x4*>(a.pre_shift + c4[u] * 4);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float y = x[e] * sc[e] + sf[e];
-                            x[e] = a.pre_relu ? fmaxf(y, 0.f) : y;
-                        }
+                        sc = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_sc, c16, K * 4 - left, 0));
+                        sf = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_sf, c16, K * 4 - left, 0));
                     }
-                    *reinterpret_cast<f32x4*>(sA + row[u] * P + c4[u] * 4) = x;
+                    auto group = [&](auto n_) {                                    // N row passes: all loads in flight, then prologue + LDS write
+                        constexpr int N = decltype(n_)::value;
+                        asm volatile("; ie-mark as-stage n=%0 relu=%1" ::"n"(N), "n"(int(RELU)));       // names the variant's blocks for scripts/isa_mix.py
+                        u32x4 v[N];
+#pragma unroll
+                        for (int u = 0; u < N; ++u) {
+                            v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, g, 0, 0);
+                            g += gstep;
+                        }
+#pragma unroll
+                        for (int u = 0; u < N; ++u) {
+                            f32x4 x = __builtin_bit_cast(f32x4, v[u]);
+                            if constexpr (PRE) x = __builtin_elementwise_fma(x, sc, sf);       // one rounding per element, as v_fma_f32
+                            if constexpr (PRE && RELU) x = __builtin_elementwise_max(x, zero);
+                            *reinterpret_cast<f32x4*>(l) = x;
+                            l += lstep;
+                        }
+                        asm volatile("; ie-mark as-stage-end n=%0 relu=%1" ::"n"(N), "n"(int(RELU)));   // (and keeps the variants' tails apart: fma and max stay in one block)
+                    };
+                    if (npass >= U) {                                              // npass is a power of two
+                        for (int p0 = 0; p0 < npass; p0 += U) group(std::integral_constant<int, U>{});
+                    } else if (npass == 2) {
+                        group(std::integral_constant<int, 2>{});
+                    } else {
+                        group(std::integral_constant<int, 1>{});
+                    }
+                    g += gnext;
+                    l += lnext;
                 }
             }
-        }
+        };
+        if (PRE && __builtin_amdgcn_readfirstlane(a.pre_relu) != 0) stage(std::true_type{});
+        else stage(std::false_type{});
     }
+#pragma unroll
+    for (int s = D - DLATE; s < D; ++s) issue(s);
     __syncthreads();
 
+    // the lane index is formed again here (and hidden from value numbering) so that no thread-index register lives through the staging loop,
+    // where ring, constants and four rows in flight already fill the register budget of eight waves per SIMD
+    int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(lane));
+    const int r = lane & 15, gk = lane >> 4;
+    wlane = unsigned(lane) * 16u;
     f32x4 acc[PB][TNW];
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb)
@@ -490,7 +531,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_as_kernel(const ConvArgs a
         for (int j = 0; j < TNW; ++j) acc[pb][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* abase[PB];                            // this lane's fragment address in each pixel block, at the current ring trip
 #pragma unroll
-    for (int pb = 0; pb < PB; ++pb) abase[pb] = sA + (pb * 16 + r) * P + gk * 4;
+    for (int pb = 0; pb < PB; ++pb) abase[pb] = sA + (__umul24(r, P) + pb * 16 * P + gk * 4);
     // activation fragments are read one chunk ahead of the MFMAs that consume them (the LDS latency hides behind 4*PB*TNW MFMAs
     // instead of stalling every chunk; the scheduler otherwise sinks each read to its use).  The read ahead of the last chunk runs
     // 16 floats past K: the row's pad and the head of the next row (the launcher allocates 64 bytes behind the last row).
@@ -527,26 +568,35 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_as_kernel(const ConvArgs a
     for (int s = 0; s < D; ++s)
         if (s < rem) compute(s);                       // wave-uniform: the last CH % D chunks are already in their slots
 
+    // Epilogue: the lane's row / quad offset is formed once; pixel block and channel block are scalar.  Rows past M lie behind the
+    // descriptor's range ((M - 1) * pitch + Cout floats, pitch >= Cout): their stores are dropped without a predicate.
     const __amdgpu_buffer_rsrc_t rs_out =
         __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), 0x00020000);
-#pragma unroll
-    for (int pb = 0; pb < PB; ++pb) {
-        const int m = m0 + pb * 16 + r;
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias != nullptr ? Cout * 4 : 0, 0x00020000);
+    const unsigned o0 = (unsigned(m0) * unsigned(opitch) + __umul24(r, opitch) + 4 * gk) * 4u;
+    const unsigned ostep = unsigned(opitch) * 64u;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    auto finish = [&](auto relu_, auto bias_) {            // bias and ReLU are decided once, not per element
+        constexpr bool RELU = decltype(relu_)::value, BIAS = decltype(bias_)::value;
+        asm volatile("; ie-mark as-finish relu=%0 bias=%1" ::"n"(int(RELU)), "n"(int(BIAS)));
 #pragma unroll
         for (int j = 0; j < TNW; ++j) {
-            const int n = n0 + j * 16 + 4 * gk;
-            f32x4 v = acc[pb][j];
-            if (a.bias != nullptr) {
-                const f32x4 bq = *reinterpret_cast<const f32x4*>(a.bias + n);
+            f32x4 bq = zero;
+            if constexpr (BIAS) bq = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, unsigned(gk) * 16u, (n0 + j * 16) * 4, 0));
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += bq[e];
+            for (int pb = 0; pb < PB; ++pb) {
+                f32x4 v = acc[pb][j];
+                if constexpr (BIAS) v += bq;
+                if constexpr (RELU) v = __builtin_elementwise_max(v, zero);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, o0 + pb * ostep, (n0 + j * 16) * 4, 0);
             }
-            if (a.relu) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, m < M ? unsigned(m * opitch + n) * 4u : OOB, 0, 0);
         }
+    };
+    switch (__builtin_amdgcn_readfirstlane((a.relu ? 1 : 0) | (a.bias != nullptr ? 2 : 0))) {
+        case 0: finish(std::false_type{}, std::false_type{}); break;
+        case 1: finish(std::true_type{}, std::false_type{}); break;
+        case 2: finish(std::false_type{}, std::true_type{}); break;
+        default: finish(std::true_type{}, std::true_type{}); break;
     }
 }
 
@@ -567,7 +617,22 @@ static bool as_eligible(const ConvArgs& a, int at) {
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
     if (M > (int64_t(1) << 22) || M * a.in.sw * 4 >= (int64_t(1) << 31) || M * a.out.sw * 4 >= (int64_t(1) << 31) || int64_t(a.out.c) * a.in.c * 4 >= (int64_t(1) << 31))
         return false;
+    if (a.in.sw >= (int64_t(1) << 22) || a.out.sw >= (int64_t(1) << 22)) return false;      // 24-bit row * pitch products; 31 rows past M stay below 2^32 bytes
     return size_t(16 * t.pb) * (a.in.c + 8) * 4 + 64 <= size_t(160) * 1024;
+}
+
+// log2 of the staging loop's column count (16, 32 or 64 four-channel columns per block; a thread keeps one column and walks rows).  Fewest
+// groups of four loads in flight first (each group is one memory round trip), then fewest load slots per thread, then the widest block.
+static int as_col_shift(int K, int threads, int rows) {
+    const int c4n = K / 4;
+    int best = 6;
+    long best_key = -1;
+    for (int s = 6; s >= 4; --s) {
+        const int ct = 1 << s, blocks = (c4n + ct - 1) / ct, npass = rows * ct / threads;
+        const long key = (long(blocks * ((npass + 3) / 4)) << 24) + blocks * npass;
+        if (best_key < 0 || key < best_key) best = s, best_key = key;
+    }
+    return best;
 }
 
 template <int AT>
@@ -580,7 +645,7 @@ static hipError_t launch_as_t(const ConvArgs& a_in, hipStream_t stream) {
     // (pitch = 8 or 40 mod 64 for K % 32 == 0) is conflict-free: the counter reads 0 and the LDS-active cycles halve -- at unchanged
     // kernel time (0.610 ms -> 0.610 ms per forward): the kernel was never LDS-bound.
     const int pad = Knobs().as_pad;
-    a.debug = pad << 8;
+    a.debug = (pad << 8) | (as_col_shift(a.in.c, 64 * t.waves, 16 * t.pb) << 16);
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
     const dim3 grid(unsigned((M + 16 * t.pb - 1) / (16 * t.pb)), unsigned(a.out.c / (16 * t.tnw * t.waves)));
     const size_t lds = size_t(16 * t.pb) * (a.in.c + pad) * 4 + 64;      // + the read-ahead past the last row
