@@ -118,7 +118,7 @@ namespace {
 std::string tune_file_header() {
     std::ostringstream o;
     o << kTuneFileTag << ' ' << kNumIgemmTiles << ' ' << kNumConvRasterTiles << ' ' << kNumConvWs32Tiles << ' ' << kNumConvWs16Tiles << ' ' << kNumConvWs3Tiles << ' '
-      << kNumConvDirectTiles << ' ' << kNumConvWinoTiles << ' ' << kNumConvX6Tiles << ' ' << kNumConvWs8Tiles << ' ' << kNumConvWs38Tiles;
+      << kNumConvDirectTiles << ' ' << kNumConvWinoTiles << ' ' << kNumConvX6Tiles << ' ' << kNumConvWs8Tiles << ' ' << kNumConvWs38Tiles << ' ' << kNumConvDenseFusedTiles;
     return o.str();
 }
 
@@ -952,7 +952,7 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
         return;
     }
     if (s.algo == ConvAlgo::DenseFused) {
-        // fused vs split is one more timed choice (tile 1 .. 5 = fused tile variants of kernels_fused.hip, 0 = the two plain launches)
+        // fused vs split is one more timed choice (tile 1 .. kNumConvDenseFusedTiles = fused tile variants of kernels_fused.hip, 0 = the two plain launches)
         const Step& p3 = s.parts[0];
         const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, 1, 1, 1, 1, 0, 0, s.in.h, s.in.w, s.in.pitch, s.out.pitch, 0, int64_t(ConvAlgo::DenseFused),
                                           s.pre_scale_off >= 0, s.bias_off >= 0, p3.in.c, p3.in.pitch};
@@ -965,7 +965,7 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
             const ConvArgs a1 = MakeConvArgs(pi, s);
             float best = 1e30f;
             choice = 0;
-            for (int t = 0; t <= 5; ++t)
+            for (int t = 0; t <= kNumConvDenseFusedTiles; ++t)
                 if (t == 0 || ConvDenseFusedEligible(a1, f, t))
                     if (const float ms = time_tile(t); ms < best) { best = ms; choice = t; }
             ctx.store(key, choice, 1);
@@ -1613,7 +1613,7 @@ static std::string kernel_label(const Step& s) {
                                    : std::string("convt_phase_kernel<") + (s.out.f16 ? "f16,px" : "f32,px") + std::to_string(32 * kConvtPixelBlocks[s.tile]) + ">";
             if (s.algo == ConvAlgo::DenseBlock) return s.tile != 0 ? "dense_block_f16_kernel<" + std::to_string(s.parts.size() / 2) + " layers>" : "dense_block_parts<" + std::to_string(s.parts.size()) + " launches>";
             if (s.algo == ConvAlgo::DenseFused && s.tile == 0) return "dense_fused_parts<2 launches>";
-            if (s.algo == ConvAlgo::DenseFused) return (s.tile >= 4 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";
+            if (s.algo == ConvAlgo::DenseFused) return (s.tile == 4 || s.tile == 5 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";
             if (s.algo == ConvAlgo::DualF8) return s.in.f8 ? "conv1x1_ws_f8_kernel<dual,t" + std::to_string(s.tile >= kWs8Code ? s.tile - kWs8Code : 1) + ">" : "dual_f8_parts<2 launches>";
             if (s.algo == ConvAlgo::IgemmF8 && s.tile >= kWs38Code) return "conv3x3_ws_f8_kernel<t" + std::to_string(s.tile - kWs38Code) + ">";
             if (s.algo == ConvAlgo::IgemmF8 && s.tile >= kWs8Code) return "conv1x1_ws_f8_kernel<t" + std::to_string(s.tile - kWs8Code) + ">";

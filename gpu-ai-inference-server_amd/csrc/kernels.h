@@ -73,11 +73,23 @@ static_assert(sizeof(ConvArgs) == 464 && offsetof(ConvArgs, in_bytes) == 456, "C
 
 // The 3x3 half of a fused dense-layer step (kernels_fused.hip): bottleneck tensor in, 32 fresh channels out (the tail of the 1x1's
 // input view), fragment-major 3x3 weights.
+// Per-launch constants of conv_dense_fused_kernel, worked out on the host by LaunchConvDenseFused so that the kernel divides nothing:
+// reciprocals (mg20_*: ceil(2^20 / d), for per-lane quotients n * d < 2^20 with a 24-bit multiply; mg32_*: floor(2^32 / d), 2^32 - 1 for
+// d == 1, for wave-uniform quotients on the scalar unit with one correction step) and the slot counts of the two staging loops.
+struct FusedConsts {
+    unsigned mg20_c4n3 = 0, mg20_c4n = 0, mg20_w = 0, mg20_h = 0;      // columns of a window row / of an old-channel row (4 channels each), map width, map height (0: h > 512)
+    unsigned hbig = 0x7fffffff;                                         // map height when it is above 512 (a tile then wraps past an image's last row at most once)
+    unsigned mg32_hw = 0, mg32_w = 0, mg32_cpt3 = 0;                    // pixels per image, map width, 16-channel chunks per 3x3 tap
+    int wrpp = 0, wfull = 0, wlast = 0;                                 // window: rows per slot, full slots, rows of the partial last slot
+    int rpp = 0, xfull = 0, xlast = 0;                                  // old channels: the same
+};
+
 struct FusedArgs {
     TensorArg in3, out3;
     const float* wfrag3 = nullptr;
     const float* bias3 = nullptr;
     int relu3 = 0;
+    FusedConsts k;                     // filled by LaunchConvDenseFused
 };
 
 struct PoolArgs {
@@ -305,7 +317,9 @@ hipError_t LaunchSplitWeightsX6(const float* w, void* dst, int Cout, int K, hipS
 hipError_t InitKernelsX6();
 // Fused dense-layer step (fp32): 3x3 growth conv of layer L + 1x1 bottleneck conv of layer L+1 per 16*pb-pixel tile, one launch.
 // tile: 1 / 2 = 16-pixel blocks per workgroup; 3 = 16-pixel tiles, two workgroups per CU (<= 128 VGPRs, <= 80 KB LDS);
-// 4 / 5 = wave-specialised variant (3x3 and 1x1 run concurrently on different waves), 16 / 32 pixels
+// 4 / 5 = wave-specialised variant (3x3 and 1x1 run concurrently on different waves), 16 / 32 pixels;
+// 6 = 16-pixel tiles on a two-row grid: row h recomputes the 3x3 and owns output channels [64h, 64h + 64) of the 1x1 (maps too small to fill the CUs)
+constexpr int kNumConvDenseFusedTiles = 6;      // tiles 1..6; 0 = the two plain launches
 bool ConvDenseFusedEligible(const ConvArgs& a, const FusedArgs& f, int tile);
 hipError_t LaunchConvDenseFused(const ConvArgs& a, const FusedArgs& f, int tile, hipStream_t stream);
 hipError_t InitKernelsFused();

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "env.h"
 #include "kernels.h"
@@ -35,146 +36,209 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // profiles/r02); pitch = 8 mod 32 banks is conflict-free for channel counts that are multiples of 32 (kernels_direct.hip, launch_as_t).
 constexpr int kRowPad = 8;
 
+// Wave-uniform n / d on the scalar unit: mg = floor(2^32 / d) (2^32 - 1 for d == 1) undershoots the quotient by at most one.
+__device__ __forceinline__ unsigned udiv_uniform(unsigned n, unsigned d, unsigned mg) {
+    unsigned q = __umulhi(n, mg);
+    if (n - q * d >= d) ++q;
+    return q;
+}
+
 // PB: 16-pixel blocks per workgroup.  8 waves.  1x1: Cout == 128 (16 per wave).  3x3: stride 1, pad 1, Cout == 32, 9 * Cin3 / 16 <= 72 chunks.
 // OCC2: a variant meant to run TWO workgroups per CU (16-pixel tiles, <= 128 VGPRs, <= 80 KB of LDS): the old-channel loads are issued only
 // after the 3x3's MFMAs (their registers would otherwise overlap the 3x3's weight fragments); the latency this exposes is what the
 // second workgroup on the CU fills.
-template <int PB, bool PRE, bool OCC2>
+// NSPLIT (tile 6): a two-row grid for maps with fewer tiles than half the CUs.  Both rows run phases (a)-(i) alike (bit-identical fresh
+// channels; row 0 stores them); in the 1x1 row h owns output channels [64h, 64h + 64): waves 0-3 take 16 each, ALL chunks in the usual order
+// on one accumulator (the same sums as tile 1, bit for bit) behind a 16-deep weight ring -- one wave per SIMD covers the weight latency
+// alone -- and waves 4-7 leave after the last barrier.
+//
+// fp32 MFMAs and vector-ALU instructions share the issue slot, so the kernel keeps the vector ALU for the work itself:
+//   * nothing is divided (FusedConsts: reciprocals and slot counts from the host; per-lane quotients are a 24-bit multiply and a shift, wave-
+//     uniform ones run on the scalar unit) and nothing is multiplied per slot: a thread keeps ONE 4-channel column in both staging loops and
+//     walks rows, so a slot is one add on the global offset and one on the LDS address;
+//   * rows before 0 and past M lie outside the buffer descriptors' ranges (reads give zeros, stores are dropped) -- no per-slot predicate;
+//     slots are counted per launch (full slots for every active thread, one partial last slot);
+//   * a wave's K slice of the 3x3 (at most Cin3 / 16 + 1 chunks) touches at most TWO taps: the lane's fragment address for each of the
+//     two is formed once, an out-of-image tap points at a zeroed 64-byte row with a step of 0, and a chunk costs one add per pixel block;
+//   * prologue ReLU, relu3, bias and ReLU select a code variant per launch (`; ie-mark` names the variants for scripts/isa_mix.py).
+template <int PB, bool PRE, bool OCC2, bool NSPLIT = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC2 ? 4 : 2, OCC2 ? 4 : 2)))
 void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part_off) {
-    constexpr int WAVES = 8, NT = 64 * WAVES, PX = 16 * PB, D = 8, MAXC3 = 9, TN3 = 2, PP = 32 + 4;
-    constexpr int MAXS = PB == 1 ? 8 : 16;             // staging slots per thread for the old channels: PX * (K - 32) / 4 <= MAXS * NT
+    static_assert(!NSPLIT || (PB == 1 && !OCC2), "the N-split form is a 16-pixel, one-workgroup-per-CU tile");
+    constexpr int WAVES = 8, NT = 64 * WAVES, PX = 16 * PB, D = NSPLIT ? 16 : 8, MAXC3 = 9, TN3 = 2, PP = 32 + 4;
+    constexpr int MAXS = PB == 1 ? 8 : 16;             // staging slots per thread for the old channels (checked by the launcher)
+    constexpr int MAXW = 8;                            // window slots per thread (checked by the launcher)
     constexpr unsigned OOB = 0x80000000u;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_fused[];
     const int K = a.in.c, Kold = K - 32, P = K + kRowPad, CH = K >> 4, Cin3 = f.in3.c, P3 = Cin3 + kRowPad;
     float* const sA = reinterpret_cast<float*>(smem_fused);                        // [PX][P]: the 1x1's activation rows
-    float* const sWin = sA;                                                        // [npx][P3]: bottleneck window of the 3x3; sA's rows are only
-                                                                                   // written once every wave is done with the window
+    // the bottleneck window of the 3x3, [npx][P3], starts at sA too: sA's rows are only written once every wave is done with the window
     float* const sPart = sA + part_off;                                            // [WAVES/2][PX][PP], behind max(sA, sWin)
+    const unsigned zero_row = unsigned(part_off + (WAVES / 2) * PX * PP) * 4u;     // 16 zero floats behind the partial tiles (byte offset)
+    const FusedConsts& k = f.k;
 
-    const int tid = threadIdx.x, lane = tid & 63, r = lane & 15, gk = lane >> 4;
+    const unsigned tid = threadIdx.x, lane = tid & 63, r = lane & 15, gk = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = a.in.h, W = a.in.w;
     const int M = a.in.n * H * W;
     const int m0 = blockIdx.x * PX;
-    const int ipitch = int(a.in.sw), opitch = int(a.out.sw), bpitch = int(f.in3.sw);
+    const int ipitch = int(a.in.sw), opitch = int(a.out.sw), bpitch = int(f.in3.sw), o3pitch = int(f.out3.sw);
+    const int nb = NSPLIT ? 4 * int(blockIdx.y) + wave : wave;                     // this wave's 16-channel block of the 1x1's output
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
-    // ---- (a) bottleneck window loads (issued first: they are waited for first) ----
+    // the two per-thread (row, 4-channel column) splits of the staging loops: tid / columns as a 24-bit multiply and a shift
+    const int c4n3 = Cin3 >> 2, c4n = Kold >> 2;
+    const unsigned wrow0 = __umul24(tid, k.mg20_c4n3) >> 20, wc4 = tid - __umul24(wrow0, c4n3);
+    const unsigned xrow0 = __umul24(tid, k.mg20_c4n) >> 20, xc4 = tid - __umul24(xrow0, c4n);
+    const bool wact = wrow0 < unsigned(k.wrpp), wlast = wrow0 < unsigned(k.wlast);       // NT - wrpp * c4n3 threads sit the window out
+    const bool xact = xrow0 < unsigned(k.rpp), xlast = xrow0 < unsigned(k.xlast);        // NT - rpp * c4n threads sit the old channels out
+    if (tid < 4) *reinterpret_cast<f32x4*>(smem_fused + zero_row + tid * 16u) = zero;
+
+    // ---- (a) bottleneck window loads (issued first: they are waited for first).  Window row w is pixel m0 - W - 1 + w: the rows before
+    //      pixel 0 wrap to offsets above 2^31 and the rows from M on start past the last row's channels, both outside the descriptor ----
     const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(f.in3.p, 0, int((int64_t(M - 1) * bpitch + Cin3) * 4), 0x00020000);
-    const int c4n3 = Cin3 >> 2;
-    const int p_lo = m0 - W - 1;
-    const int npx = PX + 2 * W + 2;
-    const int items3 = npx * c4n3;
-    constexpr int MAXW = 8;                            // window slots per thread: items3 <= MAXW * NT (checked by the launcher)
     u32x4 wv[MAXW];
-    // (row, 4-channel column) of slot u = (tid + u * NT) / c4n3: ONE division, then scalar strides with a carry -- an fp32 kernel pays
-    // for VALU instructions in MFMA slots and this workgroup is alone on its CU
-    const int wq = NT / c4n3, wr = NT - wq * c4n3;     // wave-uniform
-    int wrow[MAXW], wc4[MAXW];
-    wrow[0] = tid / c4n3;
-    wc4[0] = tid - wrow[0] * c4n3;
+    {
+        unsigned g = unsigned(m0 - W - 1) * unsigned(bpitch) * 4u + __umul24(wrow0, unsigned(bpitch) * 4u) + wc4 * 16u;      // (the byte pitch is the scalar factor: 24-bit products)
+        if (!wact) g = OOB;
+        const unsigned gstep = unsigned(k.wrpp * bpitch) * 4u;
 #pragma unroll
-    for (int u = 1; u < MAXW; ++u) {
-        const int c = wc4[u - 1] + wr;
-        const bool carry = c >= c4n3;
-        wc4[u] = carry ? c - c4n3 : c;
-        wrow[u] = wrow[u - 1] + wq + (carry ? 1 : 0);
-    }
-#pragma unroll
-    for (int u = 0; u < MAXW; ++u) {
-        const int p = p_lo + wrow[u];
-        wv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, (wrow[u] < npx && p >= 0 && p < M) ? unsigned(p * bpitch + wc4[u] * 4) * 4u : OOB, 0, 0);
+        for (int u = 0; u < MAXW; ++u) {
+            if (u < k.wfull) {                         // wave-uniform
+                asm volatile("; ie-mark fused-win-load u=%0" ::"n"(u));            // (the slot marks let scripts/isa_mix.py walk the path of one shape)
+                wv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, g, 0, 0);
+                g += gstep;
+            } else if (u == k.wfull && k.wlast != 0) {
+                asm volatile("; ie-mark fused-win-load-last u=%0" ::"n"(u));
+                wv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, wlast ? g : OOB, 0, 0);
+            }
+        }
     }
 
-    // ---- (b) the 3x3's weight fragments of this wave's K slice (fragment-major: 1 KiB per load) ----
+    // ---- (b) the 3x3's weight fragments of this wave's K slice (fragment-major: 1 KiB per load; lane * 16 in the VGPR, the chunk scalar) ----
     const int cpt3 = Cin3 >> 4, total3 = 9 * cpt3;
-    const int cb = int(int64_t(total3) * wave / WAVES), ce = int(int64_t(total3) * (wave + 1) / WAVES);
+    const int cb = (total3 * wave) >> 3, ce = (total3 * (wave + 1)) >> 3;
     const __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.wfrag3), 0, 32 * 9 * Cin3 * 4, 0x00020000);
     u32x4 B3[MAXC3][TN3];
+    {
+        const unsigned l16 = (a.debug & 4) ? OOB : lane * 16u;
 #pragma unroll
-    for (int i = 0; i < MAXC3; ++i) {
-        const int ch = cb + i;
+        for (int i = 0; i < MAXC3; ++i)
+            if (cb + i < ce) {                         // wave-uniform; the chunk loop below tests the same
 #pragma unroll
-        for (int j = 0; j < TN3; ++j)
-            B3[i][j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w3, (ch < ce && !(a.debug & 4)) ? unsigned((j * total3 + ch) * 64 + lane) * 16u : OOB, 0, 0);
+                for (int j = 0; j < TN3; ++j) B3[i][j] = __builtin_amdgcn_raw_buffer_load_b128(rs_w3, l16, (j * total3 + cb + i) * 1024, 0);
+            }
     }
 
     // ---- (c) the 1x1's old channels [0, Kold) of this tile's pixel rows: loads only, consumed after the 3x3.  A thread keeps ONE
     //      4-channel column for all its rows (rows advance by rpp per slot), so the prologue's scale/shift for that column is one pair
     //      of 16-byte loads issued here, not a dependent global round trip per slot later ----
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int((int64_t(M - 1) * ipitch + K) * 4), 0x00020000);
-    const int c4n = Kold >> 2;
-    const int rpp = NT / c4n;                          // rows per pass (>= 1: Kold / 4 <= 512, checked by the launcher)
-    const int xrow0 = tid / c4n, xc4 = tid - xrow0 * c4n;
-    const bool xact = xrow0 < rpp;                     // NT - rpp * c4n threads sit this phase out
     u32x4 xv[MAXS];
+    unsigned xg = unsigned(m0) * unsigned(ipitch) * 4u + __umul24(xrow0, unsigned(ipitch) * 4u) + xc4 * 16u;
+    if (!xact || (a.debug & 8)) xg = OOB;
     auto load_old_channels = [&]() {
+        const unsigned gstep = unsigned(k.rpp * ipitch) * 4u;
 #pragma unroll
         for (int u = 0; u < MAXS; ++u) {
-            const int row = xrow0 + u * rpp;
-            const int p = m0 + row;
-            xv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (xact && row < PX && p < M && !(a.debug & 8)) ? unsigned(p * ipitch + xc4 * 4) * 4u : OOB, 0, 0);
+            if (u < k.xfull) {                         // wave-uniform
+                asm volatile("; ie-mark fused-old-load u=%0" ::"n"(u));
+                xv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, xg, 0, 0);
+                xg += gstep;
+            } else if (u == k.xfull && k.xlast != 0) {
+                asm volatile("; ie-mark fused-old-load-last u=%0" ::"n"(u));
+                xv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, xlast ? xg : OOB, 0, 0);
+            }
         }
     };
     if constexpr (!OCC2) load_old_channels();
-    f32x4 xsc = {1.f, 1.f, 1.f, 1.f}, xsf = {0.f, 0.f, 0.f, 0.f};
-    f32x2 fsc = {1.f, 1.f}, fsf = {0.f, 0.f}, fb3 = {0.f, 0.f};
-    const int fc2 = (tid & 15) * 2;                    // this thread's channel pair of the fresh 32 (phase i)
-    if constexpr (PRE) {
-        if (xact) {
-            xsc = *reinterpret_cast<const f32x4*>(a.pre_scale + xc4 * 4);
-            xsf = *reinterpret_cast<const f32x4*>(a.pre_shift + xc4 * 4);
+    // prologue constants, 3x3 bias and epilogue bias through descriptors: an absent vector has range 0 and reads zeros, no branch
+    // (the two-workgroups-per-CU variant issues them with its old-channel loads, behind the 3x3: it has 128 registers)
+    f32x4 xsc = zero, xsf = zero, ebias = zero;
+    f32x2 fsc = {0.f, 0.f}, fsf = {0.f, 0.f}, fb3 = {0.f, 0.f};
+    const unsigned fc2 = (tid & 15) * 2;               // this thread's channel pair of the fresh 32 (phase i)
+    auto load_constants = [&]() {
+        if constexpr (PRE) {
+            const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_scale), 0, K * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_shift), 0, K * 4, 0x00020000);
+            xsc = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_sc, xc4 * 16u, 0, 0));
+            xsf = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_sf, xc4 * 16u, 0, 0));
+            fsc = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_sc, fc2 * 4u, Kold * 4, 0));
+            fsf = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_sf, fc2 * 4u, Kold * 4, 0));
         }
-        fsc = *reinterpret_cast<const f32x2*>(a.pre_scale + Kold + fc2);
-        fsf = *reinterpret_cast<const f32x2*>(a.pre_shift + Kold + fc2);
-    }
-    if (f.bias3 != nullptr) fb3 = *reinterpret_cast<const f32x2*>(f.bias3 + fc2);
-    f32x4 ebias = {0.f, 0.f, 0.f, 0.f};                // the 1x1's epilogue bias for this lane's 4 output channels
-    if (a.bias != nullptr) ebias = *reinterpret_cast<const f32x4*>(a.bias + wave * 16 + 4 * gk);
+        const __amdgpu_buffer_rsrc_t rs_b3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.bias3), 0, f.bias3 != nullptr ? 32 * 4 : 0, 0x00020000);
+        fb3 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_b3, fc2 * 4u, 0, 0));
+        const __amdgpu_buffer_rsrc_t rs_eb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias != nullptr ? 128 * 4 : 0, 0x00020000);
+        ebias = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_eb, gk * 16u, nb * 64, 0));      // this lane's 4 output channels
+    };
+    if constexpr (!OCC2) load_constants();
 
     // ---- (d) window -> LDS ----
+    if (wact) {
+        unsigned l = __umul24(wrow0, unsigned(P3) * 4u) + wc4 * 16u;
+        const unsigned lstep = unsigned(k.wrpp * P3) * 4u;
+        int wfull = k.wfull;
+        asm volatile("" : "+s"(wfull));                // compared afresh: the load loop's eight slot conditions are not kept in registers for this
 #pragma unroll
-    for (int u = 0; u < MAXW; ++u)
-        if (wrow[u] < npx) *reinterpret_cast<u32x4*>(sWin + wrow[u] * P3 + wc4[u] * 4) = wv[u];
+        for (int u = 0; u < MAXW; ++u) {
+            if (u < wfull) {
+                asm volatile("; ie-mark fused-win-put u=%0" ::"n"(u));
+                *reinterpret_cast<u32x4*>(smem_fused + l) = wv[u];
+                l += lstep;
+            } else if (u == wfull && k.wlast != 0) {
+                asm volatile("; ie-mark fused-win-put-last u=%0" ::"n"(u));
+                if (wlast) *reinterpret_cast<u32x4*>(smem_fused + l) = wv[u];
+            }
+        }
+    }
     __syncthreads();
 
     // ---- (e) 3x3 on 16 x 16 x 4 tiles: lane (r, gk) owns pixel r of each pixel block ----
+    // The tile's first pixel sits at (oy0, ox0) of its image (scalar); the lane's pixels follow from there with two 24-bit multiplies.  A wave's
+    // slice [cb, ce) starts cidx chunks into tap tapA and runs into tapA + 1 at most: per pixel block one fragment address and step for each
+    // of the two (the zero row and 0 where the tap falls outside the image or the pixel past M); the switch is a wave-uniform branch.
     f32x4 acc3[PB][TN3];
-    bool mok[PB];
-    int oy[PB], ox[PB];
+    unsigned cur[PB], inc[PB], curB[PB], incB[PB];
+    const unsigned tapA = udiv_uniform(unsigned(cb), unsigned(cpt3), k.mg32_cpt3);
+    int cidx = cb - int(tapA) * cpt3;
+    {
+        const unsigned HW = unsigned(H * W);
+        const unsigned rem0 = unsigned(m0) - udiv_uniform(unsigned(m0), HW, k.mg32_hw) * HW;
+        const unsigned oy0 = udiv_uniform(rem0, unsigned(W), k.mg32_w), ox0 = rem0 - oy0 * unsigned(W);
+        const int kyA = int(tapA * 11u) >> 5, kxA = int(tapA) - 3 * kyA;               // tap / 3 for taps 0..9
+        const int kyB = int((tapA + 1u) * 11u) >> 5, kxB = int(tapA) + 1 - 3 * kyB;
+        const unsigned offA = unsigned((kyA * W + kxA) * P3 + cidx * 16) * 4u, offB = unsigned((kyB * W + kxB) * P3) * 4u;
+        const unsigned wl0 = __umul24(r, unsigned(P3) * 4u) + gk * 16u, zl = zero_row + gk * 16u;
 #pragma unroll
-    for (int pb = 0; pb < PB; ++pb) {
-        const int m = m0 + pb * 16 + r;
-        mok[pb] = m < M;
-        const int rem = (mok[pb] ? m : 0) % (H * W);
-        oy[pb] = rem / W;
-        ox[pb] = rem - oy[pb] * W;
+        for (int pb = 0; pb < PB; ++pb) {
+            const unsigned j = pb * 16 + r, n = ox0 + j;                               // n < W + 32
+            const unsigned q = __umul24(n, k.mg20_w) >> 20;                            // image rows from the tile's first pixel on
+            const int ox = int(n - __umul24(q, W));
+            const unsigned y = oy0 + q;                                                // < H + 33
+            const unsigned q2 = (__umul24(y, k.mg20_h) >> 20) + (y >= k.hbig ? 1u : 0u);
+            const int oy = int(y - __umul24(q2, H));
+            const bool mok = int(j) < M - m0;
+            const bool okA = mok && unsigned(oy + kyA - 1) < unsigned(H) && unsigned(ox + kxA - 1) < unsigned(W);
+            const bool okB = mok && unsigned(oy + kyB - 1) < unsigned(H) && unsigned(ox + kxB - 1) < unsigned(W);
+            const unsigned base = wl0 + unsigned(pb * 16 * P3) * 4u;
+            cur[pb] = okA ? base + offA : zl;
+            inc[pb] = okA ? 64u : 0u;
+            curB[pb] = okB ? base + offB : zl;
+            incB[pb] = okB ? 64u : 0u;
 #pragma unroll
-        for (int j = 0; j < TN3; ++j) acc3[pb][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int j3 = 0; j3 < TN3; ++j3) acc3[pb][j3] = zero;
+        }
     }
-    // which of the nine taps fall inside the image for this lane's pixel: one bit each, tested in the chunk loop with a shift
-    unsigned tapmask[PB];
-#pragma unroll
-    for (int pb = 0; pb < PB; ++pb) {
-        unsigned mk = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-            if (mok[pb] && unsigned(oy[pb] + t / 3 - 1) < unsigned(H) && unsigned(ox[pb] + t % 3 - 1) < unsigned(W)) mk |= 1u << t;
-        tapmask[pb] = mk;
-    }
-    const float* const wlane = sWin + r * P3 + gk * 4;
+    const int ce3 = (a.debug & 1) ? cb : ce;           // debug bits: timing-only ablations, wrong results
 #pragma unroll
     for (int i = 0; i < MAXC3; ++i) {
-        if (cb + i < ce && !(a.debug & 1)) {           // wave-uniform (debug bits: timing-only ablations, wrong results)
-            const int ch = cb + i;
-            const int tap = ch / cpt3, c0 = (ch - tap * cpt3) * 16;
-            const int ky = tap / 3, kx = tap - ky * 3;
-            const float* const wtap = wlane + (ky * W + kx) * P3 + c0;      // scalar offset on a loop-invariant lane address
+        if (cb + i < ce3) {                            // wave-uniform
+            asm volatile("; ie-mark fused-chunk i=%0" ::"n"(i));
             f32x4 av[PB];
 #pragma unroll
             for (int pb = 0; pb < PB; ++pb) {
-                av[pb] = *reinterpret_cast<const f32x4*>(wtap + pb * 16 * P3);
-                if (!((tapmask[pb] >> tap) & 1u)) av[pb] = f32x4{0.f, 0.f, 0.f, 0.f};
+                av[pb] = *reinterpret_cast<const f32x4*>(smem_fused + cur[pb]);
+                cur[pb] += inc[pb];
             }
 #pragma unroll
             for (int j = 0; j < TN3; ++j) {
@@ -184,97 +248,134 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
 #pragma unroll
                     for (int pb = 0; pb < PB; ++pb) acc3[pb][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[e], av[pb][e], acc3[pb][j], 0, 0, 0);
             }
+            if (++cidx == cpt3) {                      // wave-uniform: the slice runs into its second tap (once per wave at most)
+                asm volatile("; ie-mark fused-tap-switch i=%0" ::"n"(i));
+#pragma unroll
+                for (int pb = 0; pb < PB; ++pb) {
+                    cur[pb] = curB[pb];
+                    inc[pb] = incB[pb];
+                }
+            }
         }
     }
 
-    if constexpr (OCC2) load_old_channels();
+    if constexpr (OCC2) {
+        load_old_channels();
+        load_constants();
+    }
 
     // ---- (f) prime the 1x1's weight ring (its latency hides behind the reduction and the staging below) ----
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, 128 * K * 4, 0x00020000);
     u32x4 ring[D];
     int c_l = 0;
+    const unsigned rl16 = (a.debug & 16) ? OOB : lane * 16u;
     auto issue = [&](int slot) {
         // lane * 16 in the VGPR, the rest scalar; past the last chunk the last one again (in range, never consumed): no VALU in the K loop
-        ring[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (a.debug & 16) ? OOB : unsigned(lane) * 16u, (wave * CH + (c_l < CH ? c_l : CH - 1)) * 1024, 0);
+        ring[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, rl16, (nb * CH + (c_l < CH ? c_l : CH - 1)) * 1024, 0);
         ++c_l;
     };
+    if (!NSPLIT || wave < WAVES / 2) {
 #pragma unroll
-    for (int s = 0; s < D; ++s) issue(s);
+        for (int s = 0; s < D; ++s) issue(s);
+    }
 
     // ---- (g) sum the eight partial 3x3 tiles in wave order: waves 4..7 publish, waves 0..3 add theirs and publish ----
-    if (wave >= WAVES / 2) {                           // (the partial tiles have their own storage: no need to wait for the window's readers)
-#pragma unroll
-        for (int pb = 0; pb < PB; ++pb)
-#pragma unroll
-            for (int j = 0; j < TN3; ++j) *reinterpret_cast<f32x4*>(sPart + ((wave - WAVES / 2) * PX + pb * 16 + r) * PP + j * 16 + 4 * gk) = acc3[pb][j];
-    }
-    __syncthreads();
-    if (wave < WAVES / 2) {
-#pragma unroll
-        for (int pb = 0; pb < PB; ++pb)
-#pragma unroll
-            for (int j = 0; j < TN3; ++j) {
-                float* const q = sPart + (wave * PX + pb * 16 + r) * PP + j * 16 + 4 * gk;
-                const f32x4 o = *reinterpret_cast<const f32x4*>(q);
-                *reinterpret_cast<f32x4*>(q) = f32x4{acc3[pb][j][0] + o[0], acc3[pb][j][1] + o[1], acc3[pb][j][2] + o[2], acc3[pb][j][3] + o[3]};
-            }
-    }
-
-    // ---- (h) old channels: prologue, -> sA ----
-    if (xact) {
-#pragma unroll
-        for (int u = 0; u < MAXS; ++u) {
-            const int row = xrow0 + u * rpp;
-            if (row < PX) {
-                f32x4 x = __builtin_bit_cast(f32x4, xv[u]);
-                if constexpr (PRE) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float y = x[e] * xsc[e] + xsf[e];
-                        x[e] = a.pre_relu ? fmaxf(y, 0.f) : y;
-                    }
-                }
-                *reinterpret_cast<f32x4*>(sA + row * P + xc4 * 4) = x;
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- (i) fresh channels: final sum, 3x3 epilogue, raw value to the block buffer, prologue'd value to sA ----
     {
-        const __amdgpu_buffer_rsrc_t rs_o3 = __builtin_amdgcn_make_buffer_rsrc(f.out3.p, 0, int((int64_t(M - 1) * int(f.out3.sw) + 32) * 4), 0x00020000);
-        for (int idx = tid; idx < PX * 16; idx += NT) {
-            const int p = idx >> 4, c2 = (idx & 15) * 2;
-            f32x2 v = {0.f, 0.f};
+        float* const q0 = sPart + ((wave & (WAVES / 2 - 1)) * PX * PP + int(r) * PP + 4 * int(gk));
+        if (wave >= WAVES / 2) {                       // (the partial tiles have their own storage: no need to wait for the window's readers)
 #pragma unroll
-            for (int w = 0; w < WAVES / 2; ++w) {
-                const f32x2 x = *reinterpret_cast<const f32x2*>(sPart + (w * PX + p) * PP + c2);
-                v[0] += x[0];
-                v[1] += x[1];
-            }
-            v[0] += fb3[0];
-            v[1] += fb3[1];
-            if (f.relu3) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); }
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rs_o3, m0 + p < M ? unsigned((m0 + p) * int(f.out3.sw) + c2) * 4u : OOB, 0, 0);
-            if constexpr (PRE) {
+            for (int pb = 0; pb < PB; ++pb)
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const float y = v[e] * fsc[e] + fsf[e];
-                    v[e] = a.pre_relu ? fmaxf(y, 0.f) : y;
+                for (int j = 0; j < TN3; ++j) *reinterpret_cast<f32x4*>(q0 + pb * 16 * PP + j * 16) = acc3[pb][j];
+        }
+        __syncthreads();
+        if (wave < WAVES / 2) {
+#pragma unroll
+            for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+                for (int j = 0; j < TN3; ++j) {
+                    float* const q = q0 + pb * 16 * PP + j * 16;
+                    *reinterpret_cast<f32x4*>(q) = acc3[pb][j] + *reinterpret_cast<const f32x4*>(q);
+                }
+        }
+    }
+
+    // ---- (h) old channels: prologue, -> sA.  The prologue's ReLU is decided once per launch, not per element ----
+    auto stage = [&](auto relu_) {
+        constexpr bool RELU = decltype(relu_)::value;
+        asm volatile("; ie-mark fused-stage relu=%0" ::"n"(int(RELU)));
+        auto put = [&](unsigned l, const u32x4& v) {
+            f32x4 x = __builtin_bit_cast(f32x4, v);
+            if constexpr (PRE) x = __builtin_elementwise_fma(x, xsc, xsf);             // one rounding per element, as v_fma_f32
+            if constexpr (PRE && RELU) x = __builtin_elementwise_max(x, zero);
+            *reinterpret_cast<f32x4*>(smem_fused + l) = x;
+        };
+        if (xact) {
+            unsigned l = __umul24(xrow0, unsigned(P) * 4u) + xc4 * 16u;
+            const unsigned lstep = unsigned(k.rpp * P) * 4u;
+            int xfull = k.xfull;
+            asm volatile("" : "+s"(xfull));            // compared afresh, as in (d)
+#pragma unroll
+            for (int u = 0; u < MAXS; ++u) {
+                if (u < xfull) {                       // wave-uniform
+                    asm volatile("; ie-mark fused-stage-put relu=%0 u=%1" ::"n"(int(RELU)), "n"(u));
+                    put(l, xv[u]);
+                    l += lstep;
+                } else if (u == xfull && k.xlast != 0) {
+                    asm volatile("; ie-mark fused-stage-put-last relu=%0 u=%1" ::"n"(int(RELU)), "n"(u));
+                    if (xlast) put(l, xv[u]);
                 }
             }
-            *reinterpret_cast<f32x2*>(sA + p * P + Kold + c2) = v;
+        }
+        asm volatile("; ie-mark fused-stage-end relu=%0" ::"n"(int(RELU)));
+    };
+    const int pre_relu = PRE ? __builtin_amdgcn_readfirstlane(a.pre_relu) : 0;
+    if (pre_relu != 0) stage(std::true_type{});
+    else stage(std::false_type{});
+    __syncthreads();
+
+    // ---- (i) fresh channels: final sum, 3x3 epilogue, raw value to the block buffer, prologue'd value to sA.  One (pixel, channel pair) per
+    //      thread of the first PX / 4 waves; rows past M start behind the descriptor's range ----
+    // the thread's three addresses (pixel tid >> 4): its partial sums, its pair in the block buffer, its pair in sA -- formed once, outside the variants
+    unsigned fresh_q = unsigned(part_off) * 4u + __umul24(tid >> 4, PP * 4) + fc2 * 4u;
+    unsigned fresh_g = unsigned(m0) * unsigned(o3pitch) * 4u + __umul24(tid >> 4, unsigned(o3pitch) * 4u) + fc2 * 4u;
+    unsigned fresh_l = __umul24(tid >> 4, unsigned(P) * 4u) + unsigned(Kold) * 4u + fc2 * 4u;
+    asm volatile("" : "+v"(fresh_q), "+v"(fresh_g), "+v"(fresh_l));
+    auto fresh = [&](auto relu3_, auto relu_) {
+        constexpr bool RELU3 = decltype(relu3_)::value, RELU = decltype(relu_)::value;
+        asm volatile("; ie-mark fused-fresh relu3=%0 relu=%1" ::"n"(int(RELU3)), "n"(int(RELU)));
+        const float* const q = reinterpret_cast<const float*>(smem_fused + fresh_q);
+        f32x2 v = {0.f, 0.f};
+#pragma unroll
+        for (int w = 0; w < WAVES / 2; ++w) v += *reinterpret_cast<const f32x2*>(q + w * PX * PP);
+        v += fb3;
+        if constexpr (RELU3) v = __builtin_elementwise_max(v, f32x2{0.f, 0.f});
+        if (!NSPLIT || blockIdx.y == 0) {
+            const __amdgpu_buffer_rsrc_t rs_o3 = __builtin_amdgcn_make_buffer_rsrc(f.out3.p, 0, int((int64_t(M - 1) * o3pitch + 32) * 4), 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rs_o3, fresh_g, 0, 0);
+        }
+        if constexpr (PRE) v = __builtin_elementwise_fma(v, fsc, fsf);
+        if constexpr (PRE && RELU) v = __builtin_elementwise_max(v, f32x2{0.f, 0.f});
+        *reinterpret_cast<f32x2*>(smem_fused + fresh_l) = v;
+    };
+    if (PX * 16 >= NT || wave < PX * 16 / 64) {        // wave-uniform
+        switch ((__builtin_amdgcn_readfirstlane(f.relu3) != 0 ? 1 : 0) | (pre_relu != 0 ? 2 : 0)) {
+            case 0: fresh(std::false_type{}, std::false_type{}); break;
+            case 1: fresh(std::true_type{}, std::false_type{}); break;
+            case 2: fresh(std::false_type{}, std::true_type{}); break;
+            default: fresh(std::true_type{}, std::true_type{}); break;
         }
     }
     __syncthreads();
+    if (NSPLIT && wave >= WAVES / 2) return;           // no barrier from here on
 
     // ---- (k) the 1x1: conv1x1_as_kernel's loop, 16 output channels per wave ----
     f32x4 acc[PB];
 #pragma unroll
-    for (int pb = 0; pb < PB; ++pb) acc[pb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* abase[PB];                            // fragment address per pixel block at the current ring trip; chunk = immediate offset
+    for (int pb = 0; pb < PB; ++pb) acc[pb] = zero;
+    const unsigned char* abase[PB];                    // fragment address per pixel block at the current ring trip; chunk = immediate offset
 #pragma unroll
-    for (int pb = 0; pb < PB; ++pb) abase[pb] = sA + (pb * 16 + r) * P + gk * 4;
+    for (int pb = 0; pb < PB; ++pb) abase[pb] = smem_fused + (__umul24(r, unsigned(P) * 4u) + unsigned(pb * 16 * P) * 4u + gk * 16u);
     f32x4 avn[PB];
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb) avn[pb] = *reinterpret_cast<const f32x4*>(abase[pb]);
@@ -283,7 +384,7 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
 #pragma unroll
         for (int pb = 0; pb < PB; ++pb) av[pb] = avn[pb];
 #pragma unroll
-        for (int pb = 0; pb < PB; ++pb) avn[pb] = *reinterpret_cast<const f32x4*>(abase[pb] + (slot + 1) * 16);
+        for (int pb = 0; pb < PB; ++pb) avn[pb] = *reinterpret_cast<const f32x4*>(abase[pb] + (slot + 1) * 64);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -300,25 +401,32 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
             issue(s);
         }
 #pragma unroll
-        for (int pb = 0; pb < PB; ++pb) abase[pb] += D * 16;
+        for (int pb = 0; pb < PB; ++pb) abase[pb] += D * 64;
     }
 #pragma unroll
     for (int s = 0; s < D; ++s)
         if (s < rem) compute(s);
 
+    // Epilogue: bias and ReLU are decided once per launch; the lane's row / quad offset is formed once, rows past M start behind the
+    // descriptor's range ((M - 1) * pitch + 128 floats, pitch >= 128) and their stores are dropped
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + 128) * 4), 0x00020000);
+    const unsigned o0 = unsigned(m0) * unsigned(opitch) * 4u + __umul24(r, unsigned(opitch) * 4u) + gk * 16u;
+    auto finish = [&](auto relu_, auto bias_) {
+        constexpr bool RELU = decltype(relu_)::value, BIAS = decltype(bias_)::value;
+        asm volatile("; ie-mark fused-finish relu=%0 bias=%1" ::"n"(int(RELU)), "n"(int(BIAS)));
 #pragma unroll
-    for (int pb = 0; pb < PB; ++pb) {
-        const int m = m0 + pb * 16 + r;
-        const int n = wave * 16 + 4 * gk;
-        f32x4 v = acc[pb];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += ebias[e];
-        if (a.relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        for (int pb = 0; pb < PB; ++pb) {
+            f32x4 v = acc[pb];
+            if constexpr (BIAS) v += ebias;
+            if constexpr (RELU) v = __builtin_elementwise_max(v, zero);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, o0 + unsigned(pb * 16 * opitch) * 4u, nb * 64, 0);
         }
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, m < M ? unsigned(m * opitch + n) * 4u : OOB, 0, 0);
+    };
+    switch ((__builtin_amdgcn_readfirstlane(a.relu) != 0 ? 1 : 0) | (a.bias != nullptr ? 2 : 0)) {
+        case 0: finish(std::false_type{}, std::false_type{}); break;
+        case 1: finish(std::true_type{}, std::false_type{}); break;
+        case 2: finish(std::false_type{}, std::true_type{}); break;
+        default: finish(std::true_type{}, std::true_type{}); break;
     }
 }
 
@@ -610,17 +718,45 @@ static size_t fused_lds_bytes(const ConvArgs& a, const FusedArgs& f, int pb, int
     const size_t rows = px * (a.in.c + kRowPad) * 4, win = (px + 2 * a.in.w + 2) * (f.in3.c + kRowPad) * 4, part = size_t(4) * px * 36 * 4;
     const size_t first = (rows > win ? rows : win);
     if (part_off) *part_off = int(first / 4);
-    return first + part;
+    return first + part + 64;                          // + the zeroed row the 3x3's out-of-image taps read
+}
+
+// ceil(2^20 / d): n / d == (n * mg) >> 20 for n * d < 2^20;  floor(2^32 / d): see udiv_uniform
+static unsigned mg20(unsigned d) { return ((1u << 20) + d - 1) / d; }
+static unsigned mg32(unsigned d) { return d == 1 ? 0xffffffffu : unsigned((uint64_t(1) << 32) / d); }
+
+static FusedConsts fused_consts(const ConvArgs& a, const FusedArgs& f, int pb) {
+    FusedConsts k;
+    const int px = 16 * pb, c4n3 = f.in3.c / 4, c4n = (a.in.c - 32) / 4, npx = px + 2 * a.in.w + 2;
+    k.mg20_c4n3 = mg20(c4n3);
+    k.mg20_c4n = mg20(c4n);
+    k.mg20_w = mg20(a.in.w);
+    k.mg20_h = a.in.h <= 512 ? mg20(a.in.h) : 0;
+    k.hbig = a.in.h <= 512 ? 0x7fffffffu : unsigned(a.in.h);
+    k.mg32_hw = mg32(unsigned(a.in.h) * unsigned(a.in.w));
+    k.mg32_w = mg32(a.in.w);
+    k.mg32_cpt3 = mg32(f.in3.c / 16);
+    k.wrpp = 512 / c4n3;
+    k.wfull = npx / k.wrpp;
+    k.wlast = npx % k.wrpp;
+    k.rpp = 512 / c4n;
+    k.xfull = px / k.rpp;
+    k.xlast = px % k.rpp;
+    return k;
 }
 
 static bool dense(const TensorArg& t) { return t.sc == 1 && t.sh == t.w * t.sw && t.sn == t.h * t.sh; }
 
-// tile: 1 / 2 = 16-pixel blocks per workgroup (one workgroup per CU); 3 = 16-pixel tiles in the two-workgroups-per-CU variant
+// tile: 1 / 2 = 16-pixel blocks per workgroup (one workgroup per CU); 3 = 16-pixel tiles in the two-workgroups-per-CU variant;
+// 4 / 5 = wave-specialised, 16 / 32 pixels; 6 = 16-pixel tiles on a two-row grid (each row half of the 1x1's output channels)
+static int fused_pixel_blocks(int tile) { return tile == 3 || tile == 6 ? 1 : (tile >= 4 ? tile - 3 : tile); }
+
 bool ConvDenseFusedEligible(const ConvArgs& a, const FusedArgs& f, int tile) {
-    if (tile < 1 || tile > 5) return false;
-    const int pb = tile == 3 ? 1 : (tile >= 4 ? tile - 3 : tile);
+    if (tile < 1 || tile > kNumConvDenseFusedTiles) return false;
+    const int pb = fused_pixel_blocks(tile);
+    const bool ws = tile == 4 || tile == 5;
     if (tile == 3 && fused_lds_bytes(a, f, 1) > size_t(80) * 1024) return false;
-    if (tile >= 4 && (fused_ws_lds_bytes(a, f, pb) > size_t(160) * 1024 || 9 * (f.in3.c / 16) < 4 * 1)) return false;
+    if (ws && (fused_ws_lds_bytes(a, f, pb) > size_t(160) * 1024 || 9 * (f.in3.c / 16) < 4 * 1)) return false;
     if (a.in.f16 || a.out.f16 || a.in.f8 || a.out.f8 || f.in3.f16 || f.out3.f16 || f.in3.f8 || f.out3.f8) return false;
     if (a.wfrag == nullptr || f.wfrag3 == nullptr || a.res.p != nullptr) return false;
     if (a.kh != 1 || a.kw != 1 || a.sh != 1 || a.sw != 1 || a.pt != 0 || a.pl != 0) return false;
@@ -649,14 +785,22 @@ bool ConvDenseFusedEligible(const ConvArgs& a, const FusedArgs& f, int tile) {
     }
     if ((a.in.c - 32) % 4 || (reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (f.bias3 && (reinterpret_cast<uintptr_t>(f.bias3) & 7))) return false;
     if (int64_t(px + 2 * a.in.w + 2) * (f.in3.c / 4) > int64_t(8) * 512) return false;            // window slots
+    if (!ws) {
+        // window slots with one 4-channel column per thread (512 / columns rows per slot); 24-bit row * pitch products; every row a slot can
+        // name (the window's halo and a partial last slot: < 1024 rows past M) stays below 2^31 bytes, so no offset wraps back into range
+        const int wrpp = 512 / (f.in3.c / 4);
+        if ((px + 2 * a.in.w + 2 + wrpp - 1) / wrpp > 8 || a.in.w > 500) return false;
+        if (a.in.sw >= (int64_t(1) << 22) || a.out.sw >= (int64_t(1) << 22) || f.in3.sw >= (int64_t(1) << 22)) return false;
+        if ((M + 1024) * a.in.sw * 4 >= (int64_t(1) << 31) || (M + 1024) * f.in3.sw * 4 >= (int64_t(1) << 31) || (M + 1024) * a.out.sw * 4 >= (int64_t(1) << 31)) return false;
+    }
     return fused_lds_bytes(a, f, pb) <= size_t(160) * 1024;
 }
 
 hipError_t LaunchConvDenseFused(const ConvArgs& a_in, const FusedArgs& f, int tile, hipStream_t stream) {
     if (!ConvDenseFusedEligible(a_in, f, tile)) return hipErrorInvalidValue;
     const bool occ2 = tile == 3;
-    const int pb = occ2 ? 1 : (tile >= 4 ? tile - 3 : tile);
-    if (tile >= 4) {
+    const int pb = fused_pixel_blocks(tile);
+    if (tile == 4 || tile == 5) {
         const int64_t Mw = int64_t(a_in.in.n) * a_in.in.h * a_in.in.w;
         const dim3 gridw(unsigned((Mw + 16 * pb - 1) / (16 * pb)));
         int win_off = 0, poff = 0;
@@ -680,24 +824,33 @@ hipError_t LaunchConvDenseFused(const ConvArgs& a_in, const FusedArgs& f, int ti
     const dim3 grid(unsigned((M + 16 * pb - 1) / (16 * pb)));
     int part_off = 0;
     const size_t lds = fused_lds_bytes(a, f, pb, &part_off);
+    FusedArgs fk = f;
+    fk.k = fused_consts(a, f, pb);
+    if (tile == 6) {
+        const dim3 grid2(grid.x, 2);
+        if (a.pre_scale) conv_dense_fused_kernel<1, true, false, true><<<grid2, dim3(512), lds, stream>>>(a, fk, part_off);
+        else conv_dense_fused_kernel<1, false, false, true><<<grid2, dim3(512), lds, stream>>>(a, fk, part_off);
+        return hipGetLastError();
+    }
     if (occ2) {
-        if (a.pre_scale) conv_dense_fused_kernel<1, true, true><<<grid, dim3(512), lds, stream>>>(a, f, part_off);
-        else conv_dense_fused_kernel<1, false, true><<<grid, dim3(512), lds, stream>>>(a, f, part_off);
+        if (a.pre_scale) conv_dense_fused_kernel<1, true, true><<<grid, dim3(512), lds, stream>>>(a, fk, part_off);
+        else conv_dense_fused_kernel<1, false, true><<<grid, dim3(512), lds, stream>>>(a, fk, part_off);
     } else if (pb == 1) {
-        if (a.pre_scale) conv_dense_fused_kernel<1, true, false><<<grid, dim3(512), lds, stream>>>(a, f, part_off);
-        else conv_dense_fused_kernel<1, false, false><<<grid, dim3(512), lds, stream>>>(a, f, part_off);
+        if (a.pre_scale) conv_dense_fused_kernel<1, true, false><<<grid, dim3(512), lds, stream>>>(a, fk, part_off);
+        else conv_dense_fused_kernel<1, false, false><<<grid, dim3(512), lds, stream>>>(a, fk, part_off);
     } else {
-        if (a.pre_scale) conv_dense_fused_kernel<2, true, false><<<grid, dim3(512), lds, stream>>>(a, f, part_off);
-        else conv_dense_fused_kernel<2, false, false><<<grid, dim3(512), lds, stream>>>(a, f, part_off);
+        if (a.pre_scale) conv_dense_fused_kernel<2, true, false><<<grid, dim3(512), lds, stream>>>(a, fk, part_off);
+        else conv_dense_fused_kernel<2, false, false><<<grid, dim3(512), lds, stream>>>(a, fk, part_off);
     }
     return hipGetLastError();
 }
 
 hipError_t InitKernelsFused() {
     hipError_t e;
-#define IE_FUSED_ATTR(PB, PRE, OCC)                                                                                                                                 \
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dense_fused_kernel<PB, PRE, OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+#define IE_FUSED_ATTR(PB, PRE, ...)                                                                                                                                 \
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dense_fused_kernel<PB, PRE, __VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     IE_FUSED_ATTR(1, true, false) IE_FUSED_ATTR(1, false, false) IE_FUSED_ATTR(2, true, false) IE_FUSED_ATTR(2, false, false) IE_FUSED_ATTR(1, true, true) IE_FUSED_ATTR(1, false, true)
+    IE_FUSED_ATTR(1, true, false, true) IE_FUSED_ATTR(1, false, false, true)
 #undef IE_FUSED_ATTR
 #define IE_FUSED_WS_ATTR(PB, PRE)                                                                                                                                   \
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dense_fused_ws_kernel<PB, PRE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;

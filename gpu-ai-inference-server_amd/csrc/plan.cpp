@@ -2098,7 +2098,7 @@ void Planner::FuseDenseLayers() {
             if (fuse) {
                 int pb = M <= 2048 ? 1 : 2;
                 int ftile = 0;
-                if (const char* e = env.get("IE_FUSE_PB")) { const int v = std::atoi(e); if (v == 1 || v == 2) pb = v; if (v == 3) { pb = 1; ftile = 3; } if (v == 4 || v == 5) { pb = v - 3; ftile = v; } }
+                if (const char* e = env.get("IE_FUSE_PB")) { const int v = std::atoi(e); if (v == 1 || v == 2) pb = v; if (v == 3) { pb = 1; ftile = 3; } if (v == 4 || v == 5) { pb = v - 3; ftile = v; } if (v == 6) { pb = 1; ftile = 6; } }
                 const int64_t px = 16 * pb;
                 const int64_t win = (px + 2 * s3.in.w + 2) * (s3.in.c + 8) * 4, part = 4 * px * 36 * 4;
                 const int64_t c4n = (s1.in.c - 32) / 4, rpp = c4n > 0 && c4n <= 512 ? 512 / c4n : 0;

@@ -1,5 +1,5 @@
 """Instruction mix of every kernel of one .hip file, per basic block:
-    python scripts/isa_mix.py gpu-ai-inference-server_amd/csrc/kernels_direct.hip [--kernel conv1x1_as_kernel] [--json] [--asm listing.s]
+    python scripts/isa_mix.py gpu-ai-inference-server_amd/csrc/kernels_direct.hip [--kernel conv1x1_as_kernel] [--json] [--totals] [--asm listing.s]
 
 The file is compiled to an AMDGPU listing with build.py's flags (hipcc --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form=1 -O3
 --cuda-device-only -S); --asm reads an existing listing instead.  Nothing runs on a GPU.  Per kernel symbol and basic block (a block
@@ -177,7 +177,14 @@ def totals(blocks):
     return {k: sum(b[k] for b in blocks) for k in KEYS}
 
 
-def render(kernels, out=sys.stdout):
+def render(kernels, out=sys.stdout, totals_only=False):
+    if totals_only:                                  # one line per kernel: a listing of every block of a kernel with hundreds of them is long
+        out.write(f"  {'kernel (every block once)':48s}" + "".join(f"{k:>6s}" for k in KEYS) + "  blocks\n")
+        for sym, blocks in kernels.items():
+            t = totals(blocks)
+            name = re.sub(r"^_ZN\d+[a-z]+\d+", "", sym).split("I", 1)[0] + template_args(sym)
+            out.write(f"  {name:48s}" + "".join(f"{t[k]:6d}" for k in KEYS) + f"  {len(blocks):6d}\n")
+        return
     for sym, blocks in kernels.items():
         out.write(f"{sym} {template_args(sym)}\n")
         out.write("  block        " + "".join(f"{k:>6s}" for k in KEYS) + "  -> targets\n")
@@ -195,6 +202,7 @@ def main():
     ap.add_argument("--asm", help="read this listing instead of compiling")
     ap.add_argument("--kernel", action="append", default=[], help="only symbols containing this text (repeatable)")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--totals", action="store_true", help="one line of totals per kernel instead of the block tables")
     a = ap.parse_args()
     k = analyze(a.src, a.asm)
     if a.kernel:
@@ -202,7 +210,7 @@ def main():
     if a.json:
         json.dump(k, sys.stdout)
     else:
-        render(k)
+        render(k, totals_only=a.totals)
 
 
 if __name__ == "__main__":
