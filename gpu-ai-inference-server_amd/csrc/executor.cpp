@@ -64,6 +64,16 @@ ResizeArgs MakeResizeArgs(const PlanInstance& pi, const Step& s) {
     return a;
 }
 
+LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
+    LnArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    a.gamma = s.w_off >= 0 ? weights + s.w_off : nullptr;
+    a.beta = s.bias_off >= 0 ? weights + s.bias_off : nullptr;
+    a.eps = s.ln_eps;
+    return a;
+}
+
 constexpr size_t kPinnedBytes = size_t(4) << 20;              // pinned staging for results (logits are KBs; larger outputs go direct)
 constexpr int64_t kTuneWorkspaceFloats = int64_t(16) << 20;   // 64 MiB of split-K slabs available to the autotuner
 constexpr int kNumCounters = 1 << 16;
@@ -125,6 +135,10 @@ std::string tune_file_header() {
 // Tune-file codes of the conv choices: base + tile of one kernel family, the family of a code is the last base at or below it.  Codes
 // below 100 are tiles of the tiled implicit GEMM in whichever staging (vec / scalar) the step has.  fp8 plans store their run-time
 // Step::tile (kernels.h kWs8Code, kWs38Code), which lies inside the ranges of the raster and weights-stationary 1x1 codes.
+// kLnTuneCode + tile: a layer_norm step's kernel variant.  Not a conv, so it is no entry of the table below: tune_code_valid and the layer-norm
+// branch of TuneStep know its range.
+constexpr int kLnTuneCode = 1000;
+bool ln_tune_code(int t) { return t >= kLnTuneCode && t < kLnTuneCode + kNumLnTiles; }
 struct TuneFamily { int base; ConvAlgo algo; int tiles; };
 constexpr TuneFamily kTuneFamilies[] = {
     {0, ConvAlgo::IgemmVec, kNumIgemmTiles},          {100, ConvAlgo::Raster3x3, kNumConvRasterTiles},
@@ -147,7 +161,7 @@ int tune_code(ConvAlgo algo, int tile) {
 }
 
 bool tune_code_valid(int t) {
-    return (t >= 0 && t - tune_family(t).base < tune_family(t).tiles) || (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles) ||
+    return (t >= 0 && t - tune_family(t).base < tune_family(t).tiles) || ln_tune_code(t) || (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles) ||
            (t >= kWs38Code && t < kWs38Code + kNumConvWs38Tiles);
 }
 
@@ -893,6 +907,30 @@ float DeviceModel::TimeTrial(TuneContext& ctx, const PlanInstance& pi, const Ste
 }
 
 void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
+    if (s.kind == StepKind::LayerNorm) {
+        // the generic kernel and the lane-group variants that hold the row (tune-file codes kLnTuneCode + tile)
+        // (the channel offsets decide which tiles are eligible: they are part of the signature)
+        const std::vector<int64_t> key = {s.in.n * s.in.h * s.in.w, s.in.c, s.in.pitch, s.out.pitch, s.in.c_off, s.out.c_off, int64_t(s.in.f16), int64_t(s.out.f16), kLnTuneCode,
+                                          s.bias_off >= 0};
+        std::pair<int, int> hit{-1, 0};
+        if (ctx.lookup(key, &hit)) {
+            if (ln_tune_code(hit.first)) s.tile = hit.first - kLnTuneCode;
+            return;
+        }
+        if (!ctx.allow_search) return;
+        const LnArgs a = MakeLnArgs(pi, s, w_->d_weights);
+        float best = 1e30f;
+        int best_t = s.tile;
+        for (int t = 0; t < kNumLnTiles; ++t)
+            if (LayerNormEligible(a, t)) {
+                Step trial = s;
+                trial.tile = t;
+                if (const float ms = TimeTrial(ctx, pi, trial); ms < best) { best = ms; best_t = t; }
+            }
+        s.tile = best_t;
+        ctx.store(key, kLnTuneCode + best_t, 1);
+        return;
+    }
     if (s.kind != StepKind::Conv || s.algo == ConvAlgo::Naive || s.algo == ConvAlgo::Stem) return;
     std::pair<int, int> hit{-1, 0};
     auto cached_tile = [&](const std::vector<int64_t>& key) { return ctx.lookup(key, &hit) ? hit.first : -1; };
@@ -1363,6 +1401,11 @@ SeArgs DeviceModel::MakeSeArgs(const PlanInstance& pi, const Step& s) const {
 // LDS budget, a missing weight mirror ...) -- the hand-over step, built in `scratch`.  LaunchStep launches what this returns and
 // Profile() labels it, so a declined step is reported under the kernel that ran.
 const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Step& scratch) const {
+    if (s.kind == StepKind::LayerNorm && s.tile != 0 && !LayerNormEligible(MakeLnArgs(pi, s, w_->d_weights), s.tile)) {      // the generic kernel takes every layer norm
+        scratch = s;
+        scratch.tile = 0;
+        return scratch;
+    }
     if (s.kind != StepKind::Conv) return s;
     auto with_tile = [&](int tile) -> const Step& {
         if (tile == s.tile) return s;
@@ -1587,6 +1630,10 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             check(LaunchResize(a, ResizePath(a), stream_), "resize");
             break;
         }
+        case StepKind::LayerNorm:
+            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the layer-norm kernels");
+            check(LaunchLayerNorm(MakeLnArgs(pi, s, wb), s.tile, stream_), "layer_norm");
+            break;
     }
 }
 
@@ -1651,6 +1698,9 @@ static std::string kernel_label(const Step& s) {
             const int path = ResizePath(a);
             return path == 0 ? std::string(names[0]) : std::string(names[path]) + (s.in.f16 ? "f16>" : "f32>");
         }
+        case StepKind::LayerNorm:
+            return s.tile == 0 ? std::string("layernorm_generic_kernel")
+                               : std::string("layernorm_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
         case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }
     return "?";

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -21,8 +22,11 @@ struct TensorArg {
 };
 
 // Fused pointwise activations (plan.h ActKind): 0 none, 1 sigmoid, 2 hardsigmoid max(0, min(1, a*x + b)), 3 silu x*sigmoid(x),
-// 4 hardswish x*hardsigmoid(x; a, b), 5 relu.  fp32 math in every element type.
-__host__ __device__ inline float ApplyAct(int kind, float a, float b, float x) {
+// 4 hardswish x*hardsigmoid(x; a, b), 5 relu, 6 gelu 0.5*x*(1 + erf(x / sqrt 2)), 7 its tanh approximation 0.5*x*(1 + tanh(sqrt(2/pi)*(x + 0.044715*x^3))).
+// fp32 math in every element type.
+// ApplyActBasic: codes 0-5 only.  The channel-block kernels whose register budget decides their occupancy (kernels_grouped.hip's fast kernel) call
+// it, so the erf / tanh code of the GELUs is not inlined into them; their eligibility keeps steps with a code above 5 on the generic kernels.
+__host__ __device__ inline float ApplyActBasic(int kind, float a, float b, float x) {
     switch (kind) {
         case 1: return 1.f / (1.f + expf(-x));
         case 2: return fminf(fmaxf(a * x + b, 0.f), 1.f);
@@ -30,6 +34,13 @@ __host__ __device__ inline float ApplyAct(int kind, float a, float b, float x) {
         case 4: return x * fminf(fmaxf(a * x + b, 0.f), 1.f);
         case 5: return fmaxf(x, 0.f);
         default: return x;
+    }
+}
+__host__ __device__ inline float ApplyAct(int kind, float a, float b, float x) {
+    switch (kind) {
+        case 6: return 0.5f * x * (1.f + erff(x * 0.70710678f));
+        case 7: return 0.5f * x * (1.f + tanhf(0.79788456f * (x + 0.044715f * x * x * x)));
+        default: return ApplyActBasic(kind, a, b, x);
     }
 }
 
@@ -196,6 +207,35 @@ constexpr int kNumConvtTiles = 3;
 inline constexpr int kConvtPixelBlocks[kNumConvtTiles] = {0, 1, 2};      // 32-pixel MFMA row blocks per wave
 bool ConvTransposedEligible(const ConvtArgs& a, int tile);
 hipError_t LaunchConvTransposed(const ConvtArgs& a, int tile, hipStream_t stream);
+
+// LayerNormalization over the channels of an NHWC view (kernels_ln.hip): out[p, c] = (in[p, c] - mean_p) * rsqrt(var_p + eps) * gamma[c] + beta[c] for
+// every pixel row p, var_p the mean of the centred squares.  fp32 accumulation; activations float or half (TensorArg::f16); gamma / beta fp32.
+// out may alias in.
+struct LnArgs {
+    TensorArg in, out;                 // the same shape; normalised over c
+    const float* gamma = nullptr;      // [C]
+    const float* beta = nullptr;       // [C] or null
+    float eps = 1e-5f;
+};
+// tile 0: generic (one wave per pixel row; any C, channel stride, pitch, channel offset, mixed element types); tiles 1-4: a group of 8 / 16 / 32 / 64
+// lanes per row, the row held in registers as up to kLnMaxVectors 16-byte vectors (4 floats / 8 halfs) per lane: sc == 1, C / pitch / channel offset
+// multiples of the vector width, 16-byte aligned bases, C <= lanes * kLnMaxVectors * vector width (fp32: 1536 on the 64-lane tile)
+constexpr int kNumLnTiles = 5;
+inline constexpr int kLnLanes[kNumLnTiles] = {0, 8, 16, 32, 64};
+constexpr int kLnMaxVectors = 6;
+constexpr bool LnTileFits(int64_t c, bool f16, int tile) {
+    const int64_t V = f16 ? 8 : 4;
+    return tile >= 1 && tile < kNumLnTiles && c % V == 0 && c / V <= int64_t(kLnLanes[tile]) * kLnMaxVectors;
+}
+// the smallest group that holds the row in at most three vectors per lane (what the load-time search picked on 6 of the 8 spatial layer-norm shapes
+// of ConvNeXt-Tiny, fp32 b32 and fp16 b128: DESIGN 3.22), else the smallest that holds it at all, else the generic kernel
+constexpr int LnDefaultTile(int64_t c, bool f16) {
+    for (int t = 1; t < kNumLnTiles; ++t) if (LnTileFits(c, f16, t) && c / (f16 ? 8 : 4) <= 3 * kLnLanes[t]) return t;
+    for (int t = 1; t < kNumLnTiles; ++t) if (LnTileFits(c, f16, t)) return t;
+    return 0;
+}
+bool LayerNormEligible(const LnArgs& a, int tile);
+hipError_t LaunchLayerNorm(const LnArgs& a, int tile, hipStream_t stream);
 
 // Squeeze-and-excitation block (kernels_se.hip): out = in * gate[n, c], gate = act(W2^T-packed FC(act1(W1 * mean_hw(in) + b1)) + b2).
 // Three phases, four launches: squeeze (fp32 partial sums per pixel chunk), fc1 (means + FC1 + act1 -> hidden [N][mid]), fc2 (FC2 + act -> gate [N][C]),

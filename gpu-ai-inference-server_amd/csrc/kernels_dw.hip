@@ -282,6 +282,7 @@ bool ConvDwEligible(const DwArgs& a, int tile) {
     if (a.in.f8 || a.out.f8 || a.res.f8 || a.in.c != a.out.c || a.out.sc != 1 || a.kh < 1 || a.kw < 1 || a.kh > 7 || a.kw > 7) return false;
     if (a.pre_scale && !a.pre_shift) return false;
     if (tile == 0) return true;
+    if (a.act > 5 || a.pre_act > 5) return false;      // act_sel knows the sigmoid family and ReLU: a fused GELU runs on the generic kernel
     const int V = a.out.f16 ? 8 : 4;
     return a.kh == a.kw && (a.kh == 3 || a.kh == 5) && a.sh == a.sw && (a.sh == 1 || a.sh == 2) && a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) &&
            vec_view_ok(a.out, V) && (!a.res.p || (a.res.f16 == a.out.f16 && vec_view_ok(a.res, V))) && reinterpret_cast<uintptr_t>(a.w) % 16 == 0 &&

@@ -31,21 +31,24 @@ __device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
     return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
 }
 
+// GELU: the activation codes above 5 (kernels.h ApplyAct) are compiled in; the fast kernel leaves them out (ConvGroupedEligible keeps such steps off it)
+template <bool GELU>
 __device__ __forceinline__ float prologue(const GroupedArgs& a, int c, float x) {
     if (a.pre_scale) {
         x = x * a.pre_scale[c] + a.pre_shift[c];
         if (a.pre_relu) x = fmaxf(x, 0.f);
         if (a.pre_hi < __builtin_huge_valf()) x = fminf(x, a.pre_hi);
     }
-    if (a.pre_act) x = ApplyAct(a.pre_act, a.pre_act_a, a.pre_act_b, x);
+    if (a.pre_act) x = GELU ? ApplyAct(a.pre_act, a.pre_act_a, a.pre_act_b, x) : ApplyActBasic(a.pre_act, a.pre_act_a, a.pre_act_b, x);
     return x;
 }
 
+template <bool GELU>
 __device__ __forceinline__ float epilogue(const GroupedArgs& a, float o) {
     if (a.relu) o = fmaxf(o, 0.f);
     if (a.lo > -__builtin_huge_valf()) o = fmaxf(o, a.lo);
     if (a.hi < __builtin_huge_valf()) o = fminf(o, a.hi);
-    if (a.act) o = ApplyAct(a.act, a.act_a, a.act_b, o);
+    if (a.act) o = GELU ? ApplyAct(a.act, a.act_a, a.act_b, o) : ApplyActBasic(a.act, a.act_a, a.act_b, o);
     return o;
 }
 
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(kGrpBlock) void conv_grouped_kernel(const GroupedAr
                     for (int q = 0; q < ICB / V; ++q) load16(src + q * V, v + q * V);
                     if (pre) {
 #pragma unroll
-                        for (int c = 0; c < ICB; ++c) v[c] = prologue(a, i0 + c, v[c]);
+                        for (int c = 0; c < ICB; ++c) v[c] = prologue<false>(a, i0 + c, v[c]);
                     }
                 } else {
 #pragma unroll
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(kGrpBlock) void conv_grouped_kernel(const GroupedAr
             for (int j = 0; j < OCB; ++j) o[j] += rv[j];
         }
 #pragma unroll
-        for (int j = 0; j < OCB; ++j) o[j] = epilogue(a, o[j]);
+        for (int j = 0; j < OCB; ++j) o[j] = epilogue<false>(a, o[j]);
         T* dst = out + int64_t(pn[p]) * a.out.sn + int64_t(py[p]) * a.out.sh + int64_t(px[p]) * a.out.sw + o0;
 #pragma unroll
         for (int q = 0; q < OCB / V; ++q) store16(dst + q * V, o + q * V);
@@ -205,12 +208,12 @@ __global__ __launch_bounds__(kGrpBlock) void conv_grouped_generic_kernel(const G
             const int64_t px = base + int64_t(iy) * a.in.sh + int64_t(ix) * a.in.sw;
             const float* wt = w + (ky * a.kw + kx) * cpg;
             for (int c = 0; c < cpg; ++c)
-                acc = fmaf(wt[c], prologue(a, c0 + c, ld_any(a.in.p, a.in.f16, px + int64_t(c0 + c) * a.in.sc)), acc);
+                acc = fmaf(wt[c], prologue<true>(a, c0 + c, ld_any(a.in.p, a.in.f16, px + int64_t(c0 + c) * a.in.sc)), acc);
         }
     }
     float v = acc + (a.bias ? a.bias[o] : 0.f);
     if (a.res.p) v += ld_any(a.res.p, a.res.f16, int64_t(n) * a.res.sn + int64_t(oy) * a.res.sh + int64_t(ox) * a.res.sw + int64_t(o) * a.res.sc);
-    v = epilogue(a, v);
+    v = epilogue<true>(a, v);
     const int64_t oi = int64_t(n) * a.out.sn + int64_t(oy) * a.out.sh + int64_t(ox) * a.out.sw + o;
     if (a.out.f16) reinterpret_cast<_Float16*>(a.out.p)[oi] = _Float16(v);
     else a.out.p[oi] = v;
@@ -258,6 +261,7 @@ bool ConvGroupedEligible(const GroupedArgs& a, int tile) {
     if (a.in.f8 || a.out.f8 || a.res.f8 || a.in.c % a.groups || a.out.c % a.groups || a.out.sc != 1) return false;
     if (a.kh < 1 || a.kw < 1 || a.kh > 7 || a.kw > 7 || a.sh < 1 || a.sw < 1 || (a.pre_scale && !a.pre_shift)) return false;
     if (tile == 0) return true;
+    if (a.act > 5 || a.pre_act > 5) return false;      // the fast kernel compiles the activations 0-5 only: a fused GELU runs on the generic kernel
     const int cfg = GroupedCfgFor(a.in.c, a.out.c, a.groups);
     const bool f16 = a.out.f16 != 0;
     if (cfg < 0 || !GroupedTileFits(cfg, f16, tile) || a.out.c % (kGroupedCfgs[cfg].opb * kGroupedCfgs[cfg].gpb)) return false;

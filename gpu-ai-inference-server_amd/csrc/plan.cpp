@@ -40,7 +40,7 @@ struct Val {
     bool dedicated = false;             // its buffer is never recycled
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -58,7 +58,8 @@ struct LNode {
     ResizeNearest rs_nearest = ResizeNearest::RoundPreferFloor;
     double rs_sh = 1.0, rs_sw = 1.0;
     std::vector<float> w, bias;         // conv: w packed [Cout][kh][kw][Cin]
-    std::vector<float> s, t;            // affine
+    std::vector<float> s, t;            // affine; L_LAYERNORM: gamma, beta (beta may be empty)
+    float eps = 1e-5f;                  // L_LAYERNORM
     bool has_pre = false, pre_relu = false, relu = false;
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
@@ -87,6 +88,11 @@ struct Lowering {
     std::map<std::string, OnnxTensor> derived;
     // derived initializers computed from a Shape node (and the int64 arithmetic behind it): only a Resize's `sizes` may read them
     std::set<std::string> shape_derived;
+    // Names that read their value channels-last: the result of Transpose(perm [0,2,3,1]) and of every op computed on such a view.  The value
+    // behind the name keeps its NCHW dims, its n / c / h / w and its NHWC storage: the ONNX dims [N, H, W, C] exist only in the graph file, so
+    // no pass ever sees them.  A Transpose emits no node: its output is one more name of its input's value.
+    std::set<std::string> cl_names;
+    bool is_cl(const std::string& name) const { return cl_names.count(name) != 0; }
 
     explicit Lowering(const OnnxModel& mm) : m(mm) {}
 
@@ -104,6 +110,12 @@ struct Lowering {
         vals.push_back(v);
         val_of[name] = int(vals.size()) - 1;
         return int(vals.size()) - 1;
+    }
+    // one more name for value v (a Transpose's output), read channels-last or NCHW
+    void alias_name(const std::string& name, int v, bool channels_last) {
+        if (val_of.count(name) || derived.count(name) || m.initializers.count(name)) fail("ONNX graph error: value defined twice: " + name);
+        val_of[name] = v;
+        if (channels_last) cl_names.insert(name);
     }
     int get_val(const std::string& name) const {
         auto it = val_of.find(name);
@@ -203,7 +215,9 @@ void read_window_attrs(const OnnxNode& on, LNode& n, int64_t h, int64_t w, bool 
 bool DwFastViews(const Step& s) {
     const int64_t V = s.out.f16 ? 8 : 4;
     auto ok = [&](const View& v) { return !v.nchw && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == s.out.f16; };
-    return s.kh == s.kw && (s.kh == 3 || s.kh == 5) && s.sh == s.sw && (s.sh == 1 || s.sh == 2) && ok(s.in) && ok(s.out) && (!s.has_in2 || ok(s.in2));
+    // (the fast kernel's branch-free activation knows the sigmoid family only: a fused GELU runs on the generic kernel)
+    const bool gelu = int(s.act.kind) >= int(ActKind::Gelu) || int(s.pre_act.kind) >= int(ActKind::Gelu);
+    return s.kh == s.kw && (s.kh == 3 || s.kh == 5) && s.sh == s.sw && (s.sh == 1 || s.sh == 2) && !gelu && ok(s.in) && ok(s.out) && (!s.has_in2 || ok(s.in2));
 }
 // 4 output pixels per lane on wide rows, 2 on narrow ones (7x7 maps: 4 groups of 2 instead of 2 of 4, one wasted lane in eight), the generic kernel otherwise
 int DwDefaultTile(const Step& s) { return DwFastViews(s) ? (s.out.w >= 14 ? 3 : 2) : 0; }
@@ -212,6 +226,7 @@ int DwDefaultTile(const Step& s) { return DwFastViews(s) ? (s.out.w >= 14 ? 3 : 
 bool GroupedFastViews(const Step& s, int tile) {
     const int cfg = GroupedCfgFor(s.in.c, s.out.c, s.group);
     if (cfg < 0 || !GroupedTileFits(cfg, s.out.f16, tile) || s.out.c % (kGroupedCfgs[cfg].opb * kGroupedCfgs[cfg].gpb) || s.kh > 7 || s.kw > 7) return false;
+    if (int(s.act.kind) >= int(ActKind::Gelu) || int(s.pre_act.kind) >= int(ActKind::Gelu)) return false;      // (the fast kernel compiles the activations 0-5 only)
     const int64_t V = s.out.f16 ? 8 : 4;
     auto ok = [&](const View& v) { return !v.nchw && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == s.out.f16; };
     return ok(s.in) && ok(s.out) && (!s.has_in2 || ok(s.in2));
@@ -239,6 +254,13 @@ int ConvtDefaultTile(const Step& s) {
     return waves64 >= 2048 ? 2 : 1;
 }
 
+// Layer-norm steps: the views the register-resident kernel needs for `tile` (kernels_ln.hip LayerNormEligible re-checks them with the pointers)
+bool LnFastViews(const Step& s, int tile) {
+    const int64_t V = s.out.f16 ? 8 : 4;
+    auto ok = [&](const View& v) { return !v.nchw && !v.f8 && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == s.out.f16; };
+    return LnTileFits(s.in.c, s.out.f16, tile) && ok(s.in) && ok(s.out);
+}
+
 // Algorithmic FLOPs per element of a fused activation
 double ActFlops(ActKind k) {
     switch (k) {
@@ -247,6 +269,8 @@ double ActFlops(ActKind k) {
         case ActKind::Silu: return 4;
         case ActKind::HardSwish: return 4;
         case ActKind::Relu: return 1;
+        case ActKind::Gelu: return 6;          // scale, erf, add, three multiplies
+        case ActKind::GeluTanh: return 10;     // cube, fma, scale, tanh, add, three multiplies
         default: return 0;
     }
 }
@@ -334,6 +358,9 @@ struct Planner {
     bool FoldConstantNode(const OnnxNode& on);
     bool FoldShapeArithmetic(const OnnxNode& on, const LNode& n);
     bool FoldShapeOnlyOp(const OnnxNode& on, const LNode& n);
+    bool ImportTranspose(const OnnxNode& on, const LNode& n);
+    bool cl_out = false;                   // ImportNode: the importer computed its result on a channels-last view (the output's name is one too)
+    void ImportLayerNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportConv(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportConvTranspose(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
@@ -380,6 +407,7 @@ struct Planner {
     void EmitSqueezeExcite(const LNode& n, Step& s);
     void EmitEltwise(const LNode& n, Step& s);
     void EmitResize(const LNode& n, Step& s) const;
+    void EmitLayerNorm(const LNode& n, Step& s);
 
     // ---- step-level fusions, I/O descriptors ----
     void FuseDenseLayers();
@@ -751,7 +779,9 @@ void Planner::ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odi
     if (!b || b->dims.size() != 2) fail(op + " " + n.name + ": second operand must be a 2-D initializer");
     int x = in_val(on, 0);
     const Val& X = L.vals[x];
-    if (X.h * X.w != 1) fail(op + " " + n.name + ": input must be [N, K]");
+    // a channels-last view [N, H, W, K] times [K, N']: the 1x1 conv of its pixels (ConvNeXt's Linear layers), the result channels-last again
+    const bool cl = L.is_cl(on.inputs[0]);
+    if (!cl && X.h * X.w != 1) fail(op + " " + n.name + ": input must be [N, K]");
     bool transB = op == "Gemm" && on.attr_i("transB", 0) != 0;
     if (op == "Gemm" && on.attr_i("transA", 0) != 0) fail("Gemm " + n.name + ": transA is not supported");
     float alpha = op == "Gemm" ? on.attr_f("alpha", 1.f) : 1.f;
@@ -774,6 +804,7 @@ void Planner::ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odi
     n.in = {x};
     odims = {X.n, N};
     if (X.dims.size() == 1) odims = {N};
+    if (cl) { odims = {X.n, N, X.h, X.w}; cl_out = true; }
 }
 
 void Planner::ImportBatchNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
@@ -801,6 +832,9 @@ void Planner::ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t
     const std::string& op = on.op;
     bool a0 = act_input(on, 0), a1 = act_input(on, 1);
     if (op == "Div" && (a1 || !a0)) fail("Div " + n.name + ": only the division of an activation by a constant is supported");
+    if (a0 && a1 && L.is_cl(on.inputs[0]) != L.is_cl(on.inputs[1]))
+        fail(op + " " + n.name + ": the operands mix a channels-last view and an NCHW value");
+    cl_out = (a0 && L.is_cl(on.inputs[0])) || (a1 && L.is_cl(on.inputs[1]));
     if (a0 && a1 && op == "Mul") {
         // same shapes, or [N,C,H,W] x [N,C,1,1] in either order (a squeeze-excite gate); in[0] = the full tensor
         int a = in_val(on, 0), b = in_val(on, 1);
@@ -835,7 +869,14 @@ void Planner::ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t
         }
         if (m.opset > 0 && m.opset < 7 && on.attr_i("broadcast", 0) == 0 && c->dims != X.dims && c->numel() != 1)
             fail(op + " " + n.name + ": operand shapes differ and the opset-" + std::to_string(m.opset) + " broadcast attribute is not set");
-        bool ok = L.per_channel_const(*c, X, pc, legacy_axis);
+        bool ok = !cl_out && L.per_channel_const(*c, X, pc, legacy_axis);
+        if (cl_out) {
+            // against the ONNX dims [N, H, W, C] numpy broadcasting puts the channels last: a scalar, [C], [1, C] ... [1, 1, 1, C]
+            const bool flt = c->dtype == ONNX_FLOAT || c->dtype == ONNX_DOUBLE || c->dtype == ONNX_FLOAT16;
+            if (flt && c->numel() == 1) { pc.assign(size_t(X.c), c->f[0]); ok = true; }
+            else if (flt && c->numel() == X.c && c->dims.size() <= 4 && !c->dims.empty() && c->dims.back() == X.c) { pc = c->f; ok = true; }
+            if (!ok) fail(op + " " + n.name + ": constant operand must broadcast along the last axis of the channels-last view " + on.inputs[a0 ? 0 : 1]);
+        }
         if (!ok && X.dims.size() == 2 && c->dims.size() == 1 && c->numel() == X.c) { pc = c->f; ok = true; }
         if (!ok && X.dims.size() == 2 && c->dims.size() == 2 && c->dims[0] == 1 && c->dims[1] == X.c) { pc = c->f; ok = true; }
         if (!ok) fail(op + " " + n.name + ": constant operand must broadcast per channel");
@@ -856,7 +897,7 @@ void Planner::ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t
     } else fail(op + " " + n.name + ": constant folding of two initializers is not supported");
 }
 
-// Clip, Sigmoid / HardSigmoid / HardSwish, Relu
+// Clip, Sigmoid / HardSigmoid / HardSwish / Gelu, Relu, Erf
 void Planner::ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
     const std::string& op = on.op;
     if (op == "Clip") {
@@ -878,9 +919,23 @@ void Planner::ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t
         n.kind = L_RELU;
         n.in = {in_val(on, 0)};
         odims = L.vals[n.in[0]].dims;
+    } else if (op == "Erf") {
+        // only as the middle of the five-node GELU pattern (FuseActivationPatterns); alone it is refused there
+        if (!act_input(on, 0)) fail(op + " " + n.name + ": constant input is not supported");
+        n.kind = L_ERF;
+        n.in = {in_val(on, 0)};
+        odims = L.vals[n.in[0]].dims;
+        cl_out = L.is_cl(on.inputs[0]);
     } else {
         n.kind = L_ACT;
-        if (op == "Sigmoid") n.act.kind = ActKind::Sigmoid;
+        if (op == "Gelu") {
+            const auto ap = on.attrs.find("approximate");
+            const std::string mode = ap == on.attrs.end() || ap->second.s.empty() ? "none" : ap->second.s;
+            if (mode != "none" && mode != "tanh") fail("Gelu " + n.name + ": approximate '" + mode + "' is not supported (none and tanh are)");
+            n.act.kind = mode == "tanh" ? ActKind::GeluTanh : ActKind::Gelu;
+            cl_out = L.is_cl(on.inputs[0]);
+        }
+        else if (op == "Sigmoid") n.act.kind = ActKind::Sigmoid;
         else if (op == "HardSigmoid") { n.act.kind = ActKind::HardSigmoid; n.act.a = on.attr_f("alpha", 0.2f); n.act.b = on.attr_f("beta", 0.5f); }
         else { n.act.kind = ActKind::HardSwish; n.act.a = 1.f / 6.f; n.act.b = 0.5f; }
         if (!act_input(on, 0)) fail(op + " " + n.name + ": constant input is not supported");
@@ -1066,20 +1121,78 @@ void Planner::ImportResize(const OnnxNode& on, LNode& n, std::vector<int64_t>& o
     odims = {out[0], out[1], out[2], out[3]};
 }
 
+// LayerNormalization-17 over the channel axis: the last axis of a channels-last view or of an [N, C] value.  (axis = 1 of an NCHW value would
+// normalise over C*H*W: refused.)
+void Planner::ImportLayerNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    if (!act_input(on, 0)) fail("LayerNormalization " + n.name + ": constant input is not supported");
+    const int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    const bool cl = L.is_cl(on.inputs[0]);
+    const int64_t rank = int64_t(X.dims.size()), axis_attr = on.attr_i("axis", -1);
+    const int64_t axis = axis_attr < 0 ? axis_attr + rank : axis_attr;
+    if (!(cl ? axis == rank - 1 : (rank == 2 && axis == 1)))
+        fail("LayerNormalization " + n.name + ": axis = " + std::to_string(axis_attr) + " on " + (cl ? std::string("a channels-last view") : "an NCHW value of rank " + std::to_string(rank)) +
+             " is not supported (only the channel axis alone is normalised: the last axis of a channels-last view or of an [N, C] value)");
+    if (on.attr_i("stash_type", 1) != 1) fail("LayerNormalization " + n.name + ": stash_type = " + std::to_string(on.attr_i("stash_type", 1)) + " is not supported (1 is)");
+    for (size_t k = 1; k < on.outputs.size(); ++k)
+        if (!on.outputs[k].empty()) fail("LayerNormalization " + n.name + ": the Mean / InvStdDev outputs are not supported");
+    const OnnxTensor* g = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
+    if (!g || g->dims.size() != 1 || g->numel() != X.c) fail("LayerNormalization " + n.name + ": scale must be a [C] initializer");
+    n.s = g->f;
+    if (on.inputs.size() > 2 && !on.inputs[2].empty()) {
+        const OnnxTensor* b = L.init(on.inputs[2]);
+        if (!b || b->dims.size() != 1 || b->numel() != X.c) fail("LayerNormalization " + n.name + ": B must be a [C] initializer");
+        n.t = b->f;
+    }
+    n.kind = L_LAYERNORM;
+    n.eps = on.attr_f("epsilon", 1e-5f);
+    n.in = {x};
+    odims = X.dims;
+    cl_out = cl;
+}
+
+// Transpose is a view of the NHWC storage, never a kernel: perm [0,2,3,1] of a 4-D value reads it channels-last, perm [0,3,1,2] of such a view
+// reads it as NCHW again.  The output becomes one more name of the input's value (no node, no step).  true: the node is done
+bool Planner::ImportTranspose(const OnnxNode& on, const LNode& n) {
+    if (on.op != "Transpose") return false;
+    if (!act_input(on, 0)) fail("Transpose " + n.name + ": constant input is not supported");
+    const std::vector<int64_t> perm = on.attr_ints("perm", {});
+    std::string ps = "[";
+    for (size_t k = 0; k < perm.size(); ++k) ps += (k ? "," : "") + std::to_string(perm[k]);
+    ps += "]";
+    const int v = in_val(on, 0);
+    const bool cl = L.is_cl(on.inputs[0]);
+    const bool to_cl = perm == std::vector<int64_t>{0, 2, 3, 1}, from_cl = perm == std::vector<int64_t>{0, 3, 1, 2};
+    if (L.vals[v].dims.size() != 4 || !((to_cl && !cl) || (from_cl && cl)))
+        fail("Transpose " + n.name + ": perm " + ps + " on " + (cl ? "a channels-last view" : "an NCHW value of rank " + std::to_string(L.vals[v].dims.size())) +
+             " is not supported (only [0,2,3,1] on a 4-D NCHW value and [0,3,1,2] on its channels-last view are)");
+    L.alias_name(on.outputs[0], v, to_cl);
+    return true;
+}
+
 // ---- one ONNX node -> one logical node with shape inference (or a derived initializer) ----
 void Planner::ImportNode(const OnnxNode& on) {
     if (FoldConstantNode(on)) return;
     if (on.outputs.empty() || on.inputs.empty()) fail("node " + on.name + " (" + on.op + ") has no inputs/outputs");
     LNode n;
     n.name = on.name.empty() ? on.outputs[0] : on.name;
-    if (FoldShapeArithmetic(on, n) || FoldShapeOnlyOp(on, n)) return;
     const std::string& op = on.op;
+    // a channels-last view may feed only the ops that read it as one: anything else (a Shape and the other folded ops included, hence before
+    // the folds) would take its n / c / h / w for the ONNX dims
+    static const std::set<std::string> cl_ops = {"LayerNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose"};
+    for (const std::string& name : on.inputs)
+        if (L.is_cl(name) && !cl_ops.count(op))
+            fail(op + " " + n.name + ": input " + name + " is a channels-last view (a Transpose with perm [0,2,3,1]); only LayerNormalization, MatMul, Add, Mul, Div, Erf, "
+                 "Gelu and Transpose may read one");
+    if (FoldShapeArithmetic(on, n) || FoldShapeOnlyOp(on, n) || ImportTranspose(on, n)) return;
     std::vector<int64_t> odims;
+    cl_out = false;
     if (op == "Conv") ImportConv(on, n, odims);
     else if (op == "ConvTranspose") ImportConvTranspose(on, n, odims);
     else if (op == "MatMul" || op == "Gemm") ImportGemm(on, n, odims);
     else if (op == "BatchNormalization") ImportBatchNorm(on, n, odims);
-    else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu") ImportActivation(on, n, odims);
+    else if (op == "LayerNormalization") ImportLayerNorm(on, n, odims);
+    else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu" || op == "Erf" || op == "Gelu") ImportActivation(on, n, odims);
     else if (op == "Add" || op == "Mul" || op == "Div") ImportArithmetic(on, n, odims);
     else if (op == "Concat") ImportConcat(on, n, odims);
     else if (op == "MaxPool" || op == "AveragePool" || op == "GlobalAveragePool") ImportPool(on, n, odims);
@@ -1087,6 +1200,7 @@ void Planner::ImportNode(const OnnxNode& on) {
     else if (op == "Resize" || op == "Upsample") ImportResize(on, n, odims);
     else fail("Unsupported ONNX operator: " + op + " (node " + n.name + ")");
     n.out = L.new_val(on.outputs[0], odims);
+    if (cl_out) L.cl_names.insert(on.outputs[0]);
     L.vals[n.out].producer = int(L.nodes.size());
     L.nodes.push_back(std::move(n));
 }
@@ -1094,6 +1208,7 @@ void Planner::ImportNode(const OnnxNode& on) {
 void Planner::MarkOutputs() {
     for (const auto& vo : m.outputs) {
         int v = L.get_val(vo.name);
+        if (L.is_cl(vo.name)) fail("graph output " + vo.name + " is a channels-last view (a Transpose with perm [0,2,3,1]); outputs are NCHW: transpose it back with perm [0,3,1,2]");
         L.vals[v].is_output = true;
     }
 }
@@ -1106,9 +1221,10 @@ void Planner::RefuseForF8() const {
         if (n.kind == L_CONV && n.group != 1) fail("grouped convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_CONV && (n.dil_h > 1 || n.dil_w > 1)) fail("dilated convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_RESIZE) fail("Resize is not supported in fp8 mode (node " + n.name + ")");
+        if (n.kind == L_LAYERNORM) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
     }
     for (const LNode& n : L.nodes)
-        if (n.kind == L_ACT || n.kind == L_MUL)
+        if (n.kind == L_ACT || n.kind == L_MUL || n.kind == L_ERF)
             fail("activation and squeeze-excite nodes (Sigmoid, HardSigmoid, HardSwish, Mul of two activations) are not supported in fp8 mode (node " + n.name + ")");
 }
 
@@ -1131,6 +1247,38 @@ void Planner::FuseActivationPatterns() {
             break;
         }
     }
+    // GELU as exporters write it below opset 20: Div(x, sqrt 2) | Mul(x, 1 / sqrt 2) -> Erf -> Add 1 -> Mul x (either order) -> Mul 0.5, every
+    // intermediate read by the next node only.  The constants must be the GELU's to 1e-6 relative: a near miss is not approximated, its Erf is
+    // refused like any Erf outside the pattern.
+    auto uniform_affine = [&](const LNode& a, double sv, double tv) {
+        if (a.dead || a.kind != L_AFFINE || a.relu) return false;
+        for (float v : a.s) if (std::fabs(double(v) - sv) > 1e-6 * std::fabs(sv)) return false;
+        for (float v : a.t) if (std::fabs(double(v) - tv) > 1e-6 * std::fabs(tv)) return false;
+        return true;
+    };
+    auto only_reader = [&](int v) -> LNode* { return single_consumer(v) ? &L.nodes[size_t(L.consumers(v)[0])] : nullptr; };
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& e = L.nodes[i];
+        if (e.dead || e.kind != L_ERF) continue;
+        const int p = L.vals[e.in[0]].producer;
+        LNode* dv = p >= 0 && single_consumer(e.in[0]) ? &L.nodes[size_t(p)] : nullptr;
+        LNode* a1 = only_reader(e.out);
+        LNode* mu = a1 ? only_reader(a1->out) : nullptr;
+        LNode* hf = mu ? only_reader(mu->out) : nullptr;
+        if (!dv || !hf || !uniform_affine(*dv, 0.70710678118654752, 0.0) || !uniform_affine(*a1, 1.0, 1.0) || !uniform_affine(*hf, 0.5, 0.0)) continue;
+        const int x = dv->in[0];
+        if (mu->dead || mu->kind != L_MUL || L.vals[mu->in[0]].dims != L.vals[mu->in[1]].dims || !((mu->in[0] == x && mu->in[1] == a1->out) || (mu->in[1] == x && mu->in[0] == a1->out)))
+            continue;
+        hf->kind = L_ACT;
+        hf->act = Act{ActKind::Gelu, 0.f, 0.f};
+        hf->in = {x};
+        hf->s.clear();
+        hf->t.clear();
+        hf->name = dv->name + "+" + e.name + "+" + a1->name + "+" + mu->name + "+" + hf->name;
+        dv->dead = e.dead = a1->dead = mu->dead = true;
+    }
+    for (const LNode& e : L.nodes)
+        if (!e.dead && e.kind == L_ERF) fail("Unsupported ONNX operator: Erf (node " + e.name + ")");
 }
 
 // ---- squeeze-excite: GlobalAveragePool -> Conv1x1 -> ReLU | act -> Conv1x1 -> act -> Mul(x, gate) as ONE node, where x is read by the pool
@@ -2011,6 +2159,22 @@ void Planner::EmitResize(const LNode& n, Step& s) const {
     s.flops = n.rs_mode == ResizeMode::Linear ? 6.0 * double(s.out.numel()) : 0.0;    // two lerps per axis pair: 3 FMA-equivalents
 }
 
+// layer norm: gamma at w_off, beta at bias_off (fp32 in every precision); the tile is the smallest lane group that holds the row in three 16-byte
+// vectors per lane (kernels.h LnDefaultTile), IE_FORCE_TILE picks among the eligible ones (an ineligible one: the generic kernel)
+void Planner::EmitLayerNorm(const LNode& n, Step& s) {
+    if (s.in.f8 || s.out.f8) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::LayerNorm;
+    s.w_off = push_vec(n.s);
+    if (!n.t.empty()) s.bias_off = push_vec(n.t);
+    s.ln_eps = n.eps;
+    const int def = LnDefaultTile(s.in.c, s.out.f16);
+    s.tile = def > 0 && LnFastViews(s, def) ? def : 0;
+    const int t = ForcedTile(kNumLnTiles);
+    if (t >= 0) s.tile = t == 0 || LnFastViews(s, t) ? t : 0;
+    s.flops = 8.0 * double(s.in.numel());
+    s.bytes = vbytes(s.in) + vbytes(s.out);
+}
+
 // ---- emit steps --------------------------------------------------------------------------------
 void Planner::EmitSteps() {
     for (int idx : order) {
@@ -2034,6 +2198,7 @@ void Planner::EmitSteps() {
             case L_SE: EmitSqueezeExcite(n, s); break;
             case L_ACT: case L_MUL: case L_AFFINE: case L_CLIP: case L_RELU: case L_ADD: EmitEltwise(n, s); break;
             case L_RESIZE: EmitResize(n, s); break;
+            case L_LAYERNORM: EmitLayerNorm(n, s); break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -2404,7 +2569,7 @@ static void json_view(std::ostringstream& o, const View& v) {
       << ",\"f16\":" << (v.f16 ? "true" : "false") << ",\"f8\":" << (v.f8 ? "true" : "false") << "}";
 }
 static void json_act(std::ostringstream& o, const char* key, const Act& a) {
-    static const char* names[] = {"none", "sigmoid", "hardsigmoid", "silu", "hardswish", "relu"};
+    static const char* names[] = {"none", "sigmoid", "hardsigmoid", "silu", "hardswish", "relu", "gelu", "gelu_tanh"};
     o << ",\"" << key << "\":[\"" << names[int(a.kind)] << "\"," << a.a << "," << a.b << "]";
 }
 static std::string json_escape(const std::string& s) {
@@ -2414,7 +2579,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm"};
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
@@ -2475,6 +2640,7 @@ std::string PlanToJson(const Plan& p) {
         if (s.kind == StepKind::Resize)
             o << ",\"resize\":{\"mode\":\"" << rs_modes[int(s.rs_mode)] << "\",\"coord\":\"" << rs_coords[int(s.rs_coord)] << "\",\"nearest\":\""
               << rs_nearest[int(s.rs_nearest)] << "\",\"scales\":[" << s.rs_scale_h << "," << s.rs_scale_w << "]}";
+        if (s.kind == StepKind::LayerNorm) o << ",\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile;      // (layer-norm steps only)
         if (!s.parts.empty()) {
             Plan sub;
             sub.steps = s.parts;

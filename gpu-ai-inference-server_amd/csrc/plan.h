@@ -38,7 +38,7 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7 };
 
 // Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
 enum class ResizeMode : int { Nearest = 0, Linear = 1 };
@@ -47,7 +47,9 @@ enum class ResizeNearest : int { RoundPreferFloor = 0, RoundPreferCeil = 1, Floo
 
 // Pointwise activation fused into a step (kernels.h ApplyAct): sigmoid(x), hardsigmoid(x) = max(0, min(1, a*x + b)), silu(x) = x * sigmoid(x),
 // hardswish(x) = x * hardsigmoid(x; a, b) (the ONNX HardSwish op: a = 1/6, b = 1/2).  Relu only as a squeeze-excite block's inner activation.
-enum class ActKind : int { None = 0, Sigmoid = 1, HardSigmoid = 2, Silu = 3, HardSwish = 4, Relu = 5 };
+// gelu(x) = 0.5 * x * (1 + erf(x / sqrt 2)) (the ONNX Gelu op, or the five-node Erf pattern exporters write below opset 20); GeluTanh its tanh
+// approximation (Gelu with approximate = "tanh").
+enum class ActKind : int { None = 0, Sigmoid = 1, HardSigmoid = 2, Silu = 3, HardSwish = 4, Relu = 5, Gelu = 6, GeluTanh = 7 };
 struct Act {
     ActKind kind = ActKind::None;
     float a = 0.f, b = 0.f;
@@ -124,6 +126,9 @@ struct Step {
     ResizeCoord rs_coord = ResizeCoord::HalfPixel;
     ResizeNearest rs_nearest = ResizeNearest::RoundPreferFloor;
     double rs_scale_h = 1.0, rs_scale_w = 1.0;
+    // LayerNorm (kernels_ln.hip): out = (in - mean_c) * rsqrt(var_c + ln_eps) * gamma + beta per pixel row; w_off = gamma [C], bias_off = beta [C] or
+    // -1, fp32 in every precision; tile = the kernel variant (kernels.h kNumLnTiles)
+    float ln_eps = 1e-5f;
     ConvAlgo algo = ConvAlgo::Naive;
     int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)

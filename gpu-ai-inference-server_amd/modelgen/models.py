@@ -1,5 +1,5 @@
 """Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY,
-FCN-ResNet50, DeepLabV3-ResNet50, U-Net and small test graphs).
+FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -153,6 +153,51 @@ class GraphBuilder:
         """SiLU as exporters write it: Mul(x, Sigmoid(x)) (swap: Mul(Sigmoid(x), x))."""
         g = self.sigmoid(x)
         return self.simple("Mul", [g, x] if swap else [x, g])
+
+    # ---- ConvNeXt: channels-last views, layer norm, GELU, Linear ----
+    def transpose(self, x: str, perm: Sequence[int]) -> str:
+        return self.simple("Transpose", [x], [pb.attr_ints("perm", list(perm))])
+
+    def layernorm(self, x: str, c: int, eps: float = 1e-6, axis: int = -1, name: str | None = None, bias: bool = True) -> str:
+        """LayerNormalization-17 over the trailing axes from `axis`; scale / B are [c] initializers around 1 / 0."""
+        name = name or self._uid("ln")
+        g = np.float32(1.0) + (rng.uniform(self.seed, name + "_g", c) - np.float32(0.5)) * np.float32(0.2)
+        ins = [x, self.init(name + "_scale", g.astype(np.float32))]
+        if bias:
+            b = (rng.uniform(self.seed, name + "_b", c) - np.float32(0.5)) * np.float32(0.2)
+            ins.append(self.init(name + "_B", b.astype(np.float32)))
+        y = name + "_out"
+        self.nodes.append(pb.node("LayerNormalization", ins, [y], name, [pb.attr_int("axis", axis), pb.attr_float("epsilon", eps)]))
+        return y
+
+    def gelu(self, x: str, form: str = "erf", swap: bool = False, half: float = 0.5) -> str:
+        """GELU in the forms exporters write:
+          "erf"      Div(x, sqrt 2) -> Erf -> Add 1 -> Mul(x, .) -> Mul(., 0.5)   (torch below opset 20; swap: both Mul operand orders reversed)
+          "erf_mul"  the same with Mul(x, 1 / sqrt 2) in place of the Div
+          "op"       the opset-20 Gelu operator, approximate = "none";  "op_tanh": approximate = "tanh"
+        half: the last constant (0.5 for a GELU; tests write near misses)."""
+        if form in ("op", "op_tanh"):
+            return self.simple("Gelu", [x], [pb.attr_str("approximate", "tanh" if form == "op_tanh" else "none")])
+        name = self._uid("gelu")
+        if form == "erf":
+            y = self.simple("Div", [x, self.init(name + "_sqrt2", np.array(np.sqrt(2.0), np.float32))])
+        elif form == "erf_mul":
+            y = self.simple("Mul", [x, self.init(name + "_rsqrt2", np.array(1.0 / np.sqrt(2.0), np.float32))])
+        else:
+            raise ValueError(form)
+        y = self.simple("Add", [self.simple("Erf", [y]), self.init(name + "_one", np.array(1.0, np.float32))])
+        y = self.simple("Mul", [y, x] if swap else [x, y])
+        h = self.init(name + "_half", np.array(half, np.float32))
+        return self.simple("Mul", [h, y] if swap else [y, h])
+
+    def linear(self, x: str, cin: int, cout: int, name: str | None = None, w_scale: float | None = None) -> str:
+        """torch's Linear on a [..., cin] tensor as the exporter writes it: MatMul with a [cin, cout] initializer, then Add [cout]."""
+        name = name or self._uid("fc")
+        std = w_scale if w_scale is not None else float(np.sqrt(1.0 / cin))
+        w = rng.gaussish(self.seed, name + "_w", cin * cout).reshape(cin, cout) * np.float32(std)
+        b = (rng.uniform(self.seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
+        y = self.simple("MatMul", [x, self.init(name + "_w", w.astype(np.float32))])
+        return self.simple("Add", [y, self.init(name + "_b", b.astype(np.float32))])
 
     def act(self, x: str, kind: str, form: str = "op") -> str:
         """kind: relu | hardswish | silu | sigmoid | hardsigmoid | relu6 | none"""
@@ -752,6 +797,56 @@ def efficientnet_b0(batch: int | str = 1, *, width_mult: float = 1.0, image: int
     bfc = (rng.uniform(seed, "fc_b", classes) - np.float32(0.5)) * np.float32(0.2)
     gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))], [pb.attr_int("transB", 1)], out=out_name)
     return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=13)
+
+
+def _convnext_block(gb: GraphBuilder, x: str, c: int, tag: str, gelu: str, gelu_swap: bool, out: str | None = None) -> str:
+    """depthwise 7x7 (bias) -> Transpose(0,2,3,1) -> LayerNorm -> Linear c -> 4c -> GELU -> Linear 4c -> c -> Transpose(0,3,1,2) -> layer scale [c,1,1] -> + x"""
+    y = gb.conv(x, c, c, 7, pad=3, bias=True, group=c, name=tag + "_dw")
+    y = gb.layernorm(gb.transpose(y, (0, 2, 3, 1)), c, name=tag + "_ln")
+    y = gb.gelu(gb.linear(y, c, 4 * c, name=tag + "_fc1"), gelu, gelu_swap)
+    y = gb.transpose(gb.linear(y, 4 * c, c, name=tag + "_fc2", w_scale=float(np.sqrt(2.0 / (4 * c)))), (0, 3, 1, 2))
+    ls = np.float32(0.5) + rng.uniform(gb.seed, tag + "_scale", c)
+    y = gb.simple("Mul", [gb.init(tag + "_scale", ls.reshape(c, 1, 1).astype(np.float32)), y])
+    return gb.simple("Add", [y, x], out=out)
+
+
+def convnext_block(batch: int | str, c: int, hw: int, *, gelu: str = "erf", gelu_swap: bool = False, seed: int = 7) -> bytes:
+    """One ConvNeXt block alone: x [batch, c, hw, hw] -> y of the same shape."""
+    gb = GraphBuilder("convnext_block", seed)
+    _convnext_block(gb, "x", c, "blk", gelu, gelu_swap, out="y")
+    return gb.finish([("x", [batch, c, hw, hw])], [("y", [batch, c, hw, hw])], opset=20 if gelu.startswith("op") else 17)
+
+
+def convnext(batch: int | str = 1, *, depths: Sequence[int] = (3, 3, 9, 3), dims: Sequence[int] = (96, 192, 384, 768), image: int = 224,
+             classes: int = 1000, gelu: str = "erf", gelu_swap: bool = False, seed: int = 2020, in_name: str = "input", out_name: str = "logits") -> bytes:
+    """ConvNeXt (Liu et al. 2022) as torchvision's exporter writes it at opset 17: stem conv 4x4/s4 (bias) -> LayerNorm over the channels; per stage
+    `depth` blocks [depthwise 7x7 (bias) -> LayerNorm -> Linear C -> 4C -> GELU -> Linear 4C -> C -> layer scale -> + input]; between the stages
+    LayerNorm -> conv 2x2/s2 (bias); GlobalAveragePool -> LayerNorm -> Flatten -> Gemm.  torch's LayerNorm / Linear act on the last axis, so every
+    LayerNorm and every block's MLP sits between Transpose(0,2,3,1) and Transpose(0,3,1,2).  gelu: a GraphBuilder.gelu form (the op forms need
+    opset 20).  The layer scales are drawn from [0.5, 1.5), not torchvision's initial 1e-6, at which every block is the identity to seven digits
+    and a broken block would pass every network test."""
+    gb = GraphBuilder("convnext", seed)
+
+    def ln2d(x: str, c: int, name: str) -> str:
+        return gb.transpose(gb.layernorm(gb.transpose(x, (0, 2, 3, 1)), c, name=name), (0, 3, 1, 2))
+
+    c = dims[0]
+    x = ln2d(gb.conv(in_name, 3, c, 4, stride=4, bias=True, name="stem"), c, "stem_ln")
+    for si, (depth, dim) in enumerate(zip(depths, dims)):
+        if si > 0:
+            x = gb.conv(ln2d(x, c, f"down{si}_ln"), c, dim, 2, stride=2, bias=True, name=f"down{si}")
+            c = dim
+        for bi in range(depth):
+            x = _convnext_block(gb, x, c, f"s{si}b{bi}", gelu, gelu_swap)
+    x = gb.simple("Flatten", [ln2d(gb.gap(x), c, "head_ln")], [pb.attr_int("axis", 1)])
+    wfc = rng.gaussish(seed, "fc_w", classes * c).reshape(classes, c) * np.float32(np.sqrt(1.0 / c))
+    bfc = (rng.uniform(seed, "fc_b", classes) - np.float32(0.5)) * np.float32(0.2)
+    gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))], [pb.attr_int("transB", 1)], out=out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=20 if gelu.startswith("op") else 17)
+
+
+def convnext_tiny(batch: int | str = 1, **kw) -> bytes:
+    return convnext(batch, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), **kw)
 
 
 def write_repo(root: str, name: str, model_bytes: bytes, version: str = "1", config_json: str | None = None) -> str:

@@ -14,7 +14,9 @@ max(bytes / 6.29 TB/s, FLOPs / peak) with peak = 157.3 TF (fp32) or 2.5 PF (fp16
 F.conv2d(groups=g) on channels_last tensors for the same shape.
 For transposed convolutions (unet): the graph-replay time as the median of 50 single replays, the transposed steps' share of the eager forward,
 and per step the launched kernel (IE_FORCE_TILE=0 / 1 / 2 picks the generic kernel / the MFMA tiles), its algorithmic TB/s against the copy
-rate, its roofline and torch's F.conv_transpose2d on channels_last tensors for the same shape."""
+rate, its roofline and torch's F.conv_transpose2d on channels_last tensors for the same shape.
+For layer-norm steps (convnext_tiny): their share of the eager forward, next to the depthwise, the GELU (eltwise) and the remaining steps' shares, and
+per distinct shape the launched kernel and its algorithmic GB/s (one read + one write) against the copy rate."""
 import json
 import os
 import subprocess
@@ -188,6 +190,21 @@ if cts:
         shape = f"{s['in']['h']}x{s['in']['w']}x{s['in']['c']}->{s['out']['c']}"
         ks = f"{s['k'][0]}/{s['stride'][0]}"
         print(f"{p['name'][:16]:16} {p['kernel'][:30]:30} {shape:>20} {ks:>5} {p['ms']:8.4f} {tbs:6.2f} {tbs / 6.29 * 100:6.1f}% {roof:8.4f} {roof / p['ms'] * 100:5.1f}% {t:9.4f}")
+lns = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "layer_norm"]
+if lns:
+    share = lambda ps: sum(p["ms"] for p, _ in ps)  # noqa: E731
+    elt = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "eltwise"]
+    print(f"# {len(lns)} layer-norm steps: {share(lns):.4f} ms, {share(lns) / tot * 100:.1f}% of the eager forward; {len(dws)} depthwise steps: {share(dws):.4f} ms, "
+          f"{share(dws) / tot * 100:.1f}%; {len(elt)} eltwise steps: {share(elt):.4f} ms, {share(elt) / tot * 100:.1f}%; the other steps: "
+          f"{tot - share(lns) - share(dws) - share(elt):.4f} ms")
+    print(f"{'layer-norm shape':>16} {'steps':>5} {'kernel':28} {'ms (median)':>11} {'GB/s':>7} {'%6.29T':>7}")
+    seen = {}
+    for p, s in lns:
+        seen.setdefault((s["in"]["h"], s["in"]["w"], s["in"]["c"], p["kernel"]), []).append(p)
+    for (h, w, c, kern), ps in seen.items():
+        ms = sorted(q["ms"] for q in ps)[len(ps) // 2]
+        gbs = ps[0]["bytes"] / ms / 1e6
+        print(f"{f'{h}x{w}x{c}':>16} {len(ps):5d} {kern:28} {ms:11.4f} {gbs:7.0f} {gbs / 6290 * 100:6.1f}%")
 if dws or ses or grs:
     import time
     B.RunPrepared(m, 10, True)
