@@ -74,6 +74,16 @@ LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     return a;
 }
 
+AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s) {
+    AttnArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    a.heads = s.heads;
+    a.head_dim = s.head_dim;
+    a.scale = s.attn_scale;
+    return a;
+}
+
 constexpr size_t kPinnedBytes = size_t(4) << 20;              // pinned staging for results (logits are KBs; larger outputs go direct)
 constexpr int64_t kTuneWorkspaceFloats = int64_t(16) << 20;   // 64 MiB of split-K slabs available to the autotuner
 constexpr int kNumCounters = 1 << 16;
@@ -214,6 +224,7 @@ DeviceModel::DeviceModel(std::shared_ptr<const OnnxModel> model, int device_id, 
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsX6();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsBlock();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsWs8();
+        if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsAttn();
     });
     check(g_kernels_err, "InitKernels");
     fp32_split_ = opt.fp32_split && opt.precision == Precision::F32;
@@ -1406,6 +1417,11 @@ const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Ste
         scratch.tile = 0;
         return scratch;
     }
+    if (s.kind == StepKind::Attention && s.tile != 0 && !AttentionEligible(MakeAttnArgs(pi, s), s.tile)) {      // the generic kernel takes every attention
+        scratch = s;
+        scratch.tile = 0;
+        return scratch;
+    }
     if (s.kind != StepKind::Conv) return s;
     auto with_tile = [&](int tile) -> const Step& {
         if (tile == s.tile) return s;
@@ -1634,6 +1650,20 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the layer-norm kernels");
             check(LaunchLayerNorm(MakeLnArgs(pi, s, wb), s.tile, stream_), "layer_norm");
             break;
+        case StepKind::TokenAssemble: {
+            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the token kernels");
+            TokenAssembleArgs a;
+            a.in = make_arg(pi, s.in);
+            a.out = make_arg(pi, s.out);
+            a.cls = wp(s.w_off);
+            a.pos = wp(s.bias_off);
+            check(LaunchTokenAssemble(a, stream_), "token_assemble");
+            break;
+        }
+        case StepKind::Attention:
+            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the attention kernels");
+            check(LaunchAttention(MakeAttnArgs(pi, s), s.tile, stream_), "attention");
+            break;
     }
 }
 
@@ -1701,6 +1731,10 @@ static std::string kernel_label(const Step& s) {
         case StepKind::LayerNorm:
             return s.tile == 0 ? std::string("layernorm_generic_kernel")
                                : std::string("layernorm_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
+        case StepKind::TokenAssemble: return std::string("token_assemble_kernel<") + (s.out.f16 ? "f16>" : "f32>");
+        case StepKind::Attention:
+            return s.tile == 0 ? std::string("attention_generic_kernel")
+                               : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
         case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }
     return "?";

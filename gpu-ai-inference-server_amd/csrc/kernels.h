@@ -237,6 +237,42 @@ constexpr int LnDefaultTile(int64_t c, bool f16) {
 bool LayerNormEligible(const LnArgs& a, int tile);
 hipError_t LaunchLayerNorm(const LnArgs& a, int tile, hipStream_t stream);
 
+// Multi-head attention over a token view (kernels_attn.hip).  in = the qkv rows [N, L, 3 D] (in.w = L, in.c = 3 D, D = heads * head_dim): column
+// s * D + h * head_dim + e of a row is element e of head h of q / k / v for s = 0 / 1 / 2.  out[n, i, h * head_dim + e] =
+// sum_j softmax_j(scale * q[n, h, i, :] . k[n, h, j, :]) * v[n, h, j, e].  fp32 scores, statistics and accumulation; no score matrix in memory.
+struct AttnArgs {
+    TensorArg in, out;
+    int heads = 0, head_dim = 0;
+    float scale = 1.f;
+};
+// tile 0: attention_generic_kernel (one wave per query row; any L, head_dim, pitch, offset; float or half).  tile 1: attention_mfma_kernel<T, HD>
+// (a workgroup = one image, one head, 128 queries; the head's K and V rows in LDS): head_dim 32 or 64, the channel counts, pitches and offsets
+// multiples of the 16-byte vector, and both of the head's padded K and V images inside the LDS budget
+constexpr int kNumAttnTiles = 2;
+constexpr int64_t kAttnLdsBudget = 160 * 1024;
+// bytes of LDS the MFMA kernel needs: K and V rows, L padded to whole 32-key tiles, every row padded by one 16-byte vector
+constexpr int64_t AttnLdsBytes(int64_t L, int hd, bool f16) {
+    return 2 * ((L + 31) / 32 * 32) * (int64_t(hd) * (f16 ? 2 : 4) + 16);
+}
+constexpr bool AttnMfmaFits(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out) {
+    const int64_t V = f16 ? 8 : 4;
+    return (hd == 32 || hd == 64) && L >= 1 && c_in % V == 0 && pitch_in % V == 0 && off_in % V == 0 && c_out % V == 0 && pitch_out % V == 0 && off_out % V == 0 &&
+           AttnLdsBytes(L, hd, f16) <= kAttnLdsBudget;
+}
+bool AttentionEligible(const AttnArgs& a, int tile);
+hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);
+hipError_t InitKernelsAttn();            // once per process, before any capture: lets the MFMA kernels take more than 64 KiB of LDS
+
+// Class token and position embedding (kernels_tokens.hip): out[n, 0, :] = cls + pos[0], out[n, 1 + p, :] = in[n, p, :] + pos[1 + p]; cls [D] and
+// pos [L0 + 1][D] (or null) fp32.  16-byte vectors where D, the pitches and the bases allow, else one element per thread.
+struct TokenAssembleArgs {
+    TensorArg in, out;                 // in.w = L0 tokens of D = in.c channels; out.w = L0 + 1
+    const float* cls = nullptr;
+    const float* pos = nullptr;
+};
+hipError_t LaunchTokenAssemble(const TokenAssembleArgs& a, hipStream_t stream);
+bool TokenAssembleVectorised(const TokenAssembleArgs& a);
+
 // Squeeze-and-excitation block (kernels_se.hip): out = in * gate[n, c], gate = act(W2^T-packed FC(act1(W1 * mean_hw(in) + b1)) + b2).
 // Three phases, four launches: squeeze (fp32 partial sums per pixel chunk), fc1 (means + FC1 + act1 -> hidden [N][mid]), fc2 (FC2 + act -> gate [N][C]),
 // apply.  Deterministic (fixed summation orders, no atomics).  The workspace holds chunks * N * C partials, N * mid hidden values and the N * C gate.

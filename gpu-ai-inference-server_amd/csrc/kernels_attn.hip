@@ -1,0 +1,284 @@
+// Multi-head attention over a token view (ViT-class graphs) on gfx950.
+//
+//   out[n, i, h * hd + e] = sum_j softmax_j(scale * q[n, h, i, :] . k[n, h, j, :]) * v[n, h, j, e]
+//
+// The operand is the qkv buffer the qkv Linear wrote: row (n, j) holds q | k | v, each D = heads * hd wide, head h at columns h * hd.  The result
+// goes straight into the token buffer the projection Linear reads.  Scores, softmax statistics and accumulation are fp32 in both element types; the
+// softmax subtracts the row maximum; no score is ever written to memory.
+//
+//   attention_generic_kernel        tile 0: one wave per (image, head, query row).  Any L, hd, pitch, offset, float or half.  Pass 1: the row
+//                                   maximum (lane l takes the keys l, l + 64, ...).  Pass 2: per block of 64 keys each lane computes one
+//                                   probability, the wave then walks the block with a shuffle broadcast while lane l accumulates output column l
+//                                   (columns beyond 64 in further sweeps).  The fallback and the cross-check.
+//   attention_mfma_kernel<T, HD>    tile 1: a workgroup = (image, head, 128 queries) = 4 waves x 32 queries.  The head's K and V rows are staged
+//                                   once into LDS as 16-byte vectors, L padded with zero rows to whole 32-key tiles, every row padded by one
+//                                   vector (the row stride is then 4 banks mod 64 in fp32 and 36 in fp16: the 16 lanes of a ds_read_b128 group hit
+//                                   16 different bank quads).  Each wave keeps its 32 Q rows in registers and walks the keys in tiles of 32 with
+//                                   an online softmax (running maximum m and sum l per query; O rescaled by exp(m - m') whenever m grows).
+//
+// Operand orientation of tile 1.  The scores are computed swapped, S^T = K . Q^T: the MFMA's A operand is the K tile (row = key), its B operand
+// Q^T (column = query), so in the 32x32 result (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) a lane owns ONE query column and
+// 16 of its 32 keys; the other 16 sit in lane ^ 32.  Row maximum and sum are 15 in-lane operations and one exchange with lane ^ 32.  The second
+// product is O^T += V^T . P^T, which sums over P^T's row index: the probabilities feed it as the B operand from the registers they are in.
+// The reduction index of a product may be walked in any order as long as both operands agree:
+//   QK^T   lane half hf supplies the head-dim elements hf * HD/2 ... of its Q row and of its K row: whole 16-byte vectors on both sides
+//   PV     fp32 (32x32x2): register r is one k-step: keys (r & 3) + 8 (r >> 2) in lane half 0 and that + 4 in lane half 1, and the A operand is V at
+//          that key.  fp16 (32x32x16): registers 8 s ... 8 s + 7 as halfs are k-step s; element j of lane half hf is key
+//          16 s + 8 (j >> 2) + 4 hf + (j & 3), and the V fragment is gathered in the same order (scripts/probes/attn_pv_order.hip checks both maps
+//          with exact integers).
+// Padded keys (j >= L) get -inf before the maximum; padded queries are computed from the last row and never stored.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "kernels.h"
+
+namespace ie {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+typedef _Float16 h4v __attribute__((ext_vector_type(4)));
+
+constexpr int kAttnBlock = 256;
+constexpr float kLog2e = 1.4426950408889634f;
+
+__device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
+    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
+}
+
+// rows = N * heads * L query rows, one wave each
+__global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const AttnArgs a, const int64_t rows) {
+    const int lane = int(threadIdx.x) % 64;
+    const int64_t row = int64_t(blockIdx.x) * (kAttnBlock / 64) + threadIdx.x / 64;
+    if (row >= rows) return;                       // wave-uniform
+    const int L = a.in.w, hd = a.head_dim, D = a.heads * hd;
+    const int i = int(row % L);
+    const int h = int((row / L) % a.heads);
+    const int64_t n = row / (int64_t(L) * a.heads);
+    const int64_t qb = n * a.in.sn + int64_t(i) * a.in.sw + int64_t(h) * hd * a.in.sc;       // q row; key row j: kb + j * sw
+    const int64_t kb = n * a.in.sn + int64_t(D + h * hd) * a.in.sc, vb = kb + int64_t(D) * a.in.sc;
+    const int64_t ob = n * a.out.sn + int64_t(i) * a.out.sw + int64_t(h) * hd * a.out.sc;
+    auto score = [&](int j) {
+        float s = 0.f;
+        for (int e = 0; e < hd; ++e) s = fmaf(ld_any(a.in.p, a.in.f16, qb + int64_t(e) * a.in.sc), ld_any(a.in.p, a.in.f16, kb + int64_t(j) * a.in.sw + int64_t(e) * a.in.sc), s);
+        return s * a.scale;
+    };
+    float m = -__builtin_huge_valf();
+    for (int j = lane; j < L; j += 64) m = fmaxf(m, score(j));
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) m = fmaxf(m, __shfl_xor(m, x, 64));
+    for (int e0 = 0; e0 < hd; e0 += 64) {
+        const int e = e0 + lane;
+        float l = 0.f, acc = 0.f;
+        for (int j0 = 0; j0 < L; j0 += 64) {
+            const int j = j0 + lane;
+            const float p = j < L ? expf(score(j) - m) : 0.f;
+            l += p;
+            const int cnt = L - j0 < 64 ? L - j0 : 64;
+            for (int t = 0; t < cnt; ++t) {
+                const float pj = __shfl(p, t, 64);
+                if (e < hd) acc = fmaf(pj, ld_any(a.in.p, a.in.f16, vb + int64_t(j0 + t) * a.in.sw + int64_t(e) * a.in.sc), acc);
+            }
+        }
+#pragma unroll
+        for (int x = 32; x >= 1; x >>= 1) l += __shfl_xor(l, x, 64);
+        if (e < hd) {
+            const float o = acc / l;
+            const int64_t oi = ob + int64_t(e) * a.out.sc;
+            if (a.out.f16) reinterpret_cast<_Float16*>(a.out.p)[oi] = _Float16(o);
+            else a.out.p[oi] = o;
+        }
+    }
+}
+
+__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// grid = N * heads * qblocks workgroups (qblocks = ceil(L / 128)); dynamic LDS = AttnLdsBytes(L, HD, half)
+template <typename T, int HD>
+__global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnArgs a, const int qblocks) {
+    constexpr bool F16 = sizeof(T) == 2;
+    constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
+    constexpr int RS = HD + V;                     // LDS row stride in elements
+    constexpr int HH = HD / 2;                     // head-dim elements one lane half supplies to QK^T
+    constexpr int VPR = HD / V;                    // vectors per K / V row
+    extern __shared__ __attribute__((aligned(16))) unsigned char attn_smem[];
+    const int L = a.in.w, Lp = (L + 31) / 32 * 32, D = a.heads * HD;
+    T* Ks = reinterpret_cast<T*>(attn_smem);
+    T* Vs = Ks + size_t(Lp) * RS;
+    const int qb = int(blockIdx.x) % qblocks;
+    const int hn = int(blockIdx.x) / qblocks;
+    const int h = hn % a.heads, n = hn / a.heads;
+    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // token row j: + j * sw; q at + 0, k at + D, v at + 2 D
+
+    for (int idx = int(threadIdx.x); idx < Lp * VPR; idx += kAttnBlock) {
+        const int row = idx / VPR, cv = idx % VPR;
+        uint4 kv = make_uint4(0u, 0u, 0u, 0u), vv = kv;                                   // rows past L: zeros (a zero probability times them stays zero)
+        if (row < L) {
+            const T* r = base + int64_t(row) * a.in.sw + cv * V;
+            kv = *reinterpret_cast<const uint4*>(r + D);
+            vv = *reinterpret_cast<const uint4*>(r + 2 * D);
+        }
+        *reinterpret_cast<uint4*>(Ks + row * RS + cv * V) = kv;
+        *reinterpret_cast<uint4*>(Vs + row * RS + cv * V) = vv;
+    }
+    __syncthreads();
+
+    const int wave = int(threadIdx.x) / 64, lane = int(threadIdx.x) % 64, col = lane & 31, hf = lane >> 5;
+    const int q0 = qb * 128 + wave * 32;
+    if (q0 >= L) return;                           // wave-uniform, behind the kernel's only barrier
+    const int qi = q0 + col < L ? q0 + col : L - 1;
+    const T* qrow = base + int64_t(qi) * a.in.sw + hf * HH;
+    float4 q4[F16 ? 1 : HH / 4];                   // this lane's half of its Q row, in registers for the whole kernel
+    h8v q8[F16 ? HH / 8 : 1];
+    if constexpr (F16) {
+#pragma unroll
+        for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8v*>(qrow + 8 * k);
+    } else {
+#pragma unroll
+        for (int k = 0; k < HH / 4; ++k) q4[k] = *reinterpret_cast<const float4*>(qrow + 4 * k);
+    }
+
+    f32x16 o0, o1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+    float m = -__builtin_huge_valf(), lsum = 0.f;
+    const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
+
+    for (int key0 = 0; key0 < Lp; key0 += 32) {
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        const T* krow = Ks + (key0 + col) * RS + hf * HH;
+        if constexpr (F16) {
+#pragma unroll
+            for (int k = 0; k < HH; k += 8)
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8v*>(krow + k), q8[k / 8], s, 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int k = 0; k < HH; k += 4) {
+                const float4 kf = *reinterpret_cast<const float4*>(krow + k);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, q4[k / 4].x, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, q4[k / 4].y, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, q4[k / 4].z, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, q4[k / 4].w, s, 0, 0, 0);
+            }
+        }
+        const bool tail = key0 + 32 > L;           // the last tile holds padded keys
+        float mx = -__builtin_huge_valf();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+            s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
+            mx = fmaxf(mx, s[r]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mn = fmaxf(m, mx);             // finite: every tile has at least one real key
+        const float alpha = fast_exp2(m - mn);     // 0 on the first tile (m = -inf)
+        m = mn;
+        float ps = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] = fast_exp2(s[r] - mn);
+            ps += s[r];
+            o0[r] *= alpha;
+            if constexpr (HD == 64) o1[r] *= alpha;
+        }
+        lsum = fmaf(lsum, alpha, ps);              // this lane half's share of the row sum
+        if constexpr (F16) {
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                h8v pb, va0, va1;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int key = key0 + 16 * st + 8 * (j >> 2) + 4 * hf + (j & 3);
+                    pb[j] = _Float16(s[8 * st + j]);
+                    va0[j] = Vs[key * RS + col];
+                    if constexpr (HD == 64) va1[j] = Vs[key * RS + 32 + col];
+                }
+                o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va0, pb, o0, 0, 0, 0);
+                if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va1, pb, o1, 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+                o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vs[key * RS + col]), s[r], o0, 0, 0, 0);
+                if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vs[key * RS + 32 + col]), s[r], o1, 0, 0, 0);
+            }
+        }
+    }
+
+    lsum += __shfl_xor(lsum, 32, 64);
+    if (q0 + col >= L) return;
+    const float inv = 1.f / lsum;
+    T* orow = reinterpret_cast<T*>(a.out.p) + int64_t(n) * a.out.sn + int64_t(q0 + col) * a.out.sw + h * HD;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int e0 = 8 * g + 4 * hf;             // registers 4 g ... 4 g + 3 are the output columns e0 ... e0 + 3 of this lane's query
+        if constexpr (F16) {
+            h4v x, y;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) { x[t] = _Float16(o0[4 * g + t] * inv); y[t] = _Float16(o1[4 * g + t] * inv); }
+            *reinterpret_cast<h4v*>(orow + e0) = x;
+            if constexpr (HD == 64) *reinterpret_cast<h4v*>(orow + 32 + e0) = y;
+        } else {
+            *reinterpret_cast<float4*>(orow + e0) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
+            if constexpr (HD == 64)
+                *reinterpret_cast<float4*>(orow + 32 + e0) = make_float4(o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
+        }
+    }
+}
+
+// the MFMA kernel's view: channels contiguous, token rows one pitch apart through the whole tensor, 16-byte aligned base
+bool vec_view_ok(const TensorArg& t, int V) {
+    return t.sc == 1 && t.h == 1 && t.c % V == 0 && t.sw % V == 0 && t.sn == int64_t(t.w) * t.sw && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
+}
+
+template <typename T, int HD>
+hipError_t launch_mfma(const AttnArgs& a, hipStream_t stream) {
+    const int qblocks = (a.in.w + 127) / 128;
+    const int64_t blocks = int64_t(a.in.n) * a.heads * qblocks;
+    if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    const size_t lds = size_t(AttnLdsBytes(a.in.w, HD, sizeof(T) == 2));
+    attention_mfma_kernel<T, HD><<<dim3(unsigned(blocks)), dim3(kAttnBlock), lds, stream>>>(a, qblocks);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+bool AttentionEligible(const AttnArgs& a, int tile) {
+    if (tile < 0 || tile >= kNumAttnTiles || !a.in.p || !a.out.p || a.heads < 1 || a.head_dim < 1) return false;
+    const int64_t D = int64_t(a.heads) * a.head_dim;
+    if (a.in.f8 || a.out.f8 || a.in.c != 3 * D || a.out.c != D || a.in.n != a.out.n || a.in.h != 1 || a.out.h != 1 || a.in.w != a.out.w || a.in.w < 1) return false;
+    if (tile == 0) return true;
+    const int V = a.out.f16 ? 8 : 4;
+    // (the offsets are in the base pointers: their alignment stands for the offset condition)
+    return a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) && vec_view_ok(a.out, V) &&
+           AttnMfmaFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0);
+}
+
+hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream) {
+    if (!AttentionEligible(a, tile)) return hipErrorInvalidValue;
+    if (a.in.n == 0) return hipSuccess;
+    if (tile == 0) {
+        const int64_t rows = int64_t(a.in.n) * a.heads * a.in.w;
+        const int64_t blocks = (rows + kAttnBlock / 64 - 1) / (kAttnBlock / 64);
+        if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(attention_generic_kernel, dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
+        return hipGetLastError();
+    }
+    if (a.out.f16) return a.head_dim == 64 ? launch_mfma<_Float16, 64>(a, stream) : launch_mfma<_Float16, 32>(a, stream);
+    return a.head_dim == 64 ? launch_mfma<float, 64>(a, stream) : launch_mfma<float, 32>(a, stream);
+}
+
+hipError_t InitKernelsAttn() {
+    hipError_t e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget))) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget))) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget))) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget))) != hipSuccess) return e;
+    return hipSuccess;
+}
+
+}  // namespace ie

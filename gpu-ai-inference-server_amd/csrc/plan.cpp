@@ -38,9 +38,12 @@ struct Val {
     int64_t abs_off = 0;
     int buf = -1;
     bool dedicated = false;             // its buffer is never recycled
+    // token select (Gather(axis 1, index i) of a token value [N, L, D]): this [N, D] value is row sel_idx of every image of its parent, a view of
+    // pitch sel_rows * the parent's pitch
+    int64_t sel_rows = 1, sel_idx = 0;
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -60,6 +63,10 @@ struct LNode {
     std::vector<float> w, bias;         // conv: w packed [Cout][kh][kw][Cin]
     std::vector<float> s, t;            // affine; L_LAYERNORM: gamma, beta (beta may be empty)
     float eps = 1e-5f;                  // L_LAYERNORM
+    // L_TOKASM: s = the class token [D], t = the position embedding [L][D] (empty: none); L_TOKPOS: t = the [L][D] constant an Add puts on tokens
+    // L_ATTENTION: in = the qkv tokens [N, L, 3 heads head_dim]
+    int heads = 0, head_dim = 0;
+    double attn_scale = 1.0;
     bool has_pre = false, pre_relu = false, relu = false;
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
@@ -93,6 +100,11 @@ struct Lowering {
     // no pass ever sees them.  A Transpose emits no node: its output is one more name of its input's value.
     std::set<std::string> cl_names;
     bool is_cl(const std::string& name) const { return cl_names.count(name) != 0; }
+    // Names that read their value as tokens [N, L, D]: the value behind the name has the dims [N, D, 1, L] (n = N, c = D, h = 1, w = L), so its NHWC
+    // storage is the [N, L, D] array.  flat_names: the [N, C, H*W] Reshape of a feature map, which only the Transpose [0,2,1] to tokens may read;
+    // back_names: the Transpose [0,2,1] of a token name, which only the Reshape to [N, D, h, w] may read.  Both are names of the unchanged value.
+    std::set<std::string> tok_names, flat_names, back_names;
+    bool is_tok(const std::string& name) const { return tok_names.count(name) != 0; }
 
     explicit Lowering(const OnnxModel& mm) : m(mm) {}
 
@@ -360,6 +372,18 @@ struct Planner {
     bool FoldShapeOnlyOp(const OnnxNode& on, const LNode& n);
     bool ImportTranspose(const OnnxNode& on, const LNode& n);
     bool cl_out = false;                   // ImportNode: the importer computed its result on a channels-last view (the output's name is one too)
+    bool tok_out = false;                  // ImportNode: the importer computed its result on a token view (the output's name is one too)
+    // MatchAttention: the attention subgraphs found in the ONNX graph.  attn_head: the rank-5 Reshape of a match -> what ImportAttention needs;
+    // attn_skip: the other nodes of the matches (they import nothing)
+    struct AttnMatch { int64_t heads = 0, head_dim = 0; double scale = 1.0; std::string out, name; std::vector<int64_t> shape5, shape3; };
+    std::map<const OnnxNode*, AttnMatch> attn_head;
+    std::set<const OnnxNode*> attn_skip;
+    void MatchAttention();
+    void ImportAttention(const OnnxNode& on, const AttnMatch& am);
+    bool FoldExpand(const OnnxNode& on, const LNode& n);
+    bool ImportTokenView(const OnnxNode& on, LNode& n);
+    void ImportTokenConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void push_node(LNode&& n, const std::string& out_name, const std::vector<int64_t>& odims, bool tok);
     void ImportLayerNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportConv(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportConvTranspose(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
@@ -373,6 +397,7 @@ struct Planner {
     void ImportResize(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
 
     // ---- graph-level fusions ----
+    void FuseTokenAssemble();
     void FuseActivationPatterns();
     void FuseSqueezeExcite();
     void MergeAffineChains();
@@ -408,6 +433,8 @@ struct Planner {
     void EmitEltwise(const LNode& n, Step& s);
     void EmitResize(const LNode& n, Step& s) const;
     void EmitLayerNorm(const LNode& n, Step& s);
+    void EmitTokenAssemble(const LNode& n, Step& s);
+    void EmitAttention(const LNode& n, Step& s);
 
     // ---- step-level fusions, I/O descriptors ----
     void FuseDenseLayers();
@@ -495,7 +522,7 @@ bool Planner::FoldShapeArithmetic(const OnnxNode& on, const LNode& n) {
     bool from_shape = op == "Shape";
     for (size_t k = 0; k < on.inputs.size(); ++k) {
         if (!L.shape_derived.count(on.inputs[k])) continue;
-        const bool sizes_in = (op == "Resize" && k == 3);
+        const bool sizes_in = (op == "Resize" && k == 3) || (op == "Expand" && k == 1);      // (an Expand of a constant folds: FoldExpand)
         if (!folding && !sizes_in)
             fail(op + " " + n.name + ": reads the shape arithmetic of a Shape node; shapes are only supported as the sizes of a Resize");
         from_shape = true;
@@ -775,12 +802,16 @@ void Planner::ImportConvTranspose(const OnnxNode& on, LNode& n, std::vector<int6
 void Planner::ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
     const std::string& op = on.op;
     if (!act_input(on, 0)) fail(op + " " + n.name + ": constant first operand is not supported");
+    // (a product of two activations exists only inside the attention pattern, which MatchAttention took)
+    if (op == "MatMul" && act_input(on, 1)) fail("Unsupported ONNX operator: MatMul (node " + n.name + ")");
     const OnnxTensor* b = L.init(on.inputs.at(1));
     if (!b || b->dims.size() != 2) fail(op + " " + n.name + ": second operand must be a 2-D initializer");
     int x = in_val(on, 0);
     const Val& X = L.vals[x];
     // a channels-last view [N, H, W, K] times [K, N']: the 1x1 conv of its pixels (ConvNeXt's Linear layers), the result channels-last again
-    const bool cl = L.is_cl(on.inputs[0]);
+    // (a token view [N, L, K] likewise: the 1x1 conv of its L token rows)
+    const bool tok = L.is_tok(on.inputs[0]);
+    const bool cl = L.is_cl(on.inputs[0]) || tok;
     if (!cl && X.h * X.w != 1) fail(op + " " + n.name + ": input must be [N, K]");
     bool transB = op == "Gemm" && on.attr_i("transB", 0) != 0;
     if (op == "Gemm" && on.attr_i("transA", 0) != 0) fail("Gemm " + n.name + ": transA is not supported");
@@ -804,7 +835,7 @@ void Planner::ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odi
     n.in = {x};
     odims = {X.n, N};
     if (X.dims.size() == 1) odims = {N};
-    if (cl) { odims = {X.n, N, X.h, X.w}; cl_out = true; }
+    if (cl) { odims = {X.n, N, X.h, X.w}; cl_out = !tok; tok_out = tok; }
 }
 
 void Planner::ImportBatchNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
@@ -835,6 +866,9 @@ void Planner::ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t
     if (a0 && a1 && L.is_cl(on.inputs[0]) != L.is_cl(on.inputs[1]))
         fail(op + " " + n.name + ": the operands mix a channels-last view and an NCHW value");
     cl_out = (a0 && L.is_cl(on.inputs[0])) || (a1 && L.is_cl(on.inputs[1]));
+    tok_out = (a0 && L.is_tok(on.inputs[0])) || (a1 && L.is_tok(on.inputs[1]));
+    if (a0 && a1 && L.is_tok(on.inputs[0]) != L.is_tok(on.inputs[1]))
+        fail(op + " " + n.name + ": the operands mix a token view and another value");
     if (a0 && a1 && op == "Mul") {
         // same shapes, or [N,C,H,W] x [N,C,1,1] in either order (a squeeze-excite gate); in[0] = the full tensor
         int a = in_val(on, 0), b = in_val(on, 1);
@@ -869,7 +903,23 @@ void Planner::ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t
         }
         if (m.opset > 0 && m.opset < 7 && on.attr_i("broadcast", 0) == 0 && c->dims != X.dims && c->numel() != 1)
             fail(op + " " + n.name + ": operand shapes differ and the opset-" + std::to_string(m.opset) + " broadcast attribute is not set");
-        bool ok = !cl_out && L.per_channel_const(*c, X, pc, legacy_axis);
+        if (tok_out && op == "Add" && X.w > 1 && c->numel() == X.w * X.c && (c->dtype == ONNX_FLOAT || c->dtype == ONNX_DOUBLE || c->dtype == ONNX_FLOAT16) &&
+            (c->dims == std::vector<int64_t>{1, X.w, X.c} || c->dims == std::vector<int64_t>{X.w, X.c})) {
+            // a position embedding: FuseTokenAssemble folds it into the class-token concat in front of it, or refuses it
+            n.kind = L_TOKPOS;
+            n.t = c->f;
+            n.in = {x};
+            odims = X.dims;
+            return;
+        }
+        bool ok = !cl_out && !tok_out && L.per_channel_const(*c, X, pc, legacy_axis);
+        if (tok_out) {
+            const bool flt = c->dtype == ONNX_FLOAT || c->dtype == ONNX_DOUBLE || c->dtype == ONNX_FLOAT16;
+            if (flt && c->numel() == 1) { pc.assign(size_t(X.c), c->f[0]); ok = true; }
+            else if (flt && c->numel() == X.c && c->dims.size() <= 3 && !c->dims.empty() && c->dims.back() == X.c) { pc = c->f; ok = true; }
+            if (!ok) fail(op + " " + n.name + ": constant operand must broadcast along the last axis of the token view " + on.inputs[a0 ? 0 : 1] +
+                          " (or be the [1, L, D] position embedding added directly behind the class-token Concat)");
+        }
         if (cl_out) {
             // against the ONNX dims [N, H, W, C] numpy broadcasting puts the channels last: a scalar, [C], [1, C] ... [1, 1, 1, C]
             const bool flt = c->dtype == ONNX_FLOAT || c->dtype == ONNX_DOUBLE || c->dtype == ONNX_FLOAT16;
@@ -926,6 +976,7 @@ void Planner::ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t
         n.in = {in_val(on, 0)};
         odims = L.vals[n.in[0]].dims;
         cl_out = L.is_cl(on.inputs[0]);
+        tok_out = L.is_tok(on.inputs[0]);
     } else {
         n.kind = L_ACT;
         if (op == "Gelu") {
@@ -934,6 +985,7 @@ void Planner::ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t
             if (mode != "none" && mode != "tanh") fail("Gelu " + n.name + ": approximate '" + mode + "' is not supported (none and tanh are)");
             n.act.kind = mode == "tanh" ? ActKind::GeluTanh : ActKind::Gelu;
             cl_out = L.is_cl(on.inputs[0]);
+            tok_out = L.is_tok(on.inputs[0]);
         }
         else if (op == "Sigmoid") n.act.kind = ActKind::Sigmoid;
         else if (op == "HardSigmoid") { n.act.kind = ActKind::HardSigmoid; n.act.a = on.attr_f("alpha", 0.2f); n.act.b = on.attr_f("beta", 0.5f); }
@@ -945,6 +997,8 @@ void Planner::ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t
 }
 
 void Planner::ImportConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    for (const std::string& name : on.inputs)
+        if (L.is_tok(name)) { ImportTokenConcat(on, n, odims); return; }
     int64_t axis = on.attr_i("axis", 1);
     n.kind = L_CONCAT;
     for (size_t k = 0; k < on.inputs.size(); ++k) {
@@ -1127,11 +1181,12 @@ void Planner::ImportLayerNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>
     if (!act_input(on, 0)) fail("LayerNormalization " + n.name + ": constant input is not supported");
     const int x = in_val(on, 0);
     const Val& X = L.vals[x];
-    const bool cl = L.is_cl(on.inputs[0]);
-    const int64_t rank = int64_t(X.dims.size()), axis_attr = on.attr_i("axis", -1);
+    const bool tok = L.is_tok(on.inputs[0]);
+    const bool cl = L.is_cl(on.inputs[0]) || tok;
+    const int64_t rank = tok ? 3 : int64_t(X.dims.size()), axis_attr = on.attr_i("axis", -1);
     const int64_t axis = axis_attr < 0 ? axis_attr + rank : axis_attr;
     if (!(cl ? axis == rank - 1 : (rank == 2 && axis == 1)))
-        fail("LayerNormalization " + n.name + ": axis = " + std::to_string(axis_attr) + " on " + (cl ? std::string("a channels-last view") : "an NCHW value of rank " + std::to_string(rank)) +
+        fail("LayerNormalization " + n.name + ": axis = " + std::to_string(axis_attr) + " on " + (tok ? std::string("a token view") : cl ? std::string("a channels-last view") : "an NCHW value of rank " + std::to_string(rank)) +
              " is not supported (only the channel axis alone is normalised: the last axis of a channels-last view or of an [N, C] value)");
     if (on.attr_i("stash_type", 1) != 1) fail("LayerNormalization " + n.name + ": stash_type = " + std::to_string(on.attr_i("stash_type", 1)) + " is not supported (1 is)");
     for (size_t k = 1; k < on.outputs.size(); ++k)
@@ -1148,7 +1203,8 @@ void Planner::ImportLayerNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>
     n.eps = on.attr_f("epsilon", 1e-5f);
     n.in = {x};
     odims = X.dims;
-    cl_out = cl;
+    cl_out = cl && !tok;
+    tok_out = tok;
 }
 
 // Transpose is a view of the NHWC storage, never a kernel: perm [0,2,3,1] of a 4-D value reads it channels-last, perm [0,3,1,2] of such a view
@@ -1161,6 +1217,23 @@ bool Planner::ImportTranspose(const OnnxNode& on, const LNode& n) {
     for (size_t k = 0; k < perm.size(); ++k) ps += (k ? "," : "") + std::to_string(perm[k]);
     ps += "]";
     const int v = in_val(on, 0);
+    // tokens: [N, C, H*W] (a flat name) -> [N, H*W, C] is the NHWC storage itself; the way back [N, L, D] -> [N, D, L] waits for its Reshape
+    if (L.flat_names.count(on.inputs[0]) || L.is_tok(on.inputs[0])) {
+        const bool flat = L.flat_names.count(on.inputs[0]) != 0;
+        if (perm != std::vector<int64_t>{0, 2, 1})
+            fail("Transpose " + n.name + ": perm " + ps + " on " + (flat ? "the [N, C, H*W] reshape of a feature map" : "a token view") + " is not supported (only [0,2,1] is)");
+        const Val X = L.vals[v];
+        if (!flat) { L.alias_name(on.outputs[0], v, false); L.back_names.insert(on.outputs[0]); }
+        else if (X.h == 1) { L.alias_name(on.outputs[0], v, false); L.tok_names.insert(on.outputs[0]); }
+        else {
+            LNode a;
+            a.kind = L_ALIAS;
+            a.name = n.name;
+            a.in = {v};
+            push_node(std::move(a), on.outputs[0], {X.n, X.c, 1, X.h * X.w}, true);
+        }
+        return true;
+    }
     const bool cl = L.is_cl(on.inputs[0]);
     const bool to_cl = perm == std::vector<int64_t>{0, 2, 3, 1}, from_cl = perm == std::vector<int64_t>{0, 3, 1, 2};
     if (L.vals[v].dims.size() != 4 || !((to_cl && !cl) || (from_cl && cl)))
@@ -1184,9 +1257,22 @@ void Planner::ImportNode(const OnnxNode& on) {
         if (L.is_cl(name) && !cl_ops.count(op))
             fail(op + " " + n.name + ": input " + name + " is a channels-last view (a Transpose with perm [0,2,3,1]); only LayerNormalization, MatMul, Add, Mul, Div, Erf, "
                  "Gelu and Transpose may read one");
-    if (FoldShapeArithmetic(on, n) || FoldShapeOnlyOp(on, n) || ImportTranspose(on, n)) return;
+    // token views likewise, and the two half-way names of their creation and of the way back
+    static const std::set<std::string> tok_ops = {"LayerNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose", "Concat", "Gather", "Reshape"};
+    for (const std::string& name : on.inputs) {
+        if (L.is_tok(name) && !tok_ops.count(op))
+            fail(op + " " + n.name + ": input " + name + " is a token view [N, L, D]; only LayerNormalization, MatMul, Add, Mul, Div, Erf, Gelu, Transpose, Concat, "
+                 "Gather and the Reshape of the attention pattern may read one");
+        if (L.flat_names.count(name) && op != "Transpose")
+            fail(op + " " + n.name + ": input " + name + " is the [N, C, H*W] reshape of a feature map; only a Transpose with perm [0,2,1] (to tokens [N, L, D]) may read it");
+        if (L.back_names.count(name) && op != "Reshape")
+            fail(op + " " + n.name + ": input " + name + " is the [N, D, L] transpose of a token view; only a Reshape to [N, D, h, w] with h * w = L may read it");
+    }
+    if (attn_skip.count(&on)) return;                      // inside a matched attention subgraph: its head node imports the whole of it
+    if (const auto am = attn_head.find(&on); am != attn_head.end()) { ImportAttention(on, am->second); return; }
+    if (FoldShapeArithmetic(on, n) || FoldShapeOnlyOp(on, n) || FoldExpand(on, n) || ImportTranspose(on, n) || ImportTokenView(on, n)) return;
     std::vector<int64_t> odims;
-    cl_out = false;
+    cl_out = tok_out = false;
     if (op == "Conv") ImportConv(on, n, odims);
     else if (op == "ConvTranspose") ImportConvTranspose(on, n, odims);
     else if (op == "MatMul" || op == "Gemm") ImportGemm(on, n, odims);
@@ -1201,13 +1287,332 @@ void Planner::ImportNode(const OnnxNode& on) {
     else fail("Unsupported ONNX operator: " + op + " (node " + n.name + ")");
     n.out = L.new_val(on.outputs[0], odims);
     if (cl_out) L.cl_names.insert(on.outputs[0]);
+    if (tok_out) L.tok_names.insert(on.outputs[0]);
     L.vals[n.out].producer = int(L.nodes.size());
     L.nodes.push_back(std::move(n));
+}
+
+void Planner::push_node(LNode&& n, const std::string& out_name, const std::vector<int64_t>& odims, bool tok) {
+    n.out = L.new_val(out_name, odims);
+    if (tok) L.tok_names.insert(out_name);
+    L.vals[n.out].producer = int(L.nodes.size());
+    L.nodes.push_back(std::move(n));
+}
+
+// Expand of a constant to a constant shape (the class token [1, 1, D] to [N, 1, D]): a derived initializer.  true: the node is done
+bool Planner::FoldExpand(const OnnxNode& on, const LNode& n) {
+    if (on.op != "Expand" || on.inputs.size() < 2 || !L.init(on.inputs[0]) || !L.init(on.inputs[1])) return false;
+    OnnxTensor t = *L.init(on.inputs[0]);
+    const std::vector<int64_t> shp = L.init(on.inputs[1])->i;
+    if (t.f.empty() || shp.empty()) fail("Expand " + n.name + ": only a floating-point constant and an integer shape are supported");
+    std::vector<int64_t> id = t.dims, od = shp;
+    while (id.size() < od.size()) id.insert(id.begin(), 1);
+    while (od.size() < id.size()) od.insert(od.begin(), 1);
+    int64_t total = 1;
+    for (size_t k = 0; k < od.size(); ++k) {
+        if (od[k] == 1) od[k] = id[k];
+        if (id[k] != 1 && id[k] != od[k]) fail("Expand " + n.name + ": the shape does not broadcast");
+        if (od[k] <= 0) fail("Expand " + n.name + ": non-positive dimension");
+        total *= od[k];
+    }
+    if (total > (int64_t(1) << 26)) fail("Expand " + n.name + ": the result is too large to fold");
+    std::vector<float> f(static_cast<size_t>(total));
+    for (int64_t o = 0; o < total; ++o) {
+        int64_t rem = o, src = 0, stride = 1;
+        for (size_t k = od.size(); k-- > 0;) {
+            const int64_t ix = rem % od[k];
+            rem /= od[k];
+            if (id[k] != 1) { src += ix * stride; }
+            stride *= id[k];
+        }
+        f[size_t(o)] = t.f[size_t(src)];
+    }
+    t.f = std::move(f);
+    t.dims = od;
+    t.name = on.outputs[0];
+    L.add_derived(std::move(t));
+    return true;
+}
+
+// The token constructs that emit no node of their own kind.  true: the node is done
+//   Reshape [N, C, H, W] -> [N, C, H*W]: a flat name (one more name of the value; its Transpose [0,2,1] makes the tokens)
+//   Reshape of a back name (the Transpose [0,2,1] of tokens [N, L, D]) to [N, D, h, w], h * w = L: a plain NCHW value on the same storage
+//   Gather(axis 1, scalar index i) of tokens: the [N, D] view of row i of every image (pitch L * pitch, offset i * pitch): no step
+bool Planner::ImportTokenView(const OnnxNode& on, LNode& n) {
+    const std::string& op = on.op;
+    if (op == "Reshape" && act_input(on, 0)) {
+        const int v = in_val(on, 0);
+        const Val X = L.vals[v];
+        const bool back = L.back_names.count(on.inputs[0]) != 0, tok = L.is_tok(on.inputs[0]);
+        if (!back && !tok && !(X.dims.size() == 4 && X.h * X.w != 1 && !L.is_cl(on.inputs[0]))) return false;
+        const OnnxTensor* shp = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
+        if (!shp && !back && !tok) return false;
+        if (!shp) fail("Reshape " + n.name + ": shape must be an initializer");
+        std::vector<int64_t> d = shp->i;
+        // the ONNX dims of the input: [N, L, D] of a token name, [N, D, L] of a back name, else the value's own
+        const std::vector<int64_t> idims = tok ? std::vector<int64_t>{X.n, X.w, X.c} : back ? std::vector<int64_t>{X.n, X.c, X.w} : X.dims;
+        int64_t known = 1, neg = -1, total = 1;
+        for (int64_t x : idims) total *= x;
+        for (size_t k = 0; k < d.size(); ++k) {
+            if (d[k] == 0 && k < idims.size()) d[k] = idims[k];
+            if (d[k] == -1) neg = int64_t(k); else known *= d[k];
+        }
+        if (neg >= 0 && known > 0) d[size_t(neg)] = total / known;
+        if (tok) {
+            // only as the head of the attention pattern, which MatchAttention took: a left-over one is an unsupported operator
+            if (d.size() == 5) fail("Unsupported ONNX operator: Reshape (node " + n.name + ")");
+            fail("Reshape " + n.name + ": input " + on.inputs[0] + " is a token view [N, L, D]; only the [N, L, 3, H, hd] Reshape of the attention pattern may reshape one");
+        }
+        if (back) {
+            if (d.size() != 4 || d[0] != X.n || d[1] != X.c || d[2] * d[3] != X.w || d[2] <= 0)
+                fail("Reshape " + n.name + ": the [N, D, L] transpose of a token view only reshapes to [N, D, h, w] with h * w = L");
+            if (d[2] == 1) { L.alias_name(on.outputs[0], v, false); return true; }
+            n.kind = L_ALIAS;
+            n.in = {v};
+            push_node(std::move(n), on.outputs[0], d, false);
+            return true;
+        }
+        if (d.size() != 3 || d[0] != X.n || d[1] != X.c || d[2] != X.h * X.w) return false;       // (ImportReshape refuses it as before)
+        L.alias_name(on.outputs[0], v, false);
+        L.flat_names.insert(on.outputs[0]);
+        return true;
+    }
+    if (op == "Gather" && L.is_tok(on.inputs[0])) {
+        const int v = in_val(on, 0);
+        const Val X = L.vals[v];
+        const OnnxTensor* ix = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
+        int64_t axis = on.attr_i("axis", 0);
+        if (axis < 0) axis += 3;
+        if (axis != 1 || !ix || !ix->dims.empty() || ix->i.size() != 1)
+            fail("Gather " + n.name + ": only Gather(axis = 1, scalar constant index) selects a token of the token view " + on.inputs[0]);
+        int64_t i = ix->i[0];
+        if (i < 0) i += X.w;
+        if (i < 0 || i >= X.w) fail("Gather " + n.name + ": index out of range");
+        const int o = L.new_val(on.outputs[0], {X.n, X.c});
+        L.vals[o].parent = v;
+        L.vals[o].parent_off = 0;
+        L.vals[o].sel_rows = X.w;
+        L.vals[o].sel_idx = i;
+        return true;
+    }
+    return false;
+}
+
+// Concat(axis 1) of a class-token constant [1 | N, 1, D] and a token value [N, L0, D]: the token-assemble node.  Every other token-axis concat is refused
+void Planner::ImportTokenConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    int64_t axis = on.attr_i("axis", 1);
+    if (axis < 0) axis += 3;
+    if (axis != 1) fail("Concat " + n.name + ": only axis = 1 (the token axis) is supported on token views");
+    if (on.inputs.size() != 2)
+        fail("Concat " + n.name + ": a token-axis concat takes exactly two operands, a class-token constant and the tokens (it has " + std::to_string(on.inputs.size()) + ")");
+    if (act_input(on, 0) && act_input(on, 1))
+        fail("Concat " + n.name + ": concatenating two activations along the token axis is not supported (only a class-token constant in front of the tokens)");
+    if (!L.is_tok(on.inputs[1]))
+        fail("Concat " + n.name + ": a constant behind the tokens is not supported (only a class-token constant in front of the tokens)");
+    const OnnxTensor* c = L.init(on.inputs[0]);
+    const int x = in_val(on, 1);
+    const Val& X = L.vals[x];
+    if (!c || c->f.empty() || c->dims.size() != 3 || (c->dims[0] != 1 && c->dims[0] != X.n) || c->dims[1] != 1 || c->dims[2] != X.c)
+        fail("Concat " + n.name + ": the class token must be a floating-point constant of shape [1 | N, 1, D]");
+    for (int64_t r = 1; r < c->dims[0]; ++r)
+        for (int64_t k = 0; k < X.c; ++k)
+            if (c->f[size_t(r * X.c + k)] != c->f[size_t(k)]) fail("Concat " + n.name + ": the class token must be the same for every image");
+    n.kind = L_TOKASM;
+    n.s.assign(c->f.begin(), c->f.begin() + X.c);
+    n.in = {x};
+    odims = {X.n, X.c, 1, X.w + 1};
+    tok_out = true;
+}
+
+// ---- attention: the unfused multi-head attention subgraph of a ViT export as ONE node ------------------------------------------------
+// Matched on the ONNX nodes, before the import (its inner values have ranks 4 and 5, which no Val holds), around every Softmax that sits between
+// two MatMuls of activations:
+//   R = Reshape(qkv, [N, L, 3, H, hd]) -> T = Transpose(R, [2,0,3,1,4]) -> q, k, v = Gather(T, axis 0, index 0 / 1 / 2) | Squeeze(Split(T, axis 0)[i], [0])
+//   S = MatMul(q [* c], Transpose(k, [0,1,3,2]) [* c]) [* c | / c] -> P = Softmax(S, axis -1) -> MatMul(P, v) -> Transpose [0,2,1,3] -> Reshape [N, L, D]
+// with scalar constants c in either operand order, every intermediate read by the next node only.  A near miss is refused naming what did not
+// match; nothing is approximated.  A Softmax elsewhere is left to the import, which refuses it as an unsupported operator.
+void Planner::MatchAttention() {
+    std::map<std::string, const OnnxNode*> prod;
+    std::map<std::string, int> readers;
+    std::map<std::string, OnnxTensor> consts;
+    for (const OnnxNode& on : m.nodes) {
+        for (const std::string& o : on.outputs) if (!o.empty()) prod[o] = &on;
+        for (const std::string& i : on.inputs) if (!i.empty()) ++readers[i];
+        if (on.op == "Constant" && on.outputs.size() == 1 && on.attrs.size() == 1) {
+            const OnnxAttr& at = on.attrs.begin()->second;
+            OnnxTensor t;
+            if (at.name == "value" && at.has_t) t = at.t;
+            else if (at.name == "value_float") { t.dtype = ONNX_FLOAT; t.f = {at.f}; }
+            else if (at.name == "value_int") { t.dtype = ONNX_INT64; t.i = {at.i}; }
+            else continue;
+            consts[on.outputs[0]] = t;
+        }
+    }
+    for (const auto& vo : m.outputs) ++readers[vo.name];
+    auto cst = [&](const std::string& name) -> const OnnxTensor* {
+        const auto it = m.initializers.find(name);
+        if (it != m.initializers.end()) return &it->second;
+        const auto jt = consts.find(name);
+        return jt == consts.end() ? nullptr : &jt->second;
+    };
+    auto producer = [&](const std::string& name) -> const OnnxNode* { const auto it = prod.find(name); return it == prod.end() ? nullptr : it->second; };
+    auto act_matmul = [&](const OnnxNode* p) { return p && p->op == "MatMul" && p->inputs.size() == 2 && !cst(p->inputs[0]) && !cst(p->inputs[1]); };
+    auto perm_is = [](const OnnxNode* p, std::vector<int64_t> want) { return p && p->op == "Transpose" && p->attr_ints("perm", {}) == want; };
+    for (const OnnxNode& sm : m.nodes) {
+        if (sm.op != "Softmax" || sm.inputs.size() != 1 || sm.outputs.size() != 1) continue;
+        const std::string nm = sm.name.empty() ? sm.outputs[0] : sm.name;
+        auto miss = [&](const std::string& what) { fail("Softmax " + nm + ": the attention pattern around it does not match: " + what); };
+        std::vector<const OnnxNode*> taken;
+        double scale = 1.0;
+        // a chain of Mul / Div by scalar constants above `cur`; each link read once
+        auto peel = [&](std::string cur, bool commit) -> std::string {
+            for (;;) {
+                const OnnxNode* p = producer(cur);
+                if (!p || (p->op != "Mul" && p->op != "Div") || p->inputs.size() != 2) return cur;
+                const OnnxTensor *c0 = cst(p->inputs[0]), *c1 = cst(p->inputs[1]);
+                if ((c0 != nullptr) == (c1 != nullptr) || (p->op == "Div" && !c1)) return cur;
+                const OnnxTensor* c = c0 ? c0 : c1;
+                if (!commit) { cur = p->inputs[c0 ? 1 : 0]; continue; }
+                if (c->numel() != 1 || c->f.size() != 1) miss("the scale constant of " + p->op + " " + (p->name.empty() ? p->outputs[0] : p->name) + " is not a scalar");
+                if (p->op == "Div" && c->f[0] == 0.f) miss("division by zero in " + p->name);
+                scale = p->op == "Div" ? scale / double(c->f[0]) : scale * double(c->f[0]);
+                taken.push_back(p);
+                cur = p->inputs[c0 ? 1 : 0];
+            }
+        };
+        // is this an attention at all?  scores from a MatMul of two activations (through scalings, or behind a mask Add), probabilities into a MatMul
+        const OnnxNode* pv = nullptr;
+        for (const OnnxNode& on : m.nodes)
+            if (on.op == "MatMul" && on.inputs.size() == 2 && on.inputs[0] == sm.outputs[0] && !cst(on.inputs[1])) pv = &on;
+        if (!pv) continue;
+        const OnnxNode* top = producer(peel(sm.inputs[0], false));
+        if (top && top->op == "Add" && top->inputs.size() == 2 &&
+            (act_matmul(producer(peel(top->inputs[0], false))) || act_matmul(producer(peel(top->inputs[1], false)))))
+            miss("an additive mask (Add " + (top->name.empty() ? top->outputs[0] : top->name) + ") on the scores is not supported");
+        if (!act_matmul(top)) continue;
+        const int64_t axis = sm.attr_i("axis", -1);
+        if (axis != -1 && axis != 3) miss("Softmax axis = " + std::to_string(axis) + " (only the last axis, -1 or 3, is an attention)");
+        const OnnxNode* qk = producer(peel(sm.inputs[0], true));
+        const std::string q = peel(qk->inputs[0], true);
+        const std::string kt_name = peel(qk->inputs[1], true);
+        const OnnxNode* kt = producer(kt_name);
+        if (!perm_is(kt, {0, 1, 3, 2})) miss("the second operand of MatMul " + qk->name + " is not Transpose(k, perm [0,1,3,2])");
+        const std::string k = peel(kt->inputs[0], true);
+        const std::string v = pv->inputs[1];
+        // q, k, v = slices 0, 1, 2 of one transposed qkv tensor
+        const OnnxNode* split = nullptr;
+        std::string T;
+        auto slice_of = [&](const std::string& name, int64_t want) {
+            const OnnxNode* g = producer(name);
+            std::string src;
+            int64_t idx = -1;
+            if (g && g->op == "Gather" && g->inputs.size() == 2 && g->attr_i("axis", 0) == 0) {
+                const OnnxTensor* ix = cst(g->inputs[1]);
+                if (ix && ix->dims.empty() && ix->i.size() == 1) { idx = ix->i[0]; src = g->inputs[0]; }
+            } else if (g && g->op == "Squeeze" && !g->inputs.empty()) {
+                std::vector<int64_t> ax = g->attr_ints("axes", {});
+                if (ax.empty() && g->inputs.size() > 1) if (const OnnxTensor* at = cst(g->inputs[1])) ax = at->i;
+                const OnnxNode* sp = producer(g->inputs[0]);
+                if (ax == std::vector<int64_t>{0} && sp && sp->op == "Split" && sp->outputs.size() == 3 && sp->attr_i("axis", 0) == 0 && !sp->inputs.empty()) {
+                    for (int64_t o = 0; o < 3; ++o) if (sp->outputs[size_t(o)] == g->inputs[0]) idx = o;
+                    src = sp->inputs[0];
+                    if (split && split != sp) idx = -1;
+                    split = sp;
+                    if (readers[g->inputs[0]] != 1) miss("the Split output " + g->inputs[0] + " has a second reader");
+                }
+            }
+            if (idx != want || src.empty() || (!T.empty() && src != T))
+                miss(name + " is not slice " + std::to_string(want) + " of the transposed qkv tensor (q, k, v must be Gather(axis 0, index 0 / 1 / 2) or Split(axis 0) + "
+                     "Squeeze slices of one Transpose [2,0,3,1,4])");
+            T = src;
+            taken.push_back(g);
+        };
+        slice_of(q, 0);
+        slice_of(k, 1);
+        slice_of(v, 2);
+        if (split) taken.push_back(split);
+        const OnnxNode* tr = producer(T);
+        if (!perm_is(tr, {2, 0, 3, 1, 4})) miss("q, k and v are not slices of Transpose(perm [2,0,3,1,4])");
+        const OnnxNode* rs = producer(tr->inputs[0]);
+        const OnnxTensor* s5 = rs && rs->op == "Reshape" && rs->inputs.size() == 2 ? cst(rs->inputs[1]) : nullptr;
+        if (!s5 || s5->i.size() != 5 || s5->i[2] != 3 || s5->i[3] <= 0 || s5->i[4] <= 0)
+            miss("the qkv tensor is not Reshape(x, [N, L, 3, H, hd]) with a constant shape");
+        // behind the second MatMul: Transpose [0,2,1,3] -> Reshape [N, L, D]
+        auto only_reader = [&](const std::string& name) -> const OnnxNode* {
+            if (readers[name] != 1) return nullptr;
+            for (const OnnxNode& on : m.nodes) for (const std::string& i : on.inputs) if (i == name) return &on;
+            return nullptr;
+        };
+        const OnnxNode* ot = only_reader(pv->outputs[0]);
+        if (!perm_is(ot, {0, 2, 1, 3})) miss("the result of MatMul " + pv->name + " is not read by Transpose(perm [0,2,1,3]) alone");
+        const OnnxNode* orr = only_reader(ot->outputs[0]);
+        const OnnxTensor* s3 = orr && orr->op == "Reshape" && orr->inputs.size() == 2 ? cst(orr->inputs[1]) : nullptr;
+        if (!s3 || s3->i.size() != 3) miss("the transposed result is not read by Reshape(., [N, L, D]) alone");
+        // every intermediate has one reader (the transposed qkv tensor: its three Gathers or its Split)
+        taken.insert(taken.end(), {qk, kt, pv, ot, tr, &sm});
+        for (const OnnxNode* p : taken)
+            for (const std::string& o : p->outputs) {
+                const int want = (p == tr && !split) ? 3 : 1;
+                if (readers[o] != want) miss((p == qk || o == sm.inputs[0] ? "the scores " : "the intermediate ") + o + " has " + std::to_string(readers[o]) + " readers, not " + std::to_string(want));
+            }
+        if (readers[rs->outputs[0]] != 1) miss("the intermediate " + rs->outputs[0] + " has a second reader");
+        AttnMatch am;
+        am.heads = s5->i[3];
+        am.head_dim = s5->i[4];
+        am.scale = scale;
+        am.out = orr->outputs[0];
+        am.shape5 = s5->i;
+        am.shape3 = s3->i;
+        am.name = (rs->name.empty() ? rs->outputs[0] : rs->name) + "+" + nm + "+" + (orr->name.empty() ? orr->outputs[0] : orr->name);
+        attn_head[rs] = am;
+        for (const OnnxNode* p : taken) attn_skip.insert(p);
+        attn_skip.insert(orr);
+    }
+}
+
+void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
+    auto miss = [&](const std::string& what) { fail("attention " + am.name + ": " + what); };
+    if (!L.is_tok(on.inputs[0])) miss("its qkv input " + on.inputs[0] + " is not a token view [N, L, 3 D]");
+    const int x = in_val(on, 0);
+    const Val X = L.vals[x];
+    const int64_t D = am.heads * am.head_dim;
+    if (X.c != 3 * D) miss("the qkv rows have " + std::to_string(X.c) + " columns, not 3 * H * hd = " + std::to_string(3 * D));
+    if ((am.shape5[0] != 0 && am.shape5[0] != X.n) || (am.shape5[1] != -1 && am.shape5[1] != 0 && am.shape5[1] != X.w)) miss("the Reshape to [N, L, 3, H, hd] does not keep N and L");
+    if ((am.shape3[0] != 0 && am.shape3[0] != X.n) || (am.shape3[1] != -1 && am.shape3[1] != 0 && am.shape3[1] != X.w) || (am.shape3[2] != -1 && am.shape3[2] != D))
+        miss("the last Reshape is not to [N, L, H * hd]");
+    if (am.shape3[1] == -1 && am.shape3[2] == -1) miss("the last Reshape is not to [N, L, H * hd]");
+    LNode n;
+    n.kind = L_ATTENTION;
+    n.name = am.name;
+    n.in = {x};
+    n.heads = int(am.heads);
+    n.head_dim = int(am.head_dim);
+    n.attn_scale = am.scale;
+    push_node(std::move(n), am.out, {X.n, D, 1, X.w}, true);
+}
+
+// ---- token assemble: the position-embedding Add directly behind the class-token concat, as its sole reader, folds into it ----
+void Planner::FuseTokenAssemble() {
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& a = L.nodes[i];
+        if (a.dead || a.kind != L_TOKPOS) continue;
+        const int p = L.vals[a.in[0]].producer;
+        if (p < 0 || L.nodes[size_t(p)].dead || L.nodes[size_t(p)].kind != L_TOKASM || !L.nodes[size_t(p)].t.empty() || !single_consumer(a.in[0]))
+            fail("Add " + a.name + ": a [1, L, D] constant is only added to tokens directly behind the class-token Concat, as its sole reader");
+        LNode& c = L.nodes[size_t(p)];
+        c.t = a.t;
+        c.name += "+" + a.name;
+        c.out = a.out;
+        L.vals[c.out].producer = p;
+        a.dead = true;
+    }
 }
 
 void Planner::MarkOutputs() {
     for (const auto& vo : m.outputs) {
         int v = L.get_val(vo.name);
+        if (L.is_tok(vo.name) || L.flat_names.count(vo.name) || L.back_names.count(vo.name))
+            fail("graph output " + vo.name + " is a token view; outputs are NCHW: transpose it back with perm [0,2,1] and reshape it to [N, D, h, w]");
         if (L.is_cl(vo.name)) fail("graph output " + vo.name + " is a channels-last view (a Transpose with perm [0,2,3,1]); outputs are NCHW: transpose it back with perm [0,3,1,2]");
         L.vals[v].is_output = true;
     }
@@ -1223,6 +1628,8 @@ void Planner::RefuseForF8() const {
         if (n.kind == L_RESIZE) fail("Resize is not supported in fp8 mode (node " + n.name + ")");
         if (n.kind == L_LAYERNORM) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
     }
+    for (const LNode& n : L.nodes)
+        if (n.kind == L_ATTENTION || n.kind == L_TOKASM || n.kind == L_TOKPOS) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
     for (const LNode& n : L.nodes)
         if (n.kind == L_ACT || n.kind == L_MUL || n.kind == L_ERF)
             fail("activation and squeeze-excite nodes (Sigmoid, HardSigmoid, HardSwish, Mul of two activations) are not supported in fp8 mode (node " + n.name + ")");
@@ -1600,7 +2007,7 @@ void Planner::DensifyOutputs() {
             out_vals.push_back(v);
             continue;
         }
-        if (spatial || L.vals[v].is_input || consumed) {
+        if (spatial || L.vals[v].is_input || consumed || L.vals[v].sel_rows > 1) {
             LNode cp;
             cp.kind = L_COPY;
             cp.name = "to_output(" + L.vals[v].name + ")";
@@ -1626,6 +2033,10 @@ void Planner::PlaceConcatsAndAliases() {
             // the alias output shares storage with its input: make the *input* a child of the output
             if (src.parent < 0 && !src.is_input && !src.is_output) { src.parent = n.out; src.parent_off = 0; }
             else {  // cannot alias: degrade to a copy
+                // (the copy kernel walks both sides by the output's rows and columns: a token view of another height is not a copy it can do)
+                if (src.h != L.vals[n.out].h || src.w != L.vals[n.out].w)
+                    fail("token view " + n.name + ": its input " + src.name + " already lives in another value's buffer (a second view of it, or a Concat); reshaping it "
+                         "between a feature map and tokens would need a copy, which is not supported");
                 n.kind = L_COPY;
             }
         } else if (n.kind == L_CONCAT) {
@@ -1743,8 +2154,8 @@ View Planner::view_of(int v) const {
     w.f16 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 1;
     w.f8 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 2;
     w.n = X.n; w.c = X.c; w.h = X.h; w.w = X.w;
-    w.c_off = X.abs_off;
-    w.pitch = R.c;
+    w.c_off = X.abs_off + X.sel_idx * R.c;
+    w.pitch = R.c * X.sel_rows;
     w.nchw = (X.is_input || X.is_output) && X.input_nchw;
     if (w.buf < 0) fail("internal planner error: value " + X.name + " has no buffer");
     return w;
@@ -2175,6 +2586,32 @@ void Planner::EmitLayerNorm(const LNode& n, Step& s) {
     s.bytes = vbytes(s.in) + vbytes(s.out);
 }
 
+// token assemble: the class token at w_off, the position embedding at bias_off (fp32 in every precision)
+void Planner::EmitTokenAssemble(const LNode& n, Step& s) {
+    if (s.in.f8 || s.out.f8) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::TokenAssemble;
+    s.w_off = push_vec(n.s);
+    if (!n.t.empty()) s.bias_off = push_vec(n.t);
+    s.flops = n.t.empty() ? 0.0 : double(s.out.numel());
+    s.bytes = vbytes(s.in) + vbytes(s.out);
+}
+
+// attention: tile 1 (the MFMA kernel) where kernels.h AttnMfmaFits says so, else the generic kernel; IE_FORCE_TILE as for layer norm
+void Planner::EmitAttention(const LNode& n, Step& s) {
+    if (s.in.f8 || s.out.f8) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::Attention;
+    s.heads = n.heads;
+    s.head_dim = n.head_dim;
+    s.attn_scale = float(n.attn_scale);
+    const bool fits = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 &&
+                      AttnMfmaFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off);
+    s.tile = fits ? 1 : 0;
+    const int t = ForcedTile(kNumAttnTiles);
+    if (t >= 0) s.tile = t == 0 || fits ? t : 0;
+    s.flops = 4.0 * double(s.in.n) * double(s.heads) * double(s.in.w) * double(s.in.w) * double(s.head_dim);
+    s.bytes = vbytes(s.in) + vbytes(s.out);
+}
+
 // ---- emit steps --------------------------------------------------------------------------------
 void Planner::EmitSteps() {
     for (int idx : order) {
@@ -2199,6 +2636,8 @@ void Planner::EmitSteps() {
             case L_ACT: case L_MUL: case L_AFFINE: case L_CLIP: case L_RELU: case L_ADD: EmitEltwise(n, s); break;
             case L_RESIZE: EmitResize(n, s); break;
             case L_LAYERNORM: EmitLayerNorm(n, s); break;
+            case L_TOKASM: EmitTokenAssemble(n, s); break;
+            case L_ATTENTION: EmitAttention(n, s); break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -2527,11 +2966,13 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
 
     // ---- ONNX graph -> logical nodes with shape inference ----
     P.ImportInputs();
+    P.MatchAttention();                                          // the unfused attention subgraphs, found on the ONNX nodes: each imports as one node
     for (const OnnxNode& on : m.nodes) P.ImportNode(on);
     P.MarkOutputs();
     if (f8) P.RefuseForF8();
 
     // ---- graph-level fusions ----
+    P.FuseTokenAssemble();                                       // class-token Concat -> Add pos_embedding as one node
     P.FuseActivationPatterns();                                  // Mul(x, Sigmoid(x)) -> SiLU, Mul(x, HardSigmoid(x)) -> hardswish
     if (!env.get("IE_NO_SE_FUSE")) P.FuseSqueezeExcite();        // pool -> 1x1 -> act -> 1x1 -> act -> Mul as one node
     P.MergeAffineChains();                                       // fusion 1: Affine -> Affine
@@ -2579,7 +3020,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention"};
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
@@ -2641,6 +3082,8 @@ std::string PlanToJson(const Plan& p) {
             o << ",\"resize\":{\"mode\":\"" << rs_modes[int(s.rs_mode)] << "\",\"coord\":\"" << rs_coords[int(s.rs_coord)] << "\",\"nearest\":\""
               << rs_nearest[int(s.rs_nearest)] << "\",\"scales\":[" << s.rs_scale_h << "," << s.rs_scale_w << "]}";
         if (s.kind == StepKind::LayerNorm) o << ",\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile;      // (layer-norm steps only)
+        if (s.kind == StepKind::Attention)
+            o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"tile\":" << s.tile;      // (attention steps only)
         if (!s.parts.empty()) {
             Plan sub;
             sub.steps = s.parts;

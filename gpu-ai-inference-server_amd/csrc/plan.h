@@ -38,7 +38,7 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9 };
 
 // Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
 enum class ResizeMode : int { Nearest = 0, Linear = 1 };
@@ -129,6 +129,12 @@ struct Step {
     // LayerNorm (kernels_ln.hip): out = (in - mean_c) * rsqrt(var_c + ln_eps) * gamma + beta per pixel row; w_off = gamma [C], bias_off = beta [C] or
     // -1, fp32 in every precision; tile = the kernel variant (kernels.h kNumLnTiles)
     float ln_eps = 1e-5f;
+    // TokenAssemble (kernels_tokens.hip): in = tokens [N, 1, L0, D], out = [N, 1, L0 + 1, D]; out[n, 0, :] = cls + pos[0], out[n, 1 + p, :] = in[n, p, :] +
+    // pos[1 + p]; w_off = cls [D], bias_off = pos [L0 + 1][D] or -1, fp32 in every precision
+    // Attention (kernels_attn.hip): in = the qkv tokens [N, 1, L, 3 D] (column s * D + h * head_dim + e = element e of head h of q / k / v for s = 0 / 1 / 2),
+    // out[n, i, h * head_dim + e] = sum_j softmax_j(attn_scale * q_i . k_j) * v[j, e]; tile 0 = the generic kernel, 1 = the MFMA kernel
+    int heads = 0, head_dim = 0;
+    float attn_scale = 1.f;
     ConvAlgo algo = ConvAlgo::Naive;
     int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)

@@ -1,5 +1,5 @@
 """Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY,
-FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt and small test graphs).
+FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -847,6 +847,114 @@ def convnext(batch: int | str = 1, *, depths: Sequence[int] = (3, 3, 9, 3), dims
 
 def convnext_tiny(batch: int | str = 1, **kw) -> bytes:
     return convnext(batch, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), **kw)
+
+
+def vit_attention(gb: GraphBuilder, x: str, dim: int, heads: int, tag: str, *, unbind: str = "gather", scale: str = "q", swap: bool = False,
+                  qkv: str | None = None) -> str:
+    """Multi-head self-attention on tokens x [N, L, dim] as torch's exporter writes it unfused: Linear dim -> 3 dim -> Reshape [N, L, 3, H, hd] ->
+    Transpose [2,0,3,1,4] -> q, k, v -> MatMul(q, Transpose(k, [0,1,3,2])) -> Softmax(-1) -> MatMul(p, v) -> Transpose [0,2,1,3] -> Reshape [N, L, dim].
+    unbind: "gather" (three Gather(axis 0, scalar index)) or "split" (Split(axis 0) into three, each followed by Squeeze(axes [0])).
+    scale (c = hd^-0.5): "q" Mul(q, c); "s_mul" Mul(scores, c); "s_div" Div(scores, 1 / c); "sdpa" Mul(q, sqrt c) and Mul(kT, sqrt c).
+    swap: the constant is the first operand of every Mul.  qkv: an existing [N, L, 3 dim] value instead of the Linear."""
+    hd = dim // heads
+    c = float(hd) ** -0.5
+
+    def const(name: str, v: float) -> str:
+        return gb.init(f"{tag}_{name}", np.array(v, np.float32))
+
+    def mul(a: str, k: str) -> str:
+        return gb.simple("Mul", [k, a] if swap else [a, k])
+
+    y = qkv or gb.linear(x, dim, 3 * dim, name=tag + "_qkv")
+    y = gb.simple("Reshape", [y, gb.init(tag + "_shape5", np.array([0, -1, 3, heads, hd], np.int64))])
+    y = gb.transpose(y, (2, 0, 3, 1, 4))
+    if unbind == "gather":
+        parts = []
+        for i in range(3):
+            idx = f"{tag}_i{i}"            # a scalar index (a Constant node: initializers here are at least 1-D)
+            gb.nodes.append(pb.node("Constant", [], [idx], idx, [pb.attr_int("value_int", i)]))
+            parts.append(gb.simple("Gather", [y, idx], [pb.attr_int("axis", 0)]))
+    elif unbind == "split":
+        name = gb._uid("split")
+        outs = [f"{name}_out{i}" for i in range(3)]
+        gb.nodes.append(pb.node("Split", [y, gb.init(tag + "_split", np.array([1, 1, 1], np.int64))], outs, name, [pb.attr_int("axis", 0)]))
+        ax = gb.init(tag + "_axes0", np.array([0], np.int64))
+        parts = [gb.simple("Squeeze", [o, ax]) for o in outs]
+    else:
+        raise ValueError(unbind)
+    q, k, v = parts
+    if scale == "q":
+        q = mul(q, const("scale", c))
+    elif scale == "sdpa":
+        q = mul(q, const("sqrt_scale_q", np.sqrt(c)))
+    kt = gb.transpose(k, (0, 1, 3, 2))
+    if scale == "sdpa":
+        kt = mul(kt, const("sqrt_scale_k", np.sqrt(c)))
+    s = gb.simple("MatMul", [q, kt])
+    if scale == "s_mul":
+        s = mul(s, const("scale", c))
+    elif scale == "s_div":
+        s = gb.simple("Div", [s, const("inv_scale", 1.0 / c)])
+    elif scale not in ("q", "sdpa"):
+        raise ValueError(scale)
+    p = gb.simple("Softmax", [s], [pb.attr_int("axis", -1)])
+    y = gb.transpose(gb.simple("MatMul", [p, v]), (0, 2, 1, 3))
+    return gb.simple("Reshape", [y, gb.init(tag + "_shape3", np.array([0, -1, dim], np.int64))])
+
+
+def vit_tokens(gb: GraphBuilder, x: str, dim: int) -> str:
+    """[N, dim, h, w] -> tokens [N, h w, dim]: Reshape [0, dim, -1] -> Transpose [0,2,1]"""
+    name = gb._uid("tok")
+    return gb.transpose(gb.simple("Reshape", [x, gb.init(name + "_shape", np.array([0, dim, -1], np.int64))]), (0, 2, 1))
+
+
+def vit(batch: int | str = 1, *, image: int = 224, patch: int = 16, dim: int = 768, depth: int = 12, heads: int = 12, mlp: int = 3072,
+        classes: int = 1000, unbind: str = "gather", scale: str = "q", gelu: str = "erf", seed: int = 2021, in_name: str = "input",
+        out_name: str = "logits") -> bytes:
+    """The pre-norm Vision Transformer (Dosovitskiy et al. 2021) as torch's exporter writes it at opset 17 with an unfused attention: patch conv
+    P x P / sP (bias) -> Reshape [N, D, G G] -> Transpose [0,2,1] -> Concat(axis 1)[Expand(class_token), tokens] -> Add pos_embedding; per layer
+    LayerNorm -> attention (vit_attention) -> Linear -> + x, LayerNorm -> Linear D -> mlp -> GELU -> Linear mlp -> D -> + x; LayerNorm ->
+    Gather(axis 1, index 0) -> Gemm.  The Expand's shape is a constant for an int batch and Shape(input) -> Gather 0 -> Unsqueeze -> Concat for a
+    symbolic one.  class_token and pos_embedding are O(1) draws, not torchvision's 0 / 0.02 N(0,1), at which dropping either would move the logits
+    by less than a test's tolerance."""
+    gb = GraphBuilder("vit", seed)
+    g = image // patch
+    L = g * g + 1
+    x = vit_tokens(gb, gb.conv(in_name, 3, dim, patch, stride=patch, bias=True, name="patch"), dim)
+    cls = gb.init("class_token", (rng.gaussish(seed, "class_token", dim).reshape(1, 1, dim)).astype(np.float32))
+    if isinstance(batch, int):
+        shp = gb.init("cls_shape", np.array([batch, 1, dim], np.int64))
+    else:
+        gb.nodes.append(pb.node("Shape", [in_name], ["cls_in_shape"], "cls_in_shape"))
+        gb.nodes.append(pb.node("Constant", [], ["cls_i0"], "cls_i0", [pb.attr_int("value_int", 0)]))
+        gb.nodes.append(pb.node("Gather", ["cls_in_shape", "cls_i0"], ["cls_n"], "cls_n", [pb.attr_int("axis", 0)]))
+        gb.nodes.append(pb.node("Unsqueeze", ["cls_n"], ["cls_n1"], "cls_n1", [pb.attr_ints("axes", [0])]))
+        gb.nodes.append(pb.node("Concat", ["cls_n1", gb.init("cls_tail", np.array([1, dim], np.int64))], ["cls_shape"], "cls_shape_cat", [pb.attr_int("axis", 0)]))
+        shp = "cls_shape"
+    x = gb.concat([gb.simple("Expand", [cls, shp]), x], axis=1)
+    pos = (np.float32(0.5) * rng.gaussish(seed, "pos_embedding", L * dim)).reshape(1, L, dim)
+    x = gb.simple("Add", [x, gb.init("pos_embedding", pos.astype(np.float32))])
+    for li in range(depth):
+        tag = f"l{li}"
+        y = vit_attention(gb, gb.layernorm(x, dim, name=tag + "_ln1"), dim, heads, tag + "_attn", unbind=unbind, scale=scale)
+        x = gb.simple("Add", [gb.linear(y, dim, dim, name=tag + "_proj"), x])
+        y = gb.gelu(gb.linear(gb.layernorm(x, dim, name=tag + "_ln2"), dim, mlp, name=tag + "_fc1"), gelu)
+        x = gb.simple("Add", [gb.linear(y, mlp, dim, name=tag + "_fc2", w_scale=float(np.sqrt(2.0 / mlp))), x])
+    x = gb.layernorm(x, dim, name="head_ln")
+    gb.nodes.append(pb.node("Constant", [], ["head_i0"], "head_i0", [pb.attr_int("value_int", 0)]))
+    x = gb.simple("Gather", [x, "head_i0"], [pb.attr_int("axis", 1)])
+    wfc = rng.gaussish(seed, "fc_w", classes * dim).reshape(classes, dim) * np.float32(np.sqrt(1.0 / dim))
+    bfc = (rng.uniform(seed, "fc_b", classes) - np.float32(0.5)) * np.float32(0.2)
+    gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))], [pb.attr_int("transB", 1)], out=out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=20 if gelu.startswith("op") else 17)
+
+
+def vit_b_16(batch: int | str = 1, **kw) -> bytes:
+    return vit(batch, image=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, **kw)
+
+
+def vit_tiny_16(batch: int | str = 1, **kw) -> bytes:
+    return vit(batch, image=224, patch=16, dim=192, depth=12, heads=3, mlp=768, **kw)
 
 
 def write_repo(root: str, name: str, model_bytes: bytes, version: str = "1", config_json: str | None = None) -> str:

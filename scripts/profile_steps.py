@@ -16,7 +16,11 @@ For transposed convolutions (unet): the graph-replay time as the median of 50 si
 and per step the launched kernel (IE_FORCE_TILE=0 / 1 / 2 picks the generic kernel / the MFMA tiles), its algorithmic TB/s against the copy
 rate, its roofline and torch's F.conv_transpose2d on channels_last tensors for the same shape.
 For layer-norm steps (convnext_tiny): their share of the eager forward, next to the depthwise, the GELU (eltwise) and the remaining steps' shares, and
-per distinct shape the launched kernel and its algorithmic GB/s (one read + one write) against the copy rate."""
+per distinct shape the launched kernel and its algorithmic GB/s (one read + one write) against the copy rate.
+For attention steps (vit_b_16, vit_tiny_16): the graph-replay time as the median of 50 single replays, the share of the eager forward per step family
+(attention, the qkv / proj / MLP convs, layer norms, GELU, token assemble), and per distinct attention shape the launched kernel
+(IE_FORCE_TILE=0 picks the generic one), its microseconds, its TFLOP/s against the sustained MFMA rate (129 TF/s fp32) and torch's
+F.scaled_dot_product_attention on the same [N, H, L, hd] operands, timed in a process of its own."""
 import json
 import os
 import subprocess
@@ -129,6 +133,28 @@ for n, c, h, w, mid in json.loads(sys.argv[1]):
     out.append(e0.elapsed_time(e1) / 20)
 print(json.dumps(out))
 """
+# F.scaled_dot_product_attention, ms per call (median of 20 timed calls after 5 warm ones) for each [n, heads, l, hd]
+TORCH_SDPA = """
+import json, sys, torch
+import torch.nn.functional as F
+dt = torch.float16 if sys.argv[2] == "fp16" else torch.float32
+out = []
+for n, h, l, hd in json.loads(sys.argv[1]):
+    q, k, v = (torch.randn(n, h, l, hd, device="cuda", dtype=dt) for _ in range(3))
+    f = lambda: F.scaled_dot_product_attention(q, k, v)
+    for _ in range(5):
+        f()
+    ts = []
+    for _ in range(20):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    out.append(sorted(ts)[len(ts) // 2])
+print(json.dumps(out))
+"""
 BUILDERS = {"mobilenet_v3_large": lambda: models.mobilenet_v3("N", variant="large"), "mobilenet_v3_small": lambda: models.mobilenet_v3("N", variant="small")}
 
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -205,6 +231,50 @@ if lns:
         ms = sorted(q["ms"] for q in ps)[len(ps) // 2]
         gbs = ps[0]["bytes"] / ms / 1e6
         print(f"{f'{h}x{w}x{c}':>16} {len(ps):5d} {kern:28} {ms:11.4f} {gbs:7.0f} {gbs / 6290 * 100:6.1f}%")
+ats = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "attention"]
+if ats:
+    import time
+    B.RunPrepared(m, 10, True)
+    ts = []
+    for _ in range(50):
+        t0 = time.perf_counter()
+        B.RunPrepared(m, 1, True)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    ms = sorted(ts)[len(ts) // 2]
+    print(json.dumps({"model": model_name, "batch": batch, "precision": plan["precision"], "replay_ms_per_step_median50": round(ms, 4),
+                      "images_per_s": round(batch / ms * 1e3, 1), "force_tile": os.environ.get("IE_FORCE_TILE")}))
+    # a layer's convs by position: the one in front of the attention step is qkv, the three behind it proj, fc1 and fc2; the first conv of the
+    # graph is the patch embedding, the last the head
+    kinds = [s["kind"] for s in plan["steps"]]
+    convs = [i for i, k in enumerate(kinds) if k == "conv"]
+    role = {convs[0]: "conv patch", convs[-1]: "conv head"}
+    for i, k in enumerate(kinds):
+        if k == "attention":
+            role[max(c for c in convs if c < i)] = "conv qkv"
+            for c, tag in zip([c for c in convs if c > i][:3], ("conv proj", "conv fc1", "conv fc2")):
+                role[c] = tag
+    fam = {}
+    for i, (p, s) in enumerate(zip(prof, plan["steps"])):
+        fam.setdefault(role.get(i, "conv other") if s["kind"] == "conv" else s["kind"], []).append(p["ms"])
+    print(f"{'family':16} {'steps':>5} {'ms':>9} {'share':>7}")
+    for key, v in sorted(fam.items(), key=lambda kv: -sum(kv[1])):
+        print(f"{key:16} {len(v):5d} {sum(v):9.4f} {sum(v) / tot * 100:6.1f}%")
+    mfma_tf = 129.0 if plan["precision"] == "fp32" else 2500.0          # fp32: the measured sustained rate; fp16: the roofline peak used above
+    seen = {}
+    for p, s in ats:
+        seen.setdefault((s["in"]["n"], s["heads"], s["in"]["w"], s["head_dim"], p["kernel"]), []).append(p)
+    tms = [float("nan")] * len(seen)
+    if not os.environ.get("PROFILE_NO_TORCH"):
+        child = subprocess.run([sys.executable, "-c", TORCH_SDPA, json.dumps([list(k[:4]) for k in seen]), plan["precision"]], capture_output=True, text=True, timeout=300)
+        if child.returncode == 0:
+            tms = json.loads(child.stdout.strip().splitlines()[-1])
+        else:
+            print("# torch yardstick failed:", child.stderr.strip().splitlines()[-1:])
+    print(f"{'attention N,H,L,hd':>20} {'steps':>5} {'kernel':30} {'us (median)':>11} {'TF/s':>7} {'%' + str(mfma_tf) + 'T':>8} {'torch sdpa us':>13}")
+    for ((n, h, l, hd, kern), ps), t in zip(seen.items(), tms):
+        ms = sorted(q["ms"] for q in ps)[len(ps) // 2]
+        tf = ps[0]["flops"] / ms / 1e9
+        print(f"{f'{n},{h},{l},{hd}':>20} {len(ps):5d} {kern:30} {ms * 1e3:11.1f} {tf:7.2f} {tf / mfma_tf * 100:7.1f}% {t * 1e3:13.1f}")
 if dws or ses or grs:
     import time
     B.RunPrepared(m, 10, True)
