@@ -495,7 +495,10 @@ char* EngineDescribeModel(const char* path, int batch, ErrorMessage* error) {
                 if (w == "fp16" || w == "f16" || w == "half") prec = ie::Precision::F16;
                 else if (w == "fp8" || w == "f8" || w == "e4m3") prec = ie::Precision::F8;
             }
-            o << ",\"plan\":" << ie::PlanToJson(ie::BuildPlan(m, shapes, prec));
+            // the transitions the executor may run as one launch, from shapes and views alone; `plan` stays the document's last member
+            const ie::Plan plan = ie::BuildPlan(m, shapes, prec);
+            o << ",\"paired_launches\":" << ie::PairedLaunchesToJson(ie::FindPairedLaunches(plan));
+            o << ",\"plan\":" << ie::PlanToJson(plan);
         }
         o << "}";
         return dup_cstr(o.str());

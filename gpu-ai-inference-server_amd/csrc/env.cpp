@@ -29,6 +29,8 @@ const char* const kNames[] = {
     "IE_AUTOTUNE", "IE_TUNE_CACHE", "IE_TUNE_BATCHES", "IE_TUNE_ON_DEMAND", "IE_TUNE_HOT", "IE_TUNE_LOG",
     "IE_DISABLE_GRAPH", "IE_SPLITK_IN_LAUNCH", "IE_PIPELINE_CHUNKS", "IE_PIPELINE_HEAD", "IE_MAX_PLANS", "IE_NO_FRAG_WEIGHTS",
     "IE_F8_CALIB_BATCH", "IE_F8_MARGIN",
+    "IE_POOL_CONV",            // 0: never pair a transition's pool + 1x1 conv into one launch; 1[:tile]: pair wherever eligible; 2[:tile]: also chain the
+                               // next block's entry 1x1; unset: a timed choice at load (kernels_trans.hip)
     "IE_MAX_INFLIGHT_REPLAYS", // EngineRunPrepared synchronises every n graph replays (profilers: deep un-synchronised queues crash rocprofv3)
     // ---- launch-path debugging knobs (LaunchKnobs) ------------------------------------------------------------------------------
     "IE_DEBUG_ABLATE", "IE_AS_PAD", "IE_NO_PERSISTENT",

@@ -138,7 +138,7 @@ namespace {
 std::string tune_file_header() {
     std::ostringstream o;
     o << kTuneFileTag << ' ' << kNumIgemmTiles << ' ' << kNumConvRasterTiles << ' ' << kNumConvWs32Tiles << ' ' << kNumConvWs16Tiles << ' ' << kNumConvWs3Tiles << ' '
-      << kNumConvDirectTiles << ' ' << kNumConvWinoTiles << ' ' << kNumConvX6Tiles << ' ' << kNumConvWs8Tiles << ' ' << kNumConvWs38Tiles << ' ' << kNumConvDenseFusedTiles;
+      << kNumConvDirectTiles << ' ' << kNumConvWinoTiles << ' ' << kNumConvX6Tiles << ' ' << kNumConvWs8Tiles << ' ' << kNumConvWs38Tiles << ' ' << kNumConvDenseFusedTiles << ' ' << kNumConvPooledTiles;
     return o.str();
 }
 
@@ -149,6 +149,10 @@ std::string tune_file_header() {
 // branch of TuneStep know its range.
 constexpr int kLnTuneCode = 1000;
 bool ln_tune_code(int t) { return t >= kLnTuneCode && t < kLnTuneCode + kNumLnTiles; }
+// kPoolConvTuneCode + c: how a transition's pool, conv and entry-conv steps launch (PairTransitions).  c = 0: every step on its own; 1 + t: pool + conv
+// on tile t of conv1x1_pooled_kernel, the entry conv on its own; 1 + kNumConvPooledTiles + t: all three on tile t with the chained second conv
+constexpr int kPoolConvTuneCode = 1100;
+bool pool_conv_tune_code(int t) { return t >= kPoolConvTuneCode && t <= kPoolConvTuneCode + 2 * kNumConvPooledTiles; }
 struct TuneFamily { int base; ConvAlgo algo; int tiles; };
 constexpr TuneFamily kTuneFamilies[] = {
     {0, ConvAlgo::IgemmVec, kNumIgemmTiles},          {100, ConvAlgo::Raster3x3, kNumConvRasterTiles},
@@ -171,7 +175,7 @@ int tune_code(ConvAlgo algo, int tile) {
 }
 
 bool tune_code_valid(int t) {
-    return (t >= 0 && t - tune_family(t).base < tune_family(t).tiles) || ln_tune_code(t) || (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles) ||
+    return (t >= 0 && t - tune_family(t).base < tune_family(t).tiles) || ln_tune_code(t) || pool_conv_tune_code(t) || (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles) ||
            (t >= kWs38Code && t < kWs38Code + kNumConvWs38Tiles);
 }
 
@@ -225,6 +229,7 @@ DeviceModel::DeviceModel(std::shared_ptr<const OnnxModel> model, int device_id, 
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsBlock();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsWs8();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsAttn();
+        if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsTrans();
     });
     check(g_kernels_err, "InitKernels");
     fp32_split_ = opt.fp32_split && opt.precision == Precision::F32;
@@ -259,6 +264,10 @@ DeviceModel::DeviceModel(std::shared_ptr<const OnnxModel> model, int device_id, 
     const char* tp = env_.get("IE_SPLITK_IN_LAUNCH");
     two_pass_splitk_ = !(tp && tp[0] == '1');
     autotune_ = !(at && at[0] == '0') && !env_.get("IE_FORCE_TILE") && !env_.get("IE_FORCE_SPLITK") && !env_.get("IE_FORCE_ALGO");
+    if (const char* pc = env_.get("IE_POOL_CONV"); pc && pc[0] >= '0' && pc[0] <= '2') {      // "0" | "1[:tile]" | "2[:tile]"
+        pool_conv_mode_ = pc[0] - '0';
+        if (pc[1] == ':' && pc[2] >= '0' && pc[2] <= '9') pool_conv_tile_ = std::atoi(pc + 2);
+    }
     if (const char* od = env_.get("IE_TUNE_ON_DEMAND")) tune_on_demand_ = od[0] == '1';
     if (const char* pc = env_.get("IE_PIPELINE_CHUNKS")) pipeline_chunks_ = std::max(0, std::min(kMaxChunks, std::atoi(pc)));
     if (const char* ph = env_.get("IE_PIPELINE_HEAD")) pipeline_head_ = std::max(0, std::atoi(ph));
@@ -509,6 +518,7 @@ PlanInstance& DeviceModel::Prepare(const std::vector<std::vector<int64_t>>& shap
         BuildInstance(*pi, shapes);
         check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         if (autotune_) Autotune(*pi, pi->plan.steps.size(), allow_tune || tune_on_demand_);
+        else PairTransitions(nullptr, *pi);              // (only an explicit IE_POOL_CONV pairs without a search)
         // fp8 mode bakes the activation scales into the launches: nothing is captured before they exist (a replica that owns a
         // never-uploaded blob is built before the weight broadcast); RefreshGraphs captures on first use
         if (use_graph_ && !(precision_ == Precision::F8 && !w_->f8_ready)) {
@@ -889,6 +899,7 @@ void DeviceModel::Autotune(PlanInstance& pi, size_t nsteps, bool allow_search) {
     if (const char* e = env_.get("IE_TUNE_HOT"); allow_search && !(e && std::atoi(e) != 0))
         if (hipMalloc(&ctx.scrub, TuneContext::kScrubBytes) != hipSuccess) { ctx.scrub = nullptr; (void)hipGetLastError(); }
     for (size_t si = 0; si < nsteps && si < pi.plan.steps.size(); ++si) TuneStep(ctx, pi, pi.plan.steps[si]);
+    if (nsteps >= pi.plan.steps.size()) PairTransitions(&ctx, pi);      // (a chunk instance runs head steps only: nothing is paired there)
     if (ctx.searched) SaveTuneCache();
 }
 
@@ -896,24 +907,30 @@ void DeviceModel::Autotune(PlanInstance& pi, size_t nsteps, bool allow_search) {
 // forward a layer finds neither its weights nor its input in L2 (the other layers ran in between), back-to-back repeats would flatter
 // every kernel that re-reads operands from L2 -- or hot (IE_TUNE_HOT=1, or no scrub buffer): two timed triples.
 float DeviceModel::TimeTrial(TuneContext& ctx, const PlanInstance& pi, const Step& trial) {
+    const float best = TimeLaunches(ctx, [&] { LaunchStep(pi, trial, stream_); });
+    if (ctx.log)
+        std::fprintf(stderr, "[ie-tune] M=%lld N=%lld K=%lld algo=%d tile=%d splitk=%d: %.4f ms\n", static_cast<long long>(trial.out.n * trial.out.h * trial.out.w),
+                     static_cast<long long>(trial.out.c), static_cast<long long>(trial.kh * trial.kw * trial.in.c), int(trial.algo), trial.tile, trial.splitk, best);
+    return best;
+}
+
+// The same protocol for any launch sequence (a step, or the launches of a candidate that covers several steps)
+float DeviceModel::TimeLaunches(TuneContext& ctx, const std::function<void()>& launch) {
     auto timed = [&](int launches) {
         check(hipEventRecord(ctx.e0, stream_), "hipEventRecord");
-        for (int r = 0; r < launches; ++r) LaunchStep(pi, trial, stream_);
+        for (int r = 0; r < launches; ++r) launch();
         check(hipEventRecord(ctx.e1, stream_), "hipEventRecord");
         check(hipEventSynchronize(ctx.e1), "hipEventSynchronize");
         float ms = 0;
         check(hipEventElapsedTime(&ms, ctx.e0, ctx.e1), "hipEventElapsedTime");
         return ms;
     };
-    LaunchStep(pi, trial, stream_);                  // warm
+    launch();                                        // warm
     float best = 1e30f;
     for (int rep = 0; rep < (ctx.scrub ? 3 : 2); ++rep) {
         if (ctx.scrub) check(hipMemsetAsync(ctx.scrub, 0, TuneContext::kScrubBytes, stream_), "hipMemsetAsync(scrub)");
         best = std::min(best, timed(ctx.scrub ? 1 : 3));
     }
-    if (ctx.log)
-        std::fprintf(stderr, "[ie-tune] M=%lld N=%lld K=%lld algo=%d tile=%d splitk=%d: %.4f ms\n", static_cast<long long>(trial.out.n * trial.out.h * trial.out.w),
-                     static_cast<long long>(trial.out.c), static_cast<long long>(trial.kh * trial.kw * trial.in.c), int(trial.algo), trial.tile, trial.splitk, best);
     return best;
 }
 
@@ -1740,11 +1757,259 @@ static std::string kernel_label(const Step& s) {
     return "?";
 }
 
+
+// ---- transitions in one launch (kernels_trans.hip) ------------------------------------------------------------------------------------
+namespace {
+
+bool same_view(const View& a, const View& b) {
+    return a.buf == b.buf && a.n == b.n && a.c == b.c && a.h == b.h && a.w == b.w && a.c_off == b.c_off && a.pitch == b.pitch && a.nchw == b.nchw && a.f16 == b.f16 &&
+           a.f8 == b.f8;
+}
+bool views_overlap(const View& a, const View& b) {
+    return a.buf == b.buf && (a.nchw || b.nchw || (a.c_off < b.c_off + b.c && b.c_off < a.c_off + a.c));
+}
+// a write of `w` ends the life of the tensor in view `v`: another tensor laid out in the same (recycled) buffer, or the same pixel rows with v's channels rewritten
+bool view_kills(const View& w, const View& v) {
+    if (w.buf != v.buf) return false;
+    if (w.nchw || v.nchw || w.pitch != v.pitch || w.n != v.n || w.h != v.h || w.w != v.w) return true;
+    return w.c_off <= v.c_off && w.c_off + w.c >= v.c_off + v.c;
+}
+void step_views(const Step& s, std::vector<const View*>& reads, std::vector<const View*>& writes) {
+    reads.push_back(&s.in);
+    if (s.has_in2) reads.push_back(&s.in2);
+    writes.push_back(&s.out);
+    for (const Step& q : s.parts) step_views(q, reads, writes);
+}
+// a dense 1x1 / stride-1 conv step with nothing but bias and ReLU behind it
+const char* plain_1x1(const Step& c) {
+    if (c.kind != StepKind::Conv) return "is not a conv";
+    if (!c.parts.empty() || IsGroupConv(c.algo) || c.group != 1 || c.algo == ConvAlgo::Stem) return "is a fused or grouped conv step";
+    if (c.kh != 1 || c.kw != 1 || c.sh != 1 || c.sw != 1 || c.pt || c.pl || c.pb || c.pr || c.dh != 1 || c.dw != 1) return "is not a 1x1 / stride-1 conv";
+    if (c.has_in2) return "has a residual";
+    if (c.act.kind != ActKind::None || c.lo != -__builtin_huge_valf() || c.hi != __builtin_huge_valf()) return "has an activation other than ReLU";
+    if (c.in.nchw || c.out.nchw || c.in.f16 || c.out.f16 || c.in.f8 || c.out.f8) return "is not fp32 NHWC";
+    return nullptr;
+}
+
+}  // namespace
+
+std::vector<PairedLaunch> FindPairedLaunches(const Plan& plan) {
+    std::vector<PairedLaunch> found;
+    if (plan.precision != Precision::F32) return found;
+    const std::vector<Step>& st = plan.steps;
+    for (size_t i = 0; i + 1 < st.size(); ++i) {
+        const Step& pl = st[i];
+        const Step& cv = st[i + 1];
+        if (pl.kind != StepKind::Pool || cv.kind != StepKind::Conv || cv.in.buf != pl.out.buf) continue;
+        PairedLaunch c;
+        c.steps = {int(i), int(i + 1)};
+        auto miss = [&](const std::string& why) { c.reason = why; found.push_back(c); };
+        if (pl.pool_max) { miss("the pool is a max pool"); continue; }
+        if (pl.kh != 2 || pl.kw != 2 || pl.sh != 2 || pl.sw != 2) {
+            miss("the pool is " + std::to_string(pl.kh) + "x" + std::to_string(pl.kw) + " / stride " + std::to_string(pl.sh) + ", not 2x2 / stride 2");
+            continue;
+        }
+        if (pl.pt || pl.pl || pl.pb || pl.pr) { miss("the pool has padding"); continue; }
+        if (pl.in.nchw || pl.out.nchw || pl.in.f16 || pl.out.f16 || pl.in.f8 || pl.out.f8) { miss("the pool is not fp32 NHWC"); continue; }
+        if (pl.in.h != 2 * pl.out.h || pl.in.w != 2 * pl.out.w) { miss("the pool's windows do not tile its input"); continue; }
+        if (pl.act.kind != ActKind::None || pl.pre_act.kind != ActKind::None) { miss("the pool has an activation other than ReLU"); continue; }
+        if (const char* why = plain_1x1(cv)) { miss(std::string("the conv ") + why); continue; }
+        if (cv.pre_scale_off >= 0) { miss("the conv has a prologue of its own"); continue; }
+        if (!same_view(cv.in, pl.out)) { miss("the conv reads another view than the pool writes"); continue; }
+        // nothing else may read the pooled tensor: a later step before the view is written again, or the caller (a graph output)
+        bool other = false, dead = false;
+        for (size_t j = i + 2; j < st.size() && !other && !dead; ++j) {
+            std::vector<const View*> reads, writes;
+            step_views(st[j], reads, writes);
+            for (const View* r : reads) other = other || views_overlap(*r, pl.out);
+            for (const View* w : writes) dead = dead || view_kills(*w, pl.out);
+        }
+        if (other) { miss("a later step also reads the pooled tensor"); continue; }
+        if (!dead) {
+            bool is_out = false;
+            for (const IoDesc& o : plan.outputs) is_out = is_out || views_overlap(o.view, pl.out);
+            if (is_out) { miss("the pooled tensor is a graph output"); continue; }
+        }
+        // one launch reads the pool's input while other workgroups already store the conv's output: the two may not share a (recycled) buffer
+        if (cv.out.buf == pl.in.buf) { miss("the conv's output shares the pool input's buffer"); continue; }
+        for (int t = 0; t < kNumConvPooledTiles; ++t)
+            if (ConvPooledShapeOk(t, false, cv.in.c, cv.out.c, 0)) c.tiles.push_back(t);
+        if (c.tiles.empty()) { miss("no tile takes " + std::to_string(cv.in.c) + " -> " + std::to_string(cv.out.c) + " channels"); continue; }
+        c.pairable = true;
+        // chain: the step behind the conv is the next block's entry 1x1 on exactly the tensor the conv writes
+        if (i + 2 < st.size()) {
+            const Step& en = st[i + 2];
+            std::string why;
+            if (const char* w = plain_1x1(en)) why = std::string("the entry step ") + w;
+            else if (en.pre_scale_off < 0) why = "the entry conv has no prologue";
+            else if (!same_view(en.in, cv.out)) why = "the entry conv reads another view than the conv writes";
+            else if (en.out.c != 128) why = "the entry conv has " + std::to_string(en.out.c) + " output channels, not 128";
+            else if (en.out.buf == pl.in.buf || en.out.buf == cv.out.buf) why = "the entry conv's output shares a buffer the launch still reads";
+            else {
+                for (int t = 0; t < kNumConvPooledTiles; ++t)
+                    if (ConvPooledShapeOk(t, true, cv.in.c, cv.out.c, en.out.c)) c.chain_tiles.push_back(t);
+                if (c.chain_tiles.empty()) why = "no chain tile holds " + std::to_string(cv.out.c) + " channels";
+            }
+            if (why.empty()) {
+                c.chainable = true;
+                c.steps.push_back(int(i + 2));
+            } else {
+                c.reason = "chain: " + why;
+            }
+        } else {
+            c.reason = "chain: no step behind the conv";
+        }
+        found.push_back(c);
+    }
+    return found;
+}
+
+std::string PairedLaunchesToJson(const std::vector<PairedLaunch>& v) {
+    std::ostringstream o;
+    auto list = [&](const std::vector<int>& l) {
+        o << "[";
+        for (size_t k = 0; k < l.size(); ++k) o << (k ? "," : "") << l[k];
+        o << "]";
+    };
+    o << "[";
+    for (size_t i = 0; i < v.size(); ++i) {
+        const PairedLaunch& c = v[i];
+        o << (i ? "," : "") << "{\"steps\":";
+        list(c.steps);
+        o << ",\"kind\":" << (!c.pairable ? "null" : (c.chainable ? "\"pool_conv_chain\"" : "\"pool_conv\"")) << ",\"tiles\":";
+        list(c.tiles);
+        o << ",\"chain_tiles\":";
+        list(c.chain_tiles);
+        o << ",\"reason\":\"" << c.reason << "\"}";         // (reasons are this file's own text: nothing to escape)
+    }
+    o << "]";
+    return o.str();
+}
+
+bool DeviceModel::MakePooledArgs(const PlanInstance& pi, size_t i, int count, bool chain, ConvArgs* a, PooledArgs* p) const {
+    const std::vector<Step>& st = pi.plan.steps;
+    if (i + size_t(count) > st.size() || count < (chain ? 3 : 2)) return false;
+    const float* wb = w_->d_weights;
+    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
+    const Step& pl = st[i];
+    *a = MakeConvArgs(pi, st[i + 1]);
+    *p = PooledArgs();
+    p->pin = make_arg(pi, pl.in);
+    p->pool_scale = wp(pl.pre_scale_off);
+    p->pool_shift = wp(pl.pre_shift_off);
+    p->pool_relu = pl.pre_relu;
+    if (chain) {
+        const Step& en = st[i + 2];
+        p->out2 = make_arg(pi, en.out);
+        p->wfrag2 = w_->d_weights_frag && en.w_off >= 0 ? w_->d_weights_frag + en.w_off : nullptr;
+        p->bias2 = wp(en.bias_off);
+        p->scale2 = wp(en.pre_scale_off);
+        p->shift2 = wp(en.pre_shift_off);
+        p->pre_relu2 = en.pre_relu;
+        p->relu2 = en.relu;
+    }
+    return true;
+}
+
+int DeviceModel::PairedCount(const PlanInstance& pi, size_t i, size_t last, ConvArgs* a, PooledArgs* p, LaunchRole* role) const {
+    if (i >= pi.roles.size()) return 1;
+    const LaunchRole& r = pi.roles[i];
+    if (r.count <= 1 || i + size_t(r.count) > last) return 1;
+    if (!MakePooledArgs(pi, i, r.count, r.chain, a, p) || !ConvPooledEligible(*a, *p, r.tile, r.chain)) return 1;      // the launcher would decline: split launches
+    *role = r;
+    return r.count;
+}
+
+// IE_POOL_CONV=0: nothing.  1 / 2 [":tile"]: every eligible transition pairs (2: chains where it can) without timing; a forced tile that is not
+// eligible leaves the steps split.  Unset: one timed choice per signature among the split launches, pool + conv per tile (+ the entry conv on its
+// own) and the chain per tile, cached under kPoolConvTuneCode -- and nothing without a search (IE_AUTOTUNE=0, forced kernels, the request path
+// on an unseen signature).
+void DeviceModel::PairTransitions(TuneContext* ctx, PlanInstance& pi) {
+    pi.roles.clear();
+    const int mode = pool_conv_mode_;
+    if (mode == 0 || precision_ != Precision::F32 || pi.batch_off != 0) return;
+    if (mode < 0 && (!autotune_ || ctx == nullptr)) return;
+    const std::vector<Step>& st = pi.plan.steps;
+    std::vector<LaunchRole> roles(st.size());
+    bool any = false;
+    for (const PairedLaunch& c : FindPairedLaunches(pi.plan)) {
+        if (!c.pairable) continue;
+        const size_t i = size_t(c.steps[0]);
+        ConvArgs a;
+        PooledArgs p;
+        auto can = [&](int t, bool chain) {
+            return t >= 0 && t < kNumConvPooledTiles && (!chain || c.chainable) && MakePooledArgs(pi, i, chain ? 3 : 2, chain, &a, &p) && ConvPooledEligible(a, p, t, chain);
+        };
+        int tile = -1;
+        bool chain = false;
+        if (mode > 0) {
+            if (pool_conv_tile_ >= 0) {
+                if (mode == 2 && can(pool_conv_tile_, true)) { tile = pool_conv_tile_; chain = true; }
+                else if (can(pool_conv_tile_, false)) tile = pool_conv_tile_;
+            } else {
+                for (int t = 0; mode == 2 && tile < 0 && t < kNumConvPooledTiles; ++t) if (can(t, true)) { tile = t; chain = true; }
+                for (int t = 0; tile < 0 && t < kNumConvPooledTiles; ++t) if (can(t, false)) tile = t;
+            }
+        } else {
+            const Step& pl = st[i];
+            const Step& cv = st[i + 1];
+            const size_t span = c.chainable ? 3 : 2;
+            const std::vector<int64_t> key = {cv.out.n * cv.out.h * cv.out.w, cv.out.c, cv.in.c, pl.in.h, pl.in.w, pl.in.pitch, cv.out.pitch, kPoolConvTuneCode,
+                                              pl.pre_scale_off >= 0, cv.bias_off >= 0, span == 3 ? st[i + 2].out.pitch : 0};
+            std::pair<int, int> hit{-1, 0};
+            int code = -1;
+            if (ctx->lookup(key, &hit)) {
+                if (pool_conv_tune_code(hit.first)) code = hit.first - kPoolConvTuneCode;
+            } else if (ctx->allow_search) {
+                auto alone = [&](size_t from) { for (size_t j = from; j < i + span; ++j) LaunchStep(pi, st[j], stream_); };
+                float best = TimeLaunches(*ctx, [&] { alone(i); });
+                code = 0;
+                auto consider = [&](int t, bool ch) {
+                    if (!can(t, ch)) return;
+                    const ConvArgs ta = a;
+                    const PooledArgs tp = p;
+                    const float ms = TimeLaunches(*ctx, [&] {
+                        check(LaunchConvPooled(ta, tp, t, ch, stream_), "conv1x1_pooled");
+                        if (!ch) alone(i + 2);
+                    });
+                    if (ctx->log) std::fprintf(stderr, "[ie-tune] transition at step %zu: pooled tile %d%s %.4f ms (split %.4f ms)\n", i, t, ch ? " chain" : "", ms, best);
+                    if (ms < best) { best = ms; code = 1 + (ch ? kNumConvPooledTiles : 0) + t; }
+                };
+                for (int t = 0; t < kNumConvPooledTiles; ++t) consider(t, false);
+                for (int t = 0; t < kNumConvPooledTiles; ++t) consider(t, true);
+                ctx->store(key, kPoolConvTuneCode + code, 1);
+            }
+            if (code >= 1) {
+                const bool ch = code > kNumConvPooledTiles;
+                const int t = code - 1 - (ch ? kNumConvPooledTiles : 0);
+                if (can(t, ch)) { tile = t; chain = ch; }
+            }
+        }
+        if (tile < 0) continue;
+        roles[i].count = chain ? 3 : 2;
+        roles[i].tile = tile;
+        roles[i].chain = chain;
+        roles[i + 1].count = 0;
+        if (chain) roles[i + 2].count = 0;
+        any = true;
+    }
+    if (any) pi.roles = std::move(roles);
+}
+
 void DeviceModel::RunSteps(PlanInstance& pi, size_t first, size_t last, std::vector<hipEvent_t>* events) {
     size_t k = 0;
     if (events) check(hipEventRecord((*events)[k++], stream_), "hipEventRecord");
+    ConvArgs pa;
+    PooledArgs pp;
+    LaunchRole role;
     for (size_t i = first; i < last && i < pi.plan.steps.size(); ++i) {
-        LaunchStep(pi, pi.plan.steps[i], stream_);
+        // a paired launch covers its steps at once (one event behind it); when its launcher declines, or the range cuts it, the steps launch alone
+        if (const int n = PairedCount(pi, i, std::min(last, pi.plan.steps.size()), &pa, &pp, &role); n > 1) {
+            check(LaunchConvPooled(pa, pp, role.tile, role.chain, stream_), "conv1x1_pooled");
+            i += size_t(n - 1);
+        } else {
+            LaunchStep(pi, pi.plan.steps[i], stream_);
+        }
         if (events) check(hipEventRecord((*events)[k++], stream_), "hipEventRecord");
     }
 }
@@ -1794,31 +2059,48 @@ std::vector<StepTiming> DeviceModel::Profile(PlanInstance& pi, int iters) {
     std::vector<hipEvent_t> ev(ns + 1);
     for (auto& e : ev) check(hipEventCreate(&e), "hipEventCreate");
     std::vector<StepTiming> out(ns);
-    for (size_t i = 0; i < ns; ++i) {
-        out[i].name = pi.plan.steps[i].name;
-        Step handed;
-        out[i].kernel = kernel_label(LaunchedStep(pi, pi.plan.steps[i], handed));
-        out[i].flops = pi.plan.steps[i].flops;
-        out[i].bytes = pi.plan.steps[i].bytes;
+    // one entry per plan step; a launch that covers k steps is one timed group: its k entries carry the launched kernel's label and share its time
+    // in proportion to each step's own lower bound max(bytes / 8 TB/s, flops / 157.3 TFLOP/s)
+    std::vector<std::pair<size_t, int>> groups;
+    for (size_t i = 0; i < ns;) {
+        ConvArgs pa;
+        PooledArgs pp;
+        LaunchRole role;
+        const int n = PairedCount(pi, i, ns, &pa, &pp, &role);
+        groups.emplace_back(i, n);
+        for (size_t j = i; j < i + size_t(n); ++j) {
+            out[j].name = pi.plan.steps[j].name;
+            Step handed;
+            out[j].kernel = n > 1 ? "conv1x1_pooled_kernel<f32,t" + std::to_string(role.tile) + (role.chain ? ",chain>" : ">")
+                                  : kernel_label(LaunchedStep(pi, pi.plan.steps[j], handed));
+            out[j].flops = pi.plan.steps[j].flops;
+            out[j].bytes = pi.plan.steps[j].bytes;
+        }
+        i += size_t(n);
     }
     try {
         RunSteps(pi, 0, ns, nullptr);   // warm
         check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         // per step the MEDIAN over the passes: one disturbed pass (clock ramp, a neighbour's burst) must not colour a family's figure
-        std::vector<std::vector<float>> samples(ns);
+        const size_t ng = groups.size();
+        std::vector<std::vector<float>> samples(ng);
         for (int it = 0; it < iters; ++it) {
             RunSteps(pi, 0, ns, &ev);
             check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-            for (size_t i = 0; i < ns; ++i) {
+            for (size_t i = 0; i < ng; ++i) {
                 float ms = 0;
                 check(hipEventElapsedTime(&ms, ev[i], ev[i + 1]), "hipEventElapsedTime");
                 samples[i].push_back(ms);
             }
         }
-        for (size_t i = 0; i < ns; ++i) {
-            std::sort(samples[i].begin(), samples[i].end());
-            const size_t n = samples[i].size();
-            out[i].ms = n == 0 ? 0.0 : (n % 2 ? samples[i][n / 2] : 0.5 * (samples[i][n / 2 - 1] + samples[i][n / 2]));
+        for (size_t g = 0; g < ng; ++g) {
+            std::sort(samples[g].begin(), samples[g].end());
+            const size_t n = samples[g].size();
+            const double ms = n == 0 ? 0.0 : (n % 2 ? samples[g][n / 2] : 0.5 * (samples[g][n / 2 - 1] + samples[g][n / 2]));
+            auto bound = [&](size_t j) { return std::max({out[j].bytes / 8e12, out[j].flops / 157.3e12, 1e-12}); };
+            double sum = 0;
+            for (size_t j = groups[g].first; j < groups[g].first + size_t(groups[g].second); ++j) sum += bound(j);
+            for (size_t j = groups[g].first; j < groups[g].first + size_t(groups[g].second); ++j) out[j].ms = ms * bound(j) / sum;
         }
     } catch (...) {
         for (auto& e : ev) (void)hipEventDestroy(e);

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -73,8 +74,28 @@ struct DeviceWeights {
     ~DeviceWeights();
 };
 
+// A transition the executor can run as ONE launch of conv1x1_pooled_kernel (kernels_trans.hip) although the plan lists it as a pool step, the 1x1 conv
+// on the pooled tensor and (chain) the next dense block's entry 1x1 conv: consecutive plan steps.  Found from shapes and views alone.
+struct PairedLaunch {
+    std::vector<int> steps;                // pool, conv[, entry conv]
+    bool pairable = false, chainable = false;
+    std::vector<int> tiles, chain_tiles;   // kernels.h kNumConvPooledTiles entries whose shape fits
+    std::string reason;                    // what keeps a near miss from being paired / chained ("" = nothing)
+};
+std::vector<PairedLaunch> FindPairedLaunches(const Plan& plan);
+std::string PairedLaunchesToJson(const std::vector<PairedLaunch>& v);
+
+// Launch role of a plan step: count == 1 its own launch, count == k > 1 the head of a paired launch that also covers the next k - 1 steps (their
+// count is 0).  The plan itself never changes.
+struct LaunchRole {
+    int count = 1;
+    int tile = 0;
+    bool chain = false;
+};
+
 struct PlanInstance {
     Plan plan;
+    std::vector<LaunchRole> roles;     // per plan step; empty = every step launches on its own
     std::vector<float*> buffers;       // device activation buffers (plan.buffer_floats); aliased entries are not owned
     std::vector<char> owned;           // buffers[i] was hipMalloc'ed by this instance
     float* workspace = nullptr;        // split-K slabs
@@ -177,6 +198,12 @@ private:
     struct TuneContext;                  // one top-level Autotune call: timing events, L2 scrub buffer, cache access (executor.cpp)
     void TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s);
     float TimeTrial(TuneContext& ctx, const PlanInstance& pi, const Step& trial);
+    float TimeLaunches(TuneContext& ctx, const std::function<void()>& launch);
+    // Pool + conv (+ entry conv) pairing of a transition's steps (IE_POOL_CONV; searched like the other fused steps when unset).  ctx == nullptr: no timing.
+    void PairTransitions(TuneContext* ctx, PlanInstance& pi);
+    // The paired launch that runs at step i of steps [i, last): its step count (filling the kernel's arguments), or 1 when step i launches alone
+    int PairedCount(const PlanInstance& pi, size_t i, size_t last, ConvArgs* a, PooledArgs* p, LaunchRole* role) const;
+    bool MakePooledArgs(const PlanInstance& pi, size_t i, int count, bool chain, ConvArgs* a, PooledArgs* p) const;
     void SaveTuneCache();
     void EnsurePipeline(PlanInstance& pi, bool allow_tune);
     void AllocInstance(PlanInstance& pi);
@@ -210,6 +237,8 @@ private:
     bool tune_on_demand_ = false;      // IE_TUNE_ON_DEMAND=1: search on the request path too (round-1 behaviour)
     int pipeline_chunks_ = 2;          // IE_PIPELINE_CHUNKS (0/1 = off); measured: 2 ranges beat 4 and 8 (per-range launches cost more than they hide)
     int pipeline_head_ = -1;           // IE_PIPELINE_HEAD: steps run per chunk (-1 = modelled)
+    int pool_conv_mode_ = -1;          // IE_POOL_CONV: -1 unset (searched), 0 never, 1 pool + conv, 2 also the chained entry conv
+    int pool_conv_tile_ = -1;          // its ":tile" suffix (-1: none)
     bool two_pass_splitk_ = true;      // IE_SPLITK_IN_LAUNCH=1 selects the in-launch combine instead of the reduce kernel
     std::map<std::vector<int64_t>, std::unique_ptr<PlanInstance>> plans_;
     // Least-recently-used order of the plan keys (front = oldest).  A server that sees many distinct batch sizes would otherwise keep

@@ -365,6 +365,37 @@ hipError_t LaunchPermuteWeightsFrag(const float* src, float* dst, int Cout, int 
 bool ConvDirectEligible(const ConvArgs& a, int tile);
 hipError_t LaunchConvDirect(const ConvArgs& a, int tile, hipStream_t stream);
 hipError_t InitKernelsDirect();
+// DenseNet transition in one launch (fp32, kernels_trans.hip): conv1x1_pooled_kernel = conv1x1_as_kernel whose staging loop builds each LDS row from the 2x2 /
+// stride-2 window of the pool step in front of the conv (with the pool's BN + ReLU prologue), optionally followed by a second 1x1 conv (the next
+// dense block's entry conv, 128 output channels) on the tile just stored.  `a` is the conv step's argument set (a.in = the pooled view: shape
+// only, never read; no prologue of its own), PooledArgs carries the pool's operands and the second conv's, the way FusedArgs carries the 3x3's.
+struct PooledConsts {
+    unsigned mg20_ow = 0, mg20_oh = 0;     // ceil(2^20 / d): output width / height (per-lane quotients with a 24-bit multiply)
+    unsigned mg32_ohw = 0, mg32_ow = 0;    // floor(2^32 / d): output pixels per image / output width (wave-uniform quotients, one correction step)
+};
+struct PooledArgs {
+    TensorArg pin;                     // the pool's input: NHWC channel slice at twice the conv's resolution
+    const float* pool_scale = nullptr; // the pool's prologue (x * scale + shift, then ReLU if pool_relu), or null
+    const float* pool_shift = nullptr;
+    int pool_relu = 0;
+    // chained second conv: in = the first conv's output view, prologue scale2 / shift2 (always present), 16 output channels per wave
+    TensorArg out2;
+    const float* wfrag2 = nullptr;
+    const float* bias2 = nullptr;
+    const float* scale2 = nullptr;
+    const float* shift2 = nullptr;
+    int pre_relu2 = 0, relu2 = 0;
+    PooledConsts k;                    // filled by LaunchConvPooled
+};
+// tiles 0..4 = conv1x1_as_kernel's shapes {waves, 16-channel blocks per wave, 16-pixel blocks}: {8,1,2} {4,1,2} {8,2,2} {4,1,1} {2,2,1}; tiles 0 and 2
+// (128 / 256 channels per workgroup) can chain; tile 5 = {1,1,2}: 16 channels per workgroup, for channel counts that are no multiple of 64; tiles 6 / 7 =
+// {8,1,1} / {8,2,1}: the two chain shapes on 16-pixel blocks
+constexpr int kNumConvPooledTiles = 8;
+// by shapes alone (no device): K input channels, cout output channels, the chained conv's cout2
+bool ConvPooledShapeOk(int tile, bool chain, int64_t k, int64_t cout, int64_t cout2);
+bool ConvPooledEligible(const ConvArgs& a, const PooledArgs& p, int tile, bool chain);
+hipError_t LaunchConvPooled(const ConvArgs& a, const PooledArgs& p, int tile, bool chain, hipStream_t stream);
+hipError_t InitKernelsTrans();
 // Stem conv (7x7 / stride 2 / pad 3, Cin = 3, Cout <= 64) straight from the dense NCHW fp32 graph input (kernels_stem.hip);
 // half arithmetic + half output in fp16 mode, fp32 otherwise.
 // Workgroups of `kernel` (block threads, lds dynamic LDS bytes) one CU holds, from the occupancy API (registers included), cached.
