@@ -84,6 +84,19 @@ AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s) {
     return a;
 }
 
+WinAttnArgs MakeWinAttnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
+    WinAttnArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    a.heads = s.heads;
+    a.head_dim = s.head_dim;
+    a.scale = s.attn_scale;
+    a.wh = s.win_h; a.ww = s.win_w; a.sh = s.shift_h; a.sw = s.shift_w;
+    a.bias = s.w_off >= 0 ? weights + s.w_off : nullptr;
+    a.mask = s.masked && s.w2_off >= 0 ? weights + s.w2_off : nullptr;
+    return a;
+}
+
 constexpr size_t kPinnedBytes = size_t(4) << 20;              // pinned staging for results (logits are KBs; larger outputs go direct)
 constexpr int64_t kTuneWorkspaceFloats = int64_t(16) << 20;   // 64 MiB of split-K slabs available to the autotuner
 constexpr int kNumCounters = 1 << 16;
@@ -229,6 +242,7 @@ DeviceModel::DeviceModel(std::shared_ptr<const OnnxModel> model, int device_id, 
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsBlock();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsWs8();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsAttn();
+        if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsWattn();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsTrans();
     });
     check(g_kernels_err, "InitKernels");
@@ -1439,6 +1453,11 @@ const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Ste
         scratch.tile = 0;
         return scratch;
     }
+    if (s.kind == StepKind::WindowAttention && s.tile != 0 && !WindowAttentionEligible(MakeWinAttnArgs(pi, s, w_->d_weights), s.tile)) {      // likewise
+        scratch = s;
+        scratch.tile = 0;
+        return scratch;
+    }
     if (s.kind != StepKind::Conv) return s;
     auto with_tile = [&](int tile) -> const Step& {
         if (tile == s.tile) return s;
@@ -1681,6 +1700,18 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the attention kernels");
             check(LaunchAttention(MakeAttnArgs(pi, s), s.tile, stream_), "attention");
             break;
+        case StepKind::WindowAttention:
+            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the window-attention kernels");
+            check(LaunchWindowAttention(MakeWinAttnArgs(pi, s, wb), s.tile, stream_), "window_attention");
+            break;
+        case StepKind::PatchMerge: {
+            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the patch-merge kernel");
+            PatchMergeArgs a;
+            a.in = make_arg(pi, s.in);
+            a.out = make_arg(pi, s.out);
+            check(LaunchPatchMerge(a, stream_), "patch_merge");
+            break;
+        }
     }
 }
 
@@ -1752,6 +1783,13 @@ static std::string kernel_label(const Step& s) {
         case StepKind::Attention:
             return s.tile == 0 ? std::string("attention_generic_kernel")
                                : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
+        case StepKind::WindowAttention:
+            return s.tile == 0 ? std::string("window_attention_generic_kernel")
+                               : std::string("window_attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
+        case StepKind::PatchMerge: {
+            const bool vec = !s.in.nchw && !s.out.nchw && PatchMergeVec(s.in.f16, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off);
+            return std::string("patch_merge_kernel<") + (vec ? (s.out.f16 ? "f16,8>" : "f32,4>") : (s.out.f16 ? "f16,1>" : "f32,1>"));
+        }
         case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }
     return "?";

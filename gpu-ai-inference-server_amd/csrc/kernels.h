@@ -263,6 +263,48 @@ bool AttentionEligible(const AttnArgs& a, int tile);
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);
 hipError_t InitKernelsAttn();            // once per process, before any capture: lets the MFMA kernels take more than 64 KiB of LDS
 
+// Attention inside (shifted) windows of a channels-last map (kernels_wattn.hip; Swin).  in = the qkv map [N, H, W, 3 D], out = [N, H, W, D].  The map is
+// rolled by (-sh, -sw) cyclically and cut into windows of wh x ww pixels; window (wy, wx) holds the L = wh ww tokens t = ty ww + tx at the rolled
+// pixel (wy wh + ty, wx ww + tx), i.e. the map's own pixel ((wy wh + ty + sh) mod H, (wx ww + tx + sw) mod W).  Per window and head
+//   out[pixel(i), h hd + e] = sum_j softmax_j(scale q_i . k_j + bias[h][i][j] + mask[window][i][j]) v[j, e]
+// and every result lands on the pixel its query came from: roll, partition, reverse and roll-back are index arithmetic, never a copy.
+// Tables (fp32 in every precision, packed by the planner): Lp = L rounded up to whole 32-key tiles; bias[h][j][i] and mask[window][j][i] are
+// [.][Lp][Lp] with the QUERY index fastest; padded keys (j >= L) hold -inf in the bias table and 0 in the mask table, padded queries 0.
+struct WinAttnArgs {
+    TensorArg in, out;
+    int heads = 0, head_dim = 0;
+    float scale = 1.f;
+    int wh = 0, ww = 0, sh = 0, sw = 0;
+    const float* bias = nullptr;       // [heads][Lp][Lp]
+    const float* mask = nullptr;       // [nW][Lp][Lp] or null
+};
+// tile 0: window_attention_generic_kernel (one wave per query row; any window, shift, head_dim, pitch, offset; float or half).  tile 1:
+// window_attention_mfma_kernel<T, 32> (one wave per (image, window, head), four per workgroup; K and V of the window in LDS): head_dim 32, at most
+// 64 tokens per window, channel counts, pitches and offsets multiples of the 16-byte vector
+constexpr int kNumWinAttnTiles = 2;
+constexpr int kWinAttnMaxTokens = 64;
+constexpr int64_t WinAttnPaddedTokens(int64_t L) { return (L + 31) / 32 * 32; }
+constexpr bool WinAttnMfmaFits(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out) {
+    const int64_t V = f16 ? 8 : 4;
+    return hd == 32 && L >= 1 && L <= kWinAttnMaxTokens && c_in % V == 0 && pitch_in % V == 0 && off_in % V == 0 && c_out % V == 0 && pitch_out % V == 0 &&
+           off_out % V == 0;
+}
+bool WindowAttentionEligible(const WinAttnArgs& a, int tile);
+hipError_t LaunchWindowAttention(const WinAttnArgs& a, int tile, hipStream_t stream);
+hipError_t InitKernelsWattn();           // once per process, before any capture: the fp32 MFMA kernel takes 72 KiB of LDS
+
+// Patch merging (kernels_wattn.hip; Swin): out[n, y, x, k C + c] = in[n, 2 y + (k & 1), 2 x + (k >> 1), c] for k = 0 ... 3 (torchvision's channel
+// order x[0::2, 0::2], x[1::2, 0::2], x[0::2, 1::2], x[1::2, 1::2]); in [N, H, W, C] with even H and W, out [N, H/2, W/2, 4 C].  One thread per 16-byte
+// vector where C, the pitches and the offsets allow (PatchMergeVec), else one per element.
+struct PatchMergeArgs {
+    TensorArg in, out;
+};
+constexpr bool PatchMergeVec(bool f16_in, bool f16_out, int64_t c, int64_t pitch_in, int64_t off_in, int64_t pitch_out, int64_t off_out) {
+    const int64_t V = f16_out ? 8 : 4;
+    return f16_in == f16_out && c % V == 0 && pitch_in % V == 0 && off_in % V == 0 && pitch_out % V == 0 && off_out % V == 0;
+}
+hipError_t LaunchPatchMerge(const PatchMergeArgs& a, hipStream_t stream);
+
 // Class token and position embedding (kernels_tokens.hip): out[n, 0, :] = cls + pos[0], out[n, 1 + p, :] = in[n, p, :] + pos[1 + p]; cls [D] and
 // pos [L0 + 1][D] (or null) fp32.  16-byte vectors where D, the pitches and the bases allow, else one element per thread.
 struct TokenAssembleArgs {

@@ -4,6 +4,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <set>
 #include <sstream>
@@ -43,7 +44,7 @@ struct Val {
     int64_t sel_rows = 1, sel_idx = 0;
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -67,6 +68,10 @@ struct LNode {
     // L_ATTENTION: in = the qkv tokens [N, L, 3 heads head_dim]
     int heads = 0, head_dim = 0;
     double attn_scale = 1.0;
+    // L_WATTN: in = the qkv map [N, 3 heads head_dim, H, W] read channels-last; w = the relative-position bias [heads][L][L], w2 = the shift mask
+    // [nW][L][L] (masked only), both as the graph's constants hold them (query row, key column); EmitWindowAttention packs them for the kernels
+    int win_h = 0, win_w = 0, shift_h = 0, shift_w = 0;
+    bool masked = false;
     bool has_pre = false, pre_relu = false, relu = false;
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
@@ -380,6 +385,66 @@ struct Planner {
     std::set<const OnnxNode*> attn_skip;
     void MatchAttention();
     void ImportAttention(const OnnxNode& on, const AttnMatch& am);
+    // What the matchers on the ONNX nodes share: producer and reader count of every name, the constants (initializers and Constant nodes)
+    struct GraphIndex {
+        const OnnxModel* m = nullptr;
+        std::map<std::string, const OnnxNode*> prod;
+        std::map<std::string, int> readers;
+        std::map<std::string, OnnxTensor> consts;
+        const OnnxTensor* cst(const std::string& name) const {
+            const auto it = m->initializers.find(name);
+            if (it != m->initializers.end()) return &it->second;
+            const auto jt = consts.find(name);
+            return jt == consts.end() ? nullptr : &jt->second;
+        }
+        const OnnxNode* producer(const std::string& name) const { const auto it = prod.find(name); return it == prod.end() ? nullptr : it->second; }
+        int nreaders(const std::string& name) const { const auto it = readers.find(name); return it == readers.end() ? 0 : it->second; }
+        std::vector<const OnnxNode*> readers_of(const std::string& name) const {
+            std::vector<const OnnxNode*> out;
+            for (const OnnxNode& on : m->nodes) for (const std::string& i : on.inputs) if (i == name) { out.push_back(&on); break; }
+            return out;
+        }
+        const OnnxNode* only_reader(const std::string& name) const {
+            if (nreaders(name) != 1) return nullptr;
+            const auto r = readers_of(name);
+            return r.size() == 1 ? r[0] : nullptr;
+        }
+        bool act_matmul(const OnnxNode* p) const { return p && p->op == "MatMul" && p->inputs.size() == 2 && !cst(p->inputs[0]) && !cst(p->inputs[1]); }
+        // the name above a chain of Mul / Div by constants (nothing checked, nothing taken)
+        std::string peel_quiet(std::string cur) const {
+            for (;;) {
+                const OnnxNode* p = producer(cur);
+                if (!p || (p->op != "Mul" && p->op != "Div") || p->inputs.size() != 2) return cur;
+                const OnnxTensor *c0 = cst(p->inputs[0]), *c1 = cst(p->inputs[1]);
+                if ((c0 != nullptr) == (c1 != nullptr) || (p->op == "Div" && !c1)) return cur;
+                cur = p->inputs[c0 ? 1 : 0];
+            }
+        }
+    };
+    GraphIndex gi;
+    void IndexGraph();
+    // the part of an attention between the [., L, 3, H, hd] Reshape and the [., L, D] Reshape, matched from its Softmax and the name of its scores
+    struct AttnCore { const OnnxNode *rs = nullptr, *orr = nullptr; std::vector<const OnnxNode*> taken; double scale = 1.0; std::vector<int64_t> shape5, shape3; };
+    AttnCore MatchAttentionCore(const OnnxNode& sm, const OnnxNode* pv, const std::string& scores, const std::string& miss_prefix);
+    // MatchWindowAttention: the shifted-window attention regions of a Swin export.  wattn_head: the rank-5 Reshape of a region -> what
+    // ImportWindowAttention needs; view_alias: the last node of a partition / of a reverse -> the name whose channels-last value its output renames;
+    // wattn_skip: the other nodes of the regions (they import nothing); wattn_softmax: the Softmax nodes MatchAttention must leave alone
+    struct WinMatch {
+        int64_t heads = 0, head_dim = 0, wh = 0, ww = 0, nh = 0, nw = 0, sh = 0, sw = 0;
+        bool masked = false;
+        double scale = 1.0;
+        std::vector<float> bias, mask;
+        std::string out, name;
+    };
+    std::map<const OnnxNode*, WinMatch> wattn_head;
+    std::map<const OnnxNode*, std::string> view_alias;
+    std::set<const OnnxNode*> wattn_skip, wattn_softmax;
+    void MatchWindowAttention();
+    void ImportWindowAttention(const OnnxNode& on, const WinMatch& wm);
+    // MatchPatchMerge: the eight strided Slices and the Concat(axis -1) of a Swin patch merging.  merge_head: the Concat -> the sliced name
+    std::map<const OnnxNode*, std::string> merge_head;
+    void MatchPatchMerge();
+    void ImportPatchMerge(const OnnxNode& on, const std::string& src);
     bool FoldExpand(const OnnxNode& on, const LNode& n);
     bool ImportTokenView(const OnnxNode& on, LNode& n);
     void ImportTokenConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
@@ -435,6 +500,8 @@ struct Planner {
     void EmitLayerNorm(const LNode& n, Step& s);
     void EmitTokenAssemble(const LNode& n, Step& s);
     void EmitAttention(const LNode& n, Step& s);
+    void EmitWindowAttention(const LNode& n, Step& s);
+    void EmitPatchMerge(const LNode& n, Step& s) const;
 
     // ---- step-level fusions, I/O descriptors ----
     void FuseDenseLayers();
@@ -1250,6 +1317,15 @@ void Planner::ImportNode(const OnnxNode& on) {
     LNode n;
     n.name = on.name.empty() ? on.outputs[0] : on.name;
     const std::string& op = on.op;
+    // the nodes of a matched window-attention region or patch merging: ranks 5 and 6 and the Slices never become values
+    if (const auto va = view_alias.find(&on); va != view_alias.end()) {
+        if (!L.is_cl(va->second)) fail(op + " " + n.name + ": the window region reads " + va->second + ", which is not a channels-last view [N, H, W, C]");
+        L.alias_name(on.outputs[0], L.get_val(va->second), true);
+        return;
+    }
+    if (wattn_skip.count(&on)) return;
+    if (const auto wm = wattn_head.find(&on); wm != wattn_head.end()) { ImportWindowAttention(on, wm->second); return; }
+    if (const auto mh = merge_head.find(&on); mh != merge_head.end()) { ImportPatchMerge(on, mh->second); return; }
     // a channels-last view may feed only the ops that read it as one: anything else (a Shape and the other folded ops included, hence before
     // the folds) would take its n / c / h / w for the ONNX dims
     static const std::set<std::string> cl_ops = {"LayerNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose"};
@@ -1431,13 +1507,12 @@ void Planner::ImportTokenConcat(const OnnxNode& on, LNode& n, std::vector<int64_
 //   S = MatMul(q [* c], Transpose(k, [0,1,3,2]) [* c]) [* c | / c] -> P = Softmax(S, axis -1) -> MatMul(P, v) -> Transpose [0,2,1,3] -> Reshape [N, L, D]
 // with scalar constants c in either operand order, every intermediate read by the next node only.  A near miss is refused naming what did not
 // match; nothing is approximated.  A Softmax elsewhere is left to the import, which refuses it as an unsupported operator.
-void Planner::MatchAttention() {
-    std::map<std::string, const OnnxNode*> prod;
-    std::map<std::string, int> readers;
-    std::map<std::string, OnnxTensor> consts;
+void Planner::IndexGraph() {
+    if (gi.m) return;
+    gi.m = &m;
     for (const OnnxNode& on : m.nodes) {
-        for (const std::string& o : on.outputs) if (!o.empty()) prod[o] = &on;
-        for (const std::string& i : on.inputs) if (!i.empty()) ++readers[i];
+        for (const std::string& o : on.outputs) if (!o.empty()) gi.prod[o] = &on;
+        for (const std::string& i : on.inputs) if (!i.empty()) ++gi.readers[i];
         if (on.op == "Constant" && on.outputs.size() == 1 && on.attrs.size() == 1) {
             const OnnxAttr& at = on.attrs.begin()->second;
             OnnxTensor t;
@@ -1445,34 +1520,62 @@ void Planner::MatchAttention() {
             else if (at.name == "value_float") { t.dtype = ONNX_FLOAT; t.f = {at.f}; }
             else if (at.name == "value_int") { t.dtype = ONNX_INT64; t.i = {at.i}; }
             else continue;
-            consts[on.outputs[0]] = t;
+            gi.consts[on.outputs[0]] = t;
         }
     }
-    for (const auto& vo : m.outputs) ++readers[vo.name];
-    auto cst = [&](const std::string& name) -> const OnnxTensor* {
-        const auto it = m.initializers.find(name);
-        if (it != m.initializers.end()) return &it->second;
-        const auto jt = consts.find(name);
-        return jt == consts.end() ? nullptr : &jt->second;
-    };
-    auto producer = [&](const std::string& name) -> const OnnxNode* { const auto it = prod.find(name); return it == prod.end() ? nullptr : it->second; };
-    auto act_matmul = [&](const OnnxNode* p) { return p && p->op == "MatMul" && p->inputs.size() == 2 && !cst(p->inputs[0]) && !cst(p->inputs[1]); };
-    auto perm_is = [](const OnnxNode* p, std::vector<int64_t> want) { return p && p->op == "Transpose" && p->attr_ints("perm", {}) == want; };
+    for (const auto& vo : m.outputs) ++gi.readers[vo.name];
+}
+
+void Planner::MatchAttention() {
+    IndexGraph();
     for (const OnnxNode& sm : m.nodes) {
-        if (sm.op != "Softmax" || sm.inputs.size() != 1 || sm.outputs.size() != 1) continue;
+        if (sm.op != "Softmax" || sm.inputs.size() != 1 || sm.outputs.size() != 1 || wattn_softmax.count(&sm)) continue;
         const std::string nm = sm.name.empty() ? sm.outputs[0] : sm.name;
-        auto miss = [&](const std::string& what) { fail("Softmax " + nm + ": the attention pattern around it does not match: " + what); };
+        const std::string prefix = "Softmax " + nm + ": the attention pattern around it does not match: ";
+        // is this an attention at all?  scores from a MatMul of two activations (through scalings, or behind a mask Add), probabilities into a MatMul
+        const OnnxNode* pv = nullptr;
+        for (const OnnxNode& on : m.nodes)
+            if (on.op == "MatMul" && on.inputs.size() == 2 && on.inputs[0] == sm.outputs[0] && !gi.cst(on.inputs[1])) pv = &on;
+        if (!pv) continue;
+        const OnnxNode* top = gi.producer(gi.peel_quiet(sm.inputs[0]));
+        if (top && top->op == "Add" && top->inputs.size() == 2 &&
+            (gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[0]))) || gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[1])))))
+            fail(prefix + "an additive mask (Add " + (top->name.empty() ? top->outputs[0] : top->name) + ") on the scores is not supported");
+        if (!gi.act_matmul(top)) continue;
+        const AttnCore c = MatchAttentionCore(sm, pv, sm.inputs[0], prefix);
+        AttnMatch am;
+        am.heads = c.shape5[3];
+        am.head_dim = c.shape5[4];
+        am.scale = c.scale;
+        am.out = c.orr->outputs[0];
+        am.shape5 = c.shape5;
+        am.shape3 = c.shape3;
+        am.name = (c.rs->name.empty() ? c.rs->outputs[0] : c.rs->name) + "+" + nm + "+" + (c.orr->name.empty() ? c.orr->outputs[0] : c.orr->name);
+        attn_head[c.rs] = am;
+        for (const OnnxNode* p : c.taken) attn_skip.insert(p);
+        attn_skip.insert(c.orr);
+    }
+}
+
+// `scores`: the name the scaled q k^T product reaches the Softmax (or, in a window attention, the bias Add) under
+Planner::AttnCore Planner::MatchAttentionCore(const OnnxNode& sm, const OnnxNode* pv, const std::string& scores, const std::string& miss_prefix) {
+    const auto& readers = gi.readers;
+    auto cst = [&](const std::string& name) { return gi.cst(name); };
+    auto producer = [&](const std::string& name) { return gi.producer(name); };
+    auto perm_is = [](const OnnxNode* p, std::vector<int64_t> want) { return p && p->op == "Transpose" && p->attr_ints("perm", {}) == want; };
+    auto nreaders = [&](const std::string& name) { const auto it = readers.find(name); return it == readers.end() ? 0 : it->second; };
+    {
+        auto miss = [&](const std::string& what) { fail(miss_prefix + what); };
         std::vector<const OnnxNode*> taken;
         double scale = 1.0;
         // a chain of Mul / Div by scalar constants above `cur`; each link read once
-        auto peel = [&](std::string cur, bool commit) -> std::string {
+        auto peel = [&](std::string cur) -> std::string {
             for (;;) {
                 const OnnxNode* p = producer(cur);
                 if (!p || (p->op != "Mul" && p->op != "Div") || p->inputs.size() != 2) return cur;
                 const OnnxTensor *c0 = cst(p->inputs[0]), *c1 = cst(p->inputs[1]);
                 if ((c0 != nullptr) == (c1 != nullptr) || (p->op == "Div" && !c1)) return cur;
                 const OnnxTensor* c = c0 ? c0 : c1;
-                if (!commit) { cur = p->inputs[c0 ? 1 : 0]; continue; }
                 if (c->numel() != 1 || c->f.size() != 1) miss("the scale constant of " + p->op + " " + (p->name.empty() ? p->outputs[0] : p->name) + " is not a scalar");
                 if (p->op == "Div" && c->f[0] == 0.f) miss("division by zero in " + p->name);
                 scale = p->op == "Div" ? scale / double(c->f[0]) : scale * double(c->f[0]);
@@ -1480,24 +1583,14 @@ void Planner::MatchAttention() {
                 cur = p->inputs[c0 ? 1 : 0];
             }
         };
-        // is this an attention at all?  scores from a MatMul of two activations (through scalings, or behind a mask Add), probabilities into a MatMul
-        const OnnxNode* pv = nullptr;
-        for (const OnnxNode& on : m.nodes)
-            if (on.op == "MatMul" && on.inputs.size() == 2 && on.inputs[0] == sm.outputs[0] && !cst(on.inputs[1])) pv = &on;
-        if (!pv) continue;
-        const OnnxNode* top = producer(peel(sm.inputs[0], false));
-        if (top && top->op == "Add" && top->inputs.size() == 2 &&
-            (act_matmul(producer(peel(top->inputs[0], false))) || act_matmul(producer(peel(top->inputs[1], false)))))
-            miss("an additive mask (Add " + (top->name.empty() ? top->outputs[0] : top->name) + ") on the scores is not supported");
-        if (!act_matmul(top)) continue;
         const int64_t axis = sm.attr_i("axis", -1);
         if (axis != -1 && axis != 3) miss("Softmax axis = " + std::to_string(axis) + " (only the last axis, -1 or 3, is an attention)");
-        const OnnxNode* qk = producer(peel(sm.inputs[0], true));
-        const std::string q = peel(qk->inputs[0], true);
-        const std::string kt_name = peel(qk->inputs[1], true);
+        const OnnxNode* qk = producer(peel(scores));
+        const std::string q = peel(qk->inputs[0]);
+        const std::string kt_name = peel(qk->inputs[1]);
         const OnnxNode* kt = producer(kt_name);
         if (!perm_is(kt, {0, 1, 3, 2})) miss("the second operand of MatMul " + qk->name + " is not Transpose(k, perm [0,1,3,2])");
-        const std::string k = peel(kt->inputs[0], true);
+        const std::string k = peel(kt->inputs[0]);
         const std::string v = pv->inputs[1];
         // q, k, v = slices 0, 1, 2 of one transposed qkv tensor
         const OnnxNode* split = nullptr;
@@ -1518,7 +1611,7 @@ void Planner::MatchAttention() {
                     src = sp->inputs[0];
                     if (split && split != sp) idx = -1;
                     split = sp;
-                    if (readers[g->inputs[0]] != 1) miss("the Split output " + g->inputs[0] + " has a second reader");
+                    if (nreaders(g->inputs[0]) != 1) miss("the Split output " + g->inputs[0] + " has a second reader");
                 }
             }
             if (idx != want || src.empty() || (!T.empty() && src != T))
@@ -1538,14 +1631,9 @@ void Planner::MatchAttention() {
         if (!s5 || s5->i.size() != 5 || s5->i[2] != 3 || s5->i[3] <= 0 || s5->i[4] <= 0)
             miss("the qkv tensor is not Reshape(x, [N, L, 3, H, hd]) with a constant shape");
         // behind the second MatMul: Transpose [0,2,1,3] -> Reshape [N, L, D]
-        auto only_reader = [&](const std::string& name) -> const OnnxNode* {
-            if (readers[name] != 1) return nullptr;
-            for (const OnnxNode& on : m.nodes) for (const std::string& i : on.inputs) if (i == name) return &on;
-            return nullptr;
-        };
-        const OnnxNode* ot = only_reader(pv->outputs[0]);
+        const OnnxNode* ot = gi.only_reader(pv->outputs[0]);
         if (!perm_is(ot, {0, 2, 1, 3})) miss("the result of MatMul " + pv->name + " is not read by Transpose(perm [0,2,1,3]) alone");
-        const OnnxNode* orr = only_reader(ot->outputs[0]);
+        const OnnxNode* orr = gi.only_reader(ot->outputs[0]);
         const OnnxTensor* s3 = orr && orr->op == "Reshape" && orr->inputs.size() == 2 ? cst(orr->inputs[1]) : nullptr;
         if (!s3 || s3->i.size() != 3) miss("the transposed result is not read by Reshape(., [N, L, D]) alone");
         // every intermediate has one reader (the transposed qkv tensor: its three Gathers or its Split)
@@ -1553,20 +1641,17 @@ void Planner::MatchAttention() {
         for (const OnnxNode* p : taken)
             for (const std::string& o : p->outputs) {
                 const int want = (p == tr && !split) ? 3 : 1;
-                if (readers[o] != want) miss((p == qk || o == sm.inputs[0] ? "the scores " : "the intermediate ") + o + " has " + std::to_string(readers[o]) + " readers, not " + std::to_string(want));
+                if (nreaders(o) != want) miss((p == qk || o == sm.inputs[0] ? "the scores " : "the intermediate ") + o + " has " + std::to_string(nreaders(o)) + " readers, not " + std::to_string(want));
             }
-        if (readers[rs->outputs[0]] != 1) miss("the intermediate " + rs->outputs[0] + " has a second reader");
-        AttnMatch am;
-        am.heads = s5->i[3];
-        am.head_dim = s5->i[4];
-        am.scale = scale;
-        am.out = orr->outputs[0];
-        am.shape5 = s5->i;
-        am.shape3 = s3->i;
-        am.name = (rs->name.empty() ? rs->outputs[0] : rs->name) + "+" + nm + "+" + (orr->name.empty() ? orr->outputs[0] : orr->name);
-        attn_head[rs] = am;
-        for (const OnnxNode* p : taken) attn_skip.insert(p);
-        attn_skip.insert(orr);
+        if (nreaders(rs->outputs[0]) != 1) miss("the intermediate " + rs->outputs[0] + " has a second reader");
+        AttnCore c;
+        c.rs = rs;
+        c.orr = orr;
+        c.taken = std::move(taken);
+        c.scale = scale;
+        c.shape5 = s5->i;
+        c.shape3 = s3->i;
+        return c;
     }
 }
 
@@ -1589,6 +1674,364 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     n.head_dim = int(am.head_dim);
     n.attn_scale = am.scale;
     push_node(std::move(n), am.out, {X.n, D, 1, X.w}, true);
+}
+
+// ---- window attention: the shifted-window attention of a Swin export as ONE node on the unpermuted map -------------------------------
+// Matched on the ONNX nodes, before the import and before MatchAttention, around every Softmax whose scores pass an Add of a constant and whose
+// qkv tensor comes from a rank-6 window partition:
+//   src [N,H,W,C] -> [Pad, all pads 0] -> [roll: per dim Concat(Slice(starts [s], ends [max]), Slice(starts [0], ends [s]))]
+//   -> Reshape [N, H/wh, wh, W/ww, ww, C] -> Transpose [0,1,3,2,4,5] -> Reshape [N nW, L, C] -> [MatMul W -> Add b]                (the partition)
+//   -> the attention of MatchAttentionCore with Add bias [1 | -, heads, L, L] behind the scaled scores and, in shifted blocks,
+//      Reshape [N, nW, heads, L, L] -> Add mask [1 | -, nW, 1, L, L] -> Reshape [N nW, heads, L, L] in front of the Softmax
+//   -> [MatMul Wp -> Add bp] -> Reshape [N, H/wh, W/ww, wh, ww, C] -> Transpose [0,1,3,2,4,5] -> Reshape [N, H, W, C]             (the reverse)
+//   -> [roll back: the same with starts [-s] / ends [-s]] -> [Slice(starts [0,0], ends [H,W], axes [1,2]) of the padding]
+// A Linear acts per token and commutes with the permutation of tokens, so the Linears stay ordinary nodes on the channels-last map: the last
+// partition node renames src, the last reverse node renames the projection's result, and the attention node between them does the index arithmetic.
+// A Softmax whose qkv tensor does not come from a rank-6 partition is left to MatchAttention (which refuses an additive mask by name).
+void Planner::MatchWindowAttention() {
+    IndexGraph();
+    auto nm_of = [](const OnnxNode* p) { return p->name.empty() ? p->outputs[0] : p->name; };
+    auto perm_is = [](const OnnxNode* p, std::vector<int64_t> want) { return p && p->op == "Transpose" && p->attr_ints("perm", {}) == want; };
+    auto shape_of = [&](const OnnxNode* p, size_t rank) -> const OnnxTensor* {
+        const OnnxTensor* t = p && p->op == "Reshape" && p->inputs.size() == 2 ? gi.cst(p->inputs[1]) : nullptr;
+        return t && t->i.size() == rank ? t : nullptr;
+    };
+    // an Add / MatMul with exactly one constant operand: the index of the activation operand, else -1
+    auto act_side = [&](const OnnxNode* p) { return !p || p->inputs.size() != 2 || (gi.cst(p->inputs[0]) != nullptr) == (gi.cst(p->inputs[1]) != nullptr) ? -1 : (gi.cst(p->inputs[0]) ? 1 : 0); };
+    // a float constant, through Unsqueeze nodes of constants (the constant folds of the import reduce exactly these)
+    std::function<bool(const std::string&, OnnxTensor&)> resolve = [&](const std::string& name, OnnxTensor& out) -> bool {
+        if (const OnnxTensor* t = gi.cst(name)) { out = *t; return true; }
+        const OnnxNode* p = gi.producer(name);
+        if (!p || p->op != "Unsqueeze" || p->inputs.empty() || !resolve(p->inputs[0], out)) return false;
+        std::vector<int64_t> ax = p->attr_ints("axes", {});
+        if (ax.empty() && p->inputs.size() > 1) if (const OnnxTensor* at = gi.cst(p->inputs[1])) ax = at->i;
+        if (ax.empty()) return false;
+        const int64_t rank = int64_t(out.dims.size() + ax.size());
+        for (auto& a : ax) if (a < 0) a += rank;
+        std::sort(ax.begin(), ax.end());
+        for (int64_t a : ax) { if (a < 0 || a > int64_t(out.dims.size())) return false; out.dims.insert(out.dims.begin() + a, 1); }
+        return true;
+    };
+    for (const OnnxNode& sm : m.nodes) {
+        if (sm.op != "Softmax" || sm.inputs.size() != 1 || sm.outputs.size() != 1) continue;
+        const std::string nm = nm_of(&sm);
+        const std::string prefix = "Softmax " + nm + ": the window-attention pattern around it does not match: ";
+        auto miss = [&](const std::string& what) { fail(prefix + what); };
+        // ---- is this a window attention at all?  (quietly: everything else is MatchAttention's) ----
+        const OnnxNode* pv = nullptr;
+        for (const OnnxNode& on : m.nodes)
+            if (on.op == "MatMul" && on.inputs.size() == 2 && on.inputs[0] == sm.outputs[0] && !gi.cst(on.inputs[1])) pv = &on;
+        if (!pv) continue;
+        const OnnxNode *m4 = nullptr, *madd = nullptr, *m5 = nullptr;
+        const OnnxNode* badd = gi.producer(sm.inputs[0]);
+        if (badd && badd->op == "Reshape") {
+            m4 = badd;
+            madd = gi.producer(m4->inputs[0]);
+            if (!madd || madd->op != "Add" || madd->inputs.size() != 2) continue;
+            for (int k = 0; k < 2 && !m5; ++k)
+                if (const OnnxNode* p = gi.producer(madd->inputs[size_t(k)]); p && p->op == "Reshape") m5 = p;
+            if (!m5) continue;
+            badd = gi.producer(m5->inputs[0]);
+        }
+        if (!badd || badd->op != "Add" || badd->inputs.size() != 2) continue;
+        int bs = -1;
+        for (int k = 0; k < 2; ++k) if (gi.act_matmul(gi.producer(gi.peel_quiet(badd->inputs[size_t(k)])))) bs = k;
+        if (bs < 0) continue;
+        const OnnxNode* rs = nullptr;
+        {
+            const OnnxNode* qk = gi.producer(gi.peel_quiet(badd->inputs[size_t(bs)]));
+            const OnnxNode* g = gi.producer(gi.peel_quiet(qk->inputs[0]));
+            if (g && g->op == "Squeeze" && !g->inputs.empty()) g = gi.producer(g->inputs[0]);
+            const OnnxNode* tr = g && !g->inputs.empty() ? gi.producer(g->inputs[0]) : nullptr;
+            rs = tr && tr->op == "Transpose" && !tr->inputs.empty() ? gi.producer(tr->inputs[0]) : nullptr;
+        }
+        if (!rs || rs->op != "Reshape" || rs->inputs.empty()) continue;
+        const OnnxNode *qadd = nullptr, *qmm = nullptr;
+        std::string part_out = rs->inputs[0];
+        if (const OnnxNode* p = gi.producer(part_out); p && p->op == "Add" && act_side(p) >= 0)
+            if (const OnnxNode* q = gi.producer(p->inputs[size_t(act_side(p))]); q && q->op == "MatMul" && act_side(q) == 0) { qadd = p; qmm = q; part_out = q->inputs[0]; }
+        const OnnxNode* p3 = gi.producer(part_out);
+        const OnnxNode* pt = p3 && p3->op == "Reshape" && !p3->inputs.empty() ? gi.producer(p3->inputs[0]) : nullptr;
+        if (!pt || pt->op != "Transpose" || pt->attr_ints("perm", {}).size() != 6) continue;
+        wattn_softmax.insert(&sm);
+
+        // ---- the attention between the two Reshapes, the bias and the mask ----
+        if (sm.attr_i("axis", -1) != -1 && sm.attr_i("axis", -1) != 3) miss("Softmax axis = " + std::to_string(sm.attr_i("axis", -1)) + " (only the last axis, -1 or 3, is an attention)");
+        const AttnCore c = MatchAttentionCore(sm, pv, badd->inputs[size_t(bs)], prefix);
+        if (c.rs != rs) miss("q, k and v do not come from one Reshape [N nW, L, 3, heads, hd]");
+        std::set<const OnnxNode*> skip(c.taken.begin(), c.taken.end());
+        skip.insert(c.orr);
+        skip.insert(badd);
+        auto one_reader = [&](const OnnxNode* p) {
+            for (const std::string& o : p->outputs)
+                if (gi.nreaders(o) != 1) miss("the intermediate " + o + " (" + p->op + " " + nm_of(p) + ") has " + std::to_string(gi.nreaders(o)) + " readers, not 1");
+        };
+        one_reader(badd);
+        const OnnxTensor* s6 = shape_of(gi.producer(pt->inputs[0]), 6);
+        const OnnxNode* p6 = gi.producer(pt->inputs[0]);
+        if (!s6) miss("Transpose " + nm_of(pt) + " does not read Reshape(x, [N, H/wh, wh, W/ww, ww, C]) with a constant shape");
+        if (!perm_is(pt, {0, 1, 3, 2, 4, 5})) miss("the partition Transpose " + nm_of(pt) + " does not have perm [0,1,3,2,4,5]");
+        WinMatch wm;
+        wm.nh = s6->i[1]; wm.wh = s6->i[2]; wm.nw = s6->i[3]; wm.ww = s6->i[4];
+        if (wm.nh < 1 || wm.wh < 1 || wm.nw < 1 || wm.ww < 1) miss("the partition Reshape " + nm_of(p6) + " must give the window grid and the window as positive constants");
+        const int64_t L = wm.wh * wm.ww, nW = wm.nh * wm.nw;
+        wm.heads = c.shape5[3];
+        wm.head_dim = c.shape5[4];
+        wm.scale = c.scale;
+        const OnnxTensor* s3p = shape_of(p3, 3);
+        if (!s3p || s3p->i[1] != L) miss("Reshape " + nm_of(p3) + " is not to [N nW, L, C] with L = wh ww = " + std::to_string(L));
+        if (c.shape5[1] != L && c.shape5[1] != 0 && c.shape5[1] != -1) miss("Reshape " + nm_of(rs) + " is not to [N nW, L, 3, heads, hd] with L = " + std::to_string(L));
+        if (c.shape3[1] != L && c.shape3[1] != 0 && c.shape3[1] != -1) miss("Reshape " + nm_of(c.orr) + " is not to [N nW, L, D] with L = " + std::to_string(L));
+        for (const OnnxNode* p : {p6, pt, p3}) { one_reader(p); skip.insert(p); }
+        if (qmm) { one_reader(qmm); one_reader(qadd); }
+        // the bias: a constant [1 | -, heads, L, L]
+        {
+            const OnnxTensor* b = gi.cst(badd->inputs[size_t(1 - bs)]);
+            if (!b || b->f.empty()) miss("Add " + nm_of(badd) + ": the relative-position bias must be a floating-point constant");
+            std::vector<int64_t> d = b->dims;
+            if (d.size() == 4 && d[0] == 1) d.erase(d.begin());
+            if (d.size() != 3 || d[0] != wm.heads || d[1] != L || d[2] != L)
+                miss("Add " + nm_of(badd) + ": the relative-position bias must have the shape [1, heads, L, L] = [1, " + std::to_string(wm.heads) + ", " + std::to_string(L) + ", " + std::to_string(L) + "]");
+            wm.bias = b->f;
+        }
+        if (m4) {
+            const OnnxTensor *s5m = shape_of(m5, 5), *s4m = shape_of(m4, 4);
+            if (!s5m || s5m->i[1] != nW || s5m->i[2] != wm.heads || s5m->i[3] != L || s5m->i[4] != L)
+                miss("Reshape " + nm_of(m5) + " in front of the mask is not to [N, nW, heads, L, L] with nW = " + std::to_string(nW));
+            if (!s4m || s4m->i[1] != wm.heads || s4m->i[2] != L || s4m->i[3] != L) miss("Reshape " + nm_of(m4) + " behind the mask is not to [N nW, heads, L, L]");
+            const int ms = gi.producer(madd->inputs[0]) == m5 ? 1 : 0;
+            OnnxTensor mk;
+            if (!resolve(madd->inputs[size_t(ms)], mk) || mk.f.empty())
+                miss("Add " + nm_of(madd) + ": the shift mask does not reduce to a floating-point constant");
+            std::vector<int64_t> d = mk.dims;
+            while (d.size() > 4 && d[0] == 1) d.erase(d.begin());
+            if (d.size() != 4 || d[2] != L || d[3] != L) miss("Add " + nm_of(madd) + ": the shift mask must have the shape [1, nW, 1, L, L] with L = " + std::to_string(L));
+            if (d[1] != 1) miss("Add " + nm_of(madd) + ": the shift mask must broadcast along the head axis ([1, nW, 1, L, L]), not hold " + std::to_string(d[1]) + " heads");
+            if (d[0] != nW) miss("Add " + nm_of(madd) + ": the shift mask holds " + std::to_string(d[0]) + " windows, the partition " + std::to_string(nW));
+            wm.mask = mk.f;
+            wm.masked = true;
+            for (const OnnxNode* p : {m5, madd, m4}) { one_reader(p); skip.insert(p); }
+        }
+
+        // ---- a roll: Concat(axis d) of Slice(x, [s], [max], [d]) and Slice(x, [0], [s], [d]); false: `name` is not made by a Concat of two Slices ----
+        struct Roll { std::string src; int64_t axis = 0, shift = 0; const OnnxNode *cat = nullptr, *a = nullptr, *b = nullptr; };
+        auto parse_roll = [&](const std::string& name, Roll& r) -> bool {
+            const OnnxNode* cat = gi.producer(name);
+            if (!cat || cat->op != "Concat" || cat->inputs.size() != 2) return false;
+            const OnnxNode *a = gi.producer(cat->inputs[0]), *b = gi.producer(cat->inputs[1]);
+            if (!a || !b || a->op != "Slice" || b->op != "Slice") return false;
+            auto bad = [&](const std::string& what) { miss("Concat " + nm_of(cat) + " is not a roll of the map: " + what); };
+            auto one = [&](const OnnxNode* sl, size_t k, int64_t& v) {
+                const OnnxTensor* t = sl->inputs.size() > k ? gi.cst(sl->inputs[k]) : nullptr;
+                if (!t || t->i.size() != 1) bad("Slice " + nm_of(sl) + " must have one constant start, end and axis");
+                v = t->i[0];
+            };
+            int64_t as, ae, aa, bs_, be, ba;
+            one(a, 1, as); one(a, 2, ae); one(a, 3, aa); one(b, 1, bs_); one(b, 2, be); one(b, 3, ba);
+            for (const OnnxNode* sl : {a, b})
+                if (sl->inputs.size() > 4 && !sl->inputs[4].empty()) { int64_t st; one(sl, 4, st); if (st != 1) bad("Slice " + nm_of(sl) + " has a step"); }
+            int64_t ax = cat->attr_i("axis", 0);
+            if (ax < 0) ax += 4;
+            if (aa < 0) aa += 4;
+            if (ba < 0) ba += 4;
+            if (a->inputs[0] != b->inputs[0]) bad("its two Slices read different values");
+            if (aa != ax || ba != ax) bad("the Slices' axes " + std::to_string(aa) + ", " + std::to_string(ba) + " differ from the Concat's axis " + std::to_string(ax));
+            if (ax != 1 && ax != 2) bad("only the axes 1 (H) and 2 (W) of the [N, H, W, C] map roll, not axis " + std::to_string(ax));
+            if (bs_ != 0 || be != as || as == 0 || ae < (int64_t(1) << 31) - 1) bad("its Slices must be [s:] and [:s] of one axis");
+            if (gi.nreaders(cat->inputs[0]) != 1 || gi.nreaders(cat->inputs[1]) != 1) bad("a Slice result has a second reader");
+            r.src = a->inputs[0]; r.axis = ax; r.shift = as; r.cat = cat; r.a = a; r.b = b;
+            return true;
+        };
+        // ---- above the partition: the roll, the zero Pad ----
+        int64_t fsh[3] = {0, 0, 0};
+        std::string cur = p6->inputs[0];
+        bool padded = false;
+        {
+            Roll r;
+            int need = 1;
+            for (int k = 0; k < 2 && parse_roll(cur, r); ++k) {
+                if (gi.nreaders(cur) != need) miss("the intermediate " + cur + " has " + std::to_string(gi.nreaders(cur)) + " readers, not " + std::to_string(need));
+                if (fsh[r.axis] != 0) miss("Concat " + nm_of(r.cat) + " rolls axis " + std::to_string(r.axis) + " a second time");
+                if (r.shift < 0) miss("Concat " + nm_of(r.cat) + " rolls the map forward (by " + std::to_string(-r.shift) + ") in front of the partition; torchvision rolls by -shift there");
+                fsh[r.axis] = r.shift;
+                for (const OnnxNode* p : {r.cat, r.a, r.b}) skip.insert(p);
+                cur = r.src;
+                need = 2;
+            }
+            if (const OnnxNode* pd = gi.producer(cur); pd && pd->op == "Pad") {
+                if (gi.nreaders(cur) != need) miss("the intermediate " + cur + " has " + std::to_string(gi.nreaders(cur)) + " readers, not " + std::to_string(need));
+                const OnnxTensor* pads = pd->inputs.size() > 1 ? gi.cst(pd->inputs[1]) : nullptr;
+                bool zero = pads && !pads->i.empty();
+                if (pads) for (int64_t v : pads->i) zero = zero && v == 0;
+                if (!zero) miss("Pad " + nm_of(pd) + ": a non-zero window padding is not supported (the map extents must be multiples of the window, all pads 0)");
+                skip.insert(pd);
+                padded = true;
+                cur = pd->inputs[0];
+            }
+        }
+        const std::string src = cur;
+        wm.sh = fsh[1];
+        wm.sw = fsh[2];
+        if (wm.sh >= wm.wh || wm.sw >= wm.ww)
+            miss("the shift " + std::to_string(wm.sh) + " x " + std::to_string(wm.sw) + " is not smaller than the window " + std::to_string(wm.wh) + " x " + std::to_string(wm.ww));
+        const bool rolled = wm.sh != 0 || wm.sw != 0;
+        if (rolled && !wm.masked) miss("the map is rolled (by " + std::to_string(wm.sh) + " x " + std::to_string(wm.sw) + ") but no shift mask is added to the scores");
+        if (!rolled && wm.masked) miss("a shift mask (Add " + nm_of(madd) + ") is added to the scores but the map is not rolled");
+
+        // ---- behind the attention: [the projection Linear], the reverse, the roll back, the crop of the padding ----
+        std::string tail = c.orr->outputs[0];
+        auto reader_or_miss = [&](const std::string& name, const char* what) -> const OnnxNode* {
+            const OnnxNode* r = gi.only_reader(name);
+            if (!r) miss("the intermediate " + name + " has " + std::to_string(gi.nreaders(name)) + " readers, not 1 (" + what + ")");
+            return r;
+        };
+        const OnnxNode* r6 = reader_or_miss(tail, "the attention's result");
+        if (r6->op == "MatMul" && act_side(r6) == 0) {
+            const OnnxNode* pa = reader_or_miss(r6->outputs[0], "the projection MatMul");
+            tail = r6->outputs[0];
+            if (pa->op == "Add" && act_side(pa) >= 0) { tail = pa->outputs[0]; pa = reader_or_miss(tail, "the projection's bias Add"); }
+            r6 = pa;
+        }
+        const OnnxTensor* s6r = shape_of(r6, 6);
+        if (!s6r) miss("the result " + tail + " is not read by the reverse Reshape [N, H/wh, W/ww, wh, ww, C]");
+        if (s6r->i[1] != wm.nh || s6r->i[2] != wm.nw || s6r->i[3] != wm.wh || s6r->i[4] != wm.ww)
+            miss("Reshape " + nm_of(r6) + ": the reverse has the window grid " + std::to_string(s6r->i[1]) + " x " + std::to_string(s6r->i[2]) + " and the window " +
+                 std::to_string(s6r->i[3]) + " x " + std::to_string(s6r->i[4]) + ", the partition " + std::to_string(wm.nh) + " x " + std::to_string(wm.nw) + " and " +
+                 std::to_string(wm.wh) + " x " + std::to_string(wm.ww));
+        const OnnxNode* rt = reader_or_miss(r6->outputs[0], "the reverse Reshape");
+        if (!perm_is(rt, {0, 1, 3, 2, 4, 5})) miss("the reverse " + rt->op + " " + nm_of(rt) + " is not Transpose(perm [0,1,3,2,4,5]), the partition's");
+        const OnnxNode* r4 = reader_or_miss(rt->outputs[0], "the reverse Transpose");
+        const OnnxTensor* s4r = shape_of(r4, 4);
+        if (!s4r || s4r->i[1] != wm.nh * wm.wh || s4r->i[2] != wm.nw * wm.ww) miss("the reverse does not end in Reshape [N, H, W, C] with H x W = " + std::to_string(wm.nh * wm.wh) + " x " + std::to_string(wm.nw * wm.ww));
+        const OnnxNode* last = r4;
+        int64_t bsh[3] = {0, 0, 0};
+        for (int k = 0; k < 2; ++k) {
+            const auto rd = gi.readers_of(last->outputs[0]);
+            if (rd.size() != 2 || rd[0]->op != "Slice" || rd[1]->op != "Slice" || gi.nreaders(last->outputs[0]) != 2) break;
+            const OnnxNode* cat = gi.only_reader(rd[0]->outputs[0]);
+            Roll r;
+            if (!cat || !parse_roll(cat->outputs[0], r) || r.src != last->outputs[0]) break;
+            if (bsh[r.axis] != 0) miss("Concat " + nm_of(r.cat) + " rolls axis " + std::to_string(r.axis) + " back a second time");
+            bsh[r.axis] = r.shift;
+            for (const OnnxNode* p : {r.a, r.b, last}) skip.insert(p);
+            last = r.cat;
+        }
+        for (int ax = 1; ax <= 2; ++ax)
+            if (bsh[ax] != -fsh[ax])
+                miss("the roll back does not undo the roll: axis " + std::to_string(ax) + " is rolled by " + std::to_string(-fsh[ax]) + " in front of the partition and by " +
+                     std::to_string(-bsh[ax]) + " behind the reverse");
+        if (padded) {
+            const OnnxNode* cr = reader_or_miss(last->outputs[0], "the reversed map");
+            const OnnxTensor *st = cr->op == "Slice" && cr->inputs.size() >= 4 ? gi.cst(cr->inputs[1]) : nullptr, *en = st ? gi.cst(cr->inputs[2]) : nullptr,
+                             *ax = st ? gi.cst(cr->inputs[3]) : nullptr;
+            if (!st || !en || !ax || st->i != std::vector<int64_t>{0, 0} || ax->i != std::vector<int64_t>{1, 2} || en->i.size() != 2 || en->i[0] < wm.nh * wm.wh ||
+                en->i[1] < wm.nw * wm.ww || (cr->inputs.size() > 4 && !cr->inputs[4].empty()))
+                miss("the padded map is not cropped by Slice(starts [0,0], ends [H,W], axes [1,2])");
+            skip.insert(last);
+            last = cr;
+        }
+        for (const OnnxNode* p : {r6, rt}) skip.insert(p);
+        if (last != r4) skip.insert(r4);
+        skip.erase(last);
+        skip.erase(p3);
+        wm.out = c.orr->outputs[0];
+        wm.name = nm_of(rs) + "+" + nm + "+" + nm_of(c.orr);
+        view_alias[p3] = src;
+        view_alias[last] = r6->inputs[0];
+        wattn_head[rs] = wm;
+        skip.erase(rs);
+        for (const OnnxNode* p : skip) wattn_skip.insert(p);
+    }
+}
+
+void Planner::ImportWindowAttention(const OnnxNode& on, const WinMatch& wm) {
+    auto miss = [&](const std::string& what) { fail("window attention " + wm.name + ": " + what); };
+    if (!L.is_cl(on.inputs[0])) miss("its qkv input " + on.inputs[0] + " is not a channels-last view [N, H, W, 3 D]");
+    const int x = in_val(on, 0);
+    const Val X = L.vals[x];
+    const int64_t D = wm.heads * wm.head_dim;
+    if (X.c != 3 * D) miss("the qkv rows have " + std::to_string(X.c) + " columns, not 3 * heads * hd = " + std::to_string(3 * D));
+    if (X.h % wm.wh || X.w % wm.ww)
+        miss("the map " + std::to_string(X.h) + " x " + std::to_string(X.w) + " is no multiple of the window " + std::to_string(wm.wh) + " x " + std::to_string(wm.ww) +
+             " (torchvision pads such a map; a non-zero window padding is not supported)");
+    if (X.h != wm.nh * wm.wh || X.w != wm.nw * wm.ww)
+        miss("the partition Reshape cuts a " + std::to_string(wm.nh * wm.wh) + " x " + std::to_string(wm.nw * wm.ww) + " map, the value is " + std::to_string(X.h) + " x " + std::to_string(X.w));
+    LNode n;
+    n.kind = L_WATTN;
+    n.name = wm.name;
+    n.in = {x};
+    n.heads = int(wm.heads);
+    n.head_dim = int(wm.head_dim);
+    n.attn_scale = wm.scale;
+    n.win_h = int(wm.wh); n.win_w = int(wm.ww); n.shift_h = int(wm.sh); n.shift_w = int(wm.sw);
+    n.masked = wm.masked;
+    n.w = wm.bias;
+    n.w2 = wm.mask;
+    push_node(std::move(n), wm.out, {X.n, D, X.h, X.w}, false);
+    L.cl_names.insert(wm.out);
+}
+
+// ---- patch merging: Concat(axis -1) of x[:, a::2, b::2, :] for (a, b) = (0,0), (1,0), (0,1), (1,1), each two strided Slices ----------
+void Planner::MatchPatchMerge() {
+    IndexGraph();
+    auto nm_of = [](const OnnxNode* p) { return p->name.empty() ? p->outputs[0] : p->name; };
+    // Slice(x, starts [s], ends [>= 2^31 - 1], axes [axis], steps [2])
+    auto strided = [&](const OnnxNode* sl, int64_t axis, int64_t& start) {
+        if (!sl || sl->op != "Slice" || sl->inputs.size() != 5) return false;
+        const OnnxTensor *st = gi.cst(sl->inputs[1]), *en = gi.cst(sl->inputs[2]), *ax = gi.cst(sl->inputs[3]), *sp = gi.cst(sl->inputs[4]);
+        if (!st || !en || !ax || !sp || st->i.size() != 1 || en->i.size() != 1 || ax->i.size() != 1 || sp->i.size() != 1) return false;
+        const int64_t a = ax->i[0] < 0 ? ax->i[0] + 4 : ax->i[0];
+        if (a != axis || sp->i[0] != 2 || en->i[0] < (int64_t(1) << 31) - 1) return false;
+        start = st->i[0];
+        return true;
+    };
+    for (const OnnxNode& cat : m.nodes) {
+        if (cat.op != "Concat" || cat.inputs.size() != 4) continue;
+        const int64_t axis = cat.attr_i("axis", 1);
+        if (axis != -1 && axis != 3) continue;
+        std::string src;
+        std::vector<const OnnxNode*> slices;
+        bool all = true, any = false;
+        int64_t ab[4][2];
+        for (size_t k = 0; k < 4; ++k) {
+            const OnnxNode* w = gi.producer(cat.inputs[k]);
+            const OnnxNode* h = w && w->op == "Slice" && !w->inputs.empty() ? gi.producer(w->inputs[0]) : nullptr;
+            const bool ok = strided(w, 2, ab[k][1]) && strided(h, 1, ab[k][0]) && (src.empty() || src == h->inputs[0]);
+            all = all && ok;
+            any = any || ok;
+            if (!ok) continue;
+            src = h->inputs[0];
+            slices.push_back(w);
+            slices.push_back(h);
+        }
+        if (!any) continue;
+        const std::string nm = nm_of(&cat);
+        if (!all) fail("Concat " + nm + ": a patch merging concatenates four x[:, a::2, b::2, :] slices (each Slice(axes [1], steps [2]) -> Slice(axes [2], steps [2])) of ONE map");
+        static const int64_t want[4][2] = {{0, 0}, {1, 0}, {0, 1}, {1, 1}};
+        for (size_t k = 0; k < 4; ++k)
+            if (ab[k][0] != want[k][0] || ab[k][1] != want[k][1])
+                fail("Concat " + nm + ": the slices of a patch merging must start at (0,0), (1,0), (0,1), (1,1) in this order (torchvision's x0, x1, x2, x3); operand " +
+                     std::to_string(k) + " starts at (" + std::to_string(ab[k][0]) + "," + std::to_string(ab[k][1]) + ")");
+        for (const OnnxNode* p : slices)
+            if (gi.nreaders(p->outputs[0]) != 1) fail("Concat " + nm + ": the slice " + p->outputs[0] + " of the patch merging has a second reader");
+        merge_head[&cat] = src;
+        for (const OnnxNode* p : slices) wattn_skip.insert(p);
+    }
+}
+
+void Planner::ImportPatchMerge(const OnnxNode& on, const std::string& src) {
+    const std::string nm = on.name.empty() ? on.outputs[0] : on.name;
+    if (!L.is_cl(src)) fail("Concat " + nm + ": the patch merging reads " + src + ", which is not a channels-last view [N, H, W, C]");
+    const int x = L.get_val(src);
+    const Val X = L.vals[x];
+    if (X.h % 2 || X.w % 2)
+        fail("Concat " + nm + ": patch merging of an odd map (" + std::to_string(X.h) + " x " + std::to_string(X.w) + ") is not supported (torchvision pads it: a non-zero padding)");
+    LNode n;
+    n.kind = L_PATCHMERGE;
+    n.name = nm;
+    n.in = {x};
+    push_node(std::move(n), on.outputs[0], {X.n, 4 * X.c, X.h / 2, X.w / 2}, false);
+    L.cl_names.insert(on.outputs[0]);
 }
 
 // ---- token assemble: the position-embedding Add directly behind the class-token concat, as its sole reader, folds into it ----
@@ -1630,6 +2073,8 @@ void Planner::RefuseForF8() const {
     }
     for (const LNode& n : L.nodes)
         if (n.kind == L_ATTENTION || n.kind == L_TOKASM || n.kind == L_TOKPOS) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
+    for (const LNode& n : L.nodes)
+        if (n.kind == L_WATTN || n.kind == L_PATCHMERGE) fail("window attention and patch merging are not supported in fp8 mode (node " + n.name + ")");
     for (const LNode& n : L.nodes)
         if (n.kind == L_ACT || n.kind == L_MUL || n.kind == L_ERF)
             fail("activation and squeeze-excite nodes (Sigmoid, HardSigmoid, HardSwish, Mul of two activations) are not supported in fp8 mode (node " + n.name + ")");
@@ -2612,6 +3057,43 @@ void Planner::EmitAttention(const LNode& n, Step& s) {
     s.bytes = vbytes(s.in) + vbytes(s.out);
 }
 
+// window attention: the bias and the mask packed for the kernels (kernels.h WinAttnArgs: [.][Lp][Lp], the query index fastest, -inf in the bias
+// rows of the padded keys), fp32 in every precision; tile 1 (the MFMA kernel) where kernels.h WinAttnMfmaFits says so; IE_FORCE_TILE as for attention
+void Planner::EmitWindowAttention(const LNode& n, Step& s) {
+    if (s.in.f8 || s.out.f8) fail("window attention and patch merging are not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::WindowAttention;
+    s.heads = n.heads;
+    s.head_dim = n.head_dim;
+    s.attn_scale = float(n.attn_scale);
+    s.win_h = n.win_h; s.win_w = n.win_w; s.shift_h = n.shift_h; s.shift_w = n.shift_w;
+    s.masked = n.masked;
+    const int64_t Lw = int64_t(n.win_h) * n.win_w, Lp = WinAttnPaddedTokens(Lw), nW = (s.in.h / n.win_h) * (s.in.w / n.win_w);
+    auto pack = [&](const std::vector<float>& t, int64_t count, float pad_key) {
+        std::vector<float> p(size_t(count * Lp * Lp), 0.f);
+        for (int64_t b = 0; b < count; ++b)
+            for (int64_t j = 0; j < Lp; ++j)
+                for (int64_t i = 0; i < Lp; ++i)
+                    p[size_t((b * Lp + j) * Lp + i)] = j >= Lw ? pad_key : (i >= Lw ? 0.f : t[size_t((b * Lw + i) * Lw + j)]);
+        return p;
+    };
+    if (int64_t(n.w.size()) != n.heads * Lw * Lw || (n.masked && int64_t(n.w2.size()) != nW * Lw * Lw)) fail("internal planner error: window-attention tables of node " + n.name);
+    s.w_off = push_vec(pack(n.w, n.heads, -kInf));
+    if (n.masked) s.w2_off = push_vec(pack(n.w2, nW, 0.f));
+    const bool fits = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 &&
+                      WinAttnMfmaFits(Lw, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off);
+    s.tile = fits ? 1 : 0;
+    const int t = ForcedTile(kNumWinAttnTiles);
+    if (t >= 0) s.tile = t == 0 || fits ? t : 0;
+    s.flops = 4.0 * double(s.in.n) * double(nW) * double(s.heads) * double(Lw) * double(Lw) * double(s.head_dim);
+    s.bytes = vbytes(s.in) + vbytes(s.out) + 4.0 * double(Lp * Lp) * double(n.heads + (n.masked ? nW : 0));
+}
+
+void Planner::EmitPatchMerge(const LNode& n, Step& s) const {
+    if (s.in.f8 || s.out.f8) fail("window attention and patch merging are not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::PatchMerge;
+    s.bytes = vbytes(s.in) + vbytes(s.out);
+}
+
 // ---- emit steps --------------------------------------------------------------------------------
 void Planner::EmitSteps() {
     for (int idx : order) {
@@ -2638,6 +3120,8 @@ void Planner::EmitSteps() {
             case L_LAYERNORM: EmitLayerNorm(n, s); break;
             case L_TOKASM: EmitTokenAssemble(n, s); break;
             case L_ATTENTION: EmitAttention(n, s); break;
+            case L_WATTN: EmitWindowAttention(n, s); break;
+            case L_PATCHMERGE: EmitPatchMerge(n, s); break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -2966,6 +3450,8 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
 
     // ---- ONNX graph -> logical nodes with shape inference ----
     P.ImportInputs();
+    P.MatchWindowAttention();                                    // the shifted-window attention regions of a Swin export: Linears stay, the rest is one node
+    P.MatchPatchMerge();                                         // eight strided Slices and a Concat: one node
     P.MatchAttention();                                          // the unfused attention subgraphs, found on the ONNX nodes: each imports as one node
     for (const OnnxNode& on : m.nodes) P.ImportNode(on);
     P.MarkOutputs();
@@ -3020,7 +3506,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge"};
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
@@ -3084,6 +3570,9 @@ std::string PlanToJson(const Plan& p) {
         if (s.kind == StepKind::LayerNorm) o << ",\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile;      // (layer-norm steps only)
         if (s.kind == StepKind::Attention)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"tile\":" << s.tile;      // (attention steps only)
+        if (s.kind == StepKind::WindowAttention)      // (window-attention steps only)
+            o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"window\":[" << s.win_h << "," << s.win_w << "],\"shift\":["
+              << s.shift_h << "," << s.shift_w << "],\"masked\":" << (s.masked ? "true" : "false") << ",\"tile\":" << s.tile;
         if (!s.parts.empty()) {
             Plan sub;
             sub.steps = s.parts;

@@ -38,7 +38,7 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11 };
 
 // Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
 enum class ResizeMode : int { Nearest = 0, Linear = 1 };
@@ -135,6 +135,12 @@ struct Step {
     // out[n, i, h * head_dim + e] = sum_j softmax_j(attn_scale * q_i . k_j) * v[j, e]; tile 0 = the generic kernel, 1 = the MFMA kernel
     int heads = 0, head_dim = 0;
     float attn_scale = 1.f;
+    // WindowAttention (kernels_wattn.hip): in = the qkv map [N, H, W, 3 D], out = [N, H, W, D]; attention inside the win_h x win_w windows of the map
+    // rolled by (-shift_h, -shift_w), every result on its query's own pixel; w_off = the relative-position bias, w2_off = the shift mask (masked
+    // steps only), both packed as kernels.h WinAttnArgs describes, fp32 in every precision; heads, head_dim, attn_scale, tile as for Attention
+    // PatchMerge (kernels_wattn.hip): in [N, H, W, C] -> out [N, H/2, W/2, 4 C], the four pixels of every 2 x 2 block side by side
+    int win_h = 0, win_w = 0, shift_h = 0, shift_w = 0;
+    bool masked = false;
     ConvAlgo algo = ConvAlgo::Naive;
     int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)

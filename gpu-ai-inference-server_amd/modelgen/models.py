@@ -1,5 +1,5 @@
 """Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY,
-FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT and small test graphs).
+FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT, Swin and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -955,6 +955,220 @@ def vit_b_16(batch: int | str = 1, **kw) -> bytes:
 
 def vit_tiny_16(batch: int | str = 1, **kw) -> bytes:
     return vit(batch, image=224, patch=16, dim=192, depth=12, heads=3, mlp=768, **kw)
+
+
+INT64_MAX = 9223372036854775807
+
+
+def swin_relative_position_bias(seed: int, tag: str, window: Sequence[int], heads: int) -> np.ndarray:
+    """torchvision's relative-position bias of one block, [1, heads, L, L]: a table [(2 wh - 1)(2 ww - 1), heads] gathered by the relative-position
+    index of every (query, key) pair of a window.  The table is an O(1) draw, not 0.02 N(0,1): a dropped bias must move the logits."""
+    wh, ww = window
+    L = wh * ww
+    table = rng.gaussish(seed, tag + "_rpb_table", (2 * wh - 1) * (2 * ww - 1) * heads).reshape(-1, heads)
+    coords = np.stack(np.meshgrid(np.arange(wh), np.arange(ww), indexing="ij")).reshape(2, L)
+    rel = (coords[:, :, None] - coords[:, None, :]).transpose(1, 2, 0).copy()
+    rel[:, :, 0] += wh - 1
+    rel[:, :, 1] += ww - 1
+    rel[:, :, 0] *= 2 * ww - 1
+    index = rel.sum(-1).reshape(-1)
+    return np.ascontiguousarray(table[index].reshape(L, L, heads).transpose(2, 0, 1)[None], np.float32)
+
+
+def swin_shift_mask(hw: Sequence[int], window: Sequence[int], shift: Sequence[int]) -> np.ndarray:
+    """torchvision's shift mask [nW, L, L] (0 / -100) from its three-slice region labelling of the rolled map"""
+    (H, W), (wh, ww), (sh, sw) = hw, window, shift
+    lab = np.zeros((H, W), np.float32)
+    count = 0
+    for h in ((0, -wh), (-wh, -sh), (-sh, None)):
+        for w in ((0, -ww), (-ww, -sw), (-sw, None)):
+            lab[h[0]:h[1], w[0]:w[1]] = count
+            count += 1
+    lab = lab.reshape(H // wh, wh, W // ww, ww).transpose(0, 2, 1, 3).reshape(-1, wh * ww)
+    d = lab[:, None, :] - lab[:, :, None]
+    return np.where(d != 0, np.float32(-100.0), np.float32(0.0)).astype(np.float32)
+
+
+def swin_window_attention(gb: GraphBuilder, x: str, dim: int, heads: int, hw: Sequence[int], window: Sequence[int], shift: Sequence[int],
+                          batch: int | str, tag: str, *, pad: bool = False, mask: str = "init", unbind: str = "gather", scale: str = "q",
+                          swap: bool = False, linear: bool = True, tweak: dict | None = None) -> str:
+    """torchvision's shifted_window_attention on a channels-last map x [N, H, W, dim] (linear = False: [N, H, W, 3 dim], no Linears) as the
+    TorchScript exporter lowers it: [Pad with zero pads] -> roll by -shift (per dim two Slices and a Concat) -> Reshape [N, H/wh, wh, W/ww, ww, C] ->
+    Transpose [0,1,3,2,4,5] -> Reshape [N nW, L, C] -> qkv Linear -> the attention of vit_attention with Add bias [1, heads, L, L] and, in shifted
+    blocks, Reshape [N, nW, heads, L, L] -> Add mask [1, nW, 1, L, L] -> Reshape [N nW, heads, L, L] in front of the Softmax -> proj Linear ->
+    Reshape [N, H/wh, W/ww, wh, ww, C] -> Transpose [0,1,3,2,4,5] -> Reshape [N, H, W, C] -> roll by +shift [-> the identity Slice of the padding].
+    The caller has already set a dim's shift to 0 where the window covers the map.  Batch-dependent shape entries are -1 for a symbolic batch.
+    mask: "init" ([1, nW, 1, L, L] initializer) or "unsqueeze" ([nW, L, L] behind two Unsqueeze nodes).  unbind / scale / swap: as vit_attention.
+    tweak: near misses for the tests (keys: pad_value, back_shift, back_axes, rev_window, rev_perm, bias_heads, bias_l, mask_nw, mask_l, mask_heads,
+    second_reader, mask_without_roll, roll_without_mask, reverse_roll)."""
+    tw = dict(tweak or {})
+    (H, W), (wh, ww), (sh, sw) = hw, window, shift
+    L, nW, hd = wh * ww, (H // wh) * (W // ww), dim // heads
+    sym = not isinstance(batch, int)
+    nb, nbw = (-1, -1) if sym else (batch, batch * nW)
+    cin = dim if linear else 3 * dim
+
+    def i64(name: str, v: Sequence[int]) -> str:
+        return gb.init(f"{tag}_{name}", np.array(list(v), np.int64))
+
+    def roll(y: str, sign: int, which: str, shifts: Sequence[int], axes: Sequence[int] = (1, 2)) -> str:
+        for d, s in zip(axes, shifts):
+            if s == 0:
+                continue
+            s = sign * s * (-1 if tw.get("reverse_roll") else 1)        # roll by -shift: x[s:] ++ x[:s]; roll by +shift: x[-s:] ++ x[:-s]
+            a = gb.simple("Slice", [y, i64(f"{which}{d}_s0", [s]), i64(f"{which}{d}_e0", [INT64_MAX]), i64(f"{which}{d}_a0", [d])])
+            b = gb.simple("Slice", [y, i64(f"{which}{d}_s1", [0]), i64(f"{which}{d}_e1", [s]), i64(f"{which}{d}_a1", [d])])
+            y = gb.concat([a, b], axis=d)
+        return y
+
+    def const(name: str, v: float) -> str:
+        return gb.init(f"{tag}_{name}", np.array(v, np.float32))
+
+    def mul(a: str, k: str) -> str:
+        return gb.simple("Mul", [k, a] if swap else [a, k])
+
+    shifted = (sh != 0 or sw != 0)
+    y = x
+    if pad:
+        pads = [0] * 8
+        if "pad_value" in tw:
+            pads[6] = int(tw["pad_value"])          # W's end pad
+        y = gb.simple("Pad", [y, i64("pads", pads)], [pb.attr_str("mode", "constant")])
+    if shifted and not tw.get("mask_without_roll"):
+        y = roll(y, 1, "roll", (sh, sw))
+    y = gb.simple("Reshape", [y, i64("part6", [nb, H // wh, wh, W // ww, ww, cin])])
+    y = gb.transpose(y, (0, 1, 3, 2, 4, 5))
+    y = gb.simple("Reshape", [y, i64("part3", [nbw, L, cin])])
+    if linear:
+        y = gb.linear(y, dim, 3 * dim, name=tag + "_qkv")
+    y = gb.simple("Reshape", [y, i64("shape5", [nbw, L, 3, heads, hd])])
+    y = gb.transpose(y, (2, 0, 3, 1, 4))
+    if unbind == "gather":
+        parts = []
+        for i in range(3):
+            idx = f"{tag}_i{i}"
+            gb.nodes.append(pb.node("Constant", [], [idx], idx, [pb.attr_int("value_int", i)]))
+            parts.append(gb.simple("Gather", [y, idx], [pb.attr_int("axis", 0)]))
+    elif unbind == "split":
+        name = gb._uid("split")
+        outs = [f"{name}_out{i}" for i in range(3)]
+        gb.nodes.append(pb.node("Split", [y, i64("split", [1, 1, 1])], outs, name, [pb.attr_int("axis", 0)]))
+        ax = i64("axes0", [0])
+        parts = [gb.simple("Squeeze", [o, ax]) for o in outs]
+    else:
+        raise ValueError(unbind)
+    q, k, v = parts
+    c = float(hd) ** -0.5
+    if scale == "q":
+        q = mul(q, const("scale", c))
+    elif scale == "sdpa":
+        q = mul(q, const("sqrt_scale_q", np.sqrt(c)))
+    kt = gb.transpose(k, (0, 1, 3, 2))
+    if scale == "sdpa":
+        kt = mul(kt, const("sqrt_scale_k", np.sqrt(c)))
+    s = gb.simple("MatMul", [q, kt])
+    if scale == "s_mul":
+        s = mul(s, const("scale", c))
+    elif scale == "s_div":
+        s = gb.simple("Div", [s, const("inv_scale", 1.0 / c)])
+    elif scale not in ("q", "sdpa"):
+        raise ValueError(scale)
+    bias = swin_relative_position_bias(gb.seed, tag, (wh, ww), heads)
+    if "bias_heads" in tw:
+        bias = np.ascontiguousarray(np.resize(bias, (1, tw["bias_heads"], L, L)))
+    if "bias_l" in tw:
+        bias = np.ascontiguousarray(np.resize(bias, (1, heads, L, tw["bias_l"])))
+    s = gb.simple("Add", [s, gb.init(tag + "_rpb", bias)])
+    if tw.get("second_reader"):
+        gb.simple("Relu", [s], out=tag + "_second_reader")
+    if (shifted and not tw.get("roll_without_mask")) or tw.get("mask_without_roll"):
+        mk = swin_shift_mask((H, W), (wh, ww), (sh, sw))
+        if "mask_nw" in tw:
+            mk = np.ascontiguousarray(np.resize(mk, (tw["mask_nw"], L, L)))
+        if "mask_l" in tw:
+            mk = np.ascontiguousarray(np.resize(mk, (nW, L, tw["mask_l"])))
+        s = gb.simple("Reshape", [s, i64("mask5", [nb, nW, heads, L, L])])
+        if mask == "init":
+            mk5 = mk[None, :, None]
+            if "mask_heads" in tw:
+                mk5 = np.ascontiguousarray(np.repeat(mk5, tw["mask_heads"], axis=2))
+            mname = gb.init(tag + "_mask", np.ascontiguousarray(mk5))
+        elif mask == "unsqueeze":
+            mname = gb.simple("Unsqueeze", [gb.init(tag + "_mask", mk), i64("mask_ax1", [1])])
+            mname = gb.simple("Unsqueeze", [mname, i64("mask_ax0", [0])])
+        else:
+            raise ValueError(mask)
+        s = gb.simple("Add", [s, mname])
+        s = gb.simple("Reshape", [s, i64("mask4", [nbw, heads, L, L])])
+    p = gb.simple("Softmax", [s], [pb.attr_int("axis", -1)])
+    y = gb.transpose(gb.simple("MatMul", [p, v]), (0, 2, 1, 3))
+    y = gb.simple("Reshape", [y, i64("shape3", [nbw, L, dim])])
+    if linear:
+        y = gb.linear(y, dim, dim, name=tag + "_proj")
+    rwh, rww = tw.get("rev_window", (wh, ww))
+    y = gb.simple("Reshape", [y, i64("rev6", [nb, H // rwh, W // rww, rwh, rww, dim])])
+    y = gb.transpose(y, tw.get("rev_perm", (0, 1, 3, 2, 4, 5)))
+    y = gb.simple("Reshape", [y, i64("rev4", [nb, H, W, dim])])
+    if shifted and not tw.get("mask_without_roll"):
+        y = roll(y, -1, "unroll", tw.get("back_shift", (sh, sw)), tw.get("back_axes", (1, 2)))
+    if pad:
+        y = gb.simple("Slice", [y, i64("crop_s", [0, 0]), i64("crop_e", [H, W]), i64("crop_a", [1, 2])])
+    return y
+
+
+def swin_patch_merge(gb: GraphBuilder, x: str, c: int, tag: str, reduce: bool = True) -> str:
+    """torchvision's PatchMerging (V1) on a channels-last map [N, H, W, c]: x[..., a::2, b::2, :] for (a, b) = (0,0), (1,0), (0,1), (1,1), each two
+    strided Slices -> Concat(axis -1) [N, H/2, W/2, 4c] -> LayerNorm -> Linear 4c -> 2c without a bias (reduce = False: the Concat alone)"""
+    def i64(name: str, v: Sequence[int]) -> str:
+        return gb.init(f"{tag}_{name}", np.array(list(v), np.int64))
+
+    parts = []
+    for k, (a, b) in enumerate(((0, 0), (1, 0), (0, 1), (1, 1))):
+        y = gb.simple("Slice", [x, i64(f"h{k}_s", [a]), i64(f"h{k}_e", [INT64_MAX]), i64(f"h{k}_a", [1]), i64(f"h{k}_t", [2])])
+        parts.append(gb.simple("Slice", [y, i64(f"w{k}_s", [b]), i64(f"w{k}_e", [INT64_MAX]), i64(f"w{k}_a", [2]), i64(f"w{k}_t", [2])]))
+    y = gb.concat(parts, axis=-1)
+    if not reduce:
+        return y
+    y = gb.layernorm(y, 4 * c, eps=1e-5, name=tag + "_ln")
+    w = rng.gaussish(gb.seed, tag + "_red_w", 8 * c * c).reshape(4 * c, 2 * c) * np.float32(np.sqrt(1.0 / (4 * c)))
+    return gb.simple("MatMul", [y, gb.init(tag + "_red_w", w.astype(np.float32))])
+
+
+def swin(batch: int | str = 1, *, image: int = 224, patch: int = 4, dims: Sequence[int] = (96, 192, 384, 768), depths: Sequence[int] = (2, 2, 6, 2),
+         heads: Sequence[int] = (3, 6, 12, 24), window: int = 7, classes: int = 1000, pad: bool = False, mask: str = "init", unbind: str = "gather",
+         scale: str = "q", swap: bool = False, gelu: str = "erf", seed: int = 2103, in_name: str = "input", out_name: str = "logits",
+         tweak: dict | None = None) -> bytes:
+    """The Swin Transformer V1 (Liu et al. 2021) in the graph form torchvision's swin_transformer.py gives under the TorchScript exporter's known
+    lowerings at opset 17 (written from the source: no real export was at hand): patch conv 4x4/s4 (bias) -> Transpose [0,2,3,1] -> LayerNorm; per
+    block x += proj(window attention(LayerNorm(x))) (swin_window_attention; odd blocks of a stage shifted by window // 2, a dim's shift 0 where the
+    window covers the map), x += Linear(GELU(Linear(LayerNorm(x)))) with mlp = 4 C; between the stages swin_patch_merge; LayerNorm ->
+    Transpose [0,3,1,2] -> GlobalAveragePool -> Flatten -> Gemm."""
+    gb = GraphBuilder("swin", seed)
+    c = dims[0]
+    hw = image // patch
+    x = gb.layernorm(gb.transpose(gb.conv(in_name, 3, c, patch, stride=patch, bias=True, name="patch"), (0, 2, 3, 1)), c, eps=1e-5, name="patch_ln")
+    for si, (depth, dim, nh) in enumerate(zip(depths, dims, heads)):
+        if si > 0:
+            x = swin_patch_merge(gb, x, c, f"merge{si}")
+            c, hw = dim, hw // 2
+        for bi in range(depth):
+            tag = f"s{si}b{bi}"
+            s = 0 if (bi % 2 == 0 or window >= hw) else window // 2
+            y = swin_window_attention(gb, gb.layernorm(x, c, eps=1e-5, name=tag + "_ln1"), c, nh, (hw, hw), (window, window), (s, s), batch, tag + "_attn",
+                                      pad=pad, mask=mask, unbind=unbind, scale=scale, swap=swap, tweak=tweak)
+            x = gb.simple("Add", [x, y])
+            y = gb.gelu(gb.linear(gb.layernorm(x, c, eps=1e-5, name=tag + "_ln2"), c, 4 * c, name=tag + "_fc1"), gelu)
+            x = gb.simple("Add", [x, gb.linear(y, 4 * c, c, name=tag + "_fc2", w_scale=float(np.sqrt(2.0 / (4 * c))))])
+    x = gb.transpose(gb.layernorm(x, c, eps=1e-5, name="head_ln"), (0, 3, 1, 2))
+    x = gb.simple("Flatten", [gb.gap(x)], [pb.attr_int("axis", 1)])
+    wfc = rng.gaussish(seed, "fc_w", classes * c).reshape(classes, c) * np.float32(np.sqrt(1.0 / c))
+    bfc = (rng.uniform(seed, "fc_b", classes) - np.float32(0.5)) * np.float32(0.2)
+    gb.simple("Gemm", [x, gb.init("fc_w", wfc.astype(np.float32)), gb.init("fc_b", bfc.astype(np.float32))], [pb.attr_int("transB", 1)], out=out_name)
+    return gb.finish([(in_name, [batch, 3, image, image])], [(out_name, [batch, classes])], opset=20 if gelu.startswith("op") else 17)
+
+
+def swin_t(batch: int | str = 1, **kw) -> bytes:
+    return swin(batch, image=224, dims=(96, 192, 384, 768), depths=(2, 2, 6, 2), heads=(3, 6, 12, 24), window=7, **kw)
 
 
 def write_repo(root: str, name: str, model_bytes: bytes, version: str = "1", config_json: str | None = None) -> str:

@@ -20,7 +20,9 @@ per distinct shape the launched kernel and its algorithmic GB/s (one read + one 
 For attention steps (vit_b_16, vit_tiny_16): the graph-replay time as the median of 50 single replays, the share of the eager forward per step family
 (attention, the qkv / proj / MLP convs, layer norms, GELU, token assemble), and per distinct attention shape the launched kernel
 (IE_FORCE_TILE=0 picks the generic one), its microseconds, its TFLOP/s against the sustained MFMA rate (129 TF/s fp32) and torch's
-F.scaled_dot_product_attention on the same [N, H, L, hd] operands, timed in a process of its own."""
+F.scaled_dot_product_attention on the same [N, H, L, hd] operands, timed in a process of its own.
+For window-attention steps (swin_t): the graph-replay time, the share of the eager forward per step family, and per distinct window-attention and
+patch-merge shape the launched kernel with its algorithmic TB/s next to the 3.6 TB/s that layernorm_kernel sustains."""
 import json
 import os
 import subprocess
@@ -275,6 +277,46 @@ if ats:
         ms = sorted(q["ms"] for q in ps)[len(ps) // 2]
         tf = ps[0]["flops"] / ms / 1e9
         print(f"{f'{n},{h},{l},{hd}':>20} {len(ps):5d} {kern:30} {ms * 1e3:11.1f} {tf:7.2f} {tf / mfma_tf * 100:7.1f}% {t * 1e3:13.1f}")
+wts = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "window_attention"]
+if wts:
+    import time
+    B.RunPrepared(m, 10, True)
+    ts = []
+    for _ in range(50):
+        t0 = time.perf_counter()
+        B.RunPrepared(m, 1, True)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    ms = sorted(ts)[len(ts) // 2]
+    print(json.dumps({"model": model_name, "batch": batch, "precision": plan["precision"], "replay_ms_per_step_median50": round(ms, 4),
+                      "images_per_s": round(batch / ms * 1e3, 1), "force_tile": os.environ.get("IE_FORCE_TILE")}))
+    # a block's convs by position: the one in front of the window_attention step is qkv, the three behind it proj, fc1 and fc2; the conv behind a
+    # patch_merge (and its layer norm) is the reduction; the first conv of the graph is the patch embedding, the last the head
+    kinds = [s["kind"] for s in plan["steps"]]
+    convs = [i for i, k in enumerate(kinds) if k == "conv"]
+    role = {convs[0]: "conv patch", convs[-1]: "conv head"}
+    for i, k in enumerate(kinds):
+        if k == "window_attention":
+            role[max(c for c in convs if c < i)] = "conv qkv"
+            for c, tag in zip([c for c in convs if c > i][:3], ("conv proj", "conv fc1", "conv fc2")):
+                role[c] = tag
+        if k == "patch_merge":
+            role[min(c for c in convs if c > i)] = "conv reduction"
+    fam = {}
+    for i, (p, s) in enumerate(zip(prof, plan["steps"])):
+        fam.setdefault(role.get(i, "conv other") if s["kind"] == "conv" else s["kind"], []).append(p["ms"])
+    print(f"{'family':16} {'steps':>5} {'ms':>9} {'share':>7}")
+    for key, v in sorted(fam.items(), key=lambda kv: -sum(kv[1])):
+        print(f"{key:16} {len(v):5d} {sum(v):9.4f} {sum(v) / tot * 100:6.1f}%")
+    # the step is bandwidth-bound: its roofline is its bytes at the rate layernorm_kernel sustains (3.6 TB/s)
+    seen = {}
+    for p, s in wts + [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "patch_merge"]:
+        key = (s["kind"], s["in"]["n"], s["in"]["h"], s["in"]["w"], s.get("heads", 0), tuple(s.get("shift", ())), p["kernel"])
+        seen.setdefault(key, []).append(p)
+    print(f"{'step N,HxW,heads,shift':>44} {'steps':>5} {'kernel':40} {'us (median)':>11} {'TB/s':>6} {'%3.6T':>6}")
+    for (kind, n, h, w, heads, shift, kern), ps in seen.items():
+        ms = sorted(q["ms"] for q in ps)[len(ps) // 2]
+        tbs = ps[0]["bytes"] / ms / 1e9
+        print(f"{f'{kind} {n},{h}x{w},{heads},{list(shift)}':>44} {len(ps):5d} {kern:40} {ms * 1e3:11.1f} {tbs:6.2f} {tbs / 3.6 * 100:5.1f}%")
 if dws or ses or grs:
     import time
     B.RunPrepared(m, 10, True)
