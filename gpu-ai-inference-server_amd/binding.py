@@ -25,6 +25,8 @@ LIB_PATH = os.environ.get("INFERENCE_ENGINE_LIB", os.path.join(_HERE, "lib", "li
 # enums (inference_binding.go:19-50)
 DataTypeFloat32, DataTypeInt32, DataTypeInt64, DataTypeUint8, DataTypeInt8, DataTypeString, DataTypeBool, DataTypeFp16, \
     DataTypeUnknown = range(9)
+# what an input payload of each accepted type is marshalled as (INT64: token / type ids of a text encoder)
+_PAYLOAD_DTYPE = {DataTypeFloat32: np.float32, DataTypeUint8: np.uint8, DataTypeInt64: np.int64}
 DeviceCPU, DeviceGPU = 0, 1
 ModelUnknown, ModelTensorFlow, ModelTensorRT, ModelONNX, ModelPyTorch, ModelCustom = range(6)
 
@@ -252,9 +254,9 @@ class Model:
             cout = (CTensorData * max(len(outs), 1))()
             keep = []
             for i, t in enumerate(inputs):
-                if t.DataType not in (DataTypeFloat32, DataTypeUint8):
+                if t.DataType not in _PAYLOAD_DTYPE:
                     raise RuntimeError(f"unsupported data type for input '{t.Name}'")
-                arr = np.ascontiguousarray(t.Data, dtype=np.float32 if t.DataType == DataTypeFloat32 else np.uint8).ravel()
+                arr = np.ascontiguousarray(t.Data, dtype=_PAYLOAD_DTYPE[t.DataType]).ravel()
                 nm = t.Name.encode()
                 keep.append(nm)
                 dims = list(t.Shape.Dims)
@@ -312,7 +314,9 @@ class Model:
                 cout = (CTensorData * max(len(outs), 1))()
                 keep = []
                 for i, t in enumerate(inputs):
-                    arr = np.ascontiguousarray(t.Data, dtype=np.float32 if t.DataType == DataTypeFloat32 else np.uint8).ravel()
+                    if t.DataType not in _PAYLOAD_DTYPE:
+                        raise RuntimeError(f"unsupported data type for input '{t.Name}'")
+                    arr = np.ascontiguousarray(t.Data, dtype=_PAYLOAD_DTYPE[t.DataType]).ravel()
                     nm = t.Name.encode()
                     dims = (C.c_int64 * len(t.Shape.Dims))(*t.Shape.Dims)
                     keep += [nm, dims]

@@ -225,7 +225,9 @@ bool ModelInfer(ModelHandle handle, const TensorData* inputs, int num_inputs, Te
                 for (size_t k = 0; k < gin.size(); ++k) {
                     if (gin[k].name != nm) continue;
                     // FLOAT32 as in the reference (bridge:744), plus UINT8 image bytes that the engine converts on the device
-                    if (t.data_type != DATATYPE_FLOAT32 && t.data_type != DATATYPE_UINT8) { req.err = "Unsupported data type for input: " + nm; break; }
+                    // and INT64 ids for an INT64 graph input, uploaded as they are; neither kind of input takes the other's payload
+                    const bool i64 = gin[k].elem_type == ie::ONNX_INT64;
+                    if (i64 ? t.data_type != DATATYPE_INT64 : (t.data_type != DATATYPE_FLOAT32 && t.data_type != DATATYPE_UINT8)) { req.err = "Unsupported data type for input: " + nm; break; }
                     req.in_u8[k] = t.data_type == DATATYPE_UINT8 ? 1 : 0;
                     provided[k] = 1;
                     req.shapes[k].clear();
@@ -236,6 +238,30 @@ bool ModelInfer(ModelHandle handle, const TensorData* inputs, int num_inputs, Te
             }
             for (size_t k = 0; k < gin.size() && req.err.empty(); ++k)
                 if (!provided[k]) req.err = "Required input tensor not provided: " + gin[k].name;
+            // ---- INT64 ids: the payload size against the request's own [N, L], then every id against its table, before anything is enqueued ----
+            for (size_t k = 0; k < gin.size() && req.err.empty(); ++k) {
+                if (gin[k].elem_type != ie::ONNX_INT64) continue;
+                const std::vector<int64_t>& sh = req.shapes[k];
+                if (sh.size() != 2 || sh[0] <= 0 || sh[1] <= 0) continue;          // (the planner reports a rank or dimension mismatch in its own words)
+                const size_t count = size_t(sh[0]) * size_t(sh[1]);
+                if (!req.in_ptr[k] || req.in_bytes[k] != count * sizeof(int64_t)) {
+                    req.err = "Invalid data size for input: " + gin[k].name + " Got: " + std::to_string(req.in_bytes[k]) + " bytes Expected: " + std::to_string(count * sizeof(int64_t)) +
+                              " bytes (" + std::to_string(sh[0]) + " x " + std::to_string(sh[1]) + " INT64)";
+                    break;
+                }
+                const int64_t V = k < M.id_rows.size() ? M.id_rows[k] : 0;
+                if (V < 0) continue;                                               // a key mask
+                if (V == 0) { req.err = "internal error: no embedding table was recorded for INT64 input: " + gin[k].name; break; }
+                const char* p = static_cast<const char*>(req.in_ptr[k]);
+                for (size_t q = 0; q < count; ++q) {
+                    int64_t id;
+                    std::memcpy(&id, p + q * sizeof(int64_t), sizeof(int64_t));      // (the caller's buffer need not be 8-byte aligned)
+                    if (id >= -V && id < V) continue;
+                    req.err = "Index out of range for input: " + gin[k].name + " at position [" + std::to_string(q / size_t(sh[1])) + ", " + std::to_string(q % size_t(sh[1])) + "]: value " +
+                              std::to_string(id) + " is outside the valid range [" + std::to_string(-V) + ", " + std::to_string(V - 1) + "]";
+                    break;
+                }
+            }
             // coalescing needs one common leading (batch) dimension and the declared ranks
             batched = req.err.empty() && M.batchable && M.max_batch > 1;
             if (batched) {

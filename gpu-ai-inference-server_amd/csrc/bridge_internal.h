@@ -202,6 +202,7 @@ struct ModelObj {
     WorkerPool workers;
     struct RcclInfo { bool used = false; int ranks = 0; size_t bytes = 0; double init_ms = 0, bcast_ms = 0; int owners = 1; } rccl;
     float u8_scale = 1.0f / 255.0f, u8_bias = 0.0f;
+    std::vector<int64_t> id_rows;  // per graph input: rows of the embedding table it indexes (ModelInfer checks ids against it); -1 = a key mask (nothing to check), 0 = not an INT64 input
     int64_t load_time_ns = 0;
     std::atomic<int64_t> inference_count{0}, total_ns{0}, last_ns{0};
     std::atomic<size_t> memory_usage_bytes{0};

@@ -130,7 +130,19 @@ bool ModelObj::Load() {
                     for (size_t k = 0; k < s.size(); ++k) if (s[k] <= 0) s[k] = (k == 0 ? cfg_batch : 1);
                     shapes.push_back(s);
                 }
-                primary->Prepare(shapes, true);
+                {
+                    const ie::Plan& pl = primary->Prepare(shapes, true).plan;
+                    id_rows.assign(pl.inputs.size(), 0);
+                    for (const ie::Step& st : pl.steps) {
+                        if (st.kind == ie::StepKind::Attention && st.key_mask)      // a key mask: any integer is a valid value (-1: nothing to check)
+                            for (size_t i = 0; i < pl.inputs.size(); ++i) if (pl.inputs[i].view.buf == st.in2.buf) id_rows[i] = -1;
+                        if (st.kind != ie::StepKind::Embed) continue;
+                        for (size_t i = 0; i < pl.inputs.size(); ++i) {
+                            if (pl.inputs[i].view.buf == st.in.buf) id_rows[i] = st.emb_vocab;
+                            if (st.has_in2 && pl.inputs[i].view.buf == st.in2.buf) id_rows[i] = st.emb_types;
+                        }
+                    }
+                }
                 bool symbolic_batch = !inf.inputs.empty();
                 for (auto& vi : inf.inputs) if (vi.dims.empty() || vi.dims[0] > 0) symbolic_batch = false;
                 for (auto& vi : inf.outputs) if (vi.dims.empty() || vi.dims[0] > 0) symbolic_batch = false;

@@ -73,7 +73,7 @@ std::vector<ie::IoDesc> ModelObj::RunOnLanes(const std::vector<std::vector<int64
             mine.second.resize(segs.second.size());
             for (size_t i = 0; i < segs.first.size() && i < pi.plan.inputs.size(); ++i) {
                 if (segs.first[i].empty()) continue;
-                const size_t row_bytes = size_t(pi.plan.inputs[i].view.numel() / nr) * (segs.first[i][0].u8 ? 1 : sizeof(float));
+                const size_t row_bytes = size_t(pi.plan.inputs[i].view.numel() / nr) * (segs.first[i][0].u8 ? 1 : size_t(pi.plan.inputs[i].view.esize()));
                 const size_t a = size_t(r0) * row_bytes, b = size_t(r1) * row_bytes;
                 for (const auto& sg : segs.first[i]) {
                     const size_t lo = std::max(sg.dev_off, a), hi = std::min(sg.dev_off + sg.need, b);
@@ -132,6 +132,8 @@ void ModelObj::Execute(std::vector<Pending*>& batch) {
         // elements per row of every graph input / output come from the request's own shapes (inputs) and the model (outputs are
         // sized by the plan: the segment's `need` is clipped by InferHostSegments against the planned tensor)
         auto row_elems = [](const std::vector<int64_t>& sh) { size_t n = 1; for (size_t k = 1; k < sh.size(); ++k) n *= size_t(sh[k]); return n; };
+        // bytes per element of graph input i as it is uploaded: fp32, or int64 ids (a UINT8 payload: one)
+        auto in_esize = [&](size_t i) { return info.inputs[i].elem_type == ie::ONNX_INT64 ? sizeof(int64_t) : sizeof(float); };
         if (!coalesced) {
             Pending& r = *batch[0];
             const int64_t rows = r.shapes.empty() || r.shapes[0].empty() ? 0 : r.shapes[0][0];
@@ -142,7 +144,7 @@ void ModelObj::Execute(std::vector<Pending*>& batch) {
                 // per-row sizes need the output row size: take it from the primary's plan for one row per shard ... the plan for the
                 // slice is only known inside the slice, so describe outputs by the model's declared dims instead
                 for (size_t i = 0; i < nin; ++i) {
-                    const size_t rb = row_elems(r.shapes[i]) * (r.in_u8[i] ? 1 : sizeof(float));
+                    const size_t rb = row_elems(r.shapes[i]) * (r.in_u8[i] ? 1 : in_esize(i));
                     segs.first[i].push_back({r.in_ptr[i], r.in_ptr[i] ? r.in_bytes[i] : 0, size_t(rows) * rb, 0, r.in_u8[i] != 0});
                 }
                 for (int j = 0; j < r.num_outputs && size_t(j) < nout; ++j) {
@@ -221,7 +223,7 @@ void ModelObj::Execute(std::vector<Pending*>& batch) {
         int64_t row0 = 0;
         for (auto* r : batch) {
             for (size_t k = 0; k < nin; ++k) {
-                const size_t rb = row_elems(shapes[k]) * sizeof(float);
+                const size_t rb = row_elems(shapes[k]) * in_esize(k);
                 segs.first[k].push_back({r->in_ptr[k], r->in_bytes[k], size_t(r->rows) * rb, size_t(row0) * rb});
             }
             for (int j = 0; j < r->num_outputs && size_t(j) < nout; ++j) {
@@ -231,7 +233,13 @@ void ModelObj::Execute(std::vector<Pending*>& batch) {
             }
             row0 += r->rows;
         }
-        // rows of the bucket beyond `total` stay whatever the input buffer held: they are padding whose results nobody reads
+        // rows of the bucket beyond `total` stay whatever the input buffer held: they are padding whose results nobody reads.  Integer inputs are
+        // zero-filled there (a segment without host memory): id 0 is a valid row of every table
+        for (size_t k = 0; k < nin; ++k)
+            if (info.inputs[k].elem_type == ie::ONNX_INT64 && bucket > total) {
+                const size_t rb = row_elems(shapes[k]) * in_esize(k);
+                segs.first[k].push_back({nullptr, 0, size_t(bucket - total) * rb, size_t(total) * rb});
+            }
         bool sharded = false;
         const std::vector<ie::IoDesc> outs = RunOnLanes(shapes, bucket, out_known, segs, &sharded);
         device_batches.fetch_add(1);

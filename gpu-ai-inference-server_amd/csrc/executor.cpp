@@ -74,6 +74,22 @@ LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     return a;
 }
 
+EmbedArgs MakeEmbedArgs(const PlanInstance& pi, const Step& s, const float* weights) {
+    EmbedArgs a;
+    a.ids = reinterpret_cast<const int64_t*>(make_arg(pi, s.in).p);
+    a.tids = s.has_in2 ? reinterpret_cast<const int64_t*>(make_arg(pi, s.in2).p) : nullptr;
+    a.out = make_arg(pi, s.out);
+    a.word = s.w_off >= 0 ? weights + s.w_off : nullptr;
+    a.type = s.w2_off >= 0 ? weights + s.w2_off : nullptr;
+    a.pos = s.emb_pos_off >= 0 ? weights + s.emb_pos_off : nullptr;
+    a.gamma = s.bias_off >= 0 ? weights + s.bias_off : nullptr;
+    a.beta = s.bias2_off >= 0 ? weights + s.bias2_off : nullptr;
+    a.vocab = int(s.emb_vocab);
+    a.types = int(s.emb_types);
+    a.eps = s.ln_eps;
+    return a;
+}
+
 AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s) {
     AttnArgs a;
     a.in = make_arg(pi, s.in);
@@ -81,6 +97,11 @@ AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s) {
     a.heads = s.heads;
     a.head_dim = s.head_dim;
     a.scale = s.attn_scale;
+    if (s.key_mask && s.has_in2) {
+        a.mask = reinterpret_cast<const int64_t*>(make_arg(pi, s.in2).p);
+        a.mask_sn = s.in2.pitch;
+        a.mask_value = s.mask_value;
+    }
     return a;
 }
 
@@ -465,7 +486,7 @@ void DeviceModel::AllocInstance(PlanInstance& pi) {
     for (size_t i = 0; i < pi.plan.buffer_floats.size(); ++i) {
         float* p = nullptr;
         const int dt = pi.plan.buffer_f16[i];
-        size_t bytes = size_t(std::max<int64_t>(pi.plan.buffer_floats[i], 16)) * (dt == 2 ? 1 : (dt == 1 ? 2 : 4));
+        size_t bytes = size_t(std::max<int64_t>(pi.plan.buffer_floats[i], 16)) * size_t(BufferElemBytes(dt));
         check(hipMalloc(reinterpret_cast<void**>(&p), bytes), "hipMalloc(activations)");
         check(hipMemsetAsync(p, 0, bytes, stream_), "hipMemset(activations)");
         device_bytes_ += bytes;
@@ -768,7 +789,7 @@ void DeviceModel::EnsurePipeline(PlanInstance& pi, bool allow_tune) {
     size_t head = 0;
     {
         double in_bytes = 0;
-        for (auto& d : full.inputs) in_bytes += double(d.view.numel()) * 4.0;
+        for (auto& d : full.inputs) in_bytes += double(d.view.numel()) * double(d.view.esize());
         const double t_h2d = in_bytes * double(C - 1) / double(C) / 40e9;                // pageable H2D: ~40 GB/s measured
         const double peak = precision_ == Precision::F32 ? 0.45 * 157.3e12 : 0.3 * 2.5e15;
         double total = 0;
@@ -1448,6 +1469,11 @@ const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Ste
         scratch.tile = 0;
         return scratch;
     }
+    if (s.kind == StepKind::Embed && s.tile != 0 && !EmbedEligible(MakeEmbedArgs(pi, s, w_->d_weights), s.tile)) {      // the generic kernel takes every embed
+        scratch = s;
+        scratch.tile = 0;
+        return scratch;
+    }
     if (s.kind == StepKind::Attention && s.tile != 0 && !AttentionEligible(MakeAttnArgs(pi, s), s.tile)) {      // the generic kernel takes every attention
         scratch = s;
         scratch.tile = 0;
@@ -1686,6 +1712,10 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the layer-norm kernels");
             check(LaunchLayerNorm(MakeLnArgs(pi, s, wb), s.tile, stream_), "layer_norm");
             break;
+        case StepKind::Embed:
+            if (s.out.f8 || !s.in.i64) throw std::runtime_error("internal error: the embed kernels take int64 ids and write floats or halfs");
+            check(LaunchEmbed(MakeEmbedArgs(pi, s, wb), s.tile, stream_), "embed");
+            break;
         case StepKind::TokenAssemble: {
             if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the token kernels");
             TokenAssembleArgs a;
@@ -1779,10 +1809,13 @@ static std::string kernel_label(const Step& s) {
         case StepKind::LayerNorm:
             return s.tile == 0 ? std::string("layernorm_generic_kernel")
                                : std::string("layernorm_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
+        case StepKind::Embed:
+            return s.tile == 0 ? std::string("embed_ln_generic_kernel")
+                               : std::string("embed_ln_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
         case StepKind::TokenAssemble: return std::string("token_assemble_kernel<") + (s.out.f16 ? "f16>" : "f32>");
         case StepKind::Attention:
-            return s.tile == 0 ? std::string("attention_generic_kernel")
-                               : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
+            return s.tile == 0 ? std::string(s.key_mask ? "attention_generic_kernel<mask>" : "attention_generic_kernel")
+                               : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.key_mask ? ",mask>" : ">");
         case StepKind::WindowAttention:
             return s.tile == 0 ? std::string("window_attention_generic_kernel")
                                : std::string("window_attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
@@ -2153,7 +2186,7 @@ void DeviceModel::InferHost(PlanInstance& pi, const std::vector<const void*>& in
     std::vector<std::vector<InSeg>> in(pi.plan.inputs.size());
     for (size_t i = 0; i < pi.plan.inputs.size(); ++i) {
         const bool u8 = i < in_u8.size() && in_u8[i];
-        const size_t need = size_t(pi.plan.inputs[i].view.numel()) * (u8 ? 1 : sizeof(float));
+        const size_t need = size_t(pi.plan.inputs[i].view.numel()) * (u8 ? 1 : size_t(pi.plan.inputs[i].view.esize()));
         in[i].push_back({inputs[i], inputs[i] ? std::min(in_bytes[i], need) : 0, need, 0, u8});
     }
     std::vector<std::vector<OutSeg>> out(pi.plan.outputs.size());
@@ -2193,7 +2226,8 @@ void DeviceModel::InferHostSegments(PlanInstance& pi, const std::vector<std::vec
                 }
                 base = static_cast<char*>(pi.u8_stage[i]);
             }
-            const size_t total = size_t(v.numel()) * (u8 ? 1 : sizeof(float));
+            if (u8 && v.i64) throw std::runtime_error("internal error: UINT8 payload for an INT64 input");
+            const size_t total = size_t(v.numel()) * (u8 ? 1 : size_t(v.esize()));      // (fp32 or int64: the input buffer's own element size)
             const size_t per_chunk = total / size_t(C);          // C divides the batch, so ranges are whole images
             for (const InSeg& sg : in[i]) {
                 if (sg.u8 != u8) throw std::runtime_error("internal error: mixed UINT8 / FLOAT32 segments for one input");

@@ -22,7 +22,8 @@ struct TensorArg {
 };
 
 // Fused pointwise activations (plan.h ActKind): 0 none, 1 sigmoid, 2 hardsigmoid max(0, min(1, a*x + b)), 3 silu x*sigmoid(x),
-// 4 hardswish x*hardsigmoid(x; a, b), 5 relu, 6 gelu 0.5*x*(1 + erf(x / sqrt 2)), 7 its tanh approximation 0.5*x*(1 + tanh(sqrt(2/pi)*(x + 0.044715*x^3))).
+// 4 hardswish x*hardsigmoid(x; a, b), 5 relu, 6 gelu 0.5*x*(1 + erf(x / sqrt 2)), 7 its tanh approximation 0.5*x*(1 + tanh(sqrt(2/pi)*(x + 0.044715*x^3))),
+// 8 tanh(x) (BERT's pooler).
 // fp32 math in every element type.
 // ApplyActBasic: codes 0-5 only.  The channel-block kernels whose register budget decides their occupancy (kernels_grouped.hip's fast kernel) call
 // it, so the erf / tanh code of the GELUs is not inlined into them; their eligibility keeps steps with a code above 5 on the generic kernels.
@@ -40,6 +41,7 @@ __host__ __device__ inline float ApplyAct(int kind, float a, float b, float x) {
     switch (kind) {
         case 6: return 0.5f * x * (1.f + erff(x * 0.70710678f));
         case 7: return 0.5f * x * (1.f + tanhf(0.79788456f * (x + 0.044715f * x * x * x)));
+        case 8: return tanhf(x);
         default: return ApplyActBasic(kind, a, b, x);
     }
 }
@@ -237,27 +239,67 @@ constexpr int LnDefaultTile(int64_t c, bool f16) {
 bool LayerNormEligible(const LnArgs& a, int tile);
 hipError_t LaunchLayerNorm(const LnArgs& a, int tile, hipStream_t stream);
 
+// Token embedding + LayerNormalization (kernels_embed.hip; BERT-class graphs): for every token row r = (n, l) of out [N, L, D]
+//   out[r, :] = LayerNorm(word[ids[r]] + type[tids[r]] + pos[l]; gamma, beta, eps)
+// ids / tids are the dense int64 [N, L] graph inputs; a negative index counts from the end, the wrapped index is clamped into the table.  Tables,
+// position rows, gamma and beta are fp32 in every precision; out is float or half (TensorArg::f16).  Statistics as LnArgs.
+struct EmbedArgs {
+    const int64_t* ids = nullptr;      // [N * L]
+    const int64_t* tids = nullptr;     // [N * L], or null (no second table)
+    const float* word = nullptr;       // [vocab][D]
+    const float* type = nullptr;       // [types][D] or null
+    const float* pos = nullptr;        // [L][D] or null
+    const float* gamma = nullptr;      // [D]
+    const float* beta = nullptr;       // [D] or null
+    TensorArg out;                     // out.n = N, out.w = L, out.c = D, out.h = 1
+    int vocab = 0, types = 0;
+    float eps = 1e-5f;
+};
+// tile 0: embed_ln_generic_kernel (one wave per token row; any D, pitch, offset).  tiles 1-4: embed_ln_kernel, the lane groups of the layer-norm
+// kernel (kLnLanes): D a multiple of the OUTPUT type's 16-byte vector (4 floats / 8 halfs; the fp32 table rows are then whole 16-byte vectors
+// too), the row inside the register budget (at most kLnMaxVectors vectors per lane), the output pitch and offset multiples of the vector
+constexpr int kNumEmbedTiles = kNumLnTiles;
+constexpr bool EmbedTileFits(int64_t d, bool f16_out, int64_t pitch_out, int64_t off_out, int tile) {
+    const int64_t V = f16_out ? 8 : 4;
+    return LnTileFits(d, f16_out, tile) && pitch_out % V == 0 && off_out % V == 0;
+}
+// the planner's default: the layer-norm rule (the smallest lane group that holds the row in three vectors per lane), else the generic kernel
+constexpr int EmbedDefaultTile(int64_t d, bool f16_out, int64_t pitch_out, int64_t off_out) {
+    const int t = LnDefaultTile(d, f16_out);
+    return t > 0 && EmbedTileFits(d, f16_out, pitch_out, off_out, t) ? t : 0;
+}
+bool EmbedEligible(const EmbedArgs& a, int tile);
+hipError_t LaunchEmbed(const EmbedArgs& a, int tile, hipStream_t stream);
+
 // Multi-head attention over a token view (kernels_attn.hip).  in = the qkv rows [N, L, 3 D] (in.w = L, in.c = 3 D, D = heads * head_dim): column
 // s * D + h * head_dim + e of a row is element e of head h of q / k / v for s = 0 / 1 / 2.  out[n, i, h * head_dim + e] =
 // sum_j softmax_j(scale * q[n, h, i, :] . k[n, h, j, :]) * v[n, h, j, e].  fp32 scores, statistics and accumulation; no score matrix in memory.
+// Key mask (BERT's attention_mask): mask = the int64 [N, L] graph input (row n at mask + n * mask_sn), mask_value = c; the score of key j of image n
+// gets the bias (1 - float(mask[n, j])) * c, computed in fp32 as the graph's Cast -> Sub -> Mul computes it, before the softmax.  The biased score
+// is kept finite (c = finfo(float32).min would otherwise make a fully masked row exp(-inf - -inf) = NaN): such a row gives what the graph gives.
 struct AttnArgs {
     TensorArg in, out;
     int heads = 0, head_dim = 0;
     float scale = 1.f;
+    const int64_t* mask = nullptr;     // null: no mask
+    int64_t mask_sn = 0;
+    float mask_value = 0.f;
 };
 // tile 0: attention_generic_kernel (one wave per query row; any L, head_dim, pitch, offset; float or half).  tile 1: attention_mfma_kernel<T, HD>
 // (a workgroup = one image, one head, 128 queries; the head's K and V rows in LDS): head_dim 32 or 64, the channel counts, pitches and offsets
 // multiples of the 16-byte vector, and both of the head's padded K and V images inside the LDS budget
 constexpr int kNumAttnTiles = 2;
 constexpr int64_t kAttnLdsBudget = 160 * 1024;
-// bytes of LDS the MFMA kernel needs: K and V rows, L padded to whole 32-key tiles, every row padded by one 16-byte vector
-constexpr int64_t AttnLdsBytes(int64_t L, int hd, bool f16) {
-    return 2 * ((L + 31) / 32 * 32) * (int64_t(hd) * (f16 ? 2 : 4) + 16);
+// bytes of LDS the MFMA kernel needs: K and V rows, L padded to whole 32-key tiles, every row padded by one 16-byte vector; masked: one fp32 bias
+// per padded key behind them
+constexpr int64_t AttnLdsBytes(int64_t L, int hd, bool f16, bool masked = false) {
+    return 2 * ((L + 31) / 32 * 32) * (int64_t(hd) * (f16 ? 2 : 4) + 16) + (masked ? 4 * ((L + 31) / 32 * 32) : 0);
 }
-constexpr bool AttnMfmaFits(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out) {
+constexpr bool AttnMfmaFits(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out,
+                            bool masked = false) {
     const int64_t V = f16 ? 8 : 4;
     return (hd == 32 || hd == 64) && L >= 1 && c_in % V == 0 && pitch_in % V == 0 && off_in % V == 0 && c_out % V == 0 && pitch_out % V == 0 && off_out % V == 0 &&
-           AttnLdsBytes(L, hd, f16) <= kAttnLdsBudget;
+           AttnLdsBytes(L, hd, f16, masked) <= kAttnLdsBudget;
 }
 bool AttentionEligible(const AttnArgs& a, int tile);
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);

@@ -27,6 +27,17 @@
 //          16 s + 8 (j >> 2) + 4 hf + (j & 3), and the V fragment is gathered in the same order (scripts/probes/attn_pv_order.hip checks both maps
 //          with exact integers).
 // Padded keys (j >= L) get -inf before the maximum; padded queries are computed from the last row and never stored.
+//
+// MASK (both kernels): the key mask of a BERT-class graph.  Key j of image n gets the bias (1 - float(mask[n, j])) * c on its scaled score, computed in
+// fp32 as the graph computes it.  Tile 1 stages the image's L biases in LDS behind K / V, already in units of log2 and clamped at -FLT_MAX
+// (c = finfo.min times log2 e would overflow to -inf, and a fully masked row would be exp2(-inf - -inf) = NaN), padded keys at -inf; the bias is
+// added to the fp32 scaled score before the running maximum.  -FLT_MAX + s rounds to -FLT_MAX for every real score, so a fully masked row with
+// c = min is the uniform average of V, as the graph's own fp32 (and fp64) sum gives; with c = -10000 it is the unmasked softmax.
+// A softmax does not change when one number is taken from every score of a row, and the biases of an image are the same for all of its queries: where
+// the image's largest bias is no larger in magnitude than 2^24 (kMaskShiftMax: up to there an fp32 sum keeps something of a score of order 1) it is
+// subtracted from every bias first -- exactly, for 0 / 1 masks -- so the fully masked image of c = -10000 computes its softmax on the bare scores
+// instead of on scores rounded to the 1e-3 spacing of floats near 10^4.  Beyond 2^24 (c = min) nothing is subtracted and the sum absorbs the scores,
+// as the graph's does.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -47,7 +58,11 @@ __device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
     return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
 }
 
+constexpr float kFltMax = 3.402823466e+38f;
+constexpr float kMaskShiftMax = 16777216.f;
+
 // rows = N * heads * L query rows, one wave each
+template <bool MASK>
 __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const AttnArgs a, const int64_t rows) {
     const int lane = int(threadIdx.x) % 64;
     const int64_t row = int64_t(blockIdx.x) * (kAttnBlock / 64) + threadIdx.x / 64;
@@ -59,10 +74,19 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
     const int64_t qb = n * a.in.sn + int64_t(i) * a.in.sw + int64_t(h) * hd * a.in.sc;       // q row; key row j: kb + j * sw
     const int64_t kb = n * a.in.sn + int64_t(D + h * hd) * a.in.sc, vb = kb + int64_t(D) * a.in.sc;
     const int64_t ob = n * a.out.sn + int64_t(i) * a.out.sw + int64_t(h) * hd * a.out.sc;
+    [[maybe_unused]] float shift = 0.f;            // MASK: the image's largest bias, where it is small enough to be taken out exactly
+    if constexpr (MASK) {
+        float bm = -kFltMax;
+        for (int j = lane; j < L; j += 64) bm = fmaxf(bm, (1.f - float(a.mask[n * a.mask_sn + j])) * a.mask_value);
+#pragma unroll
+        for (int x = 32; x >= 1; x >>= 1) bm = fmaxf(bm, __shfl_xor(bm, x, 64));
+        shift = fabsf(bm) <= kMaskShiftMax ? bm : 0.f;
+    }
     auto score = [&](int j) {
         float s = 0.f;
         for (int e = 0; e < hd; ++e) s = fmaf(ld_any(a.in.p, a.in.f16, qb + int64_t(e) * a.in.sc), ld_any(a.in.p, a.in.f16, kb + int64_t(j) * a.in.sw + int64_t(e) * a.in.sc), s);
-        return s * a.scale;
+        if constexpr (MASK) return fmaxf(s * a.scale + ((1.f - float(a.mask[n * a.mask_sn + j])) * a.mask_value - shift), -kFltMax);
+        else return s * a.scale;
     };
     float m = -__builtin_huge_valf();
     for (int j = lane; j < L; j += 64) m = fmaxf(m, score(j));
@@ -95,7 +119,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // grid = N * heads * qblocks workgroups (qblocks = ceil(L / 128)); dynamic LDS = AttnLdsBytes(L, HD, half)
-template <typename T, int HD>
+template <typename T, int HD, bool MASK>
 __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnArgs a, const int qblocks) {
     constexpr bool F16 = sizeof(T) == 2;
     constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
@@ -122,6 +146,11 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
         *reinterpret_cast<uint4*>(Ks + row * RS + cv * V) = kv;
         *reinterpret_cast<uint4*>(Vs + row * RS + cv * V) = vv;
     }
+    [[maybe_unused]] float* Bs = reinterpret_cast<float*>(Vs + size_t(Lp) * RS);      // MASK: the image's key biases in units of log2 (16-byte aligned: RS * sizeof(T) is)
+    if constexpr (MASK) {
+        for (int j = int(threadIdx.x); j < Lp; j += kAttnBlock)
+            Bs[j] = j < L ? fmaxf((1.f - float(a.mask[int64_t(n) * a.mask_sn + j])) * a.mask_value * kLog2e, -kFltMax) : -__builtin_huge_valf();
+    }
     __syncthreads();
 
     const int wave = int(threadIdx.x) / 64, lane = int(threadIdx.x) % 64, col = lane & 31, hf = lane >> 5;
@@ -144,6 +173,14 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
     for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
     float m = -__builtin_huge_valf(), lsum = 0.f;
     const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
+    [[maybe_unused]] float shift = 0.f;            // MASK: the image's largest bias (every wave finds it for itself), where it is small enough to be taken out exactly
+    if constexpr (MASK) {
+        float bm = -kFltMax;
+        for (int j = lane; j < L; j += 64) bm = fmaxf(bm, Bs[j]);
+#pragma unroll
+        for (int x = 32; x >= 1; x >>= 1) bm = fmaxf(bm, __shfl_xor(bm, x, 64));
+        shift = fabsf(bm) <= kMaskShiftMax * kLog2e ? bm : 0.f;
+    }
 
     for (int key0 = 0; key0 < Lp; key0 += 32) {
         f32x16 s;
@@ -169,7 +206,11 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-            s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
+            if constexpr (MASK) {
+                const float b = Bs[key];               // -inf on a padded key, else finite: the biased score of a real key stays finite
+                s[r] = b < -kFltMax ? b : fmaxf(fmaf(s[r], sl2, b - shift), -kFltMax);
+            }
+            else s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
             mx = fmaxf(mx, s[r]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -235,13 +276,13 @@ bool vec_view_ok(const TensorArg& t, int V) {
     return t.sc == 1 && t.h == 1 && t.c % V == 0 && t.sw % V == 0 && t.sn == int64_t(t.w) * t.sw && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
 }
 
-template <typename T, int HD>
+template <typename T, int HD, bool MASK>
 hipError_t launch_mfma(const AttnArgs& a, hipStream_t stream) {
     const int qblocks = (a.in.w + 127) / 128;
     const int64_t blocks = int64_t(a.in.n) * a.heads * qblocks;
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-    const size_t lds = size_t(AttnLdsBytes(a.in.w, HD, sizeof(T) == 2));
-    attention_mfma_kernel<T, HD><<<dim3(unsigned(blocks)), dim3(kAttnBlock), lds, stream>>>(a, qblocks);
+    const size_t lds = size_t(AttnLdsBytes(a.in.w, HD, sizeof(T) == 2, MASK));
+    attention_mfma_kernel<T, HD, MASK><<<dim3(unsigned(blocks)), dim3(kAttnBlock), lds, stream>>>(a, qblocks);
     return hipGetLastError();
 }
 
@@ -251,11 +292,12 @@ bool AttentionEligible(const AttnArgs& a, int tile) {
     if (tile < 0 || tile >= kNumAttnTiles || !a.in.p || !a.out.p || a.heads < 1 || a.head_dim < 1) return false;
     const int64_t D = int64_t(a.heads) * a.head_dim;
     if (a.in.f8 || a.out.f8 || a.in.c != 3 * D || a.out.c != D || a.in.n != a.out.n || a.in.h != 1 || a.out.h != 1 || a.in.w != a.out.w || a.in.w < 1) return false;
+    if (a.mask && a.mask_sn < a.in.w) return false;
     if (tile == 0) return true;
     const int V = a.out.f16 ? 8 : 4;
     // (the offsets are in the base pointers: their alignment stands for the offset condition)
     return a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) && vec_view_ok(a.out, V) &&
-           AttnMfmaFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0);
+           AttnMfmaFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr);
 }
 
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream) {
@@ -265,19 +307,26 @@ hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream) {
         const int64_t rows = int64_t(a.in.n) * a.heads * a.in.w;
         const int64_t blocks = (rows + kAttnBlock / 64 - 1) / (kAttnBlock / 64);
         if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(attention_generic_kernel, dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
+        if (a.mask) hipLaunchKernelGGL(attention_generic_kernel<true>, dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
+        else hipLaunchKernelGGL(attention_generic_kernel<false>, dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
         return hipGetLastError();
     }
-    if (a.out.f16) return a.head_dim == 64 ? launch_mfma<_Float16, 64>(a, stream) : launch_mfma<_Float16, 32>(a, stream);
-    return a.head_dim == 64 ? launch_mfma<float, 64>(a, stream) : launch_mfma<float, 32>(a, stream);
+    if (a.mask) {
+        if (a.out.f16) return a.head_dim == 64 ? launch_mfma<_Float16, 64, true>(a, stream) : launch_mfma<_Float16, 32, true>(a, stream);
+        return a.head_dim == 64 ? launch_mfma<float, 64, true>(a, stream) : launch_mfma<float, 32, true>(a, stream);
+    }
+    if (a.out.f16) return a.head_dim == 64 ? launch_mfma<_Float16, 64, false>(a, stream) : launch_mfma<_Float16, 32, false>(a, stream);
+    return a.head_dim == 64 ? launch_mfma<float, 64, false>(a, stream) : launch_mfma<float, 32, false>(a, stream);
 }
 
 hipError_t InitKernelsAttn() {
-    hipError_t e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget))) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget))) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget))) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget))) != hipSuccess) return e;
+    const void* const kernels[] = {
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, true>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, true>)};
+    for (const void* k : kernels)
+        if (const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget)); e != hipSuccess) return e;
     return hipSuccess;
 }
 

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <functional>
+#include <list>
 #include <map>
 #include <set>
 #include <sstream>
@@ -33,6 +34,7 @@ struct Val {
     int64_t n = 0, c = 0, h = 1, w = 1;
     int producer = -1;                  // LNode index, -1 = graph input
     bool is_input = false, is_output = false, input_nchw = false;
+    bool is_i64 = false;                // an INT64 graph input [N, L] (ids): its buffer holds int64, only an embed node reads it
     int parent = -1;                    // concat parent value
     int64_t parent_off = 0;
     int root = -1;
@@ -44,7 +46,7 @@ struct Val {
     int64_t sel_rows = 1, sel_idx = 0;
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -72,6 +74,11 @@ struct LNode {
     // [nW][L][L] (masked only), both as the graph's constants hold them (query row, key column); EmitWindowAttention packs them for the kernels
     int win_h = 0, win_w = 0, shift_h = 0, shift_w = 0;
     bool masked = false;
+    bool key_mask = false;              // L_ATTENTION: in[1] = the int64 key mask [N, L]; the bias of a masked key is mask_value
+    float mask_value = 0.f;
+    // L_EMBED: in = the int64 ids of the first table (and of the second); w = the first table [emb_vocab][D], w2 = the second [emb_types][D] (empty:
+    // none), bias = the position rows [L][D] (empty: none), s / t / eps = gamma / beta / epsilon of the LayerNormalization behind the sum
+    int64_t emb_vocab = 0, emb_types = 0;
     bool has_pre = false, pre_relu = false, relu = false;
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
@@ -288,6 +295,7 @@ double ActFlops(ActKind k) {
         case ActKind::Relu: return 1;
         case ActKind::Gelu: return 6;          // scale, erf, add, three multiplies
         case ActKind::GeluTanh: return 10;     // cube, fma, scale, tanh, add, three multiplies
+        case ActKind::Tanh: return 2;
         default: return 0;
     }
 }
@@ -380,7 +388,27 @@ struct Planner {
     bool tok_out = false;                  // ImportNode: the importer computed its result on a token view (the output's name is one too)
     // MatchAttention: the attention subgraphs found in the ONNX graph.  attn_head: the rank-5 Reshape of a match -> what ImportAttention needs;
     // attn_skip: the other nodes of the matches (they import nothing)
-    struct AttnMatch { int64_t heads = 0, head_dim = 0; double scale = 1.0; std::string out, name; std::vector<int64_t> shape5, shape3; };
+    struct AttnMatch {
+        int64_t heads = 0, head_dim = 0;
+        double scale = 1.0;
+        std::string out, name;
+        std::vector<int64_t> shape5, shape3;
+        // the separate q / k / v spelling (BERT): the token value the three Linears read and their merged weights [Din, 3 D] / bias [3 D] (derived initializers)
+        bool split = false;
+        std::string x, w_name, b_name;
+        // the key mask: the INT64 graph input behind the ext chain and its constant c
+        std::string mask;
+        float mask_value = 0.f;
+    };
+    // the ext chain of a key mask, matched once per name and shared by all layers: Unsqueeze(s) -> Cast FLOAT -> Sub(1, .) -> Mul(., c)
+    struct KeyMask { bool ok = false; std::string input; float c = 0.f; std::vector<const OnnxNode*> nodes; int uses = 0; };
+    std::map<std::string, KeyMask> key_masks;
+    const KeyMask& MatchKeyMask(const std::string& name);
+    std::set<const OnnxNode*> mask_nodes;          // the nodes of the matched ext chains (they import nothing; they may read an INT64 graph input)
+    std::list<OnnxNode> synth_nodes;               // nodes the planner writes itself (the merged qkv Linear of a split attention)
+    struct SplitCore;
+    bool MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const std::string& scores, const std::string& prefix, AttnMatch& am, const OnnxNode*& head,
+                             std::vector<const OnnxNode*>& taken);
     std::map<const OnnxNode*, AttnMatch> attn_head;
     std::set<const OnnxNode*> attn_skip;
     void MatchAttention();
@@ -445,6 +473,14 @@ struct Planner {
     std::map<const OnnxNode*, std::string> merge_head;
     void MatchPatchMerge();
     void ImportPatchMerge(const OnnxNode& on, const std::string& src);
+    // MatchEmbed: the token-embedding sums of a BERT-class export.  embed_head: the LayerNormalization behind a sum -> what ImportEmbed needs;
+    // embed_skip: the Gathers, Adds and position-id nodes of the sums (they import nothing)
+    struct EmbedMatch { std::vector<std::string> ids; std::vector<const OnnxTensor*> tables; std::vector<float> pos; std::string names; };
+    std::map<const OnnxNode*, EmbedMatch> embed_head;
+    std::set<const OnnxNode*> embed_skip;
+    void MatchEmbed();
+    void ImportEmbed(const OnnxNode& on, const EmbedMatch& em);
+    void EmitEmbed(const LNode& n, Step& s);
     bool FoldExpand(const OnnxNode& on, const LNode& n);
     bool ImportTokenView(const OnnxNode& on, LNode& n);
     void ImportTokenConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
@@ -547,7 +583,9 @@ void Planner::ImportInputs() {
     for (size_t i = 0; i < m.inputs.size(); ++i) {
         const auto& vi = m.inputs[i];
         const auto& got = input_shapes[i];
-        if (vi.elem_type != ONNX_FLOAT) fail("Unsupported data type for input: " + vi.name);
+        // INT64 [N, L]: token / type ids.  What may read one is MatchEmbed's business; every other non-float input is refused as before
+        const bool i64 = vi.elem_type == ONNX_INT64 && vi.dims.size() == 2;
+        if (vi.elem_type != ONNX_FLOAT && !i64) fail("Unsupported data type for input: " + vi.name);
         if (!vi.dims.empty()) {
             if (got.size() != vi.dims.size())
                 fail("Invalid rank for input: " + vi.name + " Got: " + std::to_string(got.size()) +
@@ -560,6 +598,7 @@ void Planner::ImportInputs() {
         int v = L.new_val(vi.name, got);
         L.vals[v].is_input = true;
         L.vals[v].input_nchw = (L.vals[v].h * L.vals[v].w > 1);
+        L.vals[v].is_i64 = i64;
     }
 }
 
@@ -1054,6 +1093,7 @@ void Planner::ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t
             cl_out = L.is_cl(on.inputs[0]);
             tok_out = L.is_tok(on.inputs[0]);
         }
+        else if (op == "Tanh") n.act.kind = ActKind::Tanh;
         else if (op == "Sigmoid") n.act.kind = ActKind::Sigmoid;
         else if (op == "HardSigmoid") { n.act.kind = ActKind::HardSigmoid; n.act.a = on.attr_f("alpha", 0.2f); n.act.b = on.attr_f("beta", 0.5f); }
         else { n.act.kind = ActKind::HardSwish; n.act.a = 1.f / 6.f; n.act.b = 0.5f; }
@@ -1344,6 +1384,8 @@ void Planner::ImportNode(const OnnxNode& on) {
         if (L.back_names.count(name) && op != "Reshape")
             fail(op + " " + n.name + ": input " + name + " is the [N, D, L] transpose of a token view; only a Reshape to [N, D, h, w] with h * w = L may read it");
     }
+    if (embed_skip.count(&on)) return;                     // inside a matched embedding sum: the LayerNormalization behind it imports the whole of it
+    if (const auto eh = embed_head.find(&on); eh != embed_head.end()) { ImportEmbed(on, eh->second); return; }
     if (attn_skip.count(&on)) return;                      // inside a matched attention subgraph: its head node imports the whole of it
     if (const auto am = attn_head.find(&on); am != attn_head.end()) { ImportAttention(on, am->second); return; }
     if (FoldShapeArithmetic(on, n) || FoldShapeOnlyOp(on, n) || FoldExpand(on, n) || ImportTranspose(on, n) || ImportTokenView(on, n)) return;
@@ -1354,7 +1396,7 @@ void Planner::ImportNode(const OnnxNode& on) {
     else if (op == "MatMul" || op == "Gemm") ImportGemm(on, n, odims);
     else if (op == "BatchNormalization") ImportBatchNorm(on, n, odims);
     else if (op == "LayerNormalization") ImportLayerNorm(on, n, odims);
-    else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu" || op == "Erf" || op == "Gelu") ImportActivation(on, n, odims);
+    else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu" || op == "Erf" || op == "Gelu" || op == "Tanh") ImportActivation(on, n, odims);
     else if (op == "Add" || op == "Mul" || op == "Div") ImportArithmetic(on, n, odims);
     else if (op == "Concat") ImportConcat(on, n, odims);
     else if (op == "MaxPool" || op == "AveragePool" || op == "GlobalAveragePool") ImportPool(on, n, odims);
@@ -1538,12 +1580,36 @@ void Planner::MatchAttention() {
             if (on.op == "MatMul" && on.inputs.size() == 2 && on.inputs[0] == sm.outputs[0] && !gi.cst(on.inputs[1])) pv = &on;
         if (!pv) continue;
         const OnnxNode* top = gi.producer(gi.peel_quiet(sm.inputs[0]));
-        if (top && top->op == "Add" && top->inputs.size() == 2 &&
-            (gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[0]))) || gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[1])))))
-            fail(prefix + "an additive mask (Add " + (top->name.empty() ? top->outputs[0] : top->name) + ") on the scores is not supported");
-        if (!gi.act_matmul(top)) continue;
-        const AttnCore c = MatchAttentionCore(sm, pv, sm.inputs[0], prefix);
+        std::string scores = sm.inputs[0];
         AttnMatch am;
+        const OnnxNode* mask_add = nullptr;
+        if (top && top->op == "Add" && top->inputs.size() == 2 &&
+            (gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[0]))) || gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[1]))))) {
+            // only the key mask of an INT64 graph input [N, L], broadcast as [N, 1, 1, L], directly in front of the Softmax
+            const int si = gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[0]))) ? 0 : 1;
+            const KeyMask* km = top->outputs[0] == sm.inputs[0] ? &MatchKeyMask(top->inputs[size_t(1 - si)]) : nullptr;
+            if (!km || !km->ok) fail(prefix + "an additive mask (Add " + (top->name.empty() ? top->outputs[0] : top->name) + ") on the scores is not supported");
+            am.mask = km->input;
+            am.mask_value = km->c;
+            ++key_masks[top->inputs[size_t(1 - si)]].uses;
+            mask_add = top;
+            scores = top->inputs[size_t(si)];
+            top = gi.producer(gi.peel_quiet(scores));
+        }
+        if (!gi.act_matmul(top)) continue;
+        if (mask_add && gi.nreaders(mask_add->outputs[0]) != 1) fail(prefix + "the scores " + mask_add->outputs[0] + " have " + std::to_string(gi.nreaders(mask_add->outputs[0])) + " readers, not 1");
+        if (mask_add) attn_skip.insert(mask_add);
+        {
+            const OnnxNode* head = nullptr;
+            std::vector<const OnnxNode*> taken;
+            if (MatchSplitAttention(sm, pv, scores, prefix, am, head, taken)) {
+                am.name += "+" + nm;
+                attn_head[head] = am;
+                for (const OnnxNode* p : taken) if (p != head) attn_skip.insert(p);
+                continue;
+            }
+        }
+        const AttnCore c = MatchAttentionCore(sm, pv, scores, prefix);
         am.heads = c.shape5[3];
         am.head_dim = c.shape5[4];
         am.scale = c.scale;
@@ -1555,6 +1621,161 @@ void Planner::MatchAttention() {
         for (const OnnxNode* p : c.taken) attn_skip.insert(p);
         attn_skip.insert(c.orr);
     }
+    // an ext chain is the matched attentions' alone
+    for (const auto& kv : key_masks)
+        if (kv.second.ok && kv.second.uses > 0) {
+            if (gi.nreaders(kv.first) != kv.second.uses)
+                fail("Mul " + kv.first + ": the key mask has " + std::to_string(gi.nreaders(kv.first)) + " readers, " + std::to_string(kv.second.uses) + " of them attention scores; only those may read it");
+            for (const OnnxNode* p : kv.second.nodes) { attn_skip.insert(p); mask_nodes.insert(p); }
+        }
+}
+
+// ext = Mul(Sub(1.0, Cast(Unsqueeze(Unsqueeze(mask, [1]), [2]) | Unsqueeze(mask, [1, 2]), FLOAT)), c), mask an INT64 graph input [N, L]: ok, else not a key mask
+const Planner::KeyMask& Planner::MatchKeyMask(const std::string& name) {
+    if (const auto it = key_masks.find(name); it != key_masks.end()) return it->second;
+    KeyMask& km = key_masks[name];
+    auto scalar = [&](const std::string& n, float& v) {
+        const OnnxTensor* t = gi.cst(n);
+        if (!t || t->numel() != 1 || t->f.size() != 1) return false;
+        v = t->f[0];
+        return true;
+    };
+    const OnnxNode* mul = gi.producer(name);
+    if (!mul || mul->op != "Mul" || mul->inputs.size() != 2) return km;
+    float c = 0.f, one = 0.f;
+    const int ci = scalar(mul->inputs[0], c) ? 0 : (scalar(mul->inputs[1], c) ? 1 : -1);
+    if (ci < 0) return km;
+    const OnnxNode* sb = gi.producer(mul->inputs[size_t(1 - ci)]);
+    if (!sb || sb->op != "Sub" || sb->inputs.size() != 2 || !scalar(sb->inputs[0], one) || one != 1.f || gi.nreaders(sb->outputs[0]) != 1) return km;
+    const OnnxNode* cast = gi.producer(sb->inputs[1]);
+    if (!cast || cast->op != "Cast" || cast->attr_i("to", 0) != ONNX_FLOAT || gi.nreaders(cast->outputs[0]) != 1) return km;
+    std::vector<int64_t> axes;
+    std::vector<const OnnxNode*> nodes = {mul, sb, cast};
+    std::string cur = cast->inputs[0];
+    for (int k = 0; k < 2; ++k) {
+        const OnnxNode* u = gi.producer(cur);
+        if (!u) break;
+        if (u->op != "Unsqueeze" || gi.nreaders(cur) != 1) return km;
+        std::vector<int64_t> ax = u->attr_ints("axes", {});
+        if (ax.empty() && u->inputs.size() > 1) if (const OnnxTensor* t = gi.cst(u->inputs[1])) ax = t->i;
+        axes.insert(axes.begin(), ax.begin(), ax.end());
+        nodes.push_back(u);
+        cur = u->inputs[0];
+    }
+    // [N, L] -> [N, 1, 1, L]: axes [1] then [2], or [1, 2] at once
+    if (axes != std::vector<int64_t>{1, 2}) return km;
+    bool is_input = false;
+    for (const auto& vi : m.inputs) if (vi.name == cur && vi.elem_type == ONNX_INT64 && vi.dims.size() == 2) is_input = true;
+    if (!is_input) return km;
+    km.ok = true;
+    km.input = cur;
+    km.c = c;
+    km.nodes = nodes;
+    return km;
+}
+
+// The separate q / k / v spelling (BERT's eager attention):
+//   q, k, v = Transpose(Reshape(MatMul(x, W*) + b*, [N, L, H, hd]), [0,2,1,3]);  kT = Transpose(k, [0,1,3,2]) (or the single Transpose [0,2,3,1] of the Reshape)
+//   MatMul(q, kT) [* c | / c] -> [+ mask] -> Softmax -> MatMul(., v) -> Transpose [0,2,1,3] -> Reshape [N, L, D]
+// The three Linears read the same token value and are read by their Reshape alone: they become ONE Linear x -> [N, L, 3 D] (weights and bias
+// concatenated, column s D + h hd + e), and the attention node reads today's qkv layout.  false: q is not Transpose [0,2,1,3] (the other spelling)
+bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const std::string& scores, const std::string& prefix, AttnMatch& am, const OnnxNode*& head,
+                                  std::vector<const OnnxNode*>& taken) {
+    auto miss = [&](const std::string& what) { fail(prefix + what); };
+    auto nm_of = [](const OnnxNode* p) { return p->name.empty() ? p->outputs[0] : p->name; };
+    auto perm_is = [](const OnnxNode* p, std::vector<int64_t> want) { return p && p->op == "Transpose" && p->attr_ints("perm", {}) == want; };
+    double scale = 1.0;
+    auto peel = [&](std::string cur) -> std::string {
+        for (;;) {
+            const OnnxNode* p = gi.producer(cur);
+            if (!p || (p->op != "Mul" && p->op != "Div") || p->inputs.size() != 2) return cur;
+            const OnnxTensor *c0 = gi.cst(p->inputs[0]), *c1 = gi.cst(p->inputs[1]);
+            if ((c0 != nullptr) == (c1 != nullptr) || (p->op == "Div" && !c1)) return cur;
+            const OnnxTensor* c = c0 ? c0 : c1;
+            if (c->numel() != 1 || c->f.size() != 1) miss("the scale constant of " + p->op + " " + nm_of(p) + " is not a scalar");
+            if (p->op == "Div" && c->f[0] == 0.f) miss("division by zero in " + nm_of(p));
+            scale = p->op == "Div" ? scale / double(c->f[0]) : scale * double(c->f[0]);
+            taken.push_back(p);
+            cur = p->inputs[c0 ? 1 : 0];
+        }
+    };
+    const OnnxNode* qk = gi.producer(peel(scores));
+    const OnnxNode* qt = gi.producer(gi.peel_quiet(qk->inputs[0]));
+    if (!perm_is(qt, {0, 2, 1, 3})) { taken.clear(); return false; }
+    (void)peel(qk->inputs[0]);
+    const OnnxNode* kt = gi.producer(peel(qk->inputs[1]));
+    const OnnxNode* k_rs = nullptr;
+    if (perm_is(kt, {0, 2, 3, 1})) k_rs = gi.producer(kt->inputs[0]);
+    else if (perm_is(kt, {0, 1, 3, 2}) && perm_is(gi.producer(kt->inputs[0]), {0, 2, 1, 3})) {
+        taken.push_back(gi.producer(kt->inputs[0]));
+        k_rs = gi.producer(gi.producer(kt->inputs[0])->inputs[0]);
+    } else miss("the second operand of MatMul " + nm_of(qk) + " is neither Transpose(Transpose(k, [0,2,1,3]), [0,1,3,2]) nor Transpose(k, [0,2,3,1])");
+    const OnnxNode* vt = gi.producer(pv->inputs[1]);
+    if (!perm_is(vt, {0, 2, 1, 3})) miss("the second operand of MatMul " + nm_of(pv) + " is not Transpose(v, perm [0,2,1,3])");
+    const OnnxNode* rs[3] = {gi.producer(qt->inputs[0]), k_rs, gi.producer(vt->inputs[0])};
+    static const char* const which[3] = {"q", "k", "v"};
+    const OnnxNode *mm[3], *add[3];
+    const OnnxTensor *W[3], *B[3];
+    std::vector<int64_t> shape4;
+    for (int s = 0; s < 3; ++s) {
+        const OnnxTensor* s4 = rs[s] && rs[s]->op == "Reshape" && rs[s]->inputs.size() == 2 ? gi.cst(rs[s]->inputs[1]) : nullptr;
+        if (!s4 || s4->i.size() != 4 || s4->i[2] <= 0 || s4->i[3] <= 0) miss(std::string(which[s]) + " is not Reshape(Linear(x), [N, L, H, hd]) with a constant shape");
+        if (s == 0) shape4 = s4->i;
+        else if (s4->i[2] != shape4[2] || s4->i[3] != shape4[3]) miss("the q / k / v Reshapes differ in heads or head size");
+        add[s] = gi.producer(rs[s]->inputs[0]);
+        if (!add[s] || add[s]->op != "Add" || add[s]->inputs.size() != 2) miss(std::string(which[s]) + " is not the Reshape of a Linear (MatMul + Add)");
+        const int bi = gi.cst(add[s]->inputs[0]) ? 0 : 1;
+        B[s] = gi.cst(add[s]->inputs[size_t(bi)]);
+        mm[s] = gi.producer(add[s]->inputs[size_t(1 - bi)]);
+        W[s] = mm[s] && mm[s]->op == "MatMul" && mm[s]->inputs.size() == 2 ? gi.cst(mm[s]->inputs[1]) : nullptr;
+        if (!B[s] || !W[s] || gi.cst(mm[s]->inputs[0]) || W[s]->f.empty() || B[s]->f.empty() || W[s]->dims.size() != 2)
+            miss(std::string(which[s]) + " is not the Reshape of a Linear (MatMul(x, W [Din, D]) + b [D])");
+        if (mm[s]->inputs[0] != mm[0]->inputs[0])
+            miss("the " + std::string(which[s]) + " Linear " + nm_of(mm[s]) + " reads " + mm[s]->inputs[0] + ", the q Linear " + mm[0]->inputs[0] + " (q, k and v must come from the same tokens)");
+        const int64_t D = shape4[2] * shape4[3];
+        if (W[s]->dims != W[0]->dims || W[s]->dims[1] != D || B[s]->numel() != D)
+            miss("the " + std::string(which[s]) + " Linear " + nm_of(mm[s]) + " is not [Din, H * hd = " + std::to_string(D) + "] with a bias [" + std::to_string(D) + "] like the q Linear");
+        for (const OnnxNode* p : {mm[s], add[s], rs[s]})
+            if (gi.nreaders(p->outputs[0]) != 1) miss("the " + std::string(which[s]) + " Linear's " + p->op + " " + nm_of(p) + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1 (only its own attention may read it)");
+        taken.insert(taken.end(), {mm[s], add[s], rs[s]});
+    }
+    const int64_t axis = sm.attr_i("axis", -1);
+    if (axis != -1 && axis != 3) miss("Softmax axis = " + std::to_string(axis) + " (only the last axis, -1 or 3, is an attention)");
+    const OnnxNode* ot = gi.only_reader(pv->outputs[0]);
+    if (!perm_is(ot, {0, 2, 1, 3})) miss("the result of MatMul " + nm_of(pv) + " is not read by Transpose(perm [0,2,1,3]) alone");
+    const OnnxNode* orr = gi.only_reader(ot->outputs[0]);
+    const OnnxTensor* s3 = orr && orr->op == "Reshape" && orr->inputs.size() == 2 ? gi.cst(orr->inputs[1]) : nullptr;
+    if (!s3 || s3->i.size() != 3) miss("the transposed result is not read by Reshape(., [N, L, D]) alone");
+    for (const OnnxNode* p : {qk, qt, kt, vt, pv, ot, &sm})
+        if (gi.nreaders(p->outputs[0]) != 1) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
+    for (const OnnxNode* p : taken)
+        if ((p->op == "Mul" || p->op == "Div" || p->op == "Transpose") && gi.nreaders(p->outputs[0]) != 1) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
+    taken.insert(taken.end(), {qk, qt, kt, vt, pv, ot, orr, &sm});
+    // the merged Linear: column s D + h hd + e
+    const int64_t Din = W[0]->dims[0], D = W[0]->dims[1];
+    OnnxTensor w, b;
+    w.dtype = b.dtype = ONNX_FLOAT;
+    w.dims = {Din, 3 * D};
+    b.dims = {3 * D};
+    w.f.resize(size_t(Din * 3 * D));
+    for (int64_t k = 0; k < Din; ++k)
+        for (int s = 0; s < 3; ++s) std::copy(W[s]->f.begin() + k * D, W[s]->f.begin() + (k + 1) * D, w.f.begin() + k * 3 * D + s * D);
+    for (int s = 0; s < 3; ++s) b.f.insert(b.f.end(), B[s]->f.begin(), B[s]->f.end());
+    // the head: the first of the three MatMuls in graph order (x is defined there)
+    for (const OnnxNode& on : m.nodes) if (&on == mm[0] || &on == mm[1] || &on == mm[2]) { head = &on; break; }
+    am.split = true;
+    am.x = mm[0]->inputs[0];
+    am.name = nm_of(mm[0]) + "+" + nm_of(mm[1]) + "+" + nm_of(mm[2]);
+    am.w_name = w.name = am.name + "/qkv_w";
+    am.b_name = b.name = am.name + "/qkv_b";
+    L.add_derived(std::move(w));
+    L.add_derived(std::move(b));
+    am.heads = shape4[2];
+    am.head_dim = shape4[3];
+    am.scale = scale;
+    am.out = orr->outputs[0];
+    am.shape3 = s3->i;
+    return true;
 }
 
 // `scores`: the name the scaled q k^T product reaches the Softmax (or, in a window attention, the bias Add) under
@@ -1657,12 +1878,31 @@ Planner::AttnCore Planner::MatchAttentionCore(const OnnxNode& sm, const OnnxNode
 
 void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     auto miss = [&](const std::string& what) { fail("attention " + am.name + ": " + what); };
-    if (!L.is_tok(on.inputs[0])) miss("its qkv input " + on.inputs[0] + " is not a token view [N, L, 3 D]");
-    const int x = in_val(on, 0);
+    std::string qkv = on.inputs[0];
+    if (am.split) {
+        // the merged Linear as two nodes of the planner's own, imported like any Linear on tokens (a 1x1 conv; the bias folds into it)
+        if (!L.is_tok(am.x)) miss("the input " + am.x + " of its q / k / v Linears is not a token view [N, L, D]");
+        OnnxNode mm, add;
+        mm.op = "MatMul";
+        mm.name = am.name + "/qkv";
+        mm.inputs = {am.x, am.w_name};
+        mm.outputs = {am.name + "/qkv_mm"};
+        add.op = "Add";
+        add.name = am.name + "/qkv_bias";
+        add.inputs = {mm.outputs[0], am.b_name};
+        add.outputs = {am.name + "/qkv_out"};
+        qkv = add.outputs[0];
+        synth_nodes.push_back(std::move(mm));
+        ImportNode(synth_nodes.back());
+        synth_nodes.push_back(std::move(add));
+        ImportNode(synth_nodes.back());
+    }
+    if (!L.is_tok(qkv)) miss("its qkv input " + qkv + " is not a token view [N, L, 3 D]");
+    const int x = L.get_val(qkv);
     const Val X = L.vals[x];
     const int64_t D = am.heads * am.head_dim;
     if (X.c != 3 * D) miss("the qkv rows have " + std::to_string(X.c) + " columns, not 3 * H * hd = " + std::to_string(3 * D));
-    if ((am.shape5[0] != 0 && am.shape5[0] != X.n) || (am.shape5[1] != -1 && am.shape5[1] != 0 && am.shape5[1] != X.w)) miss("the Reshape to [N, L, 3, H, hd] does not keep N and L");
+    if (!am.split && ((am.shape5[0] != 0 && am.shape5[0] != X.n) || (am.shape5[1] != -1 && am.shape5[1] != 0 && am.shape5[1] != X.w))) miss("the Reshape to [N, L, 3, H, hd] does not keep N and L");
     if ((am.shape3[0] != 0 && am.shape3[0] != X.n) || (am.shape3[1] != -1 && am.shape3[1] != 0 && am.shape3[1] != X.w) || (am.shape3[2] != -1 && am.shape3[2] != D))
         miss("the last Reshape is not to [N, L, H * hd]");
     if (am.shape3[1] == -1 && am.shape3[2] == -1) miss("the last Reshape is not to [N, L, H * hd]");
@@ -1673,6 +1913,14 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     n.heads = int(am.heads);
     n.head_dim = int(am.head_dim);
     n.attn_scale = am.scale;
+    if (!am.mask.empty()) {
+        const int mv = L.get_val(am.mask);
+        if (L.vals[mv].n != X.n || L.vals[mv].c != X.w)
+            miss("the key mask " + am.mask + " is [" + std::to_string(L.vals[mv].n) + ", " + std::to_string(L.vals[mv].c) + "], the tokens [" + std::to_string(X.n) + ", " + std::to_string(X.w) + ", .]");
+        n.in.push_back(mv);
+        n.key_mask = true;
+        n.mask_value = am.mask_value;
+    }
     push_node(std::move(n), am.out, {X.n, D, 1, X.w}, true);
 }
 
@@ -2035,6 +2283,190 @@ void Planner::ImportPatchMerge(const OnnxNode& on, const std::string& src) {
 }
 
 // ---- token assemble: the position-embedding Add directly behind the class-token concat, as its sole reader, folds into it ----
+// ---- token embeddings: table Gathers by INT64 graph inputs, their sum and the LayerNormalization behind it as ONE node ----------------------
+// Matched on the ONNX nodes, before the import (no Val ever holds an integer activation or a [N, L, D] sum of gathers):
+//   e = Gather(word [V, D], ids, axis 0) [+ Gather(type [T, D], type_ids, axis 0)] [+ pos]  ->  LayerNormalization(e, axis -1)
+// ids / type_ids INT64 graph inputs [N, L]; pos a floating-point constant [1, L, D] / [L, D], or Gather(table [P, D], position ids) with the ids a
+// constant or a Slice of one (how exporters write BERT's position embedding); the Adds in any order, every partial sum read by the next node only.
+// A near miss is refused naming what did not match.  Graphs without an INT64 [N, L] input are not looked at.
+void Planner::MatchEmbed() {
+    std::vector<std::string> id_inputs;
+    for (const auto& vi : m.inputs) if (vi.elem_type == ONNX_INT64 && vi.dims.size() == 2) id_inputs.push_back(vi.name);
+    if (id_inputs.empty()) return;
+    IndexGraph();
+    auto input_index = [&](const std::string& name) {
+        for (size_t k = 0; k < id_inputs.size(); ++k) if (id_inputs[k] == name) return int(k);
+        return -1;
+    };
+    auto float_const = [&](const std::string& name) -> const OnnxTensor* {
+        const OnnxTensor* t = gi.cst(name);
+        return t && !t->f.empty() && (t->dtype == ONNX_FLOAT || t->dtype == ONNX_DOUBLE || t->dtype == ONNX_FLOAT16) ? t : nullptr;
+    };
+    // Gather(floating-point constant, an activation): an embedding lookup, which must be the supported one
+    auto table_gather = [&](const OnnxNode& g) {
+        if (g.op != "Gather" || g.inputs.size() != 2 || !float_const(g.inputs[0]) || gi.cst(g.inputs[1])) return false;
+        if (const OnnxNode* sl = gi.producer(g.inputs[1]); sl && sl->op == "Slice" && !sl->inputs.empty() && gi.cst(sl->inputs[0])) return false;      // constant position ids
+        const std::string nm = g.name.empty() ? g.outputs[0] : g.name;
+        if (input_index(g.inputs[1]) < 0)
+            fail("Gather " + nm + ": the indices " + g.inputs[1] + " of an embedding table are not an INT64 graph input [N, L] (only a graph input may index a table)");
+        const OnnxTensor* t = float_const(g.inputs[0]);
+        if (t->dims.size() != 2)
+            fail("Gather " + nm + ": the embedding table " + g.inputs[0] + " must be a 2-D floating-point initializer [V, D] (it has rank " + std::to_string(t->dims.size()) + ")");
+        if (g.attr_i("axis", 0) != 0) fail("Gather " + nm + ": an embedding table is gathered along axis 0 (axis = " + std::to_string(g.attr_i("axis", 0)) + ")");
+        return true;
+    };
+    auto ints_const = [&](const std::string& name, std::vector<int64_t>& out) {
+        const OnnxTensor* t = name.empty() ? nullptr : gi.cst(name);
+        if (!t || t->i.empty()) return false;
+        out = t->i;
+        return true;
+    };
+    for (const OnnxNode& g : m.nodes) {
+        if (embed_skip.count(&g) || !table_gather(g)) continue;
+        const std::string gname = g.name.empty() ? g.outputs[0] : g.name;
+        // down to the LayerNormalization: Adds only, every value read once
+        std::string cur = g.outputs[0];
+        const OnnxNode* ln = nullptr;
+        for (;;) {
+            const OnnxNode* r = gi.only_reader(cur);
+            if (!r) fail("Gather " + gname + ": " + cur + " has " + std::to_string(gi.nreaders(cur)) + " readers; the sum of the embedding gathers is read by its LayerNormalization alone, every partial sum by the next Add alone");
+            if (r->op == "Add") { cur = r->outputs[0]; continue; }
+            if (r->op == "LayerNormalization" && r->inputs[0] == cur) { ln = r; break; }
+            fail(r->op + " " + (r->name.empty() ? r->outputs[0] : r->name) + ": reads the embedding sum " + cur + "; only Adds and then a LayerNormalization may (the embedding and its LayerNormalization run as one step)");
+        }
+        if (embed_head.count(ln)) continue;
+        const std::string lname = ln->name.empty() ? ln->outputs[0] : ln->name;
+        EmbedMatch em;
+        std::vector<const OnnxNode*> gathers, taken;
+        int pos_count = 0;
+        int64_t Lq = 0;
+        for (size_t i = 0; i < m.inputs.size(); ++i) if (m.inputs[i].name == g.inputs[1]) Lq = input_shapes[i].size() == 2 ? input_shapes[i][1] : 0;
+        auto add_pos = [&](const std::vector<float>& f, const std::vector<int64_t>& dims, const std::string& what) {
+            const bool ok = (dims.size() == 3 && dims[0] == 1 && dims[1] == Lq) || (dims.size() == 2 && dims[0] == Lq);
+            if (!ok || f.empty()) fail("LayerNormalization " + lname + ": " + what + " of the embedding sum must be a floating-point constant [1, L, D] or [L, D] with L = " + std::to_string(Lq));
+            if (++pos_count > 1) fail("LayerNormalization " + lname + ": the embedding sum has more than one constant operand (" + what + ")");
+            em.pos = f;
+        };
+        std::function<void(const std::string&)> walk = [&](const std::string& name) {
+            const OnnxNode* p = gi.producer(name);
+            if (p && p->op == "Add" && p->inputs.size() == 2 && !(gi.cst(p->inputs[0]) && gi.cst(p->inputs[1]))) {
+                if (gi.nreaders(name) != 1)
+                    fail("Add " + (p->name.empty() ? name : p->name) + ": the embedding sum " + name + " has a second reader in front of its LayerNormalization");
+                taken.push_back(p);
+                walk(p->inputs[0]);
+                walk(p->inputs[1]);
+                return;
+            }
+            if (const OnnxTensor* c = gi.cst(name)) {
+                if (!float_const(name)) fail("LayerNormalization " + lname + ": the constant " + name + " of the embedding sum is not floating-point");
+                add_pos(c->f, c->dims, "the constant " + name);
+                return;
+            }
+            if (p && table_gather(*p)) {
+                if (gi.nreaders(name) != 1) fail("Gather " + (p->name.empty() ? name : p->name) + ": " + name + " has " + std::to_string(gi.nreaders(name)) + " readers; an embedding gather is read by its sum alone");
+                gathers.push_back(p);
+                return;
+            }
+            // the position embedding as exporters write it: Gather(table [P, D], position ids), the ids a constant or a Slice (step 1, last axis) of one
+            if (p && p->op == "Gather" && p->inputs.size() == 2 && float_const(p->inputs[0]) && p->attr_i("axis", 0) == 0 && gi.nreaders(name) == 1) {
+                const OnnxTensor* tab = float_const(p->inputs[0]);
+                std::vector<int64_t> ix;
+                const OnnxNode* sl = gi.producer(p->inputs[1]);
+                bool ok = tab->dims.size() == 2 && ints_const(p->inputs[1], ix);
+                if (!ok && tab->dims.size() == 2 && sl && sl->op == "Slice" && sl->inputs.size() >= 3 && gi.nreaders(p->inputs[1]) == 1) {
+                    std::vector<int64_t> src, st, en, ax = {0}, stp = {1};
+                    const OnnxTensor* srct = gi.cst(sl->inputs[0]);
+                    ok = srct && ints_const(sl->inputs[0], src) && ints_const(sl->inputs[1], st) && ints_const(sl->inputs[2], en) && st.size() == 1 && en.size() == 1;
+                    if (ok && sl->inputs.size() > 3 && !sl->inputs[3].empty()) ok = ints_const(sl->inputs[3], ax) && ax.size() == 1;
+                    if (ok && sl->inputs.size() > 4 && !sl->inputs[4].empty()) ok = ints_const(sl->inputs[4], stp) && stp.size() == 1;
+                    if (ok) {
+                        const int64_t rank = int64_t(srct->dims.size()), P = int64_t(src.size());
+                        const int64_t axis = ax[0] < 0 ? ax[0] + rank : ax[0];
+                        ok = rank >= 1 && rank <= 2 && axis == rank - 1 && srct->dims[size_t(rank - 1)] == P && stp[0] == 1;
+                        if (ok) {
+                            const int64_t b = std::clamp<int64_t>(st[0] < 0 ? st[0] + P : st[0], 0, P), e = std::clamp<int64_t>(en[0] < 0 ? en[0] + P : en[0], b, P);
+                            ix.assign(src.begin() + b, src.begin() + e);
+                            taken.push_back(sl);
+                        }
+                    }
+                }
+                if (ok && int64_t(ix.size()) == Lq) {
+                    const int64_t P = tab->dims[0], D = tab->dims[1];
+                    std::vector<float> f(size_t(Lq * D));
+                    for (int64_t l = 0; l < Lq; ++l) {
+                        const int64_t r = ix[size_t(l)] < 0 ? ix[size_t(l)] + P : ix[size_t(l)];
+                        if (r < 0 || r >= P) fail("Gather " + (p->name.empty() ? name : p->name) + ": position id " + std::to_string(ix[size_t(l)]) + " is outside the table of " + std::to_string(P) + " rows");
+                        std::copy(tab->f.begin() + r * D, tab->f.begin() + (r + 1) * D, f.begin() + l * D);
+                    }
+                    taken.push_back(p);
+                    add_pos(f, {Lq, D}, "the position Gather " + (p->name.empty() ? name : p->name));
+                    return;
+                }
+            }
+            fail("LayerNormalization " + lname + ": the operand " + name + " of the embedding sum is neither the Gather of a table [V, D] by an INT64 graph input nor a constant [1, L, D] "
+                 "(nor the Gather of a table by constant position ids)");
+        };
+        walk(ln->inputs[0]);
+        if (gathers.empty() || gathers.size() > 2)
+            fail("LayerNormalization " + lname + ": the embedding sum has " + std::to_string(gathers.size()) + " table Gathers by graph inputs (one or two are supported)");
+        std::sort(gathers.begin(), gathers.end(), [&](const OnnxNode* a, const OnnxNode* b) { return input_index(a->inputs[1]) < input_index(b->inputs[1]); });
+        if (gathers.size() == 2 && gathers[0]->inputs[1] == gathers[1]->inputs[1])
+            fail("LayerNormalization " + lname + ": both table Gathers of the embedding sum read " + gathers[0]->inputs[1] + " (two different INT64 graph inputs are expected)");
+        for (const OnnxNode* t : gathers) {
+            const OnnxTensor* tab = float_const(t->inputs[0]);
+            if (tab->dims[1] != float_const(gathers[0]->inputs[0])->dims[1] || (pos_count && int64_t(em.pos.size()) != Lq * tab->dims[1]))
+                fail("LayerNormalization " + lname + ": the tables and the position rows of the embedding sum differ in width");
+            em.ids.push_back(t->inputs[1]);
+            em.tables.push_back(tab);
+            em.names += (em.names.empty() ? "" : "+") + (t->name.empty() ? t->outputs[0] : t->name);
+            embed_skip.insert(t);
+        }
+        for (const OnnxNode* t : taken) embed_skip.insert(t);
+        embed_head[ln] = std::move(em);
+    }
+    // whatever else reads an id input is refused by name
+    for (const std::string& in : id_inputs) {
+        for (const auto& vo : m.outputs) if (vo.name == in) fail("graph output " + in + " is an INT64 graph input; only the Gather of an embedding table may read one");
+        for (const OnnxNode* r : gi.readers_of(in))
+            if (mask_nodes.count(r)) continue;             // the key mask of the attentions (MatchAttention took its chain)
+            else if (!embed_skip.count(r) || r->op != "Gather")
+                fail(r->op + " " + (r->name.empty() ? r->outputs[0] : r->name) + ": reads the INT64 graph input " + in + "; only the Gather (axis 0) of a floating-point embedding table [V, D] may read one");
+    }
+}
+
+void Planner::ImportEmbed(const OnnxNode& on, const EmbedMatch& em) {
+    LNode n;
+    n.kind = L_EMBED;
+    n.name = on.name.empty() ? on.outputs[0] : on.name;
+    for (const std::string& id : em.ids) n.in.push_back(L.get_val(id));
+    const Val& I = L.vals[n.in[0]];
+    for (int v : n.in)
+        if (L.vals[v].dims != I.dims) fail("LayerNormalization " + n.name + ": the id inputs of the embedding sum differ in shape");
+    const int64_t N = I.n, Lq = I.c, D = em.tables[0]->dims[1];
+    const int64_t axis = on.attr_i("axis", -1);
+    if (axis != -1 && axis != 2) fail("LayerNormalization " + n.name + ": axis = " + std::to_string(axis) + " on a token view is not supported (only the channel axis alone is normalised: the last axis of a channels-last view or of an [N, C] value)");
+    if (on.attr_i("stash_type", 1) != 1) fail("LayerNormalization " + n.name + ": stash_type = " + std::to_string(on.attr_i("stash_type", 1)) + " is not supported (1 is)");
+    for (size_t k = 1; k < on.outputs.size(); ++k)
+        if (!on.outputs[k].empty()) fail("LayerNormalization " + n.name + ": the Mean / InvStdDev outputs are not supported");
+    const OnnxTensor* g = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
+    if (!g || g->dims.size() != 1 || g->numel() != D) fail("LayerNormalization " + n.name + ": scale must be a [C] initializer");
+    n.s = g->f;
+    if (on.inputs.size() > 2 && !on.inputs[2].empty()) {
+        const OnnxTensor* b = L.init(on.inputs[2]);
+        if (!b || b->dims.size() != 1 || b->numel() != D) fail("LayerNormalization " + n.name + ": B must be a [C] initializer");
+        n.t = b->f;
+    }
+    n.eps = on.attr_f("epsilon", 1e-5f);
+    n.w = em.tables[0]->f;
+    n.emb_vocab = em.tables[0]->dims[0];
+    if (em.tables.size() > 1) { n.w2 = em.tables[1]->f; n.emb_types = em.tables[1]->dims[0]; }
+    n.bias = em.pos;
+    if (n.emb_vocab < 1 || n.emb_vocab >= (int64_t(1) << 31) || n.emb_types >= (int64_t(1) << 31) || D < 1 || D >= (int64_t(1) << 31))
+        fail("LayerNormalization " + n.name + ": embedding table sizes out of range");
+    n.name = em.names + "+" + n.name;
+    push_node(std::move(n), on.outputs[0], {N, D, 1, Lq}, true);
+}
+
 void Planner::FuseTokenAssemble() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& a = L.nodes[i];
@@ -2069,7 +2501,7 @@ void Planner::RefuseForF8() const {
         if (n.kind == L_CONV && n.group != 1) fail("grouped convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_CONV && (n.dil_h > 1 || n.dil_w > 1)) fail("dilated convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_RESIZE) fail("Resize is not supported in fp8 mode (node " + n.name + ")");
-        if (n.kind == L_LAYERNORM) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
+        if (n.kind == L_LAYERNORM || n.kind == L_EMBED) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
     }
     for (const LNode& n : L.nodes)
         if (n.kind == L_ATTENTION || n.kind == L_TOKASM || n.kind == L_TOKPOS) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
@@ -2586,7 +3018,7 @@ void Planner::MarkBufferTypes() {
         for (size_t v = 0; v < L.vals.size(); ++v)
             if (used[v] && L.vals[v].root == int(v) && L.vals[v].buf >= 0 && L.vals[v].h * L.vals[v].w == 1) plan.buffer_f16[size_t(L.vals[v].buf)] = 1;
     for (size_t v = 0; v < L.vals.size(); ++v)
-        if (L.vals[v].is_input && L.vals[L.vals[v].root].buf >= 0) plan.buffer_f16[size_t(L.vals[L.vals[v].root].buf)] = 0;
+        if (L.vals[v].is_input && L.vals[L.vals[v].root].buf >= 0) plan.buffer_f16[size_t(L.vals[L.vals[v].root].buf)] = L.vals[v].is_i64 ? 3 : 0;
     for (int v : out_vals)
         if (L.vals[L.vals[v].root].buf >= 0) plan.buffer_f16[size_t(L.vals[L.vals[v].root].buf)] = 0;
 }
@@ -2598,6 +3030,7 @@ View Planner::view_of(int v) const {
     w.buf = R.buf;
     w.f16 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 1;
     w.f8 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 2;
+    w.i64 = R.buf >= 0 && plan.buffer_f16[size_t(R.buf)] == 3;
     w.n = X.n; w.c = X.c; w.h = X.h; w.w = X.w;
     w.c_off = X.abs_off + X.sel_idx * R.c;
     w.pitch = R.c * X.sel_rows;
@@ -3031,6 +3464,29 @@ void Planner::EmitLayerNorm(const LNode& n, Step& s) {
     s.bytes = vbytes(s.in) + vbytes(s.out);
 }
 
+// embed: the tables, the position rows, gamma and beta fp32 in the blob (in that order); the tile as for layer norm, by kernels.h EmbedTileFits
+void Planner::EmitEmbed(const LNode& n, Step& s) {
+    if (s.out.f8) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::Embed;
+    if (n.in.size() > 1) { s.in2 = view_of(n.in[1]); s.has_in2 = true; }
+    if (!s.in.i64 || (s.has_in2 && !s.in2.i64) || s.out.nchw) fail("internal planner error: embed views of node " + n.name);
+    s.emb_vocab = n.emb_vocab;
+    s.emb_types = n.emb_types;
+    s.w_off = push_vec(n.w);
+    if (!n.w2.empty()) s.w2_off = push_vec(n.w2);
+    if (!n.bias.empty()) s.emb_pos_off = push_vec(n.bias);
+    s.bias_off = push_vec(n.s);
+    if (!n.t.empty()) s.bias2_off = push_vec(n.t);
+    s.ln_eps = n.eps;
+    s.tile = EmbedDefaultTile(s.out.c, s.out.f16, s.out.pitch, s.out.c_off);
+    const int t = ForcedTile(kNumEmbedTiles);
+    if (t >= 0) s.tile = t == 0 || EmbedTileFits(s.out.c, s.out.f16, s.out.pitch, s.out.c_off, t) ? t : 0;
+    const double rows = double(s.out.n) * double(s.out.w), D = double(s.out.c);
+    s.flops = 8.0 * rows * D;
+    // per token row: one fp32 row of every table and of the position rows, the ids, the result once
+    s.bytes = rows * (4.0 * D * double(1 + (s.has_in2 ? 1 : 0) + (s.emb_pos_off >= 0 ? 1 : 0)) + 8.0 * double(s.has_in2 ? 2 : 1)) + vbytes(s.out);
+}
+
 // token assemble: the class token at w_off, the position embedding at bias_off (fp32 in every precision)
 void Planner::EmitTokenAssemble(const LNode& n, Step& s) {
     if (s.in.f8 || s.out.f8) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
@@ -3048,13 +3504,20 @@ void Planner::EmitAttention(const LNode& n, Step& s) {
     s.heads = n.heads;
     s.head_dim = n.head_dim;
     s.attn_scale = float(n.attn_scale);
+    if (n.key_mask) {
+        s.in2 = view_of(n.in[1]);
+        s.has_in2 = true;
+        s.key_mask = true;
+        s.mask_value = n.mask_value;
+        if (!s.in2.i64) fail("internal planner error: the key mask of node " + n.name + " is not an int64 view");
+    }
     const bool fits = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 &&
-                      AttnMfmaFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off);
+                      AttnMfmaFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask);
     s.tile = fits ? 1 : 0;
     const int t = ForcedTile(kNumAttnTiles);
     if (t >= 0) s.tile = t == 0 || fits ? t : 0;
     s.flops = 4.0 * double(s.in.n) * double(s.heads) * double(s.in.w) * double(s.in.w) * double(s.head_dim);
-    s.bytes = vbytes(s.in) + vbytes(s.out);
+    s.bytes = vbytes(s.in) + vbytes(s.out) + (n.key_mask ? vbytes(s.in2) : 0.0);
 }
 
 // window attention: the bias and the mask packed for the kernels (kernels.h WinAttnArgs: [.][Lp][Lp], the query index fastest, -inf in the bias
@@ -3122,6 +3585,7 @@ void Planner::EmitSteps() {
             case L_ATTENTION: EmitAttention(n, s); break;
             case L_WATTN: EmitWindowAttention(n, s); break;
             case L_PATCHMERGE: EmitPatchMerge(n, s); break;
+            case L_EMBED: EmitEmbed(n, s); break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -3421,7 +3885,7 @@ void Planner::DescribeIo() {
         int v = L.get_val(d.name);
         if (!used[size_t(L.vals[v].root)]) {   // input never consumed: still give it a staging buffer
             plan.buffer_floats.push_back(root_floats(v));
-            plan.buffer_f16.push_back(0);
+            plan.buffer_f16.push_back(L.vals[v].is_i64 ? 3 : 0);
             L.vals[v].buf = int(plan.buffer_floats.size()) - 1;
         }
         d.view = view_of(v);
@@ -3453,6 +3917,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
     P.MatchWindowAttention();                                    // the shifted-window attention regions of a Swin export: Linears stay, the rest is one node
     P.MatchPatchMerge();                                         // eight strided Slices and a Concat: one node
     P.MatchAttention();                                          // the unfused attention subgraphs, found on the ONNX nodes: each imports as one node
+    P.MatchEmbed();                                              // table Gathers by INT64 graph inputs, their sum and the LayerNormalization behind it: one node
     for (const OnnxNode& on : m.nodes) P.ImportNode(on);
     P.MarkOutputs();
     if (f8) P.RefuseForF8();
@@ -3493,10 +3958,12 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
 static void json_view(std::ostringstream& o, const View& v) {
     o << "{\"buf\":" << v.buf << ",\"n\":" << v.n << ",\"c\":" << v.c << ",\"h\":" << v.h << ",\"w\":" << v.w
       << ",\"c_off\":" << v.c_off << ",\"pitch\":" << v.pitch << ",\"nchw\":" << (v.nchw ? "true" : "false")
-      << ",\"f16\":" << (v.f16 ? "true" : "false") << ",\"f8\":" << (v.f8 ? "true" : "false") << "}";
+      << ",\"f16\":" << (v.f16 ? "true" : "false") << ",\"f8\":" << (v.f8 ? "true" : "false");
+    if (v.i64) o << ",\"i64\":true";      // (int64 id inputs only: other plans are unchanged)
+    o << "}";
 }
 static void json_act(std::ostringstream& o, const char* key, const Act& a) {
-    static const char* names[] = {"none", "sigmoid", "hardsigmoid", "silu", "hardswish", "relu", "gelu", "gelu_tanh"};
+    static const char* names[] = {"none", "sigmoid", "hardsigmoid", "silu", "hardswish", "relu", "gelu", "gelu_tanh", "tanh"};
     o << ",\"" << key << "\":[\"" << names[int(a.kind)] << "\"," << a.a << "," << a.b << "]";
 }
 static std::string json_escape(const std::string& s) {
@@ -3506,7 +3973,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed"};
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
@@ -3570,9 +4037,16 @@ std::string PlanToJson(const Plan& p) {
         if (s.kind == StepKind::LayerNorm) o << ",\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile;      // (layer-norm steps only)
         if (s.kind == StepKind::Attention)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"tile\":" << s.tile;      // (attention steps only)
+        if (s.kind == StepKind::Attention && s.key_mask) o << ",\"key_mask\":true,\"mask_value\":" << s.mask_value;      // (masked attention steps only)
         if (s.kind == StepKind::WindowAttention)      // (window-attention steps only)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"window\":[" << s.win_h << "," << s.win_w << "],\"shift\":["
               << s.shift_h << "," << s.shift_w << "],\"masked\":" << (s.masked ? "true" : "false") << ",\"tile\":" << s.tile;
+        if (s.kind == StepKind::Embed) {      // (embed steps only)
+            o << ",\"tables\":" << (s.w2_off >= 0 ? 2 : 1) << ",\"vocab\":[" << s.emb_vocab;
+            if (s.w2_off >= 0) o << "," << s.emb_types;
+            o << "],\"ln\":true,\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile << ",\"w2_off\":" << s.w2_off << ",\"pos_off\":" << s.emb_pos_off
+              << ",\"bias2_off\":" << s.bias2_off;
+        }
         if (!s.parts.empty()) {
             Plan sub;
             sub.steps = s.parts;

@@ -26,8 +26,9 @@ struct View {
     bool nchw = false;    // dense NCHW (pitch/c_off unused)
     bool f16 = false;     // elements are IEEE halfs (fp16 precision mode: every buffer that is not a graph input/output)
     bool f8 = false;      // elements are OCP e4m3 bytes with one per-tensor scale (fp8 precision mode: spatial tensors between stem and global pool)
+    bool i64 = false;     // elements are int64 (an INT64 graph input [N, L]: token / type ids; only an embed step reads one)
     int64_t numel() const { return n * c * h * w; }
-    int esize() const { return f8 ? 1 : (f16 ? 2 : 4); }
+    int esize() const { return i64 ? 8 : (f8 ? 1 : (f16 ? 2 : 4)); }
 };
 
 // Storage/compute precision of a plan.  F16: activations between the graph's fp32 inputs and outputs are stored as halfs and
@@ -38,7 +39,7 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12 };
 
 // Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
 enum class ResizeMode : int { Nearest = 0, Linear = 1 };
@@ -49,7 +50,7 @@ enum class ResizeNearest : int { RoundPreferFloor = 0, RoundPreferCeil = 1, Floo
 // hardswish(x) = x * hardsigmoid(x; a, b) (the ONNX HardSwish op: a = 1/6, b = 1/2).  Relu only as a squeeze-excite block's inner activation.
 // gelu(x) = 0.5 * x * (1 + erf(x / sqrt 2)) (the ONNX Gelu op, or the five-node Erf pattern exporters write below opset 20); GeluTanh its tanh
 // approximation (Gelu with approximate = "tanh").
-enum class ActKind : int { None = 0, Sigmoid = 1, HardSigmoid = 2, Silu = 3, HardSwish = 4, Relu = 5, Gelu = 6, GeluTanh = 7 };
+enum class ActKind : int { None = 0, Sigmoid = 1, HardSigmoid = 2, Silu = 3, HardSwish = 4, Relu = 5, Gelu = 6, GeluTanh = 7, Tanh = 8 };
 struct Act {
     ActKind kind = ActKind::None;
     float a = 0.f, b = 0.f;
@@ -135,12 +136,19 @@ struct Step {
     // out[n, i, h * head_dim + e] = sum_j softmax_j(attn_scale * q_i . k_j) * v[j, e]; tile 0 = the generic kernel, 1 = the MFMA kernel
     int heads = 0, head_dim = 0;
     float attn_scale = 1.f;
+    // Attention with a key mask (BERT): in2 (has_in2) = the int64 mask [N, L] graph input; key j of image n gets the bias (1 - mask[n, j]) * mask_value
+    bool key_mask = false;
+    float mask_value = 0.f;
     // WindowAttention (kernels_wattn.hip): in = the qkv map [N, H, W, 3 D], out = [N, H, W, D]; attention inside the win_h x win_w windows of the map
     // rolled by (-shift_h, -shift_w), every result on its query's own pixel; w_off = the relative-position bias, w2_off = the shift mask (masked
     // steps only), both packed as kernels.h WinAttnArgs describes, fp32 in every precision; heads, head_dim, attn_scale, tile as for Attention
     // PatchMerge (kernels_wattn.hip): in [N, H, W, C] -> out [N, H/2, W/2, 4 C], the four pixels of every 2 x 2 block side by side
     int win_h = 0, win_w = 0, shift_h = 0, shift_w = 0;
     bool masked = false;
+    // Embed (kernels_embed.hip): in = the int64 ids [N, L] of the first table, in2 (has_in2) = the ids of the second; out = tokens [N, 1, L, D] =
+    // LayerNorm(word[in] + type[in2] + pos[l]; gamma, beta, ln_eps); w_off = the first table [emb_vocab][D], w2_off = the second [emb_types][D] or -1,
+    // emb_pos_off = the position rows [L][D] or -1, bias_off = gamma [D], bias2_off = beta [D] or -1, fp32 in every precision; tile as for LayerNorm
+    int64_t emb_vocab = 0, emb_types = 0, emb_pos_off = -1;
     ConvAlgo algo = ConvAlgo::Naive;
     int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)
@@ -164,11 +172,14 @@ struct IoDesc {
     View view;                         // device staging view (dense NCHW order as the ABI expects)
 };
 
+// bytes per element of a Plan::buffer_f16 code
+inline int BufferElemBytes(int code) { return code == 3 ? 8 : (code == 2 ? 1 : (code == 1 ? 2 : 4)); }
+
 struct Plan {
     std::vector<IoDesc> inputs, outputs;
     Precision precision = Precision::F32;
     std::vector<int64_t> buffer_floats;   // size of each device activation buffer in ELEMENTS
-    std::vector<char> buffer_f16;         // element type of each buffer: 0 = float, 1 = half, 2 = e4m3 byte
+    std::vector<char> buffer_f16;         // element type of each buffer: 0 = float, 1 = half, 2 = e4m3 byte, 3 = int64
     std::vector<Step> steps;
     std::vector<float> weights;           // packed blob (batch independent)
     int64_t workspace_floats = 0;         // split-K partial-sum slabs (max over steps of splitk*M*Cout)
@@ -176,7 +187,7 @@ struct Plan {
     int64_t activation_floats() const { int64_t s = 0; for (auto b : buffer_floats) s += b; return s; }
     int64_t activation_bytes() const {
         int64_t s = 0;
-        for (size_t i = 0; i < buffer_floats.size(); ++i) s += buffer_floats[i] * (buffer_f16[i] == 2 ? 1 : (buffer_f16[i] ? 2 : 4));
+        for (size_t i = 0; i < buffer_floats.size(); ++i) s += buffer_floats[i] * BufferElemBytes(buffer_f16[i]);
         return s;
     }
 };

@@ -1,5 +1,5 @@
 """Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY,
-FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT, Swin and small test graphs).
+FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT, Swin, BERT and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -289,10 +289,10 @@ class GraphBuilder:
         self.nodes.append(pb.node(op, xs, [y], name, attrs))
         return y
 
-    def finish(self, inputs: Sequence[tuple[str, Sequence[int | str]]],
-               outputs: Sequence[tuple[str, Sequence[int | str]]], opset: int = 11) -> bytes:
+    def finish(self, inputs: Sequence[tuple], outputs: Sequence[tuple], opset: int = 11) -> bytes:
+        """inputs / outputs: (name, shape) or (name, shape, ONNX element type); FLOAT where it is not given"""
         g = pb.graph(self.name, self.nodes, self.inits,
-                     [pb.value_info(n, s) for n, s in inputs], [pb.value_info(n, s) for n, s in outputs])
+                     [pb.value_info(*t) for t in inputs], [pb.value_info(*t) for t in outputs])
         return pb.model(g, opset=opset)
 
 
@@ -955,6 +955,130 @@ def vit_b_16(batch: int | str = 1, **kw) -> bytes:
 
 def vit_tiny_16(batch: int | str = 1, **kw) -> bytes:
     return vit(batch, image=224, patch=16, dim=192, depth=12, heads=3, mlp=768, **kw)
+
+
+ONNX_INT64 = pb.INT64
+FLOAT32_MIN = float(np.finfo(np.float32).min)
+
+
+def bert_embeddings(gb: GraphBuilder, seq: int, vocab: int, dim: int, *, types: int = 2, max_pos: int = 512, pos: str | None = "const",
+                    order: str = "wtp", eps: float = 1e-12, ids: str = "input_ids", type_ids: str = "token_type_ids", table_std: float = 1.0,
+                    table_mean: float = 0.0) -> str:
+    """BertEmbeddings as the exporter writes it: Gather(word [vocab, dim], ids) + Gather(type [types, dim], type_ids) + pos -> LayerNormalization.
+    types = 0: no type table.  pos: "const" (the [1, seq, dim] rows as a constant), "gather" (Gather(position table [max_pos, dim],
+    Slice(position_ids [1, max_pos], 0 : seq, axis 1))) or None.  order: which sum comes first, "wtp" (word + type) + pos, "wpt" (word + pos) + type,
+    "ptw" pos + (type + word).  The tables are O(1) draws (table_mean + table_std * N(0,1)), not BERT's 0.02 N(0,1), at which dropping one of them
+    would move the logits by less than a test's tolerance."""
+    seed = gb.seed
+
+    def table(name: str, rows: int) -> str:
+        t = np.float32(table_mean) + np.float32(table_std) * rng.gaussish(seed, name, rows * dim).reshape(rows, dim)
+        return gb.init(name, t.astype(np.float32))
+
+    w = gb.simple("Gather", [table("word_embeddings", vocab), ids], [pb.attr_int("axis", 0)])
+    t = gb.simple("Gather", [table("token_type_embeddings", types), type_ids], [pb.attr_int("axis", 0)]) if types else None
+    p = None
+    if pos == "const":
+        rows = np.float32(table_mean) + np.float32(table_std) * rng.gaussish(seed, "position_embeddings", max_pos * dim).reshape(max_pos, dim)[:seq]
+        p = gb.init("position_rows", rows.reshape(1, seq, dim).astype(np.float32))
+    elif pos == "gather":
+        pid = gb.init("position_ids", np.arange(max_pos, dtype=np.int64).reshape(1, max_pos))
+        i64 = lambda name, v: gb.init(name, np.array(v, np.int64))  # noqa: E731
+        sl = gb.simple("Slice", [pid, i64("pos_starts", [0]), i64("pos_ends", [seq]), i64("pos_axes", [1]), i64("pos_steps", [1])])
+        p = gb.simple("Gather", [table("position_embeddings", max_pos), sl], [pb.attr_int("axis", 0)])
+    elif pos is not None:
+        raise ValueError(pos)
+    parts = {"w": w, "t": t, "p": p}
+    terms = [parts[k] for k in order if parts[k] is not None]
+    if order == "ptw" and len(terms) == 3:
+        x = gb.simple("Add", [terms[0], gb.simple("Add", [terms[1], terms[2]])])
+    else:
+        x = terms[0]
+        for y in terms[1:]:
+            x = gb.simple("Add", [x, y])
+    return gb.layernorm(x, dim, eps=eps, name="emb_ln")
+
+
+def bert_attention(gb: GraphBuilder, x: str, ext: str | None, dim: int, heads: int, tag: str, *, ktrans: str = "two", scale: str = "div",
+                   mask_swap: bool = False, linear=None) -> str:
+    """BertSelfAttention (eager): three Linears -> Reshape [N, L, H, hd] -> Transpose [0,2,1,3] (k: then [0,1,3,2] for ktrans "two", or the single
+    [0,2,3,1] for "one") -> MatMul -> Div(sqrt hd) | Mul(1 / sqrt hd) -> Add(ext) (mask_swap: ext first) -> Softmax -> MatMul(., v) -> Transpose
+    [0,2,1,3] -> Reshape [N, L, dim]"""
+    hd = dim // heads
+    shp = gb.init(tag + "_shape4", np.array([0, -1, heads, hd], np.int64))
+    linear = linear or (lambda y, name: gb.linear(y, dim, dim, name=name))      # (tests pass Linears of their own)
+    q, k, v = (gb.simple("Reshape", [linear(x, f"{tag}_{n}"), shp]) for n in ("query", "key", "value"))
+    q, v = gb.transpose(q, (0, 2, 1, 3)), gb.transpose(v, (0, 2, 1, 3))
+    kt = gb.transpose(gb.transpose(k, (0, 2, 1, 3)), (0, 1, 3, 2)) if ktrans == "two" else gb.transpose(k, (0, 2, 3, 1))
+    s = gb.simple("MatMul", [q, kt])
+    if scale == "div":
+        s = gb.simple("Div", [s, gb.init(tag + "_sqrt_hd", np.array(np.sqrt(float(hd)), np.float32))])
+    elif scale == "mul":
+        s = gb.simple("Mul", [s, gb.init(tag + "_rsqrt_hd", np.array(1.0 / np.sqrt(float(hd)), np.float32))])
+    else:
+        raise ValueError(scale)
+    if ext is not None:
+        s = gb.simple("Add", [ext, s] if mask_swap else [s, ext])
+    p = gb.simple("Softmax", [s], [pb.attr_int("axis", -1)])
+    y = gb.transpose(gb.simple("MatMul", [p, v]), (0, 2, 1, 3))
+    return gb.simple("Reshape", [y, gb.init(tag + "_shape3", np.array([0, -1, dim], np.int64))])
+
+
+def bert_extended_mask(gb: GraphBuilder, mask: str = "attention_mask", *, mask_value: str | float = "min", unsqueeze: str = "two") -> str:
+    """get_extended_attention_mask: Unsqueeze [1] -> Unsqueeze [2] (or one Unsqueeze [1, 2]) -> Cast FLOAT -> Sub(1.0, .) -> Mul(., c) = [N, 1, 1, L];
+    c = finfo(float32).min ("min") or a float such as -10000.0"""
+    c = FLOAT32_MIN if mask_value == "min" else float(mask_value)
+    ax = lambda name, v: gb.init(name, np.array(v, np.int64))  # noqa: E731
+    if unsqueeze == "two":
+        m = gb.simple("Unsqueeze", [gb.simple("Unsqueeze", [mask, ax("mask_ax1", [1])]), ax("mask_ax2", [2])])
+    elif unsqueeze == "one":
+        m = gb.simple("Unsqueeze", [mask, ax("mask_ax12", [1, 2])])
+    else:
+        raise ValueError(unsqueeze)
+    m = gb.simple("Cast", [m], [pb.attr_int("to", pb.FLOAT)])
+    m = gb.simple("Sub", [gb.init("mask_one", np.array(1.0, np.float32)), m])
+    return gb.simple("Mul", [m, gb.init("mask_value", np.array(c, np.float32))])
+
+
+def bert(batch: int | str = 1, *, seq: int = 128, vocab: int = 30522, dim: int = 768, depth: int = 12, heads: int = 12, mlp: int = 3072,
+         types: int = 2, max_pos: int = 512, classes: int = 2, mask_value: str | float = "min", eps: float = 1e-12, seed: int = 2018,
+         pos: str | None = "const", order: str = "wtp", unsqueeze: str = "two", ktrans: str = "two", scale: str = "div", mask_swap: bool = False,
+         mask: bool = True, pooler_output: bool = False, table_std: float = 1.0) -> bytes:
+    """BertForSequenceClassification (post-LN encoder, Devlin et al. 2019) written from modeling_bert.py's eager attention and the TorchScript
+    exporter's known lowerings at opset 17, as Swin's graph was: neither `transformers` nor ONNX Runtime is available to export or to run one, so the
+    graph is this restatement, checked by two independent float64 evaluations (tests/bert_ref.py, tests/test_bert_plan.py).
+    inputs input_ids, attention_mask, token_type_ids [N, seq] INT64; outputs logits [N, classes] and optionally pooler_output [N, dim]."""
+    gb = GraphBuilder("bert", seed)
+    x = bert_embeddings(gb, seq, vocab, dim, types=types, max_pos=max_pos, pos=pos, order=order, eps=eps, table_std=table_std)
+    ext = bert_extended_mask(gb, mask_value=mask_value, unsqueeze=unsqueeze) if mask else None
+    for li in range(depth):
+        tag = f"l{li}"
+        y = bert_attention(gb, x, ext, dim, heads, tag + "_attn", ktrans=ktrans, scale=scale, mask_swap=mask_swap)
+        x = gb.layernorm(gb.simple("Add", [gb.linear(y, dim, dim, name=tag + "_out"), x]), dim, eps=eps, name=tag + "_ln1")
+        y = gb.gelu(gb.linear(x, dim, mlp, name=tag + "_fc1"), "erf")
+        x = gb.layernorm(gb.simple("Add", [gb.linear(y, mlp, dim, name=tag + "_fc2", w_scale=float(np.sqrt(2.0 / mlp))), x]), dim, eps=eps, name=tag + "_ln2")
+    gb.nodes.append(pb.node("Constant", [], ["pool_i0"], "pool_i0", [pb.attr_int("value_int", 0)]))
+    x = gb.simple("Gather", [x, "pool_i0"], [pb.attr_int("axis", 1)])
+
+    def gemm(y: str, name: str, cin: int, cout: int, out: str | None = None) -> str:
+        w = rng.gaussish(seed, name + "_w", cout * cin).reshape(cout, cin) * np.float32(np.sqrt(1.0 / cin))
+        b = (rng.uniform(seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
+        return gb.simple("Gemm", [y, gb.init(name + "_w", w.astype(np.float32)), gb.init(name + "_b", b.astype(np.float32))], [pb.attr_int("transB", 1)], out=out)
+
+    pooled = gb.simple("Tanh", [gemm(x, "pooler", dim, dim)], out="pooler_output" if pooler_output else None)
+    gemm(pooled, "classifier", dim, classes, out="logits")
+    ins = [("input_ids", [batch, seq], ONNX_INT64)] + ([("attention_mask", [batch, seq], ONNX_INT64)] if mask else []) + \
+          ([("token_type_ids", [batch, seq], ONNX_INT64)] if types else [])
+    outs = [("logits", [batch, classes])] + ([("pooler_output", [batch, dim])] if pooler_output else [])
+    return gb.finish(ins, outs, opset=17)
+
+
+def bert_base(batch: int | str = 1, **kw) -> bytes:
+    return bert(batch, **dict(dict(seq=128, vocab=30522, dim=768, depth=12, heads=12, mlp=3072), **kw))
+
+
+def bert_tiny(batch: int | str = 1, **kw) -> bytes:
+    return bert(batch, **dict(dict(seq=128, vocab=30522, dim=128, depth=2, heads=2, mlp=512), **kw))
 
 
 INT64_MAX = 9223372036854775807
