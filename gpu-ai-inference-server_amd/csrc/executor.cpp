@@ -74,6 +74,20 @@ LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     return a;
 }
 
+GnArgs MakeGnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
+    GnArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    a.gamma = s.w_off >= 0 ? weights + s.w_off : nullptr;
+    a.beta = s.bias_off >= 0 ? weights + s.bias_off : nullptr;
+    a.groups = s.gn_groups;
+    a.eps = s.ln_eps;
+    a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
+    a.workspace = pi.workspace;
+    a.workspace_floats = pi.workspace_floats;
+    return a;
+}
+
 EmbedArgs MakeEmbedArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     EmbedArgs a;
     a.ids = reinterpret_cast<const int64_t*>(make_arg(pi, s.in).p);
@@ -1469,6 +1483,11 @@ const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Ste
         scratch.tile = 0;
         return scratch;
     }
+    if (s.kind == StepKind::GroupNorm && s.tile != 0 && !GroupNormEligible(MakeGnArgs(pi, s, w_->d_weights), s.tile)) {      // the generic kernel takes every group norm
+        scratch = s;
+        scratch.tile = 0;
+        return scratch;
+    }
     if (s.kind == StepKind::Embed && s.tile != 0 && !EmbedEligible(MakeEmbedArgs(pi, s, w_->d_weights), s.tile)) {      // the generic kernel takes every embed
         scratch = s;
         scratch.tile = 0;
@@ -1712,6 +1731,10 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the layer-norm kernels");
             check(LaunchLayerNorm(MakeLnArgs(pi, s, wb), s.tile, stream_), "layer_norm");
             break;
+        case StepKind::GroupNorm:
+            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the group-norm kernels");
+            check(LaunchGroupNorm(MakeGnArgs(pi, s, wb), s.tile, stream_), "group_norm");
+            break;
         case StepKind::Embed:
             if (s.out.f8 || !s.in.i64) throw std::runtime_error("internal error: the embed kernels take int64 ids and write floats or halfs");
             check(LaunchEmbed(MakeEmbedArgs(pi, s, wb), s.tile, stream_), "embed");
@@ -1809,6 +1832,12 @@ static std::string kernel_label(const Step& s) {
         case StepKind::LayerNorm:
             return s.tile == 0 ? std::string("layernorm_generic_kernel")
                                : std::string("layernorm_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
+        case StepKind::GroupNorm: {
+            static const char* const acts[] = {"none", "sigmoid", "", "silu", "", "relu"};
+            const std::string t = s.out.f16 ? "f16" : "f32";
+            return s.tile == 0 ? std::string("groupnorm_generic_kernel")
+                               : "groupnorm_stats_kernel<" + t + "> + groupnorm_apply_kernel<" + t + "," + acts[int(s.act.kind)] + ">";
+        }
         case StepKind::Embed:
             return s.tile == 0 ? std::string("embed_ln_generic_kernel")
                                : std::string("embed_ln_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";

@@ -239,6 +239,59 @@ constexpr int LnDefaultTile(int64_t c, bool f16) {
 bool LayerNormEligible(const LnArgs& a, int tile);
 hipError_t LaunchLayerNorm(const LnArgs& a, int tile, hipStream_t stream);
 
+// GroupNormalization of an NHWC view (kernels_gn.hip): for image n and group g = c / (C / groups), over the C / groups channels of the group and every pixel,
+//   out[n, p, c] = act((in[n, p, c] - mean_ng) * rsqrt(var_ng + eps) * gamma[c] + beta[c]),  var_ng the mean of the centred squares.
+// fp32 statistics in both element types; gamma / beta fp32; no atomics, every combine in a fixed order.  out may alias in.
+struct GnArgs {
+    TensorArg in, out;                 // the same shape
+    const float* gamma = nullptr;      // [C]
+    const float* beta = nullptr;       // [C] or null
+    int groups = 1;
+    float eps = 1e-5f;
+    int act = 0; float act_a = 0.f, act_b = 0.f;   // ApplyAct on the result
+    float* workspace = nullptr;        // tile 1: the (count, mean, M2) records, GnWorkspaceFloats of them
+    int64_t workspace_floats = 0;
+};
+// tile 0: groupnorm_generic_kernel, one workgroup per (image, group), three passes over its data: any C / groups, channel stride, pitch, channel
+// offset, mixed element types.  tile 1: groupnorm_stats_kernel + groupnorm_apply_kernel over (image, slab of pixels) with 16-byte channel vectors
+// (V = 4 floats / 8 halfs of the OUTPUT type): C, both pitches and both channel offsets multiples of V, at most kGnMaxVectors vectors per pixel
+// (a lane keeps one), and a vector inside one group or made of whole groups (C / groups a multiple or a divisor of V); the activation one of
+// none / sigmoid / silu / relu.
+constexpr int kNumGnTiles = 2;
+constexpr int kGnBlock = 256;
+constexpr int kGnMaxVectors = kGnBlock;
+constexpr bool GnActOk(int act) { return act == 0 || act == 1 || act == 3 || act == 5; }
+constexpr bool GnTileFits(int64_t c, int64_t groups, bool f16_out, int64_t pitch_in, int64_t off_in, int64_t pitch_out, int64_t off_out, int act, int tile) {
+    const int64_t V = f16_out ? 8 : 4;
+    if (tile != 1 || groups < 1 || c % groups || c % V || c / V > kGnMaxVectors || !GnActOk(act)) return false;
+    const int64_t cpg = c / groups;
+    return (cpg % V == 0 || V % cpg == 0) && pitch_in % V == 0 && off_in % V == 0 && pitch_out % V == 0 && off_out % V == 0;
+}
+// Pixels per slab: at least about 64 KiB of the image per workgroup (enough work to hide the launch), whole multiples of the pixel rows a workgroup
+// covers per iteration; larger where that would make more than kGnMaxSlabs slabs per image or more than about kGnWantBlocks workgroups in all (every
+// apply workgroup combines all of its image's records first: with 256 slabs of 64 KiB that combine took longer than the slab's own traffic)
+constexpr int kGnMaxSlabs = 256;
+constexpr int kGnWantBlocks = 2048;
+constexpr int64_t GnSlabPixels(int64_t n, int64_t hw, int64_t c, bool f16) {
+    const int64_t cv = c / (f16 ? 8 : 4), rows = cv >= 1 && cv <= kGnBlock ? kGnBlock / cv : 1;      // pixel rows per iteration
+    int64_t px = 65536 / (c < 1 ? 1 : c * (f16 ? 2 : 4));
+    int64_t want = kGnWantBlocks / (n < 1 ? 1 : n);
+    want = want < 1 ? 1 : (want > kGnMaxSlabs ? kGnMaxSlabs : want);
+    if (px * want < hw) px = (hw + want - 1) / want;
+    px = (px + rows - 1) / rows * rows;
+    return px < 1 ? 1 : px;
+}
+constexpr int64_t GnSlabs(int64_t n, int64_t hw, int64_t c, bool f16) { const int64_t px = GnSlabPixels(n, hw, c, f16); return (hw + px - 1) / px; }
+// floats of workspace tile 1 needs: one (count, mean, M2) record per (image, slab, group)
+constexpr int64_t GnWorkspaceFloats(int64_t n, int64_t hw, int64_t c, int64_t groups, bool f16) { return 3 * n * GnSlabs(n, hw, c, f16) * groups; }
+// the planner's default where tile 1 fits: two launches cost more than they save while one workgroup per (image, group) still has little to read
+constexpr int64_t kGnTile1MinGroupElems = 2048;
+constexpr int GnDefaultTile(int64_t n, int64_t hw, int64_t c, int64_t groups) { return hw * (c / groups) >= kGnTile1MinGroupElems ? 1 : 0; }
+bool GroupNormEligible(const GnArgs& a, int tile);
+hipError_t LaunchGroupNorm(const GnArgs& a, int tile, hipStream_t stream);
+// tile 1's launches one by one (scripts): 0 statistics, 1 apply
+hipError_t LaunchGroupNormPhase(const GnArgs& a, int phase, hipStream_t stream);
+
 // Token embedding + LayerNormalization (kernels_embed.hip; BERT-class graphs): for every token row r = (n, l) of out [N, L, D]
 //   out[r, :] = LayerNorm(word[ids[r]] + type[tids[r]] + pos[l]; gamma, beta, eps)
 // ids / tids are the dense int64 [N, L] graph inputs; a negative index counts from the end, the wrapped index is clamped into the table.  Tables,

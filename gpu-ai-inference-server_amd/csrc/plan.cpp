@@ -46,7 +46,7 @@ struct Val {
     int64_t sel_rows = 1, sel_idx = 0;
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED, L_GROUPNORM };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -79,6 +79,8 @@ struct LNode {
     // L_EMBED: in = the int64 ids of the first table (and of the second); w = the first table [emb_vocab][D], w2 = the second [emb_types][D] (empty:
     // none), bias = the position rows [L][D] (empty: none), s / t / eps = gamma / beta / epsilon of the LayerNormalization behind the sum
     int64_t emb_vocab = 0, emb_types = 0;
+    // L_GROUPNORM: s / t = gamma / beta per channel (the inner InstanceNormalization's scale and bias folded in), eps, act = the fused activation
+    int gn_groups = 0;
     bool has_pre = false, pre_relu = false, relu = false;
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
@@ -481,6 +483,22 @@ struct Planner {
     void MatchEmbed();
     void ImportEmbed(const OnnxNode& on, const EmbedMatch& em);
     void EmitEmbed(const LNode& n, Step& s);
+    // MatchGroupNorm: the spellings of a group norm.  gn_head: the last node of a match -> what ImportGroupNorm needs; gn_skip: its other nodes
+    struct GnMatch {
+        char form = 'a';                       // 'a' Reshape -> InstanceNormalization -> Reshape [-> Mul] [-> Add], 'b' GroupNormalization, 'c' InstanceNormalization on the map
+        std::string x, out, name, in_name;     // in_name: the InstanceNormalization / GroupNormalization node (messages)
+        int64_t groups = 0;                    // form c: the channel count, known at the import
+        float eps = 1e-5f;
+        std::vector<int64_t> shape1, back;     // form a: the two Reshape targets; back empty: Shape(x)
+        const OnnxTensor *scale = nullptr, *bias = nullptr, *gamma = nullptr, *beta = nullptr;
+        std::string gamma_name, beta_name;
+    };
+    std::map<const OnnxNode*, GnMatch> gn_head;
+    std::set<const OnnxNode*> gn_skip;
+    void MatchGroupNorm();
+    void ImportGroupNorm(const OnnxNode& on, const GnMatch& gm);
+    void FuseGroupNormActivations();
+    void EmitGroupNorm(const LNode& n, Step& s);
     bool FoldExpand(const OnnxNode& on, const LNode& n);
     bool ImportTokenView(const OnnxNode& on, LNode& n);
     void ImportTokenConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
@@ -1325,12 +1343,14 @@ bool Planner::ImportTranspose(const OnnxNode& on, const LNode& n) {
     ps += "]";
     const int v = in_val(on, 0);
     // tokens: [N, C, H*W] (a flat name) -> [N, H*W, C] is the NHWC storage itself; the way back [N, L, D] -> [N, D, L] waits for its Reshape
-    if (L.flat_names.count(on.inputs[0]) || L.is_tok(on.inputs[0])) {
-        const bool flat = L.flat_names.count(on.inputs[0]) != 0;
+    if (L.flat_names.count(on.inputs[0]) || L.is_tok(on.inputs[0]) || L.back_names.count(on.inputs[0])) {
+        const bool flat = L.flat_names.count(on.inputs[0]) != 0, back = L.back_names.count(on.inputs[0]) != 0;
         if (perm != std::vector<int64_t>{0, 2, 1})
-            fail("Transpose " + n.name + ": perm " + ps + " on " + (flat ? "the [N, C, H*W] reshape of a feature map" : "a token view") + " is not supported (only [0,2,1] is)");
+            fail("Transpose " + n.name + ": perm " + ps + " on " + (flat ? "the [N, C, H*W] reshape of a feature map" : back ? "the [N, D, L] transpose of a token view" : "a token view") + " is not supported (only [0,2,1] is)");
         const Val X = L.vals[v];
-        if (!flat) { L.alias_name(on.outputs[0], v, false); L.back_names.insert(on.outputs[0]); }
+        // [N, L, D] -> [N, D, L] -> [N, L, D]: two transposes back to back cancel (torch writes group_norm(h.transpose(1, 2)).transpose(1, 2) unfolded)
+        if (back) { L.alias_name(on.outputs[0], v, false); L.tok_names.insert(on.outputs[0]); }
+        else if (!flat) { L.alias_name(on.outputs[0], v, false); L.back_names.insert(on.outputs[0]); }
         else if (X.h == 1) { L.alias_name(on.outputs[0], v, false); L.tok_names.insert(on.outputs[0]); }
         else {
             LNode a;
@@ -1366,6 +1386,9 @@ void Planner::ImportNode(const OnnxNode& on) {
     if (wattn_skip.count(&on)) return;
     if (const auto wm = wattn_head.find(&on); wm != wattn_head.end()) { ImportWindowAttention(on, wm->second); return; }
     if (const auto mh = merge_head.find(&on); mh != merge_head.end()) { ImportPatchMerge(on, mh->second); return; }
+    // a matched group norm: its last node imports the whole of it (ImportGroupNorm checks what its input may be: a flat name is one of them)
+    if (gn_skip.count(&on)) return;
+    if (const auto gh = gn_head.find(&on); gh != gn_head.end()) { ImportGroupNorm(on, gh->second); return; }
     // a channels-last view may feed only the ops that read it as one: anything else (a Shape and the other folded ops included, hence before
     // the folds) would take its n / c / h / w for the ONNX dims
     static const std::set<std::string> cl_ops = {"LayerNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose"};
@@ -1381,7 +1404,7 @@ void Planner::ImportNode(const OnnxNode& on) {
                  "Gather and the Reshape of the attention pattern may read one");
         if (L.flat_names.count(name) && op != "Transpose")
             fail(op + " " + n.name + ": input " + name + " is the [N, C, H*W] reshape of a feature map; only a Transpose with perm [0,2,1] (to tokens [N, L, D]) may read it");
-        if (L.back_names.count(name) && op != "Reshape")
+        if (L.back_names.count(name) && op != "Reshape" && op != "Transpose")
             fail(op + " " + n.name + ": input " + name + " is the [N, D, L] transpose of a token view; only a Reshape to [N, D, h, w] with h * w = L may read it");
     }
     if (embed_skip.count(&on)) return;                     // inside a matched embedding sum: the LayerNormalization behind it imports the whole of it
@@ -2467,6 +2490,187 @@ void Planner::ImportEmbed(const OnnxNode& on, const EmbedMatch& em) {
     push_node(std::move(n), on.outputs[0], {N, D, 1, Lq}, true);
 }
 
+// ---- group norm: every spelling of a GroupNorm as ONE node ---------------------------------------------------------------------------------
+// Matched on the ONNX nodes, before the import (the [N, G, -1] value in the middle is no feature map):
+//   a) Reshape(x, [0, G, -1]) -> InstanceNormalization(scale [G], B [G]) -> Reshape(constant | Shape(x)) [-> Mul(gamma)] [-> Add(beta)]   (torch below opset 18)
+//   b) GroupNormalization(x, scale, bias; num_groups, epsilon)       scale / bias [G] below opset 21, [C] from it on
+//   c) InstanceNormalization directly on a map: G = C
+// The matcher takes the structure and the reader counts; ImportGroupNorm, which knows x's shape, checks the shapes.  A near miss is refused naming
+// the node and what did not match.
+void Planner::MatchGroupNorm() {
+    bool any = false;
+    for (const OnnxNode& on : m.nodes) any = any || on.op == "InstanceNormalization" || on.op == "GroupNormalization";
+    if (!any) return;
+    IndexGraph();
+    auto nm = [](const OnnxNode& o) { return o.name.empty() ? o.outputs[0] : o.name; };
+    // the constant operand of a two-operand node with exactly one; act = the index of the other
+    auto const_operand = [&](const OnnxNode& o, int& act) -> const OnnxTensor* {
+        if (o.inputs.size() != 2) return nullptr;
+        const OnnxTensor *c0 = gi.cst(o.inputs[0]), *c1 = gi.cst(o.inputs[1]);
+        if ((c0 != nullptr) == (c1 != nullptr)) return nullptr;
+        act = c0 ? 1 : 0;
+        return c0 ? c0 : c1;
+    };
+    for (const OnnxNode& on : m.nodes) {
+        if (on.op != "InstanceNormalization" && on.op != "GroupNormalization") continue;
+        GnMatch gm;
+        gm.name = gm.in_name = nm(on);
+        const std::string who = on.op + " " + gm.in_name;
+        if (on.inputs.size() != 3 || on.outputs.size() != 1) fail(who + ": expected the inputs x, scale, bias and one output");
+        gm.scale = gi.cst(on.inputs[1]);
+        gm.bias = gi.cst(on.inputs[2]);
+        if (!gm.scale || !gm.bias || gm.scale->f.empty() || gm.bias->f.empty()) fail(who + ": scale and bias must be floating-point constants");
+        gm.eps = on.attr_f("epsilon", 1e-5f);
+        gm.x = on.inputs[0];
+        gm.out = on.outputs[0];
+        if (on.op == "GroupNormalization") {
+            gm.form = 'b';
+            gm.groups = on.attr_i("num_groups", 0);
+            if (gm.groups < 1) fail(who + ": num_groups must be positive");
+            if (on.attr_i("stash_type", 1) != 1) fail(who + ": stash_type = " + std::to_string(on.attr_i("stash_type", 1)) + " is not supported (1 is)");
+            gn_head[&on] = gm;
+            continue;
+        }
+        const OnnxNode* r1 = gi.producer(on.inputs[0]);
+        const OnnxTensor* shp1 = r1 && r1->op == "Reshape" && r1->inputs.size() == 2 ? gi.cst(r1->inputs[1]) : nullptr;
+        if (!shp1 || shp1->i.size() != 3) {          // directly on a map
+            gm.form = 'c';
+            gn_head[&on] = gm;
+            continue;
+        }
+        const std::string prefix = who + ": the group-norm pattern around it does not match: ";
+        auto one_reader = [&](const std::string& name) {
+            if (gi.nreaders(name) != 1) fail(prefix + "the intermediate value " + name + " has " + std::to_string(gi.nreaders(name)) + " readers, not 1");
+        };
+        gm.form = 'a';
+        gm.shape1 = shp1->i;
+        gm.groups = gm.shape1[1];
+        gm.x = r1->inputs[0];
+        one_reader(r1->outputs[0]);
+        one_reader(on.outputs[0]);
+        const OnnxNode* r2 = gi.only_reader(on.outputs[0]);
+        if (!r2 || r2->op != "Reshape" || r2->inputs.size() != 2 || r2->inputs[0] != on.outputs[0])
+            fail(prefix + "a Reshape back to the input's shape must read " + on.outputs[0]);
+        std::vector<const OnnxNode*> taken = {r1, &on, r2};
+        if (const OnnxTensor* b = gi.cst(r2->inputs[1])) {
+            gm.back = b->i;
+            if (gm.back.empty()) fail(prefix + "the shape of Reshape " + nm(*r2) + " must be an integer constant or Shape(" + gm.x + ")");
+        } else {
+            const OnnxNode* sh = gi.producer(r2->inputs[1]);
+            if (!sh || sh->op != "Shape" || sh->inputs.size() != 1 || sh->inputs[0] != gm.x || sh->attrs.count("start") || sh->attrs.count("end"))
+                fail(prefix + "the shape of Reshape " + nm(*r2) + " must be an integer constant or Shape(" + gm.x + ")");
+            one_reader(sh->outputs[0]);
+            taken.push_back(sh);
+        }
+        // Mul(gamma) and Add(beta) behind it, either operand order; a missing one is gamma 1 / beta 0
+        const OnnxNode* last = r2;
+        auto affine = [&](const char* op, const OnnxTensor*& c, std::string& cname) {
+            const std::string& o = last->outputs[0];
+            const OnnxNode* hit = nullptr;
+            int act = 0;
+            for (const OnnxNode* r : gi.readers_of(o))
+                if (r->op == op && const_operand(*r, act) && r->inputs[size_t(act)] == o) hit = r;
+            if (!hit) return;
+            one_reader(o);
+            c = const_operand(*hit, act);
+            cname = hit->inputs[size_t(1 - act)];
+            taken.push_back(hit);
+            last = hit;
+        };
+        affine("Mul", gm.gamma, gm.gamma_name);
+        affine("Add", gm.beta, gm.beta_name);
+        gm.out = last->outputs[0];
+        gm.name.clear();
+        for (const OnnxNode* p : taken) if (p->op != "Shape") gm.name += (gm.name.empty() ? "" : "+") + nm(*p);
+        for (const OnnxNode* p : taken) if (p != last) gn_skip.insert(p);
+        gn_head[last] = gm;
+    }
+}
+
+void Planner::ImportGroupNorm(const OnnxNode& on, const GnMatch& gm) {
+    const std::string who = std::string(gm.form == 'b' ? "GroupNormalization " : "InstanceNormalization ") + gm.in_name;
+    auto dstr = [](const std::vector<int64_t>& d) {
+        std::string s = "[";
+        for (size_t k = 0; k < d.size(); ++k) s += (k ? "," : "") + std::to_string(d[k]);
+        return s + "]";
+    };
+    if (L.init(gm.x)) fail(who + ": constant input is not supported");
+    if (L.is_tok(gm.x)) fail(who + ": input " + gm.x + " is a token view [N, L, D]; a group norm reads an NCHW feature map or its [N, C, H*W] reshape");
+    if (L.is_cl(gm.x)) fail(who + ": input " + gm.x + " is a channels-last view (a Transpose with perm [0,2,3,1]); a group norm reads an NCHW feature map or its [N, C, H*W] reshape");
+    const int v = L.get_val(gm.x);
+    const Val X = L.vals[v];
+    if (X.is_i64) fail(who + ": input " + gm.x + " is not a floating-point value");
+    const bool flat = L.flat_names.count(gm.x) != 0, back = L.back_names.count(gm.x) != 0;
+    const std::vector<int64_t> xd = flat ? std::vector<int64_t>{X.n, X.c, X.h * X.w} : back ? std::vector<int64_t>{X.n, X.c, X.w} : X.dims;
+    if (xd.size() != 3 && xd.size() != 4) fail(who + ": an input of rank " + std::to_string(xd.size()) + " is not supported (ranks 3 and 4 are)");
+    const int64_t C = X.c, G = gm.form == 'c' ? C : gm.groups;
+    if (G < 1 || C % G) fail(who + ": C = " + std::to_string(C) + " is not divisible by num_groups = " + std::to_string(G));
+    int64_t total = 1;
+    for (int64_t d : xd) total *= d;
+    const int64_t per = gm.form == 'b' && m.opset >= 21 ? C : (gm.form == 'c' ? C : G);
+    if (gm.scale->numel() != per || gm.bias->numel() != per || gm.scale->dims.size() != 1 || gm.bias->dims.size() != 1)
+        fail(who + ": scale " + dstr(gm.scale->dims) + " and bias " + dstr(gm.bias->dims) + " must both be [" + std::to_string(per) + "]");
+    if (gm.form == 'a') {
+        const std::vector<int64_t>& s1 = gm.shape1;
+        if (!((s1[0] == 0 || s1[0] == xd[0]) && (s1[2] == -1 || s1[2] == total / (xd[0] * G))))
+            fail(who + ": the Reshape in front of it goes to " + dstr(s1) + ", not to [0, " + std::to_string(G) + ", -1]");
+        if (!gm.back.empty()) {
+            std::vector<int64_t> d = gm.back;
+            int64_t known = 1, neg = -1;
+            for (size_t k = 0; k < d.size(); ++k) {
+                if (d[k] == 0 && k < 3) d[k] = k == 0 ? xd[0] : (k == 1 ? G : total / (xd[0] * G));      // (0 copies the dim of the Reshape's own input [N, G, .])
+                if (d[k] == -1) neg = int64_t(k); else known *= d[k];
+            }
+            if (neg >= 0 && known > 0 && total % known == 0) d[size_t(neg)] = total / known;
+            if (d != xd) fail(who + ": the Reshape behind it restores " + dstr(gm.back) + ", not the input's shape " + dstr(xd));
+        }
+        const std::vector<int64_t> want = xd.size() == 4 ? std::vector<int64_t>{C, 1, 1} : std::vector<int64_t>{C, 1};
+        auto per_channel = [&](const OnnxTensor* t, const std::string& name, const char* what) {
+            if (t && (t->f.empty() || t->dims != want)) fail(who + ": " + what + " " + name + " has the shape " + dstr(t->dims) + ", not " + dstr(want));
+        };
+        per_channel(gm.gamma, gm.gamma_name, "gamma");
+        per_channel(gm.beta, gm.beta_name, "beta");
+    }
+    LNode n;
+    n.kind = L_GROUPNORM;
+    n.name = gm.name;
+    n.gn_groups = int(G);
+    n.eps = gm.eps;
+    n.s.resize(size_t(C));
+    n.t.resize(size_t(C));
+    const int64_t cpg = C / G;
+    for (int64_t c = 0; c < C; ++c) {
+        const size_t k = size_t(per == C ? c : c / cpg);
+        const float s = gm.scale->f[k], b = gm.bias->f[k];
+        const float g = gm.gamma ? gm.gamma->f[size_t(c)] : 1.f, be = gm.beta ? gm.beta->f[size_t(c)] : 0.f;
+        // (xn * s + b) * g + be: exact where the inner scale and bias are 1 and 0
+        n.s[size_t(c)] = s * g;
+        n.t[size_t(c)] = b * g + be;
+    }
+    n.in = {v};
+    (void)on;
+    push_node(std::move(n), gm.out, X.dims, false);
+    if (flat) L.flat_names.insert(gm.out);
+    if (back) L.back_names.insert(gm.out);
+}
+
+// ---- a SiLU, ReLU or Sigmoid behind a group norm, as its sole reader, runs in the norm's apply phase ----
+void Planner::FuseGroupNormActivations() {
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& gn = L.nodes[i];
+        if (gn.dead || gn.kind != L_GROUPNORM || gn.act.kind != ActKind::None || !single_consumer(gn.out)) continue;
+        LNode& b = L.nodes[size_t(L.consumers(gn.out)[0])];
+        if (b.in.size() != 1) continue;
+        if (b.kind == L_RELU) gn.act = Act{ActKind::Relu, 0.f, 0.f};
+        else if (b.kind == L_ACT && (b.act.kind == ActKind::Silu || b.act.kind == ActKind::Sigmoid)) gn.act = b.act;
+        else continue;
+        gn.name += "+" + b.name;
+        gn.out = b.out;
+        L.vals[gn.out].producer = int(i);
+        b.dead = true;
+    }
+}
+
 void Planner::FuseTokenAssemble() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& a = L.nodes[i];
@@ -2502,6 +2706,7 @@ void Planner::RefuseForF8() const {
         if (n.kind == L_CONV && (n.dil_h > 1 || n.dil_w > 1)) fail("dilated convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_RESIZE) fail("Resize is not supported in fp8 mode (node " + n.name + ")");
         if (n.kind == L_LAYERNORM || n.kind == L_EMBED) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
+        if (n.kind == L_GROUPNORM) fail("GroupNormalization is not supported in fp8 mode (node " + n.name + ")");
     }
     for (const LNode& n : L.nodes)
         if (n.kind == L_ATTENTION || n.kind == L_TOKASM || n.kind == L_TOKPOS) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
@@ -3003,10 +3208,23 @@ void Planner::AssignBuffers() {
     for (size_t v = 0; v < L.vals.size(); ++v)
         if (used[v] && L.vals[v].root == int(v) && first_def[v] == -1) alloc_buf(int(v), free_pool);
     for (size_t pos = 0; pos < order.size(); ++pos) {
+        // a group norm whose whole-buffer input dies here writes in place (its kernels read every element before they write it): the output takes over
+        // the input's buffer, which therefore does not return to the pool at this position
+        int handed = -1;
+        if (const LNode& gn = L.nodes[size_t(order[pos])]; gn.kind == L_GROUPNORM) {
+            const int ri = L.vals[gn.in[0]].root, ro = L.vals[gn.out].root;
+            const Val& I = L.vals[gn.in[0]];
+            if (ro == gn.out && first_def[ro] == int(pos) && last_use[ro] != kLiveForever && last_use[ri] == int(pos) && L.vals[ri].buf >= 0 && !L.vals[ri].dedicated &&
+                I.abs_off == 0 && I.c == L.vals[ri].c && I.sel_rows == 1 && root_floats(ri) == root_floats(ro) && precision != Precision::F8) {
+                L.vals[ro].buf = L.vals[ri].buf;
+                L.vals[ro].dedicated = false;
+                handed = ri;
+            }
+        }
         for (size_t v = 0; v < L.vals.size(); ++v)
-            if (used[v] && L.vals[v].root == int(v) && first_def[v] == int(pos)) alloc_buf(int(v), free_pool);
+            if (used[v] && L.vals[v].root == int(v) && first_def[v] == int(pos) && !(handed >= 0 && int(v) == L.vals[L.nodes[size_t(order[pos])].out].root)) alloc_buf(int(v), free_pool);
         for (size_t v = 0; v < L.vals.size(); ++v)
-            if (used[v] && L.vals[v].root == int(v) && last_use[v] == int(pos) && L.vals[v].buf >= 0 && !L.vals[v].dedicated)
+            if (used[v] && L.vals[v].root == int(v) && last_use[v] == int(pos) && L.vals[v].buf >= 0 && !L.vals[v].dedicated && int(v) != handed)
                 free_pool.insert({plan.buffer_floats[size_t(L.vals[v].buf)], L.vals[v].buf});
     }
 }
@@ -3464,6 +3682,34 @@ void Planner::EmitLayerNorm(const LNode& n, Step& s) {
     s.bytes = vbytes(s.in) + vbytes(s.out);
 }
 
+// Group-norm steps: the views tile 1 needs (kernels_gn.hip GroupNormEligible re-checks them with the pointers)
+static bool GnFastViews(const Step& s, int tile) {
+    auto ok = [&](const View& v) { return !v.nchw && !v.f8 && !v.i64 && v.f16 == s.out.f16; };
+    return ok(s.in) && ok(s.out) && GnTileFits(s.in.c, s.gn_groups, s.out.f16, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off, int(s.act.kind), tile);
+}
+
+// group norm: gamma at w_off, beta at bias_off (fp32 in every precision).  Tile 1 (statistics + apply) where kernels.h GnTileFits admits the views and the
+// group is large enough to pay for a second launch (GnDefaultTile), else the generic kernel; IE_FORCE_TILE as for layer norm, IE_GN_TILE the same for
+// the group norms alone.  Tile 1's records live in the workspace
+void Planner::EmitGroupNorm(const LNode& n, Step& s) {
+    if (s.in.f8 || s.out.f8) fail("GroupNormalization is not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::GroupNorm;
+    s.w_off = push_vec(n.s);
+    s.bias_off = push_vec(n.t);
+    s.ln_eps = n.eps;
+    s.gn_groups = n.gn_groups;
+    s.act = n.act;
+    const int64_t hw = s.in.h * s.in.w;
+    s.tile = GnFastViews(s, 1) ? GnDefaultTile(s.in.n, hw, s.in.c, s.gn_groups) : 0;
+    int t = ForcedTile(kNumGnTiles);
+    if (const char* e = env.get("IE_GN_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumGnTiles) t = std::atoi(e);      // (the group norms alone)
+    if (t >= 0) s.tile = t == 0 || GnFastViews(s, t) ? t : 0;
+    if (s.tile == 1) plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, GnWorkspaceFloats(s.in.n, hw, s.in.c, s.gn_groups, s.out.f16));
+    s.flops = 8.0 * double(s.in.numel());
+    // tile 1 reads the input twice (statistics, apply), the generic kernel three times (sum, centred squares, apply)
+    s.bytes = (s.tile == 1 ? 2.0 : 3.0) * vbytes(s.in) + vbytes(s.out);
+}
+
 // embed: the tables, the position rows, gamma and beta fp32 in the blob (in that order); the tile as for layer norm, by kernels.h EmbedTileFits
 void Planner::EmitEmbed(const LNode& n, Step& s) {
     if (s.out.f8) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
@@ -3586,6 +3832,7 @@ void Planner::EmitSteps() {
             case L_WATTN: EmitWindowAttention(n, s); break;
             case L_PATCHMERGE: EmitPatchMerge(n, s); break;
             case L_EMBED: EmitEmbed(n, s); break;
+            case L_GROUPNORM: EmitGroupNorm(n, s); break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -3918,6 +4165,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
     P.MatchPatchMerge();                                         // eight strided Slices and a Concat: one node
     P.MatchAttention();                                          // the unfused attention subgraphs, found on the ONNX nodes: each imports as one node
     P.MatchEmbed();                                              // table Gathers by INT64 graph inputs, their sum and the LayerNormalization behind it: one node
+    P.MatchGroupNorm();                                          // the spellings of a group norm: one node
     for (const OnnxNode& on : m.nodes) P.ImportNode(on);
     P.MarkOutputs();
     if (f8) P.RefuseForF8();
@@ -3925,6 +4173,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
     // ---- graph-level fusions ----
     P.FuseTokenAssemble();                                       // class-token Concat -> Add pos_embedding as one node
     P.FuseActivationPatterns();                                  // Mul(x, Sigmoid(x)) -> SiLU, Mul(x, HardSigmoid(x)) -> hardswish
+    P.FuseGroupNormActivations();                                // GroupNorm -> SiLU / ReLU / Sigmoid as one node
     if (!env.get("IE_NO_SE_FUSE")) P.FuseSqueezeExcite();        // pool -> 1x1 -> act -> 1x1 -> act -> Mul as one node
     P.MergeAffineChains();                                       // fusion 1: Affine -> Affine
     P.FuseConvEpilogues();                                       // fusion 2: Conv -> Affine / ReLU / Add / Clip / activation
@@ -3973,7 +4222,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed", "group_norm"};
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
@@ -4019,7 +4268,7 @@ std::string PlanToJson(const Plan& p) {
             o << "]";
         }
         // (only where set: the plans of graphs without these activations are unchanged)
-        if (s.act.kind != ActKind::None) json_act(o, "act", s.act);
+        if (s.act.kind != ActKind::None || s.kind == StepKind::GroupNorm) json_act(o, "act", s.act);
         if (s.pre_act.kind != ActKind::None) json_act(o, "pre_act", s.pre_act);
         if (s.mul) o << ",\"mul\":true";
         if (s.kind == StepKind::SqueezeExcite) {
@@ -4041,6 +4290,7 @@ std::string PlanToJson(const Plan& p) {
         if (s.kind == StepKind::WindowAttention)      // (window-attention steps only)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"window\":[" << s.win_h << "," << s.win_w << "],\"shift\":["
               << s.shift_h << "," << s.shift_w << "],\"masked\":" << (s.masked ? "true" : "false") << ",\"tile\":" << s.tile;
+        if (s.kind == StepKind::GroupNorm) o << ",\"groups\":" << s.gn_groups << ",\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile;      // (group-norm steps only)
         if (s.kind == StepKind::Embed) {      // (embed steps only)
             o << ",\"tables\":" << (s.w2_off >= 0 ? 2 : 1) << ",\"vocab\":[" << s.emb_vocab;
             if (s.w2_off >= 0) o << "," << s.emb_types;

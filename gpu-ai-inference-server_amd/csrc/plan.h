@@ -39,7 +39,7 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12, GroupNorm = 13 };
 
 // Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
 enum class ResizeMode : int { Nearest = 0, Linear = 1 };
@@ -149,6 +149,10 @@ struct Step {
     // LayerNorm(word[in] + type[in2] + pos[l]; gamma, beta, ln_eps); w_off = the first table [emb_vocab][D], w2_off = the second [emb_types][D] or -1,
     // emb_pos_off = the position rows [L][D] or -1, bias_off = gamma [D], bias2_off = beta [D] or -1, fp32 in every precision; tile as for LayerNorm
     int64_t emb_vocab = 0, emb_types = 0, emb_pos_off = -1;
+    // GroupNorm (kernels_gn.hip): out = act((in - mean_ng) * rsqrt(var_ng + ln_eps) * gamma + beta), the statistics over the in.c / gn_groups channels of
+    // group g and every pixel of image n; w_off = gamma [C], bias_off = beta [C], fp32 in every precision; act = the fused SiLU / ReLU / Sigmoid; tile 0 =
+    // the generic kernel, 1 = the statistics + apply launches, whose records live in the workspace (kernels.h GnWorkspaceFloats)
+    int gn_groups = 0;
     ConvAlgo algo = ConvAlgo::Naive;
     int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)

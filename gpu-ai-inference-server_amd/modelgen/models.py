@@ -1,5 +1,5 @@
 """Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY,
-FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT, Swin, BERT and small test graphs).
+FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT, Swin, BERT, GroupNorm ResNets, the diffusion VAE decoder and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -168,6 +168,67 @@ class GraphBuilder:
             ins.append(self.init(name + "_B", b.astype(np.float32)))
         y = name + "_out"
         self.nodes.append(pb.node("LayerNormalization", ins, [y], name, [pb.attr_int("axis", axis), pb.attr_float("epsilon", eps)]))
+        return y
+
+    def group_norm(self, x: str, c: int, groups: int, eps: float = 1e-5, form: str = "instancenorm", back: str = "const", rank3: bool = False,
+                   *, hw: Sequence[int] | None = None, name: str | None = None, swap: bool = False, affine: bool = True, per_group: bool = False,
+                   inner: str = "ones", out: str | None = None) -> str:
+        """GroupNorm of x [N, c, H, W] (rank3: of its [N, c, H*W] reshape) in the forms exporters write:
+          "instancenorm"  torch below opset 18: Reshape [0, groups, -1] -> InstanceNormalization(ones [groups], zeros [groups]) -> Reshape back ->
+                          Mul(gamma [c, 1, 1]) -> Add(beta [c, 1, 1]) ([c, 1] for rank3).  back: "const" the constant [0, c, H, W] (needs hw = (H, W)) or
+                          "shape" Shape(x), as the exporter writes it.  swap: the constants first.  affine False: no Mul / Add.
+                          inner "random": scale and B of the InstanceNormalization are drawn, not ones and zeros (a test of their folding)
+          "op18"          GroupNormalization with scale / bias [groups] (opset 18: build the model with finish(..., opset=18))
+          "op21"          GroupNormalization with scale / bias [c] (opset 21)
+          "instance"      InstanceNormalization directly on x with scale / B [c] (groups must equal c)
+        gamma and beta are drawn around 1 and 0 from the streams name_g / name_b; per_group (always for "op18"): one draw per group, repeated over its
+        channels, so that every form describes the same function."""
+        name = name or self._uid("gn")
+        k = groups if (per_group or form == "op18") else c
+        g = np.float32(1.0) + (rng.uniform(self.seed, name + "_g", k) - np.float32(0.5)) * np.float32(0.2)
+        b = (rng.uniform(self.seed, name + "_b", k) - np.float32(0.5)) * np.float32(0.2)
+        y = out or name + "_out"
+        if form in ("op18", "op21"):
+            if form == "op21" and k != c:
+                g, b = np.repeat(g, c // groups), np.repeat(b, c // groups)
+            ins = [x, self.init(name + "_scale", g.astype(np.float32)), self.init(name + "_bias", b.astype(np.float32))]
+            self.nodes.append(pb.node("GroupNormalization", ins, [y], name, [pb.attr_float("epsilon", eps), pb.attr_int("num_groups", groups)]))
+            return y
+        if k != c:
+            g, b = np.repeat(g, c // groups), np.repeat(b, c // groups)
+        if form == "instance":
+            assert groups == c
+            ins = [x, self.init(name + "_scale", g.astype(np.float32)), self.init(name + "_B", b.astype(np.float32))]
+            self.nodes.append(pb.node("InstanceNormalization", ins, [y], name, [pb.attr_float("epsilon", eps)]))
+            return y
+        if form != "instancenorm":
+            raise ValueError(form)
+        r1 = name + "_r1"
+        self.nodes.append(pb.node("Reshape", [x, self.init(name + "_shape1", np.array([0, groups, -1], np.int64))], [r1], r1))
+        if inner == "ones":
+            si, bi = np.ones(groups, np.float32), np.zeros(groups, np.float32)
+        else:
+            si = np.float32(1.0) + (rng.uniform(self.seed, name + "_is", groups) - np.float32(0.5))
+            bi = rng.uniform(self.seed, name + "_ib", groups) - np.float32(0.5)
+        ino = name + "_in"
+        self.nodes.append(pb.node("InstanceNormalization", [r1, self.init(name + "_in_scale", si.astype(np.float32)), self.init(name + "_in_B", bi.astype(np.float32))],
+                                  [ino], ino, [pb.attr_float("epsilon", eps)]))
+        if back == "const":
+            shp = self.init(name + "_shape2", np.array([0, c, hw[0] * hw[1]] if rank3 else [0, c, hw[0], hw[1]], np.int64))
+        elif back == "shape":
+            shp = name + "_xshape"
+            self.nodes.append(pb.node("Shape", [x], [shp], shp))
+        else:
+            raise ValueError(back)
+        r2 = name + "_r2" if affine else y
+        self.nodes.append(pb.node("Reshape", [ino, shp], [r2], name + "_r2"))
+        if not affine:
+            return y
+        tail = [c, 1] if rank3 else [c, 1, 1]
+        gi, bi2 = self.init(name + "_gamma", g.astype(np.float32).reshape(tail)), self.init(name + "_beta", b.astype(np.float32).reshape(tail))
+        mu = name + "_mul"
+        self.nodes.append(pb.node("Mul", [gi, r2] if swap else [r2, gi], [mu], mu))
+        self.nodes.append(pb.node("Add", [bi2, mu] if swap else [mu, bi2], [y], name + "_add"))
         return y
 
     def gelu(self, x: str, form: str = "erf", swap: bool = False, half: float = 0.5) -> str:
@@ -452,7 +513,7 @@ def two_input_graph(batch: int | str = 2, ca: int = 8, cb: int = 16, image: int 
 
 def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width: int = 64, image: int = 224, classes: int = 1000,
            seed: int = 50, in_name: str = "data", out_name: str = "logits", groups: int = 1, width_per_group: int = 64,
-           dilate: Sequence[bool] = (False, False, False)) -> bytes:
+           dilate: Sequence[bool] = (False, False, False), norm: str = "bn", gn_groups: int = 32) -> bytes:
     """ResNet-v1.5 bottleneck network (ResNet-50 with the defaults; BASELINE.json configs[4] names this architecture).
 
     groups / width_per_group give ResNeXt as torchvision builds it: the bottleneck's 3x3 is a grouped conv of
@@ -466,9 +527,12 @@ def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width:
 
     dilate[i] replaces the stride of stage i + 2 by a dilation, as torchvision's replace_stride_with_dilation does: the first block of a
     dilated stage keeps the previous dilation, the others use the doubled one (3x3 convs with pads = dilation).
+
+    norm "gn": every BatchNormalization is a GroupNorm of gn_groups groups in torch's spelling below opset 18 (GraphBuilder.group_norm, back "shape"),
+    as torchvision's resnet50(norm_layer=lambda c: GroupNorm(32, c)) exports.
     """
     gb = GraphBuilder("resnet", seed)
-    x, cin = _resnet_body(gb, in_name, layers, width, groups, width_per_group, dilate)
+    x, cin = _resnet_body(gb, in_name, layers, width, groups, width_per_group, dilate, norm, gn_groups)
     x = gb.gap(x)
     x = gb.simple("Flatten", [x], [pb.attr_int("axis", 1)])
     wfc = rng.gaussish(seed, "fc_w", classes * cin).reshape(classes, cin) * np.float32(np.sqrt(1.0 / cin))
@@ -479,10 +543,13 @@ def resnet(batch: int | str = 1, *, layers: Sequence[int] = (3, 4, 6, 3), width:
 
 
 def _resnet_body(gb: GraphBuilder, in_name: str, layers: Sequence[int], width: int, groups: int, width_per_group: int,
-                 dilate: Sequence[bool]) -> tuple[str, int]:
+                 dilate: Sequence[bool], norm: str = "bn", gn_groups: int = 32) -> tuple[str, int]:
     """The stem and the four bottleneck stages of resnet(); returns (feature map, its channels)"""
+    if norm not in ("bn", "gn"):
+        raise ValueError(norm)
+    bn = gb.bn if norm == "bn" else (lambda x, c, name: gb.group_norm(x, c, gn_groups, back="shape", name=name))
     x = gb.conv(in_name, 3, width, 7, stride=2, pad=3, name="conv1")
-    x = gb.relu(gb.bn(x, width, name="bn1"))
+    x = gb.relu(bn(x, width, name="bn1"))
     x = gb.pool("MaxPool", x, 3, 2, pad=1)
     cin = width
     dilation = 1
@@ -499,11 +566,11 @@ def _resnet_body(gb: GraphBuilder, in_name: str, layers: Sequence[int], width: i
             stride = stage_stride if bi == 0 else 1
             d = first_dilation if bi == 0 else dilation
             tag = f"s{si + 1}b{bi + 1}"
-            y = gb.relu(gb.bn(gb.conv(x, cin, mid, 1, name=tag + "_c1"), mid, name=tag + "_bn1"))
-            y = gb.relu(gb.bn(gb.conv(y, mid, mid, 3, stride=stride, pad=d, name=tag + "_c2", group=groups, dilation=d), mid, name=tag + "_bn2"))
-            y = gb.bn(gb.conv(y, mid, cout, 1, name=tag + "_c3", w_scale=float(0.5 * np.sqrt(2.0 / mid))), cout, name=tag + "_bn3")
+            y = gb.relu(bn(gb.conv(x, cin, mid, 1, name=tag + "_c1"), mid, name=tag + "_bn1"))
+            y = gb.relu(bn(gb.conv(y, mid, mid, 3, stride=stride, pad=d, name=tag + "_c2", group=groups, dilation=d), mid, name=tag + "_bn2"))
+            y = bn(gb.conv(y, mid, cout, 1, name=tag + "_c3", w_scale=float(0.5 * np.sqrt(2.0 / mid))), cout, name=tag + "_bn3")
             if bi == 0:
-                sc = gb.bn(gb.conv(x, cin, cout, 1, stride=stride, name=tag + "_proj"), cout, name=tag + "_bnp")
+                sc = bn(gb.conv(x, cin, cout, 1, stride=stride, name=tag + "_proj"), cout, name=tag + "_bnp")
             else:
                 sc = x
             x = gb.relu(gb.simple("Add", [y, sc]))
@@ -607,6 +674,11 @@ def unet(batch: int | str = 1, *, image: int = 224, base: int = 64, depth: int =
 
 def resnet50(batch: int | str = 1) -> bytes:
     return resnet(batch)
+
+
+def resnet50_gn(batch: int | str = 1, **kw) -> bytes:
+    """ResNet-50 with GroupNorm(32) in place of every BatchNorm (torchvision's resnet50(norm_layer=GroupNorm), detectron2 / BiT backbones)"""
+    return resnet(batch, norm="gn", gn_groups=32, **kw)
 
 
 def resnext50_32x4d(batch: int | str = 1, **kw) -> bytes:
@@ -1293,6 +1365,73 @@ def swin(batch: int | str = 1, *, image: int = 224, patch: int = 4, dims: Sequen
 
 def swin_t(batch: int | str = 1, **kw) -> bytes:
     return swin(batch, image=224, dims=(96, 192, 384, 768), depths=(2, 2, 6, 2), heads=(3, 6, 12, 24), window=7, **kw)
+
+
+def vae_resnet_block(gb: GraphBuilder, x: str, cin: int, cout: int, hw: Sequence[int], tag: str, gn) -> str:
+    """diffusers' ResnetBlock2D without a time embedding: norm1 -> SiLU -> conv1 3x3 -> norm2 -> SiLU -> conv2 3x3, the shortcut a 1x1 conv where the
+    channel count changes, out = shortcut + h"""
+    h = gb.conv(gb.silu(gn(x, cin, hw, tag + "_norm1")), cin, cout, 3, pad=1, bias=True, name=tag + "_conv1")
+    h = gb.conv(gb.silu(gn(h, cout, hw, tag + "_norm2")), cout, cout, 3, pad=1, bias=True, name=tag + "_conv2", w_scale=float(0.5 * np.sqrt(2.0 / (9 * cout))))
+    sc = x if cin == cout else gb.conv(x, cin, cout, 1, bias=True, name=tag + "_conv_shortcut")
+    return gb.simple("Add", [sc, h])
+
+
+def vae_attention(gb: GraphBuilder, x: str, c: int, hw: Sequence[int], tag: str, gn) -> str:
+    """diffusers' Attention with AttnProcessor2_0 on a map x [N, c, h, w], one head of c channels: view [N, c, h w] -> transpose(1, 2) ->
+    group_norm(. transpose(1, 2)).transpose(1, 2) (two Transposes back to back, as torch writes them) -> to_q / to_k / to_v -> view [N, L, 1, c] ->
+    transpose(1, 2) -> scaled_dot_product_attention in the exporter's lowering (q and k^T each times sqrt(c^-0.5)) -> transpose(1, 2) -> reshape
+    [N, L, c] -> to_out -> transpose(-1, -2) -> reshape [N, c, h, w] -> + residual"""
+    t = vit_tokens(gb, x, c)
+    g = gb.transpose(gn(gb.transpose(t, (0, 2, 1)), c, hw, tag + "_group_norm", rank3=True), (0, 2, 1))
+    shp = gb.init(tag + "_shape4", np.array([0, -1, 1, c], np.int64))
+    q, k, v = (gb.transpose(gb.simple("Reshape", [gb.linear(g, c, c, name=f"{tag}_to_{n}"), shp]), (0, 2, 1, 3)) for n in ("q", "k", "v"))
+    rs = gb.init(tag + "_sqrt_scale", np.array(np.sqrt(float(c) ** -0.5), np.float32))
+    s = gb.simple("MatMul", [gb.simple("Mul", [q, rs]), gb.simple("Mul", [gb.transpose(k, (0, 1, 3, 2)), rs])])
+    p = gb.simple("Softmax", [s], [pb.attr_int("axis", -1)])
+    y = gb.transpose(gb.simple("MatMul", [p, v]), (0, 2, 1, 3))
+    y = gb.simple("Reshape", [y, gb.init(tag + "_shape3", np.array([0, -1, c], np.int64))])
+    y = gb.linear(y, c, c, name=tag + "_to_out")
+    y = gb.simple("Reshape", [gb.transpose(y, (0, 2, 1)), gb.init(tag + "_shape_back", np.array([0, c, hw[0], hw[1]], np.int64))])
+    return gb.simple("Add", [y, x])
+
+
+def vae_decoder(batch: int | str = 1, *, latent: int = 32, base: int = 128, mults: Sequence[int] = (1, 2, 4, 4), layers: int = 2, groups: int = 32,
+                latent_ch: int = 4, gn_form: str = "instancenorm", seed: int = 860, in_name: str = "latent_sample", out_name: str = "sample") -> bytes:
+    """The decoder of diffusers' AutoencoderKL as Stable Diffusion 1.x configures it: latents [N, latent_ch, latent, latent] -> sample
+    [N, 3, 8 latent, 8 latent] (with four mults).  Written from diffusers' vae.py (Decoder, UNetMidBlock2D, UpDecoderBlock2D), resnet.py
+    (ResnetBlock2D, Upsample2D), attention_processor.py (Attention, AttnProcessor2_0) and the exporter's known lowerings at opset 17; no file of
+    that project is executed.
+
+    post_quant_conv 1x1 -> conv_in 3x3 -> mid block (ResnetBlock, single-head self-attention, ResnetBlock) on base * mults[-1] channels -> one up
+    block per entry of reversed(mults), each layers + 1 ResnetBlocks (a 1x1 conv shortcut where the channel count changes) and, but for the last,
+    a nearest x2 Resize + 3x3 conv -> conv_norm_out -> SiLU -> conv_out 3x3.  Every norm is GroupNorm(groups, eps 1e-6) in the spelling gn_form:
+    "instancenorm" (opset 17, the back-Reshape from Shape(x)), "op18" or "op21" (GroupNormalization, the model's opset 18 / 21).  SiLU is
+    Mul(x, Sigmoid(x)).  The divisions by output_scale_factor = 1 and rescale_output_factor = 1 that the modules write are left out."""
+    opset = {"instancenorm": 17, "op18": 18, "op21": 21}[gn_form]
+    gb = GraphBuilder("vae_decoder", seed)
+
+    def gn(x: str, c: int, hw: Sequence[int], name: str, rank3: bool = False) -> str:
+        return gb.group_norm(x, c, groups, eps=1e-6, form=gn_form, back="shape", rank3=rank3, hw=hw, name=name)
+
+    hw = (latent, latent)
+    c = base * mults[-1]
+    x = gb.conv(in_name, latent_ch, latent_ch, 1, bias=True, name="post_quant_conv", w_scale=float(np.sqrt(1.0 / latent_ch)))
+    x = gb.conv(x, latent_ch, c, 3, pad=1, bias=True, name="conv_in", w_scale=float(np.sqrt(1.0 / (9 * latent_ch))))
+    x = vae_resnet_block(gb, x, c, c, hw, "mid_res1", gn)
+    x = vae_attention(gb, x, c, hw, "mid_attn", gn)
+    x = vae_resnet_block(gb, x, c, c, hw, "mid_res2", gn)
+    for bi, mult in enumerate(reversed(list(mults))):
+        cout = base * mult
+        for li in range(layers + 1):
+            x = vae_resnet_block(gb, x, c, cout, hw, f"up{bi}_res{li}", gn)
+            c = cout
+        if bi + 1 < len(mults):
+            x = gb.resize(x, [batch, c, hw[0], hw[1]], scales=[2.0, 2.0], mode="nearest", coord="asymmetric", nearest="floor", form="scales", name=f"up{bi}_upsample")
+            hw = (2 * hw[0], 2 * hw[1])
+            x = gb.conv(x, c, c, 3, pad=1, bias=True, name=f"up{bi}_upsample_conv")
+    x = gb.silu(gn(x, c, hw, "conv_norm_out"))
+    gb.conv(x, c, 3, 3, pad=1, bias=True, name="conv_out", out=out_name)
+    return gb.finish([(in_name, [batch, latent_ch, latent, latent])], [(out_name, [batch, 3, hw[0], hw[1]])], opset=opset)
 
 
 def write_repo(root: str, name: str, model_bytes: bytes, version: str = "1", config_json: str | None = None) -> str:

@@ -22,7 +22,9 @@ For attention steps (vit_b_16, vit_tiny_16): the graph-replay time as the median
 (IE_FORCE_TILE=0 picks the generic one), its microseconds, its TFLOP/s against the sustained MFMA rate (129 TF/s fp32) and torch's
 F.scaled_dot_product_attention on the same [N, H, L, hd] operands, timed in a process of its own.
 For window-attention steps (swin_t): the graph-replay time, the share of the eager forward per step family, and per distinct window-attention and
-patch-merge shape the launched kernel with its algorithmic TB/s next to the 3.6 TB/s that layernorm_kernel sustains."""
+patch-merge shape the launched kernel with its algorithmic TB/s next to the 3.6 TB/s that layernorm_kernel sustains.
+For group-norm steps (vae_decoder, resnet50_gn): their share and the attention steps' share of the eager forward, the time per image, and per distinct
+shape the launched kernels and their algorithmic TB/s (one read + one write) against the copy rate."""
 import json
 import os
 import subprocess
@@ -170,8 +172,9 @@ else:
         models.write_repo(root, model_name, BUILDERS[model_name]() if model_name in BUILDERS else getattr(models, model_name)("N"))
 plan = B.DescribeModel(mdir, batch)["plan"]
 m = B.CreateModel(mdir, os.path.basename(os.path.dirname(mdir)))
-din, dout = B.Prepare(m, [[batch, 3, 224, 224]], 1)
-B.CopyToDevice(m, din[0], models.synthetic_input((batch, 3, 224, 224), stream="prof"))
+ishape = plan["inputs"][0]["dims"]          # [batch, 3, 224, 224] for the classifiers; the VAE decoder reads latents [batch, 4, 32, 32]
+din, dout = B.Prepare(m, [ishape], 1)
+B.CopyToDevice(m, din[0], models.synthetic_input(tuple(ishape), stream="prof"))
 B.RunPrepared(m, 5, True)
 # per step the median over the passes (50 for a graph with transposed convs: its table is what DESIGN 3.21 records)
 prof = B.Profile(m, 50 if any(s.get("algo") == "transposed" for s in plan["steps"]) else 10)
@@ -317,6 +320,21 @@ if wts:
         ms = sorted(q["ms"] for q in ps)[len(ps) // 2]
         tbs = ps[0]["bytes"] / ms / 1e9
         print(f"{f'{kind} {n},{h}x{w},{heads},{list(shift)}':>44} {len(ps):5d} {kern:40} {ms * 1e3:11.1f} {tbs:6.2f} {tbs / 3.6 * 100:5.1f}%")
+gns = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "group_norm"]
+if gns:
+    share = lambda ps: sum(p["ms"] for p, _ in ps)  # noqa: E731
+    ats = [(p, s) for p, s in zip(prof, plan["steps"]) if s["kind"] == "attention"]
+    print(f"# {len(gns)} group-norm steps: {share(gns):.4f} ms, {share(gns) / tot * 100:.1f}% of the eager forward ({tot / batch:.4f} ms per image); "
+          f"{len(ats)} attention steps ({', '.join(sorted(set(p['kernel'] for p, _ in ats))) or '-'}): {share(ats):.4f} ms, {share(ats) / tot * 100:.1f}%")
+    print(f"{'group-norm shape':>18} {'steps':>5} {'kernel':68} {'ms (median)':>11} {'TB/s':>6} {'%6.29T':>7}")
+    seen = {}
+    for p, s in gns:
+        seen.setdefault((s["in"]["h"], s["in"]["w"], s["in"]["c"], p["kernel"]), []).append((p, s))
+    for (h, w, c, kern), ps in seen.items():
+        ms = sorted(q["ms"] for q, _ in ps)[len(ps) // 2]
+        s0 = ps[0][1]
+        tbs = 2.0 * s0["in"]["n"] * h * w * c * (2 if s0["in"]["f16"] else 4) / ms / 1e9       # algorithmic: one read, one write
+        print(f"{f'{h}x{w}x{c}':>18} {len(ps):5d} {kern:68} {ms:11.4f} {tbs:6.2f} {tbs / 6.29 * 100:6.1f}%")
 if dws or ses or grs:
     import time
     B.RunPrepared(m, 10, True)

@@ -1,0 +1,293 @@
+"""CPU: GroupNorm through the ONNX reader and the planner (EngineDescribeModel): every spelling of a group norm becomes the same `group_norm`
+step with the same weight blob, the activation behind it fuses, near misses are refused by name, and the GroupNorm ResNet and the VAE decoder
+plan into the expected steps.  The float64 reference of tests/gn_ref.py is checked against a torch restatement of the decoder, and the test data
+against three broken ways of taking the statistics."""
+import numpy as np
+import pytest
+
+import gn_graphs as G
+import gn_ref
+from gpu_ai_inference_server_amd import binding as B
+from gpu_ai_inference_server_amd.modelgen import models
+from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
+
+PRECS = ("fp32", "fp16")
+RTOL16 = 3e-3
+
+
+def _describe(path, batch, monkeypatch, prec, **env):
+    monkeypatch.setenv("IE_PRECISION", prec)
+    for k in ("IE_FORCE_TILE", "IE_FORCE_ALGO", "IE_FORCE_SPLITK"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    return B.DescribeModel(path, batch)["plan"]
+
+
+def _plan_of(tmp_path, name, mb, monkeypatch, prec="fp32", batch=2, **env):
+    return _describe(models.write_repo(str(tmp_path), name, mb), batch, monkeypatch, prec, **env)
+
+
+# ---- one step from every spelling ------------------------------------------------------------------------------------------------------------
+SPELLINGS = {
+    "a_const": dict(form="instancenorm", back="const"),
+    "a_shape": dict(form="instancenorm", back="shape"),
+    "a_swapped": dict(form="instancenorm", back="shape", swap=True),
+    "b_op18": dict(form="op18"),
+    "b_op21": dict(form="op21"),
+}
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_same_plan_from_every_spelling(tmp_path, monkeypatch, prec):
+    """per_group: gamma and beta are one draw per group, so the opset-18 form (scale / bias [G]) describes the same function as the others"""
+    n, c, h, w, g = 2, 64, 9, 9, 32
+    steps, blobs = {}, {}
+    for key, kw in SPELLINGS.items():
+        path = models.write_repo(str(tmp_path), key, G.gn_graph(n, c, h, w, g, act="silu", per_group=True, **kw))
+        plan = _describe(path, n, monkeypatch, prec)
+        assert [s["kind"] for s in plan["steps"]] == ["copy", "group_norm", "copy"], key
+        s = dict(G.gn_step(plan))
+        assert s.pop("name").startswith("gn")
+        steps[key] = s
+        blobs[key] = B.PlanWeights(path, n)
+    first = steps["a_const"]
+    assert first["groups"] == g and first["act"] == ["silu", 0, 0] and abs(first["eps"] - 1e-5) < 1e-11 and first["tile"] in (0, 1)
+    assert first["w_off"] >= 0 and first["bias_off"] == first["w_off"] + c and first["flops"] == 8.0 * n * c * h * w
+    es = 2 if prec == "fp16" else 4
+    assert first["bytes"] == (3 if first["tile"] == 0 else 2) * n * c * h * w * es + n * c * h * w * es
+    for key in SPELLINGS:
+        assert steps[key] == first, key
+        np.testing.assert_array_equal(blobs[key], blobs["a_const"])
+    # gamma, then beta, fp32: the draws of GraphBuilder.group_norm, each repeated over its group's channels
+    blob = blobs["a_const"]
+    gamma, beta = blob[first["w_off"]:first["w_off"] + c], blob[first["bias_off"]:first["bias_off"] + c]
+    assert (gamma.reshape(g, -1) == gamma.reshape(g, -1)[:, :1]).all() and np.unique(gamma).size == g and abs(gamma.mean() - 1) < 0.05
+    assert (beta.reshape(g, -1) == beta.reshape(g, -1)[:, :1]).all() and np.unique(beta).size == g
+
+
+def test_inner_scale_and_bias_fold_exactly(tmp_path, monkeypatch):
+    """a drawn scale s [G] and bias b [G] on the inner InstanceNormalization: gamma' = s_g gamma_c, beta' = b_g gamma_c + beta_c in fp32; a missing
+    Mul / Add is gamma 1 / beta 0; form c) is G = C with its own scale / B"""
+    n, c, h, w, g = 1, 16, 4, 4, 4
+    mb = G.gn_graph(n, c, h, w, g, inner="random")
+    path = models.write_repo(str(tmp_path), "inner", mb)
+    s = G.gn_step(_describe(path, n, monkeypatch, "fp32"))
+    blob = B.PlanWeights(path, n)
+    from oracle import onnx_oracle as O
+    I = O.load_model(mb).inits
+    si, bi = np.repeat(I["gn_in_scale"], c // g), np.repeat(I["gn_in_B"], c // g)
+    ga, be = I["gn_gamma"].reshape(-1), I["gn_beta"].reshape(-1)
+    np.testing.assert_array_equal(blob[s["w_off"]:s["w_off"] + c], si * ga)
+    np.testing.assert_array_equal(blob[s["bias_off"]:s["bias_off"] + c], bi * ga + be)
+    path = models.write_repo(str(tmp_path), "plain", G.gn_graph(n, c, h, w, g, affine=False))
+    s = G.gn_step(_describe(path, n, monkeypatch, "fp32"))
+    blob = B.PlanWeights(path, n)
+    assert (blob[s["w_off"]:s["w_off"] + c] == 1).all() and (blob[s["bias_off"]:s["bias_off"] + c] == 0).all()
+    mb = G.gn_graph(n, c, h, w, c, form="instance")
+    path = models.write_repo(str(tmp_path), "inst", mb)
+    s = G.gn_step(_describe(path, n, monkeypatch, "fp32"))
+    assert s["groups"] == c and s["name"] == "gn"
+    np.testing.assert_array_equal(B.PlanWeights(path, n)[s["w_off"]:s["w_off"] + c], O.load_model(mb).inits["gn_scale"])
+
+
+def test_rank3_flat_form_and_cancelling_transposes(tmp_path, monkeypatch):
+    """the norm on the [N, C, H*W] reshape: the same step on the map's storage; Transpose [0,2,1] twice behind it costs nothing"""
+    plan = _plan_of(tmp_path, "r3", G.gn_rank3_graph(2, 32, 5, 7, 8), monkeypatch)
+    assert [s["kind"] for s in plan["steps"]] == ["copy", "group_norm", "copy"]
+    s = G.gn_step(plan)
+    assert (s["in"]["c"], s["in"]["h"], s["in"]["w"], s["groups"]) == (32, 5, 7, 8)
+
+
+# ---- the activation behind the norm ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("act,swap,want", [("silu", False, "silu"), ("silu", True, "silu"), ("relu", False, "relu"), ("sigmoid", False, "sigmoid"), (None, False, "none")])
+def test_activation_fuses_into_the_step(tmp_path, monkeypatch, act, swap, want):
+    plan = _plan_of(tmp_path, "act", G.gn_graph(2, 32, 5, 7, 8, act=act, act_swap=swap), monkeypatch)
+    assert [s["kind"] for s in plan["steps"]] == ["copy", "group_norm", "copy"]
+    assert G.gn_step(plan)["act"] == [want, 0, 0]
+
+
+def test_activation_with_a_second_reader_of_the_norm_stays_a_step(tmp_path, monkeypatch):
+    gb = models.GraphBuilder("g", 3)
+    y = gb.group_norm("x", 32, 8, back="shape", name="gn")
+    gb.simple("Add", [gb.silu(y), y], out="y")
+    plan = _plan_of(tmp_path, "act2", gb.finish([("x", [2, 32, 5, 7])], [("y", [2, 32, 5, 7])], opset=17), monkeypatch)
+    kinds = [s["kind"] for s in plan["steps"]]
+    assert kinds.count("group_norm") == 1 and kinds.count("eltwise") == 2
+    assert G.gn_step(plan)["act"] == ["none", 0, 0]
+    assert [s["act"] for s in plan["steps"] if s["kind"] == "eltwise" and "act" in s] == [["silu", 0, 0]]
+
+
+# ---- tiles -----------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("shape", [(2, 32, 1, 1, 32), (1, 64, 9, 9, 32), (2, 128, 16, 16, 32), (1, 512, 8, 8, 32), (1, 20, 3, 3, 5), (1, 64, 37, 41, 32), (1, 24, 4, 4, 2)])
+def test_tiles_and_workspace(tmp_path, monkeypatch, shape, prec):
+    """the default tile follows kernels.h GnDefaultTile, a forced tile 1 that does not fit falls back to tile 0, tile 1 raises the workspace to its
+    (count, mean, M2) records.  (1, 24, 4, 4, 2): 12 channels per group are neither a multiple nor a divisor of a vector"""
+    n, c, h, w, g = shape
+    f16 = prec == "fp16"
+    path = models.write_repo(str(tmp_path), "t", G.gn_graph(n, c, h, w, g))
+    fits = G.gn_tile_fits(c, g, f16)
+    assert G.gn_step(_describe(path, n, monkeypatch, prec))["tile"] == G.gn_default_tile(c, g, h * w, f16)
+    assert G.gn_step(_describe(path, n, monkeypatch, prec, IE_FORCE_TILE="0"))["tile"] == 0
+    plan = _describe(path, n, monkeypatch, prec, IE_FORCE_TILE="1")
+    assert G.gn_step(plan)["tile"] == (1 if fits else 0)
+    if fits:
+        assert plan["workspace_floats"] >= 3 * n * G.gn_slabs(n, h * w, c, f16)[1] * g
+    if shape == (1, 64, 37, 41, 32):
+        px, slabs = G.gn_slabs(n, h * w, c, f16)
+        assert slabs >= 3 and (h * w) % px != 0
+
+
+# ---- refusals --------------------------------------------------------------------------------------------------------------------------------
+def _manual(gamma_dims=None, back=None, extra_reader=None, c=16, g=4, hw=(4, 4)):
+    """form a) written node by node, with one thing wrong"""
+    gb = models.GraphBuilder("g", 3)
+    i64 = lambda name, v: gb.init(name, np.array(v, np.int64))  # noqa: E731
+    r1 = gb.simple("Reshape", ["x", i64("s1", [0, g, -1])], out="r1")
+    y = gb.simple("InstanceNormalization", [r1, gb.init("is", np.ones(g, np.float32)), gb.init("ib", np.zeros(g, np.float32))], [pb.attr_float("epsilon", 1e-5)], out="inorm")
+    r2 = gb.simple("Reshape", [y, i64("s2", back or [0, c, hw[0], hw[1]])], out="r2")
+    m = gb.simple("Mul", [r2, gb.init("gamma", np.ones(gamma_dims or [c, 1, 1], np.float32))], out="m")
+    gb.simple("Add", [m, gb.init("beta", np.zeros([c, 1, 1], np.float32))], out="y")
+    outs = [("y", [2, c, hw[0], hw[1]])]
+    if extra_reader:
+        gb.simple("Relu", [extra_reader], out="z")
+        outs.append(("z", [2, c, hw[0], hw[1]] if extra_reader in ("r2", "m") else [2, g, c // g * hw[0] * hw[1]]))
+    return gb.finish([("x", [2, c, hw[0], hw[1]])], outs, opset=17)
+
+
+def _on(view, c=16, g=4):
+    """GroupNormalization-21 on a view of x [2, 16, 4, 4] / on a [2, 16] input"""
+    gb = models.GraphBuilder("g", 3)
+    x = {"tokens": lambda: models.vit_tokens(gb, "x", c), "channels_last": lambda: gb.transpose("x", (0, 2, 3, 1)), "rank2": lambda: "x"}[view]()
+    gb.group_norm(x, c, g, form="op21", name="gn", out="y")
+    shape = [2, c] if view == "rank2" else [2, c, 4, 4]
+    return gb.finish([("x", shape)], [("y", shape)], opset=21)
+
+
+REFUSALS = {
+    "c_not_divisible": (lambda: G.gn_graph(2, 20, 3, 3, 8, form="op21"), r"^GroupNormalization gn: C = 20 is not divisible by num_groups = 8$"),
+    "c_not_divisible_form_a": (lambda: _manual(c=18, g=4, hw=(2, 2), back=[0, 18, 2, 2]), r"^InstanceNormalization instancenormalization_\d+: C = 18 is not divisible by num_groups = 4$"),
+    "back_to_another_shape": (lambda: _manual(back=[0, 16, 2, 8]), r"^InstanceNormalization instancenormalization_\d+: the Reshape behind it restores \[0,16,2,8\], not the input's shape \[2,16,4,4\]$"),
+    "gamma_of_another_shape": (lambda: _manual(gamma_dims=[1, 16, 1, 1]), r"^InstanceNormalization instancenormalization_\d+: gamma gamma has the shape \[1,16,1,1\], not \[16,1,1\]$"),
+    "second_reader_of_the_first_reshape": (lambda: _manual(extra_reader="r1"), r"^InstanceNormalization instancenormalization_\d+: the group-norm pattern around it does not match: the intermediate value r1 has 2 readers, not 1$"),
+    "second_reader_of_the_instance_norm": (lambda: _manual(extra_reader="inorm"), r"the intermediate value inorm has 2 readers, not 1$"),
+    "second_reader_before_gamma": (lambda: _manual(extra_reader="r2"), r"the intermediate value r2 has 2 readers, not 1$"),
+    "second_reader_before_beta": (lambda: _manual(extra_reader="m"), r"the intermediate value m has 2 readers, not 1$"),
+    "token_view": (lambda: _on("tokens"), r"^GroupNormalization gn: input transpose_\d+_out is a token view \[N, L, D\]; a group norm reads an NCHW feature map or its \[N, C, H\*W\] reshape$"),
+    "channels_last_view": (lambda: _on("channels_last"), r"^GroupNormalization gn: input transpose_\d+_out is a channels-last view"),
+    "rank_2": (lambda: _on("rank2"), r"^GroupNormalization gn: an input of rank 2 is not supported \(ranks 3 and 4 are\)$"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(REFUSALS))
+def test_refusals(tmp_path, monkeypatch, case):
+    build, match = REFUSALS[case]
+    path = models.write_repo(str(tmp_path), "bad", build())
+    with pytest.raises(RuntimeError, match=match):
+        _describe(path, 2, monkeypatch, "fp32")
+
+
+@pytest.mark.parametrize("form", ["instancenorm", "op21", "instance"])
+def test_fp8_is_refused(tmp_path, monkeypatch, form):
+    path = models.write_repo(str(tmp_path), "f8", G.gn_graph(2, 16, 4, 4, 16 if form == "instance" else 4, form=form))
+    with pytest.raises(RuntimeError, match=r"^GroupNormalization is not supported in fp8 mode \(node gn"):
+        _describe(path, 2, monkeypatch, "fp8")
+
+
+# ---- whole networks --------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def decoder_paths(tmp_path_factory):
+    root = str(tmp_path_factory.mktemp("dec"))
+    return {form: models.write_repo(root, "dec_" + form, G.narrow_decoder("N", gn_form=form)) for form in ("instancenorm", "op18")}
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("form", ["instancenorm", "op18"])
+def test_vae_decoder_plan(decoder_paths, monkeypatch, form, prec):
+    plan = _describe(decoder_paths[form], 2, monkeypatch, prec)
+    steps = plan["steps"]
+    kinds = [s["kind"] for s in steps]
+    layers, nm = G.NARROW["layers"], len(G.NARROW["mults"])
+    blocks = 2 + nm * (layers + 1)
+    # two norms per ResnetBlock, the attention's, conv_norm_out; two convs per block, a shortcut per narrowing up block, an upsample conv behind
+    # every Resize, post_quant_conv, conv_in, conv_out, the merged q / k / v Linear and to_out
+    assert kinds.count("group_norm") == 2 * blocks + 2
+    assert kinds.count("conv") == 2 * blocks + 2 + 3 + 3 + 2
+    assert kinds.count("resize") == nm - 1 and kinds.count("attention") == 1 and kinds.count("copy") == 1
+    # no SiLU is left alone: the only eltwise step is the attention's residual Add
+    elt = [s for s in steps if s["kind"] == "eltwise"]
+    assert len(elt) == 1 and "act" not in elt[0] and "in2" in elt[0]
+    gns = [s for s in steps if s["kind"] == "group_norm"]
+    assert [s["act"][0] for s in gns].count("none") == 1 and all(s["act"][0] in ("silu", "none") for s in gns)
+    assert all(s["groups"] == G.NARROW["groups"] and abs(s["eps"] - 1e-6) < 1e-12 for s in gns)
+    (at,) = [s for s in steps if s["kind"] == "attention"]
+    c = G.NARROW["base"] * G.NARROW["mults"][-1]
+    assert (at["heads"], at["head_dim"], at["tile"]) == (1, c, 0) and abs(at["scale"] - c ** -0.5) < 1e-6 * c ** -0.5
+    # the norm in front of it reads the map's storage as [N, C, 1, L] and is the one without an activation
+    flat = steps[at["idx"] - 2]
+    assert flat["kind"] == "group_norm" and flat["act"][0] == "none" and (flat["in"]["h"], flat["in"]["w"]) == (1, G.NARROW["latent"] ** 2)
+    # every block's Add runs in a conv's epilogue
+    assert sum(bool(s.get("residual")) for s in steps) == blocks
+    rz = [s for s in steps if s["kind"] == "resize"]
+    assert all(s["resize"]["mode"] == "nearest" and s["resize"]["scales"] == [2, 2] for s in rz)
+    out = plan["outputs"][0]
+    assert out["name"] == "sample" and out["dims"] == [2, 3, 8 * G.NARROW["latent"], 8 * G.NARROW["latent"]]
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_resnet50_gn_plan(tmp_path, monkeypatch, prec):
+    plan = _plan_of(tmp_path, "r50gn", models.resnet50_gn("N", image=64, classes=10), monkeypatch, prec, batch=2)
+    steps = plan["steps"]
+    kinds = [s["kind"] for s in steps]
+    assert kinds.count("group_norm") == 53 and kinds.count("conv") == 54 and kinds.count("eltwise") == 16 and kinds.count("gap") == 1
+    gns = [s for s in steps if s["kind"] == "group_norm"]
+    assert all(s["groups"] == 32 for s in gns)
+    assert [s["act"][0] for s in gns].count("relu") == 1 + 2 * 16 and [s["act"][0] for s in gns].count("none") == 16 + 4
+    # no BatchNorm folded anything: every conv is bare, every block's Add (+ ReLU) is one eltwise step
+    convs = [s for s in steps if s["kind"] == "conv"]
+    assert not any(s["relu"] for s in convs) and sum(s["bias"] for s in convs) == 1          # (the classifier's)
+    elt = [s for s in steps if s["kind"] == "eltwise"]
+    assert all("in2" in s for s in elt) and sum(s["relu"] for s in elt) >= 15                # (the last block's ReLU may run in the global pool's prologue)
+
+
+def test_existing_resnet_bytes_are_unchanged():
+    """norm="bn" is the default and writes what it wrote before the option existed"""
+    assert models.resnet(2, width=16, image=64, classes=10) == models.resnet(2, width=16, image=64, classes=10, norm="bn", gn_groups=8)
+    assert models.resnet(2, width=16, image=64, classes=10) != models.resnet(2, width=16, image=64, classes=10, norm="gn", gn_groups=8)
+
+
+# ---- the reference and the data --------------------------------------------------------------------------------------------------------------
+def test_decoder_graph_is_the_decoder():
+    """the float64 walk of the written graph against torch's own operators on the same weights: the graph writer's structure is diffusers'"""
+    z = G.half_exact(np.random.RandomState(5).randn(2, 4, 8, 8))
+    mb = G.narrow_decoder(2)
+    ref = gn_ref.run_f64(mb, {"latent_sample": z})["sample"]
+    assert ref.shape == (2, 3, 64, 64) and np.abs(ref).max() > 0.1
+    assert np.abs(G.decoder_torch_f64(mb, z, **G.NARROW) - ref).max() < 1e-10
+    for form in ("op18", "op21"):          # (their gamma / beta are other draws: only the structure is compared, through the shapes)
+        assert gn_ref.run_f64(G.narrow_decoder(2, gn_form=form), {"latent_sample": z})["sample"].shape == ref.shape
+
+
+def test_group_norm_reference_agrees_with_torch():
+    import torch
+    import torch.nn.functional as F
+    st = np.random.RandomState(3)
+    x, g, b = 3.0 + st.randn(2, 12, 5, 7), st.randn(12), st.randn(12)
+    t = F.group_norm(torch.from_numpy(x), 4, torch.from_numpy(g), torch.from_numpy(b), 1e-5).numpy()
+    assert np.abs(gn_ref.group_norm(x, 4, g, b, 1e-5) - t).max() < 1e-12
+
+
+@pytest.mark.parametrize("shape", [(2, 32, 5, 7, 8), (2, 128, 16, 16, 32), (2, 16, 6, 6, 16)])
+def test_group_distinct_data_tells_broken_statistics_apart(shape):
+    """Statistics over the wrong channel range (the group boundary off by one channel), over the whole image, or shared by the images each move
+    the float64 result by more than 30 x the fp16 bound on the group-distinct data: a kernel that did any of these could not pass."""
+    n, c, h, w, g = shape
+    x = G.data("distinct", n, c, h, w, g)
+    ref = gn_ref.group_norm(x, g)
+    scale = np.abs(ref).max()
+    broken = {"image": gn_ref.group_norm(x, g, stats="image"), "batch": gn_ref.group_norm(x, g, stats="batch")}
+    if c // g > 1:                         # (with one channel per group there is no boundary to move)
+        broken["shift"] = gn_ref.group_norm(x, g, shift=1)
+    for what, y in broken.items():
+        assert np.abs(y - ref).max() / scale > 30 * RTOL16, (what, np.abs(y - ref).max() / scale)
