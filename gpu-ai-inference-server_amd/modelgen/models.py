@@ -1118,7 +1118,7 @@ def bert(batch: int | str = 1, *, seq: int = 128, vocab: int = 30522, dim: int =
          mask: bool = True, pooler_output: bool = False, table_std: float = 1.0) -> bytes:
     """BertForSequenceClassification (post-LN encoder, Devlin et al. 2019) written from modeling_bert.py's eager attention and the TorchScript
     exporter's known lowerings at opset 17, as Swin's graph was: neither `transformers` nor ONNX Runtime is available to export or to run one, so the
-    graph is this restatement, checked by two independent float64 evaluations (tests/bert_ref.py, tests/test_bert_plan.py).
+    graph is this restatement, checked by two independent float64 evaluations (tests/ref64.py, tests/test_bert_plan.py).
     inputs input_ids, attention_mask, token_type_ids [N, seq] INT64; outputs logits [N, classes] and optionally pooler_output [N, dim]."""
     gb = GraphBuilder("bert", seed)
     x = bert_embeddings(gb, seq, vocab, dim, types=types, max_pos=max_pos, pos=pos, order=order, eps=eps, table_std=table_std)

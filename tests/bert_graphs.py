@@ -1,8 +1,11 @@
 """Test graphs shared by the BERT plan and GPU tests, and what the tests know about the embed kernel's tiles."""
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
+import ref64
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
 
@@ -93,3 +96,92 @@ def masked_attn_graph(n: int, l: int, heads: int, hd: int, *, mask_value="min", 
 def narrow_bert(batch=3, **kw) -> bytes:
     """dim 64, 2 heads of 32, 2 layers, seq 40, vocab 50; logits and pooler_output"""
     return models.bert(batch, **dict(dict(seq=40, vocab=50, dim=64, depth=2, heads=2, mlp=128, max_pos=64, pooler_output=True), **kw))
+
+
+@functools.lru_cache(maxsize=None)
+def narrow_feeds():
+    """three rows of ids / mask / types for narrow_bert (lengths 40 / 17 / 1); shared, read-only by convention"""
+    st = np.random.RandomState(7)
+    ids = st.randint(0, 50, size=(3, 40)).astype(np.int64)
+    tt = (st.rand(3, 40) < 0.5).astype(np.int64)
+    mask = np.zeros((3, 40), np.int64)
+    for n, ln in enumerate((40, 17, 1)):
+        mask[n, :ln] = 1
+    return {"input_ids": ids, "attention_mask": mask, "token_type_ids": tt}
+
+
+# ---- data of the embed and key-masked attention tests, with their float64 references (computed once, read-only) ----------------------------------
+TABLE_MEANS = {"randn": 0.0, "offset": 100.0}
+MASKED_KINDS = ("randn", "peaked")
+MASK_VALUES = ("min", -10000.0)
+
+
+def make_ids(n, l, v, types=2):
+    """ids with 0, V - 1, -1, -V and a repeat; type ids that use both rows"""
+    st = np.random.RandomState(100 * l + v)
+    ids = st.randint(0, v, size=(n, l)).astype(np.int64)
+    special = [0, v - 1, -1, -v, v - 1]
+    ids.ravel()[:min(len(special), ids.size)] = special[:ids.size]
+    tt = (np.arange(n * l).reshape(n, l) % max(types, 1)).astype(np.int64)
+    return ids, tt
+
+
+def embed_feeds(ids, tt, types):
+    return {"input_ids": ids, **({"token_type_ids": tt} if types else {})}
+
+
+@functools.lru_cache(maxsize=None)
+def embed_graph_and_reference(n, l, v, d, kind, types, pos):
+    mb = embed_graph(n, l, v, d, types=types, pos=pos, table_mean=TABLE_MEANS[kind])
+    ids, tt = make_ids(n, l, v, types)
+    ref = ref64.run_f64(mb, embed_feeds(ids, tt, types))["y"]
+    ref.setflags(write=False)
+    return mb, ref
+
+
+def mask_rows(l):
+    """the eight mask rows of the test, [8, l]"""
+    rows = []
+    for ln in (1, 31, 32, 33, l):
+        r = np.zeros(l, np.int64)
+        r[:min(ln, l)] = 1
+        rows.append(r)
+    hole = np.ones(l, np.int64)
+    hole[l // 3: max(l // 3 + 1, 2 * l // 3)] = 0
+    return np.stack(rows + [hole, np.zeros(l, np.int64), np.ones(l, np.int64)])
+
+
+def mask_requests(n, l):
+    """the mask rows dealt over mask_requests of n images: [mask_requests, n, l], and per request the index of each image's mask row"""
+    rows = mask_rows(l)
+    idx = np.arange(8).reshape(8 // n, n)
+    return rows[idx], idx
+
+
+@functools.lru_cache(maxsize=None)
+def masked_input(n, l, h, hd, kind, row):
+    """x [n, 3 D, 1, l] for the images whose mask rows are `row` (a tuple): hidden keys are multiples of the all-ones vector"""
+    st = np.random.RandomState(1000 * l + 10 * hd + h + len(kind))
+    half = lambda a: a.astype(np.float16).astype(np.float32)  # noqa: E731
+    v = half(st.randn(n, h, l, hd))
+    if kind == "randn":
+        q, k, big = half(st.randn(n, h, l, hd) + 0.5), half(st.randn(n, h, l, hd)), 2.0
+    else:
+        k = st.randint(-2, 3, size=(n, h, l, hd)).astype(np.float32)
+        q, big = 16.0 * k + 16.0, 4.0
+    rows = mask_rows(l)
+    for i, r in enumerate(row):
+        if rows[r].any():                              # (a fully masked image keeps its keys: nothing is hidden from anything)
+            k[i][:, rows[r] == 0, :] = big
+    x = np.stack([q, k, v], 0).transpose(1, 0, 2, 4, 3).reshape(n, 3 * h * hd, 1, l)
+    x = np.ascontiguousarray(x, np.float32)
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def masked_reference(n, l, h, hd, kind, c, row, masked=True):
+    m = mask_rows(l)[list(row)] if masked else np.ones((n, l), np.int64)
+    ref = ref64.run_f64(masked_attn_graph(n, l, h, hd, mask_value=c), {"x": masked_input(n, l, h, hd, kind, row), "attention_mask": m})["y"]
+    ref.setflags(write=False)
+    return ref

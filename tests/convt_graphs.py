@@ -9,7 +9,7 @@ import numpy as np
 
 import kernel_graphs as G
 import kernel_ref as R
-import unet_ref
+import ref64
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
 
@@ -59,7 +59,7 @@ def random_graph(cfg, batch=2):
         y = gb.concat([gb.conv_transpose(u, cin, 8, cfg["k"], cfg["s"], cfg["pads"], cfg["op"], bias=True, name="side"), y])
         ctot += 8
     gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
-    oh, ow = unet_ref.convt_out_hw(cfg["h"], cfg["w"], cfg["k"], cfg["s"], cfg["pads"], cfg["op"])
+    oh, ow = ref64.convt_out_hw(cfg["h"], cfg["w"], cfg["k"], cfg["s"], cfg["pads"], cfg["op"])
     return gb.finish([("x", list(ishape))], [("y", [batch, ctot, oh, ow])]), ishape, (batch, ctot, oh, ow)
 
 
@@ -97,7 +97,7 @@ def map_case(seed, n, h, w, cin, cout, k, stride, pads=(0, 0, 0, 0), op=(0, 0), 
     if post in (1, 2):
         nodes.append(pb.node("Relu", [y], ["y2"], "postrelu"))
         y = "y2"
-    oh, ow = unet_ref.convt_out_hw(h, w, k, stride, pads, op)
+    oh, ow = ref64.convt_out_hw(h, w, k, stride, pads, op)
     nodes.append(pb.node("Concat", [y, y], ["out"], "cat", [pb.attr_int("axis", 1)]))
     g = pb.graph(f"tcase{seed}", nodes, inits, [pb.value_info("x", [n, 3, h, w])], [pb.value_info("out", [n, 2 * cout, oh, ow])])
     d.update(model=pb.model(g), ishape=(n, 3, h, w), oshape=(n, 2 * cout, oh, ow), oh=oh, ow=ow)
@@ -105,7 +105,7 @@ def map_case(seed, n, h, w, cin, cout, k, stride, pads=(0, 0, 0, 0), op=(0, 0), 
 
 
 def map_operands(d, x=None, half_weights=False):
-    """(cols [M, K], wm [Cout, K], bias or None, relu, rounded_operands) of case `d` in the im2col form (unet_ref.convt_im2col), as the kernel is
+    """(cols [M, K], wm [Cout, K], bias or None, relu, rounded_operands) of case `d` in the im2col form (convt_im2col), as the kernel is
     given them: the BN folded into weights and bias in float32 as the planner does it.  x: another input on the same grid (default d["x"]).
     half_weights: the kernel reads the half mirror of the weights, so the step rounds w' to half itself unless it is representable already."""
     xh = G.lifted(d["x"] if x is None else x, d["w0"])
@@ -117,5 +117,25 @@ def map_operands(d, x=None, half_weights=False):
         b0 = np.zeros(d["cout"], f32) if b is None else b
         b = ((b0 * s).astype(f32) + t).astype(f32)
     rounded = 1 if half_weights and not np.array_equal(R.half_exact(wt), wt) else 0
-    cols, wm, _ = unet_ref.convt_im2col(xh, wt, d["stride"], d["pads"], d["op"])
+    cols, wm, _ = convt_im2col(xh, wt, d["stride"], d["pads"], d["op"])
     return cols, wm, b, d["post"] in (1, 2), rounded
+
+
+def convt_im2col(x, w, strides=(1, 1), pads=(0, 0, 0, 0), output_padding=(0, 0)):
+    """The same op as an ordinary stride-1 convolution: kernel_ref.im2col of the zero-stuffed input (s - 1 zeros between neighbours) with pads
+    k - 1 - p (plus output_padding at the bottom / right) against the spatially flipped, channel-swapped weights.  Needs pads < k.
+    -> (cols [M, K], wm [Cout, K], (N, OH, OW)) in x's and w's dtypes."""
+    x, w = np.asarray(x), np.asarray(w)
+    n, cin, h, wd = x.shape
+    _, cout, kh, kw = w.shape
+    sh, sw = strides
+    assert pads[0] < kh and pads[2] < kh and pads[1] < kw and pads[3] < kw
+    xs = np.zeros((n, cin, (h - 1) * sh + 1, (wd - 1) * sw + 1), x.dtype)
+    xs[:, :, ::sh, ::sw] = x
+    ip = (kh - 1 - pads[0], kw - 1 - pads[1], kh - 1 - pads[2] + output_padding[0], kw - 1 - pads[3] + output_padding[1])
+    # kernel_ref.im2col takes one kernel extent per axis and one stride
+    cols = R.im2col(xs, kh, kw, 1, ip)
+    wf = np.ascontiguousarray(w[:, :, ::-1, ::-1].transpose(1, 0, 2, 3))          # [Cout, Cin, kh, kw], flipped
+    oh, ow = ref64.convt_out_hw(h, wd, (kh, kw), strides, pads, output_padding)
+    assert cols.shape[:3] == (n, oh, ow), (cols.shape, (n, oh, ow))
+    return cols.reshape(-1, kh * kw * cin), R.wmat(wf), (n, oh, ow)

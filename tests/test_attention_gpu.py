@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the attention kernels on the MI355X against the float64 walk of tests/vit_ref.py, with the project's bounds
+"""GPU (-m gpu): the attention kernels on the MI355X against the float64 walk of tests/ref64.py, with the project's bounds
 (tests/test_gpu_parity.py): fp32 within 2e-4 of max|ref|, fp16 within 3e-3.
 
 Graph: x [N, 3 D, 1, L] -> Reshape [N, 3 D, L] -> Transpose [0,2,1] -> the attention pattern -> Transpose [0,2,1] -> Reshape [N, D, 1, L] -> y, so the
@@ -12,81 +12,27 @@ Data: randn; peaked (integer k in [-2, 2], q = 16 k: scores of several hundred, 
 (score of key j = j, resp. j / 16, for hd = 64: the running maximum grows in every key tile, by 32 or by 2, so the online rescale always fires and,
 with the slow ramp, every tile still contributes)."""
 import functools
-import os
 
 import numpy as np
 import pytest
 
 import vit_graphs as G
-import vit_ref
-from gpu_ai_inference_server_amd import binding as B
+import ref64
+from engine_run import plan_of, RTOL, run_model
 from gpu_ai_inference_server_amd.modelgen import models
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
 KINDS = ("randn", "peaked", "ramp", "ramp16")
 LMAX = {prec: G.max_mfma_tokens(64, prec == "fp16") for prec in RTOL}
 SHAPES = [(2, 5, 1, 32), (2, 32, 2, 64), (2, 33, 3, 64), (1, 50, 2, 32), (1, 129, 2, 64), (2, 197, 3, 64), (2, 7, 2, 20)]
 
 
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def pack(q, k, v):
-    """q, k, v [N, H, L, hd] -> x [N, 3 D, 1, L]: channel s * D + h * hd + e of token j is element e of head h of q / k / v"""
-    n, h, l, hd = q.shape
-    x = np.stack([q, k, v], 0).transpose(1, 0, 2, 4, 3).reshape(n, 3 * h * hd, 1, l)
-    return np.ascontiguousarray(x, np.float32)
-
-
-@functools.lru_cache(maxsize=None)
-def make_input(n, l, h, hd, kind):
-    st = np.random.RandomState(1000 * l + 10 * hd + h + len(kind))
-    half = lambda a: a.astype(np.float16).astype(np.float32)  # noqa: E731
-    v = half(st.randn(n, h, l, hd))
-    if kind == "randn":
-        q, k = st.randn(n, h, l, hd), st.randn(n, h, l, hd)
-    elif kind == "peaked":
-        k = st.randint(-2, 3, size=(n, h, l, hd)).astype(np.float64)
-        q = 16.0 * k
-    else:
-        u = np.where(st.rand(n, h, 1, hd) < 0.5, -1.0, 1.0)
-        step = 1.0 / 8.0 if kind == "ramp" else 1.0 / 128.0
-        q = np.broadcast_to(u, (n, h, l, hd))
-        k = u * (np.arange(l, dtype=np.float64) * step).reshape(1, 1, l, 1)
-    x = pack(np.asarray(q, np.float32), np.asarray(k, np.float32), v)
-    x.setflags(write=False)
-    return x
-
-
 @functools.lru_cache(maxsize=None)
 def reference(n, l, h, hd, kind):
     """the float64 walk of the graph (the spelling does not matter to it: tests/test_vit_plan.py), computed once per input"""
-    ref = vit_ref.run_f64(G.attn_graph(n, l, h, hd), {"x": make_input(n, l, h, hd, kind)})["y"]
+    ref = ref64.run_f64(G.attn_graph(n, l, h, hd), {"x": G.make_input(n, l, h, hd, kind)})["y"]
     ref.setflags(write=False)
     return ref
-
-
-def _run(path, name, env, x, oshape):
-    """-> (output, {step kind-ish name: launched kernel})"""
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            r = m.Infer([B.TensorData("x", B.DataTypeFloat32, B.Shape(list(x.shape)), x)], [B.OutputConfig("y", Shape=list(oshape), DataType="FLOAT32")])
-            return r[0].Data.reshape(oshape), [p["kernel"] for p in B.Profile(m, 1)]
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
 
 
 def _every_tile(path, name, prec, x, oshape, hd, check, expect_mfma=None):
@@ -94,12 +40,12 @@ def _every_tile(path, name, prec, x, oshape, hd, check, expect_mfma=None):
     ran = []
     for forced in (None, 0, 1):
         env = dict(IE_PRECISION=prec, **({} if forced is None else {"IE_FORCE_TILE": str(forced)}))
-        steps = _with_env(env, lambda: B.DescribeModel(path, x.shape[0])["plan"])["steps"]
+        steps = plan_of(path, x.shape[0], env)["steps"]
         (at,) = [s for s in steps if s["kind"] == "attention"]
         if forced is not None and at["tile"] != forced:
             assert at["tile"] == 0                      # not eligible: the generic kernel, which forced tile 0 runs
             continue
-        y, kern = _run(path, name, env, x, oshape)
+        y, kern = run_model(path, name, env, {"x": x}, "y", oshape)
         (label,) = [k for k in kern if k.startswith("attention_")]
         assert label == G.attn_label(at["tile"], at["out"]["f16"], hd), (forced, at["tile"], label)
         assert kern.count("copy_kernel") == 2 and len(kern) == len(steps), kern          # the NCHW graph input and output only
@@ -114,11 +60,11 @@ def _every_tile(path, name, prec, x, oshape, hd, check, expect_mfma=None):
 def _case(tmp_path, n, l, h, hd, kind, prec, **graph_kw):
     mb = G.attn_graph(n, l, h, hd, **graph_kw)
     path = models.write_repo(str(tmp_path), "attn", mb)
-    x, ref = make_input(n, l, h, hd, kind), reference(n, l, h, hd, kind)
+    x, ref = G.make_input(n, l, h, hd, kind), reference(n, l, h, hd, kind)
 
     def check(y, tile, forced):
         assert np.isfinite(y).all(), (kind, tile)
-        err = vit_ref.rel_err(y, ref)
+        err = ref64.rel_err(y, ref)
         print(f"N {n} L {l} H {h} hd {hd} {kind} {prec} {graph_kw or ''} forced {forced} tile {tile}: max err / max|ref| {err:.3e}")
         assert err < RTOL[prec], (n, l, h, hd, kind, prec, tile, err)
 
@@ -142,10 +88,10 @@ def test_attention_at_the_lds_budget(tmp_path, past, kind, prec):
 
 
 def test_peaked_scores_are_as_large_as_claimed():
-    x = make_input(2, 197, 3, 64, "peaked").astype(np.float64)[:, :, 0, :].transpose(0, 2, 1).reshape(2, 197, 3, 3, 64)
+    x = G.make_input(2, 197, 3, 64, "peaked").astype(np.float64)[:, :, 0, :].transpose(0, 2, 1).reshape(2, 197, 3, 3, 64)
     s = np.einsum("nlhe,nmhe->nhlm", x[:, :, 0], x[:, :, 1]) / 8.0
     assert 200 < np.abs(s).max() < 400
-    r = make_input(1, 129, 2, 64, "ramp").astype(np.float64)[:, :, 0, :].transpose(0, 2, 1).reshape(1, 129, 3, 2, 64)
+    r = G.make_input(1, 129, 2, 64, "ramp").astype(np.float64)[:, :, 0, :].transpose(0, 2, 1).reshape(1, 129, 3, 2, 64)
     s = np.einsum("nlhe,nmhe->nhlm", r[:, :, 0], r[:, :, 1]) / 8.0
     np.testing.assert_array_equal(s[0, 0, 5], np.arange(129.0))          # the score of key j is exactly j
 
@@ -167,12 +113,12 @@ def test_split_unbind(tmp_path, prec):
 def test_batch_independence(tmp_path, tile, prec):
     """image 1 of an N = 2 run equals the N = 1 run of that image"""
     n, l, h, hd = 2, 50, 2, 32
-    x = np.array(make_input(n, l, h, hd, "randn"))
+    x = np.array(G.make_input(n, l, h, hd, "randn"))
     env = dict(IE_PRECISION=prec, IE_FORCE_TILE=str(tile))
-    y2, _ = _run(models.write_repo(str(tmp_path), "a2", G.attn_graph(2, l, h, hd)), "a2", env, x, (2, h * hd, 1, l))
-    y1, _ = _run(models.write_repo(str(tmp_path), "a1", G.attn_graph(1, l, h, hd)), "a1", env, x[1:], (1, h * hd, 1, l))
-    assert vit_ref.rel_err(y2[1], y1[0]) < RTOL[prec]
-    assert vit_ref.rel_err(y2, reference(n, l, h, hd, "randn")) < RTOL[prec]
+    y2, _ = run_model(models.write_repo(str(tmp_path), "a2", G.attn_graph(2, l, h, hd)), "a2", env, {"x": x}, "y", (2, h * hd, 1, l))
+    y1, _ = run_model(models.write_repo(str(tmp_path), "a1", G.attn_graph(1, l, h, hd)), "a1", env, {"x": x[1:]}, "y", (1, h * hd, 1, l))
+    assert ref64.rel_err(y2[1], y1[0]) < RTOL[prec]
+    assert ref64.rel_err(y2, reference(n, l, h, hd, "randn")) < RTOL[prec]
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
@@ -182,14 +128,14 @@ def test_qkv_from_a_linear(tmp_path, prec):
     mb = G.attn_graph(n, l, h, hd, linear=True)
     path = models.write_repo(str(tmp_path), "lin", mb)
     x = np.random.RandomState(4).randn(n, h * hd, 1, l).astype(np.float32)
-    ref = vit_ref.run_f64(mb, {"x": x})["y"]
+    ref = ref64.run_f64(mb, {"x": x})["y"]
     for tile in (0, 1):
         env = dict(IE_PRECISION=prec, IE_FORCE_TILE=str(tile))
-        steps = _with_env(env, lambda: B.DescribeModel(path, n)["plan"])["steps"]
+        steps = plan_of(path, n, env)["steps"]
         assert [s["kind"] for s in steps] == ["conv", "attention", "copy"]             # (the conv reads the NCHW input itself)
         at = steps[1]
         assert at["tile"] == tile and (at["in"]["buf"], at["in"]["pitch"], at["in"]["c"]) == (steps[0]["out"]["buf"], 3 * h * hd, 3 * h * hd)
-        y, kern = _run(path, "lin", env, x, (n, h * hd, 1, l))
-        err = vit_ref.rel_err(y, ref)
+        y, kern = run_model(path, "lin", env, {"x": x}, "y", (n, h * hd, 1, l))
+        err = ref64.rel_err(y, ref)
         print(f"qkv from a Linear {prec} tile {tile}: max err / max|ref| {err:.3e}; {kern}")
         assert err < RTOL[prec] and G.attn_label(tile, prec == "fp16", hd) in kern

@@ -1,37 +1,23 @@
-"""GPU (-m gpu): whole BERT encoders (modelgen.models.bert) on the MI355X against the float64 walk of tests/bert_ref.py, with the project's bounds
+"""GPU (-m gpu): whole BERT encoders (modelgen.models.bert) on the MI355X against the float64 walk of tests/ref64.py, with the project's bounds
 (tests/test_gpu_parity.py): fp32 within 2e-4 of max|ref|, fp16 within 3e-3, for `logits` and `pooler_output`.
 
 The narrow net: dim 64, 2 heads of 32, 2 layers, seq 40, vocab 50; batch 3 with lengths 40 / 17 / 1.  Graph replay is bit-equal to the eager run;
 bert_tiny (dim 128, 2 heads of 64, seq 128, vocab 30522) runs once in fp32; with dynamic batching three concurrent callers of 1 / 2 / 3 rows each get
 their own rows -- the batcher's padding rows are id 0 with mask 0, fully masked images that must not disturb them."""
-import os
 import threading
 
 import numpy as np
 import pytest
 
 import bert_graphs as G
-import bert_ref
+import ref64
+from engine_run import RTOL, with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
 SEQ, VOCAB, DIM = 40, 50, 64
 NAMES = ("input_ids", "attention_mask", "token_type_ids")
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def make_feeds(n, seq, vocab, lengths, seed=7):
@@ -50,7 +36,7 @@ def narrow(tmp_path_factory):
     root = str(tmp_path_factory.mktemp("bert"))
     path = models.write_repo(root, "bert", G.narrow_bert("N"))
     feeds = make_feeds(6, SEQ, VOCAB, (40, 17, 1, 33, 8, 40))
-    ref = bert_ref.run_f64(G.narrow_bert(6), feeds)
+    ref = ref64.run_f64(G.narrow_bert(6), feeds)
     for a in list(feeds.values()) + list(ref.values()):
         a.setflags(write=False)
     return path, feeds, ref
@@ -78,10 +64,10 @@ def test_narrow_net(narrow, prec):
         assert kern[0] == G.embed_label(G.embed_default_tile(DIM, prec == "fp16"), prec == "fp16") and kern.count(f"attention_mfma_kernel<{t},32,mask>") == 2, kern
         for k in ("logits", "pooler_output"):
             assert np.isfinite(y[k]).all()
-            err = bert_ref.rel_err(y[k], ref[k][:3])
+            err = ref64.rel_err(y[k], ref[k][:3])
             print(f"narrow BERT {prec} {k}: max err / max|ref| {err:.3e}")
             assert err < RTOL[prec], (k, err)
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION=prec), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION=prec), go)
 
 
 def test_replay_is_bit_equal(narrow):
@@ -102,14 +88,14 @@ def test_replay_is_bit_equal(narrow):
             np.testing.assert_array_equal(p, y_host["pooler_output"])
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
 
 
 def test_bert_tiny(tmp_path):
     mb = models.bert_tiny(2, pooler_output=True)
     path = models.write_repo(str(tmp_path), "tiny", mb)
     feeds = make_feeds(2, 128, 30522, (128, 45), seed=9)
-    ref = bert_ref.run_f64(mb, feeds)
+    ref = ref64.run_f64(mb, feeds)
 
     def go():
         m = B.CreateModel(path, "tiny")
@@ -120,10 +106,10 @@ def test_bert_tiny(tmp_path):
             m.Destroy()
         assert kern.count("attention_mfma_kernel<f32,64,mask>") == 2 and kern[0].startswith("embed_ln_kernel<f32,"), kern
         for k in ("logits", "pooler_output"):
-            err = bert_ref.rel_err(y[k], ref[k])
+            err = ref64.rel_err(y[k], ref[k])
             print(f"bert_tiny fp32 {k}: max err / max|ref| {err:.3e}")
             assert err < RTOL["fp32"], (k, err)
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
 
 
 def test_three_concurrent_callers(narrow):
@@ -151,7 +137,7 @@ def test_three_concurrent_callers(narrow):
             for lo, hi in spans:
                 for k in ("logits", "pooler_output"):
                     assert np.isfinite(out[lo][k]).all()
-                    assert bert_ref.rel_err(out[lo][k], ref[k][lo:hi]) < RTOL["fp32"], (lo, hi, k)
+                    assert ref64.rel_err(out[lo][k], ref[k][lo:hi]) < RTOL["fp32"], (lo, hi, k)
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32", IE_DYNAMIC_BATCH="8", IE_BATCH_WINDOW_US="200000"), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32", IE_DYNAMIC_BATCH="8", IE_BATCH_WINDOW_US="200000"), go)

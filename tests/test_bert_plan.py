@@ -4,42 +4,31 @@
   LayerNormalization behind it are ONE embed step in every spelling, the same plan modulo names; the tables sit in the weight blob as the graph holds them
 * INT64 inputs in DescribeModel: element type 7, 8-byte buffers, the memory estimate
 * every near miss is refused by name, and the refusals older tests pin still fire
-* modelgen.models.bert: the float64 walk of the graph (tests/bert_ref.py) agrees with an independent torch restatement of the model to 1e-10, and the
+* modelgen.models.bert: the float64 walk of the graph (tests/ref64.py) agrees with an independent torch restatement of the model to 1e-10, and the
   type table, the position rows and the mask each move the narrow net's logits by more than 5 %
 * whole encoders: bert_base is 1 embed + 12 x 8 steps + head without a copy; the three q / k / v Linears are ONE qkv conv whose blob is the concatenation
   of the graph's matrices; every spelling (Unsqueeze forms, k-transpose forms, Div / Mul scale, Add operand order, position forms) is the same plan; near
   misses of the q / k / v Linears are refused by name, every other additive mask with the text the ViT tests pin
 """
-import functools
-
 import numpy as np
 import pytest
 
 import bert_graphs as G
-import bert_ref
-import test_embed_gpu as EG
-import test_masked_attention_gpu as MA
+import ref64
+from engine_run import describe_model, RTOL
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
+from oracle import onnx_oracle as O
 
 PRECS = ("fp32", "fp16")
 N, L, V, D = 2, 5, 37, 8
 
 
-def _describe(path, batch, monkeypatch, prec="fp32", **env):
-    monkeypatch.setenv("IE_PRECISION", prec)
-    for k in ("IE_FORCE_TILE", "IE_FORCE_ALGO", "IE_FORCE_SPLITK"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    return B.DescribeModel(path, batch)
-
-
 def _refused(tmp_path, monkeypatch, mb, text, prec="fp32", batch=N):
     path = models.write_repo(str(tmp_path), "bad", mb)
     with pytest.raises(RuntimeError) as e:
-        _describe(path, batch, monkeypatch, prec)
+        describe_model(path, batch, monkeypatch, prec)
     assert text in str(e.value), str(e.value)
 
 
@@ -51,7 +40,7 @@ def _nameless(step):
 @pytest.mark.parametrize("prec", PRECS)
 def test_embed_plan(tmp_path, monkeypatch, prec):
     path = models.write_repo(str(tmp_path), "embed", G.embed_graph(N, L, V, D))
-    d = _describe(path, N, monkeypatch, prec)
+    d = describe_model(path, N, monkeypatch, prec)
     steps = d["plan"]["steps"]
     assert [s["kind"] for s in steps] == ["embed", "copy"]
     em = steps[0]
@@ -65,7 +54,7 @@ def test_embed_plan(tmp_path, monkeypatch, prec):
     assert em["flops"] == 8 * N * L * D
     assert em["bytes"] == N * L * (3 * 4 * D + 2 * 8) + N * L * D * (2 if f16 else 4)          # three fp32 rows and two ids read, the row written once
     # the tables, the position rows, gamma and beta: fp32 in the blob in both precisions, as the graph holds them
-    m = bert_ref.O.load_model(G.embed_graph(N, L, V, D))
+    m = O.load_model(G.embed_graph(N, L, V, D))
     w = B.PlanWeights(path, N)
     blob = lambda off, name: np.testing.assert_array_equal(w[off:off + m.inits[name].size], np.asarray(m.inits[name], np.float32).ravel())  # noqa: E731
     blob(em["w_off"], "word_embeddings")
@@ -81,7 +70,7 @@ def test_every_spelling_is_the_same_plan(tmp_path, monkeypatch, prec):
     plans, blobs = [], []
     for i, kw in enumerate([dict(), dict(order="wpt"), dict(order="ptw"), dict(pos="gather"), dict(pos="gather", order="ptw")]):
         path = models.write_repo(str(tmp_path), f"e{i}", G.embed_graph(N, L, V, D, **kw))
-        plans.append([_nameless(s) for s in _describe(path, N, monkeypatch, prec)["plan"]["steps"]])
+        plans.append([_nameless(s) for s in describe_model(path, N, monkeypatch, prec)["plan"]["steps"]])
         blobs.append(B.PlanWeights(path, N))
     for p, w in zip(plans[1:], blobs[1:]):
         assert p == plans[0]
@@ -90,7 +79,7 @@ def test_every_spelling_is_the_same_plan(tmp_path, monkeypatch, prec):
 
 def test_embed_without_type_table_or_positions(tmp_path, monkeypatch):
     path = models.write_repo(str(tmp_path), "embed", G.embed_graph(N, L, V, D, types=0, pos=None))
-    em = _describe(path, N, monkeypatch)["plan"]["steps"][0]
+    em = describe_model(path, N, monkeypatch)["plan"]["steps"][0]
     assert em["kind"] == "embed" and "in2" not in em and em["tables"] == 1 and em["vocab"] == [V] and em["w2_off"] == -1 and em["pos_off"] == -1
     assert em["bytes"] == N * L * (4 * D + 8) + N * L * D * 4
 
@@ -99,13 +88,13 @@ def test_embed_without_type_table_or_positions(tmp_path, monkeypatch):
 def test_forced_embed_tiles(tmp_path, monkeypatch, d, f16, forced, tile):
     """IE_FORCE_TILE picks the lane group where kernels.h EmbedTileFits allows it, else the generic kernel"""
     path = models.write_repo(str(tmp_path), "embed", G.embed_graph(1, 3, 5, d))
-    em = _describe(path, 1, monkeypatch, "fp16" if f16 else "fp32", IE_FORCE_TILE=str(forced))["plan"]["steps"][0]
+    em = describe_model(path, 1, monkeypatch, "fp16" if f16 else "fp32", IE_FORCE_TILE=str(forced))["plan"]["steps"][0]
     assert em["tile"] == tile == (forced if forced == 0 or G.embed_tile_fits(d, f16, forced) else 0)
 
 
 def test_int64_inputs_in_describe_model(tmp_path, monkeypatch):
     path = models.write_repo(str(tmp_path), "embed", G.embed_graph("N", L, V, D))
-    d = _describe(path, 3, monkeypatch)
+    d = describe_model(path, 3, monkeypatch)
     assert d["inputs"] == [{"name": "input_ids", "elem_type": 7, "dims": [-1, L]}, {"name": "token_type_ids", "elem_type": 7, "dims": [-1, L]}]
     assert d["outputs"][0]["elem_type"] == 1
     # the reference's estimate: the I/O tensors over their positive dims (8-byte ids) + 10 MiB
@@ -221,7 +210,7 @@ def _check_encoder(steps, depth, dim, heads, mlp, n, seq, f16, c):
 def test_bert_base_plan(tmp_path, monkeypatch, prec):
     """1 embed + 12 x (qkv conv, attention with key_mask, proj conv + residual, LN, fc1, GELU, fc2 + residual, LN) + head; no copy step (logits is the last conv's output)"""
     path = models.write_repo(str(tmp_path), "bert", models.bert_base(2, vocab=1000))          # (the plan does not depend on the vocabulary; 30522 rows are 94 MB)
-    steps = _describe(path, 2, monkeypatch, prec)["plan"]["steps"]
+    steps = describe_model(path, 2, monkeypatch, prec)["plan"]["steps"]
     assert "copy" not in [s["kind"] for s in steps]
     _check_encoder(steps, 12, 768, 12, 3072, 2, 128, prec == "fp16", float(np.finfo(np.float32).min))
     assert steps[0]["tile"] == (3 if prec == "fp16" else 4) and steps[0]["vocab"] == [1000, 2]
@@ -234,7 +223,7 @@ VARIANTS = [dict(unsqueeze="one"), dict(ktrans="one"), dict(scale="mul"), dict(m
 def test_every_encoder_spelling_is_the_same_plan(tmp_path, monkeypatch, prec):
     def plan(i, **kw):
         path = models.write_repo(str(tmp_path), f"b{i}", NARROW(**kw))
-        return [_nameless(s) for s in _describe(path, 3, monkeypatch, prec)["plan"]["steps"]], B.PlanWeights(path, 3)
+        return [_nameless(s) for s in describe_model(path, 3, monkeypatch, prec)["plan"]["steps"]], B.PlanWeights(path, 3)
     base, blob = plan(0)
     _check_encoder(base[:-1], 2, 64, 2, 128, 3, 40, prec == "fp16", float(np.finfo(np.float32).min))
     assert base[-1]["kind"] == "copy"                   # pooler_output is read by the classifier too: it is copied to its own output buffer
@@ -254,8 +243,8 @@ def test_every_encoder_spelling_is_the_same_plan(tmp_path, monkeypatch, prec):
 def test_merged_qkv_weights_are_the_concatenation(tmp_path, monkeypatch):
     mb = NARROW()
     path = models.write_repo(str(tmp_path), "bert", mb)
-    steps = _describe(path, 3, monkeypatch)["plan"]["steps"]
-    m = bert_ref.O.load_model(mb)
+    steps = describe_model(path, 3, monkeypatch)["plan"]["steps"]
+    m = O.load_model(mb)
     w = B.PlanWeights(path, 3)
     for li in range(2):
         qkv = steps[1 + 8 * li]
@@ -327,11 +316,11 @@ def test_left_over_chain_ops_stay_unsupported(tmp_path, monkeypatch):
         mb = gb.finish([("x", [2, 3, 4, 4])], [("y", [2, 8, 4, 4])], opset=17)
         path = models.write_repo(str(tmp_path), "left" + op, mb)
         if op == "Tanh":
-            steps = _describe(path, 2, monkeypatch)["plan"]["steps"]
+            steps = describe_model(path, 2, monkeypatch)["plan"]["steps"]
             assert any(s.get("act", [None])[0] == "tanh" for s in steps)
         else:
             with pytest.raises(RuntimeError, match="Unsupported ONNX operator: Cast"):
-                _describe(path, 2, monkeypatch)
+                describe_model(path, 2, monkeypatch)
 
 
 # ---- the graph writer ------------------------------------------------------------------------------------------------------------------------
@@ -339,22 +328,11 @@ def NARROW(**kw):
     return models.bert(3, **dict(dict(seq=40, vocab=50, dim=64, depth=2, heads=2, mlp=128, max_pos=64, pooler_output=True), **kw))
 
 
-@functools.lru_cache(maxsize=None)
-def narrow_feeds():
-    st = np.random.RandomState(7)
-    ids = st.randint(0, 50, size=(3, 40)).astype(np.int64)
-    tt = (st.rand(3, 40) < 0.5).astype(np.int64)
-    mask = np.zeros((3, 40), np.int64)
-    for n, ln in enumerate((40, 17, 1)):
-        mask[n, :ln] = 1
-    return {"input_ids": ids, "attention_mask": mask, "token_type_ids": tt}
-
-
 def torch_bert(mb, feeds, c):
     """the same model restated with torch (float64, CPU): nn.Embedding, F.layer_norm, softmax, the graph's own weights"""
     import torch
     import torch.nn.functional as F
-    m = bert_ref.O.load_model(mb)
+    m = O.load_model(mb)
     W = {k: torch.from_numpy(np.asarray(v, np.float64)) for k, v in m.inits.items() if np.asarray(v).dtype.kind == "f"}
     ids, tt, mask = (torch.from_numpy(feeds[k]) for k in ("input_ids", "token_type_ids", "attention_mask"))
     dim, heads, eps = W["word_embeddings"].shape[1], 2, 1e-12
@@ -383,25 +361,25 @@ def torch_bert(mb, feeds, c):
 @pytest.mark.parametrize("mask_value", ["min", -10000.0])
 def test_walk_agrees_with_torch(mask_value):
     mb = NARROW(mask_value=mask_value)
-    ref = bert_ref.run_f64(mb, narrow_feeds())
+    ref = ref64.run_f64(mb, G.narrow_feeds())
     c = float(np.finfo(np.float32).min) if mask_value == "min" else -10000.0
-    other = torch_bert(mb, narrow_feeds(), c)
+    other = torch_bert(mb, G.narrow_feeds(), c)
     for k in ("logits", "pooler_output"):
         assert np.isfinite(ref[k]).all()
-        assert bert_ref.rel_err(other[k], ref[k]) < 1e-10, k
+        assert ref64.rel_err(other[k], ref[k]) < 1e-10, k
 
 
 def test_every_spelling_walks_to_the_same_logits():
-    ref = bert_ref.run_f64(NARROW(), narrow_feeds())["logits"]
+    ref = ref64.run_f64(NARROW(), G.narrow_feeds())["logits"]
     for kw in (dict(unsqueeze="one"), dict(ktrans="one"), dict(scale="mul"), dict(mask_swap=True), dict(pos="gather"), dict(order="ptw")):
-        assert bert_ref.rel_err(bert_ref.run_f64(NARROW(**kw), narrow_feeds())["logits"], ref) < 1e-6, kw
+        assert ref64.rel_err(ref64.run_f64(NARROW(**kw), G.narrow_feeds())["logits"], ref) < 1e-6, kw
 
 
 def test_type_table_positions_and_mask_matter():
     """zeroing the type table, the position rows or the mask each move the narrow net's float64 logits by more than 5 %"""
     mb = NARROW()
-    ref = bert_ref.run_f64(mb, narrow_feeds())["logits"]
-    m = bert_ref.O.load_model(mb)
+    ref = ref64.run_f64(mb, G.narrow_feeds())["logits"]
+    m = O.load_model(mb)
 
     def without(name):
         z = np.zeros_like(np.asarray(m.inits[name]))
@@ -410,11 +388,11 @@ def test_type_table_positions_and_mask_matter():
     for name in ("token_type_embeddings", "position_rows"):
         changed = without(name)
         assert changed != mb
-        moved = bert_ref.rel_err(bert_ref.run_f64(changed, narrow_feeds())["logits"], ref)
+        moved = ref64.rel_err(ref64.run_f64(changed, G.narrow_feeds())["logits"], ref)
         print(f"without {name}: logits move by {moved:.3f} of max|ref|")
         assert moved > 0.05, (name, moved)
-    feeds = dict(narrow_feeds(), attention_mask=np.ones((3, 40), np.int64))
-    moved = bert_ref.rel_err(bert_ref.run_f64(mb, feeds)["logits"][1:], ref[1:])          # (image 0 has no padding)
+    feeds = dict(G.narrow_feeds(), attention_mask=np.ones((3, 40), np.int64))
+    moved = ref64.rel_err(ref64.run_f64(mb, feeds)["logits"][1:], ref[1:])          # (image 0 has no padding)
     print(f"without the mask: logits move by {moved:.3f} of max|ref|")
     assert moved > 0.05, moved
 
@@ -429,24 +407,45 @@ def test_embed_tiles_are_as_the_shapes_claim():
 def test_the_offset_tables_need_the_centred_variance():
     """a LayerNormalization of the test's own mean-100 rows with var = E[x^2] - mean^2 in fp32 misses the fp32 bound the GPU test holds the kernel to"""
     n, l, v, d = 2, 4, 11, 768
-    mb, ref = EG.graph_and_reference(n, l, v, d, "offset", 2, "const")
-    m = bert_ref.O.load_model(mb)
-    ids, tt = EG.make_ids(n, l, v)
+    mb, ref = G.embed_graph_and_reference(n, l, v, d, "offset", 2, "const")
+    m = O.load_model(mb)
+    ids, tt = G.make_ids(n, l, v)
     f32 = lambda name: np.asarray(m.inits[name], np.float32)  # noqa: E731
     x = f32("word_embeddings")[ids] + f32("token_type_embeddings")[tt] + f32("position_rows")
     mean = x.mean(-1, keepdims=True, dtype=np.float32)
     var = (x * x).mean(-1, keepdims=True, dtype=np.float32) - mean * mean
     y = (x - mean) / np.sqrt(np.maximum(var, np.float32(0)) + np.float32(1e-12)) * f32("emb_ln_scale") + f32("emb_ln_B")
-    err = bert_ref.rel_err(y.transpose(0, 2, 1).reshape(n, d, 1, l), ref)
+    err = ref64.rel_err(y.transpose(0, 2, 1).reshape(n, d, 1, l), ref)
     print(f"naive fp32 variance on the offset tables: max err / max|ref| {err:.3e}")
-    assert err > EG.RTOL["fp32"]
+    assert err > RTOL["fp32"]
 
 
-@pytest.mark.parametrize("kind", MA.KINDS)
-@pytest.mark.parametrize("c", MA.CS, ids=str)
+@pytest.mark.parametrize("kind", G.MASKED_KINDS)
+@pytest.mark.parametrize("c", G.MASK_VALUES, ids=str)
 def test_a_dropped_mask_is_far_outside_the_bound(kind, c):
-    MA.check_a_dropped_mask_is_far_outside_the_bound(kind, c)
+    """float64: ignoring the mask moves every partly masked image by more than 30 x the fp16 bound"""
+    n, l, h, hd = 2, 33, 3, 64
+    _, idx = G.mask_requests(n, l)
+    for r in idx:
+        ref, bare = G.masked_reference(n, l, h, hd, kind, c, tuple(r)), G.masked_reference(n, l, h, hd, kind, c, tuple(r), masked=False)
+        for i, row in enumerate(r):
+            hidden = G.mask_rows(l)[row]
+            if hidden.all() or not hidden.any():
+                continue
+            moved = float(np.abs(bare[i] - ref[i]).max() / np.abs(ref).max())
+            assert moved > 30 * RTOL["fp16"], (kind, c, row, moved)
 
 
 def test_fully_masked_rows_are_what_the_graph_gives():
-    MA.check_fully_masked_rows_are_what_the_graph_gives()
+    """float64: with c = min a fully masked image is the uniform average of V; with c = -10000 the unmasked softmax"""
+    n, l, h, hd = 2, 33, 3, 64
+    _, idx = G.mask_requests(n, l)
+    (r,) = [r for r in idx if 6 in r]
+    i = list(r).index(6)
+    x = G.masked_input(n, l, h, hd, "randn", tuple(r)).astype(np.float64)[i, :, 0, :].T.reshape(l, 3, h, hd)
+    uniform = x[:, 2].mean(0).reshape(h * hd)
+    y = G.masked_reference(n, l, h, hd, "randn", "min", tuple(r))[i, :, 0, :]
+    assert np.abs(y - uniform[:, None]).max() < 1e-12
+    y = G.masked_reference(n, l, h, hd, "randn", -10000.0, tuple(r))[i]
+    bare = G.masked_reference(n, l, h, hd, "randn", -10000.0, tuple(r), masked=False)[i]
+    assert np.abs(y - bare).max() < 1e-9

@@ -1,7 +1,7 @@
 """CPU: ConvNeXt through the ONNX reader and the planner (EngineDescribeModel): the channels-last views (a Transpose is never a step), the
 layer-norm steps and their tiles, the block's two Linear layers as 1x1 convs with the bias, the layer scale and the residual folded into the
 second, the GELU spellings, the refusals, and plan digests.  tests/golden/plan_digests_convnext.json pins ConvNeXt-Tiny's plans and weight blob.
-The float64 reference of tests/convnext_ref.py is checked against torch's own layer norm.
+The float64 reference of tests/ref64.py is checked against torch's own layer norm.
 
     python tests/test_convnext_plan.py            # rewrites tests/golden/plan_digests_convnext.json from the built library
 """
@@ -19,9 +19,10 @@ if __name__ == "__main__":
     from _pkg import load_package
     load_package()
 
-import convnext_ref  # noqa: E402
+import ref64  # noqa: E402
 from convnext_graphs import LANES, ln_default_tile, ln_graph, ln_tile_fits, narrow  # noqa: E402
 import test_plan_digests as D  # noqa: E402
+from engine_run import describe  # noqa: E402
 from gpu_ai_inference_server_amd import binding as B  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import models  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb  # noqa: E402
@@ -30,15 +31,6 @@ from oracle import onnx_oracle as O  # noqa: E402
 GOLDEN = os.path.join(HERE, "golden", "plan_digests_convnext.json")
 PRECS = ("fp32", "fp16")
 DEPTHS, DIMS = (3, 3, 9, 3), (96, 192, 384, 768)
-
-
-def _describe(path, batch, monkeypatch, prec, **env):
-    monkeypatch.setenv("IE_PRECISION", prec)
-    for k in ("IE_FORCE_TILE", "IE_FORCE_ALGO", "IE_FORCE_SPLITK"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    return B.DescribeModel(path, batch)["plan"]
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +44,7 @@ def tiny(tmp_path_factory):
 @pytest.mark.parametrize("batch", [1, 32])
 def test_convnext_tiny_plan(tiny, monkeypatch, prec, batch):
     path, _ = tiny
-    p = _describe(path, batch, monkeypatch, prec)
+    p = describe(path, batch, monkeypatch, prec)
     steps = p["steps"]
     f16 = prec == "fp16"
     # a Transpose is a view: no copy anywhere (the stem conv reads the NCHW input itself, the [N, classes] output needs none), and the only
@@ -118,7 +110,7 @@ def test_convnext_tiny_plan(tiny, monkeypatch, prec, batch):
 def test_layer_scale_folds_into_the_second_linear(tiny, monkeypatch):
     """fc2's planned weights are diag(scale) . W2^T and its bias scale * b2, computed here from the file's initializers"""
     path, mb = tiny
-    p = _describe(path, 1, monkeypatch, "fp32")
+    p = describe(path, 1, monkeypatch, "fp32")
     blob = B.PlanWeights(path, 1)
     inits = O.load_model(mb).inits
     for tag in ("s0b0", "s2b4"):
@@ -141,7 +133,7 @@ def test_gelu_spellings_give_the_same_activation(tmp_path, monkeypatch):
     plans = {}
     for form, swap in (("erf", False), ("erf", True), ("erf_mul", False), ("erf_mul", True), ("op", False), ("op_tanh", False)):
         path = models.write_repo(str(tmp_path), f"g_{form}_{int(swap)}", narrow(gelu=form, gelu_swap=swap))
-        steps = _describe(path, 2, monkeypatch, "fp32")["steps"]
+        steps = describe(path, 2, monkeypatch, "fp32")["steps"]
         plans[form, swap] = [(s["kind"], s.get("act"), s.get("algo"), s.get("tile"), s["in"]["c"], s["out"]["c"], s.get("residual")) for s in steps]
         acts = [s["act"] for s in steps if s["kind"] == "eltwise"]
         assert acts == [["gelu_tanh" if form == "op_tanh" else "gelu", 0, 0]] * 5, (form, swap, acts)
@@ -156,13 +148,13 @@ def test_near_miss_of_the_erf_pattern_is_refused(tmp_path, monkeypatch):
     gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     path = models.write_repo(str(tmp_path), "near", gb.finish([("x", [2, 4, 6, 6])], [("y", [2, 8, 6, 6])], opset=17))
     with pytest.raises(RuntimeError, match=r"Unsupported ONNX operator: Erf \(node erf_\d+\)"):
-        _describe(path, 2, monkeypatch, "fp32")
+        describe(path, 2, monkeypatch, "fp32")
     # the same graph with 0.5 plans; an Erf whose Div output has a second reader does not
     gb = models.GraphBuilder("g", 3)
     y = gb.gelu(gb.conv("x", 4, 8, 1), "erf")
     gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     path = models.write_repo(str(tmp_path), "hit", gb.finish([("x", [2, 4, 6, 6])], [("y", [2, 8, 6, 6])], opset=17))
-    assert [s.get("act") for s in _describe(path, 2, monkeypatch, "fp32")["steps"] if s["kind"] == "eltwise"] == [["gelu", 0, 0]]
+    assert [s.get("act") for s in describe(path, 2, monkeypatch, "fp32")["steps"] if s["kind"] == "eltwise"] == [["gelu", 0, 0]]
     gb = models.GraphBuilder("g", 3)
     x = gb.conv("x", 4, 8, 1)
     d = gb.simple("Div", [x, gb.init("sqrt2", np.array(np.sqrt(2.0), np.float32))])
@@ -171,7 +163,7 @@ def test_near_miss_of_the_erf_pattern_is_refused(tmp_path, monkeypatch):
     gb.nodes.append(pb.node("Add", [y, d], ["y"], "out"))
     path = models.write_repo(str(tmp_path), "shared", gb.finish([("x", [2, 4, 6, 6])], [("y", [2, 8, 6, 6])], opset=17))
     with pytest.raises(RuntimeError, match="Unsupported ONNX operator: Erf"):
-        _describe(path, 2, monkeypatch, "fp32")
+        describe(path, 2, monkeypatch, "fp32")
 
 
 def test_gelu_behind_a_depthwise_conv_takes_the_generic_tile(tmp_path, monkeypatch):
@@ -183,7 +175,7 @@ def test_gelu_behind_a_depthwise_conv_takes_the_generic_tile(tmp_path, monkeypat
         gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
         path = models.write_repo(str(tmp_path), "dw" + act, gb.finish([("x", [2, 4, 16, 16])], [("y", [2, 16, 16, 16])], opset=20))
         for forced in (None, "2"):
-            (dw,) = [s for s in _describe(path, 2, monkeypatch, "fp32", **({} if forced is None else {"IE_FORCE_TILE": forced}))["steps"] if s.get("algo") == "depthwise"]
+            (dw,) = [s for s in describe(path, 2, monkeypatch, "fp32", **({} if forced is None else {"IE_FORCE_TILE": forced}))["steps"] if s.get("algo") == "depthwise"]
             assert dw["act"][0] == act and dw["tile"] == (0 if act == "gelu" else int(forced or want)), (act, forced, dw["tile"])
 
 
@@ -195,7 +187,7 @@ def test_layer_norm_tiles(tmp_path, monkeypatch, prec):
         path = models.write_repo(str(tmp_path), f"ln{c}", ln_graph(2, c, 3, 5))
         got = {}
         for forced in (None, "0", "1", "2", "3", "4", "5"):
-            steps = _describe(path, 2, monkeypatch, prec, **({} if forced is None else {"IE_FORCE_TILE": forced}))["steps"]
+            steps = describe(path, 2, monkeypatch, prec, **({} if forced is None else {"IE_FORCE_TILE": forced}))["steps"]
             assert [s["kind"] for s in steps] == ["copy", "layer_norm", "copy"]         # the NCHW graph input and output; nothing for the Transposes
             got[forced] = steps[1]["tile"]
         fits = [t for t in (1, 2, 3, 4) if ln_tile_fits(c, prec == "fp16", t)]
@@ -211,7 +203,7 @@ def test_layer_norm_on_a_matrix(tmp_path, monkeypatch):
         y = gb.layernorm(gb.simple("Flatten", [gb.gap(gb.conv("x", 4, 24, 1))], [pb.attr_int("axis", 1)]), 24, axis=axis, name="ln")
         gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
         path = models.write_repo(str(tmp_path), f"m{axis}", gb.finish([("x", [3, 4, 6, 6])], [("y", [3, 24])], opset=17))
-        (ln,) = [s for s in _describe(path, 3, monkeypatch, "fp32")["steps"] if s["kind"] == "layer_norm"]
+        (ln,) = [s for s in describe(path, 3, monkeypatch, "fp32")["steps"] if s["kind"] == "layer_norm"]
         assert (ln["in"]["n"], ln["in"]["c"], ln["in"]["h"], ln["in"]["w"]) == (3, 24, 1, 1)
 
 
@@ -222,7 +214,7 @@ def _refused(tmp_path, monkeypatch, name, build, ishape, oshape, match, prec="fp
     gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     path = models.write_repo(str(tmp_path), name, gb.finish([("x", ishape)], [("y", oshape)], opset=17))
     with pytest.raises(RuntimeError, match=match):
-        _describe(path, ishape[0], monkeypatch, prec)
+        describe(path, ishape[0], monkeypatch, prec)
 
 
 def test_refusals(tmp_path, monkeypatch):
@@ -265,29 +257,29 @@ def test_channels_last_graph_output_is_refused(tmp_path, monkeypatch):
     y = gb.layernorm(gb.transpose("x", (0, 2, 3, 1)), 8, name="ln")
     path = models.write_repo(str(tmp_path), "clout", gb.finish([("x", [2, 8, 6, 6])], [(y, [2, 6, 6, 8])], opset=17))
     with pytest.raises(RuntimeError, match=r"graph output ln_out is a channels-last view"):
-        _describe(path, 2, monkeypatch, "fp32")
+        describe(path, 2, monkeypatch, "fp32")
 
 
 def test_fp8_is_refused(tiny, tmp_path, monkeypatch):
     path, _ = tiny
     with pytest.raises(RuntimeError, match=r"^LayerNormalization is not supported in fp8 mode \(node stem_ln\)$"):
-        _describe(path, 1, monkeypatch, "fp8")
+        describe(path, 1, monkeypatch, "fp8")
     # without a LayerNormalization in front of it, a GELU falls under the activation refusal
     gb = models.GraphBuilder("g", 3)
     y = gb.gelu(gb.conv("x", 16, 16, 1), "erf")
     gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     p8 = models.write_repo(str(tmp_path), "g8", gb.finish([("x", [2, 16, 6, 6])], [("y", [2, 16, 6, 6])], opset=17))
     with pytest.raises(RuntimeError, match=r"^activation and squeeze-excite nodes .* are not supported in fp8 mode"):
-        _describe(p8, 2, monkeypatch, "fp8")
+        describe(p8, 2, monkeypatch, "fp8")
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------------
 def test_reference_layer_norm_is_torchs():
-    assert convnext_ref.ln_agrees_with_torch() < 1e-12
+    assert ref64.ln_agrees_with_torch() < 1e-12
     # and the walk of a block: the op spelling and the Erf pattern are the same function
     x = np.random.RandomState(0).randn(2, 8, 6, 6)
-    ys = [convnext_ref.run_f64(models.convnext_block(2, 8, 6, gelu=g, gelu_swap=sw), {"x": x})["y"] for g, sw in (("erf", False), ("erf_mul", True), ("op", False))]
-    assert ys[0].shape == (2, 8, 6, 6) and convnext_ref.rel_err(ys[1], ys[0]) < 1e-7 and convnext_ref.rel_err(ys[2], ys[0]) < 1e-7     # (the constants are float32)
+    ys = [ref64.run_f64(models.convnext_block(2, 8, 6, gelu=g, gelu_swap=sw), {"x": x})["y"] for g, sw in (("erf", False), ("erf_mul", True), ("op", False))]
+    assert ys[0].shape == (2, 8, 6, 6) and ref64.rel_err(ys[1], ys[0]) < 1e-7 and ref64.rel_err(ys[2], ys[0]) < 1e-7     # (the constants are float32)
 
 
 # ---- digests ------------------------------------------------------------------------------------------------------------------------------

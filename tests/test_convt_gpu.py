@@ -1,47 +1,16 @@
-"""GPU (-m gpu): ConvTranspose on the MI355X against the float64 reference of tests/unet_ref.py (a torch-CPU double walk; the numpy scatter for
+"""GPU (-m gpu): ConvTranspose on the MI355X against the float64 reference of tests/ref64.py (a torch-CPU double walk; the numpy scatter for
 asymmetric pads).  Bounds as tests/test_gpu_parity.py and tests/test_seg_gpu.py: fp32 within 2e-4 of max|ref|, fp16 within 3e-3."""
-import os
 
 import numpy as np
 import pytest
 
 import convt_graphs as TG
-import unet_ref
+import ref64
+from engine_run import infer, plan_of, RTOL, run_model, with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _infer(m, iname, x, oname, oshape):
-    r = m.Infer([B.TensorData(iname, B.DataTypeFloat32, B.Shape(list(x.shape)), x)], [B.OutputConfig(oname, Shape=list(oshape), DataType="FLOAT32")])
-    return r[0].Data.reshape(oshape)
-
-
-def _run_engine(path, name, env, iname, x, oname, oshape):
-    """-> (output, [(step name, launched kernel)])"""
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            y = _infer(m, iname, x, oname, oshape)
-            return y, [(p["name"], p["kernel"]) for p in B.Profile(m, 1)]
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
 
 
 # ---- seeded random single ops ----------------------------------------------------------------------------------------------------------------
@@ -52,12 +21,12 @@ def test_random_transposed_convs(tmp_path, seed, prec):
     mb, ishape, oshape = TG.random_graph(cfg)
     path = models.write_repo(str(tmp_path), "ct", mb)
     x = models.synthetic_input(ishape, stream=f"ct{seed}")
-    ref = unet_ref.run_f64(mb, {"x": x})["y"]
+    ref = ref64.run_f64(mb, {"x": x})["y"]
     assert ref.shape == oshape
     for env in (dict(), dict(IE_FORCE_TILE="0")):
-        st = TG.tconv_step(_with_env(dict(IE_PRECISION=prec, **env), lambda: B.DescribeModel(path, 2)["plan"]))
-        y, kern = _run_engine(path, "ct", dict(IE_PRECISION=prec, **env), "x", x, "y", oshape)
-        err = unet_ref.rel_err(y, ref)
+        st = TG.tconv_step(plan_of(path, 2, dict(IE_PRECISION=prec, **env)))
+        y, kern = run_model(path, "ct", dict(IE_PRECISION=prec, **env), {"x": x}, "y", oshape, by_step=True)
+        err = ref64.rel_err(y, ref)
         (label,) = [k for n, k in kern if n == st["name"]]
         print(f"seed {seed} {prec} {env} tile {st['tile']} {label}: rel err {err:.3e}")
         assert label.startswith("convt_phase_kernel<" + ("f16" if prec == "fp16" else "f32")) if st["tile"] > 0 else label == "convt_generic_kernel", (cfg, env, label)
@@ -66,9 +35,9 @@ def test_random_transposed_convs(tmp_path, seed, prec):
 
 # ---- whole networks --------------------------------------------------------------------------------------------------------------------------
 def _check_unet(mb, path, name, x, oshape, prec):
-    ref = unet_ref.run_f64(mb, {"image": x})["out"]
-    y, kern = _run_engine(path, name, dict(IE_PRECISION=prec), "image", x, "out", oshape)
-    err = unet_ref.rel_err(y, ref)
+    ref = ref64.run_f64(mb, {"image": x})["out"]
+    y, kern = run_model(path, name, dict(IE_PRECISION=prec), {"image": x}, "out", oshape, by_step=True)
+    err = ref64.rel_err(y, ref)
     print(f"{name} {prec}: rel err {err:.3e}; transposed steps {[k for n, k in kern if k.startswith('convt_')]}")
     assert err < RTOL[prec]
     labels = [k for _, k in kern]
@@ -109,18 +78,18 @@ def test_replay_and_batch_independence(tmp_path):
     def go():
         m = B.CreateModel(path, "unetr")
         try:
-            y_host = _infer(m, "image", x, "out", (2, 2, 64, 64))
+            y_host = infer(m, {"image": x}, "out", (2, 2, 64, 64))
             din, dout = B.Prepare(m, [[2, 3, 64, 64]], 1)
             B.CopyToDevice(m, din[0], x)
             B.RunPrepared(m, 2, True)                                              # graph replay
             y = np.empty((2, 2, 64, 64), np.float32)
             B.CopyToHost(m, y, dout[0])
             np.testing.assert_array_equal(y, y_host)
-            y1 = _infer(m, "image", x[:1], "out", (1, 2, 64, 64))
-            assert unet_ref.rel_err(y_host[0], y1[0]) < RTOL["fp32"]
+            y1 = infer(m, {"image": x[:1]}, "out", (1, 2, 64, 64))
+            assert ref64.rel_err(y_host[0], y1[0]) < RTOL["fp32"]
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0"), go)
+    with_env(dict(IE_AUTOTUNE="0"), go)
 
 
 def test_autotuned_unet_matches(tmp_path):
@@ -128,21 +97,21 @@ def test_autotuned_unet_matches(tmp_path):
     mb = models.unet(2, image=64, base=16)
     path = models.write_repo(str(tmp_path), "unett", mb)
     x = models.synthetic_input((2, 3, 64, 64), stream="unett")
-    ref = unet_ref.run_f64(mb, {"image": x})["out"]
+    ref = ref64.run_f64(mb, {"image": x})["out"]
 
     def go():
         m = B.CreateModel(path, "unett")
         try:
-            y = _infer(m, "image", x, "out", (2, 2, 64, 64))
+            y = infer(m, {"image": x}, "out", (2, 2, 64, 64))
             return y, [p["kernel"] for p in B.Profile(m, 1)]
         finally:
             m.Destroy()
-    y, kern = _with_env(dict(IE_TUNE_CACHE="0", IE_TUNE_BATCHES="2"), go)      # the search runs at load
-    assert unet_ref.rel_err(y, ref) < RTOL["fp32"]
+    y, kern = with_env(dict(IE_TUNE_CACHE="0", IE_TUNE_BATCHES="2"), go)      # the search runs at load
+    assert ref64.rel_err(y, ref) < RTOL["fp32"]
     assert sum(k.startswith("convt_") for k in kern) == 4
 
 
 def test_fp8_load_is_refused(tmp_path):
     path = models.write_repo(str(tmp_path), "unet8", models.unet("N", image=64, base=16))
     with pytest.raises(Exception, match="ConvTranspose is not supported in fp8 mode"):
-        _with_env(dict(IE_PRECISION="fp8", IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "unet8"))
+        with_env(dict(IE_PRECISION="fp8", IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "unet8"))

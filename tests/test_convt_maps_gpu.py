@@ -3,7 +3,7 @@ checks the conv families.
 
 Each case is a single-step graph with exact operands (tests/convt_graphs.map_case): it forces the tile with IE_FORCE_TILE, asserts through
 Profile() that this kernel ran, and holds every element to  |y - ref64| <= 2 * c_emul * u * S  (tests/kernel_ref.py), ref64, S and c_emul
-computed on the CPU from the op's im2col form (unet_ref.convt_im2col: the zero-stuffed input against the flipped weights), plus the derived
+computed on the CPU from the op's im2col form (convt_graphs.convt_im2col: the zero-stuffed input against the flipped weights), plus the derived
 half-rounding terms in fp16 mode.  Every case runs three times on one model with three different inputs: an element the kernel never wrote
 would hold one and the same value in all three results, so three results that each meet their bound prove that every element of the step is
 written wherever two of the references lie further apart than their bounds together -- which is asserted for every element of the cases

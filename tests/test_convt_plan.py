@@ -2,7 +2,7 @@
 transposed step takes and leaves, FLOP accounting, the refusals, the forcing switches, the random test graphs' eligibility for the MFMA kernel,
 and plan digests.  tests/golden/plan_digests_unet.json pins U-Net's plans and weight blob; tests/golden/plan_digests_unet_resize_parent.json
 pins the bilinear-upsample variant (no transposed conv in the graph) as the commit BEFORE this operator planned it: it must not move.
-The references of tests/unet_ref.py are checked against each other.
+The references of tests/ref64.py are checked against each other.
 
     python tests/test_convt_plan.py            # rewrites tests/golden/plan_digests_unet.json from the built library
 """
@@ -23,7 +23,8 @@ if __name__ == "__main__":
 import convt_graphs as TG  # noqa: E402
 import kernel_ref as R  # noqa: E402
 import test_plan_digests as D  # noqa: E402
-import unet_ref  # noqa: E402
+import ref64  # noqa: E402
+from engine_run import describe  # noqa: E402
 from gpu_ai_inference_server_amd import binding as B  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import models  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb  # noqa: E402
@@ -31,13 +32,6 @@ from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb  # noqa: E402
 GOLDEN_UNET = os.path.join(HERE, "golden", "plan_digests_unet.json")
 GOLDEN_RESIZE = os.path.join(HERE, "golden", "plan_digests_unet_resize_parent.json")
 PRECS = ("fp32", "fp16")
-
-
-def _describe(path, batch, monkeypatch, prec, **env):
-    monkeypatch.setenv("IE_PRECISION", prec)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    return B.DescribeModel(path, batch)["plan"]
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +43,7 @@ def unet_path(tmp_path_factory):
 @pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("batch", [1, 8])
 def test_unet_plan(unet_path, monkeypatch, prec, batch):
-    p = _describe(unet_path, batch, monkeypatch, prec)
+    p = describe(unet_path, batch, monkeypatch, prec)
     steps = p["steps"]
     ts = [s for s in steps if s.get("algo") == "transposed"]
     assert len(ts) == 4 and all(s["name"].startswith(f"up{lv}+up{lv}_bn+relu_") for s, lv in zip(ts, (3, 2, 1, 0))), [s["name"] for s in ts]
@@ -77,7 +71,7 @@ def test_unet_plan(unet_path, monkeypatch, prec, batch):
 @pytest.mark.parametrize("prec", PRECS)
 def test_unet_sigmoid_and_small(tmp_path, monkeypatch, prec):
     path = models.write_repo(str(tmp_path), "us", models.unet(2, image=96, base=16, final="sigmoid"))
-    p = _describe(path, 2, monkeypatch, prec)
+    p = describe(path, 2, monkeypatch, prec)
     ts = [s for s in p["steps"] if s.get("algo") == "transposed"]
     assert len(ts) == 4 and [s["out"]["h"] for s in ts] == [12, 24, 48, 96]
     # fp32 K-step 8, fp16 K-step 16: Cin = 256 .. 32 all take the MFMA kernel
@@ -87,16 +81,16 @@ def test_unet_sigmoid_and_small(tmp_path, monkeypatch, prec):
 
 def test_forcing_switches(unet_path, monkeypatch):
     """IE_FORCE_ALGO is ignored for transposed steps; IE_FORCE_TILE picks the variant where eligible, other values leave the planner's choice"""
-    base = [s["tile"] for s in _describe(unet_path, 8, monkeypatch, "fp32")["steps"] if s.get("algo") == "transposed"]
+    base = [s["tile"] for s in describe(unet_path, 8, monkeypatch, "fp32")["steps"] if s.get("algo") == "transposed"]
     assert base == [1, 1, 1, 2]
     for algo in ("naive", "igemm", "ws", "direct", "raster"):
-        got = [(s["algo"], s["tile"]) for s in _describe(unet_path, 8, monkeypatch, "fp32", IE_FORCE_ALGO=algo)["steps"] if s["name"].startswith("up")]
+        got = [(s["algo"], s["tile"]) for s in describe(unet_path, 8, monkeypatch, "fp32", IE_FORCE_ALGO=algo)["steps"] if s["name"].startswith("up")]
         assert got == [("transposed", t) for t in base], algo
     monkeypatch.delenv("IE_FORCE_ALGO")
     for t in (0, 1, 2):
-        got = [s["tile"] for s in _describe(unet_path, 8, monkeypatch, "fp32", IE_FORCE_TILE=str(t))["steps"] if s.get("algo") == "transposed"]
+        got = [s["tile"] for s in describe(unet_path, 8, monkeypatch, "fp32", IE_FORCE_TILE=str(t))["steps"] if s.get("algo") == "transposed"]
         assert got == [t] * 4
-    got = [s["tile"] for s in _describe(unet_path, 8, monkeypatch, "fp32", IE_FORCE_TILE="3")["steps"] if s.get("algo") == "transposed"]
+    got = [s["tile"] for s in describe(unet_path, 8, monkeypatch, "fp32", IE_FORCE_TILE="3")["steps"] if s.get("algo") == "transposed"]
     assert got == base
 
 
@@ -108,11 +102,11 @@ def test_fast_tile_needs_the_non_overlapping_geometry(tmp_path, monkeypatch):
         y = gb.conv_transpose(gb.conv("x", 4, 16, 1), 16, 8, k, s, p, op, name="tconv")
         gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
         kk, ss = (k, k) if isinstance(k, int) else k, (s, s) if isinstance(s, int) else s
-        oh, ow = unet_ref.convt_out_hw(6, 6, kk, ss, (p,) * 4, (op, op))
+        oh, ow = ref64.convt_out_hw(6, 6, kk, ss, (p,) * 4, (op, op))
         path = models.write_repo(str(tmp_path), name, gb.finish([("x", [2, 4, 6, 6])], [("y", [2, 8, oh, ow])]))
         for forced in (None, "1", "2"):
             env = {} if forced is None else dict(IE_FORCE_TILE=forced)
-            st = TG.tconv_step(_describe(path, 2, monkeypatch, "fp32", **env))
+            st = TG.tconv_step(describe(path, 2, monkeypatch, "fp32", **env))
             monkeypatch.delenv("IE_FORCE_TILE", raising=False)
             assert (st["out"]["h"], st["out"]["w"]) == (oh, ow)
             assert st["tile"] == (0 if not want else int(forced or 1)), (name, forced, st["tile"])
@@ -133,7 +127,7 @@ def test_fusions_not_taken(tmp_path, monkeypatch):
     gb.nodes.append(pb.node("Identity", [t5], ["z"], "out2"))
     path = models.write_repo(str(tmp_path), "nf", gb.finish([("x", [2, 4, 6, 6])], [("y", [2, 8, 12, 12]), ("z", [2, 8, 6, 6])]))
     for prec in PRECS:
-        steps = _describe(path, 2, monkeypatch, prec)["steps"]
+        steps = describe(path, 2, monkeypatch, prec)["steps"]
         ts = {s["name"]: s for s in steps if s.get("algo") == "transposed"}
         assert sorted(ts) == ["t1", "t2", "t3", "t4", "t5"], sorted(ts)             # nothing rode along
         for s in ts.values():
@@ -182,7 +176,7 @@ def test_accepted_attribute_forms(tmp_path, monkeypatch):
                                      (S2 + [pb.attr_str("auto_pad", "VALID"), pb.attr_ints("pads", [1, 1, 1, 1])], 13),
                                      (S2 + [pb.attr_ints("kernel_shape", [3, 3]), pb.attr_ints("output_padding", [1, 1])], 14)]):
         path = models.write_repo(str(tmp_path), f"ok{i}", _one_node(attrs, out_hw=(hw, hw)))
-        (st,) = [s for s in _describe(path, 2, monkeypatch, "fp32")["steps"] if s.get("algo") == "transposed"]
+        (st,) = [s for s in describe(path, 2, monkeypatch, "fp32")["steps"] if s.get("algo") == "transposed"]
         assert (st["out"]["h"], st["out"]["w"], st["out"]["c"]) == (hw, hw, 6)
 
 
@@ -207,14 +201,14 @@ def test_random_cases_are_valid_and_a_third_is_eligible(tmp_path, monkeypatch):
             mb, ishape, oshape = TG.random_graph(cfg)
             assert min(oshape) >= 1
             path = models.write_repo(str(tmp_path), f"c{seed}", mb)
-            st = TG.tconv_step(_describe(path, 2, monkeypatch, prec))
+            st = TG.tconv_step(describe(path, 2, monkeypatch, prec))
             assert st["algo"] == "transposed" and (st["out"]["h"], st["out"]["w"]) == oshape[2:] and st["output_padding"] == cfg["op"]
             assert st["relu"] == cfg["bn_relu"] and st["bias"] == (cfg["bias"] or cfg["bn_relu"])
             assert (st["out"]["pitch"] > st["out"]["c"]) == cfg["cat_out"] and (st["in"]["pitch"] > st["in"]["c"]) == cfg["cat_in"]
             fast += st["tile"] > 0
             if st["tile"] > 0:
                 assert cfg["k"] == cfg["s"] and cfg["pads"] == [0] * 4 and cfg["op"] == [0, 0] and cfg["cin"] % (16 if prec == "fp16" else 8) == 0
-            assert TG.tconv_step(_describe(path, 2, monkeypatch, prec, IE_FORCE_TILE="0"))["tile"] == 0
+            assert TG.tconv_step(describe(path, 2, monkeypatch, prec, IE_FORCE_TILE="0"))["tile"] == 0
             monkeypatch.delenv("IE_FORCE_TILE")
         assert 3 * fast >= TG.NUM_SEEDS, (prec, fast)
     assert TG.NUM_SEEDS >= 24
@@ -240,12 +234,12 @@ def _ref_case(seed):
 def test_references_agree(seed):
     """numpy scatter == torch double F.conv_transpose2d (symmetric pads) == the im2col form the bound is computed on, to 1e-12"""
     c = _ref_case(seed)
-    y = unet_ref.convt_scatter(c["x"], c["w"], c["b"], c["s"], c["pads"], c["op"])
+    y = ref64.convt_scatter(c["x"], c["w"], c["b"], c["s"], c["pads"], c["op"])
     scale = np.abs(y).max()
     if c["sym"]:
-        yt = unet_ref.convt_torch(c["x"], c["w"], c["b"], c["s"], c["pads"][:2], c["op"])
+        yt = ref64.convt_torch(c["x"], c["w"], c["b"], c["s"], c["pads"][:2], c["op"])
         assert yt.shape == y.shape and np.abs(yt - y).max() <= 1e-12 * scale
-    cols, wm, shape = unet_ref.convt_im2col(c["x"], c["w"], c["s"], c["pads"], c["op"])
+    cols, wm, shape = TG.convt_im2col(c["x"], c["w"], c["s"], c["pads"], c["op"])
     ref, S = R.ref64_S(cols, wm, c["b"])
     assert np.abs(R.to_nchw(ref, shape) - y).max() <= 1e-12 * scale
     assert np.all(R.to_nchw(S, shape) >= np.abs(y) - 1e-12 * scale)
@@ -258,9 +252,9 @@ def test_float64_walk_uses_the_scatter_for_asymmetric_pads():
     x = np.random.RandomState(1).randn(*ishape)
     from oracle import onnx_oracle as O
     m = O.load_model(mb)
-    y = unet_ref.run_f64(mb, {"x": x})["y"]
+    y = ref64.run_f64(mb, {"x": x})["y"]
     assert y.shape == oshape
-    np.testing.assert_allclose(y, unet_ref.convt_scatter(x, m.inits["tconv_w"], m.inits["tconv_b"], (2, 3), (0, 1, 2, 0), (1, 2)), rtol=0, atol=1e-12)
+    np.testing.assert_allclose(y, ref64.convt_scatter(x, m.inits["tconv_w"], m.inits["tconv_b"], (2, 3), (0, 1, 2, 0), (1, 2)), rtol=0, atol=1e-12)
 
 
 # ---- digests ------------------------------------------------------------------------------------------------------------------------------

@@ -1,47 +1,17 @@
-"""GPU (-m gpu): depthwise convolutions and Clip on the MI355X against a float64 torch-CPU walk of the same ONNX graph (tests/dw_ref.py).
+"""GPU (-m gpu): depthwise convolutions and Clip on the MI355X against a float64 torch-CPU walk of the same ONNX graph (tests/ref64.py).
 Bounds as tests/test_gpu_parity.py: fp32 within 2e-4 of max|ref|, fp16 within 3e-3."""
 import os
 
 import numpy as np
 import pytest
 
-import dw_ref
+import ref64
+from engine_run import infer, plan_of, RTOL, run_model, with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _infer(m, iname, x, oname, oshape):
-    r = m.Infer([B.TensorData(iname, B.DataTypeFloat32, B.Shape(list(x.shape)), x)], [B.OutputConfig(oname, Shape=list(oshape), DataType="FLOAT32")])
-    return r[0].Data.reshape(oshape)
-
-
-def _run_engine(path, name, env, iname, x, oname, oshape, want_kernels=False):
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            y = _infer(m, iname, x, oname, oshape)
-            kern = [p["kernel"] for p in B.Profile(m, 1)] if want_kernels else None
-            return y, kern
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
 
 
 # ---- seeded random depthwise graphs ------------------------------------------------------------------------------------------------
@@ -97,17 +67,17 @@ def test_random_depthwise_graphs(tmp_path, cfg, prec):
     mb, oshape = _random_graph(cfg)
     path = models.write_repo(str(tmp_path), "dw", mb)
     x = models.synthetic_input((2, 4, cfg["h"], cfg["w"]), stream=f"dw{cfg['seed']}")
-    ref = dw_ref.run_f64(mb, {"x": x})["y"]
-    plan = _with_env(dict(IE_PRECISION=prec), lambda: B.DescribeModel(path, 2)["plan"])
+    ref = ref64.run_f64(mb, {"x": x})["y"]
+    plan = plan_of(path, 2, dict(IE_PRECISION=prec))
     dws = [st for st in plan["steps"] if st.get("algo") == "depthwise"]
     assert len(dws) == (1 if cfg["c"] > 1 else 0)          # (C = 1: group 1, an ordinary conv)
     fast_ok = bool(dws) and dws[0]["tile"] != 0
     tiles = ["0"] + ([str(1 + cfg["seed"] % 3)] if fast_ok else [])      # the generic kernel, and a channel-vector variant where one applies
     for t in tiles:
-        y, kern = _run_engine(path, "dw", dict(IE_PRECISION=prec, IE_FORCE_TILE=t), "x", x, "y", oshape, want_kernels=True)
+        y, kern = run_model(path, "dw", dict(IE_PRECISION=prec, IE_FORCE_TILE=t), {"x": x}, "y", oshape)
         if dws:
             assert any(q.startswith("conv_dw_generic_kernel" if t == "0" else "conv_dw_kernel<") for q in kern), kern
-        err = dw_ref.rel_err(y, ref)
+        err = ref64.rel_err(y, ref)
         assert err < RTOL[prec], (cfg, prec, t, err)
 
 
@@ -117,17 +87,17 @@ def test_mini_mobilenet_v2(tmp_path, prec):
     mb = models.mobilenet_v2("N", image=64, classes=50, seed=63)
     path = models.write_repo(str(tmp_path), "mini_mnv2", mb)
     x = models.synthetic_input((3, 3, 64, 64), stream="mini_mnv2")
-    ref = dw_ref.run_f64(mb, {"data": x})["logits"]
-    y, kern = _run_engine(path, "mini_mnv2", dict(IE_PRECISION=prec), "data", x, "logits", (3, 50), want_kernels=True)
+    ref = ref64.run_f64(mb, {"data": x})["logits"]
+    y, kern = run_model(path, "mini_mnv2", dict(IE_PRECISION=prec), {"data": x}, "logits", (3, 50))
     assert sum(q.startswith("conv_dw_kernel<") for q in kern) == 17, kern
-    assert dw_ref.rel_err(y, ref) < RTOL[prec]
+    assert ref64.rel_err(y, ref) < RTOL[prec]
 
 
 @pytest.fixture(scope="module")
 def mnv2(tmp_path_factory):
     mb = models.mobilenet_v2("N")
     path = models.write_repo(str(tmp_path_factory.mktemp("mnv2")), "mobilenet_v2", mb)
-    m = _with_env(dict(IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "mobilenet_v2"))
+    m = with_env(dict(IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "mobilenet_v2"))
     yield mb, path, m
     m.Destroy()
 
@@ -135,25 +105,25 @@ def mnv2(tmp_path_factory):
 def test_full_mobilenet_v2_fp32_vs_float64(mnv2):
     mb, _, m = mnv2
     x = models.synthetic_input((2, 3, 224, 224), stream="mnv2")
-    ref = dw_ref.run_f64(mb, {"data": x})["logits"]
-    y = _infer(m, "data", x, "logits", (2, 1000))
-    assert dw_ref.rel_err(y, ref) < RTOL["fp32"]
+    ref = ref64.run_f64(mb, {"data": x})["logits"]
+    y = infer(m, {"data": x}, "logits", (2, 1000))
+    assert ref64.rel_err(y, ref) < RTOL["fp32"]
     assert (y.argmax(1) == ref.argmax(1)).all()
 
 
 def test_mobilenet_v2_batch_independence(mnv2):
     _, _, m = mnv2
     x = models.synthetic_input((32, 3, 224, 224), stream="mnv2b")
-    y32 = _infer(m, "data", x, "logits", (32, 1000))
+    y32 = infer(m, {"data": x}, "logits", (32, 1000))
     for i in (0, 13, 31):
-        y1 = _infer(m, "data", x[i:i + 1], "logits", (1, 1000))
-        assert dw_ref.rel_err(y32[i], y1[0]) < RTOL["fp32"], i
+        y1 = infer(m, {"data": x[i:i + 1]}, "logits", (1, 1000))
+        assert ref64.rel_err(y32[i], y1[0]) < RTOL["fp32"], i
 
 
 def test_mobilenet_v2_graph_replay_matches_model_infer(mnv2):
     _, _, m = mnv2
     x = models.synthetic_input((4, 3, 224, 224), stream="mnv2r")
-    y_host = _infer(m, "data", x, "logits", (4, 1000))
+    y_host = infer(m, {"data": x}, "logits", (4, 1000))
     din, dout = B.Prepare(m, [[4, 3, 224, 224]], 1)
     B.CopyToDevice(m, din[0], x)
     B.RunPrepared(m, 2, True)
@@ -178,14 +148,14 @@ def test_depthwise_choices_survive_a_restart(tmp_path):
             return [p["kernel"] for p in B.Profile(m, 1)]
         finally:
             m.Destroy()
-    first = _with_env(dict(IE_AUTOTUNE="1"), kernels)
+    first = with_env(dict(IE_AUTOTUNE="1"), kernels)
     caches = [f for f in os.listdir(path) if f.startswith(".ie_tune")]
     assert len(caches) == 1, caches
     cache = os.path.join(path, caches[0])
     stamp = (os.stat(cache).st_mtime_ns, open(cache).read())
     entries = [(k.split(), int(v.split()[0])) for k, v in (ln.split(":") for ln in stamp[1].splitlines()[1:])]
     assert sum(len(k) == 16 and 700 <= code < 704 for k, code in entries) >= 5, entries
-    second = _with_env(dict(IE_AUTOTUNE="1"), kernels)
+    second = with_env(dict(IE_AUTOTUNE="1"), kernels)
     assert (os.stat(cache).st_mtime_ns, open(cache).read()) == stamp
     assert second == first and sum("conv_dw" in q for q in first) == 17
 
@@ -193,4 +163,4 @@ def test_depthwise_choices_survive_a_restart(tmp_path):
 def test_fp8_model_with_depthwise_conv_is_refused(tmp_path):
     path = models.write_repo(str(tmp_path), "mnv2_f8", models.mobilenet_v2("N", width_mult=0.5, image=64, classes=10))
     with pytest.raises(Exception, match="depthwise convolution is not supported in fp8 mode"):
-        _with_env(dict(IE_PRECISION="fp8", IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "mnv2_f8"))
+        with_env(dict(IE_PRECISION="fp8", IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "mnv2_f8"))

@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-import dw_ref
+import ref64
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
@@ -41,7 +41,7 @@ def _check_mobilenet_plan(p, mb, batch):
     assert all(q["kind"] == "conv" and q["relu"] and "clip" not in q for q in producers)
     assert not any("clip" in s or "pre_clip" in s for s in convs if s["algo"] != "depthwise")
     # FLOPs: 2 x the MACs of the ONNX graph's convs and Gemm
-    macs = dw_ref.conv_macs(mb, (batch, 3, 224, 224))
+    macs = sum(ref64.conv_macs(mb, (batch, 3, 224, 224)).values())
     conv_flops = sum(s["flops"] for s in convs)
     assert abs(conv_flops / (2 * macs) - 1) < 1e-6
     assert p["total_flops"] >= conv_flops and abs(p["total_flops"] / (2 * macs) - 1) < 0.01

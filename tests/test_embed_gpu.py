@@ -1,5 +1,5 @@
 """GPU (-m gpu): the embed kernels (token + type + position embedding and the LayerNormalization behind them, one step) on the MI355X against the
-float64 walk of tests/bert_ref.py, with the project's bounds (tests/test_gpu_parity.py): fp32 within 2e-4 of max|ref|, fp16 within 3e-3.
+float64 walk of tests/ref64.py, with the project's bounds (tests/test_gpu_parity.py): fp32 within 2e-4 of max|ref|, fp16 within 3e-3.
 
 Graph: input_ids (, token_type_ids) [N, L] INT64 -> the embedding sum -> LayerNormalization -> Transpose [0,2,1] -> Reshape [N, D, 1, L] -> y, so every
 token row the step writes reaches the output.  Every case runs on the planner's default tile and on every forced tile the plan accepts
@@ -10,86 +10,33 @@ D = 7 (generic only); D = 768 (BERT's own width: three vectors per lane on the 6
 widest group in both precisions: generic only).
 Ids: 0, V - 1, -1 (= V - 1), -V (= 0), repeats; type ids of both rows.  Tables: randn, and mean 100 / std 1 (the variance of the centred values
 survives; E[x^2] - mean^2 would not)."""
-import functools
-import os
 
 import numpy as np
 import pytest
 
 import bert_graphs as G
-import bert_ref
+import ref64
+from engine_run import plan_of, RTOL, run_model, tensor, with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
 SHAPES = [(2, 5, 37, 8), (2, 5, 37, 20), (1, 3, 5, 7), (2, 4, 11, 768), (1, 3, 5, 3080)]
-MEANS = {"randn": 0.0, "offset": 100.0}
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def make_ids(n, l, v, types=2):
-    """ids with 0, V - 1, -1, -V and a repeat; type ids that use both rows"""
-    st = np.random.RandomState(100 * l + v)
-    ids = st.randint(0, v, size=(n, l)).astype(np.int64)
-    special = [0, v - 1, -1, -v, v - 1]
-    ids.ravel()[:min(len(special), ids.size)] = special[:ids.size]
-    tt = (np.arange(n * l).reshape(n, l) % max(types, 1)).astype(np.int64)
-    return ids, tt
-
-
-def feeds_of(ids, tt, types):
-    return {"input_ids": ids, **({"token_type_ids": tt} if types else {})}
-
-
-@functools.lru_cache(maxsize=None)
-def graph_and_reference(n, l, v, d, kind, types, pos):
-    mb = G.embed_graph(n, l, v, d, types=types, pos=pos, table_mean=MEANS[kind])
-    ids, tt = make_ids(n, l, v, types)
-    ref = bert_ref.run_f64(mb, feeds_of(ids, tt, types))["y"]
-    ref.setflags(write=False)
-    return mb, ref
 
 
 def _tensors(ids, tt, types):
-    t = [B.TensorData("input_ids", B.DataTypeInt64, B.Shape(list(ids.shape)), ids)]
-    if types:
-        t.append(B.TensorData("token_type_ids", B.DataTypeInt64, B.Shape(list(tt.shape)), tt))
-    return t
-
-
-def _run(path, name, env, tensors, oshape):
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            r = m.Infer(tensors, [B.OutputConfig("y", Shape=list(oshape), DataType="FLOAT32")])
-            return r[0].Data.reshape(oshape), [p["kernel"] for p in B.Profile(m, 1)]
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
+    return [tensor(k, v) for k, v in G.embed_feeds(ids, tt, types).items()]
 
 
 def _case(tmp_path, n, l, v, d, kind, prec, types=2, pos="const"):
-    mb, ref = graph_and_reference(n, l, v, d, kind, types, pos)
+    mb, ref = G.embed_graph_and_reference(n, l, v, d, kind, types, pos)
     path = models.write_repo(str(tmp_path), "embed", mb)
-    ids, tt = make_ids(n, l, v, types)
+    ids, tt = G.make_ids(n, l, v, types)
     f16 = prec == "fp16"
     ran = []
     for forced in (None, 0, 1, 2, 3, 4):
         env = dict(IE_PRECISION=prec, **({} if forced is None else {"IE_FORCE_TILE": str(forced)}))
-        steps = _with_env(env, lambda: B.DescribeModel(path, n)["plan"])["steps"]
+        steps = plan_of(path, n, env)["steps"]
         assert [s["kind"] for s in steps] == ["embed", "copy"]
         em = steps[0]
         assert em["out"]["f16"] == f16 and em["tables"] == (2 if types else 1) and em["vocab"] == ([v, types] if types else [v])
@@ -98,10 +45,10 @@ def _case(tmp_path, n, l, v, d, kind, prec, types=2, pos="const"):
         elif em["tile"] != forced:
             assert em["tile"] == 0 and not G.embed_tile_fits(d, f16, forced)        # not eligible: the generic kernel, which forced tile 0 runs
             continue
-        y, kern = _run(path, "embed", env, _tensors(ids, tt, types), (n, d, 1, l))
+        y, kern = run_model(path, "embed", env, G.embed_feeds(ids, tt, types), "y", (n, d, 1, l))
         assert kern == [G.embed_label(em["tile"], f16), "copy_kernel"], (forced, em["tile"], kern)
         assert np.isfinite(y).all()
-        err = bert_ref.rel_err(y, ref)
+        err = ref64.rel_err(y, ref)
         print(f"N {n} L {l} V {v} D {d} {kind} {prec} types {types} pos {pos} forced {forced} tile {em['tile']}: max err / max|ref| {err:.3e}")
         assert err < RTOL[prec], (n, l, v, d, kind, prec, em["tile"], err)
         ran.append(em["tile"])
@@ -110,7 +57,7 @@ def _case(tmp_path, n, l, v, d, kind, prec, types=2, pos="const"):
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
-@pytest.mark.parametrize("kind", list(MEANS))
+@pytest.mark.parametrize("kind", list(G.TABLE_MEANS))
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_embed(tmp_path, shape, kind, prec):
     _case(tmp_path, *shape, kind, prec)
@@ -127,9 +74,9 @@ def test_embed_variants(tmp_path, types, pos, prec):
 def test_out_of_range_id_is_refused(tmp_path):
     """ModelInfer names the input, the position, the value and the range; nothing ran, and the model answers the next valid request"""
     n, l, v, d = 2, 5, 37, 8
-    mb, ref = graph_and_reference(n, l, v, d, "randn", 2, "const")
+    mb, ref = G.embed_graph_and_reference(n, l, v, d, "randn", 2, "const")
     path = models.write_repo(str(tmp_path), "embed", mb)
-    ids, tt = make_ids(n, l, v)
+    ids, tt = G.make_ids(n, l, v)
     out = [B.OutputConfig("y", Shape=[n, d, 1, l], DataType="FLOAT32")]
 
     def go():
@@ -145,7 +92,7 @@ def test_out_of_range_id_is_refused(tmp_path):
             with pytest.raises(RuntimeError, match=r"Index out of range for input: token_type_ids at position \[1, 0\]: value 2 is outside the valid range \[-2, 1\]"):
                 m.Infer(_tensors(ids, x, 2), out)
             y = m.Infer(_tensors(ids, tt, 2), out)[0].Data.reshape(n, d, 1, l)
-            assert bert_ref.rel_err(y, ref) < RTOL["fp32"]
+            assert ref64.rel_err(y, ref) < RTOL["fp32"]
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)

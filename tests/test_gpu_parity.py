@@ -10,19 +10,16 @@ import numpy as np
 import pytest
 
 from conftest import MINI, ROOT
+from engine_run import with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd import build
 from gpu_ai_inference_server_amd.modelgen import models
 from oracle import onnx_oracle as O
+from ref64 import rel_err
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(ROOT, "tests", "golden")
 RTOL = 2e-4   # of max|ref| ; contract (BASELINE.json north_star): 1e-3
-
-
-def rel_err(y, ref):
-    ref = np.asarray(ref, np.float64)
-    return float(np.abs(np.asarray(y, np.float64) - ref).max() / max(np.abs(ref).max(), 1e-30))
 
 
 @pytest.fixture(scope="module")
@@ -587,7 +584,7 @@ def test_direct_split_k_kernel(tmp_path, tile, prec):
         finally:
             m.Destroy()
         return nd, y, y2
-    nd, y, y2 = _run_with_env(dict(IE_PRECISION=prec, IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go)
+    nd, y, y2 = with_env(dict(IE_PRECISION=prec, IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go)
     np.testing.assert_array_equal(y, y2)
     e = rel_err(y, ref)
     print(f"direct tile {tile} {prec}: {nd} convs on the direct split-K kernel, rel err {e:.2e}")
@@ -618,7 +615,7 @@ def test_direct_window_kernel(tmp_path, tile):
         finally:
             m.Destroy()
         return nd, y, y2, prof
-    nd, y, y2, prof = _run_with_env(dict(IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go)
+    nd, y, y2, prof = with_env(dict(IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go)
     np.testing.assert_array_equal(y, y2)
     e = rel_err(y, ref)
     print(f"direct window tile {tile}: {nd} convs, kernels {sorted(prof)}, rel err {e:.2e}")
@@ -654,7 +651,7 @@ def test_window_kernel_random_same_size_convs(tmp_path):
             finally:
                 m.Destroy()
             return y, dims, kern
-        y, dims, kern = _run_with_env(dict(IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go)
+        y, dims, kern = with_env(dict(IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go)
         assert f"conv_win_kernel<f32,t{tile}>" in kern, (desc, kern)
         e = rel_err(y, ref)
         worst = max(worst, e)
@@ -714,7 +711,7 @@ def test_activations_stationary_1x1_kernel(tmp_path, tile):
             finally:
                 m.Destroy()
             return y, dims, kern
-        y, dims, kern = _run_with_env(dict(IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go)
+        y, dims, kern = with_env(dict(IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go)
         assert f"conv1x1_as_kernel<f32,t{tile}>" in kern, (case, kern)
         e = rel_err(y, ref)
         worst = max(worst, e)
@@ -733,7 +730,7 @@ def test_activations_stationary_1x1_kernel(tmp_path, tile):
             finally:
                 m.Destroy()
             return y, kern
-        y, kern = _run_with_env(dict(IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go_net)
+        y, kern = with_env(dict(IE_FORCE_ALGO="direct", IE_FORCE_TILE=str(tile)), go_net)
         assert f"conv1x1_as_kernel<f32,t{tile}>" in kern, kern       # the bottleneck 1x1s read a slice of the concat buffer
         worst = max(worst, rel_err(y, ref))
         assert rel_err(y, ref) < RTOL
@@ -754,15 +751,6 @@ def _f16_env(**extra):
     env = dict(IE_PRECISION="fp16")
     env.update(extra)
     return env
-
-
-def _run_with_env(env, fn):
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k_ in env:
-            os.environ.pop(k_, None)
 
 
 def _f16_densenet_bytes():
@@ -796,7 +784,7 @@ def test_fp16_mode_graphs_vs_float64_oracle(model_repo, tmp_path, name):
         finally:
             m.Destroy()
         return plan, y, y2, dims
-    plan, y, y2, dims = _run_with_env(_f16_env(), go)
+    plan, y, y2, dims = with_env(_f16_env(), go)
     assert dims == list(oshape)
     np.testing.assert_array_equal(y, y2)
     e = rel_err(y, ref)
@@ -826,7 +814,7 @@ def test_fp16_every_tile_and_split_k(tmp_path, tile, splitk):
             return infer(m, "", "data_0", x, "fc6_1", [3, 24, 1, 1])[0]
         finally:
             m.Destroy()
-    y = _run_with_env(_f16_env(IE_FORCE_ALGO="igemm", IE_FORCE_TILE=str(tile), IE_FORCE_SPLITK=str(splitk)), go)
+    y = with_env(_f16_env(IE_FORCE_ALGO="igemm", IE_FORCE_TILE=str(tile), IE_FORCE_SPLITK=str(splitk)), go)
     e = rel_err(y, ref)
     assert e < F16_RTOL, (tile, splitk, e)
 
@@ -853,7 +841,7 @@ def test_fp16_weights_stationary_kernels(tmp_path, tile, image):
             return n1, n3, infer(m, "", "data_0", x, "fc6_1", [3, 40, 1, 1])[0]
         finally:
             m.Destroy()
-    n1, n3, y = _run_with_env(_f16_env(IE_FORCE_ALGO="ws", IE_FORCE_TILE=str(tile)), go)
+    n1, n3, y = with_env(_f16_env(IE_FORCE_ALGO="ws", IE_FORCE_TILE=str(tile)), go)
     assert n1 >= (3 if tile % 6 >= 2 else 2) and n3 == 4, (n1, n3)
     e = rel_err(y, ref)
     print(f"ws tile {tile} image {image}: {n1} 1x1 + {n3} 3x3 convs on the weights-stationary kernels, rel err {e:.2e}")
@@ -883,7 +871,7 @@ def test_fp16_random_conv_graphs_vs_oracle(tmp_path, seed):
                 return infer(m, "", "x", x, "out", oshape)
             finally:
                 m.Destroy()
-        y, dims = _run_with_env(env, go)
+        y, dims = with_env(env, go)
         assert dims == list(oshape)
         e = rel_err(y, ref)
         worst = max(worst, e)
@@ -916,8 +904,8 @@ def test_fp16_dense_block_chain_kernel(tmp_path, batch, image, stem, blocks, ban
             return y, [p_["kernel"] for p_ in B.Profile(m, 1)], B.DescribeModel(path, batch)["plan"]
         finally:
             m.Destroy()
-    y, kern, plan = _run_with_env(_f16_env(IE_AUTOTUNE="0", IE_DENSE_BAND=str(band)), go)
-    y0, kern0, plan0 = _run_with_env(_f16_env(IE_AUTOTUNE="0", IE_NO_DENSE_BLOCK="1"), go)
+    y, kern, plan = with_env(_f16_env(IE_AUTOTUNE="0", IE_DENSE_BAND=str(band)), go)
+    y0, kern0, plan0 = with_env(_f16_env(IE_AUTOTUNE="0", IE_NO_DENSE_BLOCK="1"), go)
     chains = [s for s in plan["steps"] if s.get("algo") == "dense_block" and s["tile"] != 0]
     if band:
         assert any(s["in"]["h"] * (s["in"]["w"] + 1) > 224 for s in chains), [(s["in"]["h"], s["in"]["w"]) for s in chains]
@@ -955,8 +943,8 @@ def test_stem_and_max_pool_in_one_launch(tmp_path, batch, image, stem, prec):
             return y, [p_["kernel"] for p_ in B.Profile(m, 1)], B.DescribeModel(path, batch)["plan"]
         finally:
             m.Destroy()
-    y, kern, plan = _run_with_env(dict(IE_PRECISION=prec, IE_AUTOTUNE="0"), go)
-    y0, kern0, plan0 = _run_with_env(dict(IE_PRECISION=prec, IE_AUTOTUNE="0", IE_NO_STEM_POOL="1"), go)
+    y, kern, plan = with_env(dict(IE_PRECISION=prec, IE_AUTOTUNE="0"), go)
+    y0, kern0, plan0 = with_env(dict(IE_PRECISION=prec, IE_AUTOTUNE="0", IE_NO_STEM_POOL="1"), go)
     s0 = plan["steps"][0]
     conv_hw = (image + 6 - 7) // 2 + 1
     tag = "f16" if prec == "fp16" else "f32"
@@ -1010,7 +998,7 @@ def test_fp16_test_model_known_answer(model_repo):
             return infer(m, "", "input", x, "output", [1, 2])[0]
         finally:
             m.Destroy()
-    y = _run_with_env(_f16_env(), go)
+    y = with_env(_f16_env(), go)
     np.testing.assert_allclose(np.asarray(y).reshape(-1), [-0.6017066, 1.8522782], rtol=5e-3, atol=5e-3)
 
 
@@ -1018,7 +1006,7 @@ def test_unknown_precision_is_a_load_error(model_repo):
     def go():
         with pytest.raises(RuntimeError, match="unsupported precision"):
             B.CreateModel(os.path.join(model_repo, "test_model", "1"), "test_model")
-    _run_with_env(dict(IE_PRECISION="int3"), go)
+    with_env(dict(IE_PRECISION="int3"), go)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1044,7 +1032,7 @@ def test_fp16_weights_stationary_3x3_wide_outputs(tmp_path, tile):
             return n3, infer(m, "", "data", x, "logits", [2, 20])[0]
         finally:
             m.Destroy()
-    n3, y = _run_with_env(dict(IE_PRECISION="fp16", IE_FORCE_ALGO="ws", IE_FORCE_TILE=str(tile)), go)
+    n3, y = with_env(dict(IE_PRECISION="fp16", IE_FORCE_ALGO="ws", IE_FORCE_TILE=str(tile)), go)
     assert len(n3) >= 3 and {st["out"]["c"] for st in n3} >= {64, 128}, [(st["in"]["c"], st["out"]["c"]) for st in n3]
     e = rel_err(y, ref)
     print(f"ws3x3 wide tile {tile}: {len(n3)} convs, rel err {e:.2e}")
@@ -1065,7 +1053,7 @@ def test_resnet_mini_vs_float64_oracle(tmp_path, prec):
             return infer(m, "", "data", x, "logits", [3, 20])
         finally:
             m.Destroy()
-    y, dims = _run_with_env(dict(IE_PRECISION=prec), go)
+    y, dims = with_env(dict(IE_PRECISION=prec), go)
     assert dims == [3, 20]
     e = rel_err(y, ref)
     print(f"resnet mini {prec}: rel err vs float64 oracle {e:.2e}")
@@ -1087,7 +1075,7 @@ def test_resnet50_b2_vs_float64_oracle(tmp_path, prec):
             return infer(m, "", "data", x, "logits", [2, 1000])
         finally:
             m.Destroy()
-    y, dims = _run_with_env(dict(IE_PRECISION=prec), go)
+    y, dims = with_env(dict(IE_PRECISION=prec), go)
     assert dims == [2, 1000]
     e = rel_err(y, ref)
     print(f"resnet50 {prec} B=2: rel err vs float64 oracle {e:.2e}")
@@ -1208,7 +1196,7 @@ def test_plan_cache_is_bounded(model_repo):
             m.Destroy()
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
-        _run_with_env(dict(IE_MAX_PLANS="2", IE_AUTOTUNE="0"), lambda: go(tmp))
+        with_env(dict(IE_MAX_PLANS="2", IE_AUTOTUNE="0"), lambda: go(tmp))
 
 
 def test_output_dims_survive_plan_eviction_under_concurrency(tmp_path):
@@ -1242,7 +1230,7 @@ def test_output_dims_survive_plan_eviction_under_concurrency(tmp_path):
             assert not errs, errs
         finally:
             m.Destroy()
-    _run_with_env(dict(IE_MAX_PLANS="1", IE_AUTOTUNE="0", IE_SHARD_DEVICES="0,0"), go)
+    with_env(dict(IE_MAX_PLANS="1", IE_AUTOTUNE="0", IE_SHARD_DEVICES="0,0"), go)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1324,8 +1312,8 @@ def test_config3_fp16_b1024_over_8_shards(densenet_repo, tmp_path):
             return r.Data.reshape(1024, 1000).copy()
         finally:
             m.Destroy()
-    y128 = _run_with_env(dict(IE_AUTOTUNE="0"), unsharded)
-    y = _run_with_env(dict(IE_AUTOTUNE="0", IE_SHARD_DEVICES="0,0,0,0,0,0,0,0"), sharded)
+    y128 = with_env(dict(IE_AUTOTUNE="0"), unsharded)
+    y = with_env(dict(IE_AUTOTUNE="0", IE_SHARD_DEVICES="0,0,0,0,0,0,0,0"), sharded)
     assert np.isfinite(y).all()
     for k, p_ in enumerate(perms):
         got = y[128 * k:128 * (k + 1)]
@@ -1431,7 +1419,7 @@ def test_rccl_weight_broadcast_to_a_private_replica(densenet_repo):
             return info, y2, B.ShardStats(m2)
         finally:
             m2.Destroy()
-    info, y2, st = _run_with_env(dict(IE_SHARD_DEVICES="0,0", IE_SHARD_PRIVATE_WEIGHTS="1"), go)
+    info, y2, st = with_env(dict(IE_SHARD_DEVICES="0,0", IE_SHARD_PRIVATE_WEIGHTS="1"), go)
     assert info["lanes"] == 2 and info["shards"] == 2 and info["lane_shares_weights_with"] == [0, 1]
     r = info["rccl"]
     assert r["used"] and r["ranks"] == 1 and r["weight_owners"] == 2 and r["bytes"] > 30e6 and r["broadcast_ms"] > 0
@@ -1439,7 +1427,7 @@ def test_rccl_weight_broadcast_to_a_private_replica(densenet_repo):
     assert st == (2, 1)
     assert rel_err(y2, y1) < 2e-5
     # without private weights a same-device replica shares the primary's blob: nothing to broadcast
-    info3 = _run_with_env(dict(IE_SHARD_DEVICES="0,0"), lambda: (lambda mm: (B.RuntimeInfo(mm), mm.Destroy())[0])(B.CreateModel(path, "densenet_onnx")))
+    info3 = with_env(dict(IE_SHARD_DEVICES="0,0"), lambda: (lambda mm: (B.RuntimeInfo(mm), mm.Destroy())[0])(B.CreateModel(path, "densenet_onnx")))
     assert info3["lane_shares_weights_with"] == [0, 0] and not info3["rccl"]["used"]
 
 
@@ -1475,8 +1463,8 @@ def test_private_replicas_hold_the_primarys_blob_and_every_mirror(tmp_path, prec
             return y, y2, B.RuntimeInfo(m, checksums=True), B.ShardStats(m)
         finally:
             m.Destroy()
-    y1, y1u, info1, _ = _run_with_env(dict(IE_PRECISION=prec), lambda: run(True))
-    y4, y4u, info4, st = _run_with_env(dict(IE_PRECISION=prec, IE_SHARD_DEVICES="0,0,0,0", IE_SHARD_PRIVATE_WEIGHTS="1"), lambda: run(True))
+    y1, y1u, info1, _ = with_env(dict(IE_PRECISION=prec), lambda: run(True))
+    y4, y4u, info4, st = with_env(dict(IE_PRECISION=prec, IE_SHARD_DEVICES="0,0,0,0", IE_SHARD_PRIVATE_WEIGHTS="1"), lambda: run(True))
     assert info4["lanes"] == 4 and info4["lane_shares_weights_with"] == [0, 1, 2, 3] and st[0] == 4 and st[1] >= 2
     assert info4["rccl"]["used"] and info4["rccl"]["weight_owners"] == 4
     assert len(set(info4["weight_checksums"])) == 1 and info4["weight_checksums"][0] == info1["weight_checksums"][0]
@@ -1515,7 +1503,7 @@ def test_pipelined_host_path_matches_single_shot(densenet_repo):
         finally:
             m.Destroy()
     yf, yu, ys = run(2)
-    yf0, yu0, ys0 = _run_with_env(dict(IE_PIPELINE_CHUNKS="0"), lambda: run(1))
+    yf0, yu0, ys0 = with_env(dict(IE_PIPELINE_CHUNKS="0"), lambda: run(1))
     assert rel_err(yf, yf0) < 2e-5 and rel_err(yu, yu0) < 2e-5 and rel_err(ys, ys0) < 2e-5
     assert rel_err(ys.reshape(32, 1000)[:13], yf.reshape(32, 1000)[:13]) < 2e-5        # whole images before the cut are unaffected
     assert np.abs(ys.reshape(32, 1000)[14:] - ys.reshape(32, 1000)[14]).max() < 1e-5   # all-zero images give one common answer
@@ -1548,7 +1536,7 @@ def test_dynamic_batcher_feeds_the_sharder(densenet_repo):
             return np.stack(out), B.BatcherStats(m), B.ShardStats(m)
         finally:
             m.Destroy()
-    out, bs, ss = _run_with_env(dict(IE_DYNAMIC_BATCH="8", IE_BATCH_WINDOW_US="200000", IE_SHARD_DEVICES="0,0"), go)
+    out, bs, ss = with_env(dict(IE_DYNAMIC_BATCH="8", IE_BATCH_WINDOW_US="200000", IE_SHARD_DEVICES="0,0"), go)
     assert bs["coalesced_requests"] == 8 and bs["device_batches"] < 8
     assert ss[1] >= 1                                  # at least one coalesced batch had >= 2 rows and was cut over both replicas
     assert rel_err(out, ref) < 2e-5
@@ -1595,7 +1583,7 @@ def test_fused_step_choices_survive_a_restart(tmp_path):
         stamp = (os.stat(cache).st_mtime_ns, open(cache).read())
         keys = [ln.split(":")[0].split() for ln in stamp[1].splitlines()[1:]]
         assert any(len(k) == 7 for k in keys) and any(len(k) == 10 for k in keys), sorted({len(k) for k in keys})     # stem + pool, dense block
-        plan = _run_with_env(dict(IE_PRECISION="fp16"), lambda: B.DescribeModel(path, 4)["plan"])
+        plan = with_env(dict(IE_PRECISION="fp16"), lambda: B.DescribeModel(path, 4)["plan"])
         assert plan["steps"][0]["algo"] == "stem_pool" and any(s.get("algo") == "dense_block" for s in plan["steps"])
     finally:
         m.Destroy()
@@ -1682,7 +1670,7 @@ def _fp8_run(path, name, x, iname, oname, oshape, env=None):
             m.Destroy()
     e = dict(IE_PRECISION="fp8")
     e.update(env or {})
-    return _run_with_env(e, go)
+    return with_env(e, go)
 
 
 @pytest.mark.parametrize("tile", [-1, 0, 1, 2, 3, 4, 5, 6])
@@ -1701,7 +1689,7 @@ def test_fp8_resnet_mini_every_tile(tmp_path, tile):
 
     def plan_and_blob():
         return B.DescribeModel(path, 3)["plan"], B.PlanWeights(path, 3)
-    plan, blob = _run_with_env(dict(IE_PRECISION="fp8", **env), plan_and_blob)
+    plan, blob = with_env(dict(IE_PRECISION="fp8", **env), plan_and_blob)
     emu = F.run_plan(plan, blob, {"data": x}, act_scales=info["f8_act_scales"], fp8=True)["logits"]
     e_emu, e_ref, emu_ref = rel_err(y, emu), rel_err(y, ref), rel_err(emu, ref)
     print(f"fp8 resnet mini tile {tile}: vs fp8 emulation {e_emu:.2e}, vs float64 oracle {e_ref:.2e} (emulation vs float64 {emu_ref:.2e})")
@@ -1721,7 +1709,7 @@ def test_fp8_stem_and_max_pool_one_launch_or_two(tmp_path, image):
     errs = []
     for env in ({}, dict(IE_NO_STEM_POOL="1")):
         y, info = _fp8_run(path, "resnet_f8sp", x, "data", "logits", [3, 20], dict(IE_AUTOTUNE="0", **env))
-        plan, blob = _run_with_env(dict(IE_PRECISION="fp8", **env), lambda: (B.DescribeModel(path, 3)["plan"], B.PlanWeights(path, 3)))
+        plan, blob = with_env(dict(IE_PRECISION="fp8", **env), lambda: (B.DescribeModel(path, 3)["plan"], B.PlanWeights(path, 3)))
         assert (plan["steps"][0]["algo"] == "stem") == bool(env) and (plan["steps"][0]["algo"] == "stem_pool") == (not env)
         emu = F.run_plan(plan, blob, {"data": x}, act_scales=info["f8_act_scales"], fp8=True)["logits"]
         errs.append((rel_err(y, emu), rel_err(y, ref)))
@@ -1753,12 +1741,12 @@ def test_fp8_weights_stationary_kernels(tmp_path, tile):
             m.Destroy()
     y, info = _fp8_run(path, "resnet_f8w", x, "data", "logits", [3, 20], env)
     y0, _ = _fp8_run(path, "resnet_f8w", x, "data", "logits", [3, 20], dict(IE_FORCE_TILE="3"))
-    kern = _run_with_env(dict(IE_PRECISION="fp8", **env), kernels)
+    kern = with_env(dict(IE_PRECISION="fp8", **env), kernels)
     want = "conv1x1_ws_f8_kernel" if tile < 200 else "conv3x3_ws_f8_kernel"
     nws = sum(k.startswith(want) for k in kern)
     assert nws >= (4 if tile < 200 else 2), kern         # (the strided 3x3 of a stage's first block stays on the tiled kernel)
     assert any(k.startswith("conv1x1_ws_f8_kernel<dual") for k in kern), kern          # the first block's projection shortcut: one launch, two GEMMs
-    plan, blob = _run_with_env(dict(IE_PRECISION="fp8", **env), lambda: (B.DescribeModel(path, 3)["plan"], B.PlanWeights(path, 3)))
+    plan, blob = with_env(dict(IE_PRECISION="fp8", **env), lambda: (B.DescribeModel(path, 3)["plan"], B.PlanWeights(path, 3)))
     if tile < 200:
         # Profile() names what was launched, step by step.  A 1x1 variant of tn x 32 output channels per workgroup declines a conv of at most
         # 32 x (tn / 2) of them (MFMA rows spent on padding: here the 32-channel reductions of stage 1 for every variant, the 64-channel
@@ -1786,7 +1774,7 @@ def test_fp8_deep_resnet_mini_vs_float64_oracle(tmp_path):
     x = models.synthetic_input((3, 3, 64, 64), stream="resnet_f8")
     ref = O.run(O.load_model(mb), {"data": x}, dtype=np.float64)["logits"]
     y, info = _fp8_run(path, "resnet_f8d", x, "data", "logits", [3, 20])
-    plan, blob = _run_with_env(dict(IE_PRECISION="fp8"), lambda: (B.DescribeModel(path, 3)["plan"], B.PlanWeights(path, 3)))
+    plan, blob = with_env(dict(IE_PRECISION="fp8"), lambda: (B.DescribeModel(path, 3)["plan"], B.PlanWeights(path, 3)))
     emu = F.run_plan(plan, blob, {"data": x}, act_scales=info["f8_act_scales"], fp8=True)["logits"]
     print(f"fp8 deep resnet mini: vs float64 oracle {rel_err(y, ref):.2e}, vs fp8 emulation {rel_err(y, emu):.2e}, emulation vs float64 {rel_err(emu, ref):.2e}")
     assert rel_err(y, ref) < F8_RTOL_MINI and rel_err(y, emu) < F8_RTOL_MINI
@@ -1801,7 +1789,7 @@ def test_fp8_resnet50_b2_vs_float64_oracle_and_emulation(tmp_path):
     x = models.synthetic_input((2, 3, 224, 224), stream="resnet50")
     ref = O.run(O.load_model(mb), {"data": x}, dtype=np.float64)["logits"]
     y, info = _fp8_run(path, "resnet50", x, "data", "logits", [2, 1000])
-    plan, blob = _run_with_env(dict(IE_PRECISION="fp8"), lambda: (B.DescribeModel(path, 2)["plan"], B.PlanWeights(path, 2)))
+    plan, blob = with_env(dict(IE_PRECISION="fp8"), lambda: (B.DescribeModel(path, 2)["plan"], B.PlanWeights(path, 2)))
     emu = F.run_plan(plan, blob, {"data": x}, act_scales=info["f8_act_scales"], fp8=True)["logits"]
     e_emu, e_ref = rel_err(y, emu), rel_err(y, ref)
     top5 = [set(np.argsort(r)[-5:]) for r in ref]
@@ -1879,7 +1867,7 @@ def test_fp8_rejects_graphs_it_cannot_run(densenet_repo):
     def go():
         with pytest.raises(RuntimeError, match="fp8 precision"):
             B.CreateModel(os.path.join(densenet_repo, "densenet_onnx", "1"), "densenet_onnx")
-    _run_with_env(dict(IE_PRECISION="fp8"), go)
+    with_env(dict(IE_PRECISION="fp8"), go)
 
 
 @pytest.mark.parametrize("fuse_tile", ["", "3", "4", "5"])
@@ -1907,10 +1895,10 @@ def test_fused_dense_layer_kernel(tmp_path, batch, image, blocks, fuse_tile):
     env = dict(IE_AUTOTUNE="0")
     if fuse_tile:
         env["IE_FUSE_PB"] = fuse_tile          # 3 = two-workgroups-per-CU variant of the 16-pixel tile; 4, 5 = wave-specialised variants
-    plan, y = _run_with_env(env, go)
+    plan, y = with_env(env, go)
     nf = [s for s in plan["steps"] if s.get("algo") == "dense_fused"]
     assert len(nf) >= sum(b - 1 for b in blocks) - 2, (len(nf), blocks)
-    plan0, y0 = _run_with_env(dict(IE_AUTOTUNE="0", IE_NO_DENSE_FUSE="1"), go)
+    plan0, y0 = with_env(dict(IE_AUTOTUNE="0", IE_NO_DENSE_FUSE="1"), go)
     assert not [s for s in plan0["steps"] if s.get("algo") == "dense_fused"]
     e, e0 = rel_err(y, ref), rel_err(y0, ref)
     print(f"fused dense layers B={batch} image={image}: {len(nf)} fused steps (tiles {sorted({s['tile'] for s in nf})}), rel err {e:.2e} (unfused {e0:.2e})")
@@ -1939,8 +1927,8 @@ def test_fp32_split_densenet121_full_size(densenet_repo):
             return y2, y32, y1, kernels
         finally:
             m.Destroy()
-    y2, y32, y1, kern = _run_with_env(dict(IE_FP32_SPLIT="1", IE_TUNE_CACHE="0", IE_TUNE_BATCHES="2,32"), run)      # the search runs at load, never in a request
-    n2, n32, _, kern0 = _run_with_env(dict(IE_TUNE_CACHE="0", IE_TUNE_BATCHES="2,32"), run)
+    y2, y32, y1, kern = with_env(dict(IE_FP32_SPLIT="1", IE_TUNE_CACHE="0", IE_TUNE_BATCHES="2,32"), run)      # the search runs at load, never in a request
+    n2, n32, _, kern0 = with_env(dict(IE_TUNE_CACHE="0", IE_TUNE_BATCHES="2,32"), run)
     nx = sum(k.startswith("conv1x1_x6_kernel") for k in kern)
     assert nx >= 12 and not any(k.startswith("conv1x1_x6_kernel") for k in kern0), (nx, kern)
     e, e0 = rel_err(y2, g["logits_f64"]), rel_err(n2, g["logits_f64"])
@@ -1974,10 +1962,10 @@ def test_bf16x6_1x1_kernel(tmp_path, tile, batch, image, blocks):
             m.Destroy()
         np.testing.assert_array_equal(y, y2)
         return plan, y
-    plan, y = _run_with_env(dict(IE_FP32_SPLIT="1", IE_FORCE_ALGO="x6", IE_FORCE_TILE=str(tile)), go)
+    plan, y = with_env(dict(IE_FP32_SPLIT="1", IE_FORCE_ALGO="x6", IE_FORCE_TILE=str(tile)), go)
     nx = [s for s in plan["steps"] if s.get("algo") == "conv1x1_x6"]
     assert len(nx) >= sum(blocks) and all(s["out"]["c"] % 128 == 0 and s["k"] == [1, 1] for s in nx)
-    _, y0 = _run_with_env(dict(IE_AUTOTUNE="0"), go)
+    _, y0 = with_env(dict(IE_AUTOTUNE="0"), go)
     e, e0 = rel_err(y, ref), rel_err(y0, ref)
     print(f"bf16x6 tile {tile} B={batch} image={image}: {len(nx)} convs, rel err {e:.2e} (native fp32 kernels {e0:.2e})")
     assert e < RTOL and e < 3 * e0 + 1e-7 and rel_err(y, y0) < 2e-5
@@ -2007,10 +1995,10 @@ def test_winograd_3x3_kernel(tmp_path, tile, batch, image, blocks):
     env = dict(IE_FORCE_ALGO="wino", IE_FORCE_TILE=str(tile))
     if tile >= 8:                                   # tiles 8-11: the Winograd-domain products as bf16x6 (opt-in mirror)
         env["IE_FP32_SPLIT"] = "1"
-    plan, y = _run_with_env(env, go)
+    plan, y = with_env(env, go)
     nw = [s for s in plan["steps"] if s.get("algo") == "wino3x3"]
     assert len(nw) == sum(blocks) and all(s["out"]["c"] == 32 for s in nw)
-    _, y0 = _run_with_env(dict(IE_AUTOTUNE="0"), go)
+    _, y0 = with_env(dict(IE_AUTOTUNE="0"), go)
     e = rel_err(y, ref)
     print(f"winograd tile {tile} B={batch} image={image}: {len(nw)} convs, rel err {e:.2e} (default kernels {rel_err(y0, ref):.2e})")
     assert e < RTOL and rel_err(y, y0) < 2e-5
@@ -2038,8 +2026,8 @@ def test_profile_names_the_kernel_that_was_launched(tmp_path, algo, tile, planne
             m.Destroy()
         return steps, y, prof
     env = dict(IE_FORCE_ALGO=algo, IE_FORCE_TILE=str(tile))
-    steps, y, prof = _run_with_env(env, go)
-    steps0, y0, prof0 = _run_with_env(dict(env, IE_NO_FRAG_WEIGHTS="1"), go)
+    steps, y, prof = with_env(env, go)
+    steps0, y0, prof0 = with_env(dict(env, IE_NO_FRAG_WEIGHTS="1"), go)
     idx = [i for i, s in enumerate(steps) if s.get("algo") == planned]
     assert len(idx) >= 4 and [s.get("algo") for s in steps0] == [s.get("algo") for s in steps]
     assert [p_["name"] for p_ in prof] == [s["name"] for s in steps] == [p_["name"] for p_ in prof0]

@@ -1,52 +1,23 @@
-"""GPU (-m gpu): grouped convolutions on the MI355X against a float64 torch-CPU walk of the same ONNX graph (tests/grouped_ref.py).
+"""GPU (-m gpu): grouped convolutions on the MI355X against a float64 torch-CPU walk of the same ONNX graph (tests/ref64.py).
 Bounds as tests/test_gpu_parity.py: fp32 within 2e-4 of max|ref|, fp16 within 3e-3."""
 import os
 
 import numpy as np
 import pytest
 
-import grouped_ref
+import ref64
+from engine_run import infer, RTOL, run_model, with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
 
 
 @pytest.fixture(autouse=True)
 def grouped_on(monkeypatch):
     """Grouped convolutions are opt-in (IE_GROUPED_CONV=1)."""
     monkeypatch.setenv("IE_GROUPED_CONV", "1")
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _infer(m, iname, x, oname, oshape):
-    r = m.Infer([B.TensorData(iname, B.DataTypeFloat32, B.Shape(list(x.shape)), x)], [B.OutputConfig(oname, Shape=list(oshape), DataType="FLOAT32")])
-    return r[0].Data.reshape(oshape)
-
-
-def _run_engine(path, name, env, iname, x, oname, oshape):
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            y = _infer(m, iname, x, oname, oshape)
-            return y, [p["kernel"] for p in B.Profile(m, 1)]
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
 
 
 # ---- seeded random grouped graphs ------------------------------------------------------------------------------------------------------
@@ -104,7 +75,7 @@ def _eligible_tiles(path, prec):
     """IE_FORCE_TILE values the planner keeps for the graph's grouped step (it falls back to its default for a tile the views do not admit)."""
     out = []
     for t in range(4):
-        plan = _with_env(dict(IE_PRECISION=prec, IE_FORCE_TILE=str(t)), lambda: B.DescribeModel(path, 2)["plan"])
+        plan = with_env(dict(IE_PRECISION=prec, IE_FORCE_TILE=str(t)), lambda: B.DescribeModel(path, 2)["plan"])
         (g,) = [st for st in plan["steps"] if st.get("algo") == "grouped"]
         if g["tile"] == t:
             out.append(t)
@@ -117,14 +88,14 @@ def test_random_grouped_graphs(tmp_path, cfg, prec):
     mb, oshape = _random_graph(cfg)
     path = models.write_repo(str(tmp_path), "grp", mb)
     x = models.synthetic_input((2, 4, cfg["h"], cfg["w"]), stream=f"grp{cfg['seed']}")
-    ref = grouped_ref.run_f64(mb, {"x": x})["y"]
+    ref = ref64.run_f64(mb, {"x": x})["y"]
     tiles = _eligible_tiles(path, prec)
     assert 0 in tiles
     for t in tiles:
-        y, kern = _run_engine(path, "grp", dict(IE_PRECISION=prec, IE_FORCE_TILE=str(t)), "x", x, "y", oshape)
+        y, kern = run_model(path, "grp", dict(IE_PRECISION=prec, IE_FORCE_TILE=str(t)), {"x": x}, "y", oshape)
         want = "conv_grouped_generic_kernel" if t == 0 else "conv_grouped_kernel<"
         assert any(q.startswith(want) for q in kern) and (t == 0 or f"px{[0, 1, 2, 4][t]}>" in " ".join(kern)), (t, kern)
-        err = grouped_ref.rel_err(y, ref)
+        err = ref64.rel_err(y, ref)
         assert err < RTOL[prec], (cfg, prec, t, err)
 
 
@@ -139,7 +110,7 @@ def nets(tmp_path_factory):
     for name, f in NETS.items():
         mb = f("N")
         x = models.synthetic_input((2, 3, 224, 224), stream=name)
-        out[name] = (mb, models.write_repo(root, name, mb), x, grouped_ref.run_f64(mb, {"data": x})["logits"])
+        out[name] = (mb, models.write_repo(root, name, mb), x, ref64.run_f64(mb, {"data": x})["logits"])
     return out
 
 
@@ -147,8 +118,8 @@ def nets(tmp_path_factory):
 @pytest.mark.parametrize("name", list(NETS))
 def test_networks_vs_float64(nets, name, prec):
     _, path, x, ref = nets[name]
-    y, kern = _run_engine(path, name, dict(IE_PRECISION=prec), "data", x, "logits", (2, 1000))
-    assert grouped_ref.rel_err(y, ref) < RTOL[prec]
+    y, kern = run_model(path, name, dict(IE_PRECISION=prec), {"data": x}, "logits", (2, 1000))
+    assert ref64.rel_err(y, ref) < RTOL[prec]
     assert (y.argmax(1) == ref.argmax(1)).all()
     grouped = [q for q in kern if q.startswith("conv_grouped")]
     assert len(grouped) == 16 and not any("generic" in q for q in grouped), kern
@@ -159,17 +130,17 @@ def test_resnext50_searched_set_fp32_b32(tmp_path):
     mb = models.resnext50_32x4d("N")
     path = models.write_repo(str(tmp_path), "rx_tuned", mb, config_json='{"tune_batches": [32]}')
     x = models.synthetic_input((32, 3, 224, 224), stream="rx_tuned")
-    ref = grouped_ref.run_f64(mb, {"data": x[:4]})["logits"]
+    ref = ref64.run_f64(mb, {"data": x[:4]})["logits"]
 
     def go():
         m = B.CreateModel(path, "rx_tuned")
         try:
-            y = _infer(m, "data", x, "logits", (32, 1000))
+            y = infer(m, {"data": x}, "logits", (32, 1000))
             return y, [p["kernel"] for p in B.Profile(m, 1)]
         finally:
             m.Destroy()
-    y, kern = _with_env(dict(IE_AUTOTUNE="1"), go)
-    assert grouped_ref.rel_err(y[:4], ref) < RTOL["fp32"]
+    y, kern = with_env(dict(IE_AUTOTUNE="1"), go)
+    assert ref64.rel_err(y[:4], ref) < RTOL["fp32"]
     assert (y[:4].argmax(1) == ref.argmax(1)).all()
     assert sum(q.startswith("conv_grouped") for q in kern) == 16
 
@@ -188,8 +159,8 @@ def test_replay_reruns_and_batch_independence(tmp_path, tile):
     def go():
         m = B.CreateModel(path, "mrx")
         try:
-            y_host = _infer(m, "data", x, "logits", (4, 20))
-            again = _infer(m, "data", x, "logits", (4, 20))
+            y_host = infer(m, {"data": x}, "logits", (4, 20))
+            again = infer(m, {"data": x}, "logits", (4, 20))
             np.testing.assert_array_equal(y_host, again)                           # reruns are bit-identical
             din, dout = B.Prepare(m, [[4, 3, 64, 64]], 1)
             B.CopyToDevice(m, din[0], x)
@@ -198,12 +169,12 @@ def test_replay_reruns_and_batch_independence(tmp_path, tile):
             B.CopyToHost(m, y, dout[0])
             np.testing.assert_array_equal(y, y_host)
             for i in (0, 3):
-                y1 = _infer(m, "data", x[i:i + 1], "logits", (1, 20))
-                assert grouped_ref.rel_err(y_host[i], y1[0]) < RTOL["fp32"], i
+                y1 = infer(m, {"data": x[i:i + 1]}, "logits", (1, 20))
+                assert ref64.rel_err(y_host[i], y1[0]) < RTOL["fp32"], i
             return [p["kernel"] for p in B.Profile(m, 1)]
         finally:
             m.Destroy()
-    kern = _with_env(dict(IE_AUTOTUNE="0", IE_FORCE_TILE=tile), go)
+    kern = with_env(dict(IE_AUTOTUNE="0", IE_FORCE_TILE=tile), go)
     assert sum(q.startswith("conv_grouped_kernel<") and q.endswith(f"px{[0, 1, 2, 4][int(tile)]}>") for q in kern) == 4, kern
 
 
@@ -223,14 +194,14 @@ def test_grouped_choices_survive_a_restart(tmp_path):
             return [p["kernel"] for p in B.Profile(m, 1)]
         finally:
             m.Destroy()
-    first = _with_env(dict(IE_AUTOTUNE="1"), kernels)
+    first = with_env(dict(IE_AUTOTUNE="1"), kernels)
     caches = [f for f in os.listdir(path) if f.startswith(".ie_tune")]
     assert len(caches) == 1, caches
     cache = os.path.join(path, caches[0])
     stamp = (os.stat(cache).st_mtime_ns, open(cache).read())
     entries = [(k.split(), int(v.split()[0])) for k, v in (ln.split(":") for ln in stamp[1].splitlines()[1:])]
     assert sum(len(k) == 18 and 800 <= code < 804 for k, code in entries) >= 4, entries        # 4 grouped convs per tuned batch size
-    second = _with_env(dict(IE_AUTOTUNE="1"), kernels)
+    second = with_env(dict(IE_AUTOTUNE="1"), kernels)
     assert (os.stat(cache).st_mtime_ns, open(cache).read()) == stamp
     assert second == first and sum(q.startswith("conv_grouped") for q in first) == 4
 
@@ -238,4 +209,4 @@ def test_grouped_choices_survive_a_restart(tmp_path):
 def test_fp8_model_with_grouped_conv_is_refused(tmp_path):
     path = models.write_repo(str(tmp_path), "rx_f8", _mini_resnext())
     with pytest.raises(Exception, match="grouped convolution is not supported in fp8 mode"):
-        _with_env(dict(IE_PRECISION="fp8", IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "rx_f8"))
+        with_env(dict(IE_PRECISION="fp8", IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "rx_f8"))

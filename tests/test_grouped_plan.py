@@ -9,7 +9,8 @@ import os
 import numpy as np
 import pytest
 
-import grouped_ref
+import ref64
+from engine_run import describe
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
@@ -47,11 +48,6 @@ def grouped_on(monkeypatch):
     monkeypatch.setenv("IE_GROUPED_CONV", "1")
 
 
-def _describe(path, batch, monkeypatch, prec):
-    monkeypatch.setenv("IE_PRECISION", prec)
-    return B.DescribeModel(path, batch)["plan"]
-
-
 def _grouped(p):
     return [s for s in p["steps"] if s.get("algo") == "grouped"]
 
@@ -60,13 +56,13 @@ def _check_conv_flops(p, mb, batch):
     """The conv steps' FLOPs are 2x the graph's conv + Gemm MACs (a fused stem + max-pool step also counts the pool's 9 compares per output)."""
     convs = [s for s in p["steps"] if s["kind"] == "conv"]
     pool = sum(9 * s["out"]["n"] * s["out"]["c"] * s["out"]["h"] * s["out"]["w"] for s in convs if s["algo"] == "stem_pool")
-    assert sum(s["flops"] for s in convs) - pool == 2 * grouped_ref.conv_macs(mb, (batch, 3, 224, 224))
+    assert sum(s["flops"] for s in convs) - pool == 2 * sum(ref64.conv_macs(mb, (batch, 3, 224, 224)).values())
 
 
 @pytest.mark.parametrize("prec,batch", [("fp32", 32), ("fp16", 128)])
 def test_resnext50_plan(nets, monkeypatch, prec, batch):
     mb, path = nets["resnext50"]
-    p = _describe(path, batch, monkeypatch, prec)
+    p = describe(path, batch, monkeypatch, prec)
     g = _grouped(p)
     assert len(g) == 16 and all(s["group"] == 32 and s["k"] == [3, 3] and s["pads"] == [1, 1, 1, 1] for s in g)
     # Cin / group = 4 / 8 / 16 / 32 by stage (128 / 256 / 512 / 1024 channels at 56 / 28 / 14 / 7), stride 2 on the first block of stages 2-4
@@ -85,14 +81,14 @@ def test_resnext50_plan(nets, monkeypatch, prec, batch):
 def test_resnext50_fp32_structure_equals_resnet50(nets, monkeypatch):
     def structure(p):
         return [(s["kind"], s.get("residual", False), s["relu"]) for s in p["steps"]]
-    px = _describe(nets["resnext50"][1], 32, monkeypatch, "fp32")
-    pr = _describe(nets["resnet50"][1], 32, monkeypatch, "fp32")
+    px = describe(nets["resnext50"][1], 32, monkeypatch, "fp32")
+    pr = describe(nets["resnet50"][1], 32, monkeypatch, "fp32")
     assert structure(px) == structure(pr)
 
 
 @pytest.mark.parametrize("prec,batch", [("fp32", 32), ("fp16", 128)])
 def test_regnet_plans(nets, monkeypatch, prec, batch):
-    p = _describe(nets["regnet_y"][1], batch, monkeypatch, prec)
+    p = describe(nets["regnet_y"][1], batch, monkeypatch, prec)
     g = _grouped(p)
     ses = [s for s in p["steps"] if s["kind"] == "squeeze_excite"]
     assert len(g) == 16 and len(ses) == 16
@@ -100,7 +96,7 @@ def test_regnet_plans(nets, monkeypatch, prec, batch):
     assert all(s["in"]["c"] // s["group"] == 8 and s["tile"] != 0 for s in g)       # group width 8, 104 and 440 included
     # the squeeze-excite reads the grouped conv's output
     assert all(p["steps"][s["in_src"]].get("algo") == "grouped" for s in ses)
-    p = _describe(nets["regnet_x"][1], batch, monkeypatch, prec)
+    p = describe(nets["regnet_x"][1], batch, monkeypatch, prec)
     g = _grouped(p)
     assert len(g) == 22 and all(s["in"]["c"] // s["group"] == 16 and s["tile"] != 0 for s in g)
     assert [s["in"]["c"] for s in g] == [32] + [64] * 2 + [160] * 7 + [400] * 12

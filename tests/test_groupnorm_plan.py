@@ -1,12 +1,13 @@
 """CPU: GroupNorm through the ONNX reader and the planner (EngineDescribeModel): every spelling of a group norm becomes the same `group_norm`
 step with the same weight blob, the activation behind it fuses, near misses are refused by name, and the GroupNorm ResNet and the VAE decoder
-plan into the expected steps.  The float64 reference of tests/gn_ref.py is checked against a torch restatement of the decoder, and the test data
+plan into the expected steps.  The float64 reference of tests/ref64.py is checked against a torch restatement of the decoder, and the test data
 against three broken ways of taking the statistics."""
 import numpy as np
 import pytest
 
 import gn_graphs as G
-import gn_ref
+import ref64
+from engine_run import describe
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
@@ -15,17 +16,8 @@ PRECS = ("fp32", "fp16")
 RTOL16 = 3e-3
 
 
-def _describe(path, batch, monkeypatch, prec, **env):
-    monkeypatch.setenv("IE_PRECISION", prec)
-    for k in ("IE_FORCE_TILE", "IE_FORCE_ALGO", "IE_FORCE_SPLITK"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    return B.DescribeModel(path, batch)["plan"]
-
-
 def _plan_of(tmp_path, name, mb, monkeypatch, prec="fp32", batch=2, **env):
-    return _describe(models.write_repo(str(tmp_path), name, mb), batch, monkeypatch, prec, **env)
+    return describe(models.write_repo(str(tmp_path), name, mb), batch, monkeypatch, prec, **env)
 
 
 # ---- one step from every spelling ------------------------------------------------------------------------------------------------------------
@@ -45,7 +37,7 @@ def test_same_plan_from_every_spelling(tmp_path, monkeypatch, prec):
     steps, blobs = {}, {}
     for key, kw in SPELLINGS.items():
         path = models.write_repo(str(tmp_path), key, G.gn_graph(n, c, h, w, g, act="silu", per_group=True, **kw))
-        plan = _describe(path, n, monkeypatch, prec)
+        plan = describe(path, n, monkeypatch, prec)
         assert [s["kind"] for s in plan["steps"]] == ["copy", "group_norm", "copy"], key
         s = dict(G.gn_step(plan))
         assert s.pop("name").startswith("gn")
@@ -72,7 +64,7 @@ def test_inner_scale_and_bias_fold_exactly(tmp_path, monkeypatch):
     n, c, h, w, g = 1, 16, 4, 4, 4
     mb = G.gn_graph(n, c, h, w, g, inner="random")
     path = models.write_repo(str(tmp_path), "inner", mb)
-    s = G.gn_step(_describe(path, n, monkeypatch, "fp32"))
+    s = G.gn_step(describe(path, n, monkeypatch, "fp32"))
     blob = B.PlanWeights(path, n)
     from oracle import onnx_oracle as O
     I = O.load_model(mb).inits
@@ -81,12 +73,12 @@ def test_inner_scale_and_bias_fold_exactly(tmp_path, monkeypatch):
     np.testing.assert_array_equal(blob[s["w_off"]:s["w_off"] + c], si * ga)
     np.testing.assert_array_equal(blob[s["bias_off"]:s["bias_off"] + c], bi * ga + be)
     path = models.write_repo(str(tmp_path), "plain", G.gn_graph(n, c, h, w, g, affine=False))
-    s = G.gn_step(_describe(path, n, monkeypatch, "fp32"))
+    s = G.gn_step(describe(path, n, monkeypatch, "fp32"))
     blob = B.PlanWeights(path, n)
     assert (blob[s["w_off"]:s["w_off"] + c] == 1).all() and (blob[s["bias_off"]:s["bias_off"] + c] == 0).all()
     mb = G.gn_graph(n, c, h, w, c, form="instance")
     path = models.write_repo(str(tmp_path), "inst", mb)
-    s = G.gn_step(_describe(path, n, monkeypatch, "fp32"))
+    s = G.gn_step(describe(path, n, monkeypatch, "fp32"))
     assert s["groups"] == c and s["name"] == "gn"
     np.testing.assert_array_equal(B.PlanWeights(path, n)[s["w_off"]:s["w_off"] + c], O.load_model(mb).inits["gn_scale"])
 
@@ -128,9 +120,9 @@ def test_tiles_and_workspace(tmp_path, monkeypatch, shape, prec):
     f16 = prec == "fp16"
     path = models.write_repo(str(tmp_path), "t", G.gn_graph(n, c, h, w, g))
     fits = G.gn_tile_fits(c, g, f16)
-    assert G.gn_step(_describe(path, n, monkeypatch, prec))["tile"] == G.gn_default_tile(c, g, h * w, f16)
-    assert G.gn_step(_describe(path, n, monkeypatch, prec, IE_FORCE_TILE="0"))["tile"] == 0
-    plan = _describe(path, n, monkeypatch, prec, IE_FORCE_TILE="1")
+    assert G.gn_step(describe(path, n, monkeypatch, prec))["tile"] == G.gn_default_tile(c, g, h * w, f16)
+    assert G.gn_step(describe(path, n, monkeypatch, prec, IE_FORCE_TILE="0"))["tile"] == 0
+    plan = describe(path, n, monkeypatch, prec, IE_FORCE_TILE="1")
     assert G.gn_step(plan)["tile"] == (1 if fits else 0)
     if fits:
         assert plan["workspace_floats"] >= 3 * n * G.gn_slabs(n, h * w, c, f16)[1] * g
@@ -185,14 +177,14 @@ def test_refusals(tmp_path, monkeypatch, case):
     build, match = REFUSALS[case]
     path = models.write_repo(str(tmp_path), "bad", build())
     with pytest.raises(RuntimeError, match=match):
-        _describe(path, 2, monkeypatch, "fp32")
+        describe(path, 2, monkeypatch, "fp32")
 
 
 @pytest.mark.parametrize("form", ["instancenorm", "op21", "instance"])
 def test_fp8_is_refused(tmp_path, monkeypatch, form):
     path = models.write_repo(str(tmp_path), "f8", G.gn_graph(2, 16, 4, 4, 16 if form == "instance" else 4, form=form))
     with pytest.raises(RuntimeError, match=r"^GroupNormalization is not supported in fp8 mode \(node gn"):
-        _describe(path, 2, monkeypatch, "fp8")
+        describe(path, 2, monkeypatch, "fp8")
 
 
 # ---- whole networks --------------------------------------------------------------------------------------------------------------------------
@@ -205,7 +197,7 @@ def decoder_paths(tmp_path_factory):
 @pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("form", ["instancenorm", "op18"])
 def test_vae_decoder_plan(decoder_paths, monkeypatch, form, prec):
-    plan = _describe(decoder_paths[form], 2, monkeypatch, prec)
+    plan = describe(decoder_paths[form], 2, monkeypatch, prec)
     steps = plan["steps"]
     kinds = [s["kind"] for s in steps]
     layers, nm = G.NARROW["layers"], len(G.NARROW["mults"])
@@ -262,11 +254,11 @@ def test_decoder_graph_is_the_decoder():
     """the float64 walk of the written graph against torch's own operators on the same weights: the graph writer's structure is diffusers'"""
     z = G.half_exact(np.random.RandomState(5).randn(2, 4, 8, 8))
     mb = G.narrow_decoder(2)
-    ref = gn_ref.run_f64(mb, {"latent_sample": z})["sample"]
+    ref = ref64.run_f64(mb, {"latent_sample": z})["sample"]
     assert ref.shape == (2, 3, 64, 64) and np.abs(ref).max() > 0.1
     assert np.abs(G.decoder_torch_f64(mb, z, **G.NARROW) - ref).max() < 1e-10
     for form in ("op18", "op21"):          # (their gamma / beta are other draws: only the structure is compared, through the shapes)
-        assert gn_ref.run_f64(G.narrow_decoder(2, gn_form=form), {"latent_sample": z})["sample"].shape == ref.shape
+        assert ref64.run_f64(G.narrow_decoder(2, gn_form=form), {"latent_sample": z})["sample"].shape == ref.shape
 
 
 def test_group_norm_reference_agrees_with_torch():
@@ -275,7 +267,7 @@ def test_group_norm_reference_agrees_with_torch():
     st = np.random.RandomState(3)
     x, g, b = 3.0 + st.randn(2, 12, 5, 7), st.randn(12), st.randn(12)
     t = F.group_norm(torch.from_numpy(x), 4, torch.from_numpy(g), torch.from_numpy(b), 1e-5).numpy()
-    assert np.abs(gn_ref.group_norm(x, 4, g, b, 1e-5) - t).max() < 1e-12
+    assert np.abs(ref64.group_norm(x, 4, g, b, 1e-5) - t).max() < 1e-12
 
 
 @pytest.mark.parametrize("shape", [(2, 32, 5, 7, 8), (2, 128, 16, 16, 32), (2, 16, 6, 6, 16)])
@@ -284,10 +276,10 @@ def test_group_distinct_data_tells_broken_statistics_apart(shape):
     the float64 result by more than 30 x the fp16 bound on the group-distinct data: a kernel that did any of these could not pass."""
     n, c, h, w, g = shape
     x = G.data("distinct", n, c, h, w, g)
-    ref = gn_ref.group_norm(x, g)
+    ref = ref64.group_norm(x, g)
     scale = np.abs(ref).max()
-    broken = {"image": gn_ref.group_norm(x, g, stats="image"), "batch": gn_ref.group_norm(x, g, stats="batch")}
+    broken = {"image": ref64.group_norm(x, g, stats="image"), "batch": ref64.group_norm(x, g, stats="batch")}
     if c // g > 1:                         # (with one channel per group there is no boundary to move)
-        broken["shift"] = gn_ref.group_norm(x, g, shift=1)
+        broken["shift"] = ref64.group_norm(x, g, shift=1)
     for what, y in broken.items():
         assert np.abs(y - ref).max() / scale > 30 * RTOL16, (what, np.abs(y - ref).max() / scale)

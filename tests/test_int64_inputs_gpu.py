@@ -1,33 +1,20 @@
 """GPU (-m gpu): INT64 graph inputs through the C ABI -- payload types, sizes, the request batcher, the row-slice sharder, the device-resident entry
 points -- on the embed graph of tests/bert_graphs.py (ids -> embedding sum -> LayerNormalization -> y [N, D, 1, L]) against the float64 walk of
-tests/bert_ref.py, fp32 within 2e-4 of max|ref| (tests/test_gpu_parity.py)."""
-import os
+tests/ref64.py, fp32 within 2e-4 of max|ref| (tests/test_gpu_parity.py)."""
 import threading
 
 import numpy as np
 import pytest
 
 import bert_graphs as G
-import bert_ref
+import ref64
+from engine_run import with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 
 pytestmark = pytest.mark.gpu
 RTOL = 2e-4
 L, V, D = 6, 23, 16
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.fixture(scope="module")
@@ -38,7 +25,7 @@ def net(tmp_path_factory):
     st = np.random.RandomState(3)
     ids = st.randint(-V, V, size=(8, L)).astype(np.int64)
     tt = st.randint(0, 2, size=(8, L)).astype(np.int64)
-    ref = bert_ref.run_f64(G.embed_graph(8, L, V, D), {"input_ids": ids, "token_type_ids": tt})["y"]
+    ref = ref64.run_f64(G.embed_graph(8, L, V, D), {"input_ids": ids, "token_type_ids": tt})["y"]
     for a in (ids, tt, ref):
         a.setflags(write=False)
     return path, ids, tt, ref
@@ -69,7 +56,7 @@ def test_payload_types_and_sizes(net, tmp_path):
             short = [B.TensorData("input_ids", B.DataTypeInt64, B.Shape([2, L]), ids[:1]), B.TensorData("token_type_ids", B.DataTypeInt64, B.Shape([2, L]), tt[:2])]
             with pytest.raises(RuntimeError, match=r"Invalid data size for input: input_ids Got: %d bytes Expected: %d bytes" % (L * 8, 2 * L * 8)):
                 m.Infer(short, [B.OutputConfig("y", Shape=[2, D, 1, L], DataType="FLOAT32")])
-            assert bert_ref.rel_err(_infer(m, ids[:2], tt[:2]), ref[:2]) < RTOL
+            assert ref64.rel_err(_infer(m, ids[:2], tt[:2]), ref[:2]) < RTOL
         finally:
             m.Destroy()
         # INT64 for a float input: the same text
@@ -81,7 +68,7 @@ def test_payload_types_and_sizes(net, tmp_path):
                 f.Infer([B.TensorData("input", B.DataTypeInt64, B.Shape([1, 3]), x)], [B.OutputConfig("output", [1, 2])])
         finally:
             f.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
 
 
 def test_replay_is_bit_equal_and_device_resident_ids_are_clamped(net):
@@ -100,7 +87,7 @@ def test_replay_is_bit_equal_and_device_resident_ids_are_clamped(net):
             y = np.empty((4, D, 1, L), np.float32)
             B.CopyToHost(m, y, dout[0])
             np.testing.assert_array_equal(y, y_host)
-            assert bert_ref.rel_err(y, ref[:4]) < RTOL
+            assert ref64.rel_err(y, ref[:4]) < RTOL
             wild, tame = ids[:4].copy(), ids[:4].copy()
             wild[0, 0], tame[0, 0] = V + 100, V - 1
             wild[3, L - 1], tame[3, L - 1] = -V - 5, 0
@@ -110,7 +97,7 @@ def test_replay_is_bit_equal_and_device_resident_ids_are_clamped(net):
             np.testing.assert_array_equal(y, _infer(m, tame, tt[:4]))
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32"), go)
 
 
 def test_batcher_coalesces_integer_rows(net):
@@ -137,10 +124,10 @@ def test_batcher_coalesces_integer_rows(net):
             assert not errs, errs
             assert B.BatcherStats(m)["coalesced_requests"] - before["coalesced_requests"] == 3
             for lo, hi in spans:
-                assert bert_ref.rel_err(out[lo], ref[lo:hi]) < RTOL, (lo, hi)
+                assert ref64.rel_err(out[lo], ref[lo:hi]) < RTOL, (lo, hi)
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32", IE_DYNAMIC_BATCH="8", IE_BATCH_WINDOW_US="200000"), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32", IE_DYNAMIC_BATCH="8", IE_BATCH_WINDOW_US="200000"), go)
 
 
 def test_sharder_slices_integer_rows(net):
@@ -153,7 +140,7 @@ def test_sharder_slices_integer_rows(net):
             assert B.ShardStats(m) == (3, 0)
             y = _infer(m, ids, tt)
             assert B.ShardStats(m) == (3, 1)
-            assert bert_ref.rel_err(y, ref) < RTOL
+            assert ref64.rel_err(y, ref) < RTOL
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32", IE_SHARD_DEVICES="0,0,0"), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp32", IE_SHARD_DEVICES="0,0,0"), go)

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the layer-norm kernels on the MI355X against the float64 restatement of the ONNX definition in tests/convnext_ref.py, per
+"""GPU (-m gpu): the layer-norm kernels on the MI355X against the float64 restatement of the ONNX definition in tests/ref64.py, per
 element, with the project's bounds (tests/test_gpu_parity.py): fp32 within 2e-4 of max|ref|, fp16 within 3e-3.
 
 Graph of every case but the last two: fp32 x [N, C, H, W] -> Transpose(0,2,3,1) -> LayerNormalization -> Transpose(0,3,1,2) -> y.  Every case runs
@@ -6,45 +6,18 @@ on the planner's default tile and on every eligible one (IE_FORCE_TILE 0 ... 4),
 N, H, W = 2, 3, 5: 30 pixel rows, a multiple of no tile's rows per workgroup (4 for the generic kernel; 32 / 16 / 8 / 4 for tiles 1-4).
 C: 6 generic only; 8 one fp16 vector; 96 a partly idle lane group; 100 fp32-fast but fp16-generic; 768 a full group; 1536 the largest row held in
 registers (fp32); 1540 just past it."""
-import os
 
 import numpy as np
 import pytest
 
 import convnext_graphs as G
-import convnext_ref
-from gpu_ai_inference_server_amd import binding as B
+import ref64
+from engine_run import plan_of, RTOL, run_model
 from gpu_ai_inference_server_amd.modelgen import models
 from oracle import onnx_oracle as O
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
 N, H, W = 2, 3, 5
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _run(path, name, env, x, oshape):
-    """-> (output, {step name: launched kernel})"""
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            r = m.Infer([B.TensorData("x", B.DataTypeFloat32, B.Shape(list(x.shape)), x)], [B.OutputConfig("y", Shape=list(oshape), DataType="FLOAT32")])
-            return r[0].Data.reshape(oshape), {p["name"]: p["kernel"] for p in B.Profile(m, 1)}
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
 
 
 def _every_tile(path, name, prec, x, oshape, check, expect_fast=None):
@@ -52,11 +25,12 @@ def _every_tile(path, name, prec, x, oshape, check, expect_fast=None):
     ran = []
     for forced in (None, 0, 1, 2, 3, 4):
         env = dict(IE_PRECISION=prec, **({} if forced is None else {"IE_FORCE_TILE": str(forced)}))
-        (ln,) = [s for s in _with_env(env, lambda: B.DescribeModel(path, x.shape[0])["plan"])["steps"] if s["kind"] == "layer_norm"]
+        (ln,) = [s for s in plan_of(path, x.shape[0], env)["steps"] if s["kind"] == "layer_norm"]
         if forced is not None and ln["tile"] != forced:
             assert ln["tile"] == 0                      # not eligible: the generic kernel, which forced tile 0 runs
             continue
-        y, kern = _run(path, name, env, x, oshape)
+        y, kern = run_model(path, name, env, {"x": x}, "y", oshape, by_step=True)
+        kern = dict(kern)
         assert kern["ln"] == G.ln_label(ln["tile"], ln["out"]["f16"]), (forced, ln["tile"], kern["ln"])
         check(y, ln["tile"], forced)
         ran.append(ln["tile"])
@@ -66,7 +40,7 @@ def _every_tile(path, name, prec, x, oshape, check, expect_fast=None):
 
 
 def _ref_of(mb, x):
-    return convnext_ref.run_f64(mb, {"x": x})["y"]
+    return ref64.run_f64(mb, {"x": x})["y"]
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
@@ -137,7 +111,7 @@ def test_layer_norm_into_a_concat(tmp_path, c, prec):
     path = models.write_repo(str(tmp_path), "lncat", mb)
     x = np.random.RandomState(c).randn(N, 4, H, W).astype(np.float32)
     ref = _ref_of(mb, x)
-    plan = _with_env(dict(IE_PRECISION=prec), lambda: B.DescribeModel(path, N)["plan"])
+    plan = plan_of(path, N, dict(IE_PRECISION=prec))
     (ln,) = [s for s in plan["steps"] if s["kind"] == "layer_norm"]
     assert (ln["in"]["c_off"], ln["in"]["pitch"], ln["out"]["c_off"], ln["out"]["pitch"], ln["in"]["buf"]) == (0, 2 * c, c, 2 * c, ln["out"]["buf"])
     assert [s["name"] for s in plan["steps"] if s["kind"] == "copy"] == ["to_output(y)"]

@@ -1,49 +1,18 @@
 """GPU (-m gpu): squeeze-excite blocks and the MobileNetV3 / EfficientNet activations on the MI355X against a float64 torch-CPU walk of the same
-ONNX graph (tests/se_ref.py), the fused SE step against its IE_NO_SE_FUSE=1 form.  Bounds as tests/test_depthwise_gpu.py: fp32 within 2e-4 of
+ONNX graph (tests/ref64.py), the fused SE step against its IE_NO_SE_FUSE=1 form.  Bounds as tests/test_depthwise_gpu.py: fp32 within 2e-4 of
 max|ref|, fp16 within 3e-3."""
-import os
 
 import numpy as np
 import pytest
 
-import se_ref
+import ref64
+from engine_run import infer, plan_of, RTOL, run_model, with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
 SE_KERNELS = "se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel"
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _infer(m, iname, x, oname, oshape):
-    r = m.Infer([B.TensorData(iname, B.DataTypeFloat32, B.Shape(list(x.shape)), x)], [B.OutputConfig(oname, Shape=list(oshape), DataType="FLOAT32")])
-    return r[0].Data.reshape(oshape)
-
-
-def _run_engine(path, name, env, iname, x, oname, oshape, want_kernels=False):
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            y = _infer(m, iname, x, oname, oshape)
-            kern = [p["kernel"] for p in B.Profile(m, 1)] if want_kernels else None
-            return y, kern
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
 
 
 # ---- seeded random SE / activation graphs ---------------------------------------------------------------------------------------------
@@ -83,8 +52,8 @@ def test_random_se_graphs(tmp_path, cfg, prec):
     mb, oshape = _random_graph(cfg)
     path = models.write_repo(str(tmp_path), "se", mb)
     x = models.synthetic_input((2, 4, cfg["h"], cfg["w"]), stream=f"se{cfg['seed']}")
-    ref = se_ref.run_f64(mb, {"x": x})["y"]
-    plan = _with_env(dict(IE_PRECISION=prec), lambda: B.DescribeModel(path, 2)["plan"])
+    ref = ref64.run_f64(mb, {"x": x})["y"]
+    plan = plan_of(path, 2, dict(IE_PRECISION=prec))
     fused = any(st["kind"] == "squeeze_excite" for st in plan["steps"])
     oh, ow = oshape[2:]
     assert fused == (oh * ow > 1)                 # (a 1x1 map: the gate Mul has two [N,C,1,1] operands, an eltwise step)
@@ -92,15 +61,15 @@ def test_random_se_graphs(tmp_path, cfg, prec):
     tiles = ["0"] + (["1", "2", "3"] if dws and dws[0]["tile"] != 0 else [])
     outs = {}
     for t in tiles:
-        y, kern = _run_engine(path, "se", dict(IE_PRECISION=prec, IE_FORCE_TILE=t), "x", x, "y", oshape, want_kernels=True)
+        y, kern = run_model(path, "se", dict(IE_PRECISION=prec, IE_FORCE_TILE=t), {"x": x}, "y", oshape)
         assert (SE_KERNELS in " ".join(kern)) == fused, kern
-        err = se_ref.rel_err(y, ref)
+        err = ref64.rel_err(y, ref)
         assert err < RTOL[prec], (cfg, prec, t, err)
         outs[t] = y
-    y_unf, kern = _run_engine(path, "se", dict(IE_PRECISION=prec, IE_NO_SE_FUSE="1"), "x", x, "y", oshape, want_kernels=True)
+    y_unf, kern = run_model(path, "se", dict(IE_PRECISION=prec, IE_NO_SE_FUSE="1"), {"x": x}, "y", oshape)
     assert not any(SE_KERNELS in q for q in kern)
-    assert se_ref.rel_err(y_unf, ref) < RTOL[prec], (cfg, prec, "unfused")
-    assert se_ref.rel_err(outs["0"], y_unf) < RTOL[prec]
+    assert ref64.rel_err(y_unf, ref) < RTOL[prec], (cfg, prec, "unfused")
+    assert ref64.rel_err(outs["0"], y_unf) < RTOL[prec]
 
 
 # ---- the networks -----------------------------------------------------------------------------------------------------------------------
@@ -117,10 +86,10 @@ def test_mini_networks(tmp_path, name, prec):
     mb = NETS[name](width_mult=0.5, image=64, classes=50, seed=91)
     path = models.write_repo(str(tmp_path), "mini_" + name, mb)
     x = models.synthetic_input((2, 3, 64, 64), stream="mini_" + name)
-    ref = se_ref.run_f64(mb, {"data": x})["logits"]
-    y, kern = _run_engine(path, "mini_" + name, dict(IE_PRECISION=prec), "data", x, "logits", (2, 50), want_kernels=True)
+    ref = ref64.run_f64(mb, {"data": x})["logits"]
+    y, kern = run_model(path, "mini_" + name, dict(IE_PRECISION=prec), {"data": x}, "logits", (2, 50))
     assert sum(SE_KERNELS in q for q in kern) == {"mnv3_large": 8, "mnv3_small": 9, "effnet_b0": 16}[name], kern
-    assert se_ref.rel_err(y, ref) < RTOL[prec]
+    assert ref64.rel_err(y, ref) < RTOL[prec]
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
@@ -129,12 +98,12 @@ def test_full_networks_vs_float64(tmp_path, name, prec):
     mb = NETS[name]()
     path = models.write_repo(str(tmp_path), name, mb)
     x = models.synthetic_input((2, 3, 224, 224), stream=name)
-    ref = se_ref.run_f64(mb, {"data": x})["logits"]
-    y, kern = _run_engine(path, name, dict(IE_PRECISION=prec), "data", x, "logits", (2, 1000), want_kernels=True)
+    ref = ref64.run_f64(mb, {"data": x})["logits"]
+    y, kern = run_model(path, name, dict(IE_PRECISION=prec), {"data": x}, "logits", (2, 1000))
     # fused activations launch nothing of their own: the only eltwise launches are the classifier's hardswish (and MobileNetV3-Large's stem
     # activation, read by a depthwise conv and an identity Add)
     assert sum(q == "eltwise_kernel" for q in kern) == {"mnv3_large": 2, "mnv3_small": 1, "effnet_b0": 0}[name], kern
-    assert se_ref.rel_err(y, ref) < RTOL[prec]
+    assert ref64.rel_err(y, ref) < RTOL[prec]
     if prec == "fp32":
         assert (y.argmax(1) == ref.argmax(1)).all()
 
@@ -143,7 +112,7 @@ def test_full_networks_vs_float64(tmp_path, name, prec):
 def effnet(tmp_path_factory):
     mb = models.efficientnet_b0("N", width_mult=0.5, image=96, classes=100, seed=92)
     path = models.write_repo(str(tmp_path_factory.mktemp("effnet")), "effnet", mb)
-    m = _with_env(dict(IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "effnet"))
+    m = with_env(dict(IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "effnet"))
     yield mb, path, m
     m.Destroy()
 
@@ -152,17 +121,17 @@ def test_batch_independence(effnet):
     """Image i of a batch of 8 against the same image alone: a per-(n, c) indexing slip in the gate shows here."""
     _, _, m = effnet
     x = models.synthetic_input((8, 3, 96, 96), stream="effb")
-    y8 = _infer(m, "data", x, "logits", (8, 100))
+    y8 = infer(m, {"data": x}, "logits", (8, 100))
     for i in (0, 3, 7):
-        y1 = _infer(m, "data", x[i:i + 1], "logits", (1, 100))
-        assert se_ref.rel_err(y8[i], y1[0]) < RTOL["fp32"], i
+        y1 = infer(m, {"data": x[i:i + 1]}, "logits", (1, 100))
+        assert ref64.rel_err(y8[i], y1[0]) < RTOL["fp32"], i
 
 
 def test_graph_replay_matches_model_infer_and_runs_are_bit_identical(effnet):
     _, _, m = effnet
     x = models.synthetic_input((4, 3, 96, 96), stream="effr")
-    y_host = _infer(m, "data", x, "logits", (4, 100))
-    np.testing.assert_array_equal(_infer(m, "data", x, "logits", (4, 100)), y_host)      # no atomics: two runs agree bit for bit
+    y_host = infer(m, {"data": x}, "logits", (4, 100))
+    np.testing.assert_array_equal(infer(m, {"data": x}, "logits", (4, 100)), y_host)      # no atomics: two runs agree bit for bit
     din, dout = B.Prepare(m, [[4, 3, 96, 96]], 1)
     B.CopyToDevice(m, din[0], x)
     B.RunPrepared(m, 2, True)
@@ -179,12 +148,12 @@ def test_mobilenet_v3_large_fp16_batch_independence(tmp_path):
     def go():
         m = B.CreateModel(path, "mnv3")
         try:
-            y8 = _infer(m, "data", x, "logits", (8, 40))
-            return y8, [_infer(m, "data", x[i:i + 1], "logits", (1, 40))[0] for i in (1, 6)]
+            y8 = infer(m, {"data": x}, "logits", (8, 40))
+            return y8, [infer(m, {"data": x[i:i + 1]}, "logits", (1, 40))[0] for i in (1, 6)]
         finally:
             m.Destroy()
-    y8, singles = _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp16"), go)
+    y8, singles = with_env(dict(IE_AUTOTUNE="0", IE_PRECISION="fp16"), go)
     for i, y1 in zip((1, 6), singles):
-        assert se_ref.rel_err(y8[i], y1) < RTOL["fp16"], i
-    ref = se_ref.run_f64(mb, {"data": x})["logits"]
-    assert se_ref.rel_err(y8, ref) < RTOL["fp16"]
+        assert ref64.rel_err(y8[i], y1) < RTOL["fp16"], i
+    ref = ref64.run_f64(mb, {"data": x})["logits"]
+    assert ref64.rel_err(y8, ref) < RTOL["fp16"]

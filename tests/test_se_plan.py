@@ -4,7 +4,7 @@ refusals."""
 import numpy as np
 import pytest
 
-import se_ref
+import ref64
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
@@ -65,7 +65,7 @@ def _check_plan(name, p, mb, batch):
     (gap,) = [s for s in steps if s["kind"] == "gap"]
     assert _act(gap, "pre_act") == ("silu" if name == "effnet_b0" else "hardswish")
     # FLOPs: the conv steps plus the SE blocks' two FCs = 2 x the MACs of the ONNX graph's convs and Gemms
-    macs = se_ref.conv_macs(mb, (batch, 3, 224, 224))
+    macs = sum(ref64.conv_macs(mb, (batch, 3, 224, 224)).values())
     fc = sum(4 * s["in"]["n"] * s["in"]["c"] * s["se"]["mid"] for s in ses)
     assert abs((sum(s["flops"] for s in steps if s["kind"] == "conv") + fc) / (2 * macs) - 1) < 1e-6
     for s in ses:

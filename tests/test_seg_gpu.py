@@ -1,46 +1,16 @@
-"""GPU (-m gpu): dilated convolutions and Resize on the MI355X against a float64 torch-CPU walk of the same ONNX graph (tests/seg_ref.py).
+"""GPU (-m gpu): dilated convolutions and Resize on the MI355X against a float64 torch-CPU walk of the same ONNX graph (tests/ref64.py).
 Bounds as tests/test_gpu_parity.py: fp32 within 2e-4 of max|ref|, fp16 within 3e-3."""
-import os
 
 import numpy as np
 import pytest
 
-import seg_ref
+import ref64
+from engine_run import infer, plan_of, RTOL, run_model, with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
-
-
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _infer(m, iname, x, oname, oshape):
-    r = m.Infer([B.TensorData(iname, B.DataTypeFloat32, B.Shape(list(x.shape)), x)], [B.OutputConfig(oname, Shape=list(oshape), DataType="FLOAT32")])
-    return r[0].Data.reshape(oshape)
-
-
-def _run_engine(path, name, env, iname, x, oname, oshape):
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            y = _infer(m, iname, x, oname, oshape)
-            return y, [p["kernel"] for p in B.Profile(m, 1)]
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
 
 
 # ---- seeded random dilated convs ---------------------------------------------------------------------------------------------------------
@@ -94,21 +64,21 @@ def test_random_dilated_convs(tmp_path, seed, prec):
     mb, oshape = _dil_graph(cfg)
     path = models.write_repo(str(tmp_path), "dil", mb)
     x = models.synthetic_input((2, 4, cfg["h"], cfg["w"]), stream=f"dil{seed}")
-    ref = seg_ref.run_f64(mb, {"x": x})["y"]
+    ref = ref64.run_f64(mb, {"x": x})["y"]
     for env in (dict(), dict(IE_FORCE_ALGO="igemm", IE_FORCE_TILE=str(cfg["tile"]), IE_FORCE_SPLITK=str(cfg["splitk"])), dict(IE_FORCE_ALGO="naive")):
-        plan = _with_env(dict(IE_PRECISION=prec, **env), lambda: B.DescribeModel(path, 2)["plan"])
+        plan = plan_of(path, 2, dict(IE_PRECISION=prec, **env))
         dsteps = [s for s in plan["steps"] if s["name"].startswith("dconv") or "dconv" in s["name"]]
         assert dsteps and all(s["algo"] in ("igemm_vec", "igemm_scalar", "naive") for s in plan["steps"] if "dilations" in s)
-        y, _ = _run_engine(path, "dil", dict(IE_PRECISION=prec, **env), "x", x, "y", oshape)
-        assert seg_ref.rel_err(y, ref) < RTOL[prec], (cfg, env)
+        y, _ = run_model(path, "dil", dict(IE_PRECISION=prec, **env), {"x": x}, "y", oshape)
+        assert ref64.rel_err(y, ref) < RTOL[prec], (cfg, env)
 
 
 # ---- seeded random Resize cases ----------------------------------------------------------------------------------------------------------
 def _resize_case(seed):
     r = np.random.RandomState(seed)
     mode = ["nearest", "linear"][seed % 2]
-    coord = seg_ref.COORDS[(seed // 2) % 4]
-    nearest = seg_ref.NEAREST[(seed // 8) % 4]
+    coord = ref64.COORDS[(seed // 2) % 4]
+    nearest = ref64.NEAREST[(seed // 8) % 4]
     h, w = int(r.choice([1, 5, 7, 12])), int(r.choice([1, 6, 9, 14]))
     form = ["scales", "sizes"][(seed // 3) % 2]
     c = int(r.choice([8, 16, 21, 24]))
@@ -153,9 +123,9 @@ def test_random_resize(tmp_path, seed, prec):
     mb, oshape = _resize_graph(cfg)
     path = models.write_repo(str(tmp_path), "rz", mb)
     x = models.synthetic_input((2, 4, cfg["h"], cfg["w"]), stream=f"rz{seed}")
-    ref = seg_ref.run_f64(mb, {"x": x})["y"]
-    y, kern = _run_engine(path, "rz", dict(IE_PRECISION=prec), "x", x, "y", oshape)
-    assert seg_ref.rel_err(y, ref) < RTOL[prec], cfg
+    ref = ref64.run_f64(mb, {"x": x})["y"]
+    y, kern = run_model(path, "rz", dict(IE_PRECISION=prec), {"x": x}, "y", oshape)
+    assert ref64.rel_err(y, ref) < RTOL[prec], cfg
     assert any(q.startswith("resize_") for q in kern), kern
 
 
@@ -164,8 +134,8 @@ def test_resize_graph_output_is_written_by_the_resize(tmp_path):
     mb, oshape = _resize_graph(cfg)
     path = models.write_repo(str(tmp_path), "rzo", mb)
     x = models.synthetic_input((2, 4, 7, 7), stream="rzo")
-    y, kern = _run_engine(path, "rzo", dict(IE_PRECISION="fp16"), "x", x, "y", oshape)
-    assert seg_ref.rel_err(y, seg_ref.run_f64(mb, {"x": x})["y"]) < RTOL["fp16"]
+    y, kern = run_model(path, "rzo", dict(IE_PRECISION="fp16"), {"x": x}, "y", oshape)
+    assert ref64.rel_err(y, ref64.run_f64(mb, {"x": x})["y"]) < RTOL["fp16"]
     assert "resize_nchw_kernel<f16>" in kern and "copy_kernel" not in kern, kern
 
 
@@ -179,9 +149,9 @@ def test_network_vs_float64(tmp_path, net, prec):
     mb = NETS[net](2, width=16, image=96, resize="shape")
     path = models.write_repo(str(tmp_path), net, mb)
     x = models.synthetic_input((2, 3, 96, 96), stream=net)
-    ref = seg_ref.run_f64(mb, {"image": x})["out"]
-    y, kern = _run_engine(path, net, dict(IE_PRECISION=prec), "image", x, "out", (2, 21, 96, 96))
-    assert seg_ref.rel_err(y, ref) < RTOL[prec]
+    ref = ref64.run_f64(mb, {"image": x})["out"]
+    y, kern = run_model(path, net, dict(IE_PRECISION=prec), {"image": x}, "out", (2, 21, 96, 96))
+    assert ref64.rel_err(y, ref) < RTOL[prec]
     assert (y.argmax(1) == ref.argmax(1)).mean() > (0.999 if prec == "fp32" else 0.99)      # (fp16: near-ties among 21 classes)
     assert "copy_kernel" not in kern and sum(q.startswith("resize_") for q in kern) == (1 if net == "fcn" else 2), kern
 
@@ -192,9 +162,9 @@ def test_network_at_224(tmp_path, net):
     mb = NETS[net](1)
     path = models.write_repo(str(tmp_path), net, mb)
     x = models.synthetic_input((1, 3, 224, 224), stream=net + "224")
-    ref = seg_ref.run_f64(mb, {"image": x})["out"]
-    y, _ = _run_engine(path, net, dict(IE_PRECISION="fp32"), "image", x, "out", (1, 21, 224, 224))
-    assert seg_ref.rel_err(y, ref) < RTOL["fp32"]
+    ref = ref64.run_f64(mb, {"image": x})["out"]
+    y, _ = run_model(path, net, dict(IE_PRECISION="fp32"), {"image": x}, "out", (1, 21, 224, 224))
+    assert ref64.rel_err(y, ref) < RTOL["fp32"]
 
 
 def test_replay_and_batch_independence(tmp_path):
@@ -205,21 +175,21 @@ def test_replay_and_batch_independence(tmp_path):
     def go():
         m = B.CreateModel(path, "dlr")
         try:
-            y_host = _infer(m, "image", x, "out", (2, 21, 64, 64))
+            y_host = infer(m, {"image": x}, "out", (2, 21, 64, 64))
             din, dout = B.Prepare(m, [[2, 3, 64, 64]], 1)
             B.CopyToDevice(m, din[0], x)
             B.RunPrepared(m, 2, True)                                              # graph replay
             y = np.empty((2, 21, 64, 64), np.float32)
             B.CopyToHost(m, y, dout[0])
             np.testing.assert_array_equal(y, y_host)
-            y1 = _infer(m, "image", x[:1], "out", (1, 21, 64, 64))
-            assert seg_ref.rel_err(y_host[0], y1[0]) < RTOL["fp32"]
+            y1 = infer(m, {"image": x[:1]}, "out", (1, 21, 64, 64))
+            assert ref64.rel_err(y_host[0], y1[0]) < RTOL["fp32"]
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0"), go)
+    with_env(dict(IE_AUTOTUNE="0"), go)
 
 
 def test_fp8_load_is_refused(tmp_path):
     path = models.write_repo(str(tmp_path), "dl8", models.deeplabv3_resnet50("N", width=8, image=64, resize="scales"))
     with pytest.raises(Exception, match="dilated convolution is not supported in fp8 mode"):
-        _with_env(dict(IE_PRECISION="fp8", IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "dl8"))
+        with_env(dict(IE_PRECISION="fp8", IE_AUTOTUNE="0"), lambda: B.CreateModel(path, "dl8"))

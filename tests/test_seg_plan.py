@@ -1,7 +1,7 @@
 """CPU: dilated convolutions and Resize / Upsample through the ONNX reader and the planner (EngineDescribeModel): FCN-ResNet50 and
 DeepLabV3-ResNet50 step structures in fp32 and fp16, FLOP accounting, the Shape arithmetic of torch's interpolate exports, the refusals, and the
 plans of the graphs that loaded before, which must stay byte-identical (tests/golden/plan_sha256_parent.json).  The numpy Resize reference of
-seg_ref.py is checked against torch's F.interpolate where the two definitions coincide."""
+ref64.py is checked against torch's F.interpolate where the two definitions coincide."""
 import ctypes as C
 import hashlib
 import json
@@ -10,7 +10,8 @@ import os
 import numpy as np
 import pytest
 
-import seg_ref
+import ref64
+from engine_run import describe
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
@@ -29,11 +30,6 @@ def plan_json(path, batch):
     s = B._take_string(p)
     assert s.endswith("}")
     return s[s.index('"plan":') + len('"plan":'):-1]
-
-
-def _describe(path, batch, monkeypatch, prec):
-    monkeypatch.setenv("IE_PRECISION", prec)
-    return B.DescribeModel(path, batch)["plan"]
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +53,7 @@ def _check_common(p, mb, batch):
     assert fin["resize"] == {"mode": "linear", "coord": "pytorch_half_pixel", "nearest": "round_prefer_floor", "scales": [8, 8]}
     assert p["outputs"][0]["view"]["buf"] == fin["out"]["buf"]
     # FLOPs: 2 x the graph's conv MACs (a collapsed conv counts as its 1x1), + 6 per linear Resize output element
-    macs = seg_ref.conv_macs(mb, (batch, 3, 224, 224))
+    macs = ref64.conv_macs(mb, (batch, 3, 224, 224))
     convs = [s for s in steps if s["kind"] == "conv"]
     pool = sum(9 * s["out"]["n"] * s["out"]["c"] * s["out"]["h"] * s["out"]["w"] for s in convs if s["algo"] == "stem_pool")
     collapsed = sum(v * 8 // 9 for k, v in macs.items() if k == "aspp3")
@@ -71,7 +67,7 @@ def _check_common(p, mb, batch):
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
 def test_fcn_plan(nets, monkeypatch, prec):
     mb, path = nets["fcn"]
-    p = _describe(path, 8, monkeypatch, prec)
+    p = describe(path, 8, monkeypatch, prec)
     dil = _check_common(p, mb, 8)
     # stage 3: first block d = 1, five blocks d = 2; stage 4: first block d = 2, two blocks d = 4; all at 28x28, stride 1
     assert [s["dilations"][0] for s in dil] == [2] * 6 + [4] * 2
@@ -83,7 +79,7 @@ def test_fcn_plan(nets, monkeypatch, prec):
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
 def test_deeplabv3_plan(nets, monkeypatch, prec):
     mb, path = nets["deeplab"]
-    p = _describe(path, 8, monkeypatch, prec)
+    p = describe(path, 8, monkeypatch, prec)
     dil = _check_common(p, mb, 8)
     assert [s["dilations"][0] for s in dil] == [2] * 6 + [4] * 2 + [12, 24]
     steps = p["steps"]
@@ -239,13 +235,13 @@ def test_resize_ref_matches_torch(hw, out):
     sc = (out[0] / hw[0], out[1] / hw[1])
     # bilinear, align_corners=False == pytorch_half_pixel (and half_pixel when the output is not 1 wide)
     ref = F.interpolate(t, size=out, mode="bilinear", align_corners=False).numpy()
-    np.testing.assert_allclose(seg_ref.resize_ref(x, out, sc, "linear", "pytorch_half_pixel"), ref, rtol=1e-12, atol=1e-12)
-    np.testing.assert_allclose(seg_ref.resize_ref(x, out, sc, "linear", "half_pixel"), ref, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(ref64.resize_ref(x, out, sc, "linear", "pytorch_half_pixel"), ref, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(ref64.resize_ref(x, out, sc, "linear", "half_pixel"), ref, rtol=1e-12, atol=1e-12)
     ref = F.interpolate(t, size=out, mode="bilinear", align_corners=True).numpy()
-    np.testing.assert_allclose(seg_ref.resize_ref(x, out, sc, "linear", "align_corners"), ref, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(ref64.resize_ref(x, out, sc, "linear", "align_corners"), ref, rtol=1e-12, atol=1e-12)
     # torch's "nearest" is asymmetric + floor with scale in / out
     ref = F.interpolate(t, size=out, mode="nearest").numpy()
-    np.testing.assert_array_equal(seg_ref.resize_ref(x, out, sc, "nearest", "asymmetric", "floor"), ref)
+    np.testing.assert_array_equal(ref64.resize_ref(x, out, sc, "nearest", "asymmetric", "floor"), ref)
     # "nearest-exact" is half_pixel + round half up (ties never occur away from x.5 boundaries): round_prefer_ceil
     ref = F.interpolate(t, size=out, mode="nearest-exact").numpy()
-    np.testing.assert_array_equal(seg_ref.resize_ref(x, out, sc, "nearest", "half_pixel", "round_prefer_ceil"), ref)
+    np.testing.assert_array_equal(ref64.resize_ref(x, out, sc, "nearest", "half_pixel", "round_prefer_ceil"), ref)

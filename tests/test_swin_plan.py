@@ -13,22 +13,14 @@ import numpy as np
 import pytest
 
 import swin_graphs as G
-import swin_ref
+import ref64
+from engine_run import describe
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from oracle import onnx_oracle as O
 
 PRECS = ("fp32", "fp16")
 BATCH = 2
-
-
-def _describe(path, batch, monkeypatch, prec="fp32", **env):
-    monkeypatch.setenv("IE_PRECISION", prec)
-    for k in ("IE_FORCE_TILE", "IE_FORCE_ALGO", "IE_FORCE_SPLITK"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    return B.DescribeModel(path, batch)["plan"]
 
 
 def _same_view(a, b):
@@ -85,7 +77,7 @@ def _check_net(steps, batch, image, dims, depths, heads, window, f16):
 def test_narrow_swin_plan(tmp_path, monkeypatch, prec):
     """fails on a planner without the window matcher, which refuses the graph at its first Slice"""
     path = models.write_repo(str(tmp_path), "swin", G.narrow(BATCH))
-    p = _describe(path, BATCH, monkeypatch, prec)
+    p = describe(path, BATCH, monkeypatch, prec)
     ats = _check_net(p["steps"], BATCH, 56, (32, 64), (2, 2), (1, 2), 7, prec == "fp16")
     assert [(a["shift"], a["masked"]) for a in ats] == [([0, 0], False), ([3, 3], True), ([0, 0], False), ([0, 0], False)]
     assert p["outputs"][0]["dims"] == [BATCH, 10]
@@ -93,7 +85,7 @@ def test_narrow_swin_plan(tmp_path, monkeypatch, prec):
 
 def test_swin_t_plan(tmp_path, monkeypatch):
     path = models.write_repo(str(tmp_path), "swin_t", models.swin_t(1))
-    p = _describe(path, 1, monkeypatch)
+    p = describe(path, 1, monkeypatch)
     ats = _check_net(p["steps"], 1, 224, (96, 192, 384, 768), (2, 2, 6, 2), (3, 6, 12, 24), 7, False)
     assert len(ats) == 12 and sum(a["masked"] for a in ats) == 5 and all(a["masked"] == (a["shift"] != [0, 0]) for a in ats)
     assert [a["heads"] for a in ats] == [3, 3, 6, 6] + [12] * 6 + [24, 24] and all(a["head_dim"] == 32 and a["tile"] == 1 for a in ats)
@@ -112,7 +104,7 @@ def test_spellings_give_the_same_plan(tmp_path, monkeypatch):
     first = blob = None
     for k, kw in enumerate(variants):
         path = models.write_repo(str(tmp_path), f"v{k}", G.narrow(BATCH, **kw))
-        key = _plan_key(_describe(path, BATCH, monkeypatch)["steps"])
+        key = _plan_key(describe(path, BATCH, monkeypatch)["steps"])
         w = B.PlanWeights(path, BATCH)
         if first is None:
             first, blob = key, w
@@ -123,8 +115,8 @@ def test_spellings_give_the_same_plan(tmp_path, monkeypatch):
 
 def test_symbolic_batch(tmp_path, monkeypatch):
     """batch "N": every batch-dependent shape entry is -1; the plan is that of the constant shapes"""
-    a = _describe(models.write_repo(str(tmp_path), "sym", G.narrow("N")), 3, monkeypatch)
-    b = _describe(models.write_repo(str(tmp_path), "con", G.narrow(3)), 3, monkeypatch)
+    a = describe(models.write_repo(str(tmp_path), "sym", G.narrow("N")), 3, monkeypatch)
+    b = describe(models.write_repo(str(tmp_path), "con", G.narrow(3)), 3, monkeypatch)
     assert _plan_key(a["steps"]) == _plan_key(b["steps"])
     assert np.array_equal(B.PlanWeights(str(tmp_path / "sym" / "1"), 3), B.PlanWeights(str(tmp_path / "con" / "1"), 3))
     shapes = [v for k, v in O.load_model(G.narrow("N")).inits.items() if k.endswith(("part6", "part3", "shape5", "mask5", "mask4", "shape3", "rev6", "rev4"))]
@@ -135,7 +127,7 @@ def test_tables_are_in_the_blob(tmp_path, monkeypatch):
     """the bias and the mask are the graph's constants, repacked [.][Lp][Lp] with the query index fastest and -inf on the padded keys"""
     mb = G.narrow(BATCH)
     path = models.write_repo(str(tmp_path), "swin", mb)
-    at = [s for s in _describe(path, BATCH, monkeypatch, "fp16")["steps"] if s["kind"] == "window_attention"][1]
+    at = [s for s in describe(path, BATCH, monkeypatch, "fp16")["steps"] if s["kind"] == "window_attention"][1]
     inits = O.load_model(mb).inits
     blob = B.PlanWeights(path, BATCH)
     L, lp = 49, 64
@@ -157,7 +149,7 @@ def test_window_attention_tiles(tmp_path, monkeypatch, prec):
         path = models.write_repo(str(tmp_path), f"w{hw[0]}_{win}_{hd}", G.wattn_graph(2, hw, win, win // 2, heads, hd))
         got = {}
         for forced in (None, "0", "1", "2"):
-            steps = _describe(path, 2, monkeypatch, prec, **({} if forced is None else {"IE_FORCE_TILE": forced}))["steps"]
+            steps = describe(path, 2, monkeypatch, prec, **({} if forced is None else {"IE_FORCE_TILE": forced}))["steps"]
             assert [s["kind"] for s in steps] == ["copy", "window_attention", "copy"]          # the NCHW graph input and output; nothing for the views
             got[forced] = steps[1]["tile"]
         assert G.wattn_mfma_ok(win * win, hd, heads * hd, prec == "fp16") == ok
@@ -166,14 +158,14 @@ def test_window_attention_tiles(tmp_path, monkeypatch, prec):
 
 def test_linear_region_plan(tmp_path, monkeypatch):
     path = models.write_repo(str(tmp_path), "lin", G.wattn_graph(2, (14, 14), 7, 3, 2, 32, linear=True))
-    steps = _describe(path, 2, monkeypatch)["steps"]
+    steps = describe(path, 2, monkeypatch)["steps"]
     assert [s["kind"] for s in steps] == ["conv", "window_attention", "conv", "copy"]          # (the qkv conv reads the NCHW input itself)
 
 
 def test_patch_merge_plan(tmp_path, monkeypatch):
     for c, label in ((8, "patch_merge_kernel<f32,4>"), (5, "patch_merge_kernel<f32,1>")):
         path = models.write_repo(str(tmp_path), f"m{c}", G.merge_graph(2, c, (6, 10)))
-        steps = _describe(path, 2, monkeypatch)["steps"]
+        steps = describe(path, 2, monkeypatch)["steps"]
         assert [s["kind"] for s in steps] == ["copy", "patch_merge", "copy"]
         assert (steps[1]["out"]["c"], steps[1]["out"]["h"], steps[1]["out"]["w"]) == (4 * c, 3, 5)
 
@@ -203,7 +195,7 @@ def test_refusals(tmp_path, monkeypatch, kw, node, rule):
     shift = kw.pop("shift", 3)
     path = models.write_repo(str(tmp_path), "bad", G.wattn_graph(2, (14, 14), 7, shift, 2, 32, linear=True, **kw))
     with pytest.raises(Exception) as e:
-        _describe(path, 2, monkeypatch)
+        describe(path, 2, monkeypatch)
     msg = str(e.value)
     assert rule in msg and node in msg and "window-attention pattern" in msg, msg
 
@@ -215,7 +207,7 @@ def test_refusals_at_import(tmp_path, monkeypatch):
             ("big", G.wattn_graph(2, (14, 14), 7, 7, 2, 32), "the shift 7 x 7 is not smaller than the window 7 x 7"),
             ("merge", G.merge_graph(2, 8, (7, 10)), "patch merging of an odd map (7 x 10) is not supported")):
         with pytest.raises(Exception) as e:
-            _describe(models.write_repo(str(tmp_path), name, mb), 2, monkeypatch)
+            describe(models.write_repo(str(tmp_path), name, mb), 2, monkeypatch)
         assert rule in str(e.value), str(e.value)
 
 
@@ -237,7 +229,7 @@ def test_a_plain_attention_with_a_mask_is_still_refused_by_name(tmp_path, monkey
     gb.simple("Reshape", [y, gb.init("back", np.array([0, 64, 1, 5], np.int64))], out="y")
     path = models.write_repo(str(tmp_path), "masked", gb.finish([("x", [2, 192, 1, 5])], [("y", [2, 64, 1, 5])], opset=17))
     with pytest.raises(Exception, match="an additive mask"):
-        _describe(path, 2, monkeypatch)
+        describe(path, 2, monkeypatch)
 
 
 # ---- the float64 reference notices what a broken kernel would drop --------------------------------------------------------------------------
@@ -248,14 +240,14 @@ def test_reference_sensitivity():
     # the roll act on (on smooth images every token of a window carries nearly the same v, and the global pool averages the rest away)
     st = np.random.RandomState(1)
     x = (st.randn(BATCH, 3, 56, 56) + 2.0 * np.repeat(np.repeat(st.randn(BATCH, 3, 7, 7), 8, 2), 8, 3)).astype(np.float32)
-    ref = swin_ref.run_f64(mb, {"input": x})["logits"]
+    ref = ref64.run_f64(mb, {"input": x})["logits"]
     inits = O.load_model(mb).inits
     zero = lambda suffix: {k: np.zeros_like(v) for k, v in inits.items() if k.endswith(suffix)}  # noqa: E731
     assert len(zero("_rpb")) == 4 and len(zero("_mask")) == 1
     moved = {
-        "bias": swin_ref.rel_err(swin_ref.run_f64(mb, {"input": x}, zero("_rpb"))["logits"], ref),
-        "mask": swin_ref.rel_err(swin_ref.run_f64(mb, {"input": x}, zero("_mask"))["logits"], ref),
-        "roll": swin_ref.rel_err(swin_ref.run_f64(G.narrow(BATCH, tweak=dict(reverse_roll=True)), {"input": x})["logits"], ref),
+        "bias": ref64.rel_err(ref64.run_f64(mb, {"input": x}, overrides=zero("_rpb"))["logits"], ref),
+        "mask": ref64.rel_err(ref64.run_f64(mb, {"input": x}, overrides=zero("_mask"))["logits"], ref),
+        "roll": ref64.rel_err(ref64.run_f64(G.narrow(BATCH, tweak=dict(reverse_roll=True)), {"input": x})["logits"], ref),
     }
     print(moved)
     assert all(v > 0.05 for v in moved.values()), moved

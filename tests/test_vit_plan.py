@@ -20,8 +20,9 @@ if __name__ == "__main__":
     load_package()
 
 import vit_graphs as G  # noqa: E402
-import vit_ref  # noqa: E402
+import ref64  # noqa: E402
 import test_plan_digests as D  # noqa: E402
+from engine_run import describe  # noqa: E402
 from gpu_ai_inference_server_amd import binding as B  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import models  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb  # noqa: E402
@@ -29,15 +30,6 @@ from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb  # noqa: E402
 GOLDEN = os.path.join(HERE, "golden", "plan_digests_vit.json")
 PRECS = ("fp32", "fp16")
 BATCH, DIM, HEADS, MLP, DEPTH, L = 2, 64, 2, 128, 2, 17
-
-
-def _describe(path, batch, monkeypatch, prec, **env):
-    monkeypatch.setenv("IE_PRECISION", prec)
-    for k in ("IE_FORCE_TILE", "IE_FORCE_ALGO", "IE_FORCE_SPLITK"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    return B.DescribeModel(path, batch)["plan"]
 
 
 def _same_view(a, b):
@@ -50,7 +42,7 @@ def _same_view(a, b):
 @pytest.mark.parametrize("unbind", G.UNBINDS)
 def test_narrow_vit_plan(tmp_path, monkeypatch, unbind, scale, prec):
     path = models.write_repo(str(tmp_path), "vit", G.narrow(BATCH, unbind=unbind, scale=scale))
-    p = _describe(path, BATCH, monkeypatch, prec)
+    p = describe(path, BATCH, monkeypatch, prec)
     steps = p["steps"]
     f16 = prec == "fp16"
     layer = ["layer_norm", "conv", "attention", "conv", "layer_norm", "conv", "eltwise", "conv"]
@@ -89,7 +81,7 @@ def test_spellings_give_the_same_plan(tmp_path, monkeypatch):
     for unbind in G.UNBINDS:
         for scale in G.SCALES:
             path = models.write_repo(str(tmp_path), f"v_{unbind}_{scale}", G.narrow(BATCH, unbind=unbind, scale=scale))
-            steps = _describe(path, BATCH, monkeypatch, "fp32")["steps"]
+            steps = describe(path, BATCH, monkeypatch, "fp32")["steps"]
             plans[unbind, scale] = [(s["kind"], s.get("algo"), s.get("tile"), s["in"], s["out"], s.get("residual"), s.get("heads"), s["w_off"]) for s in steps]
     first = plans["gather", "q"]
     assert all(v == first for v in plans.values())
@@ -97,8 +89,8 @@ def test_spellings_give_the_same_plan(tmp_path, monkeypatch):
 
 def test_symbolic_batch_folds_the_expand_shape(tmp_path, monkeypatch):
     """batch "N": the Expand's shape is Shape(input) -> Gather 0 -> Unsqueeze -> Concat; the plan is that of the constant shape"""
-    a = _describe(models.write_repo(str(tmp_path), "sym", G.narrow("N")), 3, monkeypatch, "fp32")
-    b = _describe(models.write_repo(str(tmp_path), "con", G.narrow(3)), 3, monkeypatch, "fp32")
+    a = describe(models.write_repo(str(tmp_path), "sym", G.narrow("N")), 3, monkeypatch, "fp32")
+    b = describe(models.write_repo(str(tmp_path), "con", G.narrow(3)), 3, monkeypatch, "fp32")
     assert [(s["kind"], s["in"], s["out"]) for s in a["steps"]] == [(s["kind"], s["in"], s["out"]) for s in b["steps"]]
     assert np.array_equal(B.PlanWeights(os.path.join(str(tmp_path), "sym", "1"), 3), B.PlanWeights(os.path.join(str(tmp_path), "con", "1"), 3))
 
@@ -107,7 +99,7 @@ def test_assemble_constants_are_in_the_blob(tmp_path, monkeypatch):
     from oracle import onnx_oracle as O
     mb = G.narrow(BATCH)
     path = models.write_repo(str(tmp_path), "vit", mb)
-    asm = _describe(path, BATCH, monkeypatch, "fp16")["steps"][1]
+    asm = describe(path, BATCH, monkeypatch, "fp16")["steps"][1]
     blob = B.PlanWeights(path, BATCH)
     inits = O.load_model(mb).inits
     np.testing.assert_array_equal(blob[asm["w_off"]:asm["w_off"] + DIM], inits["class_token"].reshape(DIM))
@@ -126,7 +118,7 @@ def test_attention_tiles(tmp_path, monkeypatch, prec):
         path = models.write_repo(str(tmp_path), f"a{l}_{hd}", G.attn_graph(2, l, heads, hd))
         got = {}
         for forced in (None, "0", "1", "2"):
-            steps = _describe(path, 2, monkeypatch, prec, **({} if forced is None else {"IE_FORCE_TILE": forced}))["steps"]
+            steps = describe(path, 2, monkeypatch, prec, **({} if forced is None else {"IE_FORCE_TILE": forced}))["steps"]
             assert [s["kind"] for s in steps] == ["copy", "attention", "copy"]             # the NCHW graph input and output; nothing for the views
             got[forced] = steps[1]["tile"]
         ok = G.attn_mfma_ok(l, hd, heads * hd, f16)
@@ -138,7 +130,7 @@ def test_attention_tiles(tmp_path, monkeypatch, prec):
 @pytest.mark.parametrize("prec", PRECS)
 def test_tokens_back_to_a_feature_map(tmp_path, monkeypatch, prec):
     path = models.write_repo(str(tmp_path), "back", G.way_back_graph(2))
-    steps = _describe(path, 2, monkeypatch, prec)["steps"]
+    steps = describe(path, 2, monkeypatch, prec)["steps"]
     assert [s["kind"] for s in steps] == ["conv", "layer_norm", "conv", "copy"] and steps[3]["name"] == "to_output(y)"       # (the NCHW graph output)
     ln, c3 = steps[1], steps[2]
     assert (ln["in"]["h"], ln["in"]["w"], ln["in"]["c"]) == (1, 16, 8) and ln["in"]["buf"] == steps[0]["out"]["buf"]
@@ -153,7 +145,7 @@ def _refused(tmp_path, monkeypatch, name, build, ishape, match, prec="fp32"):
         gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     path = models.write_repo(str(tmp_path), name, gb.finish([("x", ishape)], [("y", [1])], opset=17))
     with pytest.raises(RuntimeError, match=match):
-        _describe(path, ishape[0], monkeypatch, prec)
+        describe(path, ishape[0], monkeypatch, prec)
 
 
 def _tok(gb, c=8):
@@ -244,7 +236,7 @@ def test_token_graph_output_is_refused(tmp_path, monkeypatch):
     y = gb.layernorm(_tok(gb), 8, name="ln")
     path = models.write_repo(str(tmp_path), "tokout", gb.finish([("x", [2, 8, 2, 3])], [(y, [2, 6, 8])], opset=17))
     with pytest.raises(RuntimeError, match=r"graph output ln_out is a token view"):
-        _describe(path, 2, monkeypatch, "fp32")
+        describe(path, 2, monkeypatch, "fp32")
 
 
 def _attn_variant(tmp_path, monkeypatch, name, mutate, match, heads=2, hd=4, l=6):
@@ -255,7 +247,7 @@ def _attn_variant(tmp_path, monkeypatch, name, mutate, match, heads=2, hd=4, l=6
     mutate(gb, t, d, heads)
     path = models.write_repo(str(tmp_path), name, gb.finish([("x", [2, 3 * d, 1, l])], [("y", [2, d, 1, l])], opset=17))
     with pytest.raises(RuntimeError, match=match):
-        _describe(path, 2, monkeypatch, "fp32")
+        describe(path, 2, monkeypatch, "fp32")
 
 
 def _attention_by_hand(gb, t, d, heads, *, softmax_axis=-1, scale_shape=(), mask=False, second_reader=False, k_index=1, perm5=(2, 0, 3, 1, 4), out_perm=(0, 2, 1, 3)):
@@ -306,28 +298,28 @@ def test_left_over_pieces_are_unsupported_operators(tmp_path, monkeypatch):
 def test_fp8_is_refused(tmp_path, monkeypatch):
     path = models.write_repo(str(tmp_path), "vit", G.narrow(BATCH))
     with pytest.raises(RuntimeError, match=r"^LayerNormalization is not supported in fp8 mode \(node l0_ln1\)$"):
-        _describe(path, BATCH, monkeypatch, "fp8")
+        describe(path, BATCH, monkeypatch, "fp8")
     # without a LayerNormalization, the attention itself is refused
     p8 = models.write_repo(str(tmp_path), "a8", G.attn_graph(2, 6, 2, 16))
     with pytest.raises(RuntimeError, match=r"^attention and token views are not supported in fp8 mode \(node "):
-        _describe(p8, 2, monkeypatch, "fp8")
+        describe(p8, 2, monkeypatch, "fp8")
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------------
 def test_reference_walk_is_the_attention_definition():
     """the float64 walk of the unfused graph equals the closed form, in every spelling (the constants are float32: 1e-7)"""
     x = np.random.RandomState(0).randn(2, 3 * 24, 1, 7)
-    want = vit_ref.attention(x[:, :, 0, :].transpose(0, 2, 1), 3, 8 ** -0.5).transpose(0, 2, 1)[:, :, None, :]
+    want = ref64.attention(x[:, :, 0, :].transpose(0, 2, 1), 3, 8 ** -0.5).transpose(0, 2, 1)[:, :, None, :]
     for unbind in G.UNBINDS:
         for scale in G.SCALES:
             for swap in (False, True):
-                y = vit_ref.run_f64(G.attn_graph(2, 7, 3, 8, unbind=unbind, scale=scale, swap=swap), {"x": x})["y"]
-                assert y.shape == want.shape and vit_ref.rel_err(y, want) < 1e-6, (unbind, scale, swap)
+                y = ref64.run_f64(G.attn_graph(2, 7, 3, 8, unbind=unbind, scale=scale, swap=swap), {"x": x})["y"]
+                assert y.shape == want.shape and ref64.rel_err(y, want) < 1e-6, (unbind, scale, swap)
     import torch
     import torch.nn.functional as F
     t = torch.from_numpy(x[:, :, 0, :].transpose(0, 2, 1).reshape(2, 7, 3, 3, 8)).permute(2, 0, 3, 1, 4)
     sd = F.scaled_dot_product_attention(t[0], t[1], t[2]).permute(0, 2, 1, 3).reshape(2, 7, 24).numpy()
-    assert vit_ref.rel_err(sd.transpose(0, 2, 1)[:, :, None, :], want) < 1e-12
+    assert ref64.rel_err(sd.transpose(0, 2, 1)[:, :, None, :], want) < 1e-12
 
 
 def test_dropped_class_token_or_position_embedding_would_be_seen():
@@ -335,11 +327,11 @@ def test_dropped_class_token_or_position_embedding_would_be_seen():
     from oracle import onnx_oracle as O
     mb = G.narrow(2)
     x = models.synthetic_input((2, 3, 32, 32), stream="vit")
-    ref = vit_ref.run_f64(mb, {"input": x})["logits"]
+    ref = ref64.run_f64(mb, {"input": x})["logits"]
     inits = O.load_model(mb).inits
     for name in ("pos_embedding", "class_token"):
-        y = vit_ref.run_f64(mb, {"input": x, name: np.zeros_like(inits[name])})["logits"]           # (a feed overrides the initializer)
-        assert vit_ref.rel_err(y, ref) > 0.05, name
+        y = ref64.run_f64(mb, {"input": x, name: np.zeros_like(inits[name])})["logits"]           # (a feed overrides the initializer)
+        assert ref64.rel_err(y, ref) > 0.05, name
 
 
 # ---- digests ------------------------------------------------------------------------------------------------------------------------------

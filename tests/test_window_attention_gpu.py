@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the window-attention kernels on the MI355X against the float64 walk of the literal ONNX nodes (tests/swin_ref.py), with the
+"""GPU (-m gpu): the window-attention kernels on the MI355X against the float64 walk of the literal ONNX nodes (tests/ref64.py), with the
 project's bounds (tests/test_gpu_parity.py): fp32 within 2e-4 of max|ref|, fp16 within 3e-3.
 
 Graph: x [N, 3 D, H, W] -> Transpose [0,2,3,1] -> the window region without Linears (roll, partition, attention + bias [+ mask], reverse, roll back)
@@ -8,26 +8,24 @@ plan accepts (IE_FORCE_TILE 0 / 1), and the Profile label must be the kernel the
 Shapes (N, H x W, window, shift, heads, hd): L = 16, below one 32-key tile; a rectangular window on a rectangular map with L = 32, exactly one tile;
 L = 49 unshifted and shifted (17 real keys in the second tile, all nine mask regions); H != W with three heads (swapped index arithmetic); L = 64,
 exactly two tiles; one window per image; hd = 20 (generic kernel only).
-Data (tests/test_attention_gpu.py's generators, the L = H W tokens laid out row by row): randn; peaked (integer k in [-2, 2], q = 16 k: scores of
+Data (tests/vit_graphs.py's generators, the L = H W tokens laid out row by row): randn; peaked (integer k in [-2, 2], q = 16 k: scores of
 several hundred, exp overflows without the max subtraction; exact in fp16)."""
 import functools
-import os
 
 import numpy as np
 import pytest
 
+import ref64
 import swin_graphs as G
-import swin_ref
-import test_attention_gpu as A
+import vit_graphs
+from engine_run import plan_of, RTOL, run_model, with_env
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 
 pytestmark = pytest.mark.gpu
-RTOL = {"fp32": 2e-4, "fp16": 3e-3}
 KINDS = ("randn", "peaked")
 SHAPES = [(2, (8, 8), (4, 4), (2, 2), 2, 32), (2, (8, 16), (4, 8), (2, 4), 2, 32), (2, (14, 14), (7, 7), (0, 0), 2, 32), (2, (14, 14), (7, 7), (3, 3), 2, 32),
           (1, (14, 21), (7, 7), (3, 3), 3, 32), (2, (16, 16), (8, 8), (4, 4), 1, 32), (2, (7, 7), (7, 7), (0, 0), 2, 32), (1, (8, 8), (4, 4), (2, 2), 2, 20)]
-_with_env = A._with_env
 
 
 def _id(s):
@@ -38,7 +36,7 @@ def _id(s):
 @functools.lru_cache(maxsize=None)
 def make_input(n, hw, heads, hd, kind):
     """[N, 3 D, H, W]: token y W + x of the attention generators is the map's pixel (y, x)"""
-    x = np.array(A.make_input(n, hw[0] * hw[1], heads, hd, kind)).reshape(n, 3 * heads * hd, hw[0], hw[1])
+    x = np.array(vit_graphs.make_input(n, hw[0] * hw[1], heads, hd, kind)).reshape(n, 3 * heads * hd, hw[0], hw[1])
     x.setflags(write=False)
     return x
 
@@ -46,21 +44,9 @@ def make_input(n, hw, heads, hd, kind):
 @functools.lru_cache(maxsize=None)
 def reference(n, hw, win, sh, heads, hd, kind):
     """the float64 walk of the graph, computed once per input"""
-    ref = swin_ref.run_f64(G.wattn_graph(n, hw, win, sh, heads, hd), {"x": make_input(n, hw, heads, hd, kind)})["y"]
+    ref = ref64.run_f64(G.wattn_graph(n, hw, win, sh, heads, hd), {"x": make_input(n, hw, heads, hd, kind)})["y"]
     ref.setflags(write=False)
     return ref
-
-
-def _run(path, name, env, x, oshape):
-    """-> (output, [launched kernel per step])"""
-    def go():
-        m = B.CreateModel(path, name)
-        try:
-            r = m.Infer([B.TensorData("x", B.DataTypeFloat32, B.Shape(list(x.shape)), x)], [B.OutputConfig("y", Shape=list(oshape), DataType="FLOAT32")])
-            return r[0].Data.reshape(oshape), [p["kernel"] for p in B.Profile(m, 1)]
-        finally:
-            m.Destroy()
-    return _with_env(dict(IE_AUTOTUNE="0", **env), go)
 
 
 def _every_tile(path, name, prec, x, oshape, hd, check, expect_mfma):
@@ -68,12 +54,12 @@ def _every_tile(path, name, prec, x, oshape, hd, check, expect_mfma):
     ran = []
     for forced in (None, 0, 1):
         env = dict(IE_PRECISION=prec, **({} if forced is None else {"IE_FORCE_TILE": str(forced)}))
-        steps = _with_env(env, lambda: B.DescribeModel(path, x.shape[0])["plan"])["steps"]
+        steps = plan_of(path, x.shape[0], env)["steps"]
         (at,) = [s for s in steps if s["kind"] == "window_attention"]
         if forced is not None and at["tile"] != forced:
             assert at["tile"] == 0                      # not eligible: the generic kernel, which forced tile 0 runs
             continue
-        y, kern = _run(path, name, env, x, oshape)
+        y, kern = run_model(path, name, env, {"x": x}, "y", oshape)
         (label,) = [k for k in kern if k.startswith("window_attention_")]
         assert label == G.wattn_label(at["tile"], at["out"]["f16"], hd), (forced, at["tile"], label)
         assert kern.count("copy_kernel") == 2 and len(kern) == len(steps) == 3, kern          # the NCHW graph input and output only
@@ -93,7 +79,7 @@ def test_window_attention(tmp_path, shape, kind, prec):
 
     def check(y, tile, forced):
         assert np.isfinite(y).all(), (kind, tile)
-        err = swin_ref.rel_err(y, ref)
+        err = ref64.rel_err(y, ref)
         print(f"{_id(shape)} {kind} {prec} forced {forced} tile {tile}: max err / max|ref| {err:.3e}")
         assert err < RTOL[prec], (shape, kind, prec, tile, err)
 
@@ -113,10 +99,10 @@ def test_batch_independence(tmp_path, tile, prec):
     hw, win, sh, heads, hd = (14, 14), (7, 7), (3, 3), 2, 32
     x = np.array(make_input(2, hw, heads, hd, "randn"))
     env = dict(IE_PRECISION=prec, IE_FORCE_TILE=str(tile))
-    y2, _ = _run(models.write_repo(str(tmp_path), "a2", G.wattn_graph(2, hw, win, sh, heads, hd)), "a2", env, x, (2, heads * hd, 14, 14))
-    y1, _ = _run(models.write_repo(str(tmp_path), "a1", G.wattn_graph(1, hw, win, sh, heads, hd)), "a1", env, x[1:], (1, heads * hd, 14, 14))
+    y2, _ = run_model(models.write_repo(str(tmp_path), "a2", G.wattn_graph(2, hw, win, sh, heads, hd)), "a2", env, {"x": x}, "y", (2, heads * hd, 14, 14))
+    y1, _ = run_model(models.write_repo(str(tmp_path), "a1", G.wattn_graph(1, hw, win, sh, heads, hd)), "a1", env, {"x": x[1:]}, "y", (1, heads * hd, 14, 14))
     np.testing.assert_array_equal(y2[1], y1[0])
-    assert swin_ref.rel_err(y2, reference(2, hw, win, sh, heads, hd, "randn")) < RTOL[prec]
+    assert ref64.rel_err(y2, reference(2, hw, win, sh, heads, hd, "randn")) < RTOL[prec]
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
@@ -140,7 +126,7 @@ def test_graph_replay_is_bit_identical(tmp_path, tile, prec):
             np.testing.assert_array_equal(y, y_host)
         finally:
             m.Destroy()
-    _with_env(dict(IE_AUTOTUNE="0", IE_PRECISION=prec, IE_FORCE_TILE=str(tile)), go)
+    with_env(dict(IE_AUTOTUNE="0", IE_PRECISION=prec, IE_FORCE_TILE=str(tile)), go)
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
@@ -150,14 +136,14 @@ def test_qkv_from_a_linear(tmp_path, prec):
     mb = G.wattn_graph(n, hw, win, sh, heads, hd, linear=True)
     path = models.write_repo(str(tmp_path), "lin", mb)
     x = np.random.RandomState(4).randn(n, heads * hd, 14, 14).astype(np.float32)
-    ref = swin_ref.run_f64(mb, {"x": x})["y"]
+    ref = ref64.run_f64(mb, {"x": x})["y"]
     for tile in (0, 1):
         env = dict(IE_PRECISION=prec, IE_FORCE_TILE=str(tile))
-        steps = _with_env(env, lambda: B.DescribeModel(path, n)["plan"])["steps"]
+        steps = plan_of(path, n, env)["steps"]
         assert [s["kind"] for s in steps] == ["conv", "window_attention", "conv", "copy"]
         at = steps[1]
         assert at["tile"] == tile and (at["in"]["buf"], at["in"]["pitch"], at["in"]["c"]) == (steps[0]["out"]["buf"], 3 * heads * hd, 3 * heads * hd)
-        y, kern = _run(path, "lin", env, x, (n, heads * hd, 14, 14))
-        err = swin_ref.rel_err(y, ref)
+        y, kern = run_model(path, "lin", env, {"x": x}, "y", (n, heads * hd, 14, 14))
+        err = ref64.rel_err(y, ref)
         print(f"qkv from a Linear {prec} tile {tile}: max err / max|ref| {err:.3e}; {kern}")
         assert err < RTOL[prec] and G.wattn_label(tile, prec == "fp16", hd) in kern

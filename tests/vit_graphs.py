@@ -1,6 +1,8 @@
 """Test graphs shared by the ViT plan and GPU tests, and what the tests know about the attention kernel's tiles."""
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from gpu_ai_inference_server_amd.modelgen import models
@@ -59,3 +61,30 @@ def way_back_graph(n: int = 2) -> bytes:
     y = gb.simple("Reshape", [gb.transpose(t, (0, 2, 1)), gb.init("map_shape", np.array([0, 8, 4, 4], np.int64))])
     gb.conv(y, 8, 8, 3, pad=1, bias=True, name="c3", out="y")
     return gb.finish([("x", [n, 3, 16, 16])], [("y", [n, 8, 4, 4])], opset=17)
+
+
+def pack(q, k, v):
+    """q, k, v [N, H, L, hd] -> x [N, 3 D, 1, L]: channel s * D + h * hd + e of token j is element e of head h of q / k / v"""
+    n, h, l, hd = q.shape
+    x = np.stack([q, k, v], 0).transpose(1, 0, 2, 4, 3).reshape(n, 3 * h * hd, 1, l)
+    return np.ascontiguousarray(x, np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def make_input(n, l, h, hd, kind):
+    st = np.random.RandomState(1000 * l + 10 * hd + h + len(kind))
+    half = lambda a: a.astype(np.float16).astype(np.float32)  # noqa: E731
+    v = half(st.randn(n, h, l, hd))
+    if kind == "randn":
+        q, k = st.randn(n, h, l, hd), st.randn(n, h, l, hd)
+    elif kind == "peaked":
+        k = st.randint(-2, 3, size=(n, h, l, hd)).astype(np.float64)
+        q = 16.0 * k
+    else:
+        u = np.where(st.rand(n, h, 1, hd) < 0.5, -1.0, 1.0)
+        step = 1.0 / 8.0 if kind == "ramp" else 1.0 / 128.0
+        q = np.broadcast_to(u, (n, h, l, hd))
+        k = u * (np.arange(l, dtype=np.float64) * step).reshape(1, 1, l, 1)
+    x = pack(np.asarray(q, np.float32), np.asarray(k, np.float32), v)
+    x.setflags(write=False)
+    return x
