@@ -340,8 +340,12 @@ struct AttnArgs {
 };
 // tile 0: attention_generic_kernel (one wave per query row; any L, head_dim, pitch, offset; float or half).  tile 1: attention_mfma_kernel<T, HD>
 // (a workgroup = one image, one head, 128 queries; the head's K and V rows in LDS): head_dim 32 or 64, the channel counts, pitches and offsets
-// multiples of the 16-byte vector, and both of the head's padded K and V images inside the LDS budget
-constexpr int kNumAttnTiles = 2;
+// multiples of the 16-byte vector, and both of the head's padded K and V images inside the LDS budget.  tile 2: attention_stream_kernel<T, HD>
+// (a workgroup = one image, one head, 32 queries; its four waves split the head dim; K and V streamed in tiles of 32 keys, LDS independent of L):
+// head_dim 128, 256 or 512, no key mask, the same vector conditions
+constexpr int kNumAttnTiles = 3;
+// IE_FORCE_TILE reaches tiles 0 and 1 of an attention step only (2 keeps meaning "not forced"); tile 2 is pinned with IE_ATTN_TILE
+constexpr int kNumAttnForcedTiles = 2;
 constexpr int64_t kAttnLdsBudget = 160 * 1024;
 // bytes of LDS the MFMA kernel needs: K and V rows, L padded to whole 32-key tiles, every row padded by one 16-byte vector; masked: one fp32 bias
 // per padded key behind them
@@ -353,6 +357,22 @@ constexpr bool AttnMfmaFits(int64_t L, int hd, bool f16, int64_t c_in, int64_t p
     const int64_t V = f16 ? 8 : 4;
     return (hd == 32 || hd == 64) && L >= 1 && c_in % V == 0 && pitch_in % V == 0 && off_in % V == 0 && c_out % V == 0 && pitch_out % V == 0 && off_out % V == 0 &&
            AttnLdsBytes(L, hd, f16, masked) <= kAttnLdsBudget;
+}
+// bytes of LDS the streaming kernel needs: two V tiles of 32 keys and two sets of the four waves' partial 32 x 32 fp32 score tiles
+constexpr int64_t AttnStreamLdsBytes(int hd, bool f16) { return 2 * (32 * int64_t(hd) * (f16 ? 2 : 4) + 4 * 32 * 32 * 4); }
+constexpr bool AttnStreamFits(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out,
+                              bool masked = false) {
+    const int64_t V = f16 ? 8 : 4;
+    return (hd == 128 || hd == 256 || hd == 512) && L >= 1 && !masked && c_in % V == 0 && pitch_in % V == 0 && off_in % V == 0 && c_out % V == 0 &&
+           pitch_out % V == 0 && off_out % V == 0 && AttnStreamLdsBytes(hd, f16) <= kAttnLdsBudget;
+}
+// the planner's default: tile 1 where it fits; else tile 2 where it fits and the sequence is long enough for 32-query workgroups to beat the
+// generic kernel's one wave per query row (measured: DESIGN 3.28); else the generic kernel
+constexpr int64_t kAttnStreamMinTokens = 128;
+constexpr int AttnDefaultTile(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out,
+                              bool masked = false) {
+    if (AttnMfmaFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, masked)) return 1;
+    return AttnStreamFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, masked) && L >= kAttnStreamMinTokens ? 2 : 0;
 }
 bool AttentionEligible(const AttnArgs& a, int tile);
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);

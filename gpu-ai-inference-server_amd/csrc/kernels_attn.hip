@@ -15,6 +15,8 @@
 //                                   vector (the row stride is then 4 banks mod 64 in fp32 and 36 in fp16: the 16 lanes of a ds_read_b128 group hit
 //                                   16 different bank quads).  Each wave keeps its 32 Q rows in registers and walks the keys in tiles of 32 with
 //                                   an online softmax (running maximum m and sum l per query; O rescaled by exp(m - m') whenever m grows).
+//   attention_stream_kernel<T, HD>  tile 2: one wide head (HD 128 / 256 / 512, no mask).  A workgroup = (image, head, 32 queries); its 4 waves split the
+//                                   head dim; K and V are streamed in tiles of 32 keys, LDS does not depend on L (described at the kernel).
 //
 // Operand orientation of tile 1.  The scores are computed swapped, S^T = K . Q^T: the MFMA's A operand is the K tile (row = key), its B operand
 // Q^T (column = query), so in the 32x32 result (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) a lane owns ONE query column and
@@ -271,6 +273,200 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
     }
 }
 
+// Tile 2: one wide head.  grid = N * heads * qblocks workgroups (qblocks = ceil(L / 32)); dynamic LDS = AttnStreamLdsBytes(HD, half).
+// A workgroup is (image, head, 32 queries); wave w owns the head-dim slice [w SL, (w + 1) SL), SL = HD / 4, of Q, K, V and O.  Per tile of 32 keys:
+//   1. the wave's PARTIAL S^T = K_slice . Q_slice^T (tile 1's orientation) from its Q registers and K fragments read straight from global memory
+//   2. the four partial tiles meet in LDS and every wave adds them in the same order ((p0 + p1) + p2) + p3: all four hold bit-identical scores,
+//      hence bit-identical m, l, alpha and P (a wave that summed in another order would rescale its O slice by another factor than its neighbours)
+//   3. tile 1's online softmax on the summed tile, in every wave
+//   4. O_slice^T += V_slice^T . P^T with SL / 32 accumulator blocks, P from the registers it is in, V through LDS (the A operand reads V by column)
+// The K fragments and the V vectors of tile t + 1 are loaded into registers before tile t's softmax and second product (one wave per SIMD at hd 512
+// fp32: nobody else hides the loads).  V tiles and partial tiles are double-buffered by tile parity, so one barrier per tile is enough: what tile t + 1
+// overwrites was last read in tile t - 1, and every wave has passed tile t's barrier behind those reads.
+// QK^T reduction order: lane half hf supplies the 16-byte vectors 2 k + hf (k = 0 ...) of the slice of its Q row and of its K row, not one contiguous
+// half as in tile 1: the two halves of a K row's 32 bytes then come from one cache line, and a fragment load touches 32 lines instead of 64.
+template <typename T, int HD>
+__global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const AttnArgs a, const int qblocks) {
+    constexpr bool F16 = sizeof(T) == 2;
+    constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
+    constexpr int SL = HD / 4;                     // head-dim slice of one wave
+    constexpr int NQ = SL / (2 * V);               // 16-byte vectors of its Q row (and of one K row) a lane holds
+    constexpr int NB = SL / 32;                    // accumulator blocks of 32 output columns per wave
+    constexpr int VPR = HD / V;                    // vectors per V row
+    constexpr int NV = 32 * VPR / kAttnBlock;      // vectors of a V tile one thread stages
+    constexpr int VT = 32 * HD;                    // elements of a V tile
+    static_assert(NQ >= 1 && NB >= 1 && NV >= 1 && 32 * VPR % kAttnBlock == 0, "head dim");
+    extern __shared__ __attribute__((aligned(16))) unsigned char attn_smem[];
+    T* Vs = reinterpret_cast<T*>(attn_smem);                                               // [2][32 keys][HD]
+    float4* Ps = reinterpret_cast<float4*>(attn_smem + 2 * VT * sizeof(T));                // [2][4 waves][4 register groups][64 lanes]
+    const int L = a.in.w, D = a.heads * HD, ntiles = (L + 31) / 32;
+    // Workgroups are handed to the 8 XCDs in turn (blockIdx % 8 labels the ones that share an L2).  Every workgroup of an (image, head) streams the
+    // same K and V, so the ids are dealt out anew: the workgroups of one L2 get one run of consecutive (image, head, query block)s
+    const int xg = int(blockIdx.x) % 8, xq = int(gridDim.x) / 8, xr = int(gridDim.x) % 8;
+    const int bid = (xg < xr ? xg * (xq + 1) : xr * (xq + 1) + (xg - xr) * xq) + int(blockIdx.x) / 8;
+    const int qb = bid % qblocks;
+    const int hn = bid / qblocks;
+    const int h = hn % a.heads, n = hn / a.heads;
+    const int tid = int(threadIdx.x), wave = tid / 64, lane = tid % 64, col = lane & 31, hf = lane >> 5;
+    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // token row j: + j * sw; q at + 0, k at + D, v at + 2 D
+    const int q0 = qb * 32;                        // < L: qblocks = ceil(L / 32)
+    const int qi = q0 + col < L ? q0 + col : L - 1;
+
+    uint4 qv[NQ], kv[NQ], vv[NV];                  // Q for the whole kernel; K fragments and V vectors of the tile to come
+    {
+        const T* qrow = base + int64_t(qi) * a.in.sw + wave * SL + hf * V;
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) qv[k] = *reinterpret_cast<const uint4*>(qrow + 2 * k * V);
+    }
+    // Every load is unconditional, its row clamped to the last one: a load under a lane condition becomes a branch of its own, and the copies behind
+    // it made the compiler wait for all loads in flight right behind the barrier.  A K row past L gives scores that are replaced by -inf below; a V
+    // row past L is zeroed where it is written to LDS; the loads behind the last tile read the last row again and are never used.
+    auto load_k = [&](int key0) {
+        const int row = key0 + col < L ? key0 + col : L - 1;
+        const T* krow = base + int64_t(row) * a.in.sw + D + wave * SL + hf * V;
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) kv[k] = *reinterpret_cast<const uint4*>(krow + 2 * k * V);
+    };
+    auto load_v = [&](int key0) {
+#pragma unroll
+        for (int it = 0; it < NV; ++it) {
+            const int id = it * kAttnBlock + tid, cv = id % VPR, row = key0 + id / VPR < L ? key0 + id / VPR : L - 1;
+            vv[it] = *reinterpret_cast<const uint4*>(base + int64_t(row) * a.in.sw + 2 * D + cv * V);
+        }
+    };
+    load_k(0);
+    load_v(0);
+
+    f32x16 o[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[b][r] = 0.f;
+    float m = -__builtin_huge_valf(), lsum = 0.f;
+    const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
+
+    for (int t = 0; t < ntiles; ++t) {
+        const int key0 = 32 * t, buf = t & 1;
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) {
+            if constexpr (F16) {
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8v, kv[k]), __builtin_bit_cast(h8v, qv[k]), s, 0, 0, 0);
+            } else {
+                const float4 kf = __builtin_bit_cast(float4, kv[k]), qf = __builtin_bit_cast(float4, qv[k]);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf.x, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf.y, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf.z, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf.w, s, 0, 0, 0);
+            }
+        }
+        load_k(key0 + 32);
+        float4* pw = Ps + ((buf * 4 + wave) * 4) * 64 + lane;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) pw[g * 64] = make_float4(s[4 * g], s[4 * g + 1], s[4 * g + 2], s[4 * g + 3]);
+        T* vs = Vs + buf * VT;
+#pragma unroll
+        for (int it = 0; it < NV; ++it) {          // rows past L: zeros (a zero probability times them stays zero); row * HD + cv * V = id * V
+            const int id = it * kAttnBlock + tid;
+            *reinterpret_cast<uint4*>(vs + id * V) = key0 + id / VPR < L ? vv[it] : make_uint4(0u, 0u, 0u, 0u);
+        }
+        __syncthreads();
+        load_v(key0 + 32);
+        const float4* pr = Ps + (buf * 16) * 64 + lane;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 p0 = pr[g * 64], p1 = pr[(4 + g) * 64], p2 = pr[(8 + g) * 64], p3 = pr[(12 + g) * 64];
+            s[4 * g] = ((p0.x + p1.x) + p2.x) + p3.x;
+            s[4 * g + 1] = ((p0.y + p1.y) + p2.y) + p3.y;
+            s[4 * g + 2] = ((p0.z + p1.z) + p2.z) + p3.z;
+            s[4 * g + 3] = ((p0.w + p1.w) + p2.w) + p3.w;
+        }
+        const bool tail = key0 + 32 > L;           // the last tile holds padded keys
+        float mx = -__builtin_huge_valf();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+            s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
+            mx = fmaxf(mx, s[r]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mn = fmaxf(m, mx);             // finite: every tile has at least one real key
+        const float alpha = fast_exp2(m - mn);     // 0 on the first tile (m = -inf)
+        m = mn;
+        float ps = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] = fast_exp2(s[r] - mn);
+            ps += s[r];
+        }
+        lsum = fmaf(lsum, alpha, ps);              // this lane half's share of the row sum
+        if (__builtin_amdgcn_ballot_w64(alpha != 1.f)) {      // no maximum of the wave's 32 queries grew: O stays as it is (a product with 1 is exact)
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[b][r] *= alpha;
+        }
+        const T* vc = vs + wave * SL + col;        // this lane's column of the wave's V slice: key row j at + j * HD, block b at + 32 b
+        if constexpr (F16) {
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                h8v pb;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pb[j] = _Float16(s[8 * st + j]);
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    h8v va;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) va[j] = vc[(16 * st + 8 * (j >> 2) + 4 * hf + (j & 3)) * HD + 32 * b];
+                    o[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pb, o[b], 0, 0, 0);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = (r & 3) + 8 * (r >> 2) + 4 * hf;
+#pragma unroll
+                for (int b = 0; b < NB; ++b) o[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(float(vc[key * HD + 32 * b]), s[r], o[b], 0, 0, 0);
+            }
+        }
+    }
+
+    lsum += __shfl_xor(lsum, 32, 64);
+    const bool live = q0 + col < L;                // padded queries were computed from the last row and are not stored
+    const float inv = 1.f / lsum;
+    T* orow = reinterpret_cast<T*>(a.out.p) + int64_t(n) * a.out.sn + int64_t(q0 + col) * a.out.sw + h * HD + wave * SL;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if constexpr (F16) {
+            // registers 4 g ... 4 g + 3 are the columns 8 g + 4 hf ... + 3: the lane halves trade so that half 0 holds the eight columns of the even
+            // groups and half 1 those of the odd groups, one 16-byte vector each
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                uint2 mine[2];
+#pragma unroll
+                for (int x = 0; x < 2; ++x) {
+                    h4v y;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) y[e] = _Float16(o[b][4 * (2 * p + x) + e] * inv);
+                    mine[x] = __builtin_bit_cast(uint2, y);
+                }
+                const uint2 give = hf ? mine[0] : mine[1], keep = hf ? mine[1] : mine[0];
+                uint2 got;
+                got.x = unsigned(__shfl_xor(int(give.x), 32, 64));
+                got.y = unsigned(__shfl_xor(int(give.y), 32, 64));
+                const uint4 w = hf ? make_uint4(got.x, got.y, keep.x, keep.y) : make_uint4(keep.x, keep.y, got.x, got.y);
+                if (live) *reinterpret_cast<uint4*>(orow + 32 * b + 8 * (2 * p + hf)) = w;
+            }
+        } else {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                if (live) *reinterpret_cast<float4*>(orow + 32 * b + 8 * g + 4 * hf) = make_float4(o[b][4 * g] * inv, o[b][4 * g + 1] * inv, o[b][4 * g + 2] * inv, o[b][4 * g + 3] * inv);
+        }
+    }
+}
+
 // the MFMA kernel's view: channels contiguous, token rows one pitch apart through the whole tensor, 16-byte aligned base
 bool vec_view_ok(const TensorArg& t, int V) {
     return t.sc == 1 && t.h == 1 && t.c % V == 0 && t.sw % V == 0 && t.sn == int64_t(t.w) * t.sw && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
@@ -286,6 +482,25 @@ hipError_t launch_mfma(const AttnArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+template <typename T, int HD>
+hipError_t launch_stream(const AttnArgs& a, hipStream_t stream) {
+    const int qblocks = (a.in.w + 31) / 32;
+    const int64_t blocks = int64_t(a.in.n) * a.heads * qblocks;
+    if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    attention_stream_kernel<T, HD><<<dim3(unsigned(blocks)), dim3(kAttnBlock), size_t(AttnStreamLdsBytes(HD, sizeof(T) == 2)), stream>>>(a, qblocks);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_stream_hd(const AttnArgs& a, hipStream_t stream) {
+    switch (a.head_dim) {
+        case 128: return launch_stream<T, 128>(a, stream);
+        case 256: return launch_stream<T, 256>(a, stream);
+        case 512: return launch_stream<T, 512>(a, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace
 
 bool AttentionEligible(const AttnArgs& a, int tile) {
@@ -296,8 +511,9 @@ bool AttentionEligible(const AttnArgs& a, int tile) {
     if (tile == 0) return true;
     const int V = a.out.f16 ? 8 : 4;
     // (the offsets are in the base pointers: their alignment stands for the offset condition)
-    return a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) && vec_view_ok(a.out, V) &&
-           AttnMfmaFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr);
+    if (a.in.f16 != a.out.f16 || !vec_view_ok(a.in, V) || !vec_view_ok(a.out, V)) return false;
+    return tile == 1 ? AttnMfmaFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr)
+                     : AttnStreamFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr);
 }
 
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream) {
@@ -311,6 +527,7 @@ hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream) {
         else hipLaunchKernelGGL(attention_generic_kernel<false>, dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
         return hipGetLastError();
     }
+    if (tile == 2) return a.out.f16 ? launch_stream_hd<_Float16>(a, stream) : launch_stream_hd<float>(a, stream);
     if (a.mask) {
         if (a.out.f16) return a.head_dim == 64 ? launch_mfma<_Float16, 64, true>(a, stream) : launch_mfma<_Float16, 32, true>(a, stream);
         return a.head_dim == 64 ? launch_mfma<float, 64, true>(a, stream) : launch_mfma<float, 32, true>(a, stream);
@@ -324,7 +541,10 @@ hipError_t InitKernelsAttn() {
         reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false>),
         reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false>),
         reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, true>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, true>)};
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, true>),
+        reinterpret_cast<const void*>(&attention_stream_kernel<float, 128>), reinterpret_cast<const void*>(&attention_stream_kernel<float, 256>),
+        reinterpret_cast<const void*>(&attention_stream_kernel<float, 512>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 128>),
+        reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 256>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 512>)};
     for (const void* k : kernels)
         if (const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget)); e != hipSuccess) return e;
     return hipSuccess;

@@ -3743,7 +3743,9 @@ void Planner::EmitTokenAssemble(const LNode& n, Step& s) {
     s.bytes = vbytes(s.in) + vbytes(s.out);
 }
 
-// attention: tile 1 (the MFMA kernel) where kernels.h AttnMfmaFits says so, else the generic kernel; IE_FORCE_TILE as for layer norm
+// attention: kernels.h AttnDefaultTile (tile 1, the MFMA kernel, where AttnMfmaFits says so; tile 2, the streaming kernel, on a wide head with
+// at least kAttnStreamMinTokens tokens; else the generic kernel).  IE_FORCE_TILE as for layer norm but over tiles 0 and 1 only; IE_ATTN_TILE
+// pins the attention steps alone, tile 2 included (an ineligible value is the generic kernel)
 void Planner::EmitAttention(const LNode& n, Step& s) {
     if (s.in.f8 || s.out.f8) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
     s.kind = StepKind::Attention;
@@ -3757,11 +3759,16 @@ void Planner::EmitAttention(const LNode& n, Step& s) {
         s.mask_value = n.mask_value;
         if (!s.in2.i64) fail("internal planner error: the key mask of node " + n.name + " is not an int64 view");
     }
-    const bool fits = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 &&
-                      AttnMfmaFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask);
-    s.tile = fits ? 1 : 0;
-    const int t = ForcedTile(kNumAttnTiles);
-    if (t >= 0) s.tile = t == 0 || fits ? t : 0;
+    const bool views = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16;
+    auto fits = [&](int tile) {
+        if (tile == 0) return true;
+        return views && (tile == 1 ? AttnMfmaFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask)
+                                   : AttnStreamFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask));
+    };
+    s.tile = views ? AttnDefaultTile(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask) : 0;
+    int t = ForcedTile(kNumAttnForcedTiles);
+    if (const char* e = env.get("IE_ATTN_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumAttnTiles) t = std::atoi(e);      // (the attention steps alone)
+    if (t >= 0) s.tile = fits(t) ? t : 0;
     s.flops = 4.0 * double(s.in.n) * double(s.heads) * double(s.in.w) * double(s.in.w) * double(s.head_dim);
     s.bytes = vbytes(s.in) + vbytes(s.out) + (n.key_mask ? vbytes(s.in2) : 0.0);
 }
