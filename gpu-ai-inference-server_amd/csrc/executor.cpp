@@ -1,4 +1,4 @@
-#include "executor.h"
+#include "executor_internal.h"
 #include "env.h"
 
 #include <algorithm>
@@ -15,128 +15,13 @@
 #include "igemm_tiles.h"
 #include "kernels.h"
 
+
 namespace ie {
 namespace {
 
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
-}
-
-// Kernel operand for a planned view.  A chunk instance of the pipelined host path (PlanInstance::batch_off > 0) addresses its
-// image range inside the parent's buffers: same layout, pointer advanced by batch_off images.
-TensorArg make_arg(const PlanInstance& pi, const View& v) {
-    TensorArg t;
-    char* base = reinterpret_cast<char*>(pi.buffers.at(size_t(v.buf)));
-    t.n = int(v.n); t.h = int(v.h); t.w = int(v.w); t.c = int(v.c);
-    t.f16 = v.f16 ? 1 : 0;
-    t.f8 = v.f8 ? 1 : 0;
-    const int64_t esize = v.esize();
-    if (v.nchw) {
-        t.sw = 1; t.sh = v.w; t.sc = v.h * v.w; t.sn = v.c * v.h * v.w;
-        t.p = reinterpret_cast<float*>(base + pi.batch_off * t.sn * esize);
-    } else {
-        t.sc = 1; t.sw = v.pitch; t.sh = v.w * v.pitch; t.sn = v.h * v.w * v.pitch;
-        t.p = reinterpret_cast<float*>(base + (v.c_off + pi.batch_off * t.sn) * esize);
-    }
-    return t;
-}
-
-// A view's shape and strides as make_arg lays them out, without a buffer (kernel labels of steps outside a plan instance)
-TensorArg view_strides(const View& v) {
-    TensorArg t;
-    t.n = int(v.n); t.h = int(v.h); t.w = int(v.w); t.c = int(v.c);
-    t.f16 = v.f16 ? 1 : 0;
-    t.f8 = v.f8 ? 1 : 0;
-    if (v.nchw) { t.sw = 1; t.sh = v.w; t.sc = v.h * v.w; t.sn = v.c * v.h * v.w; }
-    else { t.sc = 1; t.sw = v.pitch; t.sh = v.w * v.pitch; t.sn = v.h * v.w * v.pitch; }
-    return t;
-}
-
-ResizeArgs MakeResizeArgs(const PlanInstance& pi, const Step& s) {
-    ResizeArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    a.mode = int(s.rs_mode);
-    a.coord = int(s.rs_coord);
-    a.nearest = int(s.rs_nearest);
-    a.scale_h = s.rs_scale_h;
-    a.scale_w = s.rs_scale_w;
-    return a;
-}
-
-LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
-    LnArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    a.gamma = s.w_off >= 0 ? weights + s.w_off : nullptr;
-    a.beta = s.bias_off >= 0 ? weights + s.bias_off : nullptr;
-    a.eps = s.ln_eps;
-    return a;
-}
-
-GnArgs MakeGnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
-    GnArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    a.gamma = s.w_off >= 0 ? weights + s.w_off : nullptr;
-    a.beta = s.bias_off >= 0 ? weights + s.bias_off : nullptr;
-    a.groups = s.gn_groups;
-    a.eps = s.ln_eps;
-    a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
-    a.workspace = pi.workspace;
-    a.workspace_floats = pi.workspace_floats;
-    return a;
-}
-
-EmbedArgs MakeEmbedArgs(const PlanInstance& pi, const Step& s, const float* weights) {
-    EmbedArgs a;
-    a.ids = reinterpret_cast<const int64_t*>(make_arg(pi, s.in).p);
-    a.tids = s.has_in2 ? reinterpret_cast<const int64_t*>(make_arg(pi, s.in2).p) : nullptr;
-    a.out = make_arg(pi, s.out);
-    a.word = s.w_off >= 0 ? weights + s.w_off : nullptr;
-    a.type = s.w2_off >= 0 ? weights + s.w2_off : nullptr;
-    a.pos = s.emb_pos_off >= 0 ? weights + s.emb_pos_off : nullptr;
-    a.gamma = s.bias_off >= 0 ? weights + s.bias_off : nullptr;
-    a.beta = s.bias2_off >= 0 ? weights + s.bias2_off : nullptr;
-    a.vocab = int(s.emb_vocab);
-    a.types = int(s.emb_types);
-    a.eps = s.ln_eps;
-    return a;
-}
-
-AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s) {
-    AttnArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    a.heads = s.heads;
-    a.head_dim = s.head_dim;
-    a.scale = s.attn_scale;
-    if (s.key_mask && s.has_in2) {
-        a.mask = reinterpret_cast<const int64_t*>(make_arg(pi, s.in2).p);
-        a.mask_sn = s.in2.pitch;
-        a.mask_value = s.mask_value;
-    }
-    return a;
-}
-
-WinAttnArgs MakeWinAttnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
-    WinAttnArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    a.heads = s.heads;
-    a.head_dim = s.head_dim;
-    a.scale = s.attn_scale;
-    a.wh = s.win_h; a.ww = s.win_w; a.sh = s.shift_h; a.sw = s.shift_w;
-    a.bias = s.w_off >= 0 ? weights + s.w_off : nullptr;
-    a.mask = s.masked && s.w2_off >= 0 ? weights + s.w2_off : nullptr;
-    return a;
-}
-
 constexpr size_t kPinnedBytes = size_t(4) << 20;              // pinned staging for results (logits are KBs; larger outputs go direct)
 constexpr int64_t kTuneWorkspaceFloats = int64_t(16) << 20;   // 64 MiB of split-K slabs available to the autotuner
-constexpr int kNumCounters = 1 << 16;
 constexpr int kMaxChunks = 8;
-constexpr const char* kTuneFileTag = "# ie-tune-v2";
 
 std::once_flag g_kernels_once;
 hipError_t g_kernels_err = hipSuccess;
@@ -181,77 +66,6 @@ DeviceWeights::~DeviceWeights() {
     if (d_weights_wino_x6) (void)hipFree(d_weights_wino_x6);
 }
 
-namespace {
-
-std::string tune_file_header() {
-    std::ostringstream o;
-    o << kTuneFileTag << ' ' << kNumIgemmTiles << ' ' << kNumConvRasterTiles << ' ' << kNumConvWs32Tiles << ' ' << kNumConvWs16Tiles << ' ' << kNumConvWs3Tiles << ' '
-      << kNumConvDirectTiles << ' ' << kNumConvWinoTiles << ' ' << kNumConvX6Tiles << ' ' << kNumConvWs8Tiles << ' ' << kNumConvWs38Tiles << ' ' << kNumConvDenseFusedTiles << ' ' << kNumConvPooledTiles;
-    return o.str();
-}
-
-// Tune-file codes of the conv choices: base + tile of one kernel family, the family of a code is the last base at or below it.  Codes
-// below 100 are tiles of the tiled implicit GEMM in whichever staging (vec / scalar) the step has.  fp8 plans store their run-time
-// Step::tile (kernels.h kWs8Code, kWs38Code), which lies inside the ranges of the raster and weights-stationary 1x1 codes.
-// kLnTuneCode + tile: a layer_norm step's kernel variant.  Not a conv, so it is no entry of the table below: tune_code_valid and the layer-norm
-// branch of TuneStep know its range.
-constexpr int kLnTuneCode = 1000;
-bool ln_tune_code(int t) { return t >= kLnTuneCode && t < kLnTuneCode + kNumLnTiles; }
-// kPoolConvTuneCode + c: how a transition's pool, conv and entry-conv steps launch (PairTransitions).  c = 0: every step on its own; 1 + t: pool + conv
-// on tile t of conv1x1_pooled_kernel, the entry conv on its own; 1 + kNumConvPooledTiles + t: all three on tile t with the chained second conv
-constexpr int kPoolConvTuneCode = 1100;
-bool pool_conv_tune_code(int t) { return t >= kPoolConvTuneCode && t <= kPoolConvTuneCode + 2 * kNumConvPooledTiles; }
-struct TuneFamily { int base; ConvAlgo algo; int tiles; };
-constexpr TuneFamily kTuneFamilies[] = {
-    {0, ConvAlgo::IgemmVec, kNumIgemmTiles},          {100, ConvAlgo::Raster3x3, kNumConvRasterTiles},
-    {200, ConvAlgo::Ws1x1, std::max(kNumConvWs16Tiles, kNumConvWs32Tiles)},
-    {300, ConvAlgo::Ws3x3, kNumConvWs3Tiles},         {400, ConvAlgo::Direct, kNumConvDirectTiles},
-    {500, ConvAlgo::Wino3x3, kNumConvWinoTiles},      {600, ConvAlgo::X6, kNumConvX6Tiles},
-    {700, ConvAlgo::Depthwise, kNumConvDwTiles},      {800, ConvAlgo::Grouped, kNumConvGroupedTiles},
-    {900, ConvAlgo::Transposed, kNumConvtTiles},
-};
-
-const TuneFamily& tune_family(int code) {
-    const TuneFamily* f = &kTuneFamilies[0];
-    for (const auto& g : kTuneFamilies) if (code >= g.base) f = &g;
-    return *f;
-}
-
-int tune_code(ConvAlgo algo, int tile) {
-    for (const auto& g : kTuneFamilies) if (g.base != 0 && g.algo == algo) return g.base + tile;
-    return tile;
-}
-
-bool tune_code_valid(int t) {
-    return (t >= 0 && t - tune_family(t).base < tune_family(t).tiles) || ln_tune_code(t) || pool_conv_tune_code(t) || (t >= kWs8Code && t < kWs8Code + kNumConvWs8Tiles) ||
-           (t >= kWs38Code && t < kWs38Code + kNumConvWs38Tiles);
-}
-
-// "<signature ints> : <encoded tile> <splitk>" per line behind a header naming the tile tables the numbers index into; a file
-// written by an engine with other tables is ignored as a whole.
-void load_tune_file(const std::string& path, std::map<std::vector<int64_t>, std::pair<int, int>>& cache) {
-    std::ifstream f(path);
-    std::string line;
-    if (!f || !std::getline(f, line) || line != tune_file_header()) return;
-    while (std::getline(f, line)) {
-        std::istringstream is(line);
-        std::vector<int64_t> key;
-        std::string tok;
-        bool ok = true;
-        while (is >> tok && tok != ":") {
-            char* endp = nullptr;
-            const long long v = std::strtoll(tok.c_str(), &endp, 10);
-            if (!endp || *endp) { ok = false; break; }
-            key.push_back(v);
-        }
-        int t = -1, sp = 0;
-        if (ok && (is >> t >> sp) && tune_code_valid(t) && sp >= 1 && sp <= 64 &&
-            key.size() >= 6)          // (the fused steps have short signatures: stem + pool 7 numbers, dense block 10, dual 9)
-            cache[key] = {t, sp};
-    }
-}
-
-}  // namespace
 
 DeviceModel::DeviceModel(std::shared_ptr<const OnnxModel> model, int device_id, const DeviceModelOptions& opt)
     : model_(std::move(model)), device_(device_id), precision_(opt.precision) {
@@ -908,1193 +722,6 @@ void DeviceModel::EnsurePipeline(PlanInstance& pi, bool allow_tune) {
         throw;
     }
     pi.head_steps = int(head);
-}
-
-// One top-level Autotune call: the timing events and the L2 scrub buffer (freed on every way out), the cache accessors, and whether a
-// choice was searched (the tune file is then saved once, at the end).  The parts of a fused step are tuned with the same context.
-struct DeviceModel::TuneContext {
-    DeviceWeights& w;
-    bool allow_search, log;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    void* scrub = nullptr;                 // nullptr: the hot protocol
-    bool searched = false;
-    static constexpr size_t kScrubBytes = size_t(64) << 20;       // > 8 x 4 MiB of L2
-    ~TuneContext() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (scrub) (void)hipFree(scrub);
-    }
-    bool lookup(const std::vector<int64_t>& key, std::pair<int, int>* choice) {     // (encoded tile, split-K) of a signature
-        std::lock_guard<std::mutex> g(w.tune_mu);
-        auto hit = w.tune_cache.find(key);
-        if (hit == w.tune_cache.end()) return false;
-        *choice = hit->second;
-        return true;
-    }
-    void store(const std::vector<int64_t>& key, int code, int splitk) {
-        std::lock_guard<std::mutex> g(w.tune_mu);
-        w.tune_cache[key] = {code, splitk};
-        w.tune_dirty = true;
-        searched = true;
-    }
-};
-
-// Kernel choice per conv step of pi.plan.steps[0, nsteps): an exact hit in the device's cache, else (allow_search) the exhaustive
-// timed search, else the cached choice of the same conv at the nearest pixel count (within 2x), else the planner's default.
-void DeviceModel::Autotune(PlanInstance& pi, size_t nsteps, bool allow_search) {
-    TuneContext ctx{*w_, allow_search, env_.flag("IE_TUNE_LOG")};
-    check(hipEventCreate(&ctx.e0), "hipEventCreate");
-    check(hipEventCreate(&ctx.e1), "hipEventCreate");
-    if (const char* e = env_.get("IE_TUNE_HOT"); allow_search && !(e && std::atoi(e) != 0))
-        if (hipMalloc(&ctx.scrub, TuneContext::kScrubBytes) != hipSuccess) { ctx.scrub = nullptr; (void)hipGetLastError(); }
-    for (size_t si = 0; si < nsteps && si < pi.plan.steps.size(); ++si) TuneStep(ctx, pi, pi.plan.steps[si]);
-    if (nsteps >= pi.plan.steps.size()) PairTransitions(&ctx, pi);      // (a chunk instance runs head steps only: nothing is paired there)
-    if (ctx.searched) SaveTuneCache();
-}
-
-// Best time in ms of one trial step: a warm launch, then cold -- three rounds of L2 scrub + one timed launch: in the real
-// forward a layer finds neither its weights nor its input in L2 (the other layers ran in between), back-to-back repeats would flatter
-// every kernel that re-reads operands from L2 -- or hot (IE_TUNE_HOT=1, or no scrub buffer): two timed triples.
-float DeviceModel::TimeTrial(TuneContext& ctx, const PlanInstance& pi, const Step& trial) {
-    const float best = TimeLaunches(ctx, [&] { LaunchStep(pi, trial, stream_); });
-    if (ctx.log)
-        std::fprintf(stderr, "[ie-tune] M=%lld N=%lld K=%lld algo=%d tile=%d splitk=%d: %.4f ms\n", static_cast<long long>(trial.out.n * trial.out.h * trial.out.w),
-                     static_cast<long long>(trial.out.c), static_cast<long long>(trial.kh * trial.kw * trial.in.c), int(trial.algo), trial.tile, trial.splitk, best);
-    return best;
-}
-
-// The same protocol for any launch sequence (a step, or the launches of a candidate that covers several steps)
-float DeviceModel::TimeLaunches(TuneContext& ctx, const std::function<void()>& launch) {
-    auto timed = [&](int launches) {
-        check(hipEventRecord(ctx.e0, stream_), "hipEventRecord");
-        for (int r = 0; r < launches; ++r) launch();
-        check(hipEventRecord(ctx.e1, stream_), "hipEventRecord");
-        check(hipEventSynchronize(ctx.e1), "hipEventSynchronize");
-        float ms = 0;
-        check(hipEventElapsedTime(&ms, ctx.e0, ctx.e1), "hipEventElapsedTime");
-        return ms;
-    };
-    launch();                                        // warm
-    float best = 1e30f;
-    for (int rep = 0; rep < (ctx.scrub ? 3 : 2); ++rep) {
-        if (ctx.scrub) check(hipMemsetAsync(ctx.scrub, 0, TuneContext::kScrubBytes, stream_), "hipMemsetAsync(scrub)");
-        best = std::min(best, timed(ctx.scrub ? 1 : 3));
-    }
-    return best;
-}
-
-void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
-    if (s.kind == StepKind::LayerNorm) {
-        // the generic kernel and the lane-group variants that hold the row (tune-file codes kLnTuneCode + tile)
-        // (the channel offsets decide which tiles are eligible: they are part of the signature)
-        const std::vector<int64_t> key = {s.in.n * s.in.h * s.in.w, s.in.c, s.in.pitch, s.out.pitch, s.in.c_off, s.out.c_off, int64_t(s.in.f16), int64_t(s.out.f16), kLnTuneCode,
-                                          s.bias_off >= 0};
-        std::pair<int, int> hit{-1, 0};
-        if (ctx.lookup(key, &hit)) {
-            if (ln_tune_code(hit.first)) s.tile = hit.first - kLnTuneCode;
-            return;
-        }
-        if (!ctx.allow_search) return;
-        const LnArgs a = MakeLnArgs(pi, s, w_->d_weights);
-        float best = 1e30f;
-        int best_t = s.tile;
-        for (int t = 0; t < kNumLnTiles; ++t)
-            if (LayerNormEligible(a, t)) {
-                Step trial = s;
-                trial.tile = t;
-                if (const float ms = TimeTrial(ctx, pi, trial); ms < best) { best = ms; best_t = t; }
-            }
-        s.tile = best_t;
-        ctx.store(key, kLnTuneCode + best_t, 1);
-        return;
-    }
-    if (s.kind != StepKind::Conv || s.algo == ConvAlgo::Naive || s.algo == ConvAlgo::Stem) return;
-    std::pair<int, int> hit{-1, 0};
-    auto cached_tile = [&](const std::vector<int64_t>& key) { return ctx.lookup(key, &hit) ? hit.first : -1; };
-    auto time_tile = [&](int t) {
-        Step trial = s;
-        trial.tile = t;
-        return TimeTrial(ctx, pi, trial);
-    };
-    if (s.algo == ConvAlgo::DualF8) {
-        if (!s.in.f8) return;                  // (a calibration plan: never tuned)
-        const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, s.parts.size() == 2 ? s.parts[0].in.c : 0, s.parts.size() == 2 ? s.parts[0].sh : 0,
-                                          s.in.pitch, s.out.pitch, int64_t(ConvAlgo::DualF8), s.bias_off >= 0};
-        if (ctx.lookup(key, &hit)) { s.tile = hit.first; return; }
-        if (!ctx.allow_search || !w_->f8_ready) return;
-        const ConvArgs a = MakeConvArgs(pi, s);
-        float best = 1e30f;
-        int best_t = kWs8Code + 1;             // (tile 0 is not a candidate)
-        for (int t = 1; t < kNumConvWs8Tiles; ++t)
-            if (ConvWs8Eligible(a, t))
-                if (const float ms = time_tile(kWs8Code + t); ms < best) { best = ms; best_t = kWs8Code + t; }
-        s.tile = best_t;
-        ctx.store(key, best_t, 1);
-        return;
-    }
-    if (s.algo == ConvAlgo::StemPool) {
-        // fused vs the two launches: one timed choice (tile 1 / 0), cached like the others
-        const std::vector<int64_t> key = {s.in.n, s.in.h, s.in.w, s.out.c, s.out.pitch, s.out.f8 ? 2 : (s.out.f16 ? 1 : 0), int64_t(ConvAlgo::StemPool)};
-        int choice = cached_tile(key);
-        const bool can = ConvStemPoolEligible(MakeConvArgs(pi, s));
-        if (choice < 0 && ctx.allow_search && can && !(s.out.f8 && !w_->f8_ready)) {
-            const float two = time_tile(0), one = time_tile(1);
-            choice = one <= two * 1.05f ? 1 : 0;      // within the timer's noise the single launch wins: it moves a third of the bytes
-            ctx.store(key, choice, 1);
-        }
-        if (!can) choice = 0;
-        if (choice >= 0) s.tile = choice;
-        return;
-    }
-    // the parts of a fused step get their own kernel choices (what runs when the fused launcher declines, and the yardstick), tuned in
-    // place: they address the parent's buffers like every step (make_arg reads only buffers and batch_off)
-    if (s.algo == ConvAlgo::DenseBlock || s.algo == ConvAlgo::DenseFused)
-        for (Step& q : s.parts) TuneStep(ctx, pi, q);
-    if (s.algo == ConvAlgo::DenseBlock) {
-        // chain vs parts is one more timed choice (tile 1 = one launch, 0 = the 2n plain launches)
-        const std::vector<int64_t> key = {s.in.n * s.in.h * s.in.w, int64_t(s.parts.size()), s.in.c, s.in.h, s.in.w, s.in.pitch, s.in.c_off, int64_t(ConvAlgo::DenseBlock),
-                                          s.pre_scale_off >= 0, s.bias_off >= 0};
-        int choice = cached_tile(key);
-        DenseBlockArgs b;
-        const bool can = MakeBlockArgs(pi, s, &b) && DenseBlockEligible(b);
-        if (choice < 0 && ctx.allow_search && can) {
-            const float parts = time_tile(0), chain = time_tile(1);
-            choice = chain <= parts ? 1 : 0;
-            ctx.store(key, choice, 1);
-        }
-        if (!can) choice = 0;
-        if (choice >= 0) s.tile = choice;
-        return;
-    }
-    if (s.algo == ConvAlgo::DenseFused) {
-        // fused vs split is one more timed choice (tile 1 .. kNumConvDenseFusedTiles = fused tile variants of kernels_fused.hip, 0 = the two plain launches)
-        const Step& p3 = s.parts[0];
-        const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, 1, 1, 1, 1, 0, 0, s.in.h, s.in.w, s.in.pitch, s.out.pitch, 0, int64_t(ConvAlgo::DenseFused),
-                                          s.pre_scale_off >= 0, s.bias_off >= 0, p3.in.c, p3.in.pitch};
-        int choice = cached_tile(key);
-        if (choice < 0 && ctx.allow_search) {
-            FusedArgs f;
-            f.in3 = make_arg(pi, p3.in);
-            f.out3 = make_arg(pi, p3.out);
-            f.wfrag3 = w_->d_weights_frag && p3.w_off >= 0 ? w_->d_weights_frag + p3.w_off : nullptr;
-            const ConvArgs a1 = MakeConvArgs(pi, s);
-            float best = 1e30f;
-            choice = 0;
-            for (int t = 0; t <= kNumConvDenseFusedTiles; ++t)
-                if (t == 0 || ConvDenseFusedEligible(a1, f, t))
-                    if (const float ms = time_tile(t); ms < best) { best = ms; choice = t; }
-            ctx.store(key, choice, 1);
-        }
-        if (choice >= 0) s.tile = choice;          // tile 0: ConvDenseFusedEligible declines, the parts run
-        return;
-    }
-    if (s.algo == ConvAlgo::Depthwise) {
-        // the generic kernel and the three channel-vector variants (tune-file codes 700 + tile); nothing else may run a depthwise conv
-        const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch, s.out.pitch,
-                                          s.in.nchw ? 2 : int64_t(s.in.f16), int64_t(ConvAlgo::Depthwise), s.pre_scale_off >= 0, s.has_in2};
-        if (ctx.lookup(key, &hit)) {
-            if (tune_family(hit.first).algo == ConvAlgo::Depthwise) s.tile = hit.first - tune_family(hit.first).base;
-            return;
-        }
-        if (!ctx.allow_search) return;
-        const DwArgs a = MakeDwArgs(pi, s);
-        float best = 1e30f;
-        int best_t = s.tile;
-        for (int t = 0; t < kNumConvDwTiles; ++t)
-            if (ConvDwEligible(a, t))
-                if (const float ms = time_tile(t); ms < best) { best = ms; best_t = t; }
-        s.tile = best_t;
-        ctx.store(key, tune_code(ConvAlgo::Depthwise, best_t), 1);
-        return;
-    }
-    if (s.algo == ConvAlgo::Grouped) {
-        // the generic kernel and the channel-block variants (tune-file codes 800 + tile); nothing else may run a grouped conv
-        const std::vector<int64_t> key = {s.out.n * s.out.h * s.out.w, s.out.c, s.in.c, s.group, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch,
-                                          s.out.pitch, s.in.nchw ? 2 : int64_t(s.in.f16), int64_t(ConvAlgo::Grouped), s.pre_scale_off >= 0, s.has_in2};
-        if (ctx.lookup(key, &hit)) {
-            if (tune_family(hit.first).algo == ConvAlgo::Grouped) s.tile = hit.first - tune_family(hit.first).base;
-            return;
-        }
-        if (!ctx.allow_search) return;
-        const GroupedArgs a = MakeGroupedArgs(pi, s);
-        float best = 1e30f;
-        int best_t = s.tile;
-        for (int t = 0; t < kNumConvGroupedTiles; ++t)
-            if (ConvGroupedEligible(a, t))
-                if (const float ms = time_tile(t); ms < best) { best = ms; best_t = t; }
-        s.tile = best_t;
-        ctx.store(key, tune_code(ConvAlgo::Grouped, best_t), 1);
-        return;
-    }
-    if (s.algo == ConvAlgo::Transposed) {
-        // the generic kernel and the MFMA variants of the non-overlapping case (tune-file codes 900 + tile); nothing else may run a transposed conv
-        const std::vector<int64_t> key = {s.in.n * s.in.h * s.in.w, s.out.c, s.in.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.pb, s.pr, s.oph, s.opw, s.in.h, s.in.w,
-                                          s.in.pitch, s.out.pitch, s.in.nchw ? 2 : int64_t(s.in.f16), int64_t(ConvAlgo::Transposed), s.bias_off >= 0};
-        if (ctx.lookup(key, &hit)) {
-            if (tune_family(hit.first).algo == ConvAlgo::Transposed) s.tile = hit.first - tune_family(hit.first).base;
-            return;
-        }
-        if (!ctx.allow_search) return;
-        const ConvtArgs a = MakeConvtArgs(pi, s);
-        float best = 1e30f;
-        int best_t = s.tile;
-        for (int t = 0; t < kNumConvtTiles; ++t)
-            if (ConvTransposedEligible(a, t))
-                if (const float ms = time_tile(t); ms < best) { best = ms; best_t = t; }
-        s.tile = best_t;
-        ctx.store(key, tune_code(ConvAlgo::Transposed, best_t), 1);
-        return;
-    }
-    const int64_t M = s.out.n * s.out.h * s.out.w, N = s.out.c;
-    if (s.algo == ConvAlgo::IgemmF8) {
-        // fp8 convs: the tiled implicit GEMM's tiles, then the weights-stationary 1x1 kernel's, then the 3x3's
-        const std::vector<int64_t> key = {M, N, s.in.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch, s.out.pitch, 0, int64_t(s.algo), 0,
-                                          s.bias_off >= 0, 8, s.has_in2};
-        if (ctx.lookup(key, &hit)) { s.tile = hit.first; return; }
-        if (!ctx.allow_search || !w_->f8_ready) return;
-        const ConvArgs a = MakeConvArgs(pi, s);
-        float best = 1e30f;
-        int best_t = s.tile;
-        auto consider = [&](int t) { if (const float ms = time_tile(t); ms < best) { best = ms; best_t = t; } };
-        for (int t = 0; t < kNumConvF8Tiles; ++t) if (!(kIgemmTiles[t].bn > 32 && N <= 32)) consider(t);
-        for (int t = 0; t < kNumConvWs8Tiles; ++t) if (ConvWs8Eligible(a, t)) consider(kWs8Code + t);
-        for (int t = 0; t < kNumConvWs38Tiles; ++t) if (ConvWs38Eligible(a, t)) consider(kWs38Code + t);
-        s.tile = best_t;
-        ctx.store(key, best_t, 1);
-        return;
-    }
-    const Step planned = s;                    // the planner's default, kept when nothing better is known
-    // the planner's default may already name a specialised kernel: the search starts from the tiled implicit GEMM either way
-    if (s.algo == ConvAlgo::Ws1x1 || s.algo == ConvAlgo::Ws3x3 || s.algo == ConvAlgo::Direct || s.algo == ConvAlgo::Raster3x3 || s.algo == ConvAlgo::Wino3x3 || s.algo == ConvAlgo::X6) {
-        s.algo = ConvAlgo::IgemmVec;
-        s.tile = s.base_tile;
-        s.splitk = 1;
-    }
-    const int64_t bk = s.in.f16 ? 2 * kIgemmBK : kIgemmBK;
-    const int64_t KT = s.algo == ConvAlgo::IgemmVec ? int64_t(s.kh) * s.kw * ((s.in.c + bk - 1) / bk)
-                                                   : (int64_t(s.kh) * s.kw * s.in.c + kIgemmBK - 1) / kIgemmBK;
-    std::vector<int64_t> key = {M, N, s.in.c, s.kh, s.kw, s.sh, s.sw, s.pt, s.pl, s.in.h, s.in.w, s.in.pitch, s.out.pitch,
-                                s.in.nchw, int64_t(s.algo), s.pre_scale_off >= 0, s.bias_off >= 0};
-    if (s.in.f16 || s.out.f16) { key.push_back(s.in.f16); key.push_back(s.out.f16); }   // fp32 signatures keep 17 entries
-    if (s.has_in2) key.push_back(1);              // a fused residual changes which kernels apply (18 / 20 entries)
-    const bool dil = s.dh != 1 || s.dw != 1;
-    if (dil) key.insert(key.end(), {-1, s.dh, s.dw});   // dilated convs: -1 (no other signature has a negative entry) and the dilation
-    // Split-K admissibility (sp > 1) of the two families that split, for the search and for a choice taken from another pixel count
-    auto igemm_split_ok = [&](const IgemmTile& T, int sp) {
-        const int64_t wgs = ((M + T.bm - 1) / T.bm) * ((N + T.bn - 1) / T.bn);
-        if (T.kg > 1 && ((!two_pass_splitk_ && !s.in.f16) || KT / (sp * T.kg) < 2)) return false;
-        return KT / sp >= 2 && int64_t(sp) * wgs * T.bm * T.bn <= pi.workspace_floats && wgs <= kNumCounters && wgs * sp <= 8192 && wgs < 1024;
-    };
-    auto raster_split_ok = [&](int sp) {
-        const int64_t chunks = (s.in.c + kIgemmBK - 1) / kIgemmBK, Mr = s.in.n * (s.in.h + 1) * (s.in.w + 1);
-        return sp <= chunks && Mr / 64 * sp <= 16384 && int64_t(sp) * (M + 256) * (N + 64) * 2 <= pi.workspace_floats;
-    };
-    bool exact = ctx.lookup(key, &hit);
-    if (!exact && !ctx.allow_search) {
-        // nearest pixel count of the same conv (every other field of the signature equal), at most 2x away
-        double best_d = 1.0;        // |log2(M' / M)| <= 1
-        std::lock_guard<std::mutex> g(w_->tune_mu);
-        for (const auto& kv : w_->tune_cache) {
-            if (kv.first.size() != key.size() || !std::equal(kv.first.begin() + 1, kv.first.end(), key.begin() + 1)) continue;
-            const double d = std::fabs(std::log2(double(kv.first[0]) / double(M)));
-            if (d <= best_d) { best_d = d; hit = kv.second; }
-        }
-    }
-    if (exact || hit.first >= 0) {
-        const TuneFamily& f = tune_family(hit.first);
-        int sp = hit.second;
-        if (!exact && sp > 1 && !(f.base == 0 ? igemm_split_ok(kIgemmTiles[hit.first], sp) : f.algo == ConvAlgo::Raster3x3 && raster_split_ok(sp)))
-            sp = 1;                             // split-K slabs must fit this instance's workspace at this pixel count
-        if (f.base != 0) s.algo = f.algo;
-        s.tile = hit.first - f.base;
-        s.splitk = sp;
-        return;
-    }
-    if (!ctx.allow_search) { s = planned; return; }
-    float best = 1e30f;
-    Step chosen = s;
-    auto consider = [&](ConvAlgo algo, int t, int sp) {
-        Step trial = s;
-        trial.algo = algo;
-        trial.tile = t;
-        trial.splitk = sp;
-        if (const float ms = TimeTrial(ctx, pi, trial); ms < best) { best = ms; chosen = trial; }
-    };
-    // LDS-window kernel for 3x3/s1/p1 convs without an activation prologue
-    // (a dilated conv only has the implicit GEMM's base tiles: every other family reads adjacent taps)
-    if (!dil && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.sh == 1 && s.sw == 1 && s.pt == 1 && s.pl == 1 && s.pb == 1 &&
-        s.pr == 1 && s.pre_scale_off < 0) {
-        ConvArgs probe;
-        probe.in = make_arg(pi, s.in);
-        probe.out = make_arg(pi, s.out);
-        probe.w = w_->d_weights + s.w_off;
-        probe.kh = 3; probe.kw = 3; probe.pt = 1; probe.pl = 1;
-        for (int t = 0; t < kNumConvRasterTiles; ++t) {
-            if (!ConvRasterEligible(probe, t) || (ConvRasterTileBn(t) > 32 && N <= 32)) continue;
-            for (int sp : {1, 2, 4, 8})
-                if (sp == 1 || raster_split_ok(sp)) consider(ConvAlgo::Raster3x3, t, sp);
-        }
-    }
-    // Winograd F(2x2, 3x3): 2.25x fewer MACs for the 32-channel 3x3 convs on even-sized images
-    if (!dil && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3 && s.out.c == 32 && !s.has_in2) {
-        Step probe_step = s;
-        probe_step.algo = ConvAlgo::Wino3x3;
-        ConvArgs probe = MakeConvArgs(pi, probe_step);
-        for (int t = 0; t < kNumConvWinoTiles; ++t) {
-            if (!ConvWinoEligible(probe, t)) {
-                if (ctx.log)
-                    std::fprintf(stderr, "[ie-tune] M=%lld wino tile %d ineligible: wfrag=%p in(c=%d h=%d w=%d sw=%lld sh=%lld sn=%lld p=%p) out(c=%d sw=%lld p=%p) bias=%p pre=%p\n",
-                                 static_cast<long long>(M), t, (const void*)probe.wfrag, probe.in.c, probe.in.h, probe.in.w, (long long)probe.in.sw, (long long)probe.in.sh,
-                                 (long long)probe.in.sn, (void*)probe.in.p, probe.out.c, (long long)probe.out.sw, (void*)probe.out.p, (const void*)probe.bias, (const void*)probe.pre_scale);
-                continue;
-            }
-            consider(ConvAlgo::Wino3x3, t, 1);
-        }
-    }
-    // bf16x6 (opt-in): the 1x1 convs on the bf16 matrix pipe with exactly split operands
-    if (!dil && w_->d_weights_x6 && !s.in.f16 && !s.out.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1 && !s.has_in2) {
-        Step probe_step = s;
-        probe_step.algo = ConvAlgo::X6;
-        ConvArgs probe = MakeConvArgs(pi, probe_step);
-        for (int t = 0; t < kNumConvX6Tiles; ++t)
-            if (ConvX6Eligible(probe, t)) consider(ConvAlgo::X6, t, 1);
-    }
-    // the kernels_direct.hip family (every variant checks its own pixel-count / shape limits): K split over the waves with
-    // operands straight from global memory, LDS-window tiles, activations-stationary 1x1, window + streamed weights
-    if (!dil && s.algo == ConvAlgo::IgemmVec) {
-        ConvArgs probe = MakeConvArgs(pi, s);
-        probe.res = TensorArg();                   // LaunchStep adds the shortcut in a second kernel for this family
-        for (int t = 0; t < kNumConvDirectTiles; ++t)
-            if (ConvDirectEligible(probe, t)) consider(ConvAlgo::Direct, t, 1);
-    }
-    // 1x1/s1: weights-stationary streaming kernel (either precision)
-    if (!dil && s.algo == ConvAlgo::IgemmVec && s.kh == 1 && s.kw == 1) {
-        ConvArgs probe = MakeConvArgs(pi, s);
-        for (int t = 0; t < (s.in.f16 ? kNumConvWs16Tiles : kNumConvWs32Tiles); ++t)
-            if (s.in.f16 ? ConvWsEligible(probe, t) : ConvWs32Eligible(probe, t)) consider(ConvAlgo::Ws1x1, t, 1);
-    }
-    if (!dil && s.in.f16 && s.algo == ConvAlgo::IgemmVec && s.kh == 3 && s.kw == 3) {
-        ConvArgs probe = MakeConvArgs(pi, s);
-        for (int t = 0; t < kNumConvWs3Tiles; ++t)
-            if (ConvWs3Eligible(probe, t)) consider(ConvAlgo::Ws3x3, t, 1);
-    }
-    static const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24};
-    for (int t = 0; t < kNumIgemmTiles; ++t) {
-        const IgemmTile& T = kIgemmTiles[t];
-        if (dil && t >= kNumIgemmBaseTiles) continue;
-        if ((T.bn > 32 && N <= 32) || (T.bn > 64 && N <= 64)) continue;
-        if ((T.kg > 1 || T.deep) && (s.algo != ConvAlgo::IgemmVec || KT < 2 * T.kg)) continue;
-        if (T.deep && s.in.f16) continue;         // the fp16 kernel has no deep-prefetch variants
-        if (T.deep && ((M + T.bm - 1) / T.bm) * ((N + T.bn - 1) / T.bn) > 1024) continue;       // the deep-prefetch variants target grids that cannot fill the chip
-        for (int sp : kSplits)
-            if (sp == 1 || igemm_split_ok(T, sp)) consider(s.algo, t, sp);
-    }
-    s = chosen;
-    ctx.store(key, tune_code(s.algo, s.tile), s.splitk);
-}
-
-// Whole-file rewrite through a temporary + rename, so a reader (another process loading the same model) never sees a torn file
-// and concurrent writers cannot interleave lines.
-void DeviceModel::SaveTuneCache() {
-    std::lock_guard<std::mutex> g(w_->tune_mu);
-    if (w_->tune_cache_path.empty() || !w_->tune_dirty) return;
-    const std::string tmp = w_->tune_cache_path + ".tmp" + std::to_string(long(getpid())) + "." + std::to_string(device_);
-    {
-        std::ofstream f(tmp, std::ios::trunc);
-        if (!f) return;                                   // read-only model directory: keep the choices in memory only
-        f << tune_file_header() << '\n';
-        for (auto& kv : w_->tune_cache) {
-            for (auto v : kv.first) f << v << ' ';
-            f << ": " << kv.second.first << ' ' << kv.second.second << '\n';
-        }
-        if (!f.good()) { f.close(); std::remove(tmp.c_str()); return; }
-    }
-    if (std::rename(tmp.c_str(), w_->tune_cache_path.c_str()) != 0) std::remove(tmp.c_str());
-    else w_->tune_dirty = false;
-}
-
-// Kernel arguments of a dense-block chain step (kernels_block.hip) from its parts: (1x1, 3x3) pairs on one concat buffer.
-bool DeviceModel::MakeBlockArgs(const PlanInstance& pi, const Step& s, DenseBlockArgs* out) const {
-    if (s.parts.size() < 2 || s.parts.size() % 2 || s.parts.size() / 2 > size_t(kMaxBlockLayers) || !w_->d_weights16 || !w_->d_weights16_frag) return false;
-    DenseBlockArgs b;
-    const Step& f1 = s.parts[0];
-    const TensorArg xin = make_arg(pi, f1.in);
-    b.x = reinterpret_cast<_Float16*>(xin.p) - f1.in.c_off;           // pixel row start of the concat buffer (this plan instance's image range)
-    b.pitch = int(f1.in.pitch);
-    b.in_coff = int(f1.in.c_off);
-    b.n = int(f1.in.n); b.h = int(f1.in.h); b.w = int(f1.in.w);
-    b.wfrag16 = static_cast<const _Float16*>(w_->d_weights16_frag);
-    b.w16 = static_cast<const _Float16*>(w_->d_weights16);
-    b.w32 = w_->d_weights;
-    b.w16_bytes = uint64_t(w_->weight_floats) * 2;
-    b.nlayers = int(s.parts.size() / 2);
-    auto u = [](int64_t off) { return off >= 0 ? unsigned(off) : 0xffffffffu; };
-    for (int l = 0; l < b.nlayers; ++l) {
-        const Step& c1 = s.parts[size_t(2 * l)];
-        const Step& c3 = s.parts[size_t(2 * l + 1)];
-        bool have1 = false, have3 = false;
-        for (const auto& fr : w_->frag16_regions) { have1 = have1 || fr.w_off == c1.w_off; have3 = have3 || fr.w_off == c3.w_off; }
-        if (!have1 || !have3 || c1.w_off >= (int64_t(1) << 31) || c3.w_off >= (int64_t(1) << 31)) return false;
-        DenseBlockLayer& L = b.layer[l];
-        L.K = int(c1.in.c);
-        L.out_coff = int(c3.out.c_off);
-        L.w1 = unsigned(c1.w_off);
-        L.w3 = unsigned(c3.w_off);
-        L.ps = u(c1.pre_scale_off);
-        L.pt = u(c1.pre_shift_off);
-        L.b1 = u(c1.bias_off);
-        L.b3 = u(c3.bias_off);
-        L.flags = (c1.pre_relu ? 1 : 0) | (c1.relu ? 2 : 0) | (c3.relu ? 4 : 0);
-    }
-    *out = b;
-    return true;
-}
-
-ConvArgs DeviceModel::MakeConvArgs(const PlanInstance& pi, const Step& s) const {
-    const float* wb = w_->d_weights;
-    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
-    ConvArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    if (s.has_in2) a.res = make_arg(pi, s.in2);
-    a.w = wp(s.w_off);
-    a.w16 = w_->d_weights16 && s.w_off >= 0 ? static_cast<const char*>(w_->d_weights16) + s.w_off * 2 : nullptr;
-    a.wfrag = w_->d_weights_frag && s.w_off >= 0 && s.out.c % 16 == 0 && s.in.c % 16 == 0 && s.kh * s.kw <= 49 ? w_->d_weights_frag + s.w_off : nullptr;
-    a.bias = wp(s.bias_off);
-    a.pre_scale = wp(s.pre_scale_off);
-    a.pre_shift = wp(s.pre_shift_off);
-    if (w_->d_weights16 && s.pre_scale_off >= 0) {
-        a.pre_scale16 = static_cast<const char*>(w_->d_weights16) + s.pre_scale_off * 2;
-        a.pre_shift16 = static_cast<const char*>(w_->d_weights16) + s.pre_shift_off * 2;
-    }
-    a.kh = s.kh; a.kw = s.kw; a.sh = s.sh; a.sw = s.sw; a.pt = s.pt; a.pl = s.pl;
-    a.dh = int16_t(s.dh); a.dw = int16_t(s.dw);
-    a.pre_relu = s.pre_relu; a.relu = s.relu;
-    a.workspace = pi.workspace;
-    a.workspace_floats = pi.workspace_floats;
-    a.counters = pi.counters;
-    a.num_counters = pi.counters ? kNumCounters : 0;
-    if (s.algo == ConvAlgo::X6) {                    // the split kernel reads its three bf16 planes through `w16`
-        a.w16 = nullptr;
-        for (const auto& xr : w_->x6_regions)
-            if (xr.w_off == s.w_off && w_->d_weights_x6) a.w16 = static_cast<const char*>(w_->d_weights_x6) + xr.byte_off;
-    }
-    if (s.algo == ConvAlgo::Wino3x3) {               // the Winograd kernel reads the transformed weights through `wfrag`
-        a.wfrag = nullptr;
-        a.w16 = nullptr;
-        for (const auto& wr : w_->wino_regions)
-            if (wr.w_off == s.w_off && w_->d_weights_wino) {
-                a.wfrag = w_->d_weights_wino + wr.u_off;
-                a.w16 = w_->d_weights_wino_x6 ? static_cast<const char*>(w_->d_weights_wino_x6) + wr.u_off * 6 : nullptr;
-            }
-    }
-    if (s.out.f8 || s.in.f8) {       // fp8 mode: e4m3 weights, per-channel epilogue multipliers, tensor scales
-        const DeviceWeights& W = *w_;
-        auto scale_of = [&](int step) { return step >= 0 && size_t(step) < W.act_scale.size() && W.act_scale[size_t(step)] > 0.f ? W.act_scale[size_t(step)] : 1.f; };
-        a.out_qscale = 1.0f / scale_of(s.idx);
-        a.res_scale = scale_of(s.in2_src);
-        for (const auto& fc : W.f8_convs)
-            if (fc.w_off == s.w_off) {
-                a.w8 = static_cast<const char*>(W.d_weights8) + fc.w_off;
-                a.escale = W.d_f8_aux + fc.aux_off + (fc.cout + 3) / 4 * 4;
-            }
-        if (s.algo == ConvAlgo::DualF8 && s.parts.size() == 2) {       // the projection conv rides along as a second GEMM
-            const Step& pj = s.parts[0];
-            a.in2 = make_arg(pi, pj.in);
-            a.sh2 = pj.sh; a.sw2 = pj.sw;
-            a.bias_b = wp(pj.bias_off);
-            for (const auto& fc : W.f8_convs)
-                if (fc.w_off == pj.w_off) {
-                    a.w8b = static_cast<const char*>(W.d_weights8) + fc.w_off;
-                    a.escale_b = W.d_f8_aux + fc.aux_off + (fc.cout + 3) / 4 * 4;
-                }
-        }
-    }
-    return a;
-}
-
-DwArgs DeviceModel::MakeDwArgs(const PlanInstance& pi, const Step& s) const {
-    const float* wb = w_->d_weights;
-    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
-    DwArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    if (s.has_in2) a.res = make_arg(pi, s.in2);
-    a.w = wp(s.w_off);
-    a.bias = wp(s.bias_off);
-    a.pre_scale = wp(s.pre_scale_off);
-    a.pre_shift = wp(s.pre_shift_off);
-    a.pre_relu = s.pre_relu;
-    a.pre_hi = s.pre_hi;
-    a.kh = s.kh; a.kw = s.kw; a.sh = s.sh; a.sw = s.sw; a.pt = s.pt; a.pl = s.pl;
-    a.relu = s.relu;
-    a.lo = s.lo;
-    a.hi = s.hi;
-    a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
-    a.pre_act = int(s.pre_act.kind); a.pre_act_a = s.pre_act.a; a.pre_act_b = s.pre_act.b;
-    return a;
-}
-
-GroupedArgs DeviceModel::MakeGroupedArgs(const PlanInstance& pi, const Step& s) const {
-    GroupedArgs a;
-    static_cast<DwArgs&>(a) = MakeDwArgs(pi, s);
-    a.w16 = w_->d_weights16 && s.w_off >= 0 ? static_cast<const char*>(w_->d_weights16) + s.w_off * 2 : nullptr;
-    a.groups = s.group;
-    return a;
-}
-
-ConvtArgs DeviceModel::MakeConvtArgs(const PlanInstance& pi, const Step& s) const {
-    ConvtArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    a.w = s.w_off >= 0 ? w_->d_weights + s.w_off : nullptr;
-    a.w16 = w_->d_weights16 && s.w_off >= 0 ? static_cast<const char*>(w_->d_weights16) + s.w_off * 2 : nullptr;
-    a.bias = s.bias_off >= 0 ? w_->d_weights + s.bias_off : nullptr;
-    a.kh = s.kh; a.kw = s.kw; a.sh = s.sh; a.sw = s.sw; a.pt = s.pt; a.pl = s.pl; a.pb = s.pb; a.pr = s.pr; a.oph = s.oph; a.opw = s.opw;
-    a.relu = s.relu;
-    return a;
-}
-
-SeArgs DeviceModel::MakeSeArgs(const PlanInstance& pi, const Step& s) const {
-    const float* wb = w_->d_weights;
-    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
-    SeArgs a;
-    a.in = make_arg(pi, s.in);
-    a.out = make_arg(pi, s.out);
-    a.w1 = wp(s.w_off);
-    a.b1 = wp(s.bias_off);
-    a.w2t = wp(s.w2_off);
-    a.b2 = wp(s.bias2_off);
-    a.mid = s.se_mid;
-    a.act1 = int(s.se_act1.kind); a.act1_a = s.se_act1.a; a.act1_b = s.se_act1.b;
-    a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
-    a.chunks = s.se_chunks;
-    a.workspace = pi.workspace;
-    a.workspace_floats = pi.workspace_floats;
-    return a;
-}
-
-// The step that really runs when `s` is launched: `s` itself, or -- a specialised launcher that declines this operand set (alignment,
-// LDS budget, a missing weight mirror ...) -- the hand-over step, built in `scratch`.  LaunchStep launches what this returns and
-// Profile() labels it, so a declined step is reported under the kernel that ran.
-const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Step& scratch) const {
-    if (s.kind == StepKind::LayerNorm && s.tile != 0 && !LayerNormEligible(MakeLnArgs(pi, s, w_->d_weights), s.tile)) {      // the generic kernel takes every layer norm
-        scratch = s;
-        scratch.tile = 0;
-        return scratch;
-    }
-    if (s.kind == StepKind::GroupNorm && s.tile != 0 && !GroupNormEligible(MakeGnArgs(pi, s, w_->d_weights), s.tile)) {      // the generic kernel takes every group norm
-        scratch = s;
-        scratch.tile = 0;
-        return scratch;
-    }
-    if (s.kind == StepKind::Embed && s.tile != 0 && !EmbedEligible(MakeEmbedArgs(pi, s, w_->d_weights), s.tile)) {      // the generic kernel takes every embed
-        scratch = s;
-        scratch.tile = 0;
-        return scratch;
-    }
-    if (s.kind == StepKind::Attention && s.tile != 0 && !AttentionEligible(MakeAttnArgs(pi, s), s.tile)) {      // the generic kernel takes every attention
-        scratch = s;
-        scratch.tile = 0;
-        return scratch;
-    }
-    if (s.kind == StepKind::WindowAttention && s.tile != 0 && !WindowAttentionEligible(MakeWinAttnArgs(pi, s, w_->d_weights), s.tile)) {      // likewise
-        scratch = s;
-        scratch.tile = 0;
-        return scratch;
-    }
-    if (s.kind != StepKind::Conv) return s;
-    auto with_tile = [&](int tile) -> const Step& {
-        if (tile == s.tile) return s;
-        scratch = s;
-        scratch.tile = tile;
-        return scratch;
-    };
-    switch (s.algo) {
-        case ConvAlgo::Depthwise:       // the generic kernel takes every depthwise conv
-            return with_tile(ConvDwEligible(MakeDwArgs(pi, s), s.tile) ? s.tile : 0);
-        case ConvAlgo::Grouped:         // the generic kernel takes every grouped conv
-            return with_tile(ConvGroupedEligible(MakeGroupedArgs(pi, s), s.tile) ? s.tile : 0);
-        case ConvAlgo::Transposed:      // the generic kernel takes every transposed conv
-            return with_tile(ConvTransposedEligible(MakeConvtArgs(pi, s), s.tile) ? s.tile : 0);
-        case ConvAlgo::StemPool:        // tile 0: the two plain steps
-            return with_tile(s.tile != 0 && ConvStemPoolEligible(MakeConvArgs(pi, s)) ? s.tile : 0);
-        case ConvAlgo::DenseBlock: {    // tile 0: the 2n plain steps
-            DenseBlockArgs b;
-            return with_tile(s.tile != 0 && MakeBlockArgs(pi, s, &b) && DenseBlockEligible(b) ? s.tile : 0);
-        }
-        case ConvAlgo::DenseFused: {    // tile 0: the two plain steps
-            if (s.tile == 0) return s;
-            const Step& s3 = s.parts.at(0);
-            FusedArgs f;
-            f.in3 = make_arg(pi, s3.in);
-            f.out3 = make_arg(pi, s3.out);
-            f.wfrag3 = w_->d_weights_frag && s3.w_off >= 0 ? w_->d_weights_frag + s3.w_off : nullptr;
-            f.bias3 = s3.bias_off >= 0 ? w_->d_weights + s3.bias_off : nullptr;
-            f.relu3 = s3.relu;
-            return with_tile(ConvDenseFusedEligible(MakeConvArgs(pi, s), f, s.tile) ? s.tile : 0);
-        }
-        case ConvAlgo::IgemmF8: {       // a weights-stationary launcher that declines these operands hands the step to the tiled fp8 kernel
-            const int t8 = s.tile;
-            if (t8 < kWs8Code) return s;
-            const ConvArgs a = MakeConvArgs(pi, s);
-            const bool ok = t8 >= kWs38Code ? ConvWs38Eligible(a, t8 - kWs38Code) : ConvWs8Eligible(a, t8 - kWs8Code);
-            return with_tile(ok ? t8 : (s.base_tile < kNumConvF8Tiles ? s.base_tile : 3));
-        }
-        case ConvAlgo::Ws1x1: case ConvAlgo::Ws3x3: case ConvAlgo::Direct: case ConvAlgo::Raster3x3: case ConvAlgo::Wino3x3: case ConvAlgo::X6:
-        case ConvAlgo::Stem: {          // the tiled kernel takes every dense conv
-            const ConvArgs a = MakeConvArgs(pi, s);
-            ConvArgs plain = a;                        // what a kernel without a residual epilogue is asked to do (see split_res in LaunchStep)
-            plain.res = TensorArg();
-            bool ok = true;
-            switch (s.algo) {
-                case ConvAlgo::Ws1x1: ok = s.in.f16 ? ConvWsEligible(a, s.tile) : ConvWs32Eligible(a, s.tile); break;
-                case ConvAlgo::Ws3x3: ok = ConvWs3Eligible(plain, s.tile); break;
-                case ConvAlgo::Direct: ok = ConvDirectEligible(plain, s.tile); break;
-                case ConvAlgo::Raster3x3: ok = ConvRasterEligible(plain, s.tile); break;
-                case ConvAlgo::Wino3x3: ok = ConvWinoEligible(plain, s.tile); break;
-                case ConvAlgo::X6: ok = ConvX6Eligible(plain, s.tile); break;
-                default: ok = ConvStemEligible(a); break;
-            }
-            if (ok) return s;
-            scratch = s;
-            scratch.algo = s.algo == ConvAlgo::Stem ? ConvAlgo::IgemmScalar : ConvAlgo::IgemmVec;
-            scratch.tile = s.base_tile;
-            scratch.splitk = 1;
-            return scratch;
-        }
-        default: return s;
-    }
-}
-
-void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream_t stream_) {
-    Step handed;
-    const Step& s = LaunchedStep(pi, s_in, handed);
-    const float* wb = w_->d_weights;
-    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
-    switch (s.kind) {
-        case StepKind::Conv: {
-            if (s.algo == ConvAlgo::DualF8) {
-                if (s.in.f8) {          // fp8 plan: the two GEMMs of one launch; e4m3 tensors never reach another kernel
-                    if (!w_->f8_ready) throw std::runtime_error("fp8 precision: scales are not calibrated yet");
-                    const ConvArgs a = MakeConvArgs(pi, s);
-                    const int t = s.tile >= kWs8Code ? s.tile - kWs8Code : 1;
-                    if (a.in2.p == nullptr || !ConvWs8Eligible(a, t)) throw std::runtime_error("fp8 precision: the projection-shortcut step " + s.name + " cannot run on the dual 1x1 kernel");
-                    check(LaunchConvWs1x1F8(a, t, stream_), "conv1x1_ws_f8(dual)");
-                } else {                // the fp16 plan of the fp8 calibration: the same step list, the two plain convs
-                    for (const Step& q : s.parts) LaunchStep(pi, q, stream_);
-                }
-                break;
-            }
-            if (s.algo == ConvAlgo::Depthwise) {
-                check(LaunchConvDw(MakeDwArgs(pi, s), s.tile, stream_), "conv_dw");
-                break;
-            }
-            if (s.algo == ConvAlgo::Grouped) {
-                check(LaunchConvGrouped(MakeGroupedArgs(pi, s), s.tile, stream_), "conv_grouped");
-                break;
-            }
-            if (s.algo == ConvAlgo::Transposed) {
-                if (s.has_in2 || s.pre_scale_off >= 0) throw std::runtime_error("internal error: transposed conv " + s.name + " with a prologue or a residual");
-                check(LaunchConvTransposed(MakeConvtArgs(pi, s), s.tile, stream_), "conv_transposed");
-                break;
-            }
-            if (s.algo == ConvAlgo::StemPool) {
-                // the stem conv and the max pool behind it in one launch (out = the pooled tensor); tile 0: the two plain steps
-                if (s.tile != 0) check(LaunchConvStemPool(MakeConvArgs(pi, s), stream_), "conv_stem_pool");
-                else for (const Step& q : s.parts) LaunchStep(pi, q, stream_);
-                break;
-            }
-            if (s.algo == ConvAlgo::DenseBlock) {
-                DenseBlockArgs b;
-                if (s.tile != 0 && MakeBlockArgs(pi, s, &b)) check(LaunchDenseBlockF16(b, stream_), "dense_block_f16");
-                else for (const Step& q : s.parts) LaunchStep(pi, q, stream_);
-                break;
-            }
-            if (s.algo == ConvAlgo::DenseFused) {
-                // one launch for the 3x3 of dense layer L and the 1x1 of layer L+1; tile 0: the two plain steps
-                const Step& s3 = s.parts.at(0);
-                ConvArgs a1 = MakeConvArgs(pi, s);
-                FusedArgs f;
-                f.in3 = make_arg(pi, s3.in);
-                f.out3 = make_arg(pi, s3.out);
-                f.wfrag3 = w_->d_weights_frag && s3.w_off >= 0 ? w_->d_weights_frag + s3.w_off : nullptr;
-                f.bias3 = wp(s3.bias_off);
-                f.relu3 = s3.relu;
-                if (s.tile != 0) check(LaunchConvDenseFused(a1, f, s.tile, stream_), "conv_dense_fused");
-                else {
-                    LaunchStep(pi, s.parts[0], stream_);
-                    LaunchStep(pi, s.parts[1], stream_);
-                }
-                break;
-            }
-            ConvArgs a = MakeConvArgs(pi, s);
-            if (s.algo == ConvAlgo::IgemmF8) {
-                // e4m3 tensors: only the fp8 kernel may touch them; a declined launch is an error, never a hand-over to a kernel that
-                // would read the bytes as floats
-                if (!w_->f8_ready) throw std::runtime_error("fp8 precision: scales are not calibrated yet");
-                const int t8 = s.tile;
-                if (t8 >= kWs38Code) check(LaunchConvWs3x3F8(a, t8 - kWs38Code, stream_), "conv3x3_ws_f8");        // weights-stationary 3x3 (kernels_ws8.hip)
-                else if (t8 >= kWs8Code) check(LaunchConvWs1x1F8(a, t8 - kWs8Code, stream_), "conv1x1_ws_f8");   // weights-stationary 1x1
-                else check(LaunchConvIgemmF8(a, t8, stream_), "conv_igemm_f8");
-                break;
-            }
-            if (a.in.f8 || a.res.f8 || (a.out.f8 && s_in.algo != ConvAlgo::Stem)) throw std::runtime_error("internal error: fp8 tensor reached a non-fp8 conv kernel");
-            if ((s.dh != 1 || s.dw != 1) && !DilationOk(s.algo)) throw std::runtime_error("internal error: dilated conv " + s.name + " reached a kernel without dilation");
-            // A fused residual Add lives in the weights-stationary 1x1 epilogues; any other kernel runs the conv without its ReLU
-            // and adds the shortcut in place afterwards.
-            const TensorArg res = a.res;
-            const int relu = a.relu;
-            const bool split_res = res.p != nullptr && s.algo != ConvAlgo::Ws1x1;
-            if (split_res) { a.res = TensorArg(); a.relu = 0; }
-            if (s.algo == ConvAlgo::Naive) check(LaunchConvNaive(a, stream_), "conv_naive");
-            else if (s.algo == ConvAlgo::Raster3x3) check(LaunchConvRaster3x3(a, s.tile, s.splitk, stream_), "conv3x3_raster");
-            else if (s.algo == ConvAlgo::Ws1x1 && s.in.f16) check(LaunchConvWs1x1F16(a, s.tile, stream_), "conv1x1_ws_f16");
-            else if (s.algo == ConvAlgo::Ws1x1) check(LaunchConvWs1x1F32(a, s.tile, stream_), "conv1x1_ws_f32");
-            else if (s.algo == ConvAlgo::Ws3x3) check(LaunchConvWs3x3F16(a, s.tile, stream_), "conv3x3_ws_f16");
-            else if (s.algo == ConvAlgo::Stem) check(LaunchConvStem(a, stream_), "conv_stem");
-            else if (s.algo == ConvAlgo::Wino3x3) check(LaunchConvWino3x3(a, s.tile, stream_), "conv3x3_wino");
-            else if (s.algo == ConvAlgo::X6) check(LaunchConvX6(a, s.tile, stream_), "conv1x1_x6");
-            else if (s.algo == ConvAlgo::Direct) check(LaunchConvDirect(a, s.tile, stream_), "conv_direct");
-            else if (s.in.f16) check(LaunchConvIgemmF16(a, s.tile, s.splitk, stream_), "conv_igemm_f16");
-            else check(LaunchConvIgemm(a, s.tile, s.algo == ConvAlgo::IgemmVec ? 1 : 0, s.splitk, stream_), "conv_igemm");
-            if (split_res) {
-                EltArgs e;
-                e.a = a.out; e.b = res; e.out = a.out; e.relu = relu;
-                check(LaunchEltwise(e, stream_), "eltwise(residual)");
-            }
-            break;
-        }
-        case StepKind::Pool: {
-            PoolArgs a;
-            a.in = make_arg(pi, s.in);
-            a.out = make_arg(pi, s.out);
-            a.kh = s.kh; a.kw = s.kw; a.sh = s.sh; a.sw = s.sw; a.pt = s.pt; a.pl = s.pl; a.pb = s.pb; a.pr = s.pr;
-            a.is_max = s.pool_max; a.count_include_pad = s.count_include_pad;
-            a.pre_scale = wp(s.pre_scale_off); a.pre_shift = wp(s.pre_shift_off); a.pre_relu = s.pre_relu;
-            if (a.in.f8 || a.out.f8) {
-                const DeviceWeights& W = *w_;
-                auto scale_of = [&](int step) { return step >= 0 && size_t(step) < W.act_scale.size() && W.act_scale[size_t(step)] > 0.f ? W.act_scale[size_t(step)] : 1.f; };
-                a.in_scale = scale_of(s.in_src);
-                a.out_qscale = 1.0f / scale_of(s.idx);
-                check(LaunchPoolF8(a, stream_), "pool_f8");
-                break;
-            }
-            check(LaunchPool(a, stream_), "pool");
-            break;
-        }
-        case StepKind::GlobalAvgPool:
-            if (s.in.f8) {
-                const DeviceWeights& W = *w_;
-                const float sc = s.in_src >= 0 && size_t(s.in_src) < W.act_scale.size() && W.act_scale[size_t(s.in_src)] > 0.f ? W.act_scale[size_t(s.in_src)] : 1.f;
-                check(LaunchGlobalAvgPoolF8(make_arg(pi, s.in), make_arg(pi, s.out), sc, stream_), "global_avg_pool_f8");
-                break;
-            }
-            check(LaunchGlobalAvgPool(make_arg(pi, s.in), make_arg(pi, s.out), wp(s.pre_scale_off), wp(s.pre_shift_off),
-                                      s.pre_relu, stream_, int(s.pre_act.kind), s.pre_act.a, s.pre_act.b), "global_avg_pool");
-            break;
-        case StepKind::Eltwise: {
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the eltwise kernel");
-            EltArgs a;
-            a.a = make_arg(pi, s.in);
-            if (s.has_in2) a.b = make_arg(pi, s.in2);
-            a.out = make_arg(pi, s.out);
-            a.scale = wp(s.pre_scale_off);
-            a.shift = wp(s.pre_shift_off);
-            a.relu = s.relu;
-            a.lo = s.lo;
-            a.hi = s.hi;
-            a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
-            a.b_mul = s.mul;
-            a.b_bcast = s.has_in2 && s.in2.h * s.in2.w == 1 && s.out.h * s.out.w > 1;
-            check(LaunchEltwise(a, stream_), "eltwise");
-            break;
-        }
-        case StepKind::SqueezeExcite: {
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the squeeze-excite kernels");
-            const SeArgs a = MakeSeArgs(pi, s);
-            if (!SqueezeExciteEligible(a)) throw std::runtime_error("squeeze-excite step " + s.name + ": the kernels decline its operands");
-            check(LaunchSqueezeExcite(a, stream_), "squeeze_excite");
-            break;
-        }
-        case StepKind::Copy:
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the copy kernel");
-            check(LaunchCopy(make_arg(pi, s.in), make_arg(pi, s.out), stream_), "copy");
-            break;
-        case StepKind::Resize: {
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the resize kernels");
-            const ResizeArgs a = MakeResizeArgs(pi, s);
-            check(LaunchResize(a, ResizePath(a), stream_), "resize");
-            break;
-        }
-        case StepKind::LayerNorm:
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the layer-norm kernels");
-            check(LaunchLayerNorm(MakeLnArgs(pi, s, wb), s.tile, stream_), "layer_norm");
-            break;
-        case StepKind::GroupNorm:
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the group-norm kernels");
-            check(LaunchGroupNorm(MakeGnArgs(pi, s, wb), s.tile, stream_), "group_norm");
-            break;
-        case StepKind::Embed:
-            if (s.out.f8 || !s.in.i64) throw std::runtime_error("internal error: the embed kernels take int64 ids and write floats or halfs");
-            check(LaunchEmbed(MakeEmbedArgs(pi, s, wb), s.tile, stream_), "embed");
-            break;
-        case StepKind::TokenAssemble: {
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the token kernels");
-            TokenAssembleArgs a;
-            a.in = make_arg(pi, s.in);
-            a.out = make_arg(pi, s.out);
-            a.cls = wp(s.w_off);
-            a.pos = wp(s.bias_off);
-            check(LaunchTokenAssemble(a, stream_), "token_assemble");
-            break;
-        }
-        case StepKind::Attention:
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the attention kernels");
-            check(LaunchAttention(MakeAttnArgs(pi, s), s.tile, stream_), "attention");
-            break;
-        case StepKind::WindowAttention:
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the window-attention kernels");
-            check(LaunchWindowAttention(MakeWinAttnArgs(pi, s, wb), s.tile, stream_), "window_attention");
-            break;
-        case StepKind::PatchMerge: {
-            if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the patch-merge kernel");
-            PatchMergeArgs a;
-            a.in = make_arg(pi, s.in);
-            a.out = make_arg(pi, s.out);
-            check(LaunchPatchMerge(a, stream_), "patch_merge");
-            break;
-        }
-    }
-}
-
-static std::string kernel_label(const Step& s) {
-    switch (s.kind) {
-        case StepKind::Conv:
-            if (s.algo == ConvAlgo::Naive) return "conv_naive_kernel";
-            if (s.algo == ConvAlgo::Depthwise) {
-                static const int px[kNumConvDwTiles] = {0, 1, 2, 4};
-                const bool act = s.act.kind != ActKind::None || s.pre_act.kind != ActKind::None;
-                return s.tile == 0 ? std::string("conv_dw_generic_kernel")
-                                   : std::string("conv_dw_kernel<") + (s.out.f16 ? "f16,k" : "f32,k") + std::to_string(s.kh) + ",s" + std::to_string(s.sh) + ",px" +
-                                         std::to_string(DwLanePixels(px[s.tile], s.out.f16, s.kh, s.sh, act)) + (act ? ",act>" : ">");
-            }
-            if (s.algo == ConvAlgo::Grouped) {
-                const int cfg = GroupedCfgFor(s.in.c, s.out.c, s.group);
-                if (s.tile == 0 || cfg < 0) return "conv_grouped_generic_kernel";
-                const GroupedCfg& c = kGroupedCfgs[cfg];
-                return std::string("conv_grouped_kernel<") + (s.out.f16 ? "f16,c" : "f32,c") + std::to_string(c.cpg) + ",o" + std::to_string(c.opb) + "x" +
-                       std::to_string(c.gpb) + ",px" + std::to_string(kGroupedPx[s.tile]) + ">";
-            }
-            if (s.algo == ConvAlgo::Transposed)
-                return s.tile == 0 ? std::string("convt_generic_kernel")
-                                   : std::string("convt_phase_kernel<") + (s.out.f16 ? "f16,px" : "f32,px") + std::to_string(32 * kConvtPixelBlocks[s.tile]) + ">";
-            if (s.algo == ConvAlgo::DenseBlock) return s.tile != 0 ? "dense_block_f16_kernel<" + std::to_string(s.parts.size() / 2) + " layers>" : "dense_block_parts<" + std::to_string(s.parts.size()) + " launches>";
-            if (s.algo == ConvAlgo::DenseFused && s.tile == 0) return "dense_fused_parts<2 launches>";
-            if (s.algo == ConvAlgo::DenseFused) return (s.tile == 4 || s.tile == 5 ? "conv_dense_fused_ws_kernel<t" : "conv_dense_fused_kernel<t") + std::to_string(s.tile) + ">";
-            if (s.algo == ConvAlgo::DualF8) return s.in.f8 ? "conv1x1_ws_f8_kernel<dual,t" + std::to_string(s.tile >= kWs8Code ? s.tile - kWs8Code : 1) + ">" : "dual_f8_parts<2 launches>";
-            if (s.algo == ConvAlgo::IgemmF8 && s.tile >= kWs38Code) return "conv3x3_ws_f8_kernel<t" + std::to_string(s.tile - kWs38Code) + ">";
-            if (s.algo == ConvAlgo::IgemmF8 && s.tile >= kWs8Code) return "conv1x1_ws_f8_kernel<t" + std::to_string(s.tile - kWs8Code) + ">";
-            if (s.algo == ConvAlgo::IgemmF8)
-                return "conv_igemm_f8_kernel<" + std::to_string(kIgemmTiles[s.tile].bm) + "x" + std::to_string(kIgemmTiles[s.tile].bn) + ">";
-            if (s.algo == ConvAlgo::Direct) {       // one launcher family, three kernels (kernels_direct.hip): report the one that runs
-                const char* k = s.tile >= 10 ? "conv1x1_as_kernel<f32,t" : s.tile >= kNumDirectBaseTiles ? "conv_win_kernel<f32,t"
-                                             : s.in.f16 ? "conv_direct_kernel<f16,t" : "conv_direct_kernel<f32,t";
-                return std::string(k) + std::to_string(s.tile) + ">";
-            }
-            if (s.algo == ConvAlgo::StemPool) return s.tile != 0 ? (s.out.f8 ? "conv_stem_kernel<f16,pool,e4m3 out>" : (s.out.f16 ? "conv_stem_kernel<f16,pool>" : "conv_stem_kernel<f32,pool>")) : "stem + pool (2 launches)";
-            if (s.algo == ConvAlgo::Stem) return s.out.f8 ? "conv_stem_kernel<f16,e4m3 out>" : (s.out.f16 ? "conv_stem_kernel<f16>" : "conv_stem_kernel<f32>");
-            if (s.algo == ConvAlgo::Ws1x1) return std::string(s.in.f16 ? "conv1x1_ws_f16_kernel<t" : "conv1x1_ws_f32_kernel<t") + std::to_string(s.tile) + ">";
-            if (s.algo == ConvAlgo::Ws3x3) return "conv3x3_ws_f16_kernel<t" + std::to_string(s.tile) + ">";
-            if (s.algo == ConvAlgo::Wino3x3) return std::string(s.tile >= 8 ? "conv3x3_wino_x6_kernel<t" : "conv3x3_wino_kernel<t") + std::to_string(s.tile) + ">";
-            if (s.algo == ConvAlgo::X6) return "conv1x1_x6_kernel<t" + std::to_string(s.tile) + ">";
-            if (s.algo == ConvAlgo::Raster3x3)
-                return "conv3x3_raster_kernel<t" + std::to_string(s.tile) + (s.splitk > 1 ? ",splitk" + std::to_string(s.splitk) : std::string()) + ">";
-            return std::string(s.in.f16 ? "conv_igemm_f16_kernel<" : "conv_igemm_kernel<") + std::to_string(kIgemmTiles[s.tile].bm) + "x" +
-                   std::to_string(kIgemmTiles[s.tile].bn) + (kIgemmTiles[s.tile].kg > 1 ? "x" + std::to_string(kIgemmTiles[s.tile].kg) + "kg" : std::string()) +
-                   (kIgemmTiles[s.tile].deep ? ",deep" : "") +
-                   (s.algo == ConvAlgo::IgemmVec ? ",vec" : ",scalar") +
-                   (s.splitk > 1 ? ",splitk" + std::to_string(s.splitk) : std::string()) + ">";
-        case StepKind::Pool: return s.in.f8 ? "pool_f8_kernel" : "pool_kernel";
-        case StepKind::GlobalAvgPool: return s.in.f8 ? "gap_f8_kernel" : "gap_kernel";
-        case StepKind::Eltwise: return "eltwise_kernel";
-        case StepKind::Copy: return "copy_kernel";
-        case StepKind::Resize: {
-            static const char* const names[3] = {"resize_generic_kernel", "resize_vec_kernel<", "resize_nchw_kernel<"};
-            ResizeArgs a;
-            a.in = view_strides(s.in);
-            a.out = view_strides(s.out);
-            if (s.in.c_off % (s.in.f16 ? 8 : 4)) a.in.p = reinterpret_cast<float*>(uintptr_t(4));    // (a misaligned view: the launcher sees its address)
-            if (s.out.c_off % (s.out.f16 ? 8 : 4)) a.out.p = reinterpret_cast<float*>(uintptr_t(4));
-            const int path = ResizePath(a);
-            return path == 0 ? std::string(names[0]) : std::string(names[path]) + (s.in.f16 ? "f16>" : "f32>");
-        }
-        case StepKind::LayerNorm:
-            return s.tile == 0 ? std::string("layernorm_generic_kernel")
-                               : std::string("layernorm_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
-        case StepKind::GroupNorm: {
-            static const char* const acts[] = {"none", "sigmoid", "", "silu", "", "relu"};
-            const std::string t = s.out.f16 ? "f16" : "f32";
-            return s.tile == 0 ? std::string("groupnorm_generic_kernel")
-                               : "groupnorm_stats_kernel<" + t + "> + groupnorm_apply_kernel<" + t + "," + acts[int(s.act.kind)] + ">";
-        }
-        case StepKind::Embed:
-            return s.tile == 0 ? std::string("embed_ln_generic_kernel")
-                               : std::string("embed_ln_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
-        case StepKind::TokenAssemble: return std::string("token_assemble_kernel<") + (s.out.f16 ? "f16>" : "f32>");
-        case StepKind::Attention:
-            if (s.tile == 2) return std::string("attention_stream_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
-            return s.tile == 0 ? std::string(s.key_mask ? "attention_generic_kernel<mask>" : "attention_generic_kernel")
-                               : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.key_mask ? ",mask>" : ">");
-        case StepKind::WindowAttention:
-            return s.tile == 0 ? std::string("window_attention_generic_kernel")
-                               : std::string("window_attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
-        case StepKind::PatchMerge: {
-            const bool vec = !s.in.nchw && !s.out.nchw && PatchMergeVec(s.in.f16, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off);
-            return std::string("patch_merge_kernel<") + (vec ? (s.out.f16 ? "f16,8>" : "f32,4>") : (s.out.f16 ? "f16,1>" : "f32,1>"));
-        }
-        case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
-    }
-    return "?";
-}
-
-
-// ---- transitions in one launch (kernels_trans.hip) ------------------------------------------------------------------------------------
-namespace {
-
-bool same_view(const View& a, const View& b) {
-    return a.buf == b.buf && a.n == b.n && a.c == b.c && a.h == b.h && a.w == b.w && a.c_off == b.c_off && a.pitch == b.pitch && a.nchw == b.nchw && a.f16 == b.f16 &&
-           a.f8 == b.f8;
-}
-bool views_overlap(const View& a, const View& b) {
-    return a.buf == b.buf && (a.nchw || b.nchw || (a.c_off < b.c_off + b.c && b.c_off < a.c_off + a.c));
-}
-// a write of `w` ends the life of the tensor in view `v`: another tensor laid out in the same (recycled) buffer, or the same pixel rows with v's channels rewritten
-bool view_kills(const View& w, const View& v) {
-    if (w.buf != v.buf) return false;
-    if (w.nchw || v.nchw || w.pitch != v.pitch || w.n != v.n || w.h != v.h || w.w != v.w) return true;
-    return w.c_off <= v.c_off && w.c_off + w.c >= v.c_off + v.c;
-}
-void step_views(const Step& s, std::vector<const View*>& reads, std::vector<const View*>& writes) {
-    reads.push_back(&s.in);
-    if (s.has_in2) reads.push_back(&s.in2);
-    writes.push_back(&s.out);
-    for (const Step& q : s.parts) step_views(q, reads, writes);
-}
-// a dense 1x1 / stride-1 conv step with nothing but bias and ReLU behind it
-const char* plain_1x1(const Step& c) {
-    if (c.kind != StepKind::Conv) return "is not a conv";
-    if (!c.parts.empty() || IsGroupConv(c.algo) || c.group != 1 || c.algo == ConvAlgo::Stem) return "is a fused or grouped conv step";
-    if (c.kh != 1 || c.kw != 1 || c.sh != 1 || c.sw != 1 || c.pt || c.pl || c.pb || c.pr || c.dh != 1 || c.dw != 1) return "is not a 1x1 / stride-1 conv";
-    if (c.has_in2) return "has a residual";
-    if (c.act.kind != ActKind::None || c.lo != -__builtin_huge_valf() || c.hi != __builtin_huge_valf()) return "has an activation other than ReLU";
-    if (c.in.nchw || c.out.nchw || c.in.f16 || c.out.f16 || c.in.f8 || c.out.f8) return "is not fp32 NHWC";
-    return nullptr;
-}
-
-}  // namespace
-
-std::vector<PairedLaunch> FindPairedLaunches(const Plan& plan) {
-    std::vector<PairedLaunch> found;
-    if (plan.precision != Precision::F32) return found;
-    const std::vector<Step>& st = plan.steps;
-    for (size_t i = 0; i + 1 < st.size(); ++i) {
-        const Step& pl = st[i];
-        const Step& cv = st[i + 1];
-        if (pl.kind != StepKind::Pool || cv.kind != StepKind::Conv || cv.in.buf != pl.out.buf) continue;
-        PairedLaunch c;
-        c.steps = {int(i), int(i + 1)};
-        auto miss = [&](const std::string& why) { c.reason = why; found.push_back(c); };
-        if (pl.pool_max) { miss("the pool is a max pool"); continue; }
-        if (pl.kh != 2 || pl.kw != 2 || pl.sh != 2 || pl.sw != 2) {
-            miss("the pool is " + std::to_string(pl.kh) + "x" + std::to_string(pl.kw) + " / stride " + std::to_string(pl.sh) + ", not 2x2 / stride 2");
-            continue;
-        }
-        if (pl.pt || pl.pl || pl.pb || pl.pr) { miss("the pool has padding"); continue; }
-        if (pl.in.nchw || pl.out.nchw || pl.in.f16 || pl.out.f16 || pl.in.f8 || pl.out.f8) { miss("the pool is not fp32 NHWC"); continue; }
-        if (pl.in.h != 2 * pl.out.h || pl.in.w != 2 * pl.out.w) { miss("the pool's windows do not tile its input"); continue; }
-        if (pl.act.kind != ActKind::None || pl.pre_act.kind != ActKind::None) { miss("the pool has an activation other than ReLU"); continue; }
-        if (const char* why = plain_1x1(cv)) { miss(std::string("the conv ") + why); continue; }
-        if (cv.pre_scale_off >= 0) { miss("the conv has a prologue of its own"); continue; }
-        if (!same_view(cv.in, pl.out)) { miss("the conv reads another view than the pool writes"); continue; }
-        // nothing else may read the pooled tensor: a later step before the view is written again, or the caller (a graph output)
-        bool other = false, dead = false;
-        for (size_t j = i + 2; j < st.size() && !other && !dead; ++j) {
-            std::vector<const View*> reads, writes;
-            step_views(st[j], reads, writes);
-            for (const View* r : reads) other = other || views_overlap(*r, pl.out);
-            for (const View* w : writes) dead = dead || view_kills(*w, pl.out);
-        }
-        if (other) { miss("a later step also reads the pooled tensor"); continue; }
-        if (!dead) {
-            bool is_out = false;
-            for (const IoDesc& o : plan.outputs) is_out = is_out || views_overlap(o.view, pl.out);
-            if (is_out) { miss("the pooled tensor is a graph output"); continue; }
-        }
-        // one launch reads the pool's input while other workgroups already store the conv's output: the two may not share a (recycled) buffer
-        if (cv.out.buf == pl.in.buf) { miss("the conv's output shares the pool input's buffer"); continue; }
-        for (int t = 0; t < kNumConvPooledTiles; ++t)
-            if (ConvPooledShapeOk(t, false, cv.in.c, cv.out.c, 0)) c.tiles.push_back(t);
-        if (c.tiles.empty()) { miss("no tile takes " + std::to_string(cv.in.c) + " -> " + std::to_string(cv.out.c) + " channels"); continue; }
-        c.pairable = true;
-        // chain: the step behind the conv is the next block's entry 1x1 on exactly the tensor the conv writes
-        if (i + 2 < st.size()) {
-            const Step& en = st[i + 2];
-            std::string why;
-            if (const char* w = plain_1x1(en)) why = std::string("the entry step ") + w;
-            else if (en.pre_scale_off < 0) why = "the entry conv has no prologue";
-            else if (!same_view(en.in, cv.out)) why = "the entry conv reads another view than the conv writes";
-            else if (en.out.c != 128) why = "the entry conv has " + std::to_string(en.out.c) + " output channels, not 128";
-            else if (en.out.buf == pl.in.buf || en.out.buf == cv.out.buf) why = "the entry conv's output shares a buffer the launch still reads";
-            else {
-                for (int t = 0; t < kNumConvPooledTiles; ++t)
-                    if (ConvPooledShapeOk(t, true, cv.in.c, cv.out.c, en.out.c)) c.chain_tiles.push_back(t);
-                if (c.chain_tiles.empty()) why = "no chain tile holds " + std::to_string(cv.out.c) + " channels";
-            }
-            if (why.empty()) {
-                c.chainable = true;
-                c.steps.push_back(int(i + 2));
-            } else {
-                c.reason = "chain: " + why;
-            }
-        } else {
-            c.reason = "chain: no step behind the conv";
-        }
-        found.push_back(c);
-    }
-    return found;
-}
-
-std::string PairedLaunchesToJson(const std::vector<PairedLaunch>& v) {
-    std::ostringstream o;
-    auto list = [&](const std::vector<int>& l) {
-        o << "[";
-        for (size_t k = 0; k < l.size(); ++k) o << (k ? "," : "") << l[k];
-        o << "]";
-    };
-    o << "[";
-    for (size_t i = 0; i < v.size(); ++i) {
-        const PairedLaunch& c = v[i];
-        o << (i ? "," : "") << "{\"steps\":";
-        list(c.steps);
-        o << ",\"kind\":" << (!c.pairable ? "null" : (c.chainable ? "\"pool_conv_chain\"" : "\"pool_conv\"")) << ",\"tiles\":";
-        list(c.tiles);
-        o << ",\"chain_tiles\":";
-        list(c.chain_tiles);
-        o << ",\"reason\":\"" << c.reason << "\"}";         // (reasons are this file's own text: nothing to escape)
-    }
-    o << "]";
-    return o.str();
-}
-
-bool DeviceModel::MakePooledArgs(const PlanInstance& pi, size_t i, int count, bool chain, ConvArgs* a, PooledArgs* p) const {
-    const std::vector<Step>& st = pi.plan.steps;
-    if (i + size_t(count) > st.size() || count < (chain ? 3 : 2)) return false;
-    const float* wb = w_->d_weights;
-    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
-    const Step& pl = st[i];
-    *a = MakeConvArgs(pi, st[i + 1]);
-    *p = PooledArgs();
-    p->pin = make_arg(pi, pl.in);
-    p->pool_scale = wp(pl.pre_scale_off);
-    p->pool_shift = wp(pl.pre_shift_off);
-    p->pool_relu = pl.pre_relu;
-    if (chain) {
-        const Step& en = st[i + 2];
-        p->out2 = make_arg(pi, en.out);
-        p->wfrag2 = w_->d_weights_frag && en.w_off >= 0 ? w_->d_weights_frag + en.w_off : nullptr;
-        p->bias2 = wp(en.bias_off);
-        p->scale2 = wp(en.pre_scale_off);
-        p->shift2 = wp(en.pre_shift_off);
-        p->pre_relu2 = en.pre_relu;
-        p->relu2 = en.relu;
-    }
-    return true;
-}
-
-int DeviceModel::PairedCount(const PlanInstance& pi, size_t i, size_t last, ConvArgs* a, PooledArgs* p, LaunchRole* role) const {
-    if (i >= pi.roles.size()) return 1;
-    const LaunchRole& r = pi.roles[i];
-    if (r.count <= 1 || i + size_t(r.count) > last) return 1;
-    if (!MakePooledArgs(pi, i, r.count, r.chain, a, p) || !ConvPooledEligible(*a, *p, r.tile, r.chain)) return 1;      // the launcher would decline: split launches
-    *role = r;
-    return r.count;
-}
-
-// IE_POOL_CONV=0: nothing.  1 / 2 [":tile"]: every eligible transition pairs (2: chains where it can) without timing; a forced tile that is not
-// eligible leaves the steps split.  Unset: one timed choice per signature among the split launches, pool + conv per tile (+ the entry conv on its
-// own) and the chain per tile, cached under kPoolConvTuneCode -- and nothing without a search (IE_AUTOTUNE=0, forced kernels, the request path
-// on an unseen signature).
-void DeviceModel::PairTransitions(TuneContext* ctx, PlanInstance& pi) {
-    pi.roles.clear();
-    const int mode = pool_conv_mode_;
-    if (mode == 0 || precision_ != Precision::F32 || pi.batch_off != 0) return;
-    if (mode < 0 && (!autotune_ || ctx == nullptr)) return;
-    const std::vector<Step>& st = pi.plan.steps;
-    std::vector<LaunchRole> roles(st.size());
-    bool any = false;
-    for (const PairedLaunch& c : FindPairedLaunches(pi.plan)) {
-        if (!c.pairable) continue;
-        const size_t i = size_t(c.steps[0]);
-        ConvArgs a;
-        PooledArgs p;
-        auto can = [&](int t, bool chain) {
-            return t >= 0 && t < kNumConvPooledTiles && (!chain || c.chainable) && MakePooledArgs(pi, i, chain ? 3 : 2, chain, &a, &p) && ConvPooledEligible(a, p, t, chain);
-        };
-        int tile = -1;
-        bool chain = false;
-        if (mode > 0) {
-            if (pool_conv_tile_ >= 0) {
-                if (mode == 2 && can(pool_conv_tile_, true)) { tile = pool_conv_tile_; chain = true; }
-                else if (can(pool_conv_tile_, false)) tile = pool_conv_tile_;
-            } else {
-                for (int t = 0; mode == 2 && tile < 0 && t < kNumConvPooledTiles; ++t) if (can(t, true)) { tile = t; chain = true; }
-                for (int t = 0; tile < 0 && t < kNumConvPooledTiles; ++t) if (can(t, false)) tile = t;
-            }
-        } else {
-            const Step& pl = st[i];
-            const Step& cv = st[i + 1];
-            const size_t span = c.chainable ? 3 : 2;
-            const std::vector<int64_t> key = {cv.out.n * cv.out.h * cv.out.w, cv.out.c, cv.in.c, pl.in.h, pl.in.w, pl.in.pitch, cv.out.pitch, kPoolConvTuneCode,
-                                              pl.pre_scale_off >= 0, cv.bias_off >= 0, span == 3 ? st[i + 2].out.pitch : 0};
-            std::pair<int, int> hit{-1, 0};
-            int code = -1;
-            if (ctx->lookup(key, &hit)) {
-                if (pool_conv_tune_code(hit.first)) code = hit.first - kPoolConvTuneCode;
-            } else if (ctx->allow_search) {
-                auto alone = [&](size_t from) { for (size_t j = from; j < i + span; ++j) LaunchStep(pi, st[j], stream_); };
-                float best = TimeLaunches(*ctx, [&] { alone(i); });
-                code = 0;
-                auto consider = [&](int t, bool ch) {
-                    if (!can(t, ch)) return;
-                    const ConvArgs ta = a;
-                    const PooledArgs tp = p;
-                    const float ms = TimeLaunches(*ctx, [&] {
-                        check(LaunchConvPooled(ta, tp, t, ch, stream_), "conv1x1_pooled");
-                        if (!ch) alone(i + 2);
-                    });
-                    if (ctx->log) std::fprintf(stderr, "[ie-tune] transition at step %zu: pooled tile %d%s %.4f ms (split %.4f ms)\n", i, t, ch ? " chain" : "", ms, best);
-                    if (ms < best) { best = ms; code = 1 + (ch ? kNumConvPooledTiles : 0) + t; }
-                };
-                for (int t = 0; t < kNumConvPooledTiles; ++t) consider(t, false);
-                for (int t = 0; t < kNumConvPooledTiles; ++t) consider(t, true);
-                ctx->store(key, kPoolConvTuneCode + code, 1);
-            }
-            if (code >= 1) {
-                const bool ch = code > kNumConvPooledTiles;
-                const int t = code - 1 - (ch ? kNumConvPooledTiles : 0);
-                if (can(t, ch)) { tile = t; chain = ch; }
-            }
-        }
-        if (tile < 0) continue;
-        roles[i].count = chain ? 3 : 2;
-        roles[i].tile = tile;
-        roles[i].chain = chain;
-        roles[i + 1].count = 0;
-        if (chain) roles[i + 2].count = 0;
-        any = true;
-    }
-    if (any) pi.roles = std::move(roles);
 }
 
 void DeviceModel::RunSteps(PlanInstance& pi, size_t first, size_t last, std::vector<hipEvent_t>* events) {

@@ -48,6 +48,9 @@ struct DeviceWeights {
     struct F8Conv { int step; int64_t w_off; int cout, k; int in_src; int64_t aux_off; };
     std::vector<F8Conv> f8_convs;
     std::vector<float> act_scale;
+    float scale_of(int step) const {     // the calibrated activation scale of the tensor step `step` writes; 1 for no step and before calibration
+        return step >= 0 && size_t(step) < act_scale.size() && act_scale[size_t(step)] > 0.f ? act_scale[size_t(step)] : 1.f;
+    }
     bool f8_ready = false;
     std::atomic<uint64_t> f8_gen{0};   // bumped whenever act_scale / escale change: graphs captured under an older value are stale (scales are by-value kernel arguments)
     // fp32 mode: Winograd-transformed weights U (16 x Cout x Cin floats per eligible 3x3 conv, fragment-major), own offsets
@@ -92,6 +95,10 @@ struct LaunchRole {
     int tile = 0;
     bool chain = false;
 };
+
+// What DeviceModel::TiledFamily tells its caller about a family beside its functions: the label its launch errors carry, and the noun of "fp8 tensor
+// reached the <noun> kernels" (nullptr: the family has no such guard)
+struct TiledNames { const char* label; const char* fp8_noun; };
 
 struct PlanInstance {
     Plan plan;
@@ -195,8 +202,10 @@ private:
     // Exhaustive (tile, split-K) search per distinct conv shape, timed with HIP events on the model's stream; the
     // MI355X counterpart of the reference's cudnn_conv_algo_search = Exhaustive (model.cpp:886).  Only steps [0, nsteps).
     void Autotune(PlanInstance& pi, size_t nsteps, bool allow_search);
-    struct TuneContext;                  // one top-level Autotune call: timing events, L2 scrub buffer, cache access (executor.cpp)
+    struct TuneContext;                  // one top-level Autotune call: timing events, L2 scrub buffer, cache access (tune.cpp)
     void TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s);
+    template <class Can>
+    void TuneFusedChoice(TuneContext& ctx, const PlanInstance& pi, Step& s, const std::vector<int64_t>& key, int last_tile, bool search, float margin, bool or_equal, Can&& can);
     float TimeTrial(TuneContext& ctx, const PlanInstance& pi, const Step& trial);
     float TimeLaunches(TuneContext& ctx, const std::function<void()>& launch);
     // Pool + conv (+ entry conv) pairing of a transition's steps (IE_POOL_CONV; searched like the other fused steps when unset).  ctx == nullptr: no timing.
@@ -205,11 +214,18 @@ private:
     int PairedCount(const PlanInstance& pi, size_t i, size_t last, ConvArgs* a, PooledArgs* p, LaunchRole* role) const;
     bool MakePooledArgs(const PlanInstance& pi, size_t i, int count, bool chain, ConvArgs* a, PooledArgs* p) const;
     void SaveTuneCache();
+    // The members this class gained with the kernel-family tables.  The library is built with default visibility, so every member of this class is an
+    // exported symbol; these three are marked so that the export list stays what it was.
+    __attribute__((visibility("hidden"))) void TuneTiles(TuneContext& ctx, const PlanInstance& pi, Step& s, const std::vector<int64_t>& key, int code_base, int ntiles);
+    __attribute__((visibility("hidden"))) void LaunchParts(const PlanInstance& pi, const Step& s, hipStream_t stream);             // tile 0 of a fused step
+    __attribute__((visibility("hidden"))) FusedArgs MakeFusedArgs(const PlanInstance& pi, const Step& s) const;                    // the one place that builds FusedArgs
     void EnsurePipeline(PlanInstance& pi, bool allow_tune);
     void AllocInstance(PlanInstance& pi);
     void RefreshGraphs(PlanInstance& pi);   // (re)capture the graphs of `pi` when they are missing or older than the current fp8 scales
     void PrepareF8(const std::vector<float>* adopt_act_scales = nullptr);       // quantise the conv weights, calibrate the activation scales, derive the epilogue multipliers (once per DeviceWeights)
     void LaunchStep(const PlanInstance& pi, const Step& s, hipStream_t stream);
+    template <class F>
+    bool TiledFamily(const PlanInstance& pi, const Step& s, F&& f) const;                    // the generic-plus-variants families (executor_internal.h)
     const Step& LaunchedStep(const PlanInstance& pi, const Step& s, Step& scratch) const;   // what LaunchStep really runs for `s` (a declined launcher hands over)
     ConvArgs MakeConvArgs(const PlanInstance& pi, const Step& s) const;
     DwArgs MakeDwArgs(const PlanInstance& pi, const Step& s) const;

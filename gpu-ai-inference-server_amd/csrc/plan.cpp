@@ -3263,7 +3263,7 @@ bool Planner::output_in_buffer(int buf) const {
 }
 
 ConvFacts::ConvFacts(const LNode& nn, const Step& ss) : n(nn), s(ss) {
-    // a dilated conv may only take the kernels that honour the dilation (plan.h DilationOk): the implicit GEMMs' base tiles and the
+    // a dilated conv may only take the kernels that honour the dilation (launch.cpp ConvFamily::dilation): the implicit GEMMs' base tiles and the
     // naive kernel.  Every specialised kernel's eligibility is false for it, and the forcing switches cannot move it elsewhere
     dil = s.dh > 1 || s.dw > 1;
     M = s.out.n * s.out.h * s.out.w; N = s.out.c; K = int64_t(n.kh) * n.kw * s.in.c;

@@ -89,8 +89,6 @@ enum class ConvAlgo : int {
 // The conv algorithms whose weights are not the dense [Cout][kh][kw][Cin] layout (depthwise, grouped, transposed): no dense-conv pass or weight
 // mirror may take their steps
 inline bool IsGroupConv(ConvAlgo a) { return a == ConvAlgo::Depthwise || a == ConvAlgo::Grouped || a == ConvAlgo::Transposed; }
-// The conv algorithms that honour a dilation > 1 (the only ones a dilated step may take)
-inline bool DilationOk(ConvAlgo a) { return a == ConvAlgo::IgemmVec || a == ConvAlgo::IgemmScalar || a == ConvAlgo::Naive; }
 
 struct Step {
     StepKind kind = StepKind::Conv;

@@ -1,5 +1,5 @@
 """CPU: which transitions the executor may run as one launch of conv1x1_pooled_kernel (EngineDescribeModel's `paired_launches`, decided from
-shapes and views alone; csrc/executor.cpp FindPairedLaunches), and that the plan itself never moves with IE_POOL_CONV.
+shapes and views alone; csrc/tune.cpp FindPairedLaunches), and that the plan itself never moves with IE_POOL_CONV.
 
 DenseNet-121 fp32 has three transitions (256 -> 128, 512 -> 256, 1024 -> 512 channels): all three pair, the first two can also chain the next
 block's entry 1x1 (chain tiles of 128 and 256 channels; no 512-channel chain tile is built).  Half and e4m3 plans list nothing.  The near
