@@ -26,7 +26,7 @@ const char* const kNames[] = {
     "IE_GROUPED_CONV",         // 1: plan convs with 1 < group (not depthwise) as grouped steps (kernels_grouped.hip); unset: they are refused
     "IE_FORCE_ALGO", "IE_FORCE_TILE", "IE_FORCE_SPLITK",      // tests: pin the kernel family / tile / split-K of every conv
     "IE_GN_TILE",              // 0 | 1: the tile of the group-norm steps alone (an ineligible 1 is the generic kernel), every other step as planned
-    "IE_ATTN_TILE",            // 0 | 1 | 2: the tile of the attention steps alone, read when IE_FORCE_TILE did not force (an ineligible value is the generic kernel)
+    "IE_ATTN_TILE",            // 0 | 1 | 2 | 3: the tile of the attention steps alone, read when IE_FORCE_TILE did not force (an ineligible value is the generic kernel)
     // ---- executor ----------------------------------------------------------------------------------------------------------------
     "IE_AUTOTUNE", "IE_TUNE_CACHE", "IE_TUNE_BATCHES", "IE_TUNE_ON_DEMAND", "IE_TUNE_HOT", "IE_TUNE_LOG",
     "IE_DISABLE_GRAPH", "IE_SPLITK_IN_LAUNCH", "IE_PIPELINE_CHUNKS", "IE_PIPELINE_HEAD", "IE_MAX_PLANS", "IE_NO_FRAG_WEIGHTS",

@@ -294,6 +294,8 @@ hipError_t LaunchGroupNormPhase(const GnArgs& a, int phase, hipStream_t stream);
 
 // Token embedding + LayerNormalization (kernels_embed.hip; BERT-class graphs): for every token row r = (n, l) of out [N, L, D]
 //   out[r, :] = LayerNorm(word[ids[r]] + type[tids[r]] + pos[l]; gamma, beta, eps)
+// gamma null (a pre-LN model such as GPT-2, whose sum is read by a LayerNormalization AND by the residual Add): out[r, :] = the fp32 sum itself,
+// stored in out's element type (embed_sum_kernel<T, LANES> / embed_sum_generic_kernel; the same tiles and eligibility).
 // ids / tids are the dense int64 [N, L] graph inputs; a negative index counts from the end, the wrapped index is clamped into the table.  Tables,
 // position rows, gamma and beta are fp32 in every precision; out is float or half (TensorArg::f16).  Statistics as LnArgs.
 struct EmbedArgs {
@@ -302,7 +304,7 @@ struct EmbedArgs {
     const float* word = nullptr;       // [vocab][D]
     const float* type = nullptr;       // [types][D] or null
     const float* pos = nullptr;        // [L][D] or null
-    const float* gamma = nullptr;      // [D]
+    const float* gamma = nullptr;      // [D], or null: no LayerNormalization behind the sum
     const float* beta = nullptr;       // [D] or null
     TensorArg out;                     // out.n = N, out.w = L, out.c = D, out.h = 1
     int vocab = 0, types = 0;
@@ -337,14 +339,16 @@ struct AttnArgs {
     const int64_t* mask = nullptr;     // null: no mask
     int64_t mask_sn = 0;
     float mask_value = 0.f;
+    int causal = 0;                    // query i attends to the keys j <= i only (a decoder's mask); never together with a key mask
 };
 // tile 0: attention_generic_kernel (one wave per query row; any L, head_dim, pitch, offset; float or half).  tile 1: attention_mfma_kernel<T, HD>
 // (a workgroup = one image, one head, 128 queries; the head's K and V rows in LDS): head_dim 32 or 64, the channel counts, pitches and offsets
 // multiples of the 16-byte vector, and both of the head's padded K and V images inside the LDS budget.  tile 2: attention_stream_kernel<T, HD>
 // (a workgroup = one image, one head, 32 queries; its four waves split the head dim; K and V streamed in tiles of 32 keys, LDS independent of L):
-// head_dim 128, 256 or 512, no key mask, the same vector conditions
-constexpr int kNumAttnTiles = 3;
-// IE_FORCE_TILE reaches tiles 0 and 1 of an attention step only (2 keeps meaning "not forced"); tile 2 is pinned with IE_ATTN_TILE
+// head_dim 128, 256 or 512, no key mask, not causal, the same vector conditions.  tile 3: attention_chunk_kernel<T, HD, CAUSAL> (tile 1's workgroup,
+// K and V staged in chunks of kAttnChunkKeys keys, LDS independent of L): head_dim 32 or 64, no key mask, the same vector conditions
+constexpr int kNumAttnTiles = 4;
+// IE_FORCE_TILE reaches tiles 0 and 1 of an attention step only (2 and 3 keep meaning "not forced"); tiles 2 and 3 are pinned with IE_ATTN_TILE
 constexpr int kNumAttnForcedTiles = 2;
 constexpr int64_t kAttnLdsBudget = 160 * 1024;
 // bytes of LDS the MFMA kernel needs: K and V rows, L padded to whole 32-key tiles, every row padded by one 16-byte vector; masked: one fp32 bias
@@ -373,6 +377,22 @@ constexpr int AttnDefaultTile(int64_t L, int hd, bool f16, int64_t c_in, int64_t
                               bool masked = false) {
     if (AttnMfmaFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, masked)) return 1;
     return AttnStreamFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, masked) && L >= kAttnStreamMinTokens ? 2 : 0;
+}
+// tile 3: keys per chunk (a multiple of the 32-key tile), and the bytes of LDS of one chunk of K and V rows, every row padded by one 16-byte vector
+// (fp32 hd 64: 2 * 256 * 272 = 136 KiB: one workgroup per CU)
+constexpr int kAttnChunkKeys = 256;
+constexpr int64_t AttnChunkLdsBytes(int hd, bool f16) { return 2 * int64_t(kAttnChunkKeys) * (int64_t(hd) * (f16 ? 2 : 4) + 16); }
+constexpr bool AttnChunkFits(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out,
+                             bool masked = false) {
+    const int64_t V = f16 ? 8 : 4;
+    return (hd == 32 || hd == 64) && L >= 1 && !masked && c_in % V == 0 && pitch_in % V == 0 && off_in % V == 0 && c_out % V == 0 && pitch_out % V == 0 &&
+           off_out % V == 0 && AttnChunkLdsBytes(hd, f16) <= kAttnLdsBudget;
+}
+// a causal step: tile 1 where it fits, else tile 3 where it fits, else the generic kernel (tile 2 has no causal form).  A non-causal step reaches tile 3
+// through IE_ATTN_TILE=3 only
+constexpr int AttnCausalDefaultTile(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out) {
+    if (AttnMfmaFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, false)) return 1;
+    return AttnChunkFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, false) ? 3 : 0;
 }
 bool AttentionEligible(const AttnArgs& a, int tile);
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);

@@ -30,7 +30,14 @@
 //          with exact integers).
 // Padded keys (j >= L) get -inf before the maximum; padded queries are computed from the last row and never stored.
 //
-// MASK (both kernels): the key mask of a BERT-class graph.  Key j of image n gets the bias (1 - float(mask[n, j])) * c on its scaled score, computed in
+//   attention_chunk_kernel<T, HD>   tile 3: tile 1's workgroup, orientation, online softmax and epilogue, for any L: K and V pass through LDS in chunks of
+//                                   kAttnChunkKeys keys (stage, barrier, the chunk's key tiles, barrier), so LDS is a constant (described at the kernel).
+//
+// CAUSAL (tiles 0, 1 and 3; never with MASK): query i attends to the keys j <= i.  The keys above the diagonal are left out, not computed and discarded:
+// tile 0 ends its key loops at i + 1; a workgroup of tile 1 / 3 stages only the key rows below 128 (qb + 1), a wave's key-tile loop ends with the tile
+// that holds its last query (key0 <= q0 + 31), and only the tile with key0 == q0 tests its elements (key > query -> -inf, before the maximum).
+//
+// MASK (tiles 0 and 1): the key mask of a BERT-class graph.  Key j of image n gets the bias (1 - float(mask[n, j])) * c on its scaled score, computed in
 // fp32 as the graph computes it.  Tile 1 stages the image's L biases in LDS behind K / V, already in units of log2 and clamped at -FLT_MAX
 // (c = finfo.min times log2 e would overflow to -inf, and a fully masked row would be exp2(-inf - -inf) = NaN), padded keys at -inf; the bias is
 // added to the fp32 scaled score before the running maximum.  -FLT_MAX + s rounds to -FLT_MAX for every real score, so a fully masked row with
@@ -64,7 +71,7 @@ constexpr float kFltMax = 3.402823466e+38f;
 constexpr float kMaskShiftMax = 16777216.f;
 
 // rows = N * heads * L query rows, one wave each
-template <bool MASK>
+template <bool MASK, bool CAUSAL>
 __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const AttnArgs a, const int64_t rows) {
     const int lane = int(threadIdx.x) % 64;
     const int64_t row = int64_t(blockIdx.x) * (kAttnBlock / 64) + threadIdx.x / 64;
@@ -76,6 +83,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
     const int64_t qb = n * a.in.sn + int64_t(i) * a.in.sw + int64_t(h) * hd * a.in.sc;       // q row; key row j: kb + j * sw
     const int64_t kb = n * a.in.sn + int64_t(D + h * hd) * a.in.sc, vb = kb + int64_t(D) * a.in.sc;
     const int64_t ob = n * a.out.sn + int64_t(i) * a.out.sw + int64_t(h) * hd * a.out.sc;
+    const int Lk = CAUSAL ? i + 1 : L;             // the keys of this query: j < Lk
     [[maybe_unused]] float shift = 0.f;            // MASK: the image's largest bias, where it is small enough to be taken out exactly
     if constexpr (MASK) {
         float bm = -kFltMax;
@@ -91,17 +99,17 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
         else return s * a.scale;
     };
     float m = -__builtin_huge_valf();
-    for (int j = lane; j < L; j += 64) m = fmaxf(m, score(j));
+    for (int j = lane; j < Lk; j += 64) m = fmaxf(m, score(j));
 #pragma unroll
     for (int x = 32; x >= 1; x >>= 1) m = fmaxf(m, __shfl_xor(m, x, 64));
     for (int e0 = 0; e0 < hd; e0 += 64) {
         const int e = e0 + lane;
         float l = 0.f, acc = 0.f;
-        for (int j0 = 0; j0 < L; j0 += 64) {
+        for (int j0 = 0; j0 < Lk; j0 += 64) {
             const int j = j0 + lane;
-            const float p = j < L ? expf(score(j) - m) : 0.f;
+            const float p = j < Lk ? expf(score(j) - m) : 0.f;
             l += p;
-            const int cnt = L - j0 < 64 ? L - j0 : 64;
+            const int cnt = Lk - j0 < 64 ? Lk - j0 : 64;
             for (int t = 0; t < cnt; ++t) {
                 const float pj = __shfl(p, t, 64);
                 if (e < hd) acc = fmaf(pj, ld_any(a.in.p, a.in.f16, vb + int64_t(j0 + t) * a.in.sw + int64_t(e) * a.in.sc), acc);
@@ -120,13 +128,133 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// grid = N * heads * qblocks workgroups (qblocks = ceil(L / 128)); dynamic LDS = AttnLdsBytes(L, HD, half)
-template <typename T, int HD, bool MASK>
+// What a wave of tile 1 / 3 carries through its key tiles: its lane's half of its Q row, the O^T accumulators and the softmax statistics of its query
+template <typename T, int HD>
+struct AttnWave {
+    static constexpr bool F16 = sizeof(T) == 2;
+    static constexpr int HH = HD / 2;              // head-dim elements one lane half supplies to QK^T
+    float4 q4[F16 ? 1 : HH / 4];
+    h8v q8[F16 ? HH / 8 : 1];
+    f32x16 o0, o1;
+    float m, lsum;
+
+    __device__ __forceinline__ void init(const T* qrow) {
+        if constexpr (F16) {
+#pragma unroll
+            for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8v*>(qrow + 8 * k);
+        } else {
+#pragma unroll
+            for (int k = 0; k < HH / 4; ++k) q4[k] = *reinterpret_cast<const float4*>(qrow + 4 * k);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+        m = -__builtin_huge_valf();
+        lsum = 0.f;
+    }
+
+    // One tile of 32 keys: Kt / Vt = the LDS rows of key key0 (row stride RS), Bt = the biases from key0 on (MASK).  query = q0 + col (CAUSAL); diag: this
+    // is the tile with key0 == q0, the only one of a causal wave whose elements are tested.
+    // Every tile a wave visits holds at least one visible key for each of its queries, which keeps the running maximum finite: a tile holds a real key
+    // (key0 < L); causal, a tile below the diagonal holds only keys < q0 <= every query of the wave, and the diagonal tile's first key q0 is <= every
+    // query of the wave and real (q0 < L; the padded queries q0 + col >= L are only ever compared as q0 + col, which admits more keys, not fewer).
+    template <int RS, bool MASK, bool CAUSAL>
+    __device__ __forceinline__ void key_tile(const T* Kt, const T* Vt, const float* Bt, int key0, int L, int query, bool diag, float sl2, float shift, int col, int hf) {
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        const T* krow = Kt + col * RS + hf * HH;
+        if constexpr (F16) {
+#pragma unroll
+            for (int k = 0; k < HH; k += 8)
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8v*>(krow + k), q8[k / 8], s, 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int k = 0; k < HH; k += 4) {
+                const float4 kf = *reinterpret_cast<const float4*>(krow + k);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, q4[k / 4].x, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, q4[k / 4].y, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, q4[k / 4].z, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, q4[k / 4].w, s, 0, 0, 0);
+            }
+        }
+        const bool tail = key0 + 32 > L;           // the last tile holds padded keys
+        float mx = -__builtin_huge_valf();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int kt = (r & 3) + 8 * (r >> 2) + 4 * hf, key = key0 + kt;
+            if constexpr (MASK) {
+                const float b = Bt[kt];                // -inf on a padded key, else finite: the biased score of a real key stays finite
+                s[r] = b < -kFltMax ? b : fmaxf(fmaf(s[r], sl2, b - shift), -kFltMax);
+            }
+            else if constexpr (CAUSAL) s[r] = (tail && key >= L) || (diag && key > query) ? -__builtin_huge_valf() : s[r] * sl2;
+            else s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
+            mx = fmaxf(mx, s[r]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mn = fmaxf(m, mx);             // finite: every tile has at least one visible key (above)
+        const float alpha = fast_exp2(m - mn);     // 0 on the first tile (m = -inf)
+        m = mn;
+        float ps = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] = fast_exp2(s[r] - mn);
+            ps += s[r];
+            o0[r] *= alpha;
+            if constexpr (HD == 64) o1[r] *= alpha;
+        }
+        lsum = fmaf(lsum, alpha, ps);              // this lane half's share of the row sum
+        if constexpr (F16) {
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                h8v pb, va0, va1;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int kt = 16 * st + 8 * (j >> 2) + 4 * hf + (j & 3);
+                    pb[j] = _Float16(s[8 * st + j]);
+                    va0[j] = Vt[kt * RS + col];
+                    if constexpr (HD == 64) va1[j] = Vt[kt * RS + 32 + col];
+                }
+                o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va0, pb, o0, 0, 0, 0);
+                if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va1, pb, o1, 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int kt = (r & 3) + 8 * (r >> 2) + 4 * hf;
+                o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vt[kt * RS + col]), s[r], o0, 0, 0, 0);
+                if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vt[kt * RS + 32 + col]), s[r], o1, 0, 0, 0);
+            }
+        }
+    }
+
+    // O / l of this lane's query into its output row (columns h HD ...); both lane halves hold the whole row sum afterwards
+    __device__ __forceinline__ void store(T* orow, int hf) {
+        const float inv = 1.f / lsum;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int e0 = 8 * g + 4 * hf;             // registers 4 g ... 4 g + 3 are the output columns e0 ... e0 + 3 of this lane's query
+            if constexpr (F16) {
+                h4v x, y;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) { x[t] = _Float16(o0[4 * g + t] * inv); y[t] = _Float16(o1[4 * g + t] * inv); }
+                *reinterpret_cast<h4v*>(orow + e0) = x;
+                if constexpr (HD == 64) *reinterpret_cast<h4v*>(orow + 32 + e0) = y;
+            } else {
+                *reinterpret_cast<float4*>(orow + e0) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
+                if constexpr (HD == 64)
+                    *reinterpret_cast<float4*>(orow + 32 + e0) = make_float4(o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
+            }
+        }
+    }
+};
+
+// grid = N * heads * qblocks workgroups (qblocks = ceil(L / 128)); dynamic LDS = AttnLdsBytes(L, HD, half) (by L, causal or not)
+template <typename T, int HD, bool MASK, bool CAUSAL>
 __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnArgs a, const int qblocks) {
-    constexpr bool F16 = sizeof(T) == 2;
+    static_assert(!(MASK && CAUSAL), "a key mask together with a causal mask is not built");
     constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
     constexpr int RS = HD + V;                     // LDS row stride in elements
-    constexpr int HH = HD / 2;                     // head-dim elements one lane half supplies to QK^T
+    constexpr int HH = HD / 2;
     constexpr int VPR = HD / V;                    // vectors per K / V row
     extern __shared__ __attribute__((aligned(16))) unsigned char attn_smem[];
     const int L = a.in.w, Lp = (L + 31) / 32 * 32, D = a.heads * HD;
@@ -136,8 +264,9 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
     const int hn = int(blockIdx.x) / qblocks;
     const int h = hn % a.heads, n = hn / a.heads;
     const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // token row j: + j * sw; q at + 0, k at + D, v at + 2 D
+    const int Ls = CAUSAL && 128 * (qb + 1) < Lp ? 128 * (qb + 1) : Lp;                    // CAUSAL: no query of this workgroup sees a key beyond its last query
 
-    for (int idx = int(threadIdx.x); idx < Lp * VPR; idx += kAttnBlock) {
+    for (int idx = int(threadIdx.x); idx < Ls * VPR; idx += kAttnBlock) {
         const int row = idx / VPR, cv = idx % VPR;
         uint4 kv = make_uint4(0u, 0u, 0u, 0u), vv = kv;                                   // rows past L: zeros (a zero probability times them stays zero)
         if (row < L) {
@@ -159,21 +288,8 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
     const int q0 = qb * 128 + wave * 32;
     if (q0 >= L) return;                           // wave-uniform, behind the kernel's only barrier
     const int qi = q0 + col < L ? q0 + col : L - 1;
-    const T* qrow = base + int64_t(qi) * a.in.sw + hf * HH;
-    float4 q4[F16 ? 1 : HH / 4];                   // this lane's half of its Q row, in registers for the whole kernel
-    h8v q8[F16 ? HH / 8 : 1];
-    if constexpr (F16) {
-#pragma unroll
-        for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8v*>(qrow + 8 * k);
-    } else {
-#pragma unroll
-        for (int k = 0; k < HH / 4; ++k) q4[k] = *reinterpret_cast<const float4*>(qrow + 4 * k);
-    }
-
-    f32x16 o0, o1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-    float m = -__builtin_huge_valf(), lsum = 0.f;
+    AttnWave<T, HD> w;                             // this lane's half of its Q row in registers for the whole kernel
+    w.init(base + int64_t(qi) * a.in.sw + hf * HH);
     const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
     [[maybe_unused]] float shift = 0.f;            // MASK: the image's largest bias (every wave finds it for itself), where it is small enough to be taken out exactly
     if constexpr (MASK) {
@@ -184,93 +300,73 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
         shift = fabsf(bm) <= kMaskShiftMax * kLog2e ? bm : 0.f;
     }
 
-    for (int key0 = 0; key0 < Lp; key0 += 32) {
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-        const T* krow = Ks + (key0 + col) * RS + hf * HH;
-        if constexpr (F16) {
-#pragma unroll
-            for (int k = 0; k < HH; k += 8)
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8v*>(krow + k), q8[k / 8], s, 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int k = 0; k < HH; k += 4) {
-                const float4 kf = *reinterpret_cast<const float4*>(krow + k);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, q4[k / 4].x, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, q4[k / 4].y, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, q4[k / 4].z, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, q4[k / 4].w, s, 0, 0, 0);
+    const int kend = CAUSAL ? q0 + 32 : Lp;        // CAUSAL: the wave's last tile is the one that holds its queries (q0 + 32 <= Ls)
+    for (int key0 = 0; key0 < kend; key0 += 32)
+        w.template key_tile<RS, MASK, CAUSAL>(Ks + key0 * RS, Vs + key0 * RS, Bs + key0, key0, L, q0 + col, key0 == q0, sl2, shift, col, hf);
+
+    w.lsum += __shfl_xor(w.lsum, 32, 64);
+    if (q0 + col >= L) return;
+    w.store(reinterpret_cast<T*>(a.out.p) + int64_t(n) * a.out.sn + int64_t(q0 + col) * a.out.sw + h * HD, hf);
+}
+
+// Tile 3.  grid = N * heads * qblocks workgroups (qblocks = ceil(L / 128)); dynamic LDS = AttnChunkLdsBytes(HD, half), whatever L.
+// Tile 1 with K and V staged chunk by chunk: per chunk of kAttnChunkKeys keys the workgroup stages the rows, meets at a barrier, every wave walks the
+// chunk's key tiles (AttnWave::key_tile, so scores, statistics and accumulation are tile 1's to the bit), and a second barrier lets the next chunk
+// overwrite the rows (single-buffered: one workgroup per CU at fp32 hd 64 either way).
+// EVERY wave takes part in EVERY barrier: a wave whose queries lie beyond L, and a causal wave that is already past its diagonal, keep staging and
+// waiting and only skip the key tiles; there is no return in front of the last barrier (tile 1 may leave behind its only barrier; here that would hang
+// the workgroup).  CAUSAL: the workgroup's chunk loop ends with the chunk that holds key 128 qb + 127.
+// The late query blocks of a causal step do the most work: block ids are dealt out reversed, the last query block of every (image, head) first, so the
+// grid's tail is made of the light workgroups.
+template <typename T, int HD, bool CAUSAL>
+__global__ __launch_bounds__(kAttnBlock) void attention_chunk_kernel(const AttnArgs a, const int qblocks) {
+    constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
+    constexpr int RS = HD + V;                     // LDS row stride in elements
+    constexpr int HH = HD / 2;
+    constexpr int VPR = HD / V;                    // vectors per K / V row
+    constexpr int KC = kAttnChunkKeys;
+    static_assert(KC % 32 == 0, "whole key tiles per chunk");
+    extern __shared__ __attribute__((aligned(16))) unsigned char attn_smem[];
+    const int L = a.in.w, Lp = (L + 31) / 32 * 32, D = a.heads * HD;
+    T* Ks = reinterpret_cast<T*>(attn_smem);
+    T* Vs = Ks + size_t(KC) * RS;
+    const int nh = int(gridDim.x) / qblocks;       // images x heads
+    const int qb = qblocks - 1 - int(blockIdx.x) / nh;
+    const int hn = int(blockIdx.x) % nh;
+    const int h = hn % a.heads, n = hn / a.heads;
+    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // token row j: + j * sw; q at + 0, k at + D, v at + 2 D
+    const int wave = int(threadIdx.x) / 64, lane = int(threadIdx.x) % 64, col = lane & 31, hf = lane >> 5;
+    const int q0 = qb * 128 + wave * 32;
+    const bool live = q0 < L;                      // wave-uniform
+    const int qi = q0 + col < L ? q0 + col : L - 1;
+    AttnWave<T, HD> w;
+    w.init(base + int64_t(qi) * a.in.sw + hf * HH);
+    const float sl2 = a.scale * kLog2e;
+    const int Ls = CAUSAL && 128 * (qb + 1) < Lp ? 128 * (qb + 1) : Lp;      // the workgroup's keys: whole tiles, the same for its four waves
+    const int kend = !live ? 0 : (CAUSAL ? q0 + 32 : Lp);                 // this wave's keys (live: q0 + 32 <= Ls)
+
+    for (int c0 = 0; c0 < Ls; c0 += KC) {          // (the bounds are the workgroup's: every wave runs every iteration)
+        const int rows = Ls - c0 < KC ? Ls - c0 : KC;
+        for (int idx = int(threadIdx.x); idx < rows * VPR; idx += kAttnBlock) {
+            const int lr = idx / VPR, cv = idx % VPR, row = c0 + lr;
+            uint4 kv = make_uint4(0u, 0u, 0u, 0u), vv = kv;                               // rows past L: zeros
+            if (row < L) {
+                const T* r = base + int64_t(row) * a.in.sw + cv * V;
+                kv = *reinterpret_cast<const uint4*>(r + D);
+                vv = *reinterpret_cast<const uint4*>(r + 2 * D);
             }
+            *reinterpret_cast<uint4*>(Ks + lr * RS + cv * V) = kv;
+            *reinterpret_cast<uint4*>(Vs + lr * RS + cv * V) = vv;
         }
-        const bool tail = key0 + 32 > L;           // the last tile holds padded keys
-        float mx = -__builtin_huge_valf();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-            if constexpr (MASK) {
-                const float b = Bs[key];               // -inf on a padded key, else finite: the biased score of a real key stays finite
-                s[r] = b < -kFltMax ? b : fmaxf(fmaf(s[r], sl2, b - shift), -kFltMax);
-            }
-            else s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
-            mx = fmaxf(mx, s[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mn = fmaxf(m, mx);             // finite: every tile has at least one real key
-        const float alpha = fast_exp2(m - mn);     // 0 on the first tile (m = -inf)
-        m = mn;
-        float ps = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = fast_exp2(s[r] - mn);
-            ps += s[r];
-            o0[r] *= alpha;
-            if constexpr (HD == 64) o1[r] *= alpha;
-        }
-        lsum = fmaf(lsum, alpha, ps);              // this lane half's share of the row sum
-        if constexpr (F16) {
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                h8v pb, va0, va1;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int key = key0 + 16 * st + 8 * (j >> 2) + 4 * hf + (j & 3);
-                    pb[j] = _Float16(s[8 * st + j]);
-                    va0[j] = Vs[key * RS + col];
-                    if constexpr (HD == 64) va1[j] = Vs[key * RS + 32 + col];
-                }
-                o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va0, pb, o0, 0, 0, 0);
-                if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va1, pb, o1, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-                o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vs[key * RS + col]), s[r], o0, 0, 0, 0);
-                if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vs[key * RS + 32 + col]), s[r], o1, 0, 0, 0);
-            }
-        }
+        __syncthreads();
+        const int cend = c0 + rows < kend ? c0 + rows : kend;
+        for (int key0 = c0; key0 < cend; key0 += 32)
+            w.template key_tile<RS, false, CAUSAL>(Ks + (key0 - c0) * RS, Vs + (key0 - c0) * RS, nullptr, key0, L, q0 + col, key0 == q0, sl2, 0.f, col, hf);
+        __syncthreads();                           // the next chunk overwrites the rows
     }
 
-    lsum += __shfl_xor(lsum, 32, 64);
-    if (q0 + col >= L) return;
-    const float inv = 1.f / lsum;
-    T* orow = reinterpret_cast<T*>(a.out.p) + int64_t(n) * a.out.sn + int64_t(q0 + col) * a.out.sw + h * HD;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int e0 = 8 * g + 4 * hf;             // registers 4 g ... 4 g + 3 are the output columns e0 ... e0 + 3 of this lane's query
-        if constexpr (F16) {
-            h4v x, y;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { x[t] = _Float16(o0[4 * g + t] * inv); y[t] = _Float16(o1[4 * g + t] * inv); }
-            *reinterpret_cast<h4v*>(orow + e0) = x;
-            if constexpr (HD == 64) *reinterpret_cast<h4v*>(orow + 32 + e0) = y;
-        } else {
-            *reinterpret_cast<float4*>(orow + e0) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-            if constexpr (HD == 64)
-                *reinterpret_cast<float4*>(orow + 32 + e0) = make_float4(o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
-        }
-    }
+    w.lsum += __shfl_xor(w.lsum, 32, 64);
+    if (q0 + col < L) w.store(reinterpret_cast<T*>(a.out.p) + int64_t(n) * a.out.sn + int64_t(q0 + col) * a.out.sw + h * HD, hf);
 }
 
 // Tile 2: one wide head.  grid = N * heads * qblocks workgroups (qblocks = ceil(L / 32)); dynamic LDS = AttnStreamLdsBytes(HD, half).
@@ -472,14 +568,33 @@ bool vec_view_ok(const TensorArg& t, int V) {
     return t.sc == 1 && t.h == 1 && t.c % V == 0 && t.sw % V == 0 && t.sn == int64_t(t.w) * t.sw && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
 }
 
-template <typename T, int HD, bool MASK>
+template <typename T, int HD, bool MASK, bool CAUSAL>
 hipError_t launch_mfma(const AttnArgs& a, hipStream_t stream) {
     const int qblocks = (a.in.w + 127) / 128;
     const int64_t blocks = int64_t(a.in.n) * a.heads * qblocks;
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
     const size_t lds = size_t(AttnLdsBytes(a.in.w, HD, sizeof(T) == 2, MASK));
-    attention_mfma_kernel<T, HD, MASK><<<dim3(unsigned(blocks)), dim3(kAttnBlock), lds, stream>>>(a, qblocks);
+    attention_mfma_kernel<T, HD, MASK, CAUSAL><<<dim3(unsigned(blocks)), dim3(kAttnBlock), lds, stream>>>(a, qblocks);
     return hipGetLastError();
+}
+
+template <typename T, int HD, bool CAUSAL>
+hipError_t launch_chunk(const AttnArgs& a, hipStream_t stream) {
+    const int qblocks = (a.in.w + 127) / 128;
+    const int64_t blocks = int64_t(a.in.n) * a.heads * qblocks;
+    if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    attention_chunk_kernel<T, HD, CAUSAL><<<dim3(unsigned(blocks)), dim3(kAttnBlock), size_t(AttnChunkLdsBytes(HD, sizeof(T) == 2)), stream>>>(a, qblocks);
+    return hipGetLastError();
+}
+
+// tiles 1 and 3 by head dim (32 / 64: the eligibility admitted nothing else)
+template <typename T, bool MASK, bool CAUSAL>
+hipError_t launch_mfma_hd(const AttnArgs& a, hipStream_t stream) {
+    return a.head_dim == 64 ? launch_mfma<T, 64, MASK, CAUSAL>(a, stream) : launch_mfma<T, 32, MASK, CAUSAL>(a, stream);
+}
+template <typename T, bool CAUSAL>
+hipError_t launch_chunk_hd(const AttnArgs& a, hipStream_t stream) {
+    return a.head_dim == 64 ? launch_chunk<T, 64, CAUSAL>(a, stream) : launch_chunk<T, 32, CAUSAL>(a, stream);
 }
 
 template <typename T, int HD>
@@ -508,10 +623,12 @@ bool AttentionEligible(const AttnArgs& a, int tile) {
     const int64_t D = int64_t(a.heads) * a.head_dim;
     if (a.in.f8 || a.out.f8 || a.in.c != 3 * D || a.out.c != D || a.in.n != a.out.n || a.in.h != 1 || a.out.h != 1 || a.in.w != a.out.w || a.in.w < 1) return false;
     if (a.mask && a.mask_sn < a.in.w) return false;
+    if (a.causal && (a.mask || tile == 2)) return false;      // no kernel has both masks, and tile 2 has no causal form
     if (tile == 0) return true;
     const int V = a.out.f16 ? 8 : 4;
     // (the offsets are in the base pointers: their alignment stands for the offset condition)
     if (a.in.f16 != a.out.f16 || !vec_view_ok(a.in, V) || !vec_view_ok(a.out, V)) return false;
+    if (tile == 3) return AttnChunkFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr);
     return tile == 1 ? AttnMfmaFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr)
                      : AttnStreamFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr);
 }
@@ -523,25 +640,33 @@ hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream) {
         const int64_t rows = int64_t(a.in.n) * a.heads * a.in.w;
         const int64_t blocks = (rows + kAttnBlock / 64 - 1) / (kAttnBlock / 64);
         if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-        if (a.mask) hipLaunchKernelGGL(attention_generic_kernel<true>, dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
-        else hipLaunchKernelGGL(attention_generic_kernel<false>, dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
+        if (a.mask) hipLaunchKernelGGL((attention_generic_kernel<true, false>), dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
+        else if (a.causal) hipLaunchKernelGGL((attention_generic_kernel<false, true>), dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
+        else hipLaunchKernelGGL((attention_generic_kernel<false, false>), dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
         return hipGetLastError();
     }
     if (tile == 2) return a.out.f16 ? launch_stream_hd<_Float16>(a, stream) : launch_stream_hd<float>(a, stream);
-    if (a.mask) {
-        if (a.out.f16) return a.head_dim == 64 ? launch_mfma<_Float16, 64, true>(a, stream) : launch_mfma<_Float16, 32, true>(a, stream);
-        return a.head_dim == 64 ? launch_mfma<float, 64, true>(a, stream) : launch_mfma<float, 32, true>(a, stream);
+    if (tile == 3) {
+        if (a.causal) return a.out.f16 ? launch_chunk_hd<_Float16, true>(a, stream) : launch_chunk_hd<float, true>(a, stream);
+        return a.out.f16 ? launch_chunk_hd<_Float16, false>(a, stream) : launch_chunk_hd<float, false>(a, stream);
     }
-    if (a.out.f16) return a.head_dim == 64 ? launch_mfma<_Float16, 64, false>(a, stream) : launch_mfma<_Float16, 32, false>(a, stream);
-    return a.head_dim == 64 ? launch_mfma<float, 64, false>(a, stream) : launch_mfma<float, 32, false>(a, stream);
+    if (a.mask) return a.out.f16 ? launch_mfma_hd<_Float16, true, false>(a, stream) : launch_mfma_hd<float, true, false>(a, stream);
+    if (a.causal) return a.out.f16 ? launch_mfma_hd<_Float16, false, true>(a, stream) : launch_mfma_hd<float, false, true>(a, stream);
+    return a.out.f16 ? launch_mfma_hd<_Float16, false, false>(a, stream) : launch_mfma_hd<float, false, false>(a, stream);
 }
 
 hipError_t InitKernelsAttn() {
     const void* const kernels[] = {
-        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, true>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, true>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, true, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, true, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, true, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, true, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false, true>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false, true>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<float, 32, false>), reinterpret_cast<const void*>(&attention_chunk_kernel<float, 64, false>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 32, false>), reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 64, false>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<float, 32, true>), reinterpret_cast<const void*>(&attention_chunk_kernel<float, 64, true>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 32, true>), reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 64, true>),
         reinterpret_cast<const void*>(&attention_stream_kernel<float, 128>), reinterpret_cast<const void*>(&attention_stream_kernel<float, 256>),
         reinterpret_cast<const void*>(&attention_stream_kernel<float, 512>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 128>),
         reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 256>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 512>)};

@@ -17,7 +17,11 @@
 //   embed_ln_generic_kernel          one wave per token row, any D, pitch and offset, float or half output; the row is rebuilt from the tables for
 //                                    each of its three passes (the same fp32 sums every time).
 //
-// Both only enqueue work on the given stream: they are graph-capturable, and a replay is bit-identical to the eager run.
+//   embed_sum_kernel<T, LANES>       gamma null: the sum itself is the result (a pre-LN model, GPT-2: the sum is read by a LayerNormalization and by the
+//   embed_sum_generic_kernel         residual Add, so it has to exist).  The same lane groups, the same row assembly from 16-byte table loads, no
+//                                    statistics and no shuffles; the sum is fp32, the store in out's element type.  The generic form is one wave per row.
+//
+// All only enqueue work on the given stream: they are graph-capturable, and a replay is bit-identical to the eager run.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -61,6 +65,14 @@ __device__ __forceinline__ void store_vec(_Float16* p, const float* v) {
     *reinterpret_cast<h8v*>(p) = o;
 }
 
+// output vector cv of a token row: word + type + pos (the fp32 sum every embed kernel starts from)
+template <int V>
+__device__ __forceinline__ void sum_vec(const float* wrow, const float* trow, const float* prow, int cv, float* x) {
+    load_row<V>(wrow + cv * V, x);
+    if (trow) add_row<V>(trow + cv * V, x);
+    if (prow) add_row<V>(prow + cv * V, x);
+}
+
 template <int LANES>
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
@@ -86,11 +98,8 @@ __global__ __launch_bounds__(kEmbBlock) void embed_ln_kernel(const EmbedArgs a, 
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         const int cv = j * LANES + lane;
-        if (live && cv < cvn) {
-            load_row<V>(wrow + cv * V, x[j]);
-            if (trow) add_row<V>(trow + cv * V, x[j]);
-            if (prow) add_row<V>(prow + cv * V, x[j]);
-        } else {
+        if (live && cv < cvn) sum_vec<V>(wrow, trow, prow, cv, x[j]);
+        else {
 #pragma unroll
             for (int v = 0; v < V; ++v) x[j][v] = 0.f;
         }
@@ -161,6 +170,45 @@ __global__ __launch_bounds__(kEmbBlock) void embed_ln_generic_kernel(const Embed
     }
 }
 
+// rows = N * L token rows; cvn = D / V output vectors per row, lane l of a group writes the vectors l, l + LANES, ...; row r is written at r * a.out.sw
+template <typename T, int LANES>
+__global__ __launch_bounds__(kEmbBlock) void embed_sum_kernel(const EmbedArgs a, const int64_t rows, const int cvn) {
+    constexpr int V = 16 / int(sizeof(T));
+    const int lane = int(threadIdx.x) % LANES;
+    const int64_t r = (int64_t(blockIdx.x) * kEmbBlock + threadIdx.x) / LANES;
+    if (r >= rows) return;                         // (no shuffle and no barrier below)
+    const int D = a.out.c;
+    const float* wrow = a.word + table_row(a.ids[r], a.vocab) * D;
+    const float* trow = a.type ? a.type + table_row(a.tids[r], a.types) * D : nullptr;
+    const float* prow = a.pos ? a.pos + (r % a.out.w) * D : nullptr;
+    T* out = reinterpret_cast<T*>(a.out.p) + r * a.out.sw;
+    for (int cv = lane; cv < cvn; cv += LANES) {
+        float x[V];
+        sum_vec<V>(wrow, trow, prow, cv, x);
+        store_vec(out + cv * V, x);
+    }
+}
+
+// one wave per token row (kEmbBlock / 64 rows per workgroup)
+__global__ __launch_bounds__(kEmbBlock) void embed_sum_generic_kernel(const EmbedArgs a, const int64_t rows) {
+    const int lane = int(threadIdx.x) % 64;
+    const int64_t row = int64_t(blockIdx.x) * (kEmbBlock / 64) + threadIdx.x / 64;
+    if (row >= rows) return;                       // wave-uniform
+    const int D = a.out.c;
+    const float* wrow = a.word + table_row(a.ids[row], a.vocab) * D;
+    const float* trow = a.type ? a.type + table_row(a.tids[row], a.types) * D : nullptr;
+    const float* prow = a.pos ? a.pos + (row % a.out.w) * D : nullptr;
+    const int64_t ob = (row / a.out.w) * a.out.sn + (row % a.out.w) * a.out.sw;
+    for (int c = lane; c < D; c += 64) {
+        float o = wrow[c];
+        if (trow) o += trow[c];
+        if (prow) o += prow[c];
+        const int64_t oi = ob + int64_t(c) * a.out.sc;
+        if (a.out.f16) reinterpret_cast<_Float16*>(a.out.p)[oi] = _Float16(o);
+        else a.out.p[oi] = o;
+    }
+}
+
 template <typename T, int LANES, int NV>
 hipError_t launch_nv(const EmbedArgs& a, int64_t rows, int cvn, hipStream_t stream) {
     const int64_t blocks = (rows * LANES + kEmbBlock - 1) / kEmbBlock;
@@ -171,6 +219,12 @@ hipError_t launch_nv(const EmbedArgs& a, int64_t rows, int cvn, hipStream_t stre
 
 template <typename T, int LANES>
 hipError_t launch_lanes(const EmbedArgs& a, int64_t rows, int cvn, hipStream_t stream) {
+    if (!a.gamma) {
+        const int64_t blocks = (rows * LANES + kEmbBlock - 1) / kEmbBlock;
+        if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+        embed_sum_kernel<T, LANES><<<dim3(unsigned(blocks)), dim3(kEmbBlock), 0, stream>>>(a, rows, cvn);
+        return hipGetLastError();
+    }
     const int nv = (cvn + LANES - 1) / LANES;
     if (nv <= 1) return launch_nv<T, LANES, 1>(a, rows, cvn, stream);
     if (nv <= 2) return launch_nv<T, LANES, 2>(a, rows, cvn, stream);
@@ -195,13 +249,13 @@ bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0;
 }  // namespace
 
 bool EmbedEligible(const EmbedArgs& a, int tile) {
-    if (tile < 0 || tile >= kNumEmbedTiles || !a.ids || !a.word || !a.gamma || !a.out.p || a.vocab < 1) return false;
+    if (tile < 0 || tile >= kNumEmbedTiles || !a.ids || !a.word || (!a.gamma && a.beta) || !a.out.p || a.vocab < 1) return false;
     if ((a.type != nullptr) != (a.tids != nullptr) || (a.type && a.types < 1)) return false;
     if (a.out.f8 || a.out.c < 1 || a.out.h != 1 || a.out.w < 1 || a.out.n < 0 || a.out.sn != int64_t(a.out.w) * a.out.sw) return false;
     if (tile == 0) return true;
     // (the offset is in the base pointer: its alignment stands for the offset condition)
     return a.out.sc == 1 && EmbedTileFits(a.out.c, a.out.f16 != 0, a.out.sw, 0, tile) && aligned16(a.out.p) && aligned16(a.word) && (!a.type || aligned16(a.type)) &&
-           (!a.pos || aligned16(a.pos)) && aligned16(a.gamma) && (!a.beta || aligned16(a.beta));
+           (!a.pos || aligned16(a.pos)) && (!a.gamma || aligned16(a.gamma)) && (!a.beta || aligned16(a.beta));
 }
 
 hipError_t LaunchEmbed(const EmbedArgs& a, int tile, hipStream_t stream) {
@@ -211,7 +265,8 @@ hipError_t LaunchEmbed(const EmbedArgs& a, int tile, hipStream_t stream) {
     if (tile == 0) {
         const int64_t blocks = (rows + kEmbBlock / 64 - 1) / (kEmbBlock / 64);
         if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(embed_ln_generic_kernel, dim3(unsigned(blocks)), dim3(kEmbBlock), 0, stream, a, rows);
+        if (a.gamma) hipLaunchKernelGGL(embed_ln_generic_kernel, dim3(unsigned(blocks)), dim3(kEmbBlock), 0, stream, a, rows);
+        else hipLaunchKernelGGL(embed_sum_generic_kernel, dim3(unsigned(blocks)), dim3(kEmbBlock), 0, stream, a, rows);
         return hipGetLastError();
     }
     return a.out.f16 ? launch_fast<_Float16>(a, tile, rows, stream) : launch_fast<float>(a, tile, rows, stream);

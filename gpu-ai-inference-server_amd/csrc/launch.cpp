@@ -87,6 +87,7 @@ AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s) {
         a.mask_sn = s.in2.pitch;
         a.mask_value = s.mask_value;
     }
+    a.causal = s.causal ? 1 : 0;
     return a;
 }
 
@@ -664,14 +665,16 @@ std::string kernel_label(const Step& s) {
             return s.tile == 0 ? std::string("groupnorm_generic_kernel")
                                : "groupnorm_stats_kernel<" + t + "> + groupnorm_apply_kernel<" + t + "," + acts[int(s.act.kind)] + ">";
         }
-        case StepKind::Embed:
-            return s.tile == 0 ? std::string("embed_ln_generic_kernel")
-                               : std::string("embed_ln_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
+        case StepKind::Embed: {
+            const std::string stem = s.bias_off >= 0 ? "embed_ln" : "embed_sum";       // (no gamma: the sum alone)
+            return s.tile == 0 ? stem + "_generic_kernel" : stem + "_kernel<" + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
+        }
         case StepKind::TokenAssemble: return std::string("token_assemble_kernel<") + (s.out.f16 ? "f16>" : "f32>");
         case StepKind::Attention:
             if (s.tile == 2) return std::string("attention_stream_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
-            return s.tile == 0 ? std::string(s.key_mask ? "attention_generic_kernel<mask>" : "attention_generic_kernel")
-                               : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.key_mask ? ",mask>" : ">");
+            if (s.tile == 3) return std::string("attention_chunk_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.causal ? ",causal>" : ">");
+            return s.tile == 0 ? std::string(s.key_mask ? "attention_generic_kernel<mask>" : s.causal ? "attention_generic_kernel<causal>" : "attention_generic_kernel")
+                               : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.key_mask ? ",mask>" : s.causal ? ",causal>" : ">");
         case StepKind::WindowAttention:
             return s.tile == 0 ? std::string("window_attention_generic_kernel")
                                : std::string("window_attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";

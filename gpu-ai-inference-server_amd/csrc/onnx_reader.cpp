@@ -133,6 +133,11 @@ OnnxTensor parse_tensor(Reader r) {
             if (has_raw) { need(raw.end - raw.p, 4); t.i.resize(n); for (int64_t k = 0; k < n; ++k) { int32_t v; std::memcpy(&v, raw.p + 4 * k, 4); t.i[k] = v; } }
             else { need(i32.size(), 1); t.i.resize(n); for (int64_t k = 0; k < n; ++k) t.i[k] = int32_t(i32[k]); }
             break;
+        case ONNX_BOOL:      // one byte per element (a causal mask's condition); kept as 0 / 1 in t.i
+            t.i.resize(n);
+            if (has_raw) { need(raw.end - raw.p, 1); for (int64_t k = 0; k < n; ++k) t.i[k] = raw.p[k] != 0; }
+            else { need(i32.size(), 1); for (int64_t k = 0; k < n; ++k) t.i[k] = i32[k] != 0; }
+            break;
         default:
             throw std::runtime_error("ONNX initializer " + t.name + ": unsupported data type " + std::to_string(t.dtype));
     }

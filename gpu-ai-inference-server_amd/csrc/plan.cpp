@@ -76,6 +76,7 @@ struct LNode {
     bool masked = false;
     bool key_mask = false;              // L_ATTENTION: in[1] = the int64 key mask [N, L]; the bias of a masked key is mask_value
     float mask_value = 0.f;
+    bool causal = false;                // L_ATTENTION: query i attends to the keys j <= i
     // L_EMBED: in = the int64 ids of the first table (and of the second); w = the first table [emb_vocab][D], w2 = the second [emb_types][D] (empty:
     // none), bias = the position rows [L][D] (empty: none), s / t / eps = gamma / beta / epsilon of the LayerNormalization behind the sum
     int64_t emb_vocab = 0, emb_types = 0;
@@ -401,7 +402,27 @@ struct Planner {
         // the key mask: the INT64 graph input behind the ext chain and its constant c
         std::string mask;
         float mask_value = 0.f;
+        // GPT-2's spelling: q, k and v are the three parts of Split(axis 2) of ONE Linear's result, which is the qkv layout itself (the Split is the head)
+        bool fused = false;
+        // the causal mask (a Where or an additive constant on the scores), checked element by element; causal_len = its L
+        bool causal = false;
+        int64_t causal_len = 0;
     };
+    // MatchCausalWhere / MatchCausalAdd: the two spellings of a causal mask on the scores (false / a refusal by name: not one)
+    void MatchCausalWhere(const OnnxNode& wh, const std::string& prefix, AttnMatch& am, std::vector<const OnnxNode*>& taken);
+    bool MatchCausalAdd(const OnnxTensor& mk, AttnMatch& am) const;
+    // MatchConv1D: HF's Conv1D on tokens, Reshape [-1, D] -> Gemm -> Reshape [N, L, Dout].  conv1d_view: the two Reshapes (false: the first, true: the
+    // second), which rename their input's token value; conv1d_gemm: the Gemms, which then read a token view like a MatMul does
+    std::map<const OnnxNode*, bool> conv1d_view;
+    std::set<const OnnxNode*> conv1d_gemm;
+    void MatchConv1D();
+    bool ImportConv1DView(const OnnxNode& on, bool second);
+    // MatchGeluTanh: gelu_new spelled out, 0.5 x (1 + Tanh(c (x + 0.044715 x^3))).  gelu_head: its last Mul -> x; gelu_skip: its other nodes
+    std::map<const OnnxNode*, std::string> gelu_head;
+    std::set<const OnnxNode*> gelu_skip;
+    void MatchGeluTanh();
+    bool FoldConstTranspose(const OnnxNode& on);
+    std::set<int> tok_outputs;                 // MarkOutputs: the graph outputs that are token values [N, L, D] (row-major in their NHWC buffer)
     // the ext chain of a key mask, matched once per name and shared by all layers: Unsqueeze(s) -> Cast FLOAT -> Sub(1, .) -> Mul(., c)
     struct KeyMask { bool ok = false; std::string input; float c = 0.f; std::vector<const OnnxNode*> nodes; int uses = 0; };
     std::map<std::string, KeyMask> key_masks;
@@ -477,7 +498,8 @@ struct Planner {
     void ImportPatchMerge(const OnnxNode& on, const std::string& src);
     // MatchEmbed: the token-embedding sums of a BERT-class export.  embed_head: the LayerNormalization behind a sum -> what ImportEmbed needs;
     // embed_skip: the Gathers, Adds and position-id nodes of the sums (they import nothing)
-    struct EmbedMatch { std::vector<std::string> ids; std::vector<const OnnxTensor*> tables; std::vector<float> pos; std::string names; };
+    // (sum_only: the head is the sum's last Add, not a LayerNormalization: a pre-LN model, whose sum has other readers)
+    struct EmbedMatch { std::vector<std::string> ids; std::vector<const OnnxTensor*> tables; std::vector<float> pos; std::string names; bool sum_only = false; };
     std::map<const OnnxNode*, EmbedMatch> embed_head;
     std::set<const OnnxNode*> embed_skip;
     void MatchEmbed();
@@ -943,6 +965,9 @@ void Planner::ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odi
     float beta = op == "Gemm" ? on.attr_f("beta", 1.f) : 1.f;
     int64_t K = transB ? b->dims[1] : b->dims[0], N = transB ? b->dims[0] : b->dims[1];
     if (K != X.c) fail(op + " " + n.name + ": inner dimensions do not match");
+    // (a vocabulary head: the conv kernels' eligibility keeps 32-bit kernels off spans of 2^31 bytes and more, and no kernel is checked beyond them)
+    if (tok && X.n * X.w * N * 4 >= (int64_t(1) << 31))
+        fail(op + " " + n.name + ": the result [" + std::to_string(X.n) + ", " + std::to_string(X.w) + ", " + std::to_string(N) + "] holds 2^31 bytes or more in fp32; no conv kernel runs on such a span (use a smaller batch)");
     n.kind = L_CONV;
     n.w.resize(size_t(N * K));
     for (int64_t o = 0; o < N; ++o)
@@ -1334,6 +1359,46 @@ void Planner::ImportLayerNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>
 
 // Transpose is a view of the NHWC storage, never a kernel: perm [0,2,3,1] of a 4-D value reads it channels-last, perm [0,3,1,2] of such a view
 // reads it as NCHW again.  The output becomes one more name of the input's value (no node, no step).  true: the node is done
+// Transpose(perm [1,0]) of a 2-D floating-point constant: a derived initializer (a tied vocabulary head reads the embedding table this way)
+bool Planner::FoldConstTranspose(const OnnxNode& on) {
+    if (on.op != "Transpose" || on.inputs.size() != 1) return false;
+    const OnnxTensor* t = L.init(on.inputs[0]);
+    const std::vector<int64_t> perm = on.attr_ints("perm", {1, 0});
+    if (!t || t->dims.size() != 2 || t->f.empty() || perm != std::vector<int64_t>{1, 0}) return false;
+    OnnxTensor o;
+    o.dtype = t->dtype;
+    o.name = on.outputs[0];
+    const int64_t R = t->dims[0], C = t->dims[1];
+    o.dims = {C, R};
+    o.f.resize(t->f.size());
+    for (int64_t r = 0; r < R; ++r)
+        for (int64_t c = 0; c < C; ++c) o.f[size_t(c * R + r)] = t->f[size_t(r * C + c)];
+    L.add_derived(std::move(o));
+    return true;
+}
+
+// The two Reshapes of a matched Conv1D (MatchConv1D) rename their input's token value: [N, L, D] -> [N L, D] in front of the Gemm, [N L, Dout] ->
+// [N, L, Dout] behind it.  false: the input is no token view or the shape is another one, and the node imports (or is refused) as before
+bool Planner::ImportConv1DView(const OnnxNode& on, bool second) {
+    if (!L.is_tok(on.inputs[0])) return false;
+    const int v = in_val(on, 0);
+    const Val& X = L.vals[v];
+    const OnnxTensor* shp = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
+    if (!shp) return false;
+    std::vector<int64_t> d = shp->i;
+    const std::vector<int64_t> idims = second ? std::vector<int64_t>{X.n * X.w, X.c} : std::vector<int64_t>{X.n, X.w, X.c};
+    int64_t known = 1, neg = -1;
+    for (size_t k = 0; k < d.size(); ++k) {
+        if (d[k] == 0 && k < idims.size()) d[k] = idims[k];
+        if (d[k] == -1) neg = int64_t(k); else known *= d[k];
+    }
+    if (neg >= 0 && known > 0) d[size_t(neg)] = X.n * X.w * X.c / known;
+    if (d != (second ? std::vector<int64_t>{X.n, X.w, X.c} : std::vector<int64_t>{X.n * X.w, X.c})) return false;
+    L.alias_name(on.outputs[0], v, false);
+    L.tok_names.insert(on.outputs[0]);
+    return true;
+}
+
 bool Planner::ImportTranspose(const OnnxNode& on, const LNode& n) {
     if (on.op != "Transpose") return false;
     if (!act_input(on, 0)) fail("Transpose " + n.name + ": constant input is not supported");
@@ -1389,6 +1454,22 @@ void Planner::ImportNode(const OnnxNode& on) {
     // a matched group norm: its last node imports the whole of it (ImportGroupNorm checks what its input may be: a flat name is one of them)
     if (gn_skip.count(&on)) return;
     if (const auto gh = gn_head.find(&on); gh != gn_head.end()) { ImportGroupNorm(on, gh->second); return; }
+    // gelu_new spelled out: its last Mul imports the whole of it as the Gelu(approximate = "tanh") node it is
+    if (gelu_skip.count(&on)) return;
+    if (const auto gh = gelu_head.find(&on); gh != gelu_head.end()) {
+        OnnxNode g;
+        g.op = "Gelu";
+        g.name = n.name;
+        g.inputs = {gh->second};
+        g.outputs = {on.outputs[0]};
+        OnnxAttr ap;
+        ap.name = "approximate";
+        ap.s = "tanh";
+        g.attrs["approximate"] = ap;
+        synth_nodes.push_back(std::move(g));
+        ImportNode(synth_nodes.back());
+        return;
+    }
     // a channels-last view may feed only the ops that read it as one: anything else (a Shape and the other folded ops included, hence before
     // the folds) would take its n / c / h / w for the ONNX dims
     static const std::set<std::string> cl_ops = {"LayerNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose"};
@@ -1399,7 +1480,8 @@ void Planner::ImportNode(const OnnxNode& on) {
     // token views likewise, and the two half-way names of their creation and of the way back
     static const std::set<std::string> tok_ops = {"LayerNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose", "Concat", "Gather", "Reshape"};
     for (const std::string& name : on.inputs) {
-        if (L.is_tok(name) && !tok_ops.count(op))
+        // (a Conv1D's Gemm reads its token view like a MatMul; the Split of a GPT-2 attention is its head; a Pow is no operator of the planner at all, whatever it reads)
+        if (L.is_tok(name) && !tok_ops.count(op) && !(op == "Gemm" && conv1d_gemm.count(&on)) && !attn_head.count(&on) && op != "Pow")
             fail(op + " " + n.name + ": input " + name + " is a token view [N, L, D]; only LayerNormalization, MatMul, Add, Mul, Div, Erf, Gelu, Transpose, Concat, "
                  "Gather and the Reshape of the attention pattern may read one");
         if (L.flat_names.count(name) && op != "Transpose")
@@ -1411,7 +1493,8 @@ void Planner::ImportNode(const OnnxNode& on) {
     if (const auto eh = embed_head.find(&on); eh != embed_head.end()) { ImportEmbed(on, eh->second); return; }
     if (attn_skip.count(&on)) return;                      // inside a matched attention subgraph: its head node imports the whole of it
     if (const auto am = attn_head.find(&on); am != attn_head.end()) { ImportAttention(on, am->second); return; }
-    if (FoldShapeArithmetic(on, n) || FoldShapeOnlyOp(on, n) || FoldExpand(on, n) || ImportTranspose(on, n) || ImportTokenView(on, n)) return;
+    if (const auto cv = conv1d_view.find(&on); cv != conv1d_view.end() && ImportConv1DView(on, cv->second)) return;
+    if (FoldShapeArithmetic(on, n) || FoldShapeOnlyOp(on, n) || FoldExpand(on, n) || FoldConstTranspose(on) || ImportTranspose(on, n) || ImportTokenView(on, n)) return;
     std::vector<int64_t> odims;
     cl_out = tok_out = false;
     if (op == "Conv") ImportConv(on, n, odims);
@@ -1602,24 +1685,60 @@ void Planner::MatchAttention() {
         for (const OnnxNode& on : m.nodes)
             if (on.op == "MatMul" && on.inputs.size() == 2 && on.inputs[0] == sm.outputs[0] && !gi.cst(on.inputs[1])) pv = &on;
         if (!pv) continue;
-        const OnnxNode* top = gi.producer(gi.peel_quiet(sm.inputs[0]));
-        std::string scores = sm.inputs[0];
         AttnMatch am;
+        std::vector<const OnnxNode*> causal_nodes;
+        // a causal mask as Where(cond, scores, c), directly in front of the Softmax or of the key-mask Add (GPT-2 writes the Where first)
+        auto causal_where = [&](const std::string& name) -> const OnnxNode* {
+            const OnnxNode* p = gi.producer(name);
+            return p && p->op == "Where" && p->inputs.size() == 3 && gi.act_matmul(gi.producer(gi.peel_quiet(p->inputs[1]))) ? p : nullptr;
+        };
+        // the scaled product of two activations, also behind a causal Where
+        auto is_scores = [&](const std::string& name) {
+            const std::string cur = gi.peel_quiet(name);
+            return gi.act_matmul(gi.producer(cur)) || causal_where(cur) != nullptr;
+        };
+        const std::string both = "a causal mask together with a key mask (attention_mask) on the scores is not supported";
+        std::string sm_in = sm.inputs[0];          // the name the scores reach the Softmax (or the causal Where in front of it) under
+        if (const OnnxNode* wh = causal_where(sm_in)) {
+            MatchCausalWhere(*wh, prefix, am, causal_nodes);
+            sm_in = wh->inputs[1];
+        }
+        const OnnxNode* top = gi.producer(gi.peel_quiet(sm_in));
+        std::string scores = sm_in;
         const OnnxNode* mask_add = nullptr;
-        if (top && top->op == "Add" && top->inputs.size() == 2 &&
-            (gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[0]))) || gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[1]))))) {
-            // only the key mask of an INT64 graph input [N, L], broadcast as [N, 1, 1, L], directly in front of the Softmax
-            const int si = gi.act_matmul(gi.producer(gi.peel_quiet(top->inputs[0]))) ? 0 : 1;
-            const KeyMask* km = top->outputs[0] == sm.inputs[0] ? &MatchKeyMask(top->inputs[size_t(1 - si)]) : nullptr;
-            if (!km || !km->ok) fail(prefix + "an additive mask (Add " + (top->name.empty() ? top->outputs[0] : top->name) + ") on the scores is not supported");
-            am.mask = km->input;
-            am.mask_value = km->c;
-            ++key_masks[top->inputs[size_t(1 - si)]].uses;
-            mask_add = top;
+        if (top && top->op == "Add" && top->inputs.size() == 2 && (is_scores(top->inputs[0]) || is_scores(top->inputs[1]))) {
+            const int si = is_scores(top->inputs[0]) ? 0 : 1;
+            const std::string tname = top->name.empty() ? top->outputs[0] : top->name;
+            const OnnxTensor* mk = gi.cst(top->inputs[size_t(1 - si)]);
+            if (top->outputs[0] == sm_in && !am.causal && mk && MatchCausalAdd(*mk, am)) {
+                // the causal mask as an additive constant: 0 on and below the diagonal, one value <= -1e30 above it
+                causal_nodes.push_back(top);
+            } else {
+                // only the key mask of an INT64 graph input [N, L], broadcast as [N, 1, 1, L], directly in front of the Softmax
+                const KeyMask* km = top->outputs[0] == sm_in ? &MatchKeyMask(top->inputs[size_t(1 - si)]) : nullptr;
+                if (km && km->ok && am.causal) fail(prefix + both + " (Add " + tname + ")");
+                if (!km || !km->ok) fail(prefix + "an additive mask (Add " + tname + ") on the scores is not supported");
+                am.mask = km->input;
+                am.mask_value = km->c;
+                ++key_masks[top->inputs[size_t(1 - si)]].uses;
+                mask_add = top;
+            }
             scores = top->inputs[size_t(si)];
+            // one mask only: whatever masks the scores below this Add makes two
+            if (causal_where(gi.peel_quiet(scores))) fail(prefix + both + " (Where " + causal_where(gi.peel_quiet(scores))->outputs[0] + " below Add " + tname + ")");
             top = gi.producer(gi.peel_quiet(scores));
+            if (top && top->op == "Add" && top->inputs.size() == 2 && (is_scores(top->inputs[0]) || is_scores(top->inputs[1]))) {
+                bool two = am.causal;
+                AttnMatch probe;
+                for (const std::string& o : top->inputs) if (const OnnxTensor* c2 = gi.cst(o); c2 && MatchCausalAdd(*c2, probe)) two = true;
+                if (two) fail(prefix + both + " (Add " + (top->name.empty() ? top->outputs[0] : top->name) + " below Add " + tname + ")");
+            }
         }
         if (!gi.act_matmul(top)) continue;
+        for (const OnnxNode* p : causal_nodes) {
+            if (p->op != "Slice" && gi.nreaders(p->outputs[0]) != 1) fail(prefix + "the masked scores " + p->outputs[0] + " have " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
+            attn_skip.insert(p);
+        }
         if (mask_add && gi.nreaders(mask_add->outputs[0]) != 1) fail(prefix + "the scores " + mask_add->outputs[0] + " have " + std::to_string(gi.nreaders(mask_add->outputs[0])) + " readers, not 1");
         if (mask_add) attn_skip.insert(mask_add);
         {
@@ -1697,6 +1816,176 @@ const Planner::KeyMask& Planner::MatchKeyMask(const std::string& name) {
     return km;
 }
 
+// Where(cond, scores, c) on the scores: cond a BOOL constant [1, 1, L, L], or one or two Slices with constant indices of a [1, 1, P, P] one (GPT-2's
+// `bias` buffer), exactly j <= i after slicing; c a scalar constant <= -1e30.  At such a value exp(c - max) is exactly 0 in fp32 and in float64 for
+// every score an fp32 graph can produce: leaving the masked keys out approximates nothing.  Anything else is refused naming the Where and the rule
+void Planner::MatchCausalWhere(const OnnxNode& wh, const std::string& prefix, AttnMatch& am, std::vector<const OnnxNode*>& taken) {
+    const std::string nm = wh.name.empty() ? wh.outputs[0] : wh.name;
+    auto miss = [&](const std::string& what) { fail(prefix + "Where " + nm + ": " + what); };
+    std::vector<const OnnxNode*> slices;
+    std::string cur = wh.inputs[0];
+    for (const OnnxNode* p = gi.producer(cur); p && p->op == "Slice" && !p->inputs.empty() && slices.size() < 2; p = gi.producer(cur)) {
+        slices.push_back(p);
+        cur = p->inputs[0];
+    }
+    const OnnxTensor* base = gi.cst(cur);
+    if (!base || base->dtype != ONNX_BOOL || base->dims.size() != 4 || base->dims[0] != 1 || base->dims[1] != 1 || base->dims[2] != base->dims[3])
+        miss("its condition " + wh.inputs[0] + " is not a BOOL constant [1, 1, L, L], nor one or two constant Slices of a [1, 1, P, P] one");
+    std::vector<int64_t> dims = base->dims, v = base->i;
+    for (size_t k = slices.size(); k-- > 0;) {
+        const OnnxNode* sl = slices[k];
+        const std::string snm = sl->name.empty() ? sl->outputs[0] : sl->name;
+        auto ints = [&](size_t i, std::vector<int64_t>& out) {
+            if (i >= sl->inputs.size() || sl->inputs[i].empty()) return false;
+            const OnnxTensor* t = gi.cst(sl->inputs[i]);
+            if (!t || t->i.empty()) miss("the indices of Slice " + snm + " in front of its condition are not constants");
+            out = t->i;
+            return true;
+        };
+        std::vector<int64_t> st, en, ax, stp;
+        if (!ints(1, st) || !ints(2, en) || st.size() != en.size()) miss("the indices of Slice " + snm + " in front of its condition are not constants");
+        if (!ints(3, ax)) for (size_t a = 0; a < st.size(); ++a) ax.push_back(int64_t(a));
+        if (!ints(4, stp)) stp.assign(st.size(), 1);
+        if (ax.size() != st.size() || stp.size() != st.size()) miss("Slice " + snm + ": starts, ends, axes and steps differ in length");
+        for (size_t a = 0; a < ax.size(); ++a) {
+            const int64_t axis = ax[a] < 0 ? ax[a] + 4 : ax[a];
+            if (axis < 0 || axis > 3 || stp[a] != 1) miss("Slice " + snm + ": only step 1 along the axes of the [1, 1, P, P] condition is supported");
+            const int64_t P = dims[size_t(axis)];
+            const int64_t b = std::clamp<int64_t>(st[a] < 0 ? st[a] + P : st[a], 0, P), e = std::clamp<int64_t>(en[a] < 0 ? en[a] + P : en[a], b, P);
+            int64_t outer = 1, inner = 1;
+            for (int64_t d = 0; d < axis; ++d) outer *= dims[size_t(d)];
+            for (int64_t d = axis + 1; d < 4; ++d) inner *= dims[size_t(d)];
+            std::vector<int64_t> w;
+            w.reserve(size_t(outer * (e - b) * inner));
+            for (int64_t o = 0; o < outer; ++o) w.insert(w.end(), v.begin() + (o * P + b) * inner, v.begin() + (o * P + e) * inner);
+            v = std::move(w);
+            dims[size_t(axis)] = e - b;
+        }
+        taken.push_back(sl);
+    }
+    if (dims[0] != 1 || dims[1] != 1 || dims[2] != dims[3] || dims[2] < 1) miss("its condition is [" + std::to_string(dims[0]) + ", " + std::to_string(dims[1]) + ", " + std::to_string(dims[2]) + ", " + std::to_string(dims[3]) + "] after slicing, not [1, 1, L, L]");
+    const int64_t Lq = dims[2];
+    for (int64_t i = 0; i < Lq; ++i)
+        for (int64_t j = 0; j < Lq; ++j)
+            if ((v[size_t(i * Lq + j)] != 0) != (j <= i))
+                miss("its condition is not the causal mask j <= i: element [" + std::to_string(i) + ", " + std::to_string(j) + "] is " + (v[size_t(i * Lq + j)] ? "true" : "false"));
+    const OnnxTensor* c = gi.cst(wh.inputs[2]);
+    if (!c || c->numel() != 1 || c->f.size() != 1) miss("the value " + wh.inputs[2] + " of the masked scores is not a scalar floating-point constant");
+    if (!(c->f[0] <= -1e30f)) miss("the value " + std::to_string(c->f[0]) + " of the masked scores is above -1e30: the masked keys keep a probability, and the kernels leave them out");
+    am.causal = true;
+    am.causal_len = Lq;
+    taken.push_back(&wh);
+}
+
+// Add(scores, M): M a floating-point constant [1, 1, L, L], 0 where j <= i and ONE value, -inf or <= -1e30, above the diagonal (HF's additive masks
+// hold finfo.min): s + M is M there for every score an fp32 graph can produce, the masked keys' probabilities are exactly 0.  false: not such a mask
+bool Planner::MatchCausalAdd(const OnnxTensor& mk, AttnMatch& am) const {
+    if (mk.f.empty() || mk.dims.size() != 4 || mk.dims[0] != 1 || mk.dims[1] != 1 || mk.dims[2] != mk.dims[3] || mk.dims[2] < 1) return false;
+    const int64_t Lq = mk.dims[2];
+    const float fill = Lq > 1 ? mk.f[1] : 0.f;
+    if (Lq > 1 && !(fill <= -1e30f)) return false;
+    for (int64_t i = 0; i < Lq; ++i)
+        for (int64_t j = 0; j < Lq; ++j)
+            if (mk.f[size_t(i * Lq + j)] != (j <= i ? 0.f : fill)) return false;
+    am.causal = true;
+    am.causal_len = Lq;
+    return true;
+}
+
+// HF's Conv1D on a token value: Reshape(t, [-1, D] | [N L, D]) -> Gemm(., W [D, Dout], b; alpha = beta = 1, no transposes) -> Reshape(., [N, L, Dout]).
+// Matched on the structure and the reader counts; the shapes are checked at the import, where t's are known (ImportConv1DView).  The Gemm is then the
+// 1x1 conv a MatMul + Add on the token value gives, and the two Reshapes cost nothing.  Any other Reshape of a token value keeps its refusal
+void Planner::MatchConv1D() {
+    bool any = false;
+    for (const OnnxNode& on : m.nodes) any = any || on.op == "Gemm";
+    if (!any) return;
+    IndexGraph();
+    for (const OnnxNode& g : m.nodes) {
+        if (g.op != "Gemm" || g.inputs.size() < 2 || g.outputs.size() != 1 || gi.cst(g.inputs[0]) || !gi.cst(g.inputs[1])) continue;
+        if (g.attr_i("transA", 0) != 0 || g.attr_i("transB", 0) != 0 || g.attr_f("alpha", 1.f) != 1.f || g.attr_f("beta", 1.f) != 1.f) continue;
+        const OnnxNode* r1 = gi.producer(g.inputs[0]);
+        const OnnxNode* r2 = gi.only_reader(g.outputs[0]);
+        auto shape_rank = [&](const OnnxNode* r) -> size_t {
+            const OnnxTensor* t = r && r->op == "Reshape" && r->inputs.size() == 2 ? gi.cst(r->inputs[1]) : nullptr;
+            return t ? t->i.size() : 0;
+        };
+        if (shape_rank(r1) != 2 || shape_rank(r2) != 3 || r2->inputs[0] != g.outputs[0] || gi.nreaders(r1->outputs[0]) != 1 || gi.cst(r1->inputs[0])) continue;
+        conv1d_view[r1] = false;
+        conv1d_view[r2] = true;
+        conv1d_gemm.insert(&g);
+    }
+}
+
+// gelu_new as torch spells it: 0.5 * x * (1 + Tanh(sqrt(2 / pi) * (x + 0.044715 * Pow(x, 3)))), every operand order, Mul(x, Mul(x, x)) in place of the
+// Pow, the constants to 1e-6 relative (as the Erf pattern's).  It is the activation Gelu(approximate = "tanh") names.  Every intermediate is read once;
+// a near miss is no match and its nodes import (or are refused: a left-over Pow is an unsupported operator) one by one
+void Planner::MatchGeluTanh() {
+    bool any = false;
+    for (const OnnxNode& on : m.nodes) any = any || on.op == "Tanh";
+    if (!any) return;
+    IndexGraph();
+    auto near = [&](const std::string& name, double want) {
+        const OnnxTensor* t = gi.cst(name);
+        if (!t || t->numel() != 1) return false;
+        const double v = t->f.size() == 1 ? double(t->f[0]) : (t->i.size() == 1 ? double(t->i[0]) : want + 1.0);
+        return std::fabs(v - want) <= 1e-6 * std::fabs(want);
+    };
+    // Mul / Add of a constant near c and something else: the something else's name (empty: not that)
+    auto with_const = [&](const OnnxNode* p, const char* op, double c) -> std::string {
+        if (!p || p->op != op || p->inputs.size() != 2 || gi.nreaders(p->outputs[0]) != 1) return "";
+        if (near(p->inputs[0], c) && !gi.cst(p->inputs[1])) return p->inputs[1];
+        if (near(p->inputs[1], c) && !gi.cst(p->inputs[0])) return p->inputs[0];
+        return "";
+    };
+    for (const OnnxNode& th : m.nodes) {
+        if (th.op != "Tanh" || th.inputs.size() != 1 || gi.nreaders(th.outputs[0]) != 1) continue;
+        std::vector<const OnnxNode*> taken = {&th};
+        const OnnxNode* m1 = gi.producer(th.inputs[0]);                    // c1 * (x + c2 x^3)
+        const std::string inner = with_const(m1, "Mul", 0.7978845608028654);
+        const OnnxNode* ad = inner.empty() ? nullptr : gi.producer(inner);
+        if (!ad || ad->op != "Add" || ad->inputs.size() != 2 || gi.nreaders(ad->outputs[0]) != 1) continue;
+        taken.insert(taken.end(), {m1, ad});
+        std::string x;
+        bool ok = false;
+        for (int side = 0; side < 2 && !ok; ++side) {
+            x = ad->inputs[size_t(side)];
+            const OnnxNode* m2 = gi.producer(ad->inputs[size_t(1 - side)]);  // c2 * x^3
+            const std::string cube = with_const(m2, "Mul", 0.044715);
+            const OnnxNode* cb = cube.empty() ? nullptr : gi.producer(cube);
+            if (!cb || cb->inputs.size() != 2 || gi.nreaders(cb->outputs[0]) != 1 || gi.cst(x)) continue;
+            if (cb->op == "Pow" && cb->inputs[0] == x && near(cb->inputs[1], 3.0)) { taken.insert(taken.end(), {m2, cb}); ok = true; }
+            else if (cb->op == "Mul") {
+                for (int s2 = 0; s2 < 2 && !ok; ++s2) {
+                    const OnnxNode* sq = gi.producer(cb->inputs[size_t(1 - s2)]);
+                    if (cb->inputs[size_t(s2)] == x && sq && sq->op == "Mul" && sq->inputs.size() == 2 && sq->inputs[0] == x && sq->inputs[1] == x && gi.nreaders(sq->outputs[0]) == 1) {
+                        taken.insert(taken.end(), {m2, cb, sq});
+                        ok = true;
+                    }
+                }
+            }
+        }
+        if (!ok) continue;
+        // behind the Tanh: 1 + tanh, then the product with x and 0.5 in any association
+        const OnnxNode* a1 = gi.only_reader(th.outputs[0]);
+        if (with_const(a1, "Add", 1.0) != th.outputs[0]) continue;
+        taken.push_back(a1);
+        const OnnxNode* p1 = gi.only_reader(a1->outputs[0]);
+        if (!p1 || p1->op != "Mul" || p1->inputs.size() != 2) continue;
+        const std::string o1 = p1->inputs[p1->inputs[0] == a1->outputs[0] ? 1 : 0];
+        const OnnxNode* head = nullptr;
+        if (const OnnxNode* hx = gi.producer(o1); with_const(hx, "Mul", 0.5) == x) { taken.push_back(hx); head = p1; }      // (0.5 x) (1 + t)
+        else {
+            const OnnxNode* p2 = gi.only_reader(p1->outputs[0]);
+            if (!p2 || p2->op != "Mul" || p2->inputs.size() != 2) continue;
+            const std::string o2 = p2->inputs[p2->inputs[0] == p1->outputs[0] ? 1 : 0];
+            if ((o1 == x && near(o2, 0.5)) || (near(o1, 0.5) && o2 == x)) { taken.push_back(p1); head = p2; }               // ((1 + t) x) 0.5, ((1 + t) 0.5) x
+        }
+        if (!head) continue;
+        for (const OnnxNode* p : taken) gelu_skip.insert(p);
+        gelu_head[head] = x;
+    }
+}
+
 // The separate q / k / v spelling (BERT's eager attention):
 //   q, k, v = Transpose(Reshape(MatMul(x, W*) + b*, [N, L, H, hd]), [0,2,1,3]);  kT = Transpose(k, [0,1,3,2]) (or the single Transpose [0,2,3,1] of the Reshape)
 //   MatMul(q, kT) [* c | / c] -> [+ mask] -> Softmax -> MatMul(., v) -> Transpose [0,2,1,3] -> Reshape [N, L, D]
@@ -1740,7 +2029,32 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
     const OnnxNode *mm[3], *add[3];
     const OnnxTensor *W[3], *B[3];
     std::vector<int64_t> shape4;
-    for (int s = 0; s < 3; ++s) {
+    // GPT-2: q, k, v = the three parts of Split(axis 2, [D, D, D]) of one c_attn Linear (the exporter omits `split` when the parts are equal): the
+    // Split's input is the qkv layout itself, and the Split is the head
+    const OnnxNode* sp = rs[0] && !rs[0]->inputs.empty() ? gi.producer(rs[0]->inputs[0]) : nullptr;
+    const bool fused = sp && sp->op == "Split" && sp->outputs.size() == 3 && rs[1] && rs[2] && rs[0]->op == "Reshape" && rs[1]->op == "Reshape" && rs[2]->op == "Reshape";
+    if (fused) {
+        for (int s = 0; s < 3; ++s) {
+            const OnnxTensor* s4 = rs[s]->inputs.size() == 2 ? gi.cst(rs[s]->inputs[1]) : nullptr;
+            if (!s4 || s4->i.size() != 4 || s4->i[2] <= 0 || s4->i[3] <= 0) miss(std::string(which[s]) + " is not Reshape(part " + std::to_string(s) + " of the Split, [N, L, H, hd]) with a constant shape");
+            if (s == 0) shape4 = s4->i;
+            else if (s4->i[2] != shape4[2] || s4->i[3] != shape4[3]) miss("the q / k / v Reshapes differ in heads or head size");
+            if (rs[s]->inputs[0] != sp->outputs[size_t(s)]) miss(std::string(which[s]) + " is not part " + std::to_string(s) + " of Split " + nm_of(sp) + " (q, k, v must be its outputs 0, 1, 2)");
+            for (const OnnxNode* p : {rs[s]})
+                if (gi.nreaders(p->outputs[0]) != 1 || gi.nreaders(p->inputs[0]) != 1) miss("the " + std::string(which[s]) + " part of Split " + nm_of(sp) + " or its Reshape has a second reader (only its own attention may read it)");
+            taken.push_back(rs[s]);
+        }
+        const int64_t D = shape4[2] * shape4[3], ax = sp->attr_i("axis", 0);
+        if (ax != 2 && ax != -1) miss("Split " + nm_of(sp) + " has axis = " + std::to_string(ax) + ", not 2 (the channel axis of [N, L, 3 D])");
+        std::vector<int64_t> parts = sp->attr_ints("split", {});
+        if (parts.empty() && sp->inputs.size() > 1 && !sp->inputs[1].empty()) {
+            const OnnxTensor* pt = gi.cst(sp->inputs[1]);
+            if (!pt) miss("the split sizes of Split " + nm_of(sp) + " are not constant");
+            parts = pt->i;
+        }
+        if (!parts.empty() && parts != std::vector<int64_t>{D, D, D}) miss("Split " + nm_of(sp) + " does not cut [H * hd, H * hd, H * hd] = three parts of " + std::to_string(D));
+    }
+    for (int s = 0; s < 3 && !fused; ++s) {
         const OnnxTensor* s4 = rs[s] && rs[s]->op == "Reshape" && rs[s]->inputs.size() == 2 ? gi.cst(rs[s]->inputs[1]) : nullptr;
         if (!s4 || s4->i.size() != 4 || s4->i[2] <= 0 || s4->i[3] <= 0) miss(std::string(which[s]) + " is not Reshape(Linear(x), [N, L, H, hd]) with a constant shape");
         if (s == 0) shape4 = s4->i;
@@ -1774,6 +2088,17 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
     for (const OnnxNode* p : taken)
         if ((p->op == "Mul" || p->op == "Div" || p->op == "Transpose") && gi.nreaders(p->outputs[0]) != 1) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
     taken.insert(taken.end(), {qk, qt, kt, vt, pv, ot, orr, &sm});
+    if (fused) {
+        head = sp;
+        am.fused = true;
+        am.name = nm_of(sp);
+        am.heads = shape4[2];
+        am.head_dim = shape4[3];
+        am.scale = scale;
+        am.out = orr->outputs[0];
+        am.shape3 = s3->i;
+        return true;
+    }
     // the merged Linear: column s D + h hd + e
     const int64_t Din = W[0]->dims[0], D = W[0]->dims[1];
     OnnxTensor w, b;
@@ -1925,7 +2250,7 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     const Val X = L.vals[x];
     const int64_t D = am.heads * am.head_dim;
     if (X.c != 3 * D) miss("the qkv rows have " + std::to_string(X.c) + " columns, not 3 * H * hd = " + std::to_string(3 * D));
-    if (!am.split && ((am.shape5[0] != 0 && am.shape5[0] != X.n) || (am.shape5[1] != -1 && am.shape5[1] != 0 && am.shape5[1] != X.w))) miss("the Reshape to [N, L, 3, H, hd] does not keep N and L");
+    if (!am.split && !am.fused && ((am.shape5[0] != 0 && am.shape5[0] != X.n) || (am.shape5[1] != -1 && am.shape5[1] != 0 && am.shape5[1] != X.w))) miss("the Reshape to [N, L, 3, H, hd] does not keep N and L");
     if ((am.shape3[0] != 0 && am.shape3[0] != X.n) || (am.shape3[1] != -1 && am.shape3[1] != 0 && am.shape3[1] != X.w) || (am.shape3[2] != -1 && am.shape3[2] != D))
         miss("the last Reshape is not to [N, L, H * hd]");
     if (am.shape3[1] == -1 && am.shape3[2] == -1) miss("the last Reshape is not to [N, L, H * hd]");
@@ -1943,6 +2268,10 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
         n.in.push_back(mv);
         n.key_mask = true;
         n.mask_value = am.mask_value;
+    }
+    if (am.causal) {
+        if (am.causal_len != X.w) miss("its causal mask is [1, 1, " + std::to_string(am.causal_len) + ", " + std::to_string(am.causal_len) + "], the sequence has " + std::to_string(X.w) + " tokens");
+        n.causal = true;
     }
     push_node(std::move(n), am.out, {X.n, D, 1, X.w}, true);
 }
@@ -2350,30 +2679,39 @@ void Planner::MatchEmbed() {
         // down to the LayerNormalization: Adds only, every value read once
         std::string cur = g.outputs[0];
         const OnnxNode* ln = nullptr;
+        // A sum that is not read by one LayerNormalization alone (a pre-LN model: GPT-2's is read by ln_1 and by the residual Add) becomes an embed step
+        // without the norm, headed by its last Add, where it is one table Gather plus position rows; any other such sum keeps `refusal`
+        std::string refusal;
         for (;;) {
             const OnnxNode* r = gi.only_reader(cur);
-            if (!r) fail("Gather " + gname + ": " + cur + " has " + std::to_string(gi.nreaders(cur)) + " readers; the sum of the embedding gathers is read by its LayerNormalization alone, every partial sum by the next Add alone");
-            if (r->op == "Add") { cur = r->outputs[0]; continue; }
-            if (r->op == "LayerNormalization" && r->inputs[0] == cur) { ln = r; break; }
-            fail(r->op + " " + (r->name.empty() ? r->outputs[0] : r->name) + ": reads the embedding sum " + cur + "; only Adds and then a LayerNormalization may (the embedding and its LayerNormalization run as one step)");
+            if (!r) refusal = "Gather " + gname + ": " + cur + " has " + std::to_string(gi.nreaders(cur)) + " readers; the sum of the embedding gathers is read by its LayerNormalization alone, every partial sum by the next Add alone";
+            else if (r->op == "Add") { cur = r->outputs[0]; continue; }
+            else if (r->op == "LayerNormalization" && r->inputs[0] == cur) { ln = r; break; }
+            else refusal = r->op + " " + (r->name.empty() ? r->outputs[0] : r->name) + ": reads the embedding sum " + cur + "; only Adds and then a LayerNormalization may (the embedding and its LayerNormalization run as one step)";
+            const OnnxNode* last = gi.producer(cur);
+            if (cur == g.outputs[0] || !last || last->op != "Add") fail(refusal);
+            ln = last;
+            break;
         }
         if (embed_head.count(ln)) continue;
         const std::string lname = ln->name.empty() ? ln->outputs[0] : ln->name;
         EmbedMatch em;
+        em.sum_only = !refusal.empty();
+        const std::string who = (em.sum_only ? "Add " : "LayerNormalization ") + lname;
         std::vector<const OnnxNode*> gathers, taken;
         int pos_count = 0;
         int64_t Lq = 0;
         for (size_t i = 0; i < m.inputs.size(); ++i) if (m.inputs[i].name == g.inputs[1]) Lq = input_shapes[i].size() == 2 ? input_shapes[i][1] : 0;
         auto add_pos = [&](const std::vector<float>& f, const std::vector<int64_t>& dims, const std::string& what) {
             const bool ok = (dims.size() == 3 && dims[0] == 1 && dims[1] == Lq) || (dims.size() == 2 && dims[0] == Lq);
-            if (!ok || f.empty()) fail("LayerNormalization " + lname + ": " + what + " of the embedding sum must be a floating-point constant [1, L, D] or [L, D] with L = " + std::to_string(Lq));
-            if (++pos_count > 1) fail("LayerNormalization " + lname + ": the embedding sum has more than one constant operand (" + what + ")");
+            if (!ok || f.empty()) fail(who + ": " + what + " of the embedding sum must be a floating-point constant [1, L, D] or [L, D] with L = " + std::to_string(Lq));
+            if (++pos_count > 1) fail(who + ": the embedding sum has more than one constant operand (" + what + ")");
             em.pos = f;
         };
         std::function<void(const std::string&)> walk = [&](const std::string& name) {
             const OnnxNode* p = gi.producer(name);
             if (p && p->op == "Add" && p->inputs.size() == 2 && !(gi.cst(p->inputs[0]) && gi.cst(p->inputs[1]))) {
-                if (gi.nreaders(name) != 1)
+                if (gi.nreaders(name) != 1 && !(em.sum_only && p == ln))
                     fail("Add " + (p->name.empty() ? name : p->name) + ": the embedding sum " + name + " has a second reader in front of its LayerNormalization");
                 taken.push_back(p);
                 walk(p->inputs[0]);
@@ -2381,7 +2719,7 @@ void Planner::MatchEmbed() {
                 return;
             }
             if (const OnnxTensor* c = gi.cst(name)) {
-                if (!float_const(name)) fail("LayerNormalization " + lname + ": the constant " + name + " of the embedding sum is not floating-point");
+                if (!float_const(name)) fail(who + ": the constant " + name + " of the embedding sum is not floating-point");
                 add_pos(c->f, c->dims, "the constant " + name);
                 return;
             }
@@ -2426,25 +2764,26 @@ void Planner::MatchEmbed() {
                     return;
                 }
             }
-            fail("LayerNormalization " + lname + ": the operand " + name + " of the embedding sum is neither the Gather of a table [V, D] by an INT64 graph input nor a constant [1, L, D] "
+            fail(who + ": the operand " + name + " of the embedding sum is neither the Gather of a table [V, D] by an INT64 graph input nor a constant [1, L, D] "
                  "(nor the Gather of a table by constant position ids)");
         };
-        walk(ln->inputs[0]);
+        walk(em.sum_only ? ln->outputs[0] : ln->inputs[0]);
+        if (em.sum_only && (gathers.size() != 1 || pos_count != 1)) fail(refusal);
         if (gathers.empty() || gathers.size() > 2)
-            fail("LayerNormalization " + lname + ": the embedding sum has " + std::to_string(gathers.size()) + " table Gathers by graph inputs (one or two are supported)");
+            fail(who + ": the embedding sum has " + std::to_string(gathers.size()) + " table Gathers by graph inputs (one or two are supported)");
         std::sort(gathers.begin(), gathers.end(), [&](const OnnxNode* a, const OnnxNode* b) { return input_index(a->inputs[1]) < input_index(b->inputs[1]); });
         if (gathers.size() == 2 && gathers[0]->inputs[1] == gathers[1]->inputs[1])
-            fail("LayerNormalization " + lname + ": both table Gathers of the embedding sum read " + gathers[0]->inputs[1] + " (two different INT64 graph inputs are expected)");
+            fail(who + ": both table Gathers of the embedding sum read " + gathers[0]->inputs[1] + " (two different INT64 graph inputs are expected)");
         for (const OnnxNode* t : gathers) {
             const OnnxTensor* tab = float_const(t->inputs[0]);
             if (tab->dims[1] != float_const(gathers[0]->inputs[0])->dims[1] || (pos_count && int64_t(em.pos.size()) != Lq * tab->dims[1]))
-                fail("LayerNormalization " + lname + ": the tables and the position rows of the embedding sum differ in width");
+                fail(who + ": the tables and the position rows of the embedding sum differ in width");
             em.ids.push_back(t->inputs[1]);
             em.tables.push_back(tab);
             em.names += (em.names.empty() ? "" : "+") + (t->name.empty() ? t->outputs[0] : t->name);
             embed_skip.insert(t);
         }
-        for (const OnnxNode* t : taken) embed_skip.insert(t);
+        for (const OnnxNode* t : taken) if (t != ln) embed_skip.insert(t);
         embed_head[ln] = std::move(em);
     }
     // whatever else reads an id input is refused by name
@@ -2466,6 +2805,16 @@ void Planner::ImportEmbed(const OnnxNode& on, const EmbedMatch& em) {
     for (int v : n.in)
         if (L.vals[v].dims != I.dims) fail("LayerNormalization " + n.name + ": the id inputs of the embedding sum differ in shape");
     const int64_t N = I.n, Lq = I.c, D = em.tables[0]->dims[1];
+    if (em.sum_only) {
+        // `on` is the sum's last Add: no norm behind it, the step writes the sum (gamma absent)
+        n.w = em.tables[0]->f;
+        n.emb_vocab = em.tables[0]->dims[0];
+        n.bias = em.pos;
+        if (n.emb_vocab < 1 || n.emb_vocab >= (int64_t(1) << 31) || D < 1 || D >= (int64_t(1) << 31)) fail("Add " + n.name + ": embedding table sizes out of range");
+        n.name = em.names + "+" + n.name;
+        push_node(std::move(n), on.outputs[0], {N, D, 1, Lq}, true);
+        return;
+    }
     const int64_t axis = on.attr_i("axis", -1);
     if (axis != -1 && axis != 2) fail("LayerNormalization " + n.name + ": axis = " + std::to_string(axis) + " on a token view is not supported (only the channel axis alone is normalised: the last axis of a channels-last view or of an [N, C] value)");
     if (on.attr_i("stash_type", 1) != 1) fail("LayerNormalization " + n.name + ": stash_type = " + std::to_string(on.attr_i("stash_type", 1)) + " is not supported (1 is)");
@@ -2690,7 +3039,23 @@ void Planner::FuseTokenAssemble() {
 void Planner::MarkOutputs() {
     for (const auto& vo : m.outputs) {
         int v = L.get_val(vo.name);
-        if (L.is_tok(vo.name) || L.flat_names.count(vo.name) || L.back_names.count(vo.name))
+        // A token value [N, L, D] is an output as it is where a decoder needs one: its NHWC buffer [N, 1, L, D] is that tensor row-major.  Two kinds
+        // are taken: the result of a Linear (the vocabulary head: a conv step writes the dense fp32 buffer itself in every precision, as a classifier's
+        // last Gemm does), and a value the graph also reads further (last_hidden_state under the head: copied, like every output that is read further).
+        // A token value that no Linear made and nothing else reads keeps the refusal (another producer would have to write fp32 out of an fp16
+        // plan: an attention step then leaves its MFMA tiles, which want one element type on both sides), and so do the half-way names of the token views
+        auto linear_result = [&](int x) {
+            const int p = L.vals[x].producer;
+            if (p < 0) return false;
+            const LNode& n = L.nodes[size_t(p)];
+            if (n.kind == L_CONV) return true;
+            // (the bias Add of a Linear, which FuseConvEpilogues folds into the conv in front of it)
+            const int q = n.kind == L_AFFINE && single_consumer(n.in[0]) ? L.vals[n.in[0]].producer : -1;
+            return q >= 0 && L.nodes[size_t(q)].kind == L_CONV;
+        };
+        const bool half_way = L.flat_names.count(vo.name) || L.back_names.count(vo.name);
+        if (L.is_tok(vo.name) && !half_way && (linear_result(v) || !L.consumers(v).empty())) tok_outputs.insert(v);
+        else if (L.is_tok(vo.name) || half_way)
             fail("graph output " + vo.name + " is a token view; outputs are NCHW: transpose it back with perm [0,2,1] and reshape it to [N, D, h, w]");
         if (L.is_cl(vo.name)) fail("graph output " + vo.name + " is a channels-last view (a Transpose with perm [0,2,3,1]); outputs are NCHW: transpose it back with perm [0,3,1,2]");
         L.vals[v].is_output = true;
@@ -3079,7 +3444,8 @@ void Planner::DensifyOutputs() {
         int v = L.get_val(vo.name);
         // Always materialise through a copy when the tensor is spatial (NHWC->NCHW) or is a graph input;
         // [N,C,1,1] / [N,C] tensors are already in ABI order and only need their own dense buffer.
-        bool spatial = L.vals[v].h * L.vals[v].w > 1;
+        const bool tok = tok_outputs.count(v) != 0;
+        bool spatial = L.vals[v].h * L.vals[v].w > 1 && !tok;      // (a token output stays [N, L, D] rows: no NCHW transposition)
         bool consumed = !L.consumers(v).empty();
         // a Resize whose result is read by nothing else writes the dense NCHW fp32 output itself (a segmentation head's last step)
         const int pr = L.vals[v].producer;
@@ -3089,7 +3455,8 @@ void Planner::DensifyOutputs() {
             out_vals.push_back(v);
             continue;
         }
-        if (spatial || L.vals[v].is_input || consumed || L.vals[v].sel_rows > 1) {
+        if (spatial || L.vals[v].is_input || consumed || L.vals[v].sel_rows > 1 ||
+            (tok && (std::find(out_vals.begin(), out_vals.end(), v) != out_vals.end() || L.vals[v].producer < 0 || L.nodes[size_t(L.vals[v].producer)].kind == L_ALIAS))) {
             LNode cp;
             cp.kind = L_COPY;
             cp.name = "to_output(" + L.vals[v].name + ")";
@@ -3097,6 +3464,7 @@ void Planner::DensifyOutputs() {
             cp.out = L.new_val(L.vals[v].name + "/out", L.vals[v].dims);
             L.vals[cp.out].is_output = true;
             L.vals[cp.out].input_nchw = spatial;   // reused flag: dense NCHW layout
+            if (tok) tok_outputs.insert(cp.out);
             L.vals[v].is_output = false;
             L.vals[cp.out].producer = int(L.nodes.size());
             L.nodes.push_back(cp);
@@ -3721,14 +4089,14 @@ void Planner::EmitEmbed(const LNode& n, Step& s) {
     s.w_off = push_vec(n.w);
     if (!n.w2.empty()) s.w2_off = push_vec(n.w2);
     if (!n.bias.empty()) s.emb_pos_off = push_vec(n.bias);
-    s.bias_off = push_vec(n.s);
+    if (!n.s.empty()) s.bias_off = push_vec(n.s);      // (empty: the sum without a LayerNormalization)
     if (!n.t.empty()) s.bias2_off = push_vec(n.t);
     s.ln_eps = n.eps;
     s.tile = EmbedDefaultTile(s.out.c, s.out.f16, s.out.pitch, s.out.c_off);
     const int t = ForcedTile(kNumEmbedTiles);
     if (t >= 0) s.tile = t == 0 || EmbedTileFits(s.out.c, s.out.f16, s.out.pitch, s.out.c_off, t) ? t : 0;
     const double rows = double(s.out.n) * double(s.out.w), D = double(s.out.c);
-    s.flops = 8.0 * rows * D;
+    s.flops = (n.s.empty() ? 2.0 : 8.0) * rows * D;
     // per token row: one fp32 row of every table and of the position rows, the ids, the result once
     s.bytes = rows * (4.0 * D * double(1 + (s.has_in2 ? 1 : 0) + (s.emb_pos_off >= 0 ? 1 : 0)) + 8.0 * double(s.has_in2 ? 2 : 1)) + vbytes(s.out);
 }
@@ -3744,8 +4112,9 @@ void Planner::EmitTokenAssemble(const LNode& n, Step& s) {
 }
 
 // attention: kernels.h AttnDefaultTile (tile 1, the MFMA kernel, where AttnMfmaFits says so; tile 2, the streaming kernel, on a wide head with
-// at least kAttnStreamMinTokens tokens; else the generic kernel).  IE_FORCE_TILE as for layer norm but over tiles 0 and 1 only; IE_ATTN_TILE
-// pins the attention steps alone, tile 2 included (an ineligible value is the generic kernel)
+// at least kAttnStreamMinTokens tokens; else the generic kernel).  A causal step: AttnCausalDefaultTile (tile 1, else tile 3, the chunk kernel, else
+// the generic kernel).  IE_FORCE_TILE as for layer norm but over tiles 0 and 1 only; IE_ATTN_TILE pins the attention steps alone, tiles 2 and 3
+// included (an ineligible value is the generic kernel); a non-causal step reaches tile 3 this way only
 void Planner::EmitAttention(const LNode& n, Step& s) {
     if (s.in.f8 || s.out.f8) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
     s.kind = StepKind::Attention;
@@ -3759,17 +4128,22 @@ void Planner::EmitAttention(const LNode& n, Step& s) {
         s.mask_value = n.mask_value;
         if (!s.in2.i64) fail("internal planner error: the key mask of node " + n.name + " is not an int64 view");
     }
+    s.causal = n.causal;
     const bool views = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16;
     auto fits = [&](int tile) {
         if (tile == 0) return true;
+        if (tile == 3) return views && AttnChunkFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask);
+        if (tile == 2 && n.causal) return false;       // (tile 2 has no causal form)
         return views && (tile == 1 ? AttnMfmaFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask)
                                    : AttnStreamFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask));
     };
     s.tile = views ? AttnDefaultTile(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask) : 0;
+    if (n.causal) s.tile = views ? AttnCausalDefaultTile(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off) : 0;
     int t = ForcedTile(kNumAttnForcedTiles);
     if (const char* e = env.get("IE_ATTN_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumAttnTiles) t = std::atoi(e);      // (the attention steps alone)
     if (t >= 0) s.tile = fits(t) ? t : 0;
     s.flops = 4.0 * double(s.in.n) * double(s.heads) * double(s.in.w) * double(s.in.w) * double(s.head_dim);
+    if (n.causal) s.flops = 2.0 * double(s.in.n) * double(s.heads) * double(s.in.w) * double(s.in.w + 1) * double(s.head_dim);      // the lower triangle: the work needed
     s.bytes = vbytes(s.in) + vbytes(s.out) + (n.key_mask ? vbytes(s.in2) : 0.0);
 }
 
@@ -4152,7 +4526,9 @@ void Planner::DescribeIo() {
         d.model_dims = m.outputs[i].dims;
         d.dims = L.vals[out_vals[i]].dims;
         d.view = view_of(out_vals[i]);
-        if (!d.view.nchw && (d.view.c_off != 0 || d.view.pitch != d.view.c || d.view.h * d.view.w != 1))
+        const bool tok = tok_outputs.count(out_vals[i]) != 0;      // [N, L, D]: the rows of the NHWC buffer [N, 1, L, D], dense when the pitch is D
+        if (tok) d.dims = {d.view.n, d.view.w, d.view.c};
+        if (!d.view.nchw && (d.view.c_off != 0 || d.view.pitch != d.view.c || (tok ? d.view.h != 1 : d.view.h * d.view.w != 1)))
             fail("internal planner error: output " + d.name + " is not dense");
         plan.outputs.push_back(d);
     }
@@ -4173,6 +4549,8 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
     P.MatchAttention();                                          // the unfused attention subgraphs, found on the ONNX nodes: each imports as one node
     P.MatchEmbed();                                              // table Gathers by INT64 graph inputs, their sum and the LayerNormalization behind it: one node
     P.MatchGroupNorm();                                          // the spellings of a group norm: one node
+    P.MatchConv1D();                                             // HF's Conv1D on tokens (Reshape -> Gemm -> Reshape): a Linear, the Reshapes are names
+    P.MatchGeluTanh();                                           // gelu_new spelled out with Pow and Tanh: the Gelu(approximate = "tanh") node
     for (const OnnxNode& on : m.nodes) P.ImportNode(on);
     P.MarkOutputs();
     if (f8) P.RefuseForF8();
@@ -4294,6 +4672,7 @@ std::string PlanToJson(const Plan& p) {
         if (s.kind == StepKind::Attention)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"tile\":" << s.tile;      // (attention steps only)
         if (s.kind == StepKind::Attention && s.key_mask) o << ",\"key_mask\":true,\"mask_value\":" << s.mask_value;      // (masked attention steps only)
+        if (s.kind == StepKind::Attention && s.causal) o << ",\"causal\":true";      // (causal attention steps only)
         if (s.kind == StepKind::WindowAttention)      // (window-attention steps only)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"window\":[" << s.win_h << "," << s.win_w << "],\"shift\":["
               << s.shift_h << "," << s.shift_w << "],\"masked\":" << (s.masked ? "true" : "false") << ",\"tile\":" << s.tile;
@@ -4301,7 +4680,7 @@ std::string PlanToJson(const Plan& p) {
         if (s.kind == StepKind::Embed) {      // (embed steps only)
             o << ",\"tables\":" << (s.w2_off >= 0 ? 2 : 1) << ",\"vocab\":[" << s.emb_vocab;
             if (s.w2_off >= 0) o << "," << s.emb_types;
-            o << "],\"ln\":true,\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile << ",\"w2_off\":" << s.w2_off << ",\"pos_off\":" << s.emb_pos_off
+            o << "],\"ln\":" << (s.bias_off >= 0 ? "true" : "false") << ",\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile << ",\"w2_off\":" << s.w2_off << ",\"pos_off\":" << s.emb_pos_off
               << ",\"bias2_off\":" << s.bias2_off;
         }
         if (!s.parts.empty()) {

@@ -137,6 +137,8 @@ struct Step {
     // Attention with a key mask (BERT): in2 (has_in2) = the int64 mask [N, L] graph input; key j of image n gets the bias (1 - mask[n, j]) * mask_value
     bool key_mask = false;
     float mask_value = 0.f;
+    // Causal attention (GPT-2): query i attends to the keys j <= i; the graph's mask constant was checked element by element at load and is not kept
+    bool causal = false;
     // WindowAttention (kernels_wattn.hip): in = the qkv map [N, H, W, 3 D], out = [N, H, W, D]; attention inside the win_h x win_w windows of the map
     // rolled by (-shift_h, -shift_w), every result on its query's own pixel; w_off = the relative-position bias, w2_off = the shift mask (masked
     // steps only), both packed as kernels.h WinAttnArgs describes, fp32 in every precision; heads, head_dim, attn_scale, tile as for Attention
@@ -146,6 +148,7 @@ struct Step {
     // Embed (kernels_embed.hip): in = the int64 ids [N, L] of the first table, in2 (has_in2) = the ids of the second; out = tokens [N, 1, L, D] =
     // LayerNorm(word[in] + type[in2] + pos[l]; gamma, beta, ln_eps); w_off = the first table [emb_vocab][D], w2_off = the second [emb_types][D] or -1,
     // emb_pos_off = the position rows [L][D] or -1, bias_off = gamma [D], bias2_off = beta [D] or -1, fp32 in every precision; tile as for LayerNorm
+    // bias_off = -1: no LayerNormalization behind the sum (a pre-LN model): out = the sum itself
     int64_t emb_vocab = 0, emb_types = 0, emb_pos_off = -1;
     // GroupNorm (kernels_gn.hip): out = act((in - mean_ng) * rsqrt(var_ng + ln_eps) * gamma + beta), the statistics over the in.c / gn_groups channels of
     // group g and every pixel of image n; w_off = gamma [C], bias_off = beta [C], fp32 in every precision; act = the fused SiLU / ReLU / Sigmoid; tile 0 =

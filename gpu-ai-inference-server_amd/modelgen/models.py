@@ -1,5 +1,5 @@
 """Synthetic ONNX model builders (DenseNet-121, ResNet-50, ResNeXt-50, MobileNetV2, MobileNetV3, EfficientNet-B0, RegNetX / RegNetY,
-FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT, Swin, BERT, GroupNorm ResNets, the diffusion VAE decoder and small test graphs).
+FCN-ResNet50, DeepLabV3-ResNet50, U-Net, ConvNeXt, ViT, Swin, BERT, GPT-2, GroupNorm ResNets, the diffusion VAE decoder and small test graphs).
 
 The reference's `models/densenet_onnx/1/model.onnx` is not in the mount (.MISSING_LARGE_BLOBS:1), so the
 benchmark model is rebuilt from its I/O contract (`models/densenet_onnx/1/config.json:5-20`: input `data_0`
@@ -1151,6 +1151,139 @@ def bert_base(batch: int | str = 1, **kw) -> bytes:
 
 def bert_tiny(batch: int | str = 1, **kw) -> bytes:
     return bert(batch, **dict(dict(seq=128, vocab=30522, dim=128, depth=2, heads=2, mlp=512), **kw))
+
+
+def causal_mask_constant(gb: GraphBuilder, seq: int, mask: str, max_pos: int, tag: str) -> str:
+    """The causal mask of a GPT-2 attention as a name: "where_slice" GPT-2's `bias` buffer, BOOL tril [1, 1, max_pos, max_pos], cut to [1, 1, seq, seq]
+    by two Slices (bias[:, :, key - query : key, :key]); "where_const" the BOOL tril [1, 1, seq, seq] itself; "add" the float mask [1, 1, seq, seq],
+    0 on and below the diagonal and finfo(float32).min above it"""
+    i64 = lambda name, v: gb.init(f"{tag}_{name}", np.array(v, np.int64))  # noqa: E731
+    if mask == "where_slice":
+        b = gb.init(tag + "_bias", np.tril(np.ones((max_pos, max_pos), np.bool_)).reshape(1, 1, max_pos, max_pos))
+        b = gb.simple("Slice", [b, i64("q_starts", [0]), i64("q_ends", [seq]), i64("q_axes", [2]), i64("q_steps", [1])])
+        return gb.simple("Slice", [b, i64("k_starts", [0]), i64("k_ends", [seq]), i64("k_axes", [3]), i64("k_steps", [1])])
+    if mask == "where_const":
+        return gb.init(tag + "_bias", np.tril(np.ones((seq, seq), np.bool_)).reshape(1, 1, seq, seq))
+    if mask == "add":
+        return gb.init(tag + "_mask", np.triu(np.full((seq, seq), FLOAT32_MIN, np.float32), 1).reshape(1, 1, seq, seq))
+    raise ValueError(mask)
+
+
+def gpt2_attention(gb: GraphBuilder, x: str, seq: int, dim: int, heads: int, tag: str, *, mask: str | None = "where_slice", scale: str = "div",
+                   ktrans: str = "two", split_attr: bool = True, max_pos: int = 1024, linear=None, mask_swap: bool = False) -> str:
+    """GPT2Attention (eager) behind its c_attn Linear: Split(axis 2) of the [N, L, 3 dim] rows (split_attr: the sizes as an input, else omitted as
+    the exporter does for equal parts) -> per part Reshape [N, L, H, hd] -> Transpose [0,2,1,3] (k: then [0,1,3,2] for ktrans "two", or the single
+    [0,2,3,1] for "one") -> MatMul -> Div(sqrt hd) | Mul(1 / sqrt hd) -> the causal mask (causal_mask_constant; Where(cond, scores, finfo.min) or
+    Add(scores, M), mask_swap: M first; None: no mask) -> Softmax -> MatMul(., v) -> Transpose [0,2,1,3] -> Reshape [N, L, dim].  x: the c_attn result,
+    or with `linear` the tokens it is applied to"""
+    hd = dim // heads
+    qkv = linear(x, tag + "_c_attn") if linear else x
+    ins = [qkv] + ([gb.init(tag + "_split", np.array([dim, dim, dim], np.int64))] if split_attr else [])
+    parts = [gb._uid(tag + "_part") for _ in range(3)]
+    gb.nodes.append(pb.node("Split", ins, parts, tag + "_split_qkv", [pb.attr_int("axis", 2)]))
+    shp = gb.init(tag + "_shape4", np.array([0, -1, heads, hd], np.int64))
+    q, k, v = (gb.simple("Reshape", [p, shp]) for p in parts)
+    q, v = gb.transpose(q, (0, 2, 1, 3)), gb.transpose(v, (0, 2, 1, 3))
+    kt = gb.transpose(gb.transpose(k, (0, 2, 1, 3)), (0, 1, 3, 2)) if ktrans == "two" else gb.transpose(k, (0, 2, 3, 1))
+    s = gb.simple("MatMul", [q, kt])
+    if scale == "div":
+        s = gb.simple("Div", [s, gb.init(tag + "_sqrt_hd", np.array(np.sqrt(float(hd)), np.float32))])
+    elif scale == "mul":
+        s = gb.simple("Mul", [s, gb.init(tag + "_rsqrt_hd", np.array(1.0 / np.sqrt(float(hd)), np.float32))])
+    else:
+        raise ValueError(scale)
+    if mask in ("where_slice", "where_const"):
+        s = gb.simple("Where", [causal_mask_constant(gb, seq, mask, max_pos, tag), s, gb.init(tag + "_mask_value", np.array(FLOAT32_MIN, np.float32))])
+    elif mask is not None:
+        m = causal_mask_constant(gb, seq, mask, max_pos, tag)
+        s = gb.simple("Add", [m, s] if mask_swap else [s, m])
+    p = gb.simple("Softmax", [s], [pb.attr_int("axis", -1)])
+    y = gb.transpose(gb.simple("MatMul", [p, v]), (0, 2, 1, 3))
+    return gb.simple("Reshape", [y, gb.init(tag + "_shape3", np.array([0, -1, dim], np.int64))])
+
+
+def gelu_new(gb: GraphBuilder, x: str, form: str = "pow") -> str:
+    """NewGELUActivation, 0.5 * x * (1 + tanh(sqrt(2 / pi) * (x + 0.044715 * x^3))), as the exporter writes it: "pow" with Pow(x, 3.0), "mulmul" with
+    Mul(x, Mul(x, x)) in its place, "op" the opset-20 Gelu(approximate = "tanh")"""
+    if form == "op":
+        return gb.gelu(x, "op_tanh")
+    name = gb._uid("gelu_new")
+    c = lambda tag, v: gb.init(f"{name}_{tag}", np.array(v, np.float32))  # noqa: E731
+    half = gb.simple("Mul", [x, c("half", 0.5)])
+    if form == "pow":
+        cube = gb.simple("Pow", [x, c("three", 3.0)])
+    elif form == "mulmul":
+        cube = gb.simple("Mul", [x, gb.simple("Mul", [x, x])])
+    else:
+        raise ValueError(form)
+    inner = gb.simple("Add", [x, gb.simple("Mul", [cube, c("c2", 0.044715)])])
+    t = gb.simple("Tanh", [gb.simple("Mul", [inner, c("c1", np.sqrt(2.0 / np.pi))])])
+    return gb.simple("Mul", [half, gb.simple("Add", [t, c("one", 1.0)])])
+
+
+def gpt2(batch: int | str = 1, *, seq: int = 128, vocab: int = 50257, dim: int = 768, depth: int = 12, heads: int = 12, mlp: int = 3072,
+         max_pos: int = 1024, eps: float = 1e-5, seed: int = 2019, mask: str | None = "where_slice", scale: str = "div", ktrans: str = "two",
+         linear: str = "conv1d", gelu: str = "pow", lm_head: str = "transpose", split_attr: bool = True, pos: str = "gather", logits: bool = True,
+         last_hidden_state: bool = False, table_std: float = 1.0) -> bytes:
+    """GPT2LMHeadModel as a prefill / scoring forward (pre-LN decoder, Radford et al. 2019), ids [N, seq] -> logits [N, seq, vocab], written from
+    modeling_gpt2.py's eager attention and the TorchScript exporter's known lowerings, not from a real export (neither `transformers` nor ONNX
+    Runtime is available here); checked by the float64 walk of tests/ref64.py.  The switches are the spellings the planner accepts:
+      mask     "where_slice" | "where_const" | "add" (causal_mask_constant), None: the same graph without the mask
+      linear   "conv1d" HF's Conv1D, Reshape [-1, D] -> Gemm -> Reshape [N, L, Dout]; "matmul" MatMul + Add
+      gelu     "pow" | "mulmul" | "op" (gelu_new);  lm_head  "transpose" Transpose(wte, [1,0]) (the tied head) | "init" a [dim, vocab] initializer
+      pos      "gather" Gather(wpe, Slice(position_ids)) | "const" the [1, seq, dim] rows;  split_attr: Split with its sizes, or without
+    outputs: logits (optional), last_hidden_state [N, seq, dim] behind ln_f (optional; the engine takes it beside the logits, whose head reads it)"""
+    gb = GraphBuilder("gpt2", seed)
+    wte = np.float32(table_std) * rng.gaussish(seed, "wte", vocab * dim).reshape(vocab, dim).astype(np.float32)
+    wpe = np.float32(table_std) * rng.gaussish(seed, "wpe", max_pos * dim).reshape(max_pos, dim).astype(np.float32)
+    x = gb.simple("Gather", [gb.init("wte", wte), "input_ids"], [pb.attr_int("axis", 0)])
+    if pos == "gather":
+        i64 = lambda name, v: gb.init(name, np.array(v, np.int64))  # noqa: E731
+        pid = gb.simple("Slice", [gb.init("position_ids", np.arange(max_pos, dtype=np.int64).reshape(1, max_pos)), i64("pos_starts", [0]), i64("pos_ends", [seq]),
+                                  i64("pos_axes", [1]), i64("pos_steps", [1])])
+        p = gb.simple("Gather", [gb.init("wpe", wpe), pid], [pb.attr_int("axis", 0)])
+    elif pos == "const":
+        p = gb.init("position_rows", wpe[:seq].reshape(1, seq, dim))
+    else:
+        raise ValueError(pos)
+    x = gb.simple("Add", [x, p])
+
+    def lin(y: str, name: str, cin: int, cout: int, w_scale: float | None = None) -> str:
+        w = rng.gaussish(seed, name + "_w", cin * cout).reshape(cin, cout) * np.float32(w_scale if w_scale is not None else np.sqrt(1.0 / cin))
+        b = (rng.uniform(seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
+        wn, bn = gb.init(name + "_w", w.astype(np.float32)), gb.init(name + "_b", b.astype(np.float32))
+        if linear == "matmul":
+            return gb.simple("Add", [gb.simple("MatMul", [y, wn]), bn])
+        if linear != "conv1d":
+            raise ValueError(linear)
+        flat = gb.simple("Reshape", [y, gb.init(name + "_flat", np.array([-1, cin], np.int64))])
+        g = gb.simple("Gemm", [flat, wn, bn], [pb.attr_float("alpha", 1.0), pb.attr_float("beta", 1.0)])
+        return gb.simple("Reshape", [g, gb.init(name + "_back", np.array([-1 if isinstance(batch, str) else batch, seq, cout], np.int64))])
+
+    for li in range(depth):
+        tag = f"h{li}"
+        y = gpt2_attention(gb, lin(gb.layernorm(x, dim, eps=eps, name=tag + "_ln_1"), tag + "_c_attn", dim, 3 * dim), seq, dim, heads, tag + "_attn",
+                           mask=mask, scale=scale, ktrans=ktrans, split_attr=split_attr, max_pos=max_pos)
+        x = gb.simple("Add", [lin(y, tag + "_c_proj", dim, dim), x])
+        y = gelu_new(gb, lin(gb.layernorm(x, dim, eps=eps, name=tag + "_ln_2"), tag + "_c_fc", dim, mlp), gelu)
+        x = gb.simple("Add", [x, lin(y, tag + "_mlp_proj", mlp, dim, w_scale=float(np.sqrt(2.0 / mlp)))])
+    gb.nodes.append(pb.node("LayerNormalization", [x, gb.init("ln_f_g", np.ones(dim, np.float32)), gb.init("ln_f_b", np.zeros(dim, np.float32))],
+                            ["last_hidden_state"], "ln_f", [pb.attr_int("axis", -1), pb.attr_float("epsilon", eps)]))
+    if logits:
+        head = gb.transpose("wte", (1, 0)) if lm_head == "transpose" else gb.init("lm_head_w", np.ascontiguousarray(wte.T))
+        if lm_head not in ("transpose", "init"):
+            raise ValueError(lm_head)
+        gb.simple("MatMul", ["last_hidden_state", head], out="logits")
+    outs = ([("logits", [batch, seq, vocab])] if logits else []) + ([("last_hidden_state", [batch, seq, dim])] if last_hidden_state or not logits else [])
+    return gb.finish([("input_ids", [batch, seq], ONNX_INT64)], outs, opset=20 if gelu == "op" else 17)
+
+
+def gpt2_small(batch: int | str = 1, **kw) -> bytes:
+    return gpt2(batch, **dict(dict(seq=128, vocab=50257, dim=768, depth=12, heads=12, mlp=3072, max_pos=1024), **kw))
+
+
+def gpt2_tiny(batch: int | str = 1, **kw) -> bytes:
+    return gpt2(batch, **dict(dict(seq=40, vocab=61, dim=128, depth=2, heads=2, mlp=256, max_pos=64), **kw))
 
 
 INT64_MAX = 9223372036854775807

@@ -17,7 +17,7 @@ from typing import Iterable, Sequence
 import numpy as np
 
 # TensorProto.DataType
-FLOAT, UINT8, INT8, INT32, INT64, FLOAT16 = 1, 2, 3, 6, 7, 10
+FLOAT, UINT8, INT8, INT32, INT64, BOOL, FLOAT16 = 1, 2, 3, 6, 7, 9, 10
 # AttributeProto.AttributeType
 A_FLOAT, A_INT, A_STRING, A_TENSOR, A_FLOATS, A_INTS = 1, 2, 3, 4, 6, 7
 
@@ -67,6 +67,8 @@ def tensor(name: str, arr: np.ndarray, raw: bool = True) -> bytes:
         dt = INT32
     elif arr.dtype == np.float16:
         dt = FLOAT16
+    elif arr.dtype == np.bool_:
+        dt = BOOL          # one byte per element in raw_data
     else:
         raise TypeError(arr.dtype)
     out = b"".join(f_varint(1, d) for d in arr.shape)
