@@ -71,7 +71,7 @@ ABI_SYMBOLS = [
     "ModelLoad", "ModelUnload",
 ]
 EXT_SYMBOLS = ["EngineDescribeModel", "EnginePrepare", "EngineRunPrepared", "EngineSynchronize", "EngineGetStream",
-               "EngineProfile", "EngineGetWeightBlob", "EngineWeightsUpdated", "EngineGetPrecision", "EngineMemcpy", "EngineMfmaPeak", "EngineGetBatcherStats", "EngineGetShardStats", "EngineGetRuntimeInfo", "EngineE4m3RoundTrip", "EnginePlanWeights", "EngineVectorAdd"]
+               "EngineProfile", "EngineGetWeightBlob", "EngineWeightsUpdated", "EngineGetPrecision", "EngineMemcpy", "EngineReadBuffer", "EngineMfmaPeak", "EngineGetBatcherStats", "EngineGetShardStats", "EngineGetRuntimeInfo", "EngineE4m3RoundTrip", "EnginePlanWeights", "EngineVectorAdd"]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -115,6 +115,7 @@ def lib() -> C.CDLL:
             "EngineWeightsUpdated": (C.c_bool, [vp, ep]), "EngineGetPrecision": (C.c_int, [vp]),
             "EngineVectorAdd": (C.c_bool, [vp, vp, vp, C.c_size_t, ep]),
             "EngineMemcpy": (C.c_bool, [vp, vp, vp, C.c_size_t, C.c_int, ep]),
+            "EngineReadBuffer": (C.c_bool, [vp, C.c_int, vp, C.c_size_t, ep]),
             "EngineMfmaPeak": (C.c_double, [C.c_int, C.c_int, C.c_int]),
             "EngineGetBatcherStats": (C.c_bool, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
             "EngineGetShardStats": (C.c_bool, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
@@ -625,6 +626,15 @@ def CopyToHost(model: Model, dst: np.ndarray, src_dev: int) -> None:
     err = C.c_void_p()
     if not lib().EngineMemcpy(model.handle, dst.ctypes.data, src_dev, dst.nbytes, 2, C.byref(err)):
         raise RuntimeError(_take_error(err))
+
+
+def ReadBuffer(model: Model, buf: int, nbytes: int) -> np.ndarray:
+    """The first nbytes raw bytes of activation buffer `buf` of the prepared plan (test support; plan under IE_KEEP_BUFFERS=1)."""
+    dst = np.empty(int(nbytes), np.uint8)
+    err = C.c_void_p()
+    if not lib().EngineReadBuffer(model.handle, int(buf), dst.ctypes.data, dst.nbytes, C.byref(err)):
+        raise RuntimeError(_take_error(err))
+    return dst
 
 
 def MfmaPeak(nacc: int = 4, blocks_per_cu: int = 1, iters: int = 2000) -> float:

@@ -699,6 +699,24 @@ bool EngineMemcpy(ModelHandle handle, void* dst, const void* src, size_t bytes, 
     catch (...) { set_error(error, "unknown error"); return false; }
 }
 
+bool EngineReadBuffer(ModelHandle handle, int buf, void* dst, size_t bytes, ErrorMessage* error) {
+    if (!handle || !dst) { set_error(error, "Invalid parameters"); return false; }
+    try {
+        ModelObj& M = *handle->model;
+        Lane0 L0(M);
+        if (!L0.dev() || !L0.dev()->current()) { set_error(error, "Model not prepared"); return false; }
+        const ie::PlanInstance& pi = *L0.dev()->current();
+        if (buf < 0 || size_t(buf) >= pi.buffers.size() || size_t(buf) >= pi.plan.buffer_floats.size()) { set_error(error, "EngineReadBuffer: no such buffer"); return false; }
+        // the allocation holds buffer_floats ELEMENTS of the buffer's own type (1, 2, 4 or 8 bytes): never read past it
+        const size_t have = size_t(pi.plan.buffer_floats[size_t(buf)]) * size_t(ie::BufferElemBytes(pi.plan.buffer_f16[size_t(buf)]));
+        if (bytes > have || bytes > 4 * size_t(pi.plan.buffer_floats[size_t(buf)])) { set_error(error, "EngineReadBuffer: more bytes than the buffer holds"); return false; }
+        L0.dev()->Synchronize();
+        L0.dev()->CopySync(dst, pi.buffers[size_t(buf)], bytes, hipMemcpyDeviceToHost, "hipMemcpy(read buffer)");
+        return true;
+    } catch (const std::exception& e) { set_error(error, e.what()); return false; }
+    catch (...) { set_error(error, "unknown error"); return false; }
+}
+
 double EngineMfmaPeak(int nacc, int blocks_per_cu, int iters) {
     if (ie::HipDeviceCount() <= 0) return -1.0;
     try { return ie::MfmaPeakTflops(nacc, blocks_per_cu, iters); } catch (...) { return -1.0; }

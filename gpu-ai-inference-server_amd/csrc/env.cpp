@@ -25,6 +25,7 @@ const char* const kNames[] = {
     "IE_NO_SE_FUSE",           // 1: squeeze-excite blocks as separate steps (global pool, two 1x1 convs, eltwise activation and gate Mul)
     "IE_GROUPED_CONV",         // 1: plan convs with 1 < group (not depthwise) as grouped steps (kernels_grouped.hip); unset: they are refused
     "IE_FORCE_ALGO", "IE_FORCE_TILE", "IE_FORCE_SPLITK",      // tests: pin the kernel family / tile / split-K of every conv
+    "IE_KEEP_BUFFERS",         // 1 (tests): no activation buffer is recycled, so EngineReadBuffer can read every value after a forward
     "IE_GN_TILE",              // 0 | 1: the tile of the group-norm steps alone (an ineligible 1 is the generic kernel), every other step as planned
     "IE_ATTN_TILE",            // 0 | 1 | 2 | 3: the tile of the attention steps alone, read when IE_FORCE_TILE did not force (an ineligible value is the generic kernel)
     // ---- executor ----------------------------------------------------------------------------------------------------------------

@@ -356,6 +356,7 @@ struct Planner {
     const Env& env;                        // the planner's switches, read once per plan build
     const Precision precision;
     const bool f8_fusions;
+    const bool keep_buffers;               // IE_KEEP_BUFFERS=1 (tests): no buffer is recycled, every value stays readable after the forward
     Lowering L;
     Plan plan;
     std::vector<int> out_vals;             // DensifyOutputs: the value each graph output is read from, in graph order
@@ -365,7 +366,7 @@ struct Planner {
     std::map<std::vector<int64_t>, int> writer;   // EmitSteps: (buffer, channel offset, channels) -> step index, for Step::in_src / in2_src
 
     Planner(const OnnxModel& mm, const std::vector<std::vector<int64_t>>& shapes, const Env& e, Precision p, bool f8)
-        : m(mm), input_shapes(shapes), env(e), precision(p), f8_fusions(f8), L(mm) { plan.precision = p; }
+        : m(mm), input_shapes(shapes), env(e), precision(p), f8_fusions(f8), keep_buffers(e.flag("IE_KEEP_BUFFERS")), L(mm) { plan.precision = p; }
 
     // ---- helpers ----
     bool single_consumer(int v) const { return !L.vals[v].is_output && L.consumers(v).size() == 1; }
@@ -3554,7 +3555,7 @@ void Planner::alloc_buf(int r, std::multimap<int64_t, int>& free_pool) {
     // a recycled buffer never changes element type
     bool dedicated = last_use[r] == kLiveForever || (precision == Precision::F8 && L.vals[r].h * L.vals[r].w == 1);
     L.vals[r].dedicated = dedicated;
-    if (!dedicated) {
+    if (!dedicated && !keep_buffers) {
         auto it = free_pool.lower_bound(need);
         // accept a recycled buffer up to 2x the needed size; otherwise grow a new one
         if (it != free_pool.end() && it->first <= 2 * need) {
@@ -3592,7 +3593,7 @@ void Planner::AssignBuffers() {
         for (size_t v = 0; v < L.vals.size(); ++v)
             if (used[v] && L.vals[v].root == int(v) && first_def[v] == int(pos) && !(handed >= 0 && int(v) == L.vals[L.nodes[size_t(order[pos])].out].root)) alloc_buf(int(v), free_pool);
         for (size_t v = 0; v < L.vals.size(); ++v)
-            if (used[v] && L.vals[v].root == int(v) && last_use[v] == int(pos) && L.vals[v].buf >= 0 && !L.vals[v].dedicated && int(v) != handed)
+            if (!keep_buffers && used[v] && L.vals[v].root == int(v) && last_use[v] == int(pos) && L.vals[v].buf >= 0 && !L.vals[v].dedicated && int(v) != handed)
                 free_pool.insert({plan.buffer_floats[size_t(L.vals[v].buf)], L.vals[v].buf});
     }
 }

@@ -47,6 +47,11 @@ int EngineGetPrecision(ModelHandle handle);
 /* Synchronous hipMemcpy on the model's device: kind 1 = host->device, 2 = device->host, 3 = device->device.
  * Lets a test or benchmark fill / read the engine-owned buffers returned by EnginePrepare. */
 bool EngineMemcpy(ModelHandle handle, void* dst, const void* src, size_t bytes, int kind, ErrorMessage* error);
+/* Test support: copy the first `bytes` raw bytes of activation buffer `buf` (the index a plan view carries) of lane 0's current prepared
+ * instance to the host, on that lane's stream after synchronising it.  Refused: a `buf` out of range, and more bytes than the buffer holds
+ * (plan.buffer_floats[buf] elements of its own type, never more than 4 bytes each).  A value is still in its buffer after the forward
+ * only when no later step reused it: plan under IE_KEEP_BUFFERS=1, which recycles none. */
+bool EngineReadBuffer(ModelHandle handle, int buf, void* dst, size_t bytes, ErrorMessage* error);
 /* Calibration microbenchmark: TFLOP/s of a register-resident v_mfma_f32_32x32x2_f32 loop with `nacc` (1, 2 or 4)
  * independent accumulator chains per wave and `blocks_per_cu` 4-wave workgroups per CU; <= 0 on error. */
 double EngineMfmaPeak(int nacc, int blocks_per_cu, int iters);
