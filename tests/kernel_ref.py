@@ -17,6 +17,9 @@ fp16 mode adds two derived terms (u_h = 2^-11): u_h |ref64| when the step writes
 rounds to half itself (a prologue result, a BN-folded weight); operands that are exactly representable in half add nothing.
 
 Convolution operands are handled in im2col form: cols [M, K] with M = (n, oh, ow) and K = (tap, channel), wm [Cout, K].
+
+Channel-local steps (depthwise and grouped convolutions, channel_*) are walked tap by tap on NCHW tensors instead, with a residual in S
+(S = sum |w'| |x_hat| + |b| + |res|) and the fused activations' allowance in channel_allowance.
 """
 import numpy as np
 
@@ -261,6 +264,195 @@ def c_emul(cols, wm, bias=None, relu=False, nsplit=1, seed=0, extra_runs=()):
         runs[f"extra{i}"] = y
     cs = {k: c_stat(v, ref, S)[0] for k, v in runs.items()}
     return max(cs.values()), cs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# channel-local steps: depthwise (groups == C) and grouped convolutions
+# ---------------------------------------------------------------------------------------------------------------------
+def channel_out_hw(h, w, kh, kw, stride, pads):
+    pt, pl, pb, pr = pads
+    return (h + pt + pb - kh) // stride + 1, (w + pl + pr - kw) // stride + 1
+
+
+def _taps(xh, kh, kw, stride, pads):
+    """(tap index, [N, G * cpg, OH, OW] window of the zero-padded input) per filter tap, row-major: no [M, K] matrix is built."""
+    n, c, h, w = xh.shape
+    pt, pl, pb, pr = pads
+    oh, ow = channel_out_hw(h, w, kh, kw, stride, pads)
+    xp = np.zeros((n, c, h + pt + pb, w + pl + pr), xh.dtype)
+    xp[:, :, pt:pt + h, pl:pl + w] = xh
+    for i in range(kh):
+        for j in range(kw):
+            yield i * kw + j, xp[:, :, i:i + (oh - 1) * stride + 1:stride, j:j + (ow - 1) * stride + 1:stride]
+
+
+def _grouped_w(w, groups):
+    """[Cout, cpg, kh, kw] -> [taps, cpg, G, opg, 1, 1] float64"""
+    cout, cpg, kh, kw = w.shape
+    return np.asarray(w, f64).reshape(groups, cout // groups, cpg, kh * kw).transpose(3, 2, 0, 1)[..., None, None]
+
+
+def channel_ref64_S(xh, w, groups, stride=1, pads=(0, 0, 0, 0), bias=None, res=None):
+    """(ref64, S) of a channel-local conv step BEFORE any activation, each [N, Cout, OH, OW] float64.  xh: the input after the prologue, NCHW
+    (float32, or float64 where a prologue activation makes the reference's x_hat a real number); w [Cout, Cin / groups, kh, kw]; output
+    channel o reads the input channels of group o // (Cout / groups); pads = (top, left, bottom, right), padding taps contribute 0;
+    S = sum |w| |x_hat| + |bias| + |res|.  ReLU and Clip are 1-Lipschitz: a bound on this value holds for the clamped one (clamp)."""
+    cout, cpg, kh, kw = w.shape
+    n = xh.shape[0]
+    wg = _grouped_w(w, groups)
+    ref = S = 0.0
+    for t, win in _taps(np.asarray(xh), kh, kw, stride, pads):
+        xg = win.astype(f64).reshape(n, groups, cpg, *win.shape[2:])
+        for c in range(cpg):
+            p = xg[:, :, c, None] * wg[t, c][None]                       # [N, G, opg, OH, OW]
+            ref = ref + p
+            S = S + np.abs(p)
+    ref, S = ref.reshape(n, cout, *ref.shape[3:]), S.reshape(n, cout, *S.shape[3:])
+    if bias is not None:
+        b = np.asarray(bias, f64).reshape(1, -1, 1, 1)
+        ref, S = ref + b, S + np.abs(b)
+    if res is not None:
+        ref, S = ref + np.asarray(res, f64), S + np.abs(np.asarray(res, f64))
+    return ref, S
+
+
+def channel_chain32(xh, w, groups, stride=1, pads=(0, 0, 0, 0), bias=None, res=None, order=None, half_acc=False):
+    """Both kernels' order: the fp32 FMA chain from 0 over taps, then the group's channels (`order`: a permutation of the taps * cpg terms
+    instead), then + bias, then + res, each rounded to float32.  half_acc (a mutant): the accumulator rounded to half after every tap."""
+    cout, cpg, kh, kw = w.shape
+    n = xh.shape[0]
+    wg = _grouped_w(np.asarray(w, f32), groups)
+    wins = [win.astype(f32).reshape(n, groups, cpg, *win.shape[2:]) for _, win in _taps(np.asarray(xh, f32), kh, kw, stride, pads)]
+    terms = [(t, c) for t in range(kh * kw) for c in range(cpg)]
+    acc = np.zeros((n, groups, cout // groups) + wins[0].shape[3:], f32)
+    for i, k in enumerate(range(len(terms)) if order is None else order):
+        t, c = terms[k]
+        acc = (acc.astype(f64) + wins[t][:, :, c, None].astype(f64) * wg[t, c][None]).astype(f32)
+        if half_acc and (i + 1) % cpg == 0:
+            acc = acc.astype(np.float16).astype(f32)
+    acc = acc.reshape(n, cout, *acc.shape[3:])
+    if bias is not None:
+        acc = (acc + np.asarray(bias, f32).reshape(1, -1, 1, 1)).astype(f32)
+    if res is not None:
+        acc = (acc + np.asarray(res, f32)).astype(f32)
+    return acc
+
+
+def channel_c_emul(xh, w, groups, stride=1, pads=(0, 0, 0, 0), bias=None, res=None, seed=0, extra_runs=(), ref_S=None):
+    """c_emul of a channel-local step on its own data: the kernels' tap-then-channel chain, one seeded random order of the same terms, and
+    any further legal results in `extra_runs` (the two-rounding prologue's).  Returns (c_emul, {name: c})."""
+    ref, S = ref_S if ref_S is not None else channel_ref64_S(xh, w, groups, stride, pads, bias, res)
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    runs = {"seq": channel_chain32(xh, w, groups, stride, pads, bias, res),
+            "perm": channel_chain32(xh, w, groups, stride, pads, bias, res, order=np.random.RandomState(seed).permutation(K))}
+    for i, y in enumerate(extra_runs):
+        runs[f"extra{i}"] = y
+    cs = {k: c_stat(v, ref, S)[0] for k, v in runs.items()}
+    return max(cs.values()), cs
+
+
+def clamp(z, relu=False, lo=None, hi=None):
+    """The epilogue's ReLU and Clip bounds (None: open), in the argument's precision."""
+    if relu:
+        z = np.maximum(z, 0)
+    if lo is not None:
+        z = np.maximum(z, lo)
+    if hi is not None:
+        z = np.minimum(z, hi)
+    return z
+
+
+# fused activations: the codes 1-4 of kernels.h's ApplyActBasic
+ACT_SIGMOID, ACT_HARDSIGMOID, ACT_SILU, ACT_HARDSWISH = 1, 2, 3, 4
+_SILU_KNEE = 2.399357280515468          # |x| where silu'' = 0: silu' is largest (1.0998) at +knee and smallest (-0.0998) at -knee
+
+
+def _sig(x):
+    return 1.0 / (1.0 + np.exp(-np.asarray(x, f64)))
+
+
+def act64(kind, x, a=0.0, b=0.0):
+    """The activation in float64 (a, b: the hard forms' slope and offset, as the float32 numbers the kernel holds)."""
+    x = np.asarray(x, f64)
+    if kind == 0:
+        return x
+    g = np.clip(float(a) * x + float(b), 0.0, 1.0) if kind in (ACT_HARDSIGMOID, ACT_HARDSWISH) else _sig(x)
+    return x * g if kind in (ACT_SILU, ACT_HARDSWISH) else g
+
+
+def _act_d(kind, x, a, b):
+    """|f'| at x from the closed forms (one-sided limits at the kinks of the hard forms are covered by act_lipschitz)"""
+    s = _sig(x)
+    if kind == ACT_SIGMOID:
+        return s * (1 - s)
+    if kind == ACT_SILU:
+        return np.abs(s * (1 + x * (1 - s)))
+    lin = (a * x + b > 0) & (a * x + b < 1)
+    if kind == ACT_HARDSIGMOID:
+        return np.where(lin, abs(a), 0.0)
+    return np.abs(np.where(lin, 2 * a * x + b, np.where(a * x + b >= 1, 1.0, 0.0)))
+
+
+def act_lipschitz(kind, lo, hi, a=0.0, b=0.0):
+    """max |f'| on [lo, hi], element by element: |f'| at the end points and at every point of the interval where it can peak (0 for the
+    sigmoid, +-knee for SiLU, both sides of the two kinks of the hard forms)."""
+    lo, hi = np.asarray(lo, f64), np.asarray(hi, f64)
+    if kind == 0:
+        return np.ones_like(lo)
+    a, b = float(a), float(b)
+    L = np.maximum(_act_d(kind, lo, a, b), _act_d(kind, hi, a, b))
+    pts = {ACT_SIGMOID: [0.0], ACT_SILU: [-_SILU_KNEE, _SILU_KNEE]}.get(kind)
+    if pts is None:
+        k0, k1 = sorted((-b / a, (1 - b) / a))
+        eps = 1e-9 * max(1.0, abs(k0), abs(k1))
+        pts = [k0 - eps, k0 + eps, k1 - eps, k1 + eps]
+    for p in pts:
+        L = np.where((lo <= p) & (p <= hi), np.maximum(L, _act_d(kind, np.full_like(lo, p), a, b)), L)
+    return L
+
+
+def channel_allowance(ref_z, S, c_emul, relu=False, lo=None, hi=None, act=(0, 0.0, 0.0), rounded=0, pre_act=False, f16=False, rtol=0.0):
+    """The per-element yardstick of a channel-local step behind its epilogue -> dict(ref, S, extra, L_rest): a result y is held to
+    c_stat(y, ref, S, extra) <= MARGIN * c_emul, that is  |y - ref| <= MARGIN * c_emul * u * S + extra.
+
+    z, the value before the epilogue, is bound by  delta = MARGIN c_emul u S_z + rest,  rest = u_h S_z per operand the kernel rounds to half
+    (fp16 mode) + rtol S_z where a prologue activation gives every tap's x_hat that relative error.  ReLU and Clip are 1-Lipschitz, so delta
+    carries through them.  Behind a fused activation f (codes 1-4):  |y - f(ref_z)| <= L delta + E,  L = max |f'| on [ref_z - delta,
+    ref_z + delta] from the closed forms and E = rtol |f(ref_z)|.  E is the project's own relative figure (engine_run.RTOL) applied per
+    element, not a new number: generous for one exp and one divide, to be tightened from the ratios the GPU tests print.  A half result
+    adds u_h |ref|.  Returned S is L S_z, extra the rest; L_rest = L * rest and half = the half result's term (for the printed ratios)."""
+    S = np.asarray(S, f64)
+    rest = (rounded * UH * S if f16 else 0.0) + (rtol * S if pre_act else 0.0)
+    zc = clamp(np.asarray(ref_z, f64), relu, lo, hi)
+    kind, a, b = act
+    if kind:
+        delta = MARGIN * c_emul * U * S + rest
+        L = act_lipschitz(kind, zc - delta, zc + delta, a, b)
+        ref = act64(kind, zc, a, b)
+        E = rtol * np.abs(ref)
+    else:
+        L, ref, E = np.ones_like(S), zc, 0.0
+    half = UH * np.abs(ref) if f16 else np.zeros_like(S)
+    return dict(ref=ref, S=L * S, extra=L * rest + E + half, L_rest=L * rest, half=half)
+
+
+def written_check_is_conclusive(refs, vector=1):
+    """refs: (ref64, S, additive allowance, c_emul) of three runs of one model on three inputs.  An element the kernel never wrote holds one and
+    the same value in all three results: where two of the references lie further apart than their bounds together no single value meets all
+    three bounds, so three results within their bounds prove the element is written.  True when that holds at EVERY element (and no
+    reference is zero, which a cleared buffer would meet).  vector > 1: at one element at least of every run of `vector` consecutive channels
+    -- the unit a kernel that stores whole channel vectors writes or skips (fp16 maps of millions of elements: three half-precision bounds
+    overlap at a few elements per million by chance)."""
+    bounds = [MARGIN * ce * U * S + extra for _, S, extra, ce in refs]
+    apart = np.zeros(refs[0][0].shape, bool)
+    for i in range(3):
+        for j in range(i + 1, 3):
+            apart |= np.abs(refs[i][0] - refs[j][0]) > bounds[i] + bounds[j]
+    if vector > 1:
+        n, c = apart.shape[:2]
+        assert c % vector == 0
+        apart = apart.reshape(n, c // vector, vector, *apart.shape[2:]).any(axis=2)
+    return bool(np.all(apart)) and all(bool(np.all(r[0] != 0)) for r in refs)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -81,16 +81,6 @@ def run_all(tmp_path, d, xs, env, prec):
     return st, ys, prof[st["name"]]
 
 
-def written_check_is_conclusive(refs):
-    """No single value can meet the bounds of all three runs at any element (and no reference is zero)"""
-    bounds = [R.MARGIN * ce * R.U * S + extra for _, S, extra, ce in refs]
-    apart = np.zeros(refs[0][0].shape, bool)
-    for i in range(3):
-        for j in range(i + 1, 3):
-            apart |= np.abs(refs[i][0] - refs[j][0]) > bounds[i] + bounds[j]
-    return bool(np.all(apart)) and all(bool(np.all(r[0] != 0)) for r in refs)
-
-
 def check(tmp_path, d, tile, prec, want_label):
     xs = inputs(d)
     st, ys, label = run_all(tmp_path, d, xs, dict(IE_FORCE_TILE=str(tile)), prec)
@@ -103,7 +93,7 @@ def check(tmp_path, d, tile, prec, want_label):
         assert c <= R.MARGIN * ce, (f"{want_label} {prec}: c {c:.2f} > 2 x c_emul {ce:.2f} at (n, channel, row, col) = {at}: got {y[at]!r}, ref64 {ref[at]!r}, "
                                     f"S {S[at]:.3e}, case {d['seed']} run {run}")
     if d["post"] in (0, 3) and d["bias"]:
-        assert written_check_is_conclusive(refs), "two of the three inputs must give distinguishable results at every element"
+        assert R.written_check_is_conclusive(refs), "two of the three inputs must give distinguishable results at every element"
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])

@@ -1,5 +1,6 @@
 """GPU (-m gpu): depthwise convolutions and Clip on the MI355X against a float64 torch-CPU walk of the same ONNX graph (tests/ref64.py).
-Bounds as tests/test_gpu_parity.py: fp32 within 2e-4 of max|ref|, fp16 within 3e-3."""
+Bounds as tests/test_gpu_parity.py: fp32 within 2e-4 of max|ref|, fp16 within 3e-3.
+The per-kernel checks (every instantiation forced, each element held to its own bound) are in tests/test_channel_maps_gpu.py."""
 import os
 
 import numpy as np

@@ -25,15 +25,16 @@ IGEMM_TILES = [(128, 128, 1, 0), (128, 64, 1, 0), (128, 32, 1, 0), (64, 64, 1, 0
 NUM_IGEMM_BASE_TILES = 7          # the scalar loader has the K-group-free tiles only: a forced tile beyond them plans the heuristic one
 
 
-def C(seed, n, h, w, cin, cout, k=1, s=1, p=0, pre=0, bias=0, post=0, hw=0):
-    """One conv case (kernel_graphs.conv_case arguments); post: 0 none, 1 ReLU, 2 BN + ReLU, 3 BN; hw: half-representable weights."""
-    return (seed, n, h, w, cin, cout, k, s, p, bool(pre), bool(bias), post, bool(hw))
+def C(seed, n, h, w, cin, cout, k=1, s=1, p=0, pre=0, bias=0, post=0, hw=0, dil=1):
+    """One conv case (kernel_graphs.conv_case arguments); post: 0 none, 1 ReLU, 2 BN + ReLU, 3 BN; hw: half-representable weights; a dilation
+    other than 1 is a 14th entry (the undilated cases stay the 13-tuples they were)."""
+    return (seed, n, h, w, cin, cout, k, s, p, bool(pre), bool(bias), post, bool(hw)) + ((dil,) if dil != 1 else ())
 
 
 @functools.lru_cache(maxsize=None)
 def build(case):
-    seed, n, h, w, cin, cout, k, s, p, pre, bias, post, hw = case
-    return G.conv_case(seed, n, h, w, cin, cout, k, s, p, pre, bias, post, hw)
+    seed, n, h, w, cin, cout, k, s, p, pre, bias, post, hw = case[:13]
+    return G.conv_case(seed, n, h, w, cin, cout, k, s, p, pre, bias, post, hw, *case[13:])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -161,7 +162,7 @@ def reference(case, prec, nsplit=1, family=""):
         # a loader that rounds s * x before it adds t is as legal as the FMA: its result on the same data is one more order
         p = d["pre_bn"]
         x2 = R.prologue32(G.lifted(d["x"], d["w0"]), *R.bn_affine(p["g"], p["b"], p["m"], p["v"]), fused=False)
-        extra_runs.append(R.chain32(R.im2col(x2, d["k"], d["k"], d["stride"], (d["pad"],) * 4).reshape(cols.shape), wm, b, relu=relu))
+        extra_runs.append(R.chain32(R.im2col(x2, d["k"], d["k"], d["stride"], (d["pad"],) * 4, d["dil"]).reshape(cols.shape), wm, b, relu=relu))
     if family in ("wino", "wino_x6"):
         wt = wm.reshape(d["cout"], 3, 3, d["cin"]).transpose(0, 3, 1, 2)
         yw = R.wino32(G.conv_xhat(d), wt, b, relu, x6=(family == "wino_x6"))

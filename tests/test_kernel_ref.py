@@ -264,3 +264,229 @@ def test_position_classes():
     assert R.position_class((0, 33, 2, 2), shape) == "last channel block"
     assert R.position_class((0, 3, 2, 2), shape) == "tile-block border"         # pixel 16
     assert R.position_class((0, 3, 2, 4), shape) == "interior"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# channel-local steps (depthwise, grouped): the reference against the graph oracle, and the mutants the per-element check must reject
+# ---------------------------------------------------------------------------------------------------------------------
+import channel_graphs as CG  # noqa: E402
+import ref64  # noqa: E402
+import test_channel_maps_gpu as CM  # noqa: E402  (the GPU tables: the mutants use their shapes)
+from engine_run import RTOL  # noqa: E402
+
+
+class ChannelCase:
+    """One table entry of tests/test_channel_maps_gpu.py with its operands, yardstick and the plain fp32 chain of its first input.  small_block:
+    (first channel, count) of output channels whose folded weights and bias are scaled by 2^-13 -- a block behind a small BatchNorm scale, the
+    magnitude at which the old bound (a fraction of max|ref| of the whole output) sees nothing."""
+    def __init__(self, case, prec="fp32", run=0, small_block=None):
+        self.d = d = CM.build(case)
+        self.prec, self.f16 = prec, prec == "fp16"
+        self.x = CM.inputs(d)[run]
+        dot = self.f16 and d["groups"] != d["c"] and (d["c"] // d["groups"]) % 2 == 0
+        self.op = op = CG.channel_operands(d, self.x, self.f16, dot)
+        if small_block is not None:
+            lo, n = small_block
+            op["w"] = op["w"].copy()
+            op["w"][lo:lo + n] *= f32(2.0 ** -13)
+            if op["bias"] is not None:
+                op["bias"] = op["bias"].copy()
+                op["bias"][lo:lo + n] *= f32(2.0 ** -13)
+        self.geom = (d["groups"], d["stride"], d["pads"])
+        self.zref, self.Sz = R.channel_ref64_S(op["xh"], op["w"], *self.geom, op["bias"], op["res"])
+        runs = [R.channel_chain32(op["xh2"], op["w"], *self.geom, op["bias"], op["res"])] if op["xh2"] is not None else []
+        self.c_emul, self.cs = R.channel_c_emul(op["xh"], op["w"], *self.geom, op["bias"], op["res"], seed=d["seed"], extra_runs=runs, ref_S=(self.zref, self.Sz))
+        self.a = R.channel_allowance(self.zref, self.Sz, self.c_emul, op["relu"], op["lo"], op["hi"], op["act"], op["rounded"], op["pre_act"], self.f16, RTOL[prec])
+        self.seq = self.finish(R.channel_chain32(op["xh"], op["w"], *self.geom, op["bias"], op["res"]))
+
+    def finish(self, z):
+        """the epilogue on a pre-activation result, as the kernel applies it (and the half store of fp16 mode)"""
+        op = self.op
+        y = R.act64(op["act"][0], R.clamp(np.asarray(z, f64), op["relu"], op["lo"], op["hi"]), *op["act"][1:])
+        return y.astype(np.float16).astype(f64) if self.f16 else y.astype(f32).astype(f64)
+
+    def c(self, y):
+        return R.c_stat(y, self.a["ref"], self.a["S"], self.a["extra"])
+
+    def ok(self, y):
+        return self.c(y)[0] <= R.MARGIN * self.c_emul
+
+    def old_ok(self, y):
+        return ref64.rel_err(y, self.a["ref"]) < RTOL[self.prec]
+
+
+@functools.lru_cache(maxsize=None)
+def ccase(case, prec="fp32", run=0, small_block=None):
+    return ChannelCase(case, prec, run, small_block)
+
+
+CHANNEL_SAMPLE = CM.DW_PLAIN + CM.DW_ACT[:4] + CM.DW_EDGE[1:6] + CM.GROUPED + CM.GROUPED_GENERIC[:1]
+
+
+@pytest.mark.parametrize("case", [CM.DW_PLAIN[0], CM.GROUPED[1], CM.DW_EDGE[3], CM.DW_EDGE[5], CM.DW_ACT[3], CM.GROUPED[4]], ids=lambda c: f"case{c[0]}")
+def test_channel_reference_agrees_with_the_graph_oracle(case):
+    """The prologue acts on in-range taps only (the ONNX graph pads the prologue's OUTPUT): kernel_ref's reference of a step with a BN + ReLU
+    prologue and padding, depthwise and grouped, against tests/ref64.py's float64 walk of the same ONNX bytes, within the float32 roundings of
+    x_hat, s and w' (8 u S); asymmetric pads, the prologue bound, a prologue activation and an epilogue activation likewise."""
+    cs = ccase(case)
+    d = cs.d
+    want = ref64.run_f64(d["model"], {"x": cs.x})["out"]
+    assert want.shape == tuple(d["oshape"])
+    got = CG.tile_copies(d, cs.a["ref"])
+    tol = CG.tile_copies(d, 8 * R.U * cs.a["S"] + 1e-6 * np.abs(cs.a["ref"]) * bool(d["act"]))          # (the hard activations' a = fl32(1 / 6) against 1 / 6)
+    err = np.abs(CG.copies(d, want) - got)
+    assert np.all(err <= tol), float((err / np.maximum(tol, 1e-300)).max())
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16"])
+@pytest.mark.parametrize("case", CHANNEL_SAMPLE, ids=lambda c: f"case{c[0]}")
+def test_channel_bound_accepts_the_kernels_order_and_another(case, prec):
+    cs = ccase(case, prec)
+    K = cs.op["w"][0].size
+    for order in (None, np.random.RandomState(977).permutation(K)):
+        op = cs.op
+        xs = [op["xh"]] + ([op["xh2"]] if op["xh2"] is not None else [])
+        for xh in xs:
+            y = cs.finish(R.channel_chain32(xh, op["w"], *cs.geom, op["bias"], op["res"], order=order))
+            assert cs.ok(y), (cs.c(y), cs.c_emul)
+    print(f"case {case[0]} {prec}: c_emul {cs.c_emul:.2f} {cs.cs}")
+    assert 0.4 < cs.c_emul < 8.0, cs.cs
+
+
+def test_activation_lipschitz_constants_bound_the_difference_quotient():
+    rs = np.random.RandomState(4)
+    lo = rs.uniform(-8, 8, 4000)
+    hi = lo + rs.uniform(0, 3, 4000) * rs.randint(0, 2, 4000)
+    for kind, a, b in ((R.ACT_SIGMOID, 0, 0), (R.ACT_HARDSIGMOID, CG.HSIG_A, CG.HSIG_B), (R.ACT_SILU, 0, 0), (R.ACT_HARDSWISH, CG.HSWISH_A, CG.HSWISH_B)):
+        L = R.act_lipschitz(kind, lo, hi, a, b)
+        for t in np.linspace(0, 1, 33):
+            p, q = lo + t * (hi - lo), lo + rs.rand(4000) * (hi - lo)
+            assert np.all(np.abs(R.act64(kind, p, a, b) - R.act64(kind, q, a, b)) <= L * np.abs(p - q) * (1 + 1e-9) + 1e-15), kind
+    assert abs(float(R.act_lipschitz(R.ACT_SILU, -9.0, 9.0)) - 1.0998) < 1e-4 and float(R.act_lipschitz(R.ACT_HARDSWISH, -9.0, 9.0, CG.HSWISH_A, 0.5)) == pytest.approx(1.5, abs=1e-6)
+    assert float(R.act_lipschitz(R.ACT_HARDSIGMOID, 4.0, 5.0, CG.HSIG_A, 0.5)) == 0.0 and float(R.act_lipschitz(R.ACT_SIGMOID, -1.0, 2.0)) == 0.25
+    # the sigmoid in float32 (one exp, one divide) meets E = RTOL |f| by orders of magnitude
+    x = np.linspace(-8, 8, 4001).astype(f32)
+    g = (f32(1) / (f32(1) + np.exp(-x).astype(f32))).astype(f32)
+    assert np.all(np.abs(g - R.act64(R.ACT_SIGMOID, x)) <= 8 * R.U * R.act64(R.ACT_SIGMOID, x))
+
+
+def _mut_prologue_on_padding(cs):
+    """the prologue's shift also applied on the padding taps: x_hat = relu(t) there instead of 0"""
+    d, op = cs.d, cs.op
+    p = d["pre_bn"]
+    s, t = R.bn_affine(p["g"], p["b"], p["m"], p["v"])
+    pt, pl, pb_, pr = d["pads"]
+    src = np.pad(G.lifted(cs.x, d["w0"]), ((0, 0), (0, 0), (pt, pb_), (pl, pr)))
+    return cs.finish(R.channel_chain32(R.prologue32(src, s, t), op["w"], d["groups"], d["stride"], (0, 0, 0, 0), op["bias"], op["res"]))
+
+
+def _mut_half_weights(cs):
+    """the centre tap's weights rounded to half (all taps: with 9 terms and no averaging the old bound notices as well)"""
+    op = cs.op
+    w = op["w"].copy()
+    w[:, :, w.shape[2] // 2, w.shape[3] // 2] = R.half_exact(w[:, :, w.shape[2] // 2, w.shape[3] // 2])
+    return cs.finish(R.channel_chain32(op["xh"], w, *cs.geom, op["bias"], op["res"]))
+
+
+def _mut_half_accumulator(cs):
+    op = cs.op
+    return cs.finish(R.channel_chain32(op["xh"], op["w"], *cs.geom, op["bias"], op["res"], half_acc=True))
+
+
+def _smallest_S_channel(cs):
+    return int(np.argmin(cs.Sz.max(axis=(0, 2, 3))))
+
+
+def _mut_bias_twice(cs):
+    ch = _smallest_S_channel(cs)
+    z = R.channel_chain32(cs.op["xh"], cs.op["w"], *cs.geom, cs.op["bias"], cs.op["res"])
+    z[:, ch] = (z[:, ch] + cs.op["bias"][ch]).astype(f32)
+    return cs.finish(z), ch
+
+
+def _mut_groups_swapped(cs, block):
+    """one output block reads the NEXT group's input channels"""
+    d, op = cs.d, cs.op
+    lo, n = block
+    cpg, opg = d["c"] // d["groups"], d["cout"] // d["groups"]
+    g = lo // opg
+    xh = op["xh"].copy()
+    a, b = g * cpg, ((g + 1) % d["groups"]) * cpg
+    xh[:, a:a + cpg], xh[:, b:b + cpg] = op["xh"][:, b:b + cpg], op["xh"][:, a:a + cpg]
+    z = R.channel_chain32(op["xh"], op["w"], *cs.geom, op["bias"], op["res"])
+    z[:, lo:lo + n] = R.channel_chain32(xh, op["w"], *cs.geom, op["bias"], op["res"])[:, lo:lo + n]
+    return cs.finish(z)
+
+
+@pytest.mark.parametrize("case", [CM.DW_PLAIN[0], CM.GROUPED[1]], ids=lambda c: f"case{c[0]}")
+def test_channel_bound_rejects_a_prologue_on_padding_taps(case):
+    """(this mutant is wrong by a whole tap at every border: the old global bound rejects it too, so only the new one is asserted)"""
+    cs = ccase(case)
+    y = _mut_prologue_on_padding(cs)
+    c, at = cs.c(y)
+    print(f"case {case[0]} prologue on padding: c {c:.0f} at {at}")
+    sh = y.shape
+    assert not cs.ok(y) and R.position_class(at, sh) == "image border"
+
+
+@pytest.mark.parametrize("case", [CM.DW_PLAIN[3], CM.DW_EDGE[1], CM.DW_EDGE[2], CM.GROUPED_MORE[0], CM.GROUPED[2], CM.GROUPED[6]], ids=lambda c: f"case{c[0]}")
+def test_channel_bound_rejects_half_rounded_weights_in_fp32_mode(case):
+    cs = ccase(case)
+    y = _mut_half_weights(cs)
+    c, at = cs.c(y)
+    print(f"case {case[0]} weights rounded to half: c {c:.0f} at {at}, 2 x c_emul {2 * cs.c_emul:.1f}; old bound {ref64.rel_err(y, cs.a['ref']):.1e}")
+    assert not cs.ok(y) and c > 10 * R.MARGIN * cs.c_emul
+    assert cs.old_ok(y)
+
+
+@pytest.mark.parametrize("case", [CM.DW_PLAIN[3], CM.DW_EDGE[8], CM.GROUPED[5], CM.GROUPED[7]], ids=lambda c: f"case{c[0]}")
+def test_channel_bound_rejects_a_half_accumulator(case):
+    """fp16 mode (where a half accumulator is the tempting mistake): the sum rounded to half after every tap, against u_h |ref| for the one
+    rounding of the result.  (Grouped cases with half-exact weights: where the v_dot2 path rounds the weights itself it is allowed u_h S.)"""
+    cs = ccase(case, "fp16")
+    assert cs.op["rounded"] == 0
+    y = _mut_half_accumulator(cs)
+    c, at = cs.c(y)
+    print(f"case {case[0]} half accumulator: c {c:.0f} beyond the half terms at {at}; old bound {ref64.rel_err(y, cs.a['ref']):.1e}")
+    assert not cs.ok(y) and c > 10 * R.MARGIN * cs.c_emul
+    assert cs.old_ok(y)
+
+
+@pytest.mark.parametrize("case,block", [(CM.DW_PLAIN[3], (8, 4)), (CM.DW_EDGE[4], (20, 4)), (CM.GROUPED[0], (16, 16)), (CM.GROUPED[5], (16, 16))], ids=lambda c: f"case{c[0]}" if len(c) > 2 else "")
+def test_channel_bound_rejects_a_bias_added_twice_on_the_smallest_channel(case, block):
+    cs = ccase(case, small_block=block)
+    y, ch = _mut_bias_twice(cs)
+    assert block[0] <= ch < block[0] + block[1]
+    c, at = cs.c(y)
+    print(f"case {case[0]} bias twice on channel {ch}: c {c:.0f} at {at}; old bound {ref64.rel_err(y, cs.a['ref']):.1e}")
+    assert not cs.ok(y) and at[1] == ch
+    assert cs.old_ok(y)
+
+
+@pytest.mark.parametrize("case,block", [(CM.GROUPED[1], (0, 16)), (CM.GROUPED[2], (16, 16)), (CM.GROUPED[3], (8, 8)), (CM.GROUPED[5], (16, 16)), (CM.GROUPED_MORE[0], (32, 16))],
+                         ids=lambda c: f"case{c[0]}" if len(c) > 2 else "")
+def test_channel_bound_rejects_swapped_group_inputs(case, block):
+    """One output block (a wave's channel block, behind a small BatchNorm scale) multiplies the neighbouring group's input channels"""
+    cs = ccase(case, small_block=block)
+    y = _mut_groups_swapped(cs, block)
+    c, at = cs.c(y)
+    print(f"case {case[0]} groups swapped for outputs {block}: c {c:.0f} at {at}; old bound {ref64.rel_err(y, cs.a['ref']):.1e}")
+    assert not cs.ok(y) and block[0] <= at[1] < block[0] + block[1]
+    assert cs.old_ok(y)
+
+
+@pytest.mark.parametrize("case", [CM.DW_EDGE[1], CM.DW_EDGE[4], CM.DW_PLAIN[3]], ids=lambda c: f"case{c[0]}")
+def test_three_inputs_catch_a_pixel_that_is_never_stored(case):
+    """The last pixel of every PX = 4 group is not written: it keeps what the previous request left in the reused buffer.  With ONE input run again
+    (what the graph tests do) that value is the correct one and every bound passes; with another input before it the per-element bound of the
+    second run rejects it, at such a pixel."""
+    a, b = ccase(case, run=0), ccase(case, run=1)
+    ow = a.d["ow"]
+    last = [x for x in range(ow) if x % 4 == 3 or x == ow - 1]
+    stale_same, stale_other = b.seq.copy(), b.seq.copy()
+    stale_other[..., last] = a.seq[..., last]
+    assert b.ok(stale_same) and b.old_ok(stale_same)
+    c, at = b.c(stale_other)
+    assert not b.ok(stale_other) and at[3] in last, (c, at)
+    refs = [ccase(case, run=r) for r in range(3)]
+    assert R.written_check_is_conclusive([(r.a["ref"], r.a["S"], r.a["extra"], r.c_emul) for r in refs])
