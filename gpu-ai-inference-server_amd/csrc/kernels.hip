@@ -25,24 +25,15 @@
 #include <mutex>
 #include <utility>
 
+#include "device_util.h"
 #include "igemm_tiles.h"
 #include "env.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // element access that honours TensorArg::f16 (scalar kernels; the MFMA kernels have dedicated half paths)
-__device__ __forceinline__ float ld_elem(const float* p, int f16, int64_t i) {
-    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
-}
-__device__ __forceinline__ void st_elem(float* p, int f16, int64_t i, float v) {
-    if (f16) reinterpret_cast<_Float16*>(p)[i] = _Float16(v);
-    else p[i] = v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // In-launch split-K combine ("the last arriver reduces").  Every K-slice workgroup of an output tile stores its raw
 // accumulators to a slab, publishes them with ONE agent-scope release, and draws a ticket from the tile's counter; the
@@ -282,9 +273,9 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_kernel(const Con
         constexpr unsigned OOB = 0x80000000u;    // >= num_records of every descriptor (views are < 2^31 bytes)
 
         const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(in), 0, int(a.in_bytes), 0x00020000);
+            const_cast<float*>(in), 0, int(a.in_bytes), kBufferRsrcFlags);
         const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(wgt), 0, Cout * Ktot * 4, 0x00020000);
+            const_cast<float*>(wgt), 0, Cout * Ktot * 4, kBufferRsrcFlags);
 
         int poff[A_IT];                  // element offset of tap (0,0), channel c4 of this row's window
         unsigned taps[A_IT];             // bit t set: tap t of this row lies inside the image (kh*kw <= 32)
@@ -549,7 +540,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, const int nsp
     float v = bias ? bias[n] : 0.f;
     for (int s = 0; s < nsplit; ++s) v += ws[int64_t(s) * total + idx];
     if (relu) v = fmaxf(v, 0.f);
-    st_elem(out, out_f16, m * opitch + n, v);
+    st_any(out, out_f16, m * opitch + n, v);
 }
 
 hipError_t LaunchSplitKReduce(const ConvArgs& a, int splitk, hipStream_t stream) {
@@ -575,13 +566,8 @@ int ResidentPerCu(const void* kernel, int block, size_t lds) {
 }
 
 static int PersistentSlots(const void* kernel, int block, size_t lds) {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    return ResidentPerCu(kernel, block, lds) * cus;
+    const int cus = DeviceCus();
+    return ResidentPerCu(kernel, block, lds) * (cus ? cus : 256);
 }
 static int PersistentGrid(int num_tiles, int slots, int splitk) {
     const bool off = Knobs().no_persistent;
@@ -659,10 +645,9 @@ hipError_t LaunchConvIgemm(const ConvArgs& a_in, int tile, int vec, int splitk, 
         int64_t(a.out.n) * a.out.h * a.out.w * a.out.sw >= (int64_t(1) << 31))
         return hipErrorInvalidValue;
     if (vec) {
-        if (a.in.sc != 1 || (a.in.c & 3) || (a.in.sw & 3) || (a.in.sh & 3) || (a.in.sn & 3) ||
-            (reinterpret_cast<uintptr_t>(a.in.p) & 15) || (reinterpret_cast<uintptr_t>(a.w) & 15))
+        if (a.in.sc != 1 || (a.in.c & 3) || (a.in.sw & 3) || (a.in.sh & 3) || (a.in.sn & 3) || !Aligned16(a.in.p) || !Aligned16(a.w))
             return hipErrorInvalidValue;
-        if (a.pre_scale && ((reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift) & 15)))
+        if (a.pre_scale && (!Aligned16(a.pre_scale) || !Aligned16(a.pre_shift)))
             return hipErrorInvalidValue;
     }
     if (a.dh != 1 || a.dw != 1) {
@@ -790,8 +775,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_raster_kernel(const ConvAr
     }
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in.p), 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, Cout * 9 * Cin * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in.p), 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, Cout * 9 * Cin * 4, kBufferRsrcFlags);
 
     f32x16 acc[TMW][TN];
 #pragma unroll
@@ -1019,8 +1004,7 @@ bool ConvRasterEligible(const ConvArgs& a, int tile) {
     if (tile < 0 || tile >= kNumRasterTiles) return false;
     if (a.kh != 3 || a.kw != 3 || a.sh != 1 || a.sw != 1 || a.pt != 1 || a.pl != 1) return false;
     if (a.out.h != a.in.h || a.out.w != a.in.w || a.pre_scale != nullptr || a.in.f16 || a.out.f16) return false;
-    if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c & 3) || (a.in.sw & 3) || (reinterpret_cast<uintptr_t>(a.in.p) & 15) ||
-        (reinterpret_cast<uintptr_t>(a.w) & 15))
+    if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c & 3) || (a.in.sw & 3) || !Aligned16(a.in.p) || !Aligned16(a.w))
         return false;
     if (a.in.sh != a.in.sw * a.in.w || a.in.sn != a.in.sh * a.in.h) return false;      // pixel-major NHWC view
     if (int64_t(a.in.n) * (a.in.h + 1) * (a.in.w + 1) + 4096 >= (int64_t(1) << 31)) return false;
@@ -1091,7 +1075,7 @@ __global__ void conv_naive_kernel(const ConvArgs a, const int64_t total) {
             const int64_t px = int64_t(b) * a.in.sn + int64_t(iy) * a.in.sh + int64_t(ix) * a.in.sw;
             const float* wp = wrow + (ky * a.kw + kx) * Cin;
             for (int c = 0; c < Cin; ++c) {
-                float v = ld_elem(a.in.p, a.in.f16, px + int64_t(c) * a.in.sc);
+                float v = ld_any(a.in.p, a.in.f16, px + int64_t(c) * a.in.sc);
                 if (a.pre_scale) { v = v * a.pre_scale[c] + a.pre_shift[c]; if (a.pre_relu) v = fmaxf(v, 0.f); }
                 acc = fmaf(v, wp[c], acc);
             }
@@ -1099,7 +1083,7 @@ __global__ void conv_naive_kernel(const ConvArgs a, const int64_t total) {
     }
     if (a.bias) acc += a.bias[n];
     if (a.relu) acc = fmaxf(acc, 0.f);
-    st_elem(a.out.p, a.out.f16, int64_t(b) * a.out.sn + int64_t(oy) * a.out.sh + int64_t(ox) * a.out.sw + n, acc);
+    st_any(a.out.p, a.out.f16, int64_t(b) * a.out.sn + int64_t(oy) * a.out.sh + int64_t(ox) * a.out.sw + n, acc);
 }
 
 hipError_t LaunchConvNaive(const ConvArgs& a, hipStream_t stream) {
@@ -1118,7 +1102,6 @@ template <int V>      // V = 4: float4 lanes (fp32), V = 8: 8 halfs per lane (fp
 __global__ void pool_kernel(const PoolArgs a, const int64_t total) {
     const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
     const int CV = a.out.c / V;
     const int c = int(idx % CV) * V;
     int64_t m = idx / CV;
@@ -1165,7 +1148,7 @@ __global__ void pool_kernel(const PoolArgs a, const int64_t total) {
                 const h8 t = *reinterpret_cast<const h8*>(reinterpret_cast<const _Float16*>(a.in.p) + off);
 #pragma unroll
                 for (int v = 0; v < 8; ++v) x[v] = float(t[v]);
-            } else x[0] = ld_elem(a.in.p, a.in.f16, off);
+            } else x[0] = ld_any(a.in.p, a.in.f16, off);
             if (a.pre_scale) {
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
@@ -1190,14 +1173,14 @@ __global__ void pool_kernel(const PoolArgs a, const int64_t total) {
 #pragma unroll
         for (int v = 0; v < 8; ++v) t[v] = _Float16(acc[v]);
         *reinterpret_cast<h8*>(reinterpret_cast<_Float16*>(a.out.p) + ooff) = t;
-    } else st_elem(a.out.p, a.out.f16, ooff, acc[0]);
+    } else st_any(a.out.p, a.out.f16, ooff, acc[0]);
 }
 
 static bool aligned4(const TensorArg& t) {
-    return !t.f16 && t.sc == 1 && !(t.c & 3) && !(t.sw & 3) && !(t.sh & 3) && !(t.sn & 3) && !(reinterpret_cast<uintptr_t>(t.p) & 15);
+    return !t.f16 && t.sc == 1 && !(t.c & 3) && !(t.sw & 3) && !(t.sh & 3) && !(t.sn & 3) && Aligned16(t.p);
 }
 static bool aligned8h(const TensorArg& t) {
-    return t.f16 && t.sc == 1 && !(t.c & 7) && !(t.sw & 7) && !(t.sh & 7) && !(t.sn & 7) && !(reinterpret_cast<uintptr_t>(t.p) & 15);
+    return t.f16 && t.sc == 1 && !(t.c & 7) && !(t.sw & 7) && !(t.sh & 7) && !(t.sn & 7) && Aligned16(t.p);
 }
 
 hipError_t LaunchPool(const PoolArgs& a, hipStream_t stream) {
@@ -1230,7 +1213,7 @@ __global__ __launch_bounds__(256) void gap_kernel(const TensorArg in, const Tens
     if (cok)
         for (int p = g; p < HW; p += 4) {
             const int y = p / in.w, x = p - y * in.w;
-            float v = ld_elem(in.p, in.f16, int64_t(b) * in.sn + int64_t(y) * in.sh + int64_t(x) * in.sw + c);
+            float v = ld_any(in.p, in.f16, int64_t(b) * in.sn + int64_t(y) * in.sh + int64_t(x) * in.sw + c);
             if (ps) { v = v * s + t; }
             if (pre_relu) v = fmaxf(v, 0.f);
             if (pre_act) v = ApplyAct(pre_act, pa, pb, v);
@@ -1240,7 +1223,7 @@ __global__ __launch_bounds__(256) void gap_kernel(const TensorArg in, const Tens
     __syncthreads();
     if (g == 0 && cok) {
         const float tot = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
-        st_elem(out.p, out.f16, int64_t(b) * out.sn + c, tot / float(HW));
+        st_any(out.p, out.f16, int64_t(b) * out.sn + c, tot / float(HW));
     }
 }
 
@@ -1264,10 +1247,10 @@ __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
     const int x = int(m % a.out.w); m /= a.out.w;
     const int y = int(m % a.out.h);
     const int b = int(m / a.out.h);
-    float v = ld_elem(a.a.p, a.a.f16, int64_t(b) * a.a.sn + int64_t(y) * a.a.sh + int64_t(x) * a.a.sw + int64_t(c) * a.a.sc);
+    float v = ld_any(a.a.p, a.a.f16, int64_t(b) * a.a.sn + int64_t(y) * a.a.sh + int64_t(x) * a.a.sw + int64_t(c) * a.a.sc);
     if (a.scale) v = v * a.scale[c] + a.shift[c];
     if (a.b.p) {
-        const float u = ld_elem(a.b.p, a.b.f16, a.b_bcast ? int64_t(b) * a.b.sn + int64_t(c) * a.b.sc
+        const float u = ld_any(a.b.p, a.b.f16, a.b_bcast ? int64_t(b) * a.b.sn + int64_t(c) * a.b.sc
                                                            : int64_t(b) * a.b.sn + int64_t(y) * a.b.sh + int64_t(x) * a.b.sw + int64_t(c) * a.b.sc);
         v = a.b_mul ? v * u : v + u;
     }
@@ -1275,14 +1258,13 @@ __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
     if (a.lo > -__builtin_huge_valf()) v = fmaxf(v, a.lo);
     if (a.hi < __builtin_huge_valf()) v = fminf(v, a.hi);
     if (a.act) v = ApplyAct(a.act, a.act_a, a.act_b, v);
-    st_elem(a.out.p, a.out.f16, int64_t(b) * a.out.sn + int64_t(y) * a.out.sh + int64_t(x) * a.out.sw + int64_t(c) * a.out.sc, v);
+    st_any(a.out.p, a.out.f16, int64_t(b) * a.out.sn + int64_t(y) * a.out.sh + int64_t(x) * a.out.sw + int64_t(c) * a.out.sc, v);
 }
 
 // 16 bytes per lane (4 floats / 8 halfs of one pixel's channels) when every operand is pixel-major NHWC of one element type
 template <bool HALF>
 __global__ void eltwise_vec_kernel(const EltArgs a, const int64_t total_vec, const int cv) {
     constexpr int V = HALF ? 8 : 4;
-    typedef _Float16 h8v __attribute__((ext_vector_type(8)));
     const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (idx >= total_vec) return;
     const int64_t p = idx / cv;
@@ -1290,7 +1272,7 @@ __global__ void eltwise_vec_kernel(const EltArgs a, const int64_t total_vec, con
     float v[V], w[V];
     auto load = [&](const TensorArg& t, float* dst, int64_t off) {
         if constexpr (HALF) {
-            const h8v x = *reinterpret_cast<const h8v*>(reinterpret_cast<const _Float16*>(t.p) + off);
+            const h8 x = *reinterpret_cast<const h8*>(reinterpret_cast<const _Float16*>(t.p) + off);
 #pragma unroll
             for (int i = 0; i < V; ++i) dst[i] = float(x[i]);
         } else {
@@ -1330,18 +1312,17 @@ __global__ void eltwise_vec_kernel(const EltArgs a, const int64_t total_vec, con
         for (int i = 0; i < V; ++i) v[i] = ApplyAct(a.act, a.act_a, a.act_b, v[i]);
     }
     if constexpr (HALF) {
-        h8v o;
+        h8 o;
 #pragma unroll
         for (int i = 0; i < V; ++i) o[i] = _Float16(v[i]);
-        *reinterpret_cast<h8v*>(reinterpret_cast<_Float16*>(a.out.p) + p * a.out.sw + c) = o;
+        *reinterpret_cast<h8*>(reinterpret_cast<_Float16*>(a.out.p) + p * a.out.sw + c) = o;
     } else {
         *reinterpret_cast<float4*>(a.out.p + p * a.out.sw + c) = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
 
 static bool elt_vec_ok(const TensorArg& t, int f16, int V) {
-    return t.f16 == f16 && t.sc == 1 && (t.c % V) == 0 && (t.sw % V) == 0 && t.sh == t.w * t.sw && t.sn == t.h * t.sh &&
-           (reinterpret_cast<uintptr_t>(t.p) % 16) == 0;
+    return t.f16 == f16 && t.sc == 1 && (t.c % V) == 0 && (t.sw % V) == 0 && t.sh == t.w * t.sw && t.sn == t.h * t.sh && Aligned16(t.p);
 }
 
 hipError_t LaunchEltwise(const EltArgs& a, hipStream_t stream) {
@@ -1350,7 +1331,7 @@ hipError_t LaunchEltwise(const EltArgs& a, hipStream_t stream) {
     {
         const int f16 = a.out.f16, V = f16 ? 8 : 4;
         // a broadcast gate [N, C, 1, 1]: 16-byte vectors at (n, c)
-        const bool b_ok = a.b.p == nullptr || (a.b_bcast ? (a.b.f16 == f16 && a.b.sc == 1 && a.b.c % V == 0 && a.b.sn % V == 0 && (reinterpret_cast<uintptr_t>(a.b.p) % 16) == 0)
+        const bool b_ok = a.b.p == nullptr || (a.b_bcast ? (a.b.f16 == f16 && a.b.sc == 1 && a.b.c % V == 0 && a.b.sn % V == 0 && Aligned16(a.b.p))
                                                          : elt_vec_ok(a.b, f16, V));
         if (elt_vec_ok(a.out, f16, V) && elt_vec_ok(a.a, f16, V) && b_ok) {
             const int64_t tv = total / V;
@@ -1386,8 +1367,8 @@ __global__ void copy_kernel(const TensorArg in, const TensorArg out, const int o
         y = int(m % out.h); m /= out.h;
         c = int(m % out.c); b = int(m / out.c);
     }
-    st_elem(out.p, out.f16, int64_t(b) * out.sn + int64_t(y) * out.sh + int64_t(x) * out.sw + int64_t(c) * out.sc,
-            ld_elem(in.p, in.f16, int64_t(b) * in.sn + int64_t(y) * in.sh + int64_t(x) * in.sw + int64_t(c) * in.sc));
+    st_any(out.p, out.f16, int64_t(b) * out.sn + int64_t(y) * out.sh + int64_t(x) * out.sw + int64_t(c) * out.sc,
+           ld_any(in.p, in.f16, int64_t(b) * in.sn + int64_t(y) * in.sh + int64_t(x) * in.sw + int64_t(c) * in.sc));
 }
 
 hipError_t LaunchCopy(const TensorArg& in, const TensorArg& out, hipStream_t stream) {

@@ -51,21 +51,15 @@
 
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-
 constexpr int kAttnBlock = 256;
 constexpr float kLog2e = 1.4426950408889634f;
-
-__device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
-    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
-}
 
 constexpr float kFltMax = 3.402823466e+38f;
 constexpr float kMaskShiftMax = 16777216.f;
@@ -126,22 +120,20 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
     }
 }
 
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
 // What a wave of tile 1 / 3 carries through its key tiles: its lane's half of its Q row, the O^T accumulators and the softmax statistics of its query
 template <typename T, int HD>
 struct AttnWave {
     static constexpr bool F16 = sizeof(T) == 2;
     static constexpr int HH = HD / 2;              // head-dim elements one lane half supplies to QK^T
     float4 q4[F16 ? 1 : HH / 4];
-    h8v q8[F16 ? HH / 8 : 1];
+    h8 q8[F16 ? HH / 8 : 1];
     f32x16 o0, o1;
     float m, lsum;
 
     __device__ __forceinline__ void init(const T* qrow) {
         if constexpr (F16) {
 #pragma unroll
-            for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8v*>(qrow + 8 * k);
+            for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8*>(qrow + 8 * k);
         } else {
 #pragma unroll
             for (int k = 0; k < HH / 4; ++k) q4[k] = *reinterpret_cast<const float4*>(qrow + 4 * k);
@@ -166,7 +158,7 @@ struct AttnWave {
         if constexpr (F16) {
 #pragma unroll
             for (int k = 0; k < HH; k += 8)
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8v*>(krow + k), q8[k / 8], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(krow + k), q8[k / 8], s, 0, 0, 0);
         } else {
 #pragma unroll
             for (int k = 0; k < HH; k += 4) {
@@ -206,7 +198,7 @@ struct AttnWave {
         if constexpr (F16) {
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                h8v pb, va0, va1;
+                h8 pb, va0, va1;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int kt = 16 * st + 8 * (j >> 2) + 4 * hf + (j & 3);
@@ -234,11 +226,11 @@ struct AttnWave {
         for (int g = 0; g < 4; ++g) {
             const int e0 = 8 * g + 4 * hf;             // registers 4 g ... 4 g + 3 are the output columns e0 ... e0 + 3 of this lane's query
             if constexpr (F16) {
-                h4v x, y;
+                h4 x, y;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) { x[t] = _Float16(o0[4 * g + t] * inv); y[t] = _Float16(o1[4 * g + t] * inv); }
-                *reinterpret_cast<h4v*>(orow + e0) = x;
-                if constexpr (HD == 64) *reinterpret_cast<h4v*>(orow + 32 + e0) = y;
+                *reinterpret_cast<h4*>(orow + e0) = x;
+                if constexpr (HD == 64) *reinterpret_cast<h4*>(orow + 32 + e0) = y;
             } else {
                 *reinterpret_cast<float4*>(orow + e0) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
                 if constexpr (HD == 64)
@@ -449,7 +441,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const Attn
 #pragma unroll
         for (int k = 0; k < NQ; ++k) {
             if constexpr (F16) {
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8v, kv[k]), __builtin_bit_cast(h8v, qv[k]), s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, kv[k]), __builtin_bit_cast(h8, qv[k]), s, 0, 0, 0);
             } else {
                 const float4 kf = __builtin_bit_cast(float4, kv[k]), qf = __builtin_bit_cast(float4, qv[k]);
                 s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf.x, s, 0, 0, 0);
@@ -508,12 +500,12 @@ __global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const Attn
         if constexpr (F16) {
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                h8v pb;
+                h8 pb;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pb[j] = _Float16(s[8 * st + j]);
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
-                    h8v va;
+                    h8 va;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) va[j] = vc[(16 * st + 8 * (j >> 2) + 4 * hf + (j & 3)) * HD + 32 * b];
                     o[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pb, o[b], 0, 0, 0);
@@ -543,7 +535,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const Attn
                 uint2 mine[2];
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
-                    h4v y;
+                    h4 y;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) y[e] = _Float16(o[b][4 * (2 * p + x) + e] * inv);
                     mine[x] = __builtin_bit_cast(uint2, y);
@@ -563,9 +555,12 @@ __global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const Attn
     }
 }
 
-// the MFMA kernel's view: channels contiguous, token rows one pitch apart through the whole tensor, 16-byte aligned base
-bool vec_view_ok(const TensorArg& t, int V) {
-    return t.sc == 1 && t.h == 1 && t.c % V == 0 && t.sw % V == 0 && t.sn == int64_t(t.w) * t.sw && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
+// the MFMA kernels' view: a token view (one row per image), token rows one pitch apart through the whole tensor.  Differs from VecViewOk twice: the
+// images must be dense (stricter), and the row stride of the single row addresses nothing, so it carries no condition (laxer: checked as 0)
+bool token_view_ok(const TensorArg& t, int V) {
+    TensorArg row = t;
+    row.sh = 0;
+    return t.h == 1 && t.sn == int64_t(t.w) * t.sw && VecViewOk(row, V);
 }
 
 template <typename T, int HD, bool MASK, bool CAUSAL>
@@ -627,7 +622,7 @@ bool AttentionEligible(const AttnArgs& a, int tile) {
     if (tile == 0) return true;
     const int V = a.out.f16 ? 8 : 4;
     // (the offsets are in the base pointers: their alignment stands for the offset condition)
-    if (a.in.f16 != a.out.f16 || !vec_view_ok(a.in, V) || !vec_view_ok(a.out, V)) return false;
+    if (a.in.f16 != a.out.f16 || !token_view_ok(a.in, V) || !token_view_ok(a.out, V)) return false;
     if (tile == 3) return AttnChunkFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr);
     return tile == 1 ? AttnMfmaFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr)
                      : AttnStreamFits(a.in.w, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0, a.mask != nullptr);

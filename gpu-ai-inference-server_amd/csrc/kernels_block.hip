@@ -22,16 +22,11 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 // s_setprio(1) for the producer waves, A/B'd in the probe: 355 vs 323 us per 24-layer chain at batch 128 (the raised priority also slows the
 // consumers' epilogue and 3x3, where the producers have nothing to hide): off.
@@ -110,11 +105,11 @@ __global__ __launch_bounds__(512) void dense_block_f16_kernel(const DenseBlockAr
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pitch = a.pitch;
     _Float16* const ximg = a.x + size_t(img) * H * W * pitch;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(ximg, 0, H * W * pitch * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wf = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.wfrag16), 0, int(a.w16_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w16 = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.w16), 0, int(a.w16_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(ximg, 0, H * W * pitch * 2, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_wf = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.wfrag16), 0, int(a.w16_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_w16 = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.w16), 0, int(a.w16_bytes), kBufferRsrcFlags);
     const __amdgpu_buffer_rsrc_t rs_w32 =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w32), 0, int(a.w16_bytes * 2 < 0x7fffffffull ? a.w16_bytes * 2 : 0x7fffffffull), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w32), 0, int(a.w16_bytes * 2 < 0x7fffffffull ? a.w16_bytes * 2 : 0x7fffffffull), kBufferRsrcFlags);
 
     // ---- zero the raster once: pad rows / columns are never written again ----
     {
@@ -470,11 +465,11 @@ __global__ __launch_bounds__(512) void dense_strip_f16_kernel(const DenseBlockAr
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pitch = a.pitch;
     _Float16* const ximg = a.x + size_t(img) * H * W * pitch;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(ximg, 0, H * W * pitch * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wf = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.wfrag16), 0, int(a.w16_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w16 = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.w16), 0, int(a.w16_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(ximg, 0, H * W * pitch * 2, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_wf = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.wfrag16), 0, int(a.w16_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_w16 = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.w16), 0, int(a.w16_bytes), kBufferRsrcFlags);
     const __amdgpu_buffer_rsrc_t rs_w32 =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w32), 0, int(a.w16_bytes * 2 < 0x7fffffffull ? a.w16_bytes * 2 : 0x7fffffffull), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w32), 0, int(a.w16_bytes * 2 < 0x7fffffffull ? a.w16_bytes * 2 : 0x7fffffffull), kBufferRsrcFlags);
     const DenseBlockLayer& L = a.layer[0];
     const int K = L.K, NC = (K + 63) >> 6;
     const int G = nsteps * NC;                             // chunks of the whole strip, as one stream
@@ -776,8 +771,7 @@ bool DenseBlockEligible(const DenseBlockArgs& a) {
     if (cfg < 0 || block_lds_bytes(cfg, a.h, a.w, rows) > size_t(160) * 1024) return false;
     if (int64_t(a.n) * ((cfg == 2 ? (a.h + rows - 1) / rows : 1)) >= (int64_t(1) << 31)) return false;
     if (cfg >= 3 && a.layer[0].K > kMaxK) return false;
-    if ((a.pitch & 7) || (a.in_coff & 7) || (reinterpret_cast<uintptr_t>(a.x) & 15) || (reinterpret_cast<uintptr_t>(a.wfrag16) & 15) ||
-        (reinterpret_cast<uintptr_t>(a.w16) & 15))
+    if ((a.pitch & 7) || (a.in_coff & 7) || !Aligned16(a.x) || !Aligned16(a.wfrag16) || !Aligned16(a.w16))
         return false;
     if (int64_t(a.h) * a.w * a.pitch * 2 >= (int64_t(1) << 31) || a.w16_bytes == 0 || a.w16_bytes >= (uint64_t(1) << 31)) return false;
     for (int l = 0; l < a.nlayers; ++l) {

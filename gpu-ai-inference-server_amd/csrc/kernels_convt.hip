@@ -25,21 +25,15 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
 constexpr int kConvtBlock = 256;   // 4 waves
 constexpr int kConvtTapGroup = 4;  // taps per wave: 4 * PB accumulator tiles of 16 registers
-
-__device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
-    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
-}
 
 template <typename T> struct Frag;
 template <> struct Frag<float> { typedef f32x4 type; };
@@ -199,10 +193,10 @@ bool ConvTransposedEligible(const ConvtArgs& a, int tile) {
     if (a.kh != a.sh || a.kw != a.sw || a.pt || a.pl || a.pb || a.pr || a.oph || a.opw || a.kh * a.kw > 16) return false;
     const bool f16 = a.out.f16 != 0;
     const int V = f16 ? 8 : 4;
-    if ((a.in.f16 != 0) != f16 || a.in.sc != 1 || a.in.c % (2 * V) || a.in.sw % V || a.in.sh % V || a.in.sn % V) return false;
-    if (reinterpret_cast<uintptr_t>(a.in.p) % 16 || int64_t(a.in.n) * a.in.h * a.in.w >= (int64_t(1) << 31) - 64) return false;
+    if ((a.in.f16 != 0) != f16 || !VecViewOk(a.in, V) || a.in.c % (2 * V)) return false;      // (whole K-steps of two vectors, not only whole vectors)
+    if (int64_t(a.in.n) * a.in.h * a.in.w >= (int64_t(1) << 31) - 64) return false;
     const void* w = f16 ? a.w16 : static_cast<const void*>(a.w);
-    return w && reinterpret_cast<uintptr_t>(w) % 16 == 0;
+    return w && Aligned16(w);
 }
 
 hipError_t LaunchConvTransposed(const ConvtArgs& a, int tile, hipStream_t stream) {

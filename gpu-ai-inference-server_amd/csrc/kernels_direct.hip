@@ -20,17 +20,12 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "device_util.h"
 #include "env.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 struct DirectGeom {
     int cpt;        // chunks per tap = Cin / CW
@@ -67,9 +62,9 @@ __global__ __launch_bounds__(64 * WAVES) void conv_direct_kernel(const ConvArgs 
     const int iy0 = oy * a.sh - a.pt, ix0 = ox * a.sw - a.pl;
 
     const int cb = int(int64_t(g.total) * wave / WAVES), ce = int(int64_t(g.total) * (wave + 1) / WAVES);
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
     const void* const wbase = HALF ? a.w16 : static_cast<const void*>(a.w);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wbase), 0, Cout * KK * Cin * ESZ, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wbase), 0, Cout * KK * Cin * ESZ, kBufferRsrcFlags);
 
     // ---- every operand fragment of this wave's K slice, requested at once ----
     u32x4 A[MAXC][2], B[MAXC][TN][2];
@@ -173,7 +168,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_direct_kernel(const ConvArgs 
     // thread t sums channel pair (t % (BN/2))*2 of pixel t / (BN/2) over the waves, in wave order
     const int esz = a.out.f16 ? 2 : 4;
     const __amdgpu_buffer_rsrc_t rs_out =
-        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * a.out.sw + Cout) * esz), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * a.out.sw + Cout) * esz), kBufferRsrcFlags);
     for (int idx = tid; idx < 32 * (BN / 2); idx += NT) {
         const int p = idx / (BN / 2), c2 = (idx - p * (BN / 2)) * 2;
         f32x2 v = {0.f, 0.f};
@@ -195,7 +190,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_direct_kernel(const ConvArgs 
             const h2 hv = {_Float16(v[0]), _Float16(v[1])};
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hv), rs_out, n < Cout ? rowoff + unsigned(n * 2) : OOB, 0, 0);
         } else {
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, v), rs_out,
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rs_out,
                                                   n < Cout ? rowoff + unsigned(n * 4) : OOB, 0, 0);
         }
     }
@@ -236,7 +231,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_win_kernel(const ConvArgs a, 
     // ---- this wave's weight fragments: fragment-major, 1 KiB per load, all in flight at once ----
     const int cb = int(int64_t(g.total) * wave / WAVES), ce = int(int64_t(g.total) * (wave + 1) / WAVES);
     const __amdgpu_buffer_rsrc_t rs_w =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, Cout * a.kh * a.kw * Cin * 4, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, Cout * a.kh * a.kw * Cin * 4, kBufferRsrcFlags);
     u32x4 B[MAXC][TN];
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
@@ -250,7 +245,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_win_kernel(const ConvArgs a, 
     // ---- activation window -> LDS (coalesced rows; prologue applied here, padding is masked at fragment time) ----
     {
         constexpr int U = 4;
-        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
         const int c4n = Cin >> 2;
         const int p_lo = m0 - a.pt * W - a.pl;
         const int npx = 16 + (a.kh - 1) * W + (a.kw - 1);
@@ -318,7 +313,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_win_kernel(const ConvArgs a, 
     for (int j = 0; j < TN; ++j) *reinterpret_cast<f32x4*>(sPart + (wave * 16 + r) * PP + j * 16 + 4 * gk) = acc[j];
     __syncthreads();
     const __amdgpu_buffer_rsrc_t rs_out =
-        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * a.out.sw + Cout) * 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * a.out.sw + Cout) * 4), kBufferRsrcFlags);
     for (int idx = tid; idx < 16 * (BN / 2); idx += NT) {
         const int p = idx / (BN / 2), c2 = (idx - p * (BN / 2)) * 2;
         f32x2 v = {0.f, 0.f};
@@ -331,7 +326,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_win_kernel(const ConvArgs a, 
         const int n = n0 + c2;                         // Cout % BN == 0 (eligibility): always in range
         if (a.bias != nullptr) { v[0] += a.bias[n]; v[1] += a.bias[n + 1]; }
         if (a.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); }
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, v), rs_out,
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rs_out,
                                               m0 + p < M ? unsigned((m0 + p) * int(a.out.sw) + n) * 4u : OOB, 0, 0);
     }
 }
@@ -375,10 +370,10 @@ static bool win_eligible(const ConvArgs& a, int wt) {
     if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c % 16) || (a.out.c % (16 * t.tn))) return false;
     if (a.sh != 1 || a.sw != 1 || a.out.h != a.in.h || a.out.w != a.in.w || a.out.n != a.in.n) return false;
     if (a.pt < 0 || a.pl < 0 || a.pt >= a.kh || a.pl >= a.kw) return false;
-    if ((a.in.sw % 4) || a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh || (reinterpret_cast<uintptr_t>(a.in.p) & 15)) return false;
-    if ((reinterpret_cast<uintptr_t>(a.wfrag) & 15) || (a.out.sw & 1) || (reinterpret_cast<uintptr_t>(a.out.p) & 7)) return false;
+    if ((a.in.sw % 4) || a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh || !Aligned16(a.in.p)) return false;
+    if (!Aligned16(a.wfrag) || (a.out.sw & 1) || (reinterpret_cast<uintptr_t>(a.out.p) & 7)) return false;
     if (a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh) return false;
-    if (a.pre_scale && ((reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift) & 15))) return false;
+    if (a.pre_scale && (!Aligned16(a.pre_scale) || !Aligned16(a.pre_shift))) return false;
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
     if (M > 65536 || (M + 64) * a.in.sw * 4 >= (int64_t(1) << 31) || M * a.out.sw * 4 >= (int64_t(1) << 31) ||
         int64_t(a.out.c) * a.kh * a.kw * a.in.c * 4 >= (int64_t(1) << 31))
@@ -430,7 +425,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_as_kernel(const ConvArgs a
     const int ipitch = int(a.in.sw), opitch = int(a.out.sw);
 
     // ---- weight ring: chunk c of 16-channel block nb is the KiB at ((nb * CH + c) * 64 + lane) * 16 ----
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, Cout * K * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, Cout * K * 4, kBufferRsrcFlags);
     const int nb = n0 >> 4;
     // fp32 MFMAs and VALU instructions do not overlap on this part: the K loop carries no vector address arithmetic.
     // Weight loads: lane * 16 in the VGPR, everything else in the scalar offset; past the last chunk the last chunk is loaded again
@@ -461,9 +456,9 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_as_kernel(const ConvArgs a
         const int cs = a.debug >> 16, CT = 1 << cs;
         const int rstep = NT >> cs, npass = R / rstep;                            // wave-uniform (R, NT and CT are powers of two)
         const int col = tid & (CT - 1), row0 = tid >> cs;
-        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, ((M - 1) * ipitch + K) * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_scale), 0, PRE ? K * 4 : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_shift), 0, PRE ? K * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, ((M - 1) * ipitch + K) * 4, kBufferRsrcFlags);
+        const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_scale), 0, PRE ? K * 4 : 0, kBufferRsrcFlags);
+        const __amdgpu_buffer_rsrc_t rs_sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_shift), 0, PRE ? K * 4 : 0, kBufferRsrcFlags);
         const unsigned c16 = unsigned(col) * 16u;                                  // byte offset of the lane's column within a block
         unsigned g = (unsigned(m0) * unsigned(ipitch) + __umul24(row0, ipitch)) * 4u + c16;      // pitches < 2^22 (as_eligible)
         unsigned char* l = smem_direct + (__umul24(row0, P) * 4u + c16);            // the LDS address itself: no base to add per item
@@ -571,8 +566,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_as_kernel(const ConvArgs a
     // Epilogue: the lane's row / quad offset is formed once; pixel block and channel block are scalar.  Rows past M lie behind the
     // descriptor's range ((M - 1) * pitch + Cout floats, pitch >= Cout): their stores are dropped without a predicate.
     const __amdgpu_buffer_rsrc_t rs_out =
-        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias != nullptr ? Cout * 4 : 0, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias != nullptr ? Cout * 4 : 0, kBufferRsrcFlags);
     const unsigned o0 = (unsigned(m0) * unsigned(opitch) + __umul24(r, opitch) + 4 * gk) * 4u;
     const unsigned ostep = unsigned(opitch) * 64u;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -610,10 +605,10 @@ static bool as_eligible(const ConvArgs& a, int at) {
     if (a.kh != 1 || a.kw != 1 || a.sh != 1 || a.sw != 1 || a.pt != 0 || a.pl != 0) return false;
     if (a.out.h != a.in.h || a.out.w != a.in.w || a.out.n != a.in.n) return false;
     if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c % 16) || (a.out.c % (16 * t.tnw * t.waves))) return false;
-    if ((a.in.sw % 4) || a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh || (reinterpret_cast<uintptr_t>(a.in.p) & 15)) return false;
-    if ((a.out.sw % 4) || a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh || (reinterpret_cast<uintptr_t>(a.out.p) & 15)) return false;
-    if ((reinterpret_cast<uintptr_t>(a.wfrag) & 15) || (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15))) return false;
-    if (a.pre_scale && ((reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift) & 15))) return false;
+    if ((a.in.sw % 4) || a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh || !Aligned16(a.in.p)) return false;
+    if ((a.out.sw % 4) || a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh || !Aligned16(a.out.p)) return false;
+    if (!Aligned16(a.wfrag) || (a.bias && !Aligned16(a.bias))) return false;
+    if (a.pre_scale && (!Aligned16(a.pre_scale) || !Aligned16(a.pre_shift))) return false;
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
     if (M > (int64_t(1) << 22) || M * a.in.sw * 4 >= (int64_t(1) << 31) || M * a.out.sw * 4 >= (int64_t(1) << 31) || int64_t(a.out.c) * a.in.c * 4 >= (int64_t(1) << 31))
         return false;
@@ -680,14 +675,14 @@ bool ConvDirectEligible(const ConvArgs& a, int tile) {
     if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c % cw) || a.kh * a.kw > 49) return false;
     if (half ? (a.w16 == nullptr) : (a.w == nullptr)) return false;
     const int align = half ? 8 : 4;                    // 16-byte fragments
-    if ((a.in.sw % align) || (a.in.sh % align) || (a.in.sn % align) || (reinterpret_cast<uintptr_t>(a.in.p) & 15)) return false;
-    if (reinterpret_cast<uintptr_t>(half ? a.w16 : static_cast<const void*>(a.w)) & 15) return false;
+    if ((a.in.sw % align) || (a.in.sh % align) || (a.in.sn % align) || !Aligned16(a.in.p)) return false;
+    if (!Aligned16(half ? a.w16 : static_cast<const void*>(a.w))) return false;
     if ((a.out.c & 1) || (a.out.sw & 1) || (reinterpret_cast<uintptr_t>(a.out.p) & 7)) return false;
     if (a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh) return false;    // output pixels at a constant pitch
     if (a.pre_scale) {
         if (half && (a.pre_scale16 == nullptr || a.pre_shift16 == nullptr)) return false;
-        if ((reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift) & 15)) return false;
-        if (half && ((reinterpret_cast<uintptr_t>(a.pre_scale16) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift16) & 15))) return false;
+        if (!Aligned16(a.pre_scale) || !Aligned16(a.pre_shift)) return false;
+        if (half && (!Aligned16(a.pre_scale16) || !Aligned16(a.pre_shift16))) return false;
     }
     const int esz = half ? 2 : 4;
     const int64_t in_span = int64_t(a.in.n - 1) * a.in.sn + int64_t(a.in.h - 1) * a.in.sh + int64_t(a.in.w - 1) * a.in.sw + a.in.c;

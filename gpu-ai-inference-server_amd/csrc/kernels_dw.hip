@@ -21,13 +21,12 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
 constexpr int kDwBlock = 256;
 
@@ -43,34 +42,6 @@ __device__ __forceinline__ float act_sel(int kind, float a, float b, float x) {
     const float g = hard ? h : sg;
     const float y = mul ? x * g : g;
     return kind == 0 ? x : (kind == 5 ? fmaxf(x, 0.f) : y);
-}
-
-// V consecutive elements (16 bytes) -> floats
-template <typename T>
-__device__ __forceinline__ void load16(const T* p, float* d);
-template <>
-__device__ __forceinline__ void load16<float>(const float* p, float* d) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
-}
-template <>
-__device__ __forceinline__ void load16<_Float16>(const _Float16* p, float* d) {
-    const h8v x = *reinterpret_cast<const h8v*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = float(x[i]);
-}
-template <typename T>
-__device__ __forceinline__ void store16(T* p, const float* v);
-template <>
-__device__ __forceinline__ void store16<float>(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <>
-__device__ __forceinline__ void store16<_Float16>(_Float16* p, const float* v) {
-    h8v o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = _Float16(v[i]);
-    *reinterpret_cast<h8v*>(p) = o;
 }
 
 // groups = N * OH * ceil(OW / PX) pixel groups; the grid holds cvn * nslots lanes, lane (slot, cv) walks groups slot, slot + nslots, ...
@@ -194,10 +165,6 @@ __global__ __launch_bounds__(kDwBlock) void conv_dw_kernel(const DwArgs a, const
     }
 }
 
-__device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
-    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
-}
-
 __global__ __launch_bounds__(kDwBlock) void conv_dw_generic_kernel(const DwArgs a, const int64_t total) {
     const int64_t idx = int64_t(blockIdx.x) * kDwBlock + threadIdx.x;
     if (idx >= total) return;
@@ -240,10 +207,6 @@ __global__ __launch_bounds__(kDwBlock) void conv_dw_generic_kernel(const DwArgs 
 
 constexpr int kDwPx[kNumConvDwTiles] = {1, 1, 2, 4};      // output pixels per lane of each tile (tile 0: the generic kernel)
 
-bool vec_view_ok(const TensorArg& t, int V) {
-    return t.sc == 1 && t.c % V == 0 && t.sw % V == 0 && t.sh % V == 0 && t.sn % V == 0 && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
-}
-
 template <typename T, int K, int S, bool ACT>
 hipError_t launch_fast(const DwArgs& a, int px, hipStream_t stream) {
     constexpr int V = 16 / int(sizeof(T));
@@ -284,10 +247,9 @@ bool ConvDwEligible(const DwArgs& a, int tile) {
     if (tile == 0) return true;
     if (a.act > 5 || a.pre_act > 5) return false;      // act_sel knows the sigmoid family and ReLU: a fused GELU runs on the generic kernel
     const int V = a.out.f16 ? 8 : 4;
-    return a.kh == a.kw && (a.kh == 3 || a.kh == 5) && a.sh == a.sw && (a.sh == 1 || a.sh == 2) && a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) &&
-           vec_view_ok(a.out, V) && (!a.res.p || (a.res.f16 == a.out.f16 && vec_view_ok(a.res, V))) && reinterpret_cast<uintptr_t>(a.w) % 16 == 0 &&
-           (!a.bias || reinterpret_cast<uintptr_t>(a.bias) % 16 == 0) &&
-           (!a.pre_scale || (reinterpret_cast<uintptr_t>(a.pre_scale) % 16 == 0 && reinterpret_cast<uintptr_t>(a.pre_shift) % 16 == 0));
+    return a.kh == a.kw && (a.kh == 3 || a.kh == 5) && a.sh == a.sw && (a.sh == 1 || a.sh == 2) && a.in.f16 == a.out.f16 && VecViewOk(a.in, V) &&
+           VecViewOk(a.out, V) && (!a.res.p || (a.res.f16 == a.out.f16 && VecViewOk(a.res, V))) && Aligned16(a.w) && (!a.bias || Aligned16(a.bias)) &&
+           (!a.pre_scale || (Aligned16(a.pre_scale) && Aligned16(a.pre_shift)));
 }
 
 hipError_t LaunchConvDw(const DwArgs& a, int tile, hipStream_t stream) {

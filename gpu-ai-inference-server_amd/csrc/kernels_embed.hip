@@ -26,12 +26,12 @@
 
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
-
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
 constexpr int kEmbBlock = 256;
 
@@ -57,13 +57,6 @@ __device__ __forceinline__ void load_row(const float* p, float* d) {
         d[k] = x.x; d[k + 1] = x.y; d[k + 2] = x.z; d[k + 3] = x.w;
     }
 }
-__device__ __forceinline__ void store_vec(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ void store_vec(_Float16* p, const float* v) {
-    h8v o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = _Float16(v[i]);
-    *reinterpret_cast<h8v*>(p) = o;
-}
 
 // output vector cv of a token row: word + type + pos (the fp32 sum every embed kernel starts from)
 template <int V>
@@ -71,13 +64,6 @@ __device__ __forceinline__ void sum_vec(const float* wrow, const float* trow, co
     load_row<V>(wrow + cv * V, x);
     if (trow) add_row<V>(trow + cv * V, x);
     if (prow) add_row<V>(prow + cv * V, x);
-}
-
-template <int LANES>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int m = LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LANES);
-    return v;
 }
 
 // rows = N * L token rows; cvn = D / V output vectors per row (<= LANES * NV); row r is written at r * a.out.sw
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(kEmbBlock) void embed_ln_kernel(const EmbedArgs a, 
         }
 #pragma unroll
         for (int v = 0; v < V; ++v) o[v] = fmaf(x[j][v] * rstd, g[v], b[v]);
-        store_vec(out + cv * V, o);
+        store16(out + cv * V, o);
     }
 }
 
@@ -185,7 +171,7 @@ __global__ __launch_bounds__(kEmbBlock) void embed_sum_kernel(const EmbedArgs a,
     for (int cv = lane; cv < cvn; cv += LANES) {
         float x[V];
         sum_vec<V>(wrow, trow, prow, cv, x);
-        store_vec(out + cv * V, x);
+        store16(out + cv * V, x);
     }
 }
 
@@ -244,8 +230,6 @@ hipError_t launch_fast(const EmbedArgs& a, int tile, int64_t rows, hipStream_t s
     }
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 }  // namespace
 
 bool EmbedEligible(const EmbedArgs& a, int tile) {
@@ -254,8 +238,8 @@ bool EmbedEligible(const EmbedArgs& a, int tile) {
     if (a.out.f8 || a.out.c < 1 || a.out.h != 1 || a.out.w < 1 || a.out.n < 0 || a.out.sn != int64_t(a.out.w) * a.out.sw) return false;
     if (tile == 0) return true;
     // (the offset is in the base pointer: its alignment stands for the offset condition)
-    return a.out.sc == 1 && EmbedTileFits(a.out.c, a.out.f16 != 0, a.out.sw, 0, tile) && aligned16(a.out.p) && aligned16(a.word) && (!a.type || aligned16(a.type)) &&
-           (!a.pos || aligned16(a.pos)) && (!a.gamma || aligned16(a.gamma)) && (!a.beta || aligned16(a.beta));
+    return a.out.sc == 1 && EmbedTileFits(a.out.c, a.out.f16 != 0, a.out.sw, 0, tile) && Aligned16(a.out.p) && Aligned16(a.word) && (!a.type || Aligned16(a.type)) &&
+           (!a.pos || Aligned16(a.pos)) && (!a.gamma || Aligned16(a.gamma)) && (!a.beta || Aligned16(a.beta));
 }
 
 hipError_t LaunchEmbed(const EmbedArgs& a, int tile, hipStream_t stream) {

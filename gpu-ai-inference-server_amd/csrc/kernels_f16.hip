@@ -9,14 +9,12 @@
 
 #include <cstdlib>
 
+#include "device_util.h"
 #include "igemm_tiles.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 // DIL: tap (ky, kx) reads input pixel (iy0 + ky*dh, ix0 + kx*dw) (ConvArgs::dh / dw), as in the fp32 kernel
 template <int BM, int BN, int WM, int WN, int KG, bool PRE, bool DIL = false>
@@ -104,8 +102,8 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_f16_kernel(const
     const int ish = int(a.in.sh), isw = int(a.in.sw);
     constexpr unsigned OOB = 0x80000000u;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w16), 0, Cout * Ktot * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w16), 0, Cout * Ktot * 2, kBufferRsrcFlags);
 
     int poff[A_IT];
     unsigned taps[A_IT];
@@ -254,7 +252,6 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void conv_igemm_f16_kernel(const
                 if (!mok) continue;
                 if (vec_store && n + 3 < Cout) {
                     if (store_half) {
-                        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
                         h4 hv = {_Float16(v[0]), _Float16(v[1]), _Float16(v[2]), _Float16(v[3])};
                         *reinterpret_cast<h4*>(outh + row + n) = hv;
                     } else {
@@ -288,9 +285,9 @@ static hipError_t launch_f16_t(const ConvArgs& a, int splitk, hipStream_t stream
     if (splitk > 1 && (a.workspace == nullptr || int64_t(splitk) * M * a.out.c > a.workspace_floats)) return hipErrorInvalidValue;
     // quad stores need 4-channel granularity and 8-/16-byte aligned quads in whichever buffer this launch writes
     int vec_store;
-    if (splitk > 1) vec_store = (a.out.c % 4 == 0) && (reinterpret_cast<uintptr_t>(a.workspace) % 16 == 0);
+    if (splitk > 1) vec_store = (a.out.c % 4 == 0) && Aligned16(a.workspace);
     else if (a.out.f16) vec_store = (a.out.c % 4 == 0) && (a.out.sw % 4 == 0) && (reinterpret_cast<uintptr_t>(a.out.p) % 8 == 0);
-    else vec_store = (a.out.c % 4 == 0) && (a.out.sw % 4 == 0) && (reinterpret_cast<uintptr_t>(a.out.p) % 16 == 0);
+    else vec_store = (a.out.c % 4 == 0) && (a.out.sw % 4 == 0) && Aligned16(a.out.p);
     conv_igemm_f16_kernel<t.bm, t.bn, t.wm, t.wn, t.kg, PRE, DIL>
         <<<dim3(num_tiles, splitk), dim3(64 * t.wm * t.wn * t.kg), f16_lds_bytes<T>(), stream>>>(a, tiles_n, num_tiles, vec_store);
     hipError_t e = hipGetLastError();
@@ -308,11 +305,9 @@ static hipError_t init_f16_t() {
 hipError_t LaunchConvIgemmF16(const ConvArgs& a_in, int tile, int splitk, hipStream_t stream) {
     ConvArgs a = a_in;
     if (!a.in.f16 || a.w16 == nullptr || a.out.sc != 1 || a.in.sc != 1) return hipErrorInvalidValue;
-    if ((a.in.c & 7) || (a.in.sw & 7) || (a.in.sh & 7) || (a.in.sn & 7) || (reinterpret_cast<uintptr_t>(a.in.p) & 15) ||
-        (reinterpret_cast<uintptr_t>(a.w16) & 15) || a.kh * a.kw > 32)
+    if ((a.in.c & 7) || (a.in.sw & 7) || (a.in.sh & 7) || (a.in.sn & 7) || !Aligned16(a.in.p) || !Aligned16(a.w16) || a.kh * a.kw > 32)
         return hipErrorInvalidValue;
-    if (a.pre_scale && (a.pre_scale16 == nullptr || a.pre_shift16 == nullptr || (reinterpret_cast<uintptr_t>(a.pre_scale16) & 15) ||
-                        (reinterpret_cast<uintptr_t>(a.pre_shift16) & 15)))
+    if (a.pre_scale && (a.pre_scale16 == nullptr || a.pre_shift16 == nullptr || !Aligned16(a.pre_scale16) || !Aligned16(a.pre_shift16)))
         return hipErrorInvalidValue;
     a.in_bytes = 2 * (int64_t(a.in.n - 1) * a.in.sn + int64_t(a.in.h - 1) * a.in.sh + int64_t(a.in.w - 1) * a.in.sw + int64_t(a.in.c - 1) + 1);
     if (a.in_bytes >= (int64_t(1) << 31) || int64_t(a.out.c) * a.kh * a.kw * a.in.c * 2 >= (int64_t(1) << 31)) return hipErrorInvalidValue;

@@ -14,35 +14,12 @@
 
 #include <cstdint>
 
+#include "device_util.h"
 #include "igemm_tiles.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef long i64x2 __attribute__((ext_vector_type(2)));
-
-constexpr float kE4m3Max = 448.0f;
-
-// four floats -> four e4m3 bytes (round to nearest even; the inputs are clamped to the finite range first, so nothing overflows
-// into the NaN encoding)
-__device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float d) {
-    a = __builtin_fminf(__builtin_fmaxf(a, -kE4m3Max), kE4m3Max);
-    b = __builtin_fminf(__builtin_fmaxf(b, -kE4m3Max), kE4m3Max);
-    c = __builtin_fminf(__builtin_fmaxf(c, -kE4m3Max), kE4m3Max);
-    d = __builtin_fminf(__builtin_fmaxf(d, -kE4m3Max), kE4m3Max);
-    int p = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    p = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, p, true);
-    return unsigned(p);
-}
-__device__ __forceinline__ void unpack4_e4m3(unsigned p, float* v) {
-    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(int(p), false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(int(p), true);
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
-}
 
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_f8_kernel(const ConvArgs a, const int tiles_n, const int num_tiles) {
@@ -123,8 +100,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_f8_kernel(const ConvA
     const int ish = int(a.in.sh), isw = int(a.in.sw);
     constexpr unsigned OOB = 0x80000000u;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w8), 0, Cout * Ktot, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w8), 0, Cout * Ktot, kBufferRsrcFlags);
 
     int poff[A_IT];
     unsigned taps[A_IT];
@@ -283,10 +260,10 @@ bool ConvF8Eligible(const ConvArgs& a, int tile) {
     if (tile < 0 || tile >= kNumConvF8Tiles) return false;
     if (!a.in.f8 || !a.out.f8 || a.w8 == nullptr || a.escale == nullptr || a.pre_scale != nullptr) return false;
     if (a.in.sc != 1 || a.out.sc != 1 || a.kh * a.kw > 32) return false;
-    if ((a.in.c & 15) || (a.in.sw & 15) || (a.in.sh & 15) || (a.in.sn & 15) || (reinterpret_cast<uintptr_t>(a.in.p) & 15)) return false;
-    if ((a.out.c & 15) || (a.out.sw & 15) || (reinterpret_cast<uintptr_t>(a.out.p) & 15)) return false;
-    if ((reinterpret_cast<uintptr_t>(a.w8) & 15) || (reinterpret_cast<uintptr_t>(a.escale) & 15) || (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15))) return false;
-    if (a.res.p && (!a.res.f8 || a.res.sc != 1 || (a.res.sw & 15) || (reinterpret_cast<uintptr_t>(a.res.p) & 15) || a.res.n != a.out.n || a.res.h != a.out.h ||
+    if ((a.in.c & 15) || (a.in.sw & 15) || (a.in.sh & 15) || (a.in.sn & 15) || !Aligned16(a.in.p)) return false;
+    if ((a.out.c & 15) || (a.out.sw & 15) || !Aligned16(a.out.p)) return false;
+    if (!Aligned16(a.w8) || !Aligned16(a.escale) || (a.bias && !Aligned16(a.bias))) return false;
+    if (a.res.p && (!a.res.f8 || a.res.sc != 1 || (a.res.sw & 15) || !Aligned16(a.res.p) || a.res.n != a.out.n || a.res.h != a.out.h ||
                     a.res.w != a.out.w || a.res.c != a.out.c))
         return false;
     const int64_t in_span = int64_t(a.in.n - 1) * a.in.sn + int64_t(a.in.h - 1) * a.in.sh + int64_t(a.in.w - 1) * a.in.sw + a.in.c;
@@ -417,7 +394,7 @@ __global__ void pool_f8_kernel(const PoolArgs a, const int64_t total) {
 
 hipError_t LaunchPoolF8(const PoolArgs& a, hipStream_t stream) {
     if (!a.in.f8 || !a.out.f8 || a.in.sc != 1 || a.out.sc != 1 || a.pre_scale != nullptr) return hipErrorInvalidValue;
-    if ((a.in.c & 15) || (a.in.sw & 15) || (a.out.sw & 15) || (reinterpret_cast<uintptr_t>(a.in.p) & 15) || (reinterpret_cast<uintptr_t>(a.out.p) & 15) ||
+    if ((a.in.c & 15) || (a.in.sw & 15) || (a.out.sw & 15) || !Aligned16(a.in.p) || !Aligned16(a.out.p) ||
         a.in.c != a.out.c)
         return hipErrorInvalidValue;
     const int64_t total = int64_t(a.out.n) * a.out.h * a.out.w * (a.out.c / 16);

@@ -21,27 +21,17 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "device_util.h"
 #include "env.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // Pad (floats) of the LDS pixel rows.  The fragment reads are ds_read_b128 at row * pitch + k-group * 4: with a pad of 4 two lanes of
 // every 16-lane service group share a 16-byte slot (2-way conflict on every read, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.42 in
 // profiles/r02); pitch = 8 mod 32 banks is conflict-free for channel counts that are multiples of 32 (kernels_direct.hip, launch_as_t).
 constexpr int kRowPad = 8;
-
-// Wave-uniform n / d on the scalar unit: mg = floor(2^32 / d) (2^32 - 1 for d == 1) undershoots the quotient by at most one.
-__device__ __forceinline__ unsigned udiv_uniform(unsigned n, unsigned d, unsigned mg) {
-    unsigned q = __umulhi(n, mg);
-    if (n - q * d >= d) ++q;
-    return q;
-}
 
 // PB: 16-pixel blocks per workgroup.  8 waves.  1x1: Cout == 128 (16 per wave).  3x3: stride 1, pad 1, Cout == 32, 9 * Cin3 / 16 <= 72 chunks.
 // OCC2: a variant meant to run TWO workgroups per CU (16-pixel tiles, <= 128 VGPRs, <= 80 KB of LDS): the old-channel loads are issued only
@@ -96,7 +86,7 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
 
     // ---- (a) bottleneck window loads (issued first: they are waited for first).  Window row w is pixel m0 - W - 1 + w: the rows before
     //      pixel 0 wrap to offsets above 2^31 and the rows from M on start past the last row's channels, both outside the descriptor ----
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(f.in3.p, 0, int((int64_t(M - 1) * bpitch + Cin3) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(f.in3.p, 0, int((int64_t(M - 1) * bpitch + Cin3) * 4), kBufferRsrcFlags);
     u32x4 wv[MAXW];
     {
         unsigned g = unsigned(m0 - W - 1) * unsigned(bpitch) * 4u + __umul24(wrow0, unsigned(bpitch) * 4u) + wc4 * 16u;      // (the byte pitch is the scalar factor: 24-bit products)
@@ -118,7 +108,7 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
     // ---- (b) the 3x3's weight fragments of this wave's K slice (fragment-major: 1 KiB per load; lane * 16 in the VGPR, the chunk scalar) ----
     const int cpt3 = Cin3 >> 4, total3 = 9 * cpt3;
     const int cb = (total3 * wave) >> 3, ce = (total3 * (wave + 1)) >> 3;
-    const __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.wfrag3), 0, 32 * 9 * Cin3 * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.wfrag3), 0, 32 * 9 * Cin3 * 4, kBufferRsrcFlags);
     u32x4 B3[MAXC3][TN3];
     {
         const unsigned l16 = (a.debug & 4) ? OOB : lane * 16u;
@@ -133,7 +123,7 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
     // ---- (c) the 1x1's old channels [0, Kold) of this tile's pixel rows: loads only, consumed after the 3x3.  A thread keeps ONE
     //      4-channel column for all its rows (rows advance by rpp per slot), so the prologue's scale/shift for that column is one pair
     //      of 16-byte loads issued here, not a dependent global round trip per slot later ----
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int((int64_t(M - 1) * ipitch + K) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int((int64_t(M - 1) * ipitch + K) * 4), kBufferRsrcFlags);
     u32x4 xv[MAXS];
     unsigned xg = unsigned(m0) * unsigned(ipitch) * 4u + __umul24(xrow0, unsigned(ipitch) * 4u) + xc4 * 16u;
     if (!xact || (a.debug & 8)) xg = OOB;
@@ -159,16 +149,16 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
     const unsigned fc2 = (tid & 15) * 2;               // this thread's channel pair of the fresh 32 (phase i)
     auto load_constants = [&]() {
         if constexpr (PRE) {
-            const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_scale), 0, K * 4, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rs_sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_shift), 0, K * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_scale), 0, K * 4, kBufferRsrcFlags);
+            const __amdgpu_buffer_rsrc_t rs_sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pre_shift), 0, K * 4, kBufferRsrcFlags);
             xsc = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_sc, xc4 * 16u, 0, 0));
             xsf = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_sf, xc4 * 16u, 0, 0));
             fsc = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_sc, fc2 * 4u, Kold * 4, 0));
             fsf = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_sf, fc2 * 4u, Kold * 4, 0));
         }
-        const __amdgpu_buffer_rsrc_t rs_b3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.bias3), 0, f.bias3 != nullptr ? 32 * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_b3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.bias3), 0, f.bias3 != nullptr ? 32 * 4 : 0, kBufferRsrcFlags);
         fb3 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_b3, fc2 * 4u, 0, 0));
-        const __amdgpu_buffer_rsrc_t rs_eb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias != nullptr ? 128 * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_eb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias != nullptr ? 128 * 4 : 0, kBufferRsrcFlags);
         ebias = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_eb, gk * 16u, nb * 64, 0));      // this lane's 4 output channels
     };
     if constexpr (!OCC2) load_constants();
@@ -265,7 +255,7 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
     }
 
     // ---- (f) prime the 1x1's weight ring (its latency hides behind the reduction and the staging below) ----
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, 128 * K * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, 128 * K * 4, kBufferRsrcFlags);
     u32x4 ring[D];
     int c_l = 0;
     const unsigned rl16 = (a.debug & 16) ? OOB : lane * 16u;
@@ -351,7 +341,7 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
         v += fb3;
         if constexpr (RELU3) v = __builtin_elementwise_max(v, f32x2{0.f, 0.f});
         if (!NSPLIT || blockIdx.y == 0) {
-            const __amdgpu_buffer_rsrc_t rs_o3 = __builtin_amdgcn_make_buffer_rsrc(f.out3.p, 0, int((int64_t(M - 1) * o3pitch + 32) * 4), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_o3 = __builtin_amdgcn_make_buffer_rsrc(f.out3.p, 0, int((int64_t(M - 1) * o3pitch + 32) * 4), kBufferRsrcFlags);
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rs_o3, fresh_g, 0, 0);
         }
         if constexpr (PRE) v = __builtin_elementwise_fma(v, fsc, fsf);
@@ -409,7 +399,7 @@ void conv_dense_fused_kernel(const ConvArgs a, const FusedArgs f, const int part
 
     // Epilogue: bias and ReLU are decided once per launch; the lane's row / quad offset is formed once, rows past M start behind the
     // descriptor's range ((M - 1) * pitch + 128 floats, pitch >= 128) and their stores are dropped
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + 128) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + 128) * 4), kBufferRsrcFlags);
     const unsigned o0 = unsigned(m0) * unsigned(opitch) * 4u + __umul24(r, unsigned(opitch) * 4u) + gk * 16u;
     auto finish = [&](auto relu_, auto bias_) {
         constexpr bool RELU = decltype(relu_)::value, BIAS = decltype(bias_)::value;
@@ -465,7 +455,7 @@ __global__ __launch_bounds__(512) void conv_dense_fused_ws_kernel(const ConvArgs
     const int ipitch = int(a.in.sw), opitch = int(a.out.sw), bpitch = int(f.in3.sw);
 
     // ---- phase 0 (all waves): window + old channels -> LDS; each role primes its weight ring ----
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(f.in3.p, 0, int((int64_t(M - 1) * bpitch + Cin3) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(f.in3.p, 0, int((int64_t(M - 1) * bpitch + Cin3) * 4), kBufferRsrcFlags);
     const int c4n3 = Cin3 >> 2;
     const int p_lo = m0 - W - 1;
     const int items3 = (PX + 2 * W + 2) * c4n3;
@@ -477,7 +467,7 @@ __global__ __launch_bounds__(512) void conv_dense_fused_ws_kernel(const ConvArgs
         const int p = p_lo + row;
         wv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, (idx < items3 && p >= 0 && p < M) ? unsigned(p * bpitch + c4 * 4) * 4u : OOB, 0, 0);
     }
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int((int64_t(M - 1) * ipitch + K) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int((int64_t(M - 1) * ipitch + K) * 4), kBufferRsrcFlags);
     const int c4n = Kold >> 2;
     const int rpp = NT / c4n;
     const int xrow0 = tid / c4n, xc4 = tid - xrow0 * c4n;
@@ -492,8 +482,8 @@ __global__ __launch_bounds__(512) void conv_dense_fused_ws_kernel(const ConvArgs
     // weight rings: one array, the role decides what it holds (3x3: D3 chunks x 2 channel blocks; 1x1: D chunks x 2 channel blocks)
     const int cpt3 = Cin3 >> 4, total3 = 9 * cpt3;
     const int cb = int(int64_t(total3) * wr / CW), ce = int(int64_t(total3) * (wr + 1) / CW);
-    const __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.wfrag3), 0, 32 * 9 * Cin3 * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, 128 * K * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.wfrag3), 0, 32 * 9 * Cin3 * 4, kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, 128 * K * 4, kBufferRsrcFlags);
     u32x4 ring[D][2];
     int c_l = 0;                                       // next chunk to load (role-relative)
     auto issue = [&](int slot) {
@@ -606,7 +596,7 @@ __global__ __launch_bounds__(512) void conv_dense_fused_ws_kernel(const ConvArgs
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         // final sum of a quarter of the tile: bias / ReLU of the 3x3, raw value to the block buffer, prologue'd value into the 1x1's rows
         {
-            const __amdgpu_buffer_rsrc_t rs_o3 = __builtin_amdgcn_make_buffer_rsrc(f.out3.p, 0, int((int64_t(M - 1) * int(f.out3.sw) + 32) * 4), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_o3 = __builtin_amdgcn_make_buffer_rsrc(f.out3.p, 0, int((int64_t(M - 1) * int(f.out3.sw) + 32) * 4), kBufferRsrcFlags);
             constexpr int ROWS = PX / CW;              // rows per 3x3 wave
             for (int idx = lane; idx < ROWS * 16; idx += 64) {
                 const int p = wr * ROWS + (idx >> 4), c2 = (idx & 15) * 2;
@@ -683,7 +673,7 @@ __global__ __launch_bounds__(512) void conv_dense_fused_ws_kernel(const ConvArgs
     for (int s = 0; s < D; ++s)
         if (s < rem) compute(s);
 
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + 128) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + 128) * 4), kBufferRsrcFlags);
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb) {
         const int m = m0 + pb * 16 + r;
@@ -772,10 +762,10 @@ bool ConvDenseFusedEligible(const ConvArgs& a, const FusedArgs& f, int tile) {
     if ((a.in.sw % 4) || (a.out.sw % 4) || (f.in3.sw % 4) || (f.out3.sw % 2)) return false;
     for (const void* p : {static_cast<const void*>(a.in.p), static_cast<const void*>(a.out.p), static_cast<const void*>(f.in3.p), static_cast<const void*>(a.wfrag),
                           static_cast<const void*>(f.wfrag3)})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+        if (!Aligned16(p)) return false;
     if (reinterpret_cast<uintptr_t>(f.out3.p) & 7) return false;
-    if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15)) return false;
-    if (a.pre_scale && ((reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift) & 15))) return false;
+    if (a.bias && !Aligned16(a.bias)) return false;
+    if (a.pre_scale && (!Aligned16(a.pre_scale) || !Aligned16(a.pre_shift))) return false;
     const int64_t M = int64_t(a.in.n) * a.in.h * a.in.w;
     if (M > 65536 || (M + 64) * a.in.sw * 4 >= (int64_t(1) << 31) || M * a.out.sw * 4 >= (int64_t(1) << 31) || (M + 64) * f.in3.sw * 4 >= (int64_t(1) << 31)) return false;
     const int px = 16 * pb;
@@ -783,7 +773,7 @@ bool ConvDenseFusedEligible(const ConvArgs& a, const FusedArgs& f, int tile) {
         const int c4n = (a.in.c - 32) / 4;
         if (c4n > 512 || (px + 512 / c4n - 1) / (512 / c4n) > (pb == 1 ? 8 : 16)) return false;
     }
-    if ((a.in.c - 32) % 4 || (reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (f.bias3 && (reinterpret_cast<uintptr_t>(f.bias3) & 7))) return false;
+    if ((a.in.c - 32) % 4 || !Aligned16(a.pre_scale) || (f.bias3 && (reinterpret_cast<uintptr_t>(f.bias3) & 7))) return false;
     if (int64_t(px + 2 * a.in.w + 2) * (f.in3.c / 4) > int64_t(8) * 512) return false;            // window slots
     if (!ws) {
         // window slots with one 4-channel column per thread (512 / columns rows per slot); 24-bit row * pitch products; every row a slot can

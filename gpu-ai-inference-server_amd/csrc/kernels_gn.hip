@@ -29,39 +29,12 @@
 
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
-
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-
-template <typename T>
-__device__ __forceinline__ void load16(const T* p, float* d);
-template <>
-__device__ __forceinline__ void load16<float>(const float* p, float* d) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
-}
-template <>
-__device__ __forceinline__ void load16<_Float16>(const _Float16* p, float* d) {
-    const h8v x = *reinterpret_cast<const h8v*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = float(x[i]);
-}
-template <typename T>
-__device__ __forceinline__ void store16(T* p, const float* v);
-template <>
-__device__ __forceinline__ void store16<float>(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <>
-__device__ __forceinline__ void store16<_Float16>(_Float16* p, const float* v) {
-    h8v o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = _Float16(v[i]);
-    *reinterpret_cast<h8v*>(p) = o;
-}
 
 // Chan's combine of (n, mean, m2) with (nb, mb, m2b); n + nb > 0
 __device__ __forceinline__ void chan(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
@@ -82,10 +55,6 @@ __device__ __forceinline__ float block_sum(float v, float* s_w) {
 #pragma unroll
     for (int w = 0; w < kGnBlock / 64; ++w) s += s_w[w];
     return s;
-}
-
-__device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
-    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
 }
 
 // grid.x = image * groups + group
@@ -243,10 +212,8 @@ __global__ __launch_bounds__(kGnBlock) void groupnorm_apply_kernel(const GnArgs 
     }
 }
 
-// tile 1's view: channels contiguous, whole 16-byte vectors, the pixels of an image one pitch apart
-bool vec_view_ok(const TensorArg& t, int V) {
-    return t.sc == 1 && t.c % V == 0 && t.sw % V == 0 && t.sn % V == 0 && t.sh == int64_t(t.w) * t.sw && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
-}
+// stricter than VecViewOk: tile 1 walks the h * w pixels of an image one pitch apart, so no gap between the rows of an image
+bool image_dense(const TensorArg& t) { return t.sh == int64_t(t.w) * t.sw; }
 
 template <typename T, int CPV>
 void launch_stats_cpv(const GnArgs& a, dim3 grid, int slab_px, int cvn, hipStream_t stream) {
@@ -286,8 +253,9 @@ bool GroupNormEligible(const GnArgs& a, int tile) {
     if (tile == 0) return true;
     const int V = a.out.f16 ? 8 : 4;
     const int64_t hw = int64_t(a.in.h) * a.in.w;
-    return GnTileFits(a.in.c, a.groups, a.out.f16 != 0, a.in.sw, 0, a.out.sw, 0, a.act, tile) && a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) && vec_view_ok(a.out, V) &&
-           hw < (int64_t(1) << 31) && a.in.n <= 65535 && a.workspace && a.workspace_floats >= GnWorkspaceFloats(a.in.n, hw, a.in.c, a.groups, a.out.f16 != 0);
+    return GnTileFits(a.in.c, a.groups, a.out.f16 != 0, a.in.sw, 0, a.out.sw, 0, a.act, tile) && a.in.f16 == a.out.f16 && VecViewOk(a.in, V) && image_dense(a.in) &&
+           VecViewOk(a.out, V) && image_dense(a.out) && hw < (int64_t(1) << 31) && a.in.n <= 65535 && a.workspace &&
+           a.workspace_floats >= GnWorkspaceFloats(a.in.n, hw, a.in.c, a.groups, a.out.f16 != 0);
 }
 
 hipError_t LaunchGroupNormPhase(const GnArgs& a, int phase, hipStream_t stream) {

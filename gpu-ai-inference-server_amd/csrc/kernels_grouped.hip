@@ -17,19 +17,14 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
 
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-
 constexpr int kGrpBlock = 256;     // 4 waves
-
-__device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
-    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
-}
 
 // GELU: the activation codes above 5 (kernels.h ApplyAct) are compiled in; the fast kernel leaves them out (ConvGroupedEligible keeps such steps off it)
 template <bool GELU>
@@ -50,24 +45,6 @@ __device__ __forceinline__ float epilogue(const GroupedArgs& a, float o) {
     if (a.hi < __builtin_huge_valf()) o = fminf(o, a.hi);
     if (a.act) o = GELU ? ApplyAct(a.act, a.act_a, a.act_b, o) : ApplyActBasic(a.act, a.act_a, a.act_b, o);
     return o;
-}
-
-// 16-byte vectors <-> floats
-__device__ __forceinline__ void load16(const float* p, float* d) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
-}
-__device__ __forceinline__ void load16(const _Float16* p, float* d) {
-    const h8v x = *reinterpret_cast<const h8v*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = float(x[i]);
-}
-__device__ __forceinline__ void store16(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ void store16(_Float16* p, const float* v) {
-    h8v o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = _Float16(v[i]);
-    *reinterpret_cast<h8v*>(p) = o;
 }
 
 // nb channel blocks x ptiles pixel tiles of 64 * PX pixels; wave w of the grid takes block w % nb of tile w / nb
@@ -114,7 +91,7 @@ __global__ __launch_bounds__(kGrpBlock) void conv_grouped_kernel(const GroupedAr
         for (int kx = 0; kx < a.kw; ++kx) {
             const int tap = ky * a.kw + kx;
             float xf[DOT ? 1 : PX][DOT ? 1 : XR];
-            h2v xh[DOT ? PX : 1][DOT ? XR : 1];
+            h2 xh[DOT ? PX : 1][DOT ? XR : 1];
 #pragma unroll
             for (int p = 0; p < PX; ++p) {
                 const int iy = py[p] * a.sh - a.pt + ky, ix = px[p] * a.sw - a.pl + kx;
@@ -133,7 +110,7 @@ __global__ __launch_bounds__(kGrpBlock) void conv_grouped_kernel(const GroupedAr
                 }
                 if constexpr (DOT) {
 #pragma unroll
-                    for (int c = 0; c < XR; ++c) xh[p][c] = h2v{_Float16(v[2 * c]), _Float16(v[2 * c + 1])};
+                    for (int c = 0; c < XR; ++c) xh[p][c] = h2{_Float16(v[2 * c]), _Float16(v[2 * c + 1])};
                 } else {
 #pragma unroll
                     for (int c = 0; c < XR; ++c) xf[p][c] = v[c];
@@ -144,10 +121,10 @@ __global__ __launch_bounds__(kGrpBlock) void conv_grouped_kernel(const GroupedAr
             for (int j = 0; j < OCB; ++j) {
                 const int64_t wrow = (int64_t(o0 + j) * KK + tap) * CPG;
                 if constexpr (DOT) {
-                    const h2v* wj = reinterpret_cast<const h2v*>(static_cast<const _Float16*>(a.w16) + wrow);
+                    const h2* wj = reinterpret_cast<const h2*>(static_cast<const _Float16*>(a.w16) + wrow);
 #pragma unroll
                     for (int c = 0; c < CPG / 2; ++c) {
-                        const h2v w2 = wj[c];
+                        const h2 w2 = wj[c];
 #pragma unroll
                         for (int p = 0; p < PX; ++p) acc[p][j] = __builtin_amdgcn_fdot2(xh[p][(j / OPB) * (CPG / 2) + c], w2, acc[p][j], false);
                     }
@@ -219,10 +196,6 @@ __global__ __launch_bounds__(kGrpBlock) void conv_grouped_generic_kernel(const G
     else a.out.p[oi] = v;
 }
 
-bool vec_view_ok(const TensorArg& t, int V) {
-    return t.sc == 1 && t.c % V == 0 && t.sw % V == 0 && t.sh % V == 0 && t.sn % V == 0 && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
-}
-
 template <typename T, int CFG, int PX>
 hipError_t launch_fast(const GroupedArgs& a, hipStream_t stream) {
     constexpr GroupedCfg c = kGroupedCfgs[CFG];
@@ -267,7 +240,7 @@ bool ConvGroupedEligible(const GroupedArgs& a, int tile) {
     if (cfg < 0 || !GroupedTileFits(cfg, f16, tile) || a.out.c % (kGroupedCfgs[cfg].opb * kGroupedCfgs[cfg].gpb)) return false;
     if (f16 && kGroupedCfgs[cfg].cpg % 2 == 0 && (!a.w16 || reinterpret_cast<uintptr_t>(a.w16) % 4)) return false;
     const int V = f16 ? 8 : 4;
-    return a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) && vec_view_ok(a.out, V) && (!a.res.p || (a.res.f16 == a.out.f16 && vec_view_ok(a.res, V)));
+    return a.in.f16 == a.out.f16 && VecViewOk(a.in, V) && VecViewOk(a.out, V) && (!a.res.p || (a.res.f16 == a.out.f16 && VecViewOk(a.res, V)));
 }
 
 hipError_t LaunchConvGrouped(const GroupedArgs& a, int tile, hipStream_t stream) {

@@ -18,49 +18,14 @@
 
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
 
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-
 constexpr int kLnBlock = 256;
-
-template <typename T>
-__device__ __forceinline__ void load16(const T* p, float* d);
-template <>
-__device__ __forceinline__ void load16<float>(const float* p, float* d) {
-    const float4 x = *reinterpret_cast<const float4*>(p);
-    d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
-}
-template <>
-__device__ __forceinline__ void load16<_Float16>(const _Float16* p, float* d) {
-    const h8v x = *reinterpret_cast<const h8v*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = float(x[i]);
-}
-template <typename T>
-__device__ __forceinline__ void store16(T* p, const float* v);
-template <>
-__device__ __forceinline__ void store16<float>(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <>
-__device__ __forceinline__ void store16<_Float16>(_Float16* p, const float* v) {
-    h8v o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = _Float16(v[i]);
-    *reinterpret_cast<h8v*>(p) = o;
-}
-
-// sum over the LANES lanes of a group (a power of two <= 64, groups aligned inside the wave); every lane of the wave takes part
-template <int LANES>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int m = LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LANES);
-    return v;
-}
 
 // rows: pixel rows of the view; cvn = C / V channel vectors per row (<= LANES * NV); row p starts at p * a.in.sw / p * a.out.sw
 template <typename T, int LANES, int NV>
@@ -119,10 +84,6 @@ __global__ __launch_bounds__(kLnBlock) void layernorm_kernel(const LnArgs a, con
     }
 }
 
-__device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
-    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
-}
-
 // one wave per pixel row (kLnBlock / 64 rows per workgroup)
 __global__ __launch_bounds__(kLnBlock) void layernorm_generic_kernel(const LnArgs a, const int64_t rows) {
     const int lane = int(threadIdx.x) % 64;
@@ -151,11 +112,6 @@ __global__ __launch_bounds__(kLnBlock) void layernorm_generic_kernel(const LnArg
         if (a.out.f16) reinterpret_cast<_Float16*>(a.out.p)[oi] = _Float16(o);
         else a.out.p[oi] = o;
     }
-}
-
-// the fast kernel's view: channels contiguous, whole 16-byte vectors, pixel rows one pitch apart through the whole tensor
-bool vec_view_ok(const TensorArg& t, int V) {
-    return t.sc == 1 && t.c % V == 0 && t.sw % V == 0 && t.sh == int64_t(t.w) * t.sw && t.sn == int64_t(t.h) * t.sh && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
 }
 
 template <typename T, int LANES, int NV>
@@ -194,8 +150,9 @@ bool LayerNormEligible(const LnArgs& a, int tile) {
     if (a.in.f8 || a.out.f8 || a.in.c < 1 || a.in.c != a.out.c || a.in.n != a.out.n || a.in.h != a.out.h || a.in.w != a.out.w) return false;
     if (tile == 0) return true;
     const int V = a.out.f16 ? 8 : 4;
-    return LnTileFits(a.in.c, a.out.f16 != 0, tile) && a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) && vec_view_ok(a.out, V) &&
-           reinterpret_cast<uintptr_t>(a.gamma) % 16 == 0 && (!a.beta || reinterpret_cast<uintptr_t>(a.beta) % 16 == 0);
+    // stricter than VecViewOk alone: the fast kernel walks n * h * w pixel rows one pitch apart (RowsDense)
+    return LnTileFits(a.in.c, a.out.f16 != 0, tile) && a.in.f16 == a.out.f16 && VecViewOk(a.in, V) && RowsDense(a.in) &&
+           VecViewOk(a.out, V) && RowsDense(a.out) && Aligned16(a.gamma) && (!a.beta || Aligned16(a.beta));
 }
 
 hipError_t LaunchLayerNorm(const LnArgs& a, int tile, hipStream_t stream) {

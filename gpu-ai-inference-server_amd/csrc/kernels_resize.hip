@@ -16,7 +16,9 @@
 #include <cmath>
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
@@ -91,11 +93,11 @@ __global__ __launch_bounds__(kResizeBlock) void resize_generic_kernel(const Resi
 template <typename T> struct Vec;
 template <> struct Vec<float> {
     static constexpr int V = 4;
-    typedef float v_t __attribute__((ext_vector_type(4)));
+    typedef f32x4 v_t;
 };
 template <> struct Vec<_Float16> {
     static constexpr int V = 8;
-    typedef _Float16 v_t __attribute__((ext_vector_type(8)));
+    typedef h8 v_t;
 };
 
 template <typename T>
@@ -158,7 +160,7 @@ int ResizePath(const ResizeArgs& a) {
     if (a.in.f16 != a.out.f16) return 0;
     const int V = a.in.f16 ? 8 : 4;
     const bool ok = a.in.c % V == 0 && a.in.sw % V == 0 && a.in.sh % V == 0 && a.in.sn % V == 0 && a.out.sw % V == 0 && a.out.sh % V == 0 &&
-                    a.out.sn % V == 0 && (reinterpret_cast<uintptr_t>(a.in.p) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.out.p) & 15) == 0;
+                    a.out.sn % V == 0 && Aligned16(a.in.p) && Aligned16(a.out.p);
     return ok ? 1 : 0;
 }
 

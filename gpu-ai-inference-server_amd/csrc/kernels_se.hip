@@ -23,12 +23,12 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
-
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
 constexpr int kSeBlock = 256;
 constexpr int kSeVecs = 64;           // channel vectors per squeeze workgroup
@@ -36,29 +36,16 @@ constexpr int kFc1Images = 16;       // images per fc1 wave
 constexpr int kFc2Images = 8;        // images per fc2 lane
 constexpr int kFc2Tile = 256;        // hidden units staged in LDS per pass
 
-// V consecutive elements -> floats (V = 16 bytes' worth, or 1)
+// V consecutive elements <-> floats (V = 16 bytes' worth, or 1)
 template <typename T, int V>
 __device__ __forceinline__ void ldv(const T* p, float* d) {
     if constexpr (V == 1) d[0] = float(*p);
-    else if constexpr (sizeof(T) == 4) {
-        const float4 x = *reinterpret_cast<const float4*>(p);
-        d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
-    } else {
-        const h8v x = *reinterpret_cast<const h8v*>(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) d[i] = float(x[i]);
-    }
+    else load16<T>(p, d);
 }
 template <typename T, int V>
 __device__ __forceinline__ void stv(T* p, const float* v) {
     if constexpr (V == 1) *p = T(v[0]);
-    else if constexpr (sizeof(T) == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else {
-        h8v o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = _Float16(v[i]);
-        *reinterpret_cast<h8v*>(p) = o;
-    }
+    else store16<T>(p, v);
 }
 
 struct SeWs {
@@ -205,10 +192,6 @@ __global__ __launch_bounds__(kSeBlock) void se_apply_kernel(const TensorArg in, 
     stv<T, V>(reinterpret_cast<T*>(out.p) + int64_t(n) * out.sn + int64_t(y) * out.sh + int64_t(x) * out.sw + c, v);
 }
 
-bool vec_ok(const TensorArg& t, int V) {
-    return t.sc == 1 && t.c % V == 0 && t.sw % V == 0 && t.sh % V == 0 && t.sn % V == 0 && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
-}
-
 template <typename T, int V>
 hipError_t launch_phase(const SeArgs& a, int phase, hipStream_t stream) {
     const SeWs ws = se_ws(a);
@@ -246,7 +229,7 @@ bool SqueezeExciteEligible(const SeArgs& a) {
 hipError_t LaunchSqueezeExcitePhase(const SeArgs& a, int phase, hipStream_t stream) {
     if (!SqueezeExciteEligible(a) || phase < 0 || phase > 3) return hipErrorInvalidValue;
     const int V = a.in.f16 ? 8 : 4;
-    const bool vec = vec_ok(a.in, V) && vec_ok(a.out, V);
+    const bool vec = VecViewOk(a.in, V) && VecViewOk(a.out, V);
     if (a.in.f16) return vec ? launch_phase<_Float16, 8>(a, phase, stream) : launch_phase<_Float16, 1>(a, phase, stream);
     return vec ? launch_phase<float, 4>(a, phase, stream) : launch_phase<float, 1>(a, phase, stream);
 }

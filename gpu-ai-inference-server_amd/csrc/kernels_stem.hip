@@ -17,21 +17,15 @@
 // 112 x 112 x 64 tensor between the two ops -- the largest of the whole network -- is never written or read.
 #include <hip/hip_runtime.h>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 #ifndef STEM_ABLATE
 #define STEM_ABLATE 0     // scripts/probes/stem_probe.cpp builds variants with parts of the kernel switched off
 #endif
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 struct StemGeom {
     int tiles_x, tiles_y, num_tiles;
@@ -85,7 +79,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_stem_kernel(const ConvArgs a,
     // ---- preamble: weights [Cout][KH][KW][CIN] (fp32) -> sWt[n][(c*KH + ky)*8 + kx], zero padded; eight independent loads in flight per
     //      thread (one dependent load per trip cost every workgroup ~40 L2 round trips before its first tile) ----
     {
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, Cout * KH * KW * CIN * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, Cout * KH * KW * CIN * 4, kBufferRsrcFlags);
         constexpr int WTRIPS = ((64 * KP + NT - 1) / NT + 7) / 8 * 8;
         for (int t0 = 0; t0 < WTRIPS; t0 += 8) {
             float wv[8];
@@ -108,10 +102,10 @@ __global__ __launch_bounds__(64 * WAVES) void conv_stem_kernel(const ConvArgs a,
     }
     for (int q = tid; q < 64; q += NT) sBias[q] = (a.bias != nullptr && q < Cout) ? a.bias[q] : 0.f;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
     const int esz = a.out.f8 ? 1 : (a.out.f16 ? 2 : 4);
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
-        a.out.p, 0, int((int64_t(a.out.n) * a.out.h * a.out.w - 1) * opitch * esz + Cout * esz), 0x00020000);
+        a.out.p, 0, int((int64_t(a.out.n) * a.out.h * a.out.w - 1) * opitch * esz + Cout * esz), kBufferRsrcFlags);
 
     // The window gather: element e = tid + i * NT of the window is (c, wy, wx) whatever the tile, so its offset relative to the window's
     // corner and its LDS slot are computed ONCE; per tile a load costs two compares and an add.  (Recomputing them per tile let the
@@ -392,7 +386,7 @@ bool ConvStemEligible(const ConvArgs& a) {
     if (a.in.f16 || a.in.c != 3 || a.kh != 7 || a.kw != 7 || a.sh != 2 || a.sw != 2 || a.pt != 3 || a.pl != 3) return false;
     if (a.pre_scale != nullptr || a.w == nullptr) return false;
     if (a.in.sw != 1 || a.in.sh != a.in.w || a.in.sc != int64_t(a.in.h) * a.in.w || a.in.sn != a.in.sc * a.in.c) return false;   // dense NCHW
-    if (a.out.sc != 1 || a.out.c > 64 || (a.out.c & 7) || (a.out.sw & 7) || (reinterpret_cast<uintptr_t>(a.out.p) & 15)) return false;
+    if (a.out.sc != 1 || a.out.c > 64 || (a.out.c & 7) || (a.out.sw & 7) || !Aligned16(a.out.p)) return false;
     if (a.out.f8 && ((a.out.c & 15) || (a.out.sw & 15))) return false;
     if (a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh) return false;
     if (a.out.h != (a.in.h + 6 - 7) / 2 + 1 || a.out.w != (a.in.w + 6 - 7) / 2 + 1) return false;
@@ -401,18 +395,7 @@ bool ConvStemEligible(const ConvArgs& a) {
 }
 
 // 16-byte gathers: every image row starts on a 16-byte boundary
-static bool stem_vec_ok(const ConvArgs& a) { return (a.in.w & 3) == 0 && (reinterpret_cast<uintptr_t>(a.in.p) & 15) == 0; }
-
-static int stem_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        cus = prop.multiProcessorCount;
-    }
-    return cus;
-}
+static bool stem_vec_ok(const ConvArgs& a) { return (a.in.w & 3) == 0 && Aligned16(a.in.p); }
 
 template <typename T>
 static hipError_t launch_stem_t(const ConvArgs& a, hipStream_t stream) {
@@ -423,7 +406,7 @@ static hipError_t launch_stem_t(const ConvArgs& a, hipStream_t stream) {
     g.num_tiles = a.out.n * g.tiles_x * g.tiles_y;
     g.oh = a.out.h; g.ow = a.out.w;
     const size_t lds = stem_lds_bytes<T, 3, 7, 7, 2, WAVES>();
-    const int cus = stem_cus();
+    const int cus = DeviceCus();
     if (cus == 0) return hipErrorUnknown;
     int per_cu = int((size_t(160) * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
@@ -448,7 +431,7 @@ bool ConvStemPoolEligible(const ConvArgs& a) {
     if (a.in.f16 || a.in.f8 || a.in.c != 3 || a.kh != 7 || a.kw != 7 || a.sh != 2 || a.sw != 2 || a.pt != 3 || a.pl != 3) return false;
     if (a.pre_scale != nullptr || a.w == nullptr || !a.relu || a.res.p != nullptr) return false;      // the ReLU makes 0 the neutral element of the max
     if (a.in.sw != 1 || a.in.sh != a.in.w || a.in.sc != int64_t(a.in.h) * a.in.w || a.in.sn != a.in.sc * a.in.c) return false;   // dense NCHW
-    if (a.out.sc != 1 || a.out.c > 64 || (a.out.c & 7) || (a.out.sw & 7) || (reinterpret_cast<uintptr_t>(a.out.p) & 15)) return false;
+    if (a.out.sc != 1 || a.out.c > 64 || (a.out.c & 7) || (a.out.sw & 7) || !Aligned16(a.out.p)) return false;
     if (a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh) return false;
     const int oh = (a.in.h + 6 - 7) / 2 + 1, ow = (a.in.w + 6 - 7) / 2 + 1;          // the conv's output
     if (oh < 1 || ow < 1 || a.out.h != (oh + 2 - 3) / 2 + 1 || a.out.w != (ow + 2 - 3) / 2 + 1) return false;   // 3x3 / s2 / p1 windows over it
@@ -465,7 +448,7 @@ static hipError_t launch_stem_pool_t(const ConvArgs& a, hipStream_t stream) {
     g.num_tiles = a.out.n * g.tiles_x * g.tiles_y;
     g.oh = (a.in.h + 6 - 7) / 2 + 1; g.ow = (a.in.w + 6 - 7) / 2 + 1;
     const size_t lds = stem_lds_bytes<T, 3, 7, 7, 2, WAVES, true>();
-    const int cus = stem_cus();
+    const int cus = DeviceCus();
     if (cus == 0) return hipErrorUnknown;
     const int per_cu = int((size_t(160) * 1024) / lds) >= 2 ? 2 : 1;
     const int slots = cus * per_cu;

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
@@ -72,7 +73,7 @@ hipError_t launch(const TokenAssembleArgs& a, hipStream_t stream) {
 
 bool TokenAssembleVectorised(const TokenAssembleArgs& a) {
     const int V = a.out.f16 ? 8 : 4;
-    auto ok = [&](const TensorArg& t) { return t.c % V == 0 && t.sw % V == 0 && t.sn % V == 0 && reinterpret_cast<uintptr_t>(t.p) % 16 == 0; };
+    auto ok = [&](const TensorArg& t) { return t.c % V == 0 && t.sw % V == 0 && t.sn % V == 0 && Aligned16(t.p); };
     return args_ok(a) && ok(a.in) && ok(a.out);
 }
 

@@ -22,22 +22,14 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "device_util.h"
 #include "env.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// Wave-uniform n / d on the scalar unit: mg = floor(2^32 / d) (2^32 - 1 for d == 1) undershoots the quotient by at most one.
-__device__ __forceinline__ unsigned udiv_uniform(unsigned n, unsigned d, unsigned mg) {
-    unsigned q = __umulhi(n, mg);
-    if (n - q * d >= d) ++q;
-    return q;
-}
 
 // v * s for factors below 2^24 on the full-rate 24-bit multiplier, s wave-uniform (a kernel argument or derived from one).  Written as the
 // instruction itself: the optimiser rewrites __umul24 into a 32-bit multiply -- quarter rate -- wherever it learns the range of one operand, and the
@@ -121,7 +113,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_pooled_kernel(const ConvAr
     const int m0 = blockIdx.x * (16 * PB), n0 = blockIdx.y * BN + wave * BNW;
     const int ipitch = int(p.pin.sw), opitch = int(a.out.sw);
 
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, Cout * K * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, Cout * K * 4, kBufferRsrcFlags);
     const int nb = n0 >> 4;
     AsLoop<TNW, PB, D> loop;
     unsigned wlane = unsigned(tid & 63) * 16u;
@@ -142,9 +134,9 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_pooled_kernel(const ConvAr
         const int col = tid & (CT - 1), row0 = tid >> cs;
         const unsigned IH = unsigned(p.pin.h), IW = unsigned(p.pin.w), OH = unsigned(a.out.h), OW = unsigned(a.out.w);
         const int in_px = p.pin.n * p.pin.h * p.pin.w;
-        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(p.pin.p, 0, ((in_px - 1) * ipitch + K) * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.pool_scale), 0, PRE ? K * 4 : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.pool_shift), 0, PRE ? K * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(p.pin.p, 0, ((in_px - 1) * ipitch + K) * 4, kBufferRsrcFlags);
+        const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.pool_scale), 0, PRE ? K * 4 : 0, kBufferRsrcFlags);
+        const __amdgpu_buffer_rsrc_t rs_sf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.pool_shift), 0, PRE ? K * 4 : 0, kBufferRsrcFlags);
         // the tile's first pixel, on the scalar unit
         const unsigned ohw = OH * OW;
         const unsigned b0 = udiv_uniform(unsigned(m0), ohw, p.k.mg32_ohw), rem0 = unsigned(m0) - b0 * ohw;
@@ -239,8 +231,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_pooled_kernel(const ConvAr
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     {
         const __amdgpu_buffer_rsrc_t rs_out =
-            __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias != nullptr ? Cout * 4 : 0, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), kBufferRsrcFlags);
+        const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias != nullptr ? Cout * 4 : 0, kBufferRsrcFlags);
         const unsigned o0 = (unsigned(m0) * unsigned(opitch) + mul24(r, opitch) + 4 * gk) * 4u;
         const unsigned ostep = unsigned(opitch) * 64u;
         auto finish = [&](auto relu_, auto bias_) {            // bias and ReLU are decided once, not per element
@@ -271,14 +263,14 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_pooled_kernel(const ConvAr
     if constexpr (CHAIN) {
         // ---- the entry 1x1 of the next block on the tile just stored: K2 = Cout, 16 output channels per wave ----
         const int K2 = Cout, P2 = K2 + pad, CH2 = K2 >> 4, Cout2 = p.out2.c;
-        const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wfrag2), 0, Cout2 * K2 * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wfrag2), 0, Cout2 * K2 * 4, kBufferRsrcFlags);
         AsLoop<1, PB, D> loop2;
 #pragma unroll
         for (int s = 0; s < D; ++s) loop2.issue(rs_w2, wlane, wave, CH2, s);       // in flight across the two barriers
         __syncthreads();                                                           // every wave has left the first loop: the staging area is free
         {
-            const __amdgpu_buffer_rsrc_t rs_s2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.scale2), 0, K2 * 4, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rs_t2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.shift2), 0, K2 * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_s2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.scale2), 0, K2 * 4, kBufferRsrcFlags);
+            const __amdgpu_buffer_rsrc_t rs_t2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.shift2), 0, K2 * 4, kBufferRsrcFlags);
             const bool relu2 = __builtin_amdgcn_readfirstlane(p.pre_relu2) != 0;
 #pragma unroll
             for (int j = 0; j < TNW; ++j) {
@@ -299,8 +291,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_pooled_kernel(const ConvAr
         loop2.run(rs_w2, wlane, wave, CH2, sA, P2, r, gk, acc2);
         const int opitch2 = int(p.out2.sw);
         const __amdgpu_buffer_rsrc_t rs_out2 =
-            __builtin_amdgcn_make_buffer_rsrc(p.out2.p, 0, int((int64_t(M - 1) * opitch2 + Cout2) * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_b2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias2), 0, p.bias2 != nullptr ? Cout2 * 4 : 0, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(p.out2.p, 0, int((int64_t(M - 1) * opitch2 + Cout2) * 4), kBufferRsrcFlags);
+        const __amdgpu_buffer_rsrc_t rs_b2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias2), 0, p.bias2 != nullptr ? Cout2 * 4 : 0, kBufferRsrcFlags);
         const unsigned o2 = (unsigned(m0) * unsigned(opitch2) + mul24(r, opitch2) + 4 * gk) * 4u;
         f32x4 bq = zero;
         if (p.bias2 != nullptr) bq = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b2, unsigned(gk) * 16u, wave * 64, 0));
@@ -327,8 +319,6 @@ constexpr TransTile kTransTiles[kNumConvPooledTiles] = {{8, 1, 2, true}, {4, 1, 
 
 unsigned mg20(unsigned d) { return ((1u << 20) + d - 1) / d; }
 unsigned mg32(unsigned d) { return d == 1 ? 0xffffffffu : unsigned((uint64_t(1) << 32) / d); }
-
-bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // log2 of the staging loop's column count, as launch_as_t picks it: fewest row groups first, then fewest load slots, then the widest block
 int col_shift(int K, int threads, int rows) {
@@ -412,14 +402,14 @@ bool ConvPooledEligible(const ConvArgs& a, const PooledArgs& p, int tile, bool c
     if (a.in.f16 || a.out.f16 || a.in.f8 || a.out.f8 || a.wfrag == nullptr || a.res.p != nullptr || a.pre_scale != nullptr) return false;
     if (a.kh != 1 || a.kw != 1 || a.sh != 1 || a.sw != 1 || a.pt != 0 || a.pl != 0) return false;
     if (a.out.h != a.in.h || a.out.w != a.in.w || a.out.n != a.in.n) return false;
-    if (a.out.sc != 1 || (a.out.sw % 4) || a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh || !aligned16(a.out.p)) return false;
-    if (!aligned16(a.wfrag) || (a.bias && !aligned16(a.bias))) return false;
+    if (a.out.sc != 1 || (a.out.sw % 4) || a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh || !Aligned16(a.out.p)) return false;
+    if (!Aligned16(a.wfrag) || (a.bias && !Aligned16(a.bias))) return false;
     // the pool's input: an NHWC channel slice at twice the resolution, pixels at a constant pitch
     const TensorArg& x = p.pin;
     if (x.p == nullptr || x.f16 || x.f8 || x.sc != 1 || x.c != a.in.c || x.n != a.in.n || x.h != 2 * a.in.h || x.w != 2 * a.in.w) return false;
-    if ((x.sw % 4) || x.sw < x.c || x.sh != x.w * x.sw || x.sn != x.h * x.sh || !aligned16(x.p)) return false;
+    if ((x.sw % 4) || x.sw < x.c || x.sh != x.w * x.sw || x.sn != x.h * x.sh || !Aligned16(x.p)) return false;
     if ((p.pool_scale == nullptr) != (p.pool_shift == nullptr)) return false;
-    if (p.pool_scale && (!aligned16(p.pool_scale) || !aligned16(p.pool_shift))) return false;
+    if (p.pool_scale && (!Aligned16(p.pool_scale) || !Aligned16(p.pool_shift))) return false;
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
     if (M <= 0 || M > (int64_t(1) << 22) || a.out.h > 512 || a.out.w > 512) return false;       // 2^20 reciprocals: (extent + 31) * extent < 2^20
     // rows past M map up to 32 images past the last one: their pixel index and byte offset must not wrap (24-bit factors, 32-bit offsets)
@@ -431,10 +421,10 @@ bool ConvPooledEligible(const ConvArgs& a, const PooledArgs& p, int tile, bool c
     if (!chain) return true;
     // the entry conv: reads exactly the tile just stored, 16 output channels per wave
     const TensorArg& o2 = p.out2;
-    if (p.wfrag2 == nullptr || !aligned16(p.wfrag2) || p.scale2 == nullptr || p.shift2 == nullptr || !aligned16(p.scale2) || !aligned16(p.shift2)) return false;
-    if (p.bias2 && !aligned16(p.bias2)) return false;
+    if (p.wfrag2 == nullptr || !Aligned16(p.wfrag2) || p.scale2 == nullptr || p.shift2 == nullptr || !Aligned16(p.scale2) || !Aligned16(p.shift2)) return false;
+    if (p.bias2 && !Aligned16(p.bias2)) return false;
     if (o2.p == nullptr || o2.f16 || o2.f8 || o2.sc != 1 || o2.n != a.out.n || o2.h != a.out.h || o2.w != a.out.w) return false;
-    if ((o2.sw % 4) || o2.sh != o2.w * o2.sw || o2.sn != o2.h * o2.sh || !aligned16(o2.p)) return false;
+    if ((o2.sw % 4) || o2.sh != o2.w * o2.sw || o2.sn != o2.h * o2.sh || !Aligned16(o2.p)) return false;
     if (o2.sw >= (int64_t(1) << 22) || (M + 32) * o2.sw * 4 >= (int64_t(1) << 31)) return false;
     return true;
 }

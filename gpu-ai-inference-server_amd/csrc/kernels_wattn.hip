@@ -24,26 +24,16 @@
 
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8v __attribute__((ext_vector_type(8)));
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-
 constexpr int kWinBlock = 256;
 constexpr int kWinWaves = kWinBlock / 64;
 constexpr float kLog2e = 1.4426950408889634f;
-
-__device__ __forceinline__ float ld_any(const float* p, int f16, int64_t i) {
-    return f16 ? float(reinterpret_cast<const _Float16*>(p)[i]) : p[i];
-}
-__device__ __forceinline__ void st_any(float* p, int f16, int64_t i, float v) {
-    if (f16) reinterpret_cast<_Float16*>(p)[i] = _Float16(v);
-    else p[i] = v;
-}
 
 // the map pixel (y, x) of token t of window (wy, wx)
 __device__ __forceinline__ void tok_yx(const WinAttnArgs& a, int wy, int wx, int t, int& y, int& x) {
@@ -117,8 +107,6 @@ __global__ __launch_bounds__(kWinBlock) void window_attention_generic_kernel(con
     }
 }
 
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
 // dynamic LDS of the MFMA kernel: per wave the K and V rows of one window, Lp rows of hd + one vector
 constexpr int64_t WinAttnLdsBytes(int64_t Lp, int hd, bool f16) { return kWinWaves * 2 * Lp * (int64_t(hd) * (f16 ? 2 : 4) + 16); }
 
@@ -188,10 +176,10 @@ __global__ __launch_bounds__(kWinBlock) void window_attention_mfma_kernel(const 
         tok_yx_fast(a, inv_ww, wy, wx, qi, qy, qx);
         const T* qrow = base + int64_t(qy) * a.in.sh + int64_t(qx) * a.in.sw + hf * HH;
         float4 q4[F16 ? 1 : HH / 4];               // this lane's half of its Q row
-        h8v q8[F16 ? HH / 8 : 1];
+        h8 q8[F16 ? HH / 8 : 1];
         if constexpr (F16) {
 #pragma unroll
-            for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8v*>(qrow + 8 * k);
+            for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8*>(qrow + 8 * k);
         } else {
 #pragma unroll
             for (int k = 0; k < HH / 4; ++k) q4[k] = *reinterpret_cast<const float4*>(qrow + 4 * k);
@@ -218,7 +206,7 @@ __global__ __launch_bounds__(kWinBlock) void window_attention_mfma_kernel(const 
             if constexpr (F16) {
 #pragma unroll
                 for (int k = 0; k < HH; k += 8)
-                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8v*>(krow + k), q8[k / 8], s[kt], 0, 0, 0);
+                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(krow + k), q8[k / 8], s[kt], 0, 0, 0);
             } else {
 #pragma unroll
                 for (int k = 0; k < HH; k += 4) {
@@ -253,7 +241,7 @@ __global__ __launch_bounds__(kWinBlock) void window_attention_mfma_kernel(const 
             if constexpr (F16) {
 #pragma unroll
                 for (int st = 0; st < 2; ++st) {
-                    h8v pb, va0;
+                    h8 pb, va0;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const int key = 32 * kt + 16 * st + 8 * (j >> 2) + 4 * hf + (j & 3);
@@ -278,20 +266,15 @@ __global__ __launch_bounds__(kWinBlock) void window_attention_mfma_kernel(const 
         for (int g = 0; g < 4; ++g) {
             const int e0 = 8 * g + 4 * hf;         // registers 4 g ... 4 g + 3 are the output columns e0 ... e0 + 3 of this lane's query
             if constexpr (F16) {
-                h4v x;
+                h4 x;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) x[t] = _Float16(o0[4 * g + t] * inv);
-                *reinterpret_cast<h4v*>(orow + e0) = x;
+                *reinterpret_cast<h4*>(orow + e0) = x;
             } else {
                 *reinterpret_cast<float4*>(orow + e0) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
             }
         }
     }
-}
-
-// the MFMA kernel's view: channels contiguous, pixel rows one pitch apart through the whole tensor, 16-byte aligned base
-bool vec_view_ok(const TensorArg& t, int V) {
-    return t.sc == 1 && t.c % V == 0 && t.sw % V == 0 && t.sh == int64_t(t.w) * t.sw && t.sn == int64_t(t.h) * t.sh && reinterpret_cast<uintptr_t>(t.p) % 16 == 0;
 }
 
 template <typename T, int HD>
@@ -346,7 +329,9 @@ bool WindowAttentionEligible(const WinAttnArgs& a, int tile) {
     if (tile == 0) return true;
     const int V = a.out.f16 ? 8 : 4;
     // (the offsets are in the base pointers: their alignment stands for the offset condition)
-    return a.in.f16 == a.out.f16 && vec_view_ok(a.in, V) && vec_view_ok(a.out, V) &&
+    // stricter than VecViewOk alone: RowsDense is the layer-norm tiles' condition, taken over with them; the MFMA kernel addresses by sn / sh / sw and
+    // would run without it, but the tile keeps accepting exactly the views it was tested on
+    return a.in.f16 == a.out.f16 && VecViewOk(a.in, V) && RowsDense(a.in) && VecViewOk(a.out, V) && RowsDense(a.out) &&
            WinAttnMfmaFits(int64_t(a.wh) * a.ww, a.head_dim, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.c, a.out.sw, 0);
 }
 
@@ -377,7 +362,7 @@ hipError_t LaunchPatchMerge(const PatchMergeArgs& a, hipStream_t stream) {
         return hipErrorInvalidValue;
     const int V = a.out.f16 ? 8 : 4;
     const bool vec = a.in.sc == 1 && a.out.sc == 1 && PatchMergeVec(a.in.f16 != 0, a.out.f16 != 0, a.in.c, a.in.sw, 0, a.out.sw, 0) && a.in.sh % V == 0 && a.in.sn % V == 0 &&
-                     a.out.sh % V == 0 && a.out.sn % V == 0 && reinterpret_cast<uintptr_t>(a.in.p) % 16 == 0 && reinterpret_cast<uintptr_t>(a.out.p) % 16 == 0;
+                     a.out.sh % V == 0 && a.out.sn % V == 0 && Aligned16(a.in.p) && Aligned16(a.out.p);
     if (vec) return a.out.f16 ? launch_merge<_Float16, 8>(a, stream) : launch_merge<float, 4>(a, stream);
     return launch_merge<float, 1>(a, stream);
 }

@@ -15,15 +15,11 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // U[xi = 4i + j][cout][cin] = (G g G^T)[i][j], G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]], stored fragment-major for the MFMA B operand:
 // element ((xi * (Cin/8) + ch8) * 64 + lane) * 4 + e  =  U[xi][cout = lane & 31][cin = ch8*8 + (lane >> 5)*4 + e]
@@ -158,8 +154,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, (
     const int y0 = 2 * ty0 - 1, x0 = 2 * tx0 - 1;
     const int ntiles = g.TR * g.TC;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, 16 * 32 * Cin * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wfrag), 0, 16 * 32 * Cin * 4, kBufferRsrcFlags);
 
     const int items = npx * 4;
     int woff[PITW];
@@ -215,7 +211,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, (
         for (int e = 0; e < 16; ++e) acc[xl][e] = 0.f;
     if constexpr (X6) {
         static_assert(NJ == 2, "the split variant is written for eight waves");
-        const __amdgpu_buffer_rsrc_t rs_ux = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w16), 0, 3 * 16 * 32 * Cin * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_ux = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w16), 0, 3 * 16 * 32 * Cin * 2, kBufferRsrcFlags);
         const int KB = Cin >> 4;
         const int plane_b = 16 * 32 * Cin * 2;          // bytes per plane
         u32x4 ux0[NJ][3], ux1[NJ][3];                   // U fragments: even / odd slices
@@ -399,7 +395,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, (
 
     // ---- output transform (as above: M through LDS in two halves) ----
     const __amdgpu_buffer_rsrc_t rs_out =
-        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(a.out.n) * H * W - 1) * opitch * 4 + 32 * 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(a.out.n) * H * W - 1) * opitch * 4 + 32 * 4), kBufferRsrcFlags);
     constexpr int OIT = (32 * 32 + NT - 1) / NT;
     float s0[OIT][4], s1[OIT][4];
 #pragma unroll
@@ -470,13 +466,13 @@ bool ConvWinoEligible(const ConvArgs& a, int tile) {
     if (a.out.h != a.in.h || a.out.w != a.in.w || a.out.n != a.in.n) return false;
     if (a.in.sc != 1 || a.out.sc != 1 || (a.in.sw & 3) || (a.out.sw & 3)) return false;
     if (a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh || a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh) return false;
-    if ((reinterpret_cast<uintptr_t>(a.in.p) & 15) || (reinterpret_cast<uintptr_t>(a.out.p) & 15) || (reinterpret_cast<uintptr_t>(a.wfrag) & 15)) return false;
-    if (a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15)) return false;
+    if (!Aligned16(a.in.p) || !Aligned16(a.out.p) || !Aligned16(a.wfrag)) return false;
+    if (a.bias && !Aligned16(a.bias)) return false;
     const int64_t M = int64_t(a.in.n) * a.in.h * a.in.w;
     if (M * a.in.sw * 4 >= (int64_t(1) << 31) || M * a.out.sw * 4 >= (int64_t(1) << 31)) return false;
     const WinoTile t = kWinoTiles[tile];
     if ((2 * t.tr + 2) * (2 * t.tc + 2) * 4 > 4 * 256) return false;      // window prefetch slots
-    if (tile >= 8 && (a.w16 == nullptr || (reinterpret_cast<uintptr_t>(a.w16) & 15))) return false;      // the split U mirror (IE_FP32_SPLIT=1)
+    if (tile >= 8 && (a.w16 == nullptr || !Aligned16(a.w16))) return false;      // the split U mirror (IE_FP32_SPLIT=1)
     return t.tr * t.tc <= 32 && wino_lds_bytes(t.tr, t.tc) <= size_t(64) * 1024;
 }
 

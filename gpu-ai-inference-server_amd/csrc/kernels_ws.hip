@@ -13,20 +13,15 @@
 // v_permlane32_swap the two half-waves exchange quads so that each lane stores 8 consecutive halfs (16 bytes).
 #include <hip/hip_runtime.h>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 #ifndef WS_ABLATE
 #define WS_ABLATE 0       // scripts/probes/ws_probe.cpp builds variants with parts of conv1x1_ws_f16_kernel switched off (timing only, wrong results)
 #endif
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
 // Register chunks (32 channels x 32 pixels = 2 KiB each) a wave keeps in flight: 4 beside 64 accumulator registers, 6 otherwise.
 constexpr int ws_ring_depth(int tn) { return tn >= 4 ? 4 : 6; }
@@ -61,7 +56,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f16_kernel(const ConvAr
     // Ring of register chunks with STATIC slots (the chunk loop below is unrolled by D, so the compiler's waitcnt pass sees the
     // loads in issue order and waits with exact counts, vmcnt(2(D-1)), instead of draining the ring).
     u32x4 ring[D][2];
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
     auto issue = [&](int slot) {
         const int m = rb_l * 32 + r;
         const unsigned off = (rb_l < nrb && m < M && WS_ABLATE != 5 && WS_ABLATE != 8) ? unsigned(m * ipitch + c_l * 32 + hh * 8) * 2u : OOB;
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f16_kernel(const ConvAr
         const int k8 = K >> 3;
         // U loads in flight per thread: a one-at-a-time loop would pay the L2 round trip BN*K/(8*NT) times in a row
         constexpr int U = 8;
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(w), 0, Cout * K * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(w), 0, Cout * K * 2, kBufferRsrcFlags);
         auto stage_trip = [&](int idx0) {
             u32x4 v[U];
 #pragma unroll
@@ -166,11 +161,11 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f16_kernel(const ConvAr
     const bool store_half = a.out.f16 != 0;
     const int esz = store_half ? 2 : 4;
     const int opitch = int(a.out.sw);
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * esz), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * esz), kBufferRsrcFlags);
     const bool has_res = a.res.p != nullptr;        // residual Add fused into the epilogue (same element type as the output)
     const int rpitch = int(a.res.sw);
     const __amdgpu_buffer_rsrc_t rs_res =
-        __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p : a.out.p, 0, has_res ? int((int64_t(M - 1) * rpitch + Cout) * esz) : 0, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p : a.out.p, 0, has_res ? int((int64_t(M - 1) * rpitch + Cout) * esz) : 0, kBufferRsrcFlags);
     const h2 relu_floor = a.relu ? h2{_Float16(0.f), _Float16(0.f)} : h2{-__builtin_inff16(), -__builtin_inff16()};       // FAST: ReLU = packed max with this
     auto epilogue = [&]() {
         const int m = rb_c * 32 + r;
@@ -206,8 +201,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f16_kernel(const ConvAr
                     const int n = n0 + j * 32 + 8 * g + 4 * hh;
                     const unsigned off = n < Cout ? rrow + unsigned(n * esz) : OOB;
                     if (store_half) {
-                        typedef unsigned u32x2r __attribute__((ext_vector_type(2)));
-                        const h4 rq = __builtin_bit_cast(h4, __builtin_bit_cast(u32x2r, __builtin_amdgcn_raw_buffer_load_b64(rs_res, off, 0, 0)));
+                        const h4 rq = __builtin_bit_cast(h4, __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_res, off, 0, 0)));
 #pragma unroll
                         for (int q = 0; q < 4; ++q) v[4 * g + q] += float(rq[q]);
                     } else {
@@ -226,7 +220,6 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f16_kernel(const ConvAr
                 for (int gp = 0; gp < 2; ++gp) {
                     const h4 qa = {_Float16(v[8 * gp + 0]), _Float16(v[8 * gp + 1]), _Float16(v[8 * gp + 2]), _Float16(v[8 * gp + 3])};
                     const h4 qb = {_Float16(v[8 * gp + 4]), _Float16(v[8 * gp + 5]), _Float16(v[8 * gp + 6]), _Float16(v[8 * gp + 7])};
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                     const u32x2 xa = __builtin_bit_cast(u32x2, qa), xb = __builtin_bit_cast(u32x2, qb);
                     const auto s0 = __builtin_amdgcn_permlane32_swap(xa[0], xb[0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane32_swap(xa[1], xb[1], false, false);
@@ -273,19 +266,18 @@ bool ConvWsEligible(const ConvArgs& a, int tile) {
     if (tile < 0 || tile >= kNumConvWs16Tiles) return false;
     if (!a.in.f16 || a.w16 == nullptr || a.kh != 1 || a.kw != 1 || a.sh != 1 || a.sw != 1 || a.pt != 0 || a.pl != 0) return false;
     if (a.in.sc != 1 || a.out.sc != 1 || a.in.h != a.out.h || a.in.w != a.out.w) return false;
-    if ((a.in.c & 31) || (a.in.sw & 7) || (reinterpret_cast<uintptr_t>(a.in.p) & 15) || (reinterpret_cast<uintptr_t>(a.w16) & 15)) return false;
+    if ((a.in.c & 31) || (a.in.sw & 7) || !Aligned16(a.in.p) || !Aligned16(a.w16)) return false;
     if (a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh) return false;           // pixels at a constant pitch
     if (a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh) return false;
-    if (a.pre_scale && (a.pre_scale16 == nullptr || a.pre_shift16 == nullptr || (reinterpret_cast<uintptr_t>(a.pre_scale16) & 15) ||
-                        (reinterpret_cast<uintptr_t>(a.pre_shift16) & 15)))
+    if (a.pre_scale && (a.pre_scale16 == nullptr || a.pre_shift16 == nullptr || !Aligned16(a.pre_scale16) || !Aligned16(a.pre_shift16)))
         return false;
     const int64_t M = int64_t(a.in.n) * a.in.h * a.in.w;
     if (M * a.in.sw * 2 >= (int64_t(1) << 31) || M * a.out.sw * 4 >= (int64_t(1) << 31)) return false;
     // 16-byte stores: 8 halfs / 4 floats per lane
     if (a.out.f16 ? ((a.out.c % 8) || (a.out.sw % 8)) : ((a.out.c % 4) || (a.out.sw % 4))) return false;
-    if (reinterpret_cast<uintptr_t>(a.out.p) % 16) return false;
+    if (!Aligned16(a.out.p)) return false;
     if (a.res.p != nullptr) {                          // fused residual: same element type and pixel-major layout as the output
-        if (a.res.f16 != a.out.f16 || a.res.sc != 1 || (a.res.sw % 4) || (reinterpret_cast<uintptr_t>(a.res.p) % 16)) return false;
+        if (a.res.f16 != a.out.f16 || a.res.sc != 1 || (a.res.sw % 4) || !Aligned16(a.res.p)) return false;
         if (a.res.sh != a.res.w * a.res.sw || a.res.sn != a.res.h * a.res.sh || M * a.res.sw * 4 >= (int64_t(1) << 31)) return false;
     }
     const WsTile t = kWsTiles[tile % 6];
@@ -300,13 +292,8 @@ static hipError_t launch_ws_t(const ConvArgs& a, int grid_variant, hipStream_t s
     const int64_t M = int64_t(a.in.n) * a.in.h * a.in.w;
     const int nrb = int((M + 31) / 32);
     const size_t lds = ws_lds_bytes(TN, a.in.c);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-        cus = prop.multiProcessorCount;
-    }
+    const int cus = DeviceCus();
+    if (cus == 0) return hipErrorUnknown;
     // resident workgroups: LDS and 2048 threads per CU; then the smallest grid with the same number of row blocks per wave
     // (LDS and wave slots only: sizing the grid by the true residency -- registers included, ResidentPerCu() -- measured SLOWER: a few workgroups more
     //  than fit at once cost less than a fifth row block for every wave, e.g. K = 128 at batch 128: 39 us vs 55 us)
@@ -409,7 +396,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_ws_f16_kernel(const ConvAr
         const _Float16* const w = static_cast<const _Float16*>(a.w16);
         const int items = 9 * NS * 32 * 8;
         constexpr int U = 8;                             // loads in flight per thread
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(w), 0, Cout * 9 * Cin * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(w), 0, Cout * 9 * Cin * 2, kBufferRsrcFlags);
         for (int q0 = tid; q0 < items; q0 += U * NT) {
             u32x4 v[U];
 #pragma unroll
@@ -431,9 +418,9 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_ws_f16_kernel(const ConvAr
         for (int q = tid; q < 32; q += NT) sBias[q] = (a.bias != nullptr && n0 + q < Cout) ? a.bias[n0 + q] : 0.f;
     }
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
     const __amdgpu_buffer_rsrc_t rs_out =
-        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(a.out.n) * a.out.h * a.out.w - 1) * opitch * 2 + Cout * 2), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(a.out.n) * a.out.h * a.out.w - 1) * opitch * 2 + Cout * 2), kBufferRsrcFlags);
 
     f32x16 acc[TMW];
 #pragma unroll
@@ -512,7 +499,6 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_ws_f16_kernel(const ConvAr
             for (int gp = 0; gp < 2; ++gp) {
                 const h4 qa = {_Float16(v[8 * gp + 0]), _Float16(v[8 * gp + 1]), _Float16(v[8 * gp + 2]), _Float16(v[8 * gp + 3])};
                 const h4 qb = {_Float16(v[8 * gp + 4]), _Float16(v[8 * gp + 5]), _Float16(v[8 * gp + 6]), _Float16(v[8 * gp + 7])};
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                 const u32x2 xa = __builtin_bit_cast(u32x2, qa), xb = __builtin_bit_cast(u32x2, qb);
                 const auto s0 = __builtin_amdgcn_permlane32_swap(xa[0], xb[0], false, false);
                 const auto s1 = __builtin_amdgcn_permlane32_swap(xa[1], xb[1], false, false);
@@ -560,10 +546,9 @@ bool ConvWs3Eligible(const ConvArgs& a, int tile) {
     if (tile < 0 || tile >= kNumConvWs3Tiles) return false;
     if (!a.in.f16 || !a.out.f16 || a.w16 == nullptr || a.pre_scale != nullptr) return false;
     if (a.kh != 3 || a.kw != 3 || a.sh != 1 || a.sw != 1 || a.pt != 1 || a.pl != 1 || a.out.h != a.in.h || a.out.w != a.in.w) return false;
-    if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c & 7) || (a.in.sw & 7) || (reinterpret_cast<uintptr_t>(a.in.p) & 15) ||
-        (reinterpret_cast<uintptr_t>(a.w16) & 15))
+    if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c & 7) || (a.in.sw & 7) || !Aligned16(a.in.p) || !Aligned16(a.w16))
         return false;
-    if ((a.out.c & 7) || (a.out.sw & 7) || (reinterpret_cast<uintptr_t>(a.out.p) & 15)) return false;      // any Cout, 32 per N-tile
+    if ((a.out.c & 7) || (a.out.sw & 7) || !Aligned16(a.out.p)) return false;      // any Cout, 32 per N-tile
     if (a.in.sh != a.in.sw * a.in.w || a.in.sn != a.in.sh * a.in.h) return false;          // pixel-major NHWC views
     if (a.out.sh != a.out.sw * a.out.w || a.out.sn != a.out.sh * a.out.h) return false;
     const int64_t Mr = int64_t(a.in.n) * (a.in.h + 1) * (a.in.w + 1), Mpix = int64_t(a.in.n) * a.in.h * a.in.w;
@@ -595,13 +580,8 @@ static hipError_t launch_ws3_t(const ConvArgs& a, hipStream_t stream) {
     magic_div(unsigned(g.RH * g.PW), &g.m_img, &g.sh_img);
     magic_div(unsigned(g.PW), &g.m_pw, &g.sh_pw);
     const size_t lds = ws3_lds_bytes(T, a.in.c, g.PW);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-        cus = prop.multiProcessorCount;
-    }
+    const int cus = DeviceCus();
+    if (cus == 0) return hipErrorUnknown;
     int per_cu = int((size_t(160) * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
     const int gy = (a.out.c + 31) / 32;

@@ -11,14 +11,12 @@
 
 #include <cstdlib>
 
+#include "device_util.h"
 #include "env.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <int TN, int WAVES, bool PRE>
 __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f32_kernel(const ConvArgs a) {
@@ -42,8 +40,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f32_kernel(const ConvAr
     const int stride = gridDim.x * WAVES;
     const int CH = K >> 4;                             // 16-channel chunks per row block (two 16-byte loads per lane)
     const int ipitch = int(a.in.sw), opitch = int(a.out.sw);
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), kBufferRsrcFlags);
 
     // ring of register chunks with static slots (loop unrolled by D): the waitcnt pass sees the loads in issue order
     int rb_l = blockIdx.x * WAVES + wave, c_l = 0;
@@ -64,7 +62,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f32_kernel(const ConvAr
     {
         constexpr int U = 8;
         const int k4 = K >> 2;
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, Cout * K * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, Cout * K * 4, kBufferRsrcFlags);
         for (int idx0 = tid; idx0 < ((a.debug & 128) ? 0 : BN * k4); idx0 += U * NT) {      // debug 128: timing-only, no weight preamble
             u32x4 v[U];
 #pragma unroll
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f32_kernel(const ConvAr
     const bool has_res = a.res.p != nullptr;        // residual Add fused into the epilogue (ResNet shortcuts)
     const int rpitch = int(a.res.sw);
     const __amdgpu_buffer_rsrc_t rs_res =
-        __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p : a.out.p, 0, has_res ? int((int64_t(M - 1) * rpitch + Cout) * 4) : 0, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p : a.out.p, 0, has_res ? int((int64_t(M - 1) * rpitch + Cout) * 4) : 0, kBufferRsrcFlags);
     auto epilogue = [&]() {
         const int m = rb_c * 32 + r;
         const unsigned rowoff = m < M ? unsigned(m * opitch * 4) : OOB;
@@ -214,8 +212,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_wsk_f32_kernel(const ConvA
     const int CHt = K >> 4;                            // 16-channel chunks of the whole K
     const int cb = CHt * wave / WAVES, ce = CHt * (wave + 1) / WAVES;      // this wave's slice (>= 1 chunk: eligibility)
     const int ipitch = int(a.in.sw), opitch = int(a.out.sw);
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), kBufferRsrcFlags);
 
     int rb_l = blockIdx.x, c_l = cb;
     int rb_c = rb_l, c_c = cb;
@@ -233,7 +231,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_wsk_f32_kernel(const ConvA
     {   // preamble: weight slice, BN scale/shift, bias -> LDS (8 loads in flight per thread)
         constexpr int U = 8;
         const int k4 = K >> 2;
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, Cout * K * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, Cout * K * 4, kBufferRsrcFlags);
         for (int idx0 = tid; idx0 < BN * k4; idx0 += U * NT) {
             u32x4 v[U];
 #pragma unroll
@@ -291,7 +289,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_wsk_f32_kernel(const ConvA
     const bool has_res = a.res.p != nullptr;
     const int rpitch = int(a.res.sw);
     const __amdgpu_buffer_rsrc_t rs_res =
-        __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p : a.out.p, 0, has_res ? int((int64_t(M - 1) * rpitch + Cout) * 4) : 0, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p : a.out.p, 0, has_res ? int((int64_t(M - 1) * rpitch + Cout) * 4) : 0, kBufferRsrcFlags);
     // lane (r, hh) holds pixel r, channels 8g + 4hh + q: a tile row is one pixel's 32 channels
     auto row_block_done = [&]() {
 #pragma unroll
@@ -366,15 +364,15 @@ bool ConvWs32Eligible(const ConvArgs& a, int tile) {
     if (tile < 0 || tile >= kNumConvWs32Tiles) return false;
     if (a.in.f16 || a.out.f16 || a.w == nullptr || a.kh != 1 || a.kw != 1 || a.sh != 1 || a.sw != 1 || a.pt != 0 || a.pl != 0) return false;
     if (a.in.sc != 1 || a.out.sc != 1 || a.in.h != a.out.h || a.in.w != a.out.w) return false;
-    if ((a.in.c & 15) || (a.in.sw & 3) || (reinterpret_cast<uintptr_t>(a.in.p) & 15) || (reinterpret_cast<uintptr_t>(a.w) & 15)) return false;
+    if ((a.in.c & 15) || (a.in.sw & 3) || !Aligned16(a.in.p) || !Aligned16(a.w)) return false;
     if (a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh) return false;           // pixels at a constant pitch
     if (a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh) return false;
-    if (a.pre_scale && ((reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift) & 15))) return false;
+    if (a.pre_scale && (!Aligned16(a.pre_scale) || !Aligned16(a.pre_shift))) return false;
     const int64_t M = int64_t(a.in.n) * a.in.h * a.in.w;
     if (M * a.in.sw * 4 >= (int64_t(1) << 31) || M * a.out.sw * 4 >= (int64_t(1) << 31)) return false;
-    if ((a.out.c % 4) || (a.out.sw % 4) || (reinterpret_cast<uintptr_t>(a.out.p) % 16)) return false;      // 16-byte stores
+    if ((a.out.c % 4) || (a.out.sw % 4) || !Aligned16(a.out.p)) return false;      // 16-byte stores
     if (a.res.p != nullptr) {                          // fused residual: same pixel-major layout, 16-byte loads
-        if (a.res.f16 || a.res.sc != 1 || (a.res.sw % 4) || (reinterpret_cast<uintptr_t>(a.res.p) % 16)) return false;
+        if (a.res.f16 || a.res.sc != 1 || (a.res.sw % 4) || !Aligned16(a.res.p)) return false;
         if (a.res.sh != a.res.w * a.res.sw || a.res.sn != a.res.h * a.res.sh || M * a.res.sw * 4 >= (int64_t(1) << 31)) return false;
     }
     if (tile >= kNumConvWsTiles && tile < kNumConvWsTiles + 2) {      // K-split variants: every wave needs at least one 16-channel chunk
@@ -392,13 +390,8 @@ static hipError_t launch_wsk32_t(const ConvArgs& a, hipStream_t stream) {
     const int64_t M = int64_t(a.in.n) * a.in.h * a.in.w;
     const int nrb = int((M + 31) / 32);
     const size_t lds = wsk32_lds_bytes(WAVES, a.in.c);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-        cus = prop.multiProcessorCount;
-    }
+    const int cus = DeviceCus();
+    if (cus == 0) return hipErrorUnknown;
     const int gy = (a.out.c + 31) / 32;
     int per_cu = int((size_t(160) * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 2048 / (64 * WAVES) ? 2048 / (64 * WAVES) : per_cu);
@@ -418,13 +411,8 @@ static hipError_t launch_ws32_t(const ConvArgs& a, int grid_variant, hipStream_t
     const int64_t M = int64_t(a.in.n) * a.in.h * a.in.w;
     const int nrb = int((M + 31) / 32);
     const size_t lds = ws32_lds_bytes(TN, a.in.c);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-        cus = prop.multiProcessorCount;
-    }
+    const int cus = DeviceCus();
+    if (cus == 0) return hipErrorUnknown;
     const int gy = (a.out.c + 32 * TN - 1) / (32 * TN);
     // resident workgroups (LDS, 2048 threads per CU) shared by the gy N-tiles; then the smallest grid with the same number of
     // row blocks per wave, so that no wave runs a round more than the others have to

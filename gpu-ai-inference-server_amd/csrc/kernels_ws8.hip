@@ -18,31 +18,13 @@
 
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef long i64x2 __attribute__((ext_vector_type(2)));
-
 namespace {
-constexpr float kE4m3Max8 = 448.0f;
-__device__ __forceinline__ unsigned pack4_e4m3_ws(float a, float b, float c, float d) {
-    a = __builtin_fminf(__builtin_fmaxf(a, -kE4m3Max8), kE4m3Max8);
-    b = __builtin_fminf(__builtin_fmaxf(b, -kE4m3Max8), kE4m3Max8);
-    c = __builtin_fminf(__builtin_fmaxf(c, -kE4m3Max8), kE4m3Max8);
-    d = __builtin_fminf(__builtin_fmaxf(d, -kE4m3Max8), kE4m3Max8);
-    int p = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-    p = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, p, true);
-    return unsigned(p);
-}
-__device__ __forceinline__ void unpack4_e4m3_ws(unsigned p, float* v) {
-    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(int(p), false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(int(p), true);
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
-}
 constexpr unsigned kOOB8 = 0x80000000u;
 constexpr int kRing8 = 4;          // register chunks (32 channels x 32 pixels = 1 KiB) a wave keeps in flight
 }  // namespace
@@ -78,8 +60,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f8_kernel(const ConvArg
     const int CH1 = K1 >> 5, CH = CH1 + (K2 >> 5);    // 32-channel chunks per row block: GEMM 1's, then GEMM 2's
     const int ipitch = int(a.in.sw);
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_in2 = __builtin_amdgcn_make_buffer_rsrc(DUAL ? a.in2.p : a.in.p, 0, DUAL ? int(a.in2_bytes) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_in2 = __builtin_amdgcn_make_buffer_rsrc(DUAL ? a.in2.p : a.in.p, 0, DUAL ? int(a.in2_bytes) : 0, kBufferRsrcFlags);
 
     // load stream (rb_l, c_l) runs D chunks ahead of the compute stream (rb_c, c_c)
     int rb_l = blockIdx.x * WAVES + wave, c_l = 0;
@@ -123,7 +105,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f8_kernel(const ConvArg
         auto stage_w = [&](const void* w8, int K, int P, unsigned char* dst) {
             const int k16 = K >> 4;
             constexpr int U = 8;
-            const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(w8), 0, Cout * K, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(w8), 0, Cout * K, kBufferRsrcFlags);
             for (int idx0 = tid; idx0 < BN * k16; idx0 += U * NT) {
                 u32x4 v[U];
 #pragma unroll
@@ -189,11 +171,11 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f8_kernel(const ConvArg
     };
 
     const int opitch = int(a.out.sw);
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int(int64_t(M - 1) * opitch + Cout), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int(int64_t(M - 1) * opitch + Cout), kBufferRsrcFlags);
     const bool has_res = a.res.p != nullptr;
     const int rpitch = int(a.res.sw);
-    const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p : a.out.p, 0, has_res ? int(int64_t(M - 1) * rpitch + Cout) : 0, 0x00020000);
-    const float rsq = a.res_scale * a.out_qscale, lo = a.relu ? 0.f : -kE4m3Max8;
+    const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(has_res ? a.res.p : a.out.p, 0, has_res ? int(int64_t(M - 1) * rpitch + Cout) : 0, kBufferRsrcFlags);
+    const float rsq = a.res_scale * a.out_qscale, lo = a.relu ? 0.f : -kE4m3Max;
     auto epilogue = [&]() {
         const int m = rb_c * 32 + r;
         const unsigned rowoff = m < M ? unsigned(m * opitch) : kOOB8;
@@ -225,12 +207,12 @@ __global__ __launch_bounds__(64 * WAVES) void conv1x1_ws_f8_kernel(const ConvArg
                 }
                 if (has_res) {
                     float rv[4];
-                    unpack4_e4m3_ws(rq[gq], rv);
+                    unpack4_e4m3(rq[gq], rv);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[q] += rv[q] * rsq;
                 }
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = __builtin_amdgcn_fmed3f(v[q], lo, kE4m3Max8);
+                for (int q = 0; q < 4; ++q) v[q] = __builtin_amdgcn_fmed3f(v[q], lo, kE4m3Max);
                 int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
                 pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
                 d[gq] = unsigned(pk);
@@ -271,7 +253,7 @@ static size_t ws8_lds_bytes(int tn, int K1, int K2) {
 }
 
 static bool ws8_tensor_ok(const TensorArg& t) {
-    return t.f8 && t.sc == 1 && !(t.c & 31) && !(t.sw & 15) && !(t.sh & 15) && !(t.sn & 15) && !(reinterpret_cast<uintptr_t>(t.p) & 15);
+    return t.f8 && t.sc == 1 && !(t.c & 31) && !(t.sw & 15) && !(t.sh & 15) && !(t.sn & 15) && Aligned16(t.p);
 }
 
 bool ConvWs8Eligible(const ConvArgs& a, int tile) {
@@ -282,18 +264,18 @@ bool ConvWs8Eligible(const ConvArgs& a, int tile) {
     if (a.out.h != (a.in.h - 1) / a.sh + 1 || a.out.w != (a.in.w - 1) / a.sw + 1) return false;
     if ((a.sh != 1 || a.sw != 1) && dual) return false;                                                       // a strided first input: the single-GEMM variant only
     if (a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh) return false;                          // pixels at a constant pitch
-    if (a.out.sc != 1 || (a.out.c & 15) || (a.out.sw & 15) || (reinterpret_cast<uintptr_t>(a.out.p) & 15)) return false;
+    if (a.out.sc != 1 || (a.out.c & 15) || (a.out.sw & 15) || !Aligned16(a.out.p)) return false;
     if (a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh) return false;
-    if ((reinterpret_cast<uintptr_t>(a.w8) & 15)) return false;
+    if (!Aligned16(a.w8)) return false;
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
     if (int64_t(a.in.n) * a.in.sn >= (int64_t(1) << 31) || M * a.out.sw >= (int64_t(1) << 31) || int64_t(a.out.c) * a.in.c >= (int64_t(1) << 31)) return false;
     if (a.res.p != nullptr) {
-        if (!a.res.f8 || a.res.sc != 1 || (a.res.sw & 15) || (reinterpret_cast<uintptr_t>(a.res.p) & 15) || a.res.c != a.out.c) return false;
+        if (!a.res.f8 || a.res.sc != 1 || (a.res.sw & 15) || !Aligned16(a.res.p) || a.res.c != a.out.c) return false;
         if (a.res.sh != a.res.w * a.res.sw || a.res.sn != a.res.h * a.res.sh || a.res.n != a.out.n || a.res.h != a.out.h || a.res.w != a.out.w) return false;
         if (M * a.res.sw >= (int64_t(1) << 31)) return false;
     }
     if (dual) {
-        if (!ws8_tensor_ok(a.in2) || a.w8b == nullptr || a.escale_b == nullptr || (reinterpret_cast<uintptr_t>(a.w8b) & 15) || a.sh2 < 1 || a.sw2 < 1) return false;
+        if (!ws8_tensor_ok(a.in2) || a.w8b == nullptr || a.escale_b == nullptr || !Aligned16(a.w8b) || a.sh2 < 1 || a.sw2 < 1) return false;
         if (a.in2.n != a.out.n || (a.out.h - 1) * a.sh2 >= a.in2.h || (a.out.w - 1) * a.sw2 >= a.in2.w) return false;
         const int64_t span2 = int64_t(a.in2.n - 1) * a.in2.sn + int64_t(a.in2.h - 1) * a.in2.sh + int64_t(a.in2.w - 1) * a.in2.sw + a.in2.c;
         if (span2 >= (int64_t(1) << 31) || int64_t(a.out.c) * a.in2.c >= (int64_t(1) << 31)) return false;
@@ -317,13 +299,8 @@ static hipError_t launch_ws8_t(const ConvArgs& a, bool one_per_cu, hipStream_t s
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
     const int nrb = int((M + 31) / 32);
     const size_t lds = ws8_lds_bytes(TN, a.in.c, DUAL ? a.in2.c : 0);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-        cus = prop.multiProcessorCount;
-    }
+    const int cus = DeviceCus();
+    if (cus == 0) return hipErrorUnknown;
     int per_cu = int((size_t(160) * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 2048 / (64 * WAVES) ? 2048 / (64 * WAVES) : per_cu);
     if (per_cu > 2) per_cu = 2;                      // (the grid that measured best; see launch_ws_t in kernels_ws.hip on sizing by true residency)
@@ -418,7 +395,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_ws_f8_kernel(const ConvArg
     {
         const int items = 9 * NS * 32 * 8;
         constexpr int U = 8;
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w8), 0, Cout * 9 * Cin, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w8), 0, Cout * 9 * Cin, kBufferRsrcFlags);
         for (int q0 = tid; q0 < items; q0 += U * NT) {
             u32x4 v[U];
 #pragma unroll
@@ -442,8 +419,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_ws_f8_kernel(const ConvArg
         }
     }
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(a.out.n) * a.out.h * a.out.w - 1) * opitch + Cout), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(a.out.n) * a.out.h * a.out.w - 1) * opitch + Cout), kBufferRsrcFlags);
 
     f32x16 acc[TMW];
 #pragma unroll
@@ -520,7 +497,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_ws_f8_kernel(const ConvArg
                     if (a.relu) v[q] = fmaxf(v[q], 0.f);
                     acc[i][4 * gq + q] = 0.f;
                 }
-                d[gq] = pack4_e4m3_ws(v[0] * qs, v[1] * qs, v[2] * qs, v[3] * qs);
+                d[gq] = pack4_e4m3(v[0] * qs, v[1] * qs, v[2] * qs, v[3] * qs);
             }
             const auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
             const auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -567,8 +544,8 @@ bool ConvWs38Eligible(const ConvArgs& a, int tile) {
     if (tile < 0 || tile >= kNumConvWs38Tiles) return false;
     if (!a.in.f8 || !a.out.f8 || a.w8 == nullptr || a.escale == nullptr || a.pre_scale != nullptr || a.res.p != nullptr || a.in2.p != nullptr) return false;
     if (a.kh != 3 || a.kw != 3 || a.sh != 1 || a.sw != 1 || a.pt != 1 || a.pl != 1 || a.out.h != a.in.h || a.out.w != a.in.w || a.out.n != a.in.n) return false;
-    if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c & 31) || (a.in.sw & 15) || (reinterpret_cast<uintptr_t>(a.in.p) & 15) || (reinterpret_cast<uintptr_t>(a.w8) & 15)) return false;
-    if ((a.out.c & 15) || (a.out.sw & 15) || (reinterpret_cast<uintptr_t>(a.out.p) & 15)) return false;
+    if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c & 31) || (a.in.sw & 15) || !Aligned16(a.in.p) || !Aligned16(a.w8)) return false;
+    if ((a.out.c & 15) || (a.out.sw & 15) || !Aligned16(a.out.p)) return false;
     if (a.in.sh != a.in.sw * a.in.w || a.in.sn != a.in.sh * a.in.h) return false;
     if (a.out.sh != a.out.sw * a.out.w || a.out.sn != a.out.sh * a.out.h) return false;
     const int64_t Mr = int64_t(a.in.n) * (a.in.h + 1) * (a.in.w + 1), Mpix = int64_t(a.in.n) * a.in.h * a.in.w;
@@ -593,13 +570,8 @@ static hipError_t launch_ws38_t(const ConvArgs& a, bool one_per_cu, hipStream_t 
     magic_div8(unsigned(g.RH * g.PW), &g.m_img, &g.sh_img);
     magic_div8(unsigned(g.PW), &g.m_pw, &g.sh_pw);
     const size_t lds = ws38_lds_bytes(T, a.in.c, g.PW);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-        cus = prop.multiProcessorCount;
-    }
+    const int cus = DeviceCus();
+    if (cus == 0) return hipErrorUnknown;
     int per_cu = int((size_t(160) * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
     if (one_per_cu) per_cu = 1;                      // tiles 4-7

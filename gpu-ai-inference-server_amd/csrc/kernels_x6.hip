@@ -17,15 +17,11 @@
 
 #include <cstdint>
 
+#include "device_util.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace ie {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ unsigned f2u(float x) { return __builtin_bit_cast(unsigned, x); }
 __device__ __forceinline__ float u2f(unsigned x) { return __builtin_bit_cast(float, x); }
@@ -75,8 +71,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, BMB <= 2
     const int nb = blockIdx.y * 4 + wave;
     const int ipitch = int(a.in.sw), opitch = int(a.out.sw);
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w16), 0, int(int64_t(3) * Cout * K * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(a.in.p, 0, int(a.in_bytes), kBufferRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w16), 0, int(int64_t(3) * Cout * K * 2), kBufferRsrcFlags);
     const unsigned plane_bytes = unsigned(Cout) * unsigned(K) * 2u;
 
     // ---- activation staging: thread (row r0 + 32 u, 4-channel quad q of the chunk) ----
@@ -196,7 +192,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, BMB <= 2
     if (NCH & 1) compute(wA, 0);                        // odd chunk count: the last chunk sits in buffer 0, its weights in wA
 
     // ---- epilogue: lane (channel r of the N block, hh) holds 16 pixel rows of each accumulator tile ----
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out.p, 0, int((int64_t(M - 1) * opitch + Cout) * 4), kBufferRsrcFlags);
     const int n = nb * 32 + r;
     const float bq = a.bias != nullptr ? a.bias[n] : 0.f;
 #pragma unroll
@@ -220,10 +216,10 @@ bool ConvX6Eligible(const ConvArgs& a, int tile) {
     if (a.kh != 1 || a.kw != 1 || a.sh != 1 || a.sw != 1 || a.pt != 0 || a.pl != 0) return false;
     if (a.out.h != a.in.h || a.out.w != a.in.w || a.out.n != a.in.n) return false;
     if (a.in.sc != 1 || a.out.sc != 1 || (a.in.c % 32) || a.in.c < 32 || (a.out.c % 128)) return false;
-    if ((a.in.sw % 4) || a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh || (reinterpret_cast<uintptr_t>(a.in.p) & 15)) return false;
+    if ((a.in.sw % 4) || a.in.sh != a.in.w * a.in.sw || a.in.sn != a.in.h * a.in.sh || !Aligned16(a.in.p)) return false;
     if (a.out.sh != a.out.w * a.out.sw || a.out.sn != a.out.h * a.out.sh || (reinterpret_cast<uintptr_t>(a.out.p) & 3)) return false;
-    if (reinterpret_cast<uintptr_t>(a.w16) & 15) return false;
-    if (a.pre_scale && ((reinterpret_cast<uintptr_t>(a.pre_scale) & 15) || (reinterpret_cast<uintptr_t>(a.pre_shift) & 15))) return false;
+    if (!Aligned16(a.w16)) return false;
+    if (a.pre_scale && (!Aligned16(a.pre_scale) || !Aligned16(a.pre_shift))) return false;
     const int64_t M = int64_t(a.out.n) * a.out.h * a.out.w;
     if (M * a.in.sw * 4 >= (int64_t(1) << 31) || M * a.out.sw * 4 >= (int64_t(1) << 31) || int64_t(3) * a.out.c * a.in.c * 2 >= (int64_t(1) << 31)) return false;
     return true;

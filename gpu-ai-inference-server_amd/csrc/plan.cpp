@@ -238,25 +238,28 @@ void read_window_attrs(const OnnxNode& on, LNode& n, int64_t h, int64_t w, bool 
     }
 }
 
-// Depthwise steps: the views the 16-byte channel-vector kernels need (kernels_dw.hip ConvDwEligible re-checks them with the pointers)
+// A view the 16-byte channel-vector kernels can address (V = 4 floats / 8 halfs): NHWC, channel count, pitch and channel offset whole vectors, the
+// step's element type.  The launchers' *Eligible functions re-check it with the pointers (launch_util.h VecViewOk)
+static bool VecView(const View& v, int64_t V, bool f16) { return !v.nchw && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == f16; }
+
+// Depthwise steps: the views the 16-byte channel-vector kernels need
 bool DwFastViews(const Step& s) {
     const int64_t V = s.out.f16 ? 8 : 4;
-    auto ok = [&](const View& v) { return !v.nchw && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == s.out.f16; };
     // (the fast kernel's branch-free activation knows the sigmoid family only: a fused GELU runs on the generic kernel)
     const bool gelu = int(s.act.kind) >= int(ActKind::Gelu) || int(s.pre_act.kind) >= int(ActKind::Gelu);
-    return s.kh == s.kw && (s.kh == 3 || s.kh == 5) && s.sh == s.sw && (s.sh == 1 || s.sh == 2) && !gelu && ok(s.in) && ok(s.out) && (!s.has_in2 || ok(s.in2));
+    return s.kh == s.kw && (s.kh == 3 || s.kh == 5) && s.sh == s.sw && (s.sh == 1 || s.sh == 2) && !gelu && VecView(s.in, V, s.out.f16) &&
+           VecView(s.out, V, s.out.f16) && (!s.has_in2 || VecView(s.in2, V, s.out.f16));
 }
 // 4 output pixels per lane on wide rows, 2 on narrow ones (7x7 maps: 4 groups of 2 instead of 2 of 4, one wasted lane in eight), the generic kernel otherwise
 int DwDefaultTile(const Step& s) { return DwFastViews(s) ? (s.out.w >= 14 ? 3 : 2) : 0; }
 
-// Grouped steps: the views and channel blocks the fast kernel needs for `tile` (kernels_grouped.hip ConvGroupedEligible re-checks them with the pointers)
+// Grouped steps: the views and channel blocks the fast kernel needs for `tile`
 bool GroupedFastViews(const Step& s, int tile) {
     const int cfg = GroupedCfgFor(s.in.c, s.out.c, s.group);
     if (cfg < 0 || !GroupedTileFits(cfg, s.out.f16, tile) || s.out.c % (kGroupedCfgs[cfg].opb * kGroupedCfgs[cfg].gpb) || s.kh > 7 || s.kw > 7) return false;
     if (int(s.act.kind) >= int(ActKind::Gelu) || int(s.pre_act.kind) >= int(ActKind::Gelu)) return false;      // (the fast kernel compiles the activations 0-5 only)
     const int64_t V = s.out.f16 ? 8 : 4;
-    auto ok = [&](const View& v) { return !v.nchw && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == s.out.f16; };
-    return ok(s.in) && ok(s.out) && (!s.has_in2 || ok(s.in2));
+    return VecView(s.in, V, s.out.f16) && VecView(s.out, V, s.out.f16) && (!s.has_in2 || VecView(s.in2, V, s.out.f16));
 }
 // What the autotuner picked on 63 of the 64 grouped steps of ResNeXt-50 / RegNetY-400MF (fp32 b32, fp16 b128): 2 output pixels per
 // lane for fp16 groups of 16 or more input channels, else 1; the generic kernel when no channel block fits
@@ -270,8 +273,8 @@ int GroupedDefaultTile(const Step& s) {
 // the plan's element type with Cin a multiple of the K-step (8 floats / 16 halfs) and 16-byte aligned input pixel rows
 bool ConvtFastViews(const Step& s) {
     const int64_t KS = s.out.f16 ? 16 : 8, V = s.out.f16 ? 8 : 4;
-    return s.kh == s.sh && s.kw == s.sw && !s.pt && !s.pl && !s.pb && !s.pr && !s.oph && !s.opw && s.kh * s.kw <= 16 && !s.in.nchw && !s.out.nchw &&
-           s.in.f16 == s.out.f16 && !s.in.f8 && !s.out.f8 && s.in.c % KS == 0 && s.in.pitch % V == 0 && s.in.c_off % V == 0;
+    return s.kh == s.sh && s.kw == s.sw && !s.pt && !s.pl && !s.pb && !s.pr && !s.oph && !s.opw && s.kh * s.kw <= 16 && VecView(s.in, V, s.out.f16) &&
+           s.in.c % KS == 0 && !s.out.nchw && !s.in.f8 && !s.out.f8;      // (the output only has to be NHWC: Cout tails are masked)
 }
 // 64 input pixels per wave reuse every weight fragment twice; 32 where that would leave the 256 CUs short of waves (one wave per
 // 32-channel block, pixel block and group of four taps)
@@ -281,11 +284,10 @@ int ConvtDefaultTile(const Step& s) {
     return waves64 >= 2048 ? 2 : 1;
 }
 
-// Layer-norm steps: the views the register-resident kernel needs for `tile` (kernels_ln.hip LayerNormEligible re-checks them with the pointers)
+// Layer-norm steps: the views the register-resident kernel needs for `tile`; beyond VecView, no e4m3 operand
 bool LnFastViews(const Step& s, int tile) {
     const int64_t V = s.out.f16 ? 8 : 4;
-    auto ok = [&](const View& v) { return !v.nchw && !v.f8 && v.c % V == 0 && v.pitch % V == 0 && v.c_off % V == 0 && v.f16 == s.out.f16; };
-    return LnTileFits(s.in.c, s.out.f16, tile) && ok(s.in) && ok(s.out);
+    return LnTileFits(s.in.c, s.out.f16, tile) && !s.in.f8 && !s.out.f8 && VecView(s.in, V, s.out.f16) && VecView(s.out, V, s.out.f16);
 }
 
 // Algorithmic FLOPs per element of a fused activation
@@ -4051,10 +4053,11 @@ void Planner::EmitLayerNorm(const LNode& n, Step& s) {
     s.bytes = vbytes(s.in) + vbytes(s.out);
 }
 
-// Group-norm steps: the views tile 1 needs (kernels_gn.hip GroupNormEligible re-checks them with the pointers)
+// Group-norm steps: the views tile 1 needs.  Not VecView: the vector terms are GnTileFits's (the input's channel count stands for both), and neither
+// e4m3 nor int64 operands
 static bool GnFastViews(const Step& s, int tile) {
-    auto ok = [&](const View& v) { return !v.nchw && !v.f8 && !v.i64 && v.f16 == s.out.f16; };
-    return ok(s.in) && ok(s.out) && GnTileFits(s.in.c, s.gn_groups, s.out.f16, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off, int(s.act.kind), tile);
+    return !s.in.nchw && !s.out.nchw && !s.in.f8 && !s.out.f8 && !s.in.i64 && !s.out.i64 && s.in.f16 == s.out.f16 &&
+           GnTileFits(s.in.c, s.gn_groups, s.out.f16, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off, int(s.act.kind), tile);
 }
 
 // group norm: gamma at w_off, beta at bias_off (fp32 in every precision).  Tile 1 (statistics + apply) where kernels.h GnTileFits admits the views and the
