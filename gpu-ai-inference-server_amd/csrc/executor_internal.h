@@ -15,7 +15,7 @@ TensorArg make_arg(const PlanInstance& pi, const View& v);
 LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 GnArgs MakeGnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 EmbedArgs MakeEmbedArgs(const PlanInstance& pi, const Step& s, const float* weights);
-AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s);
+AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 WinAttnArgs MakeWinAttnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 std::string kernel_label(const Step& s);
 
@@ -70,7 +70,7 @@ bool DeviceModel::TiledFamily(const PlanInstance& pi, const Step& s, F&& f) cons
         case StepKind::LayerNorm: f(MakeLnArgs(pi, s, wb), LayerNormEligible, LaunchLayerNorm, TiledNames{"layer_norm", "layer-norm"}); return true;
         case StepKind::GroupNorm: f(MakeGnArgs(pi, s, wb), GroupNormEligible, LaunchGroupNorm, TiledNames{"group_norm", "group-norm"}); return true;
         case StepKind::Embed: f(MakeEmbedArgs(pi, s, wb), EmbedEligible, LaunchEmbed, TiledNames{"embed", nullptr}); return true;
-        case StepKind::Attention: f(MakeAttnArgs(pi, s), AttentionEligible, LaunchAttention, TiledNames{"attention", "attention"}); return true;
+        case StepKind::Attention: f(MakeAttnArgs(pi, s, wb), AttentionEligible, LaunchAttention, TiledNames{"attention", "attention"}); return true;
         case StepKind::WindowAttention: f(MakeWinAttnArgs(pi, s, wb), WindowAttentionEligible, LaunchWindowAttention, TiledNames{"window_attention", "window-attention"}); return true;
         case StepKind::Conv:
             if (s.algo == ConvAlgo::Depthwise) { f(MakeDwArgs(pi, s), ConvDwEligible, LaunchConvDw, TiledNames{"conv_dw", nullptr}); return true; }

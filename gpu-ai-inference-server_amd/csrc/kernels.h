@@ -125,6 +125,8 @@ struct EltArgs {
     float act_a = 0.f, act_b = 0.f;
     int b_mul = 0;                     // 1: the second operand multiplies instead of adding
     int b_bcast = 0;                   // 1: b is [N, C, 1, 1], read at (n, c) for every pixel (a per-image channel gate)
+    int pre_act = 0;                   // ApplyAct(pre_act, pre_act_a, pre_act_b, .) on a (after scale / shift) before b joins it: SwiGLU's Mul(SiLU(gate), up)
+    float pre_act_a = 0.f, pre_act_b = 0.f;
 };
 
 // Depthwise conv (group == Cin == Cout, kernels_dw.hip): out[n, y, x, c] = clamp(act(sum_{ky,kx} w[c][ky][kx] * f(in[n, y*sh - pt + ky,
@@ -218,6 +220,10 @@ struct LnArgs {
     const float* gamma = nullptr;      // [C]
     const float* beta = nullptr;       // [C] or null
     float eps = 1e-5f;
+    // RMSNorm (Llama-class graphs): out[p, c] = in[p, c] * rsqrt(mean_c(in[p, :]^2) + eps) * gamma[c]; no mean, no centring, beta must be null.  The
+    // kernels are compile-time variants of the layer norm's under their own names (rmsnorm_kernel<T, LANES>, rmsnorm_generic_kernel): the same tiles,
+    // eligibility and default tile
+    int rms = 0;
 };
 // tile 0: generic (one wave per pixel row; any C, channel stride, pitch, channel offset, mixed element types); tiles 1-4: a group of 8 / 16 / 32 / 64
 // lanes per row, the row held in registers as up to kLnMaxVectors 16-byte vectors (4 floats / 8 halfs) per lane: sc == 1, C / pitch / channel offset
@@ -340,6 +346,17 @@ struct AttnArgs {
     int64_t mask_sn = 0;
     float mask_value = 0.f;
     int causal = 0;                    // query i attends to the keys j <= i only (a decoder's mask); never together with a key mask
+    // Grouped-query attention (Llama-class graphs): kv_heads K / V heads (0 or heads: one per query head, as above).  With Dkv = kv_heads * head_dim a
+    // token row is q (D) | k (Dkv) | v (Dkv), in.c == D + 2 Dkv, and query head h reads K / V head h / (heads / kv_heads) (HF's repeat_kv: a
+    // repeat_interleave).  heads % kv_heads == 0.  Tiles 0, 1 and 3
+    int kv_heads = 0;
+    // Rotary position embedding (null: none): fp32 tables [L][head_dim], 16-byte aligned.  q and k of token position i enter the scores as
+    //   x'[e] = x[e] * cos[i][e] + s(e) * x[p(e)] * sin[i][e],  p(e) = e + hd/2, s = -1 for e < hd/2;  p(e) = e - hd/2, s = +1 otherwise
+    // (x * cos + rotate_half(x) * sin with full-width tables: the two halves of a table row need not be equal).  fp32 arithmetic; a half operand is
+    // rounded once, where it enters LDS (k) or the MFMA fragment (q).  Tiles 1 and 3 rotate in their causal form only (attention_mfma_kernel<.,.,causal,rope>);
+    // tile 0 rotates in every form; never together with a key mask; head_dim even
+    const float* rope_cos = nullptr;
+    const float* rope_sin = nullptr;
 };
 // tile 0: attention_generic_kernel (one wave per query row; any L, head_dim, pitch, offset; float or half).  tile 1: attention_mfma_kernel<T, HD>
 // (a workgroup = one image, one head, 128 queries; the head's K and V rows in LDS): head_dim 32 or 64, the channel counts, pitches and offsets

@@ -1238,7 +1238,10 @@ hipError_t LaunchGlobalAvgPool(const TensorArg& in, const TensorArg& out, const 
 // ------------------------------------------------------------------------------------------------
 // elementwise: out = act(clamp(relu?( scale[c]*a + shift[c] (+ or * b) ), lo, hi))   (stand-alone BN / ReLU / residual Add / Clip / activation /
 // Mul; b_bcast: b is [N, C, 1, 1], a per-image channel gate)
+// PRE (a.pre_act != 0, a gated unit such as SwiGLU's Mul(SiLU(gate), up)): ApplyAct(pre_act) on the first operand before b joins it; a compile-time
+// variant, so the steps without one run the code they always ran
 // ------------------------------------------------------------------------------------------------
+template <bool PRE>
 __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
     const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (idx >= total) return;
@@ -1249,6 +1252,7 @@ __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
     const int b = int(m / a.out.h);
     float v = ld_any(a.a.p, a.a.f16, int64_t(b) * a.a.sn + int64_t(y) * a.a.sh + int64_t(x) * a.a.sw + int64_t(c) * a.a.sc);
     if (a.scale) v = v * a.scale[c] + a.shift[c];
+    if constexpr (PRE) v = ApplyAct(a.pre_act, a.pre_act_a, a.pre_act_b, v);
     if (a.b.p) {
         const float u = ld_any(a.b.p, a.b.f16, a.b_bcast ? int64_t(b) * a.b.sn + int64_t(c) * a.b.sc
                                                            : int64_t(b) * a.b.sn + int64_t(y) * a.b.sh + int64_t(x) * a.b.sw + int64_t(c) * a.b.sc);
@@ -1262,7 +1266,7 @@ __global__ void eltwise_kernel(const EltArgs a, const int64_t total) {
 }
 
 // 16 bytes per lane (4 floats / 8 halfs of one pixel's channels) when every operand is pixel-major NHWC of one element type
-template <bool HALF>
+template <bool HALF, bool PRE>
 __global__ void eltwise_vec_kernel(const EltArgs a, const int64_t total_vec, const int cv) {
     constexpr int V = HALF ? 8 : 4;
     const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1284,6 +1288,10 @@ __global__ void eltwise_vec_kernel(const EltArgs a, const int64_t total_vec, con
     if (a.scale) {
 #pragma unroll
         for (int i = 0; i < V; ++i) v[i] = v[i] * a.scale[c + i] + a.shift[c + i];
+    }
+    if constexpr (PRE) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[i] = ApplyAct(a.pre_act, a.pre_act_a, a.pre_act_b, v[i]);
     }
     if (a.b.p) {
         load(a.b, w, a.b_bcast ? p / (int64_t(a.out.h) * a.out.w) * a.b.sn + c : p * a.b.sw + c);
@@ -1337,15 +1345,19 @@ hipError_t LaunchEltwise(const EltArgs& a, hipStream_t stream) {
             const int64_t tv = total / V;
             const int64_t vblocks = (tv + 255) / 256;
             if (vblocks < (int64_t(1) << 31)) {
-                if (f16) eltwise_vec_kernel<true><<<dim3(unsigned(vblocks)), dim3(256), 0, stream>>>(a, tv, a.out.c / V);
-                else eltwise_vec_kernel<false><<<dim3(unsigned(vblocks)), dim3(256), 0, stream>>>(a, tv, a.out.c / V);
+                if (a.pre_act) {
+                    if (f16) eltwise_vec_kernel<true, true><<<dim3(unsigned(vblocks)), dim3(256), 0, stream>>>(a, tv, a.out.c / V);
+                    else eltwise_vec_kernel<false, true><<<dim3(unsigned(vblocks)), dim3(256), 0, stream>>>(a, tv, a.out.c / V);
+                } else if (f16) eltwise_vec_kernel<true, false><<<dim3(unsigned(vblocks)), dim3(256), 0, stream>>>(a, tv, a.out.c / V);
+                else eltwise_vec_kernel<false, false><<<dim3(unsigned(vblocks)), dim3(256), 0, stream>>>(a, tv, a.out.c / V);
                 return hipGetLastError();
             }
         }
     }
     const int64_t blocks = (total + 255) / 256;
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(eltwise_kernel, dim3(unsigned(blocks)), dim3(256), 0, stream, a, total);
+    if (a.pre_act) hipLaunchKernelGGL(eltwise_kernel<true>, dim3(unsigned(blocks)), dim3(256), 0, stream, a, total);
+    else hipLaunchKernelGGL(eltwise_kernel<false>, dim3(unsigned(blocks)), dim3(256), 0, stream, a, total);
     return hipGetLastError();
 }
 

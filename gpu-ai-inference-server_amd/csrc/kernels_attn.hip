@@ -37,6 +37,17 @@
 // tile 0 ends its key loops at i + 1; a workgroup of tile 1 / 3 stages only the key rows below 128 (qb + 1), a wave's key-tile loop ends with the tile
 // that holds its last query (key0 <= q0 + 31), and only the tile with key0 == q0 tests its elements (key > query -> -inf, before the maximum).
 //
+// Grouped K / V heads (tiles 0, 1 and 3; Llama-class graphs): a token row is q (D) | k (Dkv) | v (Dkv) with Dkv = kv_heads * hd, and query head h reads
+// K / V head h / (heads / kv_heads).  Only the K / V base offsets change: every (image, head, query block) workgroup still stages its K / V head itself.
+//
+// ROPE (tile 0 at run time; tiles 1 and 3 as a template parameter of their CAUSAL form): the rotary position embedding of q and k inside the loads the
+// kernels already do.  x'[e] = x[e] cos[i][e] + s(e) x[p(e)] sin[i][e] at token position i, p(e) = e +/- hd/2, s = -1 in the first half of the head and
+// +1 in the second, with full-width fp32 tables [L][hd] (the two halves of a table row need not be equal).  The staging thread of K vector (row, cv)
+// also loads the partner vector (cv + VPR/2) % VPR of the row and the cos / sin vectors of the row's GLOBAL key position (tile 3: chunk base + row)
+// and writes the rotated vector to LDS; AttnWave::init_rope loads a lane's own half and the partner half of its Q row (the lane halves of the QK^T
+// reduction are exactly the two rope halves) and rotates at its query's position.  fp32 arithmetic; a half operand is rounded once, where it enters
+// LDS (k) or the MFMA fragment (q).  V is staged as it is.  No extra pass over the qkv buffer, no extra LDS.
+//
 // MASK (tiles 0 and 1): the key mask of a BERT-class graph.  Key j of image n gets the bias (1 - float(mask[n, j])) * c on its scaled score, computed in
 // fp32 as the graph computes it.  Tile 1 stages the image's L biases in LDS behind K / V, already in units of log2 and clamped at -FLT_MAX
 // (c = finfo.min times log2 e would overflow to -inf, and a fully masked row would be exp2(-inf - -inf) = NaN), padded keys at -inf; the bias is
@@ -75,7 +86,8 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
     const int h = int((row / L) % a.heads);
     const int64_t n = row / (int64_t(L) * a.heads);
     const int64_t qb = n * a.in.sn + int64_t(i) * a.in.sw + int64_t(h) * hd * a.in.sc;       // q row; key row j: kb + j * sw
-    const int64_t kb = n * a.in.sn + int64_t(D + h * hd) * a.in.sc, vb = kb + int64_t(D) * a.in.sc;
+    const int Hkv = a.kv_heads > 0 ? a.kv_heads : a.heads, kvh = Hkv == a.heads ? h : h / (a.heads / Hkv);      // grouped K / V heads: head h reads K / V head h / group
+    const int64_t kb = n * a.in.sn + int64_t(D + kvh * hd) * a.in.sc, vb = kb + int64_t(Hkv) * hd * a.in.sc;
     const int64_t ob = n * a.out.sn + int64_t(i) * a.out.sw + int64_t(h) * hd * a.out.sc;
     const int Lk = CAUSAL ? i + 1 : L;             // the keys of this query: j < Lk
     [[maybe_unused]] float shift = 0.f;            // MASK: the image's largest bias, where it is small enough to be taken out exactly
@@ -86,9 +98,20 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
         for (int x = 32; x >= 1; x >>= 1) bm = fmaxf(bm, __shfl_xor(bm, x, 64));
         shift = fabsf(bm) <= kMaskShiftMax ? bm : 0.f;
     }
+    // element e of the row at `rb` (token position pos) after the rotary embedding: x[e] cos[pos][e] -/+ x[e +/- hd/2] sin[pos][e]
+    auto rotated = [&](int64_t rb, int pos, int e) {
+        const int hh = hd / 2, p = e < hh ? e + hh : e - hh;
+        const float x = ld_any(a.in.p, a.in.f16, rb + int64_t(e) * a.in.sc), xp = ld_any(a.in.p, a.in.f16, rb + int64_t(p) * a.in.sc);
+        const int64_t t = int64_t(pos) * hd + e;
+        return fmaf(x, a.rope_cos[t], (e < hh ? -xp : xp) * a.rope_sin[t]);
+    };
     auto score = [&](int j) {
         float s = 0.f;
-        for (int e = 0; e < hd; ++e) s = fmaf(ld_any(a.in.p, a.in.f16, qb + int64_t(e) * a.in.sc), ld_any(a.in.p, a.in.f16, kb + int64_t(j) * a.in.sw + int64_t(e) * a.in.sc), s);
+        if (a.rope_cos) {                          // (a runtime flag: this kernel is the fallback and the cross-check)
+            for (int e = 0; e < hd; ++e) s = fmaf(rotated(qb, i, e), rotated(kb + int64_t(j) * a.in.sw, j, e), s);
+        } else {
+            for (int e = 0; e < hd; ++e) s = fmaf(ld_any(a.in.p, a.in.f16, qb + int64_t(e) * a.in.sc), ld_any(a.in.p, a.in.f16, kb + int64_t(j) * a.in.sw + int64_t(e) * a.in.sc), s);
+        }
         if constexpr (MASK) return fmaxf(s * a.scale + ((1.f - float(a.mask[n * a.mask_sn + j])) * a.mask_value - shift), -kFltMax);
         else return s * a.scale;
     };
@@ -120,6 +143,27 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
     }
 }
 
+// One 16-byte vector of a q / k row after the rotary embedding: x = the vector (elements e0 ...), xp = its partner vector (elements e0 +/- HD/2 ...),
+// c / s = the cos / sin entries e0 ... of the token position's table row, sg = -1 for a vector of the first half of the head, +1 for one of the second.
+// fp32 arithmetic; halfs are rounded once, here.
+template <typename T>
+__device__ __forceinline__ uint4 rope_vec(uint4 x, uint4 xp, const float* c, const float* s, float sg) {
+    const float4 c0 = *reinterpret_cast<const float4*>(c), s0 = *reinterpret_cast<const float4*>(s);
+    if constexpr (sizeof(T) == 2) {
+        const float4 c1 = *reinterpret_cast<const float4*>(c + 4), s1 = *reinterpret_cast<const float4*>(s + 4);
+        const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, ss[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+        const h8 a = __builtin_bit_cast(h8, x), b = __builtin_bit_cast(h8, xp);
+        h8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = _Float16(fmaf(float(a[j]), cc[j], sg * float(b[j]) * ss[j]));
+        return __builtin_bit_cast(uint4, o);
+    } else {
+        const float4 a = __builtin_bit_cast(float4, x), b = __builtin_bit_cast(float4, xp);
+        return __builtin_bit_cast(uint4, make_float4(fmaf(a.x, c0.x, sg * b.x * s0.x), fmaf(a.y, c0.y, sg * b.y * s0.y), fmaf(a.z, c0.z, sg * b.z * s0.z),
+                                                     fmaf(a.w, c0.w, sg * b.w * s0.w)));
+    }
+}
+
 // What a wave of tile 1 / 3 carries through its key tiles: its lane's half of its Q row, the O^T accumulators and the softmax statistics of its query
 template <typename T, int HD>
 struct AttnWave {
@@ -137,6 +181,26 @@ struct AttnWave {
         } else {
 #pragma unroll
             for (int k = 0; k < HH / 4; ++k) q4[k] = *reinterpret_cast<const float4*>(qrow + 4 * k);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+        m = -__builtin_huge_valf();
+        lsum = 0.f;
+    }
+
+    // init with the rotary embedding: qhead = element 0 of the head's Q row, cr / sr = the cos / sin table rows of its token position.  The lane halves
+    // are exactly the two rope halves: lane half hf rotates its half with the other half as the partner
+    __device__ __forceinline__ void init_rope(const T* qhead, int hf, const float* cr, const float* sr) {
+        constexpr int V = 16 / int(sizeof(T));
+        const T* mine = qhead + hf * HH;
+        const T* other = qhead + (1 - hf) * HH;
+        const float sg = hf ? 1.f : -1.f;
+#pragma unroll
+        for (int k = 0; k < HH / V; ++k) {
+            const uint4 r = rope_vec<T>(*reinterpret_cast<const uint4*>(mine + V * k), *reinterpret_cast<const uint4*>(other + V * k), cr + hf * HH + V * k,
+                                        sr + hf * HH + V * k, sg);
+            if constexpr (F16) q8[k] = __builtin_bit_cast(h8, r);
+            else q4[k] = __builtin_bit_cast(float4, r);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
@@ -241,9 +305,12 @@ struct AttnWave {
 };
 
 // grid = N * heads * qblocks workgroups (qblocks = ceil(L / 128)); dynamic LDS = AttnLdsBytes(L, HD, half) (by L, causal or not)
-template <typename T, int HD, bool MASK, bool CAUSAL>
+// ROPE (CAUSAL only): the staging thread of K vector (row, cv) also loads the partner vector (cv + VPR / 2) % VPR of the row and the cos / sin vectors of
+// the row's key position and writes the rotated vector to LDS; AttnWave::init_rope rotates the wave's Q rows; V is staged as it is
+template <typename T, int HD, bool MASK, bool CAUSAL, bool ROPE>
 __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnArgs a, const int qblocks) {
     static_assert(!(MASK && CAUSAL), "a key mask together with a causal mask is not built");
+    static_assert(!ROPE || CAUSAL, "the rotary form is built for causal steps only");
     constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
     constexpr int RS = HD + V;                     // LDS row stride in elements
     constexpr int HH = HD / 2;
@@ -255,7 +322,10 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
     const int qb = int(blockIdx.x) % qblocks;
     const int hn = int(blockIdx.x) / qblocks;
     const int h = hn % a.heads, n = hn / a.heads;
-    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // token row j: + j * sw; q at + 0, k at + D, v at + 2 D
+    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // the head's q: token row j at + j * sw
+    // the head's k and v from `base`: + D and + 2 D, or with grouped K / V heads (head h reads K / V head h / group) + D + (kvh - h) HD and that + Dkv
+    // (no division on the path every other model takes: one K / V head per query head)
+    const int kvn = a.kv_heads > 0 ? a.kv_heads : a.heads, ko = kvn == a.heads ? D : D + (h / (a.heads / kvn) - h) * HD, vo = ko + kvn * HD;
     const int Ls = CAUSAL && 128 * (qb + 1) < Lp ? 128 * (qb + 1) : Lp;                    // CAUSAL: no query of this workgroup sees a key beyond its last query
 
     for (int idx = int(threadIdx.x); idx < Ls * VPR; idx += kAttnBlock) {
@@ -263,8 +333,13 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
         uint4 kv = make_uint4(0u, 0u, 0u, 0u), vv = kv;                                   // rows past L: zeros (a zero probability times them stays zero)
         if (row < L) {
             const T* r = base + int64_t(row) * a.in.sw + cv * V;
-            kv = *reinterpret_cast<const uint4*>(r + D);
-            vv = *reinterpret_cast<const uint4*>(r + 2 * D);
+            kv = *reinterpret_cast<const uint4*>(r + ko);
+            vv = *reinterpret_cast<const uint4*>(r + vo);
+            if constexpr (ROPE) {
+                constexpr int HV = VPR / 2;            // vectors per rope half
+                const int64_t t = int64_t(row) * HD + cv * V;
+                kv = rope_vec<T>(kv, *reinterpret_cast<const uint4*>(r + ko + (cv < HV ? HV : -HV) * V), a.rope_cos + t, a.rope_sin + t, cv < HV ? -1.f : 1.f);
+            }
         }
         *reinterpret_cast<uint4*>(Ks + row * RS + cv * V) = kv;
         *reinterpret_cast<uint4*>(Vs + row * RS + cv * V) = vv;
@@ -281,7 +356,8 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
     if (q0 >= L) return;                           // wave-uniform, behind the kernel's only barrier
     const int qi = q0 + col < L ? q0 + col : L - 1;
     AttnWave<T, HD> w;                             // this lane's half of its Q row in registers for the whole kernel
-    w.init(base + int64_t(qi) * a.in.sw + hf * HH);
+    if constexpr (ROPE) w.init_rope(base + int64_t(qi) * a.in.sw, hf, a.rope_cos + int64_t(qi) * HD, a.rope_sin + int64_t(qi) * HD);
+    else w.init(base + int64_t(qi) * a.in.sw + hf * HH);
     const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
     [[maybe_unused]] float shift = 0.f;            // MASK: the image's largest bias (every wave finds it for itself), where it is small enough to be taken out exactly
     if constexpr (MASK) {
@@ -310,7 +386,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
 // the workgroup).  CAUSAL: the workgroup's chunk loop ends with the chunk that holds key 128 qb + 127.
 // The late query blocks of a causal step do the most work: block ids are dealt out reversed, the last query block of every (image, head) first, so the
 // grid's tail is made of the light workgroups.
-template <typename T, int HD, bool CAUSAL>
+template <typename T, int HD, bool CAUSAL, bool ROPE>
 __global__ __launch_bounds__(kAttnBlock) void attention_chunk_kernel(const AttnArgs a, const int qblocks) {
     constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
     constexpr int RS = HD + V;                     // LDS row stride in elements
@@ -318,6 +394,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_chunk_kernel(const AttnA
     constexpr int VPR = HD / V;                    // vectors per K / V row
     constexpr int KC = kAttnChunkKeys;
     static_assert(KC % 32 == 0, "whole key tiles per chunk");
+    static_assert(!ROPE || CAUSAL, "the rotary form is built for causal steps only");
     extern __shared__ __attribute__((aligned(16))) unsigned char attn_smem[];
     const int L = a.in.w, Lp = (L + 31) / 32 * 32, D = a.heads * HD;
     T* Ks = reinterpret_cast<T*>(attn_smem);
@@ -326,13 +403,17 @@ __global__ __launch_bounds__(kAttnBlock) void attention_chunk_kernel(const AttnA
     const int qb = qblocks - 1 - int(blockIdx.x) / nh;
     const int hn = int(blockIdx.x) % nh;
     const int h = hn % a.heads, n = hn / a.heads;
-    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // token row j: + j * sw; q at + 0, k at + D, v at + 2 D
+    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // the head's q: token row j at + j * sw
+    // the head's k and v from `base`: + D and + 2 D, or with grouped K / V heads (head h reads K / V head h / group) + D + (kvh - h) HD and that + Dkv
+    // (no division on the path every other model takes: one K / V head per query head)
+    const int kvn = a.kv_heads > 0 ? a.kv_heads : a.heads, ko = kvn == a.heads ? D : D + (h / (a.heads / kvn) - h) * HD, vo = ko + kvn * HD;
     const int wave = int(threadIdx.x) / 64, lane = int(threadIdx.x) % 64, col = lane & 31, hf = lane >> 5;
     const int q0 = qb * 128 + wave * 32;
     const bool live = q0 < L;                      // wave-uniform
     const int qi = q0 + col < L ? q0 + col : L - 1;
     AttnWave<T, HD> w;
-    w.init(base + int64_t(qi) * a.in.sw + hf * HH);
+    if constexpr (ROPE) w.init_rope(base + int64_t(qi) * a.in.sw, hf, a.rope_cos + int64_t(qi) * HD, a.rope_sin + int64_t(qi) * HD);
+    else w.init(base + int64_t(qi) * a.in.sw + hf * HH);
     const float sl2 = a.scale * kLog2e;
     const int Ls = CAUSAL && 128 * (qb + 1) < Lp ? 128 * (qb + 1) : Lp;      // the workgroup's keys: whole tiles, the same for its four waves
     const int kend = !live ? 0 : (CAUSAL ? q0 + 32 : Lp);                 // this wave's keys (live: q0 + 32 <= Ls)
@@ -344,8 +425,13 @@ __global__ __launch_bounds__(kAttnBlock) void attention_chunk_kernel(const AttnA
             uint4 kv = make_uint4(0u, 0u, 0u, 0u), vv = kv;                               // rows past L: zeros
             if (row < L) {
                 const T* r = base + int64_t(row) * a.in.sw + cv * V;
-                kv = *reinterpret_cast<const uint4*>(r + D);
-                vv = *reinterpret_cast<const uint4*>(r + 2 * D);
+                kv = *reinterpret_cast<const uint4*>(r + ko);
+                vv = *reinterpret_cast<const uint4*>(r + vo);
+                if constexpr (ROPE) {                  // (row = the key's global position, not its row inside the chunk)
+                    constexpr int HV = VPR / 2;
+                    const int64_t t = int64_t(row) * HD + cv * V;
+                    kv = rope_vec<T>(kv, *reinterpret_cast<const uint4*>(r + ko + (cv < HV ? HV : -HV) * V), a.rope_cos + t, a.rope_sin + t, cv < HV ? -1.f : 1.f);
+                }
             }
             *reinterpret_cast<uint4*>(Ks + lr * RS + cv * V) = kv;
             *reinterpret_cast<uint4*>(Vs + lr * RS + cv * V) = vv;
@@ -563,33 +649,33 @@ bool token_view_ok(const TensorArg& t, int V) {
     return t.h == 1 && t.sn == int64_t(t.w) * t.sw && VecViewOk(row, V);
 }
 
-template <typename T, int HD, bool MASK, bool CAUSAL>
+template <typename T, int HD, bool MASK, bool CAUSAL, bool ROPE>
 hipError_t launch_mfma(const AttnArgs& a, hipStream_t stream) {
     const int qblocks = (a.in.w + 127) / 128;
     const int64_t blocks = int64_t(a.in.n) * a.heads * qblocks;
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
     const size_t lds = size_t(AttnLdsBytes(a.in.w, HD, sizeof(T) == 2, MASK));
-    attention_mfma_kernel<T, HD, MASK, CAUSAL><<<dim3(unsigned(blocks)), dim3(kAttnBlock), lds, stream>>>(a, qblocks);
+    attention_mfma_kernel<T, HD, MASK, CAUSAL, ROPE><<<dim3(unsigned(blocks)), dim3(kAttnBlock), lds, stream>>>(a, qblocks);
     return hipGetLastError();
 }
 
-template <typename T, int HD, bool CAUSAL>
+template <typename T, int HD, bool CAUSAL, bool ROPE>
 hipError_t launch_chunk(const AttnArgs& a, hipStream_t stream) {
     const int qblocks = (a.in.w + 127) / 128;
     const int64_t blocks = int64_t(a.in.n) * a.heads * qblocks;
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-    attention_chunk_kernel<T, HD, CAUSAL><<<dim3(unsigned(blocks)), dim3(kAttnBlock), size_t(AttnChunkLdsBytes(HD, sizeof(T) == 2)), stream>>>(a, qblocks);
+    attention_chunk_kernel<T, HD, CAUSAL, ROPE><<<dim3(unsigned(blocks)), dim3(kAttnBlock), size_t(AttnChunkLdsBytes(HD, sizeof(T) == 2)), stream>>>(a, qblocks);
     return hipGetLastError();
 }
 
 // tiles 1 and 3 by head dim (32 / 64: the eligibility admitted nothing else)
-template <typename T, bool MASK, bool CAUSAL>
+template <typename T, bool MASK, bool CAUSAL, bool ROPE = false>
 hipError_t launch_mfma_hd(const AttnArgs& a, hipStream_t stream) {
-    return a.head_dim == 64 ? launch_mfma<T, 64, MASK, CAUSAL>(a, stream) : launch_mfma<T, 32, MASK, CAUSAL>(a, stream);
+    return a.head_dim == 64 ? launch_mfma<T, 64, MASK, CAUSAL, ROPE>(a, stream) : launch_mfma<T, 32, MASK, CAUSAL, ROPE>(a, stream);
 }
-template <typename T, bool CAUSAL>
+template <typename T, bool CAUSAL, bool ROPE = false>
 hipError_t launch_chunk_hd(const AttnArgs& a, hipStream_t stream) {
-    return a.head_dim == 64 ? launch_chunk<T, 64, CAUSAL>(a, stream) : launch_chunk<T, 32, CAUSAL>(a, stream);
+    return a.head_dim == 64 ? launch_chunk<T, 64, CAUSAL, ROPE>(a, stream) : launch_chunk<T, 32, CAUSAL, ROPE>(a, stream);
 }
 
 template <typename T, int HD>
@@ -616,10 +702,17 @@ hipError_t launch_stream_hd(const AttnArgs& a, hipStream_t stream) {
 bool AttentionEligible(const AttnArgs& a, int tile) {
     if (tile < 0 || tile >= kNumAttnTiles || !a.in.p || !a.out.p || a.heads < 1 || a.head_dim < 1) return false;
     const int64_t D = int64_t(a.heads) * a.head_dim;
-    if (a.in.f8 || a.out.f8 || a.in.c != 3 * D || a.out.c != D || a.in.n != a.out.n || a.in.h != 1 || a.out.h != 1 || a.in.w != a.out.w || a.in.w < 1) return false;
+    const int kvn = a.kv_heads > 0 ? a.kv_heads : a.heads;
+    if (kvn > a.heads || a.heads % kvn) return false;          // whole groups of query heads per K / V head
+    if (a.in.f8 || a.out.f8 || a.in.c != D + 2 * int64_t(kvn) * a.head_dim || a.out.c != D || a.in.n != a.out.n || a.in.h != 1 || a.out.h != 1 || a.in.w != a.out.w || a.in.w < 1)
+        return false;
     if (a.mask && a.mask_sn < a.in.w) return false;
     if (a.causal && (a.mask || tile == 2)) return false;      // no kernel has both masks, and tile 2 has no causal form
+    const bool rope = a.rope_cos || a.rope_sin;
+    if (rope && (!a.rope_cos || !a.rope_sin || a.mask || a.head_dim % 2)) return false;      // both tables; no kernel rotates under a key mask
+    if (tile == 2 && (rope || kvn != a.heads)) return false;  // tile 2 has neither a rotary nor a grouped form
     if (tile == 0) return true;
+    if (rope && (!a.causal || !Aligned16(a.rope_cos) || !Aligned16(a.rope_sin))) return false;      // tiles 1 and 3 rotate in their causal form only
     const int V = a.out.f16 ? 8 : 4;
     // (the offsets are in the base pointers: their alignment stands for the offset condition)
     if (a.in.f16 != a.out.f16 || !token_view_ok(a.in, V) || !token_view_ok(a.out, V)) return false;
@@ -642,26 +735,32 @@ hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream) {
     }
     if (tile == 2) return a.out.f16 ? launch_stream_hd<_Float16>(a, stream) : launch_stream_hd<float>(a, stream);
     if (tile == 3) {
+        if (a.rope_cos) return a.out.f16 ? launch_chunk_hd<_Float16, true, true>(a, stream) : launch_chunk_hd<float, true, true>(a, stream);
         if (a.causal) return a.out.f16 ? launch_chunk_hd<_Float16, true>(a, stream) : launch_chunk_hd<float, true>(a, stream);
         return a.out.f16 ? launch_chunk_hd<_Float16, false>(a, stream) : launch_chunk_hd<float, false>(a, stream);
     }
     if (a.mask) return a.out.f16 ? launch_mfma_hd<_Float16, true, false>(a, stream) : launch_mfma_hd<float, true, false>(a, stream);
+    if (a.rope_cos) return a.out.f16 ? launch_mfma_hd<_Float16, false, true, true>(a, stream) : launch_mfma_hd<float, false, true, true>(a, stream);
     if (a.causal) return a.out.f16 ? launch_mfma_hd<_Float16, false, true>(a, stream) : launch_mfma_hd<float, false, true>(a, stream);
     return a.out.f16 ? launch_mfma_hd<_Float16, false, false>(a, stream) : launch_mfma_hd<float, false, false>(a, stream);
 }
 
 hipError_t InitKernelsAttn() {
     const void* const kernels[] = {
-        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false, false>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false, false>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, true, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, true, false>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, true, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, true, false>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false, true>),
-        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false, true>),
-        reinterpret_cast<const void*>(&attention_chunk_kernel<float, 32, false>), reinterpret_cast<const void*>(&attention_chunk_kernel<float, 64, false>),
-        reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 32, false>), reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 64, false>),
-        reinterpret_cast<const void*>(&attention_chunk_kernel<float, 32, true>), reinterpret_cast<const void*>(&attention_chunk_kernel<float, 64, true>),
-        reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 32, true>), reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 64, true>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false, false, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false, false, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false, false, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false, false, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, true, false, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, true, false, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, true, false, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, true, false, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false, true, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false, true, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false, true, false>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false, true, false>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<float, 32, false, false>), reinterpret_cast<const void*>(&attention_chunk_kernel<float, 64, false, false>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 32, false, false>), reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 64, false, false>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<float, 32, true, false>), reinterpret_cast<const void*>(&attention_chunk_kernel<float, 64, true, false>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 32, true, false>), reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 64, true, false>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<float, 32, false, true, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<float, 64, false, true, true>),
+        reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 32, false, true, true>), reinterpret_cast<const void*>(&attention_mfma_kernel<_Float16, 64, false, true, true>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<float, 32, true, true>), reinterpret_cast<const void*>(&attention_chunk_kernel<float, 64, true, true>),
+        reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 32, true, true>), reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 64, true, true>),
         reinterpret_cast<const void*>(&attention_stream_kernel<float, 128>), reinterpret_cast<const void*>(&attention_stream_kernel<float, 256>),
         reinterpret_cast<const void*>(&attention_stream_kernel<float, 512>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 128>),
         reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 256>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 512>)};

@@ -12,6 +12,15 @@
 //   layernorm_generic_kernel         one wave per pixel row, any C, channel stride, pitch and channel offset, mixed element types; the row is
 //                                    re-read for each of its three passes.
 //
+// RMSNorm (Llama-class graphs) is the compile-time variant RMS of both bodies, launched under its own kernel names:
+//
+//   out[p, c] = x[p, c] * rsqrt(mean_c(x[p, :]^2) + eps) * gamma[c]
+//
+//   rmsnorm_kernel<T, LANES, NV>     the fast body without the mean pass, the centring and beta: one reduction (the sum of squares) and the store
+//   rmsnorm_generic_kernel           the generic body with two passes over the row instead of three
+//
+// The same tiles, eligibility and default tile as the layer norm (LnTileFits, LnDefaultTile); a row of zeros gives zeros (rsqrt(eps) is finite).
+//
 // Both are correct when out aliases in (the planner recycles buffers): a group / wave reads all of its row before it writes any of it, and no
 // other group touches that row.  Rows past the end are masked (the row count need not be a multiple of the rows per workgroup).
 #include <hip/hip_runtime.h>
@@ -28,8 +37,8 @@ namespace {
 constexpr int kLnBlock = 256;
 
 // rows: pixel rows of the view; cvn = C / V channel vectors per row (<= LANES * NV); row p starts at p * a.in.sw / p * a.out.sw
-template <typename T, int LANES, int NV>
-__global__ __launch_bounds__(kLnBlock) void layernorm_kernel(const LnArgs a, const int64_t rows, const int cvn) {
+template <typename T, int LANES, int NV, bool RMS>
+__device__ __forceinline__ void ln_rows(const LnArgs& a, const int64_t rows, const int cvn) {
     constexpr int V = 16 / int(sizeof(T));
     const int lane = int(threadIdx.x) % LANES;
     const int64_t row = (int64_t(blockIdx.x) * kLnBlock + threadIdx.x) / LANES;
@@ -48,18 +57,24 @@ __global__ __launch_bounds__(kLnBlock) void layernorm_kernel(const LnArgs a, con
             for (int v = 0; v < V; ++v) x[j][v] = 0.f;
         }
 #pragma unroll
-        for (int v = 0; v < V; ++v) s += x[j][v];
+        for (int v = 0; v < V; ++v) {
+            if constexpr (RMS) s = fmaf(x[j][v], x[j][v], s);      // (the zero filling of an absent vector adds nothing)
+            else s += x[j][v];
+        }
     }
     const float inv_c = 1.f / float(a.in.c);
-    const float mean = group_sum<LANES>(s) * inv_c;
     float q = 0.f;
+    if constexpr (RMS) q = s;
+    else {
+        const float mean = group_sum<LANES>(s) * inv_c;
 #pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const bool has = j * LANES + lane < cvn;   // (the zero filling of an absent vector must not count as -mean)
+        for (int j = 0; j < NV; ++j) {
+            const bool has = j * LANES + lane < cvn;   // (the zero filling of an absent vector must not count as -mean)
 #pragma unroll
-        for (int v = 0; v < V; ++v) {
-            x[j][v] = has ? x[j][v] - mean : 0.f;
-            q = fmaf(x[j][v], x[j][v], q);
+            for (int v = 0; v < V; ++v) {
+                x[j][v] = has ? x[j][v] - mean : 0.f;
+                q = fmaf(x[j][v], x[j][v], q);
+            }
         }
     }
     const float rstd = 1.f / sqrtf(group_sum<LANES>(q) * inv_c + a.eps);
@@ -70,6 +85,13 @@ __global__ __launch_bounds__(kLnBlock) void layernorm_kernel(const LnArgs a, con
         float g[V], b[V];
         load16<float>(a.gamma + cv * V, g);
         if constexpr (V == 8) load16<float>(a.gamma + cv * V + 4, g + 4);
+        if constexpr (RMS) {
+            float o[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) o[v] = x[j][v] * rstd * g[v];
+            store16<T>(out + cv * V, o);
+            continue;
+        }
         if (a.beta) {
             load16<float>(a.beta + cv * V, b);
             if constexpr (V == 8) load16<float>(a.beta + cv * V + 4, b + 4);
@@ -84,8 +106,19 @@ __global__ __launch_bounds__(kLnBlock) void layernorm_kernel(const LnArgs a, con
     }
 }
 
+template <typename T, int LANES, int NV>
+__global__ __launch_bounds__(kLnBlock) void layernorm_kernel(const LnArgs a, const int64_t rows, const int cvn) {
+    ln_rows<T, LANES, NV, false>(a, rows, cvn);
+}
+
+template <typename T, int LANES, int NV>
+__global__ __launch_bounds__(kLnBlock) void rmsnorm_kernel(const LnArgs a, const int64_t rows, const int cvn) {
+    ln_rows<T, LANES, NV, true>(a, rows, cvn);
+}
+
 // one wave per pixel row (kLnBlock / 64 rows per workgroup)
-__global__ __launch_bounds__(kLnBlock) void layernorm_generic_kernel(const LnArgs a, const int64_t rows) {
+template <bool RMS>
+__device__ __forceinline__ void ln_row_generic(const LnArgs& a, const int64_t rows) {
     const int lane = int(threadIdx.x) % 64;
     const int64_t row = int64_t(blockIdx.x) * (kLnBlock / 64) + threadIdx.x / 64;
     if (row >= rows) return;                       // wave-uniform
@@ -96,6 +129,21 @@ __global__ __launch_bounds__(kLnBlock) void layernorm_generic_kernel(const LnArg
     const int64_t pn = r / a.in.h;
     const int64_t ib = pn * a.in.sn + int64_t(py) * a.in.sh + int64_t(px) * a.in.sw;
     const int64_t ob = pn * a.out.sn + int64_t(py) * a.out.sh + int64_t(px) * a.out.sw;
+    if constexpr (RMS) {
+        float q = 0.f;
+        for (int c = lane; c < C; c += 64) {
+            const float d = ld_any(a.in.p, a.in.f16, ib + int64_t(c) * a.in.sc);
+            q = fmaf(d, d, q);
+        }
+        const float rstd = 1.f / sqrtf(group_sum<64>(q) / float(C) + a.eps);  // (the shuffles order every lane's reads before any lane's writes)
+        for (int c = lane; c < C; c += 64) {
+            const float o = ld_any(a.in.p, a.in.f16, ib + int64_t(c) * a.in.sc) * rstd * a.gamma[c];
+            const int64_t oi = ob + int64_t(c) * a.out.sc;
+            if (a.out.f16) reinterpret_cast<_Float16*>(a.out.p)[oi] = _Float16(o);
+            else a.out.p[oi] = o;
+        }
+        return;
+    }
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += ld_any(a.in.p, a.in.f16, ib + int64_t(c) * a.in.sc);
     const float mean = group_sum<64>(s) / float(C);
@@ -114,11 +162,15 @@ __global__ __launch_bounds__(kLnBlock) void layernorm_generic_kernel(const LnArg
     }
 }
 
+__global__ __launch_bounds__(kLnBlock) void layernorm_generic_kernel(const LnArgs a, const int64_t rows) { ln_row_generic<false>(a, rows); }
+__global__ __launch_bounds__(kLnBlock) void rmsnorm_generic_kernel(const LnArgs a, const int64_t rows) { ln_row_generic<true>(a, rows); }
+
 template <typename T, int LANES, int NV>
 hipError_t launch_nv(const LnArgs& a, int64_t rows, int cvn, hipStream_t stream) {
     const int64_t blocks = (rows * LANES + kLnBlock - 1) / kLnBlock;
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-    layernorm_kernel<T, LANES, NV><<<dim3(unsigned(blocks)), dim3(kLnBlock), 0, stream>>>(a, rows, cvn);
+    if (a.rms) rmsnorm_kernel<T, LANES, NV><<<dim3(unsigned(blocks)), dim3(kLnBlock), 0, stream>>>(a, rows, cvn);
+    else layernorm_kernel<T, LANES, NV><<<dim3(unsigned(blocks)), dim3(kLnBlock), 0, stream>>>(a, rows, cvn);
     return hipGetLastError();
 }
 
@@ -146,7 +198,7 @@ hipError_t launch_fast(const LnArgs& a, int tile, int64_t rows, hipStream_t stre
 }  // namespace
 
 bool LayerNormEligible(const LnArgs& a, int tile) {
-    if (tile < 0 || tile >= kNumLnTiles || !a.in.p || !a.out.p || !a.gamma) return false;
+    if (tile < 0 || tile >= kNumLnTiles || !a.in.p || !a.out.p || !a.gamma || (a.rms && a.beta)) return false;
     if (a.in.f8 || a.out.f8 || a.in.c < 1 || a.in.c != a.out.c || a.in.n != a.out.n || a.in.h != a.out.h || a.in.w != a.out.w) return false;
     if (tile == 0) return true;
     const int V = a.out.f16 ? 8 : 4;
@@ -162,7 +214,8 @@ hipError_t LaunchLayerNorm(const LnArgs& a, int tile, hipStream_t stream) {
     if (tile == 0) {
         const int64_t blocks = (rows + kLnBlock / 64 - 1) / (kLnBlock / 64);
         if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(layernorm_generic_kernel, dim3(unsigned(blocks)), dim3(kLnBlock), 0, stream, a, rows);
+        if (a.rms) hipLaunchKernelGGL(rmsnorm_generic_kernel, dim3(unsigned(blocks)), dim3(kLnBlock), 0, stream, a, rows);
+        else hipLaunchKernelGGL(layernorm_generic_kernel, dim3(unsigned(blocks)), dim3(kLnBlock), 0, stream, a, rows);
         return hipGetLastError();
     }
     return a.out.f16 ? launch_fast<_Float16>(a, tile, rows, stream) : launch_fast<float>(a, tile, rows, stream);

@@ -42,6 +42,7 @@ LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     a.gamma = s.w_off >= 0 ? weights + s.w_off : nullptr;
     a.beta = s.bias_off >= 0 ? weights + s.bias_off : nullptr;
     a.eps = s.ln_eps;
+    a.rms = s.rms ? 1 : 0;
     return a;
 }
 
@@ -75,7 +76,7 @@ EmbedArgs MakeEmbedArgs(const PlanInstance& pi, const Step& s, const float* weig
     return a;
 }
 
-AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s) {
+AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     AttnArgs a;
     a.in = make_arg(pi, s.in);
     a.out = make_arg(pi, s.out);
@@ -88,6 +89,11 @@ AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s) {
         a.mask_value = s.mask_value;
     }
     a.causal = s.causal ? 1 : 0;
+    a.kv_heads = s.kv_heads;
+    if (s.rope) {
+        a.rope_cos = weights + s.w_off;
+        a.rope_sin = weights + s.w2_off;
+    }
     return a;
 }
 
@@ -583,6 +589,7 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             a.lo = s.lo;
             a.hi = s.hi;
             a.act = int(s.act.kind); a.act_a = s.act.a; a.act_b = s.act.b;
+            a.pre_act = int(s.pre_act.kind); a.pre_act_a = s.pre_act.a; a.pre_act_b = s.pre_act.b;
             a.b_mul = s.mul;
             a.b_bcast = s.has_in2 && s.in2.h * s.in2.w == 1 && s.out.h * s.out.w > 1;
             check(LaunchEltwise(a, stream_), "eltwise");
@@ -656,9 +663,10 @@ std::string kernel_label(const Step& s) {
             const int path = ResizePath(a);
             return path == 0 ? std::string(names[0]) : std::string(names[path]) + (s.in.f16 ? "f16>" : "f32>");
         }
-        case StepKind::LayerNorm:
-            return s.tile == 0 ? std::string("layernorm_generic_kernel")
-                               : std::string("layernorm_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
+        case StepKind::LayerNorm: {
+            const std::string stem = s.rms ? "rmsnorm" : "layernorm";
+            return s.tile == 0 ? stem + "_generic_kernel" : stem + "_kernel<" + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
+        }
         case StepKind::GroupNorm: {
             static const char* const acts[] = {"none", "sigmoid", "", "silu", "", "relu"};
             const std::string t = s.out.f16 ? "f16" : "f32";
@@ -672,9 +680,10 @@ std::string kernel_label(const Step& s) {
         case StepKind::TokenAssemble: return std::string("token_assemble_kernel<") + (s.out.f16 ? "f16>" : "f32>");
         case StepKind::Attention:
             if (s.tile == 2) return std::string("attention_stream_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
-            if (s.tile == 3) return std::string("attention_chunk_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.causal ? ",causal>" : ">");
+            if (s.tile == 3) return std::string("attention_chunk_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.rope ? ",causal,rope>" : s.causal ? ",causal>" : ">");
             return s.tile == 0 ? std::string(s.key_mask ? "attention_generic_kernel<mask>" : s.causal ? "attention_generic_kernel<causal>" : "attention_generic_kernel")
-                               : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.key_mask ? ",mask>" : s.causal ? ",causal>" : ">");
+                               : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) +
+                                     (s.key_mask ? ",mask>" : s.rope ? ",causal,rope>" : s.causal ? ",causal>" : ">");
         case StepKind::WindowAttention:
             return s.tile == 0 ? std::string("window_attention_generic_kernel")
                                : std::string("window_attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";

@@ -66,6 +66,7 @@ struct LNode {
     std::vector<float> w, bias;         // conv: w packed [Cout][kh][kw][Cin]
     std::vector<float> s, t;            // affine; L_LAYERNORM: gamma, beta (beta may be empty)
     float eps = 1e-5f;                  // L_LAYERNORM
+    bool rms = false;                   // L_LAYERNORM: an RMSNorm (no mean, no beta)
     // L_TOKASM: s = the class token [D], t = the position embedding [L][D] (empty: none); L_TOKPOS: t = the [L][D] constant an Add puts on tokens
     // L_ATTENTION: in = the qkv tokens [N, L, 3 heads head_dim]
     int heads = 0, head_dim = 0;
@@ -77,6 +78,7 @@ struct LNode {
     bool key_mask = false;              // L_ATTENTION: in[1] = the int64 key mask [N, L]; the bias of a masked key is mask_value
     float mask_value = 0.f;
     bool causal = false;                // L_ATTENTION: query i attends to the keys j <= i
+    int kv_heads = 0;                   // L_ATTENTION: K / V heads (0: heads); in = q (D) | k (Dkv) | v (Dkv).  Rotary: w / w2 = the cos / sin tables [L][head_dim]
     // L_EMBED: in = the int64 ids of the first table (and of the second); w = the first table [emb_vocab][D], w2 = the second [emb_types][D] (empty:
     // none), bias = the position rows [L][D] (empty: none), s / t / eps = gamma / beta / epsilon of the LayerNormalization behind the sum
     int64_t emb_vocab = 0, emb_types = 0;
@@ -410,7 +412,17 @@ struct Planner {
         // the causal mask (a Where or an additive constant on the scores), checked element by element; causal_len = its L
         bool causal = false;
         int64_t causal_len = 0;
+        // Llama's spelling of the split form: Linears without a bias, kv_heads K / V heads (k and v Linears [Din, kv_heads hd]) behind repeat_kv, and the
+        // rotary embedding on q and k: the cos / sin tables as the graph's constants broadcast them, [rope_rows][head_dim], and the node to name in a refusal
+        bool no_bias = false;
+        int64_t kv_heads = 0;
+        bool rope = false;
+        std::vector<float> rope_cos, rope_sin;
+        int64_t rope_rows = 0;
+        std::string rope_name;
+        std::vector<std::vector<int64_t>> rep_expand, rep_reshape;      // repeat_kv: the Expand and Reshape shapes (k, v), checked against N and L at the import
     };
+    std::set<const OnnxNode*> rope_const_nodes;      // the Unsqueeze / Slice / Gather nodes that cut the rope tables out of constants: evaluated at load, import nothing
     // MatchCausalWhere / MatchCausalAdd: the two spellings of a causal mask on the scores (false / a refusal by name: not one)
     void MatchCausalWhere(const OnnxNode& wh, const std::string& prefix, AttnMatch& am, std::vector<const OnnxNode*>& taken);
     bool MatchCausalAdd(const OnnxTensor& mk, AttnMatch& am) const;
@@ -524,6 +536,11 @@ struct Planner {
     void ImportGroupNorm(const OnnxNode& on, const GnMatch& gm);
     void FuseGroupNormActivations();
     void EmitGroupNorm(const LNode& n, Step& s);
+    // MatchRmsNorm: an RMSNorm spelled out (Pow | Mul(x, x) -> ReduceMean -> Add eps -> Sqrt -> Div(1, .) | Reciprocal -> Mul x -> Mul weight, Casts to
+    // FLOAT anywhere).  rms_head: its last Mul -> the RMSNormalization node (in synth_nodes) that imports in its place; rms_skip: its other nodes
+    std::map<const OnnxNode*, const OnnxNode*> rms_head;
+    std::set<const OnnxNode*> rms_skip;
+    void MatchRmsNorm();
     bool FoldExpand(const OnnxNode& on, const LNode& n);
     bool ImportTokenView(const OnnxNode& on, LNode& n);
     void ImportTokenConcat(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
@@ -543,6 +560,7 @@ struct Planner {
     // ---- graph-level fusions ----
     void FuseTokenAssemble();
     void FuseActivationPatterns();
+    void FuseGatedActivations();
     void FuseSqueezeExcite();
     void MergeAffineChains();
     void FuseConvEpilogues();
@@ -1140,7 +1158,7 @@ void Planner::ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t
             tok_out = L.is_tok(on.inputs[0]);
         }
         else if (op == "Tanh") n.act.kind = ActKind::Tanh;
-        else if (op == "Sigmoid") n.act.kind = ActKind::Sigmoid;
+        else if (op == "Sigmoid") { n.act.kind = ActKind::Sigmoid; tok_out = L.is_tok(on.inputs[0]); }      // (on tokens: the SiLU of a gated MLP)
         else if (op == "HardSigmoid") { n.act.kind = ActKind::HardSigmoid; n.act.a = on.attr_f("alpha", 0.2f); n.act.b = on.attr_f("beta", 0.5f); }
         else { n.act.kind = ActKind::HardSwish; n.act.a = 1.f / 6.f; n.act.b = 0.5f; }
         if (!act_input(on, 0)) fail(op + " " + n.name + ": constant input is not supported");
@@ -1331,7 +1349,9 @@ void Planner::ImportResize(const OnnxNode& on, LNode& n, std::vector<int64_t>& o
 // LayerNormalization-17 over the channel axis: the last axis of a channels-last view or of an [N, C] value.  (axis = 1 of an NCHW value would
 // normalise over C*H*W: refused.)
 void Planner::ImportLayerNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
-    if (!act_input(on, 0)) fail("LayerNormalization " + n.name + ": constant input is not supported");
+    const bool rms = on.op == "RMSNormalization";      // (opset 23, or the node MatchRmsNorm wrote for the spelled-out pattern)
+    const std::string who = on.op + " " + n.name;
+    if (!act_input(on, 0)) fail(who + ": constant input is not supported");
     const int x = in_val(on, 0);
     const Val& X = L.vals[x];
     const bool tok = L.is_tok(on.inputs[0]);
@@ -1339,17 +1359,19 @@ void Planner::ImportLayerNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>
     const int64_t rank = tok ? 3 : int64_t(X.dims.size()), axis_attr = on.attr_i("axis", -1);
     const int64_t axis = axis_attr < 0 ? axis_attr + rank : axis_attr;
     if (!(cl ? axis == rank - 1 : (rank == 2 && axis == 1)))
-        fail("LayerNormalization " + n.name + ": axis = " + std::to_string(axis_attr) + " on " + (tok ? std::string("a token view") : cl ? std::string("a channels-last view") : "an NCHW value of rank " + std::to_string(rank)) +
+        fail(who + ": axis = " + std::to_string(axis_attr) + " on " + (tok ? std::string("a token view") : cl ? std::string("a channels-last view") : "an NCHW value of rank " + std::to_string(rank)) +
              " is not supported (only the channel axis alone is normalised: the last axis of a channels-last view or of an [N, C] value)");
-    if (on.attr_i("stash_type", 1) != 1) fail("LayerNormalization " + n.name + ": stash_type = " + std::to_string(on.attr_i("stash_type", 1)) + " is not supported (1 is)");
+    if (on.attr_i("stash_type", 1) != 1) fail(who + ": stash_type = " + std::to_string(on.attr_i("stash_type", 1)) + " is not supported (1 is)");
     for (size_t k = 1; k < on.outputs.size(); ++k)
-        if (!on.outputs[k].empty()) fail("LayerNormalization " + n.name + ": the Mean / InvStdDev outputs are not supported");
+        if (!on.outputs[k].empty()) fail(who + ": the Mean / InvStdDev outputs are not supported");
     const OnnxTensor* g = on.inputs.size() > 1 ? L.init(on.inputs[1]) : nullptr;
-    if (!g || g->dims.size() != 1 || g->numel() != X.c) fail("LayerNormalization " + n.name + ": scale must be a [C] initializer");
+    if (!g || g->dims.size() != 1 || g->numel() != X.c) fail(who + ": scale must be a [C] initializer");
     n.s = g->f;
+    if (rms && on.inputs.size() > 2) fail(who + ": expected the inputs X and scale");
+    n.rms = rms;
     if (on.inputs.size() > 2 && !on.inputs[2].empty()) {
         const OnnxTensor* b = L.init(on.inputs[2]);
-        if (!b || b->dims.size() != 1 || b->numel() != X.c) fail("LayerNormalization " + n.name + ": B must be a [C] initializer");
+        if (!b || b->dims.size() != 1 || b->numel() != X.c) fail(who + ": B must be a [C] initializer");
         n.t = b->f;
     }
     n.kind = L_LAYERNORM;
@@ -1457,6 +1479,9 @@ void Planner::ImportNode(const OnnxNode& on) {
     // a matched group norm: its last node imports the whole of it (ImportGroupNorm checks what its input may be: a flat name is one of them)
     if (gn_skip.count(&on)) return;
     if (const auto gh = gn_head.find(&on); gh != gn_head.end()) { ImportGroupNorm(on, gh->second); return; }
+    // an RMSNorm spelled out: its last Mul imports the whole of it as the RMSNormalization node it is
+    if (rms_skip.count(&on)) return;
+    if (const auto rh = rms_head.find(&on); rh != rms_head.end()) { ImportNode(*rh->second); return; }
     // gelu_new spelled out: its last Mul imports the whole of it as the Gelu(approximate = "tanh") node it is
     if (gelu_skip.count(&on)) return;
     if (const auto gh = gelu_head.find(&on); gh != gelu_head.end()) {
@@ -1475,16 +1500,17 @@ void Planner::ImportNode(const OnnxNode& on) {
     }
     // a channels-last view may feed only the ops that read it as one: anything else (a Shape and the other folded ops included, hence before
     // the folds) would take its n / c / h / w for the ONNX dims
-    static const std::set<std::string> cl_ops = {"LayerNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose"};
+    static const std::set<std::string> cl_ops = {"LayerNormalization", "RMSNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose"};
     for (const std::string& name : on.inputs)
         if (L.is_cl(name) && !cl_ops.count(op))
             fail(op + " " + n.name + ": input " + name + " is a channels-last view (a Transpose with perm [0,2,3,1]); only LayerNormalization, MatMul, Add, Mul, Div, Erf, "
                  "Gelu and Transpose may read one");
     // token views likewise, and the two half-way names of their creation and of the way back
-    static const std::set<std::string> tok_ops = {"LayerNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose", "Concat", "Gather", "Reshape"};
+    static const std::set<std::string> tok_ops = {"LayerNormalization", "RMSNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose", "Concat", "Gather", "Reshape"};
     for (const std::string& name : on.inputs) {
-        // (a Conv1D's Gemm reads its token view like a MatMul; the Split of a GPT-2 attention is its head; a Pow is no operator of the planner at all, whatever it reads)
-        if (L.is_tok(name) && !tok_ops.count(op) && !(op == "Gemm" && conv1d_gemm.count(&on)) && !attn_head.count(&on) && op != "Pow")
+        // (a Conv1D's Gemm reads its token view like a MatMul; the Split of a GPT-2 attention is its head; a Pow is no operator of the planner at all, whatever it reads;
+        // a Sigmoid on tokens is the SiLU of a Llama MLP's gate)
+        if (L.is_tok(name) && !tok_ops.count(op) && !(op == "Gemm" && conv1d_gemm.count(&on)) && !attn_head.count(&on) && op != "Pow" && op != "Sigmoid")
             fail(op + " " + n.name + ": input " + name + " is a token view [N, L, D]; only LayerNormalization, MatMul, Add, Mul, Div, Erf, Gelu, Transpose, Concat, "
                  "Gather and the Reshape of the attention pattern may read one");
         if (L.flat_names.count(name) && op != "Transpose")
@@ -1504,7 +1530,7 @@ void Planner::ImportNode(const OnnxNode& on) {
     else if (op == "ConvTranspose") ImportConvTranspose(on, n, odims);
     else if (op == "MatMul" || op == "Gemm") ImportGemm(on, n, odims);
     else if (op == "BatchNormalization") ImportBatchNorm(on, n, odims);
-    else if (op == "LayerNormalization") ImportLayerNorm(on, n, odims);
+    else if (op == "LayerNormalization" || op == "RMSNormalization") ImportLayerNorm(on, n, odims);
     else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu" || op == "Erf" || op == "Gelu" || op == "Tanh") ImportActivation(on, n, odims);
     else if (op == "Add" || op == "Mul" || op == "Div") ImportArithmetic(on, n, odims);
     else if (op == "Concat") ImportConcat(on, n, odims);
@@ -1766,6 +1792,14 @@ void Planner::MatchAttention() {
         for (const OnnxNode* p : c.taken) attn_skip.insert(p);
         attn_skip.insert(c.orr);
     }
+    // the nodes that cut the rope tables out of constants were evaluated at load: they import nothing, and only rotary products may read them
+    for (const OnnxNode* p : rope_const_nodes) {
+        for (const OnnxNode* r : gi.readers_of(p->outputs[0]))
+            if (!attn_skip.count(r) && !rope_const_nodes.count(r))
+                fail(p->op + " " + (p->name.empty() ? p->outputs[0] : p->name) + ": the rope table " + p->outputs[0] + " is read by " + r->op + " " + (r->name.empty() ? r->outputs[0] : r->name) +
+                     "; only the products of a rotary embedding may read it");
+    }
+    for (const OnnxNode* p : rope_const_nodes) attn_skip.insert(p);
     // an ext chain is the matched attentions' alone
     for (const auto& kv : key_masks)
         if (kv.second.ok && kv.second.uses > 0) {
@@ -1994,6 +2028,14 @@ void Planner::MatchGeluTanh() {
 //   MatMul(q, kT) [* c | / c] -> [+ mask] -> Softmax -> MatMul(., v) -> Transpose [0,2,1,3] -> Reshape [N, L, D]
 // The three Linears read the same token value and are read by their Reshape alone: they become ONE Linear x -> [N, L, 3 D] (weights and bias
 // concatenated, column s D + h hd + e), and the attention node reads today's qkv layout.  false: q is not Transpose [0,2,1,3] (the other spelling)
+// Llama's eager attention is the same spelling with three additions, each matched here and refused by name on a near miss:
+//   * the Linears have no bias (a MatMul alone): the merged Linear then has none either
+//   * k and v come from narrower Linears [Din, Hkv hd] (Reshape [N, L, Hkv, hd]) and pass repeat_kv, Unsqueeze(axis 2) -> Expand([N, Hkv, g, L, hd]) ->
+//     Reshape([N, H, L, hd]) with constant shapes (g = 1: a no-op), behind their Transpose: the merged Linear is [Din, D + 2 Dkv], the step has kv_heads
+//   * q and k pass the rotary embedding between their Transpose [0,2,1,3] and the score MatMul, Add(Mul(t, cos), Mul(Concat(Neg(Slice(t, hd/2:)),
+//     Slice(t, :hd/2), axis -1), sin)), either operand order; cos / sin are float constants that broadcast as [1, 1, L, hd]: initializers, or Unsqueeze /
+//     Slice / Gather-by-constant of a [P, hd] table, evaluated here.  q and k must use the same tables, element for element; the tables ride in the
+//     weight blob and the kernels rotate inside their own loads (no step, no pass over the qkv buffer)
 bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const std::string& scores, const std::string& prefix, AttnMatch& am, const OnnxNode*& head,
                                   std::vector<const OnnxNode*>& taken) {
     auto miss = [&](const std::string& what) { fail(prefix + what); };
@@ -2014,19 +2056,192 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
             cur = p->inputs[c0 ? 1 : 0];
         }
     };
+    // ---- Llama's additions between Transpose(., [0,2,1,3]) and the two MatMuls ----
+    auto ints_of = [&](const OnnxNode* p, const char* attr, size_t input) {
+        std::vector<int64_t> v = p->attr_ints(attr, {});
+        if (v.empty() && p->inputs.size() > input && !p->inputs[input].empty()) if (const OnnxTensor* t = gi.cst(p->inputs[input])) v = t->i;
+        return v;
+    };
+    auto one_reader = [&](const OnnxNode* p) {
+        if (gi.nreaders(p->outputs[0]) != 1) miss("the intermediate " + p->outputs[0] + " (" + p->op + " " + nm_of(p) + ") has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
+    };
+    // a rope table as the graph's constants give it: an initializer / Constant, or Unsqueeze / Slice (step 1) / Gather(axis 0, constant indices) of one
+    std::function<bool(const std::string&, OnnxTensor&, std::vector<const OnnxNode*>&)> const_eval = [&](const std::string& name, OnnxTensor& out, std::vector<const OnnxNode*>& nodes) -> bool {
+        if (const OnnxTensor* t = gi.cst(name)) { out = *t; return !t->f.empty(); }
+        const OnnxNode* p = gi.producer(name);
+        if (!p || p->inputs.empty()) return false;
+        OnnxTensor in;
+        if (p->op != "Unsqueeze" && p->op != "Slice" && p->op != "Gather") return false;
+        if (!const_eval(p->inputs[0], in, nodes)) return false;
+        nodes.push_back(p);
+        const int64_t rank = int64_t(in.dims.size());
+        if (p->op == "Unsqueeze") {
+            std::vector<int64_t> ax = ints_of(p, "axes", 1);
+            if (ax.empty()) return false;
+            const int64_t orank = rank + int64_t(ax.size());
+            for (int64_t& a : ax) if (a < 0) a += orank;
+            std::sort(ax.begin(), ax.end());
+            out = in;
+            for (int64_t a : ax) { if (a < 0 || a > int64_t(out.dims.size())) return false; out.dims.insert(out.dims.begin() + a, 1); }
+            return true;
+        }
+        // Slice and Gather along one leading-row axis of the table: the rows [r0, r1) or the rows idx[...] of `in` seen as [rows][inner]
+        int64_t axis = 0;
+        std::vector<int64_t> pick;
+        if (p->op == "Gather") {
+            const OnnxTensor* ix = p->inputs.size() == 2 ? gi.cst(p->inputs[1]) : nullptr;
+            axis = p->attr_i("axis", 0);
+            if (!ix || ix->i.empty() || ix->dims.size() != 1) return false;
+            pick = ix->i;
+        } else {
+            const std::vector<int64_t> st = ints_of(p, "starts", 1), en = ints_of(p, "ends", 2), ax = ints_of(p, "axes", 3), sp = ints_of(p, "steps", 4);
+            if (st.size() != 1 || en.size() != 1 || ax.size() > 1 || sp.size() > 1 || (!sp.empty() && sp[0] != 1)) return false;
+            axis = ax.empty() ? 0 : ax[0];
+            if (axis < 0) axis += rank;
+            if (axis < 0 || axis >= rank) return false;
+            const int64_t n = in.dims[size_t(axis)];
+            int64_t a = st[0] < 0 ? st[0] + n : st[0], b = en[0] < 0 ? en[0] + n : en[0];
+            a = std::min(std::max(a, int64_t(0)), n);
+            b = std::min(std::max(b, int64_t(0)), n);
+            for (int64_t r = a; r < b; ++r) pick.push_back(r);
+        }
+        if (axis < 0) axis += rank;
+        if (axis < 0 || axis >= rank) return false;
+        int64_t outer = 1, inner = 1;
+        for (int64_t k = 0; k < axis; ++k) outer *= in.dims[size_t(k)];
+        for (int64_t k = axis + 1; k < rank; ++k) inner *= in.dims[size_t(k)];
+        const int64_t n = in.dims[size_t(axis)];
+        out = OnnxTensor();
+        out.dtype = in.dtype;
+        out.dims = in.dims;
+        out.dims[size_t(axis)] = int64_t(pick.size());
+        for (int64_t o = 0; o < outer; ++o)
+            for (int64_t r : pick) {
+                if (r < 0) r += n;
+                if (r < 0 || r >= n) return false;
+                out.f.insert(out.f.end(), in.f.begin() + (o * n + r) * inner, in.f.begin() + (o * n + r + 1) * inner);
+            }
+        return true;
+    };
+    struct Rope { bool on = false; std::vector<float> cos, sin; int64_t rows = 0, hd = 0; std::string name; };
+    // name = Add(Mul(t, cos), Mul(Concat(Neg(Slice(t, hd/2:)), Slice(t, :hd/2), axis -1), sin)), either operand order: -> t (name itself: no rotation here)
+    auto unrope = [&](const std::string& name, const char* which, Rope& r) -> std::string {
+        const OnnxNode* ad = gi.producer(name);
+        if (!ad || ad->op != "Add" || ad->inputs.size() != 2) return name;
+        const OnnxNode *m0 = gi.producer(ad->inputs[0]), *m1 = gi.producer(ad->inputs[1]);
+        if (!m0 || !m1 || m0->op != "Mul" || m1->op != "Mul" || m0->inputs.size() != 2 || m1->inputs.size() != 2) return name;
+        const std::string who = std::string("the rotary embedding of ") + which + " (Add " + nm_of(ad) + "): ";
+        r.name = nm_of(ad);
+        // the Mul whose activation operand is a Concat is the rotate_half branch
+        auto act_side = [&](const OnnxNode* mu, OnnxTensor& table) -> std::string {
+            for (int k = 0; k < 2; ++k) {
+                std::vector<const OnnxNode*> nodes;
+                OnnxTensor t;
+                if (const_eval(mu->inputs[size_t(k)], t, nodes)) {
+                    OnnxTensor dummy;
+                    std::vector<const OnnxNode*> n2;
+                    if (const_eval(mu->inputs[size_t(1 - k)], dummy, n2)) miss(who + "both operands of Mul " + nm_of(mu) + " are constants");
+                    table = std::move(t);
+                    for (const OnnxNode* p : nodes) rope_const_nodes.insert(p);
+                    return mu->inputs[size_t(1 - k)];
+                }
+            }
+            miss(who + "Mul " + nm_of(mu) + " has no constant operand: cos and sin must be float constants (initializers, or Unsqueeze / Slice / Gather by constants of a table)");
+            return "";
+        };
+        OnnxTensor t0, t1;
+        const std::string a0 = act_side(m0, t0), a1 = act_side(m1, t1);
+        const OnnxNode *c0 = gi.producer(a0), *c1 = gi.producer(a1);
+        const bool rot0 = c0 && c0->op == "Concat", rot1 = c1 && c1->op == "Concat";
+        if (rot0 == rot1) miss(who + "exactly one of its two products must read rotate_half, Concat(Neg(Slice(t, hd/2:)), Slice(t, :hd/2), axis -1)");
+        const OnnxNode* cat = rot0 ? c0 : c1;
+        const std::string t = rot0 ? a1 : a0;
+        OnnxTensor& cos = rot0 ? t1 : t0;
+        OnnxTensor& sin = rot0 ? t0 : t1;
+        // the tables broadcast as [1, 1, L, hd]
+        auto table2 = [&](OnnxTensor& tb, const char* what) {
+            std::vector<int64_t> d = tb.dims;
+            while (d.size() > 2 && d[0] == 1) d.erase(d.begin());
+            if (d.size() != 2 || tb.dims.size() > 4 || int64_t(tb.f.size()) != d[0] * d[1]) miss(who + "the " + what + " table does not broadcast as [1, 1, L, hd]");
+            tb.dims = d;
+        };
+        table2(cos, "cos");
+        table2(sin, "sin");
+        if (cos.dims != sin.dims) miss(who + "the cos and sin tables differ in shape");
+        const int64_t hd = cos.dims[1];
+        if (hd < 2 || hd % 2) miss(who + "the head size " + std::to_string(hd) + " of the tables is not even");
+        // rotate_half
+        const int64_t cax = cat->attr_i("axis", 0);
+        if (cat->inputs.size() != 2 || (cax != -1 && cax != 3)) miss(who + "Concat " + nm_of(cat) + " is not a Concat of two parts along the last axis");
+        const OnnxNode *ng = gi.producer(cat->inputs[0]), *lo = gi.producer(cat->inputs[1]);
+        if (!ng || ng->op != "Neg")
+            miss(who + "Concat " + nm_of(cat) + " is not rotate_half: its first part must be Neg(Slice(t, hd/2:)) and its second Slice(t, :hd/2); the order (x1, -x2) is another function");
+        const OnnxNode* hi = gi.producer(ng->inputs[0]);
+        auto half_slice = [&](const OnnxNode* sl, bool upper) {
+            if (!sl || sl->op != "Slice" || sl->inputs.empty() || sl->inputs[0] != t) return false;
+            const std::vector<int64_t> st = ints_of(sl, "starts", 1), en = ints_of(sl, "ends", 2), ax = ints_of(sl, "axes", 3), sp = ints_of(sl, "steps", 4);
+            if (st.size() != 1 || en.size() != 1 || ax.size() != 1 || (ax[0] != -1 && ax[0] != 3) || (!sp.empty() && (sp.size() != 1 || sp[0] != 1))) return false;
+            return upper ? st[0] == hd / 2 && en[0] >= hd : st[0] == 0 && en[0] == hd / 2;
+        };
+        if (!half_slice(hi, true) || !half_slice(lo, false))
+            miss(who + "Concat " + nm_of(cat) + " is not rotate_half of " + t + ": its parts must be Neg(Slice(t, " + std::to_string(hd / 2) + ":)) and Slice(t, :" + std::to_string(hd / 2) + ") along the last axis");
+        for (const OnnxNode* p : {m0, m1, cat, ng, hi, lo}) one_reader(p);
+        if (gi.nreaders(t) != 3) miss(who + "the rotated value " + t + " has " + std::to_string(gi.nreaders(t)) + " readers, not 3 (its product with cos and the two Slices of rotate_half)");
+        taken.insert(taken.end(), {ad, m0, m1, cat, ng, hi, lo});
+        r.on = true;
+        r.cos = cos.f;
+        r.sin = sin.f;
+        r.rows = cos.dims[0];
+        r.hd = hd;
+        return t;
+    };
+    // name = Reshape(Expand(Unsqueeze(t, axis 2), [N, Hkv, g, L, hd]), [N, H, L, hd]) with constant shapes: -> t (name itself: no repeat_kv here)
+    auto unrepeat = [&](const std::string& name, const char* which, int64_t& g) -> std::string {
+        const OnnxNode* rs = gi.producer(name);
+        const OnnxNode* ex = rs && rs->op == "Reshape" && !rs->inputs.empty() ? gi.producer(rs->inputs[0]) : nullptr;
+        if (!ex || ex->op != "Expand") return name;
+        const std::string who = std::string("repeat_kv of ") + which + " (Expand " + nm_of(ex) + "): ";
+        const OnnxNode* us = gi.producer(ex->inputs[0]);
+        if (!us || us->op != "Unsqueeze" || ints_of(us, "axes", 1) != std::vector<int64_t>{2}) miss(who + "its input is not Unsqueeze(., axes [2])");
+        const OnnxTensor *e5 = ex->inputs.size() == 2 ? gi.cst(ex->inputs[1]) : nullptr, *r4 = rs->inputs.size() == 2 ? gi.cst(rs->inputs[1]) : nullptr;
+        if (!e5 || e5->i.size() != 5 || !r4 || r4->i.size() != 4) miss(who + "the shapes of the Expand [N, Hkv, g, L, hd] and of the Reshape [N, H, L, hd] behind it must be constants");
+        g = e5->i[2];
+        if (g < 1) miss(who + "the group size " + std::to_string(g) + " is not positive");
+        for (const OnnxNode* p : {us, ex, rs}) one_reader(p);
+        taken.insert(taken.end(), {us, ex, rs});
+        am.rep_expand.push_back(e5->i);
+        am.rep_reshape.push_back(r4->i);
+        return us->inputs[0];
+    };
     const OnnxNode* qk = gi.producer(peel(scores));
-    const OnnxNode* qt = gi.producer(gi.peel_quiet(qk->inputs[0]));
-    if (!perm_is(qt, {0, 2, 1, 3})) { taken.clear(); return false; }
-    (void)peel(qk->inputs[0]);
+    {
+        // the other spelling (q a Gather / Squeeze slice of one transposed qkv tensor): nothing here is an Add of two products or a Transpose [0,2,1,3]
+        const OnnxNode* q0 = gi.producer(gi.peel_quiet(qk->inputs[0]));
+        const bool rope_add = q0 && q0->op == "Add" && q0->inputs.size() == 2 && gi.producer(q0->inputs[0]) && gi.producer(q0->inputs[0])->op == "Mul" &&
+                              gi.producer(q0->inputs[1]) && gi.producer(q0->inputs[1])->op == "Mul";
+        if (!perm_is(q0, {0, 2, 1, 3}) && !rope_add) { taken.clear(); return false; }
+    }
+    Rope rq, rk;
+    const OnnxNode* qt = gi.producer(unrope(peel(qk->inputs[0]), "q", rq));
+    if (!perm_is(qt, {0, 2, 1, 3})) miss(std::string("q is not ") + (rq.on ? "the rotary embedding of " : "") + "Transpose(Reshape(Linear(x), [N, L, H, hd]), [0,2,1,3])");
     const OnnxNode* kt = gi.producer(peel(qk->inputs[1]));
     const OnnxNode* k_rs = nullptr;
+    int64_t gk = 0, gv = 0;                        // repeat_kv's group size on k and on v (0: no repeat_kv)
     if (perm_is(kt, {0, 2, 3, 1})) k_rs = gi.producer(kt->inputs[0]);
-    else if (perm_is(kt, {0, 1, 3, 2}) && perm_is(gi.producer(kt->inputs[0]), {0, 2, 1, 3})) {
-        taken.push_back(gi.producer(kt->inputs[0]));
-        k_rs = gi.producer(gi.producer(kt->inputs[0])->inputs[0]);
+    else if (perm_is(kt, {0, 1, 3, 2})) {
+        const OnnxNode* k2 = gi.producer(unrope(unrepeat(kt->inputs[0], "k", gk), "k", rk));
+        if (!perm_is(k2, {0, 2, 1, 3})) miss("the second operand of MatMul " + nm_of(qk) + " is neither Transpose(Transpose(k, [0,2,1,3]), [0,1,3,2]) nor Transpose(k, [0,2,3,1])");
+        taken.push_back(k2);
+        k_rs = gi.producer(k2->inputs[0]);
     } else miss("the second operand of MatMul " + nm_of(qk) + " is neither Transpose(Transpose(k, [0,2,1,3]), [0,1,3,2]) nor Transpose(k, [0,2,3,1])");
-    const OnnxNode* vt = gi.producer(pv->inputs[1]);
+    const OnnxNode* vt = gi.producer(unrepeat(pv->inputs[1], "v", gv));
     if (!perm_is(vt, {0, 2, 1, 3})) miss("the second operand of MatMul " + nm_of(pv) + " is not Transpose(v, perm [0,2,1,3])");
+    if (rq.on != rk.on) miss(std::string("only ") + (rq.on ? "q" : "k") + " passes a rotary embedding (Add " + (rq.on ? rq.name : rk.name) + "); q and k must both be rotated");
+    if (rq.on) {
+        if (rq.rows != rk.rows || rq.hd != rk.hd || rq.cos != rk.cos) miss("the cos table of q (Add " + rq.name + ") is not the cos table of k (Add " + rk.name + "), element for element");
+        if (rq.sin != rk.sin) miss("the sin table of q (Add " + rq.name + ") is not the sin table of k (Add " + rk.name + "), element for element");
+    }
+    if (gk != gv) miss("repeat_kv repeats k " + std::to_string(gk) + " times and v " + std::to_string(gv) + " times");
     const OnnxNode* rs[3] = {gi.producer(qt->inputs[0]), k_rs, gi.producer(vt->inputs[0])};
     static const char* const which[3] = {"q", "k", "v"};
     const OnnxNode *mm[3], *add[3];
@@ -2057,28 +2272,48 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         }
         if (!parts.empty() && parts != std::vector<int64_t>{D, D, D}) miss("Split " + nm_of(sp) + " does not cut [H * hd, H * hd, H * hd] = three parts of " + std::to_string(D));
     }
+    int64_t kvh = 0;                               // K / V heads of the split form (k's and v's Reshape)
     for (int s = 0; s < 3 && !fused; ++s) {
         const OnnxTensor* s4 = rs[s] && rs[s]->op == "Reshape" && rs[s]->inputs.size() == 2 ? gi.cst(rs[s]->inputs[1]) : nullptr;
         if (!s4 || s4->i.size() != 4 || s4->i[2] <= 0 || s4->i[3] <= 0) miss(std::string(which[s]) + " is not Reshape(Linear(x), [N, L, H, hd]) with a constant shape");
         if (s == 0) shape4 = s4->i;
-        else if (s4->i[2] != shape4[2] || s4->i[3] != shape4[3]) miss("the q / k / v Reshapes differ in heads or head size");
-        add[s] = gi.producer(rs[s]->inputs[0]);
-        if (!add[s] || add[s]->op != "Add" || add[s]->inputs.size() != 2) miss(std::string(which[s]) + " is not the Reshape of a Linear (MatMul + Add)");
-        const int bi = gi.cst(add[s]->inputs[0]) ? 0 : 1;
-        B[s] = gi.cst(add[s]->inputs[size_t(bi)]);
-        mm[s] = gi.producer(add[s]->inputs[size_t(1 - bi)]);
-        W[s] = mm[s] && mm[s]->op == "MatMul" && mm[s]->inputs.size() == 2 ? gi.cst(mm[s]->inputs[1]) : nullptr;
-        if (!B[s] || !W[s] || gi.cst(mm[s]->inputs[0]) || W[s]->f.empty() || B[s]->f.empty() || W[s]->dims.size() != 2)
+        else if (s4->i[3] != shape4[3] || (s == 2 && s4->i[2] != kvh)) miss("the q / k / v Reshapes differ in heads or head size");
+        if (s == 1) kvh = s4->i[2];
+        // grouped K / V heads: fewer heads on k and v, whole groups of query heads per K / V head, repeat_kv by exactly that group
+        if (s == 1 && kvh != shape4[2]) {
+            if (kvh > shape4[2] || shape4[2] % kvh)
+                miss("heads % kv_heads != 0: q has " + std::to_string(shape4[2]) + " heads (Reshape " + nm_of(rs[0]) + "), k has " + std::to_string(kvh) + " (Reshape " + nm_of(rs[1]) +
+                     "); a K / V head serves a whole group of query heads");
+            if (gk != shape4[2] / kvh) miss("k and v have " + std::to_string(kvh) + " heads for q's " + std::to_string(shape4[2]) + ", but repeat_kv repeats them " + std::to_string(gk) + " times, not " + std::to_string(shape4[2] / kvh));
+        }
+        if (s == 1 && kvh == shape4[2] && gk > 1) miss("repeat_kv repeats k and v " + std::to_string(gk) + " times although they have q's " + std::to_string(kvh) + " heads");
+        const int64_t Ds = s4->i[2] * s4->i[3];    // this Linear's columns: H hd for q, Hkv hd for k and v
+        // the Linear: MatMul + Add, or the MatMul alone (Llama's projections have no bias)
+        const OnnxNode* top = gi.producer(rs[s]->inputs[0]);
+        add[s] = top && top->op == "Add" && top->inputs.size() == 2 ? top : nullptr;
+        B[s] = nullptr;
+        if (add[s]) {
+            const int bi = gi.cst(add[s]->inputs[0]) ? 0 : 1;
+            B[s] = gi.cst(add[s]->inputs[size_t(bi)]);
+            mm[s] = gi.producer(add[s]->inputs[size_t(1 - bi)]);
+            if (!B[s] || B[s]->f.empty()) miss(std::string(which[s]) + " is not the Reshape of a Linear (MatMul(x, W [Din, D]) + b [D])");
+        } else mm[s] = top;
+        if (!mm[s] || mm[s]->op != "MatMul") miss(std::string(which[s]) + " is not the Reshape of a Linear (MatMul + Add, or a MatMul alone)");
+        W[s] = mm[s]->inputs.size() == 2 ? gi.cst(mm[s]->inputs[1]) : nullptr;
+        if (!W[s] || gi.cst(mm[s]->inputs[0]) || W[s]->f.empty() || W[s]->dims.size() != 2)
             miss(std::string(which[s]) + " is not the Reshape of a Linear (MatMul(x, W [Din, D]) + b [D])");
         if (mm[s]->inputs[0] != mm[0]->inputs[0])
             miss("the " + std::string(which[s]) + " Linear " + nm_of(mm[s]) + " reads " + mm[s]->inputs[0] + ", the q Linear " + mm[0]->inputs[0] + " (q, k and v must come from the same tokens)");
-        const int64_t D = shape4[2] * shape4[3];
-        if (W[s]->dims != W[0]->dims || W[s]->dims[1] != D || B[s]->numel() != D)
-            miss("the " + std::string(which[s]) + " Linear " + nm_of(mm[s]) + " is not [Din, H * hd = " + std::to_string(D) + "] with a bias [" + std::to_string(D) + "] like the q Linear");
+        if (W[s]->dims[0] != W[0]->dims[0] || W[s]->dims[1] != Ds || (B[s] && B[s]->numel() != Ds))
+            miss("the " + std::string(which[s]) + " Linear " + nm_of(mm[s]) + " is not [Din, H * hd = " + std::to_string(Ds) + "] with a bias [" + std::to_string(Ds) + "] like the q Linear");
         for (const OnnxNode* p : {mm[s], add[s], rs[s]})
-            if (gi.nreaders(p->outputs[0]) != 1) miss("the " + std::string(which[s]) + " Linear's " + p->op + " " + nm_of(p) + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1 (only its own attention may read it)");
-        taken.insert(taken.end(), {mm[s], add[s], rs[s]});
+            if (p && gi.nreaders(p->outputs[0]) != 1) miss("the " + std::string(which[s]) + " Linear's " + p->op + " " + nm_of(p) + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1 (only its own attention may read it)");
+        taken.push_back(mm[s]);
+        if (add[s]) taken.push_back(add[s]);
+        taken.push_back(rs[s]);
     }
+    if (fused && (rq.on || gk > 0)) miss("a rotary embedding or repeat_kv behind the Split of one qkv Linear is not supported (the separate q / k / v Linears are)");
+    if (rq.on && rq.hd != shape4[3]) miss("the rope tables (Add " + rq.name + ") are " + std::to_string(rq.hd) + " wide, the heads " + std::to_string(shape4[3]));
     const int64_t axis = sm.attr_i("axis", -1);
     if (axis != -1 && axis != 3) miss("Softmax axis = " + std::to_string(axis) + " (only the last axis, -1 or 3, is an attention)");
     const OnnxNode* ot = gi.only_reader(pv->outputs[0]);
@@ -2086,10 +2321,11 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
     const OnnxNode* orr = gi.only_reader(ot->outputs[0]);
     const OnnxTensor* s3 = orr && orr->op == "Reshape" && orr->inputs.size() == 2 ? gi.cst(orr->inputs[1]) : nullptr;
     if (!s3 || s3->i.size() != 3) miss("the transposed result is not read by Reshape(., [N, L, D]) alone");
+    // (a rotated value has three readers, its product with cos and the two Slices of rotate_half: the rotary match counted them)
     for (const OnnxNode* p : {qk, qt, kt, vt, pv, ot, &sm})
-        if (gi.nreaders(p->outputs[0]) != 1) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
+        if (gi.nreaders(p->outputs[0]) != (rq.on && p == qt ? 3 : 1)) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
     for (const OnnxNode* p : taken)
-        if ((p->op == "Mul" || p->op == "Div" || p->op == "Transpose") && gi.nreaders(p->outputs[0]) != 1) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
+        if ((p->op == "Mul" || p->op == "Div" || p->op == "Transpose") && gi.nreaders(p->outputs[0]) != (rk.on && perm_is(p, {0, 2, 1, 3}) ? 3 : 1)) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
     taken.insert(taken.end(), {qk, qt, kt, vt, pv, ot, orr, &sm});
     if (fused) {
         head = sp;
@@ -2102,16 +2338,32 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         am.shape3 = s3->i;
         return true;
     }
-    // the merged Linear: column s D + h hd + e
-    const int64_t Din = W[0]->dims[0], D = W[0]->dims[1];
+    // the merged Linear: columns q (D) | k (Dkv) | v (Dkv), head h at h hd inside its part; without a bias where none of the three has one
+    const int64_t Din = W[0]->dims[0], D = W[0]->dims[1], Dkv = W[1]->dims[1], Dall = D + 2 * Dkv;
+    const int64_t off[3] = {0, D, D + Dkv};
     OnnxTensor w, b;
     w.dtype = b.dtype = ONNX_FLOAT;
-    w.dims = {Din, 3 * D};
-    b.dims = {3 * D};
-    w.f.resize(size_t(Din * 3 * D));
+    w.dims = {Din, Dall};
+    b.dims = {Dall};
+    w.f.resize(size_t(Din * Dall));
     for (int64_t k = 0; k < Din; ++k)
-        for (int s = 0; s < 3; ++s) std::copy(W[s]->f.begin() + k * D, W[s]->f.begin() + (k + 1) * D, w.f.begin() + k * 3 * D + s * D);
-    for (int s = 0; s < 3; ++s) b.f.insert(b.f.end(), B[s]->f.begin(), B[s]->f.end());
+        for (int s = 0; s < 3; ++s) {
+            const int64_t Ds = W[s]->dims[1];
+            std::copy(W[s]->f.begin() + k * Ds, W[s]->f.begin() + (k + 1) * Ds, w.f.begin() + k * Dall + off[s]);
+        }
+    am.no_bias = !B[0] && !B[1] && !B[2];
+    for (int s = 0; s < 3 && !am.no_bias; ++s) {
+        if (B[s]) b.f.insert(b.f.end(), B[s]->f.begin(), B[s]->f.end());
+        else b.f.insert(b.f.end(), size_t(W[s]->dims[1]), 0.f);      // (a mixed form: some of the three Linears have a bias)
+    }
+    am.kv_heads = kvh;
+    if (rq.on) {
+        am.rope = true;
+        am.rope_cos = rq.cos;
+        am.rope_sin = rq.sin;
+        am.rope_rows = rq.rows;
+        am.rope_name = rq.name;
+    }
     // the head: the first of the three MatMuls in graph order (x is defined there)
     for (const OnnxNode& on : m.nodes) if (&on == mm[0] || &on == mm[1] || &on == mm[2]) { head = &on; break; }
     am.split = true;
@@ -2120,7 +2372,7 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
     am.w_name = w.name = am.name + "/qkv_w";
     am.b_name = b.name = am.name + "/qkv_b";
     L.add_derived(std::move(w));
-    L.add_derived(std::move(b));
+    if (!am.no_bias) L.add_derived(std::move(b));
     am.heads = shape4[2];
     am.head_dim = shape4[3];
     am.scale = scale;
@@ -2242,17 +2494,31 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
         add.name = am.name + "/qkv_bias";
         add.inputs = {mm.outputs[0], am.b_name};
         add.outputs = {am.name + "/qkv_out"};
-        qkv = add.outputs[0];
+        qkv = am.no_bias ? mm.outputs[0] : add.outputs[0];
         synth_nodes.push_back(std::move(mm));
         ImportNode(synth_nodes.back());
-        synth_nodes.push_back(std::move(add));
-        ImportNode(synth_nodes.back());
+        if (!am.no_bias) {
+            synth_nodes.push_back(std::move(add));
+            ImportNode(synth_nodes.back());
+        }
     }
     if (!L.is_tok(qkv)) miss("its qkv input " + qkv + " is not a token view [N, L, 3 D]");
     const int x = L.get_val(qkv);
     const Val X = L.vals[x];
-    const int64_t D = am.heads * am.head_dim;
-    if (X.c != 3 * D) miss("the qkv rows have " + std::to_string(X.c) + " columns, not 3 * H * hd = " + std::to_string(3 * D));
+    const int64_t D = am.heads * am.head_dim, Hkv = am.kv_heads > 0 ? am.kv_heads : am.heads;
+    if (X.c != D + 2 * Hkv * am.head_dim)
+        miss("the qkv rows have " + std::to_string(X.c) + " columns, not " + (Hkv == am.heads ? "3 * H * hd = " : "(H + 2 Hkv) * hd = ") + std::to_string(D + 2 * Hkv * am.head_dim));
+    // repeat_kv's constant shapes: Expand to [N, Hkv, g, L, hd] (a 1 keeps the dim), Reshape to [N, H, L, hd]
+    for (size_t k = 0; k < am.rep_expand.size(); ++k) {
+        const std::vector<int64_t>&e = am.rep_expand[k], &r = am.rep_reshape[k];
+        const int64_t want5[5] = {X.n, Hkv, e[2], X.w, am.head_dim}, want4[4] = {X.n, am.heads, X.w, am.head_dim};
+        bool ok = e[2] * Hkv == am.heads;
+        for (int d = 0; d < 5; ++d) ok = ok && (e[size_t(d)] == want5[d] || (d != 2 && e[size_t(d)] == 1));
+        int neg = 0;
+        for (int d = 0; d < 4; ++d) { neg += r[size_t(d)] == -1; ok = ok && (r[size_t(d)] == want4[d] || r[size_t(d)] == -1 || (d == 0 && r[0] == 0)); }
+        if (!ok || neg > 1) miss("repeat_kv does not expand to [N, Hkv, g, L, hd] = [" + std::to_string(X.n) + ", " + std::to_string(Hkv) + ", " + std::to_string(am.heads / Hkv) + ", " + std::to_string(X.w) + ", " +
+                                 std::to_string(am.head_dim) + "] and reshape to [N, H, L, hd]");
+    }
     if (!am.split && !am.fused && ((am.shape5[0] != 0 && am.shape5[0] != X.n) || (am.shape5[1] != -1 && am.shape5[1] != 0 && am.shape5[1] != X.w))) miss("the Reshape to [N, L, 3, H, hd] does not keep N and L");
     if ((am.shape3[0] != 0 && am.shape3[0] != X.n) || (am.shape3[1] != -1 && am.shape3[1] != 0 && am.shape3[1] != X.w) || (am.shape3[2] != -1 && am.shape3[2] != D))
         miss("the last Reshape is not to [N, L, H * hd]");
@@ -2271,6 +2537,14 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
         n.in.push_back(mv);
         n.key_mask = true;
         n.mask_value = am.mask_value;
+    }
+    n.kv_heads = int(Hkv);
+    if (am.rope) {
+        if (!am.mask.empty()) miss("a rotary embedding (Add " + am.rope_name + ") together with a key mask (attention_mask) is not supported");
+        if (am.rope_rows != X.w)
+            miss("the rope tables (Add " + am.rope_name + ") have " + std::to_string(am.rope_rows) + " rows after slicing, the sequence has " + std::to_string(X.w) + " tokens (table rows != L)");
+        n.w = am.rope_cos;
+        n.w2 = am.rope_sin;
     }
     if (am.causal) {
         if (am.causal_len != X.w) miss("its causal mask is [1, 1, " + std::to_string(am.causal_len) + ", " + std::to_string(am.causal_len) + "], the sequence has " + std::to_string(X.w) + " tokens");
@@ -2691,8 +2965,10 @@ void Planner::MatchEmbed() {
             else if (r->op == "Add") { cur = r->outputs[0]; continue; }
             else if (r->op == "LayerNormalization" && r->inputs[0] == cur) { ln = r; break; }
             else refusal = r->op + " " + (r->name.empty() ? r->outputs[0] : r->name) + ": reads the embedding sum " + cur + "; only Adds and then a LayerNormalization may (the embedding and its LayerNormalization run as one step)";
+            // (a Llama-class model has no position rows: the Gather itself is the value its first RMSNorm and the residual Add read, and heads the step)
             const OnnxNode* last = gi.producer(cur);
-            if (cur == g.outputs[0] || !last || last->op != "Add") fail(refusal);
+            if (cur == g.outputs[0] && !r) last = &g;      // (several readers: a sole reader that is neither an Add nor a LayerNormalization keeps its refusal)
+            else if (cur == g.outputs[0] || !last || last->op != "Add") fail(refusal);
             ln = last;
             break;
         }
@@ -2700,7 +2976,7 @@ void Planner::MatchEmbed() {
         const std::string lname = ln->name.empty() ? ln->outputs[0] : ln->name;
         EmbedMatch em;
         em.sum_only = !refusal.empty();
-        const std::string who = (em.sum_only ? "Add " : "LayerNormalization ") + lname;
+        const std::string who = (ln == &g ? "Gather " : em.sum_only ? "Add " : "LayerNormalization ") + lname;
         std::vector<const OnnxNode*> gathers, taken;
         int pos_count = 0;
         int64_t Lq = 0;
@@ -2727,7 +3003,7 @@ void Planner::MatchEmbed() {
                 return;
             }
             if (p && table_gather(*p)) {
-                if (gi.nreaders(name) != 1) fail("Gather " + (p->name.empty() ? name : p->name) + ": " + name + " has " + std::to_string(gi.nreaders(name)) + " readers; an embedding gather is read by its sum alone");
+                if (gi.nreaders(name) != 1 && p != ln) fail("Gather " + (p->name.empty() ? name : p->name) + ": " + name + " has " + std::to_string(gi.nreaders(name)) + " readers; an embedding gather is read by its sum alone");
                 gathers.push_back(p);
                 return;
             }
@@ -2771,7 +3047,7 @@ void Planner::MatchEmbed() {
                  "(nor the Gather of a table by constant position ids)");
         };
         walk(em.sum_only ? ln->outputs[0] : ln->inputs[0]);
-        if (em.sum_only && (gathers.size() != 1 || pos_count != 1)) fail(refusal);
+        if (em.sum_only && (gathers.size() != 1 || pos_count != (ln == &g ? 0 : 1))) fail(refusal);
         if (gathers.empty() || gathers.size() > 2)
             fail(who + ": the embedding sum has " + std::to_string(gathers.size()) + " table Gathers by graph inputs (one or two are supported)");
         std::sort(gathers.begin(), gathers.end(), [&](const OnnxNode* a, const OnnxNode* b) { return input_index(a->inputs[1]) < input_index(b->inputs[1]); });
@@ -2784,7 +3060,7 @@ void Planner::MatchEmbed() {
             em.ids.push_back(t->inputs[1]);
             em.tables.push_back(tab);
             em.names += (em.names.empty() ? "" : "+") + (t->name.empty() ? t->outputs[0] : t->name);
-            embed_skip.insert(t);
+            if (t != ln) embed_skip.insert(t);
         }
         for (const OnnxNode* t : taken) if (t != ln) embed_skip.insert(t);
         embed_head[ln] = std::move(em);
@@ -2794,7 +3070,7 @@ void Planner::MatchEmbed() {
         for (const auto& vo : m.outputs) if (vo.name == in) fail("graph output " + in + " is an INT64 graph input; only the Gather of an embedding table may read one");
         for (const OnnxNode* r : gi.readers_of(in))
             if (mask_nodes.count(r)) continue;             // the key mask of the attentions (MatchAttention took its chain)
-            else if (!embed_skip.count(r) || r->op != "Gather")
+            else if ((!embed_skip.count(r) && !embed_head.count(r)) || r->op != "Gather")
                 fail(r->op + " " + (r->name.empty() ? r->outputs[0] : r->name) + ": reads the INT64 graph input " + in + "; only the Gather (axis 0) of a floating-point embedding table [V, D] may read one");
     }
 }
@@ -2814,7 +3090,7 @@ void Planner::ImportEmbed(const OnnxNode& on, const EmbedMatch& em) {
         n.emb_vocab = em.tables[0]->dims[0];
         n.bias = em.pos;
         if (n.emb_vocab < 1 || n.emb_vocab >= (int64_t(1) << 31) || D < 1 || D >= (int64_t(1) << 31)) fail("Add " + n.name + ": embedding table sizes out of range");
-        n.name = em.names + "+" + n.name;
+        n.name = on.op == "Gather" ? em.names : em.names + "+" + n.name;      // (a Gather that heads its own step is its only node)
         push_node(std::move(n), on.outputs[0], {N, D, 1, Lq}, true);
         return;
     }
@@ -2936,6 +3212,114 @@ void Planner::MatchGroupNorm() {
         for (const OnnxNode* p : taken) if (p->op != "Shape") gm.name += (gm.name.empty() ? "" : "+") + nm(*p);
         for (const OnnxNode* p : taken) if (p != last) gn_skip.insert(p);
         gn_head[last] = gm;
+    }
+}
+
+// ---- RMSNorm as exporters write it below opset 23 (HF's LlamaRMSNorm) ---------------------------------------------------------------------------
+//   v = ReduceMean(Pow(x, 2) | Mul(x, x), axes [-1], keepdims 1);  y = Mul(weight [D], Mul(x, Reciprocal(Sqrt(Add(v, eps))) | Div(1, Sqrt(Add(v, eps)))))
+// either operand order on every Mul / Add, the axes as an attribute or as an input, Cast(to = FLOAT) nodes anywhere in between (hidden_states.to(float32)
+// exports as one; the values here are floats already, so they are names).  The match starts at a ReduceMean of a square; from there a node that is not
+// the pattern's is refused by name.  A ReduceMean of anything else stays what it was, an unsupported operator.  The last Mul imports the whole as an
+// RMSNormalization node over the ReduceMean's axis (ImportLayerNorm checks that it is the channel axis of x's view and that weight is [D])
+void Planner::MatchRmsNorm() {
+    bool any = false;
+    for (const OnnxNode& on : m.nodes) any = any || on.op == "ReduceMean";
+    if (!any) return;
+    IndexGraph();
+    auto nm = [](const OnnxNode& o) { return o.name.empty() ? o.outputs[0] : o.name; };
+    auto float_cast = [](const OnnxNode* p) { return p && p->op == "Cast" && p->inputs.size() == 1 && p->attr_i("to", 0) == ONNX_FLOAT; };
+    auto scalar = [&](const std::string& name, double& v) {
+        const OnnxTensor* t = gi.cst(name);
+        if (!t || t->numel() != 1 || (t->f.size() != 1 && t->i.size() != 1)) return false;
+        v = t->f.size() == 1 ? double(t->f[0]) : double(t->i[0]);
+        return true;
+    };
+    for (const OnnxNode& rm : m.nodes) {
+        if (rm.op != "ReduceMean" || rm.inputs.empty() || rm.outputs.size() != 1) continue;
+        std::vector<const OnnxNode*> taken;
+        // the name above a chain of Casts to FLOAT
+        auto up = [&](std::string name) {
+            for (const OnnxNode* p = gi.producer(name); float_cast(p); p = gi.producer(name)) { taken.push_back(p); name = p->inputs[0]; }
+            return name;
+        };
+        const OnnxNode* sq = gi.producer(up(rm.inputs[0]));
+        if (!sq || sq->inputs.size() != 2) continue;
+        double e = 0.0;
+        std::string x;
+        if (sq->op == "Pow" && scalar(sq->inputs[1], e) && e == 2.0) x = up(sq->inputs[0]);
+        else if (sq->op == "Mul" && up(sq->inputs[0]) == up(sq->inputs[1])) x = up(sq->inputs[0]);
+        else continue;
+        if (gi.cst(x)) continue;
+        taken.insert(taken.end(), {sq, &rm});
+        const std::string prefix = "ReduceMean " + nm(rm) + ": the RMSNorm pattern around it does not match: ";
+        // the sole reader of a name, below a chain of Casts to FLOAT
+        auto down = [&](std::string name) -> const OnnxNode* {
+            for (;;) {
+                const OnnxNode* r = gi.only_reader(name);
+                if (!r) fail(prefix + "the intermediate value " + name + " has " + std::to_string(gi.nreaders(name)) + " readers, not 1");
+                if (!float_cast(r)) return r;
+                taken.push_back(r);
+                name = r->outputs[0];
+            }
+        };
+        // r reads `from` (below Casts) as one of its two operands: the index of the other one
+        auto other = [&](const OnnxNode* r, const std::string& from) {
+            if (r->inputs.size() != 2) return -1;
+            for (int k = 0; k < 2; ++k) if (up(r->inputs[size_t(k)]) == from) return 1 - k;
+            return -1;
+        };
+        std::vector<int64_t> axes = rm.attr_ints("axes", {});
+        if (rm.inputs.size() > 1 && !rm.inputs[1].empty()) {
+            const OnnxTensor* t = gi.cst(rm.inputs[1]);
+            if (!t || t->i.empty()) fail(prefix + "the axes must be an integer constant");
+            axes = t->i;
+        }
+        if (axes.size() != 1) fail(prefix + "the mean is taken over " + std::to_string(axes.size()) + " axes, not over the last one alone");
+        if (rm.attr_i("keepdims", 1) != 1) fail(prefix + "keepdims must be 1");
+        const OnnxNode* ad = down(rm.outputs[0]);
+        int k = ad->op == "Add" ? other(ad, rm.outputs[0]) : -1;
+        double eps = 0.0;
+        if (k < 0 || !scalar(ad->inputs[size_t(k)], eps) || !(eps >= 0.0)) fail(prefix + ad->op + " " + nm(*ad) + " reads the mean; an Add of the scalar constant eps must");
+        taken.push_back(ad);
+        const OnnxNode* sr = down(ad->outputs[0]);
+        if (sr->op != "Sqrt") fail(prefix + sr->op + " " + nm(*sr) + " reads the sum with eps; a Sqrt must");
+        taken.push_back(sr);
+        const OnnxNode* rc = down(sr->outputs[0]);
+        double one = 0.0;
+        const bool recip = (rc->op == "Reciprocal" && rc->inputs.size() == 1) ||
+                           (rc->op == "Div" && rc->inputs.size() == 2 && up(rc->inputs[1]) == sr->outputs[0] && scalar(rc->inputs[0], one) && one == 1.0);
+        if (!recip) fail(prefix + rc->op + " " + nm(*rc) + " reads the root; a Reciprocal or Div(1, root) must");
+        taken.push_back(rc);
+        const OnnxNode* mx = down(rc->outputs[0]);
+        k = mx->op == "Mul" ? other(mx, rc->outputs[0]) : -1;
+        if (k < 0 || up(mx->inputs[size_t(k)]) != x) fail(prefix + mx->op + " " + nm(*mx) + " reads the reciprocal root; a Mul with " + x + ", the value that was squared, must");
+        taken.push_back(mx);
+        const OnnxNode* mw = down(mx->outputs[0]);
+        k = mw->op == "Mul" ? other(mw, mx->outputs[0]) : -1;
+        const OnnxTensor* w = k >= 0 ? gi.cst(mw->inputs[size_t(k)]) : nullptr;
+        if (!w || w->f.empty() || w->dims.size() != 1) fail(prefix + mw->op + " " + nm(*mw) + " reads the normalised value; a Mul with the weight, a floating-point constant [D], must");
+        // every taken node but the last Mul is read inside the pattern only (a Cast of x may feed the square and the product: both are taken)
+        std::set<const OnnxNode*> inside(taken.begin(), taken.end());
+        inside.insert(mw);
+        for (const OnnxNode* p : taken)
+            for (const OnnxNode* r : gi.readers_of(p->outputs[0]))
+                if (!inside.count(r)) fail(prefix + "the intermediate value " + p->outputs[0] + " has a reader outside the pattern (" + r->op + " " + nm(*r) + ")");
+        for (const auto& vo : m.outputs)
+            for (const OnnxNode* p : taken) if (p->outputs[0] == vo.name) fail(prefix + "the intermediate value " + vo.name + " is a graph output");
+        OnnxNode g;
+        g.op = "RMSNormalization";
+        for (const OnnxNode& on : m.nodes)      // (graph order)
+            if (inside.count(&on) && on.op != "Cast") g.name += (g.name.empty() ? "" : "+") + nm(on);
+        g.inputs = {x, mw->inputs[size_t(k)]};
+        g.outputs = {mw->outputs[0]};
+        OnnxAttr ax, ep;
+        ax.name = "axis"; ax.i = axes[0];
+        ep.name = "epsilon"; ep.f = float(eps);
+        g.attrs["axis"] = ax;
+        g.attrs["epsilon"] = ep;
+        synth_nodes.push_back(std::move(g));
+        for (const OnnxNode* p : taken) rms_skip.insert(p);
+        rms_head[mw] = &synth_nodes.back();
     }
 }
 
@@ -3073,6 +3457,7 @@ void Planner::RefuseForF8() const {
         if (n.kind == L_CONV && n.group != 1) fail("grouped convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_CONV && (n.dil_h > 1 || n.dil_w > 1)) fail("dilated convolution is not supported in fp8 mode (Conv " + n.name + ")");
         if (n.kind == L_RESIZE) fail("Resize is not supported in fp8 mode (node " + n.name + ")");
+        if (n.kind == L_LAYERNORM && n.rms) fail("RMSNormalization is not supported in fp8 mode (node " + n.name + ")");
         if (n.kind == L_LAYERNORM || n.kind == L_EMBED) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
         if (n.kind == L_GROUPNORM) fail("GroupNormalization is not supported in fp8 mode (node " + n.name + ")");
     }
@@ -3136,6 +3521,26 @@ void Planner::FuseActivationPatterns() {
     }
     for (const LNode& e : L.nodes)
         if (!e.dead && e.kind == L_ERF) fail("Unsupported ONNX operator: Erf (node " + e.name + ")");
+}
+
+// ---- gated units (SwiGLU, GeGLU): Mul(act(a), b) of two activations of one shape, act a SiLU or a GELU read by the Mul alone, either operand order:
+//      ONE eltwise step, out = act(a) * b (EltArgs::pre_act).  Runs behind FuseActivationPatterns, so every SiLU / GELU spelling is an L_ACT here ----
+void Planner::FuseGatedActivations() {
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& mu = L.nodes[i];
+        if (mu.dead || mu.kind != L_MUL || mu.pre_act.kind != ActKind::None || mu.in[0] == mu.in[1] || L.vals[mu.in[0]].dims != L.vals[mu.in[1]].dims) continue;
+        for (int k = 0; k < 2; ++k) {
+            const int g = L.vals[mu.in[k]].producer;
+            if (g < 0 || L.nodes[g].dead || L.nodes[g].kind != L_ACT || !single_consumer(mu.in[k])) continue;
+            LNode& ac = L.nodes[g];
+            if (ac.act.kind != ActKind::Silu && ac.act.kind != ActKind::Gelu && ac.act.kind != ActKind::GeluTanh) continue;
+            mu.pre_act = ac.act;
+            mu.in = {ac.in[0], mu.in[1 - k]};
+            mu.name = ac.name + "+" + mu.name;
+            ac.dead = true;
+            break;
+        }
+    }
 }
 
 // ---- squeeze-excite: GlobalAveragePool -> Conv1x1 -> ReLU | act -> Conv1x1 -> act -> Mul(x, gate) as ONE node, where x is read by the pool
@@ -3581,8 +3986,9 @@ void Planner::AssignBuffers() {
     for (size_t pos = 0; pos < order.size(); ++pos) {
         // a group norm whose whole-buffer input dies here writes in place (its kernels read every element before they write it): the output takes over
         // the input's buffer, which therefore does not return to the pool at this position
+        // (an RMSNorm likewise: a lane group / wave reads all of its row before it writes any of it, and element for element in and out are one address)
         int handed = -1;
-        if (const LNode& gn = L.nodes[size_t(order[pos])]; gn.kind == L_GROUPNORM) {
+        if (const LNode& gn = L.nodes[size_t(order[pos])]; gn.kind == L_GROUPNORM || (gn.kind == L_LAYERNORM && gn.rms)) {
             const int ri = L.vals[gn.in[0]].root, ro = L.vals[gn.out].root;
             const Val& I = L.vals[gn.in[0]];
             if (ro == gn.out && first_def[ro] == int(pos) && last_use[ro] != kLiveForever && last_use[ri] == int(pos) && L.vals[ri].buf >= 0 && !L.vals[ri].dedicated &&
@@ -3994,8 +4400,9 @@ void Planner::EmitEltwise(const LNode& n, Step& s) {
             s.in2 = view_of(n.in[1]);
             s.has_in2 = true;
             s.mul = true;
+            s.pre_act = n.pre_act;             // (a gated unit: act(in) * in2)
             s.bytes = vbytes(s.in) + vbytes(s.in2) + vbytes(s.out);
-            s.flops = double(s.out.numel());
+            s.flops = double(s.out.numel()) * (1.0 + (n.pre_act.kind != ActKind::None ? ActFlops(n.pre_act.kind) : 0.0));
             break;
         case L_AFFINE:
             if (s.in.f8 || s.out.f8) fail("fp8 precision: stand-alone scale/shift " + n.name + " on an fp8 tensor is not supported");
@@ -4040,16 +4447,17 @@ void Planner::EmitResize(const LNode& n, Step& s) const {
 // layer norm: gamma at w_off, beta at bias_off (fp32 in every precision); the tile is the smallest lane group that holds the row in three 16-byte
 // vectors per lane (kernels.h LnDefaultTile), IE_FORCE_TILE picks among the eligible ones (an ineligible one: the generic kernel)
 void Planner::EmitLayerNorm(const LNode& n, Step& s) {
-    if (s.in.f8 || s.out.f8) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
+    if (s.in.f8 || s.out.f8) fail(std::string(n.rms ? "RMSNormalization" : "LayerNormalization") + " is not supported in fp8 mode (node " + n.name + ")");
     s.kind = StepKind::LayerNorm;
     s.w_off = push_vec(n.s);
     if (!n.t.empty()) s.bias_off = push_vec(n.t);
     s.ln_eps = n.eps;
+    s.rms = n.rms;
     const int def = LnDefaultTile(s.in.c, s.out.f16);
     s.tile = def > 0 && LnFastViews(s, def) ? def : 0;
     const int t = ForcedTile(kNumLnTiles);
     if (t >= 0) s.tile = t == 0 || LnFastViews(s, t) ? t : 0;
-    s.flops = 8.0 * double(s.in.numel());
+    s.flops = (n.rms ? 4.0 : 8.0) * double(s.in.numel());
     s.bytes = vbytes(s.in) + vbytes(s.out);
 }
 
@@ -4133,22 +4541,33 @@ void Planner::EmitAttention(const LNode& n, Step& s) {
         if (!s.in2.i64) fail("internal planner error: the key mask of node " + n.name + " is not an int64 view");
     }
     s.causal = n.causal;
-    const bool views = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16;
+    s.kv_heads = n.kv_heads > 0 ? n.kv_heads : n.heads;
+    const bool rope = !n.w.empty();
+    if (rope) {                                        // the cos / sin tables [L][hd], fp32 in every precision (push_vec aligns them to 32 bytes)
+        s.rope = true;
+        s.w_off = push_vec(n.w);
+        s.w2_off = push_vec(n.w2);
+    }
+    const bool gqa = s.kv_heads != s.heads;
+    // a rotary step runs on tiles 1 / 3 in their causal form only (head dims 32 / 64); non-causal rope and every other head dim: the generic kernel
+    const bool views = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 && !(rope && !n.causal);
     auto fits = [&](int tile) {
         if (tile == 0) return true;
+        if (tile == 2 && (rope || gqa)) return false;  // (tile 2 has neither a rotary nor a grouped form)
         if (tile == 3) return views && AttnChunkFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask);
         if (tile == 2 && n.causal) return false;       // (tile 2 has no causal form)
         return views && (tile == 1 ? AttnMfmaFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask)
                                    : AttnStreamFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask));
     };
     s.tile = views ? AttnDefaultTile(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask) : 0;
+    if (s.tile == 2 && !fits(2)) s.tile = 0;
     if (n.causal) s.tile = views ? AttnCausalDefaultTile(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off) : 0;
     int t = ForcedTile(kNumAttnForcedTiles);
     if (const char* e = env.get("IE_ATTN_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumAttnTiles) t = std::atoi(e);      // (the attention steps alone)
     if (t >= 0) s.tile = fits(t) ? t : 0;
     s.flops = 4.0 * double(s.in.n) * double(s.heads) * double(s.in.w) * double(s.in.w) * double(s.head_dim);
     if (n.causal) s.flops = 2.0 * double(s.in.n) * double(s.heads) * double(s.in.w) * double(s.in.w + 1) * double(s.head_dim);      // the lower triangle: the work needed
-    s.bytes = vbytes(s.in) + vbytes(s.out) + (n.key_mask ? vbytes(s.in2) : 0.0);
+    s.bytes = vbytes(s.in) + vbytes(s.out) + (n.key_mask ? vbytes(s.in2) : 0.0) + (rope ? 8.0 * double(s.in.w) * double(s.head_dim) : 0.0);
 }
 
 // window attention: the bias and the mask packed for the kernels (kernels.h WinAttnArgs: [.][Lp][Lp], the query index fastest, -inf in the bias
@@ -4553,6 +4972,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
     P.MatchAttention();                                          // the unfused attention subgraphs, found on the ONNX nodes: each imports as one node
     P.MatchEmbed();                                              // table Gathers by INT64 graph inputs, their sum and the LayerNormalization behind it: one node
     P.MatchGroupNorm();                                          // the spellings of a group norm: one node
+    P.MatchRmsNorm();                                            // an RMSNorm spelled out with Pow, ReduceMean and Sqrt: the RMSNormalization node
     P.MatchConv1D();                                             // HF's Conv1D on tokens (Reshape -> Gemm -> Reshape): a Linear, the Reshapes are names
     P.MatchGeluTanh();                                           // gelu_new spelled out with Pow and Tanh: the Gelu(approximate = "tanh") node
     for (const OnnxNode& on : m.nodes) P.ImportNode(on);
@@ -4563,6 +4983,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
     P.FuseTokenAssemble();                                       // class-token Concat -> Add pos_embedding as one node
     P.FuseActivationPatterns();                                  // Mul(x, Sigmoid(x)) -> SiLU, Mul(x, HardSigmoid(x)) -> hardswish
     P.FuseGroupNormActivations();                                // GroupNorm -> SiLU / ReLU / Sigmoid as one node
+    P.FuseGatedActivations();                                    // Mul(SiLU | GELU(a), b) -> one gated eltwise node (SwiGLU)
     if (!env.get("IE_NO_SE_FUSE")) P.FuseSqueezeExcite();        // pool -> 1x1 -> act -> 1x1 -> act -> Mul as one node
     P.MergeAffineChains();                                       // fusion 1: Affine -> Affine
     P.FuseConvEpilogues();                                       // fusion 2: Conv -> Affine / ReLU / Add / Clip / activation
@@ -4673,10 +5094,13 @@ std::string PlanToJson(const Plan& p) {
             o << ",\"resize\":{\"mode\":\"" << rs_modes[int(s.rs_mode)] << "\",\"coord\":\"" << rs_coords[int(s.rs_coord)] << "\",\"nearest\":\""
               << rs_nearest[int(s.rs_nearest)] << "\",\"scales\":[" << s.rs_scale_h << "," << s.rs_scale_w << "]}";
         if (s.kind == StepKind::LayerNorm) o << ",\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile;      // (layer-norm steps only)
+        if (s.kind == StepKind::LayerNorm && s.rms) o << ",\"rms\":true";      // (RMSNorm steps only)
         if (s.kind == StepKind::Attention)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"tile\":" << s.tile;      // (attention steps only)
         if (s.kind == StepKind::Attention && s.key_mask) o << ",\"key_mask\":true,\"mask_value\":" << s.mask_value;      // (masked attention steps only)
         if (s.kind == StepKind::Attention && s.causal) o << ",\"causal\":true";      // (causal attention steps only)
+        if (s.kind == StepKind::Attention && s.kv_heads > 0 && s.kv_heads != s.heads) o << ",\"kv_heads\":" << s.kv_heads;      // (grouped-query steps only)
+        if (s.kind == StepKind::Attention && s.rope) o << ",\"rope\":true,\"w2_off\":" << s.w2_off;      // (rotary steps only)
         if (s.kind == StepKind::WindowAttention)      // (window-attention steps only)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"window\":[" << s.win_h << "," << s.win_w << "],\"shift\":["
               << s.shift_h << "," << s.shift_w << "],\"masked\":" << (s.masked ? "true" : "false") << ",\"tile\":" << s.tile;

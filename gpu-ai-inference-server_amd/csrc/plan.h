@@ -128,6 +128,8 @@ struct Step {
     // LayerNorm (kernels_ln.hip): out = (in - mean_c) * rsqrt(var_c + ln_eps) * gamma + beta per pixel row; w_off = gamma [C], bias_off = beta [C] or
     // -1, fp32 in every precision; tile = the kernel variant (kernels.h kNumLnTiles)
     float ln_eps = 1e-5f;
+    // rms: an RMSNorm, out = in * rsqrt(mean_c(in^2) + ln_eps) * gamma (Llama-class graphs); bias_off = -1; the layer norm's tiles
+    bool rms = false;
     // TokenAssemble (kernels_tokens.hip): in = tokens [N, 1, L0, D], out = [N, 1, L0 + 1, D]; out[n, 0, :] = cls + pos[0], out[n, 1 + p, :] = in[n, p, :] +
     // pos[1 + p]; w_off = cls [D], bias_off = pos [L0 + 1][D] or -1, fp32 in every precision
     // Attention (kernels_attn.hip): in = the qkv tokens [N, 1, L, 3 D] (column s * D + h * head_dim + e = element e of head h of q / k / v for s = 0 / 1 / 2),
@@ -139,6 +141,11 @@ struct Step {
     float mask_value = 0.f;
     // Causal attention (GPT-2): query i attends to the keys j <= i; the graph's mask constant was checked element by element at load and is not kept
     bool causal = false;
+    // Grouped-query attention (Llama): kv_heads K / V heads (0 or heads: one per query head); in = q (D) | k (Dkv) | v (Dkv) with Dkv = kv_heads * head_dim,
+    // query head h reads K / V head h / (heads / kv_heads).  rope: q and k are rotated at their token position inside the kernels' own loads; w_off /
+    // w2_off = the cos / sin tables [L][head_dim], fp32 in every precision
+    int kv_heads = 0;
+    bool rope = false;
     // WindowAttention (kernels_wattn.hip): in = the qkv map [N, H, W, 3 D], out = [N, H, W, D]; attention inside the win_h x win_w windows of the map
     // rolled by (-shift_h, -shift_w), every result on its query's own pixel; w_off = the relative-position bias, w2_off = the shift mask (masked
     // steps only), both packed as kernels.h WinAttnArgs describes, fp32 in every precision; heads, head_dim, attn_scale, tile as for Attention

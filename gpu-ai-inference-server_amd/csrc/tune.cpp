@@ -172,7 +172,7 @@ void DeviceModel::TuneStep(TuneContext& ctx, const PlanInstance& pi, Step& s) {
     if (s.kind == StepKind::LayerNorm) {
         // the generic kernel and the lane-group variants that hold the row (tune-file codes kLnTuneCode + tile)
         // (the channel offsets decide which tiles are eligible: they are part of the signature)
-        TuneTiles(ctx, pi, s, {s.in.n * s.in.h * s.in.w, s.in.c, s.in.pitch, s.out.pitch, s.in.c_off, s.out.c_off, int64_t(s.in.f16), int64_t(s.out.f16), kLnTuneCode, s.bias_off >= 0},
+        TuneTiles(ctx, pi, s, {s.in.n * s.in.h * s.in.w, s.in.c, s.in.pitch, s.out.pitch, s.in.c_off, s.out.c_off, int64_t(s.in.f16), int64_t(s.out.f16), kLnTuneCode, s.rms ? 2 : s.bias_off >= 0},
                   kLnTuneCode, kNumLnTiles);
         return;
     }

@@ -170,6 +170,47 @@ class GraphBuilder:
         self.nodes.append(pb.node("LayerNormalization", ins, [y], name, [pb.attr_int("axis", axis), pb.attr_float("epsilon", eps)]))
         return y
 
+    def rmsnorm(self, x: str, c: int, eps: float = 1e-5, form: str = "pow", name: str | None = None, *, cast: bool = False, swap: bool = False,
+                axes_input: bool = True, axis: int = -1, g: np.ndarray | None = None, out: str | None = None) -> str:
+        """RMSNorm over the last axis, weight * (x * rsqrt(mean(x^2) + eps)), in the forms exporters write (HF's LlamaRMSNorm):
+          "pow"         Pow(x, 2) -> ReduceMean(axes [-1], keepdims 1) -> Add eps -> Sqrt -> Div(1, .) -> Mul(x, .) -> Mul(weight, .)   (torch's rsqrt below opset 23)
+          "mul"         the same with Mul(x, x) in place of the Pow
+          "reciprocal"  the same with Reciprocal in place of Div(1, .);  "mul_reciprocal": both
+          "op"          the opset-23 RMSNormalization operator (build the model with finish(..., opset=23))
+        cast: the Cast(to = FLOAT) nodes of hidden_states.to(torch.float32) and of the cast back, on x and on the normalised value.  swap: every Mul /
+        Add with its operands the other way round.  axes_input: the ReduceMean's axes as an input (opset >= 18), else as an attribute.  The weight [c]
+        is drawn around 1 from the stream name_g (g: given instead)."""
+        name = name or self._uid("rms")
+        if g is None:
+            g = np.float32(1.0) + (rng.uniform(self.seed, name + "_g", c) - np.float32(0.5)) * np.float32(0.2)
+        w = self.init(name + "_weight", np.asarray(g, np.float32))
+        y = out or name + "_out"
+        if form == "op":
+            self.nodes.append(pb.node("RMSNormalization", [x, w], [y], name, [pb.attr_int("axis", axis), pb.attr_float("epsilon", eps)]))
+            return y
+        if form not in ("pow", "mul", "reciprocal", "mul_reciprocal"):
+            raise ValueError(form)
+        two = lambda a, b: [b, a] if swap else [a, b]  # noqa: E731
+        xf = self.simple("Cast", [x], [pb.attr_int("to", pb.FLOAT)]) if cast else x
+        sq = self.simple("Mul", [xf, xf]) if form.startswith("mul") else self.simple("Pow", [xf, self.init(name + "_two", np.array(2.0, np.float32))])
+        if axes_input:
+            v = self.simple("ReduceMean", [sq, self.init(name + "_axes", np.array([axis], np.int64))], [pb.attr_int("keepdims", 1)])
+        else:
+            v = self.simple("ReduceMean", [sq], [pb.attr_ints("axes", [axis]), pb.attr_int("keepdims", 1)])
+        r = self.simple("Sqrt", [self.simple("Add", two(v, self.init(name + "_eps", np.array(eps, np.float32))))])
+        r = self.simple("Reciprocal", [r]) if form.endswith("reciprocal") else self.simple("Div", [self.init(name + "_one", np.array(1.0, np.float32)), r])
+        h = self.simple("Mul", two(xf, r))
+        if cast:
+            h = self.simple("Cast", [h], [pb.attr_int("to", pb.FLOAT)])
+        self.nodes.append(pb.node("Mul", two(w, h), [y], name + "_scale"))
+        return y
+
+    def swiglu(self, gate: str, up: str, act: str = "silu", swap: bool = False) -> str:
+        """A gated unit, Mul(act(gate), up): act "silu" (Mul(x, Sigmoid(x)), SwiGLU as Llama's MLP writes it) or a GraphBuilder.gelu form (GeGLU).  swap:
+        the operands of every Mul the other way round"""
+        a = self.silu(gate, swap=swap) if act == "silu" else self.gelu(gate, act, swap=swap)
+        return self.simple("Mul", [up, a] if swap else [a, up])
+
     def group_norm(self, x: str, c: int, groups: int, eps: float = 1e-5, form: str = "instancenorm", back: str = "const", rank3: bool = False,
                    *, hw: Sequence[int] | None = None, name: str | None = None, swap: bool = False, affine: bool = True, per_group: bool = False,
                    inner: str = "ones", out: str | None = None) -> str:
@@ -251,13 +292,16 @@ class GraphBuilder:
         h = self.init(name + "_half", np.array(half, np.float32))
         return self.simple("Mul", [h, y] if swap else [y, h])
 
-    def linear(self, x: str, cin: int, cout: int, name: str | None = None, w_scale: float | None = None) -> str:
-        """torch's Linear on a [..., cin] tensor as the exporter writes it: MatMul with a [cin, cout] initializer, then Add [cout]."""
+    def linear(self, x: str, cin: int, cout: int, name: str | None = None, w_scale: float | None = None, bias: bool = True) -> str:
+        """torch's Linear on a [..., cin] tensor as the exporter writes it: MatMul with a [cin, cout] initializer, then Add [cout] (bias False: the
+        MatMul alone, as Llama's projections are)."""
         name = name or self._uid("fc")
         std = w_scale if w_scale is not None else float(np.sqrt(1.0 / cin))
         w = rng.gaussish(self.seed, name + "_w", cin * cout).reshape(cin, cout) * np.float32(std)
-        b = (rng.uniform(self.seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
         y = self.simple("MatMul", [x, self.init(name + "_w", w.astype(np.float32))])
+        if not bias:
+            return y
+        b = (rng.uniform(self.seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
         return self.simple("Add", [y, self.init(name + "_b", b.astype(np.float32))])
 
     def act(self, x: str, kind: str, form: str = "op") -> str:
@@ -1287,6 +1331,149 @@ def gpt2_tiny(batch: int | str = 1, **kw) -> bytes:
 
 
 INT64_MAX = 9223372036854775807
+
+
+def rope_tables(seq: int, hd: int, theta: float = 10000.0) -> tuple[np.ndarray, np.ndarray]:
+    """LlamaRotaryEmbedding's cos / sin [seq, hd] in fp32: angle[i, e] = i * theta^(-2 (e mod hd/2) / hd), emb = cat(freqs, freqs)"""
+    inv = 1.0 / (theta ** (np.arange(0, hd, 2, dtype=np.float64) / hd))
+    ang = np.arange(seq, dtype=np.float64)[:, None] * inv[None, :]
+    emb = np.concatenate([ang, ang], axis=1)
+    return np.cos(emb).astype(np.float32), np.sin(emb).astype(np.float32)
+
+
+def rope_constants(gb: GraphBuilder, seq: int, hd: int, tag: str, *, form: str = "init", max_pos: int | None = None, theta: float = 10000.0,
+                   tables: tuple[np.ndarray, np.ndarray] | None = None) -> tuple[str, str]:
+    """The names of cos and sin as an attention reads them, broadcasting as [1, 1, seq, hd]: "init" initializers of that shape; "unsqueeze" [seq, hd]
+    initializers behind Unsqueeze(axes [0, 1]); "slice" [max_pos, hd] tables cut to their first seq rows by a Slice and then unsqueezed; "gather"
+    the tables gathered by the constant positions 0 ... seq - 1 and then unsqueezed.  tables: (cos, sin) [rows, hd] given instead of rope_tables"""
+    rows = seq if form in ("init", "unsqueeze") else (max_pos or seq)
+    cs = tables if tables is not None else rope_tables(rows, hd, theta)
+    out = []
+    i64 = lambda name, v: gb.init(f"{tag}_{name}", np.array(v, np.int64))  # noqa: E731
+    for which, t in zip(("cos", "sin"), cs):
+        t = np.ascontiguousarray(t, np.float32)
+        if form == "init":
+            out.append(gb.init(f"{tag}_{which}", t[:seq].reshape(1, 1, seq, hd)))
+            continue
+        name = gb.init(f"{tag}_{which}_table", t)
+        if form == "slice":
+            name = gb.simple("Slice", [name, i64(which + "_starts", [0]), i64(which + "_ends", [seq]), i64(which + "_axes", [0]), i64(which + "_steps", [1])])
+        elif form == "gather":
+            name = gb.simple("Gather", [name, i64(which + "_positions", np.arange(seq))], [pb.attr_int("axis", 0)])
+        elif form != "unsqueeze":
+            raise ValueError(form)
+        out.append(gb.simple("Unsqueeze", [name, i64(which + "_axes01", [0, 1])]))
+    return out[0], out[1]
+
+
+def rotate_half_rope(gb: GraphBuilder, t: str, cos: str, sin: str, hd: int, tag: str, *, swap: bool = False, order: str = "neg_first") -> str:
+    """apply_rotary_pos_emb on t [N, H, L, hd]: Add(Mul(t, cos), Mul(Concat(Neg(Slice(t, hd/2:)), Slice(t, :hd/2), axis -1), sin)); swap: every Mul /
+    Add with its operands the other way round.  order "x1_first": the Concat as (x1, -x2), which is NOT rotate_half (tests: a refusal)"""
+    i64 = lambda name, v: gb.init(f"{tag}_{name}", np.array(v, np.int64))  # noqa: E731
+    two = lambda a, b: [b, a] if swap else [a, b]  # noqa: E731
+    x1 = gb.simple("Slice", [t, i64("lo_starts", [0]), i64("lo_ends", [hd // 2]), i64("lo_axes", [-1]), i64("lo_steps", [1])])
+    x2 = gb.simple("Slice", [t, i64("hi_starts", [hd // 2]), i64("hi_ends", [INT64_MAX]), i64("hi_axes", [-1]), i64("hi_steps", [1])])
+    if order == "neg_first":
+        rot = gb.simple("Concat", [gb.simple("Neg", [x2]), x1], [pb.attr_int("axis", -1)])
+    elif order == "x1_first":
+        rot = gb.simple("Concat", [x1, gb.simple("Neg", [x2])], [pb.attr_int("axis", -1)])
+    else:
+        raise ValueError(order)
+    return gb.simple("Add", two(gb.simple("Mul", two(t, cos)), gb.simple("Mul", two(rot, sin))))
+
+
+def llama_attention(gb: GraphBuilder, x: str, seq: int, dim: int, heads: int, kv_heads: int, tag: str, *, batch: int = 1, rope: tuple[str, str] | None = None,
+                    rope_k: tuple[str, str] | None = None, repeat: str = "auto", mask: str | None = "add", scale: str = "mul", bias: bool = False,
+                    swap: bool = False, linear=None, rope_order: str = "neg_first", hd: int | None = None) -> str:
+    """LlamaAttention (eager): q / k / v Linears without a bias (dim -> H hd, Hkv hd, Hkv hd) -> Reshape [N, L, H | Hkv, hd] -> Transpose [0,2,1,3] ->
+    rotary embedding on q and k (rope = the (cos, sin) names of rope_constants; rope_k: other names for k; None: no rotation) -> repeat_kv on k and v
+    (Unsqueeze(axis 2) -> Expand [N, Hkv, g, L, hd] -> Reshape [N, H, L, hd]; repeat "auto": where g > 1, "always": also the g = 1 no-op, "never")
+    -> MatMul(q, Transpose(k, [0,1,3,2])) -> Mul(1 / sqrt hd) | Div(sqrt hd) -> the causal mask ("add" the additive triangular constant, "where_const",
+    None) -> Softmax -> MatMul(., v) -> Transpose [0,2,1,3] -> Reshape [N, L, H hd].  x: the tokens, or with `linear` = a function (x, name, cout)
+    the q / k / v rows come from it (tests hand the kernel known operands that way)"""
+    hd = hd or dim // heads
+    g = heads // max(kv_heads, 1)
+    lin = linear or (lambda y, name, cout: gb.linear(y, dim, cout, name=name, bias=bias))
+    i64 = lambda name, v: gb.init(f"{tag}_{name}", np.array(v, np.int64))  # noqa: E731
+    q = gb.simple("Reshape", [lin(x, tag + "_q_proj", heads * hd), i64("shape_q", [0, -1, heads, hd])])
+    k = gb.simple("Reshape", [lin(x, tag + "_k_proj", kv_heads * hd), i64("shape_k", [0, -1, kv_heads, hd])])
+    v = gb.simple("Reshape", [lin(x, tag + "_v_proj", kv_heads * hd), i64("shape_v", [0, -1, kv_heads, hd])])
+    q, k, v = (gb.transpose(t, (0, 2, 1, 3)) for t in (q, k, v))
+    if rope is not None:
+        q = rotate_half_rope(gb, q, rope[0], rope[1], hd, tag + "_rope_q", swap=swap, order=rope_order)
+        kc = rope_k or rope
+        k = rotate_half_rope(gb, k, kc[0], kc[1], hd, tag + "_rope_k", swap=swap)
+    if repeat == "always" or (repeat == "auto" and g > 1):
+        def repeat_kv(t: str, which: str) -> str:
+            u = gb.simple("Unsqueeze", [t, i64(which + "_rep_axis", [2])])
+            e = gb.simple("Expand", [u, i64(which + "_rep_shape5", [batch, kv_heads, g, seq, hd])])
+            return gb.simple("Reshape", [e, i64(which + "_rep_shape4", [batch, heads, seq, hd])])
+        k, v = repeat_kv(k, "k"), repeat_kv(v, "v")
+    elif repeat not in ("auto", "never"):
+        raise ValueError(repeat)
+    s = gb.simple("MatMul", [q, gb.transpose(k, (0, 1, 3, 2))])
+    if scale == "mul":
+        s = gb.simple("Mul", [s, gb.init(tag + "_rsqrt_hd", np.array(1.0 / np.sqrt(float(hd)), np.float32))])
+    elif scale == "div":
+        s = gb.simple("Div", [s, gb.init(tag + "_sqrt_hd", np.array(np.sqrt(float(hd)), np.float32))])
+    else:
+        raise ValueError(scale)
+    if mask == "where_const":
+        s = gb.simple("Where", [causal_mask_constant(gb, seq, mask, seq, tag), s, gb.init(tag + "_mask_value", np.array(FLOAT32_MIN, np.float32))])
+    elif mask is not None:
+        s = gb.simple("Add", [s, causal_mask_constant(gb, seq, mask, seq, tag)])
+    p = gb.simple("Softmax", [s], [pb.attr_int("axis", -1)])
+    y = gb.transpose(gb.simple("MatMul", [p, v]), (0, 2, 1, 3))
+    return gb.simple("Reshape", [y, i64("shape3", [0, -1, heads * hd])])
+
+
+def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576, depth: int = 30, heads: int = 9, kv_heads: int = 3, mlp: int = 1536,
+          max_pos: int = 2048, rope_theta: float = 10000.0, eps: float = 1e-5, tied: bool = True, last_hidden_state: bool = False, seed: int = 2023,
+          norm: str = "pow", cast: bool = False, swap: bool = False, rope: str = "slice", repeat: str = "auto", scale: str = "mul", mask: str = "add",
+          w_scale: float | None = None, table_std: float = 1.0) -> bytes:
+    """LlamaForCausalLM as a prefill / scoring forward (Touvron et al. 2023; the shape of Llama 2 / 3, TinyLlama, SmolLM, Mistral and the dense Qwen
+    models), ids [N, seq] -> logits [N, seq, vocab], written from modeling_llama.py's eager attention and the TorchScript exporter's known lowerings,
+    NOT from a real export (neither `transformers` nor ONNX Runtime is available here); checked by the float64 walk of tests/ref64.py.
+    Per layer: x += o_proj(attention(RMSNorm(x))) with rotary q / k and kv_heads grouped K / V heads (llama_attention), x += down(SiLU(gate(h)) * up(h))
+    with h = RMSNorm(x); then the final RMSNorm and the vocabulary head (tied: Transpose(embed_tokens, [1,0])).  No Linear has a bias; attention_mask is
+    not an input (the causal mask is the additive triangular constant).  The switches are the spellings the planner accepts:
+      norm / cast / swap   GraphBuilder.rmsnorm's form, its Cast nodes, its operand order (swap also turns the rope's and the gated unit's Muls)
+      rope     rope_constants' form: "init" | "unsqueeze" | "slice" | "gather" ("none": the same graph without the rope nodes, which is no Llama);  repeat: llama_attention's repeat_kv ("auto" | "always" | "never")
+      scale    "mul" | "div";  mask: "add" | "where_const"
+    outputs: logits, and last_hidden_state [N, seq, dim] behind the final norm (optional)"""
+    gb = GraphBuilder("llama", seed)
+    hd = dim // heads
+    emb = np.float32(table_std) * rng.gaussish(seed, "embed_tokens", vocab * dim).reshape(vocab, dim).astype(np.float32)
+    x = gb.simple("Gather", [gb.init("embed_tokens", emb), "input_ids"], [pb.attr_int("axis", 0)])
+    cs = rope_constants(gb, seq, hd, "rotary", form=rope, max_pos=max_pos, theta=rope_theta) if rope != "none" else None      # ("none": measurements only)
+    opset = 23 if norm == "op" else 18
+
+    def lin(y: str, name: str, cin: int, cout: int) -> str:
+        return gb.linear(y, cin, cout, name=name, bias=False, w_scale=w_scale)
+
+    for li in range(depth):
+        tag = f"layers{li}"
+        h = gb.rmsnorm(x, dim, eps=eps, form=norm, name=tag + "_input_layernorm", cast=cast, swap=swap)
+        y = llama_attention(gb, h, seq, dim, heads, kv_heads, tag + "_attn", batch=batch, rope=cs, repeat=repeat, scale=scale, mask=mask, swap=swap,
+                            linear=lambda t, name, cout: lin(t, name, dim, cout))
+        x = gb.simple("Add", [x, lin(y, tag + "_o_proj", dim, dim)])
+        h = gb.rmsnorm(x, dim, eps=eps, form=norm, name=tag + "_post_attention_layernorm", cast=cast, swap=swap)
+        y = gb.swiglu(lin(h, tag + "_gate_proj", dim, mlp), lin(h, tag + "_up_proj", dim, mlp), swap=swap)
+        x = gb.simple("Add", [x, lin(y, tag + "_down_proj", mlp, dim)])
+    gb.rmsnorm(x, dim, eps=eps, form=norm, name="norm", cast=cast, swap=swap, out="last_hidden_state")
+    head = gb.transpose("embed_tokens", (1, 0)) if tied else gb.init("lm_head_w", (rng.gaussish(seed, "lm_head", dim * vocab).reshape(dim, vocab) * np.float32(np.sqrt(1.0 / dim))).astype(np.float32))
+    gb.simple("MatMul", ["last_hidden_state", head], out="logits")
+    outs = [("logits", [batch, seq, vocab])] + ([("last_hidden_state", [batch, seq, dim])] if last_hidden_state else [])
+    return gb.finish([("input_ids", [batch, seq], ONNX_INT64)], outs, opset=opset)
+
+
+def llama_135m(batch: int = 1, **kw) -> bytes:
+    """SmolLM-135M's shape: 30 layers, dim 576, 9 heads of 64 over 3 K / V heads, mlp 1536, vocab 49152, tied head"""
+    return llama(batch, **dict(dict(seq=128, vocab=49152, dim=576, depth=30, heads=9, kv_heads=3, mlp=1536, max_pos=2048), **kw))
+
+
+def llama_tiny(batch: int = 1, **kw) -> bytes:
+    return llama(batch, **dict(dict(seq=40, vocab=61, dim=128, depth=2, heads=4, kv_heads=2, mlp=256, max_pos=64), **kw))
 
 
 def swin_relative_position_bias(seed: int, tag: str, window: Sequence[int], heads: int) -> np.ndarray:
