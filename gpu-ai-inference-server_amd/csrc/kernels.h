@@ -348,13 +348,13 @@ struct AttnArgs {
     int causal = 0;                    // query i attends to the keys j <= i only (a decoder's mask); never together with a key mask
     // Grouped-query attention (Llama-class graphs): kv_heads K / V heads (0 or heads: one per query head, as above).  With Dkv = kv_heads * head_dim a
     // token row is q (D) | k (Dkv) | v (Dkv), in.c == D + 2 Dkv, and query head h reads K / V head h / (heads / kv_heads) (HF's repeat_kv: a
-    // repeat_interleave).  heads % kv_heads == 0.  Tiles 0, 1 and 3
+    // repeat_interleave).  heads % kv_heads == 0.  Every tile
     int kv_heads = 0;
     // Rotary position embedding (null: none): fp32 tables [L][head_dim], 16-byte aligned.  q and k of token position i enter the scores as
     //   x'[e] = x[e] * cos[i][e] + s(e) * x[p(e)] * sin[i][e],  p(e) = e + hd/2, s = -1 for e < hd/2;  p(e) = e - hd/2, s = +1 otherwise
     // (x * cos + rotate_half(x) * sin with full-width tables: the two halves of a table row need not be equal).  fp32 arithmetic; a half operand is
-    // rounded once, where it enters LDS (k) or the MFMA fragment (q).  Tiles 1 and 3 rotate in their causal form only (attention_mfma_kernel<.,.,causal,rope>);
-    // tile 0 rotates in every form; never together with a key mask; head_dim even
+    // rounded once, where it enters LDS (k) or the MFMA fragment (q; tile 2: k too).  Tiles 1, 2 and 3 rotate in their causal form only
+    // (attention_mfma_kernel<.,.,causal,rope>), tile 2 at head_dim 128 and 256; tile 0 rotates in every form; never together with a key mask; head_dim even
     const float* rope_cos = nullptr;
     const float* rope_sin = nullptr;
 };
@@ -362,7 +362,8 @@ struct AttnArgs {
 // (a workgroup = one image, one head, 128 queries; the head's K and V rows in LDS): head_dim 32 or 64, the channel counts, pitches and offsets
 // multiples of the 16-byte vector, and both of the head's padded K and V images inside the LDS budget.  tile 2: attention_stream_kernel<T, HD>
 // (a workgroup = one image, one head, 32 queries; its four waves split the head dim; K and V streamed in tiles of 32 keys, LDS independent of L):
-// head_dim 128, 256 or 512, no key mask, not causal, the same vector conditions.  tile 3: attention_chunk_kernel<T, HD, CAUSAL> (tile 1's workgroup,
+// head_dim 128, 256 or 512, no key mask, the same vector conditions; <T, HD, CAUSAL> walks the key tiles up to the diagonal one, <T, HD, CAUSAL, ROPE>
+// (head_dim 128 or 256) also rotates q and k.  tile 3: attention_chunk_kernel<T, HD, CAUSAL> (tile 1's workgroup,
 // K and V staged in chunks of kAttnChunkKeys keys, LDS independent of L): head_dim 32 or 64, no key mask, the same vector conditions
 constexpr int kNumAttnTiles = 4;
 // IE_FORCE_TILE reaches tiles 0 and 1 of an attention step only (2 and 3 keep meaning "not forced"); tiles 2 and 3 are pinned with IE_ATTN_TILE
@@ -405,11 +406,15 @@ constexpr bool AttnChunkFits(int64_t L, int hd, bool f16, int64_t c_in, int64_t 
     return (hd == 32 || hd == 64) && L >= 1 && !masked && c_in % V == 0 && pitch_in % V == 0 && off_in % V == 0 && c_out % V == 0 && pitch_out % V == 0 &&
            off_out % V == 0 && AttnChunkLdsBytes(hd, f16) <= kAttnLdsBudget;
 }
-// a causal step: tile 1 where it fits, else tile 3 where it fits, else the generic kernel (tile 2 has no causal form).  A non-causal step reaches tile 3
-// through IE_ATTN_TILE=3 only
+// a causal step: tile 1 where it fits, else tile 3 where it fits, else tile 2 where it fits (a wide head) and the sequence has at least
+// kAttnStreamCausalMinTokens tokens, else the generic kernel.  The constant is the smallest measured length from which tile 2 wins in both
+// precisions: the shortest one measured, one key tile.  A rotary head of 512 fits no form of tile 2: the planner takes that back
+// (plan.cpp EmitAttention).  A non-causal step reaches tile 3 through IE_ATTN_TILE=3 only
+constexpr int64_t kAttnStreamCausalMinTokens = 32;
 constexpr int AttnCausalDefaultTile(int64_t L, int hd, bool f16, int64_t c_in, int64_t pitch_in, int64_t off_in, int64_t c_out, int64_t pitch_out, int64_t off_out) {
     if (AttnMfmaFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, false)) return 1;
-    return AttnChunkFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, false) ? 3 : 0;
+    if (AttnChunkFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, false)) return 3;
+    return AttnStreamFits(L, hd, f16, c_in, pitch_in, off_in, c_out, pitch_out, off_out, false) && L >= kAttnStreamCausalMinTokens ? 2 : 0;
 }
 bool AttentionEligible(const AttnArgs& a, int tile);
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);

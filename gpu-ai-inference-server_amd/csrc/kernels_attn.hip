@@ -17,6 +17,7 @@
 //                                   an online softmax (running maximum m and sum l per query; O rescaled by exp(m - m') whenever m grows).
 //   attention_stream_kernel<T, HD>  tile 2: one wide head (HD 128 / 256 / 512, no mask).  A workgroup = (image, head, 32 queries); its 4 waves split the
 //                                   head dim; K and V are streamed in tiles of 32 keys, LDS does not depend on L (described at the kernel).
+//                                   <T, HD, CAUSAL> and <T, HD, CAUSAL, ROPE> (HD 128 / 256) are its causal and rotary forms.
 //
 // Operand orientation of tile 1.  The scores are computed swapped, S^T = K . Q^T: the MFMA's A operand is the K tile (row = key), its B operand
 // Q^T (column = query), so in the 32x32 result (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) a lane owns ONE query column and
@@ -33,20 +34,23 @@
 //   attention_chunk_kernel<T, HD>   tile 3: tile 1's workgroup, orientation, online softmax and epilogue, for any L: K and V pass through LDS in chunks of
 //                                   kAttnChunkKeys keys (stage, barrier, the chunk's key tiles, barrier), so LDS is a constant (described at the kernel).
 //
-// CAUSAL (tiles 0, 1 and 3; never with MASK): query i attends to the keys j <= i.  The keys above the diagonal are left out, not computed and discarded:
+// CAUSAL (every tile; never with MASK): query i attends to the keys j <= i.  The keys above the diagonal are left out, not computed and discarded:
 // tile 0 ends its key loops at i + 1; a workgroup of tile 1 / 3 stages only the key rows below 128 (qb + 1), a wave's key-tile loop ends with the tile
-// that holds its last query (key0 <= q0 + 31), and only the tile with key0 == q0 tests its elements (key > query -> -inf, before the maximum).
+// that holds its last query (key0 <= q0 + 31), and only the tile with key0 == q0 tests its elements (key > query -> -inf, before the maximum).  A
+// workgroup of tile 2 (32 queries) walks the key tiles 0 ... qb and tests the last one.
 //
-// Grouped K / V heads (tiles 0, 1 and 3; Llama-class graphs): a token row is q (D) | k (Dkv) | v (Dkv) with Dkv = kv_heads * hd, and query head h reads
-// K / V head h / (heads / kv_heads).  Only the K / V base offsets change: every (image, head, query block) workgroup still stages its K / V head itself.
+// Grouped K / V heads (every tile; Llama-class graphs): a token row is q (D) | k (Dkv) | v (Dkv) with Dkv = kv_heads * hd, and query head h reads
+// K / V head h / (heads / kv_heads).  Only the K / V base offsets change: every (image, head, query block) workgroup still stages (tile 2: streams) its
+// K / V head itself.
 //
-// ROPE (tile 0 at run time; tiles 1 and 3 as a template parameter of their CAUSAL form): the rotary position embedding of q and k inside the loads the
+// ROPE (tile 0 at run time; tiles 1, 2 and 3 as a template parameter of their CAUSAL form): the rotary position embedding of q and k inside the loads the
 // kernels already do.  x'[e] = x[e] cos[i][e] + s(e) x[p(e)] sin[i][e] at token position i, p(e) = e +/- hd/2, s = -1 in the first half of the head and
 // +1 in the second, with full-width fp32 tables [L][hd] (the two halves of a table row need not be equal).  The staging thread of K vector (row, cv)
 // also loads the partner vector (cv + VPR/2) % VPR of the row and the cos / sin vectors of the row's GLOBAL key position (tile 3: chunk base + row)
 // and writes the rotated vector to LDS; AttnWave::init_rope loads a lane's own half and the partner half of its Q row (the lane halves of the QK^T
 // reduction are exactly the two rope halves) and rotates at its query's position.  fp32 arithmetic; a half operand is rounded once, where it enters
-// LDS (k) or the MFMA fragment (q).  V is staged as it is.  No extra pass over the qkv buffer, no extra LDS.
+// LDS (k) or the MFMA fragment (q).  V is staged as it is.  No extra pass over the qkv buffer, no extra LDS.  Tile 2 has no K in LDS: it rotates the K
+// fragments in registers (described at the kernel), a half operand rounded once, where it becomes the MFMA fragment.
 //
 // MASK (tiles 0 and 1): the key mask of a BERT-class graph.  Key j of image n gets the bias (1 - float(mask[n, j])) * c on its scaled score, computed in
 // fp32 as the graph computes it.  Tile 1 stages the image's L biases in LDS behind K / V, already in units of log2 and clamped at -FLT_MAX
@@ -145,12 +149,13 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
 
 // One 16-byte vector of a q / k row after the rotary embedding: x = the vector (elements e0 ...), xp = its partner vector (elements e0 +/- HD/2 ...),
 // c / s = the cos / sin entries e0 ... of the token position's table row, sg = -1 for a vector of the first half of the head, +1 for one of the second.
-// fp32 arithmetic; halfs are rounded once, here.
+// fp32 arithmetic; halfs are rounded once, here.  rope_rot: the table entries are in registers already, c / s = the V / 4 float4s of the vector's
+// cos / sin entries (tile 2 loads them a tile ahead); rope_vec loads them from the table row
 template <typename T>
-__device__ __forceinline__ uint4 rope_vec(uint4 x, uint4 xp, const float* c, const float* s, float sg) {
-    const float4 c0 = *reinterpret_cast<const float4*>(c), s0 = *reinterpret_cast<const float4*>(s);
+__device__ __forceinline__ uint4 rope_rot(uint4 x, uint4 xp, const float4* c, const float4* s, float sg) {
+    const float4 c0 = c[0], s0 = s[0];
     if constexpr (sizeof(T) == 2) {
-        const float4 c1 = *reinterpret_cast<const float4*>(c + 4), s1 = *reinterpret_cast<const float4*>(s + 4);
+        const float4 c1 = c[1], s1 = s[1];
         const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, ss[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
         const h8 a = __builtin_bit_cast(h8, x), b = __builtin_bit_cast(h8, xp);
         h8 o;
@@ -162,6 +167,18 @@ __device__ __forceinline__ uint4 rope_vec(uint4 x, uint4 xp, const float* c, con
         return __builtin_bit_cast(uint4, make_float4(fmaf(a.x, c0.x, sg * b.x * s0.x), fmaf(a.y, c0.y, sg * b.y * s0.y), fmaf(a.z, c0.z, sg * b.z * s0.z),
                                                      fmaf(a.w, c0.w, sg * b.w * s0.w)));
     }
+}
+
+template <typename T>
+__device__ __forceinline__ uint4 rope_vec(uint4 x, uint4 xp, const float* c, const float* s, float sg) {
+    float4 cv[2], sv[2];
+    cv[0] = *reinterpret_cast<const float4*>(c);
+    sv[0] = *reinterpret_cast<const float4*>(s);
+    if constexpr (sizeof(T) == 2) {
+        cv[1] = *reinterpret_cast<const float4*>(c + 4);
+        sv[1] = *reinterpret_cast<const float4*>(s + 4);
+    }
+    return rope_rot<T>(x, xp, cv, sv, sg);
 }
 
 // What a wave of tile 1 / 3 carries through its key tiles: its lane's half of its Q row, the O^T accumulators and the softmax statistics of its query
@@ -459,8 +476,26 @@ __global__ __launch_bounds__(kAttnBlock) void attention_chunk_kernel(const AttnA
 // overwrites was last read in tile t - 1, and every wave has passed tile t's barrier behind those reads.
 // QK^T reduction order: lane half hf supplies the 16-byte vectors 2 k + hf (k = 0 ...) of the slice of its Q row and of its K row, not one contiguous
 // half as in tile 1: the two halves of a K row's 32 bytes then come from one cache line, and a fragment load touches 32 lines instead of 64.
-template <typename T, int HD>
-__global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const AttnArgs a, const int qblocks) {
+// Grouped K / V heads (every form, a run-time property): the K / V offsets of head h are those of K / V head h / (heads / kv_heads); with one K / V
+// head per query head they are D and 2 D.  The query heads of a group are consecutive (image, head)s, so the id dealing below leaves them on one L2
+// (a group is cut only where an L2's run of ids ends): the group's K / V head is read from HBM once.
+// CAUSAL: the workgroup of query block qb walks the key tiles 0 ... qb; its last tile is the diagonal one (key0 == q0), where key key0 + r is
+// replaced by -inf for the query q0 + col when key > query.  The loads of the tile behind the diagonal one read real rows (or the last row) and are
+// never used.  The late query blocks do the most work: within an (image, head) the ids are dealt out with qb reversed, the longest workgroup first.
+// ROPE (CAUSAL only, HD 128 / 256): q and k enter the scores rotated (kernels.h AttnArgs), the qkv buffer stays as it is.  The partner of element e
+// is e +/- HD/2, which in the contiguous slicing belongs to wave w ^ 2: for QK^T (only) wave w therefore owns the two half-slices
+// [w SL/2, (w + 1) SL/2) and HD/2 + the same, so a lane holds both partners itself, vectors k and k + NQ/2 of its registers.  The partial scores
+// are sums over the wave's elements, whatever they are, and are still added ((p0 + p1) + p2) + p3 by every wave; V and O keep the contiguous
+// slices.  Q is rotated once, at its query's position qi; a K fragment is rotated where it is used, at its key's global position, with the cos / sin
+// vectors that were loaded a tile ahead together with it (the added traffic: NQ * V / 4 float4s of each table per lane and tile, L2-resident).
+// Waves per SIMD the register allocation of a tile-2 form must leave room for: what the LDS of the plain form lets run (workgroups per CU =
+// budget / AttnStreamLdsBytes, one wave per SIMD each), so the table registers of a rotary form cost no occupancy (fp16: 3 at hd 128, 2 at hd 256).
+// The other forms state a minimum of 1, which is what a 256-thread kernel has without the attribute (one wave per SIMD): their code does not change
+template <typename T, int HD, bool ROPE>
+constexpr int kStreamWaves = ROPE ? int(kAttnLdsBudget / AttnStreamLdsBytes(HD, sizeof(T) == 2)) : 1;
+
+template <typename T, int HD, bool CAUSAL = false, bool ROPE = false>
+__global__ __launch_bounds__(kAttnBlock) __attribute__((amdgpu_waves_per_eu(kStreamWaves<T, HD, ROPE>))) void attention_stream_kernel(const AttnArgs a, const int qblocks) {
     constexpr bool F16 = sizeof(T) == 2;
     constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
     constexpr int SL = HD / 4;                     // head-dim slice of one wave
@@ -469,43 +504,78 @@ __global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const Attn
     constexpr int VPR = HD / V;                    // vectors per V row
     constexpr int NV = 32 * VPR / kAttnBlock;      // vectors of a V tile one thread stages
     constexpr int VT = 32 * HD;                    // elements of a V tile
+    constexpr int TV = V / 4;                      // ROPE: float4s of a table row per 16-byte operand vector
     static_assert(NQ >= 1 && NB >= 1 && NV >= 1 && 32 * VPR % kAttnBlock == 0, "head dim");
+    static_assert(!ROPE || (CAUSAL && NQ % 2 == 0 && HD <= 256), "the rotary form is built for causal steps of head dim 128 / 256 only");
     extern __shared__ __attribute__((aligned(16))) unsigned char attn_smem[];
     T* Vs = reinterpret_cast<T*>(attn_smem);                                               // [2][32 keys][HD]
     float4* Ps = reinterpret_cast<float4*>(attn_smem + 2 * VT * sizeof(T));                // [2][4 waves][4 register groups][64 lanes]
-    const int L = a.in.w, D = a.heads * HD, ntiles = (L + 31) / 32;
+    const int L = a.in.w, D = a.heads * HD;
     // Workgroups are handed to the 8 XCDs in turn (blockIdx % 8 labels the ones that share an L2).  Every workgroup of an (image, head) streams the
     // same K and V, so the ids are dealt out anew: the workgroups of one L2 get one run of consecutive (image, head, query block)s
     const int xg = int(blockIdx.x) % 8, xq = int(gridDim.x) / 8, xr = int(gridDim.x) % 8;
     const int bid = (xg < xr ? xg * (xq + 1) : xr * (xq + 1) + (xg - xr) * xq) + int(blockIdx.x) / 8;
-    const int qb = bid % qblocks;
+    const int qb = CAUSAL ? qblocks - 1 - bid % qblocks : bid % qblocks;
     const int hn = bid / qblocks;
     const int h = hn % a.heads, n = hn / a.heads;
     const int tid = int(threadIdx.x), wave = tid / 64, lane = tid % 64, col = lane & 31, hf = lane >> 5;
-    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // token row j: + j * sw; q at + 0, k at + D, v at + 2 D
+    const T* base = reinterpret_cast<const T*>(a.in.p) + int64_t(n) * a.in.sn + h * HD;      // token row j: + j * sw; q at + 0, k at + ko, v at + vo
+    // the head's k and v from `base`: + D and + 2 D, or with grouped K / V heads (head h reads K / V head h / group) + D + (kvh - h) HD and that + Dkv
+    const int kvn = a.kv_heads > 0 ? a.kv_heads : a.heads, ko = kvn == a.heads ? D : D + (h / (a.heads / kvn) - h) * HD, vo = ko + kvn * HD;
     const int q0 = qb * 32;                        // < L: qblocks = ceil(L / 32)
     const int qi = q0 + col < L ? q0 + col : L - 1;
+    const int ntiles = CAUSAL ? qb + 1 : (L + 31) / 32;      // CAUSAL: the last tile is the diagonal one, key0 == q0
 
+    // element (inside the head) of vector k of this lane's share of a Q / K row
+    auto voff = [&](int k) {
+        if constexpr (ROPE) return (k < NQ / 2 ? 0 : HD / 2) + wave * (SL / 2) + (2 * (k % (NQ / 2)) + hf) * V;
+        else return wave * SL + (2 * k + hf) * V;
+    };
     uint4 qv[NQ], kv[NQ], vv[NV];                  // Q for the whole kernel; K fragments and V vectors of the tile to come
-    {
-        const T* qrow = base + int64_t(qi) * a.in.sw + wave * SL + hf * V;
+    [[maybe_unused]] float4 ct[ROPE ? NQ * TV : 1], st[ROPE ? NQ * TV : 1];      // ROPE: the cos / sin entries of the lane's vectors at the position of `kv`'s row
+    [[maybe_unused]] auto load_tables = [&](int pos) {          // pos < L: the tables are [L][HD]
+        const float* cr = a.rope_cos + int64_t(pos) * HD;
+        const float* sr = a.rope_sin + int64_t(pos) * HD;
 #pragma unroll
-        for (int k = 0; k < NQ; ++k) qv[k] = *reinterpret_cast<const uint4*>(qrow + 2 * k * V);
+        for (int k = 0; k < NQ; ++k)
+#pragma unroll
+            for (int j = 0; j < TV; ++j) {
+                ct[k * TV + j] = *reinterpret_cast<const float4*>(cr + voff(k) + 4 * j);
+                st[k * TV + j] = *reinterpret_cast<const float4*>(sr + voff(k) + 4 * j);
+            }
+    };
+    [[maybe_unused]] auto rotate = [&](uint4 (&x)[NQ]) {        // by the tables in ct / st; vectors k and k + NQ / 2 are partners
+#pragma unroll
+        for (int k = 0; k < NQ / 2; ++k) {
+            const uint4 lo = x[k], hi = x[k + NQ / 2];
+            x[k] = rope_rot<T>(lo, hi, ct + k * TV, st + k * TV, -1.f);
+            x[k + NQ / 2] = rope_rot<T>(hi, lo, ct + (k + NQ / 2) * TV, st + (k + NQ / 2) * TV, 1.f);
+        }
+    };
+    {
+        const T* qrow = base + int64_t(qi) * a.in.sw;
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) qv[k] = *reinterpret_cast<const uint4*>(qrow + voff(k));
+        if constexpr (ROPE) {
+            load_tables(qi);
+            rotate(qv);
+        }
     }
     // Every load is unconditional, its row clamped to the last one: a load under a lane condition becomes a branch of its own, and the copies behind
     // it made the compiler wait for all loads in flight right behind the barrier.  A K row past L gives scores that are replaced by -inf below; a V
     // row past L is zeroed where it is written to LDS; the loads behind the last tile read the last row again and are never used.
     auto load_k = [&](int key0) {
         const int row = key0 + col < L ? key0 + col : L - 1;
-        const T* krow = base + int64_t(row) * a.in.sw + D + wave * SL + hf * V;
+        const T* krow = base + int64_t(row) * a.in.sw + ko;
 #pragma unroll
-        for (int k = 0; k < NQ; ++k) kv[k] = *reinterpret_cast<const uint4*>(krow + 2 * k * V);
+        for (int k = 0; k < NQ; ++k) kv[k] = *reinterpret_cast<const uint4*>(krow + voff(k));
+        if constexpr (ROPE) load_tables(row);      // (the clamped row: a position of the table)
     };
     auto load_v = [&](int key0) {
 #pragma unroll
         for (int it = 0; it < NV; ++it) {
             const int id = it * kAttnBlock + tid, cv = id % VPR, row = key0 + id / VPR < L ? key0 + id / VPR : L - 1;
-            vv[it] = *reinterpret_cast<const uint4*>(base + int64_t(row) * a.in.sw + 2 * D + cv * V);
+            vv[it] = *reinterpret_cast<const uint4*>(base + int64_t(row) * a.in.sw + vo + cv * V);
         }
     };
     load_k(0);
@@ -519,11 +589,14 @@ __global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const Attn
     float m = -__builtin_huge_valf(), lsum = 0.f;
     const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
 
+    // (one copy of the body: left alone the compiler peels the diagonal tile off a causal loop, a second body whose live ranges add 20 - 50 registers)
+#pragma clang loop unroll(disable)
     for (int t = 0; t < ntiles; ++t) {
         const int key0 = 32 * t, buf = t & 1;
         f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        if constexpr (ROPE) rotate(kv);            // at the key's global position: ct / st came with this tile's fragments
 #pragma unroll
         for (int k = 0; k < NQ; ++k) {
             if constexpr (F16) {
@@ -558,15 +631,20 @@ __global__ __launch_bounds__(kAttnBlock) void attention_stream_kernel(const Attn
             s[4 * g + 3] = ((p0.w + p1.w) + p2.w) + p3.w;
         }
         const bool tail = key0 + 32 > L;           // the last tile holds padded keys
+        [[maybe_unused]] const bool diag = t == ntiles - 1;      // CAUSAL: key0 == q0, the only tile whose elements are tested
         float mx = -__builtin_huge_valf();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-            s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
+            // (the query's unclamped index: a padded query q0 + col >= L then sees every real key of the tile, not fewer than its row L - 1)
+            if constexpr (CAUSAL) s[r] = (tail && key >= L) || (diag && key > q0 + col) ? -__builtin_huge_valf() : s[r] * sl2;
+            else s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
             mx = fmaxf(mx, s[r]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mn = fmaxf(m, mx);             // finite: every tile has at least one real key
+        // finite: every tile has at least one real key (key0 < L) that each query sees.  CAUSAL: a tile below the diagonal holds only keys
+        // < q0 <= every query of the workgroup, all real since q0 < L; the diagonal tile's first key q0 is real and <= every query q0 + col
+        const float mn = fmaxf(m, mx);
         const float alpha = fast_exp2(m - mn);     // 0 on the first tile (m = -inf)
         m = mn;
         float ps = 0.f;
@@ -678,23 +756,24 @@ hipError_t launch_chunk_hd(const AttnArgs& a, hipStream_t stream) {
     return a.head_dim == 64 ? launch_chunk<T, 64, CAUSAL, ROPE>(a, stream) : launch_chunk<T, 32, CAUSAL, ROPE>(a, stream);
 }
 
-template <typename T, int HD>
+template <typename T, int HD, bool CAUSAL, bool ROPE>
 hipError_t launch_stream(const AttnArgs& a, hipStream_t stream) {
     const int qblocks = (a.in.w + 31) / 32;
     const int64_t blocks = int64_t(a.in.n) * a.heads * qblocks;
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
-    attention_stream_kernel<T, HD><<<dim3(unsigned(blocks)), dim3(kAttnBlock), size_t(AttnStreamLdsBytes(HD, sizeof(T) == 2)), stream>>>(a, qblocks);
+    attention_stream_kernel<T, HD, CAUSAL, ROPE><<<dim3(unsigned(blocks)), dim3(kAttnBlock), size_t(AttnStreamLdsBytes(HD, sizeof(T) == 2)), stream>>>(a, qblocks);
     return hipGetLastError();
 }
 
-template <typename T>
+// tile 2 by head dim (128 / 256 / 512, a rotary step 128 / 256: the eligibility admitted nothing else)
+template <typename T, bool CAUSAL = false, bool ROPE = false>
 hipError_t launch_stream_hd(const AttnArgs& a, hipStream_t stream) {
-    switch (a.head_dim) {
-        case 128: return launch_stream<T, 128>(a, stream);
-        case 256: return launch_stream<T, 256>(a, stream);
-        case 512: return launch_stream<T, 512>(a, stream);
-        default: return hipErrorInvalidValue;
+    if (a.head_dim == 128) return launch_stream<T, 128, CAUSAL, ROPE>(a, stream);
+    if (a.head_dim == 256) return launch_stream<T, 256, CAUSAL, ROPE>(a, stream);
+    if constexpr (!ROPE) {
+        if (a.head_dim == 512) return launch_stream<T, 512, CAUSAL, ROPE>(a, stream);
     }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -707,12 +786,12 @@ bool AttentionEligible(const AttnArgs& a, int tile) {
     if (a.in.f8 || a.out.f8 || a.in.c != D + 2 * int64_t(kvn) * a.head_dim || a.out.c != D || a.in.n != a.out.n || a.in.h != 1 || a.out.h != 1 || a.in.w != a.out.w || a.in.w < 1)
         return false;
     if (a.mask && a.mask_sn < a.in.w) return false;
-    if (a.causal && (a.mask || tile == 2)) return false;      // no kernel has both masks, and tile 2 has no causal form
+    if (a.causal && a.mask) return false;                     // no kernel has both masks
     const bool rope = a.rope_cos || a.rope_sin;
     if (rope && (!a.rope_cos || !a.rope_sin || a.mask || a.head_dim % 2)) return false;      // both tables; no kernel rotates under a key mask
-    if (tile == 2 && (rope || kvn != a.heads)) return false;  // tile 2 has neither a rotary nor a grouped form
     if (tile == 0) return true;
-    if (rope && (!a.causal || !Aligned16(a.rope_cos) || !Aligned16(a.rope_sin))) return false;      // tiles 1 and 3 rotate in their causal form only
+    if (rope && (!a.causal || !Aligned16(a.rope_cos) || !Aligned16(a.rope_sin))) return false;      // tiles 1, 2 and 3 rotate in their causal form only
+    if (tile == 2 && rope && a.head_dim != 128 && a.head_dim != 256) return false;                  // (no rotary form at hd 512)
     const int V = a.out.f16 ? 8 : 4;
     // (the offsets are in the base pointers: their alignment stands for the offset condition)
     if (a.in.f16 != a.out.f16 || !token_view_ok(a.in, V) || !token_view_ok(a.out, V)) return false;
@@ -733,7 +812,11 @@ hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream) {
         else hipLaunchKernelGGL((attention_generic_kernel<false, false>), dim3(unsigned(blocks)), dim3(kAttnBlock), 0, stream, a, rows);
         return hipGetLastError();
     }
-    if (tile == 2) return a.out.f16 ? launch_stream_hd<_Float16>(a, stream) : launch_stream_hd<float>(a, stream);
+    if (tile == 2) {
+        if (a.rope_cos) return a.out.f16 ? launch_stream_hd<_Float16, true, true>(a, stream) : launch_stream_hd<float, true, true>(a, stream);
+        if (a.causal) return a.out.f16 ? launch_stream_hd<_Float16, true>(a, stream) : launch_stream_hd<float, true>(a, stream);
+        return a.out.f16 ? launch_stream_hd<_Float16>(a, stream) : launch_stream_hd<float>(a, stream);
+    }
     if (tile == 3) {
         if (a.rope_cos) return a.out.f16 ? launch_chunk_hd<_Float16, true, true>(a, stream) : launch_chunk_hd<float, true, true>(a, stream);
         if (a.causal) return a.out.f16 ? launch_chunk_hd<_Float16, true>(a, stream) : launch_chunk_hd<float, true>(a, stream);
@@ -763,7 +846,12 @@ hipError_t InitKernelsAttn() {
         reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 32, true, true>), reinterpret_cast<const void*>(&attention_chunk_kernel<_Float16, 64, true, true>),
         reinterpret_cast<const void*>(&attention_stream_kernel<float, 128>), reinterpret_cast<const void*>(&attention_stream_kernel<float, 256>),
         reinterpret_cast<const void*>(&attention_stream_kernel<float, 512>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 128>),
-        reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 256>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 512>)};
+        reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 256>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 512>),
+        reinterpret_cast<const void*>(&attention_stream_kernel<float, 128, true>), reinterpret_cast<const void*>(&attention_stream_kernel<float, 256, true>),
+        reinterpret_cast<const void*>(&attention_stream_kernel<float, 512, true>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 128, true>),
+        reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 256, true>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 512, true>),
+        reinterpret_cast<const void*>(&attention_stream_kernel<float, 128, true, true>), reinterpret_cast<const void*>(&attention_stream_kernel<float, 256, true, true>),
+        reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 128, true, true>), reinterpret_cast<const void*>(&attention_stream_kernel<_Float16, 256, true, true>)};
     for (const void* k : kernels)
         if (const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget)); e != hipSuccess) return e;
     return hipSuccess;

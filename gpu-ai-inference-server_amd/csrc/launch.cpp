@@ -679,7 +679,7 @@ std::string kernel_label(const Step& s) {
         }
         case StepKind::TokenAssemble: return std::string("token_assemble_kernel<") + (s.out.f16 ? "f16>" : "f32>");
         case StepKind::Attention:
-            if (s.tile == 2) return std::string("attention_stream_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">";
+            if (s.tile == 2) return std::string("attention_stream_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.rope ? ",causal,rope>" : s.causal ? ",causal>" : ">");
             if (s.tile == 3) return std::string("attention_chunk_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.rope ? ",causal,rope>" : s.causal ? ",causal>" : ">");
             return s.tile == 0 ? std::string(s.key_mask ? "attention_generic_kernel<mask>" : s.causal ? "attention_generic_kernel<causal>" : "attention_generic_kernel")
                                : std::string("attention_mfma_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) +

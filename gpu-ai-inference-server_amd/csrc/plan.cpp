@@ -4525,7 +4525,7 @@ void Planner::EmitTokenAssemble(const LNode& n, Step& s) {
 
 // attention: kernels.h AttnDefaultTile (tile 1, the MFMA kernel, where AttnMfmaFits says so; tile 2, the streaming kernel, on a wide head with
 // at least kAttnStreamMinTokens tokens; else the generic kernel).  A causal step: AttnCausalDefaultTile (tile 1, else tile 3, the chunk kernel, else
-// the generic kernel).  IE_FORCE_TILE as for layer norm but over tiles 0 and 1 only; IE_ATTN_TILE pins the attention steps alone, tiles 2 and 3
+// tile 2's causal form on a wide head with at least kAttnStreamCausalMinTokens tokens, else the generic kernel).  IE_FORCE_TILE as for layer norm but over tiles 0 and 1 only; IE_ATTN_TILE pins the attention steps alone, tiles 2 and 3
 // included (an ineligible value is the generic kernel); a non-causal step reaches tile 3 this way only
 void Planner::EmitAttention(const LNode& n, Step& s) {
     if (s.in.f8 || s.out.f8) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
@@ -4548,20 +4548,19 @@ void Planner::EmitAttention(const LNode& n, Step& s) {
         s.w_off = push_vec(n.w);
         s.w2_off = push_vec(n.w2);
     }
-    const bool gqa = s.kv_heads != s.heads;
-    // a rotary step runs on tiles 1 / 3 in their causal form only (head dims 32 / 64); non-causal rope and every other head dim: the generic kernel
+    // a rotary step runs on tiles 1 / 3 (head dims 32 / 64) and tile 2 (head dims 128 / 256) in their causal form only; non-causal rope, a rotary head
+    // of 512 and every other head dim: the generic kernel.  Grouped K / V heads are a run-time property of every tile
     const bool views = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 && !(rope && !n.causal);
     auto fits = [&](int tile) {
         if (tile == 0) return true;
-        if (tile == 2 && (rope || gqa)) return false;  // (tile 2 has neither a rotary nor a grouped form)
+        if (tile == 2 && rope && s.head_dim != 128 && s.head_dim != 256) return false;      // (tile 2 has no rotary form at hd 512)
         if (tile == 3) return views && AttnChunkFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask);
-        if (tile == 2 && n.causal) return false;       // (tile 2 has no causal form)
         return views && (tile == 1 ? AttnMfmaFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask)
                                    : AttnStreamFits(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask));
     };
     s.tile = views ? AttnDefaultTile(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off, n.key_mask) : 0;
-    if (s.tile == 2 && !fits(2)) s.tile = 0;
     if (n.causal) s.tile = views ? AttnCausalDefaultTile(s.in.w, s.head_dim, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.c, s.out.pitch, s.out.c_off) : 0;
+    if (s.tile == 2 && !fits(2)) s.tile = 0;
     int t = ForcedTile(kNumAttnForcedTiles);
     if (const char* e = env.get("IE_ATTN_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumAttnTiles) t = std::atoi(e);      // (the attention steps alone)
     if (t >= 0) s.tile = fits(t) ? t : 0;

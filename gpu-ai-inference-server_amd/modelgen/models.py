@@ -1472,6 +1472,13 @@ def llama_135m(batch: int = 1, **kw) -> bytes:
     return llama(batch, **dict(dict(seq=128, vocab=49152, dim=576, depth=30, heads=9, kv_heads=3, mlp=1536, max_pos=2048), **kw))
 
 
+def llama_3b_layers(batch: int = 1, depth: int = 2, **kw) -> bytes:
+    """`depth` decoder layers of Llama-3.2-3B's shape: dim 3072, 24 heads of 128 over 8 K / V heads, mlp 8192, rope theta 500 000, behind a small
+    vocabulary (1024 ids), for measurements of the layer: a layer is 101 M weights, so two of them serialize to 0.8 GB, well under protobuf's 2 GB,
+    which the 28 layers and the 128 256-id embedding of the whole model are not"""
+    return llama(batch, **dict(dict(seq=128, vocab=1024, dim=3072, depth=depth, heads=24, kv_heads=8, mlp=8192, max_pos=2048, rope_theta=500000.0), **kw))
+
+
 def llama_tiny(batch: int = 1, **kw) -> bytes:
     return llama(batch, **dict(dict(seq=40, vocab=61, dim=128, depth=2, heads=4, kv_heads=2, mlp=256, max_pos=64), **kw))
 
