@@ -136,6 +136,9 @@ bool ModelObj::Load() {
                     for (const ie::Step& st : pl.steps) {
                         if (st.kind == ie::StepKind::Attention && st.key_mask)      // a key mask: any integer is a valid value (-1: nothing to check)
                             for (size_t i = 0; i < pl.inputs.size(); ++i) if (pl.inputs[i].view.buf == st.in2.buf) id_rows[i] = -1;
+                        // the positions of a rotary decode step index the [max_pos, hd] rope tables: checked against their rows like ids against a table
+                        if ((st.kind == ie::StepKind::Attention || st.kind == ie::StepKind::KvAppend) && st.pos.buf >= 0)
+                            for (size_t i = 0; i < pl.inputs.size(); ++i) if (pl.inputs[i].view.buf == st.pos.buf) id_rows[i] = st.rope_rows;
                         if (st.kind != ie::StepKind::Embed) continue;
                         for (size_t i = 0; i < pl.inputs.size(); ++i) {
                             if (pl.inputs[i].view.buf == st.in.buf) id_rows[i] = st.emb_vocab;

@@ -633,7 +633,8 @@ void DeviceModel::EnsurePipeline(PlanInstance& pi, bool allow_tune) {
     auto valid = [&](size_t h) {
         for (size_t i = 0; i < h; ++i) {
             const Step &a = sub.steps[i], &b = full.steps[i];
-            if (a.kind != b.kind || !same_view(a.in, b.in) || !same_view(a.out, b.out) || a.has_in2 != b.has_in2 || (a.has_in2 && !same_view(a.in2, b.in2)) ||
+            if (b.kind == StepKind::KvAppend || b.past_len > 0) return false;      // (cache views are not compared below: such a step stays in the tail)
+            if (a.kind != b.kind ||!same_view(a.in, b.in) || !same_view(a.out, b.out) || a.has_in2 != b.has_in2 || (a.has_in2 && !same_view(a.in2, b.in2)) ||
                 a.w_off != b.w_off || a.bias_off != b.bias_off || a.pre_scale_off != b.pre_scale_off || a.pre_shift_off != b.pre_shift_off ||
                 a.parts.size() != b.parts.size())
                 return false;

@@ -16,6 +16,7 @@ LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 GnArgs MakeGnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 EmbedArgs MakeEmbedArgs(const PlanInstance& pi, const Step& s, const float* weights);
 AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s, const float* weights);
+DecodeArgs MakeDecodeArgs(const PlanInstance& pi, const Step& s, const float* weights);
 WinAttnArgs MakeWinAttnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 std::string kernel_label(const Step& s);
 
@@ -70,7 +71,11 @@ bool DeviceModel::TiledFamily(const PlanInstance& pi, const Step& s, F&& f) cons
         case StepKind::LayerNorm: f(MakeLnArgs(pi, s, wb), LayerNormEligible, LaunchLayerNorm, TiledNames{"layer_norm", "layer-norm"}); return true;
         case StepKind::GroupNorm: f(MakeGnArgs(pi, s, wb), GroupNormEligible, LaunchGroupNorm, TiledNames{"group_norm", "group-norm"}); return true;
         case StepKind::Embed: f(MakeEmbedArgs(pi, s, wb), EmbedEligible, LaunchEmbed, TiledNames{"embed", nullptr}); return true;
-        case StepKind::Attention: f(MakeAttnArgs(pi, s, wb), AttentionEligible, LaunchAttention, TiledNames{"attention", "attention"}); return true;
+        case StepKind::Attention:
+            // a decode step (a past): its own two tiles, 0 = the generic kernel over `present` and kAttnDecodeTile; the step that carries the parts runs them at tile 0
+            if (s.past_len > 0) { f(MakeDecodeArgs(pi, s, wb), AttentionDecodeEligible, LaunchAttentionDecode, TiledNames{"attention_decode", "attention"}); return true; }
+            f(MakeAttnArgs(pi, s, wb), AttentionEligible, LaunchAttention, TiledNames{"attention", "attention"});
+            return true;
         case StepKind::WindowAttention: f(MakeWinAttnArgs(pi, s, wb), WindowAttentionEligible, LaunchWindowAttention, TiledNames{"window_attention", "window-attention"}); return true;
         case StepKind::Conv:
             if (s.algo == ConvAlgo::Depthwise) { f(MakeDwArgs(pi, s), ConvDwEligible, LaunchConvDw, TiledNames{"conv_dw", nullptr}); return true; }

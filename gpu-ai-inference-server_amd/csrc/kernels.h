@@ -418,6 +418,73 @@ constexpr int AttnCausalDefaultTile(int64_t L, int hd, bool f16, int64_t c_in, i
 }
 bool AttentionEligible(const AttnArgs& a, int tile);
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);
+
+// KV cache: append and one-token decode attention (kernels_decode.hip; generation with Llama-class graphs).  The cache tensors are fp32 in every
+// precision and dense [N][kv_heads][rows][head_dim]: past_k / past_v with rows = past_len (null: no past), present_k / present_v with rows =
+// past_len + new_len.  in = the qkv token rows [N, new_len, (H + 2 Hkv) hd] as AttnArgs describes them (float or half).
+//   kv_append          present rows < past_len = the past rows, bit for bit; row past_len + l = k of token l after the rotary embedding (AttnArgs'
+//                      arithmetic: full-width fp32 tables, fp32 products) resp. v of token l, converted to fp32
+//   decode attention   new_len == 1: out[n, 0, h hd + e] = sum_j softmax_j(scale q[n, h] . K[n, h / g, j] + bias[n, j]) V[n, h / g, j, e] over the
+//                      past_len + 1 rows j of present, q rotated like the new k; bias = (1 - float(mask[n, j])) * mask_value as AttnArgs' key mask, kept finite
+// The rotation's table row of token l of image n is pos[n] + l (pos = the INT64 position_ids [N, 1]; a negative value counts from the end) or l
+// without pos, clamped into [0, rope_rows - 1] on the device: a caller that skips the host check cannot make a kernel read outside the tables.
+struct DecodeArgs {
+    TensorArg in, out;
+    const float* past_k = nullptr;
+    const float* past_v = nullptr;
+    float* present_k = nullptr;
+    float* present_v = nullptr;
+    int heads = 0, kv_heads = 0, head_dim = 0;
+    int past_len = 0, new_len = 1;
+    float scale = 1.f;
+    const int64_t* mask = nullptr;     // [N][past_len + 1] rows at mask + n * mask_sn, or null
+    int64_t mask_sn = 0;
+    float mask_value = 0.f;
+    const float* rope_cos = nullptr;   // [rope_rows][head_dim] or null
+    const float* rope_sin = nullptr;
+    int64_t rope_rows = 0;
+    const int64_t* pos = nullptr;      // [N] or null
+    int splits = 1;                    // tile 4: key splits per (image, K / V head)
+    float* workspace = nullptr;        // tile 4, splits > 1: the split records
+    int64_t workspace_floats = 0;
+};
+// A decode step's tiles: 0 = attention_decode_generic_kernel (one wave per (image, query head) over `present`, which a kv_append launch wrote: any
+// head_dim up to kDecodeMaxHeadDim, any past_len, float or half); kAttnDecodeTile (4) = attention_decode_kernel<T, HD, G>: a workgroup = (image, K / V
+// head, key split) serves the g <= G query heads of its group, loads every cached K / V element once as 16-byte lanes, stores it into `present`,
+// appends the new row in the last split; splits > 1: attention_decode_combine_kernel adds the split records in a fixed order.  Tiles 1-3 take no
+// decode step.  DecodeKeyTile: the keys a workgroup of tile 4 loads per iteration (4 waves x 64 lanes x 4 floats / head_dim)
+constexpr int kAttnDecodeTile = 4;
+constexpr int kDecodeMaxHeadDim = 512;
+constexpr int kDecodeMaxGroup = 8;
+constexpr int kDecodeMaxSplits = 64;
+constexpr int DecodeKeyTile(int hd) { return 1024 / hd; }
+// tile 4 declines a mask whose bias is small enough to keep something of a score in an fp32 sum (|c| <= 2^24, e.g. -10000): tile 0 takes the image's
+// largest bias out of every score first, as attention_generic_kernel<mask> does, and a split sees only its own keys
+constexpr bool DecodeFastFits(int hd, int heads, int kv_heads, bool masked, float mask_value) {
+    return (hd == 32 || hd == 64 || hd == 128) && kv_heads >= 1 && heads % kv_heads == 0 && heads / kv_heads <= kDecodeMaxGroup &&
+           (!masked || mask_value < -16777216.f);
+}
+// floats of workspace the split records of tile 4 take: (m, l, o[hd]) per (image, query head, split)
+constexpr int64_t DecodeWorkspaceFloats(int64_t n, int heads, int hd, int splits) { return splits > 1 ? n * heads * splits * (hd + 2) : 0; }
+// the planner's split count: enough workgroups for two per CU of a 256-CU device from N * Hkv alone, each split at least kDecodeMinSplitKeys keys
+// (and one key tile), at most kDecodeMaxSplits
+constexpr int64_t kDecodeMinSplitKeys = 128;
+// the planner's default tile of a decode step: tile 4 from this many keys (past_len + 1) on, where it fits.  Chosen as kAttnStreamCausalMinTokens was: the
+// smallest measured length at which tile 4 beats the parts in both precisions, which is the smallest there is, past_len = 1
+constexpr int64_t kAttnDecodeMinKeys = 2;
+constexpr int DecodeDefaultSplits(int64_t n, int kv_heads, int64_t keys, int hd) {
+    const int64_t groups = n * kv_heads, want = (512 + groups - 1) / groups;
+    const int64_t tiles = (keys + DecodeKeyTile(hd) - 1) / DecodeKeyTile(hd), by_keys = keys / kDecodeMinSplitKeys;
+    int64_t s = want;
+    if (s > by_keys) s = by_keys;
+    if (s > tiles) s = tiles;
+    if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
+    return s < 1 ? 1 : int(s);
+}
+bool KvAppendEligible(const DecodeArgs& a);
+hipError_t LaunchKvAppend(const DecodeArgs& a, hipStream_t stream);
+bool AttentionDecodeEligible(const DecodeArgs& a, int tile);
+hipError_t LaunchAttentionDecode(const DecodeArgs& a, int tile, hipStream_t stream);
 hipError_t InitKernelsAttn();            // once per process, before any capture: lets the MFMA kernels take more than 64 KiB of LDS
 
 // Attention inside (shifted) windows of a channels-last map (kernels_wattn.hip; Swin).  in = the qkv map [N, H, W, 3 D], out = [N, H, W, D].  The map is

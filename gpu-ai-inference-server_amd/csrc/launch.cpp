@@ -97,6 +97,39 @@ AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s, const float* weight
     return a;
 }
 
+// A kv_append step or a decode attention step (kernels_decode.hip): the cache views are dense fp32 [N][Hkv][rows][hd] graph inputs / outputs
+DecodeArgs MakeDecodeArgs(const PlanInstance& pi, const Step& s, const float* weights) {
+    DecodeArgs a;
+    a.in = make_arg(pi, s.in);
+    if (s.kind == StepKind::Attention) a.out = make_arg(pi, s.out);
+    auto cache = [&](const View& v) -> float* { return v.buf >= 0 ? make_arg(pi, v).p : nullptr; };
+    a.past_k = cache(s.past_k);
+    a.past_v = cache(s.past_v);
+    a.present_k = cache(s.present_k);
+    a.present_v = cache(s.present_v);
+    a.heads = s.heads;
+    a.kv_heads = s.kv_heads > 0 ? s.kv_heads : s.heads;
+    a.head_dim = s.head_dim;
+    a.past_len = s.past_len;
+    a.new_len = int(s.in.w);
+    a.scale = s.attn_scale;
+    if (s.key_mask && s.has_in2) {
+        a.mask = reinterpret_cast<const int64_t*>(make_arg(pi, s.in2).p);
+        a.mask_sn = s.in2.pitch;
+        a.mask_value = s.mask_value;
+    }
+    if (s.rope) {
+        a.rope_cos = weights + s.w_off;
+        a.rope_sin = weights + s.w2_off;
+        a.rope_rows = s.rope_rows;
+        if (s.pos.buf >= 0) a.pos = reinterpret_cast<const int64_t*>(make_arg(pi, s.pos).p);
+    }
+    a.splits = s.splits > 0 ? s.splits : 1;
+    a.workspace = pi.workspace;
+    a.workspace_floats = pi.workspace_floats;
+    return a;
+}
+
 WinAttnArgs MakeWinAttnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     WinAttnArgs a;
     a.in = make_arg(pi, s.in);
@@ -440,6 +473,7 @@ const Step& DeviceModel::LaunchedStep(const PlanInstance& pi, const Step& s, Ste
         return scratch;
     };
     bool ok = true;
+    if (s.kind == StepKind::Attention && !s.parts.empty() && s.tile == 0) return s;      // a decode step on tile 0: its parts
     if (TiledFamily(pi, s, [&](const auto& a, auto eligible, auto, TiledNames) { ok = s.tile == 0 || eligible(a, s.tile); }))
         return with_tile(ok ? s.tile : 0);           // the generic kernel takes every step of its family
     if (s.kind != StepKind::Conv) return s;
@@ -488,6 +522,8 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
     if (s.kind == StepKind::Embed && (s.out.f8 || !s.in.i64)) throw std::runtime_error("internal error: the embed kernels take int64 ids and write floats or halfs");
     if (s.kind == StepKind::Conv && s.algo == ConvAlgo::Transposed && (s.has_in2 || s.pre_scale_off >= 0))
         throw std::runtime_error("internal error: transposed conv " + s.name + " with a prologue or a residual");
+    // a decode step on tile 0 (or one whose tile 4 declined): kv_append, then the attention over `present`
+    if (s.kind == StepKind::Attention && !s.parts.empty() && s.tile == 0) { LaunchParts(pi, s, stream_); return; }
     if (TiledFamily(pi, s, [&](const auto& a, auto, auto launch, TiledNames names) {
             if (names.fp8_noun && (s.in.f8 || s.out.f8)) throw std::runtime_error(std::string("internal error: fp8 tensor reached the ") + names.fp8_noun + " kernels");
             check(launch(a, s.tile, stream_), names.label);
@@ -624,6 +660,13 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
         }
         case StepKind::LayerNorm: case StepKind::GroupNorm: case StepKind::Embed: case StepKind::Attention: case StepKind::WindowAttention:
             break;      // (launched through TiledFamily above)
+        case StepKind::KvAppend: {
+            if (s.in.f8) throw std::runtime_error("internal error: fp8 tensor reached the kv_append kernel");
+            const DecodeArgs a = MakeDecodeArgs(pi, s, wb);
+            if (!KvAppendEligible(a)) throw std::runtime_error("kv_append step " + s.name + ": the kernel declines its operands");
+            check(LaunchKvAppend(a, stream_), "kv_append");
+            break;
+        }
         case StepKind::PatchMerge: {
             if (s.in.f8 || s.out.f8) throw std::runtime_error("internal error: fp8 tensor reached the patch-merge kernel");
             PatchMergeArgs a;
@@ -678,7 +721,12 @@ std::string kernel_label(const Step& s) {
             return s.tile == 0 ? stem + "_generic_kernel" : stem + "_kernel<" + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
         }
         case StepKind::TokenAssemble: return std::string("token_assemble_kernel<") + (s.out.f16 ? "f16>" : "f32>");
+        case StepKind::KvAppend: return std::string("kv_append_kernel<") + (s.in.f16 ? "f16>" : "f32>");
         case StepKind::Attention:
+            if (s.past_len > 0) {
+                if (s.tile == kAttnDecodeTile) return std::string("attention_decode_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">" + (s.splits > 1 ? " + attention_decode_combine_kernel" : "");
+                return std::string(s.parts.empty() ? "" : "kv_append_kernel + ") + "attention_decode_generic_kernel<" + (s.out.f16 ? "f16>" : "f32>");
+            }
             if (s.tile == 2) return std::string("attention_stream_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.rope ? ",causal,rope>" : s.causal ? ",causal>" : ">");
             if (s.tile == 3) return std::string("attention_chunk_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.rope ? ",causal,rope>" : s.causal ? ",causal>" : ">");
             return s.tile == 0 ? std::string(s.key_mask ? "attention_generic_kernel<mask>" : s.causal ? "attention_generic_kernel<causal>" : "attention_generic_kernel")

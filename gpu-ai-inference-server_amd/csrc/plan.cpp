@@ -46,7 +46,7 @@ struct Val {
     int64_t sel_rows = 1, sel_idx = 0;
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED, L_GROUPNORM };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED, L_GROUPNORM, L_KVAPPEND };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -79,6 +79,12 @@ struct LNode {
     float mask_value = 0.f;
     bool causal = false;                // L_ATTENTION: query i attends to the keys j <= i
     int kv_heads = 0;                   // L_ATTENTION: K / V heads (0: heads); in = q (D) | k (Dkv) | v (Dkv).  Rotary: w / w2 = the cos / sin tables [L][head_dim]
+    // L_KVAPPEND: in[0] = the qkv tokens, out = present k (kv_v: present v) [N, Hkv, past_len + L, hd]; in[past_in] = the past input (-1: none), in[pos_in] =
+    // the INT64 position input (-1: none); w / w2 = the rope tables [rope_rows][hd] (k only).  L_ATTENTION with past_len > 0 (a decode step): in[present_in]
+    // and in[present_in + 1] = present k / v, in[pos_in] = the positions
+    int past_len = 0, past_in = -1, pos_in = -1, present_in = -1;
+    bool kv_v = false;
+    int64_t rope_rows = 0;
     // L_EMBED: in = the int64 ids of the first table (and of the second); w = the first table [emb_vocab][D], w2 = the second [emb_types][D] (empty:
     // none), bias = the position rows [L][D] (empty: none), s / t / eps = gamma / beta / epsilon of the LayerNormalization behind the sum
     int64_t emb_vocab = 0, emb_types = 0;
@@ -421,7 +427,12 @@ struct Planner {
         int64_t rope_rows = 0;
         std::string rope_name;
         std::vector<std::vector<int64_t>> rep_expand, rep_reshape;      // repeat_kv: the Expand and Reshape shapes (k, v), checked against N and L at the import
+        // the cache: past_k / past_v = the FLOAT rank-4 graph inputs a Concat(axis 2) puts in front of the step's own k / v (a decode step); present_k /
+        // present_v = the graph outputs that name the Concat results (without a past: the rotated k and the transposed v of a prefill); rope_pos = the
+        // INT64 graph input [N, 1] that gathers the rope tables (empty: constant positions); cat_k / cat_v = the Concat nodes (messages)
+        std::string past_k, past_v, present_k, present_v, rope_pos, cat_k, cat_v;
     };
+    std::map<std::vector<float>, int64_t> rope_blob;      // EmitKvAppend: the rope tables already in the weight blob (every layer of a model gathers the same ones)
     std::set<const OnnxNode*> rope_const_nodes;      // the Unsqueeze / Slice / Gather nodes that cut the rope tables out of constants: evaluated at load, import nothing
     // MatchCausalWhere / MatchCausalAdd: the two spellings of a causal mask on the scores (false / a refusal by name: not one)
     void MatchCausalWhere(const OnnxNode& wh, const std::string& prefix, AttnMatch& am, std::vector<const OnnxNode*>& taken);
@@ -597,6 +608,7 @@ struct Planner {
     void EmitLayerNorm(const LNode& n, Step& s);
     void EmitTokenAssemble(const LNode& n, Step& s);
     void EmitAttention(const LNode& n, Step& s);
+    void EmitKvAppend(const LNode& n, Step& s);
     void EmitWindowAttention(const LNode& n, Step& s);
     void EmitPatchMerge(const LNode& n, Step& s) const;
 
@@ -2041,6 +2053,11 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
     auto miss = [&](const std::string& what) { fail(prefix + what); };
     auto nm_of = [](const OnnxNode* p) { return p->name.empty() ? p->outputs[0] : p->name; };
     auto perm_is = [](const OnnxNode* p, std::vector<int64_t> want) { return p && p->op == "Transpose" && p->attr_ints("perm", {}) == want; };
+    auto graph_input = [&](const std::string& name) -> const OnnxValueInfo* {
+        for (const auto& vi : m.inputs) if (vi.name == name) return &vi;
+        return nullptr;
+    };
+    auto graph_output = [&](const std::string& name) { for (const auto& vo : m.outputs) if (vo.name == name) return true; return false; };
     double scale = 1.0;
     auto peel = [&](std::string cur) -> std::string {
         for (;;) {
@@ -2066,6 +2083,7 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         if (gi.nreaders(p->outputs[0]) != 1) miss("the intermediate " + p->outputs[0] + " (" + p->op + " " + nm_of(p) + ") has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
     };
     // a rope table as the graph's constants give it: an initializer / Constant, or Unsqueeze / Slice (step 1) / Gather(axis 0, constant indices) of one
+    std::string gather_pos;                        // const_eval: the INT64 graph input that gathers the table being evaluated (empty: constant positions)
     std::function<bool(const std::string&, OnnxTensor&, std::vector<const OnnxNode*>&)> const_eval = [&](const std::string& name, OnnxTensor& out, std::vector<const OnnxNode*>& nodes) -> bool {
         if (const OnnxTensor* t = gi.cst(name)) { out = *t; return !t->f.empty(); }
         const OnnxNode* p = gi.producer(name);
@@ -2075,6 +2093,25 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         if (!const_eval(p->inputs[0], in, nodes)) return false;
         nodes.push_back(p);
         const int64_t rank = int64_t(in.dims.size());
+        // run-time positions (a decode step): Gather(table [max_pos, hd], position_ids [N, 1], axis 0) -> Unsqueeze(axes [1]) broadcasts as [N, 1, 1, hd].
+        // The whole table is the constant; the kernels index it with the input's values
+        if (p->op == "Gather" && p->inputs.size() == 2 && !gi.cst(p->inputs[1])) {
+            const std::string who = "Gather " + nm_of(p) + ": the position ids " + p->inputs[1] + " of the rope table ";
+            bool ok = false;
+            for (size_t i = 0; i < m.inputs.size(); ++i)
+                if (m.inputs[i].name == p->inputs[1]) ok = m.inputs[i].elem_type == ONNX_INT64 && input_shapes[i].size() == 2 && input_shapes[i][1] == 1;
+            if (!ok) miss(who + "are neither a constant nor an INT64 graph input [N, 1] (supported: constant positions, or position_ids [N, 1] of a decode step)");
+            if (p->attr_i("axis", 0) != 0 || rank != 2 || !gather_pos.empty()) miss(who + "must gather a [max_pos, hd] table once, along axis 0");
+            gather_pos = p->inputs[1];
+            out = in;
+            return true;
+        }
+        if (p->op == "Unsqueeze" && !gather_pos.empty()) {
+            if (ints_of(p, "axes", 1) != std::vector<int64_t>{1}) miss("Unsqueeze " + nm_of(p) + ": a rope table gathered by " + gather_pos + " [N, 1] must be unsqueezed at axes [1] (it then broadcasts as [N, 1, 1, hd])");
+            out = in;
+            return true;
+        }
+        if (!gather_pos.empty()) return false;
         if (p->op == "Unsqueeze") {
             std::vector<int64_t> ax = ints_of(p, "axes", 1);
             if (ax.empty()) return false;
@@ -2123,7 +2160,7 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
             }
         return true;
     };
-    struct Rope { bool on = false; std::vector<float> cos, sin; int64_t rows = 0, hd = 0; std::string name; };
+    struct Rope { bool on = false; std::vector<float> cos, sin; int64_t rows = 0, hd = 0; std::string name, pos; int tables = 0; };
     // name = Add(Mul(t, cos), Mul(Concat(Neg(Slice(t, hd/2:)), Slice(t, :hd/2), axis -1), sin)), either operand order: -> t (name itself: no rotation here)
     auto unrope = [&](const std::string& name, const char* which, Rope& r) -> std::string {
         const OnnxNode* ad = gi.producer(name);
@@ -2137,7 +2174,12 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
             for (int k = 0; k < 2; ++k) {
                 std::vector<const OnnxNode*> nodes;
                 OnnxTensor t;
+                gather_pos.clear();
                 if (const_eval(mu->inputs[size_t(k)], t, nodes)) {
+                    const std::string gp = gather_pos;
+                    if (r.tables++ > 0 && r.pos != gp) miss(who + "its cos and sin tables are not gathered by the same position ids");
+                    r.pos = gp;
+                    if (!gp.empty()) for (const OnnxNode* p : nodes) mask_nodes.insert(p);      // (they may read the INT64 graph input)
                     OnnxTensor dummy;
                     std::vector<const OnnxNode*> n2;
                     if (const_eval(mu->inputs[size_t(1 - k)], dummy, n2)) miss(who + "both operands of Mul " + nm_of(mu) + " are constants");
@@ -2207,11 +2249,35 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         if (!e5 || e5->i.size() != 5 || !r4 || r4->i.size() != 4) miss(who + "the shapes of the Expand [N, Hkv, g, L, hd] and of the Reshape [N, H, L, hd] behind it must be constants");
         g = e5->i[2];
         if (g < 1) miss(who + "the group size " + std::to_string(g) + " is not positive");
+        if (graph_output(rs->outputs[0]))
+            miss(who + "the graph output " + rs->outputs[0] + " is the value behind repeat_kv; a present output is the value in front of it, [N, Hkv, rows, hd]");
         for (const OnnxNode* p : {us, ex, rs}) one_reader(p);
         taken.insert(taken.end(), {us, ex, rs});
         am.rep_expand.push_back(e5->i);
         am.rep_reshape.push_back(r4->i);
         return us->inputs[0];
+    };
+    // name = Concat(past, t, axis 2) with past a FLOAT rank-4 graph input, the cache of a decode step: -> t (name itself: no cache here)
+    auto uncat = [&](const std::string& name, const char* which, std::string& past, std::string& present, std::string& cat_name) -> std::string {
+        const OnnxNode* cat = gi.producer(name);
+        if (!cat || cat->op != "Concat" || cat->inputs.size() != 2) return name;
+        const OnnxValueInfo *i0 = graph_input(cat->inputs[0]), *i1 = graph_input(cat->inputs[1]);
+        if (!i0 && !i1) return name;
+        const std::string who = std::string("the cache of ") + which + " (Concat " + nm_of(cat) + "): ";
+        const std::string form = std::string("; supported: Concat(past, ") + which + ", axis 2) with past a FLOAT graph input [N, Hkv, P, hd] read by this Concat alone";
+        if (!i0) miss(who + "its operands are in the order (" + which + ", past)" + form);
+        if (i1) miss(who + "both operands are graph inputs" + form);
+        const int64_t ax = cat->attr_i("axis", 0);
+        if (ax != 2 && ax != -2) miss(who + "axis = " + std::to_string(ax) + form);
+        if (i0->elem_type != ONNX_FLOAT || i0->dims.size() != 4) miss(who + "the past input " + i0->name + " is not a FLOAT tensor of rank 4" + form);
+        if (gi.nreaders(i0->name) != 1) miss(who + "the past input " + i0->name + " has " + std::to_string(gi.nreaders(i0->name)) + " readers, not 1" + form);
+        if (!graph_output(cat->outputs[0]) || gi.nreaders(cat->outputs[0]) != 2)
+            miss(who + "its result " + cat->outputs[0] + " must be a graph output (present.*) and be read by this attention alone besides; it has " + std::to_string(gi.nreaders(cat->outputs[0])) + " readers");
+        taken.push_back(cat);
+        past = i0->name;
+        present = cat->outputs[0];
+        cat_name = nm_of(cat);
+        return cat->inputs[1];
     };
     const OnnxNode* qk = gi.producer(peel(scores));
     {
@@ -2229,13 +2295,27 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
     int64_t gk = 0, gv = 0;                        // repeat_kv's group size on k and on v (0: no repeat_kv)
     if (perm_is(kt, {0, 2, 3, 1})) k_rs = gi.producer(kt->inputs[0]);
     else if (perm_is(kt, {0, 1, 3, 2})) {
-        const OnnxNode* k2 = gi.producer(unrope(unrepeat(kt->inputs[0], "k", gk), "k", rk));
+        const std::string k_cat = unrepeat(kt->inputs[0], "k", gk);
+        const std::string k_new = uncat(k_cat, "k", am.past_k, am.present_k, am.cat_k);
+        // a prefill with a cache: the rotated k (without rope: its Transpose) is also the graph output present.*.key
+        if (am.past_k.empty() && graph_output(k_new)) am.present_k = k_new;
+        const OnnxNode* k2 = gi.producer(unrope(k_new, "k", rk));
         if (!perm_is(k2, {0, 2, 1, 3})) miss("the second operand of MatMul " + nm_of(qk) + " is neither Transpose(Transpose(k, [0,2,1,3]), [0,1,3,2]) nor Transpose(k, [0,2,3,1])");
         taken.push_back(k2);
         k_rs = gi.producer(k2->inputs[0]);
     } else miss("the second operand of MatMul " + nm_of(qk) + " is neither Transpose(Transpose(k, [0,2,1,3]), [0,1,3,2]) nor Transpose(k, [0,2,3,1])");
-    const OnnxNode* vt = gi.producer(unrepeat(pv->inputs[1], "v", gv));
+    const std::string v_new = uncat(unrepeat(pv->inputs[1], "v", gv), "v", am.past_v, am.present_v, am.cat_v);
+    if (am.past_v.empty() && graph_output(v_new)) am.present_v = v_new;
+    const OnnxNode* vt = gi.producer(v_new);
     if (!perm_is(vt, {0, 2, 1, 3})) miss("the second operand of MatMul " + nm_of(pv) + " is not Transpose(v, perm [0,2,1,3])");
+    if (am.past_k.empty() != am.past_v.empty())
+        miss(std::string("only ") + (am.past_k.empty() ? "v" : "k") + " has a cache (Concat " + (am.past_k.empty() ? am.cat_v : am.cat_k) + "); k and v must both be Concat(past, ., axis 2)");
+    if (am.present_k.empty() != am.present_v.empty())
+        miss(std::string("only ") + (am.present_k.empty() ? am.present_v : am.present_k) + " is a graph output; present key and present value come as a pair");
+    if (rq.on && rq.pos != rk.pos)
+        miss("the positions of k (Add " + rk.name + ": " + (rk.pos.empty() ? "constant" : rk.pos) + ") are not the positions of q (Add " + rq.name + ": " + (rq.pos.empty() ? "constant" : rq.pos) + ")");
+    if (rq.on && !rq.pos.empty() && am.past_k.empty())
+        miss("the rope tables (Add " + rq.name + ") are gathered by the graph input " + rq.pos + " without a cache; run-time positions are supported in a decode step (Concat(past, k, axis 2)) only");
     if (rq.on != rk.on) miss(std::string("only ") + (rq.on ? "q" : "k") + " passes a rotary embedding (Add " + (rq.on ? rq.name : rk.name) + "); q and k must both be rotated");
     if (rq.on) {
         if (rq.rows != rk.rows || rq.hd != rk.hd || rq.cos != rk.cos) miss("the cos table of q (Add " + rq.name + ") is not the cos table of k (Add " + rk.name + "), element for element");
@@ -2312,6 +2392,9 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         if (add[s]) taken.push_back(add[s]);
         taken.push_back(rs[s]);
     }
+    if (fused && !am.past_k.empty())
+        miss("a cache (Concat " + am.cat_k + ") behind the Split of one qkv Linear (GPT-2's spelling) is not supported; the separate q / k / v Linears of a Llama-class graph are");
+    if (fused && !am.present_k.empty()) miss("the graph output " + am.present_k + " behind the Split of one qkv Linear (GPT-2's spelling) is not supported");
     if (fused && (rq.on || gk > 0)) miss("a rotary embedding or repeat_kv behind the Split of one qkv Linear is not supported (the separate q / k / v Linears are)");
     if (rq.on && rq.hd != shape4[3]) miss("the rope tables (Add " + rq.name + ") are " + std::to_string(rq.hd) + " wide, the heads " + std::to_string(shape4[3]));
     const int64_t axis = sm.attr_i("axis", -1);
@@ -2322,10 +2405,11 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
     const OnnxTensor* s3 = orr && orr->op == "Reshape" && orr->inputs.size() == 2 ? gi.cst(orr->inputs[1]) : nullptr;
     if (!s3 || s3->i.size() != 3) miss("the transposed result is not read by Reshape(., [N, L, D]) alone");
     // (a rotated value has three readers, its product with cos and the two Slices of rotate_half: the rotary match counted them)
+    const bool prefill_present = am.past_k.empty() && !am.present_k.empty();      // (a present output of a prefill is one more reader of k's and v's value)
     for (const OnnxNode* p : {qk, qt, kt, vt, pv, ot, &sm})
-        if (gi.nreaders(p->outputs[0]) != (rq.on && p == qt ? 3 : 1)) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
+        if (gi.nreaders(p->outputs[0]) != (rq.on && p == qt ? 3 : 1) + (prefill_present && p == vt ? 1 : 0)) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
     for (const OnnxNode* p : taken)
-        if ((p->op == "Mul" || p->op == "Div" || p->op == "Transpose") && gi.nreaders(p->outputs[0]) != (rk.on && perm_is(p, {0, 2, 1, 3}) ? 3 : 1)) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
+        if ((p->op == "Mul" || p->op == "Div" || p->op == "Transpose") && gi.nreaders(p->outputs[0]) != (rk.on && perm_is(p, {0, 2, 1, 3}) ? 3 : 1) + (prefill_present && p->outputs[0] == am.present_k ? 1 : 0)) miss("the intermediate " + p->outputs[0] + " has " + std::to_string(gi.nreaders(p->outputs[0])) + " readers, not 1");
     taken.insert(taken.end(), {qk, qt, kt, vt, pv, ot, orr, &sm});
     if (fused) {
         head = sp;
@@ -2363,6 +2447,7 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         am.rope_sin = rq.sin;
         am.rope_rows = rq.rows;
         am.rope_name = rq.name;
+        am.rope_pos = rq.pos;
     }
     // the head: the first of the three MatMuls in graph order (x is defined there)
     for (const OnnxNode& on : m.nodes) if (&on == mm[0] || &on == mm[1] || &on == mm[2]) { head = &on; break; }
@@ -2508,21 +2593,62 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     const int64_t D = am.heads * am.head_dim, Hkv = am.kv_heads > 0 ? am.kv_heads : am.heads;
     if (X.c != D + 2 * Hkv * am.head_dim)
         miss("the qkv rows have " + std::to_string(X.c) + " columns, not " + (Hkv == am.heads ? "3 * H * hd = " : "(H + 2 Hkv) * hd = ") + std::to_string(D + 2 * Hkv * am.head_dim));
+    // the cache of a decode step: the past inputs [N, Hkv, P, hd] of this step, one new token
+    const bool decode = !am.past_k.empty();
+    int64_t P = 0;
+    if (decode) {
+        const Val &PK = L.vals[L.get_val(am.past_k)], &PV = L.vals[L.get_val(am.past_v)];
+        auto dims_of = [](const Val& v) { return "[" + std::to_string(v.n) + ", " + std::to_string(v.c) + ", " + std::to_string(v.h) + ", " + std::to_string(v.w) + "]"; };
+        if (PK.h != PV.h) miss("the K and V pasts differ in their rows P: " + am.past_k + " is " + dims_of(PK) + ", " + am.past_v + " is " + dims_of(PV));
+        for (const Val* v : {&PK, &PV})
+            if (v->n != X.n || v->c != Hkv || v->w != am.head_dim)
+                miss("the past input " + v->name + " is " + dims_of(*v) + ", not [N, Hkv, P, hd] = [" + std::to_string(X.n) + ", " + std::to_string(Hkv) + ", P, " + std::to_string(am.head_dim) + "] of this step");
+        P = PK.h;
+        if (X.w != 1)
+            miss("a past (Concat " + am.cat_k + ") with Lq = " + std::to_string(X.w) + " new tokens (chunked prefill into a cache) is not supported; a decode step has one new token, Lq = 1");
+        if (am.causal) miss("a causal mask together with a past (Concat " + am.cat_k + ") is not supported; one query attends to every cached key the key mask admits");
+    }
+    const int64_t Lk = X.w + P;                    // keys of a query
     // repeat_kv's constant shapes: Expand to [N, Hkv, g, L, hd] (a 1 keeps the dim), Reshape to [N, H, L, hd]
     for (size_t k = 0; k < am.rep_expand.size(); ++k) {
         const std::vector<int64_t>&e = am.rep_expand[k], &r = am.rep_reshape[k];
-        const int64_t want5[5] = {X.n, Hkv, e[2], X.w, am.head_dim}, want4[4] = {X.n, am.heads, X.w, am.head_dim};
+        const int64_t want5[5] = {X.n, Hkv, e[2], Lk, am.head_dim}, want4[4] = {X.n, am.heads, Lk, am.head_dim};
         bool ok = e[2] * Hkv == am.heads;
         for (int d = 0; d < 5; ++d) ok = ok && (e[size_t(d)] == want5[d] || (d != 2 && e[size_t(d)] == 1));
         int neg = 0;
         for (int d = 0; d < 4; ++d) { neg += r[size_t(d)] == -1; ok = ok && (r[size_t(d)] == want4[d] || r[size_t(d)] == -1 || (d == 0 && r[0] == 0)); }
-        if (!ok || neg > 1) miss("repeat_kv does not expand to [N, Hkv, g, L, hd] = [" + std::to_string(X.n) + ", " + std::to_string(Hkv) + ", " + std::to_string(am.heads / Hkv) + ", " + std::to_string(X.w) + ", " +
+        if (!ok || neg > 1) miss("repeat_kv does not expand to [N, Hkv, g, L, hd] = [" + std::to_string(X.n) + ", " + std::to_string(Hkv) + ", " + std::to_string(am.heads / Hkv) + ", " + std::to_string(Lk) + ", " +
                                  std::to_string(am.head_dim) + "] and reshape to [N, H, L, hd]");
     }
     if (!am.split && !am.fused && ((am.shape5[0] != 0 && am.shape5[0] != X.n) || (am.shape5[1] != -1 && am.shape5[1] != 0 && am.shape5[1] != X.w))) miss("the Reshape to [N, L, 3, H, hd] does not keep N and L");
     if ((am.shape3[0] != 0 && am.shape3[0] != X.n) || (am.shape3[1] != -1 && am.shape3[1] != 0 && am.shape3[1] != X.w) || (am.shape3[2] != -1 && am.shape3[2] != D))
         miss("the last Reshape is not to [N, L, H * hd]");
     if (am.shape3[1] == -1 && am.shape3[2] == -1) miss("the last Reshape is not to [N, L, H * hd]");
+    // the cache outputs: one kv_append node each for K and V, in front of the attention node (EmitSteps makes one step of the pair)
+    int pres[2] = {-1, -1}, pos_val = -1;
+    if (am.rope && !am.rope_pos.empty()) pos_val = L.get_val(am.rope_pos);
+    if (!am.present_k.empty()) {
+        for (int which = 0; which < 2; ++which) {
+            LNode a;
+            a.kind = L_KVAPPEND;
+            a.name = am.name + (which ? "/kv_append_v" : "/kv_append_k");
+            a.in = {x};
+            a.heads = int(am.heads);
+            a.head_dim = int(am.head_dim);
+            a.kv_heads = int(Hkv);
+            a.kv_v = which == 1;
+            a.past_len = int(P);
+            if (decode) { a.past_in = int(a.in.size()); a.in.push_back(L.get_val(which ? am.past_v : am.past_k)); }
+            if (which == 0 && am.rope) {
+                a.w = am.rope_cos;
+                a.w2 = am.rope_sin;
+                a.rope_rows = am.rope_rows;
+                if (pos_val >= 0) { a.pos_in = int(a.in.size()); a.in.push_back(pos_val); }
+            }
+            push_node(std::move(a), which ? am.present_v : am.present_k, {X.n, Hkv, Lk, am.head_dim}, false);
+            pres[which] = L.get_val(which ? am.present_v : am.present_k);
+        }
+    }
     LNode n;
     n.kind = L_ATTENTION;
     n.name = am.name;
@@ -2532,7 +2658,10 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     n.attn_scale = am.scale;
     if (!am.mask.empty()) {
         const int mv = L.get_val(am.mask);
-        if (L.vals[mv].n != X.n || L.vals[mv].c != X.w)
+        if (decode && (L.vals[mv].n != X.n || L.vals[mv].c != Lk))
+            miss("the key mask " + am.mask + " is [" + std::to_string(L.vals[mv].n) + ", " + std::to_string(L.vals[mv].c) + "]; its width must be P + 1 = " + std::to_string(Lk) + " (the " + std::to_string(P) +
+                 " cached rows and the new key) for [N = " + std::to_string(X.n) + "] images");
+        if (!decode && (L.vals[mv].n != X.n || L.vals[mv].c != X.w))
             miss("the key mask " + am.mask + " is [" + std::to_string(L.vals[mv].n) + ", " + std::to_string(L.vals[mv].c) + "], the tokens [" + std::to_string(X.n) + ", " + std::to_string(X.w) + ", .]");
         n.in.push_back(mv);
         n.key_mask = true;
@@ -2540,11 +2669,19 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     }
     n.kv_heads = int(Hkv);
     if (am.rope) {
-        if (!am.mask.empty()) miss("a rotary embedding (Add " + am.rope_name + ") together with a key mask (attention_mask) is not supported");
-        if (am.rope_rows != X.w)
+        if (!am.mask.empty() && !decode) miss("a rotary embedding (Add " + am.rope_name + ") together with a key mask (attention_mask) is not supported");
+        if (am.rope_pos.empty() && am.rope_rows != X.w)      // (run-time positions: the whole [max_pos, hd] table, any number of rows)
             miss("the rope tables (Add " + am.rope_name + ") have " + std::to_string(am.rope_rows) + " rows after slicing, the sequence has " + std::to_string(X.w) + " tokens (table rows != L)");
         n.w = am.rope_cos;
         n.w2 = am.rope_sin;
+        n.rope_rows = am.rope_rows;
+    }
+    if (decode) {
+        n.past_len = int(P);
+        n.present_in = int(n.in.size());
+        n.in.push_back(pres[0]);
+        n.in.push_back(pres[1]);
+        if (pos_val >= 0) { n.pos_in = int(n.in.size()); n.in.push_back(pos_val); }
     }
     if (am.causal) {
         if (am.causal_len != X.w) miss("its causal mask is [1, 1, " + std::to_string(am.causal_len) + ", " + std::to_string(am.causal_len) + "], the sequence has " + std::to_string(X.w) + " tokens");
@@ -2951,7 +3088,7 @@ void Planner::MatchEmbed() {
         return true;
     };
     for (const OnnxNode& g : m.nodes) {
-        if (embed_skip.count(&g) || !table_gather(g)) continue;
+        if (embed_skip.count(&g) || attn_skip.count(&g) || !table_gather(g)) continue;      // (attn_skip: a rope table gathered by position_ids)
         const std::string gname = g.name.empty() ? g.outputs[0] : g.name;
         // down to the LayerNormalization: Adds only, every value read once
         std::string cur = g.outputs[0];
@@ -3830,6 +3967,10 @@ void Planner::StageNchwInputs() {
         for (int ci : L.consumers(int(v)))
             if (L.nodes[ci].kind != L_CONV || L.nodes[ci].transposed || L.nodes[ci].in[0] != int(v) || L.nodes[ci].res == int(v)) all_conv = false;
         if (all_conv && !L.vals[v].is_output) continue;
+        // the cache of a decode step is read in place, in the ABI's own order [N][Hkv][P][hd]: no staging copy
+        bool all_kv = !L.consumers(int(v)).empty() && !L.vals[v].is_output;
+        for (int ci : L.consumers(int(v))) if (L.nodes[ci].kind != L_KVAPPEND || L.nodes[ci].in[0] == int(v)) all_kv = false;
+        if (all_kv) continue;
         LNode cp;
         cp.kind = L_COPY;
         cp.name = "nchw_to_nhwc(" + L.vals[v].name + ")";
@@ -3859,6 +4000,12 @@ void Planner::DensifyOutputs() {
         const int pr = L.vals[v].producer;
         if (spatial && !consumed && !L.vals[v].is_input && pr >= 0 && L.nodes[size_t(pr)].kind == L_RESIZE && !L.nodes[size_t(pr)].dead &&
             std::find(out_vals.begin(), out_vals.end(), v) == out_vals.end()) {
+            L.vals[v].input_nchw = true;           // reused flag: dense NCHW layout
+            out_vals.push_back(v);
+            continue;
+        }
+        // a kv_append node writes the dense fp32 [N][Hkv][rows][hd] output itself; a decode step's attention reads it there
+        if (!L.vals[v].is_input && pr >= 0 && L.nodes[size_t(pr)].kind == L_KVAPPEND && std::find(out_vals.begin(), out_vals.end(), v) == out_vals.end()) {
             L.vals[v].input_nchw = true;           // reused flag: dense NCHW layout
             out_vals.push_back(v);
             continue;
@@ -4527,12 +4674,70 @@ void Planner::EmitTokenAssemble(const LNode& n, Step& s) {
 // at least kAttnStreamMinTokens tokens; else the generic kernel).  A causal step: AttnCausalDefaultTile (tile 1, else tile 3, the chunk kernel, else
 // tile 2's causal form on a wide head with at least kAttnStreamCausalMinTokens tokens, else the generic kernel).  IE_FORCE_TILE as for layer norm but over tiles 0 and 1 only; IE_ATTN_TILE pins the attention steps alone, tiles 2 and 3
 // included (an ineligible value is the generic kernel); a non-causal step reaches tile 3 this way only
+// kv_append (kernels_decode.hip): the K half of a pair; EmitSteps adds the V half.  The rope tables go into the blob once per model (rope_blob): every
+// layer gathers the same ones
+void Planner::EmitKvAppend(const LNode& n, Step& s) {
+    if (s.in.f8) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::KvAppend;
+    s.heads = n.heads;
+    s.head_dim = n.head_dim;
+    s.kv_heads = n.kv_heads;
+    s.past_len = n.past_len;
+    s.present_k = s.out;
+    if (!s.out.nchw || s.out.f16) fail("internal planner error: the present output of node " + n.name + " is not a dense fp32 graph output");
+    if (n.past_in >= 0) s.past_k = view_of(n.in[size_t(n.past_in)]);
+    if (!n.w.empty()) {
+        auto table = [&](const std::vector<float>& t) {
+            const auto it = rope_blob.find(t);
+            return it != rope_blob.end() ? it->second : (rope_blob[t] = push_vec(t));
+        };
+        s.rope = true;
+        s.w_off = table(n.w);
+        s.w2_off = table(n.w2);
+        s.rope_rows = n.rope_rows;
+        if (n.pos_in >= 0) {
+            s.pos = view_of(n.in[size_t(n.pos_in)]);
+            if (!s.pos.i64) fail("internal planner error: the positions of node " + n.name + " are not an int64 view");
+        }
+    }
+    s.bytes = vbytes(s.present_k) + (n.past_in >= 0 ? vbytes(s.past_k) : 0.0) + double(s.in.n) * double(s.in.w) * 2.0 * double(n.kv_heads) * double(n.head_dim) * double(s.in.esize());
+}
+
 void Planner::EmitAttention(const LNode& n, Step& s) {
     if (s.in.f8 || s.out.f8) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
     s.kind = StepKind::Attention;
     s.heads = n.heads;
     s.head_dim = n.head_dim;
     s.attn_scale = float(n.attn_scale);
+    if (n.past_len > 0) {
+        // a decode step: one query per head over the past_len + 1 rows of `present`.  Tile 4 where kernels.h DecodeFastFits says so, else the parts;
+        // IE_ATTN_TILE = 0 | 4 pins it (an ineligible 4 is the parts), IE_ATTN_SPLITS the key splits of tile 4.  No other tile takes a past
+        s.past_len = n.past_len;
+        s.kv_heads = n.kv_heads > 0 ? n.kv_heads : n.heads;
+        s.present_k = view_of(n.in[size_t(n.present_in)]);
+        s.present_v = view_of(n.in[size_t(n.present_in) + 1]);
+        if (n.key_mask) {
+            s.in2 = view_of(n.in[1]);
+            s.has_in2 = true;
+            s.key_mask = true;
+            s.mask_value = n.mask_value;
+            if (!s.in2.i64) fail("internal planner error: the key mask of node " + n.name + " is not an int64 view");
+        }
+        s.rope = !n.w.empty();
+        const int64_t keys = int64_t(n.past_len) + 1;
+        const bool fits = !s.in.nchw && !s.out.nchw && DecodeFastFits(s.head_dim, s.heads, s.kv_heads, n.key_mask, n.mask_value);
+        s.tile = fits && keys >= kAttnDecodeMinKeys ? kAttnDecodeTile : 0;
+        if (const char* e = env.get("IE_ATTN_TILE"); e && (std::atoi(e) == 0 || std::atoi(e) == kAttnDecodeTile)) s.tile = std::atoi(e) == kAttnDecodeTile && fits ? kAttnDecodeTile : 0;
+        if (ForcedTile(kNumAttnForcedTiles) >= 0) s.tile = 0;      // (IE_FORCE_TILE pins generic kernels everywhere: a decode step's are its parts)
+        if (s.tile == kAttnDecodeTile) {
+            s.splits =DecodeDefaultSplits(s.in.n, s.kv_heads, keys, s.head_dim);
+            if (const int f = env.integer("IE_ATTN_SPLITS", 0); f >= 1) s.splits = int(std::min<int64_t>(std::min(f, kDecodeMaxSplits), (keys + DecodeKeyTile(s.head_dim) - 1) / DecodeKeyTile(s.head_dim)));
+            plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, DecodeWorkspaceFloats(s.in.n, s.heads, s.head_dim, s.splits));
+        }
+        s.flops = 4.0 * double(s.in.n) * double(s.heads) * double(keys) * double(s.head_dim);
+        s.bytes = vbytes(s.in) + vbytes(s.out) + (n.key_mask ? vbytes(s.in2) : 0.0);      // (the cache traffic is counted on the kv_append part)
+        return;
+    }
     if (n.key_mask) {
         s.in2 = view_of(n.in[1]);
         s.has_in2 = true;
@@ -4612,6 +4817,18 @@ void Planner::EmitSteps() {
         const LNode& n = L.nodes[idx];
         if (n.kind == L_ALIAS) continue;
         if (n.kind == L_CONCAT) { EmitConcatCopies(n); continue; }
+        if (n.kind == L_KVAPPEND && n.kv_v) {          // the V half of a kv_append pair: one step with the K half in front of it
+            if (plan.steps.empty() || plan.steps.back().kind != StepKind::KvAppend || plan.steps.back().present_v.buf >= 0) fail("internal planner error: kv_append pair of node " + n.name);
+            Step& k = plan.steps.back();
+            k.name += "+" + n.name;
+            k.present_v = view_of(n.out);
+            if (n.past_in >= 0) k.past_v = view_of(n.in[size_t(n.past_in)]);
+            const double b = vbytes(k.present_v) + (n.past_in >= 0 ? vbytes(k.past_v) : 0.0);
+            k.bytes += b;
+            plan.total_bytes += b;
+            writer[{int64_t(k.present_v.buf), k.present_v.c_off, k.present_v.c}] = int(plan.steps.size()) - 1;
+            continue;
+        }
         Step s;
         s.name = n.name;
         s.in = view_of(n.in[0]);
@@ -4632,6 +4849,7 @@ void Planner::EmitSteps() {
             case L_LAYERNORM: EmitLayerNorm(n, s); break;
             case L_TOKASM: EmitTokenAssemble(n, s); break;
             case L_ATTENTION: EmitAttention(n, s); break;
+            case L_KVAPPEND: EmitKvAppend(n, s); break;
             case L_WATTN: EmitWindowAttention(n, s); break;
             case L_PATCHMERGE: EmitPatchMerge(n, s); break;
             case L_EMBED: EmitEmbed(n, s); break;
@@ -4645,6 +4863,21 @@ void Planner::EmitSteps() {
         }
         if (s.kind != StepKind::Conv && s.kind != StepKind::Copy && s.in.nchw)
             fail("internal planner error: NCHW view reached a non-conv step");
+        if (s.kind == StepKind::Attention && s.past_len > 0) {
+            // a decode step: the kv_append step in front of it becomes its first part, the attention over `present` its second (tile 0 = the parts)
+            Step kv = std::move(plan.steps.back());
+            plan.steps.pop_back();
+            s.past_k = kv.past_k; s.past_v = kv.past_v;
+            s.w_off = kv.w_off; s.w2_off = kv.w2_off; s.rope_rows = kv.rope_rows; s.pos = kv.pos;
+            s.name = kv.name + "+" + s.name;
+            Step at = s;
+            at.name = n.name;
+            at.tile = 0;
+            at.splits = 0;
+            s.parts = {std::move(kv), std::move(at)};
+            writer[{int64_t(s.present_k.buf), s.present_k.c_off, s.present_k.c}] = int(plan.steps.size());
+            writer[{int64_t(s.present_v.buf), s.present_v.c_off, s.present_v.c}] = int(plan.steps.size());
+        }
         s.idx = int(plan.steps.size());
         s.in_src = src_of(s.in);
         if (s.has_in2) s.in2_src = src_of(s.in2);
@@ -5031,7 +5264,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed", "group_norm"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed", "group_norm", "kv_append"};
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
@@ -5100,6 +5333,18 @@ std::string PlanToJson(const Plan& p) {
         if (s.kind == StepKind::Attention && s.causal) o << ",\"causal\":true";      // (causal attention steps only)
         if (s.kind == StepKind::Attention && s.kv_heads > 0 && s.kv_heads != s.heads) o << ",\"kv_heads\":" << s.kv_heads;      // (grouped-query steps only)
         if (s.kind == StepKind::Attention && s.rope) o << ",\"rope\":true,\"w2_off\":" << s.w2_off;      // (rotary steps only)
+        if (s.kind == StepKind::KvAppend || (s.kind == StepKind::Attention && s.past_len > 0)) {      // (the steps of a graph with a cache only: each field where set)
+            if (s.kind == StepKind::KvAppend) {
+                o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"kv_heads\":" << s.kv_heads;
+                if (s.rope) o << ",\"rope\":true,\"w2_off\":" << s.w2_off;
+            }
+            if (s.past_len > 0) o << ",\"past_len\":" << s.past_len;
+            if (s.rope) o << ",\"rope_rows\":" << s.rope_rows;
+            if (s.splits > 0) o << ",\"splits\":" << s.splits;
+            const std::pair<const char*, const View*> views[] = {{"past_k", &s.past_k}, {"past_v", &s.past_v}, {"present_k", &s.present_k}, {"present_v", &s.present_v}, {"positions", &s.pos}};
+            for (const auto& kv : views)
+                if (kv.second->buf >= 0) { o << ",\"" << kv.first << "\":"; json_view(o, *kv.second); }
+        }
         if (s.kind == StepKind::WindowAttention)      // (window-attention steps only)
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"window\":[" << s.win_h << "," << s.win_w << "],\"shift\":["
               << s.shift_h << "," << s.shift_w << "],\"masked\":" << (s.masked ? "true" : "false") << ",\"tile\":" << s.tile;

@@ -39,7 +39,7 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12, GroupNorm = 13 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12, GroupNorm = 13, KvAppend = 14 };
 
 // Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
 enum class ResizeMode : int { Nearest = 0, Linear = 1 };
@@ -146,6 +146,20 @@ struct Step {
     // w2_off = the cos / sin tables [L][head_dim], fp32 in every precision
     int kv_heads = 0;
     bool rope = false;
+    // KV cache (kernels_decode.hip; generation with Llama-class graphs).  Cache tensors are fp32 in every precision and dense [N][kv_heads][rows][head_dim],
+    // the ABI's order of a rank-4 input / output: past_k / past_v = the `past_key_values.*` graph inputs (rows = past_len), read in place;
+    // present_k / present_v = the `present.*` graph outputs (rows = past_len + in.w).  A view with buf -1 is absent.
+    // KvAppend: in = the qkv tokens [N, 1, L, (H + 2 Hkv) hd]; present rows < past_len are a copy of the past, row past_len + l is k of token l after the
+    // rotary embedding (rope: w_off / w2_off = the cos / sin tables [rope_rows][head_dim]) resp. v of token l, converted to fp32.  The table row of
+    // token l is pos[n] + l where pos (an INT64 graph input [N, 1]) is present, else l.  out repeats present_k.
+    // Attention with past_len > 0 (a decode step, in.w = 1): the one query of every head attends to the past_len + 1 rows of present_k / present_v; q is
+    // rotated at the same table row as the new k, cached keys are taken as they are; in2 = the key mask [N, past_len + 1].  parts = {the KvAppend step,
+    // this step without parts}: tile 0 runs the parts (kv_append_kernel, attention_decode_generic_kernel), tile 4 is one launch that copies, appends
+    // and attends (attention_decode_kernel) over `splits` key splits per (image, K / V head), plus the combine launch where splits > 1
+    View past_k, past_v, present_k, present_v, pos;
+    int past_len = 0;
+    int splits = 0;
+    int64_t rope_rows = 0;
     // WindowAttention (kernels_wattn.hip): in = the qkv map [N, H, W, 3 D], out = [N, H, W, D]; attention inside the win_h x win_w windows of the map
     // rolled by (-shift_h, -shift_w), every result on its query's own pixel; w_off = the relative-position bias, w2_off = the shift mask (masked
     // steps only), both packed as kernels.h WinAttnArgs describes, fp32 in every precision; heads, head_dim, attn_scale, tile as for Attention

@@ -1366,9 +1366,11 @@ def rope_constants(gb: GraphBuilder, seq: int, hd: int, tag: str, *, form: str =
     return out[0], out[1]
 
 
-def rotate_half_rope(gb: GraphBuilder, t: str, cos: str, sin: str, hd: int, tag: str, *, swap: bool = False, order: str = "neg_first") -> str:
+def rotate_half_rope(gb: GraphBuilder, t: str, cos: str, sin: str, hd: int, tag: str, *, swap: bool = False, order: str = "neg_first",
+                     out: str | None = None) -> str:
     """apply_rotary_pos_emb on t [N, H, L, hd]: Add(Mul(t, cos), Mul(Concat(Neg(Slice(t, hd/2:)), Slice(t, :hd/2), axis -1), sin)); swap: every Mul /
-    Add with its operands the other way round.  order "x1_first": the Concat as (x1, -x2), which is NOT rotate_half (tests: a refusal)"""
+    Add with its operands the other way round.  order "x1_first": the Concat as (x1, -x2), which is NOT rotate_half (tests: a refusal).  out: the
+    result's name"""
     i64 = lambda name, v: gb.init(f"{tag}_{name}", np.array(v, np.int64))  # noqa: E731
     two = lambda a, b: [b, a] if swap else [a, b]  # noqa: E731
     x1 = gb.simple("Slice", [t, i64("lo_starts", [0]), i64("lo_ends", [hd // 2]), i64("lo_axes", [-1]), i64("lo_steps", [1])])
@@ -1379,18 +1381,39 @@ def rotate_half_rope(gb: GraphBuilder, t: str, cos: str, sin: str, hd: int, tag:
         rot = gb.simple("Concat", [x1, gb.simple("Neg", [x2])], [pb.attr_int("axis", -1)])
     else:
         raise ValueError(order)
-    return gb.simple("Add", two(gb.simple("Mul", two(t, cos)), gb.simple("Mul", two(rot, sin))))
+    return gb.simple("Add", two(gb.simple("Mul", two(t, cos)), gb.simple("Mul", two(rot, sin))), out=out)
+
+
+def rope_gathered(gb: GraphBuilder, hd: int, tag: str, *, max_pos: int, theta: float = 10000.0, tables: tuple[np.ndarray, np.ndarray] | None = None,
+                  positions: str = "position_ids") -> tuple[str, str]:
+    """cos and sin of a decode step whose positions are run-time data: Unsqueeze(Gather(table [max_pos, hd], positions [N, Lq], axis 0), axes [1]),
+    which broadcasts as [N, 1, Lq, hd] (LlamaRotaryEmbedding on position_ids, as the exporter lowers it).  tables: (cos, sin) [max_pos, hd] given
+    instead of rope_tables"""
+    cs = tables if tables is not None else rope_tables(max_pos, hd, theta)
+    out = []
+    for which, t in zip(("cos", "sin"), cs):
+        name = gb.init(f"{tag}_{which}_table", np.ascontiguousarray(t, np.float32))
+        g = gb.simple("Gather", [name, positions], [pb.attr_int("axis", 0)])
+        out.append(gb.simple("Unsqueeze", [g, gb.init(f"{tag}_{which}_axes1", np.array([1], np.int64))]))
+    return out[0], out[1]
 
 
 def llama_attention(gb: GraphBuilder, x: str, seq: int, dim: int, heads: int, kv_heads: int, tag: str, *, batch: int = 1, rope: tuple[str, str] | None = None,
                     rope_k: tuple[str, str] | None = None, repeat: str = "auto", mask: str | None = "add", scale: str = "mul", bias: bool = False,
-                    swap: bool = False, linear=None, rope_order: str = "neg_first", hd: int | None = None) -> str:
+                    swap: bool = False, linear=None, rope_order: str = "neg_first", hd: int | None = None, past: tuple[str, str] | None = None,
+                    past_len: int = 0, present: tuple[str, str] | None = None, key_mask: str | None = None, concat_order: str = "past_first",
+                    present_after_repeat: bool = False) -> str:
     """LlamaAttention (eager): q / k / v Linears without a bias (dim -> H hd, Hkv hd, Hkv hd) -> Reshape [N, L, H | Hkv, hd] -> Transpose [0,2,1,3] ->
     rotary embedding on q and k (rope = the (cos, sin) names of rope_constants; rope_k: other names for k; None: no rotation) -> repeat_kv on k and v
     (Unsqueeze(axis 2) -> Expand [N, Hkv, g, L, hd] -> Reshape [N, H, L, hd]; repeat "auto": where g > 1, "always": also the g = 1 no-op, "never")
     -> MatMul(q, Transpose(k, [0,1,3,2])) -> Mul(1 / sqrt hd) | Div(sqrt hd) -> the causal mask ("add" the additive triangular constant, "where_const",
     None) -> Softmax -> MatMul(., v) -> Transpose [0,2,1,3] -> Reshape [N, L, H hd].  x: the tokens, or with `linear` = a function (x, name, cout)
-    the q / k / v rows come from it (tests hand the kernel known operands that way)"""
+    the q / k / v rows come from it (tests hand the kernel known operands that way).
+    With a cache (modeling_llama.py's eager attention with DynamicCache.update, as the exporter lowers it): past = the names of the cached K / V inputs
+    [N, Hkv, past_len, hd]: K = Concat(past k, rope(k), axis 2) and V = Concat(past v, v, axis 2) in front of repeat_kv, which then expands
+    past_len + seq keys; present = the names these values (without a past: rope(k) and the transposed v) get, for the graph's `present.*` outputs;
+    key_mask = the name of the additive [N, 1, 1, past_len + seq] mask (bert_extended_mask) put on the scores in place of the triangular constant.
+    concat_order "new_first" and present_after_repeat are spellings the planner refuses (tests)"""
     hd = hd or dim // heads
     g = heads // max(kv_heads, 1)
     lin = linear or (lambda y, name, cout: gb.linear(y, dim, cout, name=name, bias=bias))
@@ -1398,16 +1421,25 @@ def llama_attention(gb: GraphBuilder, x: str, seq: int, dim: int, heads: int, kv
     q = gb.simple("Reshape", [lin(x, tag + "_q_proj", heads * hd), i64("shape_q", [0, -1, heads, hd])])
     k = gb.simple("Reshape", [lin(x, tag + "_k_proj", kv_heads * hd), i64("shape_k", [0, -1, kv_heads, hd])])
     v = gb.simple("Reshape", [lin(x, tag + "_v_proj", kv_heads * hd), i64("shape_v", [0, -1, kv_heads, hd])])
-    q, k, v = (gb.transpose(t, (0, 2, 1, 3)) for t in (q, k, v))
+    # (a prefill's present: the rotated k -- without rope its Transpose -- and the transposed v carry the output names themselves)
+    pk, pv = present if present is not None and past is None and not present_after_repeat else (None, None)
+    tr = lambda t, out=None: gb.simple("Transpose", [t], [pb.attr_ints("perm", [0, 2, 1, 3])], out=out)  # noqa: E731
+    q, k, v = tr(q), tr(k, None if rope is not None else pk), tr(v, pv)
     if rope is not None:
         q = rotate_half_rope(gb, q, rope[0], rope[1], hd, tag + "_rope_q", swap=swap, order=rope_order)
         kc = rope_k or rope
-        k = rotate_half_rope(gb, k, kc[0], kc[1], hd, tag + "_rope_k", swap=swap)
+        k = rotate_half_rope(gb, k, kc[0], kc[1], hd, tag + "_rope_k", swap=swap, out=pk)
+    kv_seq = seq + (past_len if past is not None else 0)
+    if past is not None:
+        names = present if present is not None and not present_after_repeat else (None, None)
+        two = (lambda a, b: [b, a]) if concat_order == "new_first" else (lambda a, b: [a, b])
+        k = gb.simple("Concat", two(past[0], k), [pb.attr_int("axis", 2)], out=names[0])
+        v = gb.simple("Concat", two(past[1], v), [pb.attr_int("axis", 2)], out=names[1])
     if repeat == "always" or (repeat == "auto" and g > 1):
         def repeat_kv(t: str, which: str) -> str:
             u = gb.simple("Unsqueeze", [t, i64(which + "_rep_axis", [2])])
-            e = gb.simple("Expand", [u, i64(which + "_rep_shape5", [batch, kv_heads, g, seq, hd])])
-            return gb.simple("Reshape", [e, i64(which + "_rep_shape4", [batch, heads, seq, hd])])
+            e = gb.simple("Expand", [u, i64(which + "_rep_shape5", [batch, kv_heads, g, kv_seq, hd])])
+            return gb.simple("Reshape", [e, i64(which + "_rep_shape4", [batch, heads, kv_seq, hd])], out=present[0 if which == "k" else 1] if present_after_repeat and present else None)
         k, v = repeat_kv(k, "k"), repeat_kv(v, "v")
     elif repeat not in ("auto", "never"):
         raise ValueError(repeat)
@@ -1418,7 +1450,9 @@ def llama_attention(gb: GraphBuilder, x: str, seq: int, dim: int, heads: int, kv
         s = gb.simple("Div", [s, gb.init(tag + "_sqrt_hd", np.array(np.sqrt(float(hd)), np.float32))])
     else:
         raise ValueError(scale)
-    if mask == "where_const":
+    if key_mask is not None:
+        s = gb.simple("Add", [s, key_mask])
+    elif mask == "where_const":
         s = gb.simple("Where", [causal_mask_constant(gb, seq, mask, seq, tag), s, gb.init(tag + "_mask_value", np.array(FLOAT32_MIN, np.float32))])
     elif mask is not None:
         s = gb.simple("Add", [s, causal_mask_constant(gb, seq, mask, seq, tag)])
@@ -1430,7 +1464,7 @@ def llama_attention(gb: GraphBuilder, x: str, seq: int, dim: int, heads: int, kv
 def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576, depth: int = 30, heads: int = 9, kv_heads: int = 3, mlp: int = 1536,
           max_pos: int = 2048, rope_theta: float = 10000.0, eps: float = 1e-5, tied: bool = True, last_hidden_state: bool = False, seed: int = 2023,
           norm: str = "pow", cast: bool = False, swap: bool = False, rope: str = "slice", repeat: str = "auto", scale: str = "mul", mask: str = "add",
-          w_scale: float | None = None, table_std: float = 1.0) -> bytes:
+          w_scale: float | None = None, table_std: float = 1.0, present: bool = False, past: int | None = None, positions: str = "input") -> bytes:
     """LlamaForCausalLM as a prefill / scoring forward (Touvron et al. 2023; the shape of Llama 2 / 3, TinyLlama, SmolLM, Mistral and the dense Qwen
     models), ids [N, seq] -> logits [N, seq, vocab], written from modeling_llama.py's eager attention and the TorchScript exporter's known lowerings,
     NOT from a real export (neither `transformers` nor ONNX Runtime is available here); checked by the float64 walk of tests/ref64.py.
@@ -1440,12 +1474,41 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
       norm / cast / swap   GraphBuilder.rmsnorm's form, its Cast nodes, its operand order (swap also turns the rope's and the gated unit's Muls)
       rope     rope_constants' form: "init" | "unsqueeze" | "slice" | "gather" ("none": the same graph without the rope nodes, which is no Llama);  repeat: llama_attention's repeat_kv ("auto" | "always" | "never")
       scale    "mul" | "div";  mask: "add" | "where_const"
-    outputs: logits, and last_hidden_state [N, seq, dim] behind the final norm (optional)"""
+    outputs: logits, and last_hidden_state [N, seq, dim] behind the final norm (optional)
+    The two halves of generation, both default off (the bytes of every graph above are then unchanged); like the prefill graph they are written from
+    modeling_llama.py's eager attention -- here with DynamicCache -- and the exporter's known lowerings, not from a real export:
+      present=True   prefill with a cache: per layer the outputs present.{i}.key (the rotated k; without rope its Transpose [0,2,1,3]) and
+                     present.{i}.value (v's Transpose), both [N, Hkv, seq, hd], the values in front of repeat_kv; the rest of the graph is unchanged
+      past=P         one decode step (seq is 1) over a cache of capacity P >= 1: inputs input_ids [N, 1], attention_mask [N, P + 1] INT64 (mask "input",
+                     which "add" means here too; None: no mask input), position_ids [N, 1] INT64 (positions "input"; "const": none, the rotation
+                     is row P of the tables in the form `rope` names) and per layer past_key_values.{i}.key / .value FLOAT [N, Hkv, P, hd].  Per layer
+                     K = Concat(past key, rope(k), axis 2), V = Concat(past value, v, axis 2), both outputs present.{i}.* [N, Hkv, P + 1, hd] and both
+                     read by repeat_kv; cos / sin = Unsqueeze(Gather(table [max_pos, hd], position_ids, axis 0), axes [1]); the mask is BERT's chain
+                     Mul(Sub(1, Cast(Unsqueeze(attention_mask, [1, 2]))), finfo.min) added to the scores [N, H, 1, P + 1] (no triangular constant at
+                     one query).  The client writes the last row of present.* into its cache at row `len`; valid rows may sit anywhere in the cache"""
     gb = GraphBuilder("llama", seed)
     hd = dim // heads
     emb = np.float32(table_std) * rng.gaussish(seed, "embed_tokens", vocab * dim).reshape(vocab, dim).astype(np.float32)
     x = gb.simple("Gather", [gb.init("embed_tokens", emb), "input_ids"], [pb.attr_int("axis", 0)])
-    cs = rope_constants(gb, seq, hd, "rotary", form=rope, max_pos=max_pos, theta=rope_theta) if rope != "none" else None      # ("none": measurements only)
+    ext = None
+    if past is not None:
+        if past < 1 or seq != 1:
+            raise ValueError("a decode graph has past >= 1 cached rows and seq = 1 new token")
+        if mask in ("add", "input"):
+            ext = bert_extended_mask(gb, unsqueeze="one")
+        elif mask is not None:
+            raise ValueError(mask)
+        if rope == "none":
+            cs = None
+        elif positions == "input":
+            cs = rope_gathered(gb, hd, "rotary", max_pos=max_pos, theta=rope_theta)
+        elif positions == "const":
+            full = rope_tables(max_pos, hd, rope_theta)
+            cs = rope_constants(gb, 1, hd, "rotary", form=rope, tables=(full[0][past:past + 1], full[1][past:past + 1]))
+        else:
+            raise ValueError(positions)
+    else:
+        cs = rope_constants(gb, seq, hd, "rotary", form=rope, max_pos=max_pos, theta=rope_theta) if rope != "none" else None      # ("none": measurements only)
     opset = 23 if norm == "op" else 18
 
     def lin(y: str, name: str, cin: int, cout: int) -> str:
@@ -1454,8 +1517,13 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
     for li in range(depth):
         tag = f"layers{li}"
         h = gb.rmsnorm(x, dim, eps=eps, form=norm, name=tag + "_input_layernorm", cast=cast, swap=swap)
-        y = llama_attention(gb, h, seq, dim, heads, kv_heads, tag + "_attn", batch=batch, rope=cs, repeat=repeat, scale=scale, mask=mask, swap=swap,
-                            linear=lambda t, name, cout: lin(t, name, dim, cout))
+        kv = {}
+        if past is not None:
+            kv = dict(past=(f"past_key_values.{li}.key", f"past_key_values.{li}.value"), past_len=past, key_mask=ext)
+        if present or past is not None:
+            kv["present"] = (f"present.{li}.key", f"present.{li}.value")
+        y = llama_attention(gb, h, seq, dim, heads, kv_heads, tag + "_attn", batch=batch, rope=cs, repeat=repeat, scale=scale, mask=None if past is not None else mask,
+                            swap=swap, linear=lambda t, name, cout: lin(t, name, dim, cout), **kv)
         x = gb.simple("Add", [x, lin(y, tag + "_o_proj", dim, dim)])
         h = gb.rmsnorm(x, dim, eps=eps, form=norm, name=tag + "_post_attention_layernorm", cast=cast, swap=swap)
         y = gb.swiglu(lin(h, tag + "_gate_proj", dim, mlp), lin(h, tag + "_up_proj", dim, mlp), swap=swap)
@@ -1464,7 +1532,17 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
     head = gb.transpose("embed_tokens", (1, 0)) if tied else gb.init("lm_head_w", (rng.gaussish(seed, "lm_head", dim * vocab).reshape(dim, vocab) * np.float32(np.sqrt(1.0 / dim))).astype(np.float32))
     gb.simple("MatMul", ["last_hidden_state", head], out="logits")
     outs = [("logits", [batch, seq, vocab])] + ([("last_hidden_state", [batch, seq, dim])] if last_hidden_state else [])
-    return gb.finish([("input_ids", [batch, seq], ONNX_INT64)], outs, opset=opset)
+    ins = [("input_ids", [batch, seq], ONNX_INT64)]
+    if present or past is not None:
+        rows = seq + (past or 0)
+        for li in range(depth):
+            outs += [(f"present.{li}.key", [batch, kv_heads, rows, hd]), (f"present.{li}.value", [batch, kv_heads, rows, hd])]
+    if past is not None:
+        ins += [("attention_mask", [batch, past + 1], ONNX_INT64)] if ext is not None else []
+        ins += [("position_ids", [batch, 1], ONNX_INT64)] if cs is not None and positions == "input" else []
+        for li in range(depth):
+            ins += [(f"past_key_values.{li}.key", [batch, kv_heads, past, hd]), (f"past_key_values.{li}.value", [batch, kv_heads, past, hd])]
+    return gb.finish(ins, outs, opset=opset)
 
 
 def llama_135m(batch: int = 1, **kw) -> bytes:
