@@ -29,7 +29,8 @@ const char* const kNames[] = {
     "IE_GN_TILE",              // 0 | 1: the tile of the group-norm steps alone (an ineligible 1 is the generic kernel), every other step as planned
     "IE_ATTN_TILE",            // 0 | 1 | 2 | 3: the tile of the attention steps alone, read when IE_FORCE_TILE did not force (an ineligible value is the generic kernel)
                                // 0 | 4: the tile of a decode step (an attention step with a past), which reaches no other tile (an ineligible 4 is its parts)
-    "IE_ATTN_SPLITS",          // n >= 1: the key splits of a decode step on tile 4 (default: kernels.h DecodeDefaultSplits)
+                               // 0 | 5: the tile of an extend step (a past and two or more new tokens), which reaches no other tile (an ineligible 5 is its parts)
+    "IE_ATTN_SPLITS",          // n >= 1: the key splits of a decode step on tile 4 (default: kernels.h DecodeDefaultSplits) and of an extend step on tile 5 (ExtendDefaultSplits)
     // ---- executor ----------------------------------------------------------------------------------------------------------------
     "IE_AUTOTUNE", "IE_TUNE_CACHE", "IE_TUNE_BATCHES", "IE_TUNE_ON_DEMAND", "IE_TUNE_HOT", "IE_TUNE_LOG",
     "IE_DISABLE_GRAPH", "IE_SPLITK_IN_LAUNCH", "IE_PIPELINE_CHUNKS", "IE_PIPELINE_HEAD", "IE_MAX_PLANS", "IE_NO_FRAG_WEIGHTS",

@@ -91,6 +91,7 @@ DeviceModel::DeviceModel(std::shared_ptr<const OnnxModel> model, int device_id, 
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsBlock();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsWs8();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsAttn();
+        if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsDecode();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsWattn();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsTrans();
     });

@@ -426,8 +426,11 @@ hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);
 //                      arithmetic: full-width fp32 tables, fp32 products) resp. v of token l, converted to fp32
 //   decode attention   new_len == 1: out[n, 0, h hd + e] = sum_j softmax_j(scale q[n, h] . K[n, h / g, j] + bias[n, j]) V[n, h / g, j, e] over the
 //                      past_len + 1 rows j of present, q rotated like the new k; bias = (1 - float(mask[n, j])) * mask_value as AttnArgs' key mask, kept finite
-// The rotation's table row of token l of image n is pos[n] + l (pos = the INT64 position_ids [N, 1]; a negative value counts from the end) or l
-// without pos, clamped into [0, rope_rows - 1] on the device: a caller that skips the host check cannot make a kernel read outside the tables.
+//   extend attention   new_len >= 2 (chunked prefill into a cache): out[n, i, h hd + e] the same sum for new token i over the rows j <= past_len + i of
+//                      present (causal inside the chunk by chunk index, whatever the positions are), q rotated at token i's own table row
+// The rotation's table row of token l of image n is the token's own id pos[n pos_sn + l] (pos = the INT64 position_ids [N, new_len]; a negative value
+// counts from the end) or l without pos, clamped into [0, rope_rows - 1] on the device: a caller that skips the host check cannot make a kernel read
+// outside the tables.
 struct DecodeArgs {
     TensorArg in, out;
     const float* past_k = nullptr;
@@ -437,13 +440,14 @@ struct DecodeArgs {
     int heads = 0, kv_heads = 0, head_dim = 0;
     int past_len = 0, new_len = 1;
     float scale = 1.f;
-    const int64_t* mask = nullptr;     // [N][past_len + 1] rows at mask + n * mask_sn, or null
+    const int64_t* mask = nullptr;     // [N][past_len + new_len] rows at mask + n * mask_sn, or null
     int64_t mask_sn = 0;
     float mask_value = 0.f;
     const float* rope_cos = nullptr;   // [rope_rows][head_dim] or null
     const float* rope_sin = nullptr;
     int64_t rope_rows = 0;
-    const int64_t* pos = nullptr;      // [N] or null
+    const int64_t* pos = nullptr;      // [N][new_len] rows at pos + n * pos_sn, or null
+    int64_t pos_sn = 1;
     int splits = 1;                    // tile 4: key splits per (image, K / V head)
     float* workspace = nullptr;        // tile 4, splits > 1: the split records
     int64_t workspace_floats = 0;
@@ -452,7 +456,8 @@ struct DecodeArgs {
 // head_dim up to kDecodeMaxHeadDim, any past_len, float or half); kAttnDecodeTile (4) = attention_decode_kernel<T, HD, G>: a workgroup = (image, K / V
 // head, key split) serves the g <= G query heads of its group, loads every cached K / V element once as 16-byte lanes, stores it into `present`,
 // appends the new row in the last split; splits > 1: attention_decode_combine_kernel adds the split records in a fixed order.  Tiles 1-3 take no
-// decode step.  DecodeKeyTile: the keys a workgroup of tile 4 loads per iteration (4 waves x 64 lanes x 4 floats / head_dim)
+// decode step.  Tile 0 of an extend step (new_len >= 2) is attention_extend_generic_kernel, one wave per (image, query head, new token) behind the
+// kv_append launch (its other tile: kAttnExtendTile below).  DecodeKeyTile: the keys a workgroup of tile 4 loads per iteration (4 waves x 64 lanes x 4 floats / head_dim)
 constexpr int kAttnDecodeTile = 4;
 constexpr int kDecodeMaxHeadDim = 512;
 constexpr int kDecodeMaxGroup = 8;
@@ -481,6 +486,35 @@ constexpr int DecodeDefaultSplits(int64_t n, int kv_heads, int64_t keys, int hd)
     if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
     return s < 1 ? 1 : int(s);
 }
+// An extend step's tiles: 0 = the generic pair above; kAttnExtendTile (5) = a kv_append launch, then attention_extend_kernel<T, HD>: a workgroup = (image,
+// K / V head, block of 128 query rows, key split) over the fp32 `present`, the g Lq query rows of the group ordered (new token, head-in-group), K / V
+// staged through LDS in chunks of kAttnChunkKeys keys (converted to half in fp16 mode) with the chunk's key biases beside them, MFMA as in tiles 1 and
+// 3; splits > 1: attention_extend_combine_kernel adds the split records in a fixed order.  No other tile takes an extend step.  head_dim 32 or 64, a
+// group of at most kDecodeMaxGroup heads, and DecodeFastFits' rule for the mask constant (a small one stays on tile 0)
+constexpr int kAttnExtendTile = 5;
+constexpr bool ExtendFastFits(int hd, int heads, int kv_heads, bool masked, float mask_value) {
+    return (hd == 32 || hd == 64) && masked && DecodeFastFits(hd, heads, kv_heads, masked, mask_value);
+}
+// LDS of tile 5: tile 3's chunk of K and V rows plus one bias per key of the chunk
+constexpr int64_t ExtendLdsBytes(int hd, bool f16) { return AttnChunkLdsBytes(hd, f16) + 4 * int64_t(kAttnChunkKeys); }
+static_assert(ExtendLdsBytes(64, false) <= kAttnLdsBudget && ExtendLdsBytes(64, true) <= kAttnLdsBudget, "tile 5's chunk fits the LDS budget");
+// floats of workspace the split records of tile 5 take: tile 4's per new token
+constexpr int64_t ExtendWorkspaceFloats(int64_t n, int heads, int hd, int splits, int64_t lq) { return DecodeWorkspaceFloats(n, heads, hd, splits) * lq; }
+// the planner's split count of tile 5: DecodeDefaultSplits' rule with groups = N * Hkv * row blocks (128 query rows each) and 32-key tiles, but for one
+// workgroup per CU of a 256-CU device, not two: a split here costs a record per query row, and the sweeps of DESIGN 3.33 have their minima lower
+constexpr int ExtendDefaultSplits(int64_t n, int kv_heads, int64_t rows, int64_t keys) {
+    const int64_t groups = n * kv_heads * ((rows + 127) / 128), want = (256 + groups - 1) / groups;
+    const int64_t tiles = (keys + 31) / 32, by_keys = keys / kDecodeMinSplitKeys;
+    int64_t s = want;
+    if (s > by_keys) s = by_keys;
+    if (s > tiles) s = tiles;
+    if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
+    return s < 1 ? 1 : int(s);
+}
+// the planner's default tile of an extend step: tile 5 from this many query rows g * Lq on, where it fits: the smallest measured count at which tile 5
+// beats the generic pair in both precisions
+constexpr int64_t kAttnExtendMinRows = 2;
+hipError_t InitKernelsDecode();          // once per process, before any capture: lets tile 5 take more than 64 KiB of LDS
 bool KvAppendEligible(const DecodeArgs& a);
 hipError_t LaunchKvAppend(const DecodeArgs& a, hipStream_t stream);
 bool AttentionDecodeEligible(const DecodeArgs& a, int tile);

@@ -1,4 +1,5 @@
-// KV cache for generation with Llama-class graphs on gfx950: the append of a step's new K / V rows to the cache and the one-token decode attention.
+// KV cache for generation with Llama-class graphs on gfx950: the append of a step's new K / V rows to the cache, the one-token decode attention and the
+// attention of an extend step (several new tokens over a cache).
 //
 // The cache tensors are fp32 in every precision and dense [N][Hkv][rows][hd] (kernels.h DecodeArgs): `past` with P rows comes in, `present` with
 // P + L rows goes out.  A decode step (L = 1) is a bandwidth problem: the arithmetic is 2 FMAs per cached element and query head, so the kernels
@@ -6,11 +7,16 @@
 //
 //   kv_append_kernel<T, V>               one lane per V consecutive floats of `present` (V = 4: 16-byte vectors; V = 1: a head dim that is no
 //                                        multiple of 4).  Rows < P: the past row, bit for bit.  Row P + l: k of token l after the rotary embedding
-//                                        (x cos + rotate_half(x) sin at the table row pos[n] + l, fp32 arithmetic as AttnArgs describes it) resp. v of
+//                                        (x cos + rotate_half(x) sin at the token's table row pos[n][l], fp32 arithmetic as AttnArgs describes it) resp. v of
 //                                        token l, converted to fp32.  Without a past (a prefill with a cache) it writes all L rows.
 //   attention_decode_generic_kernel<T>   tile 0: one wave per (image, query head) over `present`, which a kv_append launch wrote.  Lane l owns the head
 //                                        elements l, l + 64, ...; per key one wave reduction gives the score, the online softmax runs in every lane
 //                                        alike.  Any hd <= 512, any P, with or without a mask: the route for whatever tile 4 declines, and the cross-check.
+//   attention_extend_generic_kernel<T>   tile 0 of an extend step (a past and Lq >= 2 new tokens): the same wave per (image, query head, new token i) over the
+//                                        first P + i + 1 rows of `present`: the chunk is causal by chunk index, q is rotated at its token's own table row.
+//   attention_extend_kernel<T, HD>       tile 5 of an extend step, behind the kv_append launch: a workgroup = (image, K / V head, 128 query rows of the head
+//                                        group, key split) stages `present` through LDS in chunks and runs tile 1's MFMA softmax with the key mask and the
+//                                        chunk's causal limit (described at the kernel); S > 1: attention_extend_combine_kernel<T> adds the split records.
 //   attention_decode_kernel<T, HD, G>    tile 4: a workgroup = (image, K / V head, key split s of S), four waves.  A key row is HD / 4 lanes of 16 bytes, so a
 //                                        wave takes 256 / HD keys and the workgroup DecodeKeyTile(HD) keys per iteration, contiguous in the cache.  The lane
 //                                        that loads a K / V vector stores it into `present` (the Concat costs no pass of its own), multiplies it with the
@@ -40,13 +46,14 @@ namespace {
 constexpr int kDecodeBlock = 256;
 constexpr float kFltMax = 3.402823466e+38f;
 constexpr float kMaskShiftMax = 16777216.f;
+constexpr float kLog2e = 1.4426950408889634f;
 
-// the table row of token l of image n: pos[n] + l (a negative position counts from the end), clamped into the table
+// the table row of token l of image n: the token's own id pos[n pos_sn + l] (a negative position counts from the end), l without pos, clamped into the table
 __device__ __forceinline__ int64_t rope_row(const DecodeArgs& a, int64_t n, int l) {
     int64_t r = l;
     if (a.pos) {
-        const int64_t p = a.pos[n];
-        r += p < 0 ? p + a.rope_rows : p;
+        const int64_t p = a.pos[n * a.pos_sn + l];
+        r = p < 0 ? p + a.rope_rows : p;
     }
     return r < 0 ? 0 : (r >= a.rope_rows ? a.rope_rows - 1 : r);
 }
@@ -114,22 +121,19 @@ __global__ __launch_bounds__(kDecodeBlock) void kv_append_kernel(const DecodeArg
 // the bias of key j of image n, and the image's largest bias where it is small enough to be taken out of every score exactly (0 otherwise)
 __device__ __forceinline__ float key_bias(const DecodeArgs& a, int64_t n, int j) { return (1.f - float(a.mask[n * a.mask_sn + j])) * a.mask_value; }
 
-// rows = N * heads, one wave each
+// One wave: query head h of token i of image n over the first Lk of the `rows` rows of `present` (a decode step: i = 0, Lk = rows = P + 1; an extend
+// step: Lk = P + i + 1 of P + Lq, the rest being the chunk's future).  The shift is the largest bias among the keys the query sees
 template <typename T>
-__global__ __launch_bounds__(kDecodeBlock) void attention_decode_generic_kernel(const DecodeArgs a, const int64_t rows) {
+__device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int h, int i, int Lk, int rows) {
     constexpr int kChunks = kDecodeMaxHeadDim / 64;
     const int lane = int(threadIdx.x) % 64;
-    const int64_t row = int64_t(blockIdx.x) * (kDecodeBlock / 64) + threadIdx.x / 64;
-    if (row >= rows) return;                       // wave-uniform
-    const int hd = a.head_dim, Lk = a.past_len + 1;
-    const int h = int(row % a.heads);
-    const int64_t n = row / a.heads;
+    const int hd = a.head_dim;
     const int kvh = h / (a.heads / a.kv_heads);
-    const float* K = a.present_k + (n * a.kv_heads + kvh) * int64_t(Lk) * hd;
-    const float* Vp = a.present_v + (n * a.kv_heads + kvh) * int64_t(Lk) * hd;
+    const float* K = a.present_k + (n * a.kv_heads + kvh) * int64_t(rows) * hd;
+    const float* Vp = a.present_v + (n * a.kv_heads + kvh) * int64_t(rows) * hd;
     const bool rope = a.rope_cos != nullptr;
-    const int64_t r = rope ? rope_row(a, n, 0) : 0;
-    const int64_t qb = qkv_base(a, n, 0, 0, h);
+    const int64_t r = rope ? rope_row(a, n, i) : 0;
+    const int64_t qb = qkv_base(a, n, i, 0, h);
     float q[kChunks], acc[kChunks];
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {
@@ -166,12 +170,30 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_decode_generic_kernel(
         m = mn;
     }
     T* out = reinterpret_cast<T*>(a.out.p);
-    const int64_t ob = n * a.out.sn + int64_t(h) * hd * a.out.sc;
+    const int64_t ob = n * a.out.sn + int64_t(i) * a.out.sw + int64_t(h) * hd * a.out.sc;
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {
         const int e = c * 64 + lane;
         if (e < hd) out[ob + int64_t(e) * a.out.sc] = T(acc[c] / l);
     }
+}
+
+// rows = N * heads, one wave each
+template <typename T>
+__global__ __launch_bounds__(kDecodeBlock) void attention_decode_generic_kernel(const DecodeArgs a, const int64_t rows) {
+    const int64_t row = int64_t(blockIdx.x) * (kDecodeBlock / 64) + threadIdx.x / 64;
+    if (row >= rows) return;                       // wave-uniform
+    attend_wave<T>(a, row / a.heads, int(row % a.heads), 0, a.past_len + 1, a.past_len + 1);
+}
+
+// rows = N * heads * Lq, one wave per (image, query head, new token i), the token fastest: key j is visible to token i iff j <= P + i
+template <typename T>
+__global__ __launch_bounds__(kDecodeBlock) void attention_extend_generic_kernel(const DecodeArgs a, const int64_t rows) {
+    const int64_t row = int64_t(blockIdx.x) * (kDecodeBlock / 64) + threadIdx.x / 64;
+    if (row >= rows) return;                       // wave-uniform
+    const int Lq = a.new_len, i = int(row % Lq);
+    const int64_t nh = row / Lq;
+    attend_wave<T>(a, nh / a.heads, int(nh % a.heads), i, a.past_len + i + 1, a.past_len + Lq);
 }
 
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
@@ -307,6 +329,233 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_decode_combine_kernel(
     reinterpret_cast<T*>(a.out.p)[n * a.out.sn + (h * hd + e) * a.out.sc] = T(O / L);
 }
 
+// Tile 5 of an extend step.  grid = (row blocks x S, Hkv, N), dynamic LDS = ExtendLdsBytes(HD, half); runs behind the kv_append launch and reads K / V
+// from the fp32 `present` only.  A workgroup is (image, K / V head, block of 128 query rows, key split): the query rows of the group enumerate (new token
+// i, head-in-group r) as row = i g + r, so a wave's 32 rows (one per lane column, tile 1's orientation: S^T = K Q^T, O^T += V^T P^T with MFMA 32x32x2f32 /
+// 32x32x16_f16) have visible-key limits P + i that grow with the row.  K and V of the K / V head pass through LDS in chunks of kAttnChunkKeys keys,
+// converted to T where they enter it, the chunk's key biases (units of log2, clamped at -FLT_MAX) beside them: every `present` element is read from
+// HBM once per (image, K / V head, row block, split), never once per query head.
+// Masking: a key-masked key keeps its clamped bias and the running maximum starts at -FLT_MAX, so a tile, chunk or split of masked keys leaves with
+// weight exactly 0 next to a real score (tile 4's rule); a causally hidden key (key > P + i; the padded keys of the last tile are such) is -inf and is
+// tested only in the key tiles that reach beyond P + (the wave's first token); a lane with nothing visible in a tile keeps its finite maximum.
+// EVERY wave takes part in EVERY barrier (tile 3's rule): a wave whose rows lie beyond g Lq, or that is past its last tile (the one that holds P + its
+// last token), keeps staging and waiting and only skips the key tiles.
+// S > 1: split s takes the key tiles [s per, (s + 1) per) of ceil((P + Lq) / 32), cut at the row block's last visible key, and writes (m, l, o[HD]) per
+// query row into the workspace, record ((n H + h) Lq + i) S + s; a split with nothing visible for a row writes (-FLT_MAX, 0, 0).
+template <typename T, int HD>
+__global__ __launch_bounds__(kDecodeBlock) void attention_extend_kernel(const DecodeArgs a) {
+    constexpr bool F16 = sizeof(T) == 2;
+    constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
+    constexpr int RS = HD + V;                     // LDS row stride in elements
+    constexpr int HH = HD / 2;                     // head-dim elements one lane half supplies to QK^T
+    constexpr int KC = kAttnChunkKeys;
+    constexpr int VPR = HD / 4;                    // float4s of a `present` row
+    static_assert(KC % 32 == 0, "whole key tiles per chunk");
+    extern __shared__ __attribute__((aligned(16))) unsigned char extend_smem[];
+    T* Ks = reinterpret_cast<T*>(extend_smem);
+    T* Vs = Ks + size_t(KC) * RS;
+    float* Bs = reinterpret_cast<float*>(Vs + size_t(KC) * RS);
+    const int S = a.splits, rb = int(blockIdx.x) / S, sp = int(blockIdx.x) % S, kvh = int(blockIdx.y);
+    const int64_t n = blockIdx.z;
+    const int g = a.heads / a.kv_heads, P = a.past_len, Lq = a.new_len, R = g * Lq, Lk = P + Lq;
+    const int wave = int(threadIdx.x) / 64, lane = int(threadIdx.x) % 64, col = lane & 31, hf = lane >> 5;
+    const int q0 = rb * 128 + wave * 32;
+    const bool live = q0 < R;                      // wave-uniform
+    const int row = q0 + col < R ? q0 + col : R - 1;
+    const int tok = row / g, h = kvh * g + row % g;
+    const int lim = P + tok;                       // this lane's last visible key
+    const int first_tok = (q0 < R ? q0 : R - 1) / g, last_tok = (q0 + 31 < R ? q0 + 31 : R - 1) / g;
+    const int wave_end = live ? P + last_tok + 1 : 0;      // the wave's keys: [0, wave_end)
+    const int free_end = P + first_tok + 1;                // keys below it are visible to every row of the wave
+    const int wg_end = P + (rb * 128 + 127 < R ? rb * 128 + 127 : R - 1) / g + 1;
+    const int per = ((Lk + 31) / 32 + S - 1) / S;
+    const int kbeg = sp * per * 32, kend = wg_end < (sp + 1) * per * 32 ? wg_end : (sp + 1) * per * 32;      // the workgroup's keys (none: kbeg >= kend)
+
+    // this lane's half of its Q row, rotated at its token's own table row (the lane halves are the two rope halves); halfs are rounded once, here
+    float4 q4[F16 ? 1 : HH / 4];
+    h8 q8[F16 ? HH / 8 : 1];
+    {
+        const T* qh = reinterpret_cast<const T*>(a.in.p) + n * a.in.sn + int64_t(tok) * a.in.sw + h * HD;
+        const bool rope = a.rope_cos != nullptr;
+        const int64_t t = rope ? rope_row(a, n, tok) * HD + hf * HH : 0;
+        float qf[HH];
+#pragma unroll
+        for (int k = 0; k < HH; ++k) {
+            const float x = float(qh[hf * HH + k]);
+            qf[k] = x;
+            if (rope) {
+                const float xp = float(qh[(1 - hf) * HH + k]);
+                qf[k] = fmaf(x, a.rope_cos[t + k], (hf ? xp : -xp) * a.rope_sin[t + k]);
+            }
+        }
+        if constexpr (F16) {
+#pragma unroll
+            for (int k = 0; k < HH; ++k) q8[k / 8][k % 8] = _Float16(qf[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < HH / 4; ++k) q4[k] = make_float4(qf[4 * k], qf[4 * k + 1], qf[4 * k + 2], qf[4 * k + 3]);
+        }
+    }
+    f32x16 o0, o1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+    float m = -kFltMax, lsum = 0.f;
+    const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
+    const float* pk = a.present_k + (n * a.kv_heads + kvh) * int64_t(Lk) * HD;
+    const float* pv = a.present_v + (n * a.kv_heads + kvh) * int64_t(Lk) * HD;
+
+    for (int c0 = kbeg; c0 < kend; c0 += KC) {     // (the bounds are the workgroup's: every wave runs every iteration)
+        const int rows = kend - c0 < KC ? (kend - c0 + 31) / 32 * 32 : KC;
+        for (int idx = int(threadIdx.x); idx < rows * VPR; idx += kDecodeBlock) {
+            const int lr = idx / VPR, cv = idx % VPR, key = c0 + lr;
+            float4 kx = make_float4(0.f, 0.f, 0.f, 0.f), vx = kx;                         // rows past P + Lq: zeros (a zero probability times them stays zero)
+            if (key < Lk) {
+                kx = *reinterpret_cast<const float4*>(pk + int64_t(key) * HD + cv * 4);
+                vx = *reinterpret_cast<const float4*>(pv + int64_t(key) * HD + cv * 4);
+            }
+            if constexpr (F16) {
+                h4 kh, vh;
+                kh[0] = _Float16(kx.x); kh[1] = _Float16(kx.y); kh[2] = _Float16(kx.z); kh[3] = _Float16(kx.w);
+                vh[0] = _Float16(vx.x); vh[1] = _Float16(vx.y); vh[2] = _Float16(vx.z); vh[3] = _Float16(vx.w);
+                *reinterpret_cast<h4*>(Ks + lr * RS + cv * 4) = kh;
+                *reinterpret_cast<h4*>(Vs + lr * RS + cv * 4) = vh;
+            } else {
+                *reinterpret_cast<float4*>(Ks + lr * RS + cv * 4) = kx;
+                *reinterpret_cast<float4*>(Vs + lr * RS + cv * 4) = vx;
+            }
+        }
+        for (int j = int(threadIdx.x); j < rows; j += kDecodeBlock)
+            Bs[j] = c0 + j < Lk ? fmaxf(key_bias(a, n, c0 + j) * kLog2e, -kFltMax) : 0.f;      // (a padded key is causally hidden from every row)
+        __syncthreads();
+        const int cend = c0 + rows < wave_end ? c0 + rows : wave_end;
+        for (int key0 = c0; key0 < cend; key0 += 32) {
+            const T* Kt = Ks + (key0 - c0) * RS;
+            const T* Vt = Vs + (key0 - c0) * RS;
+            const float* Bt = Bs + (key0 - c0);
+            f32x16 s;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = 0.f;
+            const T* krow = Kt + col * RS + hf * HH;
+            if constexpr (F16) {
+#pragma unroll
+                for (int k = 0; k < HH; k += 8) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(krow + k), q8[k / 8], s, 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int k = 0; k < HH; k += 4) {
+                    const float4 kf = *reinterpret_cast<const float4*>(krow + k);
+                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, q4[k / 4].x, s, 0, 0, 0);
+                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, q4[k / 4].y, s, 0, 0, 0);
+                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, q4[k / 4].z, s, 0, 0, 0);
+                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, q4[k / 4].w, s, 0, 0, 0);
+                }
+            }
+            const bool edge = key0 + 32 > free_end;        // wave-uniform: this tile reaches beyond what the wave's first token sees
+            float mx = -__builtin_huge_valf();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int kt = (r & 3) + 8 * (r >> 2) + 4 * hf;
+                const float b = fmaxf(fmaf(s[r], sl2, Bt[kt]), -kFltMax);
+                s[r] = edge && key0 + kt > lim ? -__builtin_huge_valf() : b;
+                mx = fmaxf(mx, s[r]);
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float mn = fmaxf(m, mx);             // finite: m starts at -FLT_MAX
+            const float alpha = fast_exp2(m - mn);
+            m = mn;
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                s[r] = fast_exp2(s[r] - mn);
+                ps += s[r];
+                o0[r] *= alpha;
+                if constexpr (HD == 64) o1[r] *= alpha;
+            }
+            lsum = fmaf(lsum, alpha, ps);              // this lane half's share of the row sum
+            if constexpr (F16) {
+#pragma unroll
+                for (int st = 0; st < 2; ++st) {
+                    h8 pb, va0, va1;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int kt = 16 * st + 8 * (j >> 2) + 4 * hf + (j & 3);
+                        pb[j] = _Float16(s[8 * st + j]);
+                        va0[j] = Vt[kt * RS + col];
+                        if constexpr (HD == 64) va1[j] = Vt[kt * RS + 32 + col];
+                    }
+                    o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va0, pb, o0, 0, 0, 0);
+                    if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va1, pb, o1, 0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kt = (r & 3) + 8 * (r >> 2) + 4 * hf;
+                    o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vt[kt * RS + col]), s[r], o0, 0, 0, 0);
+                    if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vt[kt * RS + 32 + col]), s[r], o1, 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();                           // the next chunk overwrites the rows
+    }
+
+    lsum += __shfl_xor(lsum, 32, 64);
+    if (q0 + col >= R) return;                     // behind the last barrier
+    // registers 4 j ... 4 j + 3 of o0 (o1: + 32) are the output columns 8 j + 4 hf ... of this lane's query row
+    if (S == 1) {
+        T* orow = reinterpret_cast<T*>(a.out.p) + n * a.out.sn + int64_t(tok) * a.out.sw + h * HD;
+        const float inv = 1.f / lsum;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e0 = 8 * j + 4 * hf;
+            if constexpr (F16) {
+                h4 x, y;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) { x[t] = _Float16(o0[4 * j + t] * inv); y[t] = _Float16(o1[4 * j + t] * inv); }
+                *reinterpret_cast<h4*>(orow + e0) = x;
+                if constexpr (HD == 64) *reinterpret_cast<h4*>(orow + 32 + e0) = y;
+            } else {
+                *reinterpret_cast<float4*>(orow + e0) = make_float4(o0[4 * j] * inv, o0[4 * j + 1] * inv, o0[4 * j + 2] * inv, o0[4 * j + 3] * inv);
+                if constexpr (HD == 64) *reinterpret_cast<float4*>(orow + 32 + e0) = make_float4(o1[4 * j] * inv, o1[4 * j + 1] * inv, o1[4 * j + 2] * inv, o1[4 * j + 3] * inv);
+            }
+        }
+        return;
+    }
+    float* rec = a.workspace + (((n * a.heads + h) * Lq + tok) * S + sp) * int64_t(HD + 2);
+    if (hf == 0) { rec[0] = m; rec[1] = lsum; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int e0 = 8 * j + 4 * hf;
+        *reinterpret_cast<float2*>(rec + 2 + e0) = make_float2(o0[4 * j], o0[4 * j + 1]);
+        *reinterpret_cast<float2*>(rec + 2 + e0 + 2) = make_float2(o0[4 * j + 2], o0[4 * j + 3]);
+        if constexpr (HD == 64) {
+            *reinterpret_cast<float2*>(rec + 2 + 32 + e0) = make_float2(o1[4 * j], o1[4 * j + 1]);
+            *reinterpret_cast<float2*>(rec + 2 + 32 + e0 + 2) = make_float2(o1[4 * j + 2], o1[4 * j + 3]);
+        }
+    }
+}
+
+// one thread per (image, query head, new token, element): the S records of the row in split order (m in units of log2).  A split with nothing visible
+// for the row has (-FLT_MAX, 0, 0): its weight next to a real maximum is exactly 0, and it adds nothing either way
+template <typename T>
+__global__ __launch_bounds__(kDecodeBlock) void attention_extend_combine_kernel(const DecodeArgs a, const int64_t total) {
+    const int64_t i = int64_t(blockIdx.x) * kDecodeBlock + threadIdx.x;
+    if (i >= total) return;
+    const int hd = a.head_dim, S = a.splits, Lq = a.new_len;
+    const int e = int(i % hd);
+    const int64_t nhi = i / hd;                    // (n heads + h) Lq + token
+    const float* rec = a.workspace + nhi * S * int64_t(hd + 2);
+    float M = -kFltMax;
+    for (int s = 0; s < S; ++s) M = fmaxf(M, rec[int64_t(s) * (hd + 2)]);
+    float L = 0.f, O = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const float* rs = rec + int64_t(s) * (hd + 2);
+        const float w = fast_exp2(rs[0] - M);
+        L = fmaf(rs[1], w, L);
+        O = fmaf(rs[2 + e], w, O);
+    }
+    const int64_t tok = nhi % Lq, nh = nhi / Lq, n = nh / a.heads, h = nh % a.heads;
+    reinterpret_cast<T*>(a.out.p)[n * a.out.sn + tok * a.out.sw + (h * hd + e) * a.out.sc] = T(O / L);
+}
+
 bool cache_ok(const DecodeArgs& a) {
     return a.in.p && a.present_k && a.present_v && a.heads >= 1 && a.kv_heads >= 1 && a.heads % a.kv_heads == 0 && a.head_dim >= 1 && a.past_len >= 0 && a.new_len >= 1 &&
            a.in.w == a.new_len && !a.in.f8 && (a.past_len == 0 || (a.past_k && a.past_v)) && (!a.rope_cos || (a.rope_sin && a.rope_rows >= 1 && a.head_dim % 2 == 0)) &&
@@ -330,6 +579,17 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
     if (e != hipSuccess || a.splits == 1) return e;
     const int64_t total = int64_t(a.in.n) * a.heads * a.head_dim;
     hipLaunchKernelGGL((attention_decode_combine_kernel<T>), dim3(unsigned((total + kDecodeBlock - 1) / kDecodeBlock)), dim3(kDecodeBlock), 0, stream, a, total);
+    return hipGetLastError();
+}
+
+template <typename T, int HD>
+hipError_t launch_extend(const DecodeArgs& a, hipStream_t stream) {
+    const int64_t rblocks = (int64_t(a.heads / a.kv_heads) * a.new_len + 127) / 128;
+    const dim3 grid(unsigned(rblocks * a.splits), unsigned(a.kv_heads), unsigned(a.in.n));
+    attention_extend_kernel<T, HD><<<grid, dim3(kDecodeBlock), size_t(ExtendLdsBytes(HD, sizeof(T) == 2)), stream>>>(a);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess || a.splits == 1) return e;
+    const int64_t total = int64_t(a.in.n) * a.heads * a.new_len * a.head_dim;
+    hipLaunchKernelGGL((attention_extend_combine_kernel<T>), dim3(unsigned((total + kDecodeBlock - 1) / kDecodeBlock)), dim3(kDecodeBlock), 0, stream, a, total);
     return hipGetLastError();
 }
 
@@ -359,9 +619,18 @@ hipError_t LaunchKvAppend(const DecodeArgs& a, hipStream_t stream) {
 }
 
 bool AttentionDecodeEligible(const DecodeArgs& a, int tile) {
-    if (!cache_ok(a) || !a.out.p || a.out.f8 || a.in.f16 != a.out.f16 || a.new_len != 1 || a.past_len < 1 || a.head_dim > kDecodeMaxHeadDim) return false;
-    if (int64_t(a.out.c) != int64_t(a.heads) * a.head_dim) return false;
+    if (!cache_ok(a) || !a.out.p || a.out.f8 || a.in.f16 != a.out.f16 || a.past_len < 1 || a.head_dim > kDecodeMaxHeadDim) return false;
+    if (int64_t(a.out.c) != int64_t(a.heads) * a.head_dim || (a.new_len > 1 && a.out.w != a.new_len)) return false;
     if (tile == 0) return true;
+    if (a.new_len > 1) {                           // an extend step: tile 5 alone
+        if (tile != kAttnExtendTile || !ExtendFastFits(a.head_dim, a.heads, a.kv_heads, a.mask != nullptr, a.mask_value)) return false;
+        const int V = a.in.f16 ? 8 : 4;
+        if (!VecViewOk(a.in, V) || !VecViewOk(a.out, V) || !Aligned16(a.present_k) || !Aligned16(a.present_v) || (a.rope_cos && (!Aligned16(a.rope_cos) || !Aligned16(a.rope_sin)))) return false;
+        const int64_t rows = int64_t(a.heads / a.kv_heads) * a.new_len, tiles = (int64_t(a.past_len) + a.new_len + 31) / 32;
+        if (a.splits < 1 || a.splits > kDecodeMaxSplits || a.splits > tiles || (rows + 127) / 128 * a.splits >= (int64_t(1) << 31) || a.kv_heads > 65535 || a.in.n > 65535) return false;
+        if (int64_t(a.in.n) * a.heads * a.new_len * a.head_dim / kDecodeBlock >= (int64_t(1) << 31) || !KvAppendEligible(a)) return false;
+        return a.splits == 1 || (a.workspace && ExtendWorkspaceFloats(a.in.n, a.heads, a.head_dim, a.splits, a.new_len) <= a.workspace_floats);
+    }
     if (tile != kAttnDecodeTile) return false;
     if (!DecodeFastFits(a.head_dim, a.heads, a.kv_heads, a.mask != nullptr, a.mask_value)) return false;
     if (!Aligned16(a.past_k) || !Aligned16(a.past_v) || !Aligned16(a.present_k) || !Aligned16(a.present_v)) return false;
@@ -370,19 +639,39 @@ bool AttentionDecodeEligible(const DecodeArgs& a, int tile) {
     return a.splits == 1 || (a.workspace && DecodeWorkspaceFloats(a.in.n, a.heads, a.head_dim, a.splits) <= a.workspace_floats);
 }
 
-// tile 0 attends over `present` as a kv_append launch left it; tile 4 copies, appends and attends in one launch (plus the combine)
+// tile 0 attends over `present` as a kv_append launch left it (new_len > 1: the extend kernel); tile 4 copies, appends and attends in one launch (plus the combine)
 hipError_t LaunchAttentionDecode(const DecodeArgs& a, int tile, hipStream_t stream) {
     if (!AttentionDecodeEligible(a, tile)) return hipErrorInvalidValue;
     if (a.in.n == 0) return hipSuccess;
     if (tile == 0) {
-        const int64_t rows = int64_t(a.in.n) * a.heads;
+        const int64_t rows = int64_t(a.in.n) * a.heads * a.new_len;
         const int64_t blocks = (rows + kDecodeBlock / 64 - 1) / (kDecodeBlock / 64);
         if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+        if (a.new_len > 1) {
+            if (a.in.f16) hipLaunchKernelGGL((attention_extend_generic_kernel<_Float16>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
+            else hipLaunchKernelGGL((attention_extend_generic_kernel<float>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
+            return hipGetLastError();
+        }
         if (a.in.f16) hipLaunchKernelGGL((attention_decode_generic_kernel<_Float16>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
         else hipLaunchKernelGGL((attention_decode_generic_kernel<float>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
         return hipGetLastError();
     }
+    if (tile == kAttnExtendTile) {                 // the append first: tile 5 reads K and V from `present` only
+        if (const hipError_t e = LaunchKvAppend(a, stream); e != hipSuccess) return e;
+        if (a.in.f16) return a.head_dim == 32 ? launch_extend<_Float16, 32>(a, stream) : launch_extend<_Float16, 64>(a, stream);
+        return a.head_dim == 32 ? launch_extend<float, 32>(a, stream) : launch_extend<float, 64>(a, stream);
+    }
     return a.in.f16 ? launch_decode<_Float16>(a, stream) : launch_decode<float>(a, stream);
+}
+
+hipError_t InitKernelsDecode() {
+    const void* const kernels[] = {
+        reinterpret_cast<const void*>(&attention_extend_kernel<float, 32>), reinterpret_cast<const void*>(&attention_extend_kernel<float, 64>),
+        reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 32>), reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 64>),
+    };
+    for (const void* k : kernels)
+        if (const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget)); e != hipSuccess) return e;
+    return hipSuccess;
 }
 
 }  // namespace ie

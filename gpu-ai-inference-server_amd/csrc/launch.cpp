@@ -122,7 +122,10 @@ DecodeArgs MakeDecodeArgs(const PlanInstance& pi, const Step& s, const float* we
         a.rope_cos = weights + s.w_off;
         a.rope_sin = weights + s.w2_off;
         a.rope_rows = s.rope_rows;
-        if (s.pos.buf >= 0) a.pos = reinterpret_cast<const int64_t*>(make_arg(pi, s.pos).p);
+        if (s.pos.buf >= 0) {
+            a.pos = reinterpret_cast<const int64_t*>(make_arg(pi, s.pos).p);
+            a.pos_sn = s.pos.pitch;
+        }
     }
     a.splits = s.splits > 0 ? s.splits : 1;
     a.workspace = pi.workspace;
@@ -724,8 +727,9 @@ std::string kernel_label(const Step& s) {
         case StepKind::KvAppend: return std::string("kv_append_kernel<") + (s.in.f16 ? "f16>" : "f32>");
         case StepKind::Attention:
             if (s.past_len > 0) {
+                if (s.tile == kAttnExtendTile) return std::string("kv_append_kernel + attention_extend_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">" + (s.splits > 1 ? " + attention_extend_combine_kernel" : "");
                 if (s.tile == kAttnDecodeTile) return std::string("attention_decode_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">" + (s.splits > 1 ? " + attention_decode_combine_kernel" : "");
-                return std::string(s.parts.empty() ? "" : "kv_append_kernel + ") + "attention_decode_generic_kernel<" + (s.out.f16 ? "f16>" : "f32>");
+                return std::string(s.parts.empty() ? "" : "kv_append_kernel + ") + (s.in.w > 1 ? "attention_extend_generic_kernel<" : "attention_decode_generic_kernel<") + (s.out.f16 ? "f16>" : "f32>");
             }
             if (s.tile == 2) return std::string("attention_stream_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.rope ? ",causal,rope>" : s.causal ? ",causal>" : ">");
             if (s.tile == 3) return std::string("attention_chunk_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + (s.rope ? ",causal,rope>" : s.causal ? ",causal>" : ">");

@@ -83,6 +83,7 @@ struct LNode {
     // the INT64 position input (-1: none); w / w2 = the rope tables [rope_rows][hd] (k only).  L_ATTENTION with past_len > 0 (a decode step): in[present_in]
     // and in[present_in + 1] = present k / v, in[pos_in] = the positions
     int past_len = 0, past_in = -1, pos_in = -1, present_in = -1;
+    bool chunk_causal = false;          // L_ATTENTION with past_len > 0 and L >= 2 new tokens (an extend step): token i sees the keys j <= past_len + i
     bool kv_v = false;
     int64_t rope_rows = 0;
     // L_EMBED: in = the int64 ids of the first table (and of the second); w = the first table [emb_vocab][D], w2 = the second [emb_types][D] (empty:
@@ -431,7 +432,17 @@ struct Planner {
         // present_v = the graph outputs that name the Concat results (without a past: the rotated k and the transposed v of a prefill); rope_pos = the
         // INT64 graph input [N, 1] that gathers the rope tables (empty: constant positions); cat_k / cat_v = the Concat nodes (messages)
         std::string past_k, past_v, present_k, present_v, rope_pos, cat_k, cat_v;
+        // an extend step: the mask is M = Where(Cast(ext, BOOL), c, C) (MatchChunkMask); chunk_c = the constant C, checked against the step's P and Lq
+        // at the import; chunk_where = the Where (messages).  rope_pos_miss: the refusal of position ids that are not [N, 1], kept for a decode step
+        bool chunk = false;
+        const OnnxTensor* chunk_c = nullptr;
+        std::string chunk_where, rope_pos_miss;
     };
+    // M = Where(Cast(ext, to BOOL), c <= -1e30, C) with ext a key-mask chain and C a float constant [1, 1, Lq, P + Lq]: the 4-D mask of an extend step,
+    // matched once per name and shared by all layers.  Its Where and Cast import nothing, and only attention Adds may read M
+    struct ChunkMask { bool ok = false; std::string ext; const OnnxTensor* c = nullptr; float fill = 0.f; std::vector<const OnnxNode*> nodes; int uses = 0; };
+    std::map<std::string, ChunkMask> chunk_masks;
+    const ChunkMask* MatchChunkMask(const std::string& name, const std::string& prefix);
     std::map<std::vector<float>, int64_t> rope_blob;      // EmitKvAppend: the rope tables already in the weight blob (every layer of a model gathers the same ones)
     std::set<const OnnxNode*> rope_const_nodes;      // the Unsqueeze / Slice / Gather nodes that cut the rope tables out of constants: evaluated at load, import nothing
     // MatchCausalWhere / MatchCausalAdd: the two spellings of a causal mask on the scores (false / a refusal by name: not one)
@@ -1754,6 +1765,16 @@ void Planner::MatchAttention() {
             if (top->outputs[0] == sm_in && !am.causal && mk && MatchCausalAdd(*mk, am)) {
                 // the causal mask as an additive constant: 0 on and below the diagonal, one value <= -1e30 above it
                 causal_nodes.push_back(top);
+            } else if (const ChunkMask* cm = top->outputs[0] == sm_in ? MatchChunkMask(top->inputs[size_t(1 - si)], prefix + "Add " + tname + ": ") : nullptr) {
+                // the 4-D mask of an extend step: the key mask and the chunk's causal constant in one value; P and Lq are known at the import
+                if (am.causal) fail(prefix + both + " (Add " + tname + ")");
+                am.mask = key_masks.at(cm->ext).input;
+                am.mask_value = cm->fill;
+                am.chunk = true;
+                am.chunk_c = cm->c;
+                am.chunk_where = top->inputs[size_t(1 - si)];
+                ++chunk_masks[top->inputs[size_t(1 - si)]].uses;
+                mask_add = top;
             } else {
                 // only the key mask of an INT64 graph input [N, L], broadcast as [N, 1, 1, L], directly in front of the Softmax
                 const KeyMask* km = top->outputs[0] == sm_in ? &MatchKeyMask(top->inputs[size_t(1 - si)]) : nullptr;
@@ -1812,6 +1833,14 @@ void Planner::MatchAttention() {
                      "; only the products of a rotary embedding may read it");
     }
     for (const OnnxNode* p : rope_const_nodes) attn_skip.insert(p);
+    // a chunk mask M is the matched attentions' alone; its Where and Cast import nothing (its ext chain: below, the Cast being the chain's one reader)
+    for (const auto& kv : chunk_masks)
+        if (kv.second.ok && kv.second.uses > 0) {
+            if (gi.nreaders(kv.first) != kv.second.uses)
+                fail("Where " + kv.first + ": the chunk mask has " + std::to_string(gi.nreaders(kv.first)) + " readers, " + std::to_string(kv.second.uses) + " of them attention scores; only those may read it");
+            for (const OnnxNode* p : kv.second.nodes) { attn_skip.insert(p); mask_nodes.insert(p); }
+            key_masks[kv.second.ext].uses = 1;
+        }
     // an ext chain is the matched attentions' alone
     for (const auto& kv : key_masks)
         if (kv.second.ok && kv.second.uses > 0) {
@@ -1863,6 +1892,40 @@ const Planner::KeyMask& Planner::MatchKeyMask(const std::string& name) {
     km.c = c;
     km.nodes = nodes;
     return km;
+}
+
+// M = Where(Cast(ext, to BOOL), c, C): ext a key-mask chain (non-zero on a masked key), c a scalar constant <= -1e30, C a float constant of rank 4.
+// nullptr: `name` is no such value (the caller's own refusal follows).  Add(ext, C), which sums two finfo.min to -inf, and a near miss of the Where
+// form are refused by name.  C's elements are checked at the import (ImportAttention), where the step's P and Lq are known
+const Planner::ChunkMask* Planner::MatchChunkMask(const std::string& name, const std::string& prefix) {
+    if (const auto it = chunk_masks.find(name); it != chunk_masks.end()) return it->second.ok ? &it->second : nullptr;
+    const OnnxNode* wh = gi.producer(name);
+    auto rank4 = [&](const std::string& n) { const OnnxTensor* t = gi.cst(n); return t && !t->f.empty() && t->dims.size() == 4 ? t : nullptr; };
+    const std::string form = "; supported: Where(Cast(ext, to BOOL), finfo.min, C) with C [1, 1, Lq, P + Lq], as AttentionMaskConverter.to_4d lowers it with a past";
+    if (wh && wh->op == "Add" && wh->inputs.size() == 2)
+        for (int k = 0; k < 2; ++k)
+            if (rank4(wh->inputs[size_t(k)]) && gi.producer(wh->inputs[size_t(1 - k)]) && MatchKeyMask(wh->inputs[size_t(1 - k)]).ok)
+                fail(prefix + "the mask " + name + " is Add(ext, C) of a key mask and a constant: a masked key of the chunk's future would be finfo.min + finfo.min = -inf" + form);
+    if (!wh || wh->op != "Where" || wh->inputs.size() != 3) return nullptr;
+    const OnnxNode* cast = gi.producer(wh->inputs[0]);
+    if (!cast || cast->op != "Cast" || cast->inputs.size() != 1 || !gi.producer(cast->inputs[0]) || !MatchKeyMask(cast->inputs[0]).ok) return nullptr;
+    const KeyMask& km = MatchKeyMask(cast->inputs[0]);
+    const std::string who = prefix + "the chunk mask Where " + (wh->name.empty() ? wh->outputs[0] : wh->name) + ": ";
+    if (cast->attr_i("to", 0) != ONNX_BOOL) fail(who + "its condition is not Cast(ext, to BOOL)" + form);
+    if (km.c == 0.f) fail(who + "the key mask's constant is 0: Cast(ext, to BOOL) is false on every key" + form);
+    if (gi.nreaders(cast->outputs[0]) != 1 || gi.nreaders(cast->inputs[0]) != 1) fail(who + "its condition or the key mask " + cast->inputs[0] + " has a second reader" + form);
+    const OnnxTensor* c = gi.cst(wh->inputs[1]);
+    if (!c || c->numel() != 1 || c->f.size() != 1) fail(who + "the value " + wh->inputs[1] + " of a masked key is not a scalar floating-point constant" + form);
+    if (!(c->f[0] <= -1e30f)) fail(who + "the value " + std::to_string(c->f[0]) + " of a masked key is above -1e30: a masked key of the chunk's future would keep a probability" + form);
+    const OnnxTensor* C = rank4(wh->inputs[2]);
+    if (!C) fail(who + "its third operand " + wh->inputs[2] + " is not a floating-point constant of rank 4" + form);
+    ChunkMask& cm = chunk_masks[name];
+    cm.ok = true;
+    cm.ext = cast->inputs[0];
+    cm.c = C;
+    cm.fill = c->f[0];
+    cm.nodes = {wh, cast};
+    return &cm;
 }
 
 // Where(cond, scores, c) on the scores: cond a BOOL constant [1, 1, L, L], or one or two Slices with constant indices of a [1, 1, P, P] one (GPT-2's
@@ -2084,6 +2147,7 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
     };
     // a rope table as the graph's constants give it: an initializer / Constant, or Unsqueeze / Slice (step 1) / Gather(axis 0, constant indices) of one
     std::string gather_pos;                        // const_eval: the INT64 graph input that gathers the table being evaluated (empty: constant positions)
+    std::string pos_miss;                          // const_eval: the refusal of position ids wider than [N, 1], for the import (AttnMatch::rope_pos_miss)
     std::function<bool(const std::string&, OnnxTensor&, std::vector<const OnnxNode*>&)> const_eval = [&](const std::string& name, OnnxTensor& out, std::vector<const OnnxNode*>& nodes) -> bool {
         if (const OnnxTensor* t = gi.cst(name)) { out = *t; return !t->f.empty(); }
         const OnnxNode* p = gi.producer(name);
@@ -2098,9 +2162,12 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         if (p->op == "Gather" && p->inputs.size() == 2 && !gi.cst(p->inputs[1])) {
             const std::string who = "Gather " + nm_of(p) + ": the position ids " + p->inputs[1] + " of the rope table ";
             bool ok = false;
+            int64_t width = 0;
             for (size_t i = 0; i < m.inputs.size(); ++i)
-                if (m.inputs[i].name == p->inputs[1]) ok = m.inputs[i].elem_type == ONNX_INT64 && input_shapes[i].size() == 2 && input_shapes[i][1] == 1;
-            if (!ok) miss(who + "are neither a constant nor an INT64 graph input [N, 1] (supported: constant positions, or position_ids [N, 1] of a decode step)");
+                if (m.inputs[i].name == p->inputs[1]) { ok = m.inputs[i].elem_type == ONNX_INT64 && input_shapes[i].size() == 2; width = ok ? input_shapes[i][1] : 0; }
+            const std::string not_n1 = who + "are neither a constant nor an INT64 graph input [N, 1] (supported: constant positions, or position_ids [N, 1] of a decode step)";
+            if (!ok) miss(not_n1);
+            if (width != 1) pos_miss = prefix + not_n1;      // (an extend step takes [N, Lq]: the import, which knows Lq, decides)
             if (p->attr_i("axis", 0) != 0 || rank != 2 || !gather_pos.empty()) miss(who + "must gather a [max_pos, hd] table once, along axis 0");
             gather_pos = p->inputs[1];
             out = in;
@@ -2314,6 +2381,7 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         miss(std::string("only ") + (am.present_k.empty() ? am.present_v : am.present_k) + " is a graph output; present key and present value come as a pair");
     if (rq.on && rq.pos != rk.pos)
         miss("the positions of k (Add " + rk.name + ": " + (rk.pos.empty() ? "constant" : rk.pos) + ") are not the positions of q (Add " + rq.name + ": " + (rq.pos.empty() ? "constant" : rq.pos) + ")");
+    if (!pos_miss.empty() && am.past_k.empty()) fail(pos_miss);
     if (rq.on && !rq.pos.empty() && am.past_k.empty())
         miss("the rope tables (Add " + rq.name + ") are gathered by the graph input " + rq.pos + " without a cache; run-time positions are supported in a decode step (Concat(past, k, axis 2)) only");
     if (rq.on != rk.on) miss(std::string("only ") + (rq.on ? "q" : "k") + " passes a rotary embedding (Add " + (rq.on ? rq.name : rk.name) + "); q and k must both be rotated");
@@ -2448,6 +2516,7 @@ bool Planner::MatchSplitAttention(const OnnxNode& sm, const OnnxNode* pv, const 
         am.rope_rows = rq.rows;
         am.rope_name = rq.name;
         am.rope_pos = rq.pos;
+        am.rope_pos_miss = pos_miss;
     }
     // the head: the first of the three MatMuls in graph order (x is defined there)
     for (const OnnxNode& on : m.nodes) if (&on == mm[0] || &on == mm[1] || &on == mm[2]) { head = &on; break; }
@@ -2604,9 +2673,28 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
             if (v->n != X.n || v->c != Hkv || v->w != am.head_dim)
                 miss("the past input " + v->name + " is " + dims_of(*v) + ", not [N, Hkv, P, hd] = [" + std::to_string(X.n) + ", " + std::to_string(Hkv) + ", P, " + std::to_string(am.head_dim) + "] of this step");
         P = PK.h;
-        if (X.w != 1)
-            miss("a past (Concat " + am.cat_k + ") with Lq = " + std::to_string(X.w) + " new tokens (chunked prefill into a cache) is not supported; a decode step has one new token, Lq = 1");
+        if (X.w != 1 && !am.chunk)
+            miss("a past (Concat " + am.cat_k + ") with Lq = " + std::to_string(X.w) + " new tokens (chunked prefill into a cache) needs the chunk's causal mask, Add(scores, Where(Cast(ext, to BOOL), "
+                 "finfo.min, C)), on the scores; it has " + (am.causal ? "a causal mask of the new tokens alone" : am.mask.empty() ? "no mask: the new tokens would see each other's future" : "a key mask alone: the new tokens would see each other's future") +
+                 "; only a decode step, one new token, Lq = 1, goes without it");
         if (am.causal) miss("a causal mask together with a past (Concat " + am.cat_k + ") is not supported; one query attends to every cached key the key mask admits");
+    }
+    if (am.chunk) {
+        // the constant C of the chunk mask against this step's P and Lq, element by element: 0 on the P cached columns and on and below the chunk's diagonal, <= -1e30 above it
+        const std::string who = "the chunk mask Where " + am.chunk_where + ": ";
+        if (!decode)
+            miss(who + "a key mask and a causal constant in one value without a past (no Concat(past, k, axis 2)) is not supported; it is the mask of an extend step over a cache");
+        const std::vector<int64_t>& d = am.chunk_c->dims;
+        if (d[0] != 1 || d[1] != 1 || d[2] != X.w || d[3] != P + X.w)
+            miss(who + "its constant is [" + std::to_string(d[0]) + ", " + std::to_string(d[1]) + ", " + std::to_string(d[2]) + ", " + std::to_string(d[3]) + "], not [1, 1, Lq, P + Lq] = [1, 1, " + std::to_string(X.w) + ", " +
+                 std::to_string(P + X.w) + "] of this step (P = " + std::to_string(P) + " cached rows, Lq = " + std::to_string(X.w) + " new tokens)");
+        for (int64_t i = 0; i < X.w; ++i)
+            for (int64_t j = 0; j < P + X.w; ++j) {
+                const float v = am.chunk_c->f[size_t(i * (P + X.w) + j)];
+                const bool visible = j <= P + i;
+                if (visible ? v != 0.f : !(v <= -1e30f))
+                    miss(who + "its constant is not the chunk's causal mask (0 where j <= P + i, <= -1e30 above): element [" + std::to_string(i) + ", " + std::to_string(j) + "] is " + std::to_string(v) + " at P = " + std::to_string(P));
+            }
     }
     const int64_t Lk = X.w + P;                    // keys of a query
     // repeat_kv's constant shapes: Expand to [N, Hkv, g, L, hd] (a 1 keeps the dim), Reshape to [N, H, L, hd]
@@ -2627,6 +2715,11 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     // the cache outputs: one kv_append node each for K and V, in front of the attention node (EmitSteps makes one step of the pair)
     int pres[2] = {-1, -1}, pos_val = -1;
     if (am.rope && !am.rope_pos.empty()) pos_val = L.get_val(am.rope_pos);
+    if (pos_val >= 0 && L.vals[pos_val].c != X.w) {
+        if (X.w == 1) fail(am.rope_pos_miss);      // (a decode step: the refusal of the match, word for word)
+        miss("the position ids " + am.rope_pos + " of the rope table are [" + std::to_string(L.vals[pos_val].n) + ", " + std::to_string(L.vals[pos_val].c) + "]; a step with a past and Lq = " + std::to_string(X.w) +
+             " new tokens takes an INT64 graph input [N, Lq] = [" + std::to_string(X.n) + ", " + std::to_string(X.w) + "], every token's own table row");
+    }
     if (!am.present_k.empty()) {
         for (int which = 0; which < 2; ++which) {
             LNode a;
@@ -2658,6 +2751,9 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     n.attn_scale = am.scale;
     if (!am.mask.empty()) {
         const int mv = L.get_val(am.mask);
+        if (decode && X.w > 1 && (L.vals[mv].n != X.n || L.vals[mv].c != Lk))
+            miss("the key mask " + am.mask + " is [" + std::to_string(L.vals[mv].n) + ", " + std::to_string(L.vals[mv].c) + "]; its width must be P + Lq = " + std::to_string(Lk) + " (the " + std::to_string(P) +
+                 " cached rows and the " + std::to_string(X.w) + " new keys) for [N = " + std::to_string(X.n) + "] images");
         if (decode && (L.vals[mv].n != X.n || L.vals[mv].c != Lk))
             miss("the key mask " + am.mask + " is [" + std::to_string(L.vals[mv].n) + ", " + std::to_string(L.vals[mv].c) + "]; its width must be P + 1 = " + std::to_string(Lk) + " (the " + std::to_string(P) +
                  " cached rows and the new key) for [N = " + std::to_string(X.n) + "] images");
@@ -2678,6 +2774,7 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
     }
     if (decode) {
         n.past_len = int(P);
+        n.chunk_causal = X.w > 1;
         n.present_in = int(n.in.size());
         n.in.push_back(pres[0]);
         n.in.push_back(pres[1]);
@@ -4724,6 +4821,25 @@ void Planner::EmitAttention(const LNode& n, Step& s) {
             if (!s.in2.i64) fail("internal planner error: the key mask of node " + n.name + " is not an int64 view");
         }
         s.rope = !n.w.empty();
+        if (n.chunk_causal) {
+            // an extend step: in.w = Lq >= 2 new tokens, token i over the past_len + i + 1 rows of `present` it may see.  Tile 5 where kernels.h
+            // ExtendFastFits says so and there are at least kAttnExtendMinRows query rows per K / V head, else the parts; IE_ATTN_TILE = 0 | 5 pins it (an
+            // ineligible 5 is the parts), IE_ATTN_SPLITS the key splits of tile 5 (at most one 32-key tile per split).  No other tile takes it
+            s.chunk_causal = true;
+            const int64_t rows = int64_t(s.heads / s.kv_heads) * s.in.w, keys = int64_t(n.past_len) + s.in.w;
+            const bool fits = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 && ExtendFastFits(s.head_dim, s.heads, s.kv_heads, n.key_mask, n.mask_value);
+            s.tile = fits && rows >= kAttnExtendMinRows ? kAttnExtendTile : 0;
+            if (const char* e = env.get("IE_ATTN_TILE"); e && (std::atoi(e) == 0 || std::atoi(e) == kAttnExtendTile)) s.tile = std::atoi(e) == kAttnExtendTile && fits ? kAttnExtendTile : 0;
+            if (ForcedTile(kNumAttnForcedTiles) >= 0) s.tile = 0;
+            if (s.tile == kAttnExtendTile) {
+                s.splits = ExtendDefaultSplits(s.in.n, s.kv_heads, rows, keys);
+                if (const int f = env.integer("IE_ATTN_SPLITS", 0); f >= 1) s.splits = int(std::min<int64_t>(std::min(f, kDecodeMaxSplits), (keys + 31) / 32));
+                plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, ExtendWorkspaceFloats(s.in.n, s.heads, s.head_dim, s.splits, s.in.w));
+            }
+            s.flops = 2.0 * double(s.in.n) * double(s.heads) * double(s.in.w) * double(2 * n.past_len + s.in.w + 1) * double(s.head_dim);      // (the visible keys: the work needed)
+            s.bytes = vbytes(s.in) + vbytes(s.out) + vbytes(s.in2);
+            return;
+        }
         const int64_t keys = int64_t(n.past_len) + 1;
         const bool fits = !s.in.nchw && !s.out.nchw && DecodeFastFits(s.head_dim, s.heads, s.kv_heads, n.key_mask, n.mask_value);
         s.tile = fits && keys >= kAttnDecodeMinKeys ? kAttnDecodeTile : 0;
@@ -5339,6 +5455,8 @@ std::string PlanToJson(const Plan& p) {
                 if (s.rope) o << ",\"rope\":true,\"w2_off\":" << s.w2_off;
             }
             if (s.past_len > 0) o << ",\"past_len\":" << s.past_len;
+            if (s.past_len > 0 && s.in.w > 1) o << ",\"new_len\":" << s.in.w;      // (the steps of an extend graph only)
+            if (s.chunk_causal) o << ",\"chunk_causal\":true";
             if (s.rope) o << ",\"rope_rows\":" << s.rope_rows;
             if (s.splits > 0) o << ",\"splits\":" << s.splits;
             const std::pair<const char*, const View*> views[] = {{"past_k", &s.past_k}, {"past_v", &s.past_v}, {"present_k", &s.present_k}, {"present_v", &s.present_v}, {"positions", &s.pos}};

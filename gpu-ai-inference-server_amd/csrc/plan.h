@@ -151,13 +151,19 @@ struct Step {
     // present_k / present_v = the `present.*` graph outputs (rows = past_len + in.w).  A view with buf -1 is absent.
     // KvAppend: in = the qkv tokens [N, 1, L, (H + 2 Hkv) hd]; present rows < past_len are a copy of the past, row past_len + l is k of token l after the
     // rotary embedding (rope: w_off / w2_off = the cos / sin tables [rope_rows][head_dim]) resp. v of token l, converted to fp32.  The table row of
-    // token l is pos[n] + l where pos (an INT64 graph input [N, 1]) is present, else l.  out repeats present_k.
+    // token l is its own id pos[n][l] where pos (an INT64 graph input [N, L]) is present, else l.  out repeats present_k.
     // Attention with past_len > 0 (a decode step, in.w = 1): the one query of every head attends to the past_len + 1 rows of present_k / present_v; q is
     // rotated at the same table row as the new k, cached keys are taken as they are; in2 = the key mask [N, past_len + 1].  parts = {the KvAppend step,
     // this step without parts}: tile 0 runs the parts (kv_append_kernel, attention_decode_generic_kernel), tile 4 is one launch that copies, appends
     // and attends (attention_decode_kernel) over `splits` key splits per (image, K / V head), plus the combine launch where splits > 1
+    // Attention with past_len > 0 and in.w = Lq >= 2 (an extend step: chunked prefill into a cache): chunk_causal; new token i attends to the rows
+    // j <= past_len + i of present_k / present_v (causal inside the chunk by chunk index), q rotated at its own table row; in2 = the key mask
+    // [N, past_len + Lq], pos = the INT64 positions [N, Lq], one id per token (KvAppend rotates k at the same rows).  The graph's mask constant was
+    // checked element by element at load and is not kept.  Tile 0 runs the parts (kv_append_kernel, attention_extend_generic_kernel), tile 5 the
+    // kv_append launch and attention_extend_kernel over `splits` key splits per (image, K / V head, block of 128 query rows), plus the combine
     View past_k, past_v, present_k, present_v, pos;
     int past_len = 0;
+    bool chunk_causal = false;
     int splits = 0;
     int64_t rope_rows = 0;
     // WindowAttention (kernels_wattn.hip): in = the qkv map [N, H, W, 3 D], out = [N, H, W, D]; attention inside the win_h x win_w windows of the map

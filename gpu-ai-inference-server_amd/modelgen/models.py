@@ -1213,6 +1213,30 @@ def causal_mask_constant(gb: GraphBuilder, seq: int, mask: str, max_pos: int, ta
     raise ValueError(mask)
 
 
+def chunk_causal_constant(gb: GraphBuilder, lq: int, past: int, tag: str, edit=None) -> str:
+    """The constant _make_causal_mask gives for lq new tokens behind `past` cached rows: float [1, 1, lq, past + lq], 0 in the first `past` columns
+    (every cached key is visible), in column past + j of row i 0 for j <= i and finfo(float32).min for j > i.  edit (i, j, value): one element
+    overwritten (tests: a constant the planner refuses)"""
+    c = np.zeros((lq, past + lq), np.float32)
+    c[:, past:] = np.triu(np.full((lq, lq), FLOAT32_MIN, np.float32), 1)
+    if edit is not None:
+        c[edit[0], edit[1]] = edit[2]
+    return gb.init(tag + "_mask", c.reshape(1, 1, lq, past + lq))
+
+
+def chunk_causal_mask(gb: GraphBuilder, ext: str, lq: int, past: int, tag: str, *, form: str = "where", fill: float = FLOAT32_MIN, edit=None) -> str:
+    """The 4-D mask of an extend step as AttentionMaskConverter.to_4d lowers it with a past: M = Where(Cast(ext, to=BOOL), finfo.min, C) [N, 1, lq,
+    past + lq], ext = bert_extended_mask's [N, 1, 1, past + lq] chain (non-zero on a masked key), C = chunk_causal_constant (edit: its).  M holds only
+    0 and finfo.min, never -inf.  form "add": Add(ext, C), which sums two finfo.min to -inf on a masked key of the future (a spelling the planner refuses)"""
+    c = chunk_causal_constant(gb, lq, past, tag, edit)
+    if form == "add":
+        return gb.simple("Add", [ext, c])
+    if form != "where":
+        raise ValueError(form)
+    cond = gb.simple("Cast", [ext], [pb.attr_int("to", pb.BOOL)])
+    return gb.simple("Where", [cond, gb.init(tag + "_mask_fill", np.array(fill, np.float32)), c])
+
+
 def gpt2_attention(gb: GraphBuilder, x: str, seq: int, dim: int, heads: int, tag: str, *, mask: str | None = "where_slice", scale: str = "div",
                    ktrans: str = "two", split_attr: bool = True, max_pos: int = 1024, linear=None, mask_swap: bool = False) -> str:
     """GPT2Attention (eager) behind its c_attn Linear: Split(axis 2) of the [N, L, 3 dim] rows (split_attr: the sizes as an input, else omitted as
@@ -1485,19 +1509,33 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
                      K = Concat(past key, rope(k), axis 2), V = Concat(past value, v, axis 2), both outputs present.{i}.* [N, Hkv, P + 1, hd] and both
                      read by repeat_kv; cos / sin = Unsqueeze(Gather(table [max_pos, hd], position_ids, axis 0), axes [1]); the mask is BERT's chain
                      Mul(Sub(1, Cast(Unsqueeze(attention_mask, [1, 2]))), finfo.min) added to the scores [N, H, 1, P + 1] (no triangular constant at
-                     one query).  The client writes the last row of present.* into its cache at row `len`; valid rows may sit anywhere in the cache"""
+                     one query).  The client writes the last row of present.* into its cache at row `len`; valid rows may sit anywhere in the cache
+      past=P, seq=Lq >= 2   an extend step (chunked prefill into a cache, the next turn of a conversation, scoring Lq drafted tokens): input_ids
+                     [N, Lq], attention_mask [N, P + Lq], position_ids [N, Lq] (every token's own table row) and the same past inputs; logits
+                     [N, Lq, V] and present.{i}.* [N, Hkv, P + Lq, hd].  K / V and cos / sin as in the decode graph (rope_gathered takes [N, Lq]
+                     positions).  The mask is one model-level value, as AttentionMaskConverter.to_4d lowers it with a past: M = Where(Cast(ext, to=BOOL),
+                     finfo.min, C) [N, 1, Lq, P + Lq] with ext the chain above and C = chunk_causal_constant (0 on the P cached columns, the causal
+                     triangle of finfo.min on the Lq new ones); every layer adds M to its scores.  M holds only 0 and finfo.min, never -inf.  Causality
+                     inside the chunk goes by chunk index, not by position_ids.  The client writes rows P .. P + Lq - 1 of present.* into its cache at
+                     row `len`; right- and left-padded caches both work.  A ragged batch pads the chunk on the right with the padded tokens' own mask
+                     columns 0: the output rows of such tokens are finite and otherwise unspecified (the graph gives a uniform average there, and
+                     nobody reads it)"""
     gb = GraphBuilder("llama", seed)
     hd = dim // heads
     emb = np.float32(table_std) * rng.gaussish(seed, "embed_tokens", vocab * dim).reshape(vocab, dim).astype(np.float32)
     x = gb.simple("Gather", [gb.init("embed_tokens", emb), "input_ids"], [pb.attr_int("axis", 0)])
     ext = None
     if past is not None:
-        if past < 1 or seq != 1:
-            raise ValueError("a decode graph has past >= 1 cached rows and seq = 1 new token")
+        if past < 1 or seq < 1:
+            raise ValueError("a graph with a cache has past >= 1 cached rows and seq >= 1 new tokens")
         if mask in ("add", "input"):
             ext = bert_extended_mask(gb, unsqueeze="one")
         elif mask is not None:
             raise ValueError(mask)
+        if seq > 1:
+            if ext is None or rope == "none" or positions != "input":
+                raise ValueError("an extend graph (past with seq > 1) has the attention_mask and position_ids inputs: without the mask its new tokens would see each other's future")
+            ext = chunk_causal_mask(gb, ext, seq, past, "chunk")
         if rope == "none":
             cs = None
         elif positions == "input":
@@ -1538,8 +1576,8 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
         for li in range(depth):
             outs += [(f"present.{li}.key", [batch, kv_heads, rows, hd]), (f"present.{li}.value", [batch, kv_heads, rows, hd])]
     if past is not None:
-        ins += [("attention_mask", [batch, past + 1], ONNX_INT64)] if ext is not None else []
-        ins += [("position_ids", [batch, 1], ONNX_INT64)] if cs is not None and positions == "input" else []
+        ins += [("attention_mask", [batch, past + seq], ONNX_INT64)] if ext is not None else []
+        ins += [("position_ids", [batch, seq], ONNX_INT64)] if cs is not None and positions == "input" else []
         for li in range(depth):
             ins += [(f"past_key_values.{li}.key", [batch, kv_heads, past, hd]), (f"past_key_values.{li}.value", [batch, kv_heads, past, hd])]
     return gb.finish(ins, outs, opset=opset)
