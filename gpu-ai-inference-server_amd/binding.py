@@ -71,7 +71,8 @@ ABI_SYMBOLS = [
     "ModelLoad", "ModelUnload",
 ]
 EXT_SYMBOLS = ["EngineDescribeModel", "EnginePrepare", "EngineRunPrepared", "EngineSynchronize", "EngineGetStream",
-               "EngineProfile", "EngineGetWeightBlob", "EngineWeightsUpdated", "EngineGetPrecision", "EngineMemcpy", "EngineReadBuffer", "EngineMfmaPeak", "EngineGetBatcherStats", "EngineGetShardStats", "EngineGetRuntimeInfo", "EngineE4m3RoundTrip", "EnginePlanWeights", "EngineVectorAdd"]
+               "EngineProfile", "EngineGetWeightBlob", "EngineWeightsUpdated", "EngineGetPrecision", "EngineMemcpy", "EngineReadBuffer", "EngineMfmaPeak", "EngineGetBatcherStats", "EngineGetShardStats", "EngineGetRuntimeInfo", "EngineE4m3RoundTrip", "EnginePlanWeights", "EngineVectorAdd",
+               "EngineKvCacheCreate", "EngineKvCacheDestroy", "EngineKvCacheBind", "EngineKvCacheGetLengths", "EngineKvCacheSetLengths", "EngineKvCacheRead", "EngineKvCacheWrite"]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -612,6 +613,86 @@ def RuntimeInfo(model: Model, checksums: bool = False) -> dict:
         return json.loads(C.string_at(p).decode())
     finally:
         lib().FreeErrorMessage(p)
+
+
+KV_CACHE_SYMBOLS = [s for s in EXT_SYMBOLS if s.startswith("EngineKvCache")]
+_kv_declared = False
+
+
+def _kv_lib() -> C.CDLL:
+    """lib() with the prototypes of the resident KV cache calls (include/inference_engine_ext.h), declared on first use"""
+    global _kv_declared
+    L = lib()
+    if not _kv_declared:
+        vp, ep, i64p = C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)
+        sig = {
+            "EngineKvCacheCreate": (vp, [C.c_int] * 6 + [ep]), "EngineKvCacheDestroy": (None, [vp]), "EngineKvCacheBind": (C.c_bool, [vp, vp, ep]),
+            "EngineKvCacheGetLengths": (C.c_bool, [vp, i64p, ep]), "EngineKvCacheSetLengths": (C.c_bool, [vp, i64p, ep]),
+            "EngineKvCacheRead": (C.c_bool, [vp, C.c_int, C.c_int, vp, C.c_size_t, ep]), "EngineKvCacheWrite": (C.c_bool, [vp, C.c_int, C.c_int, vp, C.c_size_t, ep]),
+        }
+        for name, (res, args) in sig.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _kv_declared = True
+    return L
+
+
+class KvCache:
+    """A resident KV cache (EngineKvCache*): per layer K and V, dense fp32 [batch, kv_heads, capacity, head_dim] in HBM, appended in place by the models
+    bound to it; the valid length of every image lives in the object.  A bound model's Infer takes no past_key_values.* and gives no present.*."""
+
+    def __init__(self, layers: int, batch: int, kv_heads: int, capacity: int, head_dim: int, device_id: int = 0):
+        err = C.c_void_p()
+        self.shape = (int(batch), int(kv_heads), int(capacity), int(head_dim))
+        self.layers = int(layers)
+        self.handle = _kv_lib().EngineKvCacheCreate(int(device_id), int(layers), *self.shape, C.byref(err))
+        if not self.handle:
+            raise RuntimeError(_take_error(err))
+
+    def _call(self, fn, *args):
+        if not self.handle:
+            raise RuntimeError("KV cache destroyed")
+        err = C.c_void_p()
+        if not fn(*args, C.byref(err)):
+            raise RuntimeError(_take_error(err))
+
+    def bind(self, model: Model) -> None:
+        self._call(_kv_lib().EngineKvCacheBind, model.handle, self.handle)
+
+    @staticmethod
+    def unbind(model: Model) -> None:
+        err = C.c_void_p()
+        if not _kv_lib().EngineKvCacheBind(model.handle, None, C.byref(err)):
+            raise RuntimeError(_take_error(err))
+
+    def lengths(self) -> list:
+        out = (C.c_int64 * self.shape[0])()
+        self._call(_kv_lib().EngineKvCacheGetLengths, self.handle, out)
+        return [int(x) for x in out]
+
+    def set_lengths(self, lens) -> None:
+        lens = [int(x) for x in lens]
+        if len(lens) != self.shape[0]:
+            raise ValueError(f"{self.shape[0]} lengths expected")
+        self._call(_kv_lib().EngineKvCacheSetLengths, self.handle, (C.c_int64 * len(lens))(*lens))
+
+    def read(self, layer: int, which: int) -> np.ndarray:
+        """layer's K (which 0) or V (which 1) as it sits in HBM, [batch, kv_heads, capacity, head_dim]"""
+        out = np.empty(self.shape, np.float32)
+        self._call(_kv_lib().EngineKvCacheRead, self.handle, int(layer), int(which), out.ctypes.data, out.nbytes)
+        return out
+
+    def write(self, layer: int, which: int, x: np.ndarray) -> None:
+        x = np.ascontiguousarray(x, np.float32)
+        if x.shape != self.shape:
+            raise ValueError(f"shape {self.shape} expected, got {x.shape}")
+        self._call(_kv_lib().EngineKvCacheWrite, self.handle, int(layer), int(which), x.ctypes.data, x.nbytes)
+
+    def destroy(self) -> None:
+        if self.handle:
+            _kv_lib().EngineKvCacheDestroy(self.handle)
+            self.handle = None
 
 
 def CopyToDevice(model: Model, dst_dev: int, src: np.ndarray) -> None:

@@ -196,19 +196,25 @@ bool ModelInfer(ModelHandle handle, const TensorData* inputs, int num_inputs, Te
     if (!inputs || num_inputs <= 0 || !outputs || num_outputs <= 0) { set_error(error, "Invalid parameters"); return false; }
     try {
         ModelObj::Pending req;
-        bool batched = false;
+        bool batched = false, bound = false;
         {
             std::shared_lock<std::shared_mutex> g(M.life);
             if (!M.loaded.load() || M.lanes.empty()) { set_error(error, "Model not loaded"); return false; }
             auto failv = [&](const std::string& msg) { M.SetError(msg); set_error(error, msg); return false; };
             // ---- ValidateInputs (model.cpp:734-794): count, then names ----
             const auto& gin = M.info.inputs;
-            if (size_t(num_inputs) != gin.size())
-                return failv("Expected " + std::to_string(gin.size()) + " inputs, got " + std::to_string(num_inputs));
+            // a model bound to a resident KV cache takes the graph's inputs without the cache ones: those are not inputs of the request at all
+            bound = M.kv != nullptr;
+            std::vector<char> hidden(gin.size(), 0);
+            size_t expected = gin.size();
+            for (size_t k = 0; bound && k < gin.size(); ++k)
+                if (kv_past_name(gin[k].name)) { hidden[k] = 1; --expected; }
+            if (size_t(num_inputs) != expected)
+                return failv("Expected " + std::to_string(expected) + " inputs, got " + std::to_string(num_inputs));
             for (int i = 0; i < num_inputs; ++i) {
                 const std::string nm = inputs[i].name ? inputs[i].name : "";
                 bool known = false;
-                for (auto& vi : gin) if (vi.name == nm) known = true;
+                for (size_t k = 0; k < gin.size(); ++k) if (gin[k].name == nm && !hidden[k]) known = true;
                 if (!known) return failv("Unexpected input name: " + nm);
             }
             // ---- InferONNX (model.cpp:1158-1328): order inputs by graph index ----
@@ -237,7 +243,7 @@ bool ModelInfer(ModelHandle handle, const TensorData* inputs, int num_inputs, Te
                 }
             }
             for (size_t k = 0; k < gin.size() && req.err.empty(); ++k)
-                if (!provided[k]) req.err = "Required input tensor not provided: " + gin[k].name;
+                if (!provided[k] && !hidden[k]) req.err = "Required input tensor not provided: " + gin[k].name;
             // ---- INT64 ids: the payload size against the request's own [N, L], then every id against its table, before anything is enqueued ----
             for (size_t k = 0; k < gin.size() && req.err.empty(); ++k) {
                 if (gin[k].elem_type != ie::ONNX_INT64) continue;
@@ -263,7 +269,7 @@ bool ModelInfer(ModelHandle handle, const TensorData* inputs, int num_inputs, Te
                 }
             }
             // coalescing needs one common leading (batch) dimension and the declared ranks
-            batched = req.err.empty() && M.batchable && M.max_batch > 1;
+            batched = req.err.empty() && M.batchable && M.max_batch > 1 && !bound;
             if (batched) {
                 req.rows = req.shapes[0].empty() ? 0 : req.shapes[0][0];
                 for (size_t k = 0; k < gin.size(); ++k)
@@ -277,7 +283,8 @@ bool ModelInfer(ModelHandle handle, const TensorData* inputs, int num_inputs, Te
         const auto t0 = std::chrono::steady_clock::now();
         const RoctxRange range("ModelInfer:" + M.name);
         if (req.err.empty()) {
-            if (batched) M.RunBatched(req);
+            if (bound) RunBound(M, req);
+            else if (batched) M.RunBatched(req);
             else { std::vector<ModelObj::Pending*> one{&req}; M.Execute(one); }
         }
         const int64_t ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
@@ -368,6 +375,7 @@ std::string describe_runtime(ModelObj& M, bool json, bool checksums = false) {
         }
         o << "]";
     }
+    if (up && M.kv) o << ",\"kv_cache\":" << KvCacheJson(M);      // only while a resident KV cache is bound
     o << "}";
     return o.str();
 }
@@ -588,6 +596,7 @@ bool EngineRunPrepared(ModelHandle handle, int iters, int sync, ErrorMessage* er
         // IE_MAX_INFLIGHT_REPLAYS=n: synchronise every n replays (a profiler's per-dispatch bookkeeping under deep un-synchronised graph
         // queues crashed rocprofv3 --kernel-trace: profiles/r02/graph_burst_under_kernel_trace_sigsegv.log); default: no cap
         const int cap = L0.dev()->max_inflight_replays();
+        if (M.kv) UploadStandingLens(M, *L0.dev());      // a bound model replays with the cache's lengths as they stand and does not advance them
         for (int i = 0; i < iters; ++i) {
             L0.dev()->Enqueue(*L0.dev()->current());
             if (cap > 0 && (i + 1) % cap == 0) L0.dev()->Synchronize();
@@ -625,6 +634,7 @@ char* EngineProfile(ModelHandle handle, int iters, ErrorMessage* error) {
         ModelObj& M = *handle->model;
         Lane0 L0(M);
         if (!L0.dev() || !L0.dev()->current()) { set_error(error, "Model not prepared"); return nullptr; }
+        if (M.kv) UploadStandingLens(M, *L0.dev());
         auto t = L0.dev()->Profile(*L0.dev()->current(), iters > 0 ? iters : 1);
         std::ostringstream o;
         o.precision(9);

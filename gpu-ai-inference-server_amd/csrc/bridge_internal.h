@@ -1,5 +1,5 @@
 // Internals shared by the translation units behind the C ABI (bridge.cpp: the extern "C" shims; bridge_load.cpp: load / unload, shard replicas and the
-// RCCL weight broadcast; bridge_run.cpp: lane dispatch, batch sharding and the request batcher).  Nothing here is exported.
+// RCCL weight broadcast; bridge_run.cpp: lane dispatch, batch sharding and the request batcher; bridge_kv.cpp: the resident KV cache).  Nothing here is exported.
 #pragma once
 #include <atomic>
 #include <cctype>
@@ -173,7 +173,31 @@ inline uint64_t fnv1a64(const void* data, size_t n) {
     return h;
 }
 
+struct ModelObj;
+
+}  // namespace ie_bridge
+
+// A resident KV cache (include/inference_engine_ext.h EngineKvCache*, bridge_kv.cpp): the storage in HBM, the per-image valid lengths on the
+// host, and the models bound to it.  `mu` serialises everything that reads or writes lengths or storage: the bound models' requests, Read, Write,
+// Get / SetLengths.  Lock order: a model's `life`, then `mu`.
+struct EngineKvCache {
+    std::shared_ptr<ie::KvBinding> dev;      // geometry, per-layer K / V and the device length array
+    int device_id = 0;
+    hipStream_t stream = nullptr;            // Read / Write / the zero fill (never the legacy stream: executor.h CopySync)
+    std::mutex mu;
+    std::vector<int64_t> lens;               // [batch]
+    std::vector<int> upload;                 // the 2 x batch ints on their way to dev->d_lens
+    std::vector<std::weak_ptr<ie_bridge::ModelObj>> bound;
+    size_t bytes = 0;
+};
+
+namespace ie_bridge {
+
 struct ModelObj {
+    // the resident cache this model is bound to (null: none), and what the graph appends per call: kv_lq new tokens behind kv_past cache rows (0: a
+    // prefill with `present` outputs).  Written under `life` held exclusively, read under it held shared.
+    EngineKvCache* kv = nullptr;
+    int kv_lq = 0, kv_past = 0;
     std::string path;
     ModelType type = MODEL_UNKNOWN;
     DeviceType device = DEVICE_GPU;
@@ -251,6 +275,16 @@ struct ModelObj {
 // outputs by index, in graph-output order (bridge:787-813); never writes past the caller's dims array  (bridge_run.cpp)
 void write_out_dims(TensorData* outputs, int num_outputs, const std::vector<ie::IoDesc>& odesc, int64_t rows);
 
+// ---- a model bound to a resident cache (bridge_kv.cpp); the caller holds M.life shared unless said otherwise ----
+inline bool kv_past_name(const std::string& n) { return n.compare(0, 16, "past_key_values.") == 0; }
+inline bool kv_present_name(const std::string& n) { return n.compare(0, 8, "present.") == 0; }
+// ModelInfer's request on a bound model, validated as far as an unbound one is: the mask check, the forward on lane 0 without the cache inputs and
+// `present` outputs, the new lengths.  Takes M.life itself.  Sets req.ok / req.err
+void RunBound(ModelObj& M, ModelObj::Pending& req);
+// EngineRunPrepared / EngineProfile on a bound model: the lengths as they stand go to the device, with as many new tokens as still fit
+void UploadStandingLens(ModelObj& M, ie::DeviceModel& D);
+std::string KvCacheJson(ModelObj& M);       // the "kv_cache" member of EngineGetRuntimeInfo
+void KvForget(ModelObj& M);                 // Unload (M.life held exclusively): the cache forgets the model
 }  // namespace ie_bridge
 
 #define NCCL_OK(call)                                                                                             \

@@ -261,6 +261,7 @@ bool ModelObj::Load() {
 void ModelObj::Unload() {
     std::unique_lock<std::shared_mutex> g(life);      // waits for every in-flight ModelInfer (they hold it shared)
     workers.Stop();
+    KvForget(*this);                                   // a resident KV cache the model was bound to lives on without it
     lanes.clear();
     pool.Reset(0);
     onnx.reset();

@@ -184,8 +184,68 @@ void DeviceModel::ZeroSync(void* dst, size_t bytes, const char* what) {
 }
 
 // Plan + allocate one instance (and, the first time on this device, put the packed weights into HBM).
+namespace {
+// the layer i of a cache tensor's graph name, `past_key_values.<i>.key|value` or `present.<i>.key|value` (-1: another name)
+int kv_layer_of(const std::string& name) {
+    for (const char* prefix : {"past_key_values.", "present."}) {
+        const size_t n = std::strlen(prefix);
+        if (name.compare(0, n, prefix) != 0) continue;
+        const size_t dot = name.find('.', n);
+        if (dot == std::string::npos || dot == n || dot - n > 6) return -1;
+        for (size_t k = n; k < dot; ++k) if (name[k] < '0' || name[k] > '9') return -1;
+        return std::atoi(name.substr(n, dot - n).c_str());
+    }
+    return -1;
+}
+
+// The cache steps of an instance built for a bound lane run in place: the layer is the one named by the step's `past` graph input (a prefill with a
+// cache: by its `present` graph output).  A step whose tensors are not of the bound geometry is an error here, before anything is allocated.
+void MarkInplace(PlanInstance& pi) {
+    const KvBinding& kv = *pi.kv;
+    auto layer_of = [&](const View& v, const std::vector<IoDesc>& ios) {
+        for (const IoDesc& d : ios) if (d.view.buf == v.buf && d.view.c_off == v.c_off) return kv_layer_of(d.name);
+        return -1;
+    };
+    auto mark = [&](Step& s) {
+        if (s.kind != StepKind::KvAppend && !(s.kind == StepKind::Attention && s.past_len > 0)) return;
+        const int layer = s.past_k.buf >= 0 ? layer_of(s.past_k, pi.plan.inputs) : layer_of(s.present_k, pi.plan.outputs);
+        const int hkv = s.kv_heads > 0 ? s.kv_heads : s.heads;
+        const bool fits = layer >= 0 && layer < kv.layers && s.in.n == kv.batch && hkv == kv.kv_heads && s.head_dim == kv.head_dim &&
+                          (s.past_len > 0 ? s.past_len == kv.capacity : s.in.w <= kv.capacity);
+        if (!fits) throw std::runtime_error("the cache step " + s.name + " does not fit the bound KV cache (layer " + std::to_string(layer) + ")");
+        s.inplace = true;
+        s.kv_layer = layer;
+    };
+    for (Step& s : pi.plan.steps) {
+        mark(s);
+        for (Step& q : s.parts) mark(q);
+    }
+}
+}  // namespace
+
+void DeviceModel::BindKvCache(std::shared_ptr<const KvBinding> kv) {
+    check(hipSetDevice(device_), "hipSetDevice");
+    check(hipStreamSynchronize(copy_stream_), "hipStreamSynchronize");
+    check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    for (auto& p : plans_) FreeInstance(*p.second);
+    plans_.clear();
+    lru_.clear();
+    current_ = nullptr;
+    kv_ = std::move(kv);
+}
+
+void DeviceModel::UploadKvLens(const int* host) {
+    if (!kv_) throw std::runtime_error("internal error: no KV cache is bound");
+    check(hipSetDevice(device_), "hipSetDevice");
+    check(hipMemcpyAsync(kv_->d_lens, host, size_t(2 * kv_->batch) * sizeof(int), hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(kv lengths)");
+}
+
 void DeviceModel::BuildInstance(PlanInstance& pi, const std::vector<std::vector<int64_t>>& shapes) {
     pi.plan = BuildPlan(*model_, shapes, precision_);
+    if (kv_) {
+        pi.kv = kv_;
+        MarkInplace(pi);
+    }
     {
         std::lock_guard<std::mutex> g(w_->tune_mu);     // lanes of one device may be built concurrently
         if (!w_->d_weights) {
@@ -591,6 +651,7 @@ void DeviceModel::PrepareF8(const std::vector<float>* adopt) {
 void DeviceModel::EnsurePipeline(PlanInstance& pi, bool allow_tune) {
     if (pi.pipeline_tried) return;
     pi.pipeline_tried = true;
+    if (pi.kv) return;       // a bound instance: the cache's length arrays are indexed by the image of the whole batch
     if (pipeline_chunks_ < 2 || pi.plan.inputs.empty() || pi.plan.steps.size() < 4) return;
     const int64_t B = pi.plan.inputs[0].dims.empty() ? 0 : pi.plan.inputs[0].dims[0];
     for (auto& d : pi.plan.inputs) if (d.dims.empty() || d.dims[0] != B || d.view.n != B) return;

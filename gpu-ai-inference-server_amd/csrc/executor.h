@@ -100,8 +100,18 @@ struct LaunchRole {
 // reached the <noun> kernels" (nullptr: the family has no such guard)
 struct TiledNames { const char* label; const char* fp8_noun; };
 
+// A resident KV cache as the lanes see it: per layer the dense fp32 K and V [batch][kv_heads][capacity][head_dim] in HBM, and the device
+// array of 2 x batch ints the kernels read an image's valid length (first half) and the tokens it may append (second half) from.  The bridge owns the
+// memory; a lane holds a reference while it is bound.
+struct KvBinding {
+    int layers = 0, batch = 0, kv_heads = 0, capacity = 0, head_dim = 0;
+    std::vector<float*> k, v;
+    int* d_lens = nullptr;
+};
+
 struct PlanInstance {
     Plan plan;
+    std::shared_ptr<const KvBinding> kv;   // the cache the instance was built for (null: none): its cache steps are marked Step::inplace
     std::vector<LaunchRole> roles;     // per plan step; empty = every step launches on its own
     std::vector<float*> buffers;       // device activation buffers (plan.buffer_floats); aliased entries are not owned
     std::vector<char> owned;           // buffers[i] was hipMalloc'ed by this instance
@@ -164,6 +174,13 @@ public:
     struct InSeg { const void* host; size_t have, need, dev_off; bool u8 = false; };   // u8: have/need/dev_off count bytes = elements
     struct OutSeg { void* host; size_t cap, need, dev_off; };
     void InferHostSegments(PlanInstance& pi, const std::vector<std::vector<InSeg>>& in, const std::vector<std::vector<OutSeg>>& out);
+
+    // Bind the lane to a resident cache (null: unbind).  Every plan instance is dropped: the next Prepare builds instances whose cache steps run in place
+    // (or, unbound, as the plan says).  UploadKvLens enqueues the 2 x batch ints of KvBinding::d_lens on the compute stream, in front of the next forward;
+    // `host` must stay as it is until that forward has been waited for.
+    __attribute__((visibility("hidden"))) void BindKvCache(std::shared_ptr<const KvBinding> kv);
+    __attribute__((visibility("hidden"))) void UploadKvLens(const int* host);
+    __attribute__((visibility("hidden"))) const std::shared_ptr<const KvBinding>& kv_cache() const { return kv_; }
 
     hipStream_t stream() const { return stream_; }
     int device() const { return device_; }
@@ -263,7 +280,8 @@ private:
     std::vector<std::vector<int64_t>> lru_;
     size_t max_plans_ = 8;
     PlanInstance* current_ = nullptr;
-    void* pinned_ = nullptr;           // pinned host staging for D2H results
+    std::shared_ptr<const KvBinding> kv_;   // the resident cache this lane is bound to
+    void* pinned_ = nullptr;          // pinned host staging for D2H results
     size_t pinned_bytes_ = 0;
     int64_t pipelined_calls_ = 0;
     int last_chunks_ = 1, last_head_steps_ = 0;

@@ -451,6 +451,14 @@ struct DecodeArgs {
     int splits = 1;                    // tile 4: key splits per (image, K / V head)
     float* workspace = nullptr;        // tile 4, splits > 1: the split records
     int64_t workspace_floats = 0;
+    // In place (a model bound to a resident cache): cache_rows > 0.  past_k == present_k and past_v == present_v are the resident cache
+    // [N][kv_heads][cache_rows][head_dim]; image n holds lens[n] valid rows and the step appends its first min(news[n], new_len) tokens at the rows
+    // lens[n] + i; past_len stays the graph's P (the mask has P + new_len columns, the new tokens' at P + i).  Key j is visible to new token i iff
+    // (j < lens[n] and mask[n][j]) or lens[n] <= j <= lens[n] + min(i, c - 1); no kernel reads a row at or beyond lens[n] + c.  The host keeps
+    // lens[n] + c <= cache_rows; the kernels write no row at or beyond cache_rows whatever the arrays hold
+    int64_t cache_rows = 0;
+    const int* lens = nullptr;         // [N], device
+    const int* news = nullptr;         // [N], device
 };
 // A decode step's tiles: 0 = attention_decode_generic_kernel (one wave per (image, query head) over `present`, which a kv_append launch wrote: any
 // head_dim up to kDecodeMaxHeadDim, any past_len, float or half); kAttnDecodeTile (4) = attention_decode_kernel<T, HD, G>: a workgroup = (image, K / V

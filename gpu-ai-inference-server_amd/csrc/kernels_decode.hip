@@ -27,6 +27,13 @@
 //                                        S == 1: the workgroup writes the token row.  S > 1: it writes (m, l, o[hd]) per query head into the workspace and
 //   attention_decode_combine_kernel<T>   adds the S records of a query head in split order.  No atomics: the result is bit-identical from run to run.
 //
+// In place (DecodeArgs::cache_rows > 0: the model is bound to a resident cache): past and present are one storage with its own row stride, the
+// image's valid length len and the tokens c it appends come from two device arrays, and nothing of the cache is copied.
+//   kv_append_rows_kernel<T, V>          writes the rotated k and the v of the tokens i < c at the rows len + i and touches nothing else.
+//   attention_inplace_generic_kernel<T>  tile 0 of a decode and of an extend step: the wave of the generic kernels over the rows the token may see.
+//   attention_decode_kernel<.., true>    tile 4 without the `present` store: the key loop covers [0, len), one workgroup writes row len from registers.
+//   attention_extend_kernel<.., true>    tile 5 behind the kv_append_rows launch, its causal limit counted from len.
+//
 // Scores, statistics and accumulation are fp32.  The key-mask bias (1 - float(mask[n, j])) * c is added to the scaled score in fp32 and the sum clamped
 // at -FLT_MAX, as the MASK forms of kernels_attn.hip keep it finite: the running maximum starts at -FLT_MAX too, so a split (or a whole row) whose
 // keys are all masked has m = -FLT_MAX, l = its key count and o = the plain sum of its V rows; next to a split with a real score its weight
@@ -100,6 +107,51 @@ __global__ __launch_bounds__(kDecodeBlock) void kv_append_kernel(const DecodeArg
         return;
     }
     const int l = row - P;
+    const bool rope = a.rope_cos != nullptr;
+    const int64_t r = rope ? rope_row(a, n, l) : 0;
+    const int64_t kb = qkv_base(a, n, l, 1, kvh), vb = qkv_base(a, n, l, 2, kvh);
+    float k[V], v[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        k[j] = rotated<T>(a, kb, r, ev * V + j, rope);
+        v[j] = float(reinterpret_cast<const T*>(a.in.p)[vb + int64_t(ev * V + j) * a.in.sc]);
+    }
+    if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(a.present_k + o) = make_float4(k[0], k[1], k[2], k[3]);
+        *reinterpret_cast<float4*>(a.present_v + o) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        a.present_k[o] = k[0];
+        a.present_v[o] = v[0];
+    }
+}
+
+// In place: image n's valid rows and the tokens this step appends, clamped so that whatever the two arrays hold no kernel leaves the cache:
+// 0 <= len <= cache_rows, 0 <= c <= min(new_len, cache_rows - len)
+struct Resident { int len, c; };
+__device__ __forceinline__ Resident resident(const DecodeArgs& a, int64_t n) {
+    const int rows = int(a.cache_rows);
+    int len = a.lens[n], c = a.news[n];
+    len = len < 0 ? 0 : (len > rows ? rows : len);
+    c = c > a.new_len ? a.new_len : c;
+    c = c > rows - len ? rows - len : c;
+    return {len, c < 0 ? 0 : c};
+}
+
+// In place: one lane per V consecutive floats of the step's new rows [N][Hkv][new_len][hd].  Token l < c of image n: k after the rotary embedding and v
+// go to row len + l of the cache (kv_append_kernel's arithmetic); a token l >= c and every other row of the cache: untouched
+template <typename T, int V>
+__global__ __launch_bounds__(kDecodeBlock) void kv_append_rows_kernel(const DecodeArgs a, const int64_t total) {
+    const int64_t i = int64_t(blockIdx.x) * kDecodeBlock + threadIdx.x;      // ((n Hkv + kvh) new_len + l) hd / V + ev
+    if (i >= total) return;
+    const int hd = a.head_dim, vpr = hd / V;
+    const int ev = int(i % vpr);
+    const int l = int((i / vpr) % a.new_len);
+    const int64_t nh = i / (int64_t(vpr) * a.new_len);      // n Hkv + kvh
+    const int kvh = int(nh % a.kv_heads);
+    const int64_t n = nh / a.kv_heads;
+    const Resident rs = resident(a, n);
+    if (l >= rs.c) return;
+    const int64_t o = (nh * a.cache_rows + rs.len + l) * hd + int64_t(ev) * V;
     const bool rope = a.rope_cos != nullptr;
     const int64_t r = rope ? rope_row(a, n, l) : 0;
     const int64_t kb = qkv_base(a, n, l, 1, kvh), vb = qkv_base(a, n, l, 2, kvh);
@@ -196,10 +248,76 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_generic_kernel(
     attend_wave<T>(a, nh / a.heads, int(nh % a.heads), i, a.past_len + i + 1, a.past_len + Lq);
 }
 
+// In place, tile 0 of a decode step (new_len = 1) and of an extend step alike: rows = N * heads * new_len, one wave per (image, query head, new token i), the
+// token fastest, over the resident cache a kv_append_rows launch has appended to.  The wave walks the rows [0, len + min(i, c - 1)] and no other: a
+// row below len carries its mask column's bias, a new row none (its column is one of the prefix of ones); a token with nothing visible writes zeros
+template <typename T>
+__global__ __launch_bounds__(kDecodeBlock) void attention_inplace_generic_kernel(const DecodeArgs a, const int64_t rows) {
+    constexpr int kChunks = kDecodeMaxHeadDim / 64;
+    const int64_t row = int64_t(blockIdx.x) * (kDecodeBlock / 64) + threadIdx.x / 64;
+    if (row >= rows) return;                       // wave-uniform
+    const int Lq = a.new_len, i = int(row % Lq), lane = int(threadIdx.x) % 64, hd = a.head_dim;
+    const int64_t nh = row / Lq, n = nh / a.heads;
+    const int h = int(nh % a.heads), kvh = h / (a.heads / a.kv_heads);
+    const Resident rs = resident(a, n);
+    const int Lk = rs.len + (i < rs.c ? i : rs.c - 1) + 1;
+    const float* K = a.present_k + (n * a.kv_heads + kvh) * a.cache_rows * hd;
+    const float* Vp = a.present_v + (n * a.kv_heads + kvh) * a.cache_rows * hd;
+    const bool rope = a.rope_cos != nullptr;
+    const int64_t r = rope ? rope_row(a, n, i) : 0;
+    const int64_t qb = qkv_base(a, n, i, 0, h);
+    float q[kChunks], acc[kChunks];
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c) {
+        const int e = c * 64 + lane;
+        q[c] = e < hd ? rotated<T>(a, qb, r, e, rope) * a.scale : 0.f;
+        acc[c] = 0.f;
+    }
+    float shift = 0.f;
+    if (a.mask) {
+        float bm = Lk > rs.len ? 0.f : -kFltMax;   // (a visible new row has the bias 0)
+        for (int j = lane; j < rs.len; j += 64) bm = fmaxf(bm, key_bias(a, n, j));
+#pragma unroll
+        for (int x = 32; x >= 1; x >>= 1) bm = fmaxf(bm, __shfl_xor(bm, x, 64));
+        shift = fabsf(bm) <= kMaskShiftMax ? bm : 0.f;
+    }
+    float m = -kFltMax, l = 0.f;
+    for (int j = 0; j < Lk; ++j) {
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < kChunks; ++c) {
+            const int e = c * 64 + lane;
+            if (e < hd) s = fmaf(q[c], K[int64_t(j) * hd + e], s);
+        }
+#pragma unroll
+        for (int x = 32; x >= 1; x >>= 1) s += __shfl_xor(s, x, 64);
+        if (a.mask) s = fmaxf(s + ((j < rs.len ? key_bias(a, n, j) : 0.f) - shift), -kFltMax);
+        const float mn = fmaxf(m, s), al = __expf(m - mn), p = __expf(s - mn);
+        l = l * al + p;
+#pragma unroll
+        for (int c = 0; c < kChunks; ++c) {
+            const int e = c * 64 + lane;
+            if (e < hd) acc[c] = fmaf(p, Vp[int64_t(j) * hd + e], acc[c] * al);
+        }
+        m = mn;
+    }
+    T* out = reinterpret_cast<T*>(a.out.p);
+    const int64_t ob = n * a.out.sn + int64_t(i) * a.out.sw + int64_t(h) * hd * a.out.sc;
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c) {
+        const int e = c * 64 + lane;
+        if (e < hd) out[ob + int64_t(e) * a.out.sc] = T(acc[c] * inv);
+    }
+}
+
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
 
-// grid = (splits, Hkv, N)
-template <typename T, int HD, int G>
+// grid = (splits, Hkv, N).  INPLACE: the form of a step bound to a resident cache, which is read where it lives and of which nothing is stored again.  The S
+// splits share the image's len cached keys in whole key tiles at run time (the grid is the plan's: a split beyond them has no keys and writes
+// (-FLT_MAX, 0, 0), which the combine weights with exactly 0); no workgroup reads a row at or beyond len, so the one row that is written (row len, by
+// one workgroup, from registers) is read by nobody in this launch
+template <typename T, int HD, int G, bool INPLACE = false>
 __global__ __launch_bounds__(kDecodeBlock) void attention_decode_kernel(const DecodeArgs a) {
     constexpr int LPK = HD / 4;                    // lanes of one key row
     constexpr int KPW = 64 / LPK;                  // key slots of a wave
@@ -212,7 +330,10 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_decode_kernel(const De
     const int64_t n = blockIdx.z;
     const int lane = int(threadIdx.x) % 64, wave = int(threadIdx.x) / 64;
     const int sub = lane / LPK, el = lane % LPK, slot = wave * KPW + sub;
-    const int g = a.heads / a.kv_heads, P = a.past_len, Lk = P + 1;
+    const int g = a.heads / a.kv_heads;
+    Resident rs = {0, 0};
+    if constexpr (INPLACE) rs = resident(a, n);
+    const int P = INPLACE ? rs.len : a.past_len, Lk = INPLACE ? P : P + 1;      // in place: the cached keys alone, the new one comes from registers below
     const int tiles = (Lk + KT - 1) / KT, per = (tiles + S - 1) / S;
     const int k0 = sp * per * KT, k1 = min(Lk, (sp + 1) * per * KT);      // this split's keys (none where per * S overshoots)
     const bool rope = a.rope_cos != nullptr;
@@ -233,10 +354,10 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_decode_kernel(const De
 #pragma unroll
     for (int gi = 0; gi < G; ++gi) { m[gi] = -kFltMax; l[gi] = 0.f; o[gi] = make_float4(0.f, 0.f, 0.f, 0.f); }
     const int64_t nh = n * a.kv_heads + kvh;
-    const float* pk = a.past_k + nh * int64_t(P) * HD;
-    const float* pv = a.past_v + nh * int64_t(P) * HD;
-    float* ok = a.present_k + nh * int64_t(Lk) * HD;
-    float* ov = a.present_v + nh * int64_t(Lk) * HD;
+    const float* pk = a.past_k + nh * (INPLACE ? a.cache_rows : int64_t(P)) * HD;
+    const float* pv = a.past_v + nh * (INPLACE ? a.cache_rows : int64_t(P)) * HD;
+    float* ok = a.present_k + nh * (INPLACE ? a.cache_rows : int64_t(Lk)) * HD;
+    float* ov = a.present_v + nh * (INPLACE ? a.cache_rows : int64_t(Lk)) * HD;
     // the K / V vectors of a cached row; the next iteration's are requested before this iteration's arithmetic, so their latency lies under it
     auto load_row = [&](int j, float4& kx, float4& vx) {
         kx = *reinterpret_cast<const float4*>(pk + int64_t(j) * HD + el * 4);
@@ -249,7 +370,7 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_decode_kernel(const De
         const bool valid = j < k1;
         float4 kx = kn, vx = vn;                   // (a slot past the split's end keeps stale finite values: its scores are never used)
         if (j + KT < k1 && j + KT < P) load_row(j + KT, kn, vn);
-        if (valid) {
+        if constexpr (!INPLACE) if (valid) {
             if (j >= P) {                          // the new row: k rotated, v as it is, both fp32
                 const int64_t kb = qkv_base(a, n, 0, 1, kvh), vb = qkv_base(a, n, 0, 2, kvh);
                 const T* p = reinterpret_cast<const T*>(a.in.p);
@@ -274,6 +395,40 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_decode_kernel(const De
                 o[gi].z = fmaf(p, vx.z, o[gi].z * al);
                 o[gi].w = fmaf(p, vx.w, o[gi].w * al);
                 m[gi] = mn;
+            }
+        }
+    }
+    if constexpr (INPLACE) {
+        // the split that holds the last cached key (none cached: the last split) owns the new row: every lane builds its slice of it, slot 0 stores it
+        // at row len and attends to it.  c == 0 (a padded token, or a full cache): nothing is stored, the key is not visible
+        const int owner = tiles > 0 ? (tiles - 1) / per : S - 1;
+        if (sp == owner) {                         // workgroup-uniform
+            const int64_t kb = qkv_base(a, n, 0, 1, kvh), vb = qkv_base(a, n, 0, 2, kvh);
+            const T* p = reinterpret_cast<const T*>(a.in.p);
+            const float4 kx = make_float4(rotated<T>(a, kb, r, el * 4, rope), rotated<T>(a, kb, r, el * 4 + 1, rope), rotated<T>(a, kb, r, el * 4 + 2, rope),
+                                          rotated<T>(a, kb, r, el * 4 + 3, rope));
+            const float4 vx = make_float4(float(p[vb + int64_t(el * 4) * a.in.sc]), float(p[vb + int64_t(el * 4 + 1) * a.in.sc]), float(p[vb + int64_t(el * 4 + 2) * a.in.sc]),
+                                          float(p[vb + int64_t(el * 4 + 3) * a.in.sc]));
+            const bool mine = slot == 0 && rs.c > 0;
+            if (mine) {
+                *reinterpret_cast<float4*>(ok + int64_t(P) * HD + el * 4) = kx;
+                *reinterpret_cast<float4*>(ov + int64_t(P) * HD + el * 4) = vx;
+            }
+#pragma unroll
+            for (int gi = 0; gi < G; ++gi) {
+                const float s = group_sum<LPK>(dot4(q[gi], kx));
+                if (mine && gi < g) {
+                    const float mn = fmaxf(m[gi], s), al = __expf(m[gi] - mn), pr = __expf(s - mn);
+                    l[gi] = l[gi] * al + pr;
+                    o[gi].x = fmaf(pr, vx.x, o[gi].x * al);
+                    o[gi].y = fmaf(pr, vx.y, o[gi].y * al);
+                    o[gi].z = fmaf(pr, vx.z, o[gi].z * al);
+                    o[gi].w = fmaf(pr, vx.w, o[gi].w * al);
+                    m[gi] = mn;
+                }
+                // nothing visible at all (no cached key, no new one): the weight 1 on a zero row keeps the token's output finite, and next to a real
+                // maximum the record's weight is exactly 0
+                if (slot == 0 && P == 0 && rs.c == 0) l[gi] = 1.f;
             }
         }
     }
@@ -342,7 +497,12 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_decode_combine_kernel(
 // last token), keeps staging and waiting and only skips the key tiles.
 // S > 1: split s takes the key tiles [s per, (s + 1) per) of ceil((P + Lq) / 32), cut at the row block's last visible key, and writes (m, l, o[HD]) per
 // query row into the workspace, record ((n H + h) Lq + i) S + s; a split with nothing visible for a row writes (-FLT_MAX, 0, 0).
-template <typename T, int HD>
+// INPLACE: behind a kv_append_rows launch, over the resident cache with its own row stride.  The image's len and c come
+// from the device arrays, so every limit above counts from len instead of P: token i sees the rows <= len + min(i, c - 1), of which a row below len
+// carries its mask column's bias and a new row none; the splits share the len + c rows that exist; rows at or beyond len + c are never read, those that
+// fall into a staged chunk are zeros in LDS as the padded keys are.  All of this is uniform over the workgroup (len and c belong to the image), so the
+// barrier rule holds as it stands.  A row with nothing visible at all (c = 0 over an empty cache) takes the weight 1 on its zero sum in split 0
+template <typename T, int HD, bool INPLACE = false>
 __global__ __launch_bounds__(kDecodeBlock) void attention_extend_kernel(const DecodeArgs a) {
     constexpr bool F16 = sizeof(T) == 2;
     constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
@@ -357,17 +517,20 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_kernel(const De
     float* Bs = reinterpret_cast<float*>(Vs + size_t(KC) * RS);
     const int S = a.splits, rb = int(blockIdx.x) / S, sp = int(blockIdx.x) % S, kvh = int(blockIdx.y);
     const int64_t n = blockIdx.z;
-    const int g = a.heads / a.kv_heads, P = a.past_len, Lq = a.new_len, R = g * Lq, Lk = P + Lq;
+    int len = a.past_len, app = a.new_len;         // the rows in front of the chunk and the tokens that append
+    if constexpr (INPLACE) { const Resident rs = resident(a, n); len = rs.len; app = rs.c; }
+    const int g = a.heads / a.kv_heads, P = len, Lq = a.new_len, R = g * Lq, Lk = INPLACE ? P + app : P + Lq;
     const int wave = int(threadIdx.x) / 64, lane = int(threadIdx.x) % 64, col = lane & 31, hf = lane >> 5;
     const int q0 = rb * 128 + wave * 32;
     const bool live = q0 < R;                      // wave-uniform
     const int row = q0 + col < R ? q0 + col : R - 1;
     const int tok = row / g, h = kvh * g + row % g;
-    const int lim = P + tok;                       // this lane's last visible key
+    auto seen = [app](int t) { return INPLACE && t >= app ? app - 1 : t; };      // the new rows token t sees beyond its cached ones, less one
+    const int lim = P + seen(tok);                 // this lane's last visible key
     const int first_tok = (q0 < R ? q0 : R - 1) / g, last_tok = (q0 + 31 < R ? q0 + 31 : R - 1) / g;
-    const int wave_end = live ? P + last_tok + 1 : 0;      // the wave's keys: [0, wave_end)
-    const int free_end = P + first_tok + 1;                // keys below it are visible to every row of the wave
-    const int wg_end = P + (rb * 128 + 127 < R ? rb * 128 + 127 : R - 1) / g + 1;
+    const int wave_end = live ? P + seen(last_tok) + 1 : 0;      // the wave's keys: [0, wave_end)
+    const int free_end = P + seen(first_tok) + 1;                // keys below it are visible to every row of the wave
+    const int wg_end = P + seen((rb * 128 + 127 < R ? rb * 128 + 127 : R - 1) / g) + 1;
     const int per = ((Lk + 31) / 32 + S - 1) / S;
     const int kbeg = sp * per * 32, kend = wg_end < (sp + 1) * per * 32 ? wg_end : (sp + 1) * per * 32;      // the workgroup's keys (none: kbeg >= kend)
 
@@ -401,8 +564,8 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_kernel(const De
     for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
     float m = -kFltMax, lsum = 0.f;
     const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
-    const float* pk = a.present_k + (n * a.kv_heads + kvh) * int64_t(Lk) * HD;
-    const float* pv = a.present_v + (n * a.kv_heads + kvh) * int64_t(Lk) * HD;
+    const float* pk = a.present_k + (n * a.kv_heads + kvh) * (INPLACE ? a.cache_rows : int64_t(Lk)) * HD;
+    const float* pv = a.present_v + (n * a.kv_heads + kvh) * (INPLACE ? a.cache_rows : int64_t(Lk)) * HD;
 
     for (int c0 = kbeg; c0 < kend; c0 += KC) {     // (the bounds are the workgroup's: every wave runs every iteration)
         const int rows = kend - c0 < KC ? (kend - c0 + 31) / 32 * 32 : KC;
@@ -425,7 +588,7 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_kernel(const De
             }
         }
         for (int j = int(threadIdx.x); j < rows; j += kDecodeBlock)
-            Bs[j] = c0 + j < Lk ? fmaxf(key_bias(a, n, c0 + j) * kLog2e, -kFltMax) : 0.f;      // (a padded key is causally hidden from every row)
+            Bs[j] = c0 + j < (INPLACE ? P : Lk) ? fmaxf(key_bias(a, n, c0 + j) * kLog2e, -kFltMax) : 0.f;      // (a padded key is causally hidden from every row)
         __syncthreads();
         const int cend = c0 + rows < wave_end ? c0 + rows : wave_end;
         for (int key0 = c0; key0 < cend; key0 += 32) {
@@ -498,6 +661,7 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_kernel(const De
     }
 
     lsum += __shfl_xor(lsum, 32, 64);
+    if constexpr (INPLACE) if (lim < 0 && sp == 0) lsum = 1.f;      // nothing visible at all: zeros, finite
     if (q0 + col >= R) return;                     // behind the last barrier
     // registers 4 j ... 4 j + 3 of o0 (o1: + 32) are the output columns 8 j + 4 hf ... of this lane's query row
     if (S == 1) {
@@ -556,16 +720,31 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_combine_kernel(
     reinterpret_cast<T*>(a.out.p)[n * a.out.sn + tok * a.out.sw + (h * hd + e) * a.out.sc] = T(O / L);
 }
 
+// in place: both arrays, one storage for past and present, and a capacity that is the graph's P (a prefill with a cache: at least its L rows), so that
+// every mask column below len exists
+bool inplace_ok(const DecodeArgs& a) {
+    if (a.cache_rows == 0) return true;
+    return a.lens && a.news && a.past_k == a.present_k && a.past_v == a.present_v && a.cache_rows < (int64_t(1) << 31) &&
+           (a.past_len > 0 ? a.cache_rows == a.past_len : a.cache_rows >= a.new_len);
+}
+
 bool cache_ok(const DecodeArgs& a) {
     return a.in.p && a.present_k && a.present_v && a.heads >= 1 && a.kv_heads >= 1 && a.heads % a.kv_heads == 0 && a.head_dim >= 1 && a.past_len >= 0 && a.new_len >= 1 &&
            a.in.w == a.new_len && !a.in.f8 && (a.past_len == 0 || (a.past_k && a.past_v)) && (!a.rope_cos || (a.rope_sin && a.rope_rows >= 1 && a.head_dim % 2 == 0)) &&
-           int64_t(a.in.c) == int64_t(a.heads + 2 * a.kv_heads) * a.head_dim;
+           int64_t(a.in.c) == int64_t(a.heads + 2 * a.kv_heads) * a.head_dim && inplace_ok(a);
 }
 
 template <typename T, int HD>
 hipError_t launch_decode_g(const DecodeArgs& a, hipStream_t stream) {
     const dim3 grid(unsigned(a.splits), unsigned(a.kv_heads), unsigned(a.in.n));
     const int g = a.heads / a.kv_heads;
+    if (a.cache_rows > 0) {
+        if (g == 1) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 1, true>), grid, dim3(kDecodeBlock), 0, stream, a);
+        else if (g == 2) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 2, true>), grid, dim3(kDecodeBlock), 0, stream, a);
+        else if (g <= 4) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 4, true>), grid, dim3(kDecodeBlock), 0, stream, a);
+        else hipLaunchKernelGGL((attention_decode_kernel<T, HD, 8, true>), grid, dim3(kDecodeBlock), 0, stream, a);
+        return hipGetLastError();
+    }
     if (g == 1) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 1>), grid, dim3(kDecodeBlock), 0, stream, a);
     else if (g == 2) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 2>), grid, dim3(kDecodeBlock), 0, stream, a);
     else if (g <= 4) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 4>), grid, dim3(kDecodeBlock), 0, stream, a);
@@ -586,7 +765,8 @@ template <typename T, int HD>
 hipError_t launch_extend(const DecodeArgs& a, hipStream_t stream) {
     const int64_t rblocks = (int64_t(a.heads / a.kv_heads) * a.new_len + 127) / 128;
     const dim3 grid(unsigned(rblocks * a.splits), unsigned(a.kv_heads), unsigned(a.in.n));
-    attention_extend_kernel<T, HD><<<grid, dim3(kDecodeBlock), size_t(ExtendLdsBytes(HD, sizeof(T) == 2)), stream>>>(a);
+    if (a.cache_rows > 0) attention_extend_kernel<T, HD, true><<<grid, dim3(kDecodeBlock), size_t(ExtendLdsBytes(HD, sizeof(T) == 2)), stream>>>(a);
+    else attention_extend_kernel<T, HD><<<grid, dim3(kDecodeBlock), size_t(ExtendLdsBytes(HD, sizeof(T) == 2)), stream>>>(a);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess || a.splits == 1) return e;
     const int64_t total = int64_t(a.in.n) * a.heads * a.new_len * a.head_dim;
     hipLaunchKernelGGL((attention_extend_combine_kernel<T>), dim3(unsigned((total + kDecodeBlock - 1) / kDecodeBlock)), dim3(kDecodeBlock), 0, stream, a, total);
@@ -604,10 +784,21 @@ bool KvAppendEligible(const DecodeArgs& a) {
 hipError_t LaunchKvAppend(const DecodeArgs& a, hipStream_t stream) {
     if (!KvAppendEligible(a)) return hipErrorInvalidValue;
     if (a.in.n == 0) return hipSuccess;
-    const int64_t floats = int64_t(a.in.n) * a.kv_heads * (int64_t(a.past_len) + a.new_len) * a.head_dim;
+    const bool inplace = a.cache_rows > 0;         // the new rows alone
+    const int64_t floats = int64_t(a.in.n) * a.kv_heads * (inplace ? int64_t(a.new_len) : int64_t(a.past_len) + a.new_len) * a.head_dim;
     const bool vec = a.head_dim % 4 == 0 && Aligned16(a.present_k) && Aligned16(a.present_v) && (a.past_len == 0 || (Aligned16(a.past_k) && Aligned16(a.past_v)));
     const int64_t total = vec ? floats / 4 : floats;
     const dim3 grid(unsigned((total + kDecodeBlock - 1) / kDecodeBlock));
+    if (inplace) {
+        if (vec) {
+            if (a.in.f16) hipLaunchKernelGGL((kv_append_rows_kernel<_Float16, 4>), grid, dim3(kDecodeBlock), 0, stream, a, total);
+            else hipLaunchKernelGGL((kv_append_rows_kernel<float, 4>), grid, dim3(kDecodeBlock), 0, stream, a, total);
+        } else {
+            if (a.in.f16) hipLaunchKernelGGL((kv_append_rows_kernel<_Float16, 1>), grid, dim3(kDecodeBlock), 0, stream, a, total);
+            else hipLaunchKernelGGL((kv_append_rows_kernel<float, 1>), grid, dim3(kDecodeBlock), 0, stream, a, total);
+        }
+        return hipGetLastError();
+    }
     if (vec) {
         if (a.in.f16) hipLaunchKernelGGL((kv_append_kernel<_Float16, 4>), grid, dim3(kDecodeBlock), 0, stream, a, total);
         else hipLaunchKernelGGL((kv_append_kernel<float, 4>), grid, dim3(kDecodeBlock), 0, stream, a, total);
@@ -647,6 +838,11 @@ hipError_t LaunchAttentionDecode(const DecodeArgs& a, int tile, hipStream_t stre
         const int64_t rows = int64_t(a.in.n) * a.heads * a.new_len;
         const int64_t blocks = (rows + kDecodeBlock / 64 - 1) / (kDecodeBlock / 64);
         if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+        if (a.cache_rows > 0) {                    // in place: one kernel for a decode and an extend step, behind the kv_append_rows launch
+            if (a.in.f16) hipLaunchKernelGGL((attention_inplace_generic_kernel<_Float16>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
+            else hipLaunchKernelGGL((attention_inplace_generic_kernel<float>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
+            return hipGetLastError();
+        }
         if (a.new_len > 1) {
             if (a.in.f16) hipLaunchKernelGGL((attention_extend_generic_kernel<_Float16>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
             else hipLaunchKernelGGL((attention_extend_generic_kernel<float>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
@@ -668,6 +864,8 @@ hipError_t InitKernelsDecode() {
     const void* const kernels[] = {
         reinterpret_cast<const void*>(&attention_extend_kernel<float, 32>), reinterpret_cast<const void*>(&attention_extend_kernel<float, 64>),
         reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 32>), reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 64>),
+        reinterpret_cast<const void*>(&attention_extend_kernel<float, 32, true>), reinterpret_cast<const void*>(&attention_extend_kernel<float, 64, true>),
+        reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 32, true>), reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 64, true>),
     };
     for (const void* k : kernels)
         if (const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget)); e != hipSuccess) return e;

@@ -107,6 +107,15 @@ DecodeArgs MakeDecodeArgs(const PlanInstance& pi, const Step& s, const float* we
     a.past_v = cache(s.past_v);
     a.present_k = cache(s.present_k);
     a.present_v = cache(s.present_v);
+    if (s.inplace) {       // bound to a resident cache: past and present are the layer's storage there, the graph's own cache buffers stay unused
+        const KvBinding* kv = pi.kv.get();
+        if (!kv || s.kv_layer < 0 || s.kv_layer >= kv->layers) throw std::runtime_error("internal error: in-place step " + s.name + " without its cache layer");
+        a.past_k = a.present_k = kv->k[size_t(s.kv_layer)];
+        a.past_v = a.present_v = kv->v[size_t(s.kv_layer)];
+        a.cache_rows = kv->capacity;
+        a.lens = kv->d_lens;
+        a.news = kv->d_lens + kv->batch;
+    }
     a.heads = s.heads;
     a.kv_heads = s.kv_heads > 0 ? s.kv_heads : s.heads;
     a.head_dim = s.head_dim;
@@ -724,8 +733,14 @@ std::string kernel_label(const Step& s) {
             return s.tile == 0 ? stem + "_generic_kernel" : stem + "_kernel<" + (s.out.f16 ? "f16," : "f32,") + std::to_string(kLnLanes[s.tile]) + ">";
         }
         case StepKind::TokenAssemble: return std::string("token_assemble_kernel<") + (s.out.f16 ? "f16>" : "f32>");
-        case StepKind::KvAppend: return std::string("kv_append_kernel<") + (s.in.f16 ? "f16>" : "f32>");
+        case StepKind::KvAppend: return std::string(s.inplace ? "kv_append_rows_kernel<" : "kv_append_kernel<") + (s.in.f16 ? "f16" : "f32") + (s.inplace ? ",inplace>" : ">");
         case StepKind::Attention:
+            if (s.past_len > 0 && s.inplace) {     // a step bound to a resident cache: the in-place forms
+                const std::string t = s.out.f16 ? "f16" : "f32";
+                if (s.tile == kAttnExtendTile) return "kv_append_rows_kernel + attention_extend_kernel<" + t + "," + std::to_string(s.head_dim) + ",inplace>" + (s.splits > 1 ? " + attention_extend_combine_kernel" : "");
+                if (s.tile == kAttnDecodeTile) return "attention_decode_kernel<" + t + "," + std::to_string(s.head_dim) + ",inplace>" + (s.splits > 1 ? " + attention_decode_combine_kernel" : "");
+                return std::string(s.parts.empty() ? "" : "kv_append_rows_kernel + ") + "attention_inplace_generic_kernel<" + t + ">";
+            }
             if (s.past_len > 0) {
                 if (s.tile == kAttnExtendTile) return std::string("kv_append_kernel + attention_extend_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">" + (s.splits > 1 ? " + attention_extend_combine_kernel" : "");
                 if (s.tile == kAttnDecodeTile) return std::string("attention_decode_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">" + (s.splits > 1 ? " + attention_decode_combine_kernel" : "");

@@ -162,6 +162,10 @@ struct Step {
     // checked element by element at load and is not kept.  Tile 0 runs the parts (kv_append_kernel, attention_extend_generic_kernel), tile 5 the
     // kv_append launch and attention_extend_kernel over `splits` key splits per (image, K / V head, block of 128 query rows), plus the combine
     View past_k, past_v, present_k, present_v, pos;
+    // Set by the executor on the instances of a model bound to a resident cache, never by the planner (the plan and its JSON do not know of it): the step
+    // runs in place on layer kv_layer of the cache (kernels.h DecodeArgs::cache_rows)
+    bool inplace = false;
+    int kv_layer = -1;
     int past_len = 0;
     bool chunk_causal = false;
     int splits = 0;

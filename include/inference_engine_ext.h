@@ -73,6 +73,33 @@ char* EngineGetRuntimeInfo(ModelHandle handle, int with_checksums, ErrorMessage*
 /* The device's OCP e4m3 conversion as the fp8 kernels use it: codes[i] = e4m3(src[i] / scale) (round to nearest even, saturating at
  * +-448), dst[i] = decode(codes[i]) * scale.  `codes` may be NULL.  Test support for the fp8 precision mode. */
 bool EngineE4m3RoundTrip(const float* src, float* dst, unsigned char* codes, size_t n, float scale, ErrorMessage* error);
+/* Resident KV cache: K and V of a conversation stay in HBM, are appended in place and are shared by the prefill, extend and decode models bound to it.
+ * Per layer K and V are dense fp32 [batch][kv_heads][capacity][head_dim] (in every precision), zero-filled at creation; the valid length of every image
+ * lives on the host, in the object.  Every call takes an ErrorMessage; a NULL handle is an error and touches no device.
+ *
+ * Bind: a loaded Llama-shaped model whose graph has `past_key_values.<i>.key|value` inputs and `present.<i>.key|value` outputs of exactly this geometry
+ * (a decode or extend graph with past == capacity), or the prefill graph with `present` outputs and no past (its L <= capacity).  Several models may be
+ * bound to one cache; their calls serialise on it.  Refused by name: a model without cache inputs / outputs, a geometry mismatch (the dimension is
+ * named), another device, more than one execution lane, shard replicas, the dynamic batcher, fp8.  A NULL cache unbinds.
+ *
+ * ModelInfer on a bound model takes the graph's inputs without the `past_key_values.*` ones (passing one is "Unexpected input name") and gives every
+ * output but the `present.*` ones (requesting one is refused by name).  attention_mask [N, capacity + Lq] and position_ids keep their meaning; the mask
+ * is checked on the host before anything is enqueued: a one in a cache column at or beyond the image's length, ones in the new-token columns that are no
+ * prefix, or more new tokens than the cache has room for are errors that name image and column and change nothing.  After a successful call the length
+ * of image n has grown by the ones c_n of its new-token columns.  A bound prefill graph needs every length to be 0.  For every token whose own column
+ * is 1 the outputs are those of the same graph on the equivalent right-padded client-held cache; rows of padded tokens are finite and otherwise
+ * unspecified.  EngineRunPrepared / EngineProfile replay with the lengths as they stand and do not advance them.
+ *
+ * SetLengths (0 .. capacity each) resets the cache, rolls rejected draft tokens back, or follows a Write.  Read / Write move one layer's whole K (which
+ * 0) or V (which 1) tensor, `bytes` = batch * kv_heads * capacity * head_dim * 4. */
+typedef struct EngineKvCache* EngineKvCacheHandle;
+EngineKvCacheHandle EngineKvCacheCreate(int device_id, int layers, int batch, int kv_heads, int capacity, int head_dim, ErrorMessage* error);
+void EngineKvCacheDestroy(EngineKvCacheHandle cache);
+bool EngineKvCacheBind(ModelHandle handle, EngineKvCacheHandle cache, ErrorMessage* error);
+bool EngineKvCacheGetLengths(EngineKvCacheHandle cache, int64_t* lens, ErrorMessage* error);
+bool EngineKvCacheSetLengths(EngineKvCacheHandle cache, const int64_t* lens, ErrorMessage* error);
+bool EngineKvCacheRead(EngineKvCacheHandle cache, int layer, int which, float* dst, size_t bytes, ErrorMessage* error);
+bool EngineKvCacheWrite(EngineKvCacheHandle cache, int layer, int which, const float* src, size_t bytes, ErrorMessage* error);
 /* result = a + b on the GPU for host arrays (the reference's VectorAdd smoke test, cuda_utils.cu:59-149). */
 bool EngineVectorAdd(const float* a, const float* b, float* result, size_t n, ErrorMessage* error);
 
