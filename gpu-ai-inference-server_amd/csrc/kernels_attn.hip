@@ -19,16 +19,8 @@
 //                                   head dim; K and V are streamed in tiles of 32 keys, LDS does not depend on L (described at the kernel).
 //                                   <T, HD, CAUSAL> and <T, HD, CAUSAL, ROPE> (HD 128 / 256) are its causal and rotary forms.
 //
-// Operand orientation of tile 1.  The scores are computed swapped, S^T = K . Q^T: the MFMA's A operand is the K tile (row = key), its B operand
-// Q^T (column = query), so in the 32x32 result (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) a lane owns ONE query column and
-// 16 of its 32 keys; the other 16 sit in lane ^ 32.  Row maximum and sum are 15 in-lane operations and one exchange with lane ^ 32.  The second
-// product is O^T += V^T . P^T, which sums over P^T's row index: the probabilities feed it as the B operand from the registers they are in.
-// The reduction index of a product may be walked in any order as long as both operands agree:
-//   QK^T   lane half hf supplies the head-dim elements hf * HD/2 ... of its Q row and of its K row: whole 16-byte vectors on both sides
-//   PV     fp32 (32x32x2): register r is one k-step: keys (r & 3) + 8 (r >> 2) in lane half 0 and that + 4 in lane half 1, and the A operand is V at
-//          that key.  fp16 (32x32x16): registers 8 s ... 8 s + 7 as halfs are k-step s; element j of lane half hf is key
-//          16 s + 8 (j >> 2) + 4 hf + (j & 3), and the V fragment is gathered in the same order (scripts/probes/attn_pv_order.hip checks both maps
-//          with exact integers).
+// Tile 1 computes the scores swapped, S^T = K . Q^T, and feeds P^T to the second product from the registers it is in: attn_mfma.h describes the
+// orientation and the operand orders, and holds the wave (AttnWave) that tiles 1 and 3 and the window kernel share.
 // Padded keys (j >= L) get -inf before the maximum; padded queries are computed from the last row and never stored.
 //
 //   attention_chunk_kernel<T, HD>   tile 3: tile 1's workgroup, orientation, online softmax and epilogue, for any L: K and V pass through LDS in chunks of
@@ -66,7 +58,7 @@
 
 #include <cstdint>
 
-#include "device_util.h"
+#include "attn_mfma.h"
 #include "kernels.h"
 #include "launch_util.h"
 
@@ -74,10 +66,6 @@ namespace ie {
 namespace {
 
 constexpr int kAttnBlock = 256;
-constexpr float kLog2e = 1.4426950408889634f;
-
-constexpr float kFltMax = 3.402823466e+38f;
-constexpr float kMaskShiftMax = 16777216.f;
 
 // rows = N * heads * L query rows, one wave each
 template <bool MASK, bool CAUSAL>
@@ -147,179 +135,25 @@ __global__ __launch_bounds__(kAttnBlock) void attention_generic_kernel(const Att
     }
 }
 
-// One 16-byte vector of a q / k row after the rotary embedding: x = the vector (elements e0 ...), xp = its partner vector (elements e0 +/- HD/2 ...),
-// c / s = the cos / sin entries e0 ... of the token position's table row, sg = -1 for a vector of the first half of the head, +1 for one of the second.
-// fp32 arithmetic; halfs are rounded once, here.  rope_rot: the table entries are in registers already, c / s = the V / 4 float4s of the vector's
-// cos / sin entries (tile 2 loads them a tile ahead); rope_vec loads them from the table row
-template <typename T>
-__device__ __forceinline__ uint4 rope_rot(uint4 x, uint4 xp, const float4* c, const float4* s, float sg) {
-    const float4 c0 = c[0], s0 = s[0];
-    if constexpr (sizeof(T) == 2) {
-        const float4 c1 = c[1], s1 = s[1];
-        const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, ss[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-        const h8 a = __builtin_bit_cast(h8, x), b = __builtin_bit_cast(h8, xp);
-        h8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = _Float16(fmaf(float(a[j]), cc[j], sg * float(b[j]) * ss[j]));
-        return __builtin_bit_cast(uint4, o);
+// One tile of 32 keys of a wave of tile 1 / 3: Kt / Vt = the LDS rows of key key0, Bt = the biases from key0 on (MASK).  query = q0 + col (CAUSAL); diag:
+// this is the tile with key0 == q0, the only one of a causal wave whose elements are tested.
+// Every tile a wave visits holds at least one visible key for each of its queries, which keeps the running maximum finite although it starts at -inf: a
+// tile holds a real key (key0 < L); causal, a tile below the diagonal holds only keys < q0 <= every query of the wave, and the diagonal tile's first key
+// q0 is <= every query of the wave and real (q0 < L; the padded queries q0 + col >= L are only ever compared as q0 + col, which admits more keys, not fewer).
+template <int RS, bool MASK, bool CAUSAL, typename T, int HD>
+__device__ __forceinline__ void key_tile(AttnWave<T, HD>& w, const T* Kt, const T* Vt, const float* Bt, int key0, int L, int query, bool diag, float sl2, float shift, int col, int hf) {
+    const bool tail = key0 + 32 > L;               // the last tile holds padded keys
+    if constexpr (MASK) {
+        w.template key_tile<RS>(Kt, Vt, col, hf, [=](int kt, float s) {
+            const float b = Bt[kt];                // -inf on a padded key, else finite: the biased score of a real key stays finite
+            return b < -kFltMax ? b : fmaxf(fmaf(s, sl2, b - shift), -kFltMax);
+        });
+    } else if constexpr (CAUSAL) {
+        w.template key_tile<RS>(Kt, Vt, col, hf, [=](int kt, float s) { return (tail && key0 + kt >= L) || (diag && key0 + kt > query) ? -__builtin_huge_valf() : s * sl2; });
     } else {
-        const float4 a = __builtin_bit_cast(float4, x), b = __builtin_bit_cast(float4, xp);
-        return __builtin_bit_cast(uint4, make_float4(fmaf(a.x, c0.x, sg * b.x * s0.x), fmaf(a.y, c0.y, sg * b.y * s0.y), fmaf(a.z, c0.z, sg * b.z * s0.z),
-                                                     fmaf(a.w, c0.w, sg * b.w * s0.w)));
+        w.template key_tile<RS>(Kt, Vt, col, hf, [=](int kt, float s) { return tail && key0 + kt >= L ? -__builtin_huge_valf() : s * sl2; });
     }
 }
-
-template <typename T>
-__device__ __forceinline__ uint4 rope_vec(uint4 x, uint4 xp, const float* c, const float* s, float sg) {
-    float4 cv[2], sv[2];
-    cv[0] = *reinterpret_cast<const float4*>(c);
-    sv[0] = *reinterpret_cast<const float4*>(s);
-    if constexpr (sizeof(T) == 2) {
-        cv[1] = *reinterpret_cast<const float4*>(c + 4);
-        sv[1] = *reinterpret_cast<const float4*>(s + 4);
-    }
-    return rope_rot<T>(x, xp, cv, sv, sg);
-}
-
-// What a wave of tile 1 / 3 carries through its key tiles: its lane's half of its Q row, the O^T accumulators and the softmax statistics of its query
-template <typename T, int HD>
-struct AttnWave {
-    static constexpr bool F16 = sizeof(T) == 2;
-    static constexpr int HH = HD / 2;              // head-dim elements one lane half supplies to QK^T
-    float4 q4[F16 ? 1 : HH / 4];
-    h8 q8[F16 ? HH / 8 : 1];
-    f32x16 o0, o1;
-    float m, lsum;
-
-    __device__ __forceinline__ void init(const T* qrow) {
-        if constexpr (F16) {
-#pragma unroll
-            for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8*>(qrow + 8 * k);
-        } else {
-#pragma unroll
-            for (int k = 0; k < HH / 4; ++k) q4[k] = *reinterpret_cast<const float4*>(qrow + 4 * k);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-        m = -__builtin_huge_valf();
-        lsum = 0.f;
-    }
-
-    // init with the rotary embedding: qhead = element 0 of the head's Q row, cr / sr = the cos / sin table rows of its token position.  The lane halves
-    // are exactly the two rope halves: lane half hf rotates its half with the other half as the partner
-    __device__ __forceinline__ void init_rope(const T* qhead, int hf, const float* cr, const float* sr) {
-        constexpr int V = 16 / int(sizeof(T));
-        const T* mine = qhead + hf * HH;
-        const T* other = qhead + (1 - hf) * HH;
-        const float sg = hf ? 1.f : -1.f;
-#pragma unroll
-        for (int k = 0; k < HH / V; ++k) {
-            const uint4 r = rope_vec<T>(*reinterpret_cast<const uint4*>(mine + V * k), *reinterpret_cast<const uint4*>(other + V * k), cr + hf * HH + V * k,
-                                        sr + hf * HH + V * k, sg);
-            if constexpr (F16) q8[k] = __builtin_bit_cast(h8, r);
-            else q4[k] = __builtin_bit_cast(float4, r);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-        m = -__builtin_huge_valf();
-        lsum = 0.f;
-    }
-
-    // One tile of 32 keys: Kt / Vt = the LDS rows of key key0 (row stride RS), Bt = the biases from key0 on (MASK).  query = q0 + col (CAUSAL); diag: this
-    // is the tile with key0 == q0, the only one of a causal wave whose elements are tested.
-    // Every tile a wave visits holds at least one visible key for each of its queries, which keeps the running maximum finite: a tile holds a real key
-    // (key0 < L); causal, a tile below the diagonal holds only keys < q0 <= every query of the wave, and the diagonal tile's first key q0 is <= every
-    // query of the wave and real (q0 < L; the padded queries q0 + col >= L are only ever compared as q0 + col, which admits more keys, not fewer).
-    template <int RS, bool MASK, bool CAUSAL>
-    __device__ __forceinline__ void key_tile(const T* Kt, const T* Vt, const float* Bt, int key0, int L, int query, bool diag, float sl2, float shift, int col, int hf) {
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-        const T* krow = Kt + col * RS + hf * HH;
-        if constexpr (F16) {
-#pragma unroll
-            for (int k = 0; k < HH; k += 8)
-                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(krow + k), q8[k / 8], s, 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int k = 0; k < HH; k += 4) {
-                const float4 kf = *reinterpret_cast<const float4*>(krow + k);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, q4[k / 4].x, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, q4[k / 4].y, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, q4[k / 4].z, s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, q4[k / 4].w, s, 0, 0, 0);
-            }
-        }
-        const bool tail = key0 + 32 > L;           // the last tile holds padded keys
-        float mx = -__builtin_huge_valf();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int kt = (r & 3) + 8 * (r >> 2) + 4 * hf, key = key0 + kt;
-            if constexpr (MASK) {
-                const float b = Bt[kt];                // -inf on a padded key, else finite: the biased score of a real key stays finite
-                s[r] = b < -kFltMax ? b : fmaxf(fmaf(s[r], sl2, b - shift), -kFltMax);
-            }
-            else if constexpr (CAUSAL) s[r] = (tail && key >= L) || (diag && key > query) ? -__builtin_huge_valf() : s[r] * sl2;
-            else s[r] = tail && key >= L ? -__builtin_huge_valf() : s[r] * sl2;
-            mx = fmaxf(mx, s[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mn = fmaxf(m, mx);             // finite: every tile has at least one visible key (above)
-        const float alpha = fast_exp2(m - mn);     // 0 on the first tile (m = -inf)
-        m = mn;
-        float ps = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = fast_exp2(s[r] - mn);
-            ps += s[r];
-            o0[r] *= alpha;
-            if constexpr (HD == 64) o1[r] *= alpha;
-        }
-        lsum = fmaf(lsum, alpha, ps);              // this lane half's share of the row sum
-        if constexpr (F16) {
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                h8 pb, va0, va1;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int kt = 16 * st + 8 * (j >> 2) + 4 * hf + (j & 3);
-                    pb[j] = _Float16(s[8 * st + j]);
-                    va0[j] = Vt[kt * RS + col];
-                    if constexpr (HD == 64) va1[j] = Vt[kt * RS + 32 + col];
-                }
-                o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va0, pb, o0, 0, 0, 0);
-                if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va1, pb, o1, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kt = (r & 3) + 8 * (r >> 2) + 4 * hf;
-                o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vt[kt * RS + col]), s[r], o0, 0, 0, 0);
-                if constexpr (HD == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vt[kt * RS + 32 + col]), s[r], o1, 0, 0, 0);
-            }
-        }
-    }
-
-    // O / l of this lane's query into its output row (columns h HD ...); both lane halves hold the whole row sum afterwards
-    __device__ __forceinline__ void store(T* orow, int hf) {
-        const float inv = 1.f / lsum;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int e0 = 8 * g + 4 * hf;             // registers 4 g ... 4 g + 3 are the output columns e0 ... e0 + 3 of this lane's query
-            if constexpr (F16) {
-                h4 x, y;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { x[t] = _Float16(o0[4 * g + t] * inv); y[t] = _Float16(o1[4 * g + t] * inv); }
-                *reinterpret_cast<h4*>(orow + e0) = x;
-                if constexpr (HD == 64) *reinterpret_cast<h4*>(orow + 32 + e0) = y;
-            } else {
-                *reinterpret_cast<float4*>(orow + e0) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-                if constexpr (HD == 64)
-                    *reinterpret_cast<float4*>(orow + 32 + e0) = make_float4(o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
-            }
-        }
-    }
-};
 
 // grid = N * heads * qblocks workgroups (qblocks = ceil(L / 128)); dynamic LDS = AttnLdsBytes(L, HD, half) (by L, causal or not)
 // ROPE (CAUSAL only): the staging thread of K vector (row, cv) also loads the partner vector (cv + VPR / 2) % VPR of the row and the cos / sin vectors of
@@ -373,8 +207,8 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
     if (q0 >= L) return;                           // wave-uniform, behind the kernel's only barrier
     const int qi = q0 + col < L ? q0 + col : L - 1;
     AttnWave<T, HD> w;                             // this lane's half of its Q row in registers for the whole kernel
-    if constexpr (ROPE) w.init_rope(base + int64_t(qi) * a.in.sw, hf, a.rope_cos + int64_t(qi) * HD, a.rope_sin + int64_t(qi) * HD);
-    else w.init(base + int64_t(qi) * a.in.sw + hf * HH);
+    if constexpr (ROPE) w.init_rope(base + int64_t(qi) * a.in.sw, hf, a.rope_cos + int64_t(qi) * HD, a.rope_sin + int64_t(qi) * HD, -__builtin_huge_valf());
+    else w.init(base + int64_t(qi) * a.in.sw + hf * HH, -__builtin_huge_valf());
     const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
     [[maybe_unused]] float shift = 0.f;            // MASK: the image's largest bias (every wave finds it for itself), where it is small enough to be taken out exactly
     if constexpr (MASK) {
@@ -387,7 +221,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
 
     const int kend = CAUSAL ? q0 + 32 : Lp;        // CAUSAL: the wave's last tile is the one that holds its queries (q0 + 32 <= Ls)
     for (int key0 = 0; key0 < kend; key0 += 32)
-        w.template key_tile<RS, MASK, CAUSAL>(Ks + key0 * RS, Vs + key0 * RS, Bs + key0, key0, L, q0 + col, key0 == q0, sl2, shift, col, hf);
+        key_tile<RS, MASK, CAUSAL>(w, Ks + key0 * RS, Vs + key0 * RS, Bs + key0, key0, L, q0 + col, key0 == q0, sl2, shift, col, hf);
 
     w.lsum += __shfl_xor(w.lsum, 32, 64);
     if (q0 + col >= L) return;
@@ -396,7 +230,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_mfma_kernel(const AttnAr
 
 // Tile 3.  grid = N * heads * qblocks workgroups (qblocks = ceil(L / 128)); dynamic LDS = AttnChunkLdsBytes(HD, half), whatever L.
 // Tile 1 with K and V staged chunk by chunk: per chunk of kAttnChunkKeys keys the workgroup stages the rows, meets at a barrier, every wave walks the
-// chunk's key tiles (AttnWave::key_tile, so scores, statistics and accumulation are tile 1's to the bit), and a second barrier lets the next chunk
+// chunk's key tiles (tile 1's key_tile, so scores, statistics and accumulation are tile 1's to the bit), and a second barrier lets the next chunk
 // overwrite the rows (single-buffered: one workgroup per CU at fp32 hd 64 either way).
 // EVERY wave takes part in EVERY barrier: a wave whose queries lie beyond L, and a causal wave that is already past its diagonal, keep staging and
 // waiting and only skip the key tiles; there is no return in front of the last barrier (tile 1 may leave behind its only barrier; here that would hang
@@ -429,8 +263,8 @@ __global__ __launch_bounds__(kAttnBlock) void attention_chunk_kernel(const AttnA
     const bool live = q0 < L;                      // wave-uniform
     const int qi = q0 + col < L ? q0 + col : L - 1;
     AttnWave<T, HD> w;
-    if constexpr (ROPE) w.init_rope(base + int64_t(qi) * a.in.sw, hf, a.rope_cos + int64_t(qi) * HD, a.rope_sin + int64_t(qi) * HD);
-    else w.init(base + int64_t(qi) * a.in.sw + hf * HH);
+    if constexpr (ROPE) w.init_rope(base + int64_t(qi) * a.in.sw, hf, a.rope_cos + int64_t(qi) * HD, a.rope_sin + int64_t(qi) * HD, -__builtin_huge_valf());
+    else w.init(base + int64_t(qi) * a.in.sw + hf * HH, -__builtin_huge_valf());
     const float sl2 = a.scale * kLog2e;
     const int Ls = CAUSAL && 128 * (qb + 1) < Lp ? 128 * (qb + 1) : Lp;      // the workgroup's keys: whole tiles, the same for its four waves
     const int kend = !live ? 0 : (CAUSAL ? q0 + 32 : Lp);                 // this wave's keys (live: q0 + 32 <= Ls)
@@ -456,7 +290,7 @@ __global__ __launch_bounds__(kAttnBlock) void attention_chunk_kernel(const AttnA
         __syncthreads();
         const int cend = c0 + rows < kend ? c0 + rows : kend;
         for (int key0 = c0; key0 < cend; key0 += 32)
-            w.template key_tile<RS, false, CAUSAL>(Ks + (key0 - c0) * RS, Vs + (key0 - c0) * RS, nullptr, key0, L, q0 + col, key0 == q0, sl2, 0.f, col, hf);
+            key_tile<RS, false, CAUSAL>(w, Ks + (key0 - c0) * RS, Vs + (key0 - c0) * RS, nullptr, key0, L, q0 + col, key0 == q0, sl2, 0.f, col, hf);
         __syncthreads();                           // the next chunk overwrites the rows
     }
 

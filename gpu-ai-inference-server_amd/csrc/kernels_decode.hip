@@ -43,7 +43,7 @@
 
 #include <cstdint>
 
-#include "device_util.h"
+#include "attn_mfma.h"
 #include "kernels.h"
 #include "launch_util.h"
 
@@ -51,9 +51,6 @@ namespace ie {
 namespace {
 
 constexpr int kDecodeBlock = 256;
-constexpr float kFltMax = 3.402823466e+38f;
-constexpr float kMaskShiftMax = 16777216.f;
-constexpr float kLog2e = 1.4426950408889634f;
 
 // the table row of token l of image n: the token's own id pos[n pos_sn + l] (a negative position counts from the end), l without pos, clamped into the table
 __device__ __forceinline__ int64_t rope_row(const DecodeArgs& a, int64_t n, int l) {
@@ -173,16 +170,14 @@ __global__ __launch_bounds__(kDecodeBlock) void kv_append_rows_kernel(const Deco
 // the bias of key j of image n, and the image's largest bias where it is small enough to be taken out of every score exactly (0 otherwise)
 __device__ __forceinline__ float key_bias(const DecodeArgs& a, int64_t n, int j) { return (1.f - float(a.mask[n * a.mask_sn + j])) * a.mask_value; }
 
-// One wave: query head h of token i of image n over the first Lk of the `rows` rows of `present` (a decode step: i = 0, Lk = rows = P + 1; an extend
-// step: Lk = P + i + 1 of P + Lq, the rest being the chunk's future).  The shift is the largest bias among the keys the query sees
-template <typename T>
-__device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int h, int i, int Lk, int rows) {
+// One wave of tile 0: query head h of token i of image n over the first Lk rows of its K / V head at K / Vp.  The first `biased` of them carry their mask
+// column's bias (the new rows of a resident cache carry none: their columns are of the prefix of ones); the shift is the largest bias among the keys the
+// query sees.  ZERO_EMPTY: a row with nothing visible (l = 0) comes out as zeros, and the row is scaled by 1 / l instead of divided by l
+template <typename T, bool ZERO_EMPTY>
+__device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int h, int i, const float* K, const float* Vp, int Lk, int biased) {
     constexpr int kChunks = kDecodeMaxHeadDim / 64;
     const int lane = int(threadIdx.x) % 64;
     const int hd = a.head_dim;
-    const int kvh = h / (a.heads / a.kv_heads);
-    const float* K = a.present_k + (n * a.kv_heads + kvh) * int64_t(rows) * hd;
-    const float* Vp = a.present_v + (n * a.kv_heads + kvh) * int64_t(rows) * hd;
     const bool rope = a.rope_cos != nullptr;
     const int64_t r = rope ? rope_row(a, n, i) : 0;
     const int64_t qb = qkv_base(a, n, i, 0, h);
@@ -195,8 +190,8 @@ __device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int 
     }
     float shift = 0.f;
     if (a.mask) {
-        float bm = -kFltMax;
-        for (int j = lane; j < Lk; j += 64) bm = fmaxf(bm, key_bias(a, n, j));
+        float bm = Lk > biased ? 0.f : -kFltMax;   // (a visible key without a bias has the bias 0)
+        for (int j = lane; j < biased; j += 64) bm = fmaxf(bm, key_bias(a, n, j));
 #pragma unroll
         for (int x = 32; x >= 1; x >>= 1) bm = fmaxf(bm, __shfl_xor(bm, x, 64));
         shift = fabsf(bm) <= kMaskShiftMax ? bm : 0.f;
@@ -211,7 +206,7 @@ __device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int 
         }
 #pragma unroll
         for (int x = 32; x >= 1; x >>= 1) s += __shfl_xor(s, x, 64);
-        if (a.mask) s = fmaxf(s + (key_bias(a, n, j) - shift), -kFltMax);
+        if (a.mask) s = fmaxf(s + ((j < biased ? key_bias(a, n, j) : 0.f) - shift), -kFltMax);
         const float mn = fmaxf(m, s), al = __expf(m - mn), p = __expf(s - mn);
         l = l * al + p;
 #pragma unroll
@@ -223,92 +218,55 @@ __device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int 
     }
     T* out = reinterpret_cast<T*>(a.out.p);
     const int64_t ob = n * a.out.sn + int64_t(i) * a.out.sw + int64_t(h) * hd * a.out.sc;
+    [[maybe_unused]] const float inv = l > 0.f ? 1.f / l : 0.f;
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {
         const int e = c * 64 + lane;
-        if (e < hd) out[ob + int64_t(e) * a.out.sc] = T(acc[c] / l);
+        if (e >= hd) continue;
+        if constexpr (ZERO_EMPTY) out[ob + int64_t(e) * a.out.sc] = T(acc[c] * inv);
+        else out[ob + int64_t(e) * a.out.sc] = T(acc[c] / l);
     }
 }
 
-// rows = N * heads, one wave each
+// tile 0 over `present` as a kv_append launch wrote it, `rows` rows per K / V head: every visible key carries its bias, and the new one is always visible
+template <typename T>
+__device__ __forceinline__ void attend_present(const DecodeArgs& a, int64_t n, int h, int i, int Lk, int rows) {
+    const int64_t kv = (n * a.kv_heads + h / (a.heads / a.kv_heads)) * int64_t(rows) * a.head_dim;
+    attend_wave<T, false>(a, n, h, i, a.present_k + kv, a.present_v + kv, Lk, Lk);
+}
+
+// rows = N * heads, one wave each: a decode step sees all P + 1 rows
 template <typename T>
 __global__ __launch_bounds__(kDecodeBlock) void attention_decode_generic_kernel(const DecodeArgs a, const int64_t rows) {
     const int64_t row = int64_t(blockIdx.x) * (kDecodeBlock / 64) + threadIdx.x / 64;
     if (row >= rows) return;                       // wave-uniform
-    attend_wave<T>(a, row / a.heads, int(row % a.heads), 0, a.past_len + 1, a.past_len + 1);
+    attend_present<T>(a, row / a.heads, int(row % a.heads), 0, a.past_len + 1, a.past_len + 1);
 }
 
-// rows = N * heads * Lq, one wave per (image, query head, new token i), the token fastest: key j is visible to token i iff j <= P + i
+// rows = N * heads * Lq, one wave per (image, query head, new token i), the token fastest: key j is visible to token i iff j <= P + i, the first
+// P + i + 1 of the P + Lq rows, the rest being the chunk's future
 template <typename T>
 __global__ __launch_bounds__(kDecodeBlock) void attention_extend_generic_kernel(const DecodeArgs a, const int64_t rows) {
     const int64_t row = int64_t(blockIdx.x) * (kDecodeBlock / 64) + threadIdx.x / 64;
     if (row >= rows) return;                       // wave-uniform
     const int Lq = a.new_len, i = int(row % Lq);
     const int64_t nh = row / Lq;
-    attend_wave<T>(a, nh / a.heads, int(nh % a.heads), i, a.past_len + i + 1, a.past_len + Lq);
+    attend_present<T>(a, nh / a.heads, int(nh % a.heads), i, a.past_len + i + 1, a.past_len + Lq);
 }
 
 // In place, tile 0 of a decode step (new_len = 1) and of an extend step alike: rows = N * heads * new_len, one wave per (image, query head, new token i), the
 // token fastest, over the resident cache a kv_append_rows launch has appended to.  The wave walks the rows [0, len + min(i, c - 1)] and no other: a
-// row below len carries its mask column's bias, a new row none (its column is one of the prefix of ones); a token with nothing visible writes zeros
+// row below len carries its mask column's bias, a new row none; a token with nothing visible writes zeros
 template <typename T>
 __global__ __launch_bounds__(kDecodeBlock) void attention_inplace_generic_kernel(const DecodeArgs a, const int64_t rows) {
-    constexpr int kChunks = kDecodeMaxHeadDim / 64;
     const int64_t row = int64_t(blockIdx.x) * (kDecodeBlock / 64) + threadIdx.x / 64;
     if (row >= rows) return;                       // wave-uniform
-    const int Lq = a.new_len, i = int(row % Lq), lane = int(threadIdx.x) % 64, hd = a.head_dim;
+    const int Lq = a.new_len, i = int(row % Lq);
     const int64_t nh = row / Lq, n = nh / a.heads;
-    const int h = int(nh % a.heads), kvh = h / (a.heads / a.kv_heads);
+    const int h = int(nh % a.heads);
     const Resident rs = resident(a, n);
-    const int Lk = rs.len + (i < rs.c ? i : rs.c - 1) + 1;
-    const float* K = a.present_k + (n * a.kv_heads + kvh) * a.cache_rows * hd;
-    const float* Vp = a.present_v + (n * a.kv_heads + kvh) * a.cache_rows * hd;
-    const bool rope = a.rope_cos != nullptr;
-    const int64_t r = rope ? rope_row(a, n, i) : 0;
-    const int64_t qb = qkv_base(a, n, i, 0, h);
-    float q[kChunks], acc[kChunks];
-#pragma unroll
-    for (int c = 0; c < kChunks; ++c) {
-        const int e = c * 64 + lane;
-        q[c] = e < hd ? rotated<T>(a, qb, r, e, rope) * a.scale : 0.f;
-        acc[c] = 0.f;
-    }
-    float shift = 0.f;
-    if (a.mask) {
-        float bm = Lk > rs.len ? 0.f : -kFltMax;   // (a visible new row has the bias 0)
-        for (int j = lane; j < rs.len; j += 64) bm = fmaxf(bm, key_bias(a, n, j));
-#pragma unroll
-        for (int x = 32; x >= 1; x >>= 1) bm = fmaxf(bm, __shfl_xor(bm, x, 64));
-        shift = fabsf(bm) <= kMaskShiftMax ? bm : 0.f;
-    }
-    float m = -kFltMax, l = 0.f;
-    for (int j = 0; j < Lk; ++j) {
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < kChunks; ++c) {
-            const int e = c * 64 + lane;
-            if (e < hd) s = fmaf(q[c], K[int64_t(j) * hd + e], s);
-        }
-#pragma unroll
-        for (int x = 32; x >= 1; x >>= 1) s += __shfl_xor(s, x, 64);
-        if (a.mask) s = fmaxf(s + ((j < rs.len ? key_bias(a, n, j) : 0.f) - shift), -kFltMax);
-        const float mn = fmaxf(m, s), al = __expf(m - mn), p = __expf(s - mn);
-        l = l * al + p;
-#pragma unroll
-        for (int c = 0; c < kChunks; ++c) {
-            const int e = c * 64 + lane;
-            if (e < hd) acc[c] = fmaf(p, Vp[int64_t(j) * hd + e], acc[c] * al);
-        }
-        m = mn;
-    }
-    T* out = reinterpret_cast<T*>(a.out.p);
-    const int64_t ob = n * a.out.sn + int64_t(i) * a.out.sw + int64_t(h) * hd * a.out.sc;
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-#pragma unroll
-    for (int c = 0; c < kChunks; ++c) {
-        const int e = c * 64 + lane;
-        if (e < hd) out[ob + int64_t(e) * a.out.sc] = T(acc[c] * inv);
-    }
+    const int64_t kv = (n * a.kv_heads + h / (a.heads / a.kv_heads)) * a.cache_rows * a.head_dim;
+    attend_wave<T, true>(a, n, h, i, a.present_k + kv, a.present_v + kv, rs.len + (i < rs.c ? i : rs.c - 1) + 1, rs.len);
 }
 
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
@@ -734,27 +692,25 @@ bool cache_ok(const DecodeArgs& a) {
            int64_t(a.in.c) == int64_t(a.heads + 2 * a.kv_heads) * a.head_dim && inplace_ok(a);
 }
 
-template <typename T, int HD>
+template <typename T, int HD, bool INPLACE>
 hipError_t launch_decode_g(const DecodeArgs& a, hipStream_t stream) {
     const dim3 grid(unsigned(a.splits), unsigned(a.kv_heads), unsigned(a.in.n));
     const int g = a.heads / a.kv_heads;
-    if (a.cache_rows > 0) {
-        if (g == 1) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 1, true>), grid, dim3(kDecodeBlock), 0, stream, a);
-        else if (g == 2) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 2, true>), grid, dim3(kDecodeBlock), 0, stream, a);
-        else if (g <= 4) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 4, true>), grid, dim3(kDecodeBlock), 0, stream, a);
-        else hipLaunchKernelGGL((attention_decode_kernel<T, HD, 8, true>), grid, dim3(kDecodeBlock), 0, stream, a);
-        return hipGetLastError();
-    }
-    if (g == 1) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 1>), grid, dim3(kDecodeBlock), 0, stream, a);
-    else if (g == 2) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 2>), grid, dim3(kDecodeBlock), 0, stream, a);
-    else if (g <= 4) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 4>), grid, dim3(kDecodeBlock), 0, stream, a);
-    else hipLaunchKernelGGL((attention_decode_kernel<T, HD, 8>), grid, dim3(kDecodeBlock), 0, stream, a);
+    if (g == 1) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 1, INPLACE>), grid, dim3(kDecodeBlock), 0, stream, a);
+    else if (g == 2) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 2, INPLACE>), grid, dim3(kDecodeBlock), 0, stream, a);
+    else if (g <= 4) hipLaunchKernelGGL((attention_decode_kernel<T, HD, 4, INPLACE>), grid, dim3(kDecodeBlock), 0, stream, a);
+    else hipLaunchKernelGGL((attention_decode_kernel<T, HD, 8, INPLACE>), grid, dim3(kDecodeBlock), 0, stream, a);
     return hipGetLastError();
+}
+
+template <typename T, int HD>
+hipError_t launch_decode_hd(const DecodeArgs& a, hipStream_t stream) {
+    return a.cache_rows > 0 ? launch_decode_g<T, HD, true>(a, stream) : launch_decode_g<T, HD, false>(a, stream);
 }
 
 template <typename T>
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
-    const hipError_t e = a.head_dim == 32 ? launch_decode_g<T, 32>(a, stream) : (a.head_dim == 64 ? launch_decode_g<T, 64>(a, stream) : launch_decode_g<T, 128>(a, stream));
+    const hipError_t e = a.head_dim == 32 ? launch_decode_hd<T, 32>(a, stream) : (a.head_dim == 64 ? launch_decode_hd<T, 64>(a, stream) : launch_decode_hd<T, 128>(a, stream));
     if (e != hipSuccess || a.splits == 1) return e;
     const int64_t total = int64_t(a.in.n) * a.heads * a.head_dim;
     hipLaunchKernelGGL((attention_decode_combine_kernel<T>), dim3(unsigned((total + kDecodeBlock - 1) / kDecodeBlock)), dim3(kDecodeBlock), 0, stream, a, total);

@@ -15,8 +15,8 @@
 //                                        of its window into its own LDS slice (rows past L zero, row stride hd + one 16-byte vector as in
 //                                        kernels_attn.hip), then walks the one or two blocks of 32 queries.
 //
-// Tile 1 computes the scores swapped (S^T = K . Q^T) and feeds P^T to the second product from its registers, in the operand orders
-// kernels_attn.hip documents.  Softmax form: TWO-PASS over a whole row held in registers.  L <= 64 is at most two 32-key tiles = 32 score
+// Tile 1 computes the scores swapped (S^T = K . Q^T) and feeds P^T to the second product from its registers, with the wave and in the operand orders
+// of attn_mfma.h (Q, both products and the store are AttnWave's).  Softmax form: TWO-PASS over a whole row held in registers.  L <= 64 is at most two 32-key tiles = 32 score
 // registers per lane, which fit beside Q (16) and O (16); the maximum is taken over the complete row before any exponential, so there is no
 // running maximum, no rescale of O and sum, and half the exponentials of the online form on a second tile.  Padded keys carry -inf from the bias
 // table (no compare in the kernel); padded queries are computed from the last row and never stored.
@@ -24,7 +24,7 @@
 
 #include <cstdint>
 
-#include "device_util.h"
+#include "attn_mfma.h"
 #include "kernels.h"
 #include "launch_util.h"
 
@@ -33,7 +33,6 @@ namespace {
 
 constexpr int kWinBlock = 256;
 constexpr int kWinWaves = kWinBlock / 64;
-constexpr float kLog2e = 1.4426950408889634f;
 
 // the map pixel (y, x) of token t of window (wy, wx)
 __device__ __forceinline__ void tok_yx(const WinAttnArgs& a, int wy, int wx, int t, int& y, int& x) {
@@ -113,7 +112,6 @@ constexpr int64_t WinAttnLdsBytes(int64_t Lp, int hd, bool f16) { return kWinWav
 // grid = ceil(problems / 4) workgroups, problem = ((n * nW + window) * heads + head); dynamic LDS = WinAttnLdsBytes(Lp, HD, half)
 template <typename T, int HD>
 __global__ __launch_bounds__(kWinBlock) void window_attention_mfma_kernel(const WinAttnArgs a, const int64_t problems) {
-    constexpr bool F16 = sizeof(T) == 2;
     constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
     constexpr int RS = HD + V;                     // LDS row stride in elements
     constexpr int HH = HD / 2;                     // head-dim elements one lane half supplies to QK^T
@@ -175,23 +173,14 @@ __global__ __launch_bounds__(kWinBlock) void window_attention_mfma_kernel(const 
         int qy, qx;
         tok_yx_fast(a, inv_ww, wy, wx, qi, qy, qx);
         const T* qrow = base + int64_t(qy) * a.in.sh + int64_t(qx) * a.in.sw + hf * HH;
-        float4 q4[F16 ? 1 : HH / 4];               // this lane's half of its Q row
-        h8 q8[F16 ? HH / 8 : 1];
-        if constexpr (F16) {
-#pragma unroll
-            for (int k = 0; k < HH / 8; ++k) q8[k] = *reinterpret_cast<const h8*>(qrow + 8 * k);
-        } else {
-#pragma unroll
-            for (int k = 0; k < HH / 4; ++k) q4[k] = *reinterpret_cast<const float4*>(qrow + 4 * k);
-        }
+        AttnWave<T, HD> w;                         // this lane's half of its Q row, one accumulator block; no running maximum: w.m is not used
+        w.init(qrow, 0.f);
 
         // pass 1: the whole score row (one or two 32-key tiles), bias and mask added in registers, then its maximum
-        f32x16 s[2];
+        f32x16 s[2];                               // (s[1] stays unset without a second key tile: both passes skip it)
         float mx = -__builtin_huge_valf();
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
             if (kt == 1 && !two) continue;
             // the tile's 16 bias (and mask) values per lane, requested ahead of the MFMAs that hide their latency; the 32 lanes of a half read 32
             // consecutive floats per key
@@ -202,21 +191,7 @@ __global__ __launch_bounds__(kWinBlock) void window_attention_mfma_kernel(const 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) bm[r] += mask[(32 * kt + (r & 3) + 8 * (r >> 2) + 4 * hf) * Lp + q0 + col];
             }
-            const T* krow = Ks + (32 * kt + col) * RS + hf * HH;
-            if constexpr (F16) {
-#pragma unroll
-                for (int k = 0; k < HH; k += 8)
-                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(krow + k), q8[k / 8], s[kt], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int k = 0; k < HH; k += 4) {
-                    const float4 kf = *reinterpret_cast<const float4*>(krow + k);
-                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, q4[k / 4].x, s[kt], 0, 0, 0);
-                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, q4[k / 4].y, s[kt], 0, 0, 0);
-                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, q4[k / 4].z, s[kt], 0, 0, 0);
-                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, q4[k / 4].w, s[kt], 0, 0, 0);
-                }
-            }
+            s[kt] = w.template qk_tile<RS>(Ks + 32 * kt * RS, col, hf);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 s[kt][r] = fmaf(s[kt][r], sl2, bm[r] * kLog2e);
@@ -226,54 +201,19 @@ __global__ __launch_bounds__(kWinBlock) void window_attention_mfma_kernel(const 
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));      // finite: key 0 is real
 
         // pass 2: probabilities, their sum, and O^T += V^T . P^T from the registers the probabilities are in
-        f32x16 o0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o0[r] = 0.f;
-        float lsum = 0.f;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
             if (kt == 1 && !two) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 s[kt][r] = fast_exp2(s[kt][r] - mx);
-                lsum += s[kt][r];
+                w.lsum += s[kt][r];
             }
-            if constexpr (F16) {
-#pragma unroll
-                for (int st = 0; st < 2; ++st) {
-                    h8 pb, va0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int key = 32 * kt + 16 * st + 8 * (j >> 2) + 4 * hf + (j & 3);
-                        pb[j] = _Float16(s[kt][8 * st + j]);
-                        va0[j] = Vs[key * RS + col];
-                    }
-                    o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va0, pb, o0, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * hf;
-                    o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(float(Vs[key * RS + col]), s[kt][r], o0, 0, 0, 0);
-                }
-            }
+            w.template pv_tile<RS>(Vs + 32 * kt * RS, s[kt], col, hf);
         }
-        lsum += __shfl_xor(lsum, 32, 64);
+        w.lsum += __shfl_xor(w.lsum, 32, 64);
         if (q0 + col >= L) continue;               // a padded query: no exchange follows in this iteration
-        const float inv = 1.f / lsum;
-        T* orow = reinterpret_cast<T*>(a.out.p) + n * a.out.sn + int64_t(qy) * a.out.sh + int64_t(qx) * a.out.sw + h * HD;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int e0 = 8 * g + 4 * hf;         // registers 4 g ... 4 g + 3 are the output columns e0 ... e0 + 3 of this lane's query
-            if constexpr (F16) {
-                h4 x;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) x[t] = _Float16(o0[4 * g + t] * inv);
-                *reinterpret_cast<h4*>(orow + e0) = x;
-            } else {
-                *reinterpret_cast<float4*>(orow + e0) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-            }
-        }
+        w.store(reinterpret_cast<T*>(a.out.p) + n * a.out.sn + int64_t(qy) * a.out.sh + int64_t(qx) * a.out.sw + h * HD, hf);
     }
 }
 
