@@ -20,16 +20,14 @@ from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
 from oracle import onnx_oracle as O
+from refusals import refused
 
 PRECS = ("fp32", "fp16")
 N, L, V, D = 2, 5, 37, 8
 
 
 def _refused(tmp_path, monkeypatch, mb, text, prec="fp32", batch=N):
-    path = models.write_repo(str(tmp_path), "bad", mb)
-    with pytest.raises(RuntimeError) as e:
-        describe_model(path, batch, monkeypatch, prec)
-    assert text in str(e.value), str(e.value)
+    refused(mb, batch, monkeypatch, text, prec=prec)
 
 
 def _nameless(step):
@@ -319,8 +317,7 @@ def test_left_over_chain_ops_stay_unsupported(tmp_path, monkeypatch):
             steps = describe_model(path, 2, monkeypatch)["plan"]["steps"]
             assert any(s.get("act", [None])[0] == "tanh" for s in steps)
         else:
-            with pytest.raises(RuntimeError, match="Unsupported ONNX operator: Cast"):
-                describe_model(path, 2, monkeypatch)
+            refused(path, 2, monkeypatch, match="Unsupported ONNX operator: Cast")
 
 
 # ---- the graph writer ------------------------------------------------------------------------------------------------------------------------

@@ -27,6 +27,7 @@ from gpu_ai_inference_server_amd import binding as B  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import models  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb  # noqa: E402
 from oracle import onnx_oracle as O  # noqa: E402
+from refusals import refused  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden", "plan_digests_convnext.json")
 PRECS = ("fp32", "fp16")
@@ -147,8 +148,7 @@ def test_near_miss_of_the_erf_pattern_is_refused(tmp_path, monkeypatch):
     y = gb.gelu(gb.conv("x", 4, 8, 1), "erf", half=0.6)
     gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     path = models.write_repo(str(tmp_path), "near", gb.finish([("x", [2, 4, 6, 6])], [("y", [2, 8, 6, 6])], opset=17))
-    with pytest.raises(RuntimeError, match=r"Unsupported ONNX operator: Erf \(node erf_\d+\)"):
-        describe(path, 2, monkeypatch, "fp32")
+    refused(path, 2, monkeypatch, match=r"Unsupported ONNX operator: Erf \(node erf_\d+\)")
     # the same graph with 0.5 plans; an Erf whose Div output has a second reader does not
     gb = models.GraphBuilder("g", 3)
     y = gb.gelu(gb.conv("x", 4, 8, 1), "erf")
@@ -162,8 +162,7 @@ def test_near_miss_of_the_erf_pattern_is_refused(tmp_path, monkeypatch):
     y = gb.simple("Mul", [gb.simple("Mul", [x, e]), gb.init("half", np.array(0.5, np.float32))])
     gb.nodes.append(pb.node("Add", [y, d], ["y"], "out"))
     path = models.write_repo(str(tmp_path), "shared", gb.finish([("x", [2, 4, 6, 6])], [("y", [2, 8, 6, 6])], opset=17))
-    with pytest.raises(RuntimeError, match="Unsupported ONNX operator: Erf"):
-        describe(path, 2, monkeypatch, "fp32")
+    refused(path, 2, monkeypatch, match="Unsupported ONNX operator: Erf")
 
 
 def test_gelu_behind_a_depthwise_conv_takes_the_generic_tile(tmp_path, monkeypatch):
@@ -213,8 +212,7 @@ def _refused(tmp_path, monkeypatch, name, build, ishape, oshape, match, prec="fp
     y = build(gb)
     gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     path = models.write_repo(str(tmp_path), name, gb.finish([("x", ishape)], [("y", oshape)], opset=17))
-    with pytest.raises(RuntimeError, match=match):
-        describe(path, ishape[0], monkeypatch, prec)
+    refused(path, ishape[0], monkeypatch, prec=prec, match=match)
 
 
 def test_refusals(tmp_path, monkeypatch):
@@ -256,21 +254,18 @@ def test_channels_last_graph_output_is_refused(tmp_path, monkeypatch):
     gb = models.GraphBuilder("r", 3)
     y = gb.layernorm(gb.transpose("x", (0, 2, 3, 1)), 8, name="ln")
     path = models.write_repo(str(tmp_path), "clout", gb.finish([("x", [2, 8, 6, 6])], [(y, [2, 6, 6, 8])], opset=17))
-    with pytest.raises(RuntimeError, match=r"graph output ln_out is a channels-last view"):
-        describe(path, 2, monkeypatch, "fp32")
+    refused(path, 2, monkeypatch, match=r"graph output ln_out is a channels-last view")
 
 
 def test_fp8_is_refused(tiny, tmp_path, monkeypatch):
     path, _ = tiny
-    with pytest.raises(RuntimeError, match=r"^LayerNormalization is not supported in fp8 mode \(node stem_ln\)$"):
-        describe(path, 1, monkeypatch, "fp8")
+    refused(path, 1, monkeypatch, prec="fp8", match=r"^LayerNormalization is not supported in fp8 mode \(node stem_ln\)$")
     # without a LayerNormalization in front of it, a GELU falls under the activation refusal
     gb = models.GraphBuilder("g", 3)
     y = gb.gelu(gb.conv("x", 16, 16, 1), "erf")
     gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     p8 = models.write_repo(str(tmp_path), "g8", gb.finish([("x", [2, 16, 6, 6])], [("y", [2, 16, 6, 6])], opset=17))
-    with pytest.raises(RuntimeError, match=r"^activation and squeeze-excite nodes .* are not supported in fp8 mode"):
-        describe(p8, 2, monkeypatch, "fp8")
+    refused(p8, 2, monkeypatch, prec="fp8", match=r"^activation and squeeze-excite nodes .* are not supported in fp8 mode")
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------------

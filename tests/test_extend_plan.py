@@ -19,6 +19,7 @@ import ref64
 import test_plan_digests as TPD
 from engine_run import describe, RTOL
 from gpu_ai_inference_server_amd.modelgen import models
+from refusals import refused
 
 N, P, LQ = KG.NARROW_N, KG.NARROW_P, 4
 D, H, HKV, V, DEPTH = KG.NARROW["dim"], KG.NARROW["heads"], KG.NARROW["kv_heads"], KG.NARROW["vocab"], KG.NARROW["depth"]
@@ -31,11 +32,8 @@ def _plan(tmp_path, monkeypatch, mb, name="g", batch=N, prec="fp32", **env):
 
 
 def _refused(tmp_path, monkeypatch, mb, *matches, batch=N, prec="fp32"):
-    path = models.write_repo(str(tmp_path), "bad", mb)
-    with pytest.raises(RuntimeError) as e:
-        describe(path, batch, monkeypatch, prec)
-    for match in matches:
-        assert match in str(e.value), str(e.value)
+    """the load is refused, and the text holds every one of `matches` (the node and the rule)"""
+    refused(mb, batch, monkeypatch, *matches, prec=prec)
 
 
 def test_seq_1_builds_the_decode_graph_and_seq_2_needs_its_inputs():
@@ -187,8 +185,7 @@ def test_refusals(tmp_path, monkeypatch, engine_lib):
     r(KG.decode_attn_graph(rows, N, H, 2, 32, 12, mask_width=12), "the key mask attention_mask is [2, 12]; its width must be P + 1 = 13")
     # fp8 refuses the graph as it refuses Llama
     path = models.write_repo(str(tmp_path), "f8", KG.narrow(seq=LQ, past=P))
-    with pytest.raises(RuntimeError):
-        describe(path, N, monkeypatch, "fp8")
+    refused(path, N, monkeypatch, prec="fp8")
 
 
 def test_fp16_headroom():

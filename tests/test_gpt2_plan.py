@@ -18,6 +18,7 @@ from engine_run import describe
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
+from refusals import refused
 
 N, L, V, D, H = 2, 40, 61, 128, 2
 
@@ -28,11 +29,7 @@ def _plan(tmp_path, monkeypatch, mb, name="g", batch=N, prec="fp32", **env):
 
 def _refused(tmp_path, monkeypatch, mb, *matches, batch=N):
     """the load is refused, and the text holds every one of `matches` (the node and the rule)"""
-    path = models.write_repo(str(tmp_path), "bad", mb)
-    with pytest.raises(RuntimeError) as e:
-        describe(path, batch, monkeypatch)
-    for match in matches:
-        assert match in str(e.value), str(e.value)
+    refused(mb, batch, monkeypatch, *matches)
 
 
 @pytest.mark.parametrize("prec", ("fp32", "fp16"))
@@ -236,8 +233,7 @@ def test_embed_sum_graph_plan_and_fp8(tmp_path, monkeypatch, engine_lib):
         assert [s["kind"] for s in p["steps"]] == ["embed", "layer_norm", "eltwise", "copy", "copy"] and p["steps"][0]["ln"] is False
         assert [o["dims"] for o in p["outputs"]] == [[N, L, D], [N, D, 1, L]]
     path = models.write_repo(str(tmp_path), "f8", models.gpt2_tiny(N))
-    with pytest.raises(RuntimeError, match="is not supported in fp8 mode"):
-        describe(path, N, monkeypatch, "fp8")
+    refused(path, N, monkeypatch, prec="fp8", match="is not supported in fp8 mode")
 
 
 def test_float64_walk_agrees_across_spellings(engine_lib):

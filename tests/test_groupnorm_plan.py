@@ -11,6 +11,7 @@ from engine_run import describe
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb
+from refusals import refused
 
 PRECS = ("fp32", "fp16")
 RTOL16 = 3e-3
@@ -176,15 +177,13 @@ REFUSALS = {
 def test_refusals(tmp_path, monkeypatch, case):
     build, match = REFUSALS[case]
     path = models.write_repo(str(tmp_path), "bad", build())
-    with pytest.raises(RuntimeError, match=match):
-        describe(path, 2, monkeypatch, "fp32")
+    refused(path, 2, monkeypatch, match=match)
 
 
 @pytest.mark.parametrize("form", ["instancenorm", "op21", "instance"])
 def test_fp8_is_refused(tmp_path, monkeypatch, form):
     path = models.write_repo(str(tmp_path), "f8", G.gn_graph(2, 16, 4, 4, 16 if form == "instance" else 4, form=form))
-    with pytest.raises(RuntimeError, match=r"^GroupNormalization is not supported in fp8 mode \(node gn"):
-        describe(path, 2, monkeypatch, "fp8")
+    refused(path, 2, monkeypatch, prec="fp8", match=r"^GroupNormalization is not supported in fp8 mode \(node gn")
 
 
 # ---- whole networks --------------------------------------------------------------------------------------------------------------------------

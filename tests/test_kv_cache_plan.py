@@ -14,6 +14,7 @@ import ref64
 from engine_run import describe, RTOL
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
+from refusals import refused
 
 N, P = KG.NARROW_N, KG.NARROW_P
 D, H, HKV, V, DEPTH = KG.NARROW["dim"], KG.NARROW["heads"], KG.NARROW["kv_heads"], KG.NARROW["vocab"], KG.NARROW["depth"]
@@ -26,11 +27,8 @@ def _plan(tmp_path, monkeypatch, mb, name="g", batch=N, prec="fp32", **env):
 
 
 def _refused(tmp_path, monkeypatch, mb, *matches, batch=N, prec="fp32"):
-    path = models.write_repo(str(tmp_path), "bad", mb)
-    with pytest.raises(RuntimeError) as e:
-        describe(path, batch, monkeypatch, prec)
-    for match in matches:
-        assert match in str(e.value), str(e.value)
+    """the load is refused, and the text holds every one of `matches` (the node and the rule)"""
+    refused(mb, batch, monkeypatch, *matches, prec=prec)
 
 
 def test_switches_off_leave_the_graphs_alone():
@@ -125,8 +123,7 @@ def test_refusals(tmp_path, monkeypatch, engine_lib):
     r(KG.gpt2_decode_attn_graph(N, H, 32, 12), "behind the Split of one qkv Linear (GPT-2's spelling) is not supported")
     # rope together with a key mask stays refused in the prefill form, and fp8 refuses these graphs as it refuses Llama
     path = models.write_repo(str(tmp_path), "f8", KG.narrow(seq=1, past=P))
-    with pytest.raises(RuntimeError):
-        describe(path, N, monkeypatch, "fp8")
+    refused(path, N, monkeypatch, prec="fp8")
 
 
 def test_tile_and_split_switches_show_in_the_plan(tmp_path, monkeypatch, engine_lib):

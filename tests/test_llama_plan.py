@@ -18,6 +18,7 @@ import vit_graphs as G
 from engine_run import describe, RTOL
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
+from refusals import refused
 
 N, L, V, D, H, HKV, MLP = 2, 40, 61, 128, 4, 2, 256
 
@@ -28,11 +29,7 @@ def _plan(tmp_path, monkeypatch, mb, name="g", batch=N, prec="fp32", **env):
 
 def _refused(tmp_path, monkeypatch, mb, *matches, batch=N, prec="fp32"):
     """the load is refused, and the text holds every one of `matches` (the node and the rule)"""
-    path = models.write_repo(str(tmp_path), "bad", mb)
-    with pytest.raises(RuntimeError) as e:
-        describe(path, batch, monkeypatch, prec)
-    for match in matches:
-        assert match in str(e.value), str(e.value)
+    refused(mb, batch, monkeypatch, *matches, prec=prec)
 
 
 @pytest.mark.parametrize("prec", ("fp32", "fp16"))

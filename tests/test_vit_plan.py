@@ -26,6 +26,7 @@ from engine_run import describe  # noqa: E402
 from gpu_ai_inference_server_amd import binding as B  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import models  # noqa: E402
 from gpu_ai_inference_server_amd.modelgen import onnx_pb as pb  # noqa: E402
+from refusals import refused  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden", "plan_digests_vit.json")
 PRECS = ("fp32", "fp16")
@@ -144,8 +145,7 @@ def _refused(tmp_path, monkeypatch, name, build, ishape, match, prec="fp32"):
     if y != "y":
         gb.nodes.append(pb.node("Identity", [y], ["y"], "out"))
     path = models.write_repo(str(tmp_path), name, gb.finish([("x", ishape)], [("y", [1])], opset=17))
-    with pytest.raises(RuntimeError, match=match):
-        describe(path, ishape[0], monkeypatch, prec)
+    refused(path, ishape[0], monkeypatch, prec=prec, match=match)
 
 
 def _tok(gb, c=8):
@@ -235,8 +235,7 @@ def test_token_graph_output_is_refused(tmp_path, monkeypatch):
     gb = models.GraphBuilder("r", 3)
     y = gb.layernorm(_tok(gb), 8, name="ln")
     path = models.write_repo(str(tmp_path), "tokout", gb.finish([("x", [2, 8, 2, 3])], [(y, [2, 6, 8])], opset=17))
-    with pytest.raises(RuntimeError, match=r"graph output ln_out is a token view"):
-        describe(path, 2, monkeypatch, "fp32")
+    refused(path, 2, monkeypatch, match=r"graph output ln_out is a token view")
 
 
 def _attn_variant(tmp_path, monkeypatch, name, mutate, match, heads=2, hd=4, l=6):
@@ -246,8 +245,7 @@ def _attn_variant(tmp_path, monkeypatch, name, mutate, match, heads=2, hd=4, l=6
     t = models.vit_tokens(gb, "x", 3 * d)
     mutate(gb, t, d, heads)
     path = models.write_repo(str(tmp_path), name, gb.finish([("x", [2, 3 * d, 1, l])], [("y", [2, d, 1, l])], opset=17))
-    with pytest.raises(RuntimeError, match=match):
-        describe(path, 2, monkeypatch, "fp32")
+    refused(path, 2, monkeypatch, match=match)
 
 
 def _attention_by_hand(gb, t, d, heads, *, softmax_axis=-1, scale_shape=(), mask=False, second_reader=False, k_index=1, perm5=(2, 0, 3, 1, 4), out_perm=(0, 2, 1, 3)):
@@ -297,12 +295,10 @@ def test_left_over_pieces_are_unsupported_operators(tmp_path, monkeypatch):
 
 def test_fp8_is_refused(tmp_path, monkeypatch):
     path = models.write_repo(str(tmp_path), "vit", G.narrow(BATCH))
-    with pytest.raises(RuntimeError, match=r"^LayerNormalization is not supported in fp8 mode \(node l0_ln1\)$"):
-        describe(path, BATCH, monkeypatch, "fp8")
+    refused(path, BATCH, monkeypatch, prec="fp8", match=r"^LayerNormalization is not supported in fp8 mode \(node l0_ln1\)$")
     # without a LayerNormalization, the attention itself is refused
     p8 = models.write_repo(str(tmp_path), "a8", G.attn_graph(2, 6, 2, 16))
-    with pytest.raises(RuntimeError, match=r"^attention and token views are not supported in fp8 mode \(node "):
-        describe(p8, 2, monkeypatch, "fp8")
+    refused(p8, 2, monkeypatch, prec="fp8", match=r"^attention and token views are not supported in fp8 mode \(node ")
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------------
