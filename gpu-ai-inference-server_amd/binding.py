@@ -72,7 +72,7 @@ ABI_SYMBOLS = [
 ]
 EXT_SYMBOLS = ["EngineDescribeModel", "EnginePrepare", "EngineRunPrepared", "EngineSynchronize", "EngineGetStream",
                "EngineProfile", "EngineGetWeightBlob", "EngineWeightsUpdated", "EngineGetPrecision", "EngineMemcpy", "EngineReadBuffer", "EngineMfmaPeak", "EngineGetBatcherStats", "EngineGetShardStats", "EngineGetRuntimeInfo", "EngineE4m3RoundTrip", "EnginePlanWeights", "EngineVectorAdd",
-               "EngineKvCacheCreate", "EngineKvCacheDestroy", "EngineKvCacheBind", "EngineKvCacheGetLengths", "EngineKvCacheSetLengths", "EngineKvCacheRead", "EngineKvCacheWrite"]
+               "EngineKvCacheCreate", "EngineKvCacheDestroy", "EngineKvCacheBind", "EngineKvCacheGetLengths", "EngineKvCacheSetLengths", "EngineKvCacheRead", "EngineKvCacheWrite", "EngineKvCacheCreateTyped"]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -615,7 +615,7 @@ def RuntimeInfo(model: Model, checksums: bool = False) -> dict:
         lib().FreeErrorMessage(p)
 
 
-KV_CACHE_SYMBOLS = [s for s in EXT_SYMBOLS if s.startswith("EngineKvCache")]
+KV_CACHE_SYMBOLS = [s for s in EXT_SYMBOLS if s.startswith("EngineKvCache") and s != "EngineKvCacheCreateTyped"]      # the calls that serve every cache type
 _kv_declared = False
 
 
@@ -626,7 +626,7 @@ def _kv_lib() -> C.CDLL:
     if not _kv_declared:
         vp, ep, i64p = C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)
         sig = {
-            "EngineKvCacheCreate": (vp, [C.c_int] * 6 + [ep]), "EngineKvCacheDestroy": (None, [vp]), "EngineKvCacheBind": (C.c_bool, [vp, vp, ep]),
+            "EngineKvCacheCreate": (vp, [C.c_int] * 6 + [ep]), "EngineKvCacheCreateTyped": (vp, [C.c_int] * 6 + [C.c_char_p, ep]), "EngineKvCacheDestroy": (None, [vp]), "EngineKvCacheBind": (C.c_bool, [vp, vp, ep]),
             "EngineKvCacheGetLengths": (C.c_bool, [vp, i64p, ep]), "EngineKvCacheSetLengths": (C.c_bool, [vp, i64p, ep]),
             "EngineKvCacheRead": (C.c_bool, [vp, C.c_int, C.c_int, vp, C.c_size_t, ep]), "EngineKvCacheWrite": (C.c_bool, [vp, C.c_int, C.c_int, vp, C.c_size_t, ep]),
         }
@@ -639,14 +639,16 @@ def _kv_lib() -> C.CDLL:
 
 
 class KvCache:
-    """A resident KV cache (EngineKvCache*): per layer K and V, dense fp32 [batch, kv_heads, capacity, head_dim] in HBM, appended in place by the models
-    bound to it; the valid length of every image lives in the object.  A bound model's Infer takes no past_key_values.* and gives no present.*."""
+    """A resident KV cache (EngineKvCache*): per layer K and V, dense fp32 (dtype "f16": IEEE half, for fp16 models) [batch, kv_heads, capacity, head_dim]
+    in HBM, appended in place by the models bound to it; the valid length of every image lives in the object.  A bound model's Infer takes no
+    past_key_values.* and gives no present.*.  read / write move float32 arrays whatever the dtype."""
 
-    def __init__(self, layers: int, batch: int, kv_heads: int, capacity: int, head_dim: int, device_id: int = 0):
+    def __init__(self, layers: int, batch: int, kv_heads: int, capacity: int, head_dim: int, device_id: int = 0, dtype: str = "f32"):
         err = C.c_void_p()
         self.shape = (int(batch), int(kv_heads), int(capacity), int(head_dim))
         self.layers = int(layers)
-        self.handle = _kv_lib().EngineKvCacheCreate(int(device_id), int(layers), *self.shape, C.byref(err))
+        self.dtype = str(dtype)
+        self.handle = _kv_lib().EngineKvCacheCreateTyped(int(device_id), int(layers), *self.shape, self.dtype.encode(), C.byref(err))
         if not self.handle:
             raise RuntimeError(_take_error(err))
 

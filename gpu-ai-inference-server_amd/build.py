@@ -22,7 +22,10 @@ LIB = os.path.join(PKG, "lib", "libinference_engine.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["env.cpp", "onnx_reader.cpp", "plan.cpp", "plan_match.cpp", "repository.cpp", "config.cpp", "executor.cpp", "launch.cpp", "tune.cpp", "bridge.cpp", "bridge_load.cpp", "bridge_run.cpp", "bridge_kv.cpp", "kernels.hip", "kernels_f16.hip", "kernels_ws.hip", "kernels_ws32.hip", "kernels_stem.hip", "kernels_direct.hip", "kernels_f8.hip", "kernels_fused.hip", "kernels_wino.hip", "kernels_x6.hip", "kernels_block.hip", "kernels_ws8.hip", "kernels_dw.hip", "kernels_se.hip", "kernels_grouped.hip", "kernels_resize.hip", "kernels_convt.hip", "kernels_ln.hip", "kernels_attn.hip", "kernels_decode.hip", "kernels_wattn.hip", "kernels_tokens.hip", "kernels_trans.hip", "kernels_embed.hip", "kernels_gn.hip"]
+SOURCES = ["env.cpp", "onnx_reader.cpp", "plan.cpp", "plan_match.cpp", "repository.cpp", "config.cpp", "executor.cpp", "launch.cpp", "tune.cpp", "bridge.cpp", "bridge_load.cpp", "bridge_run.cpp", "bridge_kv.cpp", "kernels.hip", "kernels_f16.hip", "kernels_ws.hip", "kernels_ws32.hip", "kernels_stem.hip", "kernels_direct.hip", "kernels_f8.hip", "kernels_fused.hip", "kernels_wino.hip", "kernels_x6.hip", "kernels_block.hip", "kernels_ws8.hip", "kernels_dw.hip", "kernels_se.hip", "kernels_grouped.hip", "kernels_resize.hip", "kernels_convt.hip", "kernels_ln.hip", "kernels_attn.hip", "kernels_decode.hip", "kernels_decode_h.hip", "kernels_wattn.hip", "kernels_tokens.hip", "kernels_trans.hip", "kernels_embed.hip", "kernels_gn.hip"]
+# per-file flags.  kernels_decode_h.hip: no packed fp32 VALU forms (v_pk_*_f32); its fp32 arithmetic is scalar fma by design
+# (the flag is a device feature: hipcc's host pass notes that it ignores it)
+EXTRA = {"kernels_decode_h.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 COMMON = ["-std=c++17", "-O3", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-unused-result",
           "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
@@ -52,6 +55,7 @@ def _compile(src: str, force: bool) -> str:
             # MFMA accumulators in ordinary VGPRs: for the 256-thread kernels the compiler otherwise parks them in AGPRs (a v_accvgpr_read / _write per
             # element in every epilogue, and 170 + 64 registers instead of 170: one wave per SIMD fewer); scripts/isa_regs.py tabulates both builds
             cmd[1:1] = ["--offload-arch=" + ARCH, "-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+            cmd[1:1] = EXTRA.get(src, [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")

@@ -188,7 +188,8 @@ struct EngineKvCache {
     std::vector<int64_t> lens;               // [batch]
     std::vector<int> upload;                 // the 2 x batch ints on their way to dev->d_lens
     std::vector<std::weak_ptr<ie_bridge::ModelObj>> bound;
-    size_t bytes = 0;
+    size_t bytes = 0;                        // of K and V in HBM, in the cache's own element type
+    float* stage = nullptr;                  // a half cache: the fp32 staging buffer of Read / Write, allocated by the first of them (under mu)
 };
 
 namespace ie_bridge {

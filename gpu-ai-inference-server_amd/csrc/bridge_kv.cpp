@@ -11,6 +11,8 @@ void hip_ok(hipError_t e, const char* what) {
     if (e != hipSuccess) { (void)hipGetLastError(); throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e)); }
 }
 
+constexpr size_t kKvStageFloats = size_t(1) << 22;      // Read / Write on a half cache: the staging buffer, 16 MiB of fp32
+
 size_t tensor_floats(const ie::KvBinding& g) { return size_t(g.batch) * size_t(g.kv_heads) * size_t(g.capacity) * size_t(g.head_dim); }
 
 // the layer of `past_key_values.<i>.key|value` / `present.<i>.key|value` and whether it is the value (-1: not such a name)
@@ -117,7 +119,9 @@ std::string KvCacheJson(ModelObj& M) {
     std::ostringstream o;
     const ie::KvBinding& d = *C->dev;
     o << "{\"device\":" << C->device_id << ",\"layers\":" << d.layers << ",\"batch\":" << d.batch << ",\"kv_heads\":" << d.kv_heads << ",\"capacity\":" << d.capacity
-      << ",\"head_dim\":" << d.head_dim << ",\"bytes\":" << C->bytes << ",\"lengths\":[";
+      << ",\"head_dim\":" << d.head_dim << ",\"bytes\":" << C->bytes;
+    if (d.f16) o << ",\"dtype\":\"f16\"";      // (an fp32 cache's member stays what it was)
+    o << ",\"lengths\":[";
     for (size_t i = 0; i < C->lens.size(); ++i) o << (i ? "," : "") << C->lens[i];
     size_t models = 0;
     for (const auto& w : C->bound) if (!w.expired()) ++models;
@@ -216,17 +220,24 @@ using ie_bridge::set_error;
 
 extern "C" {
 
-EngineKvCacheHandle EngineKvCacheCreate(int device_id, int layers, int batch, int kv_heads, int capacity, int head_dim, ErrorMessage* error) {
-    if (layers < 1 || batch < 1 || kv_heads < 1 || capacity < 1 || head_dim < 1 || layers > 4096 || batch > 65535 || kv_heads > 65535) {
-        set_error(error, "EngineKvCacheCreate: layers, batch, kv_heads, capacity and head_dim must be positive (layers <= 4096, batch and kv_heads <= 65535)");
+namespace {
+// both creation calls; `who` = the entry point's name in front of its refusals
+EngineKvCacheHandle create_cache(const std::string& who, int device_id, int layers, int batch, int kv_heads, int capacity, int head_dim, const std::string& type, ErrorMessage* error) {
+    if (type != "f32" && type != "f16") {
+        set_error(error, who + ": unknown dtype \"" + type + "\" (a resident cache stores \"f32\" or \"f16\")");
         return nullptr;
     }
-    if (device_id < 0 || device_id >= ie::HipDeviceCount()) { set_error(error, "EngineKvCacheCreate: no HIP device " + std::to_string(device_id)); return nullptr; }
+    if (layers < 1 || batch < 1 || kv_heads < 1 || capacity < 1 || head_dim < 1 || layers > 4096 || batch > 65535 || kv_heads > 65535) {
+        set_error(error, who + ": layers, batch, kv_heads, capacity and head_dim must be positive (layers <= 4096, batch and kv_heads <= 65535)");
+        return nullptr;
+    }
+    if (device_id < 0 || device_id >= ie::HipDeviceCount()) { set_error(error, who + ": no HIP device " + std::to_string(device_id)); return nullptr; }
     auto C = std::make_unique<EngineKvCache>();
     auto dev = std::make_shared<ie::KvBinding>();
     try {
         dev->layers = layers; dev->batch = batch; dev->kv_heads = kv_heads; dev->capacity = capacity; dev->head_dim = head_dim;
-        const size_t bytes = ie_bridge::tensor_floats(*dev) * sizeof(float);
+        dev->f16 = type == "f16";
+        const size_t bytes = ie_bridge::tensor_floats(*dev) * (dev->f16 ? 2 : sizeof(float));
         ie_bridge::hip_ok(hipSetDevice(device_id), "hipSetDevice");
         ie_bridge::hip_ok(hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking), "hipStreamCreate");
         for (int l = 0; l < 2 * layers; ++l) {
@@ -251,6 +262,15 @@ EngineKvCacheHandle EngineKvCacheCreate(int device_id, int layers, int batch, in
     C->device_id = device_id;
     C->lens.assign(size_t(batch), 0);
     return C.release();
+}
+}  // namespace
+
+EngineKvCacheHandle EngineKvCacheCreate(int device_id, int layers, int batch, int kv_heads, int capacity, int head_dim, ErrorMessage* error) {
+    return create_cache("EngineKvCacheCreate", device_id, layers, batch, kv_heads, capacity, head_dim, "f32", error);
+}
+
+EngineKvCacheHandle EngineKvCacheCreateTyped(int device_id, int layers, int batch, int kv_heads, int capacity, int head_dim, const char* dtype, ErrorMessage* error) {
+    return create_cache("EngineKvCacheCreateTyped", device_id, layers, batch, kv_heads, capacity, head_dim, dtype ? dtype : "", error);
 }
 
 void EngineKvCacheDestroy(EngineKvCacheHandle cache) {
@@ -278,6 +298,7 @@ void EngineKvCacheDestroy(EngineKvCacheHandle cache) {
     for (float* p : cache->dev->k) (void)hipFree(p);
     for (float* p : cache->dev->v) (void)hipFree(p);
     if (cache->dev->d_lens) (void)hipFree(cache->dev->d_lens);
+    if (cache->stage) (void)hipFree(cache->stage);
     delete cache;
 }
 
@@ -291,6 +312,8 @@ bool EngineKvCacheBind(ModelHandle handle, EngineKvCacheHandle cache, ErrorMessa
         auto refuse = [&](const std::string& why) { set_error(error, "EngineKvCacheBind: " + why); return false; };
         const ie::KvBinding& g = *cache->dev;
         if (M.lanes[0]->precision() == ie::Precision::F8) return refuse("fp8 precision has no cache steps; a resident cache binds to fp32 and fp16 models");
+        if (g.f16 && M.lanes[0]->precision() != ie::Precision::F16)
+            return refuse("the cache stores f16 and the model runs in fp32 precision; an f16 cache binds to models loaded under IE_PRECISION=fp16");
         if (M.num_shards > 1) return refuse("the model has " + std::to_string(M.num_shards) + " shard replicas; a resident cache binds to a model of one lane");
         if (M.lanes.size() > 1) return refuse("the model has " + std::to_string(M.lanes.size()) + " execution lanes (instance_count); a resident cache binds to a model of one lane");
         if (M.batchable && M.max_batch > 1) return refuse("the model uses the dynamic batcher; a resident cache binds to a model without it");
@@ -355,6 +378,25 @@ bool cache_copy(EngineKvCacheHandle cache, int layer, int which, void* dst, cons
             }
         float* p = (which ? d.v : d.k)[size_t(layer)];
         ie_bridge::hip_ok(hipSetDevice(cache->device_id), "hipSetDevice");
+        if (d.f16) {
+            // a half cache behind the fp32 signature: chunks of the tensor pass through one fp32 staging buffer on the device, where a small kernel rounds
+            // them to nearest-even on the way in and widens them exactly on the way out
+            const size_t total = ie_bridge::tensor_floats(d), chunk = std::min(total, ie_bridge::kKvStageFloats);
+            if (!cache->stage) ie_bridge::hip_ok(hipMalloc(reinterpret_cast<void**>(&cache->stage), chunk * sizeof(float)), "hipMalloc(kv staging)");
+            char* half = reinterpret_cast<char*>(p);
+            for (size_t at = 0; at < total; at += chunk) {
+                const size_t n = std::min(chunk, total - at);
+                if (to_host) {
+                    ie_bridge::hip_ok(ie::LaunchKvConvert(half + at * 2, cache->stage, int64_t(n), false, cache->stream), "kv_convert_kernel");
+                    ie_bridge::hip_ok(hipMemcpyAsync(static_cast<float*>(dst) + at, cache->stage, n * sizeof(float), hipMemcpyDeviceToHost, cache->stream), "hipMemcpyAsync(kv cache)");
+                } else {
+                    ie_bridge::hip_ok(hipMemcpyAsync(cache->stage, static_cast<const float*>(src) + at, n * sizeof(float), hipMemcpyHostToDevice, cache->stream), "hipMemcpyAsync(kv cache)");
+                    ie_bridge::hip_ok(ie::LaunchKvConvert(cache->stage, half + at * 2, int64_t(n), true, cache->stream), "kv_convert_kernel");
+                }
+                ie_bridge::hip_ok(hipStreamSynchronize(cache->stream), "hipStreamSynchronize");      // (the host side of a chunk may be pageable: the buffer is free again)
+            }
+            return true;
+        }
         ie_bridge::hip_ok(to_host ? hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, cache->stream) : hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, cache->stream), "hipMemcpyAsync(kv cache)");
         ie_bridge::hip_ok(hipStreamSynchronize(cache->stream), "hipStreamSynchronize");
         return true;

@@ -213,8 +213,10 @@ void MarkInplace(PlanInstance& pi) {
         const bool fits = layer >= 0 && layer < kv.layers && s.in.n == kv.batch && hkv == kv.kv_heads && s.head_dim == kv.head_dim &&
                           (s.past_len > 0 ? s.past_len == kv.capacity : s.in.w <= kv.capacity);
         if (!fits) throw std::runtime_error("the cache step " + s.name + " does not fit the bound KV cache (layer " + std::to_string(layer) + ")");
+        if (kv.f16 && !s.in.f16) throw std::runtime_error("the cache step " + s.name + " has fp32 activations: a half KV cache serves half activations only");
         s.inplace = true;
         s.kv_layer = layer;
+        s.kv_f16 = kv.f16;
     };
     for (Step& s : pi.plan.steps) {
         mark(s);

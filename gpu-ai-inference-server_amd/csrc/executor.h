@@ -107,6 +107,7 @@ struct KvBinding {
     int layers = 0, batch = 0, kv_heads = 0, capacity = 0, head_dim = 0;
     std::vector<float*> k, v;
     int* d_lens = nullptr;
+    bool f16 = false;                  // K and V hold IEEE half behind the float pointers: half the bytes, fp16 models only
 };
 
 struct PlanInstance {

@@ -420,7 +420,7 @@ bool AttentionEligible(const AttnArgs& a, int tile);
 hipError_t LaunchAttention(const AttnArgs& a, int tile, hipStream_t stream);
 
 // KV cache: append and one-token decode attention (kernels_decode.hip; generation with Llama-class graphs).  The cache tensors are fp32 in every
-// precision and dense [N][kv_heads][rows][head_dim]: past_k / past_v with rows = past_len (null: no past), present_k / present_v with rows =
+// precision (but for a half resident cache, DecodeArgs::cache_f16) and dense [N][kv_heads][rows][head_dim]: past_k / past_v with rows = past_len (null: no past), present_k / present_v with rows =
 // past_len + new_len.  in = the qkv token rows [N, new_len, (H + 2 Hkv) hd] as AttnArgs describes them (float or half).
 //   kv_append          present rows < past_len = the past rows, bit for bit; row past_len + l = k of token l after the rotary embedding (AttnArgs'
 //                      arithmetic: full-width fp32 tables, fp32 products) resp. v of token l, converted to fp32
@@ -459,6 +459,9 @@ struct DecodeArgs {
     int64_t cache_rows = 0;
     const int* lens = nullptr;         // [N], device
     const int* news = nullptr;         // [N], device
+    // A half resident cache (in place only, in.f16 only): K and V are IEEE half in the same dense layout, and the four cache pointers above
+    // address _Float16 elements behind their float type.  New k rows are rotated in fp32 and rounded once to nearest-even, v rows are copied as they are
+    bool cache_f16 = false;
 };
 // A decode step's tiles: 0 = attention_decode_generic_kernel (one wave per (image, query head) over `present`, which a kv_append launch wrote: any
 // head_dim up to kDecodeMaxHeadDim, any past_len, float or half); kAttnDecodeTile (4) = attention_decode_kernel<T, HD, G>: a workgroup = (image, K / V
@@ -471,6 +474,9 @@ constexpr int kDecodeMaxHeadDim = 512;
 constexpr int kDecodeMaxGroup = 8;
 constexpr int kDecodeMaxSplits = 64;
 constexpr int DecodeKeyTile(int hd) { return 1024 / hd; }
+// tile 4 over a half cache (attention_decode_h_kernel): the same 16 bytes per lane are eight halfs.  The grid and the eligibility stay DecodeKeyTile's: the
+// kernel shares len among the plan's splits in whole tiles of its own at run time
+constexpr int DecodeKeyTileHalf(int hd) { return 2048 / hd; }
 // tile 4 declines a mask whose bias is small enough to keep something of a score in an fp32 sum (|c| <= 2^24, e.g. -10000): tile 0 takes the image's
 // largest bias out of every score first, as attention_generic_kernel<mask> does, and a split sees only its own keys
 constexpr bool DecodeFastFits(int hd, int heads, int kv_heads, bool masked, float mask_value) {
@@ -527,6 +533,8 @@ bool KvAppendEligible(const DecodeArgs& a);
 hipError_t LaunchKvAppend(const DecodeArgs& a, hipStream_t stream);
 bool AttentionDecodeEligible(const DecodeArgs& a, int tile);
 hipError_t LaunchAttentionDecode(const DecodeArgs& a, int tile, hipStream_t stream);
+// n elements fp32 -> half (round to nearest even, NaN stays NaN) or half -> fp32 (exact): EngineKvCacheWrite / Read on a half cache (kernels_decode_h.hip)
+hipError_t LaunchKvConvert(const void* src, void* dst, int64_t n, bool to_half, hipStream_t stream);
 hipError_t InitKernelsAttn();            // once per process, before any capture: lets the MFMA kernels take more than 64 KiB of LDS
 
 // Attention inside (shifted) windows of a channels-last map (kernels_wattn.hip; Swin).  in = the qkv map [N, H, W, 3 D], out = [N, H, W, D].  The map is

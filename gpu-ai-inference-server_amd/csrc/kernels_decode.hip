@@ -34,6 +34,10 @@
 //   attention_decode_kernel<.., true>    tile 4 without the `present` store: the key loop covers [0, len), one workgroup writes row len from registers.
 //   attention_extend_kernel<.., true>    tile 5 behind the kv_append_rows launch, its causal limit counted from len.
 //
+// A half resident cache (DecodeArgs::cache_f16): the cache pointers address halfs.  Tile 0 and tile 5 are the kernels above with the cache's
+// element type as a template parameter (KV resp. KVH); the append and tile 4 over such a cache are kernels of their own in kernels_decode_h.hip, which
+// LaunchKvAppend and launch_decode hand over to.
+//
 // Scores, statistics and accumulation are fp32.  The key-mask bias (1 - float(mask[n, j])) * c is added to the scaled score in fp32 and the sum clamped
 // at -FLT_MAX, as the MASK forms of kernels_attn.hip keep it finite: the running maximum starts at -FLT_MAX too, so a split (or a whole row) whose
 // keys are all masked has m = -FLT_MAX, l = its key count and o = the plain sum of its V rows; next to a split with a real score its weight
@@ -44,42 +48,12 @@
 #include <cstdint>
 
 #include "attn_mfma.h"
+#include "decode_util.h"
 #include "kernels.h"
 #include "launch_util.h"
 
 namespace ie {
 namespace {
-
-constexpr int kDecodeBlock = 256;
-
-// the table row of token l of image n: the token's own id pos[n pos_sn + l] (a negative position counts from the end), l without pos, clamped into the table
-__device__ __forceinline__ int64_t rope_row(const DecodeArgs& a, int64_t n, int l) {
-    int64_t r = l;
-    if (a.pos) {
-        const int64_t p = a.pos[n * a.pos_sn + l];
-        r = p < 0 ? p + a.rope_rows : p;
-    }
-    return r < 0 ? 0 : (r >= a.rope_rows ? a.rope_rows - 1 : r);
-}
-
-// element e of the head whose row starts at element `rb` of the qkv buffer, rotated at table row r (cos null: as it is)
-template <typename T>
-__device__ __forceinline__ float rotated(const DecodeArgs& a, int64_t rb, int64_t r, int e, bool rope) {
-    const T* p = reinterpret_cast<const T*>(a.in.p);
-    const float x = float(p[rb + int64_t(e) * a.in.sc]);
-    if (!rope) return x;
-    const int hh = a.head_dim / 2, pe = e < hh ? e + hh : e - hh;
-    const float xp = float(p[rb + int64_t(pe) * a.in.sc]);
-    const int64_t t = r * a.head_dim + e;
-    return fmaf(x, a.rope_cos[t], (e < hh ? -xp : xp) * a.rope_sin[t]);
-}
-
-// the first element of k (which = 1) or v (which = 2) of K / V head kvh of token (n, l) in the qkv buffer; which = 0: of query head kvh
-__device__ __forceinline__ int64_t qkv_base(const DecodeArgs& a, int64_t n, int l, int which, int head) {
-    const int64_t D = int64_t(a.heads) * a.head_dim, Dkv = int64_t(a.kv_heads) * a.head_dim;
-    const int64_t col = (which == 0 ? 0 : (which == 1 ? D : D + Dkv)) + int64_t(head) * a.head_dim;
-    return n * a.in.sn + int64_t(l) * a.in.sw + col * a.in.sc;
-}
 
 template <typename T, int V>
 __global__ __launch_bounds__(kDecodeBlock) void kv_append_kernel(const DecodeArgs a, const int64_t total) {
@@ -122,18 +96,6 @@ __global__ __launch_bounds__(kDecodeBlock) void kv_append_kernel(const DecodeArg
     }
 }
 
-// In place: image n's valid rows and the tokens this step appends, clamped so that whatever the two arrays hold no kernel leaves the cache:
-// 0 <= len <= cache_rows, 0 <= c <= min(new_len, cache_rows - len)
-struct Resident { int len, c; };
-__device__ __forceinline__ Resident resident(const DecodeArgs& a, int64_t n) {
-    const int rows = int(a.cache_rows);
-    int len = a.lens[n], c = a.news[n];
-    len = len < 0 ? 0 : (len > rows ? rows : len);
-    c = c > a.new_len ? a.new_len : c;
-    c = c > rows - len ? rows - len : c;
-    return {len, c < 0 ? 0 : c};
-}
-
 // In place: one lane per V consecutive floats of the step's new rows [N][Hkv][new_len][hd].  Token l < c of image n: k after the rotary embedding and v
 // go to row len + l of the cache (kv_append_kernel's arithmetic); a token l >= c and every other row of the cache: untouched
 template <typename T, int V>
@@ -167,14 +129,12 @@ __global__ __launch_bounds__(kDecodeBlock) void kv_append_rows_kernel(const Deco
     }
 }
 
-// the bias of key j of image n, and the image's largest bias where it is small enough to be taken out of every score exactly (0 otherwise)
-__device__ __forceinline__ float key_bias(const DecodeArgs& a, int64_t n, int j) { return (1.f - float(a.mask[n * a.mask_sn + j])) * a.mask_value; }
-
 // One wave of tile 0: query head h of token i of image n over the first Lk rows of its K / V head at K / Vp.  The first `biased` of them carry their mask
 // column's bias (the new rows of a resident cache carry none: their columns are of the prefix of ones); the shift is the largest bias among the keys the
-// query sees.  ZERO_EMPTY: a row with nothing visible (l = 0) comes out as zeros, and the row is scaled by 1 / l instead of divided by l
-template <typename T, bool ZERO_EMPTY>
-__device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int h, int i, const float* K, const float* Vp, int Lk, int biased) {
+// query sees.  ZERO_EMPTY: a row with nothing visible (l = 0) comes out as zeros, and the row is scaled by 1 / l instead of divided by l.  KV: the
+// cache's element type (a half cache, DESIGN 3.36: every element is widened where it is read, the arithmetic stays fp32)
+template <typename T, bool ZERO_EMPTY, typename KV = float>
+__device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int h, int i, const KV* K, const KV* Vp, int Lk, int biased) {
     constexpr int kChunks = kDecodeMaxHeadDim / 64;
     const int lane = int(threadIdx.x) % 64;
     const int hd = a.head_dim;
@@ -202,7 +162,7 @@ __device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int 
 #pragma unroll
         for (int c = 0; c < kChunks; ++c) {
             const int e = c * 64 + lane;
-            if (e < hd) s = fmaf(q[c], K[int64_t(j) * hd + e], s);
+            if (e < hd) s = fmaf(q[c], float(K[int64_t(j) * hd + e]), s);
         }
 #pragma unroll
         for (int x = 32; x >= 1; x >>= 1) s += __shfl_xor(s, x, 64);
@@ -212,7 +172,7 @@ __device__ __forceinline__ void attend_wave(const DecodeArgs& a, int64_t n, int 
 #pragma unroll
         for (int c = 0; c < kChunks; ++c) {
             const int e = c * 64 + lane;
-            if (e < hd) acc[c] = fmaf(p, Vp[int64_t(j) * hd + e], acc[c] * al);
+            if (e < hd) acc[c] = fmaf(p, float(Vp[int64_t(j) * hd + e]), acc[c] * al);
         }
         m = mn;
     }
@@ -257,7 +217,7 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_generic_kernel(
 // In place, tile 0 of a decode step (new_len = 1) and of an extend step alike: rows = N * heads * new_len, one wave per (image, query head, new token i), the
 // token fastest, over the resident cache a kv_append_rows launch has appended to.  The wave walks the rows [0, len + min(i, c - 1)] and no other: a
 // row below len carries its mask column's bias, a new row none; a token with nothing visible writes zeros
-template <typename T>
+template <typename T, typename KV = float>
 __global__ __launch_bounds__(kDecodeBlock) void attention_inplace_generic_kernel(const DecodeArgs a, const int64_t rows) {
     const int64_t row = int64_t(blockIdx.x) * (kDecodeBlock / 64) + threadIdx.x / 64;
     if (row >= rows) return;                       // wave-uniform
@@ -266,7 +226,7 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_inplace_generic_kernel
     const int h = int(nh % a.heads);
     const Resident rs = resident(a, n);
     const int64_t kv = (n * a.kv_heads + h / (a.heads / a.kv_heads)) * a.cache_rows * a.head_dim;
-    attend_wave<T, true>(a, n, h, i, a.present_k + kv, a.present_v + kv, rs.len + (i < rs.c ? i : rs.c - 1) + 1, rs.len);
+    attend_wave<T, true, KV>(a, n, h, i, reinterpret_cast<const KV*>(a.present_k) + kv, reinterpret_cast<const KV*>(a.present_v) + kv, rs.len + (i < rs.c ? i : rs.c - 1) + 1, rs.len);
 }
 
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
@@ -460,15 +420,18 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_decode_combine_kernel(
 // carries its mask column's bias and a new row none; the splits share the len + c rows that exist; rows at or beyond len + c are never read, those that
 // fall into a staged chunk are zeros in LDS as the padded keys are.  All of this is uniform over the workgroup (len and c belong to the image), so the
 // barrier rule holds as it stands.  A row with nothing visible at all (c = 0 over an empty cache) takes the weight 1 on its zero sum in split 0
-template <typename T, int HD, bool INPLACE = false>
+// KVH (a half cache, T = half, in place only): a cached row goes HBM -> LDS as HD / 8 16-byte vectors with no conversion, into the same
+// rows at the same stride; everything behind the staging is the same code
+template <typename T, int HD, bool INPLACE = false, bool KVH = false>
 __global__ __launch_bounds__(kDecodeBlock) void attention_extend_kernel(const DecodeArgs a) {
     constexpr bool F16 = sizeof(T) == 2;
     constexpr int V = 16 / int(sizeof(T));         // elements per 16-byte vector
     constexpr int RS = HD + V;                     // LDS row stride in elements
     constexpr int HH = HD / 2;                     // head-dim elements one lane half supplies to QK^T
     constexpr int KC = kAttnChunkKeys;
-    constexpr int VPR = HD / 4;                    // float4s of a `present` row
+    constexpr int VPR = KVH ? HD / 8 : HD / 4;     // 16-byte vectors of a `present` row
     static_assert(KC % 32 == 0, "whole key tiles per chunk");
+    static_assert(!KVH || (F16 && INPLACE), "a half cache is resident and serves half models");
     extern __shared__ __attribute__((aligned(16))) unsigned char extend_smem[];
     T* Ks = reinterpret_cast<T*>(extend_smem);
     T* Vs = Ks + size_t(KC) * RS;
@@ -522,12 +485,38 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_kernel(const De
     for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
     float m = -kFltMax, lsum = 0.f;
     const float sl2 = a.scale * kLog2e;            // scores in units of log2: exp(x) = exp2(x * log2 e)
-    const float* pk = a.present_k + (n * a.kv_heads + kvh) * (INPLACE ? a.cache_rows : int64_t(Lk)) * HD;
-    const float* pv = a.present_v + (n * a.kv_heads + kvh) * (INPLACE ? a.cache_rows : int64_t(Lk)) * HD;
+    constexpr int KVW = KVH ? 2 : 1;               // cache elements per float of the typed pointer
+    const float* pk = a.present_k + (n * a.kv_heads + kvh) * (INPLACE ? a.cache_rows : int64_t(Lk)) * HD / KVW;
+    const float* pv = a.present_v + (n * a.kv_heads + kvh) * (INPLACE ? a.cache_rows : int64_t(Lk)) * HD / KVW;
 
     for (int c0 = kbeg; c0 < kend; c0 += KC) {     // (the bounds are the workgroup's: every wave runs every iteration)
         const int rows = kend - c0 < KC ? (kend - c0 + 31) / 32 * 32 : KC;
-        for (int idx = int(threadIdx.x); idx < rows * VPR; idx += kDecodeBlock) {
+        if constexpr (KVH) {
+            // four vectors of K and of V per thread are requested before the first of them is stored: the chunk of a short split is a handful of
+            // vectors per thread, and one at a time would pay the memory latency for each
+            for (int base = int(threadIdx.x); base < rows * VPR; base += 4 * kDecodeBlock) {
+                h8 kh[4], vh[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int idx = base + u * kDecodeBlock, lr = idx / VPR, cv = idx % VPR, key = c0 + lr;
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) { kh[u][t] = _Float16(0.f); vh[u][t] = _Float16(0.f); }
+                    if (idx < rows * VPR && key < Lk) {
+                        kh[u] = *reinterpret_cast<const h8*>(reinterpret_cast<const _Float16*>(pk) + int64_t(key) * HD + cv * 8);
+                        vh[u] = *reinterpret_cast<const h8*>(reinterpret_cast<const _Float16*>(pv) + int64_t(key) * HD + cv * 8);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int idx = base + u * kDecodeBlock, lr = idx / VPR, cv = idx % VPR;
+                    if (idx < rows * VPR) {
+                        *reinterpret_cast<h8*>(Ks + lr * RS + cv * 8) = kh[u];
+                        *reinterpret_cast<h8*>(Vs + lr * RS + cv * 8) = vh[u];
+                    }
+                }
+            }
+        }
+        for (int idx = int(threadIdx.x); idx < (KVH ? 0 : rows * VPR); idx += kDecodeBlock) {
             const int lr = idx / VPR, cv = idx % VPR, key = c0 + lr;
             float4 kx = make_float4(0.f, 0.f, 0.f, 0.f), vx = kx;                         // rows past P + Lq: zeros (a zero probability times them stays zero)
             if (key < Lk) {
@@ -679,9 +668,10 @@ __global__ __launch_bounds__(kDecodeBlock) void attention_extend_combine_kernel(
 }
 
 // in place: both arrays, one storage for past and present, and a capacity that is the graph's P (a prefill with a cache: at least its L rows), so that
-// every mask column below len exists
+// every mask column below len exists.  A half cache is a resident one and serves half activations
 bool inplace_ok(const DecodeArgs& a) {
-    if (a.cache_rows == 0) return true;
+    if (a.cache_rows == 0) return !a.cache_f16;
+    if (a.cache_f16 && !a.in.f16) return false;
     return a.lens && a.news && a.past_k == a.present_k && a.past_v == a.present_v && a.cache_rows < (int64_t(1) << 31) &&
            (a.past_len > 0 ? a.cache_rows == a.past_len : a.cache_rows >= a.new_len);
 }
@@ -710,7 +700,8 @@ hipError_t launch_decode_hd(const DecodeArgs& a, hipStream_t stream) {
 
 template <typename T>
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
-    const hipError_t e = a.head_dim == 32 ? launch_decode_hd<T, 32>(a, stream) : (a.head_dim == 64 ? launch_decode_hd<T, 64>(a, stream) : launch_decode_hd<T, 128>(a, stream));
+    const hipError_t e = a.cache_f16 ? LaunchDecodeHalf(a, stream)
+                                     : (a.head_dim == 32 ? launch_decode_hd<T, 32>(a, stream) : (a.head_dim == 64 ? launch_decode_hd<T, 64>(a, stream) : launch_decode_hd<T, 128>(a, stream)));
     if (e != hipSuccess || a.splits == 1) return e;
     const int64_t total = int64_t(a.in.n) * a.heads * a.head_dim;
     hipLaunchKernelGGL((attention_decode_combine_kernel<T>), dim3(unsigned((total + kDecodeBlock - 1) / kDecodeBlock)), dim3(kDecodeBlock), 0, stream, a, total);
@@ -721,6 +712,15 @@ template <typename T, int HD>
 hipError_t launch_extend(const DecodeArgs& a, hipStream_t stream) {
     const int64_t rblocks = (int64_t(a.heads / a.kv_heads) * a.new_len + 127) / 128;
     const dim3 grid(unsigned(rblocks * a.splits), unsigned(a.kv_heads), unsigned(a.in.n));
+    if constexpr (sizeof(T) == 2) {
+        if (a.cache_f16) {
+            attention_extend_kernel<T, HD, true, true><<<grid, dim3(kDecodeBlock), size_t(ExtendLdsBytes(HD, true)), stream>>>(a);
+            if (const hipError_t e = hipGetLastError(); e != hipSuccess || a.splits == 1) return e;
+            const int64_t total = int64_t(a.in.n) * a.heads * a.new_len * a.head_dim;
+            hipLaunchKernelGGL((attention_extend_combine_kernel<T>), dim3(unsigned((total + kDecodeBlock - 1) / kDecodeBlock)), dim3(kDecodeBlock), 0, stream, a, total);
+            return hipGetLastError();
+        }
+    }
     if (a.cache_rows > 0) attention_extend_kernel<T, HD, true><<<grid, dim3(kDecodeBlock), size_t(ExtendLdsBytes(HD, sizeof(T) == 2)), stream>>>(a);
     else attention_extend_kernel<T, HD><<<grid, dim3(kDecodeBlock), size_t(ExtendLdsBytes(HD, sizeof(T) == 2)), stream>>>(a);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess || a.splits == 1) return e;
@@ -741,6 +741,7 @@ hipError_t LaunchKvAppend(const DecodeArgs& a, hipStream_t stream) {
     if (!KvAppendEligible(a)) return hipErrorInvalidValue;
     if (a.in.n == 0) return hipSuccess;
     const bool inplace = a.cache_rows > 0;         // the new rows alone
+    if (a.cache_f16) return LaunchKvAppendRowsHalf(a, stream);
     const int64_t floats = int64_t(a.in.n) * a.kv_heads * (inplace ? int64_t(a.new_len) : int64_t(a.past_len) + a.new_len) * a.head_dim;
     const bool vec = a.head_dim % 4 == 0 && Aligned16(a.present_k) && Aligned16(a.present_v) && (a.past_len == 0 || (Aligned16(a.past_k) && Aligned16(a.past_v)));
     const int64_t total = vec ? floats / 4 : floats;
@@ -794,6 +795,10 @@ hipError_t LaunchAttentionDecode(const DecodeArgs& a, int tile, hipStream_t stre
         const int64_t rows = int64_t(a.in.n) * a.heads * a.new_len;
         const int64_t blocks = (rows + kDecodeBlock / 64 - 1) / (kDecodeBlock / 64);
         if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+        if (a.cache_f16) {                         // a half cache: the in-place wave reading half K / V
+            hipLaunchKernelGGL((attention_inplace_generic_kernel<_Float16, _Float16>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
+            return hipGetLastError();
+        }
         if (a.cache_rows > 0) {                    // in place: one kernel for a decode and an extend step, behind the kv_append_rows launch
             if (a.in.f16) hipLaunchKernelGGL((attention_inplace_generic_kernel<_Float16>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
             else hipLaunchKernelGGL((attention_inplace_generic_kernel<float>), dim3(unsigned(blocks)), dim3(kDecodeBlock), 0, stream, a, rows);
@@ -822,6 +827,7 @@ hipError_t InitKernelsDecode() {
         reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 32>), reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 64>),
         reinterpret_cast<const void*>(&attention_extend_kernel<float, 32, true>), reinterpret_cast<const void*>(&attention_extend_kernel<float, 64, true>),
         reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 32, true>), reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 64, true>),
+        reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 32, true, true>), reinterpret_cast<const void*>(&attention_extend_kernel<_Float16, 64, true, true>),
     };
     for (const void* k : kernels)
         if (const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget)); e != hipSuccess) return e;

@@ -166,6 +166,7 @@ struct Step {
     // runs in place on layer kv_layer of the cache (kernels.h DecodeArgs::cache_rows)
     bool inplace = false;
     int kv_layer = -1;
+    bool kv_f16 = false;               // ... of a half cache (kernels.h DecodeArgs::cache_f16)
     int past_len = 0;
     bool chunk_causal = false;
     int splits = 0;

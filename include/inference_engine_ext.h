@@ -74,7 +74,7 @@ char* EngineGetRuntimeInfo(ModelHandle handle, int with_checksums, ErrorMessage*
  * +-448), dst[i] = decode(codes[i]) * scale.  `codes` may be NULL.  Test support for the fp8 precision mode. */
 bool EngineE4m3RoundTrip(const float* src, float* dst, unsigned char* codes, size_t n, float scale, ErrorMessage* error);
 /* Resident KV cache: K and V of a conversation stay in HBM, are appended in place and are shared by the prefill, extend and decode models bound to it.
- * Per layer K and V are dense fp32 [batch][kv_heads][capacity][head_dim] (in every precision), zero-filled at creation; the valid length of every image
+ * Per layer K and V are dense fp32 [batch][kv_heads][capacity][head_dim] (in every precision; EngineKvCacheCreateTyped: or half), zero-filled at creation; the valid length of every image
  * lives on the host, in the object.  Every call takes an ErrorMessage; a NULL handle is an error and touches no device.
  *
  * Bind: a loaded Llama-shaped model whose graph has `past_key_values.<i>.key|value` inputs and `present.<i>.key|value` outputs of exactly this geometry
@@ -94,6 +94,13 @@ bool EngineE4m3RoundTrip(const float* src, float* dst, unsigned char* codes, siz
  * 0) or V (which 1) tensor, `bytes` = batch * kv_heads * capacity * head_dim * 4. */
 typedef struct EngineKvCache* EngineKvCacheHandle;
 EngineKvCacheHandle EngineKvCacheCreate(int device_id, int layers, int batch, int kv_heads, int capacity, int head_dim, ErrorMessage* error);
+/* The same object with a storage type: dtype "f32" (what EngineKvCacheCreate makes) or "f16"; anything else is refused by name before any device is asked
+ * for.  An "f16" cache stores K and V as IEEE half in the same layout, in half the bytes.  It binds only to models loaded under IE_PRECISION=fp16 (an
+ * fp32-precision model is refused by name, nothing changes).  New K rows are rotated in fp32 and rounded once to nearest-even, V rows are the half values
+ * the model produced; the step that appends a row attends to it as stored.  Read and Write keep their fp32 signature and their `bytes` rule: Write rounds
+ * to nearest-even on the device, Read widens exactly, NaN stays NaN.  The kv_cache member of EngineGetRuntimeInfo reports the true bytes and, for this type
+ * only, "dtype":"f16". */
+EngineKvCacheHandle EngineKvCacheCreateTyped(int device_id, int layers, int batch, int kv_heads, int capacity, int head_dim, const char* dtype, ErrorMessage* error);
 void EngineKvCacheDestroy(EngineKvCacheHandle cache);
 bool EngineKvCacheBind(ModelHandle handle, EngineKvCacheHandle cache, ErrorMessage* error);
 bool EngineKvCacheGetLengths(EngineKvCacheHandle cache, int64_t* lens, ErrorMessage* error);

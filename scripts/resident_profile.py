@@ -9,6 +9,9 @@ parent's columns are left out.
 * the extend attention step alone at DESIGN 3.33's Lq = 4 and 128 rows: the parent's tile 5, and the in-place tile 5 with len = P - Lq
 * llama_135m, batch 8, P = 1 023, fp32 and fp16: the wall time of a ModelInfer decode call (seconds inside the C call, binding.InferTimed) unbound on the
   parent build (every past tensor up, every present tensor down) and bound; the graph replay of the step (EngineRunPrepared) on both
+--cache-dtype f16 [--parent-lib ...] [out_dir] (default profiles/decode_resident_half) is the run DESIGN 3.36 records instead: fp16 only, every in-place
+step on an fp32 cache and on a half cache (B.KvCache(dtype="f16")) side by side, with the algorithmic rate (the bytes of the len cached K / V rows in the
+cache's own type over the time) against the 6.29 TB/s copy rate, and llama_135m bound to both cache types.
 Step times are HIP events around each launch (B.Profile, median of 20); wall times are medians of 20 with the spread (min .. max) beside them.  Every
 group of measurements is a child process under its own time limit; the first one that fails ends the run."""
 import json
@@ -32,23 +35,36 @@ def _setup():
     load_package()
 
 
+def _binding():
+    """the binding; over a library from before the half cache (--parent-lib) its typed creation call is stood in for by the library's own f32 one"""
+    from gpu_ai_inference_server_amd import binding as B
+    L = B.lib()
+    if not hasattr(L, "EngineKvCacheCreateTyped"):
+        def typed(dev, layers, n, hkv, cap, hd, dtype, err):
+            assert dtype == b"f32", "this library has fp32 caches only"
+            return L.EngineKvCacheCreate(dev, layers, n, hkv, cap, hd, err)
+        L.EngineKvCacheCreateTyped = typed
+    return B
+
+
 def _median(ts):
     ts = sorted(ts)
     return ts[len(ts) // 2], ts[0], ts[-1]
 
 
 def attention_child(configs):
-    """child: [(n, h, hkv, past, hd, lq, prec, len or None)] -> [{kernel, ms, samples}]: the attention step of each, unbound (len None) or bound to a cache whose
+    """child: [(n, h, hkv, past, hd, lq, prec, len or None[, cache dtype[, IE_ATTN_SPLITS]])] -> [{kernel, ms, samples}]: the attention step of each, unbound (len None) or bound to a cache whose
     images all hold len rows.  The step is profiled three times over (3 x median of 20): the spread of the three is the session's run-to-run spread"""
     _setup()
     import extend_graphs as EG
     import kv_graphs as KG
     from engine_run import with_env
-    from gpu_ai_inference_server_amd import binding as B
     from gpu_ai_inference_server_amd.modelgen import models
+    B = _binding()
     out = []
     with tempfile.TemporaryDirectory() as root:
-        for i, (n, h, hkv, past, hd, lq, prec, ln) in enumerate(configs):
+        for i, (n, h, hkv, past, hd, lq, prec, ln, *more) in enumerate(configs):
+            dt, splits = more[:1], more[1:]
             valid = [past if ln is None else ln] * n
             if lq == 1:
                 rows, feeds = KG.decode_feeds(n, h, hkv, hd, past, valid=valid, positions=valid)
@@ -63,7 +79,7 @@ def attention_child(configs):
                 kc = None
                 try:
                     if ln is not None:
-                        kc = B.KvCache(1, n, hkv, past, hd)
+                        kc = B.KvCache(1, n, hkv, past, hd, 0, *dt)
                         kc.bind(m)
                         kc.write(0, 0, feeds["past_key_values.0.key"])
                         kc.write(0, 1, feeds["past_key_values.0.value"])
@@ -82,16 +98,16 @@ def attention_child(configs):
                     if kc is not None:
                         kc.destroy()
                     m.Destroy()
-            out.append(with_env(dict(IE_PRECISION=prec, IE_AUTOTUNE="0"), go))
+            out.append(with_env(dict(IE_PRECISION=prec, IE_AUTOTUNE="0", **({"IE_ATTN_SPLITS": str(splits[0])} if splits else {})), go))
     print(json.dumps(out))
 
 
-def model_child(path, prec, bound):
+def model_child(path, prec, bound, dtype="f32"):
     """child: llama_135m's decode graph -> {infer_ms: (median, min, max), replay_ms: (median, min, max)}; bound: to a cache whose images hold P - 1 rows"""
     _setup()
     import numpy as np
     from engine_run import tensor
-    from gpu_ai_inference_server_amd import binding as B
+    B = _binding()
     os.environ.update(IE_PRECISION=prec, IE_AUTOTUNE="0")
     n, past, vocab, depth, hkv, hd = (LLAMA[k] for k in ("n", "past", "vocab", "depth", "hkv", "hd"))
     r = np.random.RandomState(0)
@@ -103,7 +119,7 @@ def model_child(path, prec, bound):
     try:
         outs = [B.OutputConfig("logits", Shape=[n, 1, vocab], DataType="FLOAT32")]
         if bound:
-            kc = B.KvCache(depth, n, hkv, past, hd)
+            kc = B.KvCache(depth, n, hkv, past, hd, 0, dtype)
             kc.bind(m)
             for i in range(depth):
                 kc.write(i, 0, cache[f"past_key_values.{i}.key"])
@@ -152,13 +168,77 @@ def child(args, what, lib=None):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
+SWEEP = (1, 2, 4, 8, 16, 32)
+COPY_RATE = 6.29e12      # B/s, the project's measured copy rate
+
+
+def main_half(parent, out_dir):
+    """the half cache beside the fp32 cache, fp16 precision: decode and extend attention steps, then llama_135m through ModelInfer"""
+    from gpu_ai_inference_server_amd.modelgen import models
+    os.makedirs(out_dir, exist_ok=True)
+    me = os.path.abspath(__file__)
+
+    def line(what, r, n, hkv, ln, hd, esize):
+        rate = 2 * n * hkv * ln * hd * esize / (r["ms"] * 1e-3)
+        spread = (max(r["samples"]) - min(r["samples"])) * 1e3
+        return (f"  {what:38s}{r['ms'] * 1e3:8.1f} us (three medians of 20: " + ", ".join(f"{s * 1e3:.1f}" for s in r["samples"]) + f"; spread {spread:.1f})   "
+                f"{rate / 1e12:5.2f} TB/s = {100 * rate / COPY_RATE:4.1f} % of the copy rate   [{r['kernel']}]")
+
+    lines = []
+    shapes = [(n, h, hkv, p, hd, 1) for n, h, hkv, p, hd in DECODE_SHAPES] + list(EXTEND_SHAPES)
+    for n, h, hkv, p, hd, lq in shapes:
+        lens = (p - 1, p // 4) if lq == 1 else (p - lq,)
+        cfg = [(n, h, hkv, p, hd, lq, "fp16", ln, dt) for ln in lens for dt in ("f32", "f16")]
+        what = f"{'decode' if lq == 1 else 'extend'} attention (N {n}, H {h} / {hkv}, P {p}, hd {hd}, Lq {lq}) fp16"
+        mine = child([me, "--attn", json.dumps(cfg)], what)
+        theirs = child([me, "--attn", json.dumps([c[:8] for c in cfg if c[8] == "f32"])], what + ", parent build", parent) if parent else []
+        lines.append(what + ":")
+        for i, (c, r) in enumerate(zip(cfg, mine)):
+            if parent and c[8] == "f32":
+                lines.append(line(f"parent build, fp32 cache, len {c[7]}", theirs[i // 2], n, hkv, c[7], hd, 4))
+            lines.append(line(f"this build, {c[8]} cache, len {c[7]}", r, n, hkv, c[7], hd, 4 if c[8] == "f32" else 2))
+        print("\n".join(lines[-(1 + len(cfg) + len(theirs)):]), flush=True)
+    # the split sweep of the decode step at hd 128, both cache types (the plan's default count is the first table's)
+    n, h, hkv, p, hd = DECODE_SHAPES[1]
+    lines.append(f"split sweep, decode attention (N {n}, H {h} / {hkv}, P {p}, hd {hd}) fp16, us (median of three medians of 20):")
+    for ln in (p - 1, p // 4):
+        cfg = [(n, h, hkv, p, hd, 1, "fp16", ln, dt, sv) for sv in SWEEP for dt in ("f32", "f16")]
+        got = child([me, "--attn", json.dumps(cfg)], f"split sweep at len {ln}")
+        for dt in ("f32", "f16"):
+            lines.append(f"  len {ln:5d}, {dt} cache: " + "   ".join(f"S {c[9]:2d}: {r['ms'] * 1e3:5.1f}" for c, r in zip(cfg, got) if c[8] == dt))
+    print("\n".join(lines[-5:]), flush=True)
+    open(os.path.join(out_dir, "half_attention.txt"), "w").write("\n".join(lines) + "\n")
+
+    lines = []
+    ms = lambda t: f"{t[0]:9.3f} ms (min {t[1]:.3f}, max {t[2]:.3f})"      # noqa: E731
+    with tempfile.TemporaryDirectory() as root:
+        path = models.write_repo(root, "llama_135m_decode", models.llama_135m(LLAMA["n"], seq=1, past=LLAMA["past"]))
+        lines.append(f"llama_135m decode step, batch {LLAMA['n']}, P {LLAMA['past']}, fp16, bound:")
+        for who, lib in (("parent build", parent), ("this build", None)):
+            for dt in ("f32", "f16"):
+                if (who == "parent build") and (not parent or dt == "f16"):
+                    continue
+                b = child([me, "--model", path, "fp16", "bound", dt], f"llama_135m on a {dt} cache, {who}", lib)
+                lines.append(f"  {who}, {dt} cache:  ModelInfer {ms(b['infer_ms'])}   graph replay {ms(b['replay_ms'])}   {b['attention']}")
+                print(lines[-1], flush=True)
+    open(os.path.join(out_dir, "llama_135m_half.txt"), "w").write("\n".join(lines) + "\n")
+
+
 def main():
     _setup()
     from gpu_ai_inference_server_amd.modelgen import models
     args = sys.argv[1:]
-    parent = None
-    if args and args[0] == "--parent-lib":
-        parent, args = os.path.abspath(args[1]), args[2:]
+    parent, dtype = None, "f32"
+    while args and args[0] in ("--parent-lib", "--cache-dtype"):
+        if args[0] == "--parent-lib":
+            parent = os.path.abspath(args[1])
+        else:
+            dtype = args[1]
+        args = args[2:]
+    if dtype == "f16":
+        return main_half(parent, args[0] if args else os.path.join(ROOT, "profiles", "decode_resident_half"))
+    if dtype != "f32":
+        sys.exit("--cache-dtype f32 or f16")
     out_dir = args[0] if args else os.path.join(ROOT, "profiles", "decode_resident")
     os.makedirs(out_dir, exist_ok=True)
     me = os.path.abspath(__file__)
@@ -209,7 +289,7 @@ def main():
 if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "--attn":
         attention_child(json.loads(sys.argv[2]))
-    elif len(sys.argv) == 5 and sys.argv[1] == "--model":
-        model_child(sys.argv[2], sys.argv[3], sys.argv[4] == "bound")
+    elif len(sys.argv) in (5, 6) and sys.argv[1] == "--model":
+        model_child(sys.argv[2], sys.argv[3], sys.argv[4] == "bound", *sys.argv[5:])
     else:
         main()
