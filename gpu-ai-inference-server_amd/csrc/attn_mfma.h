@@ -1,4 +1,4 @@
-// What the MFMA attention kernels share (included by kernels_attn.hip, kernels_wattn.hip, kernels_decode.hip and kernels_decode_h.hip only): the constants of the masked
+// What the MFMA attention kernels share (included by kernels_attn.hip, kernels_wattn.hip, kernels_decode.hip, kernels_decode_h.hip and kernels_extend_w.hip only): the constants of the masked
 // softmax, the rotary embedding of a 16-byte vector, and AttnWave, the state and the steps of one wave of 32 queries over key tiles of 32.
 //
 // Operand orientation.  The scores are computed swapped, S^T = K . Q^T: the MFMA's A operand is the K tile (row = key), its B operand

@@ -1,6 +1,6 @@
-// What the KV-cache kernel files share (included by kernels_decode.hip and kernels_decode_h.hip only): the block size, the addressing of a step's qkv
-// rows and rope tables, the clamped lengths of a resident cache, the key bias, and the launchers of the half-cache forms that kernels_decode.hip's
-// dispatch hands over to.
+// What the KV-cache kernel files share (included by kernels_decode.hip, kernels_decode_h.hip and kernels_extend_w.hip only): the block size, the
+// addressing of a step's qkv rows and rope tables, the clamped lengths of a resident cache, the key bias, and the launchers of the half-cache forms
+// and of the wide-head extend tile that kernels_decode.hip's dispatch hands over to.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,5 +60,9 @@ __device__ __forceinline__ float key_bias(const DecodeArgs& a, int64_t n, int j)
 // cache, and tile 4 of a decode step over one (the combine launch behind it where splits > 1 stays the caller's)
 hipError_t LaunchKvAppendRowsHalf(const DecodeArgs& a, hipStream_t stream);
 hipError_t LaunchDecodeHalf(const DecodeArgs& a, hipStream_t stream);
+// kernels_extend_w.hip, for an extend step at head_dim 128 that kernels_decode.hip has found eligible: tile 6 over `present` or the resident cache, fp32
+// or half (the append in front of it and the combine launch behind it stay the caller's), and its registration for more than 64 KiB of LDS
+hipError_t LaunchExtendWide(const DecodeArgs& a, hipStream_t stream);
+hipError_t InitKernelsExtendWide();
 
 }  // namespace ie

@@ -503,7 +503,7 @@ constexpr int DecodeDefaultSplits(int64_t n, int kv_heads, int64_t keys, int hd)
 // An extend step's tiles: 0 = the generic pair above; kAttnExtendTile (5) = a kv_append launch, then attention_extend_kernel<T, HD>: a workgroup = (image,
 // K / V head, block of 128 query rows, key split) over the fp32 `present`, the g Lq query rows of the group ordered (new token, head-in-group), K / V
 // staged through LDS in chunks of kAttnChunkKeys keys (converted to half in fp16 mode) with the chunk's key biases beside them, MFMA as in tiles 1 and
-// 3; splits > 1: attention_extend_combine_kernel adds the split records in a fixed order.  No other tile takes an extend step.  head_dim 32 or 64, a
+// 3; splits > 1: attention_extend_combine_kernel adds the split records in a fixed order.  Head_dim 128 has kAttnExtendWideTile (6) below.  head_dim 32 or 64, a
 // group of at most kDecodeMaxGroup heads, and DecodeFastFits' rule for the mask constant (a small one stays on tile 0)
 constexpr int kAttnExtendTile = 5;
 constexpr bool ExtendFastFits(int hd, int heads, int kv_heads, bool masked, float mask_value) {
@@ -528,7 +528,38 @@ constexpr int ExtendDefaultSplits(int64_t n, int kv_heads, int64_t rows, int64_t
 // the planner's default tile of an extend step: tile 5 from this many query rows g * Lq on, where it fits: the smallest measured count at which tile 5
 // beats the generic pair in both precisions
 constexpr int64_t kAttnExtendMinRows = 2;
-hipError_t InitKernelsDecode();          // once per process, before any capture: lets tile 5 take more than 64 KiB of LDS
+// An extend step at head_dim 128: 0 = the generic pair; kAttnExtendWideTile (6) = the same kv_append launch, then attention_extend_wide_kernel<T, 128, KW>
+// (kernels_extend_w.hip): tile 5's contract (row = i g + r, the key mask and the chunk's causal limit, the split records and the combine),
+// with a layout of its own: K / V staged in chunks of kAttnWideChunkKeys keys (tile 5's 256 would be 264 KiB of fp32 LDS), and the four waves of a
+// workgroup 4 / KW row waves by KW key waves: the 32-key tiles of a chunk are dealt to the key waves of a row wave round-robin and their partial
+// (m, l, O) meet in LDS at the end, so that the 12 to 64 query rows of a few drafted tokens over a group do not leave three waves of four idle.
+// KW follows from the rows g Lq of a K / V head: 4 up to 32 rows, 2 up to 64, else 1; a row block is 128 / KW rows.  Tiles 5 and 6 share no step
+constexpr int kAttnExtendWideTile = 6;
+constexpr int kAttnWideChunkKeys = 128;
+constexpr bool ExtendWideFits(int hd, int heads, int kv_heads, bool masked, float mask_value) {
+    return hd == 128 && masked && DecodeFastFits(hd, heads, kv_heads, masked, mask_value);
+}
+constexpr int ExtendWideKeyWaves(int64_t rows) { return rows <= 32 ? 4 : (rows <= 64 ? 2 : 1); }
+constexpr int ExtendWideRowBlock(int64_t rows) { return 128 / ExtendWideKeyWaves(rows); }
+// LDS of tile 6: one chunk of K and of V rows, every row padded by one 16-byte vector, and one bias per key of the chunk (fp32 135 680 bytes: one
+// workgroup per CU; fp16 70 144: two)
+constexpr int64_t ExtendWideLdsBytes(int hd, bool f16) { return 2 * int64_t(kAttnWideChunkKeys) * (int64_t(hd) * (f16 ? 2 : 4) + 16) + 4 * int64_t(kAttnWideChunkKeys); }
+static_assert(ExtendWideLdsBytes(128, false) == 135680 && ExtendWideLdsBytes(128, true) == 70144 && ExtendWideLdsBytes(128, false) <= kAttnLdsBudget &&
+                  2 * ExtendWideLdsBytes(128, true) <= kAttnLdsBudget, "tile 6's chunk fits the LDS budget, twice in fp16");
+// the planner's split count of tile 6: ExtendDefaultSplits' rule with the row block of the KW that `rows` selects (no rule of its own yet: DESIGN 3.37 has the sweep)
+constexpr int ExtendWideDefaultSplits(int64_t n, int kv_heads, int64_t rows, int64_t keys) {
+    const int64_t rb = ExtendWideRowBlock(rows), groups = n * kv_heads * ((rows + rb - 1) / rb), want = (256 + groups - 1) / groups;
+    const int64_t tiles = (keys + 31) / 32, by_keys = keys / kDecodeMinSplitKeys;
+    int64_t s = want;
+    if (s > by_keys) s = by_keys;
+    if (s > tiles) s = tiles;
+    if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
+    return s < 1 ? 1 : int(s);
+}
+// the planner's default tile of an extend step at head_dim 128: tile 6 from this many keys P + Lq on, where it fits.  Chosen as kAttnStreamCausalMinTokens
+// was: the smallest measured length at which tile 6 beats the generic pair in both precisions, never below one 32-key tile
+constexpr int64_t kAttnExtendWideMinKeys = 32;
+hipError_t InitKernelsDecode();          // once per process, before any capture: lets tiles 5 and 6 take more than 64 KiB of LDS
 bool KvAppendEligible(const DecodeArgs& a);
 hipError_t LaunchKvAppend(const DecodeArgs& a, hipStream_t stream);
 bool AttentionDecodeEligible(const DecodeArgs& a, int tile);

@@ -17,6 +17,7 @@
 //   attention_extend_kernel<T, HD>       tile 5 of an extend step, behind the kv_append launch: a workgroup = (image, K / V head, 128 query rows of the head
 //                                        group, key split) stages `present` through LDS in chunks and runs tile 1's MFMA softmax with the key mask and the
 //                                        chunk's causal limit (described at the kernel); S > 1: attention_extend_combine_kernel<T> adds the split records.
+//                                        Head dim 128 is tile 6, attention_extend_wide_kernel in kernels_extend_w.hip, between the same append and combine.
 //   attention_decode_kernel<T, HD, G>    tile 4: a workgroup = (image, K / V head, key split s of S), four waves.  A key row is HD / 4 lanes of 16 bytes, so a
 //                                        wave takes 256 / HD keys and the workgroup DecodeKeyTile(HD) keys per iteration, contiguous in the cache.  The lane
 //                                        that loads a K / V vector stores it into `present` (the Concat costs no pass of its own), multiplies it with the
@@ -770,12 +771,14 @@ bool AttentionDecodeEligible(const DecodeArgs& a, int tile) {
     if (!cache_ok(a) || !a.out.p || a.out.f8 || a.in.f16 != a.out.f16 || a.past_len < 1 || a.head_dim > kDecodeMaxHeadDim) return false;
     if (int64_t(a.out.c) != int64_t(a.heads) * a.head_dim || (a.new_len > 1 && a.out.w != a.new_len)) return false;
     if (tile == 0) return true;
-    if (a.new_len > 1) {                           // an extend step: tile 5 alone
-        if (tile != kAttnExtendTile || !ExtendFastFits(a.head_dim, a.heads, a.kv_heads, a.mask != nullptr, a.mask_value)) return false;
+    if (a.new_len > 1) {                           // an extend step: tile 5 (head_dim 32, 64) or tile 6 (128), with the same checks
+        const bool wide = tile == kAttnExtendWideTile;
+        if (wide ? !ExtendWideFits(a.head_dim, a.heads, a.kv_heads, a.mask != nullptr, a.mask_value)
+                 : (tile != kAttnExtendTile || !ExtendFastFits(a.head_dim, a.heads, a.kv_heads, a.mask != nullptr, a.mask_value))) return false;
         const int V = a.in.f16 ? 8 : 4;
         if (!VecViewOk(a.in, V) || !VecViewOk(a.out, V) || !Aligned16(a.present_k) || !Aligned16(a.present_v) || (a.rope_cos && (!Aligned16(a.rope_cos) || !Aligned16(a.rope_sin)))) return false;
-        const int64_t rows = int64_t(a.heads / a.kv_heads) * a.new_len, tiles = (int64_t(a.past_len) + a.new_len + 31) / 32;
-        if (a.splits < 1 || a.splits > kDecodeMaxSplits || a.splits > tiles || (rows + 127) / 128 * a.splits >= (int64_t(1) << 31) || a.kv_heads > 65535 || a.in.n > 65535) return false;
+        const int64_t rows = int64_t(a.heads / a.kv_heads) * a.new_len, tiles = (int64_t(a.past_len) + a.new_len + 31) / 32, rblock = wide ? ExtendWideRowBlock(rows) : 128;
+        if (a.splits < 1 || a.splits > kDecodeMaxSplits || a.splits > tiles || (rows + rblock - 1) / rblock * a.splits >= (int64_t(1) << 31) || a.kv_heads > 65535 || a.in.n > 65535) return false;
         if (int64_t(a.in.n) * a.heads * a.new_len * a.head_dim / kDecodeBlock >= (int64_t(1) << 31) || !KvAppendEligible(a)) return false;
         return a.splits == 1 || (a.workspace && ExtendWorkspaceFloats(a.in.n, a.heads, a.head_dim, a.splits, a.new_len) <= a.workspace_floats);
     }
@@ -818,6 +821,15 @@ hipError_t LaunchAttentionDecode(const DecodeArgs& a, int tile, hipStream_t stre
         if (a.in.f16) return a.head_dim == 32 ? launch_extend<_Float16, 32>(a, stream) : launch_extend<_Float16, 64>(a, stream);
         return a.head_dim == 32 ? launch_extend<float, 32>(a, stream) : launch_extend<float, 64>(a, stream);
     }
+    if (tile == kAttnExtendWideTile) {             // tile 6 (kernels_extend_w.hip) between tile 5's append and tile 5's combine
+        if (const hipError_t e = LaunchKvAppend(a, stream); e != hipSuccess) return e;
+        if (const hipError_t e = LaunchExtendWide(a, stream); e != hipSuccess || a.splits == 1) return e;
+        const int64_t total = int64_t(a.in.n) * a.heads * a.new_len * a.head_dim;
+        const dim3 grid(unsigned((total + kDecodeBlock - 1) / kDecodeBlock));
+        if (a.in.f16) hipLaunchKernelGGL((attention_extend_combine_kernel<_Float16>), grid, dim3(kDecodeBlock), 0, stream, a, total);
+        else hipLaunchKernelGGL((attention_extend_combine_kernel<float>), grid, dim3(kDecodeBlock), 0, stream, a, total);
+        return hipGetLastError();
+    }
     return a.in.f16 ? launch_decode<_Float16>(a, stream) : launch_decode<float>(a, stream);
 }
 
@@ -831,7 +843,7 @@ hipError_t InitKernelsDecode() {
     };
     for (const void* k : kernels)
         if (const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(kAttnLdsBudget)); e != hipSuccess) return e;
-    return hipSuccess;
+    return InitKernelsExtendWide();                // tile 6's forms, at the same moment
 }
 
 }  // namespace ie

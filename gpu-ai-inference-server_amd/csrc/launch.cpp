@@ -739,11 +739,13 @@ std::string kernel_label(const Step& s) {
             if (s.past_len > 0 && s.inplace) {     // a step bound to a resident cache: the in-place forms
                 const std::string t = s.out.f16 ? "f16" : "f32", in = s.kv_f16 ? ",inplace,kv16>" : ",inplace>";      // (kv16: the forms over a half cache)
                 if (s.tile == kAttnExtendTile) return "kv_append_rows_kernel + attention_extend_kernel<" + t + "," + std::to_string(s.head_dim) + in + (s.splits > 1 ? " + attention_extend_combine_kernel" : "");
+                if (s.tile == kAttnExtendWideTile) return "kv_append_rows_kernel + attention_extend_wide_kernel<" + t + "," + std::to_string(s.head_dim) + in + (s.splits > 1 ? " + attention_extend_combine_kernel" : "");
                 if (s.tile == kAttnDecodeTile) return "attention_decode_kernel<" + t + "," + std::to_string(s.head_dim) + in + (s.splits > 1 ? " + attention_decode_combine_kernel" : "");
                 return std::string(s.parts.empty() ? "" : "kv_append_rows_kernel + ") + "attention_inplace_generic_kernel<" + t + (s.kv_f16 ? ",kv16>" : ">");
             }
             if (s.past_len > 0) {
                 if (s.tile == kAttnExtendTile) return std::string("kv_append_kernel + attention_extend_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">" + (s.splits > 1 ? " + attention_extend_combine_kernel" : "");
+                if (s.tile == kAttnExtendWideTile) return std::string("kv_append_kernel + attention_extend_wide_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">" + (s.splits > 1 ? " + attention_extend_combine_kernel" : "");
                 if (s.tile == kAttnDecodeTile) return std::string("attention_decode_kernel<") + (s.out.f16 ? "f16," : "f32,") + std::to_string(s.head_dim) + ">" + (s.splits > 1 ? " + attention_decode_combine_kernel" : "");
                 return std::string(s.parts.empty() ? "" : "kv_append_kernel + ") + (s.in.w > 1 ? "attention_extend_generic_kernel<" : "attention_decode_generic_kernel<") + (s.out.f16 ? "f16>" : "f32>");
             }

@@ -2738,13 +2738,26 @@ void Planner::EmitAttention(const LNode& n, Step& s) {
         if (n.chunk_causal) {
             // an extend step: in.w = Lq >= 2 new tokens, token i over the past_len + i + 1 rows of `present` it may see.  Tile 5 where kernels.h
             // ExtendFastFits says so and there are at least kAttnExtendMinRows query rows per K / V head, else the parts; IE_ATTN_TILE = 0 | 5 pins it (an
-            // ineligible 5 is the parts), IE_ATTN_SPLITS the key splits of tile 5 (at most one 32-key tile per split).  No other tile takes it
+            // ineligible 5 is the parts), IE_ATTN_SPLITS the key splits of tile 5 (at most one 32-key tile per split).  Tile 6 takes head dim 128 (below)
             s.chunk_causal = true;
             const int64_t rows = int64_t(s.heads / s.kv_heads) * s.in.w, keys = int64_t(n.past_len) + s.in.w;
             const bool fits = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 && ExtendFastFits(s.head_dim, s.heads, s.kv_heads, n.key_mask, n.mask_value);
             s.tile = fits && rows >= kAttnExtendMinRows ? kAttnExtendTile : 0;
             if (const char* e = env.get("IE_ATTN_TILE"); e && (std::atoi(e) == 0 || std::atoi(e) == kAttnExtendTile)) s.tile = std::atoi(e) == kAttnExtendTile && fits ? kAttnExtendTile : 0;
+            // head dim 128: tile 6 where ExtendWideFits says so (the views are tile 5's) and the step has at least kAttnExtendWideMinKeys keys P + Lq;
+            // IE_ATTN_TILE = 6 pins it at any length, 0 the parts; 5 stays the parts here as 6 is no pin on a step it does not fit
+            const bool wide = !s.in.nchw && !s.out.nchw && s.in.f16 == s.out.f16 && ExtendWideFits(s.head_dim, s.heads, s.kv_heads, n.key_mask, n.mask_value);
+            if (wide) {
+                s.tile = keys >= kAttnExtendWideMinKeys ? kAttnExtendWideTile : 0;
+                if (const char* e = env.get("IE_ATTN_TILE"); e && (std::atoi(e) == 0 || std::atoi(e) == kAttnExtendTile || std::atoi(e) == kAttnExtendWideTile))
+                    s.tile = std::atoi(e) == kAttnExtendWideTile ? kAttnExtendWideTile : 0;
+            }
             if (ForcedTile(kNumAttnForcedTiles) >= 0) s.tile = 0;
+            if (s.tile == kAttnExtendWideTile) {
+                s.splits = ExtendWideDefaultSplits(s.in.n, s.kv_heads, rows, keys);
+                if (const int f = env.integer("IE_ATTN_SPLITS", 0); f >= 1) s.splits = int(std::min<int64_t>(std::min(f, kDecodeMaxSplits), (keys + 31) / 32));
+                plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, ExtendWorkspaceFloats(s.in.n, s.heads, s.head_dim, s.splits, s.in.w));
+            }
             if (s.tile == kAttnExtendTile) {
                 s.splits = ExtendDefaultSplits(s.in.n, s.kv_heads, rows, keys);
                 if (const int f = env.integer("IE_ATTN_SPLITS", 0); f >= 1) s.splits = int(std::min<int64_t>(std::min(f, kDecodeMaxSplits), (keys + 31) / 32));

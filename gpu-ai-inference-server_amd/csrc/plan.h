@@ -160,7 +160,8 @@ struct Step {
     // j <= past_len + i of present_k / present_v (causal inside the chunk by chunk index), q rotated at its own table row; in2 = the key mask
     // [N, past_len + Lq], pos = the INT64 positions [N, Lq], one id per token (KvAppend rotates k at the same rows).  The graph's mask constant was
     // checked element by element at load and is not kept.  Tile 0 runs the parts (kv_append_kernel, attention_extend_generic_kernel), tile 5 the
-    // kv_append launch and attention_extend_kernel over `splits` key splits per (image, K / V head, block of 128 query rows), plus the combine
+    // kv_append launch and attention_extend_kernel over `splits` key splits per (image, K / V head, block of 128 query rows), plus the combine; tile 6
+    // (head dim 128) the same with attention_extend_wide_kernel and blocks of 128, 64 or 32 query rows (kernels.h ExtendWideRowBlock)
     View past_k, past_v, present_k, present_v, pos;
     // Set by the executor on the instances of a model bound to a resident cache, never by the planner (the plan and its JSON do not know of it): the step
     // runs in place on layer kv_layer of the cache (kernels.h DecodeArgs::cache_rows)

@@ -2,6 +2,7 @@
 """An extend step (a past of P rows and Lq >= 2 new tokens) of a Llama-class model on one MI355X: what DESIGN 3.33 records.
 
     python scripts/extend_profile.py [out_dir]      writes <out_dir>/extend_attention.txt and <out_dir>/llama_135m_extend.txt (default profiles/extend)
+    python scripts/extend_profile.py --wide [out_dir]      the head dim 128 shapes of DESIGN 3.37: <out_dir>/extend_wide_attention.txt (default profiles/extend_wide)
 
 * the extend attention step alone (tests/extend_graphs.extend_attn_graph: rope at run-time positions, the chunk mask, every cache row valid) at
   (N, H / Hkv, P, hd) = (8, 9 / 3, 1 023, 64) for Lq = 4, 16, 128, 512 and at (1, 9 / 3, 4 095, 64) for Lq = 8, fp32 and fp16: tile 5 (the kv_append
@@ -74,8 +75,9 @@ def attention_child(configs):
                     for d, v in zip(din, feeds.values()):
                         B.CopyToDevice(m, d, v)
                     B.RunPrepared(m, 3, True)
-                    (p,) = [p for p in B.Profile(m, 20) if "attention_extend" in p["kernel"]]
-                    return {"kernel": p["kernel"], "ms": p["ms"], "tile": at["tile"], "splits": at.get("splits", 0)}
+                    ps = [[p for p in B.Profile(m, 20) if "attention_extend" in p["kernel"]][0] for _ in range(3)]      # three medians of 20: ms the middle one, lo / hi the others
+                    ms = sorted(p["ms"] for p in ps)
+                    return {"kernel": ps[0]["kernel"], "ms": ms[1], "lo": ms[0], "hi": ms[2], "tile": at["tile"], "splits": at.get("splits", 0)}
                 finally:
                     m.Destroy()
             out.append(with_env(dict(IE_PRECISION=prec, IE_AUTOTUNE="0", **env), go))
@@ -180,8 +182,44 @@ def main():
     open(os.path.join(out_dir, "llama_135m_extend.txt"), "w").write("\n".join(lines) + "\n")
 
 
+WIDE_SHAPES = ((8, 24, 8, 1023, 128, 4), (8, 24, 8, 1023, 128, 16), (8, 24, 8, 1023, 128, 128), (8, 24, 8, 1023, 128, 512), (1, 32, 8, 4095, 128, 8))
+
+
+def wide_main(out_dir):
+    """head dim 128: tile 6 under the planner's split count against the generic pair (IE_ATTN_TILE=0, what ran there before tile 6) and
+    torch's SDPA, the IE_ATTN_SPLITS sweep, and the short steps behind kernels.h kAttnExtendWideMinKeys.  A time is the middle of three medians of 20
+    HIP-event timings, its spread the other two; both routes of a shape run in one child process"""
+    os.makedirs(out_dir, exist_ok=True)
+    me = os.path.abspath(__file__)
+    us = lambda r: f"{r['ms'] * 1e3:9.1f} us [{r['lo'] * 1e3:.1f} .. {r['hi'] * 1e3:.1f}]"  # noqa: E731
+    lines = []
+    for n, h, hkv, past, hd, lq in WIDE_SHAPES:
+        for prec in ("fp32", "fp16"):
+            what = f"extend attention (N {n}, H {h} / {hkv}, P {past}, Lq {lq}, hd {hd}) {prec}"
+            cfg = [(n, h, hkv, past, hd, lq, prec, {}), (n, h, hkv, past, hd, lq, prec, {"IE_ATTN_TILE": "0"})] + [(n, h, hkv, past, hd, lq, prec, {"IE_ATTN_SPLITS": str(s)}) for s in (1, 2, 4, 8, 16, 32)]
+            res = child([me, "--attn", json.dumps(cfg)], what)
+            sdpa = child(["-c", TORCH_SDPA, json.dumps([n, h, hkv, past, lq, hd, prec])], f"torch SDPA for {what}")
+            d, t0 = res[0], res[1]
+            lines += [f"{what}:", f"  tile {d['tile']}, S = {d['splits']} (the planner's): {us(d)}   [{d['kernel']}]",
+                      f"  tile 0, the generic pair:         {us(t0)} ({t0['ms'] / d['ms']:.2f} x; apart by more than both spreads: {t0['lo'] > d['hi']})   [{t0['kernel']}]",
+                      f"  torch SDPA, boolean mask, K / V expanded, no append, no rotation: {sdpa['ms'] * 1e3:9.1f} us ({sdpa['ms'] / d['ms']:.2f} x)",
+                      "  IE_ATTN_SPLITS sweep: " + ", ".join(f"S {r['splits']}: {r['ms'] * 1e3:.1f} us" for r in res[2:])]
+            print("\n".join(lines[-5:]), flush=True)
+    lines.append("tile 6 (pinned, the planner's S) against the generic pair at few keys P + Lq, (N 8, H 24 / 8, Lq 4, hd 128): the table behind kAttnExtendWideMinKeys")
+    for prec in ("fp32", "fp16"):
+        keys = (8, 16, 32, 64, 128)
+        res = child([me, "--attn", json.dumps([(8, 24, 8, k - 4, 128, 4, prec, {"IE_ATTN_TILE": t}) for k in keys for t in ("6", "0")])], f"threshold sweep {prec}")
+        for i, k in enumerate(keys):
+            a, b = res[2 * i], res[2 * i + 1]
+            lines.append(f"  {prec} P + Lq {k:3d}: tile {a['tile']} (S {a['splits']}) {us(a)}, generic pair {us(b)} ({b['ms'] / a['ms']:.2f} x)")
+    print("\n".join(lines[-11:]), flush=True)
+    open(os.path.join(out_dir, "extend_wide_attention.txt"), "w").write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) == 3 and sys.argv[1] == "--attn":
+    if len(sys.argv) >= 2 and sys.argv[1] == "--wide":
+        wide_main(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "extend_wide"))
+    elif len(sys.argv) == 3 and sys.argv[1] == "--attn":
         attention_child(json.loads(sys.argv[2]))
     elif len(sys.argv) == 12 and sys.argv[1] == "--model":
         model_child(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), sys.argv[6], sys.argv[7], *(int(v) for v in sys.argv[8:12]))
