@@ -14,6 +14,7 @@ void check(hipError_t e, const char* what);
 TensorArg make_arg(const PlanInstance& pi, const View& v);
 LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 GnArgs MakeGnArgs(const PlanInstance& pi, const Step& s, const float* weights);
+QLinearArgs MakeQLinearArgs(const PlanInstance& pi, const Step& s, const float* weights);
 EmbedArgs MakeEmbedArgs(const PlanInstance& pi, const Step& s, const float* weights);
 AttnArgs MakeAttnArgs(const PlanInstance& pi, const Step& s, const float* weights);
 DecodeArgs MakeDecodeArgs(const PlanInstance& pi, const Step& s, const float* weights);
@@ -70,6 +71,7 @@ bool DeviceModel::TiledFamily(const PlanInstance& pi, const Step& s, F&& f) cons
     switch (s.kind) {
         case StepKind::LayerNorm: f(MakeLnArgs(pi, s, wb), LayerNormEligible, LaunchLayerNorm, TiledNames{"layer_norm", "layer-norm"}); return true;
         case StepKind::GroupNorm: f(MakeGnArgs(pi, s, wb), GroupNormEligible, LaunchGroupNorm, TiledNames{"group_norm", "group-norm"}); return true;
+        case StepKind::QLinear: f(MakeQLinearArgs(pi, s, wb), QLinearEligible, LaunchQLinear, TiledNames{"qlinear", "4-bit Linear"}); return true;
         case StepKind::Embed: f(MakeEmbedArgs(pi, s, wb), EmbedEligible, LaunchEmbed, TiledNames{"embed", nullptr}); return true;
         case StepKind::Attention:
             // a decode step (a past): its own two tiles, 0 = the generic kernel over `present` and kAttnDecodeTile; the step that carries the parts runs them at tile 0

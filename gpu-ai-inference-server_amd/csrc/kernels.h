@@ -245,6 +245,28 @@ constexpr int LnDefaultTile(int64_t c, bool f16) {
 bool LayerNormEligible(const LnArgs& a, int tile);
 hipError_t LaunchLayerNorm(const LnArgs& a, int tile, hipStream_t stream);
 
+// 4-bit weight-only Linear (kernels_qlinear.hip; com.microsoft MatMulNBits): for every pixel row m of `in` [.., K] and output column n
+//   out[m, n] = sum_k in[m, k] * (q[n, k] - z[n, k / block]) * s[n, k / block] + bias[n] + res[m, n]
+// codes: [N][K / 2] bytes, element 2i of a row in the LOW nibble of byte i; scales: fp32 [N][K / block]; zps: [N][ceil(K / block / 2)] bytes packed the
+// same way, or null (every zero point 8); bias fp32 [N] or null; res has the output's shape or a null p.  No atomics: every sum runs in a fixed order.
+struct QLinearArgs {
+    TensorArg in, out, res;
+    const uint8_t* codes = nullptr;
+    const float* scales = nullptr;
+    const uint8_t* zps = nullptr;
+    const float* bias = nullptr;
+    int block = 32;                    // 32 | 64 | 128, K % block == 0
+};
+// tile 0: qlinear_generic_kernel (any view, float or half activations, fp32 FMAs); tile 1: qlinear_mfma_kernel (half activations and result, N % 16 == 0,
+// rows one pitch apart, 16-byte aligned operands)
+constexpr int kNumQLinearTiles = 2;
+bool QLinearEligible(const QLinearArgs& a, int tile);
+hipError_t LaunchQLinear(const QLinearArgs& a, int tile, hipStream_t stream);
+// what tile 1 asks of a step's shapes alone (the planner's default; the launcher re-checks pointers and alignment)
+constexpr bool QLinearMfmaFits(bool in16, bool out16, bool res16, int64_t k, int64_t n, int64_t in_pitch, int64_t in_off, int64_t out_pitch, int64_t out_off, int64_t res_pitch, int64_t res_off) {
+    return in16 && out16 && res16 && k % 32 == 0 && n % 16 == 0 && in_pitch % 8 == 0 && in_off % 8 == 0 && out_pitch % 8 == 0 && out_off % 8 == 0 && res_pitch % 8 == 0 && res_off % 8 == 0;
+}
+
 // GroupNormalization of an NHWC view (kernels_gn.hip): for image n and group g = c / (C / groups), over the C / groups channels of the group and every pixel,
 //   out[n, p, c] = act((in[n, p, c] - mean_ng) * rsqrt(var_ng + eps) * gamma[c] + beta[c]),  var_ng the mean of the centred squares.
 // fp32 statistics in both element types; gamma / beta fp32; no atomics, every combine in a fixed order.  out may alias in.

@@ -46,6 +46,19 @@ LnArgs MakeLnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     return a;
 }
 
+QLinearArgs MakeQLinearArgs(const PlanInstance& pi, const Step& s, const float* weights) {
+    QLinearArgs a;
+    a.in = make_arg(pi, s.in);
+    a.out = make_arg(pi, s.out);
+    if (s.has_in2) a.res = make_arg(pi, s.in2);
+    a.codes = s.w_off >= 0 ? reinterpret_cast<const uint8_t*>(weights + s.w_off) : nullptr;
+    a.scales = s.w2_off >= 0 ? weights + s.w2_off : nullptr;
+    a.zps = s.q_zp_off >= 0 ? reinterpret_cast<const uint8_t*>(weights + s.q_zp_off) : nullptr;
+    a.bias = s.bias_off >= 0 ? weights + s.bias_off : nullptr;
+    a.block = s.q_block;
+    return a;
+}
+
 GnArgs MakeGnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     GnArgs a;
     a.in = make_arg(pi, s.in);
@@ -671,7 +684,7 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             check(LaunchTokenAssemble(a, stream_), "token_assemble");
             break;
         }
-        case StepKind::LayerNorm: case StepKind::GroupNorm: case StepKind::Embed: case StepKind::Attention: case StepKind::WindowAttention:
+        case StepKind::LayerNorm: case StepKind::GroupNorm: case StepKind::Embed: case StepKind::Attention: case StepKind::WindowAttention: case StepKind::QLinear:
             break;      // (launched through TiledFamily above)
         case StepKind::KvAppend: {
             if (s.in.f8) throw std::runtime_error("internal error: fp8 tensor reached the kv_append kernel");
@@ -760,6 +773,10 @@ std::string kernel_label(const Step& s) {
         case StepKind::PatchMerge: {
             const bool vec = !s.in.nchw && !s.out.nchw && PatchMergeVec(s.in.f16, s.out.f16, s.in.c, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off);
             return std::string("patch_merge_kernel<") + (vec ? (s.out.f16 ? "f16,8>" : "f32,4>") : (s.out.f16 ? "f16,1>" : "f32,1>"));
+        }
+        case StepKind::QLinear: {
+            const std::string form = "b" + std::to_string(s.q_block) + (s.q_zp_off >= 0 ? ",zp>" : ",sym>");
+            return s.tile == 0 ? std::string("qlinear_generic_kernel<") + (s.in.f16 ? "f16," : "f32,") + form : "qlinear_mfma_kernel<" + form;
         }
         case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }

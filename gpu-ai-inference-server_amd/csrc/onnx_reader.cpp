@@ -138,6 +138,10 @@ OnnxTensor parse_tensor(Reader r) {
             if (has_raw) { need(raw.end - raw.p, 1); for (int64_t k = 0; k < n; ++k) t.i[k] = raw.p[k] != 0; }
             else { need(i32.size(), 1); for (int64_t k = 0; k < n; ++k) t.i[k] = i32[k] != 0; }
             break;
+        case ONNX_UINT8:     // kept as bytes: the packed codes / zero points of a MatMulNBits (ParseOnnx refuses one that no such node reads)
+            if (has_raw) { need(raw.end - raw.p, 1); t.u8.assign(raw.p, raw.end); }
+            else { need(i32.size(), 1); t.u8.resize(n); for (int64_t k = 0; k < n; ++k) t.u8[k] = uint8_t(i32[k]); }
+            break;
         default:
             throw std::runtime_error("ONNX initializer " + t.name + ": unsupported data type " + std::to_string(t.dtype));
     }
@@ -259,6 +263,14 @@ OnnxModel ParseOnnx(const uint8_t* data, size_t size) {
         } else r.skip(wire);
     }
     if (!have_graph) throw std::runtime_error("ONNX parse error: no graph in model");
+    // a UINT8 initializer is the B or zero_points operand of a MatMulNBits, or it is refused as before
+    for (const auto& kv : m.initializers) {
+        if (kv.second.dtype != ONNX_UINT8) continue;
+        bool read = false;
+        for (const OnnxNode& n : m.nodes)
+            if (n.op == "MatMulNBits") for (size_t k : {size_t(1), size_t(3)}) if (n.inputs.size() > k && n.inputs[k] == kv.first) read = true;
+        if (!read) throw std::runtime_error("ONNX initializer " + kv.first + ": unsupported data type " + std::to_string(int(ONNX_UINT8)));
+    }
     for (auto& vi : all_inputs)
         if (!m.initializers.count(vi.name)) m.inputs.push_back(vi);
     return m;

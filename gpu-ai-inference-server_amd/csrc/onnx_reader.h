@@ -21,6 +21,7 @@ struct OnnxTensor {
     std::vector<int64_t> dims;
     std::vector<float> f;      // FLOAT / DOUBLE / FLOAT16 payloads converted to float
     std::vector<int64_t> i;    // INT32 / INT64 payloads
+    std::vector<uint8_t> u8;   // UINT8 payloads as they are (the packed operands of a MatMulNBits)
     int64_t numel() const { int64_t n = 1; for (auto d : dims) n *= d; return n; }
 };
 

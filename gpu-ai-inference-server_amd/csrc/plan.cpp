@@ -4,6 +4,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <sstream>
 
@@ -562,6 +563,69 @@ void Planner::ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odi
     if (cl) { odims = {X.n, N, X.h, X.w}; cl_out = !tok; tok_out = tok; }
 }
 
+// com.microsoft MatMulNBits: a Linear whose weights are 4-bit codes with one fp32 scale (and zero point) per block of block_size k.  On a token view, a
+// channels-last view or an [N, K] value, like ImportGemm; the packed operands stay as the file holds them (kernels_qlinear.hip reads them in place)
+void Planner::ImportMatMulNBits(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    auto no = [&](const std::string& why) { fail("MatMulNBits " + n.name + ": " + why); };
+    auto given = [&](size_t k) { return on.inputs.size() > k && !on.inputs[k].empty(); };
+    if (on.inputs.size() < 3 || !act_input(on, 0)) no("needs an activation A and the initializers B and scales");
+    const int64_t K = on.attr_i("K", 0), N = on.attr_i("N", 0), bits = on.attr_i("bits", 0), bs = on.attr_i("block_size", 0);
+    if (bits != 4) no("bits = " + std::to_string(bits) + " is not supported (only 4-bit codes)");
+    if (bs != 32 && bs != 64 && bs != 128) no("block_size = " + std::to_string(bs) + " is not supported (32, 64 or 128)");
+    if (K < 1 || N < 1 || K % bs) no("K = " + std::to_string(K) + " is not a positive multiple of block_size = " + std::to_string(bs) + " (N = " + std::to_string(N) + ")");
+    if (given(4)) no("g_idx is not supported");
+    const int64_t nblk = K / bs;
+    const OnnxTensor *b = L.init(on.inputs[1]), *sc = L.init(on.inputs[2]);
+    if (!b || b->dtype != ONNX_UINT8 || int64_t(b->u8.size()) != N * K / 2) no("B must be a UINT8 initializer [N, K / block_size, block_size / 2] of " + std::to_string(N * K / 2) + " bytes");
+    if (!sc || sc->dtype != ONNX_FLOAT) no("scales must be a float32 initializer (fp16-typed scales are not supported)");
+    if (int64_t(sc->f.size()) != N * nblk) no("scales must hold N * K / block_size = " + std::to_string(N * nblk) + " elements");
+    if (given(3)) {
+        const OnnxTensor* zp = L.init(on.inputs[3]);
+        if (!zp || zp->dtype != ONNX_UINT8) no("zero_points must be a packed UINT8 initializer (or absent)");
+        if (int64_t(zp->u8.size()) != N * ((nblk + 1) / 2)) no("zero_points must hold N * ceil(K / block_size / 2) = " + std::to_string(N * ((nblk + 1) / 2)) + " bytes");
+        n.q_zps = zp->u8;
+    }
+    if (given(5)) {
+        const OnnxTensor* bi = L.init(on.inputs[5]);
+        if (!bi || bi->f.empty() || bi->numel() != N) no("bias must be a [N] float initializer");
+        n.bias = bi->f;
+    }
+    const int x = in_val(on, 0);
+    const Val& X = L.vals[x];
+    const bool tok = L.is_tok(on.inputs[0]);
+    const bool cl = L.is_cl(on.inputs[0]) || tok;
+    if (!cl && X.h * X.w != 1) no("input must be [N, K], a token view or a channels-last view");
+    if (K != X.c) no("inner dimensions do not match (K = " + std::to_string(K) + ", the input has " + std::to_string(X.c) + " columns)");
+    n.kind = L_QLINEAR;
+    n.q_codes = b->u8;
+    n.s = sc->f;
+    n.q_block = int(bs);
+    n.in = {x};
+    odims = {X.n, N};
+    if (X.dims.size() == 1) odims = {N};
+    if (cl) { odims = {X.n, N, X.h, X.w}; cl_out = !tok; tok_out = tok; }
+}
+
+// The residual Add behind a 4-bit Linear (o_proj, down_proj) folds into its epilogue under the rule of FuseConvEpilogues: the other operand exists when
+// the Linear runs.  Nothing else folds into such a node
+void Planner::FuseQLinearResiduals() {
+    for (size_t i = 0; i < L.nodes.size(); ++i) {
+        LNode& q = L.nodes[i];
+        if (q.dead || q.kind != L_QLINEAR || q.res >= 0 || !single_consumer(q.out)) continue;
+        LNode& b = L.nodes[size_t(L.consumers(q.out)[0])];
+        if (b.kind != L_ADD) continue;
+        const int other = b.in[0] == q.out ? b.in[1] : b.in[0];
+        const int op = L.vals[other].producer;
+        if (other == q.out || L.vals[other].is_input || op < 0 || op >= int(i)) continue;
+        q.res = other;
+        q.in.push_back(other);
+        q.name += "+" + b.name;
+        q.out = b.out;
+        L.vals[q.out].producer = int(i);
+        b.dead = true;
+    }
+}
+
 void Planner::ImportBatchNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
     int x = in_val(on, 0);
     const Val& X = L.vals[x];
@@ -1054,13 +1118,13 @@ void Planner::ImportNode(const OnnxNode& on) {
     }
     // a channels-last view may feed only the ops that read it as one: anything else (a Shape and the other folded ops included, hence before
     // the folds) would take its n / c / h / w for the ONNX dims
-    static const std::set<std::string> cl_ops = {"LayerNormalization", "RMSNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose"};
+    static const std::set<std::string> cl_ops = {"LayerNormalization", "RMSNormalization", "MatMul", "MatMulNBits", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose"};
     for (const std::string& name : on.inputs)
         if (L.is_cl(name) && !cl_ops.count(op))
             fail(op + " " + n.name + ": input " + name + " is a channels-last view (a Transpose with perm [0,2,3,1]); only LayerNormalization, MatMul, Add, Mul, Div, Erf, "
                  "Gelu and Transpose may read one");
     // token views likewise, and the two half-way names of their creation and of the way back
-    static const std::set<std::string> tok_ops = {"LayerNormalization", "RMSNormalization", "MatMul", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose", "Concat", "Gather", "Reshape"};
+    static const std::set<std::string> tok_ops = {"LayerNormalization", "RMSNormalization", "MatMul", "MatMulNBits", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose", "Concat", "Gather", "Reshape"};
     for (const std::string& name : on.inputs) {
         // (a Conv1D's Gemm reads its token view like a MatMul; the Split of a GPT-2 attention is its head; a Pow is no operator of the planner at all, whatever it reads;
         // a Sigmoid on tokens is the SiLU of a Llama MLP's gate)
@@ -1083,6 +1147,7 @@ void Planner::ImportNode(const OnnxNode& on) {
     if (op == "Conv") ImportConv(on, n, odims);
     else if (op == "ConvTranspose") ImportConvTranspose(on, n, odims);
     else if (op == "MatMul" || op == "Gemm") ImportGemm(on, n, odims);
+    else if (op == "MatMulNBits") ImportMatMulNBits(on, n, odims);
     else if (op == "BatchNormalization") ImportBatchNorm(on, n, odims);
     else if (op == "LayerNormalization" || op == "RMSNormalization") ImportLayerNorm(on, n, odims);
     else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu" || op == "Erf" || op == "Gelu" || op == "Tanh") ImportActivation(on, n, odims);
@@ -1247,6 +1312,13 @@ void Planner::ImportAttention(const OnnxNode& on, const AttnMatch& am) {
         add.inputs = {mm.outputs[0], am.b_name};
         add.outputs = {am.name + "/qkv_out"};
         qkv = am.no_bias ? mm.outputs[0] : add.outputs[0];
+        if (am.nbits) {        // three 4-bit Linears: the merged node is a MatMulNBits over the concatenated rows
+            mm.op = "MatMulNBits";
+            mm.inputs = {am.x, am.w_name, am.q_scales};
+            if (!am.q_zps.empty()) mm.inputs.push_back(am.q_zps);
+            const char* const names[4] = {"K", "N", "bits", "block_size"};
+            for (int k = 0; k < 4; ++k) { OnnxAttr at; at.name = names[k]; at.i = am.q_attrs[size_t(k)]; mm.attrs[at.name] = at; }
+        }
         synth_nodes.push_back(std::move(mm));
         ImportNode(synth_nodes.back());
         if (!am.no_bias) {
@@ -1608,6 +1680,7 @@ void Planner::RefuseForF8() const {
         if (n.kind == L_LAYERNORM && n.rms) fail("RMSNormalization is not supported in fp8 mode (node " + n.name + ")");
         if (n.kind == L_LAYERNORM || n.kind == L_EMBED) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
         if (n.kind == L_GROUPNORM) fail("GroupNormalization is not supported in fp8 mode (node " + n.name + ")");
+        if (n.kind == L_QLINEAR) fail("MatMulNBits is not supported in fp8 mode (node " + n.name + ")");
     }
     for (const LNode& n : L.nodes)
         if (n.kind == L_ATTENTION || n.kind == L_TOKASM || n.kind == L_TOKPOS) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
@@ -2276,6 +2349,37 @@ int64_t Planner::push_vec(const std::vector<float>& v) {
     return off;
 }
 
+int64_t Planner::push_bytes(const std::vector<uint8_t>& v) {
+    while (plan.weights.size() % 8) plan.weights.push_back(0.f);
+    const int64_t off = int64_t(plan.weights.size());
+    plan.weights.resize(plan.weights.size() + (v.size() + 3) / 4, 0.f);
+    std::memcpy(plan.weights.data() + off, v.data(), v.size());
+    return off;
+}
+
+// A 4-bit Linear: the packed operands into the blob as they are; tile 1 (the MFMA kernel) where the step's views allow it, else the generic kernel.
+// IE_FORCE_TILE as for layer norm; IE_QLINEAR_TILE pins these steps alone (an ineligible 1 is the generic kernel)
+void Planner::EmitQLinear(const LNode& n, Step& s) {
+    if (s.in.f8 || s.out.f8) fail("MatMulNBits is not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::QLinear;
+    if (n.res >= 0) { s.in2 = view_of(n.res); s.has_in2 = true; }
+    s.q_block = n.q_block;
+    s.w_off = push_bytes(n.q_codes);
+    s.w2_off = push_vec(n.s);
+    if (!n.q_zps.empty()) s.q_zp_off = push_bytes(n.q_zps);
+    if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
+    const bool fits = !s.in.nchw && !s.out.nchw && !(s.has_in2 && s.in2.nchw) &&
+                      QLinearMfmaFits(s.in.f16, s.out.f16, !s.has_in2 || s.in2.f16, s.in.c, s.out.c, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off,
+                                      s.has_in2 ? s.in2.pitch : 0, s.has_in2 ? s.in2.c_off : 0);
+    s.tile = fits ? 1 : 0;
+    int t = ForcedTile(kNumQLinearTiles);
+    if (const char* e = env.get("IE_QLINEAR_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumQLinearTiles) t = std::atoi(e);
+    if (t >= 0) s.tile = t == 0 || fits ? t : 0;
+    const double rows = double(s.in.n) * double(s.in.h) * double(s.in.w);
+    s.flops = 2.0 * rows * double(s.in.c) * double(s.out.c);
+    s.bytes = vbytes(s.in) + vbytes(s.out) + (s.has_in2 ? vbytes(s.in2) : 0.0) + double(n.q_codes.size()) + 4.0 * double(n.s.size()) + double(n.q_zps.size()) + 4.0 * double(n.bias.size());
+}
+
 int Planner::src_of(const View& v) const {
     auto it = writer.find({int64_t(v.buf), v.c_off, v.c});
     return it == writer.end() ? -1 : it->second;
@@ -2897,6 +3001,7 @@ void Planner::EmitSteps() {
             case L_PATCHMERGE: EmitPatchMerge(n, s); break;
             case L_EMBED: EmitEmbed(n, s); break;
             case L_GROUPNORM: EmitGroupNorm(n, s); break;
+            case L_QLINEAR: EmitQLinear(n, s); break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -3263,6 +3368,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
     if (!env.get("IE_NO_SE_FUSE")) P.FuseSqueezeExcite();        // pool -> 1x1 -> act -> 1x1 -> act -> Mul as one node
     P.MergeAffineChains();                                       // fusion 1: Affine -> Affine
     P.FuseConvEpilogues();                                       // fusion 2: Conv -> Affine / ReLU / Add / Clip / activation
+    P.FuseQLinearResiduals();                                    // the residual Add behind a 4-bit Linear
     P.FuseRelu6IntoDepthwise();                                  // fusion 2b
     P.FuseActivationPrologues();                                 // fusion 2d
     if (!env.get("IE_NO_POOL_SWAP")) P.SwapConvAndAvgPool();     // fusion 2c: Conv1x1 -> AveragePool => AveragePool -> Conv1x1
@@ -3308,7 +3414,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed", "group_norm", "kv_append"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed", "group_norm", "kv_append", "qlinear"};
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
@@ -3395,6 +3501,10 @@ std::string PlanToJson(const Plan& p) {
             o << ",\"heads\":" << s.heads << ",\"head_dim\":" << s.head_dim << ",\"scale\":" << s.attn_scale << ",\"window\":[" << s.win_h << "," << s.win_w << "],\"shift\":["
               << s.shift_h << "," << s.shift_w << "],\"masked\":" << (s.masked ? "true" : "false") << ",\"tile\":" << s.tile;
         if (s.kind == StepKind::GroupNorm) o << ",\"groups\":" << s.gn_groups << ",\"eps\":" << s.ln_eps << ",\"tile\":" << s.tile;      // (group-norm steps only)
+        if (s.kind == StepKind::QLinear)      // (4-bit Linear steps only)
+            o << ",\"residual\":" << (s.has_in2 ? "true" : "false") << ",\"block_size\":" << s.q_block << ",\"scales_off\":" << s.w2_off << ",\"zero_points_off\":" << s.q_zp_off
+              << ",\"packed_bytes\":" << int64_t(s.out.c) * s.in.c / 2 + 4 * int64_t(s.out.c) * (s.in.c / s.q_block) + (s.q_zp_off >= 0 ? int64_t(s.out.c) * ((s.in.c / s.q_block + 1) / 2) : 0)
+              << ",\"tile\":" << s.tile;
         if (s.kind == StepKind::Embed) {      // (embed steps only)
             o << ",\"tables\":" << (s.w2_off >= 0 ? 2 : 1) << ",\"vocab\":[" << s.emb_vocab;
             if (s.w2_off >= 0) o << "," << s.emb_types;

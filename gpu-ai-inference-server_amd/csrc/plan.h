@@ -39,7 +39,7 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12, GroupNorm = 13, KvAppend = 14 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12, GroupNorm = 13, KvAppend = 14, QLinear = 15 };
 
 // Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
 enum class ResizeMode : int { Nearest = 0, Linear = 1 };
@@ -187,6 +187,12 @@ struct Step {
     // group g and every pixel of image n; w_off = gamma [C], bias_off = beta [C], fp32 in every precision; act = the fused SiLU / ReLU / Sigmoid; tile 0 =
     // the generic kernel, 1 = the statistics + apply launches, whose records live in the workspace (kernels.h GnWorkspaceFloats)
     int gn_groups = 0;
+    // QLinear (kernels_qlinear.hip): a 4-bit weight-only Linear (MatMulNBits) on the pixel rows of `in`, out[m, n] = sum_k in[m, k] (q[n, k] - z) s + bias[n]
+    // (+ in2, the folded residual Add).  The packed operands ride in the weight blob as raw bytes at float offsets: w_off = the codes [N][K / 2], w2_off =
+    // the fp32 scales [N][K / q_block], q_zp_off = the packed zero points [N][ceil(K / q_block / 2)] or -1 (every zero point 8), bias_off = the fp32 bias
+    // or -1.  No weight mirror and no dense-conv pass touches them.  tile 0 = the generic kernel, 1 = the MFMA kernel (fp16 precision)
+    int q_block = 0;
+    int64_t q_zp_off = -1;
     ConvAlgo algo = ConvAlgo::Naive;
     int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)

@@ -38,7 +38,7 @@ struct Val {
     int64_t sel_rows = 1, sel_idx = 0;
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED, L_GROUPNORM, L_KVAPPEND };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED, L_GROUPNORM, L_KVAPPEND, L_QLINEAR };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -83,6 +83,10 @@ struct LNode {
     int64_t emb_vocab = 0, emb_types = 0;
     // L_GROUPNORM: s / t = gamma / beta per channel (the inner InstanceNormalization's scale and bias folded in), eps, act = the fused activation
     int gn_groups = 0;
+    // L_QLINEAR (MatMulNBits): q_codes [N][K / 2] and q_zps [N][ceil(K / q_block / 2)] (empty: none) as the file packs them, s = the scales [N][K / q_block],
+    // bias [N] (empty: none), res = the folded residual Add
+    std::vector<uint8_t> q_codes, q_zps;
+    int q_block = 0;
     bool has_pre = false, pre_relu = false, relu = false;
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
@@ -270,6 +274,10 @@ struct Planner {
         // the separate q / k / v spelling (BERT): the token value the three Linears read and their merged weights [Din, 3 D] / bias [3 D] (derived initializers)
         bool split = false;
         std::string x, w_name, b_name;
+        // nbits: the three are MatMulNBits; w_name = the merged codes, q_scales / q_zps (empty: none) = the merged scales / zero points, q_attrs = K, N, bits, block_size
+        bool nbits = false;
+        std::string q_scales, q_zps;
+        std::vector<int64_t> q_attrs;
         // the key mask: the INT64 graph input behind the ext chain and its constant c
         std::string mask;
         float mask_value = 0.f;
@@ -460,6 +468,10 @@ struct Planner {
     void ImportConv(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportConvTranspose(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportGemm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void ImportMatMulNBits(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void FuseQLinearResiduals();
+    void EmitQLinear(const LNode& n, Step& s);
+    int64_t push_bytes(const std::vector<uint8_t>& v);   // raw bytes into the weight blob (32-byte aligned), the float offset
     void ImportBatchNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportActivation(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);

@@ -79,6 +79,8 @@ struct SplitAttention {
     // q's, k's and v's Reshape [N, L, H, hd], and behind a Reshape its Linear: the MatMul, the bias Add (or none), their constants
     const OnnxNode *rs[3] = {}, *mm[3] = {}, *add[3] = {};
     const OnnxTensor *W[3] = {}, *B[3] = {};
+    bool nbits = false;                    // the three Linears are MatMulNBits: W = their packed codes, QS / QZ = their scales / zero points (or none)
+    const OnnxTensor *QS[3] = {}, *QZ[3] = {};
     std::vector<int64_t> shape4;           // q's Reshape target
     int64_t kvh = 0;                       // K / V heads of the split form (k's and v's Reshape)
     struct Rope { bool on = false; std::vector<float> cos, sin; int64_t rows = 0, hd = 0; std::string name, pos; int tables = 0; };
@@ -344,6 +346,15 @@ struct SplitAttention {
                 mm[s] = gi.producer(add[s]->inputs[size_t(1 - bi)]);
                 if (!B[s] || B[s]->f.empty()) miss(std::string(which) + " is not the Reshape of a Linear (MatMul(x, W [Din, D]) + b [D])");
             } else mm[s] = top;
+            // a 4-bit Linear (MatMulNBits) stands where a bias-less MatMul does: all three or none, one block size and one zero-point form
+            if (mm[s] && mm[s]->op == "MatMulNBits") {
+                if (add[s]) miss("the " + std::string(which) + " Linear " + node_name(mm[s]) + " is a MatMulNBits with a bias Add behind it; only the bias-less form is merged");
+                if (s > 0 && !nbits) miss("the " + std::string(which) + " Linear " + node_name(mm[s]) + " is a MatMulNBits, the q Linear " + node_name(mm[0]) + " is not (all three or none)");
+                nbits = true;
+                MatchNBits(s, Ds);
+                continue;
+            }
+            if (s > 0 && nbits) miss("the q Linear " + node_name(mm[0]) + " is a MatMulNBits, the " + std::string(which) + " Linear " + (mm[s] ? node_name(mm[s]) : std::string("?")) + " is not (all three or none)");
             if (!mm[s] || mm[s]->op != "MatMul") miss(std::string(which) + " is not the Reshape of a Linear (MatMul + Add, or a MatMul alone)");
             W[s] = mm[s]->inputs.size() == 2 ? gi.cst(mm[s]->inputs[1]) : nullptr;
             if (!W[s] || gi.cst(mm[s]->inputs[0]) || W[s]->f.empty() || W[s]->dims.size() != 2)
@@ -360,10 +371,68 @@ struct SplitAttention {
         }
     }
 
+    // Linear s is a MatMulNBits of Ds columns: its packed operands as constants (ImportMatMulNBits checks the merged node's sizes and refuses the rest by
+    // name), the same input, block size and zero-point presence as q's, one reader
+    void MatchNBits(int s, int64_t Ds) {
+        const char* const which = kWhich[s];
+        const OnnxNode* p = mm[s];
+        const auto in = [&](size_t k) { return p->inputs.size() > k && !p->inputs[k].empty() ? gi.cst(p->inputs[k]) : nullptr; };
+        W[s] = in(1);
+        QS[s] = in(2);
+        QZ[s] = in(3);
+        if (p->inputs.size() < 3 || gi.cst(p->inputs[0]) || !W[s] || W[s]->dtype != ONNX_UINT8 || !QS[s] || QS[s]->dtype != ONNX_FLOAT)
+            miss("the " + std::string(which) + " Linear " + node_name(p) + " is not MatMulNBits(x, B UINT8, scales FLOAT[, zero_points]) with constant operands");
+        if ((p->inputs.size() > 3 && !p->inputs[3].empty() && (!QZ[s] || QZ[s]->dtype != ONNX_UINT8)) || p->inputs.size() > 4)
+            miss("the " + std::string(which) + " Linear " + node_name(p) + " has zero points that are no UINT8 constant, a g_idx or a bias; only MatMulNBits(x, B, scales[, zero_points]) is merged");
+        const int64_t K = p->attr_i("K", 0), N = p->attr_i("N", 0), bs = p->attr_i("block_size", 0);
+        if (p->inputs[0] != mm[0]->inputs[0])
+            miss("the " + std::string(which) + " Linear " + node_name(p) + " reads " + p->inputs[0] + ", the q Linear " + mm[0]->inputs[0] + " (q, k and v must come from the same tokens)");
+        if (N != Ds || K != mm[0]->attr_i("K", 0) || K < 1 || bs < 1 || K % bs || int64_t(W[s]->u8.size()) != N * K / 2 || int64_t(QS[s]->f.size()) != N * (K / bs) ||
+            (QZ[s] && int64_t(QZ[s]->u8.size()) != N * ((K / bs + 1) / 2)))
+            miss("the " + std::string(which) + " Linear " + node_name(p) + " is not [K = " + std::to_string(mm[0]->attr_i("K", 0)) + ", N = H * hd = " + std::to_string(Ds) + "] with operands of that size");
+        if (bs != mm[0]->attr_i("block_size", 0))
+            miss("the " + std::string(which) + " Linear " + node_name(p) + " has block_size " + std::to_string(bs) + ", the q Linear " + node_name(mm[0]) + " " + std::to_string(mm[0]->attr_i("block_size", 0)) + " (the merged qkv Linear has one)");
+        if ((QZ[s] != nullptr) != (QZ[0] != nullptr))
+            miss("the " + std::string(which) + " Linear " + node_name(p) + (QZ[s] ? " has" : " has no") + " zero points, the q Linear " + node_name(mm[0]) + (QZ[0] ? " has" : " has none") + " (the merged qkv Linear has them for every column or for none)");
+        for (const OnnxNode* r : {mm[s], rs[s]})
+            if (gi.nreaders(r->outputs[0]) != 1) miss("the " + std::string(which) + " Linear's " + r->op + " " + node_name(r) + " has " + std::to_string(gi.nreaders(r->outputs[0])) + " readers, not 1 (only its own attention may read it)");
+        taken.push_back(mm[s]);
+        taken.push_back(rs[s]);
+    }
+
+    // the 4-bit form of MergeLinears: the rows of the three packed operands one after the other (row n of B, scales and zero_points belongs to column n)
+    void MergeNBits() {
+        OnnxTensor b, sc, zp;
+        b.dtype = zp.dtype = ONNX_UINT8;
+        int64_t n_all = 0;
+        for (int s = 0; s < 3; ++s) {
+            b.u8.insert(b.u8.end(), W[s]->u8.begin(), W[s]->u8.end());
+            sc.f.insert(sc.f.end(), QS[s]->f.begin(), QS[s]->f.end());
+            if (QZ[s]) zp.u8.insert(zp.u8.end(), QZ[s]->u8.begin(), QZ[s]->u8.end());
+            n_all += mm[s]->attr_i("N", 0);
+        }
+        const int64_t K = mm[0]->attr_i("K", 0), bs = mm[0]->attr_i("block_size", 0);
+        b.dims = {n_all, K / bs, bs / 2};
+        sc.dims = {n_all, K / bs};
+        zp.dims = {n_all, (K / bs + 1) / 2};
+        for (const OnnxNode& on : P.m.nodes) if (&on == mm[0] || &on == mm[1] || &on == mm[2]) { head = &on; break; }
+        am.split = am.no_bias = am.nbits = true;
+        am.x = mm[0]->inputs[0];
+        am.name = node_name(mm[0]) + "+" + node_name(mm[1]) + "+" + node_name(mm[2]);
+        am.w_name = b.name = am.name + "/qkv_B";
+        am.q_scales = sc.name = am.name + "/qkv_scales";
+        if (QZ[0]) am.q_zps = zp.name = am.name + "/qkv_zero_points";
+        am.q_attrs = {K, n_all, mm[0]->attr_i("bits", 0), bs};
+        P.L.add_derived(std::move(b));
+        P.L.add_derived(std::move(sc));
+        if (QZ[0]) P.L.add_derived(std::move(zp));
+    }
+
     // The three Linears become ONE Linear x -> [N, L, D + 2 Dkv]: columns q (D) | k (Dkv) | v (Dkv), head h at h hd inside its part (weights and bias
     // concatenated, derived initializers), without a bias where none of the three has one.  The attention node then reads today's qkv layout.  The head is
     // the first of the three MatMuls in graph order (x is defined there)
     void MergeLinears() {
+        if (nbits) { MergeNBits(); return; }
         const int64_t Din = W[0]->dims[0], D = W[0]->dims[1], Dkv = W[1]->dims[1], Dall = D + 2 * Dkv;
         const int64_t off[3] = {0, D, D + Dkv};
         OnnxTensor w, b;

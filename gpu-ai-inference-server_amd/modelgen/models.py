@@ -28,6 +28,7 @@ class GraphBuilder:
         self.nodes: list[bytes] = []
         self.inits: list[bytes] = []
         self.n = 0
+        self.extra_opsets: list[tuple[str, int]] = []      # opset imports beside ai.onnx (a quantised Linear adds com.microsoft)
 
     def _uid(self, base: str) -> str:
         self.n += 1
@@ -292,13 +293,37 @@ class GraphBuilder:
         h = self.init(name + "_half", np.array(half, np.float32))
         return self.simple("Mul", [h, y] if swap else [y, h])
 
-    def linear(self, x: str, cin: int, cout: int, name: str | None = None, w_scale: float | None = None, bias: bool = True) -> str:
+    def linear(self, x: str, cin: int, cout: int, name: str | None = None, w_scale: float | None = None, bias: bool = True, quant: str | None = None,
+               q_block: int = 32, q_zero: bool = True, q_form: str = "nbits", q_codes=None) -> str:
         """torch's Linear on a [..., cin] tensor as the exporter writes it: MatMul with a [cin, cout] initializer, then Add [cout] (bias False: the
-        MatMul alone, as Llama's projections are)."""
+        MatMul alone, as Llama's projections are).
+        quant "int4": the weights quantised per block of q_block inputs of one output column to 4-bit codes q with a float32 scale s (q_zero: asymmetric
+        with a zero point z per block; else symmetric around 8).  q_form "nbits" writes com.microsoft MatMulNBits (B [cout, cin / q_block, q_block / 2]
+        UINT8, element 2i in the low nibble; scales; zero points packed the same way), "dense" the plain MatMul whose weight is the float32
+        dequantisation (q - z) * s of the SAME codes: the twin a float64 reference walks.  q_codes (tests): a function (name, cout, nblk, q_block) ->
+        (q uint8 [cout, nblk, q_block], z uint8 [cout, nblk], s float32 [cout, nblk]) that replaces the quantisation of the drawn weights."""
         name = name or self._uid("fc")
         std = w_scale if w_scale is not None else float(np.sqrt(1.0 / cin))
-        w = rng.gaussish(self.seed, name + "_w", cin * cout).reshape(cin, cout) * np.float32(std)
-        y = self.simple("MatMul", [x, self.init(name + "_w", w.astype(np.float32))])
+        w = None if quant is not None and q_codes else rng.gaussish(self.seed, name + "_w", cin * cout).reshape(cin, cout) * np.float32(std)
+        if quant is not None:
+            if quant != "int4" or q_form not in ("nbits", "dense"):
+                raise ValueError((quant, q_form))
+            q, z, s = q_codes(name, cout, cin // q_block, q_block) if q_codes else quantize_int4(w.astype(np.float32), q_block, q_zero)
+            if q_form == "dense":
+                wd = ((q.astype(np.float32) - z[:, :, None].astype(np.float32)) * s[:, :, None]).reshape(cout, cin)
+                y = self.simple("MatMul", [x, self.init(name + "_w", np.ascontiguousarray(wd.T))])
+            else:
+                ins = [x, self.init(name + "_B", pack_nibbles(q)), self.init(name + "_scales", s.reshape(-1))]
+                if q_zero:
+                    ins.append(self.init(name + "_zero_points", pack_nibbles(z)))
+                uid = self._uid("matmulnbits")
+                y = uid + "_out"
+                self.nodes.append(pb.node("MatMulNBits", ins, [y], uid, [pb.attr_int("K", cin), pb.attr_int("N", cout), pb.attr_int("bits", 4),
+                                                                         pb.attr_int("block_size", q_block)], domain="com.microsoft"))
+                if ("com.microsoft", 1) not in self.extra_opsets:
+                    self.extra_opsets.append(("com.microsoft", 1))
+        else:
+            y = self.simple("MatMul", [x, self.init(name + "_w", w.astype(np.float32))])
         if not bias:
             return y
         b = (rng.uniform(self.seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
@@ -398,7 +423,33 @@ class GraphBuilder:
         """inputs / outputs: (name, shape) or (name, shape, ONNX element type); FLOAT where it is not given"""
         g = pb.graph(self.name, self.nodes, self.inits,
                      [pb.value_info(*t) for t in inputs], [pb.value_info(*t) for t in outputs])
-        return pb.model(g, opset=opset)
+        return pb.model(g, opset=opset, extra_opsets=self.extra_opsets)
+
+
+def quantize_int4(w: np.ndarray, block: int, zero: bool) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """w [cin, cout] float32 -> codes q uint8 [cout, cin / block, block], zero points z uint8 [cout, cin / block], scales s float32 [cout, cin / block]
+    with w[k, n] ~ (q - z) * s per block of `block` consecutive k.  zero: asymmetric, s = (max - min) / 15 over the block's range extended to hold 0,
+    z = round(-min / s); else symmetric around 8, s = max |w| / 7 (the code 0 is then unused but by the block's extreme negative)"""
+    cin, cout = w.shape
+    if cin % block:
+        raise ValueError("cin must be a multiple of the block")
+    b = np.ascontiguousarray(w.T).reshape(cout, cin // block, block).astype(np.float32)
+    if zero:
+        lo, hi = np.minimum(b.min(axis=2), 0.0), np.maximum(b.max(axis=2), 0.0)
+        s = np.maximum((hi - lo) / np.float32(15.0), np.float32(1e-8)).astype(np.float32)
+        z = np.clip(np.rint(-lo / s), 0, 15).astype(np.uint8)
+    else:
+        s = np.maximum(np.abs(b).max(axis=2) / np.float32(7.0), np.float32(1e-8)).astype(np.float32)
+        z = np.full(s.shape, 8, np.uint8)
+    q = np.clip(np.rint(b / s[:, :, None]) + z[:, :, None].astype(np.float32), 0, 15).astype(np.uint8)
+    return q, z, s
+
+
+def pack_nibbles(a: np.ndarray) -> np.ndarray:
+    """uint8 values < 16 along the last axis -> two per byte, element 2i in the LOW nibble (an odd count is padded with a 0 nibble)"""
+    if a.shape[-1] % 2:
+        a = np.concatenate([a, np.zeros(a.shape[:-1] + (1,), np.uint8)], axis=-1)
+    return np.ascontiguousarray(a[..., 0::2] | (a[..., 1::2] << 4)).astype(np.uint8)
 
 
 def densenet(batch: int | str = 1, *, growth: int = 32, blocks: Sequence[int] = (6, 12, 24, 16),
@@ -500,6 +551,23 @@ def gemm_mlp(batch: int | str = 4, din: int = 64, dh: int = 96, dout: int = 10, 
     gb.simple("Gemm", [x, gb.init("w2", w2, raw=False), gb.init("b2", b2, raw=False)],
               [pb.attr_float("alpha", 0.5), pb.attr_float("beta", 2.0)], out="y")
     return gb.finish([("x", [batch, din, 1, 1])], [("y", [batch, dout])], opset=11)
+
+
+def qlinear(rows: int | str = 8, k: int = 128, n: int = 80, *, q_block: int = 32, q_zero: bool = True, q_form: str = "nbits", residual: bool = False, bias: bool = False,
+            seed: int = 11, q_codes=None) -> bytes:
+    """One 4-bit Linear alone, x [rows, k] -> y [rows, n] (the batch is the GEMM's M, like gemm_mlp): y = Linear(x) (+ r, a second input [rows, n],
+    where residual).  x, r and y pass a Mul by 1: in fp16 precision the Linear then reads and writes the half buffers a model's Linears do (each input
+    rounded to half once, the result once), in fp32 the Muls change nothing."""
+    gb = GraphBuilder("qlinear", seed)
+    one = gb.init("one", np.array(1.0, np.float32))
+    r = gb.simple("Mul", ["r", one]) if residual else None      # (in front of the Linear: its Add folds only onto a value that exists when it runs)
+    y = gb.linear(gb.simple("Mul", ["x", one]), k, n, name="fc", bias=bias, quant="int4", q_block=q_block, q_zero=q_zero, q_form=q_form, q_codes=q_codes)
+    ins = [("x", [rows, k])]
+    if residual:
+        y = gb.simple("Add", [r, y])
+        ins.append(("r", [rows, n]))
+    gb.simple("Mul", [y, one], out="y")
+    return gb.finish(ins, [("y", [rows, n])], opset=18)
 
 
 def resnet_block(batch: int | str = 2, c: int = 32, image: int = 16, seed: int = 50) -> bytes:
@@ -1488,7 +1556,8 @@ def llama_attention(gb: GraphBuilder, x: str, seq: int, dim: int, heads: int, kv
 def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576, depth: int = 30, heads: int = 9, kv_heads: int = 3, mlp: int = 1536,
           max_pos: int = 2048, rope_theta: float = 10000.0, eps: float = 1e-5, tied: bool = True, last_hidden_state: bool = False, seed: int = 2023,
           norm: str = "pow", cast: bool = False, swap: bool = False, rope: str = "slice", repeat: str = "auto", scale: str = "mul", mask: str = "add",
-          w_scale: float | None = None, table_std: float = 1.0, present: bool = False, past: int | None = None, positions: str = "input") -> bytes:
+          w_scale: float | None = None, table_std: float = 1.0, present: bool = False, past: int | None = None, positions: str = "input",
+          quant: str | None = None, q_block: int = 32, q_zero: bool = True, q_form: str = "nbits") -> bytes:
     """LlamaForCausalLM as a prefill / scoring forward (Touvron et al. 2023; the shape of Llama 2 / 3, TinyLlama, SmolLM, Mistral and the dense Qwen
     models), ids [N, seq] -> logits [N, seq, vocab], written from modeling_llama.py's eager attention and the TorchScript exporter's known lowerings,
     NOT from a real export (neither `transformers` nor ONNX Runtime is available here); checked by the float64 walk of tests/ref64.py.
@@ -1519,7 +1588,9 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
                      inside the chunk goes by chunk index, not by position_ids.  The client writes rows P .. P + Lq - 1 of present.* into its cache at
                      row `len`; right- and left-padded caches both work.  A ragged batch pads the chunk on the right with the padded tokens' own mask
                      columns 0: the output rows of such tokens are finite and otherwise unspecified (the graph gives a uniform average there, and
-                     nobody reads it)"""
+                     nobody reads it)
+    quant="int4" (q_block, q_zero, q_form: GraphBuilder.linear's) quantises every decoder Linear; the head and the embedding stay float.  q_form "dense"
+    is the float32 twin of the same codes.  quant=None: the bytes of every graph above are unchanged"""
     gb = GraphBuilder("llama", seed)
     hd = dim // heads
     emb = np.float32(table_std) * rng.gaussish(seed, "embed_tokens", vocab * dim).reshape(vocab, dim).astype(np.float32)
@@ -1550,7 +1621,7 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
     opset = 23 if norm == "op" else 18
 
     def lin(y: str, name: str, cin: int, cout: int) -> str:
-        return gb.linear(y, cin, cout, name=name, bias=False, w_scale=w_scale)
+        return gb.linear(y, cin, cout, name=name, bias=False, w_scale=w_scale, quant=quant, q_block=q_block, q_zero=q_zero, q_form=q_form)
 
     for li in range(depth):
         tag = f"layers{li}"

@@ -69,6 +69,8 @@ def tensor(name: str, arr: np.ndarray, raw: bool = True) -> bytes:
         dt = FLOAT16
     elif arr.dtype == np.bool_:
         dt = BOOL          # one byte per element in raw_data
+    elif arr.dtype == np.uint8:
+        dt = UINT8         # one byte per element in raw_data (the packed operands of a MatMulNBits)
     else:
         raise TypeError(arr.dtype)
     out = b"".join(f_varint(1, d) for d in arr.shape)
@@ -111,13 +113,15 @@ def attr_str(name: str, s: str) -> bytes:
 
 
 def node(op_type: str, inputs: Iterable[str], outputs: Iterable[str], name: str = "",
-         attrs: Iterable[bytes] = ()) -> bytes:
+         attrs: Iterable[bytes] = (), domain: str = "") -> bytes:
     out = b"".join(f_str(1, i) for i in inputs)
     out += b"".join(f_str(2, o) for o in outputs)
     if name:
         out += f_str(3, name)
     out += f_str(4, op_type)
     out += b"".join(f_bytes(5, a) for a in attrs)
+    if domain:
+        out += f_str(7, domain)
     return out
 
 
@@ -143,9 +147,11 @@ def graph(name: str, nodes: Iterable[bytes], initializers: Iterable[bytes],
 
 
 def model(graph_bytes: bytes, opset: int = 11, ir_version: int = 6,
-          producer: str = "mi355x-inference-engine-modelgen") -> bytes:
+          producer: str = "mi355x-inference-engine-modelgen", extra_opsets: Sequence[tuple[str, int]] = ()) -> bytes:
     out = f_varint(1, ir_version)
     out += f_str(2, producer)
     out += f_bytes(7, graph_bytes)
     out += f_bytes(8, f_str(1, "") + f_varint(2, opset))
+    for domain, version in extra_opsets:      # (e.g. ("com.microsoft", 1) for MatMulNBits)
+        out += f_bytes(8, f_str(1, domain) + f_varint(2, version))
     return out
