@@ -94,6 +94,7 @@ DeviceModel::DeviceModel(std::shared_ptr<const OnnxModel> model, int device_id, 
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsDecode();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsWattn();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsTrans();
+        if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsQLinear();
     });
     check(g_kernels_err, "InitKernels");
     fp32_split_ = opt.fp32_split && opt.precision == Precision::F32;

@@ -258,14 +258,19 @@ struct QLinearArgs {
     int block = 32;                    // 32 | 64 | 128, K % block == 0
 };
 // tile 0: qlinear_generic_kernel (any view, float or half activations, fp32 FMAs); tile 1: qlinear_mfma_kernel (half activations and result, N % 16 == 0,
-// rows one pitch apart, 16-byte aligned operands)
-constexpr int kNumQLinearTiles = 2;
+// rows one pitch apart, 16-byte aligned operands); tile 2: qlinear_gemm_kernel (what tile 1 takes; a 128 x 128 output tile per workgroup with the
+// weights expanded into LDS once per K-step: the prefill row counts)
+constexpr int kNumQLinearTiles = 3;
 bool QLinearEligible(const QLinearArgs& a, int tile);
 hipError_t LaunchQLinear(const QLinearArgs& a, int tile, hipStream_t stream);
+hipError_t InitKernelsQLinear();         // once per process, before any capture: lets tile 2 take more than 64 KiB of LDS
 // what tile 1 asks of a step's shapes alone (the planner's default; the launcher re-checks pointers and alignment)
 constexpr bool QLinearMfmaFits(bool in16, bool out16, bool res16, int64_t k, int64_t n, int64_t in_pitch, int64_t in_off, int64_t out_pitch, int64_t out_off, int64_t res_pitch, int64_t res_off) {
     return in16 && out16 && res16 && k % 32 == 0 && n % 16 == 0 && in_pitch % 8 == 0 && in_off % 8 == 0 && out_pitch % 8 == 0 && out_off % 8 == 0 && res_pitch % 8 == 0 && res_off % 8 == 0;
 }
+// the row count from which the planner takes tile 2 for a step that fits (the same test: tile 2 takes what tile 1 takes).  Measured: the largest
+// crossover over the eight Linear shapes of llama_3b_layers and llama_135m, and never below 128
+constexpr int64_t kQLinearGemmMinRows = 4096;
 
 // GroupNormalization of an NHWC view (kernels_gn.hip): for image n and group g = c / (C / groups), over the C / groups channels of the group and every pixel,
 //   out[n, p, c] = act((in[n, p, c] - mean_ng) * rsqrt(var_ng + eps) * gamma[c] + beta[c]),  var_ng the mean of the centred squares.

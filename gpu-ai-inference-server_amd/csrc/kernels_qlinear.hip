@@ -24,6 +24,26 @@
 //   * K need only be a multiple of 32: a lane group whose 32 k lie past K feeds zeros on both sides.
 // Then the four waves' accumulators meet in LDS and are summed in wave order (fixed: two runs are bit-equal), and the epilogue -- bias, residual, the
 // conversion to half -- leaves in 16-byte stores, eight columns of one row per lane.  LDS: 4 x MT x 1 KiB, only for that reduction.
+//
+//   qlinear_gemm_kernel<BS, ZP>     tile 2 (half activations and result; prefill row counts): a workgroup of 4 waves owns 128 rows x 128
+//                                   columns, wave (wm, wn) a 64 x 64 quarter in 2 x 2 accumulators of v_mfma_f32_32x32x16_f16 (64 registers).
+//
+// Tile 2, per K-step of 64:
+//   * weights: thread t reads ONE 16-byte vector, the 32 codes k0 + 32 (t % 2) .. of column n0 + t / 2, with their one scale and zero point (tile 1's
+//     ql_load), expands them with tile 1's ql_expand -- the same halfs, bit for bit -- puts each group of eight back into the order 0 .. 7 (a register
+//     renaming: the two halfs of a pair land in other dwords) and writes four 16-byte vectors into the LDS image W[column][k].  Every packed byte of
+//     the strip is read and expanded once per workgroup and K-step: once per 128 rows where tile 1 does it once per 64, and by 256 lanes at once.
+//   * activations: thread t reads four 16-byte vectors, k0 + 8 (t % 8) .. of rows t / 8 + 32 i, and writes them to the LDS image X[row][k] as they are.
+//     Rows past M, columns past N and k past K enter as zeros (nothing is read for them).
+//   * both images have rows of 64 + 8 halfs: a pitch of 36 words, so the 16 lanes of a ds_read_b128 group fall on 16 different bank quads (the
+//     layout of the attention K / V images).  A fragment of either side is lane (r = lane % 32, hh = lane / 32) reading the eight halfs
+//     k = 16 ks + 8 hh .. of row r: per 16 k a wave reads two weight and two activation fragments for four MFMAs.
+//   * two LDS stages: the loads of step s + 1 are issued before the MFMAs of step s, expanded and written into the other stage after them, and ONE
+//     barrier closes the step.  LDS: 2 x 256 x 72 x 2 = 73 728 bytes, two workgroups per CU.
+// D = W x X^T (the weights are the MFMA's first operand): a lane owns one row m and quads of consecutive columns; v_permlane32_swap trades quads between
+// the half-waves so that each lane holds eight consecutive columns, and bias, residual and the one rounding to half leave as in tile 1, in 16-byte
+// stores.  No K split and no atomics: every output is one fixed-order sum.  The grid runs the row blocks fastest, so that the workgroups resident
+// together share column strips of the weights.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -227,9 +247,153 @@ hipError_t launch_mfma_zp(const QLinearArgs& a, int rows, hipStream_t stream) {
     return a.zps ? launch_mfma<BS, true>(a, rows, stream) : launch_mfma<BS, false>(a, rows, stream);
 }
 
+// ---- tile 2 ------------------------------------------------------------------------------------------------------------------------------------------
+constexpr int kQgTile = 128;                       // rows and columns of a workgroup's output tile
+constexpr int kQgStep = 64;                        // k per step
+constexpr int kQgPitch = kQgStep + 8;              // halfs per LDS row: 36 words
+constexpr int kQgStage = 2 * kQgTile * kQgPitch;   // halfs per stage: the weight image [128][72], then the activation image [128][72]
+constexpr int kQgLdsBytes = 2 * kQgStage * 2;      // 73 728
+
+// what a thread holds of the next K-step while this one's MFMAs run
+struct QgFetch {
+    QlWeights w;
+    h8 x[4];
+};
+
+template <int BS, bool ZP>
+__global__ __launch_bounds__(kQlBlock) void qlinear_gemm_kernel(const QLinearArgs a, const int rows) {
+    extern __shared__ __attribute__((aligned(16))) _Float16 smem_qg[];
+    const int tid = int(threadIdx.x), lane = tid % 64, wave = tid / 64;
+    const int r = lane % 32, hh = lane / 32, wm = wave / 2, wn = wave % 2;
+    const int K = a.in.c, N = a.out.c;
+    const int m0 = int(blockIdx.x) * kQgTile, n0 = int(blockIdx.y) * kQgTile;
+    const int nblk = K / BS;
+    // staging roles.  Weights: column wc, the 32 k from 32 wk on; a column past N reads nothing (its k is K: ql_load's zeros)
+    const int wc = tid / 2, wk = 32 * (tid % 2);
+    const bool wlive = n0 + wc < N;
+    const int wcol = wlive ? n0 + wc : n0;
+    const uint8_t* qrow = a.codes + int64_t(wcol) * (K / 2);
+    const float* srow = a.scales + int64_t(wcol) * nblk;
+    const uint8_t* zrow = ZP ? a.zps + int64_t(wcol) * ((nblk + 1) / 2) : nullptr;
+    // activations: rows xr + 32 i, the 8 k from xk on; a row past M reads nothing
+    const int xr = tid / 8, xk = 8 * (tid % 8);
+    const _Float16* xrow[4];
+    bool xlive[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int m = m0 + xr + 32 * i;
+        xlive[i] = m < rows;
+        xrow[i] = reinterpret_cast<const _Float16*>(a.in.p) + int64_t(xlive[i] ? m : 0) * a.in.sw + xk;
+    }
+    auto fetch = [&](int k0) {
+        QgFetch f;
+        f.w = ql_load<BS, ZP>(qrow, srow, zrow, wlive ? k0 + wk : K, K);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f.x[i] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+            if (xlive[i] && k0 + xk < K) f.x[i] = *reinterpret_cast<const h8*>(xrow[i] + k0);      // (K % 32 == 0: the 8 k are all inside or all outside)
+        }
+        return f;
+    };
+    auto stage = [&](const QgFetch& f, _Float16* st) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const h8 b = ql_expand(f.w.q[j], f.w);                 // k in the order 0 4 1 5 2 6 3 7
+            *reinterpret_cast<h8*>(st + wc * kQgPitch + wk + 8 * j) = __builtin_shufflevector(b, b, 0, 2, 4, 6, 1, 3, 5, 7);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<h8*>(st + (kQgTile + xr + 32 * i) * kQgPitch + xk) = f.x[i];
+    };
+
+    f32x16 acc[2][2];                                  // [32 columns jn][32 rows jm] of the wave's quarter
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i / 2][i % 2][e] = 0.f;
+
+    const int nsteps = (K + kQgStep - 1) / kQgStep;
+    stage(fetch(0), smem_qg);
+    __syncthreads();
+    const int woff = (wn * 64 + r) * kQgPitch + 8 * hh, xoff = (kQgTile + wm * 64 + r) * kQgPitch + 8 * hh;
+    for (int s = 0; s < nsteps; ++s) {
+        const bool more = s + 1 < nsteps;                          // workgroup-uniform
+        QgFetch nxt;
+        if (more) nxt = fetch((s + 1) * kQgStep);
+        const _Float16* st = smem_qg + (s & 1) * kQgStage;
+#pragma unroll
+        for (int ks = 0; ks < kQgStep / 16; ++ks) {
+            h8 wf[2], xf[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                wf[j] = *reinterpret_cast<const h8*>(st + woff + j * 32 * kQgPitch + 16 * ks);
+                xf[j] = *reinterpret_cast<const h8*>(st + xoff + j * 32 * kQgPitch + 16 * ks);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i / 2][i % 2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i / 2], xf[i % 2], acc[i / 2][i % 2], 0, 0, 0);
+        }
+        if (more) stage(nxt, smem_qg + ((s + 1) & 1) * kQgStage);  // the stage step s - 1 read: every wave is past the barrier that closed it
+        __syncthreads();
+    }
+    // accumulator element 4 g + q of lane (r, hh) is column 8 g + 4 hh + q, row r of the 32 x 32 tile.  Swapping the quads of groups 2 gp and 2 gp + 1
+    // between the half-waves leaves lane (r, hh) with the eight columns 8 (2 gp + hh) .. of row r (every lane takes part: no branch around the swaps)
+#pragma unroll
+    for (int jm = 0; jm < 2; ++jm) {
+        const int m = m0 + wm * 64 + jm * 32 + r;
+#pragma unroll
+        for (int jn = 0; jn < 2; ++jn) {
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+                float v[8];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float lo = acc[jn][jm][8 * gp + q], hi = acc[jn][jm][8 * gp + 4 + q];      // (values: a bit cast of a vector element reads element 0)
+                    const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi), false, false);
+                    const unsigned s0 = sw[0], s1 = sw[1];
+                    v[q] = __builtin_bit_cast(float, s0);
+                    v[4 + q] = __builtin_bit_cast(float, s1);
+                }
+                const int n = n0 + wn * 64 + jn * 32 + 8 * (2 * gp + hh);
+                if (m >= rows || n >= N) continue;                 // (N % 16 == 0: the eight columns are all inside or all outside)
+                if (a.bias) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] += a.bias[n + i];
+                }
+                if (a.res.p) {
+                    float rv[8];
+                    load16<_Float16>(reinterpret_cast<const _Float16*>(a.res.p) + int64_t(m) * a.res.sw + n, rv);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] += rv[i];
+                }
+                store16<_Float16>(reinterpret_cast<_Float16*>(a.out.p) + int64_t(m) * a.out.sw + n, v);
+            }
+        }
+    }
+}
+
+template <int BS>
+hipError_t launch_gemm(const QLinearArgs& a, int rows, hipStream_t stream) {
+    // the row blocks run fastest: the workgroups resident together share column strips of the weights
+    const dim3 grid(unsigned((rows + kQgTile - 1) / kQgTile), unsigned((a.out.c + kQgTile - 1) / kQgTile));
+    if (a.zps) qlinear_gemm_kernel<BS, true><<<grid, dim3(kQlBlock), kQgLdsBytes, stream>>>(a, rows);
+    else qlinear_gemm_kernel<BS, false><<<grid, dim3(kQlBlock), kQgLdsBytes, stream>>>(a, rows);
+    return hipGetLastError();
+}
+
 bool same_shape(const TensorArg& x, const TensorArg& y) { return x.n == y.n && x.h == y.h && x.w == y.w; }
 
 }  // namespace
+
+hipError_t InitKernelsQLinear() {
+    const void* const kernels[] = {
+        reinterpret_cast<const void*>(&qlinear_gemm_kernel<32, true>), reinterpret_cast<const void*>(&qlinear_gemm_kernel<32, false>),
+        reinterpret_cast<const void*>(&qlinear_gemm_kernel<64, true>), reinterpret_cast<const void*>(&qlinear_gemm_kernel<64, false>),
+        reinterpret_cast<const void*>(&qlinear_gemm_kernel<128, true>), reinterpret_cast<const void*>(&qlinear_gemm_kernel<128, false>)};
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kQgLdsBytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 bool QLinearEligible(const QLinearArgs& a, int tile) {
     if (tile < 0 || tile >= kNumQLinearTiles || !a.in.p || !a.out.p || !a.codes || !a.scales) return false;
@@ -242,7 +406,9 @@ bool QLinearEligible(const QLinearArgs& a, int tile) {
     if (!a.in.f16 || !a.out.f16 || a.out.c % 16 || rows >= (int64_t(1) << 22) || rows > 65535 * 64) return false;
     if (!VecViewOk(a.in, 8) || !RowsDense(a.in) || !VecViewOk(a.out, 8) || !RowsDense(a.out)) return false;
     if (a.res.p && (!a.res.f16 || !VecViewOk(a.res, 8) || !RowsDense(a.res))) return false;
-    return Aligned16(a.codes) && a.out.c / 16 <= 0x7fffffff;
+    if (!Aligned16(a.codes) || a.out.c / 16 > 0x7fffffff) return false;
+    // tile 2: the row blocks within 65 535 (they would fit the grid's x axis far beyond; the bound keeps either axis order open), the column tiles on y
+    return tile == 1 || ((rows + kQgTile - 1) / kQgTile <= 65535 && (a.out.c + kQgTile - 1) / kQgTile <= 65535);
 }
 
 hipError_t LaunchQLinear(const QLinearArgs& a, int tile, hipStream_t stream) {
@@ -254,6 +420,13 @@ hipError_t LaunchQLinear(const QLinearArgs& a, int tile, hipStream_t stream) {
         if (gy > 65535) return hipErrorInvalidValue;
         hipLaunchKernelGGL(qlinear_generic_kernel, dim3(unsigned((a.out.c + kQlWaves - 1) / kQlWaves), unsigned(gy)), dim3(kQlBlock), 0, stream, a, rows);
         return hipGetLastError();
+    }
+    if (tile == 2) {
+        switch (a.block) {
+            case 32: return launch_gemm<32>(a, int(rows), stream);
+            case 64: return launch_gemm<64>(a, int(rows), stream);
+            default: return launch_gemm<128>(a, int(rows), stream);
+        }
     }
     switch (a.block) {
         case 32: return launch_mfma_zp<32>(a, int(rows), stream);

@@ -776,7 +776,7 @@ std::string kernel_label(const Step& s) {
         }
         case StepKind::QLinear: {
             const std::string form = "b" + std::to_string(s.q_block) + (s.q_zp_off >= 0 ? ",zp>" : ",sym>");
-            return s.tile == 0 ? std::string("qlinear_generic_kernel<") + (s.in.f16 ? "f16," : "f32,") + form : "qlinear_mfma_kernel<" + form;
+            return s.tile == 0 ? std::string("qlinear_generic_kernel<") + (s.in.f16 ? "f16," : "f32,") + form : (s.tile == 2 ? "qlinear_gemm_kernel<" : "qlinear_mfma_kernel<") + form;
         }
         case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }

@@ -2357,8 +2357,9 @@ int64_t Planner::push_bytes(const std::vector<uint8_t>& v) {
     return off;
 }
 
-// A 4-bit Linear: the packed operands into the blob as they are; tile 1 (the MFMA kernel) where the step's views allow it, else the generic kernel.
-// IE_FORCE_TILE as for layer norm; IE_QLINEAR_TILE pins these steps alone (an ineligible 1 is the generic kernel)
+// A 4-bit Linear: the packed operands into the blob as they are; where the step's views allow it tile 1 (the MFMA kernel), from kQLinearGemmMinRows
+// rows on tile 2 (the LDS-staged 128 x 128 tile), else the generic kernel.
+// IE_FORCE_TILE as for layer norm; IE_QLINEAR_TILE pins these steps alone, at any row count (an ineligible 1 or 2 is the generic kernel)
 void Planner::EmitQLinear(const LNode& n, Step& s) {
     if (s.in.f8 || s.out.f8) fail("MatMulNBits is not supported in fp8 mode (node " + n.name + ")");
     s.kind = StepKind::QLinear;
@@ -2371,11 +2372,11 @@ void Planner::EmitQLinear(const LNode& n, Step& s) {
     const bool fits = !s.in.nchw && !s.out.nchw && !(s.has_in2 && s.in2.nchw) &&
                       QLinearMfmaFits(s.in.f16, s.out.f16, !s.has_in2 || s.in2.f16, s.in.c, s.out.c, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off,
                                       s.has_in2 ? s.in2.pitch : 0, s.has_in2 ? s.in2.c_off : 0);
-    s.tile = fits ? 1 : 0;
+    const double rows = double(s.in.n) * double(s.in.h) * double(s.in.w);
+    s.tile = !fits ? 0 : rows >= double(kQLinearGemmMinRows) ? 2 : 1;
     int t = ForcedTile(kNumQLinearTiles);
     if (const char* e = env.get("IE_QLINEAR_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumQLinearTiles) t = std::atoi(e);
     if (t >= 0) s.tile = t == 0 || fits ? t : 0;
-    const double rows = double(s.in.n) * double(s.in.h) * double(s.in.w);
     s.flops = 2.0 * rows * double(s.in.c) * double(s.out.c);
     s.bytes = vbytes(s.in) + vbytes(s.out) + (s.has_in2 ? vbytes(s.in2) : 0.0) + double(n.q_codes.size()) + 4.0 * double(n.s.size()) + double(n.q_zps.size()) + 4.0 * double(n.bias.size());
 }
