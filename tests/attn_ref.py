@@ -42,12 +42,24 @@ fp16 mode (u_h = 2^-11) adds derived terms per kernel, HALF_TERMS below, read of
     out   u_h |ref|   the output is a half tensor
     v, p  u_h Sv      each, for a V or a P that the kernel rounds to half
     q, k  u_h Dqk     each, for a q or a k that the kernel rounds itself (a rotated one, or an fp32 cache row staged as half)
+    k     u_h Dqkn    ("new") where the only k the kernel rounds is the step's new rows: Dqk's sum over the keys j >= past alone
+    p     u_h Svt     ("tail") Sv without the key of the row's largest score, whose probability is exactly 1 before and after the rounding
 
 An operand that arrives as an exact half adds nothing (in fp16 mode the token rows are halves already: the reference is computed from them).
+
+A half resident cache has entries of its own ("0h", "4h", "5h", "6h").  Their Step is built from the cache AS IT IS STORED: the cached rows are
+halves, so they add no k and no v term, and the tokens are halves; what is left is what the kernel itself rounds (the table below cites the lines).
+Rounding a half to half once more changes nothing, so the rounding such an entry does NOT list shows only against the numbers the cache was rounded
+from: tests/test_attn_ref.py holds the entry to the Step of the unrounded cache, where a K or V read as stored is one rounding the entry has no term for.
 
 Appended rows (appended_check): a v row and an unrotated k row are float32(operand) bit for bit.  A rotated k element is
 fl(x cos + fl(+-x_p sin)): the product carries (1 + d1), the FMA (1 + d2), |d| <= u, so the error is at most
 u |x_p sin| + u |x cos + x_p sin| (1 + u) <= 2u (|x||cos| + |x_p||sin|) (1 + u): the coefficient is 2u.
+A half cache (half=True, kv_append_rows_h_kernel and tile 4's owning split): v is the half token and an unrotated k the half token, bit for bit (a half
+passes the conversion to float and back unchanged).  A rotated k is t = the fp32 rotation above, rounded once: with mag = |x||cos| + |x_p||sin| and
+a = 2u (1 + u), |t - ref| <= a mag and so |t| <= (1 + a) mag; the rounding to a normal half adds at most u_h |t|, to a subnormal one (|t| < 2^-14) at
+most half the subnormal spacing, 2^-25.  Together |got - ref| <= (a + u_h (1 + a)) mag + 2^-25: the coefficient is 2u + u_h (with its second-order
+factors), and every appended element is exactly half-representable.
 
 Two data builders (token_table, peaked) give the tests a softmax that is not flat, and even_lengths the lengths of the "even" data.
 """
@@ -60,6 +72,8 @@ UH = 2.0 ** -11
 MARGIN = 2.0
 EXP_ULP = 1.0                       # V_EXP_F32: 1 ULP (instruction set reference); 1 ULP = 2u
 TILE = 32                           # keys per tile of the emulated online softmax
+WIDE_CHUNK = 128                    # kernels.h kAttnWideChunkKeys: the keys tile 6 stages at a time
+HALF_TILE_ELEMS = 2048              # kernels.h DecodeKeyTileHalf(hd) = 2048 / hd keys of the half tile 4 per iteration, 512 / hd per wave
 FLT_MAX = float(np.finfo(np.float32).max)
 LOG2E = np.float32(1.4426950408889634)
 
@@ -72,6 +86,23 @@ f32, f64 = np.float32, np.float64
 #   tile 5   attention_extend_kernel: q rotated in fp32 and rounded to half (q8), K and V of the fp32 cache rounded where they enter LDS, the
 #            probabilities rounded in front of the PV MFMA (pb), the result stored as T
 #   tiles 1, 2, 3   rope_rot rounds the rotated q and k once; V is the half input as it is; the probabilities are rounded (pb); the result is T
+#   tile 6   attention_extend_wide_kernel (kernels_extend_w.hip) is tile 5 at head dim 128: q rotated in fp32 and rounded once where rope_vec<half>
+#            returns it ("halfs are rounded once, here", the q8 block; without a rotation the half passes as it is), K and V of the fp32 cache
+#            rounded where they enter LDS ("fp32 `present` in fp16 mode: converted once, here"), pb = _Float16(s) in front of the PV MFMA, the
+#            result stored as T; the key waves' partials and the split records are fp32
+# Over a half resident cache (string keys; csrc/kernels_decode_h.hip and the KV / KVH forms of the kernels above).  The cached rows are halves and the
+# tokens are halves: no v term anywhere (a cached V is read as stored, a new v is "copied as the half it is" by kv_append_rows_h_kernel and by tile
+# 4's prologue), and the k term pays for ONE rounding, of the new k row, which is rotated in fp32, rounded once, stored and read as stored
+# (kv_append_rows_h_kernel: k[j] = _Float16(rotated<_Float16>(..)); attention_decode_h_kernel's prologue: s_q[G][e] = _Float16(rotated(..)), "attends
+# to it as stored"): "new", the term of the new rows alone (Dqkn) and, as "rope", only when the step rotates, because an unrotated half k passes unchanged.
+# p = "tail" (Svt): the probabilities are s[r] = fast_exp2(s[r] - mn) with mn the running maximum, so the key that holds the row's largest score has
+# exp2(0) = 1, which pb = _Float16(s) leaves as it is; the P rounding is paid for over the other keys.  Without these two restrictions a term would
+# pay for a rounding the kernel does not make (a cached K, a probability of 1), and a V or a cached K rounded once more would pass inside it
+#   "0h"     attention_inplace_generic_kernel<half, half>: attend_wave keeps q in fp32 and widens every cache element where it is read
+#   "4h"     attention_decode_h_kernel: q rounded after the fp32 rotation (prologue, s_q[row][e] = _Float16(rotated(..))); the v_dot2 accumulator, the
+#            softmax and o = fma(p, float(v_e), o al) are fp32, so no p term; the butterfly and the wave records are fp32
+#   "5h"     attention_extend_kernel<half, HD, true, true>: the cached row goes to LDS "with no conversion"; q and pb as tile 5
+#   "6h"     attention_extend_wide_kernel<half, 128, KW, true, true>: the same staging; q and pb as tile 6
 HALF_TERMS = {
     0: dict(out=True, q=False, k=False, v=False, p=False),
     4: dict(out=True, q=False, k=False, v=False, p=False),
@@ -79,6 +110,11 @@ HALF_TERMS = {
     1: dict(out=True, q="rope", k="rope", v=False, p=True),
     2: dict(out=True, q="rope", k="rope", v=False, p=True),
     3: dict(out=True, q="rope", k="rope", v=False, p=True),
+    6: dict(out=True, q="rope", k=True, v=True, p=True),
+    "0h": dict(out=True, q=False, k="new", v=False, p=False),
+    "4h": dict(out=True, q="rope", k="new", v=False, p=False),
+    "5h": dict(out=True, q="rope", k="new", v=False, p="tail"),
+    "6h": dict(out=True, q="rope", k="new", v=False, p="tail"),
 }
 
 
@@ -198,10 +234,10 @@ def rotate64(x, cos, sin):
 
 
 def reference(step):
-    """dict(ref, Sv, D, B, E, Dqk), each [N, Lq, H, hd] float64 (the module's docstring defines them)"""
+    """dict(ref, Sv, D, B, E, Dqk, Svt, Dqkn), each [N, Lq, H, hd] float64 (the module's docstring defines them)"""
     s_ = step
     g = s_.H // s_.Hkv
-    out = {k: np.zeros((s_.N, s_.Lq, s_.H, s_.hd), f64) for k in ("ref", "Sv", "D", "E", "Dqk")}
+    out = {k: np.zeros((s_.N, s_.Lq, s_.H, s_.hd), f64) for k in ("ref", "Sv", "D", "E", "Dqk", "Svt", "Dqkn")}
     for n in range(s_.N):
         for h in range(s_.H):
             kvh = h // g
@@ -224,6 +260,9 @@ def reference(step):
             out["D"][n, :, h] = np.einsum("ij,ije->ie", pa, dev)
             out["E"][n, :, h] = np.einsum("ij,ije->ie", p, dev)
             out["Dqk"][n, :, h] = np.einsum("ij,ije->ie", p * qk, dev)
+            top = p == p.max(-1, keepdims=True)                                      # the row's largest score: its probability is exp2(0) = 1, a half
+            out["Svt"][n, :, h] = np.where(top, 0.0, p) @ np.abs(v)
+            out["Dqkn"][n, :, h] = np.einsum("ij,ije->ie", (p * qk)[:, s_.past:], dev[:, s_.past:])
     out["B"] = out["Sv"] + out["D"]
     return out
 
@@ -234,8 +273,11 @@ def exp_term(r):
 
 def half_allowance(r, tile, rope):
     """fp16 mode's additive allowance of the kernel `tile` (HALF_TERMS) per element"""
-    t = {k: (rope if v == "rope" else bool(v)) for k, v in HALF_TERMS[tile].items()}
-    return UH * (t["out"] * np.abs(r["ref"]) + (t["v"] + t["p"]) * r["Sv"] + (t["q"] + t["k"]) * r["Dqk"])
+    e = HALF_TERMS[tile]
+    t = {k: (rope if v in ("rope", "new") else bool(v)) for k, v in e.items()}
+    p = t["p"] * r["Svt" if e["p"] == "tail" else "Sv"]
+    k = t["k"] * r["Dqkn" if e["k"] == "new" else "Dqk"]
+    return UH * (t["out"] * np.abs(r["ref"]) + t["v"] * r["Sv"] + p + t["q"] * r["Dqk"] + k)
 
 
 def excess(y, r, extra=0.0):
@@ -332,7 +374,71 @@ def _merge(recs):
     return M, L, O
 
 
-def emulate(step, *, hd_order=None, tile_seed=None, splits=1, slots=0, half=(), mutant=None, drop_alpha=None):
+def _merge_in_turn(recs):
+    """tile 6's key waves: record w is added to the running one with the pair's own maximum, m' = max(m, m_w), l = fma(l, exp2(m - m'), l_w exp2(m_w - m')),
+    o likewise.  A wave that saw nothing holds (-FLT_MAX, 0, 0): next to a real maximum its weight is exactly 0, next to another such wave 1 on zeros"""
+    m, l, o = recs[0]
+    for m2, l2, o2 in recs[1:]:
+        mn = np.maximum(m, m2)
+        wa, wb = _exp2_32(m - mn), _exp2_32(m2 - mn)
+        l, o, m = _r32(l * wa + _r32(l2 * wb)), _r32(o * wa + _r32(o2 * wb)), mn
+    return m, l, o
+
+
+def _butterfly(recs):
+    """the half tile 4's key slots of one wave (a power of two of them): every slot is scaled to the wave's maximum, l w and o w rounded, and the scaled
+    records are added over the lane bits from the lowest up, which for slot 0 is the tree ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) ..."""
+    M = np.max([r[0] for r in recs], axis=0)
+    ls = [_r32(l * _exp2_32(m - M)) for m, l, _ in recs]
+    os_ = [_r32(o * _exp2_32(m - M)) for m, _, o in recs]
+    while len(ls) > 1:
+        ls = [_r32(ls[i] + ls[i + 1]) for i in range(0, len(ls), 2)]
+        os_ = [_r32(os_[i] + os_[i + 1]) for i in range(0, len(os_), 2)]
+    return M, ls[0], os_[0]
+
+
+def kernel_keys(step, n, resident=None):
+    """the Step's key indices of image n in the order an in-place kernel meets them: resident = (lens, new): the len cached rows, then the c new ones
+    (the Step keeps the cache's unused rows between them, masked); None: all Lk keys, as a kernel over `present` walks them"""
+    if resident is None:
+        return np.arange(step.Lk)
+    lens, new = resident
+    return np.concatenate([np.arange(lens[n]), step.past + np.arange(new[n])]).astype(int)
+
+
+def _key_wave_records(x, v, keys, hd, splits, waves, p_half):
+    """tile 6: split s takes the key tiles [s per, (s + 1) per) of ceil(keys / 32); its keys pass in chunks of WIDE_CHUNK, tile t of a chunk goes to key
+    wave t % waves, every key wave keeps one (m, l, o) over all chunks of the split, and the waves' records meet in key-wave order"""
+    per = -(-(-(-len(keys) // TILE)) // splits)
+    recs = []
+    for sp in range(splits):
+        k0, k1 = sp * per * TILE, min(len(keys), (sp + 1) * per * TILE)
+        mine = [[(t0 // TILE, list(keys[t0:min(k1, t0 + TILE)])) for c0 in range(k0, k1, WIDE_CHUNK) for t0 in range(c0 + w * TILE, min(k1, c0 + WIDE_CHUNK), waves * TILE)]
+                for w in range(waves)]
+        recs.append(_merge_in_turn([_online(x, v, t, hd, p_half) for t in mine]))
+    return recs
+
+
+def _half_decode_records(x, v, keys, cached, hd, splits, p_half):
+    """the half tile 4: the `cached` first keys in key tiles of KT = 2048 / hd shared by the splits, key j of a split in slot (j - k0) % KT, every slot
+    its own online softmax key by key; the split that holds the last cached key (none cached: the last split) gives the new key to slot 0, behind its
+    cached ones.  The 512 / hd slots of a wave meet by _butterfly, the four wave records in wave order (_merge); a split without keys: (-FLT_MAX, 0, 0)"""
+    kt, kpw = HALF_TILE_ELEMS // hd, HALF_TILE_ELEMS // 4 // hd
+    tiles = -(-cached // kt)
+    per = -(-tiles // splits)
+    owner = (tiles - 1) // per if tiles else splits - 1
+    recs = []
+    for sp in range(splits):
+        k0, k1 = sp * per * kt, min(cached, (sp + 1) * per * kt)
+        slots = [[(j, [keys[j]]) for j in range(k0 + t, k1, kt)] for t in range(kt)]
+        if sp == owner:
+            slots[0] += [(j, [keys[j]]) for j in range(cached, len(keys))]
+        each = [_online(x, v, d, hd, p_half) for d in slots]
+        recs.append(_merge([_butterfly(each[w * kpw:(w + 1) * kpw]) for w in range(4)]))
+    return recs
+
+
+def emulate(step, *, hd_order=None, tile_seed=None, splits=1, slots=0, waves=0, hmerge=False, resident=None, half=(), mutant=None, drop_alpha=None):
     """One legal fp32 evaluation of the step -> [N, Lq, H, hd] (float64 array of float32 numbers, of halves with "out" in `half`).
     hd_order: a permutation of the head dim for the score chain; tile_seed: a seeded random order of every split's key tiles; splits: the key tiles
     in `splits` consecutive runs, each with its own (m, l, o) record, combined in split order.
@@ -340,6 +446,8 @@ def emulate(step, *, hd_order=None, tile_seed=None, splits=1, slots=0, half=(), 
     splits cut at multiples of NS), every slot runs its own online softmax key by key, and the slots' records are merged in slot order before the
     splits are.  What this form adds is the ORDER: the record that holds the largest score may come first, and every later record is then added to
     sums that already have their full size.
+    waves = KW > 0: tile 6's partition (_key_wave_records); hmerge: the half tile 4's (_half_decode_records).  Both walk the keys of kernel_keys(step, n,
+    resident), resident = (lens, new) of a step bound to a cache: the order is the kernel's, counted from len, not from the Step's padded rows.
     half / mutant: operands rounded to half on the way ("q" and "k" after the rotation, "v", "p" in front of P V, "out"): `half` is an fp16 kernel's
     legal form, `mutant` the same switches as a precision mistake of an fp32 kernel.  drop_alpha = t: the rescale of key tile t left out of the
     second half of the head dim (a mutant)."""
@@ -373,7 +481,13 @@ def emulate(step, *, hd_order=None, tile_seed=None, splits=1, slots=0, half=(), 
             x = np.maximum(_r32(acc * sl2 + bias2[None, :]), -FLT_MAX)
             x = np.where(vis, x, -np.inf)
             recs = []
-            for sp in range(splits):
+            if waves or hmerge:
+                keys = kernel_keys(s_, n, resident)
+                if waves:
+                    recs = _key_wave_records(x, v, keys, hd, splits, waves, "p" in rnd)
+                else:
+                    recs = _half_decode_records(x, v, keys, int((keys < s_.past).sum()), hd, splits, "p" in rnd)
+            for sp in range(0 if waves or hmerge else splits):
                 k0, k1 = sp * per * width, min(s_.Lk, (sp + 1) * per * width)
                 if slots:
                     dealt = [[(j, [j]) for j in range(k0 + t, k1, slots)] for t in range(slots)]
@@ -384,17 +498,19 @@ def emulate(step, *, hd_order=None, tile_seed=None, splits=1, slots=0, half=(), 
                     rs.shuffle(tiles)
                 recs.append(_online(x, v, tiles, hd, "p" in rnd, drop_alpha))
             _, l, o = recs[0] if splits == 1 else _merge(recs)
-            y = _r32(o / l)
+            with np.errstate(invalid="ignore"):        # (an image with no key at all, c = 0 over an empty cache: 0 / 0, a row nobody reads)
+                y = _r32(o / l)
             if "out" in rnd:
                 y = _h16(y)
             out[n, :, kvh * g:(kvh + 1) * g] = y.reshape(s_.Lq, g, hd)
     return out
 
 
-def c_emul(step, r=None, rows=None, splits=1, slots=0, seed=0):
+def c_emul(step, r=None, rows=None, splits=1, slots=0, seed=0, waves=0, hmerge=False, resident=None):
     """The largest c over the legal orders of this step's own data: the sequential chains, one seeded random order of the head dim and of the key
-    tiles, (splits > 1) the records of `splits` runs of key tiles combined in split order, sequential and in the random order, and (slots > 0, tile
-    4) the key-slot partition at the step's splits.  -> (c_emul, {name: c})"""
+    tiles, (splits > 1) the records of `splits` runs of key tiles combined in split order, sequential and in the random order, (slots > 0, tile
+    4) the key-slot partition at the step's splits, (waves > 0, tile 6) the key-wave partition and (hmerge, the half tile 4) the butterfly, both at
+    the step's splits over the keys of kernel_keys(step, n, resident).  -> (c_emul, {name: c})"""
     r = r if r is not None else reference(step)
     perm = np.random.RandomState(seed).permutation(step.hd)
     runs = {"seq": emulate(step), "perm": emulate(step, hd_order=perm, tile_seed=seed)}
@@ -404,6 +520,12 @@ def c_emul(step, r=None, rows=None, splits=1, slots=0, seed=0):
     if slots:
         runs[f"slots{slots}"] = emulate(step, splits=splits, slots=slots)
         runs[f"slots{slots} perm"] = emulate(step, hd_order=perm, splits=splits, slots=slots)
+    if waves:
+        runs[f"waves{waves}"] = emulate(step, splits=splits, waves=waves, resident=resident)
+        runs[f"waves{waves} perm"] = emulate(step, hd_order=perm, splits=splits, waves=waves, resident=resident)
+    if hmerge:
+        runs["butterfly"] = emulate(step, splits=splits, hmerge=True, resident=resident)
+        runs["butterfly perm"] = emulate(step, hd_order=perm, splits=splits, hmerge=True, resident=resident)
     cs = {k: c_stat(v, r, rows) for k, v in runs.items()}
     return max(cs.values()), cs
 
@@ -414,21 +536,32 @@ MUTANTS = {"K half": dict(mutant=("k",)), "V half": dict(mutant=("v",)), "P half
 # ---------------------------------------------------------------------------------------------------------------------
 # appended rows
 # ---------------------------------------------------------------------------------------------------------------------
-def appended_check(step, got_k, got_v, image, count):
+HALF_SUBNORMAL = 2.0 ** -25          # half the spacing of the subnormal halves: the rounding error of a value below 2^-14
+
+
+def appended_check(step, got_k, got_v, image, count, half=False):
     """The first `count` new rows of image `image` as a kernel wrote them (got_k, got_v [Hkv, count, hd] float32) against the rule: v and an
     unrotated k bit for bit float32(operand); a rotated k element within 2u (|x||cos| + |x_p||sin|) (1 + u) of float64.
-    -> (ok, the worst rotated error in units of u * magnitude)"""
+    half: the rows of a half cache (the step's tokens are halves): bit for bit likewise, every element exactly a half, a rotated k element within
+    (a + u_h (1 + a)) (|x||cos| + |x_p||sin|) + 2^-25 with a = 2u (1 + u) (the module's docstring).
+    -> (ok, the worst rotated error in units of u * magnitude; half: of u_h * magnitude, the subnormal allowance taken off first)"""
     n, p = image, step.past
     k, v = step.k[n, :, p:p + count], step.v[n, :, p:p + count]
-    ok = np.array_equal(np.asarray(got_v, f32), v.astype(f32))
+    got_k, got_v = np.asarray(got_k, f32), np.asarray(got_v, f32)
+    ok = np.array_equal(got_v, v.astype(f32))
+    if half:
+        ok = ok and np.array_equal(got_k, half_exact(got_k)) and np.array_equal(got_v, half_exact(got_v))
     if not step.rope:
-        return ok and np.array_equal(np.asarray(got_k, f32), k.astype(f32)), 0.0
+        return ok and np.array_equal(got_k, k.astype(f32)), 0.0
     ref, mag = rotate64(k, step.kcos[n, p:p + count][None], step.ksin[n, p:p + count][None])
-    err = np.abs(np.asarray(got_k, f64) - ref)
+    err = np.abs(got_k.astype(f64) - ref)
+    unit, a = (UH, 2.0 * U * (1.0 + U)) if half else (U, 0.0)
+    if half:
+        err = np.maximum(err - HALF_SUBNORMAL, 0.0)
     with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(mag > 0, err / (U * np.where(mag > 0, mag, 1.0)), np.where(err > 0, np.inf, 0.0))
+        ratio = np.where(mag > 0, err / (unit * np.where(mag > 0, mag, 1.0)), np.where(err > 0, np.inf, 0.0))
     worst = float(ratio.max()) if ratio.size else 0.0
-    return ok and worst <= 2.0 * (1.0 + U), worst
+    return ok and worst <= (a / UH + 1.0 + a if half else 2.0 * (1.0 + U)), worst
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -451,12 +584,14 @@ def even_lengths(past, n=2):
     return [max(1, past - 5) if i % 2 == 0 else past for i in range(n)]
 
 
-def peaked(step, lens, cache_k, cache_v):
+def peaked(step, lens, cache_k, cache_v, also=()):
     """Copies of the cache [N, Hkv, P, hd] whose rows below lens[n] are permuted, K and V together, so that the scores of ONE query (the last new
     token of the K / V head's first query head) ascend over the cached keys of (image, K / V head) where n + kvh is odd and descend where it is even:
     with ascending scores the running maximum moves in every key tile and the largest score sits in the last split.  `step`: the Step of the
-    unpermuted data (its q is the one the kernel gets: build it from the peaked token rows)"""
+    unpermuted data (its q is the one the kernel gets: build it from the peaked token rows).  also: further arrays of the cache's shape that take the
+    same permutation, returned behind the two (the numbers a half cache was rounded from)"""
     ck, cv = np.array(cache_k, copy=True), np.array(cache_v, copy=True)
+    more = [np.array(x, copy=True) for x in also]
     g = step.H // step.Hkv
     for n in range(step.N):
         q, _ = rotate64(step.q[n, -1], step.qcos[n, -1], step.qsin[n, -1])            # [H, hd]
@@ -466,7 +601,9 @@ def peaked(step, lens, cache_k, cache_v):
             o = np.argsort(s if (n + kvh) % 2 else -s, kind="stable")
             ck[n, kvh, :ln] = np.asarray(cache_k)[n, kvh, :ln][o]
             cv[n, kvh, :ln] = np.asarray(cache_v)[n, kvh, :ln][o]
-    return ck, cv
+            for x, src in zip(more, also):
+                x[n, kvh, :ln] = np.asarray(src)[n, kvh, :ln][o]
+    return (ck, cv, *more) if also else (ck, cv)
 
 
 def peaked_prefill(tok, heads, kv_heads, hd, tables=None, q_gain=Q_GAIN):

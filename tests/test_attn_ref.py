@@ -7,7 +7,10 @@
     the old measure (max err / max|ref| against engine_run.RTOL = 2e-4) is printed on the P = 300 case: 1.93e-4 on the feeds of
     test_extend_gpu.py::test_long_cache_and_splits, which the old bound lets through, 2.2e-4 and 3.8e-4 on this file's even and peaked data;
   * tile 4's key-slot order is a legal sample the key-tile forms do not bound (found on the MI355X), so c_emul of a tile 4 case includes it;
-  * the fp16 term table (attn_ref.HALF_TERMS) admits the half-operand emulation of every kernel it describes."""
+  * the fp16 term table (attn_ref.HALF_TERMS) admits the half-operand emulation of every kernel it describes;
+  * the new kernels (tile 6 and the kernels over a half resident cache) on the data of attn_row_cases.EXTEND_WIDE, DECODE_HALF and the bound cases: the
+    reference is the float64 walk, c_emul with the key-wave and the butterfly order stays below CEILING, every new entry admits its own half form in
+    its own merge order, and rejects the rounding it does not list."""
 import numpy as np
 import pytest
 
@@ -41,12 +44,37 @@ CASES = {
     "prefill L 40": lambda: RC.prefill_case(2, 64, 40),
     "prefill L 129": lambda: RC.prefill_case(2, 32, 129),
 }
-SPLITS = {"decode P 200": 3, "extend P 300 Lq 8": 3, "extend P 40 Lq 65": 3, "extend P 40 Lq 64": 3}
+WIDE = {f"wide P {p} Lq {lq}": (p, lq) for p, lq in RC.EXTEND_WIDE}                                      # tile 6 over `present`
+HALF4 = {f"half decode H 4/{kvh} hd {hd} P {p}": (kvh, hd, p) for kvh, hd, p in RC.DECODE_HALF}              # the half tile 4 and tile 0 over a half cache
+CASES.update({name: (lambda a=a: RC.wide_case(*a)) for name, a in WIDE.items()})
+CASES.update({name: (lambda a=a: RC.decode_half_case(*a)) for name, a in HALF4.items()})
+G8 = {f"half decode H 8/1 hd {hd} P {RC.half_key_tile(hd) + 2}": (1, hd, RC.half_key_tile(hd) + 2, 8) for hd in (128, 32)}      # the G = 8 form
+CASES.update({name: (lambda a=a: RC.decode_half_case(*a)) for name, a in G8.items()})
+CASES.update({
+    "half decode 200 S 3": lambda: RC.cache_case(2, 64, 200, 1, (0, 199), (0, 199), half=True),
+    "wide half cache 300 S 3": lambda: RC.wide_case(300, 8, (129, 290), None, True),
+    "wide half cache 110 Lq 65": lambda: RC.wide_case(110, 65, (3, 40), None, True),
+    "half extend 300 S 3": lambda: RC.cache_case(2, 64, 300, 8, (255, 256), (255, 256), half=True),
+    "half extend 70 Lq 33": lambda: RC.cache_case(2, 64, 70, 33, (3, 37), (3, 37), half=True),
+    "half extend ragged c (0, 5)": lambda: RC.cache_case(2, 64, 40, 5, (7, 30), (7, 30), new=(0, 5), half=True),
+})
+PLAIN = {f"no rope half tile {t} hd {a[1]} cache {a[2]}": (t, a, sp) for t, a, sp in RC.NO_ROPE_HALF}      # half-cache cases without a rotation
+CASES.update({name: (lambda a=a: RC.no_rope_half_case(a)) for name, (_, a, _) in PLAIN.items()})
+WIDE_HALF = ["wide half cache 300 S 3", "wide half cache 110 Lq 65"]
+EXTEND_HALF = ["half extend 300 S 3", "half extend 70 Lq 33"]
+HALF4_MORE = list(G8) + ["half decode 200 S 3"]
+NEW = list(WIDE) + list(HALF4) + HALF4_MORE + list(PLAIN) + WIDE_HALF + EXTEND_HALF + ["half extend ragged c (0, 5)"]
+# the kernel's own order of a case (Case.yard): tile 6's key waves (bound to a cache: counted from len), the half tile 4's butterfly
+ORDER = {name: dict(waves=RC.wide_key_waves(2 * lq)) for name, (_, lq) in WIDE.items()}
+ORDER.update({name: dict(hmerge=True, bound=True) for name in list(HALF4) + HALF4_MORE})
+ORDER.update({"wide half cache 300 S 3": dict(waves=4, bound=True), "wide half cache 110 Lq 65": dict(waves=1, bound=True)})
+ORDER.update({name: dict(hmerge=True, bound=True) if t == 4 else dict(waves=4, bound=True) for name, (t, _, _) in PLAIN.items() if t in (4, 6)})
+SPLITS = {**{name: sp for name, (_, _, sp) in PLAIN.items()}, "half decode 200 S 3": 3, "wide half cache 300 S 3": 3, "half extend 300 S 3": 3, "decode P 200": 3, "extend P 300 Lq 8": 3, "extend P 40 Lq 65": 3, "extend P 40 Lq 64": 3}
 SLOTS = {"decode P 17": 16, "decode hd 128 P 9": 8, "decode P 200": 16}      # tile 4's key slots (kv_graphs.key_tile) of the decode cases
 
 
 @pytest.mark.parametrize("kind", RC.KINDS)
-@pytest.mark.parametrize("name", ["decode P 17", "extend P 33 Lq 5", "extend ragged c (0, 5)", "extend P 300 Lq 8", "prefill L 40"])
+@pytest.mark.parametrize("name", ["decode P 17", "extend P 33 Lq 5", "extend ragged c (0, 5)", "extend P 300 Lq 8", "prefill L 40"] + NEW)
 def test_reference_is_the_float64_walk(name, kind):
     case = CASES[name]()
     want = RC.out_rows(ref64.run_f64(case.mb, case.feeds[kind])["y" if case.form == "prefill" else "out"], case)
@@ -73,7 +101,7 @@ def test_reference_is_the_float64_walk(name, kind):
 @pytest.mark.parametrize("name", list(CASES))
 def test_c_emul_stays_below_the_ceiling(name, kind):
     case = CASES[name]()
-    _, ce, parts = case.yard(kind, splits=SPLITS.get(name, 1), slots=SLOTS.get(name, 0))
+    _, ce, parts = case.yard(kind, splits=SPLITS.get(name, 1), slots=SLOTS.get(name, 0), **ORDER.get(name, {}))
     print(f"{name} {kind}: c_emul {ce:.2f} " + " ".join(f"{k} {v:.2f}" for k, v in parts.items()))
     assert 0 < ce < CEILING, (name, kind, parts)
 
@@ -144,23 +172,60 @@ def test_a_missing_alpha_misses_the_fp32_bound_tenfold(name):
     assert first <= 1.0, "the first half of the head dim is untouched"
 
 
-HALF_FORMS = {0: ("out",), 4: ("out",), 5: ("q", "k", "v", "p", "out"), 1: ("q", "k", "p", "out"), 2: ("q", "k", "p", "out"), 3: ("q", "k", "p", "out")}
+HALF_FORMS = {0: ("out",), 4: ("out",), 5: ("q", "k", "v", "p", "out"), 1: ("q", "k", "p", "out"), 2: ("q", "k", "p", "out"), 3: ("q", "k", "p", "out"),
+              6: ("q", "k", "v", "p", "out"), "0h": ("k", "out"), "4h": ("q", "k", "out"), "5h": ("q", "k", "p", "out"), "6h": ("q", "k", "p", "out")}
+# the new entries and the cases each is held on (over a half cache "k" rounds the new row alone: the cached ones are halves already)
+ENTRY_CASES = {6: list(WIDE), "6h": WIDE_HALF, "5h": EXTEND_HALF, "4h": list(HALF4) + HALF4_MORE, "0h": list(HALF4) + ["half extend ragged c (0, 5)"]}
+for _name, (_t, _, _) in PLAIN.items():
+    ENTRY_CASES[f"{_t}h"] = ENTRY_CASES[f"{_t}h"] + [_name]
+
+
+def _order(entry, name, case, kind):
+    """(Case.yard's and attn_ref.emulate's keywords of) the merge order of the entry's kernel on the case: tile 0 and tile 5 have none of their own"""
+    kw = dict(ORDER.get(name, {})) if entry in (6, "6h", "4h") else {}
+    em = {k: v for k, v in kw.items() if k != "bound"}
+    return kw, dict(em, resident=case.resident(kind)) if kw.get("bound") else em
 
 
 @pytest.mark.parametrize("kind", RC.KINDS)
 @pytest.mark.parametrize("tile, name", [(0, "decode P 200"), (4, "decode P 200"), (0, "extend P 300 Lq 8"), (5, "extend P 300 Lq 8"), (5, "extend P 40 Lq 65"),
-                                        (1, "prefill L 129"), (3, "prefill L 129"), (2, "prefill L 40")])
+                                        (1, "prefill L 129"), (3, "prefill L 129"), (2, "prefill L 40")] + [(e, n) for e, names in ENTRY_CASES.items() for n in names])
 def test_half_terms_admit_the_half_operand_emulation(tile, name, kind):
     """the kernel's fp16 form as HALF_TERMS describes it (the token rows arrive as halves), emulated, within the fp32 bound plus the table's terms"""
     case = CASES[name]()
     assert all(bool(v) == (k in HALF_FORMS[tile]) for k, v in AR.HALF_TERMS[tile].items())
     st = case.step(kind, "fp16")
     slots = SLOTS[name] if tile == 4 else 0
-    r, ce, _ = case.yard(kind, "fp16", splits=SPLITS.get(name, 1), slots=slots)
+    yard_kw, emul_kw = _order(tile, name, case, kind)
+    r, ce, _ = case.yard(kind, "fp16", splits=SPLITS.get(name, 1), slots=slots, **yard_kw)
     rows = AR.own_key_valid(st)
-    y = AR.emulate(st, half=HALF_FORMS[tile], slots=slots)
+    y = AR.emulate(st, half=HALF_FORMS[tile], slots=slots, splits=SPLITS.get(name, 1) if emul_kw else 1, **emul_kw)
     extra = AR.half_allowance(r, tile, st.rope)
     ratio = AR.worst_ratio(y, r, ce, rows, extra)
     print(f"{name} {kind} tile {tile}: half-operand emulation at {ratio:.3f} of the bound (without the terms: {AR.worst_ratio(y, r, ce, rows):.0f})")
     assert ratio <= 1.0
     assert AR.worst_ratio(y, r, ce, rows) > 10.0, "without its terms the fp16 form is a mutant"
+
+
+@pytest.mark.parametrize("entry, switch", [("4h", "p")] + [(e, w) for w in ("v", "k") for e in ("0h", "4h", "5h", "6h")])
+def test_a_half_cache_entry_rejects_the_rounding_it_does_not_list(entry, switch):
+    """On the peaked data of the entry's cases.  "p": the probabilities of the half tile 4 rounded in front of P V, which the entry has no term for.
+    "v" and "k": a half rounded to half once more is itself, so the one V or cached-K rounding an entry without a v term (with a k term for the new
+    row alone) does not pay for is the one that made the cache: the Step holds that operand as the numbers the cache was rounded from, the kernel's
+    form reads it as stored.  At least one case must miss the bound (every case's miss is printed).
+
+    Where a step rotates, the entry's q term (u_h Dqk, a worst case over the head dim that one rounded operand uses about 1 / sqrt(hd) of) leaves room
+    for a second rounding of the same size, so the cases without a rotation (attn_row_cases.NO_ROPE_HALF), where the "rope" terms are absent, are
+    the sharp ones.  Measured there, in shares of the bound: p "4h" 1.6; v "0h" and "4h" 36, "5h" 1.4, "6h" 1.5; k "0h" and "4h" 55 .. 78,
+    "5h" 4.1, "6h" 3.9 (the rotating cases stay between 0.3 and 1.4)"""
+    miss = {}
+    for name in ENTRY_CASES[entry]:
+        case = CASES[name]()
+        st = case.step("peaked", "fp16", raw="" if switch == "p" else switch)
+        r = case.ref("peaked", "fp16") if switch == "p" else AR.reference(st)
+        yard_kw, emul_kw = _order(entry, name, case, "peaked")
+        _, ce, _ = case.yard("peaked", "fp16", splits=SPLITS.get(name, 1), **yard_kw)
+        y = AR.emulate(st, half=HALF_FORMS[entry], mutant=(switch,), splits=SPLITS.get(name, 1) if emul_kw else 1, **emul_kw)
+        miss[name] = AR.worst_ratio(y, r, ce, AR.own_key_valid(st), AR.half_allowance(r, entry, st.rope))
+        print(f"{name} peaked, entry {entry}: {switch} rounded once more: {miss[name]:.2f} of the bound")
+    assert max(miss.values()) > 1.0, (entry, switch, miss)

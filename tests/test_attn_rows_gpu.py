@@ -9,7 +9,13 @@ attn_ref.appended_check: v and an unrotated k bit for bit, a rotated k within 2u
 
 The cases that exist today (tests/test_kv_cache_gpu.py, test_extend_gpu.py, test_rope_attention_gpu.py, test_attention_stream_causal_gpu.py) are
 re-measured; the in-place cases (a model bound to a B.KvCache whose rows beyond `len` are NaN) are new: tile 5 at three splits and over more than one
-row block, c = 0 in an extend and in a decode step, tile 4 at three splits over an empty image."""
+row block, c = 0 in an extend and in a decode step, tile 4 at three splits over an empty image.
+
+Tile 6 (attention_extend_wide_kernel, head dim 128; its c_emul includes the key-wave order) runs unbound and bound to an fp32 cache in both precisions.
+Over a HALF resident cache (fp16 only; the cache of the case holds halves, so what is written is exact) run tile 6, tile 5, tile 0 and the half tile 4
+(attention_decode_h_kernel; its c_emul includes the butterfly merge), each under its own attn_ref.HALF_TERMS entry ("6h", "5h", "0h", "4h"), and the
+appended rows are held to the half form of appended_check: v and an unrotated k bit for bit, a rotated k within 2u + u_h of its magnitude, every
+element a half."""
 import numpy as np
 import pytest
 
@@ -23,6 +29,9 @@ import resident_graphs as RG
 from engine_run import plan_of
 from gpu_ai_inference_server_amd import binding as B
 from gpu_ai_inference_server_amd.modelgen import models
+from test_extend_wide_gpu import label as wide_label
+from test_extend_wide_plan import WIDE_TILE
+from test_half_cache_gpu import _kv16
 
 pytestmark = pytest.mark.gpu
 N, H = RC.N, RC.H
@@ -41,13 +50,23 @@ def _groups(case, st):
     return {f"image {n}": own & (np.arange(N)[:, None] == n) for n in range(N)}
 
 
-def _hold(y, case, kind, prec, tile, splits, what):
-    """every valid row of y within the bound, the rest finite; prints c per group.  c_emul of a tile 4 case includes the key-slot form"""
+def _order(case, tile, bound, half):
+    """the emulated orders c_emul of the case includes beyond the key tiles: tile 4's key slots, the half tile 4's butterfly, tile 6's key waves"""
+    if tile == KG.DECODE_TILE:
+        return dict(hmerge=True, bound=True) if half else dict(slots=KG.key_tile(case.hd))
+    if tile == WIDE_TILE:
+        return dict(waves=RC.wide_key_waves(case.h // case.kvh * case.lq), bound=bound)
+    return {}
+
+
+def _hold(y, case, kind, prec, tile, splits, what, bound=False, half=False):
+    """every valid row of y within the bound, the rest finite; prints c per group.  c_emul of a tile 4 case includes the key-slot form, of the half
+    tile 4 the butterfly, of tile 6 the key waves; half: the HALF_TERMS entry of the kernel over a half cache"""
     st = case.step(kind, prec)
-    r, ce, _ = case.yard(kind, prec, splits, KG.key_tile(case.hd) if tile == KG.DECODE_TILE else 0)
+    r, ce, _ = case.yard(kind, prec, splits, **_order(case, tile, bound, half))
     yr = RC.out_rows(y, case)
     assert np.isfinite(yr).all(), (what, "out is not finite")
-    extra = AR.half_allowance(r, tile, st.rope) if prec == "fp16" else 0.0
+    extra = AR.half_allowance(r, f"{tile}h" if half else tile, st.rope) if prec == "fp16" else 0.0
     for name, rows in _groups(case, st).items():
         if rows.any():
             print(f"ATTN_ROWS {what} | {kind} | {name}: c {AR.c_stat(yr, r, rows, extra):.2f} c_emul {ce:.2f} of the bound {AR.worst_ratio(yr, r, ce, rows, extra):.3f}")
@@ -55,16 +74,18 @@ def _hold(y, case, kind, prec, tile, splits, what):
     assert worst <= 1.0, (what, kind, worst)
 
 
-def _appended(case, kind, prec, got_k, got_v, what):
-    """got_k / got_v [N, Hkv, >= c, hd]: the rows a kernel appended for the image's first c new tokens"""
+def _appended(case, kind, prec, got_k, got_v, what, half=False):
+    """got_k / got_v [N, Hkv, >= c, hd]: the rows a kernel appended for the image's first c new tokens; half: to a half cache"""
     st = case.step(kind, prec)
     for n, c in enumerate(case.new[kind]):
-        ok, worst = AR.appended_check(st, got_k[n, :, :c], got_v[n, :, :c], n, c)
-        print(f"ATTN_ROWS {what} | {kind} | image {n}: {c} appended rows, rotated k within {worst:.2f} u of its magnitude")
+        ok, worst = AR.appended_check(st, got_k[n, :, :c], got_v[n, :, :c], n, c, half)
+        print(f"ATTN_ROWS {what} | {kind} | image {n}: {c} appended rows, rotated k within {worst:.2f} {'u_h' if half else 'u'} of its magnitude")
         assert ok, (what, kind, n, worst)
 
 
 def _label(bound, lq, tile, f16, hd, splits):
+    if tile == WIDE_TILE:
+        return wide_label(f16, splits, ",inplace" if bound else "")
     if bound:
         return RG.decode_label(tile, f16, hd, splits) if lq == 1 else RG.extend_label(tile, f16, hd, splits)
     return KG.decode_label(tile, f16, hd, splits) if lq == 1 else EG.extend_label(tile, f16, hd, splits)
@@ -87,6 +108,7 @@ def _client_held(tmp_path, case, prec, tile, splits=1):
     path = models.write_repo(str(tmp_path), "m", case.mb)
     env = _env(prec, tile, splits)
     _plan(path, env, tile, splits, past, lq)
+    H = case.h
     outs = {"out": (N, lq, H * hd), "present.0.key": (N, kvh, past + lq, hd), "present.0.value": (N, kvh, past + lq, hd)}
     what = f"{'decode' if lq == 1 else 'extend'} tile {tile} hd {hd} H {H}/{kvh} P {past} Lq {lq} S {splits} {prec}"
     with RG.session(env, {"m": path}) as (ms, _):
@@ -101,14 +123,16 @@ def _client_held(tmp_path, case, prec, tile, splits=1):
     assert _label(False, lq, tile, prec == "fp16", hd, splits) in kern, kern
 
 
-def _resident(tmp_path, case, prec, tile, splits=1):
-    """the model bound to a B.KvCache of case.past rows, NaN beyond every image's length: both data kinds on one model and one cache"""
-    past, lq, hd, kvh = case.past, case.lq, case.hd, case.kvh
+def _resident(tmp_path, case, prec, tile, splits=1, half=False):
+    """the model bound to a B.KvCache of case.past rows, NaN beyond every image's length: both data kinds on one model and one cache.  half: a half
+    cache, which the case's own cache must fit exactly (attn_row_cases.cache_case(..., half=True))"""
+    past, lq, hd, kvh, H = case.past, case.lq, case.hd, case.kvh, case.h
+    assert half == case.half and (not half or prec == "fp16")
     path = models.write_repo(str(tmp_path), "m", case.mb)
     env = _env(prec, tile, splits)
     _plan(path, env, tile, splits, past, lq)
-    what = f"resident {'decode' if lq == 1 else 'extend'} tile {tile} hd {hd} H {H}/{kvh} cache {past} Lq {lq} S {splits} {prec}"
-    with RG.session(env, {"m": path}, (1, N, kvh, past, hd)) as (ms, kc):
+    what = f"resident {'half ' if half else ''}{'decode' if lq == 1 else 'extend'} tile {tile} hd {hd} H {H}/{kvh} cache {past} Lq {lq} S {splits} {prec}"
+    with RG.session(env, {"m": path}, (1, N, kvh, past, hd) + ((0, "f16") if half else ())) as (ms, kc):
         for kind in RC.KINDS:
             lens, new = case.lens[kind], case.new[kind]
             written = RG.fill(kc, case.feeds[kind], lens)
@@ -122,10 +146,11 @@ def _resident(tmp_path, case, prec, tile, splits=1):
             assert kc.lengths() == [ln + c for ln, c in zip(lens, new)], (what, kind, kc.lengths())
             rows = max(new)
             app = [np.stack([np.pad(g[n, :, ln:ln + c], ((0, 0), (0, rows - c), (0, 0))) for n, (ln, c) in enumerate(zip(lens, new))]) for g in got]
-            _appended(case, kind, prec, app[0], app[1], what)
-            _hold(y, case, kind, prec, tile, splits, f"{what} len {lens} c {new}")
+            _appended(case, kind, prec, app[0], app[1], what, half)
+            _hold(y, case, kind, prec, tile, splits, f"{what} len {lens} c {new}", True, half)
         kern = [p["kernel"] for p in B.Profile(ms["m"], 1)]
     label = _label(True, lq, tile, prec == "fp16", hd, splits)
+    label = _kv16(label) if half else label
     assert label in kern and "inplace" in label, (label, kern)
 
 
@@ -221,3 +246,88 @@ def test_resident_decode_appends_nothing_for_one_image(tmp_path, ln, tile, prec)
 def test_resident_decode_three_splits_over_an_empty_image(tmp_path, prec):
     """tile 4 in place at S = 3, lens (0, 199) in a cache of 200: image 0 has no key tile (per = 0), its last split owns the new row"""
     _resident(tmp_path, RC.cache_case(2, 64, 200, 1, (0, 199), (0, 199)), prec, 4, 3)
+
+
+# ---- tile 6: the head dim 128 extend tile, four waves as 4 / KW row waves by KW key waves -------------------------------------------------------------
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("past, lq", RC.EXTEND_WIDE)
+def test_wide_extend(tmp_path, past, lq, prec):
+    """g = 2: (33, 5) 10 rows, four key waves; (127, 5) and (129, 5) round the 128-key chunk; (40, 17) 34 rows, two key waves; (40, 65) 130 rows, one
+    key wave and a second row block of 2 rows"""
+    _client_held(tmp_path, RC.wide_case(past, lq), prec, WIDE_TILE)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("splits", (1, 3))
+def test_wide_extend_long_cache(tmp_path, splits, prec):
+    _client_held(tmp_path, RC.wide_case(300, 8), prec, WIDE_TILE, splits)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_wide_extend_a_split_beyond_the_causal_limit(tmp_path, prec):
+    """P = 40, Lq = 64 at three splits over four key tiles: nobody has a key in the third"""
+    _client_held(tmp_path, RC.wide_case(40, 64), prec, WIDE_TILE, 3)
+
+
+WIDE_CACHES = (("fp32", False), ("fp16", False), ("fp16", True))      # (precision, half cache)
+
+
+@pytest.mark.parametrize("prec, half", WIDE_CACHES)
+@pytest.mark.parametrize("past, lq, lens, new, splits", RC.WIDE_BOUND)
+def test_resident_wide_extend(tmp_path, past, lq, lens, new, splits, prec, half):
+    """tile 6 bound to an fp32 cache and (fp16) to a half one: a cache of 300 rows at Lq = 8 and S = 3, where (3, 292) leaves image 0's later splits
+    empty and (127, 128), (129, 290) round the 128-key chunk; 130 query rows in two row blocks over a cache of 110; c = (0, 5) over 7 rows and over none"""
+    _resident(tmp_path, RC.wide_case(past, lq, lens, new, half), prec, WIDE_TILE, splits, half)
+
+
+# ---- a half resident cache (fp16 models only) -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tile", (0, KG.DECODE_TILE))
+@pytest.mark.parametrize("kvh, hd, past", RC.DECODE_HALF)
+def test_half_cache_decode(tmp_path, kvh, hd, past, tile):
+    """hd 32, 64, 128 at (H, Hkv) = (4, 4) and (4, 1), the longer image at the half key tile (2048 / hd keys) - 1 and + 1"""
+    _resident(tmp_path, RC.decode_half_case(kvh, hd, past), "fp16", tile, half=True)
+
+
+@pytest.mark.parametrize("ln", (0, 1, 31, 32, 33))
+def test_half_cache_decode_lengths_around_the_key_tile(tmp_path, ln):
+    """hd 64, whose half key tile is 32 keys, in a cache of 72 rows: no cached key, one, the tile - 1, the tile, the tile + 1"""
+    _resident(tmp_path, RC.cache_case(2, 64, 72, 1, (ln, ln), (ln, ln), half=True), "fp16", 4, half=True)
+
+
+def test_half_cache_decode_three_splits_over_an_empty_image(tmp_path):
+    """lens (0, 199) in a cache of 200 at S = 3: image 0 has no key tile, its last split owns the new row and the others leave before the prologue"""
+    _resident(tmp_path, RC.cache_case(2, 64, 200, 1, (0, 199), (0, 199), half=True), "fp16", 4, 3, half=True)
+
+
+@pytest.mark.parametrize("ln", (7, 0))
+def test_half_cache_decode_appends_nothing_for_one_image(tmp_path, ln):
+    """image 0 is a padded token (c = 0) over 7 cached rows and over none: nothing is stored, its new key is not visible"""
+    _resident(tmp_path, RC.cache_case(2, 64, 40, 1, (ln, 30), (ln, 30), new=(0, 1), half=True), "fp16", 4, half=True)
+
+
+@pytest.mark.parametrize("hd", (128, 32))
+def test_half_cache_decode_a_group_of_eight(tmp_path, hd):
+    """H = 8 over one K / V head: the G = 8 form, two keys beyond the half key tile"""
+    _resident(tmp_path, RC.decode_half_case(1, hd, RC.half_key_tile(hd) + 2, heads=8), "fp16", 4, half=True)
+
+
+def test_half_cache_extend_three_splits(tmp_path):
+    """tile 5 over a half cache of 300 rows, Lq = 8, S = 3, the lengths round the 256-key chunk"""
+    _resident(tmp_path, RC.cache_case(2, 64, 300, 8, (255, 256), (255, 256), half=True), "fp16", 5, 3, half=True)
+
+
+def test_half_cache_extend_two_key_tiles_of_new_rows(tmp_path):
+    """tile 5 over a half cache of 70 rows, Lq = 33: the new rows, rounded by the append, fill more than one key tile"""
+    _resident(tmp_path, RC.cache_case(2, 64, 70, 33, (3, 37), (3, 37), half=True), "fp16", 5, half=True)
+
+
+def test_half_cache_generic_extend_appends_nothing_for_one_image(tmp_path):
+    """tile 0 over a half cache of 40 rows, Lq = 5, c = (0, 5)"""
+    _resident(tmp_path, RC.cache_case(2, 64, 40, 5, (7, 30), (7, 30), new=(0, 5), half=True), "fp16", 0, half=True)
+
+
+@pytest.mark.parametrize("tile, args, splits", RC.NO_ROPE_HALF)
+def test_half_cache_without_a_rotation(tmp_path, tile, args, splits):
+    """no rotation: q and the new k row pass as the halves they are, so "0h" and "4h" allow the output's rounding alone and "5h", "6h" that and the
+    probabilities below the row's largest; the appended k rows are the tokens bit for bit.  Both images hold long peaked lengths round the key tile"""
+    _resident(tmp_path, RC.no_rope_half_case(args), "fp16", tile, splits, half=True)
