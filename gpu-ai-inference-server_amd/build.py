@@ -22,12 +22,12 @@ LIB = os.path.join(PKG, "lib", "libinference_engine.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["env.cpp", "onnx_reader.cpp", "plan.cpp", "plan_match.cpp", "repository.cpp", "config.cpp", "executor.cpp", "launch.cpp", "tune.cpp", "bridge.cpp", "bridge_load.cpp", "bridge_run.cpp", "bridge_kv.cpp", "kernels.hip", "kernels_f16.hip", "kernels_ws.hip", "kernels_ws32.hip", "kernels_stem.hip", "kernels_direct.hip", "kernels_f8.hip", "kernels_fused.hip", "kernels_wino.hip", "kernels_x6.hip", "kernels_block.hip", "kernels_ws8.hip", "kernels_dw.hip", "kernels_se.hip", "kernels_grouped.hip", "kernels_resize.hip", "kernels_convt.hip", "kernels_ln.hip", "kernels_attn.hip", "kernels_decode.hip", "kernels_decode_h.hip", "kernels_extend_w.hip", "kernels_wattn.hip", "kernels_tokens.hip", "kernels_trans.hip", "kernels_embed.hip", "kernels_gn.hip", "kernels_qlinear.hip"]
+SOURCES = ["env.cpp", "onnx_reader.cpp", "plan.cpp", "plan_match.cpp", "repository.cpp", "config.cpp", "executor.cpp", "launch.cpp", "tune.cpp", "bridge.cpp", "bridge_load.cpp", "bridge_run.cpp", "bridge_kv.cpp", "kernels.hip", "kernels_f16.hip", "kernels_ws.hip", "kernels_ws32.hip", "kernels_stem.hip", "kernels_direct.hip", "kernels_f8.hip", "kernels_fused.hip", "kernels_wino.hip", "kernels_x6.hip", "kernels_block.hip", "kernels_ws8.hip", "kernels_dw.hip", "kernels_se.hip", "kernels_grouped.hip", "kernels_resize.hip", "kernels_convt.hip", "kernels_ln.hip", "kernels_attn.hip", "kernels_decode.hip", "kernels_decode_h.hip", "kernels_extend_w.hip", "kernels_wattn.hip", "kernels_tokens.hip", "kernels_trans.hip", "kernels_embed.hip", "kernels_gn.hip", "kernels_qlinear.hip", "kernels_moe.hip"]
 # per-file flags.  kernels_decode_h.hip: no packed fp32 VALU forms (v_pk_*_f32); its fp32 arithmetic is scalar fma by design
 # (the flag is a device feature: hipcc's host pass notes that it ignores it).  kernels_extend_w.hip: the same switch, so that the softmax rescale of
 # its 64 accumulator registers is the scalar multiplies written there and the recorded register counts are this build's
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA = {"kernels_decode_h.hip": NO_PK_F32, "kernels_extend_w.hip": NO_PK_F32, "kernels_qlinear.hip": NO_PK_F32}
+EXTRA = {"kernels_decode_h.hip": NO_PK_F32, "kernels_extend_w.hip": NO_PK_F32, "kernels_qlinear.hip": NO_PK_F32, "kernels_moe.hip": NO_PK_F32}
 COMMON = ["-std=c++17", "-O3", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-unused-result",
           "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 

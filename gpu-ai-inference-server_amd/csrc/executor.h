@@ -250,6 +250,7 @@ private:
     GroupedArgs MakeGroupedArgs(const PlanInstance& pi, const Step& s) const;
     ConvtArgs MakeConvtArgs(const PlanInstance& pi, const Step& s) const;
     SeArgs MakeSeArgs(const PlanInstance& pi, const Step& s) const;
+    __attribute__((visibility("hidden"))) MoeArgs MakeMoeArgs(const PlanInstance& pi, const Step& s) const;
     bool MakeBlockArgs(const PlanInstance& pi, const Step& s, DenseBlockArgs* out) const;   // false: the step is not a well-formed dense-block chain
 
     Env env_;                            // the lane's switches, read once in the constructor

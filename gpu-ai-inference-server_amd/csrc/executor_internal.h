@@ -72,6 +72,7 @@ bool DeviceModel::TiledFamily(const PlanInstance& pi, const Step& s, F&& f) cons
         case StepKind::LayerNorm: f(MakeLnArgs(pi, s, wb), LayerNormEligible, LaunchLayerNorm, TiledNames{"layer_norm", "layer-norm"}); return true;
         case StepKind::GroupNorm: f(MakeGnArgs(pi, s, wb), GroupNormEligible, LaunchGroupNorm, TiledNames{"group_norm", "group-norm"}); return true;
         case StepKind::QLinear: f(MakeQLinearArgs(pi, s, wb), QLinearEligible, LaunchQLinear, TiledNames{"qlinear", "4-bit Linear"}); return true;
+        case StepKind::Moe: f(MakeMoeArgs(pi, s), MoeEligible, LaunchMoe, TiledNames{"moe", "mixture-of-experts"}); return true;
         case StepKind::Embed: f(MakeEmbedArgs(pi, s, wb), EmbedEligible, LaunchEmbed, TiledNames{"embed", nullptr}); return true;
         case StepKind::Attention:
             // a decode step (a past): its own two tiles, 0 = the generic kernel over `present` and kAttnDecodeTile; the step that carries the parts runs them at tile 0

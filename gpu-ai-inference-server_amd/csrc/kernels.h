@@ -272,6 +272,50 @@ constexpr bool QLinearMfmaFits(bool in16, bool out16, bool res16, int64_t k, int
 // crossover over the eight Linear shapes of llama_3b_layers and llama_135m, and never below 128
 constexpr int64_t kQLinearGemmMinRows = 4096;
 
+// Mixture of experts (kernels_moe.hip; com.microsoft MoE): for every pixel row t of `in` [.., D], with p = softmax(router[t, :]) over the E experts, sel the
+// top_k largest p (on equal values the lower expert) and g_j = p[sel_j] (normalize: divided by their sum),
+//   out[t, :] = res[t, :] + sum_j g_j * ((act(x W1[sel_j] + b1[sel_j]) * (x W3[sel_j] + b3[sel_j])) W2[sel_j] + b2[sel_j])      (no w3: no product)
+// w1 / w3: [E][I][D], w2: [E][D][I] (the reduction index contiguous), fp32; w1h / w3h / w2h: the same as halfs at the same element offsets (fp16 precision)
+// or null; b1 / b3: fp32 [E][I], b2: fp32 [E][D], or null.  Every launch has a grid fixed by the shapes, nothing is read back, no atomics: every sum
+// runs in a fixed order.  The workspace holds what MoeLayout lists.
+struct MoeArgs {
+    TensorArg in, router, out, res;    // res.p == null: no residual
+    const float *w1 = nullptr, *w3 = nullptr, *w2 = nullptr;
+    const void *w1h = nullptr, *w3h = nullptr, *w2h = nullptr;
+    const float *b1 = nullptr, *b3 = nullptr, *b2 = nullptr;
+    int experts = 0, top_k = 1, inter = 0;
+    int act = 0;                       // ApplyAct code: 0 identity, 3 silu, 5 relu, 6 gelu
+    int normalize = 0;
+    float* workspace = nullptr;
+    int64_t workspace_floats = 0;
+};
+constexpr int kMoeMaxExperts = 64, kMoeMaxTopK = 8;
+// tile 0: moe_generic_kernel (any view, float or half activations, fp32 weights and FMAs); tile 1: moe_up_kernel + moe_down_kernel on
+// v_mfma_f32_16x16x32_f16 (half activations, result and weights, D % 32 == 0, I % 32 == 0, rows one pitch apart, 16-byte aligned operands).  Both run
+// behind moe_route_kernel and moe_group_kernel and in front of moe_combine_kernel
+constexpr int kNumMoeTiles = 2;
+bool MoeEligible(const MoeArgs& a, int tile);
+hipError_t LaunchMoe(const MoeArgs& a, int tile, hipStream_t stream);
+// what tile 1 asks of a step's shapes alone (the planner's default; the launcher re-checks pointers and alignment)
+constexpr bool MoeMfmaFits(bool all16, int64_t d, int64_t inter, int64_t in_pitch, int64_t in_off, int64_t out_pitch, int64_t out_off, int64_t res_pitch, int64_t res_off) {
+    return all16 && d % 32 == 0 && inter % 32 == 0 && in_pitch % 8 == 0 && in_off % 8 == 0 && out_pitch % 8 == 0 && out_off % 8 == 0 && res_pitch % 8 == 0 && res_off % 8 == 0;
+}
+// Tile 1: 16-row tiles of gathered slots per workgroup (a slot = token * top_k + j), from the slot count alone
+constexpr int MoeRowTiles(int64_t slots) { return slots <= 16 ? 1 : (slots <= 32 ? 2 : 4); }
+// The (expert, row block) pairs a step can have at `block` rows per pair: every expert with a slot has one partly filled block at most
+constexpr int64_t MoeMaxBlocks(int64_t slots, int64_t experts, int64_t block) { return (slots < experts ? slots : experts) + slots / block; }
+// The workspace of a step, in floats from its start; every part 16-byte aligned.  sel / gate: the expert and the routing weight of every slot; offs: the
+// exclusive scan of the experts' slot counts (E + 1 values); list: the slots sorted by expert, by slot index inside one; tab: four ints per (expert, row
+// block) pair -- the expert or -1, the first sorted row, the row count --, MoeMaxBlocks(slots, E, 16) of them; part: fp32 [slots][D], by slot; h: the
+// intermediate [slots][I] by sorted row, fp32 on tile 0 and half on tile 1 (sized for fp32: a declined tile 1 runs on tile 0)
+struct MoeLayout {
+    int64_t sel, gate, offs, list, tab, part, h, total;
+    constexpr MoeLayout(int64_t slots, int64_t experts, int64_t d, int64_t inter)
+        : sel(0), gate(up4(slots)), offs(gate + up4(slots)), list(offs + up4(experts + 1)), tab(list + up4(slots)),
+          part(tab + 4 * MoeMaxBlocks(slots, experts, 16)), h(part + up4(slots * d)), total(h + up4(slots * inter)) {}
+    static constexpr int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
+};
+
 // GroupNormalization of an NHWC view (kernels_gn.hip): for image n and group g = c / (C / groups), over the C / groups channels of the group and every pixel,
 //   out[n, p, c] = act((in[n, p, c] - mean_ng) * rsqrt(var_ng + eps) * gamma[c] + beta[c]),  var_ng the mean of the centred squares.
 // fp32 statistics in both element types; gamma / beta fp32; no atomics, every combine in a fixed order.  out may alias in.

@@ -59,6 +59,30 @@ QLinearArgs MakeQLinearArgs(const PlanInstance& pi, const Step& s, const float* 
     return a;
 }
 
+// (the half weights of tile 1 are the half mirror of the blob, at the same element offsets)
+MoeArgs DeviceModel::MakeMoeArgs(const PlanInstance& pi, const Step& s) const {
+    MoeArgs a;
+    a.in = make_arg(pi, s.in);
+    a.router = make_arg(pi, s.router);
+    a.out = make_arg(pi, s.out);
+    if (s.has_in2) a.res = make_arg(pi, s.in2);
+    const float* wb = w_->d_weights;
+    const char* hb = pi.plan.precision == Precision::F16 ? static_cast<const char*>(w_->d_weights16) : nullptr;
+    auto wp = [&](int64_t off) -> const float* { return off >= 0 ? wb + off : nullptr; };
+    auto hp = [&](int64_t off) -> const void* { return off >= 0 && hb ? hb + off * 2 : nullptr; };
+    a.w1 = wp(s.w_off); a.w3 = wp(s.w3_off); a.w2 = wp(s.w2_off);
+    a.w1h = hp(s.w_off); a.w3h = hp(s.w3_off); a.w2h = hp(s.w2_off);
+    a.b1 = wp(s.bias_off); a.b3 = wp(s.bias3_off); a.b2 = wp(s.bias2_off);
+    a.experts = s.moe_experts;
+    a.top_k = s.moe_k;
+    a.inter = s.moe_inter;
+    a.act = int(s.act.kind);
+    a.normalize = s.moe_norm ? 1 : 0;
+    a.workspace = pi.workspace;
+    a.workspace_floats = pi.workspace_floats;
+    return a;
+}
+
 GnArgs MakeGnArgs(const PlanInstance& pi, const Step& s, const float* weights) {
     GnArgs a;
     a.in = make_arg(pi, s.in);
@@ -684,8 +708,8 @@ void DeviceModel::LaunchStep(const PlanInstance& pi, const Step& s_in, hipStream
             check(LaunchTokenAssemble(a, stream_), "token_assemble");
             break;
         }
-        case StepKind::LayerNorm: case StepKind::GroupNorm: case StepKind::Embed: case StepKind::Attention: case StepKind::WindowAttention: case StepKind::QLinear:
-            break;      // (launched through TiledFamily above)
+        case StepKind::LayerNorm: case StepKind::GroupNorm: case StepKind::Embed: case StepKind::Attention: case StepKind::WindowAttention: case StepKind::QLinear: case StepKind::Moe:
+            break;     // (launched through TiledFamily above)
         case StepKind::KvAppend: {
             if (s.in.f8) throw std::runtime_error("internal error: fp8 tensor reached the kv_append kernel");
             const DecodeArgs a = MakeDecodeArgs(pi, s, wb);
@@ -777,6 +801,11 @@ std::string kernel_label(const Step& s) {
         case StepKind::QLinear: {
             const std::string form = "b" + std::to_string(s.q_block) + (s.q_zp_off >= 0 ? ",zp>" : ",sym>");
             return s.tile == 0 ? std::string("qlinear_generic_kernel<") + (s.in.f16 ? "f16," : "f32,") + form : (s.tile == 2 ? "qlinear_gemm_kernel<" : "qlinear_mfma_kernel<") + form;
+        }
+        case StepKind::Moe: {
+            static const char* const acts[] = {"identity", "", "", "silu", "", "relu", "gelu"};
+            const std::string form = std::string(acts[int(s.act.kind)]) + (s.w3_off >= 0 ? ",gated>" : ",plain>");
+            return s.tile == 0 ? std::string("moe_generic_kernel<") + (s.in.f16 ? "f16," : "f32,") + form : "moe_up_kernel<" + form;
         }
         case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }

@@ -606,12 +606,79 @@ void Planner::ImportMatMulNBits(const OnnxNode& on, LNode& n, std::vector<int64_
     if (cl) { odims = {X.n, N, X.h, X.w}; cl_out = !tok; tok_out = tok; }
 }
 
-// The residual Add behind a 4-bit Linear (o_proj, down_proj) folds into its epilogue under the rule of FuseConvEpilogues: the other operand exists when
-// the Linear runs.  Nothing else folds into such a node
+// com.microsoft MoE (the operator's documented schema, ORT 1.17 to 1.22): input [rows, D] or a token view [N, L, D], router_probs (the router's logits:
+// the op takes the softmax) of the same rows and E columns, fc1 / fc3 weights [E, D, I], fc2 weights [E, I, D], biases [E, I] / [E, D], all float
+// initializers.  The weights are transposed here so that the reduction index is contiguous (kernels_moe.hip); everything else is refused by name and rule
+void Planner::ImportMoe(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims) {
+    auto no = [&](const std::string& why) { fail("MoE " + n.name + ": " + why); };
+    auto given = [&](size_t k) { return on.inputs.size() > k && !on.inputs[k].empty(); };
+    auto shape = [](const OnnxTensor& t) { std::string s = "["; for (size_t i = 0; i < t.dims.size(); ++i) s += (i ? ", " : "") + std::to_string(t.dims[i]); return s + "]"; };
+    if (on.attr_i("use_sparse_mixer", 0) != 0) no("use_sparse_mixer is not supported");
+    for (const char* key : {"swiglu_fusion", "swiglu_limit", "activation_alpha", "activation_beta"})
+        if (on.attrs.count(key)) no(std::string("the swiglu-fusion attribute ") + key + " is not supported (an interleaved fc1 is not read)");
+    const auto at = on.attrs.find("activation_type");
+    const std::string act = at == on.attrs.end() ? "relu" : at->second.s;
+    if (act == "silu") n.act.kind = ActKind::Silu;
+    else if (act == "gelu") n.act.kind = ActKind::Gelu;
+    else if (act == "relu") n.act.kind = ActKind::Relu;
+    else if (act != "identity") no("activation_type \"" + act + "\" is not supported (silu, gelu, relu or identity)");
+    if (!given(2) || !given(4) || !act_input(on, 0) || !act_input(on, 1)) no("needs the activations input and router_probs and the initializers fc1_experts_weights and fc2_experts_weights");
+    static const char* const names[8] = {"input", "router_probs", "fc1_experts_weights", "fc1_experts_bias", "fc2_experts_weights", "fc2_experts_bias", "fc3_experts_weights", "fc3_experts_bias"};
+    const OnnxTensor* t[8] = {};
+    for (size_t k = 2; k < 8 && k < on.inputs.size(); ++k) {
+        if (!given(k)) continue;
+        t[k] = L.init(on.inputs[k]);
+        if (!t[k]) no(std::string(names[k]) + " must be an initializer (" + on.inputs[k] + " is computed by the graph)");
+        if (t[k]->f.empty()) no(std::string(names[k]) + " must be a float initializer");
+        if (t[k]->dims.size() != (k % 2 ? 2u : 3u)) no(std::string(names[k]) + " has the shape " + shape(*t[k]) + "; the weights are [E, D, I] / [E, I, D] and the biases [E, I] / [E, D]");
+    }
+    if (on.inputs.size() > 8) no("has more than eight inputs");
+    const int x = in_val(on, 0), r = in_val(on, 1);
+    const Val &X = L.vals[x], &R = L.vals[r];
+    const bool tok = L.is_tok(on.inputs[0]);
+    if ((!tok && X.h * X.w != 1) || L.is_tok(on.inputs[1]) != tok) no("input and router_probs must both be [rows, .] or both token views [N, L, .]");
+    const int64_t E = t[2]->dims[0], D = t[2]->dims[1], I = t[2]->dims[2];
+    if (D != X.c) no("fc1_experts_weights " + shape(*t[2]) + " is not [E, D, I] with D = the input's " + std::to_string(X.c) + " columns");
+    if (t[4]->dims[0] != E || t[4]->dims[1] != I || t[4]->dims[2] != D)
+        no("fc2_experts_weights " + shape(*t[4]) + " is not [E, I, D] = [" + std::to_string(E) + ", " + std::to_string(I) + ", " + std::to_string(D) + "] (an interleaved fc1 is not read)");
+    if (t[6] && t[6]->dims != t[2]->dims) no("fc3_experts_weights " + shape(*t[6]) + " is not fc1's " + shape(*t[2]));
+    if (t[7] && !t[6]) no("fc3_experts_bias without fc3_experts_weights");
+    for (size_t k : {size_t(3), size_t(5), size_t(7)})
+        if (t[k] && (t[k]->dims[0] != E || t[k]->dims[1] != (k == 5 ? D : I))) no(std::string(names[k]) + " " + shape(*t[k]) + " is not [E, " + (k == 5 ? "D]" : "I]"));
+    const int64_t k = on.attr_i("k", 1);
+    if (E > kMoeMaxExperts) no("E = " + std::to_string(E) + " experts are not supported (at most " + std::to_string(kMoeMaxExperts) + ")");
+    if (k < 1 || k > E) no("k = " + std::to_string(k) + " is not between 1 and the E = " + std::to_string(E) + " experts");
+    if (k > kMoeMaxTopK) no("k = " + std::to_string(k) + " is not supported (at most " + std::to_string(kMoeMaxTopK) + ")");
+    if (R.c != E || R.n != X.n || R.h != X.h || R.w != X.w) no("router_probs must hold E = " + std::to_string(E) + " logits for every row of the input");
+    auto transposed = [&](const OnnxTensor& w, int64_t rows, int64_t cols) {       // [E][rows][cols] -> [E][cols][rows]
+        std::vector<float> o(w.f.size());
+        for (int64_t e = 0; e < E; ++e)
+            for (int64_t i = 0; i < rows; ++i)
+                for (int64_t j = 0; j < cols; ++j) o[size_t((e * cols + j) * rows + i)] = w.f[size_t((e * rows + i) * cols + j)];
+        return o;
+    };
+    n.kind = L_MOE;
+    n.w = transposed(*t[2], D, I);
+    n.w2 = transposed(*t[4], I, D);
+    if (t[6]) n.w3 = transposed(*t[6], D, I);
+    if (t[3]) n.bias = t[3]->f;
+    if (t[5]) n.bias2 = t[5]->f;
+    if (t[7]) n.bias3 = t[7]->f;
+    n.moe_experts = int(E);
+    n.moe_k = int(k);
+    n.moe_inter = int(I);
+    n.moe_norm = on.attr_i("normalize_routing_weights", 0) != 0;
+    n.in = {x, r};
+    odims = {X.n, D};
+    if (tok) { odims = {X.n, D, X.h, X.w}; tok_out = true; }
+}
+
+// The residual Add behind a 4-bit Linear (o_proj, down_proj) or a mixture of experts folds into its epilogue under the rule of FuseConvEpilogues: the
+// other operand exists when the node runs.  Nothing else folds into such a node
 void Planner::FuseQLinearResiduals() {
     for (size_t i = 0; i < L.nodes.size(); ++i) {
         LNode& q = L.nodes[i];
-        if (q.dead || q.kind != L_QLINEAR || q.res >= 0 || !single_consumer(q.out)) continue;
+        if (q.dead || (q.kind != L_QLINEAR && q.kind != L_MOE) || q.res >= 0 || !single_consumer(q.out)) continue;
         LNode& b = L.nodes[size_t(L.consumers(q.out)[0])];
         if (b.kind != L_ADD) continue;
         const int other = b.in[0] == q.out ? b.in[1] : b.in[0];
@@ -1124,7 +1191,7 @@ void Planner::ImportNode(const OnnxNode& on) {
             fail(op + " " + n.name + ": input " + name + " is a channels-last view (a Transpose with perm [0,2,3,1]); only LayerNormalization, MatMul, Add, Mul, Div, Erf, "
                  "Gelu and Transpose may read one");
     // token views likewise, and the two half-way names of their creation and of the way back
-    static const std::set<std::string> tok_ops = {"LayerNormalization", "RMSNormalization", "MatMul", "MatMulNBits", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose", "Concat", "Gather", "Reshape"};
+    static const std::set<std::string> tok_ops = {"LayerNormalization", "RMSNormalization", "MatMul", "MatMulNBits", "MoE", "Add", "Mul", "Div", "Erf", "Gelu", "Transpose", "Concat", "Gather", "Reshape"};
     for (const std::string& name : on.inputs) {
         // (a Conv1D's Gemm reads its token view like a MatMul; the Split of a GPT-2 attention is its head; a Pow is no operator of the planner at all, whatever it reads;
         // a Sigmoid on tokens is the SiLU of a Llama MLP's gate)
@@ -1148,6 +1215,7 @@ void Planner::ImportNode(const OnnxNode& on) {
     else if (op == "ConvTranspose") ImportConvTranspose(on, n, odims);
     else if (op == "MatMul" || op == "Gemm") ImportGemm(on, n, odims);
     else if (op == "MatMulNBits") ImportMatMulNBits(on, n, odims);
+    else if (op == "MoE") ImportMoe(on, n, odims);
     else if (op == "BatchNormalization") ImportBatchNorm(on, n, odims);
     else if (op == "LayerNormalization" || op == "RMSNormalization") ImportLayerNorm(on, n, odims);
     else if (op == "Clip" || op == "Sigmoid" || op == "HardSigmoid" || op == "HardSwish" || op == "Relu" || op == "Erf" || op == "Gelu" || op == "Tanh") ImportActivation(on, n, odims);
@@ -1681,6 +1749,7 @@ void Planner::RefuseForF8() const {
         if (n.kind == L_LAYERNORM || n.kind == L_EMBED) fail("LayerNormalization is not supported in fp8 mode (node " + n.name + ")");
         if (n.kind == L_GROUPNORM) fail("GroupNormalization is not supported in fp8 mode (node " + n.name + ")");
         if (n.kind == L_QLINEAR) fail("MatMulNBits is not supported in fp8 mode (node " + n.name + ")");
+        if (n.kind == L_MOE) fail("MoE is not supported in fp8 mode (node " + n.name + ")");
     }
     for (const LNode& n : L.nodes)
         if (n.kind == L_ATTENTION || n.kind == L_TOKASM || n.kind == L_TOKPOS) fail("attention and token views are not supported in fp8 mode (node " + n.name + ")");
@@ -2381,6 +2450,39 @@ void Planner::EmitQLinear(const LNode& n, Step& s) {
     s.bytes = vbytes(s.in) + vbytes(s.out) + (s.has_in2 ? vbytes(s.in2) : 0.0) + double(n.q_codes.size()) + 4.0 * double(n.s.size()) + double(n.q_zps.size()) + 4.0 * double(n.bias.size());
 }
 
+// A mixture of experts: the transposed weights and the biases fp32 into the blob (fp16 precision reads the executor's half mirror of it); tile 1 (the
+// MFMA kernels) where the step's views allow it, else the generic kernel.  IE_FORCE_TILE as for layer norm; IE_MOE_TILE pins these steps alone (an
+// ineligible 1 is the generic kernel).  FLOPs count the top_k experts of a row, bytes the min(E, rows * top_k) experts a step can touch
+void Planner::EmitMoe(const LNode& n, Step& s) {
+    if (s.in.f8 || s.out.f8) fail("MoE is not supported in fp8 mode (node " + n.name + ")");
+    s.kind = StepKind::Moe;
+    s.router = view_of(n.in[1]);
+    if (n.res >= 0) { s.in2 = view_of(n.res); s.has_in2 = true; }
+    s.act = n.act;
+    s.moe_experts = n.moe_experts;
+    s.moe_k = n.moe_k;
+    s.moe_inter = n.moe_inter;
+    s.moe_norm = n.moe_norm;
+    s.w_off = push_vec(n.w);
+    if (!n.w3.empty()) s.w3_off = push_vec(n.w3);
+    s.w2_off = push_vec(n.w2);
+    if (!n.bias.empty()) s.bias_off = push_vec(n.bias);
+    if (!n.bias3.empty()) s.bias3_off = push_vec(n.bias3);
+    if (!n.bias2.empty()) s.bias2_off = push_vec(n.bias2);
+    const bool all16 = s.in.f16 && s.router.f16 && s.out.f16 && (!s.has_in2 || s.in2.f16) && precision == Precision::F16;
+    const bool fits = !s.in.nchw && !s.router.nchw && !s.out.nchw && !(s.has_in2 && s.in2.nchw) &&
+                      MoeMfmaFits(all16, s.in.c, s.moe_inter, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off, s.has_in2 ? s.in2.pitch : 0, s.has_in2 ? s.in2.c_off : 0);
+    s.tile = fits ? 1 : 0;
+    int t = ForcedTile(kNumMoeTiles);
+    if (const char* e = env.get("IE_MOE_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumMoeTiles) t = std::atoi(e);
+    if (t >= 0) s.tile = t == 0 || fits ? t : 0;
+    const double rows = double(s.in.n) * double(s.in.h) * double(s.in.w), slots = rows * double(s.moe_k);
+    plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, MoeLayout(int64_t(slots), s.moe_experts, s.in.c, s.moe_inter).total);
+    const double per_expert = double(n.w.size() + n.w3.size() + n.w2.size() + n.bias.size() + n.bias3.size() + n.bias2.size()) / double(s.moe_experts);
+    s.flops = 2.0 * slots * double(s.in.c) * double(s.moe_inter) * (n.w3.empty() ? 2.0 : 3.0);
+    s.bytes = vbytes(s.in) + vbytes(s.router) + vbytes(s.out) + (s.has_in2 ? vbytes(s.in2) : 0.0) + std::min(double(s.moe_experts), slots) * per_expert * (s.tile == 1 ? 2.0 : 4.0);
+}
+
 int Planner::src_of(const View& v) const {
     auto it = writer.find({int64_t(v.buf), v.c_off, v.c});
     return it == writer.end() ? -1 : it->second;
@@ -3003,6 +3105,7 @@ void Planner::EmitSteps() {
             case L_EMBED: EmitEmbed(n, s); break;
             case L_GROUPNORM: EmitGroupNorm(n, s); break;
             case L_QLINEAR: EmitQLinear(n, s); break;
+            case L_MOE: EmitMoe(n, s); break;
             case L_COPY:
                 if (s.in.f8 || s.out.f8) fail("fp8 precision: layout copy " + n.name + " of an fp8 tensor is not supported");
                 s.kind = StepKind::Copy;
@@ -3369,7 +3472,7 @@ Plan BuildPlan(const OnnxModel& m, const std::vector<std::vector<int64_t>>& inpu
     if (!env.get("IE_NO_SE_FUSE")) P.FuseSqueezeExcite();        // pool -> 1x1 -> act -> 1x1 -> act -> Mul as one node
     P.MergeAffineChains();                                       // fusion 1: Affine -> Affine
     P.FuseConvEpilogues();                                       // fusion 2: Conv -> Affine / ReLU / Add / Clip / activation
-    P.FuseQLinearResiduals();                                    // the residual Add behind a 4-bit Linear
+    P.FuseQLinearResiduals();                                    // the residual Add behind a 4-bit Linear or a mixture of experts
     P.FuseRelu6IntoDepthwise();                                  // fusion 2b
     P.FuseActivationPrologues();                                 // fusion 2d
     if (!env.get("IE_NO_POOL_SWAP")) P.SwapConvAndAvgPool();     // fusion 2c: Conv1x1 -> AveragePool => AveragePool -> Conv1x1
@@ -3415,7 +3518,7 @@ static std::string json_escape(const std::string& s) {
 }
 
 std::string PlanToJson(const Plan& p) {
-    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed", "group_norm", "kv_append", "qlinear"};
+    static const char* kinds[] = {"conv", "pool", "gap", "eltwise", "copy", "squeeze_excite", "resize", "layer_norm", "token_assemble", "attention", "window_attention", "patch_merge", "embed", "group_norm", "kv_append", "qlinear", "moe"};
     static const char* rs_modes[] = {"nearest", "linear"};
     static const char* rs_coords[] = {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"};
     static const char* rs_nearest[] = {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"};
@@ -3461,7 +3564,7 @@ std::string PlanToJson(const Plan& p) {
             o << "]";
         }
         // (only where set: the plans of graphs without these activations are unchanged)
-        if (s.act.kind != ActKind::None || s.kind == StepKind::GroupNorm) json_act(o, "act", s.act);
+        if ((s.act.kind != ActKind::None && s.kind != StepKind::Moe) || s.kind == StepKind::GroupNorm) json_act(o, "act", s.act);      // (a moe step names its own below)
         if (s.pre_act.kind != ActKind::None) json_act(o, "pre_act", s.pre_act);
         if (s.mul) o << ",\"mul\":true";
         if (s.kind == StepKind::SqueezeExcite) {
@@ -3506,6 +3609,12 @@ std::string PlanToJson(const Plan& p) {
             o << ",\"residual\":" << (s.has_in2 ? "true" : "false") << ",\"block_size\":" << s.q_block << ",\"scales_off\":" << s.w2_off << ",\"zero_points_off\":" << s.q_zp_off
               << ",\"packed_bytes\":" << int64_t(s.out.c) * s.in.c / 2 + 4 * int64_t(s.out.c) * (s.in.c / s.q_block) + (s.q_zp_off >= 0 ? int64_t(s.out.c) * ((s.in.c / s.q_block + 1) / 2) : 0)
               << ",\"tile\":" << s.tile;
+        if (s.kind == StepKind::Moe) {      // (mixture-of-experts steps only)
+            static const char* const acts[] = {"identity", "", "", "silu", "", "relu", "gelu"};
+            o << ",\"router\":"; json_view(o, s.router);
+            o << ",\"experts\":" << s.moe_experts << ",\"top_k\":" << s.moe_k << ",\"inter\":" << s.moe_inter << ",\"act\":\"" << acts[int(s.act.kind)] << "\",\"gated\":"
+              << (s.w3_off >= 0 ? "true" : "false") << ",\"normalize\":" << (s.moe_norm ? "true" : "false") << ",\"residual\":" << (s.has_in2 ? "true" : "false") << ",\"tile\":" << s.tile;
+        }
         if (s.kind == StepKind::Embed) {      // (embed steps only)
             o << ",\"tables\":" << (s.w2_off >= 0 ? 2 : 1) << ",\"vocab\":[" << s.emb_vocab;
             if (s.w2_off >= 0) o << "," << s.emb_types;

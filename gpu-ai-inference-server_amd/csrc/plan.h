@@ -39,7 +39,7 @@ struct View {
 // the global pool) are halfs, graph inputs / outputs stay fp32.
 enum class Precision : int { F32 = 0, F16 = 1, F8 = 2 };
 
-enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12, GroupNorm = 13, KvAppend = 14, QLinear = 15 };
+enum class StepKind : int { Conv = 0, Pool = 1, GlobalAvgPool = 2, Eltwise = 3, Copy = 4, SqueezeExcite = 5, Resize = 6, LayerNorm = 7, TokenAssemble = 8, Attention = 9, WindowAttention = 10, PatchMerge = 11, Embed = 12, GroupNorm = 13, KvAppend = 14, QLinear = 15, Moe = 16 };
 
 // Resize / Upsample (kernels_resize.hip): the interpolation mode, the ONNX coordinate_transformation_mode and nearest_mode
 enum class ResizeMode : int { Nearest = 0, Linear = 1 };
@@ -193,6 +193,15 @@ struct Step {
     // or -1.  No weight mirror and no dense-conv pass touches them.  tile 0 = the generic kernel, 1 = the MFMA kernel (fp16 precision)
     int q_block = 0;
     int64_t q_zp_off = -1;
+    // Moe (kernels_moe.hip): a mixture-of-experts MLP (com.microsoft MoE) on the pixel rows of `in` [.., D]; router = the router's logits [.., moe_experts];
+    // in2 (has_in2) = the folded residual Add.  Per row the moe_k experts of largest softmax probability run, weighted by it (moe_norm: by its share of
+    // their sum).  fp32 in the blob, the reduction index contiguous: w_off = W1 [E][moe_inter][D], w3_off = W3 likewise or -1 (no gate product), w2_off =
+    // W2 [E][D][moe_inter]; bias_off / bias3_off = [E][moe_inter], bias2_off = [E][D], or -1.  act = the expert's activation.  The routing records,
+    // the intermediate and the per-slot results live in the workspace (kernels.h MoeLayout).  tile 0 = the generic kernel, 1 = the MFMA kernels (fp16)
+    View router;
+    int moe_experts = 0, moe_k = 0, moe_inter = 0;
+    bool moe_norm = false;
+    int64_t w3_off = -1, bias3_off = -1;
     ConvAlgo algo = ConvAlgo::Naive;
     int group = 1;             // ConvAlgo::Grouped: the ONNX group count
     int tile = 0;              // igemm tile configuration index (see igemm_tiles.h)

@@ -38,7 +38,7 @@ struct Val {
     int64_t sel_rows = 1, sel_idx = 0;
 };
 
-enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED, L_GROUPNORM, L_KVAPPEND, L_QLINEAR };
+enum LKind { L_CONV, L_AFFINE, L_RELU, L_ADD, L_CONCAT, L_MAXPOOL, L_AVGPOOL, L_GAP, L_ALIAS, L_COPY, L_CLIP, L_ACT, L_MUL, L_SE, L_RESIZE, L_LAYERNORM, L_ERF, L_TOKASM, L_TOKPOS, L_ATTENTION, L_WATTN, L_PATCHMERGE, L_EMBED, L_GROUPNORM, L_KVAPPEND, L_QLINEAR, L_MOE };
 
 constexpr float kInf = __builtin_huge_valf();
 
@@ -87,6 +87,11 @@ struct LNode {
     // bias [N] (empty: none), res = the folded residual Add
     std::vector<uint8_t> q_codes, q_zps;
     int q_block = 0;
+    // L_MOE (com.microsoft MoE): in = the tokens, the router's logits (and res, the folded residual Add); w / w3 = W1 / W3 [E][inter][D] (w3 empty: no
+    // gate product), w2 = W2 [E][D][inter], bias / bias3 [E][inter] and bias2 [E][D] (empty: none), act = the expert's activation
+    std::vector<float> w3, bias3;
+    int moe_experts = 0, moe_k = 0, moe_inter = 0;
+    bool moe_norm = false;
     bool has_pre = false, pre_relu = false, relu = false;
     std::vector<float> pre_s, pre_t;
     int res = -1;                       // conv: value added to the result before the ReLU (fused residual Add)
@@ -471,6 +476,8 @@ struct Planner {
     void ImportMatMulNBits(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void FuseQLinearResiduals();
     void EmitQLinear(const LNode& n, Step& s);
+    void ImportMoe(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
+    void EmitMoe(const LNode& n, Step& s);
     int64_t push_bytes(const std::vector<uint8_t>& v);   // raw bytes into the weight blob (32-byte aligned), the float offset
     void ImportBatchNorm(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);
     void ImportArithmetic(const OnnxNode& on, LNode& n, std::vector<int64_t>& odims);

@@ -329,6 +329,32 @@ class GraphBuilder:
         b = (rng.uniform(self.seed, name + "_b", cout) - np.float32(0.5)) * np.float32(0.2)
         return self.simple("Add", [y, self.init(name + "_b", b.astype(np.float32))])
 
+    def moe(self, x: str, router: str, d: int, inter: int, experts: int, k: int, *, act: str = "silu", gated: bool = True, normalize: bool = True,
+            bias: bool = False, name: str | None = None, weights: dict | None = None) -> str:
+        """com.microsoft MoE on x [.., d] with the router's logits router [.., experts] (the op takes the softmax): per row the k experts of largest
+        probability, y = sum_j g_j ((act(x W1[e_j] + b1) * (x W3[e_j] + b3)) W2[e_j] + b2), g = the probabilities (normalize: over their sum); gated
+        False: no fc3 and no product.  Inputs input, router_probs, fc1_experts_weights [E, d, inter], fc1_experts_bias [E, inter], fc2_experts_weights
+        [E, inter, d], fc2_experts_bias [E, d], fc3_experts_weights, fc3_experts_bias (an absent one is the empty name); attributes k, activation_type,
+        normalize_routing_weights.  Written from the operator's documented schema (ONNX Runtime 1.17 to 1.22 ContribOperators), NOT from a real export.
+        weights (tests): {"fc1" | "fc2" | "fc3" | "b1" | "b2" | "b3": array} replaces the drawn ones."""
+        name = name or self._uid("moe")
+
+        def draw(key: str, shape: tuple, std: float) -> str:
+            a = weights[key] if weights and key in weights else rng.gaussish(self.seed, f"{name}_{key}", int(np.prod(shape))).reshape(shape) * np.float32(std)
+            return self.init(f"{name}_{key}", np.ascontiguousarray(a, np.float32).reshape(shape))
+        s1, s2 = float(np.sqrt(1.0 / d)), float(np.sqrt(1.0 / inter))
+        ins = [x, router, draw("fc1", (experts, d, inter), s1), draw("b1", (experts, inter), 0.1) if bias else "",
+               draw("fc2", (experts, inter, d), s2), draw("b2", (experts, d), 0.1) if bias else ""]
+        if gated:
+            ins += [draw("fc3", (experts, d, inter), s1)] + ([draw("b3", (experts, inter), 0.1)] if bias else [])
+        while not ins[-1]:
+            ins.pop()
+        self.nodes.append(pb.node("MoE", ins, [name + "_out"], name, [pb.attr_int("k", k), pb.attr_str("activation_type", act),
+                                                                      pb.attr_int("normalize_routing_weights", int(normalize))], domain="com.microsoft"))
+        if ("com.microsoft", 1) not in self.extra_opsets:
+            self.extra_opsets.append(("com.microsoft", 1))
+        return name + "_out"
+
     def act(self, x: str, kind: str, form: str = "op") -> str:
         """kind: relu | hardswish | silu | sigmoid | hardsigmoid | relu6 | none"""
         if kind == "relu":
@@ -568,6 +594,24 @@ def qlinear(rows: int | str = 8, k: int = 128, n: int = 80, *, q_block: int = 32
         ins.append(("r", [rows, n]))
     gb.simple("Mul", [y, one], out="y")
     return gb.finish(ins, [("y", [rows, n])], opset=18)
+
+
+def moe(rows: int | str, d: int, inter: int, experts: int, k: int, *, act: str = "silu", gated: bool = True, normalize: bool = True, bias: bool = False,
+        residual: bool = False, weights: dict | None = None, seed: int = 12) -> bytes:
+    """One mixture-of-experts node alone (GraphBuilder.moe), x [rows, d] and the logits router [rows, experts] -> y [rows, d] (+ r, a third input
+    [rows, d], where residual).  The logits are a graph input, so a test hands in its own.  x, router, r and y pass a Mul by 1, as in qlinear():
+    in fp16 precision the node reads and writes half buffers."""
+    gb = GraphBuilder("moe", seed)
+    one = gb.init("one", np.array(1.0, np.float32))
+    r = gb.simple("Mul", ["r", one]) if residual else None      # (in front of the node: its Add folds only onto a value that exists when it runs)
+    y = gb.moe(gb.simple("Mul", ["x", one]), gb.simple("Mul", ["router", one]), d, inter, experts, k, act=act, gated=gated, normalize=normalize, bias=bias,
+               name="moe", weights=weights)
+    ins = [("x", [rows, d]), ("router", [rows, experts])]
+    if residual:
+        y = gb.simple("Add", [r, y])
+        ins.append(("r", [rows, d]))
+    gb.simple("Mul", [y, one], out="y")
+    return gb.finish(ins, [("y", [rows, d])], opset=18)
 
 
 def resnet_block(batch: int | str = 2, c: int = 32, image: int = 16, seed: int = 50) -> bytes:
@@ -1557,7 +1601,8 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
           max_pos: int = 2048, rope_theta: float = 10000.0, eps: float = 1e-5, tied: bool = True, last_hidden_state: bool = False, seed: int = 2023,
           norm: str = "pow", cast: bool = False, swap: bool = False, rope: str = "slice", repeat: str = "auto", scale: str = "mul", mask: str = "add",
           w_scale: float | None = None, table_std: float = 1.0, present: bool = False, past: int | None = None, positions: str = "input",
-          quant: str | None = None, q_block: int = 32, q_zero: bool = True, q_form: str = "nbits") -> bytes:
+          quant: str | None = None, q_block: int = 32, q_zero: bool = True, q_form: str = "nbits",
+          experts: int | None = None, top_k: int = 2, router_std: float | None = None) -> bytes:
     """LlamaForCausalLM as a prefill / scoring forward (Touvron et al. 2023; the shape of Llama 2 / 3, TinyLlama, SmolLM, Mistral and the dense Qwen
     models), ids [N, seq] -> logits [N, seq, vocab], written from modeling_llama.py's eager attention and the TorchScript exporter's known lowerings,
     NOT from a real export (neither `transformers` nor ONNX Runtime is available here); checked by the float64 walk of tests/ref64.py.
@@ -1590,7 +1635,11 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
                      columns 0: the output rows of such tokens are finite and otherwise unspecified (the graph gives a uniform average there, and
                      nobody reads it)
     quant="int4" (q_block, q_zero, q_form: GraphBuilder.linear's) quantises every decoder Linear; the head and the embedding stay float.  q_form "dense"
-    is the float32 twin of the same codes.  quant=None: the bytes of every graph above are unchanged"""
+    is the float32 twin of the same codes.  quant=None: the bytes of every graph above are unchanged
+    experts=E (top_k, router_std) makes every layer's MLP Mixtral's sparse block: a bias-less router Linear dim -> E (weights of standard deviation
+    router_std; None: Linear's default), the com.microsoft MoE node (GraphBuilder.moe: silu, fc3, normalize_routing_weights 1, E experts of width mlp,
+    top_k of them per token) and the residual Add.  Like the rest it is written from the operator's documented schema, not from a real export.
+    experts=None: the bytes of every graph above are unchanged"""
     gb = GraphBuilder("llama", seed)
     hd = dim // heads
     emb = np.float32(table_std) * rng.gaussish(seed, "embed_tokens", vocab * dim).reshape(vocab, dim).astype(np.float32)
@@ -1635,6 +1684,10 @@ def llama(batch: int = 1, *, seq: int = 128, vocab: int = 32000, dim: int = 576,
                             swap=swap, linear=lambda t, name, cout: lin(t, name, dim, cout), **kv)
         x = gb.simple("Add", [x, lin(y, tag + "_o_proj", dim, dim)])
         h = gb.rmsnorm(x, dim, eps=eps, form=norm, name=tag + "_post_attention_layernorm", cast=cast, swap=swap)
+        if experts is not None:
+            logits = gb.linear(h, dim, experts, name=tag + "_router", bias=False, w_scale=router_std)
+            x = gb.simple("Add", [x, gb.moe(h, logits, dim, mlp, experts, top_k, name=tag + "_moe")])
+            continue
         y = gb.swiglu(lin(h, tag + "_gate_proj", dim, mlp), lin(h, tag + "_up_proj", dim, mlp), swap=swap)
         x = gb.simple("Add", [x, lin(y, tag + "_down_proj", mlp, dim)])
     gb.rmsnorm(x, dim, eps=eps, form=norm, name="norm", cast=cast, swap=swap, out="last_hidden_state")
