@@ -35,7 +35,8 @@ const char* const kNames[] = {
                                // (ExtendDefaultSplits) or tile 6 (ExtendWideDefaultSplits), at most one 32-key tile per split and 64
     "IE_QLINEAR_TILE",         // 0 | 1 | 2: the tile of the 4-bit Linear steps alone (an ineligible 1 or 2 is the generic kernel; a pinned 2 holds at
                                // any row count, unpinned it takes the steps of kernels.h kQLinearGemmMinRows rows and more)
-    "IE_MOE_TILE",             // 0 | 1: the tile of the mixture-of-experts steps alone (an ineligible 1 is the generic kernel)
+    "IE_MOE_TILE",             // 0 | 1 | 2: the tile of the mixture-of-experts steps alone (an ineligible 1 or 2 is the generic kernel; a pinned 2 holds at
+                               // any row count, unpinned it takes the steps of kernels.h kMoeGemmMinSlotsPerExpert mean rows per expert and more)
     // ---- executor ----------------------------------------------------------------------------------------------------------------
     "IE_AUTOTUNE", "IE_TUNE_CACHE", "IE_TUNE_BATCHES", "IE_TUNE_ON_DEMAND", "IE_TUNE_HOT", "IE_TUNE_LOG",
     "IE_DISABLE_GRAPH", "IE_SPLITK_IN_LAUNCH", "IE_PIPELINE_CHUNKS", "IE_PIPELINE_HEAD", "IE_MAX_PLANS", "IE_NO_FRAG_WEIGHTS",

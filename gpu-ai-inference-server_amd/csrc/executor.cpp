@@ -95,6 +95,7 @@ DeviceModel::DeviceModel(std::shared_ptr<const OnnxModel> model, int device_id, 
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsWattn();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsTrans();
         if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsQLinear();
+        if (g_kernels_err == hipSuccess) g_kernels_err = InitKernelsMoe();
     });
     check(g_kernels_err, "InitKernels");
     fp32_split_ = opt.fp32_split && opt.precision == Precision::F32;

@@ -292,10 +292,15 @@ struct MoeArgs {
 constexpr int kMoeMaxExperts = 64, kMoeMaxTopK = 8;
 // tile 0: moe_generic_kernel (any view, float or half activations, fp32 weights and FMAs); tile 1: moe_up_kernel + moe_down_kernel on
 // v_mfma_f32_16x16x32_f16 (half activations, result and weights, D % 32 == 0, I % 32 == 0, rows one pitch apart, 16-byte aligned operands).  Both run
-// behind moe_route_kernel and moe_group_kernel and in front of moe_combine_kernel
-constexpr int kNumMoeTiles = 2;
+// tile 2: moe_gemm_up_kernel + moe_gemm_down_kernel (what tile 1 takes; a grouped GEMM over 128-row table entries with both operands staged in LDS: the
+// prefill row counts).  All run behind moe_route_kernel and moe_group_kernel and in front of moe_combine_kernel
+constexpr int kNumMoeTiles = 3;
 bool MoeEligible(const MoeArgs& a, int tile);
 hipError_t LaunchMoe(const MoeArgs& a, int tile, hipStream_t stream);
+hipError_t InitKernelsMoe();             // once per process, before any capture: lets tile 2 take more than 64 KiB of LDS
+// the mean rows per expert (rows * top_k / E) from which the planner takes tile 2 for a step that fits (the same test: tile 2 takes what tile 1 takes).
+// Measured, and never below 64
+constexpr int64_t kMoeGemmMinSlotsPerExpert = 64;
 // what tile 1 asks of a step's shapes alone (the planner's default; the launcher re-checks pointers and alignment)
 constexpr bool MoeMfmaFits(bool all16, int64_t d, int64_t inter, int64_t in_pitch, int64_t in_off, int64_t out_pitch, int64_t out_off, int64_t res_pitch, int64_t res_off) {
     return all16 && d % 32 == 0 && inter % 32 == 0 && in_pitch % 8 == 0 && in_off % 8 == 0 && out_pitch % 8 == 0 && out_off % 8 == 0 && res_pitch % 8 == 0 && res_off % 8 == 0;

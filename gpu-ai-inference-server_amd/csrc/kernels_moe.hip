@@ -27,6 +27,21 @@
 //     K load nothing and enter as zeros (K % 32 == 0: a lane's 32 k are all inside or all outside).
 //   * the four waves' accumulators meet in LDS and are added in wave order; the up epilogue forms act(u1 + b1) * (u3 + b3) in fp32 and rounds once.
 // Every sum has one fixed order, and the order of the rows inside an expert's list is the slot order: two runs are bit-equal.
+//
+//   moe_gemm_up_kernel<ACT, GATED> / moe_gemm_down_kernel   tile 2 (prefill row counts): a grouped GEMM over the table entries, which the
+//                        group kernel then cuts at 128 rows.  A workgroup of 4 waves owns one entry and one column tile; wave (wm, wn) a 64 x 64 quarter in
+//                        2 x 2 accumulators of v_mfma_f32_32x32x16_f16, after qlinear_gemm_kernel's skeleton.
+// Tile 2, per K-step of 64:
+//   * both operands are staged alike: thread t reads four 16-byte vectors, k0 + 8 (t % 8) .. of image rows t / 8 + 32 i, of the weights (rows of W[e],
+//     K contiguous) and of the gathered activations (the row of slot list[r0 + row] in the up kernel, h[r0 + row] in the down kernel; the row pointers are
+//     resolved once).  Rows past the entry's count, 32-column groups past N and k past K read nothing and enter as zeros.
+//   * gated up product: the 128 weight rows are 64 columns of h; wave wn's 64 rows are 32 columns of W1[e], then the same 32 columns of W3[e], so its two
+//     column accumulators are u1 and u3 of the same h columns in the same lanes and act(u1 + b1) * (u3 + b3) needs no exchange.  The activation rows are
+//     staged once for both products.
+//   * both LDS images have rows of 64 + 8 halfs (36 words); two stages: the loads of step s + 1 are issued before the MFMAs of step s and written into the
+//     other stage after them; ONE barrier closes the step.  LDS: 2 x 256 x 72 x 2 = 73 728 bytes, two workgroups per CU.
+// D = W x A^T (the weights are the MFMA's first operand): a lane owns one row and quads of consecutive columns; v_permlane32_swap leaves it with eight
+// consecutive columns for 16-byte stores.  No K split and no atomics: every output is one fixed-order sum.  The grid runs the entries fastest.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -356,6 +371,205 @@ __global__ __launch_bounds__(kMoeBlock) void moe_combine_kernel(const MoeArgs a,
     }
 }
 
+// ---- tile 2 ------------------------------------------------------------------------------------------------------------------------------------------
+constexpr int kMgTile = 128;                       // sorted rows of a table entry, and weight rows of a workgroup's LDS image
+constexpr int kMgStep = 64;                        // k per step
+constexpr int kMgPitch = kMgStep + 8;              // halfs per LDS row: 36 words
+constexpr int kMgStage = 2 * kMgTile * kMgPitch;   // halfs per stage: the weight image [128][72], then the activation image [128][72]
+constexpr int kMgLdsBytes = 2 * kMgStage * 2;      // 73 728
+
+// what a thread holds of the next K-step while this one's MFMAs run: the 8 k from 8 (tid % 8) on of the image rows tid / 8 + 32 i of either side
+struct MgFetch {
+    h8 w[4], x[4];
+};
+
+// The K loop of tile 2: acc[jn][jm] += W rows (wn * 64 + jn * 32 ..) x A rows (wm * 64 + jm * 32 ..) over K, both sides staged through the two LDS stages.
+// wrow[i] / xrow[i] = where image row tid / 8 + 32 i starts in global memory (at k = 8 (tid % 8)), wlive[i] / xlive[i] = it exists (else zeros, nothing is
+// read); skip (wave-uniform) = the wave's 64 A rows are all past the entry's count: it stages and meets the barriers, and leaves its accumulators zero
+__device__ __forceinline__ void moe_gemm_loop(const _Float16* const* wrow, const bool* wlive, const _Float16* const* xrow, const bool* xlive, int K, bool skip,
+                                              _Float16* smem, f32x16 (*acc)[2]) {
+    const int tid = int(threadIdx.x), lane = tid % 64, wave = tid / 64;
+    const int r = lane % 32, hh = lane / 32, wm = wave / 2, wn = wave % 2;
+    const int sr = tid / 8, sk = 8 * (tid % 8);
+    auto fetch = [&](int k0) {
+        MgFetch f;
+        const bool in_k = k0 + sk < K;             // (K % 32 == 0: the 8 k are all inside or all outside)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f.w[i] = f.x[i] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+            if (wlive[i] && in_k) f.w[i] = *reinterpret_cast<const h8*>(wrow[i] + k0);
+            if (xlive[i] && in_k) f.x[i] = *reinterpret_cast<const h8*>(xrow[i] + k0);
+        }
+        return f;
+    };
+    auto stage = [&](const MgFetch& f, _Float16* st) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            *reinterpret_cast<h8*>(st + (sr + 32 * i) * kMgPitch + sk) = f.w[i];
+            *reinterpret_cast<h8*>(st + (kMgTile + sr + 32 * i) * kMgPitch + sk) = f.x[i];
+        }
+    };
+    const int nsteps = (K + kMgStep - 1) / kMgStep;
+    stage(fetch(0), smem);
+    __syncthreads();
+    const int woff = (wn * 64 + r) * kMgPitch + 8 * hh, xoff = (kMgTile + wm * 64 + r) * kMgPitch + 8 * hh;
+    for (int s = 0; s < nsteps; ++s) {
+        const bool more = s + 1 < nsteps;          // workgroup-uniform
+        MgFetch nxt;
+        if (more) nxt = fetch((s + 1) * kMgStep);
+        const _Float16* st = smem + (s & 1) * kMgStage;
+        if (!skip) {
+#pragma unroll
+            for (int ks = 0; ks < kMgStep / 16; ++ks) {
+                h8 wf[2], xf[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    wf[j] = *reinterpret_cast<const h8*>(st + woff + j * 32 * kMgPitch + 16 * ks);
+                    xf[j] = *reinterpret_cast<const h8*>(st + xoff + j * 32 * kMgPitch + 16 * ks);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i / 2][i % 2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i / 2], xf[i % 2], acc[i / 2][i % 2], 0, 0, 0);
+            }
+        }
+        if (more) stage(nxt, smem + ((s + 1) & 1) * kMgStage);     // the stage step s - 1 read: every wave is past the barrier that closed it
+        __syncthreads();
+    }
+}
+
+// accumulator element 4 g + q of lane (r, hh) is weight row 8 g + 4 hh + q, A row r of the 32 x 32 tile.  Swapping the quads of groups 2 gp and 2 gp + 1
+// between the half-waves leaves lane (r, hh) with the eight weight rows 8 (2 gp + hh) .. of A row r (every lane takes part: no branch around the swaps)
+__device__ __forceinline__ void moe_gemm_eight(const f32x16& acc, int gp, float* v) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float lo = acc[8 * gp + q], hi = acc[8 * gp + 4 + q];
+        const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi), false, false);
+        const unsigned s0 = sw[0], s1 = sw[1];
+        v[q] = __builtin_bit_cast(float, s0);
+        v[4 + q] = __builtin_bit_cast(float, s1);
+    }
+}
+
+__device__ __forceinline__ void moe_gemm_zero(f32x16 (*acc)[2]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i / 2][i % 2][e] = 0.f;
+}
+
+// Tile 2, the up product: blockIdx.x = the table entry (fastest: the workgroups resident together share an expert's column strip), blockIdx.y = the column
+// tile.  GATED: 64 columns of h; wave wn's 64 weight rows are the 32 columns n0 + 32 wn .. of W1[e], then the same 32 columns of W3[e], so its two column
+// accumulators are u1 and u3 of the same h columns in the same lanes.  Plain: 128 columns of W1[e]
+template <int ACT, bool GATED>
+__global__ __launch_bounds__(kMoeBlock) void moe_gemm_up_kernel(const MoeArgs a, const MoeWs ws) {
+    extern __shared__ __attribute__((aligned(16))) _Float16 smem_mg[];
+    const int4 tb = ws.tab[blockIdx.x];
+    const int e = tb.x, r0 = tb.y, nr = tb.z;
+    if (e < 0) return;                             // no such (expert, row block) in this run: nothing is loaded
+    const int tid = int(threadIdx.x), lane = tid % 64, wave = tid / 64;
+    const int r = lane % 32, hh = lane / 32, wm = wave / 2, wn = wave % 2;
+    const int D = a.in.c, I = a.inter;
+    const int n0 = int(blockIdx.y) * (GATED ? 64 : kMgTile);
+    const int sr = tid / 8, sk = 8 * (tid % 8);
+    const _Float16* x = reinterpret_cast<const _Float16*>(a.in.p);
+    const _Float16* wrow[4];
+    const _Float16* xrow[4];
+    bool wlive[4], xlive[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        // image row sr + 32 i: gated = (wave column i / 2, W1 or W3 by i % 2); a 32-column group past I reads nothing (I % 32 == 0)
+        const int col = n0 + (GATED ? 32 * (i / 2) : 32 * i) + sr;
+        wlive[i] = col < I;
+        const void* w = GATED && (i % 2) ? a.w3h : a.w1h;
+        wrow[i] = reinterpret_cast<const _Float16*>(w) + (int64_t(e) * I + (wlive[i] ? col : 0)) * D + sk;
+        xlive[i] = sr + 32 * i < nr;
+        const int slot = xlive[i] ? ws.list[r0 + sr + 32 * i] : 0;
+        xrow[i] = x + int64_t(slot / a.top_k) * a.in.sw + sk;
+    }
+    f32x16 acc[2][2];                              // [32 weight rows jn][32 A rows jm] of the wave's quarter
+    moe_gemm_zero(acc);
+    moe_gemm_loop(wrow, wlive, xrow, xlive, D, wm * 64 >= nr, smem_mg, acc);
+    _Float16* h = reinterpret_cast<_Float16*>(ws.h);
+#pragma unroll
+    for (int jm = 0; jm < 2; ++jm) {
+        const int row = wm * 64 + jm * 32 + r;
+#pragma unroll
+        for (int jn = 0; jn < (GATED ? 1 : 2); ++jn) {
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+                float v[8], u[8];
+                moe_gemm_eight(acc[jn][jm], gp, v);
+                if constexpr (GATED) moe_gemm_eight(acc[1][jm], gp, u);
+                const int n = n0 + (GATED ? wn * 32 : wn * 64 + jn * 32) + 8 * (2 * gp + hh);
+                if (row >= nr || n >= I) continue;                 // (I % 32 == 0: the eight columns are all inside or all outside)
+                const int64_t bo = int64_t(e) * I + n;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = ApplyAct(ACT, 0.f, 0.f, v[i] + (a.b1 ? a.b1[bo + i] : 0.f));
+                if constexpr (GATED) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] *= u[i] + (a.b3 ? a.b3[bo + i] : 0.f);
+                }
+                store16<_Float16>(h + int64_t(r0 + row) * I + n, v);
+            }
+        }
+    }
+}
+
+// Tile 2, the down product: A = h, contiguous in sorted order, B = 128 columns of W2[e]; (sum + b2) * gate[slot] as fp32 into part[slot]
+__global__ __launch_bounds__(kMoeBlock) void moe_gemm_down_kernel(const MoeArgs a, const MoeWs ws) {
+    extern __shared__ __attribute__((aligned(16))) _Float16 smem_mg[];
+    const int4 tb = ws.tab[blockIdx.x];
+    const int e = tb.x, r0 = tb.y, nr = tb.z;
+    if (e < 0) return;
+    const int tid = int(threadIdx.x), lane = tid % 64, wave = tid / 64;
+    const int r = lane % 32, hh = lane / 32, wm = wave / 2, wn = wave % 2;
+    const int D = a.in.c, I = a.inter;
+    const int n0 = int(blockIdx.y) * kMgTile;
+    const int sr = tid / 8, sk = 8 * (tid % 8);
+    const _Float16* h = reinterpret_cast<const _Float16*>(ws.h);
+    const _Float16* wrow[4];
+    const _Float16* xrow[4];
+    bool wlive[4], xlive[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int col = n0 + 32 * i + sr;          // (D % 32 == 0: a 32-column group is all inside or all outside)
+        wlive[i] = col < D;
+        wrow[i] = reinterpret_cast<const _Float16*>(a.w2h) + (int64_t(e) * D + (wlive[i] ? col : 0)) * I + sk;
+        xlive[i] = sr + 32 * i < nr;
+        xrow[i] = h + int64_t(r0 + (xlive[i] ? sr + 32 * i : 0)) * I + sk;
+    }
+    f32x16 acc[2][2];
+    moe_gemm_zero(acc);
+    moe_gemm_loop(wrow, wlive, xrow, xlive, I, wm * 64 >= nr, smem_mg, acc);
+#pragma unroll
+    for (int jm = 0; jm < 2; ++jm) {
+        const int row = wm * 64 + jm * 32 + r;
+        const int slot = row < nr ? ws.list[r0 + row] : 0;
+        const float gate = row < nr ? ws.gate[slot] : 0.f;
+#pragma unroll
+        for (int jn = 0; jn < 2; ++jn) {
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+                float v[8];
+                moe_gemm_eight(acc[jn][jm], gp, v);
+                const int n = n0 + wn * 64 + jn * 32 + 8 * (2 * gp + hh);
+                if (row >= nr || n >= D) continue;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = (v[i] + (a.b2 ? a.b2[int64_t(e) * D + n + i] : 0.f)) * gate;
+                float* o = ws.part + int64_t(slot) * D + n;
+                store16<float>(o, v);
+                store16<float>(o + 4, v + 4);
+            }
+        }
+    }
+}
+
+template <int ACT>
+void launch_gemm_up(const MoeArgs& a, const MoeWs& ws, unsigned blocks, hipStream_t stream) {
+    // the table entries run fastest: the workgroups resident together share an expert's column strip
+    if (a.w3h) moe_gemm_up_kernel<ACT, true><<<dim3(blocks, unsigned((a.inter + 63) / 64)), dim3(kMoeBlock), kMgLdsBytes, stream>>>(a, ws);
+    else moe_gemm_up_kernel<ACT, false><<<dim3(blocks, unsigned((a.inter + kMgTile - 1) / kMgTile)), dim3(kMoeBlock), kMgLdsBytes, stream>>>(a, ws);
+}
+
 template <int ACT, bool GATED>
 void launch_up(const MoeArgs& a, const MoeWs& ws, int mt, dim3 grid, hipStream_t stream) {
     if (mt == 1) moe_up_kernel<ACT, GATED, 1><<<grid, dim3(kMoeBlock), 0, stream>>>(a, ws);
@@ -373,6 +587,20 @@ bool same_rows(const TensorArg& x, const TensorArg& y) { return x.n == y.n && x.
 
 }  // namespace
 
+hipError_t InitKernelsMoe() {
+    const void* const kernels[] = {
+        reinterpret_cast<const void*>(&moe_gemm_up_kernel<0, true>), reinterpret_cast<const void*>(&moe_gemm_up_kernel<0, false>),
+        reinterpret_cast<const void*>(&moe_gemm_up_kernel<3, true>), reinterpret_cast<const void*>(&moe_gemm_up_kernel<3, false>),
+        reinterpret_cast<const void*>(&moe_gemm_up_kernel<5, true>), reinterpret_cast<const void*>(&moe_gemm_up_kernel<5, false>),
+        reinterpret_cast<const void*>(&moe_gemm_up_kernel<6, true>), reinterpret_cast<const void*>(&moe_gemm_up_kernel<6, false>),
+        reinterpret_cast<const void*>(&moe_gemm_down_kernel)};
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMgLdsBytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 bool MoeEligible(const MoeArgs& a, int tile) {
     if (tile < 0 || tile >= kNumMoeTiles || !a.in.p || !a.router.p || !a.out.p || !a.w1 || !a.w2 || !a.workspace) return false;
     if (a.in.f8 || a.router.f8 || a.out.f8 || a.res.f8 || a.in.c < 1 || a.inter < 1 || a.out.c != a.in.c) return false;
@@ -388,7 +616,9 @@ bool MoeEligible(const MoeArgs& a, int tile) {
     if (!VecViewOk(a.in, 8) || !RowsDense(a.in) || !VecViewOk(a.out, 8) || !RowsDense(a.out)) return false;
     if (a.res.p && (!a.res.f16 || !VecViewOk(a.res, 8) || !RowsDense(a.res))) return false;
     if (!Aligned16(a.w1h) || !Aligned16(a.w2h) || !Aligned16(a.w3h) || !Aligned16(a.workspace)) return false;
-    return MoeMaxBlocks(slots, a.experts, 16 * MoeRowTiles(slots)) <= 65535;
+    if (tile == 1) return MoeMaxBlocks(slots, a.experts, 16 * MoeRowTiles(slots)) <= 65535;
+    // tile 2: the table entries within 65 535 (they would fit the grid's x axis far beyond; the bound keeps either axis order open), the column tiles on y
+    return MoeMaxBlocks(slots, a.experts, kMgTile) <= 65535 && (int64_t(a.inter) + 63) / 64 <= 65535 && (int64_t(a.in.c) + kMgTile - 1) / kMgTile <= 65535;
 }
 
 hipError_t LaunchMoe(const MoeArgs& a, int tile, hipStream_t stream) {
@@ -401,14 +631,26 @@ hipError_t LaunchMoe(const MoeArgs& a, int tile, hipStream_t stream) {
     const MoeWs ws{reinterpret_cast<int*>(w + lay.sel), w + lay.gate, reinterpret_cast<int*>(w + lay.offs), reinterpret_cast<int*>(w + lay.list),
                    reinterpret_cast<int4*>(w + lay.tab), w + lay.part, w + lay.h};
     const int mt = MoeRowTiles(slots);
-    const int blocks = int(MoeMaxBlocks(slots, a.experts, 16 * mt));
+    const int block_rows = tile == 2 ? kMgTile : 16 * mt;
+    const int blocks = int(MoeMaxBlocks(slots, a.experts, block_rows));
     const dim3 block(kMoeBlock);
     moe_route_kernel<<<dim3(unsigned((rows + kMoeWaves - 1) / kMoeWaves)), block, 0, stream>>>(a, ws, int(rows));
-    moe_group_kernel<<<dim3(1), block, 0, stream>>>(ws, int(slots), a.experts, 16 * mt, blocks);
+    moe_group_kernel<<<dim3(1), block, 0, stream>>>(ws, int(slots), a.experts, block_rows, blocks);
     if (tile == 0) {
         moe_generic_kernel<false><<<dim3(unsigned(slots), unsigned((I + kMoeWaves - 1) / kMoeWaves)), block, 0, stream>>>(a, ws);
         moe_generic_kernel<true><<<dim3(unsigned(slots), unsigned((D + kMoeWaves - 1) / kMoeWaves)), block, 0, stream>>>(a, ws);
         moe_combine_kernel<false><<<dim3(unsigned((rows * D + kMoeBlock - 1) / kMoeBlock)), block, 0, stream>>>(a, ws, rows);
+        return hipGetLastError();
+    }
+    if (tile == 2) {
+        switch (a.act) {
+            case 3: launch_gemm_up<3>(a, ws, unsigned(blocks), stream); break;
+            case 5: launch_gemm_up<5>(a, ws, unsigned(blocks), stream); break;
+            case 6: launch_gemm_up<6>(a, ws, unsigned(blocks), stream); break;
+            default: launch_gemm_up<0>(a, ws, unsigned(blocks), stream); break;
+        }
+        moe_gemm_down_kernel<<<dim3(unsigned(blocks), unsigned((D + kMgTile - 1) / kMgTile)), block, kMgLdsBytes, stream>>>(a, ws);
+        moe_combine_kernel<true><<<dim3(unsigned((rows * (D / 8) + kMoeBlock - 1) / kMoeBlock)), block, 0, stream>>>(a, ws, rows);
         return hipGetLastError();
     }
     const dim3 up(unsigned(I / 16), unsigned(blocks)), down(unsigned(D / 16), unsigned(blocks));

@@ -805,7 +805,7 @@ std::string kernel_label(const Step& s) {
         case StepKind::Moe: {
             static const char* const acts[] = {"identity", "", "", "silu", "", "relu", "gelu"};
             const std::string form = std::string(acts[int(s.act.kind)]) + (s.w3_off >= 0 ? ",gated>" : ",plain>");
-            return s.tile == 0 ? std::string("moe_generic_kernel<") + (s.in.f16 ? "f16," : "f32,") + form : "moe_up_kernel<" + form;
+            return s.tile == 0 ? std::string("moe_generic_kernel<") + (s.in.f16 ? "f16," : "f32,") + form : (s.tile == 2 ? "moe_gemm_kernel<" : "moe_up_kernel<") + form;
         }
         case StepKind::SqueezeExcite: return std::string("se_squeeze_kernel + se_fc1_kernel + se_fc2_kernel + se_apply_kernel<") + (s.out.f16 ? "f16>" : "f32>");
     }

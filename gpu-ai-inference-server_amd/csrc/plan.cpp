@@ -2451,8 +2451,8 @@ void Planner::EmitQLinear(const LNode& n, Step& s) {
 }
 
 // A mixture of experts: the transposed weights and the biases fp32 into the blob (fp16 precision reads the executor's half mirror of it); tile 1 (the
-// MFMA kernels) where the step's views allow it, else the generic kernel.  IE_FORCE_TILE as for layer norm; IE_MOE_TILE pins these steps alone (an
-// ineligible 1 is the generic kernel).  FLOPs count the top_k experts of a row, bytes the min(E, rows * top_k) experts a step can touch
+// MFMA kernels) where the step's views allow it, from kMoeGemmMinSlotsPerExpert mean rows per expert on tile 2 (the LDS-staged grouped GEMM), else the
+// generic kernel.  IE_FORCE_TILE as for layer norm; IE_MOE_TILE pins these steps alone, at any row count (an ineligible 1 or 2 is the generic kernel).  FLOPs count the top_k experts of a row, bytes the min(E, rows * top_k) experts a step can touch
 void Planner::EmitMoe(const LNode& n, Step& s) {
     if (s.in.f8 || s.out.f8) fail("MoE is not supported in fp8 mode (node " + n.name + ")");
     s.kind = StepKind::Moe;
@@ -2472,15 +2472,16 @@ void Planner::EmitMoe(const LNode& n, Step& s) {
     const bool all16 = s.in.f16 && s.router.f16 && s.out.f16 && (!s.has_in2 || s.in2.f16) && precision == Precision::F16;
     const bool fits = !s.in.nchw && !s.router.nchw && !s.out.nchw && !(s.has_in2 && s.in2.nchw) &&
                       MoeMfmaFits(all16, s.in.c, s.moe_inter, s.in.pitch, s.in.c_off, s.out.pitch, s.out.c_off, s.has_in2 ? s.in2.pitch : 0, s.has_in2 ? s.in2.c_off : 0);
-    s.tile = fits ? 1 : 0;
+    const double rows = double(s.in.n) * double(s.in.h) * double(s.in.w), slots = rows * double(s.moe_k);
+    // (the planner cannot know the routing: the mean rows per expert stand for every expert's)
+    s.tile = !fits ? 0 : slots >= double(kMoeGemmMinSlotsPerExpert) * double(s.moe_experts) ? 2 : 1;
     int t = ForcedTile(kNumMoeTiles);
     if (const char* e = env.get("IE_MOE_TILE"); e && t < 0 && std::atoi(e) >= 0 && std::atoi(e) < kNumMoeTiles) t = std::atoi(e);
     if (t >= 0) s.tile = t == 0 || fits ? t : 0;
-    const double rows = double(s.in.n) * double(s.in.h) * double(s.in.w), slots = rows * double(s.moe_k);
     plan.workspace_floats = std::max<int64_t>(plan.workspace_floats, MoeLayout(int64_t(slots), s.moe_experts, s.in.c, s.moe_inter).total);
     const double per_expert = double(n.w.size() + n.w3.size() + n.w2.size() + n.bias.size() + n.bias3.size() + n.bias2.size()) / double(s.moe_experts);
     s.flops = 2.0 * slots * double(s.in.c) * double(s.moe_inter) * (n.w3.empty() ? 2.0 : 3.0);
-    s.bytes = vbytes(s.in) + vbytes(s.router) + vbytes(s.out) + (s.has_in2 ? vbytes(s.in2) : 0.0) + std::min(double(s.moe_experts), slots) * per_expert * (s.tile == 1 ? 2.0 : 4.0);
+    s.bytes = vbytes(s.in) + vbytes(s.router) + vbytes(s.out) + (s.has_in2 ? vbytes(s.in2) : 0.0) + std::min(double(s.moe_experts), slots) * per_expert * (s.tile >= 1 ? 2.0 : 4.0);
 }
 
 int Planner::src_of(const View& v) const {

@@ -197,7 +197,8 @@ struct Step {
     // in2 (has_in2) = the folded residual Add.  Per row the moe_k experts of largest softmax probability run, weighted by it (moe_norm: by its share of
     // their sum).  fp32 in the blob, the reduction index contiguous: w_off = W1 [E][moe_inter][D], w3_off = W3 likewise or -1 (no gate product), w2_off =
     // W2 [E][D][moe_inter]; bias_off / bias3_off = [E][moe_inter], bias2_off = [E][D], or -1.  act = the expert's activation.  The routing records,
-    // the intermediate and the per-slot results live in the workspace (kernels.h MoeLayout).  tile 0 = the generic kernel, 1 = the MFMA kernels (fp16)
+    // the intermediate and the per-slot results live in the workspace (kernels.h MoeLayout).  tile 0 = the generic kernel, 1 = the MFMA kernels (fp16),
+    // 2 = the LDS-staged grouped GEMM (fp16, prefill row counts)
     View router;
     int moe_experts = 0, moe_k = 0, moe_inter = 0;
     bool moe_norm = false;
